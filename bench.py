@@ -7,12 +7,15 @@ one batch of F synthetic frames per GPU (frame i is the spot mesh rotated by 10*
 variation), inputs (post-MVP triangle streams, lights, texture) already resident in HBM, output = the reference's
 framebuffer layout (z + 3 planar float colour planes per frame) in HBM.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python bench.py --gpus N ...          (N > 1 without a launcher: bench.py starts the N ranks itself — launch_ranks below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-N = 1 also measures, after the headline config and outside its timed region, the other GPU configs of BASELINE.json
-(configs[2..4], whole frames on one GPU) and configs[1] at scope "draw" (vertex stage timed too): `configs` in the JSON.
+A plain run measures the headline only: set-up, priming + W warm-up steps, K timed steps (`value`, `ms_per_step`), the line.
+--dump-outputs DIR writes a seeded sample of the last timed step's framebuffer (dump_outputs).  --full measures the rest too:
+the unprimed region, the counting pass, the one-stream per-kernel split and, at N = 1 after the headline config and outside
+its timed region, the other GPU configs of BASELINE.json (configs[2..4], whole frames on one GPU), configs[1] at scope "draw"
+(vertex stage timed too), the README loop, the emulated N-GPU shards and the CPU baseline: `configs` in the JSON.
 
 N > 1: one process per GPU; every frame's 32-row bands are dealt round-robin to the ranks (srz_set_shard), each rank
 renders its bands of F*N frames (per-GPU pixel work fixed → weak scaling), and the exchange north_star names — ONE in-place
@@ -269,7 +272,7 @@ def pct(xs, q):
 class Case:
     """One workload resident on this rank's GPU: frameset, counters, output buffers."""
 
-    def __init__(self, ctx, torch, workload, frames_per_gpu, scope, world, n_out=1):
+    def __init__(self, ctx, torch, workload, frames_per_gpu, scope, world, n_out=1, stats=True):
         import srz
         from srz import scenes
         self.torch, self.ctx, self.name, self.scope, self.world = torch, ctx, workload, scope, world
@@ -285,8 +288,10 @@ class Case:
             frames = [suniq[i % len(suniq)] for i in range(n_frames)]
         self.frames, self._lanes = frames, {}
         self.fs = ctx.frameset(frames)
-        self.stats = self.fs.stats()  # counting variant of the kernels, run once, outside every timed region
-        self.algo_bytes = self.fs.algorithmic_bytes()
+        # counting variant of the kernels, run once, outside every timed region (stats=False: not run, self.stats is None); the
+        # algorithmic bytes need its count of textured pixels, so they are None without it too
+        self.stats = self.fs.stats() if stats else None
+        self.algo_bytes = self.fs.algorithmic_bytes() if stats else None
         self.n_frames, self.frames_per_gpu = n_frames, frames_per_gpu
         self.out = [torch.empty(self.fs.out_shape, dtype=torch.float32, device="cuda") for _ in range(n_out)]
 
@@ -311,15 +316,49 @@ class Case:
         self.torch.cuda.empty_cache()
 
 
-def time_single_gpu(case, steps, warmup, fence, lanes=2, unprimed=False):
+DUMP_SEED = 0
+DUMP_PIXELS = 1 << 20  # 1 M pixels x 4 planes: values 16 MB + their non-finite codes 16 MB + indices as float64 8 MB, below 64 MB
+
+
+def dump_outputs(out_dir, out):
+    """--dump-outputs DIR: what the timed path handed its caller after its last step, as .npy files, so that two builds can be
+    compared output for output.  out: that output on the device, [..., P, rows, cols] (frames, or ranks x frames, of P planes),
+    seen as [A, P, B]: A frames or frame shards of P planes of B pixels.  Every file holds finite numbers only, yet loses nothing:
+      framebuffer_sample.npy           float32 [S, P]  every plane of S pixels, a non-finite value (z of an uncovered pixel: +inf) as 0
+      framebuffer_sample_nonfinite.npy float32 [S, P]  what stood there instead: 0 finite, 1 +inf, -1 -inf, 2 NaN
+      framebuffer_sample_index.npy     float64 [S]     the pixels' flat indices a * B + b, ascending
+    S pixels = every pixel when there are at most DUMP_PIXELS, else DUMP_PIXELS of them drawn without replacement by numpy's
+    generator seeded with DUMP_SEED — the same pixels for the same arguments."""
+    import numpy as np
+    import torch
+    planes = out.flatten(0, -4).flatten(-2)
+    n_a, _, n_b = planes.shape
+    n = n_a * n_b
+    if n <= DUMP_PIXELS:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_PIXELS, replace=False))
+    i = torch.from_numpy(idx).to(planes.device)
+    sample = planes[i // n_b, :, i % n_b].float()
+    code = torch.zeros_like(sample)
+    code[torch.isposinf(sample)], code[torch.isneginf(sample)], code[torch.isnan(sample)] = 1.0, -1.0, 2.0
+    sample = torch.where(code == 0, sample, torch.zeros_like(sample))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "framebuffer_sample.npy"), sample.cpu().numpy())
+    np.save(os.path.join(out_dir, "framebuffer_sample_nonfinite.npy"), code.cpu().numpy())
+    np.save(os.path.join(out_dir, "framebuffer_sample_index.npy"), idx.astype(np.float64))
+
+
+def time_single_gpu(case, steps, warmup, fence, lanes=2, unprimed=False, split=True):
     """W warm-up steps, then EXACTLY K steps bracketed by fences.
 
     A step renders the whole batch: `lanes` runs of whole frames, each on a stream of its own (srz.parallel.LaneRenderer —
     the lanes are not synchronised with each other, so consecutive steps overlap at their edges; every step is complete
     before the closing fence).  Inside the timed region every render carries two HIP events on its stream (start / end of
     its launch set); the device time of the region is the span from the first start to the last end.  The per-kernel split
-    comes from a short pass AFTER the timed region — the batch in one piece on one stream, with two more events per render:
-    each event is a barrier in the stream, so the split is kept out of the throughput measurement."""
+    comes from a short pass AFTER the timed region (split=True: one_stream_split) — the batch in one piece on one stream, with
+    two more events per render: each event is a barrier in the stream, so the split is kept out of the throughput measurement.
+    On return case.out[0] holds what the last timed step computed unless the split ran (it renders into the same buffer)."""
     torch, ctx, fs = case.torch, case.ctx, case.fs
     from srz import abi
     out = case.out[0]
@@ -329,9 +368,9 @@ def time_single_gpu(case, steps, warmup, fence, lanes=2, unprimed=False):
     # priming (not counted as warm-up; reported as `priming_steps`): the first ~13 renders after idle run up to 10 % slower
     # (clock ramp, first touch of the list pool: tools/step_series_probe.py prints the series), and renders 6..23 of a frameset are the
     # ones that try the candidate grids of its clear (srz_api.hip, srz_frameset::ClearTune) — a short --warmup ends inside both.
-    # The headline case therefore times TWO regions: first exactly what the arguments say from idle (W untimed steps,
+    # With --full the headline case therefore times TWO regions: first exactly what the arguments say from idle (W untimed steps,
     # K timed: `value_unprimed` / `ms_per_step_unprimed`), then W more untimed steps and K timed ones in the steady state (`value`);
-    # the other workloads make sure of PRIME_TO untimed renders in all and time one region.
+    # a plain run and the other workloads make sure of PRIME_TO untimed renders in all and time one region.
     unprimed_dt = None
     if unprimed:  # the driver's arguments taken literally: W untimed steps from idle, then K timed ones (`value_unprimed`); they
         for _ in range(warmup):  # also serve as the priming of the region that follows
@@ -368,7 +407,21 @@ def time_single_gpu(case, steps, warmup, fence, lanes=2, unprimed=False):
     # the measurement was complete before the timed region
     dc = [s_.debug_counters() for s_ in lr.sets]
     kt["clear_wgs"], kt["clear_tuned"] = [d_["clear_wgs"] for d_ in dc], all(d_["clear_tuned"] for d_ in dc)
-    # ---- not part of the measurement: the same batch in ONE piece on ONE stream (whole-launch time, then the kernel split)
+    kt["unprimed_dt"], kt["priming_steps"] = unprimed_dt, priming
+    if split:
+        one_stream_split(case, steps, fence, kt)
+    ctx.set_kernel_timing(0)
+    return dt, kt, per_step
+
+
+def one_stream_split(case, steps, fence, kt):
+    """Not part of the measurement: the batch of time_single_gpu in ONE piece on ONE stream (whole-launch time, then the
+    per-kernel split), run after its timed region; adds one_stream_ms_per_step, bin_ms / raster_ms / shade_ms and
+    split_total_ms to kt.  Renders into case.out[0]."""
+    torch, ctx, fs = case.torch, case.ctx, case.fs
+    from srz import abi
+    out = case.out[0]
+    ctx.set_kernel_timing(1)  # (as in the timed region: a render carries its two events)
     stream = torch.cuda.Stream()
     with torch.cuda.stream(stream):
         for _ in range(PRIME_TO):  # (this frameset measures the grid of its clear too)
@@ -390,8 +443,6 @@ def time_single_gpu(case, steps, warmup, fence, lanes=2, unprimed=False):
     for k in ("bin_ms", "raster_ms", "shade_ms"):
         kt[k] = split[k]
     kt["split_total_ms"] = split["total_ms"]
-    kt["unprimed_dt"], kt["priming_steps"] = unprimed_dt, priming
-    return dt, kt, per_step
 
 
 def make_comm(ctx, dist, torch, rank, world):
@@ -429,12 +480,14 @@ def make_comm(ctx, dist, torch, rank, world):
     return comm, None
 
 
-def time_multi_gpu(case, comm, dist, steps, warmup, fence, exchange="planes", no_overlap=False, layout="shards", rank=0):
+def time_multi_gpu(case, comm, dist, steps, warmup, fence, exchange="planes", no_overlap=False, layout="shards", rank=0,
+                   exchange_alone=True):
     """N > 1 (also runs at world 1 with a one-rank communicator — tests/test_gpu_exchange.py drives it there, so the scaling
     run is not this code's first execution): render on one stream, exchange on another, double-buffered: the exchange of step
     k runs while step k+1 renders.  layout "shards": the rank renders (or resolves) straight into its slot of the gathered
     buffer and the exchange is ONE in-place all-gather, no second pass (result in rank-major shard order,
     srz_frameset_allgather_inplace); "rows": all-gather into a staging buffer + one HIP de-interleave pass (row-major frames).
+    exchange_alone=False skips the pass that times the exchange without a render beside it (its figures are then None).
     → (dt, kernel times, per-step list, multi dict)"""
     from srz import abi, parallel
     torch, ctx, fs, world = case.torch, case.ctx, case.fs, case.world
@@ -488,22 +541,26 @@ def time_multi_gpu(case, comm, dist, steps, warmup, fence, exchange="planes", no
     kt = ctx.kernel_time_ms(reset=True)
     ctx.set_kernel_timing(False)
     # the exchange alone (no render beside it), same buffers: what the overlap has to hide
-    fence()
-    t1 = time.perf_counter()
-    for k in range(steps):
-        xq.submit(lambda b=k % 2: do_exchange(b))
-    xq.drain()
-    fence()
-    x_alone = (time.perf_counter() - t1) / steps * 1e3
+    x_alone = None
+    if exchange_alone:
+        fence()
+        t1 = time.perf_counter()
+        for k in range(steps):
+            xq.submit(lambda b=k % 2: do_exchange(b))
+        xq.drain()
+        fence()
+        x_alone = (time.perf_counter() - t1) / steps * 1e3
     if dist is not None:
-        tt = torch.tensor([dt, x_alone * 1e-3], dtype=torch.float64, device="cuda")
+        tt = torch.tensor([dt, (x_alone or 0.0) * 1e-3], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt, x_alone = float(tt[0]), float(tt[1]) * 1e3
+        dt = float(tt[0])
+        if x_alone is not None:
+            x_alone = float(tt[1]) * 1e3
     step_ms = dt / steps * 1e3
     shard_bytes = shard[0].numel() * shard[0].element_size()
     multi = {"exchange": exchange, "layout": layout, "second_pass": layout != "shards", "behind_c_abi": comm is not None, "overlapped": not no_overlap,
              "step_ms": step_ms, "render_ms_per_step": kt["total_ms"], "exchange_alone_ms_per_step": x_alone,
-             "hidden_ms_per_step": max(0.0, kt["total_ms"] + x_alone - step_ms),
+             "hidden_ms_per_step": max(0.0, kt["total_ms"] + x_alone - step_ms) if x_alone is not None else None,
              "bytes_sent_per_rank_per_step": shard_bytes, "bytes_received_per_rank_per_step": (world - 1) * shard_bytes,
              "predicted_exchange_ms_at_xgmi_peak": shard_bytes / (XGMI_LINK_GBS * 1e9) * 1e3,
              "note": "exchange = ncclAllGather of every rank's band shard (each rank sends its shard once to each of the N-1 peers, one "
@@ -548,7 +605,7 @@ def case_record(case, steps, dt, kt, per_step, frag_total, vis_total):
     fs = case.fs
     fps = case.n_frames * steps / dt
     pipeline_s = kt["total_ms"] * 1e-3
-    achieved = case.algo_bytes / pipeline_s / 1e9 if pipeline_s > 0 else 0.0
+    achieved = (case.algo_bytes / pipeline_s / 1e9 if pipeline_s > 0 else 0.0) if case.algo_bytes is not None else None
     pm = pmc_counters(case.name, case.n_frames, case.scope) if case.world == 1 else None
     # VALU issue beside the HBM fraction (a kernel can sit far below the HBM roofline because it is bound by instruction issue):
     # wave-instructions per step x 2 cycles / the SIMD-cycles of the step's device time.  A CDNA4 SIMD is 32 lanes wide: with two
@@ -558,7 +615,7 @@ def case_record(case, steps, dt, kt, per_step, frag_total, vis_total):
     # valu_pipe_frac_est prices binary64 arithmetic at 4 and transcendentals at 8 cycles from the instruction-class counters
     # (packed f32 instructions, 4 cycles, are not counted apart: still a lower bound)
     valu = None
-    if pm and pipeline_s > 0:
+    if pm and pipeline_s > 0 and vis_total is not None:
         simd_cycles = N_SIMD * SCLK_HZ * pipeline_s
         valu = {"valu_wave_insts_per_step": pm["valu_wave_insts_per_step"],
                 "valu_frac": pm["valu_wave_insts_per_step"] * 2.0 / simd_cycles,
@@ -572,17 +629,20 @@ def case_record(case, steps, dt, kt, per_step, frag_total, vis_total):
         "frames_per_sec": fps, "ms_per_step": dt / steps * 1e3,
         "ms_per_step_p10_median_p90": [pct(per_step, 0.1), pct(per_step, 0.5), pct(per_step, 0.9)] if per_step else None,
         "us_per_frame_median": (pct(per_step, 0.5) * 1e3 / case.n_frames) if per_step else None,
-        "mfragments_per_sec": frag_total / fs.n_frames * fps / 1e6,
-        "fragments_per_frame": frag_total / fs.n_frames, "visible_pixels_per_frame": vis_total / fs.n_frames,
+        # (frag_total / vis_total None: the counting pass did not run, a plain run without --full)
+        "mfragments_per_sec": frag_total / fs.n_frames * fps / 1e6 if frag_total is not None else None,
+        "fragments_per_frame": frag_total / fs.n_frames if frag_total is not None else None,
+        "visible_pixels_per_frame": vis_total / fs.n_frames if vis_total is not None else None,
         "valu": valu,
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS if achieved is not None else None,
                      "traffic": pm["hbm_bytes_per_step"] if pm else None, "traffic_stale": (pmc_stale() and case.world == 1) or None,
-                     "traffic_over_algorithmic": pm["hbm_bytes_per_step"] / case.algo_bytes if pm else None,
+                     "traffic_over_algorithmic": pm["hbm_bytes_per_step"] / case.algo_bytes if pm and case.algo_bytes else None,
                      "algorithmic_bytes_per_launch": case.algo_bytes, "launch_ms": kt["total_ms"],
                      "lanes": kt.get("lanes", 1), "lane_launch_ms": kt.get("lane_launch_ms"),
                      "clear_wgs": kt.get("clear_wgs"), "clear_tuned": kt.get("clear_tuned"),
                      "one_stream": {"ms_per_step": kt.get("one_stream_ms_per_step"), "launch_ms": kt.get("split_total_ms"),
-                                    "k_setup_bin_ms": kt["bin_ms"], "k_raster_ms": kt["raster_ms"], "k_shade_ms": kt["shade_ms"]}},
+                                    "k_setup_bin_ms": kt.get("bin_ms"), "k_raster_ms": kt.get("raster_ms"), "k_shade_ms": kt.get("shade_ms")}},
     }
 
 
@@ -792,8 +852,8 @@ def main():
                          "draw: meshes + per-frame matrices resident, the vertex stage (k_vertex) is timed too")
     ap.add_argument("--exchange", choices=["bgr8", "planes", "both"], default="both",
                     help="N>1 only. planes: all-gather the 4 float planes (16 B/px: z + m_channels) — the headline; bgr8: resolve to "
-                         "8-bit on the device and all-gather display()'s image (3 B/px); both: the headline exchanges the planes and "
-                         "a second, shorter pass times bgr8 (multi_gpu.bgr8)")
+                         "8-bit on the device and all-gather display()'s image (3 B/px); both: the headline exchanges the planes and, "
+                         "with --full, a second, shorter pass times bgr8 (multi_gpu.bgr8)")
     ap.add_argument("--exchange-layout", choices=["shards", "rows"], default="shards",
                     help="N>1 only. shards: render into the rank's slot of the gathered buffer, ONE in-place all-gather, no second "
                          "pass (frames stay in rank-major shard order); rows: all-gather + a HIP de-interleave pass (row-major frames)")
@@ -802,10 +862,19 @@ def main():
                          "(srz.parallel.LaneRenderer: consecutive steps overlap at their edges); 1 = one frameset on one "
                          "stream; 0 = two lanes for steps of >= 64 frames, else one")
     ap.add_argument("--no-overlap", action="store_true", help="N>1 only: render and exchange back to back on one stream")
-    ap.add_argument("--no-extras", action="store_true", help="N=1: skip the other BASELINE configs / scope draw / the README loop")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: the unprimed region, the counting pass (Mfragments/s), the "
+                         "one-stream per-kernel split; at N=1 the other BASELINE configs / scope draw / the README loop / the "
+                         "tolerance mode / the emulated N-GPU shards and the CPU baseline; at N>1 the exchange alone and bgr8. "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a seeded sample of what the last one computed to DIR/*.npy (dump_outputs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full, N=1: skip the other BASELINE configs / scope draw / the README loop")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-budget-s", type=float, default=12.0)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- no launcher around us: start the ranks ourselves, BEFORE torch / HIP are touched in this process ----------------------
     # (SRZ_BENCH_FORCE_LAUNCHER=1: take this path at N = 1 too — one child that runs the N > 1 code at world 1: tests)
@@ -820,7 +889,7 @@ def main():
     multi_path = world > 1 or (force and os.environ.get("SRZ_BENCH_LAUNCHED") == "1")
 
     # the reference's published protocol through the C++ API: a child process, before this one initialises the GPU
-    loop_rec = readme_loop() if (world == 1 and not multi_path and not args.no_extras) else None
+    loop_rec = readme_loop() if (args.full and world == 1 and not multi_path and not args.no_extras) else None
 
     import torch
     import torch.distributed as dist
@@ -848,9 +917,11 @@ def main():
     ctx = srz.Context(local_rank, rank, world)
     comm, comm_note = (None, None) if not multi_path else make_comm(ctx, dist, torch, rank, world)
 
-    case = Case(ctx, torch, args.workload, args.frames, args.scope, world, n_out=2 if multi_path else 1)
+    case = Case(ctx, torch, args.workload, args.frames, args.scope, world, n_out=2 if multi_path else 1, stats=args.full)
     fs, stats = case.fs, case.stats
-    if multi_path:
+    if stats is None:
+        frag_total, vis_total = None, None
+    elif multi_path:
         st = torch.tensor([stats["fragments"], stats["visible"]], dtype=torch.int64, device="cuda")
         dist.all_reduce(st)
         frag_total, vis_total = int(st[0]), int(st[1])
@@ -859,12 +930,20 @@ def main():
 
     multi = None
     if not multi_path:
-        dt, kt, per_step = time_single_gpu(case, args.steps, args.warmup, fence, args.lanes, unprimed=True)
+        dt, kt, per_step = time_single_gpu(case, args.steps, args.warmup, fence, args.lanes, unprimed=args.full, split=False)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, case.out[0])
+        if args.full:
+            one_stream_split(case, args.steps, fence, kt)
+            ctx.set_kernel_timing(0)
     else:
         head_x = "bgr8" if args.exchange == "bgr8" else "planes"
         dt, kt, per_step, multi = time_multi_gpu(case, comm, dist, args.steps, args.warmup, fence, head_x,
-                                                 args.no_overlap, args.exchange_layout, rank)
-        multi.pop("last_full")
+                                                 args.no_overlap, args.exchange_layout, rank, exchange_alone=args.full)
+        last_full = multi.pop("last_full")
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last_full)
+        del last_full
         multi["headline_exchange"] = head_x
         multi["why"] = ("planes = z + the three float m_channels, what draw() leaves and what north_star's parity is stated on (z bit-exact): "
                         "the headline at every N; bgr8 = display()'s m_frameBuffer after convertTo(CV_8UC3) (src/Render.cpp:61-62 of the "
@@ -873,7 +952,7 @@ def main():
         multi["predicted"] = {"bgr8": predicted_exchange(budget["shard_bytes_bgr8"], case.n_frames),
                               "planes": predicted_exchange(budget["shard_bytes_planes"], case.n_frames),
                               "source": "DESIGN.md §6: shard bytes / 153 GB/s per xGMI link; render (≈ the N = 1 step) hidden under it"}
-        if args.exchange == "both":  # display()'s 8-bit image beside the headline
+        if args.full and args.exchange == "both":  # display()'s 8-bit image beside the headline
             torch.cuda.empty_cache()
             k2 = max(3, args.steps // 2)
             dt2, kt2, _, m2 = time_multi_gpu(case, comm, dist, k2, min(args.warmup, 2), fence, "bgr8", args.no_overlap,
@@ -896,7 +975,7 @@ def main():
                                         "(same bytes per step, kernels not overlapped), per step (not measured in this run; "
                                         "kernel sources' hash checked)") if traffic else None,
                      "kernel_source_hash": kernel_source_hash(),
-                     "frac_of_measured_copy_6290": roof["achieved"] / HBM_MEASURED_COPY_GBS,
+                     "frac_of_measured_copy_6290": roof["achieved"] / HBM_MEASURED_COPY_GBS if roof["achieved"] is not None else None,
                      "kernel": "hot path = k_setup + k_bin + k_raster (+ k_raster_slow) + k_shade in line, k_clear beside k_raster/k_shade "
                                "on a second stream (one launch each per lane per step)",
                      "launches_timed": kt["launches"],
@@ -932,7 +1011,7 @@ def main():
 
     # ---- N = 1: the other GPU configs of BASELINE.json + configs[1] at scope draw, each outside the headline's timed region
     extras = []
-    if not multi_path and not args.no_extras:
+    if args.full and not multi_path and not args.no_extras:
         todo = [(w, f, s, "raster", args.lanes, 0) for (w, f, s) in EXTRA_CASES if w != args.workload]
         todo.append((args.workload, args.frames, max(5, args.steps // 2), "draw" if args.scope == "raster" else "raster", args.lanes, 0))
         # the headline workload once more the other way (one frameset on one stream / two lanes on two streams)
@@ -973,7 +1052,7 @@ def main():
             res["roofline"]["multi_gpu_emulated"] = emulate_shards(srz, torch, local_rank, fence, args)
         except Exception as e:  # noqa: BLE001
             res["roofline"]["multi_gpu_emulated"] = {"error": str(e)[:200]}
-    if not multi_path and not args.no_cpu_baseline:
+    if args.full and not multi_path and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_budget_s)
     if rank == 0:
         emit(res, extras)

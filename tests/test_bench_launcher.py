@@ -105,3 +105,33 @@ def test_emit_prints_one_short_last_line_and_keeps_the_full_record_beside_it(tmp
     bench.emit(full, extras)
     line = capsys.readouterr().out.strip().splitlines()[-1]
     assert len(line) < bench.LINE_LIMIT and "frac" in json.loads(line)["roofline"]
+
+
+def test_dump_outputs_writes_every_pixel_or_the_same_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs on host tensors of the two layouts bench.py hands it ([F, P, rows, cols] and [ranks, F, P, rows, cols]):
+    every plane of every pixel in order when they fit, else the same DUMP_PIXELS pixels in every run, float32 values
+    + float64 flat indices; every file finite, the non-finite values (z of uncovered pixels) coded beside them without loss"""
+    sys.path.insert(0, REPO)
+    import numpy as np
+    import torch
+    import bench
+    fb = torch.arange(3 * 4 * 5 * 6, dtype=torch.float32).view(3, 4, 5, 6)
+    fb[0, 0, 0, :3] = torch.tensor([float("inf"), float("-inf"), float("nan")])
+    bench.dump_outputs(str(tmp_path / "all"), fb)
+    s, i = np.load(tmp_path / "all" / "framebuffer_sample.npy"), np.load(tmp_path / "all" / "framebuffer_sample_index.npy")
+    c = np.load(tmp_path / "all" / "framebuffer_sample_nonfinite.npy")
+    assert s.dtype == np.float32 and c.dtype == np.float32 and i.dtype == np.float64 and s.shape == c.shape == (3 * 30, 4)
+    assert np.isfinite(s).all() and np.isfinite(c).all()
+    assert c[:3, 0].tolist() == [1.0, -1.0, 2.0] and (s[:3, 0] == 0).all() and (c != 0).sum() == 3
+    expect = fb.numpy().reshape(3, 4, 30).transpose(0, 2, 1).reshape(90, 4)
+    assert np.array_equal(i, np.arange(90)) and np.array_equal(s[c == 0], expect[c == 0])
+    monkeypatch.setattr(bench, "DUMP_PIXELS", 17)
+    shards = torch.randn(2, 3, 4, 5, 6)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), shards)
+    s, i = np.load(tmp_path / "a" / "framebuffer_sample.npy"), np.load(tmp_path / "a" / "framebuffer_sample_index.npy")
+    assert s.shape == (17, 4) and len(np.unique(i)) == 17 and (np.diff(i) > 0).all() and 0 <= i.min() and i.max() < 6 * 30
+    k = i.astype(np.int64)
+    assert np.array_equal(s, shards.reshape(6, 4, 30).numpy()[k // 30, :, k % 30])
+    assert np.array_equal(s, np.load(tmp_path / "b" / "framebuffer_sample.npy"))
+    assert np.array_equal(i, np.load(tmp_path / "b" / "framebuffer_sample_index.npy"))

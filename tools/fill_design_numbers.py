@@ -64,7 +64,7 @@ for e in d["configs"]:
             nm = (NAMES.get(e["workload"]) or "2 spot TEXTURE 1024²").split(" (")[0] + " — tolerance mode"
         out.append(row(nm, e))
 txt = "\n".join(out)
-txt += (f"\n\n(`python bench.py --steps {d['steps']} --warmup {d['warmup']}`, `profiles/{os.path.basename(src)}`; `value` is the second timed region; the first one, "
+txt += (f"\n\n(`python bench.py --full --steps {d['steps']} --warmup {d['warmup']}`, `profiles/{os.path.basename(src)}`; `value` is the second timed region; the first one, "
         f"straight after the {d['warmup']} warm-up steps from idle: {d['value_unprimed']:,.0f} frames/s / {d['roofline']['algorithmic_bytes_per_launch'] / (d['ms_per_step_unprimed'] * 1e-3) / 8e12:.3f}.  "
         "Driver records of earlier rounds: round 5 278 830 frames/s / 0.620, configs 3 / 4 / 5 0.598 / 0.398 / 0.414; round 4 (builder's run) 287 000 / 0.641, 0.593 / 0.406 / 0.415; round 3 247 200 / 0.549, 0.484 / 0.338 / 0.340.)  "
         "The reference's own protocol through the C++ API "

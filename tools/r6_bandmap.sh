@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for lib in rot0.so - rot3.so rot5.so rot0.so -; do
   if [ "$lib" = "-" ]; then unset SRZ_LIB_PATH; else export SRZ_LIB_PATH=$PWD/software-rasterizer_amd/build/$lib; fi
-  python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > /dev/null 2>/dev/null
+  python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > /dev/null 2>/dev/null
   python3 -c "
 import json
 d=json.load(open('bench_details.json')); me=d['roofline']['multi_gpu_emulated']

@@ -10,7 +10,7 @@ bash tools/r6_env_sweep.sh $O/call1.log "spot_x16_texture_2048:128 spot_x8_overd
 for wf in spot_x16_texture_2048:128 spot_x8_overdraw_4096:64; do
   w=${wf%%:*}; f=${wf##*:}
   rm -rf $O/tr_$w
-  rocprofv3 --kernel-trace --output-format csv -d $O/tr_$w -- python3 bench.py --no-cpu-baseline --no-extras --workload $w --frames $f --lanes 2 --steps 10 --warmup 5 > $O/tr_$w.json 2> $O/tr_$w.err || { tail -5 $O/tr_$w.err; exit 1; }
+  rocprofv3 --kernel-trace --output-format csv -d $O/tr_$w -- python3 bench.py --full --no-cpu-baseline --no-extras --workload $w --frames $f --lanes 2 --steps 10 --warmup 5 > $O/tr_$w.json 2> $O/tr_$w.err || { tail -5 $O/tr_$w.err; exit 1; }
   echo "--- overlap $w" >> $O/call1.log
   python3 tools/overlap_trace.py $O/tr_$w $O/overlap_$w.json >> $O/call1.log
   rm -rf $O/tr_$w

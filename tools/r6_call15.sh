@@ -6,7 +6,7 @@ for wf in readme_spot_crate_1024:256 spot_texture_1024_p7.5:256 spot_texture_102
   w=${wf%%:*}; f=${wf##*:}
   for k in 1 2 3; do
     echo "== $w run $k" >> $O/call15.err
-    SRZ_CLEAR_TRACE=1 python3 bench.py --no-cpu-baseline --no-extras --workload $w --frames $f --steps 20 --warmup 5 2>>$O/call15.err | python3 -c "
+    SRZ_CLEAR_TRACE=1 python3 bench.py --full --no-cpu-baseline --no-extras --workload $w --frames $f --steps 20 --warmup 5 2>>$O/call15.err | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$w', 'run $k', 'fps', round(d['value']), 'frac', round(r['frac'],4), 'unprimed', d.get('value_unprimed'), 'wgs', r.get('clear_wgs'))" >> $O/call15.log || exit 1

@@ -6,7 +6,7 @@ O=gpurun_out/r6; mkdir -p $O; rm -f $O/call9.log $O/call9.err
 for wf in spot_texture_1024:256 spot_bunny_phong_1080p:128 spot_x16_texture_2048:128 spot_x8_overdraw_4096:64; do
   w=${wf%%:*}; f=${wf##*:}
   for e in "SRZ_CLEAR_TRACE=1" "SRZ_CLEAR_TUNE=0" "SRZ_LIB_PATH=$PWD/software-rasterizer_amd/build/base.so" "SRZ_CLEAR_TRACE=1"; do
-    env $e python3 bench.py --no-cpu-baseline --no-extras --workload $w --frames $f --steps 20 --warmup 5 2>>$O/call9.err | python3 -c "
+    env $e python3 bench.py --full --no-cpu-baseline --no-extras --workload $w --frames $f --steps 20 --warmup 5 2>>$O/call9.err | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$w', '[${e##*/}]', 'lanes', r.get('lanes'), 'fps', round(d['value']), 'ms', round(d['ms_per_step'],4), 'frac', round(r['frac'],4), 'unprimed', d.get('value_unprimed'), 'one-stream us', r.get('one_stream_us'))" >> $O/call9.log || exit 1

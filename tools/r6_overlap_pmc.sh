@@ -10,7 +10,7 @@ O=gpurun_out/r6; mkdir -p $O
 SQ="SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_INSTS_VALU"
 for wf in spot_x16_texture_2048:128 spot_x8_overdraw_4096:64; do
   w=${wf%%:*}; f=${wf##*:}
-  CMD="python3 bench.py --no-cpu-baseline --no-extras --workload $w --frames $f --steps 10 --warmup 5"
+  CMD="python3 bench.py --full --no-cpu-baseline --no-extras --workload $w --frames $f --steps 10 --warmup 5"
   rm -rf $O/ovt $O/ovp2 $O/ovp1
   rocprofv3 --kernel-trace --output-format csv -d $O/ovt -- $CMD --lanes 2 > $O/ov_$w.trace.json 2> $O/ov_$w.trace.err || { tail -5 $O/ov_$w.trace.err; exit 1; }
   python3 tools/overlap_trace.py $O/ovt $O/ov_${w}_trace.json > $O/ov_${w}_trace.txt

@@ -1,9 +1,11 @@
-# Dev tool, run ON THE GPU BOX: kernel durations of every render of a default bench.py run (main case + extras), in order
+# Dev tool (needs the GPU): kernel durations of every render of a bench.py --full run (main case + extras), in order
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-rm -rf gpurun_out/tb; rocprofv3 --kernel-trace --output-format csv -d gpurun_out/tb -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > gpurun_out/tb.json 2> gpurun_out/tb.err
-python3 - <<'PY'
-import csv, glob
-f = glob.glob("gpurun_out/tb/**/*kernel_trace.csv", recursive=True)[0]
+# usage: trace_bench.sh OUT_DIR   (the trace goes to OUT_DIR/tb, the bench line and its stderr to OUT_DIR/tb.json, OUT_DIR/tb.err)
+O=${1:?usage: trace_bench.sh OUT_DIR}; mkdir -p "$O"
+rm -rf "$O/tb"; rocprofv3 --kernel-trace --output-format csv -d "$O/tb" -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > "$O/tb.json" 2> "$O/tb.err"
+python3 - "$O" <<'PY'
+import csv, glob, sys
+f = glob.glob(sys.argv[1] + "/tb/**/*kernel_trace.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 # print per-render sequences compactly: for each k_setup start a new line
