@@ -43,6 +43,8 @@ extern "C" {
  *      the tile-list pool is sized by srz_frameset_create / srz_sceneset_create, the first srz_frameset_render no longer blocks
  *   7  srz_host_register / srz_host_unregister, SRZ_NO_Z_READBACK, srz_verify_fastlen, srz_frameset_debug_counters; srz_draw_batch reads one piece of the batch
  *      back while the next one renders
+ *      (additive, same version: no existing signature, struct or meaning changed) the tile-sparse exchange srz_frameset_sparse_capacity /
+ *      _sparse_pack / _sparse_unpack, srz_frameset_allgather_sparse
  */
 #define SRZ_ABI_VERSION 7
 
@@ -184,7 +186,9 @@ const char *srz_last_error(const srz_ctx *ctx); /* ctx may be NULL: last error o
 #define SRZ_OPT_APPROX_SHADE 2
 int srz_set_option(srz_ctx *ctx, int option, int value);
 
-/* Multi-GPU: this ctx owns the 32-row bands b with b % world == rank (local band b / world).
+/* Multi-GPU: this ctx owns the 32-row bands b of rank(b) == rank, at local band b / world.  THE BAND MAP:
+ *     rank(b) = (b + band_rot(world) * (b / world)) % world,   band_rot(world) = 5, or 1 when 5 % world == 0
+ * (integer division): every group of `world` consecutive bands hands one band to every rank, rotated by band_rot ranks per group.
  * Default (0,1) = whole frame. Affects srz_frameset_* only. */
 int srz_set_shard(srz_ctx *ctx, int rank, int world);
 
@@ -278,7 +282,7 @@ int srz_frameset_deinterleave(srz_ctx *ctx, const srz_frameset *fs, const void *
  * other ranks' shards around it: no staging copy, no de-interleave kernel, nothing but the xGMI transfers.  The result stays in
  * the all-gather's own order, "rank-major shards":
  *     [rank][frame][plane: z,c0,c1,c2 | 1][bands_per_rank * 32 rows][row bytes]
- * row y of a frame lives in the shard of rank (y / 32) % world at local row (y / 32 / world) * 32 + y % 32:
+ * row y of a frame lives in the shard of rank rank(y / 32) (THE BAND MAP at srz_set_shard) at local row (y / 32 / world) * 32 + y % 32:
  * srz_frameset_gathered_row_offset() returns that row's byte offset in d_gathered, and srz_frameset_read_gathered_frame() brings
  * one frame to the host as row-major planes ([4][H][W] float, or [H][W][3] bytes for SRZ_EXCHANGE_BGR8), de-interleaving in the
  * device→host copy itself (one strided copy per rank and plane).  A device-side consumer that needs row-major planes uses
@@ -287,6 +291,50 @@ int srz_frameset_allgather_inplace(srz_ctx *ctx, srz_comm *comm, const srz_frame
 size_t srz_frameset_gathered_row_offset(const srz_ctx *ctx, const srz_frameset *fs, int what, int frame, int plane, int row);
 int srz_frameset_read_gathered_frame(srz_ctx *ctx, const srz_frameset *fs, const void *d_gathered, int what, int frame,
                                      void *host_out, void *stream);
+
+/* ---- the TILE-SPARSE exchange: every rank sends only the 32x32 tiles its render drew into ----------------------------------------
+ * The result is exactly the layout of srz_frameset_allgather_inplace (rank-major shards [rank][frame][plane][bands_per_rank*32][row],
+ * rows found by THE BAND MAP at srz_set_shard; srz_frameset_gathered_row_offset / _read_gathered_frame / _deinterleave work on it):
+ * the rank renders or resolves into its own slot of d_gathered, and the unpack fills in the other ranks' slots.  Padding rows stay
+ * unspecified.
+ * A TOUCHED tile of a rank's shard is one its last render did not clear: some triangle's bounding box reaches it (k_bin's tile count
+ * is not 0 — the test the fused clear uses), or the frame was rendered WITHOUT SRZ_FUSED_CLEAR (frame flags | render flags), which
+ * leaves the caller's old contents in every tile: then every tile of that frame counts as touched.  Every other tile holds the clear
+ * values bit for bit (z = +inf, colour 0; SRZ_EXCHANGE_BGR8: bytes 0,0,0) and is written by the receivers themselves.
+ * MESSAGE (one per rank, identical layout on every rank, 16-byte aligned; T = n_frames * bands_per_rank * tiles_x, tiles_x = ceil(W/32)):
+ *     bytes  0..3   uint32  touched tiles (= tiles in the payload)
+ *            4..7   uint32  T
+ *            8..15  uint64  message bytes = payload offset + touched * tile bytes
+ *     16 ..         uint32  table[frame][local band][tile x]: the tile's slot in the payload, or 0xffffffff (not touched: the clear
+ *                           values); bands a rank does not have (a short last group) are never touched
+ *     payload offset = 16 + 4 T rounded up to 16:
+ *                   the touched tiles, in table order (slot k = the k-th touched tile: per-band counts + a scan, no atomics — two packs
+ *                   of one render give the same bytes), each a whole 32x32 block [plane][32 rows][32 pixels]: 16384 bytes for
+ *                   SRZ_EXCHANGE_PLANES (z, c0, c1, c2 floats), 3072 for SRZ_EXCHANGE_BGR8 (B,G,R bytes); pixels outside the frame
+ *                   (x >= W, rows past the band's end) are 0.
+ * srz_frameset_sparse_capacity: bytes of the largest message (every tile touched) — the size of d_msg; 0 for a bad `what`.
+ * srz_frameset_sparse_pack: this rank's message from its shard d_shard (what srz_frameset_render / _resolve8 wrote; for the in-place
+ *   layout: d_gathered + rank * srz_frameset_exchange_bytes()).  It reads the tile counts of the set's LAST render, so it must be
+ *   enqueued AFTER that render on the same stream (or behind it by an event) and BEFORE the set's next render or srz_frameset_stats,
+ *   which overwrite them (and before an srz_sceneset_update that changes frame flags).  msg_bytes >= capacity, else SRZ_E_INVALID.
+ *   Asynchronous on `stream`.
+ * srz_frameset_sparse_unpack: the second half alone, for a caller that brings its own collective (and for one GPU playing every
+ *   rank): the message of rank p at d_recv + p * msg_stride (msg_stride a multiple of 16) → the slots of every rank but this one in
+ *   d_gathered, real pixels only.  Asynchronous on `stream`.
+ * srz_frameset_allgather_sparse: pack first, then this call (every rank, same stream order):
+ *   1. ncclAllGather of every rank's message header and recv_bytes into a small device buffer of the communicator;
+ *   2. one device→host copy and a stream synchronise: the host learns M, the largest message (rounded up to 16).  THE CALL'S ONE
+ *      BLOCKING POINT.  If any rank's recv_bytes < world * M, EVERY rank returns SRZ_E_NOMEM (srz_last_error names the bytes needed):
+ *      no rank may leave alone while its peers enter the next collective;
+ *   3. ncclAllGather of M bytes of every rank's d_msg (which holds the capacity) into d_recv, then srz_frameset_sparse_unpack with
+ *      stride M.
+ *   With world = 1 the call does nothing.  The frameset must be of this communicator's shard (SRZ_E_INVALID). */
+size_t srz_frameset_sparse_capacity(const srz_ctx *ctx, const srz_frameset *fs, int what);
+int srz_frameset_sparse_pack(srz_ctx *ctx, srz_frameset *fs, const void *d_shard, void *d_msg, size_t msg_bytes, int what, void *stream);
+int srz_frameset_sparse_unpack(srz_ctx *ctx, const srz_frameset *fs, const void *d_recv, size_t msg_stride, void *d_gathered, int what,
+                               void *stream);
+int srz_frameset_allgather_sparse(srz_ctx *ctx, srz_comm *comm, const srz_frameset *fs, const void *d_msg, void *d_recv, size_t recv_bytes,
+                                  void *d_gathered, int what, void *stream);
 
 /* ---- device-resident framebuffer = RenderingPipeline's m_zBuffer + m_channels kept in HBM between calls ----------
  * clear(Color|Depth) immediately followed by a draw costs nothing (fused into the raster kernel); planes come back to

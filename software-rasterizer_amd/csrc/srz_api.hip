@@ -61,6 +61,7 @@ struct srz_ctx {
   bool env_no_packed = false; // SRZ_NO_PACKED (tests): see srz_frameset::no_packed
   bool env_no_turns = false;  // SRZ_NO_TURNS (A/B): renders on different streams do not wait for each other's k_raster
   uint32_t env_clear_wgs = 0; // SRZ_CLEAR_WGS: fixed grid of the side-stream clear (else measured per set, srz_frameset::ClearTune)
+  uint32_t env_unpack_wgs = 0; // SRZ_UNPACK_WGS: grid of k_sparse_unpack (else SPARSE_UNPACK_WGS; the probe's sweep)
   // what sets of this ctx have measured, by shape (clear_memo_key): a new set of a known shape starts with that grid instead of measuring
   std::vector<std::pair<uint64_t, uint32_t>> clear_memo;
   bool env_no_clear_tune = false, env_clear_trace = false; // SRZ_CLEAR_TUNE=0: the grid stays at 96; SRZ_CLEAR_TRACE=1: the measurement goes to stderr
@@ -117,6 +118,11 @@ struct srz_frameset {
   uint32_t *d_pool_heads = nullptr, *h_pool_heads = nullptr;
   static constexpr int DEMAND_PARTS = 8; // h_pool_heads holds one copy of the allocators' lines per sub-batch of a large render
   uint2 *d_tile_info = nullptr;
+  // what the tile-sparse exchange needs of the LAST render (srz_frameset_sparse_pack): its flags (the touched test of a frame is
+  // (FrameDesc::flags | these) & SRZ_FUSED_CLEAR, as in k_clear) and a word per (frame, local band) of scratch for the slot scan
+  uint32_t last_flags = 0;
+  bool rendered = false;
+  uint32_t *d_sparse_rows = nullptr;
   uint32_t *d_slow_list = nullptr, *d_slow_count = nullptr;
   uint4 *d_redo_list = nullptr; // (its counter is d_slow_count[1])
   uint32_t fast_mask = 0;   // bit NL (+ 8 with BUMP / DISPLACEMENT batches, + 16 with a non-integer exponent): some frame is shaded by that FAST build of k_shade (classify_frames)
@@ -299,6 +305,7 @@ void free_frameset_buffers(srz_frameset *fs) {
   if (fs->clear_tune.h_wgs) (void)hipHostFree(fs->clear_tune.h_wgs), fs->clear_tune.h_wgs = nullptr;
   if (fs->clear_tune.d_ctl) (void)hipFree(fs->clear_tune.d_ctl), fs->clear_tune.d_ctl = nullptr;
   (void)hipFree(fs->d_tile_info);
+  (void)hipFree(fs->d_sparse_rows);
   (void)hipFree(fs->d_slow_list);
   (void)hipFree(fs->d_slow_count);
   (void)hipFree(fs->d_redo_list);
@@ -449,6 +456,7 @@ int render_impl(srz_ctx *ctx, srz_frameset *fs, float *d_out, uint32_t flags_or,
   }
   RenderArgs a = make_args(ctx, fs, d_out, flags_or);
   if (one_frame_scratch) a.frame_stride = 0;
+  if (!size_only) fs->last_flags = flags_or, fs->rendered = true; // (this render rewrites d_tile_info: srz_frameset_sparse_pack)
   a.force_ordered = a.force_generic = stats ? 1u : 0u; // the counters are those of the reference's ordered walk
   a.any_ordered = ((flags_or & SRZ_ORDERED_RASTER) != 0 ||
                    std::any_of(fs->h_frames.begin(), fs->h_frames.end(), [](const FrameDesc &f) { return (f.flags & SRZ_ORDERED_RASTER) != 0; }))
@@ -712,6 +720,7 @@ int srz_create(srz_ctx **out, int device_id) {
   ctx->env_no_packed = getenv("SRZ_NO_PACKED") != nullptr;
   ctx->env_no_turns = getenv("SRZ_NO_TURNS") != nullptr;
   ctx->env_clear_wgs = getenv("SRZ_CLEAR_WGS") ? (uint32_t)std::max(atoi(getenv("SRZ_CLEAR_WGS")), 0) : 0u;
+  ctx->env_unpack_wgs = getenv("SRZ_UNPACK_WGS") ? (uint32_t)std::max(atoi(getenv("SRZ_UNPACK_WGS")), 0) : 0u;
   ctx->env_no_clear_tune = getenv("SRZ_CLEAR_TUNE") && atoi(getenv("SRZ_CLEAR_TUNE")) == 0;
   ctx->env_clear_trace = getenv("SRZ_CLEAR_TRACE") && atoi(getenv("SRZ_CLEAR_TRACE")) != 0;
   ctx->opt_pool_lazy = getenv("SRZ_POOL_LAZY") != nullptr;
@@ -1485,6 +1494,10 @@ extern "C" {
 struct srz_comm {
   void *comm = nullptr;
   int rank = 0, world = 1;
+  // srz_frameset_allgather_sparse: every rank's {message header, recv_bytes} (SPARSE_SLOT bytes each), on the device and in
+  // pinned host memory
+  static constexpr size_t SPARSE_SLOT = 32;
+  uint8_t *d_sizes = nullptr, *h_sizes = nullptr;
 };
 
 int srz_comm_unique_id(uint8_t *out128) {
@@ -1524,6 +1537,8 @@ void srz_comm_destroy(srz_ctx *ctx, srz_comm *c) {
   if (!c) return;
   if (ctx) (void)hipSetDevice(ctx->device), (void)hipDeviceSynchronize();
   if (c->comm) (void)rccl().CommDestroy(c->comm);
+  (void)hipFree(c->d_sizes);
+  if (c->h_sizes) (void)hipHostFree(c->h_sizes);
   delete c;
 }
 
@@ -1619,6 +1634,122 @@ int srz_frameset_read_gathered_frame(srz_ctx *ctx, const srz_frameset *fs, const
     }
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return SRZ_OK;
+}
+
+/* ---- the tile-sparse exchange (message format: include/srz.h) ------------------------------------------------------------------ */
+} // extern "C"
+namespace {
+bool sparse_kind(int what) { return what == SRZ_EXCHANGE_PLANES || what == SRZ_EXCHANGE_BGR8; }
+SparseArgs sparse_args(const srz_frameset *fs, int what) {
+  SparseArgs a{};
+  a.tile_info = fs->d_tile_info, a.frames = fs->d_frames, a.row_cnt = fs->d_sparse_rows, a.flags_or = fs->last_flags;
+  a.n_frames = (uint32_t)fs->n_frames, a.n_local_bands = fs->n_local_bands, a.bands_per_rank = fs->bands_per_rank, a.tiles_x = fs->tiles_x;
+  a.width = (uint32_t)fs->width, a.height = (uint32_t)fs->height, a.local_rows = fs->local_rows;
+  a.rank = (uint32_t)fs->shard_rank, a.world = (uint32_t)fs->shard_world;
+  a.planes = what == SRZ_EXCHANGE_BGR8 ? 1u : 4u, a.px_bytes = what == SRZ_EXCHANGE_BGR8 ? 3u : 4u, a.row_bytes = a.width * a.px_bytes;
+  const uint64_t n_tab = (uint64_t)a.n_frames * a.bands_per_rank * a.tiles_x;
+  a.payload_off = (SPARSE_HEADER + 4u * n_tab + 15u) & ~(uint64_t)15u;
+  return a;
+}
+uint64_t sparse_tile_bytes(const SparseArgs &a) { return (uint64_t)a.planes * BAND * TILE * a.px_bytes; }
+} // namespace
+extern "C" {
+
+size_t srz_frameset_sparse_capacity(const srz_ctx *ctx, const srz_frameset *fs, int what) {
+  if (!fs || !sparse_kind(what)) return 0;
+  const SparseArgs a = sparse_args(fs, what);
+  return (size_t)(a.payload_off + (uint64_t)a.n_frames * a.bands_per_rank * a.tiles_x * sparse_tile_bytes(a));
+}
+
+int srz_frameset_sparse_pack(srz_ctx *ctx, srz_frameset *fs, const void *d_shard, void *d_msg, size_t msg_bytes, int what, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  if (!fs || !d_shard || !d_msg || !sparse_kind(what)) return fail(ctx, SRZ_E_INVALID, "srz_frameset_sparse_pack: bad arguments");
+  if (fs->shard_rank != ctx->shard_rank || fs->shard_world != ctx->shard_world)
+    return fail(ctx, SRZ_E_INVALID, "srz_frameset_sparse_pack: the frameset was created under a different shard");
+  const size_t cap = srz_frameset_sparse_capacity(ctx, fs, what);
+  if (msg_bytes < cap)
+    return fail(ctx, SRZ_E_INVALID, "srz_frameset_sparse_pack: message buffer of " + std::to_string(msg_bytes) + " bytes, " +
+                                        std::to_string(cap) + " needed (srz_frameset_sparse_capacity)");
+  if ((uintptr_t)d_msg & 15u) return fail(ctx, SRZ_E_INVALID, "srz_frameset_sparse_pack: the message must be 16-byte aligned");
+  if (!fs->rendered) return fail(ctx, SRZ_E_INVALID, "srz_frameset_sparse_pack: the frameset has not been rendered");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = pick_stream(ctx, stream);
+  if (!fs->d_sparse_rows) HIP_TRY(ctx, hipMalloc(&fs->d_sparse_rows, sizeof(uint32_t) * std::max<size_t>((size_t)fs->n_frames * fs->bands_per_rank, 1)));
+  SparseArgs a = sparse_args(fs, what);
+  a.shard = d_shard, a.msg = static_cast<uint8_t *>(d_msg);
+  launch_sparse_pack(a, s);
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
+int srz_frameset_sparse_unpack(srz_ctx *ctx, const srz_frameset *fs, const void *d_recv, size_t msg_stride, void *d_gathered, int what,
+                               void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  if (!fs || !d_recv || !d_gathered || !sparse_kind(what)) return fail(ctx, SRZ_E_INVALID, "srz_frameset_sparse_unpack: bad arguments");
+  if (fs->shard_rank != ctx->shard_rank || fs->shard_world != ctx->shard_world)
+    return fail(ctx, SRZ_E_INVALID, "srz_frameset_sparse_unpack: the frameset was created under a different shard");
+  const SparseArgs a = sparse_args(fs, what);
+  if (msg_stride < a.payload_off || (msg_stride & 15u) || ((uintptr_t)d_recv & 15u))
+    return fail(ctx, SRZ_E_INVALID, "srz_frameset_sparse_unpack: the stride must be a multiple of 16 bytes of at least a message's header and "
+                                    "table (" + std::to_string(a.payload_off) + " bytes), the messages 16-byte aligned");
+  if (what == SRZ_EXCHANGE_PLANES && ((uintptr_t)d_gathered & 3u)) return fail(ctx, SRZ_E_INVALID, "srz_frameset_sparse_unpack: misaligned buffer");
+  if (fs->shard_world == 1) return SRZ_OK; // (no peers)
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  launch_sparse_unpack(a, d_recv, msg_stride, d_gathered, ctx->env_unpack_wgs, pick_stream(ctx, stream));
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
+int srz_frameset_allgather_sparse(srz_ctx *ctx, srz_comm *c, const srz_frameset *fs, const void *d_msg, void *d_recv, size_t recv_bytes,
+                                  void *d_gathered, int what, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  if (!c || !fs || !d_msg || !d_recv || !d_gathered) return fail(ctx, SRZ_E_INVALID, "srz_frameset_allgather_sparse: null argument");
+  if (fs->shard_world != c->world || fs->shard_rank != c->rank)
+    return fail(ctx, SRZ_E_INVALID, "srz_frameset_allgather_sparse: the frameset was not created under this communicator's shard");
+  if (!sparse_kind(what)) return fail(ctx, SRZ_E_INVALID, "srz_frameset_allgather_sparse: bad exchange kind");
+  if (((uintptr_t)d_msg | (uintptr_t)d_recv) & 15u) return fail(ctx, SRZ_E_INVALID, "srz_frameset_allgather_sparse: messages must be 16-byte aligned");
+  if (what == SRZ_EXCHANGE_PLANES && ((uintptr_t)d_gathered & 3u)) return fail(ctx, SRZ_E_INVALID, "srz_frameset_allgather_sparse: misaligned buffer");
+  if (c->world == 1) return SRZ_OK; // one rank: its shard is the whole buffer
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const size_t slot = srz_comm::SPARSE_SLOT, W = (size_t)c->world;
+  if (!c->d_sizes) {
+    HIP_TRY(ctx, hipMalloc(&c->d_sizes, slot * W));
+    HIP_TRY(ctx, hipHostMalloc(&c->h_sizes, slot * W, hipHostMallocDefault));
+  }
+  // 1. every rank's header and recv_bytes.  (h_sizes is free: the previous call synchronised the stream after its last use)
+  uint8_t *mine = c->d_sizes + slot * (size_t)c->rank;
+  std::memcpy(c->h_sizes + slot * (size_t)c->rank + SPARSE_HEADER, &recv_bytes, sizeof recv_bytes);
+  HIP_TRY(ctx, hipMemcpyAsync(mine, d_msg, SPARSE_HEADER, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(ctx, hipMemcpyAsync(mine + SPARSE_HEADER, c->h_sizes + slot * (size_t)c->rank + SPARSE_HEADER, sizeof recv_bytes, hipMemcpyHostToDevice, s));
+  int rc = rccl().AllGather(mine, c->d_sizes, slot, /* ncclUint8 */ 1, c->comm, s);
+  if (rc != 0) return fail(ctx, SRZ_E_NODEVICE, "ncclAllGather (message sizes): " + rccl_err(rc));
+  // 2. the call's one blocking point: the host needs M, the largest message, to size the padded all-gather
+  HIP_TRY(ctx, hipMemcpyAsync(c->h_sizes, c->d_sizes, slot * W, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  uint64_t m = 0, min_recv = ~0ull;
+  int short_rank = -1;
+  for (size_t r = 0; r < W; ++r) {
+    uint64_t b = 0, rb = 0;
+    std::memcpy(&b, c->h_sizes + slot * r + 8, sizeof b);
+    std::memcpy(&rb, c->h_sizes + slot * r + SPARSE_HEADER, sizeof rb);
+    m = std::max(m, b);
+    if (rb < min_recv) min_recv = rb, short_rank = (int)r;
+  }
+  m = (m + 15u) & ~(uint64_t)15u;
+  const size_t cap = srz_frameset_sparse_capacity(ctx, fs, what);
+  // every rank sees the same numbers and takes the same branch: no rank fails alone between the two collectives
+  if (m > cap || m < sparse_args(fs, what).payload_off)
+    return fail(ctx, SRZ_E_INVALID, "srz_frameset_allgather_sparse: a message header announces " + std::to_string(m) +
+                                        " bytes (capacity " + std::to_string(cap) + "): not a message of this frameset");
+  if (min_recv < W * m)
+    return fail(ctx, SRZ_E_NOMEM, "srz_frameset_allgather_sparse: rank " + std::to_string(short_rank) + " has a receive buffer of " +
+                                      std::to_string(min_recv) + " bytes, " + std::to_string(W * m) + " needed (world x the largest message, " +
+                                      std::to_string(m) + " bytes)");
+  // 3. M bytes of every rank's message (d_msg holds the capacity, which is >= M), then the peers' tiles into d_gathered
+  rc = rccl().AllGather(d_msg, d_recv, (size_t)m, /* ncclUint8 */ 1, c->comm, s);
+  if (rc != 0) return fail(ctx, SRZ_E_NODEVICE, "ncclAllGather (messages): " + rccl_err(rc));
+  return srz_frameset_sparse_unpack(ctx, fs, d_recv, (size_t)m, d_gathered, what, stream);
 }
 
 /* Page-locks `bytes` of the caller's memory at `ptr` (hipHostRegister): planes inside a registered range move between host and

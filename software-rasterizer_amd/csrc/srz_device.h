@@ -223,6 +223,24 @@ void launch_resolve8(const float *planes, uint8_t *out, uint32_t n_frames, uint3
                      hipStream_t s);
 void launch_deinterleave(const void *gathered, void *full, uint32_t world, uint32_t n_fp, uint32_t bands_per_rank, uint32_t row_bytes,
                          hipStream_t s);
+// ---- tile-sparse exchange (srz_frameset_sparse_*, message format: include/srz.h) -------------------------------------------------
+constexpr uint32_t SPARSE_HEADER = 16;          // {touched tiles u32, table entries u32, message bytes u64}
+constexpr uint32_t SPARSE_NONE = 0xffffffffu;   // table entry of a tile that is not in the payload (the clear values)
+constexpr uint32_t SPARSE_UNPACK_WGS = 2048;    // k_sparse_unpack's grid (SRZ_UNPACK_WGS overrides it: tools/sparse_exchange_probe.py)
+struct SparseArgs {
+  const void *shard;            // pack: this rank's shard [frame][plane][local_rows][row bytes]
+  uint8_t *msg;                 // pack: the message
+  const uint2 *tile_info;       // pack: k_bin's [frame][n_local_bands][tiles_x] (.x = triangles whose bbox reaches the tile)
+  const FrameDesc *frames;      // pack: FrameDesc::flags of the render the tile counts belong to
+  uint32_t *row_cnt;            // pack: scratch, one word per (frame, local band): touched tiles, then their first slot
+  uint32_t flags_or;            // pack: that render's flags
+  uint32_t n_frames, n_local_bands, bands_per_rank, tiles_x;
+  uint32_t width, height, local_rows, rank, world;
+  uint32_t planes, row_bytes, px_bytes; // 4 float planes (16 B / px in total) or one 8-bit BGR plane (3 B / px)
+  uint64_t payload_off;         // bytes in front of the payload (header + table, 16-byte aligned)
+};
+void launch_sparse_pack(const SparseArgs &a, hipStream_t s);
+void launch_sparse_unpack(const SparseArgs &a, const void *recv, uint64_t msg_stride, void *gathered, uint32_t wgs, hipStream_t s);
 void launch_verify_fastmath(unsigned long long *d_out4, hipStream_t s);
 void launch_verify_fastdiv(unsigned long long *d_out3, hipStream_t s);
 void launch_verify_fastpow(unsigned long long *d_out3, float p, hipStream_t s);

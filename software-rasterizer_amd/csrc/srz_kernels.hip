@@ -2781,6 +2781,157 @@ void launch_deinterleave(const void *gathered, void *full, uint32_t world, uint3
                        band_units);
 }
 
+// ================================================================================================================
+// The tile-sparse exchange (srz_frameset_sparse_*; message format in include/srz.h).  A rank sends only the 32x32 tiles its
+// render drew into; every other tile of its shard holds the clear values bit for bit, and the receivers write those themselves.
+//   k_sparse_count  one wave per (frame, local band): touched tiles of the band
+//   k_sparse_scan   one workgroup: exclusive scan of those counts = every band's first slot; the message header
+//   k_sparse_pack   one workgroup per tile: its table entry (band's first slot + touched tiles left of it: a count, no atomics —
+//                   two packs of one render give the same bytes) and, if touched, the tile's planes into its payload slot
+//   k_sparse_unpack every peer's shard from its message: payload tiles copied, the others written with the clear values
+// Units U (16, 4 or 1 bytes) never straddle a tile column or a row end: the launchers pick the largest one the row bytes and the
+// buffers' alignment allow (16-B rows of float planes of any W % 4 == 0 width; 8-bit rows of W % 16 == 0).
+// ================================================================================================================
+// "touched" = k_clear's test for a tile it does NOT clear, copied: k_clear is tuned and stays as it is, and
+// tests/test_sparse_exchange.py pins the two texts to each other.  A frame whose render was not a fused clear keeps the caller's
+// old contents in the tiles no bbox reached: every tile of it counts as touched.
+__device__ __forceinline__ bool sparse_touched(const SparseArgs &a, uint32_t f, uint32_t lb, uint32_t tx) {
+  if (lb >= a.n_local_bands) return false; // (a padding band of this shard: no rows behind it)
+  const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+  if (!((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR)) return true;
+  const SRZ_CAS u32x2 *cnt = as_const(reinterpret_cast<const u32x2 *>(a.tile_info)) + ((size_t)f * a.n_local_bands + lb) * a.tiles_x;
+  return cnt[tx].x != 0u;
+}
+template <typename U> __device__ __forceinline__ U sparse_clear(bool z) {
+  const uint32_t v = z ? 0x7f800000u : 0u; // (z = +inf, colour 0; the 8-bit image's clear is 0, and it is the only plane of byte units)
+  if constexpr (std::is_same<U, u32x4>::value) return U{v, v, v, v};
+  else if constexpr (std::is_same<U, uint32_t>::value) return v;
+  else return (U)0;
+}
+__global__ __launch_bounds__(256) void k_sparse_count(SparseArgs a) {
+  const uint32_t lane = threadIdx.x & 63u, r = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (r >= a.n_frames * a.bands_per_rank) return; // (whole waves)
+  const uint32_t f = r / a.bands_per_rank, lb = r % a.bands_per_rank;
+  uint32_t n = 0;
+  for (uint32_t x0 = 0; x0 < a.tiles_x; x0 += 64u)
+    n += (uint32_t)__builtin_popcountll(__ballot(x0 + lane < a.tiles_x && sparse_touched(a, f, lb, x0 + lane)));
+  if (lane == 0) a.row_cnt[r] = n;
+}
+__global__ __launch_bounds__(1024) void k_sparse_scan(SparseArgs a) {
+  __shared__ uint32_t s_w[16];
+  const uint32_t n_rows = a.n_frames * a.bands_per_rank, t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+  uint32_t carry = 0;
+  for (uint32_t r0 = 0; r0 < n_rows; r0 += 1024u) {
+    const uint32_t r = r0 + t, v = r < n_rows ? a.row_cnt[r] : 0u, incl = wave_scan_add(v);
+    if (lane == 63u) s_w[wave] = incl;
+    __syncthreads();
+    uint32_t before = carry, total = 0;
+    for (uint32_t w = 0; w < 16u; ++w) before += w < wave ? s_w[w] : 0u, total += s_w[w];
+    if (r < n_rows) a.row_cnt[r] = before + incl - v;
+    carry += total;
+    __syncthreads(); // (s_w is rewritten by the next chunk)
+  }
+  uint32_t *h = reinterpret_cast<uint32_t *>(a.msg);
+  for (uint64_t w = 4u + (uint64_t)n_rows * a.tiles_x + t; w < a.payload_off / 4u; w += 1024u) h[w] = 0u; // (the table's padding: 0)
+  if (t == 0) {
+    const uint64_t tile_bytes = (uint64_t)a.planes * BAND * TILE * a.px_bytes;
+    h[0] = carry, h[1] = n_rows * a.tiles_x;
+    *reinterpret_cast<uint64_t *>(h + 2) = a.payload_off + (uint64_t)carry * tile_bytes;
+  }
+}
+template <typename U>
+__global__ __launch_bounds__(256) void k_sparse_pack(SparseArgs a) {
+  const uint32_t i = blockIdx.x, tx = i % a.tiles_x, r = i / a.tiles_x;
+  const uint32_t f = r / a.bands_per_rank, lb = r % a.bands_per_rank;
+  uint32_t before = 0; // touched tiles left of this one in its band
+  for (uint32_t x0 = 0; x0 < tx; x0 += 256u) before += (uint32_t)__syncthreads_count(x0 + threadIdx.x < tx && sparse_touched(a, f, lb, x0 + threadIdx.x));
+  const bool mine = sparse_touched(a, f, lb, tx);
+  const uint32_t slot = a.row_cnt[r] + before;
+  if (threadIdx.x == 0) reinterpret_cast<uint32_t *>(a.msg + SPARSE_HEADER)[i] = mine ? slot : SPARSE_NONE;
+  if (!mine) return;
+  const uint32_t band = (uint32_t)band_of((int)lb, (int)a.rank, (int)a.world), rows = min((uint32_t)BAND, a.height - band * BAND);
+  const uint32_t tru = TILE * a.px_bytes / (uint32_t)sizeof(U), row_units = a.row_bytes / (uint32_t)sizeof(U);
+  const uint32_t x_units = tx * tru, cols = min(tru, row_units - x_units); // units of the tile's rows that are pixels of the frame
+  const U *src = reinterpret_cast<const U *>(a.shard) + ((size_t)f * a.planes * a.local_rows + (size_t)lb * BAND) * row_units + x_units;
+  const uint32_t per_plane = BAND * tru, n = a.planes * per_plane;
+  U *dst = reinterpret_cast<U *>(a.msg + a.payload_off) + (size_t)slot * n;
+  for (uint32_t k0 = threadIdx.x; k0 < n; k0 += 4u * 256u) { // [plane][32 rows][tile row]: coalesced stores, four loads in flight
+    U v[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) {
+      const uint32_t k = k0 + j * 256u, pl = k / per_plane, rem = k - pl * per_plane, ly = rem / tru, u = rem - ly * tru;
+      v[j] = (k < n && ly < rows && u < cols) ? src[((size_t)pl * a.local_rows + ly) * row_units + u] : sparse_clear<U>(false); // (edge padding: 0)
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j)
+      if (k0 + j * 256u < n) dst[k0 + j * 256u] = v[j];
+  }
+}
+// One work item = one plane of one local band of one frame of one peer, written ROW-MAJOR like k_clear: a thread takes one unit
+// column of the band and stores it in every row of the band (32 stores in flight), so runs of clear tiles and copied tiles alike
+// become long contiguous bursts of the destination.  It writes only pixels: rows that exist, x < W.
+template <typename U>
+__global__ __launch_bounds__(256) void k_sparse_unpack(SparseArgs a, const uint8_t *recv, uint64_t stride, U *gathered) {
+  const uint32_t P = a.planes, bpr = a.bands_per_rank, n_items = (a.world - 1u) * a.n_frames * bpr * P;
+  const uint32_t n_bands = (a.height + BAND - 1) / BAND;
+  const uint32_t tru = TILE * a.px_bytes / (uint32_t)sizeof(U), row_units = a.row_bytes / (uint32_t)sizeof(U), per_plane = BAND * tru;
+  const uint64_t shard_units = (uint64_t)a.n_frames * P * a.local_rows * row_units;
+  for (uint32_t it = blockIdx.x; it < n_items; it += gridDim.x) { // it = ((q * n_frames + f) * bpr + lb) * P + pl
+    const uint32_t pl = it % P, lb = (it / P) % bpr, f = (it / (P * bpr)) % a.n_frames, q = it / (P * bpr * a.n_frames);
+    const uint32_t p = q + (q >= a.rank ? 1u : 0u); // (the peers: every rank but this one)
+    const uint32_t band = (uint32_t)band_of((int)lb, (int)p, (int)a.world);
+    if (band >= n_bands) continue;
+    const uint32_t rows = min((uint32_t)BAND, a.height - band * BAND);
+    const uint8_t *m = recv + (uint64_t)p * stride;
+    const SRZ_CAS uint32_t *table = as_const(reinterpret_cast<const uint32_t *>(m + SPARSE_HEADER)) + ((size_t)f * bpr + lb) * a.tiles_x;
+    const U *payload = reinterpret_cast<const U *>(m + a.payload_off) + (size_t)pl * per_plane;
+    U *dst = gathered + p * shard_units + ((size_t)(f * P + pl) * a.local_rows + (size_t)lb * BAND) * row_units;
+    const U clear = sparse_clear<U>(P == 4u && pl == 0u);
+    for (uint32_t u = threadIdx.x; u < row_units; u += blockDim.x) {
+      const uint32_t tx = u / tru, slot = table[tx];
+      if (slot == SPARSE_NONE) {
+        for (uint32_t ly = 0; ly < rows; ++ly) __builtin_nontemporal_store(clear, dst + (size_t)ly * row_units + u);
+      } else {
+        const U *src = payload + (size_t)slot * P * per_plane + (u - tx * tru);
+        uint32_t ly = 0;
+        for (; ly + 8u <= rows; ly += 8u) { // (eight loads in flight before the stores that depend on them)
+          U v[8];
+#pragma unroll
+          for (uint32_t j = 0; j < 8u; ++j) v[j] = __builtin_nontemporal_load(src + (ly + j) * tru);
+#pragma unroll
+          for (uint32_t j = 0; j < 8u; ++j) __builtin_nontemporal_store(v[j], dst + (size_t)(ly + j) * row_units + u);
+        }
+        for (; ly < rows; ++ly) __builtin_nontemporal_store(__builtin_nontemporal_load(src + ly * tru), dst + (size_t)ly * row_units + u);
+      }
+    }
+  }
+}
+namespace {
+uint32_t sparse_unit(uint32_t row_bytes, uintptr_t al) {
+  return ((row_bytes & 15u) == 0 && (al & 15u) == 0) ? 16u : ((row_bytes & 3u) == 0 && (al & 3u) == 0) ? 4u : 1u;
+}
+} // namespace
+void launch_sparse_pack(const SparseArgs &a, hipStream_t s) {
+  const uint32_t n_rows = a.n_frames * a.bands_per_rank, n_tab = n_rows * a.tiles_x;
+  if (n_rows) hipLaunchKernelGGL(k_sparse_count, dim3((n_rows + 3) / 4), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_sparse_scan, dim3(1), dim3(1024), 0, s, a); // (also the header of an empty set)
+  if (!n_tab) return;
+  const uint32_t unit = sparse_unit(a.row_bytes, (uintptr_t)a.shard | (uintptr_t)a.msg);
+  if (unit == 16u) hipLaunchKernelGGL(k_sparse_pack<u32x4>, dim3(n_tab), dim3(256), 0, s, a);
+  else if (unit == 4u) hipLaunchKernelGGL(k_sparse_pack<uint32_t>, dim3(n_tab), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_sparse_pack<uint8_t>, dim3(n_tab), dim3(256), 0, s, a);
+}
+void launch_sparse_unpack(const SparseArgs &a, const void *recv, uint64_t msg_stride, void *gathered, uint32_t wgs, hipStream_t s) {
+  const uint32_t n_items = (a.world - 1u) * a.n_frames * a.bands_per_rank * a.planes;
+  if (!n_items) return;
+  const uint32_t grid = std::min(n_items, wgs ? wgs : SPARSE_UNPACK_WGS);
+  const uint32_t unit = sparse_unit(a.row_bytes, (uintptr_t)recv | (uintptr_t)gathered | (uintptr_t)msg_stride);
+  const uint8_t *m = static_cast<const uint8_t *>(recv);
+  if (unit == 16u) hipLaunchKernelGGL(k_sparse_unpack<u32x4>, dim3(grid), dim3(256), 0, s, a, m, msg_stride, static_cast<u32x4 *>(gathered));
+  else if (unit == 4u) hipLaunchKernelGGL(k_sparse_unpack<uint32_t>, dim3(grid), dim3(256), 0, s, a, m, msg_stride, static_cast<uint32_t *>(gathered));
+  else hipLaunchKernelGGL(k_sparse_unpack<uint8_t>, dim3(grid), dim3(256), 0, s, a, m, msg_stride, static_cast<uint8_t *>(gathered));
+}
+
 // Exhaustive check of the short exact sequences above against the IEEE expansions: all 2^32 bit patterns.
 // out[0] = operands tested on the fast path, out[1..3] = mismatches of rcp_rn / sqrt_rn / rsqrt2_rn (must be 0).
 __global__ void k_verify_fastmath(unsigned long long *out) {

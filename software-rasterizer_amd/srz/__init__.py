@@ -21,7 +21,8 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_kernel_time_ms", "srz_kernel_time_samples", "srz_set_kernel_timing", "srz_sync", "srz_debug_counters", "srz_verify_fastmath", "srz_verify_fastdiv", "srz_verify_fastpow", "srz_verify_fastlen", "srz_host_register", "srz_host_unregister", "srz_frameset_debug_counters", "srz_draw_batch",
            "srz_comm_unique_id", "srz_comm_create", "srz_comm_destroy", "srz_frameset_exchange_bytes", "srz_frameset_allgather",
            "srz_frameset_deinterleave", "srz_frameset_allgather_inplace", "srz_frameset_gathered_row_offset",
-           "srz_frameset_read_gathered_frame"]
+           "srz_frameset_read_gathered_frame", "srz_frameset_sparse_capacity", "srz_frameset_sparse_pack", "srz_frameset_sparse_unpack",
+           "srz_frameset_allgather_sparse"]
 
 
 class SrzError(RuntimeError):
@@ -93,6 +94,11 @@ def lib():
         L.srz_frameset_gathered_row_offset.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
         L.srz_frameset_gathered_row_offset.restype = C.c_size_t
         L.srz_frameset_read_gathered_frame.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
+        L.srz_frameset_sparse_capacity.argtypes = [vp, vp, C.c_int]
+        L.srz_frameset_sparse_capacity.restype = C.c_size_t
+        L.srz_frameset_sparse_pack.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_int, vp]
+        L.srz_frameset_sparse_unpack.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int, vp]
+        L.srz_frameset_allgather_sparse.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_int, vp]
         _lib = L
     return _lib
 
@@ -177,6 +183,27 @@ class FrameSet:
     def deinterleave(self, d_gathered_ptr, d_full_ptr, what=abi.EXCHANGE_PLANES, stream=None):
         self.ctx._check(lib().srz_frameset_deinterleave(self.ctx.h, self.h, C.c_void_p(d_gathered_ptr), C.c_void_p(d_full_ptr), what,
                                                         _stream(stream)))
+
+    def sparse_capacity(self, what=abi.EXCHANGE_PLANES):
+        """bytes of this rank's largest tile-sparse message (every tile touched): the size of the message buffer"""
+        return int(lib().srz_frameset_sparse_capacity(self.ctx.h, self.h, what))
+
+    def sparse_pack(self, d_shard_ptr, d_msg_ptr, msg_bytes, what=abi.EXCHANGE_PLANES, stream=None):
+        """this rank's tile-sparse message from its shard (format: include/srz.h); enqueue it after the render, before the set's
+        next render.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_sparse_pack(self.ctx.h, self.h, C.c_void_p(d_shard_ptr), C.c_void_p(d_msg_ptr), msg_bytes, what,
+                                                       _stream(stream)))
+
+    def sparse_unpack(self, d_recv_ptr, msg_stride, d_gathered_ptr, what=abi.EXCHANGE_PLANES, stream=None):
+        """every other rank's shard of a rank-major gathered buffer from its message at d_recv + rank * msg_stride.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_sparse_unpack(self.ctx.h, self.h, C.c_void_p(d_recv_ptr), msg_stride, C.c_void_p(d_gathered_ptr),
+                                                         what, _stream(stream)))
+
+    def allgather_sparse(self, comm, d_msg_ptr, d_recv_ptr, recv_bytes, d_gathered_ptr, what=abi.EXCHANGE_PLANES, stream=None):
+        """the tile-sparse exchange over RCCL (sizes all-gather, one host synchronisation, padded all-gather of the messages,
+        unpack): the same result as allgather_inplace.  SrzError SRZ_E_NOMEM on EVERY rank when some rank's recv_bytes is short."""
+        self.ctx._check(lib().srz_frameset_allgather_sparse(self.ctx.h, comm.h, self.h, C.c_void_p(d_msg_ptr), C.c_void_p(d_recv_ptr), recv_bytes,
+                                                            C.c_void_p(d_gathered_ptr), what, _stream(stream)))
 
     def stats(self):
         st = abi.SrzStats()

@@ -83,6 +83,139 @@ def all_gather_frames(shard, world, gathered, full=None, group=None):
     return deinterleave(gathered, world, full)
 
 
+# ---- the tile-sparse exchange (srz_frameset_sparse_*; the message format is documented in include/srz.h) -------------------------
+# The torch formulation of the format: what k_sparse_pack / k_sparse_unpack compute, as parallel.deinterleave is k_deinterleave's.
+# Shards are [frames, planes, local_rows, row elements]: float32 [F, 4, rows, W] (SRZ_EXCHANGE_PLANES) or uint8 [F, 1, rows, 3 W]
+# (SRZ_EXCHANGE_BGR8); messages are uint8 tensors.
+TILE = 32
+SPARSE_HEADER, SPARSE_NONE = 16, 0xFFFFFFFF
+
+
+def sparse_layout(n_frames, bands_per_rank, width, planes=4):
+    """sizes of a message: tiles_x, table entries n_tab, payload_off (header + table, 16-byte aligned), tile_bytes, capacity (every
+    tile touched = srz_frameset_sparse_capacity)"""
+    tiles_x = (width + TILE - 1) // TILE
+    n_tab = n_frames * bands_per_rank * tiles_x
+    payload_off = (SPARSE_HEADER + 4 * n_tab + 15) // 16 * 16
+    tile_bytes = planes * BAND * TILE * (4 if planes == 4 else 3)
+    return {"tiles_x": tiles_x, "n_tab": n_tab, "payload_off": payload_off, "tile_bytes": tile_bytes,
+            "capacity": payload_off + n_tab * tile_bytes}
+
+
+def _shard_bytes(shard):
+    """→ (uint8 view [F, P, rows, row bytes], bytes per pixel of a plane)"""
+    import torch
+    px = 3 if shard.dtype == torch.uint8 else 4
+    f, p, rows = shard.shape[:3]
+    return shard.contiguous().view(torch.uint8).reshape(f, p, rows, -1), px
+
+
+def _clear_rows(planes, row_bytes, device):
+    """[P, 1, row_bytes] bytes of a cleared row: z = +inf, colour 0 (the 8-bit image: 0)"""
+    import torch
+    c = torch.zeros((planes, 1, row_bytes), dtype=torch.uint8, device=device)
+    if planes == 4:
+        c[0, 0] = torch.full((row_bytes // 4,), float("inf"), dtype=torch.float32, device=device).view(torch.uint8)
+    return c
+
+
+def _bands_per_rank(height, world):
+    return (((height + BAND - 1) // BAND) + world - 1) // world
+
+
+def nonclear_tiles(shard, rank, world, height):
+    """bool [F, bands_per_rank, tiles_x]: tiles of the shard with a pixel that is not the clear value (the smallest valid touched set)"""
+    import torch
+    b, px = _shard_bytes(shard)
+    f, p, rows, row_bytes = b.shape
+    bpr, tx = _bands_per_rank(height, world), (row_bytes // px + TILE - 1) // TILE
+    diff = torch.zeros((f, p, bpr * BAND, tx * TILE * px), dtype=torch.bool, device=shard.device)
+    ne = b != _clear_rows(p, row_bytes, shard.device)
+    for (lb, _, r0, r1) in band_rows(height, rank, world):
+        diff[:, :, lb * BAND: lb * BAND + r1 - r0, :row_bytes] = ne[:, :, lb * BAND: lb * BAND + r1 - r0]
+    return diff.view(f, p, bpr, BAND, tx, TILE * px).any(dim=5).any(dim=3).any(dim=1)
+
+
+def sparse_pack(shard, touched, world, rank, height):
+    """this rank's message (uint8, exactly message-bytes long): header, table, the touched tiles in table order.  touched: bool
+    [F, bands_per_rank, tiles_x] — any superset of nonclear_tiles() reassembles the same frames; bands the rank does not have are
+    never sent"""
+    import torch
+    b, px = _shard_bytes(shard)
+    f, p, rows, row_bytes = b.shape
+    bpr = _bands_per_rank(height, world)
+    lay = sparse_layout(f, bpr, row_bytes // px, p)
+    tx, tb = lay["tiles_x"], lay["tile_bytes"]
+    tiles = torch.zeros((f, p, bpr * BAND, tx * TILE * px), dtype=torch.uint8, device=shard.device)
+    t = torch.zeros((f, bpr, tx), dtype=torch.bool, device=shard.device)
+    for (lb, _, r0, r1) in band_rows(height, rank, world):
+        tiles[:, :, lb * BAND: lb * BAND + r1 - r0, :row_bytes] = b[:, :, lb * BAND: lb * BAND + r1 - r0]
+        t[:, lb] = touched[:, lb].to(torch.bool)
+    tiles = tiles.view(f, p, bpr, BAND, tx, TILE * px).permute(0, 2, 4, 1, 3, 5).reshape(-1, tb)  # [F][lb][tx] x tile bytes
+    flat = t.reshape(-1)
+    n_t = int(flat.sum())
+    table = torch.where(flat, torch.cumsum(flat.to(torch.int64), 0) - 1, torch.full_like(flat, -1, dtype=torch.int64)).to(torch.int32)
+    msg = torch.zeros(lay["payload_off"] + n_t * tb, dtype=torch.uint8, device=shard.device)
+    msg[0:8] = torch.tensor([n_t, lay["n_tab"]], dtype=torch.int32).view(torch.uint8).to(shard.device)
+    msg[8:16] = torch.tensor([msg.numel()], dtype=torch.int64).view(torch.uint8).to(shard.device)
+    msg[SPARSE_HEADER: SPARSE_HEADER + 4 * lay["n_tab"]] = table.view(torch.uint8)
+    msg[lay["payload_off"]:] = tiles[flat].reshape(-1)
+    return msg
+
+
+def sparse_header(msg):
+    """(touched tiles, table entries, message bytes) of a message"""
+    import numpy as np
+    h = np.frombuffer(bytes(msg[:SPARSE_HEADER].cpu().numpy()), dtype="<u4")
+    return int(h[0]), int(h[1]), int(h[2]) | int(h[3]) << 32
+
+
+def sparse_unpack(messages, gathered, rank, world, height):
+    """gathered: rank-major [world, F, P, local_rows, row elements] whose slot `rank` holds this rank's shard; messages[p]: rank p's
+    message (a uint8 tensor, or a row of the padded all-gather).  Fills every other rank's slot, real pixels only."""
+    import torch
+    w_, f, p, rows = gathered.shape[:4]
+    assert w_ == world
+    px = 3 if gathered.dtype == torch.uint8 else 4
+    g = gathered.view(torch.uint8).reshape(world, f, p, rows, -1)
+    row_bytes = g.shape[-1]
+    bpr = _bands_per_rank(height, world)
+    lay = sparse_layout(f, bpr, row_bytes // px, p)
+    tx, tb, off = lay["tiles_x"], lay["tile_bytes"], lay["payload_off"]
+    clear = _clear_rows(p, TILE * px, gathered.device).expand(p, BAND, TILE * px)
+    for q in range(world):
+        if q == rank:
+            continue
+        m = messages[q]
+        n_t, n_tab, _ = sparse_header(m)
+        assert n_tab == lay["n_tab"], (n_tab, lay)
+        table = m[SPARSE_HEADER: SPARSE_HEADER + 4 * n_tab].clone().view(torch.int32).reshape(f, bpr, tx)
+        payload = m[off: off + n_t * tb].reshape(n_t, p, BAND, TILE * px)
+        tiles = clear.expand(f, bpr, tx, p, BAND, TILE * px).clone()
+        sel = table >= 0
+        tiles[sel] = payload[table[sel].long()]
+        full = tiles.permute(0, 3, 1, 4, 2, 5).reshape(f, p, bpr * BAND, tx * TILE * px)
+        for (lb, _, r0, r1) in band_rows(height, q, world):
+            g[q, :, :, lb * BAND: lb * BAND + r1 - r0] = full[:, :, lb * BAND: lb * BAND + r1 - r0, :row_bytes]
+    return gathered
+
+
+def all_gather_sparse(msg, gathered, rank, world, height, group=None):
+    """the protocol of srz_frameset_allgather_sparse on any torch.distributed backend: all-gather of the headers, M = the largest
+    message (rounded up to 16), padded all-gather of M bytes per rank, unpack.  → (gathered, M)"""
+    import torch
+    import torch.distributed as dist
+    hdr = torch.empty((world, SPARSE_HEADER), dtype=torch.uint8, device=msg.device)
+    dist.all_gather_into_tensor(hdr.view(-1), msg[:SPARSE_HEADER].contiguous(), group=group)
+    m = max(sparse_header(hdr[r])[2] for r in range(world))
+    m = (m + 15) // 16 * 16
+    send = torch.zeros(m, dtype=torch.uint8, device=msg.device)
+    send[:msg.numel()] = msg[:m]
+    recv = torch.empty((world, m), dtype=torch.uint8, device=msg.device)
+    dist.all_gather_into_tensor(recv.view(-1), send, group=group)
+    return sparse_unpack(recv, gathered, rank, world, height), m
+
+
 class TorchQueue:
     """An in-order device queue for ExchangePipeline: a torch (HIP) stream."""
 
