@@ -45,6 +45,7 @@ extern "C" {
  *      back while the next one renders
  *      (additive, same version: no existing signature, struct or meaning changed) the tile-sparse exchange srz_frameset_sparse_capacity /
  *      _sparse_pack / _sparse_unpack, srz_frameset_allgather_sparse
+ *      (additive, same version) the visibility buffer srz_frameset_render_visibility
  */
 #define SRZ_ABI_VERSION 7
 
@@ -244,6 +245,26 @@ int srz_frameset_local_rows(const srz_ctx *ctx, const srz_frameset *fs);
 size_t srz_frameset_out_bytes(const srz_ctx *ctx, const srz_frameset *fs);
 int srz_frameset_render(srz_ctx *ctx, srz_frameset *fs, void *d_out, size_t out_bytes,
                         uint32_t flags, void *stream);
+/* The VISIBILITY BUFFER instead of the shaded image: which triangle owns each pixel and where inside it the pixel lies.  Same
+ * arguments, flag mask, stream semantics, buffer size (srz_frameset_out_bytes), local_rows and band sharding as srz_frameset_render;
+ * framesets and scenesets alike.  The buffer is [frame][4 planes][local_rows][width], 4 bytes per word:
+ *     plane 0  z      float32  the owner fragment's depth, bit-identical to plane 0 of srz_frameset_render   (nobody: +inf)
+ *     plane 1  id     uint32   (triangle index + 1) | (S class ? 0x80000000 : 0)                                (nobody: 0)
+ *     plane 2  alpha  float32  the owner's barycentric alpha, exactly as the shaders use it                     (nobody: 0)
+ *     plane 3  beta   float32  the owner's beta, likewise                                                       (nobody: 0)
+ * "nobody" = a pixel no triangle owns in a frame rendered with SRZ_FUSED_CLEAR (frame flags | render flags).
+ * Triangle index: the position in the FRAME's own triangle stream — its batches in array order, culled triangles counted; for a
+ * sceneset its draws in order, n_faces records each — not in the frameset-wide array.
+ * alpha / beta (the oracle's values): V class (the 8-wide columns of the owner's bounding box) alpha = fmsub(PBx,PCy,PCx*PBy) * RN(1/area_v),
+ * S class (the scalar tail) alpha = aPBC / s_area with the IEEE division; beta likewise.  gamma is not stored: 1 - (alpha + beta) for V,
+ * (1 - alpha) - beta for S, as the shaders compute it (the class bit says which).  Exact in every mode: SRZ_OPT_APPROX_SHADE has no
+ * effect here.  SRZ_UNIFIED (every pixel V class) and SRZ_ORDERED_RASTER mean what they mean for the colour render.
+ * Without SRZ_FUSED_CLEAR the call changes exactly the pixels the colour render would change: a pixel whose incoming value survives
+ * keeps all four of its words (two visibility renders can be layered).
+ * The "nobody" words are the clear values of the exchange (z = +inf, three zero words), so a visibility buffer goes through
+ * srz_frameset_allgather / _allgather_inplace / _deinterleave / _read_gathered_frame and the tile-sparse exchange unchanged, as
+ * SRZ_EXCHANGE_PLANES.  No texture has to be uploaded; the render files no sample of the side clear's grid measurement. */
+int srz_frameset_render_visibility(srz_ctx *ctx, srz_frameset *fs, void *d_out, size_t out_bytes, uint32_t flags, void *stream);
 /* display()'s resolve on the device (cv::merge + convertTo(CV_8UC3), src/Render.cpp:61-62): the three colour planes of
  * a rendered buffer (layout of srz_frameset_render) → interleaved 8-bit [frame][local_rows][width][3], round half to even,
  * saturate.  Asynchronous on `stream`.  Any width (sizes whose plane is not a multiple of 4 pixels take a one-pixel-per-thread kernel). */

@@ -410,18 +410,20 @@ int collect_events(srz_ctx *ctx) {
 // of the tile-list pool by their demand, nothing rasterised, no texture needed yet)
 // (f_begin, f_count: only frames [f_begin, f_begin + f_count) of the set — srz_draw_batch renders a set in pieces so that the
 // read-back of one piece runs under the render of the next; d_out is the whole set's buffer either way)
+// (visibility: srz_frameset_render_visibility — k_visibility writes the visibility buffer where k_shade would write colour; no texture
+// is needed, and the render files no sample of the side clear's grid measurement)
 int render_impl(srz_ctx *ctx, srz_frameset *fs, float *d_out, uint32_t flags_or, hipStream_t s, bool stats, bool one_frame_scratch = false,
-                bool size_only = false, int f_begin = 0, int f_count = -1) {
+                bool size_only = false, int f_begin = 0, int f_count = -1, bool visibility = false) {
   if (fs->shard_rank != ctx->shard_rank || fs->shard_world != ctx->shard_world)
     return fail(ctx, SRZ_E_INVALID, "frameset was created under a different shard (call srz_set_shard before srz_frameset_create)");
   if (fs->update_failed) return fail(ctx, SRZ_E_NOMEM, "the last update of this set failed (out of memory): update it again or destroy it");
   for (const BatchDesc &b : fs->h_batches) {
-    if (size_only) break;
+    if (size_only || visibility) break;
     bool needs = b.shader == SRZ_SHADER_TEXTURE || b.shader == SRZ_SHADER_DISPLACEMENT || b.shader == SRZ_SHADER_BUMP;
     if (needs && (b.tex_id < 0 || b.tex_id >= MAX_TEX || !ctx->h_tex[b.tex_id].bgrx))
       return fail(ctx, SRZ_E_TEXTURE, "batch uses texture slot " + std::to_string(b.tex_id) + " which was never uploaded");
   }
-  if (!size_only && fs->sdesc_version != ctx->tex_version && !fs->h_batches.empty()) { // (re)resolve batch → shader/texture
+  if (!size_only && !visibility && fs->sdesc_version != ctx->tex_version && !fs->h_batches.empty()) { // (re)resolve batch → shader/texture
     std::vector<ShadeDescG> &h = fs->h_sdesc; // (owned by the set: the asynchronous copy below may read it after we return)
     h.resize(fs->h_batches.size());
     for (size_t i = 0; i < h.size(); ++i) {
@@ -529,8 +531,10 @@ int render_impl(srz_ctx *ctx, srz_frameset *fs, float *d_out, uint32_t flags_or,
   const size_t tpf = (size_t)fs->n_local_bands * fs->tiles_x;
   // the side clear's grid: measured per set, on the device (srz_frameset::ClearTune)
   uint32_t clear_wgs = ctx->env_clear_wgs ? ctx->env_clear_wgs : fs->clear_tune.wgs;
-  bool tune_stamp = false;
-  if (side && !ctx->env_clear_wgs && !ctx->env_no_clear_tune && !stats && f_count < 0 && fs->clear_tune.d_ctl) {
+  bool tune_stamp = false, tune_rebase = false;
+  if (side && visibility && !ctx->env_clear_wgs && fs->clear_tune.d_ctl && !fs->clear_tune.done)
+    tune_rebase = true; // (the grid in effect; the measurement's clock restarts at this render's end: the next colour render's sample is its own)
+  if (side && !visibility && !ctx->env_clear_wgs && !ctx->env_no_clear_tune && !stats && f_count < 0 && fs->clear_tune.d_ctl) {
     srz_frameset::ClearTune &ct = fs->clear_tune;
     if (ct.done && !detailed && ++ct.since >= srz_frameset::CLEAR_TUNE_AGAIN) {
       // what the clear runs beside may have changed (srz_sceneset_update): measure again (<= 18 of 4096 renders)
@@ -649,13 +653,17 @@ int render_impl(srz_ctx *ctx, srz_frameset *fs, float *d_out, uint32_t flags_or,
       ctx->raster_last_stream = s, ctx->raster_valid = true;
     }
     if (detailed) HIP_TRY(ctx, hipEventRecord(ep.t2, s));
-    launch_shade(v, tiles, stats, fs->fast_mask, fs->any_generic, fs->approx_shade, s);
+    if (visibility)
+      launch_visibility(v, tiles, s);
+    else
+      launch_shade(v, tiles, stats, fs->fast_mask, fs->any_generic, fs->approx_shade, s);
     if (side) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join[ev], 0));
     else if (!raster_four_waves(v))
       if (int rc = copy_demand(s)) return rc;
   }
   if (!stats) fs->pool_sized = true;
   if (tune_stamp) launch_clear_tune(fs->clear_tune.d_ctl, fs->clear_tune.h_wgs, s);
+  if (tune_rebase) launch_clear_rebase(fs->clear_tune.d_ctl, s);
   if (timed) {
     HIP_TRY(ctx, hipEventRecord(ep.t3, s));
     ctx->ev_used.push_back(ep);
@@ -1273,6 +1281,17 @@ int srz_frameset_render(srz_ctx *ctx, srz_frameset *fs, void *d_out, size_t out_
   hipStream_t s = pick_stream(ctx, stream);
   flags &= SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER;
   return render_impl(ctx, fs, (float *)d_out, flags, s, false);
+}
+
+int srz_frameset_render_visibility(srz_ctx *ctx, srz_frameset *fs, void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  if (!fs || !d_out) return fail(ctx, SRZ_E_INVALID, "srz_frameset_render_visibility: null frameset / output");
+  if (out_bytes < srz_frameset_out_bytes(ctx, fs)) return fail(ctx, SRZ_E_INVALID, "srz_frameset_render_visibility: output buffer too small");
+  if (((uintptr_t)d_out & 15u) != 0) return fail(ctx, SRZ_E_INVALID, "srz_frameset_render_visibility: output must be 16-byte aligned");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = pick_stream(ctx, stream);
+  flags &= SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER;
+  return render_impl(ctx, fs, (float *)d_out, flags, s, false, false, false, 0, -1, /*visibility=*/true);
 }
 
 int srz_frameset_resolve8(srz_ctx *ctx, const srz_frameset *fs, const void *d_planes, void *d_bgr8, size_t bgr8_bytes, void *stream) {

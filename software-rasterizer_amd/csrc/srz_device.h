@@ -209,6 +209,7 @@ struct ClearCtl {
   float score[CLEAR_CANDS];      // what the decision compared (ticks; 0: dropped after the first pass)
 };
 void launch_clear_tune(ClearCtl *ctl, uint32_t *h_wgs, hipStream_t s);
+void launch_clear_rebase(ClearCtl *ctl, hipStream_t s); // (a render that files no sample: the next one times itself alone)
 
 void launch_vertex(const DrawDesc *draws, uint32_t n_draws, uint32_t max_faces, srz_tri *tris, float *tri_pos, const FrameDesc *frames,
                    BBox *bbox_out, hipStream_t s);
@@ -219,6 +220,8 @@ void launch_raster(const RenderArgs &a, int n_frames, bool stats, hipStream_t s)
 bool raster_four_waves(const RenderArgs &a); // the latency build of k_raster serves this job (it also reports the pool's demand)
 void launch_clear(const RenderArgs &a, uint32_t max_tiles, bool beside_raster, hipStream_t s, uint32_t wgs);
 void launch_shade(const RenderArgs &a, uint32_t max_tiles, bool stats, uint32_t fast_mask, bool any_generic, bool approx, hipStream_t s);
+// the visibility buffer (srz_frameset_render_visibility) in place of launch_shade: planes 1..3 of every owned tile
+void launch_visibility(const RenderArgs &a, uint32_t max_tiles, hipStream_t s);
 void launch_resolve8(const float *planes, uint8_t *out, uint32_t n_frames, uint32_t rows, uint32_t W, uint64_t frame_stride,
                      hipStream_t s);
 void launch_deinterleave(const void *gathered, void *full, uint32_t world, uint32_t n_fp, uint32_t bands_per_rank, uint32_t row_bytes,

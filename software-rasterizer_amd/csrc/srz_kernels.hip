@@ -2685,6 +2685,123 @@ void k_shade(RenderArgs a) {
 }
 
 // ================================================================================================================
+// k_visibility — the VISIBILITY BUFFER in place of the shaded colour (srz_frameset_render_visibility, layout: include/srz.h):
+// plane 1 = owner's index in the frame + 1 | S class << 31 (0 = nobody), planes 2 / 3 = the owner's α / β exactly as k_shade
+// computes them (cover_v with the correctly rounded reciprocal, cover_s with the IEEE division).  Plane 0 is k_raster's.
+// One workgroup per owned tile, walking every work list a render filled (all build kinds, this workgroup's XCD list of each);
+// a thread owns 4 consecutive pixels of one row, so nothing is compacted or staged for the write-out: the three quads leave as
+// 16-byte non-temporal stores straight from registers.  Only the owner's 36 bytes of positions are read (the dense copy), staged
+// in LDS once per tile for lists of up to VIS_STAGE entries whose ids are list positions, gathered per pixel otherwise.  The
+// bound is the memory system: 12 bytes written per pixel of an owned tile + 1 / 2 / 4 bytes of owner ids read.
+// ================================================================================================================
+constexpr uint32_t VIS_STAGE = 256; // one list entry per thread
+__global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
+  __shared__ float s_pos[VIS_STAGE * TRI_POS_F];
+  __shared__ uint32_t s_idx[VIS_STAGE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4, p0 = ly * TILE + lx4;
+  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
+  const uint32_t tpf = a.n_local_bands * a.tiles_x;
+  for (uint32_t kind = 0; kind <= SHADE_KIND_GENERIC; ++kind) {
+    const uint32_t n_work = as_const(a.work_count)[(kind * 8u + sub) * CNT_STRIDE];
+    if (n_work == 0u) continue; // (wave-uniform: kinds no frame of the set needs have no storage slot and count 0)
+    const uint32_t Ls = ((uint32_t)(a.kind_slots >> (4u * kind)) & 15u) * 8u + sub;
+    const SRZ_CAS u32x4 *list = reinterpret_cast<const SRZ_CAS u32x4 *>(as_const(a.worklist)) + (size_t)Ls * a.work_cap;
+    for (uint32_t w = blockIdx.x >> 3; w < n_work; w += step) {
+      const u32x4 x = list[w];
+      const uint32_t f = x.x, lb = x.y & 1023u, tx = (x.y >> 10) & 1023u, cnt = x.z;
+      const bool by_lp = (x.y & WORK_LP) != 0u, lp8 = (x.y & WORK_LP8) != 0u, staged = by_lp && cnt <= VIS_STAGE;
+      const SRZ_CAS uint32_t *tlist = as_const(a.pool) + x.w;
+      // 1. this thread's 4 owner ids, decoded as shade_tile step 1 does
+      const uint32_t *slot = a.vis + (size_t)(f * tpf + lb * a.tiles_x + tx) * PIX_SLOT;
+      uint32_t idk[4];
+      if (lp8) {
+        const uint32_t w4 = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(slot) + p0);
+        idk[0] = w4 & 0xffu, idk[1] = (w4 >> 8) & 0xffu, idk[2] = (w4 >> 16) & 0xffu, idk[3] = w4 >> 24;
+      } else if (by_lp) {
+        const u32x2 w2 = *reinterpret_cast<const u32x2 *>(reinterpret_cast<const uint16_t *>(slot) + p0);
+        idk[0] = w2.x & 0xffffu, idk[1] = w2.x >> 16, idk[2] = w2.y & 0xffffu, idk[3] = w2.y >> 16;
+      } else {
+        const uint4 w4 = *reinterpret_cast<const uint4 *>(slot + p0);
+        idk[0] = w4.x, idk[1] = w4.y, idk[2] = w4.z, idk[3] = w4.w;
+      }
+      const uint32_t none = lp8 ? 0xffu : by_lp ? 0xffffu : NO_TRI, sbit = lp8 ? 0x80u : by_lp ? 0x8000u : S_CLASS_BIT;
+      const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+      const int W = fd->width, H = fd->height;
+      const uint32_t tri_off = fd->tri_off;
+      const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
+      const SRZ_CAS float *tpos = as_const(a.tri_pos) + (size_t)tri_off * a.pos_stride;
+      // 2. a short list's positions → LDS, by list position (one entry per thread)
+      if (staged && (uint32_t)tid < cnt) {
+        const uint32_t idx = tlist[tid] & PACK_IDX_MASK; // (by_lp = FD_PACKED: the entry carries the batch above the index)
+        const SRZ_CAS float *q = tpos + (size_t)idx * a.pos_stride;
+        s_idx[tid] = idx;
+#pragma unroll
+        for (int k = 0; k < (int)TRI_POS_F; ++k) s_pos[tid * TRI_POS_F + k] = q[k];
+      }
+      __syncthreads();
+      const int band = band_of((int)lb, a.shard_rank, a.shard_world);
+      const int tx0 = (int)tx * TILE, ty0 = band * BAND;
+      const int tx1 = min(tx0 + TILE, W) - 1, ty1 = min(ty0 + BAND, H) - 1;
+      const size_t plane = (size_t)a.local_rows * (size_t)W;
+      const int y = ty0 + ly, x4 = tx0 + lx4;
+      const bool in_tile = y <= ty1 && x4 <= tx1;
+      const bool full = in_tile && ((W & 3) == 0) && x4 + 3 <= tx1;
+      float *gz = a.out + (size_t)f * a.frame_stride + ((size_t)lb * BAND + ly) * (size_t)W + x4;
+      float o[3][4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[0][k] = o[1][k] = o[2][k] = 0.f;
+      if (!fused && in_tile) { // accumulate mode: pixels nobody owns keep what the buffer holds
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (x4 + k <= tx1) o[pl][k] = gz[(pl + 1) * plane + k];
+      }
+      // 3. α and β of each owned pixel from its owner's positions
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (idk[k] == none || !in_tile) continue;
+        const bool isS = (idk[k] & sbit) != 0u;
+        const uint32_t pos = idk[k] & ~sbit;
+        TriXY t;
+        uint32_t idx;
+        if (staged) {
+          const float *q = s_pos + pos * TRI_POS_F;
+          idx = s_idx[pos];
+          t.ax = q[0], t.ay = q[1], t.z0 = q[2], t.bx = q[3], t.by = q[4], t.z1 = q[5], t.cx = q[6], t.cy = q[7], t.z2 = q[8];
+        } else {
+          idx = by_lp ? (tlist[pos] & PACK_IDX_MASK) : pos; // (a long list: position → index, then the gather)
+          const SRZ_CAS float *q = tpos + (size_t)idx * a.pos_stride;
+          t.ax = q[0], t.ay = q[1], t.z0 = q[2], t.bx = q[3], t.by = q[4], t.z1 = q[5], t.cx = q[6], t.cy = q[7], t.z2 = q[8];
+        }
+        BranchMath m; // (the correctly rounded reciprocal, no flag-and-redo: there is no redo list here)
+        tri_consts(m, t);
+        const float fx = (float)(x4 + k), fy = (float)y;
+        float alpha, beta, gamma, zz;
+        if (isS)
+          cover_s(t, fx, fy, alpha, beta, gamma, zz);
+        else
+          cover_v(t, fx, fy, alpha, beta, gamma, zz);
+        o[0][k] = u2f_((idx + 1u) | (isS ? S_CLASS_BIT : 0u)), o[1][k] = alpha, o[2][k] = beta;
+      }
+      // 4. planes 1..3 of the tile's rows
+      if (full) {
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) store_nt(gz + (pl + 1) * plane, make_float4(o[pl][0], o[pl][1], o[pl][2], o[pl][3]));
+      } else if (in_tile) {
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (x4 + k <= tx1) gz[(pl + 1) * plane + k] = o[pl][k];
+      }
+      __syncthreads(); // s_pos / s_idx are reused by the next tile
+    }
+  }
+}
+
+// ================================================================================================================
 // k_resolve8 — display()'s resolve (src/Render.cpp:61-62): cv::merge(planes 0,1,2) + convertTo(CV_8UC3) =
 // saturate_cast<uchar>(cvRound(v)): round half to even, clamp to [0,255]; NaN → 0.  4 pixels per thread: three 16-byte
 // plane reads → 12 output bytes (three dword stores).
@@ -3176,6 +3293,13 @@ __global__ void k_clear_tune(ClearCtl *c, uint32_t *h_wgs) {
 
 void launch_clear_tune(ClearCtl *ctl, uint32_t *h_wgs, hipStream_t s) { hipLaunchKernelGGL(k_clear_tune, dim3(1), dim3(1), 0, s, ctl, h_wgs); }
 
+// End of a render that files no sample (srz_frameset_render_visibility) while the set measures: the next sample starts here, so that
+// it times the next colour render alone
+__global__ void k_clear_rebase(ClearCtl *c) {
+  if (!c->done) c->last = __builtin_amdgcn_s_memrealtime();
+}
+void launch_clear_rebase(ClearCtl *ctl, hipStream_t s) { hipLaunchKernelGGL(k_clear_rebase, dim3(1), dim3(1), 0, s, ctl); }
+
 void launch_clear(const RenderArgs &a, uint32_t max_tiles, bool beside_raster, hipStream_t s, uint32_t wgs) {
   if (max_tiles == 0) return;
   // Beside k_raster/k_shade the clear is THROTTLED by its grid size, so that the stores spread over the whole pipeline instead of starving
@@ -3234,6 +3358,13 @@ void launch_shade(const RenderArgs &a, uint32_t max_tiles, bool stats, uint32_t 
   // nothing, and a small grid does
   dim3 ggrid(any_generic ? grid.x : (grid.x < 128u ? grid.x : 128u));
   hipLaunchKernelGGL((k_shade<false, 0>), ggrid, dim3(256), pad, s, a);
+}
+
+void launch_visibility(const RenderArgs &a, uint32_t max_tiles, hipStream_t s) {
+  if (max_tiles == 0) return;
+  // (k_shade's grid: a tile or two per workgroup on one stream, about the resident capacity when renders interleave on several)
+  const uint32_t gcap = a.other_streams ? 2048u : 16384u;
+  hipLaunchKernelGGL(k_visibility, dim3((std::min(max_tiles, gcap) + 7u) & ~7u), dim3(256), 0, s, a);
 }
 
 bool raster_four_waves(const RenderArgs &a) { return a.n_frames * a.n_local_bands * a.tiles_x <= 4096u; }

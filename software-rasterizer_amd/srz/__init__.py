@@ -22,7 +22,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_comm_unique_id", "srz_comm_create", "srz_comm_destroy", "srz_frameset_exchange_bytes", "srz_frameset_allgather",
            "srz_frameset_deinterleave", "srz_frameset_allgather_inplace", "srz_frameset_gathered_row_offset",
            "srz_frameset_read_gathered_frame", "srz_frameset_sparse_capacity", "srz_frameset_sparse_pack", "srz_frameset_sparse_unpack",
-           "srz_frameset_allgather_sparse"]
+           "srz_frameset_allgather_sparse", "srz_frameset_render_visibility"]
 
 
 class SrzError(RuntimeError):
@@ -66,6 +66,7 @@ def lib():
         L.srz_frameset_out_bytes.argtypes = [vp, vp]
         L.srz_frameset_out_bytes.restype = C.c_size_t
         L.srz_frameset_render.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]
+        L.srz_frameset_render_visibility.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]
         L.srz_frameset_resolve8.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
         L.srz_frameset_stats.argtypes = [vp, vp, C.POINTER(abi.SrzStats)]
         L.srz_frameset_algorithmic_bytes.argtypes = [vp, vp]
@@ -139,6 +140,11 @@ class FrameSet:
     def render(self, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
         """d_out_ptr: integer device address (e.g. torch_tensor.data_ptr()). Asynchronous."""
         self.ctx._check(lib().srz_frameset_render(self.ctx.h, self.h, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def render_visibility(self, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """the visibility buffer instead of the colour: planes z, id = triangle index in the frame + 1 | S class << 31 (0 = nobody),
+        alpha, beta (include/srz.h; srz.visibility.decode takes it apart).  Same buffer and arguments as render().  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_render_visibility(self.ctx.h, self.h, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
 
     def resolve8(self, d_planes_ptr, d_bgr8_ptr, bgr8_bytes, stream=None):
         """display()'s 8-bit resolve on the device: planes (render output) → [frame][rows][W][3] uint8."""

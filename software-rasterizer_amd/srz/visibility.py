@@ -1,0 +1,46 @@
+"""The visibility buffer of FrameSet.render_visibility taken apart in torch (layout: include/srz.h, srz_frameset_render_visibility).
+
+    z        float32  the owner's depth (+inf where nobody owns the pixel in a fused-clear frame)
+    tri      int64    the owner's index in the frame's own triangle stream, -1 = nobody
+    s_class  bool     the pixel lies in the scalar-tail ("S") columns of its owner's bounding box
+    alpha, beta, gamma  float32  the barycentrics exactly as the shaders use them; gamma = 1 - (alpha + beta) for V pixels,
+                      (1 - alpha) - beta for S pixels (float32 ops, one rounding each: the shaders' bits); 0 where nobody owns the pixel
+
+Any per-vertex attribute a of the owner interpolates as alpha * a0 + beta * a1 + gamma * a2.
+"""
+from collections import namedtuple
+
+import torch
+
+Visibility = namedtuple("Visibility", "z tri s_class alpha beta gamma")
+
+S_CLASS_BIT = 0x80000000
+
+
+def decode(out):
+    """out: a render_visibility buffer as a torch tensor [..., 4, rows, W] of any 4-byte dtype (planes on dim -3)."""
+    if out.element_size() != 4 or out.dim() < 3 or out.shape[-3] != 4:
+        raise ValueError(f"decode: expected a [..., 4, rows, W] tensor of 4-byte words, got {tuple(out.shape)} {out.dtype}")
+    f = out.view(torch.float32) if out.dtype != torch.float32 else out
+    words = out.view(torch.int32)[..., 1, :, :].to(torch.int64) & 0xffffffff
+    z, alpha, beta = f[..., 0, :, :], f[..., 2, :, :], f[..., 3, :, :]
+    owned = words != 0
+    s_class = (words & S_CLASS_BIT) != 0
+    tri = torch.where(owned, (words & 0x7fffffff) - 1, torch.full_like(words, -1))
+    one = torch.ones((), dtype=torch.float32, device=f.device)
+    gamma = torch.where(s_class, (one - alpha) - beta, one - (alpha + beta))
+    gamma = torch.where(owned, gamma, torch.zeros_like(gamma))
+    return Visibility(z, tri, s_class, alpha, beta, gamma)
+
+
+def batch_of(frame, tri):
+    """The batch (a Frame) or draw (a SceneFrame's draws: pass their face counts as a sequence) each triangle index of `tri` belongs
+    to; -1 where tri is -1.  Empty batches own no index."""
+    sizes = [len(t) for t in frame.tris] if hasattr(frame, "tris") else [int(n) for n in frame]
+    tri = torch.as_tensor(tri)
+    ends = torch.cumsum(torch.tensor(sizes, dtype=torch.int64, device=tri.device), 0)
+    total = int(ends[-1]) if len(sizes) else 0
+    if bool(((tri < -1) | (tri >= total)).any()):
+        raise IndexError(f"batch_of: a triangle index outside the frame's {total} triangles")
+    b = torch.searchsorted(ends, tri.to(torch.int64), right=True)
+    return torch.where(tri < 0, torch.full_like(b, -1), b)
