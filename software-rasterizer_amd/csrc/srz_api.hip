@@ -56,24 +56,23 @@ struct srz_ctx {
   float *draw_out = nullptr;
   std::vector<uint64_t> draw_sig;
   // diagnostic switches, read ONCE when the ctx is created (never per render): frames per sub-batch of a large set (0: the
-  // default below), 32-bit owner ids even where 16 would do
+  // default, sub_batch_frames), 32-bit owner ids even where 16 would do
   int env_sub_batch = 0;
   bool env_no_packed = false; // SRZ_NO_PACKED (tests): see srz_frameset::no_packed
-  bool env_no_turns = false;  // SRZ_NO_TURNS (A/B): renders on different streams do not wait for each other's k_raster
   uint32_t env_clear_wgs = 0; // SRZ_CLEAR_WGS: fixed grid of the side-stream clear (else measured per set, srz_frameset::ClearTune)
-  uint32_t env_unpack_wgs = 0; // SRZ_UNPACK_WGS: grid of k_sparse_unpack (else SPARSE_UNPACK_WGS; the probe's sweep)
-  // what sets of this ctx have measured, by shape (clear_memo_key): a new set of a known shape starts with that grid instead of measuring
+  // what sets of this ctx have measured, by shape (clear_memo): a new set of a known shape starts with that grid instead of measuring
   std::vector<std::pair<uint64_t, uint32_t>> clear_memo;
-  bool env_no_clear_tune = false, env_clear_trace = false; // SRZ_CLEAR_TUNE=0: the grid stays at 96; SRZ_CLEAR_TRACE=1: the measurement goes to stderr
   bool opt_approx_shade = false; // SRZ_OPT_APPROX_SHADE (srz_set_option): framesets created from now on shade in the tolerance mode
   bool opt_pool_lazy = false; // SRZ_OPT_POOL_LAZY (srz_set_option; initial value: the environment variable SRZ_POOL_LAZY, read in srz_create)
+  // streams beside the launch stream, each non-null only with all its events (create_side); events are used round-robin: a render never
+  // re-records an event that a wait of the previous few renders may still refer to
+  static constexpr int EV_RING = 8;
   hipStream_t stream2 = nullptr; // k_clear runs here, next to k_raster
+  hipEvent_t ev_fork[EV_RING] = {}, ev_join[EV_RING] = {};
   float *batch_out = nullptr;    // srz_draw_batch's device planes, kept between calls (grown on demand)
   size_t batch_out_bytes = 0;
   hipStream_t stream3 = nullptr; // srz_draw_batch: the read-back of one piece of the batch under the render of the next
-  hipEvent_t ev_piece[8] = {};   // (EV_RING of them: "piece k has been rendered")
-  static constexpr int EV_RING = 8;  // fork/join events are used round-robin: a render never re-records an event that
-  hipEvent_t ev_fork[EV_RING] = {}, ev_join[EV_RING] = {}; // a wait of the previous few renders may still refer to
+  hipEvent_t ev_piece[EV_RING] = {}; // "piece k has been rendered"
   unsigned ev_next = 0;
   // Renders submitted to DIFFERENT streams (LaneRenderer) take turns in the setup..raster phase: the next one's k_setup waits
   // for the previous one's k_raster.  Two k_rasters side by side slow each other (both LDS-bound) and then leave two k_shades
@@ -161,8 +160,7 @@ struct srz_frameset {
   // the device (srz_device.h, ClearCtl / k_clear_tune): from render CLEAR_TUNE_SKIP on the clear is launched with CLEAR_GRID_MAX workgroups
   // of which the device-side state says how many take part, and a one-thread kernel ends each of the next <= 18 renders; the decision
   // arrives in a word of mapped host memory, and from the render that finds it there the host launches exactly that grid.  The pixels are
-  // the same bits under every grid.  SRZ_CLEAR_WGS fixes the grid, SRZ_CLEAR_TUNE=0 leaves it at 96, SRZ_CLEAR_TRACE=1 prints the
-  // measurement.  Every CLEAR_TUNE_AGAIN renders the set measures again (the scene of a sceneset changes under it).  A new set whose shape
+  // the same bits under every grid.  SRZ_CLEAR_WGS fixes the grid.  Every CLEAR_TUNE_AGAIN renders the set measures again (the scene of a sceneset changes under it).  A new set whose shape
   // another set of the ctx has measured (srz_ctx::clear_memo) starts with that set's grid and measures only then.
   static constexpr int CLEAR_TUNE_SKIP = 6, CLEAR_TUNE_AGAIN = 4096;
   struct ClearTune {
@@ -319,7 +317,27 @@ void free_frameset_buffers(srz_frameset *fs) {
   (void)hipFree(fs->d_draws);
 }
 
-RenderArgs make_args(const srz_ctx *ctx, const srz_frameset *fs, float *d_out, uint32_t flags_or) {
+// What a render asks for.  VISIBILITY: k_visibility writes the visibility buffer where k_shade would write colour (no texture needed; no
+// sample of the clear's grid measurement).  COUNTING: the counters of srz_stats (the reference's ordered walk).  SIZE_ONLY: the creation-
+// time pass of srz_frameset_create / srz_sceneset_create — setup + binning of every sub-batch, which size the tile-list pool, nothing else.
+struct Pass {
+  enum Kind { COLOUR, VISIBILITY, COUNTING, SIZE_ONLY } kind = COLOUR;
+  int f_begin = 0, f_count = -1; // only frames [f_begin, f_begin + f_count) of the set (-1: all); d_out is the whole set's buffer either way
+  bool one_frame_scratch = false; // a counting run whose pixels nobody reads: every frame writes the SAME one-frame buffer
+  static Pass colour() { return {}; }
+  static Pass colour_frames(int f_begin, int f_count) { return {COLOUR, f_begin, f_count}; }
+  static Pass visibility() { return {VISIBILITY}; }
+  static Pass counting() { return {COUNTING}; }
+  static Pass counting_into_one_frame() { return {COUNTING, 0, -1, true}; }
+  static Pass size_only() { return {SIZE_ONLY}; }
+};
+
+// the render's flags or some frame's have `bit`
+bool any_frame_has(const srz_frameset *fs, uint32_t flags_or, uint32_t bit) {
+  return (flags_or & bit) != 0 || std::any_of(fs->h_frames.begin(), fs->h_frames.end(), [bit](const FrameDesc &f) { return (f.flags & bit) != 0; });
+}
+
+RenderArgs make_args(const srz_ctx *ctx, const srz_frameset *fs, float *d_out, uint32_t flags_or, const Pass &pass) {
   RenderArgs a{};
   a.frames = fs->d_frames;
   a.tris = fs->d_tris;
@@ -343,7 +361,8 @@ RenderArgs make_args(const srz_ctx *ctx, const srz_frameset *fs, float *d_out, u
   a.slow_count = fs->d_slow_count;
   a.redo_list = fs->d_redo_list;
   a.redo_count = fs->d_slow_count + 1;
-  a.force_ordered = 0, a.force_generic = 0, a.any_generic = fs->any_generic ? 1u : 0u;
+  a.force_ordered = a.force_generic = pass.kind == Pass::COUNTING ? 1u : 0u; // (counting: the counters are those of the reference's ordered walk)
+  a.any_ordered = any_frame_has(fs, flags_or, SRZ_ORDERED_RASTER) ? 1u : 0u, a.any_generic = fs->any_generic ? 1u : 0u;
   a.sdesc = fs->d_sdesc;
   a.vis = fs->d_vis;
   a.worklist = fs->d_worklist;
@@ -356,7 +375,7 @@ RenderArgs make_args(const srz_ctx *ctx, const srz_frameset *fs, float *d_out, u
   a.n_frames = (uint32_t)fs->n_frames;
   a.out = d_out;
   a.local_rows = fs->local_rows;
-  a.frame_stride = 4ull * fs->local_rows * (uint64_t)fs->width;
+  a.frame_stride = pass.one_frame_scratch ? 0 : 4ull * fs->local_rows * (uint64_t)fs->width;
   a.shard_rank = fs->shard_rank;
   a.shard_world = fs->shard_world;
   a.flags_or = flags_or;
@@ -364,16 +383,14 @@ RenderArgs make_args(const srz_ctx *ctx, const srz_frameset *fs, float *d_out, u
   return a;
 }
 
-int get_events(srz_ctx *ctx, EventPair &ep) {
-  if (!ctx->ev_pool.empty()) {
-    ep = ctx->ev_pool.back();
-    ctx->ev_pool.pop_back();
-    return SRZ_OK;
-  }
-  HIP_TRY(ctx, hipEventCreate(&ep.t0));
-  HIP_TRY(ctx, hipEventCreate(&ep.t1));
-  HIP_TRY(ctx, hipEventCreate(&ep.t2));
-  HIP_TRY(ctx, hipEventCreate(&ep.t3));
+// a timed render's events (from the pool, else new ones), t0 recorded on `s`
+int begin_timing(srz_ctx *ctx, EventPair &ep, bool detailed, hipStream_t s) {
+  if (ctx->ev_pool.empty())
+    for (hipEvent_t *e : {&ep.t0, &ep.t1, &ep.t2, &ep.t3}) HIP_TRY(ctx, hipEventCreate(e));
+  else
+    ep = ctx->ev_pool.back(), ctx->ev_pool.pop_back();
+  ep.detailed = detailed;
+  HIP_TRY(ctx, hipEventRecord(ep.t0, s));
   return SRZ_OK;
 }
 
@@ -404,266 +421,272 @@ int collect_events(srz_ctx *ctx) {
   return SRZ_OK;
 }
 
-// setup → bands → raster for every frame of the set, asynchronously on `s`
-// (one_frame_scratch: a counting run whose pixels nobody reads — every frame writes the SAME one-frame buffer)
-// (size_only: the creation-time pass of srz_frameset_create / srz_sceneset_create — setup + binning of every sub-batch and the sizing
-// of the tile-list pool by their demand, nothing rasterised, no texture needed yet)
-// (f_begin, f_count: only frames [f_begin, f_begin + f_count) of the set — srz_draw_batch renders a set in pieces so that the
-// read-back of one piece runs under the render of the next; d_out is the whole set's buffer either way)
-// (visibility: srz_frameset_render_visibility — k_visibility writes the visibility buffer where k_shade would write colour; no texture
-// is needed, and the render files no sample of the side clear's grid measurement)
-int render_impl(srz_ctx *ctx, srz_frameset *fs, float *d_out, uint32_t flags_or, hipStream_t s, bool stats, bool one_frame_scratch = false,
-                bool size_only = false, int f_begin = 0, int f_count = -1, bool visibility = false) {
+// A side stream (null: none) and its rings of EV_RING events (null: none): destroyed once the stream has drained, or created all or
+// nothing — into locals, published only when every call has succeeded.
+void destroy_side(hipStream_t stream, hipEvent_t *ring_a, hipEvent_t *ring_b = nullptr) {
+  if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
+  for (hipEvent_t *ring : {ring_a, ring_b})
+    for (int i = 0; ring && i < srz_ctx::EV_RING; ++i)
+      if (ring[i]) (void)hipEventDestroy(ring[i]);
+}
+int create_side(srz_ctx *ctx, const char *what, hipStream_t *stream, bool high_priority, hipEvent_t *ring_a, hipEvent_t *ring_b = nullptr) {
+  hipStream_t st = nullptr;
+  hipEvent_t ev[2][srz_ctx::EV_RING] = {};
+  int prio_least = 0, prio_greatest = 0;
+  hipError_t e = high_priority ? hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) : hipSuccess;
+  if (e == hipSuccess && stream)
+    e = high_priority ? hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio_greatest) : hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+  for (int i = 0; i < 2 * srz_ctx::EV_RING && e == hipSuccess; ++i)
+    if (i < srz_ctx::EV_RING ? ring_a : ring_b) e = hipEventCreateWithFlags(&ev[i / srz_ctx::EV_RING][i % srz_ctx::EV_RING], hipEventDisableTiming);
+  if (e != hipSuccess) {
+    destroy_side(st, ev[0], ev[1]);
+    return fail(ctx, e == hipErrorOutOfMemory ? SRZ_E_NOMEM : SRZ_E_NODEVICE, std::string(what) + ": " + hipGetErrorString(e));
+  }
+  if (stream) *stream = st;
+  if (ring_a) std::copy(ev[0], ev[0] + srz_ctx::EV_RING, ring_a);
+  if (ring_b) std::copy(ev[1], ev[1] + srz_ctx::EV_RING, ring_b);
+  return SRZ_OK;
+}
+
+// batch → shader / texture, (re)resolved when a texture upload has changed them; SRZ_E_TEXTURE if a batch's slot was never uploaded
+int resolve_shading(srz_ctx *ctx, srz_frameset *fs, hipStream_t s) {
+  auto needs_tex = [](const BatchDesc &b) { return b.shader == SRZ_SHADER_TEXTURE || b.shader == SRZ_SHADER_DISPLACEMENT || b.shader == SRZ_SHADER_BUMP; };
+  for (const BatchDesc &b : fs->h_batches)
+    if (needs_tex(b) && (b.tex_id < 0 || b.tex_id >= MAX_TEX || !ctx->h_tex[b.tex_id].bgrx))
+      return fail(ctx, SRZ_E_TEXTURE, "batch uses texture slot " + std::to_string(b.tex_id) + " which was never uploaded");
+  if (fs->sdesc_version == ctx->tex_version || fs->h_batches.empty()) return SRZ_OK;
+  std::vector<ShadeDescG> &h = fs->h_sdesc; // (owned by the set: the asynchronous copy below may read it after we return)
+  h.resize(fs->h_batches.size());
+  for (size_t i = 0; i < h.size(); ++i) {
+    const BatchDesc &b = fs->h_batches[i];
+    const TexDesc t = needs_tex(b) ? ctx->h_tex[b.tex_id] : TexDesc{nullptr, 1, 1};
+    h[i] = ShadeDescG{b.shader, t.w, t.h, 0, t.bgrx};
+  }
+  // on the launch stream: ordered after the renders already submitted there, before this one
+  HIP_TRY(ctx, hipMemcpyAsync(fs->d_sdesc, h.data(), sizeof(ShadeDescG) * h.size(), hipMemcpyHostToDevice, s));
+  fs->sdesc_version = ctx->tex_version;
+  return SRZ_OK;
+}
+
+// h_pool_heads holds one copy of the allocators' lines (word 0 of each: a sub-pool's demand) per sub-batch of a render: sub-batch `part`'s
+// region; the largest demand of the regions of sub-batches [p0, p1); the copy of sub-batch `part`'s demand to the host, on `cs` (no event:
+// the next render reads whatever has arrived)
+uint32_t *demand_region(const srz_frameset *fs, int part) {
+  return fs->h_pool_heads + (size_t)std::min(part, srz_frameset::DEMAND_PARTS - 1) * CNT_STRIDE * 64;
+}
+uint32_t max_pool_demand(const srz_frameset *fs, int p0, int p1) {
+  uint32_t need = 0;
+  for (int p = p0; p < p1; ++p)
+    for (uint32_t i = 0; i < fs->pool_n_sub; ++i) need = std::max(need, (uint32_t) static_cast<const volatile uint32_t *>(demand_region(fs, p))[i * CNT_STRIDE]);
+  return need;
+}
+hipError_t copy_demand(const srz_frameset *fs, int part, hipStream_t cs) {
+  return hipMemcpyAsync(demand_region(fs, part), fs->d_pool_heads, sizeof(uint32_t) * CNT_STRIDE * fs->pool_n_sub, hipMemcpyDeviceToHost, cs);
+}
+// a new record pool of need + need / slack + 64 records per sub-pool, after the device has stopped reading the old one
+int grow_pool(srz_ctx *ctx, srz_frameset *fs, uint32_t need, uint32_t slack) {
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  const uint64_t cap = (uint64_t)need + need / slack + 64u;
+  if (cap * fs->pool_n_sub >= 0xffffffffull) return fail(ctx, SRZ_E_NOMEM, "tile lists exceed 2^32 records; split the batch");
+  uint32_t *p = nullptr;
+  HIP_TRY(ctx, hipMalloc(&p, sizeof(uint32_t) * cap * fs->pool_n_sub));
+  (void)hipFree(fs->d_pool);
+  fs->d_pool = p, fs->pool_sub_cap = (uint32_t)cap;
+  return SRZ_OK;
+}
+
+// Frames per sub-batch.  A LARGE set is rendered as sub-batches of whole frames one after the other on the same stream: what k_raster leaves
+// for k_shade (depth, owner ids) and k_bin for k_raster (records) stays in the 256 MiB Infinity Cache only while the frames in flight are few
+// (config 2, 1024 frames in pieces of 176 / 208 / 256 / 344 / 512: 0.633 / 0.644 / 0.656 / 0.653 / 0.632 of the roofline: NOTEBOOK r6 §6).
+// A sub-batch is a view: every per-frame array from its first frame on; counters, record pool and work lists are shared (k_setup resets
+// them, and stream order keeps one sub-batch's kernels behind the previous one's).  Its size is 256 frames' worth of 1024^2 (≈ 262 k tiles)
+// in frames of THIS set; frames so large that fewer than 96 make a sub-batch (2048^2 and up) are left alone.  SRZ_SUB_BATCH (tests) fixes it.
+int sub_batch_frames(const srz_ctx *ctx, const srz_frameset *fs, int n_all, bool one_piece) {
+  const size_t tiles_per_frame = std::max<size_t>((size_t)fs->n_local_bands * fs->tiles_x, 1);
+  const int sub = ctx->env_sub_batch > 0 ? ctx->env_sub_batch : (int)std::min<size_t>((256u * 1024u / tiles_per_frame + 7u) / 8u * 8u, 1u << 20);
+  if (sub < 96 || n_all < sub + sub / 4 || one_piece) return n_all;
+  const int parts = (n_all + sub - 1) / sub;
+  return ((n_all + parts - 1) / parts + 7) / 8 * 8;
+}
+
+// The side clear of one render (srz_frameset::ClearTune): its grid, RenderArgs::clear_wgs_dev, and how end_clear_plan ends the render
+struct ClearPlan {
+  uint32_t wgs = CLEAR_GRID_DEFAULT, *dev_wgs = nullptr;
+  bool count = false, stamp = false, rebase = false;
+};
+
+// The grids sets of this ctx have measured, by the shape of the set as far as the clear's best grid depends on it: frame size, frames,
+// bands, triangles, the shading builds in use.  wgs 0: looks the shape up (0: not measured); else files wgs for it.
+uint32_t clear_memo(srz_ctx *ctx, const srz_frameset *fs, uint32_t wgs) {
+  uint64_t key = 0xcbf29ce484222325ull;
+  for (uint64_t v : {(uint64_t)fs->width, (uint64_t)fs->height, (uint64_t)fs->n_frames, (uint64_t)fs->n_local_bands, fs->total_tris,
+                     (uint64_t)fs->fast_mask, (uint64_t)fs->approx_shade})
+    key = (key ^ v) * 0x100000001b3ull;
+  auto it = std::find_if(ctx->clear_memo.begin(), ctx->clear_memo.end(), [&](const std::pair<uint64_t, uint32_t> &m) { return m.first == key; });
+  if (wgs == 0u) return it != ctx->clear_memo.end() ? it->second : 0u;
+  if (it != ctx->clear_memo.end()) it->second = wgs;
+  else if (ctx->clear_memo.size() < 256) ctx->clear_memo.emplace_back(key, wgs);
+  return wgs;
+}
+
+// The plan of a render that clears beside k_raster (detailed: the per-kernel timing mode's barriers — not a sample, not counted)
+int plan_clear(srz_ctx *ctx, srz_frameset *fs, const Pass &pass, bool detailed, hipStream_t s, ClearPlan &p) {
+  srz_frameset::ClearTune &ct = fs->clear_tune;
+  p = ClearPlan{ctx->env_clear_wgs ? ctx->env_clear_wgs : ct.wgs};
+  if (ctx->env_clear_wgs || !ct.d_ctl) return SRZ_OK;
+  p.rebase = pass.kind == Pass::VISIBILITY && !ct.done; // (the grid in effect; the next colour render's sample then times itself alone)
+  if (pass.kind != Pass::COLOUR || pass.f_count >= 0) return SRZ_OK;
+  if (ct.done && !detailed && ++ct.since >= srz_frameset::CLEAR_TUNE_AGAIN) {
+    // what the clear runs beside may have changed (srz_sceneset_update): measure again (<= 18 of 4096 renders)
+    ct.done = false, ct.since = 0, ct.renders = srz_frameset::CLEAR_TUNE_SKIP;
+    *static_cast<volatile uint32_t *>(ct.h_wgs) = 0u; // (no k_clear_tune is in flight: the host stopped launching them when it saw the decision)
+    HIP_TRY(ctx, hipMemsetAsync(ct.d_ctl, 0, sizeof(ClearCtl), s));
+  }
+  if (!ct.done && ct.renders == 0) // (the set's first render: has a set of this shape measured before?)
+    if (const uint32_t m = clear_memo(ctx, fs, 0u)) ct.wgs = p.wgs = m, ct.done = true;
+  if (ct.done) return SRZ_OK;
+  const uint32_t h = *static_cast<volatile uint32_t *>(ct.h_wgs);
+  const int j = ct.renders - srz_frameset::CLEAR_TUNE_SKIP;
+  if (h != 0u) { // decided: launch that grid from now on
+    ct.wgs = p.wgs = h, ct.done = true;
+    clear_memo(ctx, fs, h);
+  } else if (!detailed && j < 0) { // (the first CLEAR_TUNE_SKIP renders are not measured)
+    p.count = true;
+  } else if (!detailed) { // measuring (or the decision has not reached the host yet): the device says how many of the grid take part
+    p.wgs = CLEAR_GRID_MAX, p.dev_wgs = &ct.d_ctl->wgs;
+    p.count = p.stamp = j < CLEAR_TUNE_RENDERS;
+  }
+  return SRZ_OK;
+}
+
+// After the render's last launch: counts it towards the measurement (here: an early error return loses no stamp) and ends it as planned
+void end_clear_plan(srz_frameset *fs, const ClearPlan &p, hipStream_t s) {
+  if (p.count) ++fs->clear_tune.renders;
+  if (p.stamp) launch_clear_tune(fs->clear_tune.d_ctl, fs->clear_tune.h_wgs, s);
+  if (p.rebase) launch_clear_rebase(fs->clear_tune.d_ctl, s);
+}
+
+struct RenderPlan { // what render_impl decided for the whole render, as each sub-batch needs it
+  Pass pass;
+  hipStream_t s;
+  bool side, turns, vertex_setup;
+  ClearPlan clear;
+  EventPair *ep; // the per-kernel timing mode: t1 / t2 go around k_raster; else null
+};
+
+// setup → bands → raster → shade of frames [f0, f0 + n) of the render (sub-batch `part`).  `a` is the whole render's arguments: the
+// first render's growth of the record pool updates them for the sub-batches that follow.
+int enqueue_sub_batch(srz_ctx *ctx, srz_frameset *fs, const RenderPlan &r, RenderArgs &a, int f0, int n, int part) {
+  const bool stats = r.pass.kind == Pass::COUNTING;
+  const hipStream_t s = r.s;
+  const size_t tpf = (size_t)fs->n_local_bands * fs->tiles_x;
+  RenderArgs v = a;
+  if (n != fs->n_frames) {
+    const int fa = r.pass.f_begin + f0; // (first frame of this piece in the set)
+    v.frames += fa, v.n_frames = (uint32_t)n;
+    v.vis += (size_t)fa * tpf * ((size_t)TILE * TILE);
+    v.tile_info += (size_t)fa * tpf;
+    v.out += (size_t)fa * a.frame_stride;
+    v.work_cap = (uint32_t)((size_t)(n < 8 ? n : (n + 7) / 8) * tpf);
+  }
+  const uint32_t tiles = (uint32_t)((size_t)n * tpf);
+  if (r.vertex_setup) launch_chunks(v, n, fs->max_tris, s);
+  else launch_setup(v, n, fs->max_tris, stats, s);
+  launch_bin(v, n, fs->max_tris, s);
+  // The FIRST render of a set sizes the pool by what it needs itself: it waits for k_bin's count, grows the pool if a band
+  // did not fit and bins again — a one-shot set (srz_draw_batch, the host layer's per-draw sets) has no second render that
+  // could profit from the lazy growth, and would otherwise leave its overflowing bands to the ordered rasteriser.
+  if (!fs->pool_sized && !stats) {
+    HIP_TRY(ctx, copy_demand(fs, part, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    const uint32_t need = max_pool_demand(fs, part, part + 1);
+    if (need > fs->pool_sub_cap) {
+      if (int rc = grow_pool(ctx, fs, need, 8u)) return rc; // (earlier sub-batches of this render may still be reading the old pool)
+      a.pool = v.pool = fs->d_pool, a.pool_sub_cap = v.pool_sub_cap = fs->pool_sub_cap;
+      HIP_TRY(ctx, hipMemsetAsync(fs->d_pool_heads, 0, sizeof(uint32_t) * CNT_STRIDE * fs->pool_n_sub, s));
+      launch_bin(v, n, fs->max_tris, s);
+    }
+  }
+  if (r.pass.kind == Pass::SIZE_ONLY) return SRZ_OK; // (the creation-time pass ends with the binning)
+  if (r.ep) HIP_TRY(ctx, hipEventRecord(r.ep->t1, s));
+  const unsigned ev = r.side ? ctx->ev_next++ % srz_ctx::EV_RING : 0u;
+  if (r.side) {
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_fork[ev], s));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork[ev], 0));
+    launch_clear(v, tiles, ctx->stream2, r.clear.wgs);
+    // (in front of the join: whatever follows on the launch stream — the next sub-batch's or render's k_setup zeroes the
+    // allocators — is ordered behind this copy; it is 16 words behind a kernel that outlasts k_raster)
+    HIP_TRY(ctx, copy_demand(fs, part, ctx->stream2));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_join[ev], ctx->stream2));
+  }
+  launch_raster(v, n, stats, s);
+  if (r.turns) {
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_raster[ctx->raster_next++ % srz_ctx::EV_RING], s));
+    ctx->raster_last_stream = s, ctx->raster_valid = true;
+  }
+  if (r.ep) HIP_TRY(ctx, hipEventRecord(r.ep->t2, s));
+  if (r.pass.kind == Pass::VISIBILITY) launch_visibility(v, tiles, s);
+  else launch_shade(v, tiles, stats, fs->fast_mask, fs->any_generic, fs->approx_shade, s);
+  if (r.side) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join[ev], 0));
+  else if (!raster_four_waves(v)) // (the latency build of k_raster stores the demand itself)
+    HIP_TRY(ctx, copy_demand(fs, part, s));
+  return SRZ_OK;
+}
+
+// setup → bands → raster → shade for every frame of the set (or of pass.f_begin.., pass.f_count), asynchronously on `s`
+int render_impl(srz_ctx *ctx, srz_frameset *fs, float *d_out, uint32_t flags_or, hipStream_t s, Pass pass) {
+  const bool stats = pass.kind == Pass::COUNTING, size_only = pass.kind == Pass::SIZE_ONLY;
   if (fs->shard_rank != ctx->shard_rank || fs->shard_world != ctx->shard_world)
     return fail(ctx, SRZ_E_INVALID, "frameset was created under a different shard (call srz_set_shard before srz_frameset_create)");
   if (fs->update_failed) return fail(ctx, SRZ_E_NOMEM, "the last update of this set failed (out of memory): update it again or destroy it");
-  for (const BatchDesc &b : fs->h_batches) {
-    if (size_only || visibility) break;
-    bool needs = b.shader == SRZ_SHADER_TEXTURE || b.shader == SRZ_SHADER_DISPLACEMENT || b.shader == SRZ_SHADER_BUMP;
-    if (needs && (b.tex_id < 0 || b.tex_id >= MAX_TEX || !ctx->h_tex[b.tex_id].bgrx))
-      return fail(ctx, SRZ_E_TEXTURE, "batch uses texture slot " + std::to_string(b.tex_id) + " which was never uploaded");
-  }
-  if (!size_only && !visibility && fs->sdesc_version != ctx->tex_version && !fs->h_batches.empty()) { // (re)resolve batch → shader/texture
-    std::vector<ShadeDescG> &h = fs->h_sdesc; // (owned by the set: the asynchronous copy below may read it after we return)
-    h.resize(fs->h_batches.size());
-    for (size_t i = 0; i < h.size(); ++i) {
-      const BatchDesc &b = fs->h_batches[i];
-      bool needs = b.shader == SRZ_SHADER_TEXTURE || b.shader == SRZ_SHADER_DISPLACEMENT || b.shader == SRZ_SHADER_BUMP;
-      h[i].shader = b.shader, h[i]._pad = 0;
-      h[i].tw = needs ? ctx->h_tex[b.tex_id].w : 1, h[i].th = needs ? ctx->h_tex[b.tex_id].h : 1;
-      h[i].tex = needs ? ctx->h_tex[b.tex_id].bgrx : nullptr;
-    }
-    // on the launch stream: ordered after the renders already submitted there, before this one
-    HIP_TRY(ctx, hipMemcpyAsync(fs->d_sdesc, h.data(), sizeof(ShadeDescG) * h.size(), hipMemcpyHostToDevice, s));
-    fs->sdesc_version = ctx->tex_version;
-  }
-  // the record pool follows what the previous renders asked for: growing is rare and the one place where a render waits
-  // for the device
-  { // (h_pool_heads is pinned host memory the rasteriser's first workgroup stores into: whatever it holds is a demand some
-    // finished or running render of this set really had — a stale value only delays the growth by a render)
-    uint32_t need = 0;
-    for (uint32_t i = 0; i < fs->pool_n_sub * (uint32_t)srz_frameset::DEMAND_PARTS; ++i) { // (every sub-batch's region)
-      const uint32_t v = static_cast<volatile uint32_t *>(fs->h_pool_heads)[((i / fs->pool_n_sub) * 64u + i % fs->pool_n_sub) * CNT_STRIDE];
-      if (v > need) need = v;
-    }
-    if (need > fs->pool_sub_cap) {
-      HIP_TRY(ctx, hipDeviceSynchronize());
-      const uint64_t cap = (uint64_t)need + need / 4u + 64u;
-      if (cap * fs->pool_n_sub >= 0xffffffffull) return fail(ctx, SRZ_E_NOMEM, "tile lists exceed 2^32 records; split the batch");
-      uint32_t *p = nullptr;
-      HIP_TRY(ctx, hipMalloc(&p, sizeof(uint32_t) * cap * fs->pool_n_sub));
-      (void)hipFree(fs->d_pool);
-      fs->d_pool = p, fs->pool_sub_cap = (uint32_t)cap;
-    }
-  }
-  RenderArgs a = make_args(ctx, fs, d_out, flags_or);
-  if (one_frame_scratch) a.frame_stride = 0;
+  if (pass.kind == Pass::COLOUR || stats)
+    if (int rc = resolve_shading(ctx, fs, s)) return rc;
+  // The record pool follows what the previous renders asked for: growing is rare and the one place where a render waits for the device.
+  // (Whatever h_pool_heads holds is a demand some finished or running render of this set really had: a stale value only delays the growth.)
+  const uint32_t need = max_pool_demand(fs, 0, srz_frameset::DEMAND_PARTS);
+  if (need > fs->pool_sub_cap)
+    if (int rc = grow_pool(ctx, fs, need, 4u)) return rc;
+  RenderArgs a = make_args(ctx, fs, d_out, flags_or, pass);
   if (!size_only) fs->last_flags = flags_or, fs->rendered = true; // (this render rewrites d_tile_info: srz_frameset_sparse_pack)
-  a.force_ordered = a.force_generic = stats ? 1u : 0u; // the counters are those of the reference's ordered walk
-  a.any_ordered = ((flags_or & SRZ_ORDERED_RASTER) != 0 ||
-                   std::any_of(fs->h_frames.begin(), fs->h_frames.end(), [](const FrameDesc &f) { return (f.flags & SRZ_ORDERED_RASTER) != 0; }))
-                      ? 1u : 0u;
   EventPair ep{};
   const bool timed = ctx->timing != 0 && !stats && !size_only && ctx->ev_used.size() < 65536, detailed = timed && ctx->timing >= 2;
-  if (timed) {
-    int rc = get_events(ctx, ep);
-    if (rc) return rc;
-    ep.detailed = detailed;
-    HIP_TRY(ctx, hipEventRecord(ep.t0, s));
-  }
+  if (timed)
+    if (int rc = begin_timing(ctx, ep, detailed, s)) return rc;
   if (stats) HIP_TRY(ctx, hipMemsetAsync(ctx->d_stats, 0, ST_COUNT * sizeof(unsigned long long), s));
   if (fs->max_tris == 0) { // (else: k_setup resets the per-render counters)
     HIP_TRY(ctx, hipMemsetAsync(fs->d_work_count, 0, sizeof(uint32_t) * CNT_STRIDE * N_WORK_LISTS, s));
     HIP_TRY(ctx, hipMemsetAsync(fs->d_pool_heads, 0, sizeof(uint32_t) * CNT_STRIDE * fs->pool_n_sub, s));
     HIP_TRY(ctx, hipMemsetAsync(fs->d_slow_count, 0, 2 * sizeof(uint32_t), s));
   }
-  const bool turns = !stats && !size_only && fs->max_tiles >= 8192 && !ctx->env_no_turns; // (batches; small jobs are launch-bound and gain nothing)
-  if (turns) {
-    if (!ctx->ev_raster[0])
-      for (int i = 0; i < srz_ctx::EV_RING; ++i) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_raster[i], hipEventDisableTiming));
-    if (ctx->raster_valid && ctx->raster_last_stream != s) {
-      HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_raster[(ctx->raster_next + srz_ctx::EV_RING - 1) % srz_ctx::EV_RING], 0));
-      a.other_streams = 1u;
-    }
+  const bool turns = !stats && !size_only && fs->max_tiles >= 8192; // (batches; small jobs are launch-bound and gain nothing)
+  if (turns && !ctx->ev_raster[0])
+    if (int rc = create_side(ctx, "render: raster events", nullptr, false, ctx->ev_raster)) return rc;
+  if (turns && ctx->raster_valid && ctx->raster_last_stream != s) {
+    HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_raster[(ctx->raster_next + srz_ctx::EV_RING - 1) % srz_ctx::EV_RING], 0));
+    a.other_streams = 1u;
   }
   // vertex stage on the device; outside counting runs it does the triangles' setup too (cull + bounding box from the registers
   // that hold the transformed triangle), and k_chunks replaces k_setup below
   const bool vertex_setup = fs->d_draws != nullptr && !stats;
   if (fs->d_draws) launch_vertex(fs->d_draws, fs->n_draws, fs->max_faces, fs->d_tris, fs->d_tri_pos, fs->d_frames, vertex_setup ? fs->d_bbox : nullptr, s);
   // fused clear of the tiles no bbox reaches: beside k_raster on a second stream (batches), or in the rasteriser (small jobs)
-  const bool any_fused = (flags_or & SRZ_FUSED_CLEAR) != 0 ||
-                         std::any_of(fs->h_frames.begin(), fs->h_frames.end(), [](const FrameDesc &f) { return (f.flags & SRZ_FUSED_CLEAR) != 0; });
-  const bool side = any_fused && fs->max_tiles >= 8192 && !size_only;
-  if (side && !ctx->stream2) {
-    // The clear must run BESIDE the launch stream, so it may not share a hardware queue with it: HIP deals its streams
-    // round-robin onto a few hardware queues (seen: the caller's stream and this one on the same queue — the clear then ran
-    // in front of k_raster instead of beside it, +20 % per render).  Streams of another priority live on queues of their own;
-    // the clear is throttled by its grid size, not by priority, so the highest one costs the rasteriser nothing.
-    int prio_least = 0, prio_greatest = 0;
-    HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, prio_greatest));
-    for (int i = 0; i < srz_ctx::EV_RING; ++i) {
-      HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fork[i], hipEventDisableTiming));
-      HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming));
-    }
-  }
+  const bool any_fused = any_frame_has(fs, flags_or, SRZ_FUSED_CLEAR), side = any_fused && fs->max_tiles >= 8192 && !size_only;
+  // The clear must run BESIDE the launch stream, so it may not share a hardware queue with it (HIP deals its streams round-robin onto a few:
+  // seen, the clear in front of k_raster, +20 % per render).  Streams of another priority live on queues of their own; the clear is throttled
+  // by its grid size, not by priority, so the highest one costs the rasteriser nothing.
+  if (side && !ctx->stream2)
+    if (int rc = create_side(ctx, "render: clear stream", &ctx->stream2, true, ctx->ev_fork, ctx->ev_join)) return rc;
   if (!side && any_fused) a.clear_in_raster = 1u; // (small job: the rasteriser's own waves clear the tiles no bbox reaches)
-  // A LARGE set is rendered as sub-batches of whole frames one after the other on the same stream: what k_raster leaves for
-  // k_shade (depth, owner ids) and k_bin for k_raster (records) stays in the 256 MiB Infinity Cache only while the frames in
-  // flight are few — config 2 at 128 / 256 / 384 / 512 frames per launch set: 0.539 / 0.545 / 0.499 / 0.490 of the roofline (round 3; round 6,
-  // beside the per-plane clear, 1024 frames on one stream in pieces of 176 / 208 / 256 / 344 / 512: 0.633 / 0.644 / 0.656 / 0.653 / 0.632).
-  // A sub-batch is a view: every per-frame array from its first frame on; counters, record pool and work lists are shared
-  // (k_setup resets them, and stream order keeps one sub-batch's kernels behind the previous one's).  Counting runs and the
-  // per-kernel timing mode render in one piece.
-  const int n_all = f_count < 0 ? fs->n_frames : f_count;
-  int chunk = n_all;
-  // The sub-batch size is 256 frames' worth of 1024^2 (≈ 262 k tiles: the measured sweet spot; 192 until round 6), in frames of THIS
-  // set — a rank of an 8-GPU job holds an eighth of every frame and takes 2048 of them at a time; frames so large that fewer than 96
-  // make a sub-batch (2048^2 and up) are left alone: nothing of theirs fits the cache either way (config 4, 256 frames, in pieces of
-  // 64 / 128 / 256: 0.425 / 0.422 / 0.422).
-  const int sub_env = ctx->env_sub_batch; // (tuning / tests: frames per sub-batch)
-  const size_t tiles_per_frame = std::max<size_t>((size_t)fs->n_local_bands * fs->tiles_x, 1);
-  const int sub = sub_env > 0 ? sub_env : (int)std::min<size_t>((256u * 1024u / tiles_per_frame + 7u) / 8u * 8u, 1u << 20);
-  if (sub >= 96 && n_all >= sub + sub / 4 && !stats && !detailed) {
-    const int parts = (n_all + sub - 1) / sub;
-    chunk = ((n_all + parts - 1) / parts + 7) / 8 * 8;
-  }
-  const size_t tpf = (size_t)fs->n_local_bands * fs->tiles_x;
-  // the side clear's grid: measured per set, on the device (srz_frameset::ClearTune)
-  uint32_t clear_wgs = ctx->env_clear_wgs ? ctx->env_clear_wgs : fs->clear_tune.wgs;
-  bool tune_stamp = false, tune_rebase = false;
-  if (side && visibility && !ctx->env_clear_wgs && fs->clear_tune.d_ctl && !fs->clear_tune.done)
-    tune_rebase = true; // (the grid in effect; the measurement's clock restarts at this render's end: the next colour render's sample is its own)
-  if (side && !visibility && !ctx->env_clear_wgs && !ctx->env_no_clear_tune && !stats && f_count < 0 && fs->clear_tune.d_ctl) {
-    srz_frameset::ClearTune &ct = fs->clear_tune;
-    if (ct.done && !detailed && ++ct.since >= srz_frameset::CLEAR_TUNE_AGAIN) {
-      // what the clear runs beside may have changed (srz_sceneset_update): measure again (<= 18 of 4096 renders)
-      ct.done = false, ct.since = 0, ct.renders = srz_frameset::CLEAR_TUNE_SKIP;
-      *static_cast<volatile uint32_t *>(ct.h_wgs) = 0u; // (no k_clear_tune is in flight: the host stopped launching them when it saw the decision)
-      HIP_TRY(ctx, hipMemsetAsync(ct.d_ctl, 0, sizeof(ClearCtl), s));
-    }
-    // the shape of the set, as far as the clear's best grid depends on it: frame size, frames, bands, triangles, the shading builds in use
-    auto memo_key = [&]() {
-      uint64_t k = 0xcbf29ce484222325ull;
-      for (uint64_t v : {(uint64_t)fs->width, (uint64_t)fs->height, (uint64_t)fs->n_frames, (uint64_t)fs->n_local_bands, fs->total_tris,
-                         (uint64_t)fs->fast_mask, (uint64_t)fs->approx_shade})
-        k = (k ^ v) * 0x100000001b3ull;
-      return k;
-    };
-    if (!ct.done && ct.renders == 0) // (the set's first render: has a set of this shape measured before?)
-      for (const auto &m : ctx->clear_memo)
-        if (m.first == memo_key()) ct.wgs = clear_wgs = m.second, ct.done = true;
-    if (!ct.done) {
-      const uint32_t h = *static_cast<volatile uint32_t *>(ct.h_wgs);
-      const int j = ct.renders - srz_frameset::CLEAR_TUNE_SKIP;
-      if (h != 0u) { // decided: launch that grid from now on
-        ct.wgs = clear_wgs = h, ct.done = true;
-        {
-          const uint64_t key = memo_key();
-          auto it = std::find_if(ctx->clear_memo.begin(), ctx->clear_memo.end(), [&](const std::pair<uint64_t, uint32_t> &m) { return m.first == key; });
-          if (it != ctx->clear_memo.end()) it->second = h;
-          else if (ctx->clear_memo.size() < 256) ctx->clear_memo.emplace_back(key, h);
-        }
-        if (ctx->env_clear_trace) {
-          ClearCtl c;
-          if (hipMemcpy(&c, ct.d_ctl, sizeof c, hipMemcpyDeviceToHost) == hipSuccess) {
-            fprintf(stderr, "srz: clear grid of set %p:", (void *)fs);
-            for (int i = 0; i < CLEAR_CANDS; ++i) fprintf(stderr, " %u:%.3f", CLEAR_CAND[i], c.score[i] * 1e-5f);
-            fprintf(stderr, " ms (0: dropped after the first pass) -> %u\n", h);
-          }
-        }
-      } else if (j < 0) {
-        if (!detailed) ++ct.renders;
-      } else if (!detailed) { // measuring (or the decision has not reached the host yet): the device says how many of the grid take part
-        clear_wgs = CLEAR_GRID_MAX, a.clear_wgs_dev = &ct.d_ctl->wgs;
-        if (j < CLEAR_TUNE_RENDERS) ++ct.renders, tune_stamp = true;
-      } // (the per-kernel timing mode puts barriers into the stream: not a sample, not counted, and rendered with the grid in use before)
-    }
-  }
-  int part = 0;
-  for (int f0 = 0; f0 < n_all; f0 += chunk, ++part) {
-    RenderArgs v = a;
-    const int n = std::min(chunk, n_all - f0);
-    if (n != fs->n_frames) {
-      const int fa = f_begin + f0; // (first frame of this piece in the set)
-      v.frames += fa, v.n_frames = (uint32_t)n;
-      v.vis += (size_t)fa * tpf * ((size_t)TILE * TILE);
-      v.tile_info += (size_t)fa * tpf;
-      v.out += (size_t)fa * a.frame_stride;
-      v.work_cap = (uint32_t)((size_t)(n < 8 ? n : (n + 7) / 8) * tpf);
-    }
-    const uint32_t tiles = (uint32_t)((size_t)n * tpf);
-    if (vertex_setup)
-      launch_chunks(v, n, fs->max_tris, s);
-    else
-      launch_setup(v, n, fs->max_tris, stats, s);
-    launch_bin(v, n, fs->max_tris, s);
-    // the record pool's demand of this (sub-)render → host (word 0 of every allocator's line; one region per sub-batch).  No
-    // event: the next render reads whatever has arrived (see the growth check above).  The latency build of k_raster stores it itself.
-    auto copy_demand = [&](hipStream_t cs) {
-      uint32_t *dst = fs->h_pool_heads + (size_t)std::min(part, srz_frameset::DEMAND_PARTS - 1) * CNT_STRIDE * 64;
-      HIP_TRY(ctx, hipMemcpyAsync(dst, fs->d_pool_heads, sizeof(uint32_t) * CNT_STRIDE * fs->pool_n_sub, hipMemcpyDeviceToHost, cs));
-      return (int)SRZ_OK;
-    };
-    // The FIRST render of a set sizes the pool by what it needs itself: it waits for k_bin's count, grows the pool if a band
-    // did not fit and bins again — a one-shot set (srz_draw_batch, the host layer's per-draw sets) has no second render that
-    // could profit from the lazy growth, and would otherwise leave its overflowing bands to the ordered rasteriser.
-    if (!fs->pool_sized && !stats) {
-      if (int rc = copy_demand(s)) return rc;
-      HIP_TRY(ctx, hipStreamSynchronize(s));
-      const uint32_t *dem = fs->h_pool_heads + (size_t)std::min(part, srz_frameset::DEMAND_PARTS - 1) * CNT_STRIDE * 64;
-      uint32_t need = 0;
-      for (uint32_t i = 0; i < fs->pool_n_sub; ++i) {
-        const uint32_t v = static_cast<const volatile uint32_t *>(dem)[i * CNT_STRIDE];
-        if (v > need) need = v;
-      }
-      if (need > fs->pool_sub_cap) {
-        HIP_TRY(ctx, hipDeviceSynchronize()); // (earlier sub-batches of this render may still be reading the old pool)
-        const uint64_t cap = (uint64_t)need + need / 8u + 64u;
-        if (cap * fs->pool_n_sub >= 0xffffffffull) return fail(ctx, SRZ_E_NOMEM, "tile lists exceed 2^32 records; split the batch");
-        uint32_t *p = nullptr;
-        HIP_TRY(ctx, hipMalloc(&p, sizeof(uint32_t) * cap * fs->pool_n_sub));
-        (void)hipFree(fs->d_pool);
-        fs->d_pool = p, fs->pool_sub_cap = (uint32_t)cap;
-        a.pool = v.pool = p, a.pool_sub_cap = v.pool_sub_cap = (uint32_t)cap;
-        HIP_TRY(ctx, hipMemsetAsync(fs->d_pool_heads, 0, sizeof(uint32_t) * CNT_STRIDE * fs->pool_n_sub, s));
-        launch_bin(v, n, fs->max_tris, s);
-      }
-    }
-    if (size_only) continue; // (the creation-time pass ends with the binning)
-    if (detailed) HIP_TRY(ctx, hipEventRecord(ep.t1, s));
-    unsigned ev = 0;
-    // SRZ_CLEAR_AT=1 (diagnostic, A/B): the clear starts beside k_shade instead of beside k_raster
-    static const bool clear_late = getenv("SRZ_CLEAR_AT") && atoi(getenv("SRZ_CLEAR_AT")) == 1;
-    if (side && clear_late) launch_raster(v, n, stats, s);
-    if (side) {
-      ev = ctx->ev_next++ % srz_ctx::EV_RING;
-      HIP_TRY(ctx, hipEventRecord(ctx->ev_fork[ev], s));
-      hipStream_t side_s = ctx->stream2;
-      HIP_TRY(ctx, hipStreamWaitEvent(side_s, ctx->ev_fork[ev], 0));
-      launch_clear(v, tiles, true, side_s, clear_wgs);
-      // (in front of the join: whatever follows on the launch stream — the next sub-batch's or render's k_setup zeroes the
-      // allocators — is ordered behind this copy; it is 16 words behind a kernel that outlasts k_raster)
-      if (int rc = copy_demand(side_s)) return rc;
-      HIP_TRY(ctx, hipEventRecord(ctx->ev_join[ev], side_s));
-    }
-    if (!(side && clear_late)) launch_raster(v, n, stats, s);
-    if (turns) {
-      HIP_TRY(ctx, hipEventRecord(ctx->ev_raster[ctx->raster_next++ % srz_ctx::EV_RING], s));
-      ctx->raster_last_stream = s, ctx->raster_valid = true;
-    }
-    if (detailed) HIP_TRY(ctx, hipEventRecord(ep.t2, s));
-    if (visibility)
-      launch_visibility(v, tiles, s);
-    else
-      launch_shade(v, tiles, stats, fs->fast_mask, fs->any_generic, fs->approx_shade, s);
-    if (side) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join[ev], 0));
-    else if (!raster_four_waves(v))
-      if (int rc = copy_demand(s)) return rc;
-  }
+  RenderPlan r{pass, s, side, turns, vertex_setup, ClearPlan{}, detailed ? &ep : nullptr};
+  if (side)
+    if (int rc = plan_clear(ctx, fs, pass, detailed, s, r.clear)) return rc;
+  a.clear_wgs_dev = r.clear.dev_wgs;
+  const int n_all = pass.f_count < 0 ? fs->n_frames : pass.f_count;
+  const int chunk = sub_batch_frames(ctx, fs, n_all, stats || detailed);
+  for (int f0 = 0, part = 0; f0 < n_all; f0 += chunk, ++part)
+    if (int rc = enqueue_sub_batch(ctx, fs, r, a, f0, std::min(chunk, n_all - f0), part)) return rc;
   if (!stats) fs->pool_sized = true;
-  if (tune_stamp) launch_clear_tune(fs->clear_tune.d_ctl, fs->clear_tune.h_wgs, s);
-  if (tune_rebase) launch_clear_rebase(fs->clear_tune.d_ctl, s);
+  end_clear_plan(fs, r.clear, s);
   if (timed) {
     HIP_TRY(ctx, hipEventRecord(ep.t3, s));
     ctx->ev_used.push_back(ep);
@@ -672,21 +695,16 @@ int render_impl(srz_ctx *ctx, srz_frameset *fs, float *d_out, uint32_t flags_or,
   return SRZ_OK;
 }
 
-int read_stats(srz_ctx *ctx, hipStream_t s, srz_stats *st);
-
-// The counters of srz_stats are those of the reference's ORDERED walk ("shaded" = fragments that pass the z-test when
-// their triangle is drawn), which the order-independent rasteriser does not produce.  A draw that asks for them runs the
-// counting kernels (ordered rasteriser) once more on a scratch copy of the framebuffer the draw starts from.
-int stats_pass(srz_ctx *ctx, srz_frameset *fs, const float *d_start, uint32_t flags_or, hipStream_t s, srz_stats *st) {
-  const size_t bytes = (size_t)fs->n_frames * 4u * fs->local_rows * (size_t)fs->width * sizeof(float);
-  float *d_tmp = nullptr;
-  HIP_TRY(ctx, hipMalloc(&d_tmp, bytes));
-  hipError_t e = d_start ? hipMemcpyAsync(d_tmp, d_start, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
-  int rc = e == hipSuccess ? render_impl(ctx, fs, d_tmp, flags_or, s, true) : fail(ctx, SRZ_E_NODEVICE, hipGetErrorString(e));
-  if (rc == SRZ_OK) rc = read_stats(ctx, s, st); // (synchronises s)
-  else (void)hipStreamSynchronize(s);
-  (void)hipFree(d_tmp);
-  return rc;
+// srz_frameset_render / _render_visibility
+int render_entry(const char *name, srz_ctx *ctx, srz_frameset *fs, void *d_out, size_t out_bytes, uint32_t flags, void *stream, Pass pass) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn(name);
+  if (!fs || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / output");
+  if (out_bytes < srz_frameset_out_bytes(ctx, fs)) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
+  if (((uintptr_t)d_out & 15u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": output must be 16-byte aligned");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  flags &= SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER;
+  return render_impl(ctx, fs, (float *)d_out, flags, pick_stream(ctx, stream), pass);
 }
 
 int read_stats(srz_ctx *ctx, hipStream_t s, srz_stats *st) {
@@ -698,6 +716,21 @@ int read_stats(srz_ctx *ctx, hipStream_t s, srz_stats *st) {
   st->visible_textured = h[ST_VISIBLE_TEX];
   std::memcpy(ctx->dbg, h, sizeof h);
   return SRZ_OK;
+}
+
+// The counters of srz_stats are those of the reference's ORDERED walk ("shaded" = fragments that pass the z-test when
+// their triangle is drawn), which the order-independent rasteriser does not produce.  A draw that asks for them runs the
+// counting kernels (ordered rasteriser) once more on a scratch copy of the framebuffer the draw starts from.
+int stats_pass(srz_ctx *ctx, srz_frameset *fs, const float *d_start, uint32_t flags_or, hipStream_t s, srz_stats *st) {
+  const size_t bytes = (size_t)fs->n_frames * 4u * fs->local_rows * (size_t)fs->width * sizeof(float);
+  float *d_tmp = nullptr;
+  HIP_TRY(ctx, hipMalloc(&d_tmp, bytes));
+  hipError_t e = d_start ? hipMemcpyAsync(d_tmp, d_start, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
+  int rc = e == hipSuccess ? render_impl(ctx, fs, d_tmp, flags_or, s, Pass::counting()) : fail(ctx, SRZ_E_NODEVICE, hipGetErrorString(e));
+  if (rc == SRZ_OK) rc = read_stats(ctx, s, st); // (synchronises s)
+  else (void)hipStreamSynchronize(s);
+  (void)hipFree(d_tmp);
+  return rc;
 }
 
 } // namespace
@@ -726,11 +759,7 @@ int srz_create(srz_ctx **out, int device_id) {
   ctx->device = device_id;
   ctx->env_sub_batch = getenv("SRZ_SUB_BATCH") ? atoi(getenv("SRZ_SUB_BATCH")) : 0;
   ctx->env_no_packed = getenv("SRZ_NO_PACKED") != nullptr;
-  ctx->env_no_turns = getenv("SRZ_NO_TURNS") != nullptr;
   ctx->env_clear_wgs = getenv("SRZ_CLEAR_WGS") ? (uint32_t)std::max(atoi(getenv("SRZ_CLEAR_WGS")), 0) : 0u;
-  ctx->env_unpack_wgs = getenv("SRZ_UNPACK_WGS") ? (uint32_t)std::max(atoi(getenv("SRZ_UNPACK_WGS")), 0) : 0u;
-  ctx->env_no_clear_tune = getenv("SRZ_CLEAR_TUNE") && atoi(getenv("SRZ_CLEAR_TUNE")) == 0;
-  ctx->env_clear_trace = getenv("SRZ_CLEAR_TRACE") && atoi(getenv("SRZ_CLEAR_TRACE")) != 0;
   ctx->opt_pool_lazy = getenv("SRZ_POOL_LAZY") != nullptr;
   for (int i = 0; i < MAX_TEX; ++i) ctx->h_tex[i] = TexDesc{nullptr, 0, 0}, ctx->d_texmem[i] = nullptr;
   auto bail = [&](const char *what, hipError_t err) {
@@ -764,19 +793,9 @@ void srz_destroy(srz_ctx *ctx) {
   for (int i = 0; i < MAX_MESH; ++i) (void)hipFree(ctx->mesh[i].d_verts), (void)hipFree(ctx->mesh[i].d_faces);
   (void)hipFree(ctx->d_tex);
   (void)hipFree(ctx->d_stats);
-  if (ctx->stream2) {
-    (void)hipStreamSynchronize(ctx->stream2);
-    (void)hipStreamDestroy(ctx->stream2);
-    for (int i = 0; i < srz_ctx::EV_RING; ++i) (void)hipEventDestroy(ctx->ev_fork[i]), (void)hipEventDestroy(ctx->ev_join[i]);
-  }
-  if (ctx->stream3) {
-    (void)hipStreamSynchronize(ctx->stream3);
-    (void)hipStreamDestroy(ctx->stream3);
-    for (int i = 0; i < srz_ctx::EV_RING; ++i) (void)hipEventDestroy(ctx->ev_piece[i]);
-  }
-  if (ctx->ev_raster[0]) {
-    for (int i = 0; i < srz_ctx::EV_RING; ++i) (void)hipEventDestroy(ctx->ev_raster[i]);
-  }
+  destroy_side(ctx->stream2, ctx->ev_fork, ctx->ev_join);
+  destroy_side(ctx->stream3, ctx->ev_piece);
+  destroy_side(nullptr, ctx->ev_raster);
   (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -985,7 +1004,7 @@ static int build_frameset(srz_ctx *ctx, const srz_frame *frames, int n_frames, s
 static int size_pool_at_create(srz_ctx *ctx, srz_frameset **out) {
   srz_frameset *fs = *out;
   if (fs->pool_sized) return SRZ_OK; // SRZ_OPT_POOL_LAZY
-  int rc = render_impl(ctx, fs, nullptr, 0, ctx->stream, false, false, /*size_only=*/true);
+  int rc = render_impl(ctx, fs, nullptr, 0, ctx->stream, Pass::size_only());
   if (rc == SRZ_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, SRZ_E_NODEVICE, "srz_frameset_create: the binning pass failed");
   if (rc != SRZ_OK) {
     srz_frameset_destroy(ctx, fs);
@@ -1224,7 +1243,7 @@ int srz_target_draw(srz_ctx *ctx, srz_target *t, int primitive, srz_frameset *fs
   const uint32_t flags = t->pending_clear ? SRZ_FUSED_CLEAR : 0u;
   int rc = SRZ_OK;
   if (stats) rc = stats_pass(ctx, fs, t->pending_clear ? nullptr : t->d_planes, flags, ctx->stream, stats);
-  if (rc == SRZ_OK) rc = render_impl(ctx, fs, t->d_planes, flags, ctx->stream, false);
+  if (rc == SRZ_OK) rc = render_impl(ctx, fs, t->d_planes, flags, ctx->stream, Pass::colour());
   if (rc == SRZ_OK) t->pending_clear = false; // (a failed draw leaves the pending clear(Color|Depth) in place)
   return rc;
 }
@@ -1273,25 +1292,11 @@ size_t srz_frameset_out_bytes(const srz_ctx *ctx, const srz_frameset *fs) {
 }
 
 int srz_frameset_render(srz_ctx *ctx, srz_frameset *fs, void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
-  if (!ctx) return SRZ_E_INVALID;
-  if (!fs || !d_out) return fail(ctx, SRZ_E_INVALID, "srz_frameset_render: null frameset / output");
-  if (out_bytes < srz_frameset_out_bytes(ctx, fs)) return fail(ctx, SRZ_E_INVALID, "srz_frameset_render: output buffer too small");
-  if (((uintptr_t)d_out & 15u) != 0) return fail(ctx, SRZ_E_INVALID, "srz_frameset_render: output must be 16-byte aligned");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = pick_stream(ctx, stream);
-  flags &= SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER;
-  return render_impl(ctx, fs, (float *)d_out, flags, s, false);
+  return render_entry("srz_frameset_render", ctx, fs, d_out, out_bytes, flags, stream, Pass::colour());
 }
 
 int srz_frameset_render_visibility(srz_ctx *ctx, srz_frameset *fs, void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
-  if (!ctx) return SRZ_E_INVALID;
-  if (!fs || !d_out) return fail(ctx, SRZ_E_INVALID, "srz_frameset_render_visibility: null frameset / output");
-  if (out_bytes < srz_frameset_out_bytes(ctx, fs)) return fail(ctx, SRZ_E_INVALID, "srz_frameset_render_visibility: output buffer too small");
-  if (((uintptr_t)d_out & 15u) != 0) return fail(ctx, SRZ_E_INVALID, "srz_frameset_render_visibility: output must be 16-byte aligned");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = pick_stream(ctx, stream);
-  flags &= SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER;
-  return render_impl(ctx, fs, (float *)d_out, flags, s, false, false, false, 0, -1, /*visibility=*/true);
+  return render_entry("srz_frameset_render_visibility", ctx, fs, d_out, out_bytes, flags, stream, Pass::visibility());
 }
 
 int srz_frameset_resolve8(srz_ctx *ctx, const srz_frameset *fs, const void *d_planes, void *d_bgr8, size_t bgr8_bytes, void *stream) {
@@ -1316,7 +1321,7 @@ int srz_frameset_stats(srz_ctx *ctx, srz_frameset *fs, srz_stats *stats) {
   // frames of 1024^2)
   float *d_out = nullptr;
   HIP_TRY(ctx, hipMalloc(&d_out, srz_frameset_out_bytes(ctx, fs) / (size_t)std::max(fs->n_frames, 1)));
-  int rc = render_impl(ctx, fs, d_out, SRZ_FUSED_CLEAR, ctx->stream, true, true);
+  int rc = render_impl(ctx, fs, d_out, SRZ_FUSED_CLEAR, ctx->stream, Pass::counting_into_one_frame());
   if (rc == SRZ_OK) rc = read_stats(ctx, ctx->stream, stats);
   (void)hipFree(d_out);
   if (rc == SRZ_OK) fs->stats = *stats, fs->have_stats = true;
@@ -1430,12 +1435,7 @@ int srz_frameset_debug_counters(srz_ctx *ctx, srz_frameset *fs, uint32_t *out6) 
   HIP_TRY(ctx, hipDeviceSynchronize());
   uint32_t h[2] = {0, 0};
   HIP_TRY(ctx, hipMemcpy(h, fs->d_slow_count, sizeof h, hipMemcpyDeviceToHost));
-  uint32_t need = 0;
-  for (uint32_t i = 0; i < fs->pool_n_sub * (uint32_t)srz_frameset::DEMAND_PARTS; ++i) {
-    const uint32_t v = static_cast<volatile uint32_t *>(fs->h_pool_heads)[((i / fs->pool_n_sub) * 64u + i % fs->pool_n_sub) * CNT_STRIDE];
-    if (v > need) need = v;
-  }
-  out6[0] = h[0], out6[1] = h[1], out6[2] = fs->pool_sub_cap, out6[3] = need;
+  out6[0] = h[0], out6[1] = h[1], out6[2] = fs->pool_sub_cap, out6[3] = max_pool_demand(fs, 0, srz_frameset::DEMAND_PARTS);
   const uint32_t decided = fs->clear_tune.h_wgs ? *static_cast<volatile uint32_t *>(fs->clear_tune.h_wgs) : 0u;
   out6[4] = ctx->env_clear_wgs ? ctx->env_clear_wgs : (decided ? decided : fs->clear_tune.wgs), out6[5] = (fs->clear_tune.done || decided) ? 1u : 0u;
   return SRZ_OK;
@@ -1714,7 +1714,7 @@ int srz_frameset_sparse_unpack(srz_ctx *ctx, const srz_frameset *fs, const void 
   if (what == SRZ_EXCHANGE_PLANES && ((uintptr_t)d_gathered & 3u)) return fail(ctx, SRZ_E_INVALID, "srz_frameset_sparse_unpack: misaligned buffer");
   if (fs->shard_world == 1) return SRZ_OK; // (no peers)
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  launch_sparse_unpack(a, d_recv, msg_stride, d_gathered, ctx->env_unpack_wgs, pick_stream(ctx, stream));
+  launch_sparse_unpack(a, d_recv, msg_stride, d_gathered, pick_stream(ctx, stream));
   HIP_TRY(ctx, hipGetLastError());
   return SRZ_OK;
 }
@@ -1869,7 +1869,7 @@ static int draw_impl(srz_ctx *ctx, int primitive, const srz_frame *frame, const 
     for (int p = 0; p < 4 && e == hipSuccess; ++p) e = hipMemcpyAsync(d_out + p * plane, host[p], pb, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) {
     if (stats) rc = stats_pass(ctx, fs, fused ? nullptr : d_out, 0, s, stats);
-    if (rc == SRZ_OK) rc = render_impl(ctx, fs, d_out, 0, s, false);
+    if (rc == SRZ_OK) rc = render_impl(ctx, fs, d_out, 0, s, Pass::colour());
   }
   // (planes the caller page-locked with srz_host_register move by DMA straight from / to his memory; pageable ones through the
   // runtime's staging buffers.  SRZ_NO_Z_READBACK: the depth plane stays on the device)
@@ -1900,6 +1900,9 @@ int srz_draw_batch(srz_ctx *ctx, int primitive, const srz_frame *frames, int n_f
   for (int f = 0; f < n_frames; ++f)
     if (!planes[f]) return fail(ctx, SRZ_E_INVALID, "srz_draw_batch: null plane pointer");
   if (ctx->shard_world != 1) return fail(ctx, SRZ_E_INVALID, "srz_draw_batch: whole-frame draw needs an unsharded ctx");
+  HIP_TRY(ctx, hipSetDevice(ctx->device)); // (the read-back stream first: a set is never left behind by its failure)
+  if (!ctx->stream3)
+    if (int rc = create_side(ctx, "srz_draw_batch", &ctx->stream3, false, ctx->ev_piece)) return rc;
   srz_frameset *fs = nullptr;
   int rc = srz_frameset_create(ctx, frames, n_frames, &fs);
   if (rc) return rc;
@@ -1922,10 +1925,6 @@ int srz_draw_batch(srz_ctx *ctx, int primitive, const srz_frame *frames, int n_f
   // back to the caller's planes while piece k + 1 renders (and, for accumulate-mode frames, while its planes go up) — with planes
   // the caller page-locked (srz_host_register) both directions are DMA at the link's rate, pageable ones go through the runtime's
   // staging copies.  A counting run (stats) renders in one piece first.
-  if (!ctx->stream3) {
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking));
-    for (int i = 0; i < srz_ctx::EV_RING; ++i) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_piece[i], hipEventDisableTiming));
-  }
   const int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, ((size_t)128 << 20) / fb));
   const int n_pieces = (n_frames + per - 1) / per;
   const size_t plane_b = fb / 4;
@@ -1953,7 +1952,7 @@ int srz_draw_batch(srz_ctx *ctx, int primitive, const srz_frame *frames, int n_f
         if (!(frames[f].flags & SRZ_FUSED_CLEAR))
           e = hipMemcpyAsync(reinterpret_cast<uint8_t *>(d_out) + fb * f, planes[f], fb, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) break;
-    rc = render_impl(ctx, fs, d_out, 0, s, false, false, false, f0, n);
+    rc = render_impl(ctx, fs, d_out, 0, s, Pass::colour_frames(f0, n));
     if (rc != SRZ_OK) break;
     e = hipEventRecord(ctx->ev_piece[k % srz_ctx::EV_RING], s); // (slot k % 8 was last waited for by piece k - 8's read-back, issued long ago)
     if (k > 0) read_back(k - 1);

@@ -218,7 +218,7 @@ void launch_setup(const RenderArgs &a, int n_frames, uint32_t max_tris, bool sta
 void launch_bin(const RenderArgs &a, int n_frames, uint32_t max_tris, hipStream_t s);
 void launch_raster(const RenderArgs &a, int n_frames, bool stats, hipStream_t s);
 bool raster_four_waves(const RenderArgs &a); // the latency build of k_raster serves this job (it also reports the pool's demand)
-void launch_clear(const RenderArgs &a, uint32_t max_tiles, bool beside_raster, hipStream_t s, uint32_t wgs);
+void launch_clear(const RenderArgs &a, uint32_t max_tiles, hipStream_t s, uint32_t wgs);
 void launch_shade(const RenderArgs &a, uint32_t max_tiles, bool stats, uint32_t fast_mask, bool any_generic, bool approx, hipStream_t s);
 // the visibility buffer (srz_frameset_render_visibility) in place of launch_shade: planes 1..3 of every owned tile
 void launch_visibility(const RenderArgs &a, uint32_t max_tiles, hipStream_t s);
@@ -229,7 +229,7 @@ void launch_deinterleave(const void *gathered, void *full, uint32_t world, uint3
 // ---- tile-sparse exchange (srz_frameset_sparse_*, message format: include/srz.h) -------------------------------------------------
 constexpr uint32_t SPARSE_HEADER = 16;          // {touched tiles u32, table entries u32, message bytes u64}
 constexpr uint32_t SPARSE_NONE = 0xffffffffu;   // table entry of a tile that is not in the payload (the clear values)
-constexpr uint32_t SPARSE_UNPACK_WGS = 2048;    // k_sparse_unpack's grid (SRZ_UNPACK_WGS overrides it: tools/sparse_exchange_probe.py)
+constexpr uint32_t SPARSE_UNPACK_WGS = 2048;    // k_sparse_unpack's grid
 struct SparseArgs {
   const void *shard;            // pack: this rank's shard [frame][plane][local_rows][row bytes]
   uint8_t *msg;                 // pack: the message
@@ -243,7 +243,7 @@ struct SparseArgs {
   uint64_t payload_off;         // bytes in front of the payload (header + table, 16-byte aligned)
 };
 void launch_sparse_pack(const SparseArgs &a, hipStream_t s);
-void launch_sparse_unpack(const SparseArgs &a, const void *recv, uint64_t msg_stride, void *gathered, uint32_t wgs, hipStream_t s);
+void launch_sparse_unpack(const SparseArgs &a, const void *recv, uint64_t msg_stride, void *gathered, hipStream_t s);
 void launch_verify_fastmath(unsigned long long *d_out4, hipStream_t s);
 void launch_verify_fastdiv(unsigned long long *d_out3, hipStream_t s);
 void launch_verify_fastpow(unsigned long long *d_out3, float p, hipStream_t s);

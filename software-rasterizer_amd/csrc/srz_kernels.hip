@@ -3038,10 +3038,10 @@ void launch_sparse_pack(const SparseArgs &a, hipStream_t s) {
   else if (unit == 4u) hipLaunchKernelGGL(k_sparse_pack<uint32_t>, dim3(n_tab), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(k_sparse_pack<uint8_t>, dim3(n_tab), dim3(256), 0, s, a);
 }
-void launch_sparse_unpack(const SparseArgs &a, const void *recv, uint64_t msg_stride, void *gathered, uint32_t wgs, hipStream_t s) {
+void launch_sparse_unpack(const SparseArgs &a, const void *recv, uint64_t msg_stride, void *gathered, hipStream_t s) {
   const uint32_t n_items = (a.world - 1u) * a.n_frames * a.bands_per_rank * a.planes;
   if (!n_items) return;
-  const uint32_t grid = std::min(n_items, wgs ? wgs : SPARSE_UNPACK_WGS);
+  const uint32_t grid = std::min(n_items, SPARSE_UNPACK_WGS);
   const uint32_t unit = sparse_unit(a.row_bytes, (uintptr_t)recv | (uintptr_t)gathered | (uintptr_t)msg_stride);
   const uint8_t *m = static_cast<const uint8_t *>(recv);
   if (unit == 16u) hipLaunchKernelGGL(k_sparse_unpack<u32x4>, dim3(grid), dim3(256), 0, s, a, m, msg_stride, static_cast<u32x4 *>(gathered));
@@ -3223,9 +3223,8 @@ void launch_setup(const RenderArgs &a, int n_frames, uint32_t max_tris, bool sta
 void launch_bin(const RenderArgs &a, int n_frames, uint32_t max_tris, hipStream_t s) {
   if (n_frames <= 0 || a.n_local_bands == 0) return;
   const uint32_t groups = ((uint32_t)n_frames + 7u) / 8u;
-  static const int env = getenv("SRZ_BIN_WAVES") ? atoi(getenv("SRZ_BIN_WAVES")) : 0;
   // (measured: 4 waves best at 5.9 k triangles, 8 at 94 k; a job with fewer band workgroups than CUs is pure latency: 8)
-  const int waves = env ? env : ((max_tris <= 32768u && (uint32_t)n_frames * a.n_local_bands > 256u) ? 4 : BIN_MAX_WAVES);
+  const int waves = (max_tris <= 32768u && (uint32_t)n_frames * a.n_local_bands > 256u) ? 4 : BIN_MAX_WAVES;
   const size_t lds = sizeof(uint32_t) * (3u * (size_t)a.tiles_x + 64u * waves + 4u + BIN_STAGE + 2u + 128u * waves * bin_keep((uint32_t)waves));
   hipLaunchKernelGGL(k_bin, dim3(groups * 8u * a.n_local_bands), dim3(64 * waves), lds, s, a);
 }
@@ -3300,92 +3299,78 @@ __global__ void k_clear_rebase(ClearCtl *c) {
 }
 void launch_clear_rebase(ClearCtl *ctl, hipStream_t s) { hipLaunchKernelGGL(k_clear_rebase, dim3(1), dim3(1), 0, s, ctl); }
 
-void launch_clear(const RenderArgs &a, uint32_t max_tiles, bool beside_raster, hipStream_t s, uint32_t wgs) {
+void launch_clear(const RenderArgs &a, uint32_t max_tiles, hipStream_t s, uint32_t wgs) {
   if (max_tiles == 0) return;
   // Beside k_raster/k_shade the clear is THROTTLED by its grid size, so that the stores spread over the whole pipeline instead of starving
   // the rasteriser's loads and the shader's register file.  The best grid depends on what runs beside it (config 2: 96 workgroups, 0.738
   // of the roofline against 0.727 at 80 and 0.681 at 128; config 4: 0.406 at 96, 0.438 at 256), so it is measured per set (srz_device.h,
   // ClearCtl: while that goes on the grid is CLEAR_GRID_MAX and a.clear_wgs_dev says how many of it work).  Work items are planes of bands.
   const uint32_t n_items = a.n_frames * a.n_local_bands * 4u;
-  const uint32_t cap = !beside_raster ? 2048u : (wgs ? wgs : 96u);
-  (void)max_tiles;
-  static const uint32_t env_thr = getenv("SRZ_CLEAR_THREADS") ? (uint32_t)atoi(getenv("SRZ_CLEAR_THREADS")) : 0u; // (A/B: 64 / 128 / 256)
-  const uint32_t thr = (beside_raster && env_thr) ? env_thr : 256u;
+  const uint32_t cap = wgs ? wgs : 96u;
   // (round 6, same box: the clear's stores as nt / sc1 nt / sc0 sc1 nt / sc1 / plain give config 4 3.10 / 3.22 / 3.26 / 3.29 / 3.29 ms per
   // step and config 5 5.25 / 5.48 / 5.44 / 5.71 / 5.62: nt, as round 3 found on config 2)
-  hipLaunchKernelGGL(k_clear, dim3(n_items < cap ? n_items : cap), dim3(thr), 0, s, a);
+  hipLaunchKernelGGL(k_clear, dim3(n_items < cap ? n_items : cap), dim3(256), 0, s, a);
+}
+
+// One stream: a LARGE grid (a tile or two per workgroup: in-order hand-out, one-tile tail).  Renders interleaved on several streams
+// (a.other_streams): a grid about as large as the machine's resident capacity, the workgroups striding through the lists — measured,
+// 2 x 128 frames of 1024^2 on two streams: 16384 workgroups 1.10 ms per batch, 4096 1.08, 2560 1.07, 1280 1.065 (and on ONE stream
+// 0.73 / 0.78 / — / 0.78 ms for k_shade alone).  A multiple of 8: workgroup b serves list b % 8.
+static dim3 shade_grid(const RenderArgs &a, uint32_t max_tiles) {
+  return dim3((std::min(max_tiles, a.other_streams ? 2048u : 16384u) + 7u) & ~7u);
 }
 
 void launch_shade(const RenderArgs &a, uint32_t max_tiles, bool stats, uint32_t fast_mask, bool any_generic, bool approx, hipStream_t s) {
   if (max_tiles == 0) return;
-  // One stream: a LARGE grid (a tile or two per workgroup: in-order hand-out, one-tile tail).  Renders interleaved on several
-  // streams (a.other_streams): a grid about as large as the machine's resident capacity, the workgroups striding through the
-  // lists — measured, 2 x 128 frames of 1024^2 on two streams: 16384 workgroups 1.10 ms per batch, 4096 1.08, 2560 1.07,
-  // 1280 1.065 (and on ONE stream 0.73 / 0.78 / — / 0.78 ms for k_shade alone)
-  static const uint32_t env_grid = getenv("SRZ_SHADE_GRID") ? (uint32_t)atoi(getenv("SRZ_SHADE_GRID")) : 0u;
-  const uint32_t gcap = env_grid ? env_grid : (a.other_streams ? 2048u : 16384u);
-  dim3 grid((std::min(max_tiles, gcap) + 7u) & ~7u); // (a multiple of 8: workgroup b serves list b % 8)
-  // SRZ_SHADE_LDS_PAD (diagnostic): bytes of unused dynamic LDS per workgroup — 1024 caps k_shade at five workgroups per CU, 6144 at
-  // four (26.3 KB static each, 160 KB per CU): how much room the other lane's k_raster waves find on a CU k_shade has filled
-  static const uint32_t pad = getenv("SRZ_SHADE_LDS_PAD") ? (uint32_t)atoi(getenv("SRZ_SHADE_LDS_PAD")) : 0u;
+  const dim3 grid = shade_grid(a, max_tiles);
   if (stats) { // (counting runs shade every frame with the generic build: force_generic)
-    hipLaunchKernelGGL((k_shade<true, 0>), grid, dim3(256), pad, s, a);
+    hipLaunchKernelGGL((k_shade<true, 0>), grid, dim3(256), 0, s, a);
     return;
   }
   // one FAST build per (light count, with / without BUMP or DISPLACEMENT batches) some frame of the set has:
   // fast_mask bit NL = plain, bit 8 + NL = with them
   if (approx) { // the tolerance mode's builds (classify_frames sets only the plain bits for the frames they shade)
-    if (fast_mask & 2u) hipLaunchKernelGGL((k_shade<false, 1, false, true>), grid, dim3(256), pad, s, a);
-    if (fast_mask & 4u) hipLaunchKernelGGL((k_shade<false, 2, false, true>), grid, dim3(256), pad, s, a);
-    if (fast_mask & 8u) hipLaunchKernelGGL((k_shade<false, 3, false, true>), grid, dim3(256), pad, s, a);
-    if (fast_mask & 16u) hipLaunchKernelGGL((k_shade<false, 4, false, true>), grid, dim3(256), pad, s, a);
+    if (fast_mask & 2u) hipLaunchKernelGGL((k_shade<false, 1, false, true>), grid, dim3(256), 0, s, a);
+    if (fast_mask & 4u) hipLaunchKernelGGL((k_shade<false, 2, false, true>), grid, dim3(256), 0, s, a);
+    if (fast_mask & 8u) hipLaunchKernelGGL((k_shade<false, 3, false, true>), grid, dim3(256), 0, s, a);
+    if (fast_mask & 16u) hipLaunchKernelGGL((k_shade<false, 4, false, true>), grid, dim3(256), 0, s, a);
     fast_mask = 0;
   }
-  if (fast_mask & 2u) hipLaunchKernelGGL((k_shade<false, 1, false>), grid, dim3(256), pad, s, a);
-  if (fast_mask & 4u) hipLaunchKernelGGL((k_shade<false, 2, false>), grid, dim3(256), pad, s, a);
-  if (fast_mask & 8u) hipLaunchKernelGGL((k_shade<false, 3, false>), grid, dim3(256), pad, s, a);
-  if (fast_mask & 16u) hipLaunchKernelGGL((k_shade<false, 4, false>), grid, dim3(256), pad, s, a);
-  if (fast_mask & 0x200u) hipLaunchKernelGGL((k_shade<false, 1, true>), grid, dim3(256), pad, s, a);
-  if (fast_mask & 0x400u) hipLaunchKernelGGL((k_shade<false, 2, true>), grid, dim3(256), pad, s, a);
-  if (fast_mask & 0x800u) hipLaunchKernelGGL((k_shade<false, 3, true>), grid, dim3(256), pad, s, a);
-  if (fast_mask & 0x1000u) hipLaunchKernelGGL((k_shade<false, 4, true>), grid, dim3(256), pad, s, a);
+  if (fast_mask & 2u) hipLaunchKernelGGL((k_shade<false, 1, false>), grid, dim3(256), 0, s, a);
+  if (fast_mask & 4u) hipLaunchKernelGGL((k_shade<false, 2, false>), grid, dim3(256), 0, s, a);
+  if (fast_mask & 8u) hipLaunchKernelGGL((k_shade<false, 3, false>), grid, dim3(256), 0, s, a);
+  if (fast_mask & 16u) hipLaunchKernelGGL((k_shade<false, 4, false>), grid, dim3(256), 0, s, a);
+  if (fast_mask & 0x200u) hipLaunchKernelGGL((k_shade<false, 1, true>), grid, dim3(256), 0, s, a);
+  if (fast_mask & 0x400u) hipLaunchKernelGGL((k_shade<false, 2, true>), grid, dim3(256), 0, s, a);
+  if (fast_mask & 0x800u) hipLaunchKernelGGL((k_shade<false, 3, true>), grid, dim3(256), 0, s, a);
+  if (fast_mask & 0x1000u) hipLaunchKernelGGL((k_shade<false, 4, true>), grid, dim3(256), 0, s, a);
   // ... and per light count with a non-integer exponent: bit 16 + NL
-  if (fast_mask & 0x20000u) hipLaunchKernelGGL((k_shade<false, -1, false>), grid, dim3(256), pad, s, a);
-  if (fast_mask & 0x40000u) hipLaunchKernelGGL((k_shade<false, -2, false>), grid, dim3(256), pad, s, a);
-  if (fast_mask & 0x80000u) hipLaunchKernelGGL((k_shade<false, -3, false>), grid, dim3(256), pad, s, a);
-  if (fast_mask & 0x100000u) hipLaunchKernelGGL((k_shade<false, -4, false>), grid, dim3(256), pad, s, a);
+  if (fast_mask & 0x20000u) hipLaunchKernelGGL((k_shade<false, -1, false>), grid, dim3(256), 0, s, a);
+  if (fast_mask & 0x40000u) hipLaunchKernelGGL((k_shade<false, -2, false>), grid, dim3(256), 0, s, a);
+  if (fast_mask & 0x80000u) hipLaunchKernelGGL((k_shade<false, -3, false>), grid, dim3(256), 0, s, a);
+  if (fast_mask & 0x100000u) hipLaunchKernelGGL((k_shade<false, -4, false>), grid, dim3(256), 0, s, a);
   // the generic build also serves the tiles the FAST builds hand back: when no frame is generic that is normally
   // nothing, and a small grid does
   dim3 ggrid(any_generic ? grid.x : (grid.x < 128u ? grid.x : 128u));
-  hipLaunchKernelGGL((k_shade<false, 0>), ggrid, dim3(256), pad, s, a);
+  hipLaunchKernelGGL((k_shade<false, 0>), ggrid, dim3(256), 0, s, a);
 }
 
 void launch_visibility(const RenderArgs &a, uint32_t max_tiles, hipStream_t s) {
   if (max_tiles == 0) return;
-  // (k_shade's grid: a tile or two per workgroup on one stream, about the resident capacity when renders interleave on several)
-  const uint32_t gcap = a.other_streams ? 2048u : 16384u;
-  hipLaunchKernelGGL(k_visibility, dim3((std::min(max_tiles, gcap) + 7u) & ~7u), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_visibility, shade_grid(a, max_tiles), dim3(256), 0, s, a);
 }
 
 bool raster_four_waves(const RenderArgs &a) { return a.n_frames * a.n_local_bands * a.tiles_x <= 4096u; }
 
 void launch_raster(const RenderArgs &a, int n_frames, bool stats, hipStream_t s) {
   if (n_frames <= 0 || a.n_local_bands == 0) return;
-  static bool once = false;
-  if (!once && getenv("SRZ_DEBUG")) {
-    once = true;
-    int nb = 0, ns = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_raster<1>, 64, 0);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&ns, (k_shade<false, 2>), 256, 0);
-    fprintf(stderr, "[srz] occupancy: k_raster %d waves/CU, k_shade %d WGs/CU\n", nb, ns);
-  }
   const uint32_t groups = ((uint32_t)n_frames + 7u) / 8u;
   const uint32_t tiles = groups * 8u * a.n_local_bands * a.tiles_x;
-  // a few frames: four waves per tile (the frame is as slow as its heaviest tile); batches: one wave per tile
-  if (raster_four_waves(a))
-    hipLaunchKernelGGL(k_raster<4>, dim3(tiles), dim3(256), 0, s, a);
-  else
+  // batches: one wave per tile; a few frames: four waves per tile (the frame is as slow as its heaviest tile)
+  if (!raster_four_waves(a))
     hipLaunchKernelGGL(k_raster<1>, dim3(tiles), dim3(64), 0, s, a);
+  else
+    hipLaunchKernelGGL(k_raster<4>, dim3(tiles), dim3(256), 0, s, a);
   // the ordered rasteriser for whatever k_raster listed (normally nothing: its waves read a zero and leave)
   // (a large grid whenever the ordered rasteriser is known to get every touched tile: counting runs, SRZ_ORDERED_RASTER on the
   // render or on some frame — a.any_ordered, set by the host)

@@ -11,8 +11,7 @@ and times it with device events, then unpacks every peer's message into rank 0's
     link — the figure DESIGN.md §6 uses, not measured on hardware here), local = render + pack + unpack on this GPU's HBM;
     step = max(link, local), frames/s = F·N / step — beside the dense in-place exchange's shard / 153 GB/s.
 
---unpack-grids sweeps k_sparse_unpack's grid (SRZ_UNPACK_WGS) on config 2, N = 8.  Its own time limit (--limit seconds, SIGALRM):
-no retries.  Usage:  python tools/sparse_exchange_probe.py [--configs 2,4,5] [--out FILE]
+Its own time limit (--limit seconds, SIGALRM): no retries.  Usage:  python tools/sparse_exchange_probe.py [--configs 2,4,5] [--out FILE]
 """
 import argparse
 import json
@@ -51,7 +50,7 @@ def timed(torch, fn, reps=5):
     return statistics.median(out)
 
 
-def run(cfg, world, frames, what, torch, srz, abi, parallel, tex, grids=(0,)):
+def run(cfg, world, frames, what, torch, srz, abi, parallel, tex):
     s = torch.cuda.current_stream().cuda_stream
     msgs, stats, keep = [], [], None
     h = frames[0].height
@@ -91,19 +90,8 @@ def run(cfg, world, frames, what, torch, srz, abi, parallel, tex, grids=(0,)):
     mine = sum(r1 - r0 for (_, _, r0, r1) in parallel.band_rows(h, 0, world))
     written = len(frames) * (h - mine) * row_bytes   # (the peers' real rows)
     read = sum(st["touched"] for st in stats[1:]) * lay["tile_bytes"]
-    unpack = {}
-    for wg in grids:
-        if wg:
-            os.environ["SRZ_UNPACK_WGS"] = str(wg)          # (read by srz_create: a fresh ctx of rank 0)
-            c2 = srz.Context(0, 0, world)
-            c2.texture_upload(0, tex)
-            f2 = c2.frameset(frames)
-            ms = timed(torch, lambda: f2.sparse_unpack(recv.data_ptr(), cap, g.data_ptr(), what, s))
-            f2.close(), c2.close()
-            del os.environ["SRZ_UNPACK_WGS"]
-        else:
-            ms = timed(torch, lambda: fs.sparse_unpack(recv.data_ptr(), cap, g.data_ptr(), what, s))
-        unpack[wg] = {"ms": ms, "hbm_frac": (written + read) / (ms * 1e-3) / (PEAK_TBS * 1e12), "write_tbs": written / (ms * 1e-3) / 1e12}
+    ms = timed(torch, lambda: fs.sparse_unpack(recv.data_ptr(), cap, g.data_ptr(), what, s))
+    unpack = {"ms": ms, "hbm_frac": (written + read) / (ms * 1e-3) / (PEAK_TBS * 1e12), "write_tbs": written / (ms * 1e-3) / 1e12}
     fs.close(), ctx.close()
     del g, recv
     torch.cuda.empty_cache()
@@ -114,7 +102,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="2,4,5")
     ap.add_argument("--worlds", default="2,4,8")
-    ap.add_argument("--unpack-grids", default="512,1024,2048,4096,8192")
     ap.add_argument("--limit", type=int, default=900)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -132,22 +119,21 @@ def main():
         frames = frames_of(cfg, n_frames, size)
         for world in (int(w) for w in a.worlds.split(",")):
             for what, name in ((abi.EXCHANGE_PLANES, "planes"), (abi.EXCHANGE_BGR8, "bgr8")):
-                grids = (0,) + tuple(int(x) for x in a.unpack_grids.split(",") if x) if (cfg == 2 and world == 8 and what == abi.EXCHANGE_PLANES) else (0,)
-                stats, unpack, written = run(cfg, world, frames, what, torch, srz, abi, parallel, tex, grids)
+                stats, unpack, written = run(cfg, world, frames, what, torch, srz, abi, parallel, tex)
                 frac = [st["msg_bytes"] / st["shard_bytes"] for st in stats]
                 scale = f_gpu * world / n_frames       # measured frames → F frames per GPU
                 link = max(st["msg_bytes"] for st in stats) * scale / (LINK_GBS * 1e9) * 1e3
                 dense_link = stats[0]["shard_bytes"] * scale / (LINK_GBS * 1e9) * 1e3
                 render = max(st["render_ms"] for st in stats) * scale
                 pack = max(st["pack_ms"] for st in stats) * scale
-                un = unpack[0]["ms"] * scale
+                un = unpack["ms"] * scale
                 step = max(link, render + pack + un)
                 row = {"config": cfg, "N": world, "exchange": name, "frames_measured": n_frames, "size": size, "F_per_gpu": f_gpu,
                        "msg_frac_mean": statistics.mean(frac), "msg_frac_max": max(frac),
                        "touched_frac": sum(st["touched"] for st in stats) / sum(st["tiles"] for st in stats),
                        "pack_ms": statistics.mean(st["pack_ms"] for st in stats), "pack_hbm_frac": statistics.mean(st["pack_hbm_frac"] for st in stats),
-                       "unpack_ms": unpack[0]["ms"], "unpack_hbm_frac": unpack[0]["hbm_frac"], "unpack_write_tbs": unpack[0]["write_tbs"],
-                       "unpack_grid_sweep": {str(k): v for k, v in unpack.items() if k}, "render_ms_max": max(st["render_ms"] for st in stats),
+                       "unpack_ms": unpack["ms"], "unpack_hbm_frac": unpack["hbm_frac"], "unpack_write_tbs": unpack["write_tbs"],
+                       "render_ms_max": max(st["render_ms"] for st in stats),
                        "predicted": {"link_ms": link, "render_ms": render, "pack_ms": pack, "unpack_ms": un, "step_ms": step,
                                      "frames_per_s": f_gpu * world / step * 1e3, "dense_link_ms": dense_link,
                                      "dense_frames_per_s": f_gpu * world / max(dense_link, render) * 1e3}}
