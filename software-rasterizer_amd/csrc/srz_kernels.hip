@@ -1276,48 +1276,62 @@ __device__ __forceinline__ void s_shade(M &m, const FrameK &K, const ShadeDesc &
   r2 = (q2 == q2) ? (float)(uint32_t)q2 : 0.0f;
 }
 
-// A tile that has an owner goes to one of 104 work lists for k_shade: [build that shades the frame: FAST for 1 / 2 / 3 / 4 lights,
-// the same for frames with BUMP / DISPLACEMENT batches, the same for frames with a non-integer exponent, generic][frame % 8]
-// (frame % 8 = the XCD that rasterised it), in arrival order — k_raster's workgroups run in frame order, so every list comes
-// out (roughly) frame by frame.  An entry = {frame, local band | tile x << 10 | flags (WORK_LP), entries of the tile's triangle
-// list, its first index in pool[]}: everything k_shade needs to start the tile's loads travels with it, and nothing has to be
-// divided out of a flat tile number (two scalar software divisions per tile otherwise).
-constexpr uint32_t WORK_LP = 1u << 20; // the tile's owner ids are POSITIONS in the tile's triangle list, 16 bits each (see LP_BITS)
-constexpr uint32_t WORK_LP8 = 1u << 21; // (with WORK_LP, round 6) ... 8 bits each: the list has at most LP8_MAX entries (see id_pack8)
-__device__ __forceinline__ void work_append(const RenderArgs &a, uint32_t frame_flags, uint32_t frame, uint32_t entry /* frame * tiles + tile */,
-                                            uint32_t lb, uint32_t tx, uint32_t wflags, uint32_t list_cnt, uint32_t list_off) {
+// ---- the hand-off: what the rasterisers (k_raster, k_raster_slow) leave for k_shade / k_visibility per OWNED tile -------------
+// 1. A WORK ENTRY in one of 104 work lists: [build that shades the frame: FAST for 1 / 2 / 3 / 4 lights, the same for frames with
+//    BUMP / DISPLACEMENT batches, the same for frames with a non-integer exponent, generic][frame % 8] (frame % 8 = the XCD that
+//    rasterised it), in arrival order — k_raster's workgroups run in frame order, so every list comes out (roughly) frame by frame.
+//    The lists exist only for the kinds the set's frames need: list [kind][sub] lives in storage slot work_slot(), the counters in
+//    work_count[] are indexed by kind * 8 + sub (all of them exist).  An entry = {frame, local band | tile x << 10 | WORK_LP |
+//    WORK_LP8, entries of the tile's triangle list, its first index in pool[]}: everything k_shade needs to start the tile's loads
+//    travels with it, and nothing has to be divided out of a flat tile number (two scalar software divisions per tile otherwise).
+// 2. The OWNER of every pixel, in the tile's slot of `vis` (PIX_SLOT entries, pixel p = ly * 32 + lx), in one of three widths:
+//    - 32 bits (no flag): its index in the frame | S_CLASS_BIT, NO_TRI = nobody — the ordered rasteriser, long lists;
+//    - 16 bits (WORK_LP): its POSITION in the tile's triangle list | 0x8000 for the S class, 0xffff = nobody — k_raster, tiles of at
+//      most LP_MAX list entries in frames of fewer than 2^22 - 1 triangles: the position rides in the low bits of the depth key's
+//      tie-break, below the triangle index, so the pixel's final key holds it for free.  k_shade then stages the list's triangles
+//      in LDS once per tile and every pixel reads its owner's 96 bytes from there instead of gathering them from memory; and a
+//      frame of 94 k triangles pays 2 bytes per pixel like one of 5 k;
+//    - 8 bits (WORK_LP | WORK_LP8): the same for lists of at most LP8_MAX entries (most tiles of every BASELINE config), position |
+//      0x80 for the S class, 0xff = nobody: 1 + 1 instead of 2 + 2 bytes per pixel of every owned tile written and read back, during
+//      the part of a step in which the memory system is what everything waits for (NOTEBOOK r6 §2).
+//    The S class: the pixel lies in the scalar-tail ("S") columns of its owner's bounding box.
+// 3. The tile's RECTANGLE in the framebuffer: tile_rect().
+// k_shade reads all three inline, in the same format: the helpers below, put into its tile loop, change its schedule (one form made
+// the early owner-id load wait at once), so its statements stay as they are measured.
+constexpr uint32_t WORK_LP = 1u << 20, WORK_LP8 = 1u << 21;
+constexpr uint32_t S_CLASS_BIT = 0x80000000u;
+constexpr uint32_t PIX_SLOT = TILE * TILE, PIX_BITS = 10, PIX_MASK = PIX_SLOT - 1u;
+constexpr uint32_t LP_BITS = 9, LP_MAX = 1u << LP_BITS; // (idx << 9 | position) <= 0x7ffffffe for idx < 2^22 - 1 (FD_PACKED)
+static_assert(31 - LP_BITS == PACK_IDX_BITS, "the tie-break holds an index of PACK_IDX_BITS bits above the list position");
+constexpr uint32_t LP8_MAX = 127;
+__device__ __forceinline__ uint32_t id_pack8(uint32_t id) { return id == NO_TRI ? 0xffu : ((id & 127u) | ((id >> 24) & 0x80u)); }
+__device__ __forceinline__ uint32_t id_pack16(uint32_t id) { return id == NO_TRI ? 0xffffu : ((id & (LP_MAX - 1u)) | ((id >> 16) & 0x8000u)); }
+
+__device__ __forceinline__ uint4 work_entry(uint32_t frame, uint32_t lb, uint32_t tx, bool by_lp, bool lp8, uint32_t cnt, uint32_t off) {
+  return make_uint4(frame, lb | (tx << 10) | (by_lp ? WORK_LP : 0u) | (lp8 ? WORK_LP8 : 0u), cnt, off);
+}
+struct Work {
+  uint32_t f, lb, tx, cnt, off;
+  bool by_lp, lp8; // the owner ids' width: 16 bits (by_lp), 8 (by_lp && lp8), else 32
+};
+__device__ __forceinline__ Work work_decode(u32x4 x) {
+  return {x.x, x.y & 1023u, (x.y >> 10) & 1023u, x.z, x.w, (x.y & WORK_LP) != 0u, (x.y & WORK_LP8) != 0u};
+}
+template <class A> __device__ __forceinline__ uint32_t work_slot(A &a, uint32_t kind, uint32_t sub) {
+  return ((uint32_t)(a.kind_slots >> (4u * kind)) & 15u) * 8u + sub;
+}
+__device__ __forceinline__ void work_append(const RenderArgs &a, uint32_t frame_flags, uint32_t entry /* frame * tiles + tile */, const uint4 &w) {
   // (fewer than 8 frames: the tiles are dealt over the 8 lists instead, so that every XCD has work)
   const uint32_t kind = (!a.force_generic && (frame_flags & FD_FAST_SHADE) != 0u)
                             ? ((frame_flags >> FD_NL_SHIFT) & 7u) - 1u + ((frame_flags & FD_BUMPY) ? 4u : 0u) + ((frame_flags & FD_GENPOW) ? 8u : 0u)
                             : SHADE_KIND_GENERIC;
-  const uint32_t sub = (a.n_frames >= 8u ? frame : frame + entry) & 7u, L = kind * 8u + sub;
-  const uint32_t Ls = ((uint32_t)(a.kind_slots >> (4u * kind)) & 15u) * 8u + sub; // (the kind's slot in the lists' storage)
-  a.worklist[(size_t)Ls * a.work_cap + atomicAdd(&a.work_count[L * CNT_STRIDE], 1u)] = make_uint4(frame, lb | (tx << 10) | wflags, list_cnt, list_off);
+  const uint32_t sub = (a.n_frames >= 8u ? w.x : w.x + entry) & 7u;
+  a.worklist[(size_t)work_slot(a, kind, sub) * a.work_cap + atomicAdd(&a.work_count[(kind * 8u + sub) * CNT_STRIDE], 1u)] = w;
 }
 
-// bit 31 of an owner id: the pixel lies in the scalar-tail ("S") columns of its owner's bounding box
-constexpr uint32_t S_CLASS_BIT = 0x80000000u;
-
-// What the rasterisers hand to k_shade per OWNED tile: the owner of every pixel, in the tile's slot of `vis` (PIX_SLOT dwords,
-// pixel p = ly * 32 + lx).  The owner is named
-//   by its POSITION in the tile's triangle list, 16 bits per pixel (position | 0x8000 for the S class, 0xffff = nobody) — k_raster,
-//      tiles of at most LP_MAX list entries in frames of fewer than 2^22 - 1 triangles: the position rides in the low bits of the
-//      depth key's tie-break, below the triangle index, so the pixel's final key holds it for free (work entry flag WORK_LP).
-//      k_shade then stages the list's triangles in LDS once per tile and every pixel reads its owner's 96 bytes from there
-//      instead of gathering them from memory; and a frame of 94 k triangles pays 2 bytes per pixel like one of 5 k;
-//   or by its index in the frame, 32 bits per pixel (index | S_CLASS_BIT, NO_TRI = nobody) — the ordered rasteriser, long lists.
-constexpr uint32_t PIX_SLOT = TILE * TILE, PIX_BITS = 10, PIX_MASK = PIX_SLOT - 1u;
-constexpr uint32_t LP_BITS = 9, LP_MAX = 1u << LP_BITS; // (idx << 9 | position) <= 0x7ffffffe for idx < 2^22 - 1 (FD_PACKED)
-static_assert(31 - LP_BITS == PACK_IDX_BITS, "the tie-break holds an index of PACK_IDX_BITS bits above the list position");
-// ... or, for lists of at most LP8_MAX entries (most tiles of every BASELINE config), 8 bits per pixel (position | 0x80 for the S class,
-// 0xff = nobody): the ids are written by k_raster and read back by k_shade, 1 + 1 instead of 2 + 2 bytes per pixel of every owned tile —
-// during the part of a step in which the memory system is what everything waits for (NOTEBOOK r6 §2)
-constexpr uint32_t LP8_MAX = 127;
-__device__ __forceinline__ uint32_t id_pack8(uint32_t id) { return id == NO_TRI ? 0xffu : ((id & 127u) | ((id >> 24) & 0x80u)); }
-__device__ __forceinline__ uint32_t id_pack16(uint32_t id) { return id == NO_TRI ? 0xffffu : ((id & (LP_MAX - 1u)) | ((id >> 16) & 0x8000u)); }
-__device__ __forceinline__ uint32_t id_unpack16(uint32_t h) { return h == 0xffffu ? NO_TRI : ((h & (LP_MAX - 1u)) | ((h & 0x8000u) << 16)); }
-// the four owners of pixels p0 .. p0 + 3 of a tile (p0 % 4 == 0) into / out of its slot
-__device__ __forceinline__ void ids_store4(uint32_t *slot, uint32_t p0, const uint4 &id, bool by_lp, bool lp8 = false) {
+// the owners of pixels p0 .. p0 + 3 of a tile (p0 % 4 == 0) into / out of its slot.  Reading is two steps: the raw load, and
+// ids_unpack4 into one id per pixel in the width's own code (compared with id_none / id_sbit, never widened)
+__device__ __forceinline__ void ids_store4(uint32_t *slot, uint32_t p0, const uint4 &id, bool by_lp, bool lp8) {
   if (lp8) {
     *reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(slot) + p0) = id_pack8(id.x) | (id_pack8(id.y) << 8) | (id_pack8(id.z) << 16) | (id_pack8(id.w) << 24);
   } else if (by_lp) {
@@ -1327,12 +1341,44 @@ __device__ __forceinline__ void ids_store4(uint32_t *slot, uint32_t p0, const ui
     *reinterpret_cast<uint4 *>(slot + p0) = id;
   }
 }
-__device__ __forceinline__ uint4 ids_load4(const uint32_t *slot, uint32_t p0, bool by_lp) {
-  if (by_lp) {
+__device__ __forceinline__ uint4 ids_load_raw(const uint32_t *slot, uint32_t p0, bool by_lp, bool lp8) {
+  uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+  if (lp8) {
+    raw.x = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(slot) + p0);
+  } else if (by_lp) {
     const u32x2 w = *reinterpret_cast<const u32x2 *>(reinterpret_cast<const uint16_t *>(slot) + p0);
-    return make_uint4(id_unpack16(w.x & 0xffffu), id_unpack16(w.x >> 16), id_unpack16(w.y & 0xffffu), id_unpack16(w.y >> 16));
+    raw.x = w.x, raw.y = w.y;
+  } else {
+    raw = *reinterpret_cast<const uint4 *>(slot + p0);
   }
-  return *reinterpret_cast<const uint4 *>(slot + p0);
+  return raw;
+}
+__device__ __forceinline__ void ids_unpack4(const uint4 &raw, bool by_lp, bool lp8, uint32_t id[4]) {
+  id[0] = raw.x, id[1] = raw.y, id[2] = raw.z, id[3] = raw.w;
+  if (lp8)
+    id[0] = raw.x & 0xffu, id[1] = (raw.x >> 8) & 0xffu, id[2] = (raw.x >> 16) & 0xffu, id[3] = raw.x >> 24;
+  else if (by_lp)
+    id[0] = raw.x & 0xffffu, id[1] = raw.x >> 16, id[2] = raw.y & 0xffffu, id[3] = raw.y >> 16;
+}
+__device__ __forceinline__ uint32_t id_none(bool by_lp, bool lp8) { return lp8 ? 0xffu : by_lp ? 0xffffu : NO_TRI; }
+__device__ __forceinline__ uint32_t id_sbit(bool by_lp, bool lp8) { return lp8 ? 0x80u : by_lp ? 0x8000u : S_CLASS_BIT; }
+
+// A tile's pixels [tx0, tx1] x [ty0, ty1] (frame coordinates, clipped to the frame), the floats between two planes of `out`, and
+// plane 0 (z) at row ty0 (local band lb's first row).  `A` is RenderArgs or k_shade's kernarg view of it.
+struct TileRect {
+  int tx0, ty0, tx1, ty1;
+  size_t plane;
+  float *out0;
+};
+template <class A>
+__device__ __forceinline__ TileRect tile_rect(A &a, const SRZ_CAS FrameDesc *fd, uint32_t frame, uint32_t lb, uint32_t tx) {
+  const int W = fd->width, H = fd->height;
+  TileRect r;
+  r.tx0 = (int)tx * TILE, r.ty0 = band_of((int)lb, a.shard_rank, a.shard_world) * BAND;
+  r.tx1 = min(r.tx0 + TILE, W) - 1, r.ty1 = min(r.ty0 + BAND, H) - 1;
+  r.plane = (size_t)a.local_rows * (size_t)W;
+  r.out0 = a.out + (size_t)frame * a.frame_stride + (size_t)lb * BAND * (size_t)W;
+  return r;
 }
 
 // Everything the shader needs about the owner triangle of one pixel, fetched in ONE round trip (7 independent loads)
@@ -1508,6 +1554,36 @@ __device__ __forceinline__ void store_nt(float *p, const float4 &v) {
   f32x4 w = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(w, reinterpret_cast<f32x4 *>(p));
 }
+// The quads of N planes `plane` floats apart: pixels x4 .. x4 + 3 of a row at p, p + plane, ... — one 16-byte access per plane if
+// the quad is whole, else the pixels up to tx1, pixel by pixel (a frame whose width is not a multiple of 4 has no aligned quads; a
+// tile's last quad may end at the frame's edge)
+__device__ __forceinline__ float &quad_at(float4 &v, int k) { return reinterpret_cast<float *>(&v)[k]; } // (k: a constant)
+__device__ __forceinline__ float quad_at(const float4 &v, int k) { return reinterpret_cast<const float *>(&v)[k]; }
+template <int N> __device__ __forceinline__ void quad_store(float *p, size_t plane, const float4 (&v)[N], bool whole, int x4, int tx1) {
+  if (whole) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) store_nt(p + i * plane, v[i]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (x4 + k <= tx1)
+#pragma unroll
+        for (int i = 0; i < N; ++i) p[i * plane + k] = quad_at(v[i], k);
+  }
+}
+// (pixels beyond tx1 keep what v holds)
+template <int N> __device__ __forceinline__ void quad_load(const float *p, size_t plane, float4 (&v)[N], bool whole, int x4, int tx1) {
+  if (whole) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = *reinterpret_cast<const float4 *>(p + i * plane);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (x4 + k <= tx1)
+#pragma unroll
+        for (int i = 0; i < N; ++i) quad_at(v[i], k) = p[i * plane + k];
+  }
+}
 // order-preserving image of binary32 in u32 (-0 just below +0, negative NaNs below -inf, positive NaNs above +inf)
 __device__ __forceinline__ uint32_t zkey_of(float z) {
   const uint32_t b = f2u(z);
@@ -1565,24 +1641,20 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 5 : 1) void k_raster(Rende
   const uint32_t flags = fd->flags | a.flags_or;
   if (cnt == 0u) {
     if (flags & SRZ_FUSED_CLEAR) {
-      const int W = fd->width, H = fd->height;
-      const uint32_t lb = tile / a.tiles_x;
-      const int tx0 = (int)(tile % a.tiles_x) * TILE, ty0 = band_of((int)lb, a.shard_rank, a.shard_world) * BAND;
-      const int tx1 = min(tx0 + TILE, W) - 1, ty1 = min(ty0 + BAND, H) - 1;
-      const size_t plane = (size_t)a.local_rows * (size_t)W;
-      float *out0 = a.out + (size_t)frame * a.frame_stride + (size_t)lb * BAND * (size_t)W;
+      const int W = fd->width;
+      const TileRect rc = tile_rect(a, fd, frame, tile / a.tiles_x, tile % a.tiles_x);
       const float inf = __builtin_inff();
       const float4 inf4 = make_float4(inf, inf, inf, inf), zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
       for (int k = 0; k < ITS; ++k) {
         const int it = wave * ITS + k;
-        const int ly = it * 8 + (lane >> 3), x4 = tx0 + (lane & 7) * 4;
-        if (ty0 + ly > ty1 || x4 > tx1) continue;
-        float *gz = out0 + (size_t)ly * W + x4;
-        if (((W & 3) == 0) && x4 + 3 <= tx1) {
-          store_nt(gz, inf4), store_nt(gz + plane, zero4), store_nt(gz + 2 * plane, zero4), store_nt(gz + 3 * plane, zero4);
+        const int ly = it * 8 + (lane >> 3), x4 = rc.tx0 + (lane & 7) * 4;
+        if (rc.ty0 + ly > rc.ty1 || x4 > rc.tx1) continue;
+        float *gz = rc.out0 + (size_t)ly * W + x4;
+        if (((W & 3) == 0) && x4 + 3 <= rc.tx1) {
+          store_nt(gz, inf4), store_nt(gz + rc.plane, zero4), store_nt(gz + 2 * rc.plane, zero4), store_nt(gz + 3 * rc.plane, zero4);
         } else {
-          for (int k = 0; k < 4 && x4 + k <= tx1; ++k) gz[k] = inf, gz[plane + k] = 0.f, gz[2 * plane + k] = 0.f, gz[3 * plane + k] = 0.f;
+          for (int k = 0; k < 4 && x4 + k <= rc.tx1; ++k) gz[k] = inf, gz[rc.plane + k] = 0.f, gz[2 * rc.plane + k] = 0.f, gz[3 * rc.plane + k] = 0.f;
         }
       }
     }
@@ -1597,15 +1669,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 5 : 1) void k_raster(Rende
     if (lane == 0 && wave == 0) a.slow_list[atomicAdd(a.slow_count, 1u)] = frame * tiles_per_frame + tile;
     return;
   }
-  const uint32_t lb = tile / a.tiles_x;
-  const int W = fd->width, H = fd->height;
-  const int tx0 = (int)(tile % a.tiles_x) * TILE;
-  const int band = band_of((int)lb, a.shard_rank, a.shard_world);
-  const int ty0 = band * BAND;
-  const int tx1 = min(tx0 + TILE, W) - 1, ty1 = min(ty0 + BAND, H) - 1;
+  const uint32_t lb = tile / a.tiles_x, tx = tile % a.tiles_x;
+  const int W = fd->width;
+  const TileRect rc = tile_rect(a, fd, frame, lb, tx);
   const bool fused = (flags & SRZ_FUSED_CLEAR) != 0;
-  const size_t row0 = (size_t)lb * BAND;
-  float *out0 = a.out + (size_t)frame * a.frame_stride + row0 * (size_t)W; // plane 0 (z), row ty0
 
   // (the first 64 indices of the tile's list are loaded under the tile init)
   const uint32_t i_first = as_const(a.pool)[off + min((uint32_t)lane, cnt - 1u)] & idx_mask;
@@ -1619,7 +1686,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 5 : 1) void k_raster(Rende
     for (int i = (int)threadIdx.x; i < TILE * TILE; i += 64 * WAVES) {
       const int ly = i >> 5, lx = i & 31;
       float z = __builtin_inff();
-      if (tx0 + lx <= tx1 && ty0 + ly <= ty1) z = out0[(size_t)ly * W + tx0 + lx];
+      if (rc.tx0 + lx <= rc.tx1 && rc.ty0 + ly <= rc.ty1) z = rc.out0[(size_t)ly * W + rc.tx0 + lx];
       const uint32_t zk = (z == z) ? zkey_of(z) : 0u; // a NaN already in the buffer: only the ordered algorithm knows
       s_key[ly * KEY_STRIDE + lx] = ((unsigned long long)zk << 32) | TB_NONE;
     }
@@ -1649,7 +1716,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 5 : 1) void k_raster(Rende
     // r0 = ax ay z0 bx | r1 = by z1 cx cy | r2 = z2 bbx bby -
     const uint32_t bbx = f2u(r2.y), bby = f2u(r2.z);
     const int bsx = (int16_t)(bbx & 0xffff), bsy = (int16_t)(bbx >> 16), bex = (int16_t)(bby & 0xffff), bey = (int16_t)(bby >> 16);
-    int x0 = max(bsx, tx0) - tx0, x1 = min(bex, tx1) - tx0, y0 = max(bsy, ty0) - ty0, y1 = min(bey, ty1) - ty0;
+    int x0 = max(bsx, rc.tx0) - rc.tx0, x1 = min(bex, rc.tx1) - rc.tx0, y0 = max(bsy, rc.ty0) - rc.ty0, y1 = min(bey, rc.ty1) - rc.ty0;
     // the rectangle that is walked: bounding box ∩ tile, tightened to the triangle (see tight_margin): the triangle's x-extent
     // inside the rectangle's rows, then its y-extent inside the remaining columns.  About half of the pixel tests of a large
     // triangle and 30 % of a small one's go away (the integer box starts at trunc(min), a column / row before the first pixel
@@ -1658,16 +1725,16 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 5 : 1) void k_raster(Rende
       const float ax = r0.x, ay = r0.y, bx = r0.w, by = r1.x, cx = r1.z, cy = r1.w;
       float m, mn, mx;
       if (tight_margin(ax, ay, bx, by, cx, cy, s_area, bsx, bsy, bex, bey, m)) {
-        int X0 = tx0 + x0, X1 = tx0 + x1, Y0 = ty0 + y0, Y1 = ty0 + y1;
+        int X0 = rc.tx0 + x0, X1 = rc.tx0 + x1, Y0 = rc.ty0 + y0, Y1 = rc.ty0 + y1;
         slab_extent(ax, ay, bx, by, cx, cy, (float)Y0 - m, (float)Y1 + m, mn, mx);
         clip_range(X0, X1, mn, mx, m);
         slab_extent(ay, ax, by, bx, cy, cx, (float)X0 - m, (float)X1 + m, mn, mx);
         clip_range(Y0, Y1, mn, mx, m);
-        x0 = X0 - tx0, x1 = X1 - tx0, y0 = Y0 - ty0, y1 = Y1 - ty0;
+        x0 = X0 - rc.tx0, x1 = X1 - rc.tx0, y0 = Y0 - rc.ty0, y1 = Y1 - rc.ty0;
       }
     }
     const int vend = (flags & SRZ_UNIFIED) ? bex + 1 : bsx + ((bex - bsx + 1) & ~7);
-    const int v = min(max(vend - tx0, x0), x1 + 1);
+    const int v = min(max(vend - rc.tx0, x0), x1 + 1);
     Geo g;
     g.ok = valid && x0 <= x1 && y0 <= y1;
     const uint32_t h = g.ok ? (uint32_t)(y1 - y0 + 1) : 0u, nseg = (uint32_t)(v - x0 + 7) >> 3, ws = (uint32_t)(x1 + 1 - v);
@@ -1776,7 +1843,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 5 : 1) void k_raster(Rende
       const uint32_t row = (uint32_t)(((float)i + 0.5f) * __builtin_amdgcn_rcpf((float)ns)), seg = i - __umul24(row, ns);
       const uint32_t yl = ((g >> 5) & 31u) + row, xs = (g & 31u) + 8u * seg;
       const int lim = item < TV ? (int)((g >> 10) & 63u) - (int)xs : 0; // pixels of this piece inside the V columns
-      const float fy = (float)(ty0 + (int)yl), fx0 = (float)(tx0 + (int)xs);
+      const float fy = (float)(rc.ty0 + (int)yl), fx0 = (float)(rc.tx0 + (int)xs);
       const float PBy = by - fy, PCy = cy - fy, PAy = ay - fy;
       unsigned long long *kp = s_key + ((yl << 5) + yl) + xs; // yl * KEY_STRIDE
       const uint32_t tb = 0x80000000u | idx;
@@ -1827,7 +1894,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 5 : 1) void k_raster(Rende
       const uint32_t piece = (uint32_t)(((float)i + 0.5f) * __builtin_amdgcn_rcpf((float)w)), col = i - __umul24(piece, w);
       const uint32_t yl0 = ((g >> 5) & 31u) + S_ROWS * piece, xl = ((g >> 10) & 63u) + col;
       const int lim = item < TS ? (int)((g >> 22) & 31u) + 1 - (int)(S_ROWS * piece) : 0; // rows of this piece inside the rectangle
-      const float fy0 = (float)(ty0 + (int)yl0), fx = (float)(tx0 + (int)xl);
+      const float fy0 = (float)(rc.ty0 + (int)yl0), fx = (float)(rc.tx0 + (int)xl);
       // the reference's expressions per pixel; what depends on x alone is the same for the piece's pixels.  P?x = ?x - fx is the exact
       // negative of ?Px = fx - ?x, and a product of two negated factors is the product: aPBC = PBx * PCy - PBy * PCx = BPx * CPy - BPy * CPx
       const float ABx = bx - ax, ABy = by - ay, BCx = cx - bx, BCy = cy - by, CAx = ax - cx, CAy = ay - cy;
@@ -1913,46 +1980,27 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 5 : 1) void k_raster(Rende
   }
   const bool vec_ok = (W & 3) == 0;
   if (tile_has_owner || fused) {
-    const size_t plane = (size_t)a.local_rows * (size_t)W;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     uint32_t *slot = a.vis + ((size_t)frame * tiles_per_frame + tile) * PIX_SLOT;
 #pragma unroll
     for (int it = 0; it < ITS; ++it) {
       const int ly = (wave * ITS + it) * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
-      const int y = ty0 + ly, x4 = tx0 + lx4;
+      const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
       // the owners of ALL of the tile's pixels (those beyond the frame's edge have none: their keys never got a fragment);
       // re-read by k_shade: cacheable
       if (tile_has_owner) ids_store4(slot, (uint32_t)(ly * TILE + lx4), id4[it], lp_mode, lp8);
-      if (y > ty1 || x4 > tx1) continue;
-      float *gz = out0 + (size_t)ly * W + x4;
-      const bool full = vec_ok && x4 + 3 <= tx1;
-      if (tile_has_owner) {
-        if (full) {
-          store_nt(gz, z4[it]); // final: k_shade recomputes the depth it needs from the owner triangle
-        } else {
-#define SRZ_ST(K_, M)                                                                                                  \
-  if (x4 + K_ <= tx1) gz[K_] = z4[it].M;
-          SRZ_ST(0, x) SRZ_ST(1, y) SRZ_ST(2, z) SRZ_ST(3, w)
-#undef SRZ_ST
-        }
-      } else { // touched by a bbox but owned by nobody: the clear itself
-        if (full) {
-          store_nt(gz, z4[it]);
-          store_nt(gz + plane, zero4);
-          store_nt(gz + 2 * plane, zero4);
-          store_nt(gz + 3 * plane, zero4);
-        } else {
-#define SRZ_ST(K_, M)                                                                                                  \
-  if (x4 + K_ <= tx1) gz[K_] = z4[it].M, gz[plane + K_] = 0.f, gz[2 * plane + K_] = 0.f, gz[3 * plane + K_] = 0.f;
-          SRZ_ST(0, x) SRZ_ST(1, y) SRZ_ST(2, z) SRZ_ST(3, w)
-#undef SRZ_ST
-        }
-      }
+      if (y > rc.ty1 || x4 > rc.tx1) continue;
+      float *gz = rc.out0 + (size_t)ly * W + x4;
+      const bool full = vec_ok && x4 + 3 <= rc.tx1;
+      if (tile_has_owner)
+        quad_store(gz, rc.plane, {z4[it]}, full, x4, rc.tx1); // final: k_shade recomputes the depth it needs from the owner triangle
+      else // touched by a bbox but owned by nobody: the clear itself
+        quad_store(gz, rc.plane, {z4[it], zero4, zero4, zero4}, full, x4, rc.tx1);
     }
   }
   // owned tile → the frame's own work list (a counter per frame: one shared counter serialises ~10 ns per tile)
   if (tile_has_owner && lane == 0 && wave == 0)
-    work_append(a, fd->flags, frame, frame * tiles_per_frame + tile, lb, (uint32_t)tx0 / TILE, lp_mode ? (lp8 ? WORK_LP | WORK_LP8 : WORK_LP) : 0u, cnt, off);
+    work_append(a, fd->flags, frame * tiles_per_frame + tile, work_entry(frame, lb, tx, lp_mode, lp8, cnt, off));
 }
 
 // ================================================================================================================
@@ -1975,22 +2023,17 @@ __global__ __launch_bounds__(64) void k_raster_slow(RenderArgs a) {
     const uint32_t entry = as_const(a.slow_list)[e];
     const uint32_t frame = entry / tiles_per_frame, tile = entry % tiles_per_frame;
     const SRZ_CAS FrameDesc *fd = as_const(a.frames) + frame;
-    const uint32_t lb = tile / a.tiles_x;
-    const int W = fd->width, H = fd->height;
+    const uint32_t lb = tile / a.tiles_x, tx = tile % a.tiles_x;
+    const int W = fd->width;
     const uint32_t n_tris = fd->n_tris;
     const uint32_t flags = fd->flags | a.flags_or;
-    const int tx0 = (int)(tile % a.tiles_x) * TILE;
-    const int band = band_of((int)lb, a.shard_rank, a.shard_world);
-    const int ty0 = band * BAND;
-    const int tx1 = min(tx0 + TILE, W) - 1, ty1 = min(ty0 + BAND, H) - 1;
+    const TileRect rc = tile_rect(a, fd, frame, lb, tx);
     const bool fused = (flags & SRZ_FUSED_CLEAR) != 0;
-    const size_t row0 = (size_t)lb * BAND;
-    float *out0 = a.out + (size_t)frame * a.frame_stride + row0 * (size_t)W;
     // ---- phase A: tile init (fused clear → +inf, else load the in/out z plane) -------------------------------
     for (int i = lane; i < TILE * TILE; i += 64) {
       const int ly = i >> 5, lx = i & 31;
       float z = __builtin_inff();
-      if (!fused && tx0 + lx <= tx1 && ty0 + ly <= ty1) z = out0[(size_t)ly * W + tx0 + lx];
+      if (!fused && rc.tx0 + lx <= rc.tx1 && rc.ty0 + ly <= rc.ty1) z = rc.out0[(size_t)ly * W + rc.tx0 + lx];
       zl[ly * LDS_STRIDE + lx] = z;
       il[ly * LDS_STRIDE + lx] = NO_TRI;
     }
@@ -2002,11 +2045,11 @@ __global__ __launch_bounds__(64) void k_raster_slow(RenderArgs a) {
     const uint32_t n_chunks = (n_tris + 63) / 64;
     for (uint32_t c = 0; c < n_chunks; ++c) {
       const uint32_t cr = chunk_rows[c]; // wave-uniform
-      if ((int)(int16_t)(cr & 0xffffu) > ty1 || (int)(int16_t)(cr >> 16) < ty0) continue;
+      if ((int)(int16_t)(cr & 0xffffu) > rc.ty1 || (int)(int16_t)(cr >> 16) < rc.ty0) continue;
       const uint32_t my = c * 64u + (uint32_t)lane;
       const u32x2 bb = bbox[min(my, n_tris - 1u)];
       const int bsx = (int16_t)(bb.x & 0xffff), bsy = (int16_t)(bb.x >> 16), bex = (int16_t)(bb.y & 0xffff), bey = (int16_t)(bb.y >> 16);
-      const bool hit = my < n_tris && bsx <= bex && bex >= tx0 && bsx <= tx1 && bey >= ty0 && bsy <= ty1;
+      const bool hit = my < n_tris && bsx <= bex && bex >= rc.tx0 && bsx <= rc.tx1 && bey >= rc.ty0 && bsy <= rc.ty1;
       unsigned long long m = __ballot(hit);
       if (m == 0ull) continue;
       TriXY t;
@@ -2022,9 +2065,9 @@ __global__ __launch_bounds__(64) void k_raster_slow(RenderArgs a) {
         t.ax = p[0], t.ay = p[1], t.z0 = p[2], t.bx = p[3], t.by = p[4], t.z1 = p[5], t.cx = p[6], t.cy = p[7], t.z2 = p[8];
         BranchMath bm;
         tri_consts(bm, t);
-        const int x0 = max(bsx, tx0) - tx0, x1 = min(bex, tx1) - tx0, y0 = max(bsy, ty0) - ty0, y1 = min(bey, ty1) - ty0;
+        const int x0 = max(bsx, rc.tx0) - rc.tx0, x1 = min(bex, rc.tx1) - rc.tx0, y0 = max(bsy, rc.ty0) - rc.ty0, y1 = min(bey, rc.ty1) - rc.ty0;
         const int vend = (flags & SRZ_UNIFIED) ? bex + 1 : bsx + ((bex - bsx + 1) & ~7);
-        const int v = min(max(vend - tx0, x0), x1 + 1);
+        const int v = min(max(vend - rc.tx0, x0), x1 + 1);
         const int h = y1 - y0 + 1, wv = v - x0, ws = x1 + 1 - v;
         auto pick = [h](int w) {
           const int n88 = ((w + 7) >> 3) * ((h + 7) >> 3), n164 = ((w + 15) >> 4) * ((h + 3) >> 2), n416 = ((w + 3) >> 2) * ((h + 15) >> 4);
@@ -2053,12 +2096,12 @@ __global__ __launch_bounds__(64) void k_raster_slow(RenderArgs a) {
           const int lx = lane & (bw - 1), ly = lane >> lbw;
           for (int yb = y0; yb <= y1; yb += bh) {
             const int yl = yb + ly;
-            const float fy = (float)(ty0 + yl);
+            const float fy = (float)(rc.ty0 + yl);
             const float PBy = u.by - fy, PCy = u.cy - fy, PAy = u.ay - fy;
             const bool rowok = yl <= y1;
             for (int xb = x0; xb < vx; xb += bw) {
               const int xl = xb + lx;
-              const float fx = (float)(tx0 + xl);
+              const float fx = (float)(rc.tx0 + xl);
               const float PBx = u.bx - fx, PCx = u.cx - fx, PAx = u.ax - fx;
               const float aPBC = fmsubf(PBx, PCy, PCx * PBy), aPCA = fmsubf(PCx, PAy, PAx * PCy);
               const float al = aPBC * u.v_inv, be = aPCA * u.v_inv, ga = 1.0f - (al + be);
@@ -2082,11 +2125,11 @@ __global__ __launch_bounds__(64) void k_raster_slow(RenderArgs a) {
                       CAy = u.ay - u.cy;
           for (int yb = y0; yb <= y1; yb += bh) {
             const int yl = yb + ly;
-            const float fy = (float)(ty0 + yl);
+            const float fy = (float)(rc.ty0 + yl);
             const bool rowok = yl <= y1;
             for (int xb = vx; xb <= x1; xb += bw) {
               const int xl = xb + lx;
-              const float fx = (float)(tx0 + xl);
+              const float fx = (float)(rc.tx0 + xl);
               // insideTriangle (src/Rasterizer.cpp:11-41)
               const float APx = fx - u.ax, APy = fy - u.ay, BPx = fx - u.bx, BPy = fy - u.by, CPx = fx - u.cx, CPy = fy - u.cy;
               const float e0 = ABx * APy - ABy * APx, e1 = BCx * BPy - BCy * BPx, e2 = CAx * CPy - CAy * CPx;
@@ -2120,46 +2163,27 @@ __global__ __launch_bounds__(64) void k_raster_slow(RenderArgs a) {
     // ---- phase C: write-out (as k_raster) ---------------------------------------------------------------------------
     const bool vec_ok = (W & 3) == 0;
     if (tile_has_owner || fused) {
-      const size_t plane = (size_t)a.local_rows * (size_t)W;
       const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
       for (int it = 0; it < 4; ++it) {
         const int ly = it * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
-        const int y = ty0 + ly, x4 = tx0 + lx4;
-        if (y > ty1 || x4 > tx1) continue;
+        const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
+        if (y > rc.ty1 || x4 > rc.tx1) continue;
         const float4 z4 = *reinterpret_cast<const float4 *>(&zl[ly * LDS_STRIDE + lx4]);
-        float *gz = out0 + (size_t)ly * W + x4;
-        const bool full = vec_ok && x4 + 3 <= tx1;
-        if (tile_has_owner) {
-          if (full) {
-            store_nt(gz, z4);
-          } else {
-#define SRZ_ST(K_, M)                                                                                                  \
-  if (x4 + K_ <= tx1) gz[K_] = z4.M;
-            SRZ_ST(0, x) SRZ_ST(1, y) SRZ_ST(2, z) SRZ_ST(3, w)
-#undef SRZ_ST
-          }
-        } else {
-          if (full) {
-            store_nt(gz, z4);
-            store_nt(gz + plane, zero4);
-            store_nt(gz + 2 * plane, zero4);
-            store_nt(gz + 3 * plane, zero4);
-          } else {
-#define SRZ_ST(K_, M)                                                                                                  \
-  if (x4 + K_ <= tx1) gz[K_] = z4.M, gz[plane + K_] = 0.f, gz[2 * plane + K_] = 0.f, gz[3 * plane + K_] = 0.f;
-            SRZ_ST(0, x) SRZ_ST(1, y) SRZ_ST(2, z) SRZ_ST(3, w)
-#undef SRZ_ST
-          }
-        }
+        float *gz = rc.out0 + (size_t)ly * W + x4;
+        const bool full = vec_ok && x4 + 3 <= rc.tx1;
+        if (tile_has_owner)
+          quad_store(gz, rc.plane, {z4}, full, x4, rc.tx1);
+        else
+          quad_store(gz, rc.plane, {z4, zero4, zero4, zero4}, full, x4, rc.tx1);
       }
     }
     if (tile_has_owner) { // the owners of all of the tile's pixels, by index (32 bits each), and the tile's work entry
       uint32_t *slot = a.vis + (size_t)entry * PIX_SLOT;
       for (int it = 0; it < 4; ++it) {
         const int ly = it * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
-        ids_store4(slot, (uint32_t)(ly * TILE + lx4), *reinterpret_cast<const uint4 *>(&il[ly * LDS_STRIDE + lx4]), false);
+        ids_store4(slot, (uint32_t)(ly * TILE + lx4), *reinterpret_cast<const uint4 *>(&il[ly * LDS_STRIDE + lx4]), false, false);
       }
-      if (lane == 0) work_append(a, fd->flags, frame, entry, lb, (uint32_t)tx0 / TILE, 0u, 0u, 0u);
+      if (lane == 0) work_append(a, fd->flags, entry, work_entry(frame, lb, tx, false, false, 0u, 0u));
     }
     __builtin_amdgcn_wave_barrier(); // the planes are reused by this wave's next tile
   }
@@ -2386,10 +2410,10 @@ void k_shade(RenderArgs a) {
         C1 = *reinterpret_cast<const float4 *>(gz + 2 * plane);
         C2 = *reinterpret_cast<const float4 *>(gz + 3 * plane);
       } else if (in_tile) {
-#define SRZ_LD(K_, M)                                                                                                  \
-  if (x4 + K_ <= tx1) C0.M = gz[plane + K_], C1.M = gz[2 * plane + K_], C2.M = gz[3 * plane + K_];
-        SRZ_LD(0, x) SRZ_LD(1, y) SRZ_LD(2, z) SRZ_LD(3, w)
-#undef SRZ_LD
+        if (x4 + 0 <= tx1) C0.x = gz[plane + 0], C1.x = gz[2 * plane + 0], C2.x = gz[3 * plane + 0];
+        if (x4 + 1 <= tx1) C0.y = gz[plane + 1], C1.y = gz[2 * plane + 1], C2.y = gz[3 * plane + 1];
+        if (x4 + 2 <= tx1) C0.z = gz[plane + 2], C1.z = gz[2 * plane + 2], C2.z = gz[3 * plane + 2];
+        if (x4 + 3 <= tx1) C0.w = gz[plane + 3], C1.w = gz[2 * plane + 3], C2.w = gz[3 * plane + 3];
       }
     }
     *reinterpret_cast<float4 *>(&s_c[0][p0]) = C0;
@@ -2619,10 +2643,10 @@ void k_shade(RenderArgs a) {
         store_nt(gz + 2 * plane, C1);
         store_nt(gz + 3 * plane, C2);
       } else if (in_tile) {
-#define SRZ_ST(K_, M)                                                                                                  \
-  if (x4 + K_ <= tx1) gz[plane + K_] = C0.M, gz[2 * plane + K_] = C1.M, gz[3 * plane + K_] = C2.M;
-        SRZ_ST(0, x) SRZ_ST(1, y) SRZ_ST(2, z) SRZ_ST(3, w)
-#undef SRZ_ST
+        if (x4 + 0 <= tx1) gz[plane + 0] = C0.x, gz[2 * plane + 0] = C1.x, gz[3 * plane + 0] = C2.x;
+        if (x4 + 1 <= tx1) gz[plane + 1] = C0.y, gz[2 * plane + 1] = C1.y, gz[3 * plane + 1] = C2.y;
+        if (x4 + 2 <= tx1) gz[plane + 2] = C0.z, gz[2 * plane + 2] = C1.z, gz[3 * plane + 2] = C2.z;
+        if (x4 + 3 <= tx1) gz[plane + 3] = C0.w, gz[2 * plane + 3] = C1.w, gz[3 * plane + 3] = C2.w;
       }
     }
     SRZ_STAMP(4) // → write-out issued
@@ -2705,34 +2729,22 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
   for (uint32_t kind = 0; kind <= SHADE_KIND_GENERIC; ++kind) {
     const uint32_t n_work = as_const(a.work_count)[(kind * 8u + sub) * CNT_STRIDE];
     if (n_work == 0u) continue; // (wave-uniform: kinds no frame of the set needs have no storage slot and count 0)
-    const uint32_t Ls = ((uint32_t)(a.kind_slots >> (4u * kind)) & 15u) * 8u + sub;
-    const SRZ_CAS u32x4 *list = reinterpret_cast<const SRZ_CAS u32x4 *>(as_const(a.worklist)) + (size_t)Ls * a.work_cap;
+    const SRZ_CAS u32x4 *list = reinterpret_cast<const SRZ_CAS u32x4 *>(as_const(a.worklist)) + (size_t)work_slot(a, kind, sub) * a.work_cap;
     for (uint32_t w = blockIdx.x >> 3; w < n_work; w += step) {
-      const u32x4 x = list[w];
-      const uint32_t f = x.x, lb = x.y & 1023u, tx = (x.y >> 10) & 1023u, cnt = x.z;
-      const bool by_lp = (x.y & WORK_LP) != 0u, lp8 = (x.y & WORK_LP8) != 0u, staged = by_lp && cnt <= VIS_STAGE;
-      const SRZ_CAS uint32_t *tlist = as_const(a.pool) + x.w;
-      // 1. this thread's 4 owner ids, decoded as shade_tile step 1 does
-      const uint32_t *slot = a.vis + (size_t)(f * tpf + lb * a.tiles_x + tx) * PIX_SLOT;
+      const Work e = work_decode(list[w]);
+      const bool staged = e.by_lp && e.cnt <= VIS_STAGE;
+      const SRZ_CAS uint32_t *tlist = as_const(a.pool) + e.off;
+      // 1. this thread's 4 owner ids
       uint32_t idk[4];
-      if (lp8) {
-        const uint32_t w4 = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(slot) + p0);
-        idk[0] = w4 & 0xffu, idk[1] = (w4 >> 8) & 0xffu, idk[2] = (w4 >> 16) & 0xffu, idk[3] = w4 >> 24;
-      } else if (by_lp) {
-        const u32x2 w2 = *reinterpret_cast<const u32x2 *>(reinterpret_cast<const uint16_t *>(slot) + p0);
-        idk[0] = w2.x & 0xffffu, idk[1] = w2.x >> 16, idk[2] = w2.y & 0xffffu, idk[3] = w2.y >> 16;
-      } else {
-        const uint4 w4 = *reinterpret_cast<const uint4 *>(slot + p0);
-        idk[0] = w4.x, idk[1] = w4.y, idk[2] = w4.z, idk[3] = w4.w;
-      }
-      const uint32_t none = lp8 ? 0xffu : by_lp ? 0xffffu : NO_TRI, sbit = lp8 ? 0x80u : by_lp ? 0x8000u : S_CLASS_BIT;
-      const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
-      const int W = fd->width, H = fd->height;
+      ids_unpack4(ids_load_raw(a.vis + (size_t)(e.f * tpf + e.lb * a.tiles_x + e.tx) * PIX_SLOT, p0, e.by_lp, e.lp8), e.by_lp, e.lp8, idk);
+      const uint32_t none = id_none(e.by_lp, e.lp8), sbit = id_sbit(e.by_lp, e.lp8);
+      const SRZ_CAS FrameDesc *fd = as_const(a.frames) + e.f;
+      const int W = fd->width;
       const uint32_t tri_off = fd->tri_off;
       const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
       const SRZ_CAS float *tpos = as_const(a.tri_pos) + (size_t)tri_off * a.pos_stride;
       // 2. a short list's positions → LDS, by list position (one entry per thread)
-      if (staged && (uint32_t)tid < cnt) {
+      if (staged && (uint32_t)tid < e.cnt) {
         const uint32_t idx = tlist[tid] & PACK_IDX_MASK; // (by_lp = FD_PACKED: the entry carries the batch above the index)
         const SRZ_CAS float *q = tpos + (size_t)idx * a.pos_stride;
         s_idx[tid] = idx;
@@ -2740,14 +2752,11 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
         for (int k = 0; k < (int)TRI_POS_F; ++k) s_pos[tid * TRI_POS_F + k] = q[k];
       }
       __syncthreads();
-      const int band = band_of((int)lb, a.shard_rank, a.shard_world);
-      const int tx0 = (int)tx * TILE, ty0 = band * BAND;
-      const int tx1 = min(tx0 + TILE, W) - 1, ty1 = min(ty0 + BAND, H) - 1;
-      const size_t plane = (size_t)a.local_rows * (size_t)W;
-      const int y = ty0 + ly, x4 = tx0 + lx4;
-      const bool in_tile = y <= ty1 && x4 <= tx1;
-      const bool full = in_tile && ((W & 3) == 0) && x4 + 3 <= tx1;
-      float *gz = a.out + (size_t)f * a.frame_stride + ((size_t)lb * BAND + ly) * (size_t)W + x4;
+      const TileRect rc = tile_rect(a, fd, e.f, e.lb, e.tx);
+      const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
+      const bool in_tile = y <= rc.ty1 && x4 <= rc.tx1;
+      const bool full = in_tile && ((W & 3) == 0) && x4 + 3 <= rc.tx1;
+      float *gz = rc.out0 + (size_t)ly * W + x4;
       float o[3][4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) o[0][k] = o[1][k] = o[2][k] = 0.f;
@@ -2756,7 +2765,7 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
         for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
           for (int k = 0; k < 4; ++k)
-            if (x4 + k <= tx1) o[pl][k] = gz[(pl + 1) * plane + k];
+            if (x4 + k <= rc.tx1) o[pl][k] = gz[(pl + 1) * rc.plane + k];
       }
       // 3. α and β of each owned pixel from its owner's positions
 #pragma unroll
@@ -2771,7 +2780,7 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
           idx = s_idx[pos];
           t.ax = q[0], t.ay = q[1], t.z0 = q[2], t.bx = q[3], t.by = q[4], t.z1 = q[5], t.cx = q[6], t.cy = q[7], t.z2 = q[8];
         } else {
-          idx = by_lp ? (tlist[pos] & PACK_IDX_MASK) : pos; // (a long list: position → index, then the gather)
+          idx = e.by_lp ? (tlist[pos] & PACK_IDX_MASK) : pos; // (a long list: position → index, then the gather)
           const SRZ_CAS float *q = tpos + (size_t)idx * a.pos_stride;
           t.ax = q[0], t.ay = q[1], t.z0 = q[2], t.bx = q[3], t.by = q[4], t.z1 = q[5], t.cx = q[6], t.cy = q[7], t.z2 = q[8];
         }
@@ -2786,15 +2795,9 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
         o[0][k] = u2f_((idx + 1u) | (isS ? S_CLASS_BIT : 0u)), o[1][k] = alpha, o[2][k] = beta;
       }
       // 4. planes 1..3 of the tile's rows
-      if (full) {
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) store_nt(gz + (pl + 1) * plane, make_float4(o[pl][0], o[pl][1], o[pl][2], o[pl][3]));
-      } else if (in_tile) {
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (x4 + k <= tx1) gz[(pl + 1) * plane + k] = o[pl][k];
+      if (in_tile) {
+        const float4 q[3] = {make_float4(o[0][0], o[0][1], o[0][2], o[0][3]), make_float4(o[1][0], o[1][1], o[1][2], o[1][3]), make_float4(o[2][0], o[2][1], o[2][2], o[2][3])};
+        quad_store(gz + rc.plane, rc.plane, q, full, x4, rc.tx1);
       }
       __syncthreads(); // s_pos / s_idx are reused by the next tile
     }
