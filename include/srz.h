@@ -46,6 +46,8 @@ extern "C" {
  *      (additive, same version: no existing signature, struct or meaning changed) the tile-sparse exchange srz_frameset_sparse_capacity /
  *      _sparse_pack / _sparse_unpack, srz_frameset_allgather_sparse
  *      (additive, same version) the visibility buffer srz_frameset_render_visibility
+ *      (additive, same version) shading a visibility buffer srz_frameset_shade_visibility, new shading data for a frameset
+ *      srz_frameset_update_shading
  */
 #define SRZ_ABI_VERSION 7
 
@@ -265,6 +267,32 @@ int srz_frameset_render(srz_ctx *ctx, srz_frameset *fs, void *d_out, size_t out_
  * srz_frameset_allgather / _allgather_inplace / _deinterleave / _read_gathered_frame and the tile-sparse exchange unchanged, as
  * SRZ_EXCHANGE_PLANES.  No texture has to be uploaded; the render files no sample of the side clear's grid measurement. */
 int srz_frameset_render_visibility(srz_ctx *ctx, srz_frameset *fs, void *d_out, size_t out_bytes, uint32_t flags, void *stream);
+/* The COLOUR of a visibility buffer: rasterise once (srz_frameset_render_visibility), shade many times — new lights, ka / ks / p, shader
+ * types (srz_frameset_update_shading, srz_sceneset_update).  d_vis: a visibility buffer of THIS set on this ctx's shard; d_out: a buffer
+ * in the layout of srz_frameset_render.  Size (srz_frameset_out_bytes, for each of the two), 16-byte alignment of both, the flag mask,
+ * stream semantics, local_rows and band sharding as srz_frameset_render; asynchronous, no host synchronisation.  Per pixel of d_vis:
+ *   id != 0 (and (id & 0x7fffffff) - 1 < the frame's triangle count): plane 0 = the visibility z, bit for bit; planes 1..3 = the colour
+ *            the colour render gives owner (id & 0x7fffffff) - 1 of that frame at (x, y), from the stored alpha and beta (gamma =
+ *            1 - (alpha + beta) for class V, (1 - alpha) - beta for class S: bit 31 of id) with the set's CURRENT shading data — eye, ka,
+ *            ks, p, kh, kn, lights, each batch's shader and texture (which must be uploaded, as for srz_frameset_render);
+ *   otherwise ("nobody"): with SRZ_FUSED_CLEAR (frame flags | flags) the clear values (+inf, 0, 0, 0); without it the four output
+ *            words are left untouched.
+ * So srz_frameset_shade_visibility(render_visibility(F), F) is bit-identical to srz_frameset_render(F) on all four planes, in every
+ * shading build (the tolerance mode of SRZ_OPT_APPROX_SHADE included: against that set's own colour render) and for SRZ_UNIFIED and
+ * SRZ_ORDERED_RASTER renders.  d_out == d_vis (in place) is allowed: the owned pixels' planes 1..3 are written, and with SRZ_FUSED_CLEAR
+ * the four words of a pixel whose id is out of range get the clear values; id-0 words are left as they are (after a fused visibility
+ * render they are the clear values already).  A partial overlap of the two buffers is SRZ_E_INVALID.  A sceneset
+ * runs its vertex stage first, as a render does.  The call files no sample of the side clear's grid measurement. */
+int srz_frameset_shade_visibility(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void *d_out, size_t out_bytes,
+                                  uint32_t flags, void *stream);
+/* New SHADING DATA for a set made by srz_frameset_create, its triangles untouched (batches[b].tris is ignored and may be NULL): each
+ * frame's eye, ka, ks, p, kh, kn, lights and flags, each batch's shader and tex_id.  The structure must be the set's — frame count, size,
+ * light counts, batch counts, n_tris per batch — else SRZ_E_INVALID and the set is unchanged; a sceneset is SRZ_E_INVALID (its shading
+ * changes with srz_sceneset_update).  Asynchronous copies on the ctx's stream (ordered after the renders submitted there, before the next
+ * ones; renders on other streams are the caller's to order), from a pinned staging ring like srz_sceneset_update's.  Every later
+ * render and shade of the set uses the new data.  Out of device memory for the work lists of a new build kind: SRZ_E_NOMEM, and
+ * renders are refused until an update succeeds (srz_sceneset_update). */
+int srz_frameset_update_shading(srz_ctx *ctx, srz_frameset *fs, const srz_frame *frames, int n_frames);
 /* display()'s resolve on the device (cv::merge + convertTo(CV_8UC3), src/Render.cpp:61-62): the three colour planes of
  * a rendered buffer (layout of srz_frameset_render) → interleaved 8-bit [frame][local_rows][width][3], round half to even,
  * saturate.  Asynchronous on `stream`.  Any width (sizes whose plane is not a multiple of 4 pixels take a one-pixel-per-thread kernel). */

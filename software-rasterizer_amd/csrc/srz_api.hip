@@ -100,6 +100,7 @@ struct srz_frameset {
   std::vector<FrameDesc> h_frames;
   std::vector<BatchDesc> h_batches;
   std::vector<ShadeDescG> h_sdesc;
+  std::vector<srz_light> h_lights; // refresh_frames: the host copy of the lights of the last update (what classify_frames reads)
   FrameDesc *d_frames = nullptr;
   srz_tri *d_tris = nullptr;     // the triangle stream as uploaded
   float *d_tri_pos = nullptr;    // dense copy of its positions (9 floats per triangle); null: srz_draw's one-frame set, re-uploaded per call
@@ -1299,6 +1300,54 @@ int srz_frameset_render_visibility(srz_ctx *ctx, srz_frameset *fs, void *d_out, 
   return render_entry("srz_frameset_render_visibility", ctx, fs, d_out, out_bytes, flags, stream, Pass::visibility());
 }
 
+static int refresh_frames(srz_ctx *ctx, srz_frameset *fs, const srz_frame *frames, int n_frames, hipStream_t s, const char *who, bool copy_tris);
+
+int srz_frameset_shade_visibility(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void *d_out, size_t out_bytes, uint32_t flags,
+                                  void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_shade_visibility");
+  if (!fs || !d_vis || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / output");
+  const size_t bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < bytes) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
+  if ((((uintptr_t)d_vis | (uintptr_t)d_out) & 15u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
+  const uintptr_t v = (uintptr_t)d_vis, o = (uintptr_t)d_out;
+  if (v != o && v < o + bytes && o < v + bytes) return fail(ctx, SRZ_E_INVALID, fn + ": visibility buffer and output overlap partly");
+  if (fs->shard_rank != ctx->shard_rank || fs->shard_world != ctx->shard_world)
+    return fail(ctx, SRZ_E_INVALID, "frameset was created under a different shard (call srz_set_shard before srz_frameset_create)");
+  if (fs->update_failed) return fail(ctx, SRZ_E_NOMEM, "the last update of this set failed (out of memory): update it again or destroy it");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const hipStream_t s = pick_stream(ctx, stream);
+  if (int rc = resolve_shading(ctx, fs, s)) return rc; // (textures uploaded, batch → shader / texture)
+  // a sceneset's triangles are its vertex stage's output: computed as a render computes them (no setup: nothing is rasterised)
+  if (fs->d_draws) launch_vertex(fs->d_draws, fs->n_draws, fs->max_faces, fs->d_tris, fs->d_tri_pos, fs->d_frames, nullptr, s);
+  ShadeVisArgs a{};
+  a.frames = fs->d_frames, a.tris = fs->d_tris, a.tri_batch = fs->d_tri_batch, a.lights = fs->d_lights, a.sdesc = fs->d_sdesc;
+  a.vis = (const float *)d_vis, a.out = (float *)d_out;
+  a.frame_stride = 4ull * fs->local_rows * (uint64_t)fs->width;
+  a.local_rows = fs->local_rows, a.tiles_x = fs->tiles_x, a.n_local_bands = fs->n_local_bands, a.n_frames = (uint32_t)fs->n_frames;
+  a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
+  a.flags_or = flags & (SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER), a.in_place = v == o ? 1u : 0u;
+  a.any_generic = fs->any_generic ? 1u : 0u;
+  a.redo_list = reinterpret_cast<uint32_t *>(fs->d_redo_list), a.redo_count = fs->d_slow_count + 1; // (k_shade's: a render zeroes them itself)
+  HIP_TRY(ctx, hipMemsetAsync(a.redo_count, 0, sizeof(uint32_t), s));
+  launch_shade_vis(a, fs->fast_mask, fs->any_generic, fs->approx_shade, s);
+  // no sample of the side clear's grid measurement: while the set measures, its clock restarts here, so the next colour render times
+  // only itself (as after a visibility render)
+  const srz_frameset::ClearTune &ct = fs->clear_tune;
+  if (!ctx->env_clear_wgs && ct.d_ctl && !ct.done && fs->max_tiles >= 8192) launch_clear_rebase(ct.d_ctl, s);
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
+int srz_frameset_update_shading(srz_ctx *ctx, srz_frameset *fs, const srz_frame *frames, int n_frames) {
+  if (!ctx) return SRZ_E_INVALID;
+  if (!fs || !frames) return fail(ctx, SRZ_E_INVALID, "srz_frameset_update_shading: null frameset / frames");
+  if (fs->d_draws) return fail(ctx, SRZ_E_INVALID, "srz_frameset_update_shading: a sceneset (its shading changes with srz_sceneset_update)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // (on the context's stream, like srz_sceneset_update: after every render already submitted there, before the next one)
+  return refresh_frames(ctx, fs, frames, n_frames, ctx->stream, "srz_frameset_update_shading", /*copy_tris=*/false);
+}
+
 int srz_frameset_resolve8(srz_ctx *ctx, const srz_frameset *fs, const void *d_planes, void *d_bgr8, size_t bgr8_bytes, void *stream) {
   if (!ctx) return SRZ_E_INVALID;
   if (!fs || !d_planes || !d_bgr8) return fail(ctx, SRZ_E_INVALID, "srz_frameset_resolve8: null argument");
@@ -1794,24 +1843,87 @@ int srz_sync(srz_ctx *ctx) {
   return SRZ_OK;
 }
 
-// re-upload the data of a 1-frame set made by srz_frameset_create (same structure: checked by the caller's signature)
-static int refresh_plain_frame(srz_ctx *ctx, srz_frameset *fs, const srz_frame &fr, hipStream_t s) {
-  FrameDesc &d = fs->h_frames[0];
-  std::memcpy(d.eye, fr.eye, sizeof d.eye), std::memcpy(d.ka, fr.ka, sizeof d.ka), std::memcpy(d.ks, fr.ks, sizeof d.ks);
-  d.p = fr.p, d.kh = fr.kh, d.kn = fr.kn;
-  d.flags = fr.flags & (SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER);
-  if (fr.n_lights != d.n_lights || (fr.n_lights && !fr.lights)) return fail(ctx, SRZ_E_INVALID, "srz_draw: light count changed");
-  classify_frames(fs, fr.lights, /*one_frame=*/true);
+// Re-upload the shading data of a set made by srz_frameset_create (srz_draw's one-frame set: its triangles too, copy_tris): each frame's
+// eye, ka, ks, p, kh, kn, lights and flags, each batch's shader and texture.  The structure must be the set's (frame count, size, light
+// and batch counts, triangles per batch): else SRZ_E_INVALID and the set is unchanged.  Asynchronous on `s`.
+static int refresh_frames(srz_ctx *ctx, srz_frameset *fs, const srz_frame *frames, int n_frames, hipStream_t s, const char *who, bool copy_tris) {
+  const std::string fn(who);
+  if (n_frames != fs->n_frames) return fail(ctx, SRZ_E_INVALID, fn + ": frame count changed");
+  for (int f = 0; f < n_frames; ++f) { // (everything is checked before anything changes)
+    const srz_frame &fr = frames[f];
+    const FrameDesc &d = fs->h_frames[f];
+    if (fr.width != fs->width || fr.height != fs->height) return fail(ctx, SRZ_E_INVALID, fn + ": frame size changed");
+    if (fr.n_lights != d.n_lights || (fr.n_lights && !fr.lights)) return fail(ctx, SRZ_E_INVALID, fn + ": light count changed");
+    if (fr.n_batches != d.n_batches || (fr.n_batches && !fr.batches)) return fail(ctx, SRZ_E_INVALID, fn + ": batch count changed");
+    for (uint32_t b = 0; b < fr.n_batches; ++b) {
+      const srz_batch &sb = fr.batches[b];
+      if (sb.n_tris != fs->h_batches[d.batch_off + b].count) return fail(ctx, SRZ_E_INVALID, fn + ": triangle count of a batch changed");
+      if (sb.shader < SRZ_SHADER_NORMAL || sb.shader > SRZ_SHADER_BUMP) return fail(ctx, SRZ_E_INVALID, fn + ": unknown shader type");
+      if (copy_tris && sb.n_tris && !sb.tris) return fail(ctx, SRZ_E_INVALID, fn + ": batch with null triangle pointer");
+    }
+  }
+  // the upload goes through a pinned staging ring guarded by events, as srz_sceneset_update's: a set made by srz_frameset_create gets its
+  // ring at its first refresh (before anything changes: out of memory leaves the set as it was)
+  const size_t lights_off = (sizeof(FrameDesc) * (size_t)n_frames + 15u) & ~(size_t)15u;
+  const size_t batches_off = lights_off + ((sizeof(srz_light) * (size_t)fs->total_lights + 15u) & ~(size_t)15u);
+  const size_t stage_bytes = batches_off + sizeof(BatchDesc) * fs->h_batches.size();
+  if (!fs->h_stage[0]) {
+    for (int i = 0; i < srz_frameset::STAGE_RING; ++i) {
+      hipError_t e = hipHostMalloc((void **)&fs->h_stage[i], stage_bytes, hipHostMallocDefault);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&fs->stage_ev[i], hipEventDisableTiming);
+      if (e != hipSuccess) {
+        for (int j = 0; j <= i; ++j) {
+          if (fs->h_stage[j]) (void)hipHostFree(fs->h_stage[j]);
+          if (fs->stage_ev[j]) (void)hipEventDestroy(fs->stage_ev[j]);
+          fs->h_stage[j] = nullptr, fs->stage_ev[j] = nullptr;
+        }
+        return fail(ctx, e == hipErrorOutOfMemory ? SRZ_E_NOMEM : SRZ_E_NODEVICE, fn + ": staging buffers: " + hipGetErrorString(e));
+      }
+    }
+  }
+  fs->h_lights.resize((size_t)fs->total_lights);
+  bool batches_changed = false;
+  for (int f = 0; f < n_frames; ++f) {
+    const srz_frame &fr = frames[f];
+    FrameDesc &d = fs->h_frames[f];
+    std::memcpy(d.eye, fr.eye, sizeof d.eye), std::memcpy(d.ka, fr.ka, sizeof d.ka), std::memcpy(d.ks, fr.ks, sizeof d.ks);
+    d.p = fr.p, d.kh = fr.kh, d.kn = fr.kn;
+    d.flags = fr.flags & (SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER);
+    if (fr.n_lights) std::memcpy(&fs->h_lights[d.light_off], fr.lights, sizeof(srz_light) * fr.n_lights);
+    for (uint32_t b = 0; b < fr.n_batches; ++b) {
+      BatchDesc &bd = fs->h_batches[d.batch_off + b];
+      if (bd.shader != fr.batches[b].shader || bd.tex_id != fr.batches[b].tex_id)
+        bd.shader = fr.batches[b].shader, bd.tex_id = fr.batches[b].tex_id, batches_changed = true;
+    }
+  }
+  classify_frames(fs, fs->h_lights.data());
   fs->update_failed = ensure_worklists(fs) != hipSuccess; // (see srz_sceneset_update)
-  if (fs->update_failed) return fail(ctx, SRZ_E_NOMEM, "srz_draw: hipMalloc of the work lists failed");
-  HIP_TRY(ctx, hipMemcpyAsync(fs->d_frames, fs->h_frames.data(), sizeof(FrameDesc), hipMemcpyHostToDevice, s));
-  if (fr.n_lights) HIP_TRY(ctx, hipMemcpyAsync(fs->d_lights, fr.lights, sizeof(srz_light) * fr.n_lights, hipMemcpyHostToDevice, s));
-  size_t o = 0;
-  for (uint32_t b = 0; b < fr.n_batches; ++b) {
-    const srz_batch &sb = fr.batches[b];
-    if (sb.n_tris && !sb.tris) return fail(ctx, SRZ_E_INVALID, "srz_draw: batch with null triangle pointer");
-    if (sb.n_tris) HIP_TRY(ctx, hipMemcpyAsync(fs->d_tris + o, sb.tris, sizeof(srz_tri) * sb.n_tris, hipMemcpyHostToDevice, s));
-    o += sb.n_tris;
+  if (fs->update_failed) return fail(ctx, SRZ_E_NOMEM, fn + ": hipMalloc of the work lists failed");
+  // (frames, lights and batches live in three device allocations here, not in one block as a sceneset's: three copies from one slot)
+  const unsigned slot = fs->stage_next++ % srz_frameset::STAGE_RING;
+  if (fs->stage_busy[slot]) HIP_TRY(ctx, hipEventSynchronize(fs->stage_ev[slot])); // its copies of 4 updates ago
+  uint8_t *st = fs->h_stage[slot];
+  std::memcpy(st, fs->h_frames.data(), sizeof(FrameDesc) * (size_t)n_frames);
+  if (!fs->h_lights.empty()) std::memcpy(st + lights_off, fs->h_lights.data(), sizeof(srz_light) * fs->h_lights.size());
+  if (batches_changed) std::memcpy(st + batches_off, fs->h_batches.data(), sizeof(BatchDesc) * fs->h_batches.size());
+  HIP_TRY(ctx, hipMemcpyAsync(fs->d_frames, st, sizeof(FrameDesc) * (size_t)n_frames, hipMemcpyHostToDevice, s));
+  if (!fs->h_lights.empty())
+    HIP_TRY(ctx, hipMemcpyAsync(fs->d_lights, st + lights_off, sizeof(srz_light) * fs->h_lights.size(), hipMemcpyHostToDevice, s));
+  if (batches_changed) {
+    HIP_TRY(ctx, hipMemcpyAsync(fs->d_batches, st + batches_off, sizeof(BatchDesc) * fs->h_batches.size(), hipMemcpyHostToDevice, s));
+    fs->sdesc_version = 0; // re-resolve batch → shader / texture at the next render or shade
+  }
+  HIP_TRY(ctx, hipEventRecord(fs->stage_ev[slot], s));
+  fs->stage_busy[slot] = true;
+  if (copy_tris) {
+    for (int f = 0; f < n_frames; ++f) {
+      size_t o = fs->h_frames[f].tri_off;
+      for (uint32_t b = 0; b < frames[f].n_batches; ++b) {
+        const srz_batch &sb = frames[f].batches[b];
+        if (sb.n_tris) HIP_TRY(ctx, hipMemcpyAsync(fs->d_tris + o, sb.tris, sizeof(srz_tri) * sb.n_tris, hipMemcpyHostToDevice, s));
+        o += sb.n_tris;
+      }
+    }
   }
   fs->have_stats = false;
   return SRZ_OK;
@@ -1841,7 +1953,7 @@ static int draw_impl(srz_ctx *ctx, int primitive, const srz_frame *frame, const 
   bool reuse = ctx->draw_fs && sig == ctx->draw_sig;
   if (reuse) {
     ctx->draw_fs->approx_shade = ctx->opt_approx_shade; // (the ctx's own one-frame set follows the option call by call)
-    rc = frame ? refresh_plain_frame(ctx, ctx->draw_fs, *frame, s) : srz_sceneset_update(ctx, ctx->draw_fs, scene, 1);
+    rc = frame ? refresh_frames(ctx, ctx->draw_fs, frame, 1, s, "srz_draw", /*copy_tris=*/true) : srz_sceneset_update(ctx, ctx->draw_fs, scene, 1);
     if (rc != SRZ_OK && !frame) reuse = false, rc = SRZ_OK; // (a scene whose mesh bindings changed: rebuild)
     if (rc != SRZ_OK) return rc;
   }

@@ -217,6 +217,26 @@ void launch_clear(const RenderArgs &a, uint32_t max_tiles, hipStream_t s, uint32
 void launch_shade(const RenderArgs &a, uint32_t max_tiles, bool stats, uint32_t fast_mask, bool any_generic, bool approx, hipStream_t s);
 // the visibility buffer (srz_frameset_render_visibility) in place of launch_shade: planes 1..3 of every owned tile
 void launch_visibility(const RenderArgs &a, uint32_t max_tiles, hipStream_t s);
+// srz_frameset_shade_visibility: the colour of a visibility buffer (k_shade_vis).  Everything a pixel's shading reads of the set, and the
+// two buffers in the layout of srz_frameset_render; in_place: vis == out (only the owned pixels' colour planes are written)
+struct ShadeVisArgs {
+  const FrameDesc *frames;
+  const srz_tri *tris;
+  const uint16_t *tri_batch;
+  const srz_light *lights;
+  const ShadeDescG *sdesc;
+  const float *vis;
+  float *out;
+  uint64_t frame_stride; // floats per frame in vis / out
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or, in_place;
+  uint32_t any_generic;  // some frame is not FD_FAST_SHADE (else the generic build only serves redo_list)
+  uint32_t *redo_list;   // tiles (frame * tiles per frame + tile) the FAST builds hand to the generic one
+  uint32_t *redo_count;  // (zero at launch_shade_vis)
+};
+// one launch per build kind the set's frames need (fast_mask / any_generic / approx as for launch_shade); frames of other kinds are skipped
+void launch_shade_vis(const ShadeVisArgs &a, uint32_t fast_mask, bool any_generic, bool approx, hipStream_t s);
 void launch_resolve8(const float *planes, uint8_t *out, uint32_t n_frames, uint32_t rows, uint32_t W, uint64_t frame_stride,
                      hipStream_t s);
 void launch_deinterleave(const void *gathered, void *full, uint32_t world, uint32_t n_fp, uint32_t bands_per_rank, uint32_t row_bytes,

@@ -1422,6 +1422,32 @@ __device__ __forceinline__ void late_fetch(TriFetch &f, const f32x4 *late, float
     f.q3 = late[3], f.q4 = late[4], f.q5 = late[5];
   }
 }
+// The shading from the barycentrics on, given the owner's normals and texture coordinates (a's attributes): k_shade_vis's per-pixel work
+// (α, β and z from a visibility buffer).  These are the statements of the second half of shade_pixel_v / _s below, operation for
+// operation — keep the two in step.  shade_pixel_v / _s do not call them: with that call in place every k_shade build kept its registers
+// but changed its schedule (±1..11 instructions) and the bench headline came out ~0.5 % lower, so k_shade's statements stay as measured.
+template <class M, int SH, int NL>
+__device__ __forceinline__ void shade_bary_v(M &m, const FrameK &K, const ShadeDesc &sd, const TriAttr &a, float alpha, float beta,
+                                             float gamma, float fx, float fy, float zz, float &r0, float &r1, float &r2) {
+  float nx = fmaf_(alpha, a.n0x, fmaf_(beta, a.n1x, gamma * a.n2x));
+  float ny = fmaf_(alpha, a.n0y, fmaf_(beta, a.n1y, gamma * a.n2y));
+  float nz = fmaf_(alpha, a.n0z, fmaf_(beta, a.n1z, gamma * a.n2z));
+  v_normalized(m, nx, ny, nz);
+  float u = fmaf_(alpha, a.u0, fmaf_(beta, a.u1, gamma * a.u2));
+  float v = fmaf_(alpha, a.v0, fmaf_(beta, a.v1, gamma * a.v2));
+  v_shade<M, SH, NL>(m, K, sd, fx, fy, zz, nx, ny, nz, u, v, r0, r1, r2);
+}
+template <class M, int SH, int NL>
+__device__ __forceinline__ void shade_bary_s(M &m, const FrameK &K, const ShadeDesc &sd, const TriAttr &a, float alpha, float beta,
+                                             float gamma, float fx, float fy, float zz, float &r0, float &r1, float &r2) {
+  float nx = alpha * a.n0x + beta * a.n1x + gamma * a.n2x;
+  float ny = alpha * a.n0y + beta * a.n1y + gamma * a.n2y;
+  float nz = alpha * a.n0z + beta * a.n1z + gamma * a.n2z;
+  normalize3(m, nx, ny, nz);
+  float u = alpha * a.u0 + beta * a.u1 + gamma * a.u2;
+  float v = alpha * a.v0 + beta * a.v1 + gamma * a.v2;
+  s_shade<M, SH, NL>(m, K, sd, fx, fy, zz, nx, ny, nz, u, v, r0, r1, r2);
+}
 // Shade pixel (x,y) of depth z, owner `f`, 8-wide ("V") semantics (src/Rasterizer.cpp:380-389)
 template <class M, int SH = -1, int NL = 0>
 __device__ __forceinline__ void shade_pixel_v(M &m, const FrameK &K, const ShadeDesc &sd, const TriFetch &f_in, const f32x4 *late, int x,
@@ -2805,6 +2831,302 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
 }
 
 // ================================================================================================================
+// k_shade_vis — the COLOUR OF A VISIBILITY BUFFER (srz_frameset_shade_visibility, include/srz.h): what k_shade would have written,
+// from the owner id, z, α and β a visibility render left, without rasterising again.  No work lists: the buffer is all there is,
+// so the grid walks every (frame, 32x32 tile) of the set in k_shade's XCD order (workgroup b takes the frames f ≡ b mod 8, whose
+// triangles stay in its XCD's L2; fewer than 8 frames: tiles dealt round-robin).  Per tile:
+//   1. a thread's 4 owner ids in one 16-byte load (plane 1); an id above the frame's triangle count is nobody (with SRZ_FUSED_CLEAR it
+//      gets the clear values, in place too); z, α, β only for quads with an owner, into LDS by pixel;
+//   2. the owned pixels compacted by class (V entries, then S entries), as k_shade does, so a wave runs one class per 64-entry chunk;
+//   3. per pixel: the owner's 60 bytes of normals and texture coordinates (no positions) + batch id, γ from α and β as the class
+//      computes it, then shade_bary_v / _s — the same instantiations k_shade runs for the frame's build: the FAST variants picked by
+//      one wave-uniform switch on the batch's shader type per pass, FastMath; a tile where an operand left FastMath's range is handed
+//      to the generic build through redo_list (as k_shade's FAST builds do), which re-shades it with IEEE math — the generic build
+//      re-shades its own such tiles at once; ApproxMath in the tolerance mode;
+//   4. the four planes with 16-byte non-temporal stores (in place: the owned pixels' three colour planes only, and the clear values
+//      where an out-of-range id meets SRZ_FUSED_CLEAR).
+// One launch per build kind, as launch_shade: each instantiation keeps its own register count; tiles of other kinds' frames are
+// skipped after one scalar load.  The floor is the memory system: 4 bytes of ids read per pixel, 12 more + 60 of triangle (+ a 2-byte
+// batch id) per owned pixel, and 16 bytes written per pixel with SRZ_FUSED_CLEAR (per owned pixel without it, 12 in place).
+// ================================================================================================================
+// (4 waves per SIMD: 128 VGPRs; the four-light pow_fast build needs more — held to 128 it spills 136 bytes — and gets 3)
+template <int FASTNL, bool BUMPY = false, bool APPROX = false>
+__global__ __launch_bounds__(256, FASTNL == -4 ? 3 : SRZ_SHADE_MINW) void k_shade_vis(ShadeVisArgs a) {
+  constexpr bool FAST = FASTNL != 0, GENPOW = FASTNL < 0;
+  static_assert(FAST || !BUMPY, "BUMPY is a property of the FAST builds");
+  static_assert(!APPROX || (FASTNL > 0 && !BUMPY), "the tolerance mode has FAST builds for 1..4 lights only");
+  constexpr uint32_t KIND = FAST ? (uint32_t)(light_count<FASTNL>() - 1) + (BUMPY ? 4u : 0u) + (GENPOW ? 8u : 0u) : SHADE_KIND_GENERIC;
+  __shared__ __attribute__((aligned(16))) float s_in[3][TILE * TILE]; // z, α, β by pixel
+  __shared__ __attribute__((aligned(16))) float s_c[3][TILE * TILE];  // colour by pixel
+  __shared__ uint32_t s_idx[PIX_SLOT];                                // compacted owned pixels: owner's index in the frame
+  __shared__ uint16_t s_pix[PIX_SLOT];                                // and pixel (ly * 32 + lx)
+  __shared__ uint32_t s_wcnt[4];
+  __shared__ uint32_t s_flag;
+  __shared__ uint8_t s_bog[256]; // per thread: its pixels whose id word is out of range
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4, p0 = ly * TILE + lx4;
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  // ---- tile t of frame f.  mode: 0 = the FAST variants (a tile where an operand left FastMath's range goes to redo_list), 1 = the
+  //      generic instantiation (FastMath, then IEEE if needed), 2 = IEEE at once (the tiles handed back) --------------------------------
+  auto shade_tile = [&](const uint32_t f, const uint32_t t, auto mode_c) {
+    constexpr int MODE = decltype(mode_c)::value;
+    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+    const uint32_t ff = fd->flags;
+    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
+    const int W = fd->width, H = fd->height;
+    const int tx0 = (int)tx * TILE, ty0 = band_of((int)lb, a.shard_rank, a.shard_world) * BAND;
+    const int tx1 = min(tx0 + TILE, W) - 1, ty1 = min(ty0 + BAND, H) - 1;
+    const int y = ty0 + ly, x4 = tx0 + lx4;
+    const bool in_tile = y <= ty1 && x4 <= tx1;
+    const bool whole = in_tile && (W & 3) == 0 && x4 + 3 <= tx1;
+    const bool fused = ((ff | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
+    const size_t plane = (size_t)a.local_rows * (size_t)W;
+    const size_t off = (size_t)f * a.frame_stride + ((size_t)lb * BAND + (size_t)ly) * (size_t)W + (size_t)x4;
+    const float *gv = a.vis + off;
+    float *go = a.out + off;
+    // ---- 1. owner ids (index + 1 | S class; an index outside the frame's triangles is nobody), and z, α, β of owned quads
+    uint32_t id[4] = {0u, 0u, 0u, 0u};
+    if (whole) {
+      const uint4 q = *reinterpret_cast<const uint4 *>(gv + plane);
+      id[0] = q.x, id[1] = q.y, id[2] = q.z, id[3] = q.w;
+    } else if (in_tile) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (x4 + k <= tx1) id[k] = f2u(gv[plane + k]);
+    }
+    const uint32_t n_tris = fd->n_tris;
+    uint32_t bogus = 0u; // bit k: pixel k's id word is neither 0 nor a triangle of the frame
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if ((id[k] & ~S_CLASS_BIT) - 1u >= n_tris) { // (0 and the bare class bit wrap to 0xffffffff)
+        if (id[k] != 0u) bogus |= 1u << k;
+        id[k] = 0u;
+      }
+    s_bog[tid] = (uint8_t)bogus; // (read back by the in-place write-out only: no register holds it across the passes)
+    // (what the write-out needs of the ids: one bit per pixel — the ids and the quads below are not kept alive across the passes)
+    const uint32_t own = (id[0] != 0u ? 1u : 0u) | (id[1] != 0u ? 2u : 0u) | (id[2] != 0u ? 4u : 0u) | (id[3] != 0u ? 8u : 0u);
+    const bool any_own = own != 0u;
+    float4 in[3] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+    if (any_own) {
+      if (whole) {
+        in[0] = *reinterpret_cast<const float4 *>(gv);
+        in[1] = *reinterpret_cast<const float4 *>(gv + 2 * plane);
+        in[2] = *reinterpret_cast<const float4 *>(gv + 3 * plane);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (x4 + k <= tx1) quad_at(in[0], k) = gv[k], quad_at(in[1], k) = gv[2 * plane + k], quad_at(in[2], k) = gv[3 * plane + k];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) *reinterpret_cast<float4 *>(&s_in[i][p0]) = in[i];
+    // ---- 2. compaction by class (k_shade's: per-thread counts, one packed wave scan, the waves' totals through LDS)
+    uint32_t cnt2 = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cnt2 += id[k] == 0u ? 0u : ((id[k] & S_CLASS_BIT) ? 0x10000u : 1u);
+    const uint32_t incl2 = wave_scan_add(cnt2);
+    if (lane == 63) s_wcnt[wave] = incl2;
+    if (tid == 0) s_flag = 0u;
+    __syncthreads();
+    uint32_t bV = 0, bS = 0, nV = 0, nS = 0;
+#pragma unroll
+    for (int w2 = 0; w2 < 4; ++w2) {
+      const uint32_t t2 = s_wcnt[w2];
+      bV += w2 < wave ? (t2 & 0xffffu) : 0u, bS += w2 < wave ? (t2 >> 16) : 0u, nV += t2 & 0xffffu, nS += t2 >> 16;
+    }
+    nV = (uint32_t)__builtin_amdgcn_readfirstlane((int)nV), nS = (uint32_t)__builtin_amdgcn_readfirstlane((int)nS);
+    {
+      uint32_t oV = bV + ((incl2 - cnt2) & 0xffffu), oS = nV + bS + ((incl2 - cnt2) >> 16);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (id[k] == 0u) continue;
+        const bool isS = (id[k] & S_CLASS_BIT) != 0u;
+        const uint32_t o = isS ? oS++ : oV++;
+        s_idx[o] = (id[k] & ~S_CLASS_BIT) - 1u, s_pix[o] = (uint16_t)(p0 + k);
+      }
+    }
+    __syncthreads();
+    // ---- 3. the shading passes over 64-entry chunks, dealt round-robin to the waves (S chunks first, as k_shade)
+    if (nV + nS != 0u) { // workgroup-uniform
+      const SRZ_CAS srz_tri *tris = as_const(a.tris) + fd->tri_off;
+      const SRZ_CAS uint16_t *tri_batch = as_const(a.tri_batch) + fd->tri_off;
+      const SRZ_CAS ShadeDescG *sdesc = as_const(a.sdesc) + fd->batch_off;
+      const uint32_t cV = (nV + 63) >> 6, cS = (nS + 63) >> 6;
+      // GEN: per-pixel generality (the generic build's instantiation: any shader, run-time light count, pow_cr)
+      auto class_pass = [&](auto policy, auto is_v, auto gen_c) -> bool {
+        using M = decltype(policy);
+        constexpr bool isV = decltype(is_v)::value, GEN = decltype(gen_c)::value;
+        bool bad = false;
+        FrameK K;
+        K.eye[0] = fd->eye[0], K.eye[1] = fd->eye[1], K.eye[2] = fd->eye[2];
+        K.ka[0] = fd->ka[0], K.ka[1] = fd->ka[1], K.ka[2] = fd->ka[2];
+        K.ks[0] = fd->ks[0], K.ks[1] = fd->ks[1], K.ks[2] = fd->ks[2];
+        K.p = fd->p, K.kh = fd->kh, K.kn = fd->kn, K.n_lights = fd->n_lights;
+        K.grey = (ff & FD_GREY) != 0u;
+        K.lights = as_const(a.lights) + fd->light_off;
+        for (uint32_t c = (uint32_t)wave; c < cV + cS; c += 4) {
+          if ((c >= cS) != isV) continue;
+          const uint32_t i = (isV ? c - cS : c) * 64 + lane;
+          if (i >= (isV ? nV : nS)) continue;
+          const uint32_t slot = isV ? i : nV + i;
+          const uint32_t idx = s_idx[slot], p = s_pix[slot];
+          // the owner's normals and texture coordinates (floats 9..23 of its record) and its batch
+          TriFetch tf;
+          const SRZ_CAS f32x4 *tq = reinterpret_cast<const SRZ_CAS f32x4 *>(tris + idx);
+          const F3 n0 = ld3(reinterpret_cast<const SRZ_CAS float *>(tq) + 9);
+          tf.q2 = f32x4{0.f, n0.x, n0.y, n0.z}, tf.q3 = tq[3], tf.q4 = tq[4], tf.q5 = tq[5];
+          tf.batch = tri_batch[idx];
+          TriAttr at;
+          unpack_attr(tf, at);
+          const float zz = s_in[0][p], alpha = s_in[1][p], beta = s_in[2][p];
+          const float gamma = isV ? 1.0f - (alpha + beta) : 1.0f - alpha - beta; // (cover_v / cover_s)
+          const float fx = (float)(tx0 + (int)(p & 31u)), fy = (float)(ty0 + (int)(p >> 5));
+          float r0 = 1.f, r1 = 2.f, r2 = 3.f;
+          M m;
+          ShadeDesc sd;
+          if constexpr (!GEN) {
+            // batch by batch, the batch's descriptor wave-uniform and one scalar switch on its shader type (k_shade, MODE 0)
+            bool todo = true;
+            for (unsigned long long tm = __ballot(true); tm != 0ull; tm = __ballot(todo)) {
+              const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)tf.batch, __builtin_ctzll(tm));
+              const SRZ_CAS ShadeDescG *g = sdesc + b0; // (uniform address: scalar loads)
+              sd.shader = g->shader, sd.tw = g->tw, sd.th = g->th, sd.tex = as_const(g->tex);
+              if (todo && tf.batch == b0) {
+                auto run = [&](auto sh) {
+                  if constexpr (isV)
+                    shade_bary_v<M, decltype(sh)::value, FASTNL>(m, K, sd, at, alpha, beta, gamma, fx, fy, zz, r0, r1, r2);
+                  else
+                    shade_bary_s<M, decltype(sh)::value, FASTNL>(m, K, sd, at, alpha, beta, gamma, fx, fy, zz, r0, r1, r2);
+                };
+                const int sh0 = sd.shader; // wave-uniform
+                if (sh0 == SRZ_SHADER_TEXTURE)
+                  run(std::integral_constant<int, SRZ_SHADER_TEXTURE>{});
+                else if (sh0 == SRZ_SHADER_PHONG)
+                  run(std::integral_constant<int, SRZ_SHADER_PHONG>{});
+                else if (!BUMPY || sh0 == SRZ_SHADER_NORMAL)
+                  run(std::integral_constant<int, SRZ_SHADER_NORMAL>{});
+                else if constexpr (BUMPY) {
+                  if (sh0 == SRZ_SHADER_BUMP)
+                    run(std::integral_constant<int, SRZ_SHADER_BUMP>{});
+                  else
+                    run(std::integral_constant<int, SRZ_SHADER_DISPLACEMENT>{});
+                }
+                todo = false;
+              }
+            }
+          } else {
+            const SRZ_CAS ShadeDescG *g = sdesc + tf.batch;
+            sd.shader = g->shader, sd.tw = g->tw, sd.th = g->th, sd.tex = as_const(g->tex);
+            if constexpr (isV)
+              shade_bary_v<M, -1, 0>(m, K, sd, at, alpha, beta, gamma, fx, fy, zz, r0, r1, r2);
+            else
+              shade_bary_s<M, -1, 0>(m, K, sd, at, alpha, beta, gamma, fx, fy, zz, r0, r1, r2);
+          }
+          if constexpr (std::is_same<M, FastMath>::value) bad |= m.is_bad();
+          s_c[0][p] = r0, s_c[1][p] = r1, s_c[2][p] = r2;
+        }
+        return bad;
+      };
+      auto dense_passes = [&](auto policy, auto gen_c) -> bool {
+        const bool bv = class_pass(policy, std::true_type{}, gen_c);
+        const bool bs = class_pass(policy, std::false_type{}, gen_c);
+        return bv | bs;
+      };
+      if constexpr (APPROX) {
+        dense_passes(ApproxMath{}, std::false_type{});
+      } else if constexpr (MODE == 2) {
+        dense_passes(IeeeMath{}, std::true_type{});
+      } else {
+        // FastMath first; a tile where an operand left its range is shaded again with the IEEE expansions by the generic build — the
+        // FAST builds hand it back (as k_shade's do: the IEEE instantiation inside them would cost each its register budget)
+        const bool bad = dense_passes(FastMath{}, std::integral_constant<bool, MODE == 1>{});
+        if (__ballot(bad) != 0ull && lane == 0) s_flag = 1u;
+        __syncthreads();
+        if (s_flag) { // (workgroup-uniform)
+          if constexpr (MODE == 0) {
+            if (tid == 0) a.redo_list[atomicAdd(a.redo_count, 1u)] = f * tpf + t;
+            __syncthreads();
+            return; // (the generic build writes the whole tile)
+          } else {
+            dense_passes(IeeeMath{}, std::true_type{});
+          }
+        }
+      }
+      __syncthreads();
+    }
+    // ---- 4. write-out: owned pixels z + colour (in place: colour only), the others the clear values with SRZ_FUSED_CLEAR
+    const uint32_t bog = (a.in_place && fused) ? (uint32_t)s_bog[tid] : 0u; // (in place, fused: out-of-range ids get the clear values)
+    if (in_tile && (any_own || (fused && !a.in_place) || bog != 0u)) {
+      const bool own4 = own == 15u;
+      float4 q[4];
+      q[0] = *reinterpret_cast<const float4 *>(&s_in[0][p0]);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) q[i + 1] = *reinterpret_cast<const float4 *>(&s_c[i][p0]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (!(own & (1u << k))) {
+          quad_at(q[0], k) = __builtin_inff();
+#pragma unroll
+          for (int i = 1; i < 4; ++i) quad_at(q[i], k) = 0.f;
+        }
+      if (a.in_place) {
+        if (own4) {
+          const float4 c[3] = {q[1], q[2], q[3]};
+          quad_store(go + plane, plane, c, whole, x4, tx1);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            if (own & (1u << k)) {
+#pragma unroll
+              for (int i = 1; i < 4; ++i) go[i * plane + k] = quad_at(q[i], k);
+            } else if (bog & (1u << k)) { // (an out-of-range id: nobody, whose words are not the clear values yet)
+#pragma unroll
+              for (int i = 0; i < 4; ++i) go[i * plane + k] = quad_at(q[i], k);
+            }
+          }
+        }
+      } else if (fused || own4) {
+        quad_store(go, plane, q, whole, x4, tx1);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (own & (1u << k))
+#pragma unroll
+            for (int i = 0; i < 4; ++i) go[i * plane + k] = quad_at(q[i], k);
+      }
+    }
+    __syncthreads(); // LDS is reused by the next tile
+  };
+
+  // the frames of this build's kind, tile by tile: workgroup b walks frames f ≡ b mod 8 (fewer than 8 frames: every 8th tile)
+  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
+  for (uint32_t j = blockIdx.x >> 3; FAST || a.any_generic; j += step) {
+    uint32_t f, t;
+    if (a.n_frames >= 8u) {
+      f = sub + 8u * (j / tpf), t = j % tpf;
+      if (f >= a.n_frames) break;
+    } else {
+      const uint32_t i = j * 8u + sub;
+      if (i >= n_items) break;
+      f = i / tpf, t = i % tpf;
+    }
+    const uint32_t ff = as_const(a.frames)[f].flags;
+    const uint32_t kind = (ff & FD_FAST_SHADE) ? ((ff >> FD_NL_SHIFT) & 7u) - 1u + ((ff & FD_BUMPY) ? 4u : 0u) + ((ff & FD_GENPOW) ? 8u : 0u)
+                                               : SHADE_KIND_GENERIC;
+    if (kind != KIND) continue; // (workgroup-uniform: another launch's frame)
+    shade_tile(f, t, std::integral_constant<int, FAST ? 0 : 1>{});
+  }
+  if constexpr (!FAST) { // the tiles the FAST builds handed back (they ran before this kernel on the same stream)
+    const uint32_t n_redo = *as_const(a.redo_count);
+    for (uint32_t i = blockIdx.x; i < n_redo; i += gridDim.x) {
+      const uint32_t it = as_const(a.redo_list)[i];
+      shade_tile(it / tpf, it % tpf, std::integral_constant<int, 2>{});
+    }
+  }
+}
+
+// ================================================================================================================
 // k_resolve8 — display()'s resolve (src/Render.cpp:61-62): cv::merge(planes 0,1,2) + convertTo(CV_8UC3) =
 // saturate_cast<uchar>(cvRound(v)): round half to even, clamp to [0,255]; NaN → 0.  4 pixels per thread: three 16-byte
 // plane reads → 12 output bytes (three dword stores).
@@ -3361,6 +3683,33 @@ void launch_shade(const RenderArgs &a, uint32_t max_tiles, bool stats, uint32_t 
 void launch_visibility(const RenderArgs &a, uint32_t max_tiles, hipStream_t s) {
   if (max_tiles == 0) return;
   hipLaunchKernelGGL(k_visibility, shade_grid(a, max_tiles), dim3(256), 0, s, a);
+}
+
+void launch_shade_vis(const ShadeVisArgs &a, uint32_t fast_mask, bool any_generic, bool approx, hipStream_t s) {
+  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
+  if (items == 0) return;
+  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u), blk(256); // (a multiple of 8: workgroup b serves the frames f ≡ b mod 8)
+  if (approx) { // (classify_frames sets only the plain bits for the frames the tolerance builds shade)
+    if (fast_mask & 2u) hipLaunchKernelGGL((k_shade_vis<1, false, true>), grid, blk, 0, s, a);
+    if (fast_mask & 4u) hipLaunchKernelGGL((k_shade_vis<2, false, true>), grid, blk, 0, s, a);
+    if (fast_mask & 8u) hipLaunchKernelGGL((k_shade_vis<3, false, true>), grid, blk, 0, s, a);
+    if (fast_mask & 16u) hipLaunchKernelGGL((k_shade_vis<4, false, true>), grid, blk, 0, s, a);
+    fast_mask = 0;
+  }
+  if (fast_mask & 2u) hipLaunchKernelGGL((k_shade_vis<1, false>), grid, blk, 0, s, a);
+  if (fast_mask & 4u) hipLaunchKernelGGL((k_shade_vis<2, false>), grid, blk, 0, s, a);
+  if (fast_mask & 8u) hipLaunchKernelGGL((k_shade_vis<3, false>), grid, blk, 0, s, a);
+  if (fast_mask & 16u) hipLaunchKernelGGL((k_shade_vis<4, false>), grid, blk, 0, s, a);
+  if (fast_mask & 0x200u) hipLaunchKernelGGL((k_shade_vis<1, true>), grid, blk, 0, s, a);
+  if (fast_mask & 0x400u) hipLaunchKernelGGL((k_shade_vis<2, true>), grid, blk, 0, s, a);
+  if (fast_mask & 0x800u) hipLaunchKernelGGL((k_shade_vis<3, true>), grid, blk, 0, s, a);
+  if (fast_mask & 0x1000u) hipLaunchKernelGGL((k_shade_vis<4, true>), grid, blk, 0, s, a);
+  if (fast_mask & 0x20000u) hipLaunchKernelGGL((k_shade_vis<-1, false>), grid, blk, 0, s, a);
+  if (fast_mask & 0x40000u) hipLaunchKernelGGL((k_shade_vis<-2, false>), grid, blk, 0, s, a);
+  if (fast_mask & 0x80000u) hipLaunchKernelGGL((k_shade_vis<-3, false>), grid, blk, 0, s, a);
+  if (fast_mask & 0x100000u) hipLaunchKernelGGL((k_shade_vis<-4, false>), grid, blk, 0, s, a);
+  // the generic build also serves the tiles the FAST builds hand back (redo_count: zeroed by the caller)
+  if (any_generic || fast_mask) hipLaunchKernelGGL((k_shade_vis<0>), any_generic ? grid : dim3(std::min(grid.x, 128u)), blk, 0, s, a);
 }
 
 bool raster_four_waves(const RenderArgs &a) { return a.n_frames * a.n_local_bands * a.tiles_x <= 4096u; }

@@ -22,7 +22,8 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_comm_unique_id", "srz_comm_create", "srz_comm_destroy", "srz_frameset_exchange_bytes", "srz_frameset_allgather",
            "srz_frameset_deinterleave", "srz_frameset_allgather_inplace", "srz_frameset_gathered_row_offset",
            "srz_frameset_read_gathered_frame", "srz_frameset_sparse_capacity", "srz_frameset_sparse_pack", "srz_frameset_sparse_unpack",
-           "srz_frameset_allgather_sparse", "srz_frameset_render_visibility"]
+           "srz_frameset_allgather_sparse", "srz_frameset_render_visibility", "srz_frameset_shade_visibility",
+           "srz_frameset_update_shading"]
 
 
 class SrzError(RuntimeError):
@@ -67,6 +68,9 @@ def lib():
         L.srz_frameset_out_bytes.restype = C.c_size_t
         L.srz_frameset_render.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]
         L.srz_frameset_render_visibility.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]
+        L.srz_frameset_shade_visibility.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp]
+        L.srz_frameset_update_shading.argtypes = [vp, vp, C.POINTER(abi.SrzFrame), C.c_int]
+        L.srz_sceneset_update.argtypes = [vp, vp, C.POINTER(abi.SrzSceneFrame), C.c_int]
         L.srz_frameset_resolve8.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
         L.srz_frameset_stats.argtypes = [vp, vp, C.POINTER(abi.SrzStats)]
         L.srz_frameset_algorithmic_bytes.argtypes = [vp, vp]
@@ -145,6 +149,20 @@ class FrameSet:
         """the visibility buffer instead of the colour: planes z, id = triangle index in the frame + 1 | S class << 31 (0 = nobody),
         alpha, beta (include/srz.h; srz.visibility.decode takes it apart).  Same buffer and arguments as render().  Asynchronous."""
         self.ctx._check(lib().srz_frameset_render_visibility(self.ctx.h, self.h, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def shade_visibility(self, d_vis_ptr, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """the colour of a visibility buffer of this set (render_visibility) with the set's current shading data: equal bit for bit to
+        render() of the same frames.  d_out_ptr may equal d_vis_ptr (in place); a partial overlap is an error.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_shade_visibility(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_out_ptr), out_bytes,
+                                                            flags, _stream(stream)))
+
+    def update_shading(self, frames):
+        """new eye, ka, ks, p, kh, kn, lights, flags and batch shaders / textures for a set made from abi.Frame's, triangles untouched
+        (same frame count, size, light counts, batch counts and triangles per batch).  Ordered on the context's own stream."""
+        frames = list(frames)
+        arr = abi.frames_array(frames)
+        self.ctx._check(lib().srz_frameset_update_shading(self.ctx.h, self.h, arr, len(frames)))
+        self.frames = frames
 
     def resolve8(self, d_planes_ptr, d_bgr8_ptr, bgr8_bytes, stream=None):
         """display()'s 8-bit resolve on the device: planes (render output) → [frame][rows][W][3] uint8."""
