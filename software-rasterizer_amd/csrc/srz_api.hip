@@ -22,6 +22,19 @@ struct EventPair {
   hipEvent_t t0, t1, t2, t3; // t0..t1 setup+binning, t1..t2 raster (visibility + clear), t2..t3 shade
   bool detailed;             // t1 / t2 were recorded (every recorded event is a barrier in the launch stream: ≈4 µs each)
 };
+
+// host-side tables: a set's batches (resolve_shading turns them into the device's ShadeDescG) and a ctx's textures
+struct BatchDesc {
+  int32_t shader, tex_id;
+  uint32_t first, count; // triangle range inside the frame
+};
+struct TexDesc {
+  const uint32_t *bgrx; // one dword per texel: B | G<<8 | R<<16
+  int32_t w, h;
+};
+
+// the flags of srz_frame / srz_scene_frame / a render that the device sees (FrameDesc::flags, RenderArgs::flags_or)
+constexpr uint32_t FRAME_FLAGS = SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER;
 } // namespace
 
 struct srz_ctx {
@@ -31,7 +44,6 @@ struct srz_ctx {
   int shard_rank = 0, shard_world = 1;
   TexDesc h_tex[MAX_TEX];
   uint32_t *d_texmem[MAX_TEX];
-  TexDesc *d_tex = nullptr;
   unsigned long long *d_stats = nullptr;
   struct MeshSlot {
     srz_vertex *d_verts = nullptr;
@@ -100,15 +112,14 @@ struct srz_frameset {
   std::vector<FrameDesc> h_frames;
   std::vector<BatchDesc> h_batches;
   std::vector<ShadeDescG> h_sdesc;
-  std::vector<srz_light> h_lights; // refresh_frames: the host copy of the lights of the last update (what classify_frames reads)
+  std::vector<srz_light> h_lights; // the host copy of the lights, indexed by FrameDesc::light_off (what classify_frames reads)
   FrameDesc *d_frames = nullptr;
   srz_tri *d_tris = nullptr;     // the triangle stream as uploaded
   float *d_tri_pos = nullptr;    // dense copy of its positions (9 floats per triangle); null: srz_draw's one-frame set, re-uploaded per call
   bool tris_aos = false;
   BBox *d_bbox = nullptr;
   uint16_t *d_tri_batch = nullptr;
-  BatchDesc *d_batches = nullptr;
-  srz_light *d_lights = nullptr;
+  srz_light *d_lights = nullptr; // (d_frames / d_lights / d_draws point into d_dyn)
   // per-tile triangle lists: records in a pool of n_sub sub-pools (srz_device.h, RenderArgs); every render reports what
   // it asked of each sub-pool (h_pool_heads: mapped host memory the device stores into), and a render that finds the previous demand
   // above the capacity grows the pool first — so the memory is O(triangle-tile pairs), not O(bands x triangles)
@@ -125,7 +136,7 @@ struct srz_frameset {
   uint32_t *d_sparse_rows = nullptr;
   uint32_t *d_slow_list = nullptr, *d_slow_count = nullptr;
   uint4 *d_redo_list = nullptr; // (its counter is d_slow_count[1])
-  uint32_t fast_mask = 0;   // bit NL (+ 8 with BUMP / DISPLACEMENT batches, + 16 with a non-integer exponent): some frame is shaded by that FAST build of k_shade (classify_frames)
+  uint32_t fast_kinds = 0;  // bit k: some frame is shaded by the FAST build of kind k (srz_device.h, frame_kind; classify_frames)
   bool any_generic = true;  // some frame needs the generic build
   uint32_t *d_vis = nullptr, *d_work_count = nullptr, *d_chunk_rows = nullptr; // d_vis: the per-tile pixel lists (srz_device.h)
   uint4 *d_worklist = nullptr;
@@ -140,8 +151,8 @@ struct srz_frameset {
   uint64_t total_groups = 0;
   ShadeDescG *d_sdesc = nullptr;
   DrawDesc *d_draws = nullptr; // device vertex stage (srz_sceneset_create), else null
-  // scenesets keep everything srz_sceneset_update rewrites in ONE device block [FrameDesc | lights | DrawDesc] that is
-  // refreshed by a single asynchronous copy from a small ring of pinned staging buffers (no stream sync per frame)
+  // every set keeps what an update rewrites in ONE device block [FrameDesc x n | lights | DrawDesc x draws] that is refreshed by a
+  // single asynchronous copy from a small ring of pinned staging buffers (upload_dyn; no stream sync per update), made at the first update
   static constexpr int STAGE_RING = 4;
   uint8_t *d_dyn = nullptr;
   size_t dyn_bytes = 0, dyn_lights_off = 0, dyn_draws_off = 0;
@@ -215,16 +226,15 @@ void shard_layout(int height, int rank, int world, uint32_t &n_bands, uint32_t &
 // 0 <= p <= 256 takes the builds with the exact multiplication chains, a non-integer exponent in (0, 4096] the builds whose power
 // is pow_fast (FD_GENPOW; not combined with BUMP / DISPLACEMENT batches), every other exponent the generic build.  Sets FD_FAST_SHADE + the
 // light count in the host copies of the descriptors.
-// (lights: the host copy of the set's lights, indexed by FrameDesc::light_off — or, `one_frame`, that one frame's own array)
-void classify_frames(srz_frameset *fs, const srz_light *lights, bool one_frame = false) {
-  fs->fast_mask = 0, fs->any_generic = false;
+// (the lights: the set's host copy, fs->h_lights)
+void classify_frames(srz_frameset *fs) {
+  fs->fast_kinds = 0, fs->any_generic = false;
   for (FrameDesc &d : fs->h_frames) {
     // FD_GREY: three bit-equal channels in ka, ks and every light's intensity (the shaders then compute a PHONG pixel's channel once)
-    bool grey = lights != nullptr || d.n_lights == 0;
-    grey = grey && std::memcmp(&d.ka[0], &d.ka[1], 4) == 0 && std::memcmp(&d.ka[1], &d.ka[2], 4) == 0 &&
-           std::memcmp(&d.ks[0], &d.ks[1], 4) == 0 && std::memcmp(&d.ks[1], &d.ks[2], 4) == 0;
+    bool grey = std::memcmp(&d.ka[0], &d.ka[1], 4) == 0 && std::memcmp(&d.ka[1], &d.ka[2], 4) == 0 &&
+                std::memcmp(&d.ks[0], &d.ks[1], 4) == 0 && std::memcmp(&d.ks[1], &d.ks[2], 4) == 0;
     for (uint32_t l = 0; grey && l < d.n_lights; ++l) {
-      const srz_light &L = lights[(one_frame ? 0u : d.light_off) + l];
+      const srz_light &L = fs->h_lights[d.light_off + l];
       grey = std::memcmp(&L.intensity[0], &L.intensity[1], 4) == 0 && std::memcmp(&L.intensity[1], &L.intensity[2], 4) == 0;
     }
     const bool intpow = d.p >= 0.0f && d.p <= 256.0f && d.p == std::trunc(d.p);
@@ -243,26 +253,16 @@ void classify_frames(srz_frameset *fs, const srz_light *lights, bool one_frame =
               (fast ? (FD_FAST_SHADE | (d.n_lights << FD_NL_SHIFT) | (bumpy ? FD_BUMPY : 0u) | (plain ? 0u : FD_GENPOW)) : 0u) |
               ((d.n_tris < PACK_IDX_MASK && d.n_batches <= PACK_MAX_BATCHES && !fs->no_packed) ? FD_PACKED : 0u);
     if (fast)
-      fs->fast_mask |= 1u << (d.n_lights + (bumpy ? 8u : 0u) + (plain ? 0u : 16u));
+      fs->fast_kinds |= 1u << frame_kind(d.flags);
     else
       fs->any_generic = true;
   }
 }
 
-// the build kinds (srz_device.h: SHADE_KIND_*) the classified frames send tiles to, as a bit mask; the generic kind always (counting
-// runs and SRZ_ORDERED... send everything there)
-uint32_t kinds_needed(const srz_frameset *fs) {
-  uint32_t m = 1u << SHADE_KIND_GENERIC;
-  for (uint32_t nl = 1; nl <= 4; ++nl) {
-    if (fs->fast_mask & (1u << nl)) m |= 1u << (nl - 1u);
-    if (fs->fast_mask & (1u << (8u + nl))) m |= 1u << (nl - 1u + 4u);
-    if (fs->fast_mask & (1u << (16u + nl))) m |= 1u << (nl - 1u + 8u);
-  }
-  return m;
-}
-// (re)allocates the work-list storage when the set needs a kind that has no slot yet; hipSuccess when nothing had to change
+// (re)allocates the work-list storage when the set needs a kind that has no slot yet; hipSuccess when nothing had to change.  The
+// generic kind always has one (counting runs and the FAST builds' redo tiles go there)
 hipError_t ensure_worklists(srz_frameset *fs) {
-  const uint32_t need = kinds_needed(fs) | fs->kind_mask;
+  const uint32_t need = fs->fast_kinds | 1u << SHADE_KIND_GENERIC | fs->kind_mask;
   if (need == fs->kind_mask && fs->d_worklist) return hipSuccess;
   uint64_t slots = 0;
   uint32_t n = 0;
@@ -287,17 +287,11 @@ void free_frameset_buffers(srz_frameset *fs) {
     if (fs->h_stage[i]) (void)hipHostFree(fs->h_stage[i]);
     if (fs->stage_ev[i]) (void)hipEventDestroy(fs->stage_ev[i]);
   }
-  if (fs->d_dyn) { // d_frames / d_lights / d_draws point into the block
-    (void)hipFree(fs->d_dyn);
-    fs->d_frames = nullptr, fs->d_lights = nullptr, fs->d_draws = nullptr;
-  }
-  (void)hipFree(fs->d_frames);
+  (void)hipFree(fs->d_dyn); // (d_frames / d_lights / d_draws)
   (void)hipFree(fs->d_tris);
   (void)hipFree(fs->d_tri_pos);
   (void)hipFree(fs->d_bbox);
   (void)hipFree(fs->d_tri_batch);
-  (void)hipFree(fs->d_batches);
-  (void)hipFree(fs->d_lights);
   (void)hipFree(fs->d_pool);
   (void)hipFree(fs->d_pool_heads);
   if (fs->h_pool_heads) (void)hipHostFree(fs->h_pool_heads);
@@ -315,7 +309,6 @@ void free_frameset_buffers(srz_frameset *fs) {
   (void)hipFree(fs->d_band_desc);
   (void)hipFree(fs->d_band_ent);
   (void)hipFree(fs->d_sdesc);
-  (void)hipFree(fs->d_draws);
 }
 
 // What a render asks for.  VISIBILITY: k_visibility writes the visibility buffer where k_shade would write colour (no texture needed; no
@@ -349,9 +342,7 @@ RenderArgs make_args(const srz_ctx *ctx, const srz_frameset *fs, float *d_out, u
   a.band_desc = fs->d_band_desc;
   a.band_ent = fs->d_band_ent;
   a.tri_batch = fs->d_tri_batch;
-  a.batches = fs->d_batches;
   a.lights = fs->d_lights;
-  a.tex = ctx->d_tex;
   a.pool = fs->d_pool;
   a.pool_heads = fs->d_pool_heads;
   a.pool_demand = fs->h_pool_heads; // (hipHostMallocMapped: the same address on the device)
@@ -521,7 +512,7 @@ struct ClearPlan {
 uint32_t clear_memo(srz_ctx *ctx, const srz_frameset *fs, uint32_t wgs) {
   uint64_t key = 0xcbf29ce484222325ull;
   for (uint64_t v : {(uint64_t)fs->width, (uint64_t)fs->height, (uint64_t)fs->n_frames, (uint64_t)fs->n_local_bands, fs->total_tris,
-                     (uint64_t)fs->fast_mask, (uint64_t)fs->approx_shade})
+                     (uint64_t)fs->fast_kinds, (uint64_t)fs->approx_shade})
     key = (key ^ v) * 0x100000001b3ull;
   auto it = std::find_if(ctx->clear_memo.begin(), ctx->clear_memo.end(), [&](const std::pair<uint64_t, uint32_t> &m) { return m.first == key; });
   if (wgs == 0u) return it != ctx->clear_memo.end() ? it->second : 0u;
@@ -627,19 +618,25 @@ int enqueue_sub_batch(srz_ctx *ctx, srz_frameset *fs, const RenderPlan &r, Rende
   }
   if (r.ep) HIP_TRY(ctx, hipEventRecord(r.ep->t2, s));
   if (r.pass.kind == Pass::VISIBILITY) launch_visibility(v, tiles, s);
-  else launch_shade(v, tiles, stats, fs->fast_mask, fs->any_generic, fs->approx_shade, s);
+  else launch_shade(v, tiles, stats, fs->fast_kinds, fs->any_generic, fs->approx_shade, s);
   if (r.side) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join[ev], 0));
   else if (!raster_four_waves(v)) // (the latency build of k_raster stores the demand itself)
     HIP_TRY(ctx, copy_demand(fs, part, s));
   return SRZ_OK;
 }
 
-// setup → bands → raster → shade for every frame of the set (or of pass.f_begin.., pass.f_count), asynchronously on `s`
-int render_impl(srz_ctx *ctx, srz_frameset *fs, float *d_out, uint32_t flags_or, hipStream_t s, Pass pass) {
-  const bool stats = pass.kind == Pass::COUNTING, size_only = pass.kind == Pass::SIZE_ONLY;
+// a set the ctx can render or shade now: made under the ctx's shard, its last update complete
+int check_renderable(srz_ctx *ctx, const srz_frameset *fs) {
   if (fs->shard_rank != ctx->shard_rank || fs->shard_world != ctx->shard_world)
     return fail(ctx, SRZ_E_INVALID, "frameset was created under a different shard (call srz_set_shard before srz_frameset_create)");
   if (fs->update_failed) return fail(ctx, SRZ_E_NOMEM, "the last update of this set failed (out of memory): update it again or destroy it");
+  return SRZ_OK;
+}
+
+// setup → bands → raster → shade for every frame of the set (or of pass.f_begin.., pass.f_count), asynchronously on `s`
+int render_impl(srz_ctx *ctx, srz_frameset *fs, float *d_out, uint32_t flags_or, hipStream_t s, Pass pass) {
+  const bool stats = pass.kind == Pass::COUNTING, size_only = pass.kind == Pass::SIZE_ONLY;
+  if (int rc = check_renderable(ctx, fs)) return rc;
   if (pass.kind == Pass::COLOUR || stats)
     if (int rc = resolve_shading(ctx, fs, s)) return rc;
   // The record pool follows what the previous renders asked for: growing is rare and the one place where a render waits for the device.
@@ -704,8 +701,7 @@ int render_entry(const char *name, srz_ctx *ctx, srz_frameset *fs, void *d_out, 
   if (out_bytes < srz_frameset_out_bytes(ctx, fs)) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
   if (((uintptr_t)d_out & 15u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": output must be 16-byte aligned");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  flags &= SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER;
-  return render_impl(ctx, fs, (float *)d_out, flags, pick_stream(ctx, stream), pass);
+  return render_impl(ctx, fs, (float *)d_out, flags & FRAME_FLAGS, pick_stream(ctx, stream), pass);
 }
 
 int read_stats(srz_ctx *ctx, hipStream_t s, srz_stats *st) {
@@ -766,15 +762,12 @@ int srz_create(srz_ctx **out, int device_id) {
   auto bail = [&](const char *what, hipError_t err) {
     g_create_error = std::string(what) + ": " + hipGetErrorString(err);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    (void)hipFree(ctx->d_tex);
     (void)hipFree(ctx->d_stats);
     delete ctx;
     return SRZ_E_NODEVICE;
   };
   if ((e = hipSetDevice(device_id)) != hipSuccess) return bail("hipSetDevice", e);
   if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
-  if ((e = hipMalloc(&ctx->d_tex, sizeof(TexDesc) * MAX_TEX)) != hipSuccess) return bail("hipMalloc(tex table)", e);
-  if ((e = hipMemset(ctx->d_tex, 0, sizeof(TexDesc) * MAX_TEX)) != hipSuccess) return bail("hipMemset", e);
   if ((e = hipMalloc(&ctx->d_stats, sizeof(unsigned long long) * ST_COUNT)) != hipSuccess) return bail("hipMalloc(stats)", e);
   *out = ctx;
   return SRZ_OK;
@@ -792,7 +785,6 @@ void srz_destroy(srz_ctx *ctx) {
   for (auto &ep : ctx->ev_pool) (void)hipEventDestroy(ep.t0), (void)hipEventDestroy(ep.t1), (void)hipEventDestroy(ep.t2), (void)hipEventDestroy(ep.t3);
   for (int i = 0; i < MAX_TEX; ++i) (void)hipFree(ctx->d_texmem[i]);
   for (int i = 0; i < MAX_MESH; ++i) (void)hipFree(ctx->mesh[i].d_verts), (void)hipFree(ctx->mesh[i].d_faces);
-  (void)hipFree(ctx->d_tex);
   (void)hipFree(ctx->d_stats);
   destroy_side(ctx->stream2, ctx->ev_fork, ctx->ev_join);
   destroy_side(ctx->stream3, ctx->ev_piece);
@@ -849,11 +841,57 @@ int srz_texture_upload(srz_ctx *ctx, int tex_id, const uint8_t *bgr, int w, int 
   ctx->d_texmem[tex_id] = d_px;
   ctx->h_tex[tex_id] = TexDesc{d_px, w, h};
   ctx->tex_version++;
-  HIP_TRY(ctx, hipMemcpy(ctx->d_tex + tex_id, &ctx->h_tex[tex_id], sizeof(TexDesc), hipMemcpyHostToDevice));
   return SRZ_OK;
 }
 
-static int build_frameset(srz_ctx *ctx, const srz_frame *frames, int n_frames, srz_frameset **out, bool copy_tris, bool tris_aos = false) {
+// the one writer of a frame's shading data: eye, ka, ks, p, kh, kn and the flags the device sees (classify_frames adds its own)
+static void set_shading(FrameDesc &d, const srz_frame &fr) {
+  std::memcpy(d.eye, fr.eye, sizeof d.eye), std::memcpy(d.ka, fr.ka, sizeof d.ka), std::memcpy(d.ks, fr.ks, sizeof d.ks);
+  d.p = fr.p, d.kh = fr.kh, d.kn = fr.kn;
+  d.flags = fr.flags & FRAME_FLAGS;
+}
+
+// the set's block [FrameDesc x n | lights | DrawDesc x draws] from its host copies into `st`, laid out as d_dyn
+static void stage_dyn(const srz_frameset *fs, uint8_t *st) {
+  std::memcpy(st, fs->h_frames.data(), sizeof(FrameDesc) * fs->h_frames.size());
+  if (!fs->h_lights.empty()) std::memcpy(st + fs->dyn_lights_off, fs->h_lights.data(), sizeof(srz_light) * fs->h_lights.size());
+  if (!fs->h_draws.empty()) std::memcpy(st + fs->dyn_draws_off, fs->h_draws.data(), sizeof(DrawDesc) * fs->h_draws.size());
+}
+
+// The set's staging ring, made at its first update, all or nothing: out of memory leaves the set as it was
+static int ensure_stage_ring(srz_ctx *ctx, srz_frameset *fs, const char *who) {
+  if (fs->h_stage[0]) return SRZ_OK;
+  for (int i = 0; i < srz_frameset::STAGE_RING; ++i) {
+    hipError_t e = hipHostMalloc((void **)&fs->h_stage[i], fs->dyn_bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&fs->stage_ev[i], hipEventDisableTiming);
+    if (e != hipSuccess) {
+      for (int j = 0; j <= i; ++j) {
+        if (fs->h_stage[j]) (void)hipHostFree(fs->h_stage[j]);
+        if (fs->stage_ev[j]) (void)hipEventDestroy(fs->stage_ev[j]);
+        fs->h_stage[j] = nullptr, fs->stage_ev[j] = nullptr;
+      }
+      return fail(ctx, e == hipErrorOutOfMemory ? SRZ_E_NOMEM : SRZ_E_NODEVICE, std::string(who) + ": staging buffers: " + hipGetErrorString(e));
+    }
+  }
+  return SRZ_OK;
+}
+
+// The block's upload: ONE asynchronous copy on the context's stream from the next slot of the ring, ordered after every render already
+// submitted there (which may still be reading the block) and before the next one.  Renders submitted on OTHER streams are the caller's
+// to order.
+static int upload_dyn(srz_ctx *ctx, srz_frameset *fs) {
+  const unsigned slot = fs->stage_next++ % srz_frameset::STAGE_RING;
+  if (fs->stage_busy[slot]) HIP_TRY(ctx, hipEventSynchronize(fs->stage_ev[slot])); // its copy of 4 updates ago
+  stage_dyn(fs, fs->h_stage[slot]);
+  HIP_TRY(ctx, hipMemcpyAsync(fs->d_dyn, fs->h_stage[slot], fs->dyn_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipEventRecord(fs->stage_ev[slot], ctx->stream));
+  fs->stage_busy[slot] = true;
+  return SRZ_OK;
+}
+
+// draws: the DrawDescs of a sceneset (their tri_off in the set's triangle order), null for a frameset
+static int build_frameset(srz_ctx *ctx, const srz_frame *frames, int n_frames, srz_frameset **out, bool copy_tris, bool tris_aos = false,
+                          const std::vector<DrawDesc> *draws = nullptr) {
   if (!ctx) return SRZ_E_INVALID;
   if (!out) return fail(ctx, SRZ_E_INVALID, "srz_frameset_create: out is NULL");
   *out = nullptr;
@@ -883,13 +921,9 @@ static int build_frameset(srz_ctx *ctx, const srz_frame *frames, int n_frames, s
     if (fr.n_batches > 65535) return bad("more than 65535 batches");
     FrameDesc d{};
     d.width = W, d.height = H;
-    std::memcpy(d.eye, fr.eye, sizeof d.eye);
-    std::memcpy(d.ka, fr.ka, sizeof d.ka);
-    std::memcpy(d.ks, fr.ks, sizeof d.ks);
-    d.p = fr.p, d.kh = fr.kh, d.kn = fr.kn;
+    set_shading(d, fr);
     d.n_lights = fr.n_lights, d.light_off = (uint32_t)light_off;
     d.tri_off = (uint32_t)tri_off, d.n_batches = fr.n_batches, d.batch_off = (uint32_t)batch_off;
-    d.flags = fr.flags & (SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER);
     uint64_t nt = 0;
     for (uint32_t b = 0; b < fr.n_batches; ++b) {
       const srz_batch &sb = fr.batches[b];
@@ -918,7 +952,7 @@ static int build_frameset(srz_ctx *ctx, const srz_frame *frames, int n_frames, s
   std::vector<srz_tri> h_tris(copy_tris ? (size_t)tri_off : 0);
   std::vector<float> h_pos(copy_tris && !fs->tris_aos ? (size_t)tri_off * TRI_POS_F : 0); // the dense copy of the positions
   std::vector<uint16_t> h_tb((size_t)tri_off);
-  std::vector<srz_light> h_lights((size_t)light_off);
+  fs->h_lights.resize((size_t)light_off);
   for (int f = 0; f < n_frames; ++f) {
     const srz_frame &fr = frames[f];
     const FrameDesc &d = fs->h_frames[f];
@@ -933,14 +967,28 @@ static int build_frameset(srz_ctx *ctx, const srz_frame *frames, int n_frames, s
       std::fill(h_tb.begin() + o, h_tb.begin() + o + sb.n_tris, (uint16_t)b);
       o += sb.n_tris;
     }
-    if (fr.n_lights) std::memcpy(&h_lights[d.light_off], fr.lights, sizeof(srz_light) * fr.n_lights);
+    if (fr.n_lights) std::memcpy(&fs->h_lights[d.light_off], fr.lights, sizeof(srz_light) * fr.n_lights);
   }
-  classify_frames(fs, h_lights.data());
+  classify_frames(fs);
+  if (draws) {
+    fs->h_draws = *draws, fs->n_draws = (uint32_t)draws->size();
+    for (const DrawDesc &dd : *draws) fs->max_faces = std::max(fs->max_faces, dd.n_faces);
+  }
+  // [FrameDesc x n | lights | DrawDesc x draws], 16-byte aligned parts
+  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  fs->dyn_lights_off = up16(sizeof(FrameDesc) * (size_t)n_frames);
+  fs->dyn_draws_off = up16(fs->dyn_lights_off + sizeof(srz_light) * (size_t)light_off);
+  fs->dyn_bytes = fs->dyn_draws_off + sizeof(DrawDesc) * fs->h_draws.size();
   auto dev_alloc = [&](void **p, size_t bytes) { return hipMalloc(p, std::max<size_t>(bytes, 256)); };
   hipError_t e = hipSuccess;
 #define FS_TRY(expr)                                                                                                   \
   if (e == hipSuccess) e = (expr)
-  FS_TRY(dev_alloc((void **)&fs->d_frames, sizeof(FrameDesc) * n_frames));
+  FS_TRY(dev_alloc((void **)&fs->d_dyn, fs->dyn_bytes));
+  if (e == hipSuccess) {
+    fs->d_frames = reinterpret_cast<FrameDesc *>(fs->d_dyn);
+    fs->d_lights = reinterpret_cast<srz_light *>(fs->d_dyn + fs->dyn_lights_off);
+    if (draws) fs->d_draws = reinterpret_cast<DrawDesc *>(fs->d_dyn + fs->dyn_draws_off);
+  }
   FS_TRY(dev_alloc((void **)&fs->d_tris, sizeof(srz_tri) * tri_off));
   if (!fs->tris_aos) FS_TRY(dev_alloc((void **)&fs->d_tri_pos, sizeof(float) * TRI_POS_F * tri_off + 16)); // (+16: slack behind the last triangle's 9 floats, which are read as three 12-byte pieces)
   FS_TRY(dev_alloc((void **)&fs->d_bbox, sizeof(BBox) * tri_off));
@@ -948,8 +996,6 @@ static int build_frameset(srz_ctx *ctx, const srz_frame *frames, int n_frames, s
   FS_TRY(dev_alloc((void **)&fs->d_band_desc, sizeof(uint32_t) * group_off * fs->n_local_bands));
   FS_TRY(dev_alloc((void **)&fs->d_band_ent, sizeof(uint2) * group_off * ENT_PER_GROUP));
   FS_TRY(dev_alloc((void **)&fs->d_tri_batch, sizeof(uint16_t) * tri_off));
-  FS_TRY(dev_alloc((void **)&fs->d_batches, sizeof(BatchDesc) * fs->h_batches.size()));
-  FS_TRY(dev_alloc((void **)&fs->d_lights, sizeof(srz_light) * light_off));
   fs->max_tiles = (uint32_t)n_frames * fs->n_local_bands * fs->tiles_x;
   {  // record pool: one sub-pool per ~128 binning workgroups (their bump allocators are single addresses); first guess
      // 4 records per triangle — the renders' own demand corrects it (render_impl)
@@ -979,15 +1025,14 @@ static int build_frameset(srz_ctx *ctx, const srz_frame *frames, int n_frames, s
   FS_TRY(ensure_worklists(fs)); // (8 lists per build kind the classified frames need: not all 104)
   FS_TRY(dev_alloc((void **)&fs->d_work_count, sizeof(uint32_t) * CNT_STRIDE * N_WORK_LISTS));
   FS_TRY(dev_alloc((void **)&fs->d_sdesc, sizeof(ShadeDescG) * fs->h_batches.size()));
-  FS_TRY(hipMemcpy(fs->d_frames, fs->h_frames.data(), sizeof(FrameDesc) * n_frames, hipMemcpyHostToDevice));
+  std::vector<uint8_t> h_dyn(fs->dyn_bytes);
+  stage_dyn(fs, h_dyn.data());
+  FS_TRY(hipMemcpy(fs->d_dyn, h_dyn.data(), fs->dyn_bytes, hipMemcpyHostToDevice));
   if (tri_off) {
     if (copy_tris) FS_TRY(hipMemcpy(fs->d_tris, h_tris.data(), sizeof(srz_tri) * tri_off, hipMemcpyHostToDevice));
     if (!h_pos.empty()) FS_TRY(hipMemcpy(fs->d_tri_pos, h_pos.data(), sizeof(float) * h_pos.size(), hipMemcpyHostToDevice));
     FS_TRY(hipMemcpy(fs->d_tri_batch, h_tb.data(), sizeof(uint16_t) * tri_off, hipMemcpyHostToDevice));
   }
-  if (!fs->h_batches.empty())
-    FS_TRY(hipMemcpy(fs->d_batches, fs->h_batches.data(), sizeof(BatchDesc) * fs->h_batches.size(), hipMemcpyHostToDevice));
-  if (light_off) FS_TRY(hipMemcpy(fs->d_lights, h_lights.data(), sizeof(srz_light) * light_off, hipMemcpyHostToDevice));
 #undef FS_TRY
   if (e != hipSuccess) {
     free_frameset_buffers(fs);
@@ -1041,6 +1086,33 @@ int srz_mesh_upload(srz_ctx *ctx, int mesh_id, const srz_vertex *verts, uint32_t
   return SRZ_OK;
 }
 
+// A sceneset's frames as srz_frames whose batches carry sizes only (k_vertex makes the triangles): fr[f], its batches in `batches`.
+// Every draw names an uploaded mesh (the callers have checked).
+static void scene_frames(const srz_ctx *ctx, const srz_scene_frame *frames, int n_frames, std::vector<srz_frame> &fr, std::vector<srz_batch> &batches) {
+  size_t n = 0;
+  for (int f = 0; f < n_frames; ++f) n += frames[f].n_draws;
+  fr.assign((size_t)n_frames, srz_frame{}), batches.assign(n, srz_batch{});
+  srz_batch *b = batches.data();
+  for (int f = 0; f < n_frames; ++f) {
+    const srz_scene_frame &sf = frames[f];
+    srz_frame &o = fr[f];
+    o.width = sf.width, o.height = sf.height;
+    std::memcpy(o.eye, sf.eye, sizeof o.eye), std::memcpy(o.ka, sf.ka, sizeof o.ka), std::memcpy(o.ks, sf.ks, sizeof o.ks);
+    o.p = sf.p, o.kh = sf.kh, o.kn = sf.kn;
+    o.n_lights = sf.n_lights, o.lights = sf.lights;
+    o.n_batches = sf.n_draws, o.batches = b;
+    o.flags = sf.flags;
+    for (uint32_t d = 0; d < sf.n_draws; ++d, ++b)
+      b->shader = sf.draws[d].shader, b->tex_id = sf.draws[d].tex_id, b->n_tris = ctx->mesh[sf.draws[d].mesh_id].n_faces;
+  }
+}
+// what a draw's vertex stage takes of the call: the frame's depth mapping and the draw's matrices
+static void set_draw(DrawDesc &dd, const srz_scene_frame &sf, const srz_mesh_draw &dr) {
+  dd.zscale = sf.zscale, dd.zoffset = sf.zoffset;
+  std::memcpy(dd.ndc_mvp, dr.ndc_mvp, sizeof dd.ndc_mvp), std::memcpy(dd.normal_m, dr.normal_m, sizeof dd.normal_m);
+}
+
+static int refresh_frames(srz_ctx *ctx, srz_frameset *fs, const srz_frame *frames, int n_frames, const char *who, bool copy_tris);
 static int sceneset_create_impl(srz_ctx *ctx, const srz_scene_frame *frames, int n_frames, srz_frameset **out, bool size_pool);
 int srz_sceneset_create(srz_ctx *ctx, const srz_scene_frame *frames, int n_frames, srz_frameset **out) {
   return sceneset_create_impl(ctx, frames, n_frames, out, /*size_pool=*/true);
@@ -1052,9 +1124,9 @@ static int sceneset_create_impl(srz_ctx *ctx, const srz_scene_frame *frames, int
   if (!out) return fail(ctx, SRZ_E_INVALID, "srz_sceneset_create: out is NULL");
   *out = nullptr;
   if (!frames || n_frames <= 0) return fail(ctx, SRZ_E_INVALID, "srz_sceneset_create: no frames");
-  // describe every frame as an srz_frame whose batches carry sizes only; the triangles are produced by k_vertex
-  std::vector<srz_frame> fr((size_t)n_frames);
-  std::vector<std::vector<srz_batch>> batches((size_t)n_frames);
+  std::vector<DrawDesc> draws;
+  std::vector<int> draw_mesh;
+  uint32_t first = 0; // (a draw's first triangle: the set's triangles are its frames' draws in order)
   for (int f = 0; f < n_frames; ++f) {
     const srz_scene_frame &sf = frames[f];
     if (sf.n_draws && !sf.draws) return fail(ctx, SRZ_E_INVALID, "srz_sceneset_create: null draws");
@@ -1062,66 +1134,21 @@ static int sceneset_create_impl(srz_ctx *ctx, const srz_scene_frame *frames, int
       const srz_mesh_draw &dr = sf.draws[d];
       if (dr.mesh_id < 0 || dr.mesh_id >= MAX_MESH || !ctx->mesh[dr.mesh_id].d_verts)
         return fail(ctx, SRZ_E_INVALID, "srz_sceneset_create: draw names a mesh slot that was never uploaded");
-      srz_batch b{};
-      b.shader = dr.shader, b.tex_id = dr.tex_id, b.n_tris = ctx->mesh[dr.mesh_id].n_faces, b.tris = nullptr;
-      batches[f].push_back(b);
-    }
-    srz_frame &o = fr[f];
-    o = srz_frame{};
-    o.width = sf.width, o.height = sf.height;
-    std::memcpy(o.eye, sf.eye, sizeof o.eye), std::memcpy(o.ka, sf.ka, sizeof o.ka), std::memcpy(o.ks, sf.ks, sizeof o.ks);
-    o.p = sf.p, o.kh = sf.kh, o.kn = sf.kn;
-    o.n_lights = sf.n_lights, o.lights = sf.lights;
-    o.n_batches = sf.n_draws, o.batches = batches[f].data();
-    o.flags = sf.flags;
-  }
-  srz_frameset *fs = nullptr;
-  int rc = build_frameset(ctx, fr.data(), n_frames, &fs, false);
-  if (rc) return rc;
-  std::vector<DrawDesc> h;
-  for (int f = 0; f < n_frames; ++f) {
-    uint32_t first = fs->h_frames[f].tri_off;
-    for (uint32_t d = 0; d < frames[f].n_draws; ++d) {
-      const srz_mesh_draw &dr = frames[f].draws[d];
       const srz_ctx::MeshSlot &m = ctx->mesh[dr.mesh_id];
       DrawDesc dd{};
       dd.verts = m.d_verts, dd.faces = m.d_faces, dd.n_faces = m.n_faces, dd.tri_off = first, dd.frame = (uint32_t)f;
-      dd.zscale = frames[f].zscale, dd.zoffset = frames[f].zoffset;
-      std::memcpy(dd.ndc_mvp, dr.ndc_mvp, sizeof dd.ndc_mvp), std::memcpy(dd.normal_m, dr.normal_m, sizeof dd.normal_m);
-      h.push_back(dd);
-      fs->h_draw_mesh.push_back(dr.mesh_id);
+      set_draw(dd, sf, dr);
+      draws.push_back(dd), draw_mesh.push_back(dr.mesh_id);
       first += m.n_faces;
-      fs->max_faces = std::max(fs->max_faces, m.n_faces);
     }
   }
-  fs->n_draws = (uint32_t)h.size();
-  fs->h_draws = h;
-  // one block for what srz_sceneset_update rewrites: [FrameDesc x n | lights | DrawDesc x draws], 16-byte aligned parts
-  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  fs->dyn_lights_off = up16(sizeof(FrameDesc) * (size_t)n_frames);
-  fs->dyn_draws_off = up16(fs->dyn_lights_off + sizeof(srz_light) * (size_t)fs->total_lights);
-  fs->dyn_bytes = up16(fs->dyn_draws_off + sizeof(DrawDesc) * std::max<size_t>(h.size(), 1));
-  uint8_t *blk = nullptr;
-  hipError_t e = hipMalloc(&blk, fs->dyn_bytes);
-  if (e == hipSuccess) e = hipMemcpy(blk, fs->d_frames, sizeof(FrameDesc) * (size_t)n_frames, hipMemcpyDeviceToDevice);
-  if (e == hipSuccess && fs->total_lights)
-    e = hipMemcpy(blk + fs->dyn_lights_off, fs->d_lights, sizeof(srz_light) * (size_t)fs->total_lights, hipMemcpyDeviceToDevice);
-  if (e == hipSuccess && !h.empty()) e = hipMemcpy(blk + fs->dyn_draws_off, h.data(), sizeof(DrawDesc) * h.size(), hipMemcpyHostToDevice);
-  for (int i = 0; e == hipSuccess && i < srz_frameset::STAGE_RING; ++i) {
-    e = hipHostMalloc((void **)&fs->h_stage[i], fs->dyn_bytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&fs->stage_ev[i], hipEventDisableTiming);
-  }
-  if (e != hipSuccess) {
-    (void)hipFree(blk);
-    srz_frameset_destroy(ctx, fs);
-    return fail(ctx, SRZ_E_NOMEM, std::string("srz_sceneset_create: ") + hipGetErrorString(e));
-  }
-  (void)hipFree(fs->d_frames);
-  (void)hipFree(fs->d_lights);
-  fs->d_dyn = blk;
-  fs->d_frames = reinterpret_cast<FrameDesc *>(blk);
-  fs->d_lights = reinterpret_cast<srz_light *>(blk + fs->dyn_lights_off);
-  fs->d_draws = reinterpret_cast<DrawDesc *>(blk + fs->dyn_draws_off);
+  std::vector<srz_frame> fr;
+  std::vector<srz_batch> batches;
+  scene_frames(ctx, frames, n_frames, fr, batches);
+  srz_frameset *fs = nullptr;
+  int rc = build_frameset(ctx, fr.data(), n_frames, &fs, false, false, &draws);
+  if (rc) return rc;
+  fs->h_draw_mesh = draw_mesh;
   *out = fs;
   return size_pool ? size_pool_at_create(ctx, out) : SRZ_OK; // (with the matrices of creation: a later srz_sceneset_update is followed by the lazy growth)
 }
@@ -1131,54 +1158,25 @@ int srz_sceneset_update(srz_ctx *ctx, srz_frameset *fs, const srz_scene_frame *f
   if (!fs || !frames || !fs->d_draws) return fail(ctx, SRZ_E_INVALID, "srz_sceneset_update: not a sceneset");
   if (n_frames != fs->n_frames) return fail(ctx, SRZ_E_INVALID, "srz_sceneset_update: frame count changed");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::vector<srz_light> h_lights((size_t)fs->total_lights);
-  size_t di = 0, bi = 0;
-  bool batches_changed = false;
-  for (int f = 0; f < n_frames; ++f) {
+  for (int f = 0, di = 0; f < n_frames; ++f) { // the mesh bindings (the frame path checks the rest)
     const srz_scene_frame &sf = frames[f];
-    FrameDesc &d = fs->h_frames[f];
+    const FrameDesc &d = fs->h_frames[f];
     if (sf.width != fs->width || sf.height != fs->height || sf.n_lights != d.n_lights || sf.n_draws != d.n_batches ||
         (sf.n_lights && !sf.lights) || (sf.n_draws && !sf.draws))
       return fail(ctx, SRZ_E_INVALID, "srz_sceneset_update: structure changed");
-    std::memcpy(d.eye, sf.eye, sizeof d.eye), std::memcpy(d.ka, sf.ka, sizeof d.ka), std::memcpy(d.ks, sf.ks, sizeof d.ks);
-    d.p = sf.p, d.kh = sf.kh, d.kn = sf.kn, d.flags = sf.flags & (SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER);
-    if (sf.n_lights) std::memcpy(&h_lights[d.light_off], sf.lights, sizeof(srz_light) * sf.n_lights);
-    for (uint32_t k = 0; k < sf.n_draws; ++k, ++di, ++bi) {
+    for (uint32_t k = 0; k < sf.n_draws; ++k, ++di) {
       const srz_mesh_draw &dr = sf.draws[k];
       if (dr.mesh_id != fs->h_draw_mesh[di] || dr.mesh_id < 0 || dr.mesh_id >= MAX_MESH ||
           ctx->mesh[dr.mesh_id].n_faces != fs->h_draws[di].n_faces || ctx->mesh[dr.mesh_id].d_verts != fs->h_draws[di].verts)
         return fail(ctx, SRZ_E_INVALID, "srz_sceneset_update: mesh binding changed");
-      if (dr.shader < SRZ_SHADER_NORMAL || dr.shader > SRZ_SHADER_BUMP) return fail(ctx, SRZ_E_INVALID, "srz_sceneset_update: unknown shader type");
-      DrawDesc &dd = fs->h_draws[di];
-      dd.zscale = sf.zscale, dd.zoffset = sf.zoffset;
-      std::memcpy(dd.ndc_mvp, dr.ndc_mvp, sizeof dd.ndc_mvp), std::memcpy(dd.normal_m, dr.normal_m, sizeof dd.normal_m);
-      BatchDesc &b = fs->h_batches[bi];
-      if (b.shader != dr.shader || b.tex_id != dr.tex_id) b.shader = dr.shader, b.tex_id = dr.tex_id, batches_changed = true;
     }
   }
-  classify_frames(fs, h_lights.data());
-  // (the host copies of the descriptors are re-classified by now: if the lists for a new build kind cannot be had, the set stays
-  // refused by render_impl until an update succeeds — its old lists are intact, but its frames no longer match them)
-  fs->update_failed = ensure_worklists(fs) != hipSuccess;
-  if (fs->update_failed) return fail(ctx, SRZ_E_NOMEM, "srz_sceneset_update: hipMalloc of the work lists failed");
-  // one asynchronous copy on the context's stream: ordered after every render already submitted there (which may still
-  // be reading the descriptors) and before the next one.  Renders submitted on OTHER streams are the caller's to order.
-  const unsigned slot = fs->stage_next++ % srz_frameset::STAGE_RING;
-  if (fs->stage_busy[slot]) HIP_TRY(ctx, hipEventSynchronize(fs->stage_ev[slot])); // its copy of 4 updates ago
-  uint8_t *st = fs->h_stage[slot];
-  std::memcpy(st, fs->h_frames.data(), sizeof(FrameDesc) * (size_t)n_frames);
-  if (!h_lights.empty()) std::memcpy(st + fs->dyn_lights_off, h_lights.data(), sizeof(srz_light) * h_lights.size());
-  if (!fs->h_draws.empty()) std::memcpy(st + fs->dyn_draws_off, fs->h_draws.data(), sizeof(DrawDesc) * fs->h_draws.size());
-  HIP_TRY(ctx, hipMemcpyAsync(fs->d_dyn, st, fs->dyn_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipEventRecord(fs->stage_ev[slot], ctx->stream));
-  fs->stage_busy[slot] = true;
-  if (batches_changed) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (rare: a draw switched shader or texture)
-    HIP_TRY(ctx, hipMemcpy(fs->d_batches, fs->h_batches.data(), sizeof(BatchDesc) * fs->h_batches.size(), hipMemcpyHostToDevice));
-    fs->sdesc_version = 0; // re-resolve batch → shader / texture at the next render
-  }
-  fs->have_stats = false;
-  return SRZ_OK;
+  for (int f = 0, di = 0; f < n_frames; ++f)
+    for (uint32_t k = 0; k < frames[f].n_draws; ++k) set_draw(fs->h_draws[di++], frames[f], frames[f].draws[k]);
+  std::vector<srz_frame> fr;
+  std::vector<srz_batch> batches;
+  scene_frames(ctx, frames, n_frames, fr, batches);
+  return refresh_frames(ctx, fs, fr.data(), n_frames, "srz_sceneset_update", /*copy_tris=*/false);
 }
 
 int srz_target_create(srz_ctx *ctx, int width, int height, srz_target **out) {
@@ -1300,8 +1298,6 @@ int srz_frameset_render_visibility(srz_ctx *ctx, srz_frameset *fs, void *d_out, 
   return render_entry("srz_frameset_render_visibility", ctx, fs, d_out, out_bytes, flags, stream, Pass::visibility());
 }
 
-static int refresh_frames(srz_ctx *ctx, srz_frameset *fs, const srz_frame *frames, int n_frames, hipStream_t s, const char *who, bool copy_tris);
-
 int srz_frameset_shade_visibility(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void *d_out, size_t out_bytes, uint32_t flags,
                                   void *stream) {
   if (!ctx) return SRZ_E_INVALID;
@@ -1312,9 +1308,7 @@ int srz_frameset_shade_visibility(srz_ctx *ctx, srz_frameset *fs, const void *d_
   if ((((uintptr_t)d_vis | (uintptr_t)d_out) & 15u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
   const uintptr_t v = (uintptr_t)d_vis, o = (uintptr_t)d_out;
   if (v != o && v < o + bytes && o < v + bytes) return fail(ctx, SRZ_E_INVALID, fn + ": visibility buffer and output overlap partly");
-  if (fs->shard_rank != ctx->shard_rank || fs->shard_world != ctx->shard_world)
-    return fail(ctx, SRZ_E_INVALID, "frameset was created under a different shard (call srz_set_shard before srz_frameset_create)");
-  if (fs->update_failed) return fail(ctx, SRZ_E_NOMEM, "the last update of this set failed (out of memory): update it again or destroy it");
+  if (int rc = check_renderable(ctx, fs)) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const hipStream_t s = pick_stream(ctx, stream);
   if (int rc = resolve_shading(ctx, fs, s)) return rc; // (textures uploaded, batch → shader / texture)
@@ -1326,11 +1320,11 @@ int srz_frameset_shade_visibility(srz_ctx *ctx, srz_frameset *fs, const void *d_
   a.frame_stride = 4ull * fs->local_rows * (uint64_t)fs->width;
   a.local_rows = fs->local_rows, a.tiles_x = fs->tiles_x, a.n_local_bands = fs->n_local_bands, a.n_frames = (uint32_t)fs->n_frames;
   a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
-  a.flags_or = flags & (SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER), a.in_place = v == o ? 1u : 0u;
+  a.flags_or = flags & FRAME_FLAGS, a.in_place = v == o ? 1u : 0u;
   a.any_generic = fs->any_generic ? 1u : 0u;
   a.redo_list = reinterpret_cast<uint32_t *>(fs->d_redo_list), a.redo_count = fs->d_slow_count + 1; // (k_shade's: a render zeroes them itself)
   HIP_TRY(ctx, hipMemsetAsync(a.redo_count, 0, sizeof(uint32_t), s));
-  launch_shade_vis(a, fs->fast_mask, fs->any_generic, fs->approx_shade, s);
+  launch_shade_vis(a, fs->fast_kinds, fs->any_generic, fs->approx_shade, s);
   // no sample of the side clear's grid measurement: while the set measures, its clock restarts here, so the next colour render times
   // only itself (as after a visibility render)
   const srz_frameset::ClearTune &ct = fs->clear_tune;
@@ -1345,7 +1339,7 @@ int srz_frameset_update_shading(srz_ctx *ctx, srz_frameset *fs, const srz_frame 
   if (fs->d_draws) return fail(ctx, SRZ_E_INVALID, "srz_frameset_update_shading: a sceneset (its shading changes with srz_sceneset_update)");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // (on the context's stream, like srz_sceneset_update: after every render already submitted there, before the next one)
-  return refresh_frames(ctx, fs, frames, n_frames, ctx->stream, "srz_frameset_update_shading", /*copy_tris=*/false);
+  return refresh_frames(ctx, fs, frames, n_frames, "srz_frameset_update_shading", /*copy_tris=*/false);
 }
 
 int srz_frameset_resolve8(srz_ctx *ctx, const srz_frameset *fs, const void *d_planes, void *d_bgr8, size_t bgr8_bytes, void *stream) {
@@ -1843,52 +1837,32 @@ int srz_sync(srz_ctx *ctx) {
   return SRZ_OK;
 }
 
-// Re-upload the shading data of a set made by srz_frameset_create (srz_draw's one-frame set: its triangles too, copy_tris): each frame's
-// eye, ka, ks, p, kh, kn, lights and flags, each batch's shader and texture.  The structure must be the set's (frame count, size, light
-// and batch counts, triangles per batch): else SRZ_E_INVALID and the set is unchanged.  Asynchronous on `s`.
-static int refresh_frames(srz_ctx *ctx, srz_frameset *fs, const srz_frame *frames, int n_frames, hipStream_t s, const char *who, bool copy_tris) {
-  const std::string fn(who);
-  if (n_frames != fs->n_frames) return fail(ctx, SRZ_E_INVALID, fn + ": frame count changed");
+// Re-upload the shading data of a set: each frame's eye, ka, ks, p, kh, kn, lights and flags, each batch's shader and texture (a sceneset's
+// draws too: srz_sceneset_update writes them first; srz_draw's one-frame set its triangles, copy_tris).  The structure must be the set's
+// (frame count, size, light and batch counts, triangles per batch): else SRZ_E_INVALID and the set is unchanged.  Asynchronous on the
+// context's stream.
+static int refresh_frames(srz_ctx *ctx, srz_frameset *fs, const srz_frame *frames, int n_frames, const char *who, bool copy_tris) {
+  auto bad = [&](int code, const char *what) { return fail(ctx, code, std::string(who) + ": " + what); };
+  if (n_frames != fs->n_frames) return bad(SRZ_E_INVALID, "frame count changed");
   for (int f = 0; f < n_frames; ++f) { // (everything is checked before anything changes)
     const srz_frame &fr = frames[f];
     const FrameDesc &d = fs->h_frames[f];
-    if (fr.width != fs->width || fr.height != fs->height) return fail(ctx, SRZ_E_INVALID, fn + ": frame size changed");
-    if (fr.n_lights != d.n_lights || (fr.n_lights && !fr.lights)) return fail(ctx, SRZ_E_INVALID, fn + ": light count changed");
-    if (fr.n_batches != d.n_batches || (fr.n_batches && !fr.batches)) return fail(ctx, SRZ_E_INVALID, fn + ": batch count changed");
+    if (fr.width != fs->width || fr.height != fs->height) return bad(SRZ_E_INVALID, "frame size changed");
+    if (fr.n_lights != d.n_lights || (fr.n_lights && !fr.lights)) return bad(SRZ_E_INVALID, "light count changed");
+    if (fr.n_batches != d.n_batches || (fr.n_batches && !fr.batches)) return bad(SRZ_E_INVALID, "batch count changed");
     for (uint32_t b = 0; b < fr.n_batches; ++b) {
       const srz_batch &sb = fr.batches[b];
-      if (sb.n_tris != fs->h_batches[d.batch_off + b].count) return fail(ctx, SRZ_E_INVALID, fn + ": triangle count of a batch changed");
-      if (sb.shader < SRZ_SHADER_NORMAL || sb.shader > SRZ_SHADER_BUMP) return fail(ctx, SRZ_E_INVALID, fn + ": unknown shader type");
-      if (copy_tris && sb.n_tris && !sb.tris) return fail(ctx, SRZ_E_INVALID, fn + ": batch with null triangle pointer");
+      if (sb.n_tris != fs->h_batches[d.batch_off + b].count) return bad(SRZ_E_INVALID, "triangle count of a batch changed");
+      if (sb.shader < SRZ_SHADER_NORMAL || sb.shader > SRZ_SHADER_BUMP) return bad(SRZ_E_INVALID, "unknown shader type");
+      if (copy_tris && sb.n_tris && !sb.tris) return bad(SRZ_E_INVALID, "batch with null triangle pointer");
     }
   }
-  // the upload goes through a pinned staging ring guarded by events, as srz_sceneset_update's: a set made by srz_frameset_create gets its
-  // ring at its first refresh (before anything changes: out of memory leaves the set as it was)
-  const size_t lights_off = (sizeof(FrameDesc) * (size_t)n_frames + 15u) & ~(size_t)15u;
-  const size_t batches_off = lights_off + ((sizeof(srz_light) * (size_t)fs->total_lights + 15u) & ~(size_t)15u);
-  const size_t stage_bytes = batches_off + sizeof(BatchDesc) * fs->h_batches.size();
-  if (!fs->h_stage[0]) {
-    for (int i = 0; i < srz_frameset::STAGE_RING; ++i) {
-      hipError_t e = hipHostMalloc((void **)&fs->h_stage[i], stage_bytes, hipHostMallocDefault);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&fs->stage_ev[i], hipEventDisableTiming);
-      if (e != hipSuccess) {
-        for (int j = 0; j <= i; ++j) {
-          if (fs->h_stage[j]) (void)hipHostFree(fs->h_stage[j]);
-          if (fs->stage_ev[j]) (void)hipEventDestroy(fs->stage_ev[j]);
-          fs->h_stage[j] = nullptr, fs->stage_ev[j] = nullptr;
-        }
-        return fail(ctx, e == hipErrorOutOfMemory ? SRZ_E_NOMEM : SRZ_E_NODEVICE, fn + ": staging buffers: " + hipGetErrorString(e));
-      }
-    }
-  }
-  fs->h_lights.resize((size_t)fs->total_lights);
+  if (int rc = ensure_stage_ring(ctx, fs, who)) return rc;
   bool batches_changed = false;
   for (int f = 0; f < n_frames; ++f) {
     const srz_frame &fr = frames[f];
     FrameDesc &d = fs->h_frames[f];
-    std::memcpy(d.eye, fr.eye, sizeof d.eye), std::memcpy(d.ka, fr.ka, sizeof d.ka), std::memcpy(d.ks, fr.ks, sizeof d.ks);
-    d.p = fr.p, d.kh = fr.kh, d.kn = fr.kn;
-    d.flags = fr.flags & (SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER);
+    set_shading(d, fr);
     if (fr.n_lights) std::memcpy(&fs->h_lights[d.light_off], fr.lights, sizeof(srz_light) * fr.n_lights);
     for (uint32_t b = 0; b < fr.n_batches; ++b) {
       BatchDesc &bd = fs->h_batches[d.batch_off + b];
@@ -1896,31 +1870,19 @@ static int refresh_frames(srz_ctx *ctx, srz_frameset *fs, const srz_frame *frame
         bd.shader = fr.batches[b].shader, bd.tex_id = fr.batches[b].tex_id, batches_changed = true;
     }
   }
-  classify_frames(fs, fs->h_lights.data());
-  fs->update_failed = ensure_worklists(fs) != hipSuccess; // (see srz_sceneset_update)
-  if (fs->update_failed) return fail(ctx, SRZ_E_NOMEM, fn + ": hipMalloc of the work lists failed");
-  // (frames, lights and batches live in three device allocations here, not in one block as a sceneset's: three copies from one slot)
-  const unsigned slot = fs->stage_next++ % srz_frameset::STAGE_RING;
-  if (fs->stage_busy[slot]) HIP_TRY(ctx, hipEventSynchronize(fs->stage_ev[slot])); // its copies of 4 updates ago
-  uint8_t *st = fs->h_stage[slot];
-  std::memcpy(st, fs->h_frames.data(), sizeof(FrameDesc) * (size_t)n_frames);
-  if (!fs->h_lights.empty()) std::memcpy(st + lights_off, fs->h_lights.data(), sizeof(srz_light) * fs->h_lights.size());
-  if (batches_changed) std::memcpy(st + batches_off, fs->h_batches.data(), sizeof(BatchDesc) * fs->h_batches.size());
-  HIP_TRY(ctx, hipMemcpyAsync(fs->d_frames, st, sizeof(FrameDesc) * (size_t)n_frames, hipMemcpyHostToDevice, s));
-  if (!fs->h_lights.empty())
-    HIP_TRY(ctx, hipMemcpyAsync(fs->d_lights, st + lights_off, sizeof(srz_light) * fs->h_lights.size(), hipMemcpyHostToDevice, s));
-  if (batches_changed) {
-    HIP_TRY(ctx, hipMemcpyAsync(fs->d_batches, st + batches_off, sizeof(BatchDesc) * fs->h_batches.size(), hipMemcpyHostToDevice, s));
-    fs->sdesc_version = 0; // re-resolve batch → shader / texture at the next render or shade
-  }
-  HIP_TRY(ctx, hipEventRecord(fs->stage_ev[slot], s));
-  fs->stage_busy[slot] = true;
+  classify_frames(fs);
+  // (the host copies of the descriptors are re-classified by now: if the lists for a new build kind cannot be had, the set stays
+  // refused by render_impl until an update succeeds — its old lists are intact, but its frames no longer match them)
+  fs->update_failed = ensure_worklists(fs) != hipSuccess;
+  if (fs->update_failed) return bad(SRZ_E_NOMEM, "hipMalloc of the work lists failed");
+  if (int rc = upload_dyn(ctx, fs)) return rc;
+  if (batches_changed) fs->sdesc_version = 0; // re-resolve batch → shader / texture at the next render or shade
   if (copy_tris) {
     for (int f = 0; f < n_frames; ++f) {
       size_t o = fs->h_frames[f].tri_off;
       for (uint32_t b = 0; b < frames[f].n_batches; ++b) {
         const srz_batch &sb = frames[f].batches[b];
-        if (sb.n_tris) HIP_TRY(ctx, hipMemcpyAsync(fs->d_tris + o, sb.tris, sizeof(srz_tri) * sb.n_tris, hipMemcpyHostToDevice, s));
+        if (sb.n_tris) HIP_TRY(ctx, hipMemcpyAsync(fs->d_tris + o, sb.tris, sizeof(srz_tri) * sb.n_tris, hipMemcpyHostToDevice, ctx->stream));
         o += sb.n_tris;
       }
     }
@@ -1953,7 +1915,7 @@ static int draw_impl(srz_ctx *ctx, int primitive, const srz_frame *frame, const 
   bool reuse = ctx->draw_fs && sig == ctx->draw_sig;
   if (reuse) {
     ctx->draw_fs->approx_shade = ctx->opt_approx_shade; // (the ctx's own one-frame set follows the option call by call)
-    rc = frame ? refresh_frames(ctx, ctx->draw_fs, frame, 1, s, "srz_draw", /*copy_tris=*/true) : srz_sceneset_update(ctx, ctx->draw_fs, scene, 1);
+    rc = frame ? refresh_frames(ctx, ctx->draw_fs, frame, 1, "srz_draw", /*copy_tris=*/true) : srz_sceneset_update(ctx, ctx->draw_fs, scene, 1);
     if (rc != SRZ_OK && !frame) reuse = false, rc = SRZ_OK; // (a scene whose mesh bindings changed: rebuild)
     if (rc != SRZ_OK) return rc;
   }

@@ -52,6 +52,17 @@ constexpr uint32_t FD_GREY = 0x8000u;                    // ka, ks and every lig
 constexpr uint32_t FD_GENPOW = 0x2000u;                  // a non-integer exponent in (0, 4096]: FAST builds whose power is pow_fast (exp2(p log2 x) in binary64 with a rounding-safety flag)
 constexpr uint32_t SHADE_KIND_GENERIC = 12;              // k_shade builds: kinds 0..3 = FAST for 1..4 lights, 4..7 = the same + BUMPY,
                                                          // 8..11 = FAST for 1..4 lights with any exponent (GENPOW), 12 = generic
+// the build kind that shades a frame of these flags (FrameDesc::flags, as classify_frames in srz_api.hip sets them)
+__host__ __device__ constexpr uint32_t frame_kind(uint32_t flags) {
+  return (flags & FD_FAST_SHADE) ? ((flags >> FD_NL_SHIFT) & 7u) - 1u + ((flags & FD_BUMPY) ? 4u : 0u) + ((flags & FD_GENPOW) ? 8u : 0u)
+                                 : SHADE_KIND_GENERIC;
+}
+// the kind a <FASTNL, BUMPY> build of k_shade / k_shade_vis serves (FASTNL: 1..4 lights, -1..-4 the same with GENPOW, 0 generic)
+template <int FASTNL, bool BUMPY> constexpr uint32_t build_kind() {
+  return frame_kind(FASTNL == 0 ? 0u
+                                : FD_FAST_SHADE | (uint32_t)(FASTNL < 0 ? -FASTNL : FASTNL) << FD_NL_SHIFT | (BUMPY ? FD_BUMPY : 0u) |
+                                      (FASTNL < 0 ? FD_GENPOW : 0u));
+}
 constexpr uint32_t N_WORK_LISTS = 8 * (SHADE_KIND_GENERIC + 1);
 constexpr uint32_t UNLISTED = 0xffffffffu; // tile_off of a tile whose list did not fit the record pool
 // Binning is O(triangles): k_setup / k_chunks sort every GROUP of GROUP_TRIS (512) consecutive triangles by the 32-row bands their
@@ -111,21 +122,11 @@ struct FrameDesc {
   float p, kh, kn;
   uint32_t n_lights, light_off;  // into lights[]
   uint32_t n_tris, tri_off;      // into tris[] / bbox[] / tri_batch[]
-  uint32_t n_batches, batch_off; // into batches[]
+  uint32_t n_batches, batch_off; // into sdesc[]
   uint32_t flags;
   uint32_t n_local_bands;        // bands of this frame owned by this ctx
   uint32_t chunk_off;            // into chunk_rows[]: first 64-triangle chunk of this frame
   uint32_t group_off;            // into band_desc[] / band_ent[]: first group (GROUP_TRIS triangles) of this frame
-};
-
-struct BatchDesc {
-  int32_t shader, tex_id;
-  uint32_t first, count; // triangle range inside the frame
-};
-
-struct TexDesc {
-  const uint32_t *bgrx; // one dword per texel: B | G<<8 | R<<16
-  int32_t w, h;
 };
 
 // counters accumulated by the STATS kernel variants (same order as srz_stats)
@@ -142,10 +143,8 @@ struct RenderArgs {
   uint32_t *band_desc;           // [group][n_local_bands]: first entry << 16 | entries of the group in that band, or DESC_RAW
   uint2 *band_ent;               // [group][ENT_PER_GROUP]: {triangle index in the frame, first tile x | last tile x << 16}
   const uint16_t *tri_batch;
-  const BatchDesc *batches;
   const srz_light *lights;
-  const TexDesc *tex;
-  const ShadeDescG *sdesc;       // per batch (indexed like batches[])
+  const ShadeDescG *sdesc;       // per batch of the set, in frame order (FrameDesc::batch_off)
   // per-tile triangle lists, UNORDERED (the rasteriser's result does not depend on list order): triangle indices in a pool
   // of n_sub equal sub-pools with one bump allocator each; a (frame, band) workgroup of k_bin takes its band's entries
   // from sub-pool (workgroup id & sub_mask) in one allocation.  A band that does not fit is left UNLISTED: its tiles are
@@ -179,7 +178,6 @@ struct RenderArgs {
   int32_t shard_rank, shard_world;
   uint32_t flags_or;      // OR-ed into every frame's flags (SRZ_FUSED_CLEAR / SRZ_UNIFIED)
   unsigned long long *stats;
-  unsigned long long *timeline; // diagnostic (STATS variant only): per tile {start, end (wall clock 100 MHz), hw_id, blocks}
   const uint32_t *clear_wgs_dev; // k_clear: workgroups that take part, read on the device (ClearCtl::wgs; 0 = the first candidate); null: the whole grid
 };
 
@@ -214,7 +212,8 @@ void launch_bin(const RenderArgs &a, int n_frames, uint32_t max_tris, hipStream_
 void launch_raster(const RenderArgs &a, int n_frames, bool stats, hipStream_t s);
 bool raster_four_waves(const RenderArgs &a); // the latency build of k_raster serves this job (it also reports the pool's demand)
 void launch_clear(const RenderArgs &a, uint32_t max_tiles, hipStream_t s, uint32_t wgs);
-void launch_shade(const RenderArgs &a, uint32_t max_tiles, bool stats, uint32_t fast_mask, bool any_generic, bool approx, hipStream_t s);
+// kinds: bit k = some frame is shaded by FAST build kind k (frame_kind); approx: the tolerance mode's builds serve kinds 0..3
+void launch_shade(const RenderArgs &a, uint32_t max_tiles, bool stats, uint32_t kinds, bool any_generic, bool approx, hipStream_t s);
 // the visibility buffer (srz_frameset_render_visibility) in place of launch_shade: planes 1..3 of every owned tile
 void launch_visibility(const RenderArgs &a, uint32_t max_tiles, hipStream_t s);
 // srz_frameset_shade_visibility: the colour of a visibility buffer (k_shade_vis).  Everything a pixel's shading reads of the set, and the
@@ -235,8 +234,8 @@ struct ShadeVisArgs {
   uint32_t *redo_list;   // tiles (frame * tiles per frame + tile) the FAST builds hand to the generic one
   uint32_t *redo_count;  // (zero at launch_shade_vis)
 };
-// one launch per build kind the set's frames need (fast_mask / any_generic / approx as for launch_shade); frames of other kinds are skipped
-void launch_shade_vis(const ShadeVisArgs &a, uint32_t fast_mask, bool any_generic, bool approx, hipStream_t s);
+// one launch per build kind the set's frames need (kinds / any_generic / approx as for launch_shade); frames of other kinds are skipped
+void launch_shade_vis(const ShadeVisArgs &a, uint32_t kinds, bool any_generic, bool approx, hipStream_t s);
 void launch_resolve8(const float *planes, uint8_t *out, uint32_t n_frames, uint32_t rows, uint32_t W, uint64_t frame_stride,
                      hipStream_t s);
 void launch_deinterleave(const void *gathered, void *full, uint32_t world, uint32_t n_fp, uint32_t bands_per_rank, uint32_t row_bytes,

@@ -1322,9 +1322,7 @@ template <class A> __device__ __forceinline__ uint32_t work_slot(A &a, uint32_t 
 }
 __device__ __forceinline__ void work_append(const RenderArgs &a, uint32_t frame_flags, uint32_t entry /* frame * tiles + tile */, const uint4 &w) {
   // (fewer than 8 frames: the tiles are dealt over the 8 lists instead, so that every XCD has work)
-  const uint32_t kind = (!a.force_generic && (frame_flags & FD_FAST_SHADE) != 0u)
-                            ? ((frame_flags >> FD_NL_SHIFT) & 7u) - 1u + ((frame_flags & FD_BUMPY) ? 4u : 0u) + ((frame_flags & FD_GENPOW) ? 8u : 0u)
-                            : SHADE_KIND_GENERIC;
+  const uint32_t kind = a.force_generic ? SHADE_KIND_GENERIC : frame_kind(frame_flags);
   const uint32_t sub = (a.n_frames >= 8u ? w.x : w.x + entry) & 7u;
   a.worklist[(size_t)work_slot(a, kind, sub) * a.work_cap + atomicAdd(&a.work_count[(kind * 8u + sub) * CNT_STRIDE], 1u)] = w;
 }
@@ -2687,7 +2685,7 @@ void k_shade(RenderArgs a) {
   // frames of 1024^2: a persistent grid of 4096 workgroups dealing every 128th tile of a frame 0.78 ms (one stream), a
   // persistent grid drawing tiles from atomic cursors the same on one stream but 7 % slower on two (it holds every CU slot to
   // its end), this walk 0.73 ms.
-  constexpr uint32_t KIND = FAST ? (uint32_t)(light_count<FASTNL>() - 1) + (BUMPY ? 4u : 0u) + (GENPOW ? 8u : 0u) : SHADE_KIND_GENERIC;
+  constexpr uint32_t KIND = build_kind<FASTNL, BUMPY>();
   const uint32_t L = KIND * 8u + (blockIdx.x & 7u), Ls = ((uint32_t)(a.kind_slots >> (4u * KIND)) & 15u) * 8u + (blockIdx.x & 7u);
   const SRZ_CAS u32x4 *list = reinterpret_cast<const SRZ_CAS u32x4 *>(as_const(a.worklist)) + (size_t)Ls * a.work_cap;
   // the list's length and this workgroup's first entry are loaded TOGETHER (the entry's index is clamped into the list's
@@ -2852,10 +2850,10 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
 // (4 waves per SIMD: 128 VGPRs; the four-light pow_fast build needs more — held to 128 it spills 136 bytes — and gets 3)
 template <int FASTNL, bool BUMPY = false, bool APPROX = false>
 __global__ __launch_bounds__(256, FASTNL == -4 ? 3 : SRZ_SHADE_MINW) void k_shade_vis(ShadeVisArgs a) {
-  constexpr bool FAST = FASTNL != 0, GENPOW = FASTNL < 0;
+  constexpr bool FAST = FASTNL != 0;
   static_assert(FAST || !BUMPY, "BUMPY is a property of the FAST builds");
   static_assert(!APPROX || (FASTNL > 0 && !BUMPY), "the tolerance mode has FAST builds for 1..4 lights only");
-  constexpr uint32_t KIND = FAST ? (uint32_t)(light_count<FASTNL>() - 1) + (BUMPY ? 4u : 0u) + (GENPOW ? 8u : 0u) : SHADE_KIND_GENERIC;
+  constexpr uint32_t KIND = build_kind<FASTNL, BUMPY>();
   __shared__ __attribute__((aligned(16))) float s_in[3][TILE * TILE]; // z, α, β by pixel
   __shared__ __attribute__((aligned(16))) float s_c[3][TILE * TILE];  // colour by pixel
   __shared__ uint32_t s_idx[PIX_SLOT];                                // compacted owned pixels: owner's index in the frame
@@ -3111,10 +3109,7 @@ __global__ __launch_bounds__(256, FASTNL == -4 ? 3 : SRZ_SHADE_MINW) void k_shad
       if (i >= n_items) break;
       f = i / tpf, t = i % tpf;
     }
-    const uint32_t ff = as_const(a.frames)[f].flags;
-    const uint32_t kind = (ff & FD_FAST_SHADE) ? ((ff >> FD_NL_SHIFT) & 7u) - 1u + ((ff & FD_BUMPY) ? 4u : 0u) + ((ff & FD_GENPOW) ? 8u : 0u)
-                                               : SHADE_KIND_GENERIC;
-    if (kind != KIND) continue; // (workgroup-uniform: another launch's frame)
+    if (frame_kind(as_const(a.frames)[f].flags) != KIND) continue; // (workgroup-uniform: another launch's frame)
     shade_tile(f, t, std::integral_constant<int, FAST ? 0 : 1>{});
   }
   if constexpr (!FAST) { // the tiles the FAST builds handed back (they ran before this kernel on the same stream)
@@ -3645,35 +3640,33 @@ static dim3 shade_grid(const RenderArgs &a, uint32_t max_tiles) {
   return dim3((std::min(max_tiles, a.other_streams ? 2048u : 16384u) + 7u) & ~7u);
 }
 
-void launch_shade(const RenderArgs &a, uint32_t max_tiles, bool stats, uint32_t fast_mask, bool any_generic, bool approx, hipStream_t s) {
+// One launch per FAST build kind of `kinds`, in ascending kind order: launch(FASTNL, BUMPY, APPROX) gets each as std::integral_constants.
+// The tolerance mode (approx) has builds for kinds 0..3 only: classify_frames sends it no frame of another FAST kind.
+template <int FASTNL, bool BUMPY, class L> static void launch_kind(uint32_t kinds, bool approx, L &launch) {
+  if (!((kinds >> build_kind<FASTNL, BUMPY>()) & 1u)) return;
+  if constexpr (FASTNL > 0 && !BUMPY)
+    if (approx) return launch(std::integral_constant<int, FASTNL>{}, std::false_type{}, std::true_type{});
+  launch(std::integral_constant<int, FASTNL>{}, std::bool_constant<BUMPY>{}, std::false_type{});
+}
+template <class L> static void launch_fast_kinds(uint32_t kinds, bool approx, L &&launch) {
+  launch_kind<1, false>(kinds, approx, launch), launch_kind<2, false>(kinds, approx, launch);
+  launch_kind<3, false>(kinds, approx, launch), launch_kind<4, false>(kinds, approx, launch);
+  launch_kind<1, true>(kinds, approx, launch), launch_kind<2, true>(kinds, approx, launch);
+  launch_kind<3, true>(kinds, approx, launch), launch_kind<4, true>(kinds, approx, launch);
+  launch_kind<-1, false>(kinds, approx, launch), launch_kind<-2, false>(kinds, approx, launch);
+  launch_kind<-3, false>(kinds, approx, launch), launch_kind<-4, false>(kinds, approx, launch);
+}
+
+void launch_shade(const RenderArgs &a, uint32_t max_tiles, bool stats, uint32_t kinds, bool any_generic, bool approx, hipStream_t s) {
   if (max_tiles == 0) return;
   const dim3 grid = shade_grid(a, max_tiles);
   if (stats) { // (counting runs shade every frame with the generic build: force_generic)
     hipLaunchKernelGGL((k_shade<true, 0>), grid, dim3(256), 0, s, a);
     return;
   }
-  // one FAST build per (light count, with / without BUMP or DISPLACEMENT batches) some frame of the set has:
-  // fast_mask bit NL = plain, bit 8 + NL = with them
-  if (approx) { // the tolerance mode's builds (classify_frames sets only the plain bits for the frames they shade)
-    if (fast_mask & 2u) hipLaunchKernelGGL((k_shade<false, 1, false, true>), grid, dim3(256), 0, s, a);
-    if (fast_mask & 4u) hipLaunchKernelGGL((k_shade<false, 2, false, true>), grid, dim3(256), 0, s, a);
-    if (fast_mask & 8u) hipLaunchKernelGGL((k_shade<false, 3, false, true>), grid, dim3(256), 0, s, a);
-    if (fast_mask & 16u) hipLaunchKernelGGL((k_shade<false, 4, false, true>), grid, dim3(256), 0, s, a);
-    fast_mask = 0;
-  }
-  if (fast_mask & 2u) hipLaunchKernelGGL((k_shade<false, 1, false>), grid, dim3(256), 0, s, a);
-  if (fast_mask & 4u) hipLaunchKernelGGL((k_shade<false, 2, false>), grid, dim3(256), 0, s, a);
-  if (fast_mask & 8u) hipLaunchKernelGGL((k_shade<false, 3, false>), grid, dim3(256), 0, s, a);
-  if (fast_mask & 16u) hipLaunchKernelGGL((k_shade<false, 4, false>), grid, dim3(256), 0, s, a);
-  if (fast_mask & 0x200u) hipLaunchKernelGGL((k_shade<false, 1, true>), grid, dim3(256), 0, s, a);
-  if (fast_mask & 0x400u) hipLaunchKernelGGL((k_shade<false, 2, true>), grid, dim3(256), 0, s, a);
-  if (fast_mask & 0x800u) hipLaunchKernelGGL((k_shade<false, 3, true>), grid, dim3(256), 0, s, a);
-  if (fast_mask & 0x1000u) hipLaunchKernelGGL((k_shade<false, 4, true>), grid, dim3(256), 0, s, a);
-  // ... and per light count with a non-integer exponent: bit 16 + NL
-  if (fast_mask & 0x20000u) hipLaunchKernelGGL((k_shade<false, -1, false>), grid, dim3(256), 0, s, a);
-  if (fast_mask & 0x40000u) hipLaunchKernelGGL((k_shade<false, -2, false>), grid, dim3(256), 0, s, a);
-  if (fast_mask & 0x80000u) hipLaunchKernelGGL((k_shade<false, -3, false>), grid, dim3(256), 0, s, a);
-  if (fast_mask & 0x100000u) hipLaunchKernelGGL((k_shade<false, -4, false>), grid, dim3(256), 0, s, a);
+  launch_fast_kinds(kinds, approx, [&](auto nl, auto bumpy, auto ap) {
+    hipLaunchKernelGGL((k_shade<false, decltype(nl)::value, decltype(bumpy)::value, decltype(ap)::value>), grid, dim3(256), 0, s, a);
+  });
   // the generic build also serves the tiles the FAST builds hand back: when no frame is generic that is normally
   // nothing, and a small grid does
   dim3 ggrid(any_generic ? grid.x : (grid.x < 128u ? grid.x : 128u));
@@ -3685,31 +3678,15 @@ void launch_visibility(const RenderArgs &a, uint32_t max_tiles, hipStream_t s) {
   hipLaunchKernelGGL(k_visibility, shade_grid(a, max_tiles), dim3(256), 0, s, a);
 }
 
-void launch_shade_vis(const ShadeVisArgs &a, uint32_t fast_mask, bool any_generic, bool approx, hipStream_t s) {
+void launch_shade_vis(const ShadeVisArgs &a, uint32_t kinds, bool any_generic, bool approx, hipStream_t s) {
   const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
   if (items == 0) return;
   const dim3 grid((std::min(items, 16384u) + 7u) & ~7u), blk(256); // (a multiple of 8: workgroup b serves the frames f ≡ b mod 8)
-  if (approx) { // (classify_frames sets only the plain bits for the frames the tolerance builds shade)
-    if (fast_mask & 2u) hipLaunchKernelGGL((k_shade_vis<1, false, true>), grid, blk, 0, s, a);
-    if (fast_mask & 4u) hipLaunchKernelGGL((k_shade_vis<2, false, true>), grid, blk, 0, s, a);
-    if (fast_mask & 8u) hipLaunchKernelGGL((k_shade_vis<3, false, true>), grid, blk, 0, s, a);
-    if (fast_mask & 16u) hipLaunchKernelGGL((k_shade_vis<4, false, true>), grid, blk, 0, s, a);
-    fast_mask = 0;
-  }
-  if (fast_mask & 2u) hipLaunchKernelGGL((k_shade_vis<1, false>), grid, blk, 0, s, a);
-  if (fast_mask & 4u) hipLaunchKernelGGL((k_shade_vis<2, false>), grid, blk, 0, s, a);
-  if (fast_mask & 8u) hipLaunchKernelGGL((k_shade_vis<3, false>), grid, blk, 0, s, a);
-  if (fast_mask & 16u) hipLaunchKernelGGL((k_shade_vis<4, false>), grid, blk, 0, s, a);
-  if (fast_mask & 0x200u) hipLaunchKernelGGL((k_shade_vis<1, true>), grid, blk, 0, s, a);
-  if (fast_mask & 0x400u) hipLaunchKernelGGL((k_shade_vis<2, true>), grid, blk, 0, s, a);
-  if (fast_mask & 0x800u) hipLaunchKernelGGL((k_shade_vis<3, true>), grid, blk, 0, s, a);
-  if (fast_mask & 0x1000u) hipLaunchKernelGGL((k_shade_vis<4, true>), grid, blk, 0, s, a);
-  if (fast_mask & 0x20000u) hipLaunchKernelGGL((k_shade_vis<-1, false>), grid, blk, 0, s, a);
-  if (fast_mask & 0x40000u) hipLaunchKernelGGL((k_shade_vis<-2, false>), grid, blk, 0, s, a);
-  if (fast_mask & 0x80000u) hipLaunchKernelGGL((k_shade_vis<-3, false>), grid, blk, 0, s, a);
-  if (fast_mask & 0x100000u) hipLaunchKernelGGL((k_shade_vis<-4, false>), grid, blk, 0, s, a);
-  // the generic build also serves the tiles the FAST builds hand back (redo_count: zeroed by the caller)
-  if (any_generic || fast_mask) hipLaunchKernelGGL((k_shade_vis<0>), any_generic ? grid : dim3(std::min(grid.x, 128u)), blk, 0, s, a);
+  launch_fast_kinds(kinds, approx, [&](auto nl, auto bumpy, auto ap) {
+    hipLaunchKernelGGL((k_shade_vis<decltype(nl)::value, decltype(bumpy)::value, decltype(ap)::value>), grid, blk, 0, s, a);
+  });
+  // the generic build also serves the tiles the exact FAST builds hand back (redo_count: zeroed by the caller)
+  if (any_generic || (kinds && !approx)) hipLaunchKernelGGL((k_shade_vis<0>), any_generic ? grid : dim3(std::min(grid.x, 128u)), blk, 0, s, a);
 }
 
 bool raster_four_waves(const RenderArgs &a) { return a.n_frames * a.n_local_bands * a.tiles_x <= 4096u; }
