@@ -48,6 +48,7 @@ extern "C" {
  *      (additive, same version) the visibility buffer srz_frameset_render_visibility
  *      (additive, same version) shading a visibility buffer srz_frameset_shade_visibility, new shading data for a frameset
  *      srz_frameset_update_shading
+ *      (additive, same version) the diagnostic srz_frameset_shade_kinds
  */
 #define SRZ_ABI_VERSION 7
 
@@ -444,6 +445,11 @@ int srz_verify_fastlen(srz_ctx *ctx, uint64_t *out5);
  * shading builds handed to the generic build, capacity of a tile-list sub-pool, largest demand a sub-pool reported, workgroups of the
  * side-stream clear (a batch-sized set measures them on the device within its first 24 renders, and again every 4096), 1 once that measurement has been taken }; waits for the device */
 int srz_frameset_debug_counters(srz_ctx *ctx, srz_frameset *fs, uint32_t *out6);
+/* diagnostic only (tests): which builds of the shading kernels the set's next colour render or shade launches — out2 = { mask: bit k =
+ * some frame is shaded by FAST build kind k (0..3: 1..4 lights with an integer exponent 0..256; 4..7: the same with a BUMP /
+ * DISPLACEMENT batch; 8..11: 1..4 lights with a non-integer exponent in (0, 4096]), 1 if some frame takes the generic build };
+ * host state only, launches nothing, does not wait */
+int srz_frameset_shade_kinds(srz_ctx *ctx, srz_frameset *fs, uint32_t *out2);
 /* diagnostic only: raw device counters of the last stats run (layout = csrc/srz_device.h ST_*); returns their count */
 int srz_debug_counters(srz_ctx *ctx, uint64_t *out, int n);
 

@@ -1484,6 +1484,14 @@ int srz_frameset_debug_counters(srz_ctx *ctx, srz_frameset *fs, uint32_t *out6) 
   return SRZ_OK;
 }
 
+/* diagnostic (tests): which shading builds the set's next colour render or shade launches — out2 = { fast_kinds (bit k: some frame
+ * is shaded by the FAST build of kind k, frame_kind), 1 if some frame takes the generic build }.  Host state only: launches nothing. */
+int srz_frameset_shade_kinds(srz_ctx *ctx, srz_frameset *fs, uint32_t *out2) {
+  if (!ctx || !fs || !out2) return ctx ? fail(ctx, SRZ_E_INVALID, "srz_frameset_shade_kinds: null argument") : SRZ_E_INVALID;
+  out2[0] = fs->fast_kinds, out2[1] = fs->any_generic ? 1u : 0u;
+  return SRZ_OK;
+}
+
 int srz_verify_fastlen(srz_ctx *ctx, uint64_t *out5) {
   if (!ctx || !out5) return SRZ_E_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));

@@ -23,7 +23,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_deinterleave", "srz_frameset_allgather_inplace", "srz_frameset_gathered_row_offset",
            "srz_frameset_read_gathered_frame", "srz_frameset_sparse_capacity", "srz_frameset_sparse_pack", "srz_frameset_sparse_unpack",
            "srz_frameset_allgather_sparse", "srz_frameset_render_visibility", "srz_frameset_shade_visibility",
-           "srz_frameset_update_shading"]
+           "srz_frameset_update_shading", "srz_frameset_shade_kinds"]
 
 
 class SrzError(RuntimeError):
@@ -87,6 +87,7 @@ def lib():
         L.srz_host_register.argtypes = [vp, C.c_void_p, C.c_size_t]
         L.srz_host_unregister.argtypes = [vp, C.c_void_p]
         L.srz_frameset_debug_counters.argtypes = [vp, vp, C.POINTER(C.c_uint32)]
+        L.srz_frameset_shade_kinds.argtypes = [vp, vp, C.POINTER(C.c_uint32)]
         L.srz_comm_unique_id.argtypes = [vp]
         L.srz_comm_create.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]
         L.srz_comm_destroy.argtypes = [vp, vp]
@@ -174,6 +175,13 @@ class FrameSet:
         out = (C.c_uint32 * 6)()
         self.ctx._check(lib().srz_frameset_debug_counters(self.ctx.h, self.h, out))
         return dict(zip(("slow_tiles", "redo_tiles", "pool_sub_cap", "pool_demand", "clear_wgs", "clear_tuned"), (int(x) for x in out)))
+
+    def shade_kinds(self):
+        """(tests) (mask, any_generic): bit k of mask = some frame is shaded by FAST build kind k at the next render / shade,
+        any_generic = some frame takes the generic build (srz_frameset_shade_kinds); launches nothing"""
+        out = (C.c_uint32 * 2)()
+        self.ctx._check(lib().srz_frameset_shade_kinds(self.ctx.h, self.h, out))
+        return int(out[0]), bool(out[1])
 
     def exchange_bytes(self, what=abi.EXCHANGE_PLANES):
         return int(lib().srz_frameset_exchange_bytes(self.ctx.h, self.h, what))

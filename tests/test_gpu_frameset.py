@@ -367,30 +367,46 @@ def test_lane_renderer_equals_one_frameset_and_timing_samples():
 
 @pytest.mark.parametrize("n_frames", [3, 8, 19])
 def test_mixed_fast_and_generic_frames_share_one_set(orc, n_frames):
-    """k_shade's two builds take their tiles from different work lists of the same render: frames the FAST build may shade
-    (2 lights, p = 150, NORMAL / TEXTURE / PHONG) interleaved with frames only the generic one can (3 lights, another
-    exponent, an empty frame), at frame counts below, at and above the 8 lists' period — every frame bit-identical to the
-    oracle's"""
+    """k_shade's builds take their tiles from different work lists of the same render.  The n_frames frames of the first pattern are
+    all FAST by now (2 lights with p = 150 or p = 8: kind 1; 3 lights: kind 2; the empty frame counts as kind 1 too — they were
+    "generic" before the per-light-count and integer-chain builds existed).  Each of them is followed by a frame that only the
+    generic build can shade (5 lights, or p = 5000), and a GENPOW frame (2 lights, p = 7.5: kind 9) closes the row, so FAST and
+    generic frames alternate through 2 n + 1 = 7, 17 and 39 frames: below the 8 lists' period and above it with partly filled
+    lists.  shade_kinds() proves the mix; every frame is bit-identical to the oracle's"""
     import srz
     ctx = srz.Context(0)
     ctx.texture_upload(scenes.TEX_SPOT, scenes.spot_texture())
     three = np.concatenate([scenes.LIGHTS, np.array([[[-0.7, 0.2, 0.8], [30, 40, 50]]], np.float32)])
+    five = np.concatenate([three, np.array([[[0.3, -0.8, 0.7], [7, 7, 7]], [[0.1, 0.1, 1.5], [2, 3, 4]]], np.float32)])
     frames = []
     for i in range(n_frames):
         base = scenes.config2(i, size=256, shader=(abi.SHADER_TEXTURE, abi.SHADER_PHONG, abi.SHADER_NORMAL)[i % 3])
         tris = base.tris[0]
-        if i % 4 == 1:      # generic: three lights
+        if i % 4 == 1:      # three lights (FAST kind 2)
             frames.append(abi.Frame(256, 256, scenes.EYE, three, [(abi.SHADER_TEXTURE, scenes.TEX_SPOT, tris)], abi.FUSED_CLEAR))
-        elif i % 4 == 3:    # generic: another exponent
+        elif i % 4 == 3:    # another integer exponent (FAST kind 1, the scalar loop)
             frames.append(abi.Frame(256, 256, scenes.EYE, scenes.LIGHTS, [(abi.SHADER_PHONG, -1, tris)], abi.FUSED_CLEAR, p=8.0))
         elif i == 4:        # nothing to draw: every tile is the fused clear's
             frames.append(abi.Frame(256, 256, scenes.EYE, scenes.LIGHTS, [(abi.SHADER_NORMAL, -1, tris[:0])], abi.FUSED_CLEAR))
         else:
             frames.append(base)
+        # a frame no FAST build takes: five lights, or an exponent outside both fast domains
+        gtris = scenes.config2(i + 18, size=256).tris[0]
+        if i % 2 == 0:
+            frames.append(abi.Frame(256, 256, scenes.EYE, five, [(abi.SHADER_TEXTURE, scenes.TEX_SPOT, gtris)], abi.FUSED_CLEAR))
+        else:
+            frames.append(abi.Frame(256, 256, scenes.EYE, scenes.LIGHTS, [(abi.SHADER_PHONG, -1, gtris)], abi.FUSED_CLEAR, p=5000.0))
+    frames.append(abi.Frame(256, 256, scenes.EYE, scenes.LIGHTS, [(abi.SHADER_PHONG, -1, scenes.config2(17, size=256).tris[0])],
+                            abi.FUSED_CLEAR, p=7.5))
+    assert len(frames) == 2 * n_frames + 1
     fs, out = render(ctx, frames)
+    mask, any_generic = fs.shade_kinds()
+    assert any_generic and bin(mask).count("1") >= 3, (hex(mask), any_generic)
+    assert mask == (1 << 1 | 1 << 2 | 1 << 9), hex(mask)  # (2 lights integer p, 3 lights integer p, 2 lights GENPOW)
     got = out.cpu().numpy()
     for i, f in enumerate(frames):
         rc, ref, st = orc.draw(f)
+        assert rc == 0
         for p in range(4):
             assert np.array_equal(bits(got[i, p]), bits(ref[p])), (n_frames, i, p)
     fs.close()
