@@ -1,0 +1,374 @@
+"""What the tests share, each thing once: the frame builders (inputs, numpy only), the comparisons with their stated bounds, the
+oracle-vs-GPU steps and the context fixtures.  A plain module like tests/scenes.py: importable without a GPU and without pytest
+running (tools/fuzz_probe.py imports it as a script); torch and srz are imported by the functions that need them.  Test modules
+import from here and from scenes, never from one another."""
+import functools
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import scenes
+from srz import abi
+
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+# ------------------------------------------------------------------------------------------------ inputs
+def tri(a, b, c, z=50.0, nrm=(0, 0, -1), uv=((0, 0), (0, 0), (0, 0))):
+    t = np.zeros(1, abi.TRI_DTYPE)
+    za, zb, zc = (z, z, z) if np.isscalar(z) else z
+    t["pos"][0] = [[a[0], a[1], za], [b[0], b[1], zb], [c[0], c[1], zc]]
+    t["nrm"][0] = [nrm] * 3 if np.ndim(nrm) == 1 else nrm
+    t["uv"][0] = uv
+    return t
+
+
+def ccw(a, b, c, **kw):  # a winding that survives the cull for eye=(0,0,1)
+    return tri(a, c, b, **kw)
+
+
+def frame(tris, w=64, h=64, shader=abi.SHADER_NORMAL, eye=(0, 0, 1), lights=(), flags=abi.FUSED_CLEAR, tex=-1, **kw):
+    batches = tris if isinstance(tris, list) else [(shader, tex, tris)]
+    return abi.Frame(w, h, eye, np.asarray(lights, np.float32).reshape(-1, 2, 3), batches, flags, **kw)
+
+
+def lit(f, lights=None, **kw):
+    """a copy of abi.Frame f with other lights / shading constants (same triangles)"""
+    c = f.c
+    args = dict(ka=tuple(c.ka), ks=tuple(c.ks), p=c.p, kh=c.kh, kn=c.kn)
+    args.update(kw)
+    batches = kw.pop("batches", None) or [(f._batches[i].shader, f._batches[i].tex_id, t) for i, t in enumerate(f.tris)]
+    args.pop("batches", None)
+    return abi.Frame(c.width, c.height, tuple(c.eye), f.lights if lights is None else np.asarray(lights, np.float32).reshape(-1, 2, 3),
+                     batches, c.flags, **args)
+
+
+def soup(seed, n, w, h, zs, big=False):
+    rng = np.random.default_rng(seed)
+    t = np.zeros(n, abi.TRI_DTYPE)
+    c = rng.uniform(-8, [w + 8, h + 8], (n, 1, 2))
+    r = rng.uniform(1, 70 if big else 24, (n, 1, 1))
+    xy = c + rng.uniform(-1, 1, (n, 3, 2)) * r
+    xy = np.round(xy * 4) / 4 if seed % 2 else xy  # half the seeds: quarter-pixel vertices → exact edge hits and ties
+    t["pos"][:, :, :2] = xy
+    t["pos"][:, :, 2] = rng.choice(zs, (n, 1)) if seed % 3 == 0 else rng.choice(zs, (n, 3))
+    nn = rng.normal(size=(n, 3, 3))
+    t["nrm"] = nn / np.linalg.norm(nn, axis=2, keepdims=True)
+    t["uv"] = rng.uniform(0, 1, (n, 3, 2))
+    return t
+
+
+def stack(n, w=64, h=64, jitter=0):
+    """n triangles stacked over one 32x32 tile (the list of tile (0,0) has n entries), depths shuffled, some ties"""
+    rng = np.random.default_rng(n + jitter)
+    t = np.zeros(n, abi.TRI_DTYPE)
+    c = rng.uniform(4, 28, (n, 1, 2))
+    t["pos"][:, :, :2] = np.round((c + rng.uniform(-1, 1, (n, 3, 2)) * rng.uniform(6, 30, (n, 1, 1))) * 4) / 4
+    t["pos"][:, :, 2] = rng.choice(np.float32([1, 2, 3, 4, 5, 6, 7, 8]), (n, 3))
+    t["nrm"] = [0, 0, -1]
+    return frame(t, w, h)
+
+
+def big_tris(n, w, h, seed, tall):
+    """n triangles about `tall` pixels high at random places (depths distinct per triangle)"""
+    rng = np.random.default_rng(seed)
+    t = np.zeros(n, abi.TRI_DTYPE)
+    cx, cy = rng.uniform(0, w, n), rng.uniform(0, h, n)
+    t["pos"][:, 0, :2] = np.stack([cx - 9, cy - tall / 2], 1)
+    t["pos"][:, 2, :2] = np.stack([cx + 11, cy - tall / 2 + 3], 1)  # (this winding faces the eye at (0, 0, 1))
+    t["pos"][:, 1, :2] = np.stack([cx + 2, cy + tall / 2], 1)
+    t["pos"][:, :, 2] = rng.uniform(5, 50, (n, 1))
+    nn = rng.normal(size=(n, 3, 3))
+    t["nrm"] = nn / np.linalg.norm(nn, axis=2, keepdims=True)
+    return t
+
+
+def adversarial_tris(seed, n, w, h):
+    """the shapes the tightened rectangles (k_raster's slab clips, bucket_group's band clips) must stay conservative for:
+    needles, slivers, huge and far-off-screen vertices (past the 2^20 guard too), sub-pixel triangles around pixel centres,
+    edges exactly through pixel centres and along tile borders, ordinary large triangles — in both windings"""
+    rng = np.random.default_rng(seed)
+    t = np.zeros(n, abi.TRI_DTYPE)
+    kind = rng.integers(0, 9, n)
+    c = rng.uniform([0, 0], [w, h], (n, 2))
+    ang = rng.uniform(0, 2 * np.pi, n)
+    d = np.stack([np.cos(ang), np.sin(ang)], 1)
+    nrm = np.stack([-d[:, 1], d[:, 0]], 1)
+    xy = np.zeros((n, 3, 2))
+    L = rng.uniform(100, 600, n)[:, None]
+    # 0 needles: a very short base, the apex far away
+    k = kind == 0
+    base = (10.0 ** rng.uniform(-3, 0, n))[:, None]
+    xy[k] = np.stack([c, c + nrm * base, c + d * L], 1)[k]
+    # 1 slivers: a long edge, a height of 1e-4 .. 0.5 pixels
+    k = kind == 1
+    hgt = (10.0 ** rng.uniform(-4, -0.3, n))[:, None]
+    xy[k] = np.stack([c, c + d * L, c + d * L * rng.uniform(0, 1, (n, 1)) + nrm * hgt], 1)[k]
+    # 2 huge: vertices 1e3 .. 1e6 pixels out;  3 past the guard: one vertex 2e6 .. 1e8 out
+    k = kind == 2
+    xy[k] = (c[:, None, :] + rng.normal(size=(n, 3, 2)) * (10.0 ** rng.uniform(3, 6, (n, 1, 1))))[k]
+    k = kind == 3
+    far = c[:, None, :] + rng.normal(size=(n, 3, 2)) * 300.0
+    far[:, 0] += d * (10.0 ** rng.uniform(6.3, 8, n))[:, None]
+    xy[k] = far[k]
+    # 4 sub-pixel triangles around pixel centres
+    k = kind == 4
+    xy[k] = (np.round(c)[:, None, :] + rng.uniform(-1, 1, (n, 3, 2)) * (10.0 ** rng.uniform(-3, 0, (n, 1, 1))))[k]
+    # 5 integer / half-integer / tile-border vertices: edges through pixel centres, exact zeros of the edge functions
+    k = kind == 5
+    grid = rng.choice([1.0, 0.5, 32.0], (n, 1, 1))
+    xy[k] = (np.round((c[:, None, :] + rng.uniform(-1, 1, (n, 3, 2)) * rng.uniform(2, 200, (n, 1, 1))) / grid) * grid)[k]
+    # 6 ordinary large triangles
+    k = kind == 6
+    xy[k] = (c[:, None, :] + rng.uniform(-1, 1, (n, 3, 2)) * rng.uniform(30, 400, (n, 1, 1)))[k]
+    # 7 tiny triangles (extent 2^-12 .. 2^-4 pixels) at coordinates < 64 around pixel centres, near the sliver limit of the guard:
+    #   below 2^-5 the tightened rectangles must fall back to the plain box (tight_margin), above it the margin must hold
+    k = kind == 7
+    Dt = (2.0 ** rng.uniform(-12, -4, n))[:, None]
+    c7 = np.round(rng.uniform([0, 0], [64, 64], (n, 2))) + rng.uniform(-1, 1, (n, 2)) * Dt
+    xy[k] = np.stack([c7, c7 + d * Dt, c7 + d * Dt * rng.uniform(0, 1, (n, 1)) + nrm * Dt * (2.0 ** rng.uniform(-7.5, 0, n))[:, None]], 1)[k]
+    # 8 small or ulp-sized triangles 1e4 .. 1e7 pixels off screen on ONE axis: the clamped box is an edge column / row at a
+    #   distance from the triangle that has nothing to do with its extent (plain box there)
+    k = kind == 8
+    off = np.zeros((n, 2))
+    off[np.arange(n), rng.integers(0, 2, n)] = rng.choice([-1.0, 1.0], n) * 10.0 ** rng.uniform(4, 7, n)
+    D8 = (10.0 ** rng.uniform(-3, 2.5, n))[:, None, None]
+    xy[k] = ((c + off)[:, None, :] + rng.uniform(-1, 1, (n, 3, 2)) * D8)[k]
+    flip = rng.random(n) < 0.5
+    xy[flip] = xy[flip][:, ::-1]
+    t["pos"][:, :, :2] = xy
+    # (the screen-filling kinds lie behind the others, so that every small shape decides pixels of the final image)
+    t["pos"][:, :, 2] = np.where((kind == 2) | (kind == 3), rng.uniform(60, 80, n), rng.uniform(2, 60, n))[:, None] + rng.uniform(-1, 1, (n, 3))
+    nn = rng.normal(size=(n, 3, 3))
+    t["nrm"] = nn / np.linalg.norm(nn, axis=2, keepdims=True)
+    t["uv"] = rng.uniform(0, 1, (n, 3, 2))
+    return t
+
+
+def random_frame(rng, w, h, n_tris, flags):
+    """Random soup: mostly small triangles, some large / off-screen / sliver ones, random normals, uvs beyond [0,1],
+    every shader, 0-3 lights — the shapes the tile masks, the per-frame work lists and the FastMath paths must survive."""
+    def tris(n):
+        t = np.zeros(n, abi.TRI_DTYPE)
+        c = rng.uniform([-0.1 * w, -0.1 * h], [1.1 * w, 1.1 * h], (n, 1, 2))
+        size = np.where(rng.random((n, 1, 1)) < 0.85, rng.uniform(1, 24, (n, 1, 1)), rng.uniform(24, 1.5 * max(w, h), (n, 1, 1)))
+        xy = c + rng.uniform(-1, 1, (n, 3, 2)) * size
+        snap = rng.random((n, 1, 1)) < 0.3          # vertices exactly on pixel corners: on-edge samples, exact zeros
+        xy = np.where(snap, np.round(xy), xy)
+        t["pos"][:, :, :2] = xy
+        t["pos"][:, :, 2] = rng.uniform(1, 90, (n, 1)) + rng.uniform(-0.5, 0.5, (n, 3))
+        t["nrm"] = rng.normal(0, 1, (n, 3, 3)) * rng.choice([1.0, 1e-3, 50.0], (n, 1, 1))
+        t["uv"] = rng.uniform(-0.2, 1.2, (n, 3, 2))
+        return t
+    shaders = [abi.SHADER_NORMAL, abi.SHADER_TEXTURE, abi.SHADER_PHONG, abi.SHADER_BUMP, abi.SHADER_DISPLACEMENT]
+    nb = int(rng.integers(1, 4))
+    batches = []
+    for b in range(nb):
+        sh = shaders[int(rng.integers(0, len(shaders)))]
+        batches.append((sh, 0 if sh in (abi.SHADER_TEXTURE, abi.SHADER_BUMP, abi.SHADER_DISPLACEMENT) else -1, tris(max(1, n_tris // nb))))
+    nl = int(rng.integers(0, 4))
+    lights = np.concatenate([rng.uniform([0, 0, -50], [w, h, 120], (nl, 1, 3)), rng.uniform(0, 400, (nl, 1, 3))], 1).astype(np.float32)
+    return abi.Frame(w, h, (0.0, 0.0, float(rng.uniform(0.5, 2.0))), lights, batches, flags, p=float(rng.choice([150.0, 8.0, 2.5])))
+
+
+# ------------------------------------------------------------------------------------------------ comparison
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def words(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
+def same(gpu, ref, what):
+    """the four planes are bit-identical (gpu[p], ref[p]: plane p, of one frame or of a whole set)"""
+    for p in range(4):
+        g, r = bits(gpu[p]), bits(ref[p])
+        bad = g != r
+        assert not bad.any(), f"{what}: plane {p} differs at {int(bad.sum())} pixels, first {np.argwhere(bad)[:4].tolist()}: " \
+                              f"got {g[bad][:4]} want {r[bad][:4]}"
+
+
+def compare(gpu, ref, name):
+    """the stated tolerance of the exact mode (tests/test_gpu_parity.py): z bit-identical, |Δcolour| <= 1e-3 on at most 1e-5 of the
+    covered pixels (the pow corner).  Returns the number of colour values that are not bit-identical."""
+    gz, rz = gpu[0], ref[0]
+    n_cov = max(1, int(np.isfinite(rz).sum()))
+    z_same = np.array_equal(bits(gz), bits(rz))
+    dc = np.maximum.reduce([np.abs(g.astype(np.float64) - r.astype(np.float64)) for g, r in zip(gpu[1:], ref[1:])])
+    dc = np.nan_to_num(dc, nan=0.0) + np.where(np.isnan(gpu[1]) != np.isnan(ref[1]), 1e9, 0.0)
+    n_diff = int(sum((bits(g) != bits(r)).sum() for g, r in zip(gpu[1:], ref[1:])))
+    print(f"[{name}] covered={n_cov} z_bit_identical={z_same} colour_values_not_bit_identical={n_diff} max_dcolour={dc.max():.3g}")
+    assert z_same, f"{name}: z-buffer is not bit-identical"
+    assert dc.max() <= 1e-3 and (dc > 0).sum() <= max(1, int(1e-5 * n_cov)), f"{name}: colour outside the stated tolerance"
+    return n_diff
+
+
+def changed(a, b):
+    """fraction of the covered pixels of oracle frame a whose colour differs from b's by more than the stated tolerance"""
+    cov = np.isfinite(a[0])
+    d = np.maximum.reduce([np.abs(x.astype(np.float64) - y.astype(np.float64)) for x, y in zip(a[1:], b[1:])])
+    return float((d[cov] > 1e-3).mean())
+
+
+V_TOL, S_EPS = 0.5, 1e-3
+
+
+def check_approx(gpu, gst, ref, rst, pre, s_class, name):
+    """the stated tolerance of the tolerance mode (tests/test_gpu_approx.py), on what oracle_with_probes returns"""
+    assert gst == rst, (name, gst, rst)
+    assert np.array_equal(bits(gpu[0]), bits(ref[0])), f"{name}: z plane is not bit-identical in the tolerance mode"
+    cov = np.isfinite(ref[0])
+    n_cov, n_s = int(cov.sum()), int((s_class & cov).sum())
+    worst_v, flips, exact = 0.0, 0, 0
+    for c in (1, 2, 3):
+        g, r, p = gpu[c].astype(np.float64), ref[c].astype(np.float64), pre[c].astype(np.float64)
+        assert np.array_equal(g[~cov], r[~cov]), f"{name}: uncovered pixels differ"
+        d = np.abs(g - r)
+        v = cov & ~s_class
+        worst_v = max(worst_v, float(d[v].max()) if v.any() else 0.0)
+        out = v & (d > V_TOL)
+        if out.any():
+            ys, xs = np.nonzero(out)
+            print(f"[approx {name}] channel {c}: {int(out.sum())} V values outside {V_TOL}, first at (x, y) {list(zip(xs[:6].tolist(), ys[:6].tolist()))}: "
+                  f"gpu {g[out][:6]} oracle {r[out][:6]}")
+        assert not out.any(), f"{name}: V pixel outside {V_TOL}: max {d[v].max()}"
+        s = cov & s_class
+        diff = s & (d != 0)
+        near = np.abs(p - np.rint(p)) <= S_EPS
+        assert not (diff & ~near).any(), (f"{name}: S pixel differs where the pre-truncation value is not within {S_EPS} of an integer: "
+                                          f"{int((diff & ~near).sum())} values, e.g. pre {p[diff & ~near][:4]} gpu {g[diff & ~near][:4]}")
+        assert not (d[diff] > 1.0).any(), f"{name}: S pixel off by more than one level"
+        flips += int(diff.sum())
+        exact += int((bits(gpu[c]) == bits(ref[c]))[cov].sum())
+    print(f"[approx {name}] covered={n_cov} S-class={n_s} max|dV|={worst_v:.4g} S truncation flips={flips} (of {3 * n_s} values) "
+          f"bit-identical colour values={exact} of {3 * n_cov}")
+    assert flips <= max(3, int(2e-3 * 3 * max(n_s, 1))), f"{name}: too many truncation flips"
+    return worst_v, flips
+
+
+@functools.lru_cache(maxsize=None)
+def golden():
+    """(golden.json, golden_samples.npz, the make_golden module that wrote them)"""
+    sys.path.insert(0, GOLDEN_DIR)
+    import make_golden
+    return json.load(open(os.path.join(GOLDEN_DIR, "golden.json"))), np.load(os.path.join(GOLDEN_DIR, "golden_samples.npz")), make_golden
+
+
+def check_against_golden(name, planes, stats=None, exact=True):
+    """compare planes (the oracle's or the GPU's) with the committed fixture `name`"""
+    gold, samples, make_golden = golden()
+    g = gold[name]
+    s = samples[name]
+    z, c0, c1, c2 = planes
+    xs, ys = s[:, 0].astype(int), s[:, 1].astype(int)
+    assert np.array_equal(z[ys, xs].view(np.uint32), s[:, 2]), "sampled z differs"
+    for k, p in enumerate((c0, c1, c2)):
+        got = p[ys, xs]
+        want = s[:, 3 + k].view(np.float32)
+        if exact:
+            assert np.array_equal(got.view(np.uint32), s[:, 3 + k]), f"sampled c{k} differs"
+        else:
+            assert np.abs(got - want).max() <= 0.5
+    assert int(np.isfinite(z).sum()) == g["covered"]
+    assert make_golden.digest(z) == g["sha256"]["z"]
+    if exact:
+        for k, p in zip(("c0", "c1", "c2"), (c0, c1, c2)):
+            assert make_golden.digest(p) == g["sha256"][k]
+    if stats is not None:
+        assert stats == g["stats"]
+
+
+# ------------------------------------------------------------------------------------------------ running
+def stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def render(ctx, frames, flags=abi.FUSED_CLEAR, prefill=None, vis=False):
+    """a set of the frames and its colour (or visibility) render into a fresh buffer (prefill: [n, 4, rows, W] float32 the buffer
+    starts with, else zeros) → (frameset, [n, 4, local_rows, W] float32 tensor)"""
+    import torch
+    fs = ctx.frameset(frames)
+    out = torch.zeros(fs.out_shape, dtype=torch.float32, device="cuda")
+    if prefill is not None:
+        out.copy_(torch.as_tensor(prefill))
+    (fs.render_visibility if vis else fs.render)(out.data_ptr(), fs.out_bytes, flags, stream())
+    torch.cuda.synchronize()
+    return fs, out
+
+
+def run(fs, flags=abi.FUSED_CLEAR):
+    """(colour render, shade of the visibility render into a second buffer) of the set, both as uint32 words, and the visibility buffer"""
+    import torch
+    col = torch.zeros(fs.out_shape, dtype=torch.float32, device="cuda")
+    vis, out = torch.zeros_like(col), torch.zeros_like(col)
+    s = stream()
+    fs.render(col.data_ptr(), fs.out_bytes, flags, s)
+    fs.render_visibility(vis.data_ptr(), fs.out_bytes, flags, s)
+    fs.shade_visibility(vis.data_ptr(), out.data_ptr(), fs.out_bytes, flags, s)
+    torch.cuda.synchronize()
+    return words(col), words(out), vis
+
+
+def run_both(ctx, orc, f, planes_init=None, want_stats=True, what=""):
+    """one frame through the oracle and through srz_draw, each from a copy of the incoming planes if there are any; the counters are
+    equal → (gpu planes, oracle planes)"""
+    def clone():
+        return None if planes_init is None else tuple(p.copy() for p in planes_init)
+    rc, ref, rst = orc.draw(f, clone())
+    assert rc == 0
+    gpu, gst = ctx.draw(f, clone(), want_stats=want_stats)
+    if want_stats:
+        assert gst == rst, (what, gst, rst)
+    return gpu, ref
+
+
+def both_paths(ctx, orc, f_builder, planes_init=None, what=""):
+    """run_both through the order-independent rasteriser and through the ordered one (f_builder(extra flags) → frame); both must give
+    the oracle's planes bit for bit."""
+    for extra in (0, abi.ORDERED_RASTER):
+        gpu, ref = run_both(ctx, orc, f_builder(extra), planes_init, what=f"{what} flags+={extra}")
+        same(gpu, ref, f"{what} flags+={extra}")
+
+
+def oracle_with_probes(orc, f):
+    """the oracle's planes and counters, and per pixel the colour in front of the scalar-tail truncation and the class (oracle.debug_s)"""
+    rc, ref, rst = orc.draw(f)
+    assert rc == 0
+    try:
+        orc.debug_s(1)
+        rc1, pre, _ = orc.draw(f)
+        orc.debug_s(2)
+        rc2, cls, _ = orc.draw(f)
+    finally:
+        orc.debug_s(0)
+    assert rc1 == 0 and rc2 == 0
+    s_class = cls[1] == -1.0
+    return ref, rst, pre, s_class
+
+
+# ------------------------------------------------------------------------------------------------ the context
+def make_ctx(approx=False):
+    import srz
+    c = srz.Context(0)
+    c.texture_upload(scenes.TEX_SPOT, scenes.spot_texture())
+    if approx:
+        c.set_option(abi.OPT_APPROX_SHADE, 1)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    """one context per test module that imports this fixture (`from support import ctx  # noqa: F401`), the spot texture in slot 0"""
+    yield from make_ctx()
+
+
+@pytest.fixture()
+def actx():
+    """a fresh context in the tolerance mode (SRZ_OPT_APPROX_SHADE) for every test"""
+    yield from make_ctx(approx=True)

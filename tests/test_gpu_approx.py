@@ -17,72 +17,9 @@ import pytest
 
 import scenes
 from srz import abi
+from support import actx, bits, check_approx, oracle_with_probes, random_frame, same  # noqa: F401  (actx: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-V_TOL, S_EPS = 0.5, 1e-3
-
-
-@pytest.fixture()
-def actx():
-    import srz
-    c = srz.Context(0)
-    c.texture_upload(scenes.TEX_SPOT, scenes.spot_texture())
-    c.set_option(abi.OPT_APPROX_SHADE, 1)
-    yield c
-    c.close()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def oracle_with_probes(orc, f):
-    rc, ref, rst = orc.draw(f)
-    assert rc == 0
-    try:
-        orc.debug_s(1)
-        rc1, pre, _ = orc.draw(f)
-        orc.debug_s(2)
-        rc2, cls, _ = orc.draw(f)
-    finally:
-        orc.debug_s(0)
-    assert rc1 == 0 and rc2 == 0
-    s_class = cls[1] == -1.0
-    return ref, rst, pre, s_class
-
-
-def check(gpu, gst, ref, rst, pre, s_class, name):
-    assert gst == rst, (name, gst, rst)
-    assert np.array_equal(bits(gpu[0]), bits(ref[0])), f"{name}: z plane is not bit-identical in the tolerance mode"
-    cov = np.isfinite(ref[0])
-    n_cov, n_s = int(cov.sum()), int((s_class & cov).sum())
-    worst_v, flips, exact = 0.0, 0, 0
-    for c in (1, 2, 3):
-        g, r, p = gpu[c].astype(np.float64), ref[c].astype(np.float64), pre[c].astype(np.float64)
-        assert np.array_equal(g[~cov], r[~cov]), f"{name}: uncovered pixels differ"
-        d = np.abs(g - r)
-        v = cov & ~s_class
-        worst_v = max(worst_v, float(d[v].max()) if v.any() else 0.0)
-        out = v & (d > V_TOL)
-        if out.any():
-            ys, xs = np.nonzero(out)
-            print(f"[approx {name}] channel {c}: {int(out.sum())} V values outside {V_TOL}, first at (x, y) {list(zip(xs[:6].tolist(), ys[:6].tolist()))}: "
-                  f"gpu {g[out][:6]} oracle {r[out][:6]}")
-        assert not out.any(), f"{name}: V pixel outside {V_TOL}: max {d[v].max()}"
-        s = cov & s_class
-        diff = s & (d != 0)
-        near = np.abs(p - np.rint(p)) <= S_EPS
-        assert not (diff & ~near).any(), (f"{name}: S pixel differs where the pre-truncation value is not within {S_EPS} of an integer: "
-                                          f"{int((diff & ~near).sum())} values, e.g. pre {p[diff & ~near][:4]} gpu {g[diff & ~near][:4]}")
-        assert not (d[diff] > 1.0).any(), f"{name}: S pixel off by more than one level"
-        flips += int(diff.sum())
-        exact += int((bits(gpu[c]) == bits(ref[c]))[cov].sum())
-    print(f"[approx {name}] covered={n_cov} S-class={n_s} max|dV|={worst_v:.4g} S truncation flips={flips} (of {3 * n_s} values) "
-          f"bit-identical colour values={exact} of {3 * n_cov}")
-    assert flips <= max(3, int(2e-3 * 3 * max(n_s, 1))), f"{name}: too many truncation flips"
-    return worst_v, flips
-
 
 @pytest.mark.parametrize("name,build", [
     ("config2 TEXTURE", lambda: scenes.config2(7)),
@@ -96,7 +33,7 @@ def test_tolerance_mode_within_the_stated_tolerance(actx, orc, name, build):
     f = build()
     ref, rst, pre, s_class = oracle_with_probes(orc, f)
     gpu, gst = actx.draw(f, want_stats=True)
-    worst_v, _ = check(gpu, gst, ref, rst, pre, s_class, name)
+    worst_v, _ = check_approx(gpu, gst, ref, rst, pre, s_class, name)
     same8 = (orc.resolve8(gpu) == orc.resolve8(ref)).all(axis=2)
     frac = float(same8.mean())
     print(f"[approx {name}] resolved 8-bit image identical on {frac:.6f} of the pixels")
@@ -110,7 +47,7 @@ def test_tolerance_mode_exponents(actx, orc, p):
     f = abi.Frame(512, 512, scenes.EYE, scenes.LIGHTS, [(abi.SHADER_TEXTURE, scenes.TEX_SPOT, f0.tris[0])], abi.FUSED_CLEAR, p=p)
     ref, rst, pre, s_class = oracle_with_probes(orc, f)
     gpu, gst = actx.draw(f, want_stats=True)
-    check(gpu, gst, ref, rst, pre, s_class, f"p={p}")
+    check_approx(gpu, gst, ref, rst, pre, s_class, f"p={p}")
 
 
 @pytest.mark.parametrize("n_lights", [1, 3, 4])
@@ -121,7 +58,7 @@ def test_tolerance_mode_light_counts(actx, orc, n_lights):
     f = abi.Frame(512, 512, scenes.EYE, lights, [(abi.SHADER_TEXTURE, scenes.TEX_SPOT, f0.tris[0])], abi.FUSED_CLEAR)
     ref, rst, pre, s_class = oracle_with_probes(orc, f)
     gpu, gst = actx.draw(f, want_stats=True)
-    check(gpu, gst, ref, rst, pre, s_class, f"{n_lights} lights")
+    check_approx(gpu, gst, ref, rst, pre, s_class, f"{n_lights} lights")
 
 
 def test_frames_the_tolerance_builds_do_not_cover_stay_exact(actx, orc):
@@ -166,16 +103,15 @@ def test_option_is_per_frameset_and_the_default_stays_exact(orc):
 
 @pytest.mark.parametrize("seed", range(int(__import__("os").environ.get("SRZ_FUZZ_SEEDS", "8"))))
 def test_tolerance_mode_on_random_frames(orc, seed):
-    """the fuzz frames of test_gpu_frameset (random soups, every shader, 0-3 lights placed INSIDE the image, exponents 150 / 8 / 2.5,
+    """the fuzz frames of support.random_frame (random soups, every shader, 0-3 lights placed INSIDE the image, exponents 150 / 8 / 2.5,
     degenerate normals, uvs beyond [0, 1]) through a frameset in the tolerance mode: z, coverage and counters bit-identical, colours
     within the stated tolerance; frames the tolerance builds do not cover (no light, BUMP / DISPLACEMENT batches) bit-identical"""
     import torch
     import srz
-    from test_gpu_frameset import _random_frame
     rng = np.random.default_rng(5000 + seed)
     w, h = [(64, 64), (200, 120), (97, 131), (256, 96), (33, 290), (128, 128), (320, 200), (70, 70)][seed % 8]
     flags = abi.FUSED_CLEAR | (abi.UNIFIED if seed % 3 == 2 else 0)
-    frames = [_random_frame(rng, w, h, int(rng.integers(1, 400)), flags) for _ in range(int(rng.integers(2, 8)))]
+    frames = [random_frame(rng, w, h, int(rng.integers(1, 400)), flags) for _ in range(int(rng.integers(2, 8)))]
     ctx = srz.Context(0)
     ctx.texture_upload(0, scenes.spot_texture())
     ctx.set_option(abi.OPT_APPROX_SHADE, 1)
@@ -188,8 +124,7 @@ def test_tolerance_mode_on_random_frames(orc, seed):
         ref, rst, pre, s_class = oracle_with_probes(orc, f)
         covered = len(f.lights) >= 1 and all(int(f._batches[b].shader) in (abi.SHADER_NORMAL, abi.SHADER_TEXTURE, abi.SHADER_PHONG) for b in range(f.c.n_batches))
         if covered:
-            check(tuple(got[i]), rst, ref, rst, pre, s_class, f"fuzz seed {seed} frame {i}")
+            check_approx(tuple(got[i]), rst, ref, rst, pre, s_class, f"fuzz seed {seed} frame {i}")
         else:
-            for p in range(4):
-                assert np.array_equal(bits(got[i, p]), bits(ref[p])), (seed, i, p)
+            same(got[i], ref, f"seed {seed} frame {i}")
     fs.close(), ctx.close()

@@ -13,12 +13,9 @@ import torch
 
 import scenes
 from srz import abi, parallel
+from support import bits
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.mark.parametrize("world,size", [(2, 256), (3, 320), (8, 512)])

@@ -6,26 +6,14 @@ import torch
 
 import scenes
 from srz import abi, parallel
+from support import bits, random_frame, render, same
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
 def frames():
     return [scenes.config2(i, size=512) for i in (0, 3, 7, 12, 30)]
-
-
-def render(ctx, frames, flags=abi.FUSED_CLEAR, out=None):
-    fs = ctx.frameset(frames)
-    if out is None:
-        out = torch.zeros(fs.out_shape, dtype=torch.float32, device="cuda")
-    fs.render(out.data_ptr(), fs.out_bytes, flags, torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return fs, out
 
 
 def test_frameset_equals_per_frame_draw_and_oracle(orc, frames):
@@ -37,8 +25,7 @@ def test_frameset_equals_per_frame_draw_and_oracle(orc, frames):
     tot = {}
     for i, f in enumerate(frames):
         rc, ref, st = orc.draw(f)
-        for p in range(4):
-            assert np.array_equal(bits(got[i, p]), bits(ref[p])), (i, p)
+        same(got[i], ref, f"frame {i}")
         for k, v in st.items():
             tot[k] = tot.get(k, 0) + v
     assert fs.stats() == tot
@@ -60,8 +47,7 @@ def test_both_triangle_stream_layouts_give_the_same_planes(frames):
     for rep in range(2):
         for i, f in enumerate(frames):
             planes, _ = ctx.draw(f)
-            for p in range(4):
-                assert np.array_equal(bits(got[i, p]), bits(planes[p])), (rep, i, p)
+            same(got[i], planes, f"rep {rep} frame {i}")
     ctx.close()
 
 
@@ -140,8 +126,7 @@ def test_full_size_properties_config2_batch(orc):
     got = a.cpu().numpy()
     for i in (0, 17, 35):
         rc, ref, _ = orc.draw(fr[i])
-        for p in range(4):
-            assert np.array_equal(bits(got[i, p]), bits(ref[p])), (i, p)
+        same(got[i], ref, f"frame {i}")
     ctx.close()
 
 
@@ -164,32 +149,6 @@ def test_device_resolve8_equals_display_resolve(orc, frames):
     ctx.close()
 
 
-def _random_frame(rng, w, h, n_tris, flags):
-    """Random soup: mostly small triangles, some large / off-screen / sliver ones, random normals, uvs beyond [0,1],
-    every shader, 0-3 lights — the shapes the tile masks, the per-frame work lists and the FastMath paths must survive."""
-    def tris(n):
-        t = np.zeros(n, abi.TRI_DTYPE)
-        c = rng.uniform([-0.1 * w, -0.1 * h], [1.1 * w, 1.1 * h], (n, 1, 2))
-        size = np.where(rng.random((n, 1, 1)) < 0.85, rng.uniform(1, 24, (n, 1, 1)), rng.uniform(24, 1.5 * max(w, h), (n, 1, 1)))
-        xy = c + rng.uniform(-1, 1, (n, 3, 2)) * size
-        snap = rng.random((n, 1, 1)) < 0.3          # vertices exactly on pixel corners: on-edge samples, exact zeros
-        xy = np.where(snap, np.round(xy), xy)
-        t["pos"][:, :, :2] = xy
-        t["pos"][:, :, 2] = rng.uniform(1, 90, (n, 1)) + rng.uniform(-0.5, 0.5, (n, 3))
-        t["nrm"] = rng.normal(0, 1, (n, 3, 3)) * rng.choice([1.0, 1e-3, 50.0], (n, 1, 1))
-        t["uv"] = rng.uniform(-0.2, 1.2, (n, 3, 2))
-        return t
-    shaders = [abi.SHADER_NORMAL, abi.SHADER_TEXTURE, abi.SHADER_PHONG, abi.SHADER_BUMP, abi.SHADER_DISPLACEMENT]
-    nb = int(rng.integers(1, 4))
-    batches = []
-    for b in range(nb):
-        sh = shaders[int(rng.integers(0, len(shaders)))]
-        batches.append((sh, 0 if sh in (abi.SHADER_TEXTURE, abi.SHADER_BUMP, abi.SHADER_DISPLACEMENT) else -1, tris(max(1, n_tris // nb))))
-    nl = int(rng.integers(0, 4))
-    lights = np.concatenate([rng.uniform([0, 0, -50], [w, h, 120], (nl, 1, 3)), rng.uniform(0, 400, (nl, 1, 3))], 1).astype(np.float32)
-    return abi.Frame(w, h, (0.0, 0.0, float(rng.uniform(0.5, 2.0))), lights, batches, flags, p=float(rng.choice([150.0, 8.0, 2.5])))
-
-
 import os
 
 
@@ -200,7 +159,7 @@ def test_fuzz_random_frames_bit_identical_to_oracle(orc, seed):
     rng = np.random.default_rng(1000 + seed)
     w, h = [(64, 64), (200, 120), (97, 131), (256, 96), (33, 290), (128, 128), (320, 200), (70, 70)][seed % 8]
     flags = abi.FUSED_CLEAR | (abi.UNIFIED if seed % 3 == 2 else 0)
-    frames = [_random_frame(rng, w, h, int(rng.integers(1, 400)), flags) for _ in range(int(rng.integers(2, 12)))]
+    frames = [random_frame(rng, w, h, int(rng.integers(1, 400)), flags) for _ in range(int(rng.integers(2, 12)))]
     ctx = srz.Context(0)
     ctx.texture_upload(0, scenes.spot_texture())
     fs, out = render(ctx, frames, flags=0)           # flags come from the frames
@@ -209,9 +168,7 @@ def test_fuzz_random_frames_bit_identical_to_oracle(orc, seed):
     for i, f in enumerate(frames):
         rc, ref, st = orc.draw(f)
         assert rc == 0
-        for p in range(4):
-            same = bits(got[i, p]) == bits(ref[p])
-            assert same.all(), f"seed {seed} frame {i} plane {p}: {int((~same).sum())} words differ, first at {np.argwhere(~same)[0]}"
+        same(got[i], ref, f"seed {seed} frame {i}")
         for k, v in st.items():
             tot[k] = tot.get(k, 0) + v
     assert fs.stats() == tot
@@ -236,8 +193,7 @@ def test_draw_batch_host_buffers_equal_per_frame_draw(orc):
     for i, f in enumerate(fr):
         rc, ref, s1 = orc.draw(f, init1 if i == 1 else None)
         assert rc == 0
-        for p in range(4):
-            assert np.array_equal(bits(got[i, p]), bits(ref[p])), (i, p)
+        same(got[i], ref, f"frame {i}")
         for k, v in s1.items():
             tot[k] = tot.get(k, 0) + v
     assert st == tot
@@ -315,8 +271,7 @@ def test_srz_draw_reuses_its_frameset_between_calls(orc):
     for i, f in enumerate(seq):
         rc, ref, rst = orc.draw(f)
         gpu, gst = ctx.draw(f, want_stats=(i % 2 == 0))
-        for p in range(4):
-            assert np.array_equal(bits(gpu[p]), bits(ref[p])), (i, p)
+        same(gpu, ref, f"frame {i}")
         assert gst is None or gst == rst
     # accumulate mode through the cached path: the second draw starts from the first one's planes
     f0, f1 = scenes.config2(0, size=256), scenes.config2(18, size=256, flags=0)
@@ -324,8 +279,7 @@ def test_srz_draw_reuses_its_frameset_between_calls(orc):
     rc, ref, _ = orc.draw(f1, ref)
     gpu, _ = ctx.draw(f0)
     gpu, _ = ctx.draw(f1, gpu)
-    for p in range(4):
-        assert np.array_equal(bits(gpu[p]), bits(ref[p])), p
+    same(gpu, ref, "accumulate through the cached set")
     ctx.close()
 
 
@@ -407,8 +361,7 @@ def test_mixed_fast_and_generic_frames_share_one_set(orc, n_frames):
     for i, f in enumerate(frames):
         rc, ref, st = orc.draw(f)
         assert rc == 0
-        for p in range(4):
-            assert np.array_equal(bits(got[i, p]), bits(ref[p])), (n_frames, i, p)
+        same(got[i], ref, f"{n_frames} frames, frame {i}")
     fs.close()
     ctx.close()
 
@@ -433,8 +386,7 @@ def test_two_lanes_at_batch_size_take_turns_and_match_the_oracle(orc):
     for o in outs:
         got = o.cpu().numpy()
         for i, planes in ref.items():
-            for p in range(4):
-                assert np.array_equal(bits(got[i, p]), bits(planes[p])), (i, p)
+            same(got[i], planes, f"frame {i}")
     assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32))
     lr.close()
     ctx.close()
@@ -463,8 +415,7 @@ def test_clear_grid_is_measured_and_every_grid_gives_the_same_bits(orc):
             got = first.cpu().numpy()
             for i in (0, 7):
                 ref = orc.draw(frames[i])[1]
-                for p in range(4):
-                    assert np.array_equal(bits(got[i, p]), bits(ref[p])), (i, p)
+                same(got[i], ref, f"frame {i}")
         else:
             assert torch.equal(out.view(torch.int32), first.view(torch.int32)), k
     dc = fs.debug_counters()
@@ -507,8 +458,7 @@ def test_lane_renderer_default_flags_are_the_fused_clear(orc):
     got = out.cpu().numpy()
     for i in (0, 7, 8, 15):
         ref = orc.draw(frames[i])[1]
-        for p in range(4):
-            assert np.array_equal(bits(got[i, p]), bits(ref[p])), (i, p)
+        same(got[i], ref, f"frame {i}")
     lr.close()
     ctx.close()
 
@@ -534,7 +484,6 @@ def test_large_set_rendered_as_sub_batches_matches_the_oracle(orc, monkeypatch):
         k = (7 * i) % 36
         if k not in ref:
             ref[k] = orc.draw(uniq[k])[1]
-        for p in range(4):
-            assert np.array_equal(bits(got[i, p]), bits(ref[k][p])), (i, p)
+        same(got[i], ref[k], f"frame {i}")
     fs.close()
     ctx.close()

@@ -13,47 +13,9 @@ import pytest
 
 import scenes
 from srz import abi
-from test_golden import check_against_golden
-from test_oracle_kat import ccw, frame, tri
+from support import bits, ccw, check_against_golden, compare, ctx, frame, run_both  # noqa: F401  (ctx: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import srz
-    c = srz.Context(0)
-    c.texture_upload(scenes.TEX_SPOT, scenes.spot_texture())
-    yield c
-    c.close()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def compare(gpu, ref, name):
-    gz, rz = gpu[0], ref[0]
-    n_cov = max(1, int(np.isfinite(rz).sum()))
-    z_same = np.array_equal(bits(gz), bits(rz))
-    dc = np.maximum.reduce([np.abs(g.astype(np.float64) - r.astype(np.float64)) for g, r in zip(gpu[1:], ref[1:])])
-    dc = np.nan_to_num(dc, nan=0.0) + np.where(np.isnan(gpu[1]) != np.isnan(ref[1]), 1e9, 0.0)
-    n_diff = int(sum((bits(g) != bits(r)).sum() for g, r in zip(gpu[1:], ref[1:])))
-    print(f"[{name}] covered={n_cov} z_bit_identical={z_same} colour_values_not_bit_identical={n_diff} max_dcolour={dc.max():.3g}")
-    assert z_same, f"{name}: z-buffer is not bit-identical"
-    assert dc.max() <= 1e-3 and (dc > 0).sum() <= max(1, int(1e-5 * n_cov)), f"{name}: colour outside the stated tolerance"
-    return n_diff
-
-
-def run_both(ctx, orc, f, planes_init=None, want_stats=True):
-    def clone():
-        return None if planes_init is None else tuple(p.copy() for p in planes_init)
-    rc, ref, rst = orc.draw(f, clone())
-    assert rc == 0
-    gpu, gst = ctx.draw(f, clone(), want_stats=want_stats)
-    if want_stats:
-        assert gst == rst, (gst, rst)
-    return gpu, ref
 
 
 # ------------------------------------------------------------------------------------------------ BASELINE configs

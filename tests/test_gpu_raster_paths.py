@@ -12,60 +12,14 @@ import torch
 
 import scenes
 from srz import abi
-from test_oracle_kat import frame, tri
+from support import adversarial_tris, big_tris, both_paths, ctx, frame, same, soup  # noqa: F401  (ctx: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import srz
-    c = srz.Context(0)
-    c.texture_upload(scenes.TEX_SPOT, scenes.spot_texture())
-    yield c
-    c.close()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def same(gpu, ref, what):
-    for p in range(4):
-        bad = bits(gpu[p]) != bits(ref[p])
-        assert not bad.any(), f"{what}: plane {p} differs at {int(bad.sum())} pixels, first {np.argwhere(bad)[:4].tolist()}"
-
-
-def both_paths(ctx, orc, f_builder, planes_init=None, what=""):
-    """draw through the order-independent rasteriser and through the ordered one; both must equal the oracle."""
-    for extra in (0, abi.ORDERED_RASTER):
-        f = f_builder(extra)
-        clone = (lambda: None) if planes_init is None else (lambda: tuple(p.copy() for p in planes_init))
-        rc, ref, rst = orc.draw(f, clone())
-        assert rc == 0
-        gpu, gst = ctx.draw(f, clone(), want_stats=True)
-        assert gst == rst, (what, extra, gst, rst)
-        same(gpu, ref, f"{what} flags+={extra}")
 
 
 @pytest.mark.parametrize("shader", [abi.SHADER_TEXTURE, abi.SHADER_NORMAL])
 def test_ordered_flag_equals_oracle_on_spot(ctx, orc, shader):
     both_paths(ctx, orc, lambda extra: scenes.config2(5, size=512, shader=shader, flags=abi.FUSED_CLEAR | extra), what="spot512")
-
-
-def soup(seed, n, w, h, zs, big=False):
-    rng = np.random.default_rng(seed)
-    t = np.zeros(n, abi.TRI_DTYPE)
-    c = rng.uniform(-8, [w + 8, h + 8], (n, 1, 2))
-    r = rng.uniform(1, 70 if big else 24, (n, 1, 1))
-    xy = c + rng.uniform(-1, 1, (n, 3, 2)) * r
-    xy = np.round(xy * 4) / 4 if seed % 2 else xy  # half the seeds: quarter-pixel vertices → exact edge hits and ties
-    t["pos"][:, :, :2] = xy
-    t["pos"][:, :, 2] = rng.choice(zs, (n, 1)) if seed % 3 == 0 else rng.choice(zs, (n, 3))
-    nn = rng.normal(size=(n, 3, 3))
-    t["nrm"] = nn / np.linalg.norm(nn, axis=2, keepdims=True)
-    t["uv"] = rng.uniform(0, 1, (n, 3, 2))
-    return t
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -123,7 +77,7 @@ def test_pool_overflow_then_growth(ctx, orc, monkeypatch):
             t["pos"][i] = [[-40 + 3 * i, -30, 10 + i % 5], [w + 50 - i, 10 + 2 * i, 12 + (i * 7) % 5], [200 + 5 * i, h + 60, 11 + (i * 3) % 7]]
         nn = rng.normal(size=(n, 3, 3))
         t["nrm"] = nn / np.linalg.norm(nn, axis=2, keepdims=True)
-        # (eye behind the triangles' winding: none of them is culled — with test_oracle_kat.frame's default eye every one was, and
+        # (eye behind the triangles' winding: none of them is culled — with support.frame's default eye every one was, and
         # rounds 2-5 ran this test on an empty frame)
         f = frame(t, w, h, shader=abi.SHADER_NORMAL, eye=(0, 0, -1), flags=abi.FUSED_CLEAR)
         rc, ref, st = orc.draw(f)
@@ -197,20 +151,6 @@ def test_many_small_frames_fill_every_subpool(ctx, orc):
     fs.close()
 
 
-def big_tris(n, w, h, seed, tall):
-    """n triangles about `tall` pixels high at random places (depths distinct per triangle)"""
-    rng = np.random.default_rng(seed)
-    t = np.zeros(n, abi.TRI_DTYPE)
-    cx, cy = rng.uniform(0, w, n), rng.uniform(0, h, n)
-    t["pos"][:, 0, :2] = np.stack([cx - 9, cy - tall / 2], 1)
-    t["pos"][:, 2, :2] = np.stack([cx + 11, cy - tall / 2 + 3], 1)  # (this winding faces the eye at (0, 0, 1))
-    t["pos"][:, 1, :2] = np.stack([cx + 2, cy + tall / 2], 1)
-    t["pos"][:, :, 2] = rng.uniform(5, 50, (n, 1))
-    nn = rng.normal(size=(n, 3, 3))
-    t["nrm"] = nn / np.linalg.norm(nn, axis=2, keepdims=True)
-    return t
-
-
 def test_first_render_sizes_the_pool(ctx, orc):
     """the same screen-filling triangles WITHOUT the lazy switch: a one-shot set must come out of the order-independent
     rasteriser on its first (and only) render — no tile may be left to the ordered one for want of pool space"""
@@ -249,68 +189,6 @@ def test_band_with_more_pairs_than_the_lds_stage(ctx, orc):
     t["pos"][:, :, 2] = rng.uniform(5, 50, (n, 1))
     t["nrm"][:] = [0, 0, -1]
     both_paths(ctx, orc, lambda extra: frame(t, w, h, shader=abi.SHADER_NORMAL, flags=abi.FUSED_CLEAR | extra), what="stage overflow")
-
-
-def adversarial_tris(seed, n, w, h):
-    """the shapes the tightened rectangles (k_raster's slab clips, bucket_group's band clips) must stay conservative for:
-    needles, slivers, huge and far-off-screen vertices (past the 2^20 guard too), sub-pixel triangles around pixel centres,
-    edges exactly through pixel centres and along tile borders, ordinary large triangles — in both windings"""
-    rng = np.random.default_rng(seed)
-    t = np.zeros(n, abi.TRI_DTYPE)
-    kind = rng.integers(0, 9, n)
-    c = rng.uniform([0, 0], [w, h], (n, 2))
-    ang = rng.uniform(0, 2 * np.pi, n)
-    d = np.stack([np.cos(ang), np.sin(ang)], 1)
-    nrm = np.stack([-d[:, 1], d[:, 0]], 1)
-    xy = np.zeros((n, 3, 2))
-    L = rng.uniform(100, 600, n)[:, None]
-    # 0 needles: a very short base, the apex far away
-    k = kind == 0
-    base = (10.0 ** rng.uniform(-3, 0, n))[:, None]
-    xy[k] = np.stack([c, c + nrm * base, c + d * L], 1)[k]
-    # 1 slivers: a long edge, a height of 1e-4 .. 0.5 pixels
-    k = kind == 1
-    hgt = (10.0 ** rng.uniform(-4, -0.3, n))[:, None]
-    xy[k] = np.stack([c, c + d * L, c + d * L * rng.uniform(0, 1, (n, 1)) + nrm * hgt], 1)[k]
-    # 2 huge: vertices 1e3 .. 1e6 pixels out;  3 past the guard: one vertex 2e6 .. 1e8 out
-    k = kind == 2
-    xy[k] = (c[:, None, :] + rng.normal(size=(n, 3, 2)) * (10.0 ** rng.uniform(3, 6, (n, 1, 1))))[k]
-    k = kind == 3
-    far = c[:, None, :] + rng.normal(size=(n, 3, 2)) * 300.0
-    far[:, 0] += d * (10.0 ** rng.uniform(6.3, 8, n))[:, None]
-    xy[k] = far[k]
-    # 4 sub-pixel triangles around pixel centres
-    k = kind == 4
-    xy[k] = (np.round(c)[:, None, :] + rng.uniform(-1, 1, (n, 3, 2)) * (10.0 ** rng.uniform(-3, 0, (n, 1, 1))))[k]
-    # 5 integer / half-integer / tile-border vertices: edges through pixel centres, exact zeros of the edge functions
-    k = kind == 5
-    grid = rng.choice([1.0, 0.5, 32.0], (n, 1, 1))
-    xy[k] = (np.round((c[:, None, :] + rng.uniform(-1, 1, (n, 3, 2)) * rng.uniform(2, 200, (n, 1, 1))) / grid) * grid)[k]
-    # 6 ordinary large triangles
-    k = kind == 6
-    xy[k] = (c[:, None, :] + rng.uniform(-1, 1, (n, 3, 2)) * rng.uniform(30, 400, (n, 1, 1)))[k]
-    # 7 tiny triangles (extent 2^-12 .. 2^-4 pixels) at coordinates < 64 around pixel centres, near the sliver limit of the guard:
-    #   below 2^-5 the tightened rectangles must fall back to the plain box (tight_margin), above it the margin must hold
-    k = kind == 7
-    Dt = (2.0 ** rng.uniform(-12, -4, n))[:, None]
-    c7 = np.round(rng.uniform([0, 0], [64, 64], (n, 2))) + rng.uniform(-1, 1, (n, 2)) * Dt
-    xy[k] = np.stack([c7, c7 + d * Dt, c7 + d * Dt * rng.uniform(0, 1, (n, 1)) + nrm * Dt * (2.0 ** rng.uniform(-7.5, 0, n))[:, None]], 1)[k]
-    # 8 small or ulp-sized triangles 1e4 .. 1e7 pixels off screen on ONE axis: the clamped box is an edge column / row at a
-    #   distance from the triangle that has nothing to do with its extent (plain box there)
-    k = kind == 8
-    off = np.zeros((n, 2))
-    off[np.arange(n), rng.integers(0, 2, n)] = rng.choice([-1.0, 1.0], n) * 10.0 ** rng.uniform(4, 7, n)
-    D8 = (10.0 ** rng.uniform(-3, 2.5, n))[:, None, None]
-    xy[k] = ((c + off)[:, None, :] + rng.uniform(-1, 1, (n, 3, 2)) * D8)[k]
-    flip = rng.random(n) < 0.5
-    xy[flip] = xy[flip][:, ::-1]
-    t["pos"][:, :, :2] = xy
-    # (the screen-filling kinds lie behind the others, so that every small shape decides pixels of the final image)
-    t["pos"][:, :, 2] = np.where((kind == 2) | (kind == 3), rng.uniform(60, 80, n), rng.uniform(2, 60, n))[:, None] + rng.uniform(-1, 1, (n, 3))
-    nn = rng.normal(size=(n, 3, 3))
-    t["nrm"] = nn / np.linalg.norm(nn, axis=2, keepdims=True)
-    t["uv"] = rng.uniform(0, 1, (n, 3, 2))
-    return t
 
 
 @pytest.mark.parametrize("seed", range(int(__import__("os").environ.get("SRZ_ADVERSARIAL_SEEDS", "6"))))

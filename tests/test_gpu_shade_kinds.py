@@ -4,7 +4,7 @@ The exact mode has thirteen separately compiled builds per kernel (csrc/srz_devi
 4..7 = the same with a BUMP / DISPLACEMENT batch, 8..11 = 1..4 lights with pow_fast, 12 = generic), each with a grey and a coloured
 path; the tolerance mode has four more.  classify_frames picks the kind on the host.  Here every kind shades a frame through both
 entry points (the colour render, and render_visibility + shade_visibility), every frame is compared WITH THE ORACLE through
-test_gpu_parity.compare() (bit-identical z, |Δcolour| <= 1e-3 on <= 1e-5 of the covered pixels; the count of colour words that are
+support.compare() (bit-identical z, |Δcolour| <= 1e-3 on <= 1e-5 of the covered pixels; the count of colour words that are
 not bit-identical is printed), and the kinds a set reports are compared with the rule written out below.  The tests without the gpu
 mark check on the CPU that the inputs can tell a wrong build from a right one: the pictures are not saturated, dropping the last
 light or swapping the last two intensities changes them, the exponents of the boundary cases give finite planes, and the frames of
@@ -17,8 +17,7 @@ import torch
 
 import scenes
 from srz import abi
-from test_gpu_parity import compare
-from test_gpu_shade_visibility import lit, run, stream, words
+from support import changed, check_approx, compare, ctx, lit, oracle_with_probes, run, same, stream, words  # noqa: F401  (ctx: the fixture)
 
 gpu = pytest.mark.gpu
 
@@ -106,8 +105,7 @@ def both_ways_against_the_oracle(ctx, orc, frames, expect, what, count=True):
     if count:
         SEEN["render"][0] |= expect[0]
         SEEN["render"][1] |= expect[1]
-    bad = col != out
-    assert not bad.any(), f"{what}: shade_visibility differs from the colour render at {int(bad.sum())} words, first {np.argwhere(bad)[:3].tolist()}"
+    same(out.swapaxes(0, 1), col.swapaxes(0, 1), f"{what}: shade_visibility against the colour render")
     assert (words(vis)[:, 1] != 0).any(), f"{what}: nothing drawn"
     if count:
         SEEN["shade_visibility"][0] |= expect[0]
@@ -117,23 +115,7 @@ def both_ways_against_the_oracle(ctx, orc, frames, expect, what, count=True):
     return n_diff
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    import srz
-    c = srz.Context(0)
-    c.texture_upload(scenes.TEX_SPOT, scenes.spot_texture())
-    yield c
-    c.close()
-
-
 # ------------------------------------------------------------------------------------------------ a. the kind matrix
-def changed(a, b):
-    """fraction of the covered pixels of oracle frame a whose colour differs from b's by more than the stated tolerance"""
-    cov = np.isfinite(a[0])
-    d = np.maximum.reduce([np.abs(x.astype(np.float64) - y.astype(np.float64)) for x, y in zip(a[1:], b[1:])])
-    return float((d[cov] > 1e-3).mean())
-
-
 @pytest.mark.parametrize("shader", ["TEXTURE", "PHONG", "BUMP", "DISPLACEMENT"])
 @pytest.mark.parametrize("grey", [True, False], ids=["grey", "coloured"])
 def test_matrix_inputs_tell_a_wrong_light_from_a_right_one(orc, shader, grey):
@@ -423,9 +405,8 @@ def test_kind_transitions_through_sceneset_update(ctx, orc):
 @gpu
 def test_tolerance_mode_uses_the_plain_kinds_only(orc):
     """SRZ_OPT_APPROX_SHADE: 1..4 lights with p = 150 or 7.5 go to kinds 0..3 (its four builds), never to 8..11; a BUMP frame, five
-    lights and no light keep the exact generic build — checked with test_gpu_approx.check, its tolerance unchanged"""
+    lights and no light keep the exact generic build — checked with support.check_approx, its tolerance unchanged"""
     import srz
-    from test_gpu_approx import check, oracle_with_probes
     c = srz.Context(0)
     c.set_option(abi.OPT_APPROX_SHADE, 1)
     c.texture_upload(scenes.TEX_SPOT, scenes.spot_texture())
@@ -447,7 +428,7 @@ def test_tolerance_mode_uses_the_plain_kinds_only(orc):
         got = out.cpu().numpy()
         for i, f in enumerate(frames):
             ref, rst, pre, s_class = oracle_with_probes(orc, f)
-            check(tuple(got[i]), rst, ref, rst, pre, s_class, f"approx {what} frame {i}")
+            check_approx(tuple(got[i]), rst, ref, rst, pre, s_class, f"approx {what} frame {i}")
             if f in exact:
                 assert np.array_equal(got[i].view(np.uint32), np.stack(ref).view(np.uint32)), (what, i)
         fs.close()

@@ -9,66 +9,18 @@ import torch
 
 import scenes
 from srz import abi
-from test_gpu_parity import compare
-from test_gpu_raster_paths import soup
-from test_gpu_visibility import stack
-from test_oracle_kat import frame
+from support import ccw, compare, ctx, frame, lit, run, same, soup, stack, stream, words  # noqa: F401  (ctx: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import srz
-    c = srz.Context(0)
-    c.texture_upload(scenes.TEX_SPOT, scenes.spot_texture())
-    yield c
-    c.close()
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def words(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def run(fs, flags=abi.FUSED_CLEAR, prefill=None):
-    """(colour render, shade of the visibility render into a second buffer) of the set, both as uint32 words"""
-    col = torch.zeros(fs.out_shape, dtype=torch.float32, device="cuda")
-    vis, out = torch.zeros_like(col), torch.zeros_like(col)
-    if prefill is not None:
-        for t in (col, vis, out):
-            t.copy_(torch.as_tensor(prefill))
-    s = stream()
-    fs.render(col.data_ptr(), fs.out_bytes, flags, s)
-    fs.render_visibility(vis.data_ptr(), fs.out_bytes, flags, s)
-    fs.shade_visibility(vis.data_ptr(), out.data_ptr(), fs.out_bytes, flags, s)
-    torch.cuda.synchronize()
-    return words(col), words(out), vis
 
 
 def check(ctx, frames, flags=abi.FUSED_CLEAR, what=""):
     fs = ctx.frameset(frames)
     col, out, vis = run(fs, flags)
-    for p in range(4):
-        bad = col[:, p] != out[:, p]
-        assert not bad.any(), f"{what}: plane {p} differs at {int(bad.sum())} pixels, first {np.argwhere(bad)[:3].tolist()}"
+    same(col.swapaxes(0, 1), out.swapaxes(0, 1), what)
     assert (words(vis)[:, 1] != 0).any(), f"{what}: nothing drawn"
     fs.close()
     return col
-
-
-def lit(f, lights=None, **kw):
-    """a copy of abi.Frame f with other lights / shading constants (same triangles)"""
-    c = f.c
-    args = dict(ka=tuple(c.ka), ks=tuple(c.ks), p=c.p, kh=c.kh, kn=c.kn)
-    args.update(kw)
-    batches = kw.pop("batches", None) or [(f._batches[i].shader, f._batches[i].tex_id, t) for i, t in enumerate(f.tris)]
-    args.pop("batches", None)
-    return abi.Frame(c.width, c.height, tuple(c.eye), f.lights if lights is None else np.asarray(lights, np.float32).reshape(-1, 2, 3),
-                     batches, c.flags, **args)
 
 
 @pytest.mark.parametrize("shader", [abi.SHADER_TEXTURE, abi.SHADER_PHONG, abi.SHADER_NORMAL, abi.SHADER_BUMP, abi.SHADER_DISPLACEMENT])
@@ -206,7 +158,6 @@ def test_operands_outside_the_fast_math_range(ctx, shader, build):
     """test_gpu_parity's zero / huge / tiny normals, a light straight above a pixel and one at the eye: the FAST build (2 lights) hands the
     tiles to the generic build's redo list, the generic build (5 lights, or p = 5000) re-shades them at once — both with IEEE math, bit
     for bit as the colour render"""
-    from test_oracle_kat import ccw
     tris = np.concatenate([
         ccw((4, 4), (30.5, 4), (4, 30.5), nrm=(0, 0, 0)),
         ccw((34, 4), (60.5, 4), (34, 30.5), nrm=(1e30, -1e30, 1e30)),

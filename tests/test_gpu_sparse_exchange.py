@@ -14,13 +14,10 @@ import torch
 
 import scenes
 from srz import abi, parallel
+from support import bits
 
 pytestmark = pytest.mark.gpu
 KINDS = (abi.EXCHANGE_PLANES, abi.EXCHANGE_BGR8)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def spot(i, w, h, flags=abi.FUSED_CLEAR):

@@ -6,12 +6,9 @@ import torch
 
 from srz import abi
 from srz import scenes as pscenes
+from support import bits
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.mark.parametrize("make", [pscenes.spot_texture_1024, pscenes.spot_bunny_1080p])

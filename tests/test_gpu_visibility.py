@@ -8,59 +8,33 @@ import torch
 import scenes
 import visref
 from srz import abi, parallel
-from test_gpu_raster_paths import soup
-from test_oracle_kat import frame
+from support import ctx, frame, render, same, soup, stack, words  # noqa: F401  (ctx: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import srz
-    c = srz.Context(0)
-    c.texture_upload(scenes.TEX_SPOT, scenes.spot_texture())
-    yield c
-    c.close()
-
-
-def render(ctx, frames, flags=abi.FUSED_CLEAR, prefill=None, vis=True):
-    """frames → [n, 4, local_rows, W] uint32 words (prefill: [n, 4, rows, W] float32 the buffer starts with)"""
-    fs = ctx.frameset(frames)
-    out = torch.zeros(fs.out_shape, dtype=torch.float32, device="cuda")
-    if prefill is not None:
-        out.copy_(torch.as_tensor(prefill))
-    s = torch.cuda.current_stream().cuda_stream
-    (fs.render_visibility if vis else fs.render)(out.data_ptr(), fs.out_bytes, flags, s)
-    torch.cuda.synchronize()
-    words = out.cpu().numpy().view(np.uint32)
-    return words, fs
 
 
 def check(ctx, tmp_path, orc, frames, flags=abi.FUSED_CLEAR, prefill=None, what=""):
     """every frame's visibility buffer equals the reference; returns the frameset (its debug counters) and the words"""
     refs = [visref.Reference(tmp_path, f) for f in frames]
-    words, fs = render(ctx, [r.gpu_frame for r in refs], flags, prefill)
+    fs, out = render(ctx, [r.gpu_frame for r in refs], flags, prefill, vis=True)
+    got = words(out)
     for i, r in enumerate(refs):
         init = None if prefill is None else tuple(prefill[i, p, :r.H] for p in range(4))
         exp, _, amb, _, _ = r.expected(orc, init)
         assert amb == 0, f"{what}: {amb} pixels decode ambiguously"
-        got = words[i, :, :r.H]
-        for p, name in enumerate(("z", "id", "alpha", "beta")):
-            bad = got[p] != exp[p]
-            assert not bad.any(), f"{what} frame {i}: plane {name} differs at {int(bad.sum())} pixels, first " \
-                                  f"{np.argwhere(bad)[:3].tolist()}: got {got[p][bad][:3]} want {exp[p][bad][:3]}"
-    return fs, words
+        same(got[i, :, :r.H], exp, f"{what} frame {i} (planes z, id, alpha, beta)")
+    return fs, got
 
 
 @pytest.mark.parametrize("shader", [abi.SHADER_TEXTURE, abi.SHADER_PHONG, abi.SHADER_NORMAL])
 def test_spot_ids_z_alpha_beta(ctx, tmp_path, orc, shader):
     frames = [scenes.config2(a, size=512, shader=shader) for a in (0, 4, 13, 27)]
-    _, words = check(ctx, tmp_path, orc, frames, what=f"spot512 shader {shader}")
+    _, vis = check(ctx, tmp_path, orc, frames, what=f"spot512 shader {shader}")
     # plane 0 is the colour render's plane 0 bit for bit
     refs = [visref.Reference(tmp_path, f) for f in frames]
-    col, _ = render(ctx, [r.gpu_frame for r in refs], vis=False)
-    assert np.array_equal(col[:, 0], words[:, 0])
-    assert (words[:, 1] & 0x80000000).any() and ((words[:, 1] != 0) & ((words[:, 1] & 0x80000000) == 0)).any()  # both classes
+    col = words(render(ctx, [r.gpu_frame for r in refs])[1])
+    assert np.array_equal(col[:, 0], vis[:, 0])
+    assert (vis[:, 1] & 0x80000000).any() and ((vis[:, 1] != 0) & ((vis[:, 1] & 0x80000000) == 0)).any()  # both classes
 
 
 def test_config3_and_config5(ctx, tmp_path, orc):
@@ -74,17 +48,6 @@ def test_soups_with_ties_and_unified(ctx, tmp_path, orc, seed):
     t = soup(seed, 150, 96, 80, zs, big=seed % 3 == 1)
     check(ctx, tmp_path, orc, [frame(t, 96, 80)], what=f"soup {seed}")
     check(ctx, tmp_path, orc, [frame(t, 96, 80, flags=abi.FUSED_CLEAR | abi.UNIFIED)], what=f"soup {seed} unified")
-
-
-def stack(n, w=64, h=64, jitter=0):
-    """n triangles stacked over one 32x32 tile (the list of tile (0,0) has n entries), depths shuffled, some ties"""
-    rng = np.random.default_rng(n + jitter)
-    t = np.zeros(n, abi.TRI_DTYPE)
-    c = rng.uniform(4, 28, (n, 1, 2))
-    t["pos"][:, :, :2] = np.round((c + rng.uniform(-1, 1, (n, 3, 2)) * rng.uniform(6, 30, (n, 1, 1))) * 4) / 4
-    t["pos"][:, :, 2] = rng.choice(np.float32([1, 2, 3, 4, 5, 6, 7, 8]), (n, 3))
-    t["nrm"] = [0, 0, -1]
-    return frame(t, w, h)
 
 
 @pytest.mark.parametrize("n", [100, 300, 700])
@@ -123,9 +86,9 @@ def test_sceneset_ids_are_draw_offset_plus_face(ctx):
     wl = pscenes.spot_bunny_1080p()
     wl.upload_meshes(ctx)
     idx = (0, 11)
-    ws, _ = render(ctx, [wl.scene_frame(i) for i in idx])
+    ws = words(render(ctx, [wl.scene_frame(i) for i in idx], vis=True)[1])
     frames = [wl.frame(i) for i in idx]
-    wf, _ = render(ctx, frames)
+    wf = words(render(ctx, frames, vis=True)[1])
     assert np.array_equal(ws, wf)
     n0 = len(frames[0].tris[0])
     v = visibility.decode(torch.as_tensor(ws.view(np.float32)))
@@ -140,7 +103,7 @@ def test_shards_and_both_exchanges(ctx, tmp_path, world):
     w, h = 200, 270
     frames = [abi.Frame(w, h, scenes.EYE, scenes.LIGHTS, [(abi.SHADER_TEXTURE, scenes.TEX_SPOT,
                         scenes.mesh_stream(scenes.SPOT_OBJ, w, h, float(10 * a), (0, 0, 0), 0.3))], abi.FUSED_CLEAR) for a in (3, 9)]
-    full, _ = render(ctx, frames)
+    full = words(render(ctx, frames, vis=True)[1])
     s = torch.cuda.current_stream().cuda_stream
     ctxs, sets, g, msgs = [], [], [], []
     for r in range(world):

@@ -10,12 +10,9 @@ import pytest
 import scenes as oscenes  # tests/scenes.py: oracle-built inputs
 from srz import abi, host
 from srz import scenes as pscenes
+from support import bits
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def test_png_decoder_matches_pil():

@@ -4,22 +4,9 @@ import numpy as np
 import pytest
 
 from srz import abi
+from support import ccw, frame, tri
 
 F32 = np.float32
-
-
-def tri(a, b, c, z=50.0, nrm=(0, 0, -1), uv=((0, 0), (0, 0), (0, 0))):
-    t = np.zeros(1, abi.TRI_DTYPE)
-    za, zb, zc = (z, z, z) if np.isscalar(z) else z
-    t["pos"][0] = [[a[0], a[1], za], [b[0], b[1], zb], [c[0], c[1], zc]]
-    t["nrm"][0] = [nrm] * 3 if np.ndim(nrm) == 1 else nrm
-    t["uv"][0] = uv
-    return t
-
-
-def frame(tris, w=64, h=64, shader=abi.SHADER_NORMAL, eye=(0, 0, 1), lights=(), flags=abi.FUSED_CLEAR, tex=-1, **kw):
-    batches = tris if isinstance(tris, list) else [(shader, tex, tris)]
-    return abi.Frame(w, h, eye, np.asarray(lights, np.float32).reshape(-1, 2, 3), batches, flags, **kw)
 
 
 # ---------------------------------------------------------------------------------------------- matrices (glm)
@@ -112,10 +99,6 @@ def test_nonfinite_vertex_is_dropped(orc):
 
 
 # ---------------------------------------------------------------------------------------------- coverage
-def ccw(a, b, c, **kw):  # helper: a winding that survives the cull for eye=(0,0,1)
-    return tri(a, c, b, **kw)
-
-
 def test_pixels_on_an_edge_are_not_covered_in_either_class(orc):
     # V class: legs of 32 → the area term is -1024, its reciprocal and every barycentric are exact in binary32, so the
     # strict compares (0 < a,b,c < 1) exclude exactly the on-edge pixels.  bbox x 10..42 = 33 columns → V for x < 42.

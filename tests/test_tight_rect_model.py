@@ -8,7 +8,7 @@ import pytest
 
 import scenes  # noqa: F401  (sys.path)
 from srz import abi
-from test_oracle_kat import frame
+from support import frame
 
 F = np.float32
 TILE = 32
@@ -77,7 +77,7 @@ def walked_rect(p, tx, ty, W, H):
 
 
 def shapes(rng, n, W, H):
-    """the adversarial families of tests/test_gpu_raster_paths.py, one triangle each"""
+    """the adversarial families of support.adversarial_tris, one triangle each"""
     kind = rng.integers(0, 9, n)
     c = rng.uniform([0, 0], [W, H], (n, 2))
     ang = rng.uniform(0, 2 * np.pi, n)

@@ -11,8 +11,7 @@ import torch
 import scenes
 import visref
 from srz import abi
-from test_gpu_raster_paths import soup
-from test_oracle_kat import frame
+from support import frame, soup
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 

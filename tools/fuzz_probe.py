@@ -6,12 +6,12 @@ import torch
 import scenes, srz
 from oracle import oracle
 from srz import abi
-import test_gpu_frameset as T
+from support import random_frame
 seed, fi = int(sys.argv[1]), int(sys.argv[2])
 rng = np.random.default_rng(1000 + seed)
 w, h = [(64, 64), (200, 120), (97, 131), (256, 96), (33, 290), (128, 128), (320, 200), (70, 70)][seed % 8]
 flags = abi.FUSED_CLEAR | (abi.UNIFIED if seed % 3 == 2 else 0)
-frames = [T._random_frame(rng, w, h, int(rng.integers(1, 400)), flags) for _ in range(int(rng.integers(2, 12)))]
+frames = [random_frame(rng, w, h, int(rng.integers(1, 400)), flags) for _ in range(int(rng.integers(2, 12)))]
 oracle.texture_set(0, scenes.spot_texture())
 ctx = srz.Context(0)
 ctx.texture_upload(0, scenes.spot_texture())
