@@ -338,6 +338,13 @@ static inline int32_t cvtps_epi32(float f) {
   return (int32_t)lrintf(f);
 }
 
+/* (int)f of the reference's x86 build (cvttss2si): truncation; NaN and everything outside int32 -> 0x80000000.  Written out,
+ * because the plain C cast is undefined there and other targets convert a NaN to 0 */
+static inline int32_t cvttss_si32(float f) {
+  if (!(f >= -2147483648.0f && f < 2147483648.0f)) return INT32_MIN;
+  return (int32_t)f;
+}
+
 /* BlinnPhong<__m256> (include/shader/Shader.hpp:104-229), one light */
 static void v_blinn_phong(const float n[3], const float ka[3], const float kd[3], const float ks[3],
                           const float cam[3], const srz_light *L, const float P[3], float p, float out[3]) {
@@ -400,7 +407,7 @@ static void v_shade(const orc_shade_ctx *sc, const float P[3], const float n[3],
 static void s_texel(const orc_tex *tex, float u, float v, float out[3]) {
   float cu = std_clamp(u, 0.0f, 1.0f), cv = std_clamp(v, 0.0f, 1.0f); /* glm::clamp = min(max(x,lo),hi) — same for non-NaN */
   float fx = cu * (float)tex->w, fy = cv * (float)tex->h;
-  int x = (int)fx, y = (int)fy; /* truncation */
+  int x = cvttss_si32(fx), y = cvttss_si32(fy); /* truncation; a NaN coordinate -> INT_MIN -> black below */
   if (x < 0 || x >= tex->w || y < 0 || y >= tex->h) {
     out[0] = out[1] = out[2] = 0.0f; /* u or v == 1.0 → black */
     return;

@@ -387,6 +387,12 @@ __device__ __forceinline__ int32_t cvt_rne_i32(float f) {
   if (!(f >= -2147483648.0f && f < 2147483648.0f)) return INT32_MIN;
   return (int32_t)__builtin_rintf(f);
 }
+// (int)f as x86 has it (cvttss2si, the reference's build): truncation; NaN and everything outside int32 give INT32_MIN.  The
+// device's own conversion saturates and turns a NaN into 0 — texel (0, 0) where the reference's index check says "black"
+__device__ __forceinline__ int32_t cvt_trunc_i32(float f) {
+  if (!(f >= -2147483648.0f && f < 2147483648.0f)) return INT32_MIN;
+  return (int32_t)f;
+}
 
 // ---- per-triangle constants used by both the coverage test and the shader -----------------------------------
 struct TriXY {
@@ -1119,7 +1125,7 @@ template <class M>
 __device__ __forceinline__ void s_texel(M &m, const ShadeDesc &sd, float u, float v, float &o0, float &o1, float &o2) {
   float cu = std_clamp(u, 0.0f, 1.0f), cv = std_clamp(v, 0.0f, 1.0f);
   float fx = cu * (float)sd.tw, fy = cv * (float)sd.th;
-  int x = (int)fx, y = (int)fy;
+  int x = cvt_trunc_i32(fx), y = cvt_trunc_i32(fy);
   if (x < 0 || x >= sd.tw || y < 0 || y >= sd.th) {
     o0 = o1 = o2 = 0.0f;
     return;
@@ -1183,7 +1189,7 @@ __device__ __forceinline__ void s_blinn_phong_combine(const FrameK &K, const SRZ
 __device__ __forceinline__ uint32_t s_texel_issue(const ShadeDesc &sd, float u, float v, bool &inside) {
   float cu = std_clamp(u, 0.0f, 1.0f), cv = std_clamp(v, 0.0f, 1.0f);
   float fx = cu * (float)sd.tw, fy = cv * (float)sd.th;
-  int x = (int)fx, y = (int)fy;
+  int x = cvt_trunc_i32(fx), y = cvt_trunc_i32(fy);
   inside = !(x < 0 || x >= sd.tw || y < 0 || y >= sd.th);
   const int xs = min(max(x, 0), sd.tw - 1), ys = min(max(y, 0), sd.th - 1);
   return sd.tex[(size_t)ys * sd.tw + xs];

@@ -2,7 +2,11 @@
  * shader type incl. BUMP / DISPLACEMENT on a 3 x 5 texture, 0..5 lights, triangles that are degenerate, far off screen, huge,
  * non-finite, exactly on pixel centres.  Built by `make -C oracle asan`, run by tests/test_host_fuzz.py.  The oracle is test
  * infrastructure; this only checks that the checker itself reads and writes inside its buffers.
- *   oracle_asan <frames> <seed>     prints "frames=<n> visible=<sum>" and exits 0 */
+ *   oracle_asan <frames> <seed>     prints "frames=<n> visible=<sum>" and exits 0
+ *   oracle_asan --file <path>       the same for frames a test wrote (tests/support.py dump_frames: the hostile shading inputs of
+ *                                   tests/test_oracle_shading_edges.py), little-endian: "SRZF", u32 textures, per texture i32 slot, w, h,
+ *                                   row_stride + row_stride * h bytes; u32 frames, per frame i32 w, h, f32 eye[3] ka[3] ks[3] p kh kn,
+ *                                   u32 lights, batches, flags, the lights (6 f32 each), per batch i32 shader, tex_id, u32 n + n srz_tri */
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -35,7 +39,89 @@ static float coord(int size) {
   }
 }
 
+static void need(FILE *in, void *dst, size_t n) {
+  if (n && fread(dst, 1, n, in) != n) {
+    fprintf(stderr, "oracle_asan: short file\n");
+    exit(2);
+  }
+}
+
+static void bad_file(const char *what) {
+  fprintf(stderr, "oracle_asan: bad file (%s)\n", what);
+  exit(2);
+}
+static void *must(void *p) {
+  if (!p) bad_file("out of memory");
+  return p;
+}
+
+static int run_file(const char *path) {
+  FILE *in = fopen(path, "rb");
+  if (!in) return 2;
+  char magic[4];
+  uint32_t n_tex, n_frames;
+  need(in, magic, 4), need(in, &n_tex, 4);
+  if (memcmp(magic, "SRZF", 4) != 0 || n_tex > 64) bad_file("header");
+  for (uint32_t i = 0; i < n_tex; ++i) {
+    int32_t q[4];
+    need(in, q, sizeof q);
+    if (q[1] < 1 || q[1] > 4096 || q[2] < 1 || q[2] > 4096 || q[3] < 3 * q[1] || q[3] > 3 * 4096 + 4096) bad_file("texture size");
+    uint8_t *px = (uint8_t *)must(malloc((size_t)q[3] * q[2])); /* exactly row_stride * h bytes */
+    need(in, px, (size_t)q[3] * q[2]);
+    int rc = orc_texture_set(q[0], px, q[1], q[2], q[3]);
+    free(px);
+    if (rc != SRZ_OK) bad_file("texture refused");
+  }
+  need(in, &n_frames, 4);
+  unsigned long long visible = 0;
+  for (uint32_t f = 0; f < n_frames; ++f) {
+    srz_frame fr;
+    memset(&fr, 0, sizeof fr);
+    int32_t wh[2];
+    float k[12];
+    uint32_t u[3];
+    need(in, wh, sizeof wh), need(in, k, sizeof k), need(in, u, sizeof u);
+    if (wh[0] < 1 || wh[0] > 4096 || wh[1] < 1 || wh[1] > 4096 || u[0] > 64 || u[1] > 64) bad_file("frame size or counts");
+    fr.width = wh[0], fr.height = wh[1];
+    memcpy(fr.eye, k, 12), memcpy(fr.ka, k + 3, 12), memcpy(fr.ks, k + 6, 12);
+    fr.p = k[9], fr.kh = k[10], fr.kn = k[11];
+    fr.n_lights = u[0], fr.n_batches = u[1], fr.flags = u[2];
+    srz_light *lights = (srz_light *)must(malloc(sizeof(srz_light) * (u[0] ? u[0] : 1)));
+    need(in, lights, sizeof(srz_light) * u[0]);
+    srz_batch *batches = (srz_batch *)must(calloc(u[1] ? u[1] : 1, sizeof(srz_batch)));
+    for (uint32_t b = 0; b < u[1]; ++b) {
+      int32_t st2[2];
+      uint32_t n;
+      need(in, st2, sizeof st2), need(in, &n, 4);
+      if (n > (1u << 20)) bad_file("triangle count");
+      srz_tri *t = (srz_tri *)must(malloc(sizeof(srz_tri) * (n ? n : 1)));
+      need(in, t, sizeof(srz_tri) * n);
+      batches[b].shader = st2[0], batches[b].tex_id = st2[1], batches[b].n_tris = n, batches[b].tris = t;
+    }
+    fr.lights = lights, fr.batches = batches;
+    const size_t px = (size_t)fr.width * fr.height;
+    float *pl = (float *)must(malloc(sizeof(float) * 4 * px));
+    srz_stats s;
+    int used = 0;
+    int rc = orc_draw(SRZ_PRIMITIVE_TRIANGLES, &fr, pl, pl + px, pl + 2 * px, pl + 3 * px, &s);
+    if (rc == SRZ_OK) visible += s.visible;
+    rc |= orc_draw_omp(&fr, pl, pl + px, pl + 2 * px, pl + 3 * px, 8, &used, 2) < 0;
+    free(pl), free(lights);
+    for (uint32_t b = 0; b < u[1]; ++b) free((void *)batches[b].tris);
+    free(batches);
+    if (rc != SRZ_OK) {
+      fprintf(stderr, "oracle_asan: frame %u returned %d\n", f, rc);
+      fclose(in);
+      return 1;
+    }
+  }
+  fclose(in);
+  printf("frames=%u visible=%llu\n", n_frames, visible);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc > 2 && strcmp(argv[1], "--file") == 0) return run_file(argv[2]);
   const int n_frames = argc > 1 ? atoi(argv[1]) : 40;
   st = 0x2545f4914f6cdd1dull ^ (uint64_t)(argc > 2 ? atoll(argv[2]) : 1);
   uint8_t tex[3 * 5 * 3];

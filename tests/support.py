@@ -174,6 +174,242 @@ def random_frame(rng, w, h, n_tris, flags):
     return abi.Frame(w, h, (0.0, 0.0, float(rng.uniform(0.5, 2.0))), lights, batches, flags, p=float(rng.choice([150.0, 8.0, 2.5])))
 
 
+# ------------------------------------------------------------------------------------------------ hostile shading inputs
+# Tame geometry, hostile values in everything the SHADERS read (uv, normals, lights, eye, ka / ks / kh / kn, the exponent, the
+# textures' shapes).  A fragment's position is (column, row, depth); the tame defaults put the eye and the lights far above the image
+# (depth 200..400, the triangles lie at 5..90 with normals near (0, 0, 1)), so that the diffuse and the specular term are alive.
+HOSTILE_FAMILIES = ("uv-edge", "uv-overflow", "uv-nonfinite", "normal-nonfinite", "light-edge", "eye-edge", "constants", "exponent",
+                    "texture-shape")
+HOSTILE_EXPONENTS = (0.0, 1.0, 2.0, 255.0, 256.0, 257.0, 0.5, 7.5, 4095.5, 4096.0, 4097.0, -1.0, 1e30, float("inf"), float("nan"))
+TEXTURED = (abi.SHADER_TEXTURE, abi.SHADER_BUMP, abi.SHADER_DISPLACEMENT)
+# slot -> (width, height, row_stride): slots away from the ones other modules register in the session's oracle (0, 1, 5..11); the
+# default texture of the hostile frames is the 5 x 7 one
+HOSTILE_TEX = 40
+HOSTILE_TEX_SHAPES = {12: (1, 1, 3), 23: (1, 7, 3), 31: (7, 1, 21), HOSTILE_TEX: (5, 7, 15), 47: (2, 2, 6), 62: (64, 64, 3 * 64 + 13),
+                      63: (5, 7, 15 + 2)}
+_F32 = np.float32
+_NAN, _INF = _F32(np.nan), _F32(np.inf)
+
+
+def hostile_textures():
+    """slot -> ((h, w, 3) uint8 texels, row_stride): no byte is zero (a black pixel can only come from the fetch's out-of-range
+    case), texel (0, 0) is bright; deterministic"""
+    out = {}
+    for slot, (w, h, stride) in sorted(HOSTILE_TEX_SHAPES.items()):
+        t = np.random.default_rng(1000 + slot).integers(24, 256, (h, w, 3)).astype(np.uint8)
+        t[0, 0] = (250, 200, 150)
+        out[slot] = (t, stride)
+    return out
+
+
+def padded_rows(texels, row_stride):
+    """the (h, w, 3) texels as h rows of row_stride bytes, the padding 0xFF (a fetch that ignores the stride reads it)"""
+    h, w, _ = texels.shape
+    buf = np.full((h, row_stride), 0xFF, np.uint8)
+    buf[:, :3 * w] = texels.reshape(h, 3 * w)
+    return buf
+
+
+def register_hostile_textures(orc, ctx=None):
+    """hostile_textures() into the oracle's table and (ctx given) into the context's, each from its padded rows with its row_stride"""
+    for slot, (t, stride) in hostile_textures().items():
+        h, w, _ = t.shape
+        buf = padded_rows(t, stride)
+        assert orc.lib().orc_texture_set(slot, buf.ctypes.data, w, h, stride) == 0
+        if ctx is not None:
+            import srz
+            ctx._check(srz.lib().srz_texture_upload(ctx.h, slot, buf.ctypes.data, w, h, stride))
+
+
+def _hostile_geometry(rng, w, h):
+    """(positions [n, 3, 3], thin [n]): triangle 0 fills the screen at depth 90; then triangles 10..40 pixels wide (8-wide "V" columns
+    and a scalar tail) and triangles narrower than 8 pixels (scalar-tail "S" columns only), all finite, on screen, flat in depth, with
+    the winding that survives the cull for an eye above the image; the last four wound the other way (culled unless the eye is NaN)"""
+    scale = (w * h) / (64.0 * 64.0)
+    n_med, n_thin = int(14 * scale ** 0.5) + 10, int(20 * scale ** 0.5) + 12
+    pos = [np.array([[-8.0, -8.0, 90.0], [-8.0, 2.0 * h + 8.0, 90.0], [2.0 * w + 8.0, -8.0, 90.0]])]
+    for i in range(n_med + 4):
+        c = rng.uniform([10, 10], [w - 10, h - 10])
+        ang = rng.uniform(0, 2 * np.pi) + np.array([0.0, 2.1, 4.2]) + rng.uniform(-0.4, 0.4, 3)
+        r = rng.uniform(6, 20, 3)
+        xy = c + np.stack([np.cos(ang), np.sin(ang)], 1) * r[:, None]
+        pos.append(np.concatenate([np.clip(xy, 0.25, [w - 1.25, h - 1.25]), np.full((3, 1), 30.0 + 0.25 * i)], 1))
+    for i in range(n_thin):
+        x0, y0 = rng.uniform(1, w - 8), rng.uniform(1, h - 26)
+        dx, ln = rng.uniform(0, 5.9, 3), rng.uniform(6, 24)
+        dx[int(rng.integers(0, 3))] = 0.0
+        xy = np.array([[x0 + dx[0], y0], [x0 + dx[1], y0 + ln], [x0 + dx[2], y0 + 0.45 * ln]])
+        pos.append(np.concatenate([xy, np.full((3, 1), 5.0 + 0.25 * i)], 1))
+    pos = np.asarray(pos, np.float32)
+    ab, ac = pos[:, 1, :2] - pos[:, 0, :2], pos[:, 2, :2] - pos[:, 0, :2]
+    swap = (ab[:, 0] * ac[:, 1] - ab[:, 1] * ac[:, 0]) > 0  # kept: cross(B - A, C - A).z < 0 for an eye at z > 0
+    swap[1 + n_med:1 + n_med + 4] ^= True
+    pos[swap] = pos[swap][:, [0, 2, 1]]
+    thin = np.zeros(len(pos), bool)
+    thin[1 + n_med + 4:] = True
+    return pos, thin
+
+
+def _pick(rng, values, shape):
+    return np.asarray(values, np.float32)[rng.integers(0, len(values), shape)]
+
+
+def hostile_shading_frame(seed, family, shader_mix=(abi.SHADER_TEXTURE, abi.SHADER_PHONG), n_lights=2, p=150.0, w=64, h=64,
+                          flags=abi.FUSED_CLEAR, tame=False):
+    """One frame of tame geometry whose SHADING inputs are hostile in the way `family` names (HOSTILE_FAMILIES); numpy only,
+    deterministic in its arguments.  The triangles are dealt round-robin to one batch per entry of shader_mix (texture-shape: one batch
+    per texture slot, the textured shaders of the mix in turn).  Odd seeds of light-edge, eye-edge and constants use non-finite values
+    too, even seeds finite ones only; the exponent family takes its exponent from `p` like every other (HOSTILE_EXPONENTS is the list
+    to cross it with) and arranges normals for cosines near 0 and near 1.  tame=True: the same geometry, batches, lights and seed with
+    the family's hostile values left out (uv inside [0, 1]) — the twin a test compares with.  The frame carries .family and .label:
+    "finite" when every shading input is finite, else "nonfinite" (by the INPUTS, whatever the interpolation makes of them)."""
+    assert family in HOSTILE_FAMILIES, family
+    rng = np.random.default_rng([seed, HOSTILE_FAMILIES.index(family)])
+    pos, thin = _hostile_geometry(np.random.default_rng([seed, 77]), w, h)  # (the geometry depends on the seed alone)
+    n = len(pos)
+    t = np.zeros(n, abi.TRI_DTYPE)
+    t["pos"] = pos
+    nn = np.array([0.0, 0.0, 1.0]) + rng.normal(0, 0.25, (n, 3, 3))
+    t["nrm"] = nn / np.linalg.norm(nn, axis=2, keepdims=True)
+    t["uv"] = rng.uniform(0.05, 0.95, (n, 3, 2))
+    s = w / 64.0
+    eye = np.array([w / 2.0, h / 2.0, 300.0], np.float32)
+    L = np.zeros((5, 2, 3), np.float32)
+    L[:, 0] = np.array([[-20.0, -15.0, 300.0], [89.0, 10.0, 250.0], [-12.0, 85.0, 400.0], [80.0, 90.0, 220.0], [32.0, -30.0, 350.0]]) * [s, s, 1.0]
+    L[:, 1] = (np.array([14.0, 9.0, 11.0, 7.0, 8.0]) * s)[:, None]
+    if seed % 3 == 1:
+        L[:, 1] *= np.array([0.6, 1.0, 1.3], np.float32)  # not grey
+    L = L[:n_lights].copy()
+    ka, ks, kh, kn = list(abi.DEFAULT_KA), list(abi.DEFAULT_KS), abi.DEFAULT_KH, abi.DEFAULT_KN
+    k = np.arange(n)
+    whole = (k % 3 == 0)[:, None, None]  # every third triangle takes ONE value for its three vertices
+    if tame:
+        pass
+    elif family == "uv-edge":
+        vals = [0.0, 1.0, 1.0 - 2.0 ** -24, -0.0, 1e-40, -0.3, 1.7, 1e6, 0.5]
+        per_tri = _pick(rng, vals, (n, 1, 2))
+        t["uv"] = np.where(whole, per_tri, _pick(rng, vals, (n, 3, 2)))
+        t["uv"][k % 6 == 1, :, 1] = 0.5  # (some with a tame v, so that u alone decides)
+    elif family == "uv-overflow":
+        big = _pick(rng, [3e38, -3e38], (n, 3, 2))
+        t["uv"] = np.where(rng.random((n, 3, 2)) < 0.6, big, t["uv"])
+    elif family == "uv-nonfinite":
+        bad = _pick(rng, [np.nan, np.inf, -np.inf], (n, 3, 2))
+        count = 1 + k % 3  # one, two or three vertices
+        hit = (np.arange(3)[None, :] < count[:, None])[:, :, None] & (rng.random((n, 1, 2)) < 0.7)
+        t["uv"] = np.where(hit, bad, t["uv"])
+    elif family == "normal-nonfinite":
+        kinds = np.array([[np.nan, 0.3, 1.0], [np.inf, 0.0, 1.0], [0.2, -np.inf, 1.0], [1e30, 1e-30, 1.0], [1e20, 1e20, 1e20],
+                          [1e-30, 1e-30, 1e-30], [0.0, 0.0, 0.0], [-1e30, 1e30, 1e-38], [np.inf, np.inf, -np.inf]], np.float32)
+        choice = kinds[rng.integers(0, len(kinds), (n, 3))]
+        hit = (rng.random((n, 3)) < 0.6)[:, :, None]
+        t["nrm"] = np.where(hit, choice, t["nrm"])
+    elif family == "light-edge":
+        far = pos[1, 0]  # a vertex of a triangle: the light ON a fragment's (x, y)
+        finite_pos = [[round(w / 2.0), round(h / 2.0), 200.0], list(eye), [w / 2.0, h / 2.0, -100.0], [1e30, 1e30, 1e30],
+                      [float(round(far[0])), float(round(far[1])), 40.0], [-1e30, h / 2.0, 50.0]]
+        wild_pos = [[np.nan, 10.0, 100.0], [np.inf, 10.0, 100.0], [10.0, -np.inf, np.inf], [w / 2.0, h / 2.0, np.nan]]
+        finite_I = [[0, 0, 0], [-5, -5, -5], [1e-40, 1e-40, 1e-40], [1e30, 1e30, 1e30], [12, 12, 12], [6, 12, 18], [-3, 8, 1e30], [0.0, -0.0, 0.0]]
+        wild_I = [[np.inf, np.inf, np.inf], [np.nan, np.nan, np.nan], [5, np.nan, 5], [np.inf, 3, -np.inf]]
+        pp, ii = (finite_pos, finite_I) if seed % 2 == 0 else (finite_pos + wild_pos, finite_I + wild_I)
+        for l in range(n_lights):
+            if (seed + l) % 4 != 3:  # (one light in four keeps a tame position, one in five a tame intensity)
+                L[l, 0] = pp[(seed // 2 * 3 + 5 * l) % len(pp)]
+            if (seed + l) % 5 != 4:
+                L[l, 1] = ii[(seed // 2 * 5 + 3 * l) % len(ii)]
+        if seed % 2 and n_lights and np.isfinite(L).all():  # (an odd seed always has a non-finite value: in the LAST light)
+            if seed % 4 == 1:
+                L[-1, 0] = wild_pos[(seed // 4) % len(wild_pos)]
+            else:
+                L[-1, 1] = wild_I[(seed // 4) % len(wild_I)]
+    elif family == "eye-edge":
+        v = pos[2, 1]
+        eyes = [v, [np.nan, 0.0, 1.0], [w / 2.0, h / 2.0, 0.0], [0.0, np.inf, 300.0], pos[len(pos) - 3, 0], [w / 2.0, h / 2.0, np.nan],
+                [1e30, -1e30, 1e30], [np.inf, np.inf, np.inf]]
+        eye = np.asarray(eyes[(seed % 2) + 2 * ((seed // 2) % 4)], np.float32)  # even seeds: the finite ones
+    elif family == "constants":
+        fin = [[-0.5, -0.5, -0.5], [0, 0, 0], [3, 3, 3], [0.005, 0.02, 0.005], [-0.1, 2.0, 0.3], [1e30, 1e30, 1e30], [1e-40, 0, -0.0]]
+        wild = [[np.nan, np.nan, np.nan], [np.inf, np.inf, np.inf], [0.1, np.nan, 0.1], [-np.inf, 0.5, np.inf]]
+        hs_fin, hs_wild = [0.0, -0.2, 1e30, 5.0, -1e30, 1e-40], [np.nan, np.inf, -np.inf]
+        kk, hh = (fin, hs_fin) if seed % 2 == 0 else (fin + wild, hs_fin + hs_wild)
+        j = seed // 2
+        ka, ks = kk[(3 * j) % len(kk)], kk[(5 * j + 2) % len(kk)]
+        if j % 3 == 1:
+            ka = list(abi.DEFAULT_KA)  # (one of the two stays tame in a third of the seeds)
+        if j % 3 == 2:
+            ks = list(abi.DEFAULT_KS)
+        kh, kn = hh[(2 * j) % len(hh)], hh[(3 * j + 1) % len(hh)]
+        if seed % 2 and np.isfinite(np.float32(list(ka) + list(ks) + [kh, kn])).all():  # (an odd seed always has a non-finite value)
+            ks = wild[j % len(wild)]
+    elif family == "exponent":
+        # the half-vector is (0, 0, 1) within a few degrees everywhere (eye and lights far above the image): normals near it give
+        # cosAlpha near 1, normals near the image plane give cosAlpha near 0 (some just below: clamped to exactly 0)
+        L[:, 0] = np.array([w / 2.0 + 0.37, h / 2.0 + 0.21, 3000.0], np.float32) + np.arange(n_lights, dtype=np.float32)[:, None] * _F32(7.0)
+        eye = np.array([w / 2.0 + 3.0, h / 2.0 - 2.0, 3000.0], np.float32)
+        flat = np.array([1.0, 0.3, 0.0]) + rng.normal(0, 0.02, (n, 3, 3))
+        nn = np.where((k % 2 == 1)[:, None, None], flat, np.array([0.0, 0.0, 1.0]) + rng.normal(0, 0.03, (n, 3, 3)))
+        t["nrm"] = nn / np.linalg.norm(nn, axis=2, keepdims=True)
+    if family == "texture-shape":
+        slots = sorted(HOSTILE_TEX_SHAPES)
+        textured = [sh for sh in shader_mix if sh in TEXTURED] or [abi.SHADER_TEXTURE]
+        plan = [(textured[(b + seed) % len(textured)], slots[(b + seed) % len(slots)]) for b in range(len(slots))]
+        if not tame:  # uv over the whole texture and its borders: every texel of the small ones, both ends of the padded rows
+            t["uv"] = np.where(whole, _pick(rng, [0.0, 0.999, 0.5, 1.0], (n, 1, 2)), rng.uniform(-0.05, 1.05, (n, 3, 2)))
+    else:
+        plan = [(sh, HOSTILE_TEX if sh in TEXTURED else -1) for sh in shader_mix]
+    batches = [(sh, slot, t[b::len(plan)]) for b, (sh, slot) in enumerate(plan)]
+    f = abi.Frame(w, h, tuple(float(x) for x in eye), L, batches, flags, ka=ka, ks=ks, p=p, kh=kh, kn=kn)
+    f.family = family
+    f.label = hostile_label(f)
+    return f
+
+
+def hostile_label(f):
+    """"finite" when every value the shaders read from frame f is finite (uv, normals, lights, eye, ka, ks, p, kh, kn)"""
+    parts = [np.float32([f.c.p, f.c.kh, f.c.kn]), np.float32(list(f.c.eye) + list(f.c.ka) + list(f.c.ks)), f.lights["pos"], f.lights["intensity"]]
+    parts += [x[key] for x in f.tris for key in ("uv", "nrm")]
+    return "finite" if all(np.isfinite(x).all() for x in parts) else "nonfinite"
+
+
+MIX_PLAIN = (abi.SHADER_TEXTURE, abi.SHADER_PHONG, abi.SHADER_NORMAL)
+MIX_ALL = (abi.SHADER_TEXTURE, abi.SHADER_PHONG, abi.SHADER_BUMP, abi.SHADER_DISPLACEMENT, abi.SHADER_NORMAL)
+# families whose every frame / whose even seeds are labelled finite (the others: never)
+HOSTILE_ALWAYS_FINITE = ("uv-edge", "uv-overflow", "exponent", "texture-shape")
+HOSTILE_EVEN_FINITE = ("light-edge", "eye-edge", "constants")
+
+
+def tolerance_frames(family, size=64):
+    """the frames the tolerance mode is held to (tests/test_gpu_shading_edges.py) -> [(name, frame, bounded)]: four seeds x {a mix the
+    ApproxMath builds shade, a mix with a BUMP batch: the exact generic build}.  bounded = the frame is labelled finite and (pinned on
+    the CPU by tests/test_oracle_shading_edges.py) the oracle's pre-truncation probe is finite at every covered pixel: the frames on
+    which check_approx's value bounds are asserted"""
+    out = []
+    for seed in (0, 1, 2, 3):
+        for mix in (MIX_PLAIN, MIX_ALL):
+            p = (150.0, 32.0, 0.0, 1.0)[seed] if family == "exponent" else (150.0, 7.5)[seed % 2]
+            f = hostile_shading_frame(seed, family, mix, 1 + seed % 4, p, size, size)
+            bounded = family in HOSTILE_ALWAYS_FINITE or (family in HOSTILE_EVEN_FINITE and seed % 2 == 0)
+            out.append((f"{family} seed {seed} {'plain' if mix is MIX_PLAIN else 'all'}", f, bounded))
+    return out
+
+
+def dump_frames(path, frames):
+    """hostile_textures() and the frames as the file tests/cpp/oracle_asan_main.c reads (its header states the layout)"""
+    import struct
+    with open(path, "wb") as o:
+        tex = hostile_textures()
+        o.write(b"SRZF" + struct.pack("<I", len(tex)))
+        for slot, (t, stride) in tex.items():
+            o.write(struct.pack("<4i", slot, t.shape[1], t.shape[0], stride) + padded_rows(t, stride).tobytes())
+        o.write(struct.pack("<I", len(frames)))
+        for f in frames:
+            c = f.c
+            o.write(struct.pack("<2i12f3I", c.width, c.height, *c.eye, *c.ka, *c.ks, c.p, c.kh, c.kn, c.n_lights, c.n_batches, c.flags))
+            o.write(f.lights.tobytes())
+            for b, t in enumerate(f.tris):
+                o.write(struct.pack("<2iI", f._batches[b].shader, f._batches[b].tex_id, len(t)) + t.tobytes())
+
+
 # ------------------------------------------------------------------------------------------------ comparison
 def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
@@ -199,7 +435,8 @@ def compare(gpu, ref, name):
     n_cov = max(1, int(np.isfinite(rz).sum()))
     z_same = np.array_equal(bits(gz), bits(rz))
     dc = np.maximum.reduce([np.abs(g.astype(np.float64) - r.astype(np.float64)) for g, r in zip(gpu[1:], ref[1:])])
-    dc = np.nan_to_num(dc, nan=0.0) + np.where(np.isnan(gpu[1]) != np.isnan(ref[1]), 1e9, 0.0)
+    nan_differs = np.logical_or.reduce([np.isnan(g) != np.isnan(r) for g, r in zip(gpu[1:], ref[1:])])  # (in ANY colour plane)
+    dc = np.nan_to_num(dc, nan=0.0) + np.where(nan_differs, 1e9, 0.0)
     n_diff = int(sum((bits(g) != bits(r)).sum() for g, r in zip(gpu[1:], ref[1:])))
     print(f"[{name}] covered={n_cov} z_bit_identical={z_same} colour_values_not_bit_identical={n_diff} max_dcolour={dc.max():.3g}")
     assert z_same, f"{name}: z-buffer is not bit-identical"
@@ -227,6 +464,8 @@ def check_approx(gpu, gst, ref, rst, pre, s_class, name):
     for c in (1, 2, 3):
         g, r, p = gpu[c].astype(np.float64), ref[c].astype(np.float64), pre[c].astype(np.float64)
         assert np.array_equal(g[~cov], r[~cov]), f"{name}: uncovered pixels differ"
+        # (a NaN on one side only makes d a NaN, and every `d > bound` below false: NaN-ness is compared on its own)
+        assert np.array_equal(np.isnan(g), np.isnan(r)), f"{name}: channel {c}: {int((np.isnan(g) != np.isnan(r)).sum())} pixels are NaN on one side only"
         d = np.abs(g - r)
         v = cov & ~s_class
         worst_v = max(worst_v, float(d[v].max()) if v.any() else 0.0)
