@@ -1302,8 +1302,12 @@ __device__ __forceinline__ void s_shade(M &m, const FrameK &K, const ShadeDesc &
 //      the part of a step in which the memory system is what everything waits for (NOTEBOOK r6 §2).
 //    The S class: the pixel lies in the scalar-tail ("S") columns of its owner's bounding box.
 // 3. The tile's RECTANGLE in the framebuffer: tile_rect().
-// k_shade reads all three inline, in the same format: the helpers below, put into its tile loop, change its schedule (one form made
-// the early owner-id load wait at once), so its statements stay as they are measured.
+// HELPER — k_shade's inline copy of it (any call in its tile loop moves its schedule; each copy names its helper; a fix goes into both):
+//    work_decode, id_none / id_sbit, ids_load_raw, ids_unpack4 — shade_tile: head, step 1 and the classification
+//    tile_rect — shade_tile, behind the FrameDesc loads (and k_shade_vis's shade_tile, head)
+//    frame_k — class_pass, head
+//    shade_bary_v / _s — the second half of shade_pixel_v / _s
+// (copies without a helper: k_shade_vis's compaction and batch-by-batch loop, of k_shade's; k_visibility's o[3][4], of quad_load / quad_at)
 constexpr uint32_t WORK_LP = 1u << 20, WORK_LP8 = 1u << 21;
 constexpr uint32_t S_CLASS_BIT = 0x80000000u;
 constexpr uint32_t PIX_SLOT = TILE * TILE, PIX_BITS = 10, PIX_MASK = PIX_SLOT - 1u;
@@ -1385,6 +1389,14 @@ __device__ __forceinline__ TileRect tile_rect(A &a, const SRZ_CAS FrameDesc *fd,
   return r;
 }
 
+// The frame's shading constants (scalar loads from one hot line; `lights`: the set's, before FrameDesc::light_off)
+__device__ __forceinline__ FrameK frame_k(const SRZ_CAS FrameDesc *fd, const SRZ_CAS srz_light *lights) {
+  return {{fd->eye[0], fd->eye[1], fd->eye[2]}, {fd->ka[0], fd->ka[1], fd->ka[2]}, {fd->ks[0], fd->ks[1], fd->ks[2]}, fd->p, fd->kh, fd->kn,
+          fd->n_lights, (fd->flags & FD_GREY) != 0u, lights + fd->light_off};
+}
+// A triangle's nine position floats (ax ay z0 bx by z1 cx cy z2) → TriXY in its field order, tri_consts still to come (k_shade: unpack_pos)
+template <class P> __device__ __forceinline__ TriXY tri_xy(const P *q) { return {q[0], q[1], q[3], q[4], q[6], q[7], q[2], q[5], q[8]}; }
+
 // Everything the shader needs about the owner triangle of one pixel, fetched in ONE round trip (7 independent loads)
 struct TriFetch {
   f32x4 q0, q1, q2, q3, q4, q5;
@@ -1427,9 +1439,7 @@ __device__ __forceinline__ void late_fetch(TriFetch &f, const f32x4 *late, float
   }
 }
 // The shading from the barycentrics on, given the owner's normals and texture coordinates (a's attributes): k_shade_vis's per-pixel work
-// (α, β and z from a visibility buffer).  These are the statements of the second half of shade_pixel_v / _s below, operation for
-// operation — keep the two in step.  shade_pixel_v / _s do not call them: with that call in place every k_shade build kept its registers
-// but changed its schedule (±1..11 instructions) and the bench headline came out ~0.5 % lower, so k_shade's statements stay as measured.
+// (α, β and z from a visibility buffer).  The second half of shade_pixel_v / _s below is k_shade's inline copy, operation for operation.
 template <class M, int SH, int NL>
 __device__ __forceinline__ void shade_bary_v(M &m, const FrameK &K, const ShadeDesc &sd, const TriAttr &a, float alpha, float beta,
                                              float gamma, float fx, float fy, float zz, float &r0, float &r1, float &r2) {
@@ -1509,17 +1519,13 @@ __device__ __forceinline__ void shade_pixel_s(M &m, const FrameK &K, const Shade
 // instruction-count probes (make asm-probe): the two per-pixel shading paths in isolation
 __global__ void probe_v(RenderArgs a, float *o) {
   const SRZ_CAS FrameDesc *fd = as_const(a.frames);
-  FrameK K;
-  K.eye[0] = fd->eye[0], K.eye[1] = fd->eye[1], K.eye[2] = fd->eye[2];
-  K.ka[0] = fd->ka[0], K.ka[1] = fd->ka[1], K.ka[2] = fd->ka[2];
-  K.ks[0] = fd->ks[0], K.ks[1] = fd->ks[1], K.ks[2] = fd->ks[2];
-  K.p = 150.0f, K.kh = fd->kh, K.kn = fd->kn, K.n_lights = 2; // constants: the static count is the dynamic path
+  FrameK K = frame_k(fd, as_const(a.lights));
+  K.p = 150.0f, K.n_lights = 2; // constants: the static count is the dynamic path
 #ifdef SRZ_PROBE_GREY
   K.grey = true;
 #else
   K.grey = false;
 #endif
-  K.lights = as_const(a.lights);
   TriFetch tf;
   fetch_tri(as_const(a.tris), as_const(a.tri_batch), threadIdx.x, tf);
   ShadeDesc sd;
@@ -2376,7 +2382,7 @@ void k_shade(RenderArgs a) {
     const uint32_t f = x.x, lb = x.y & 1023u, tx = (x.y >> 10) & 1023u;
     const uint32_t tile_slot = f * tpf + lb * ap->tiles_x + tx;
     uint4 id_raw = make_uint4(0u, 0u, 0u, 0u);
-    {
+    { // (inline copy of ids_load_raw; `none` / `sbit` below: of id_none / id_sbit; by_lp, lp8, f, lb, tx above: of work_decode)
       const uint32_t *slot = ap->vis + (size_t)tile_slot * PIX_SLOT;
       if (lp8) {
         id_raw.x = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(slot) + p0);
@@ -2409,7 +2415,7 @@ void k_shade(RenderArgs a) {
     const SRZ_CAS ShadeDescG *sdesc = as_const(ap->sdesc) + batch_off;
     const bool sd_staged = fd->n_batches <= STAGE_SD; // workgroup-uniform
 
-    const int band = band_of((int)lb, ap->shard_rank, ap->shard_world);
+    const int band = band_of((int)lb, ap->shard_rank, ap->shard_world); // (inline copy of tile_rect, to out0)
     const int tx0 = (int)tx * TILE, ty0 = band * BAND;
     const int tx1 = min(tx0 + TILE, W) - 1, ty1 = min(ty0 + BAND, H) - 1;
     const size_t plane = (size_t)ap->local_rows * (size_t)W;
@@ -2454,7 +2460,7 @@ void k_shade(RenderArgs a) {
     asm volatile("" : "+v"(id_raw.x), "+v"(id_raw.y), "+v"(ti[0])); // (the wait for the owner ids and the first indices lands here)
     SRZ_STAMP(0) // tile start → owner ids + list indices here
 #endif
-    uint32_t idk[4] = {id_raw.x, id_raw.y, id_raw.z, id_raw.w};
+    uint32_t idk[4] = {id_raw.x, id_raw.y, id_raw.z, id_raw.w}; // (inline copy of ids_unpack4)
     if (lp8)
       idk[0] = id_raw.x & 0xffu, idk[1] = (id_raw.x >> 8) & 0xffu, idk[2] = (id_raw.x >> 16) & 0xffu, idk[3] = id_raw.x >> 24;
     else if (by_lp)
@@ -2528,7 +2534,7 @@ void k_shade(RenderArgs a) {
       constexpr bool isV = decltype(is_v)::value, STAGED = decltype(staged_c)::value;
       bool bad = false;
       // the frame's shading constants are (re)read here, after the IO phase: scalar loads from a hot line, and ~20 SGPRs
-      // fewer alive across the phase that has none to spare
+      // fewer alive across the phase that has none to spare (inline copy of frame_k)
       FrameK K;
       K.eye[0] = fd->eye[0], K.eye[1] = fd->eye[1], K.eye[2] = fd->eye[2];
       K.ka[0] = fd->ka[0], K.ka[1] = fd->ka[1], K.ka[2] = fd->ka[2];
@@ -2787,7 +2793,7 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
       const bool in_tile = y <= rc.ty1 && x4 <= rc.tx1;
       const bool full = in_tile && ((W & 3) == 0) && x4 + 3 <= rc.tx1;
       float *gz = rc.out0 + (size_t)ly * W + x4;
-      float o[3][4];
+      float o[3][4]; // (inline copy of quad_load into float4[3] / quad_at: as float4s the staging costs 13 VGPRs and a wave per SIMD)
 #pragma unroll
       for (int k = 0; k < 4; ++k) o[0][k] = o[1][k] = o[2][k] = 0.f;
       if (!fused && in_tile) { // accumulate mode: pixels nobody owns keep what the buffer holds
@@ -2806,13 +2812,11 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
         TriXY t;
         uint32_t idx;
         if (staged) {
-          const float *q = s_pos + pos * TRI_POS_F;
           idx = s_idx[pos];
-          t.ax = q[0], t.ay = q[1], t.z0 = q[2], t.bx = q[3], t.by = q[4], t.z1 = q[5], t.cx = q[6], t.cy = q[7], t.z2 = q[8];
+          t = tri_xy(s_pos + pos * TRI_POS_F);
         } else {
           idx = e.by_lp ? (tlist[pos] & PACK_IDX_MASK) : pos; // (a long list: position → index, then the gather)
-          const SRZ_CAS float *q = tpos + (size_t)idx * a.pos_stride;
-          t.ax = q[0], t.ay = q[1], t.z0 = q[2], t.bx = q[3], t.by = q[4], t.z1 = q[5], t.cx = q[6], t.cy = q[7], t.z2 = q[8];
+          t = tri_xy(tpos + (size_t)idx * a.pos_stride);
         }
         BranchMath m; // (the correctly rounded reciprocal, no flag-and-redo: there is no redo list here)
         tri_consts(m, t);
@@ -2877,7 +2881,7 @@ __global__ __launch_bounds__(256, FASTNL == -4 ? 3 : SRZ_SHADE_MINW) void k_shad
     constexpr int MODE = decltype(mode_c)::value;
     const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
     const uint32_t ff = fd->flags;
-    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
+    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x; // (inline copy of tile_rect, to `plane`)
     const int W = fd->width, H = fd->height;
     const int tx0 = (int)tx * TILE, ty0 = band_of((int)lb, a.shard_rank, a.shard_world) * BAND;
     const int tx1 = min(tx0 + TILE, W) - 1, ty1 = min(ty0 + BAND, H) - 1;
@@ -2962,13 +2966,7 @@ __global__ __launch_bounds__(256, FASTNL == -4 ? 3 : SRZ_SHADE_MINW) void k_shad
         using M = decltype(policy);
         constexpr bool isV = decltype(is_v)::value, GEN = decltype(gen_c)::value;
         bool bad = false;
-        FrameK K;
-        K.eye[0] = fd->eye[0], K.eye[1] = fd->eye[1], K.eye[2] = fd->eye[2];
-        K.ka[0] = fd->ka[0], K.ka[1] = fd->ka[1], K.ka[2] = fd->ka[2];
-        K.ks[0] = fd->ks[0], K.ks[1] = fd->ks[1], K.ks[2] = fd->ks[2];
-        K.p = fd->p, K.kh = fd->kh, K.kn = fd->kn, K.n_lights = fd->n_lights;
-        K.grey = (ff & FD_GREY) != 0u;
-        K.lights = as_const(a.lights) + fd->light_off;
+        const FrameK K = frame_k(fd, as_const(a.lights));
         for (uint32_t c = (uint32_t)wave; c < cV + cS; c += 4) {
           if ((c >= cS) != isV) continue;
           const uint32_t i = (isV ? c - cS : c) * 64 + lane;
@@ -2990,7 +2988,7 @@ __global__ __launch_bounds__(256, FASTNL == -4 ? 3 : SRZ_SHADE_MINW) void k_shad
           M m;
           ShadeDesc sd;
           if constexpr (!GEN) {
-            // batch by batch, the batch's descriptor wave-uniform and one scalar switch on its shader type (k_shade, MODE 0)
+            // batch by batch, the batch's descriptor wave-uniform and one scalar switch on its shader type (inline copy of k_shade's, MODE 0)
             bool todo = true;
             for (unsigned long long tm = __ballot(true); tm != 0ull; tm = __ballot(todo)) {
               const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)tf.batch, __builtin_ctzll(tm));

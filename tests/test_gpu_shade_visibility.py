@@ -224,6 +224,42 @@ def test_in_place(ctx):
     fs.close()
 
 
+def test_width_not_a_multiple_of_4_or_32(ctx):
+    """50 x 37: a partial second tile column and band, no aligned quad in the frame (the ids, z, α, β and the colour of every quad go
+    pixel by pixel, the last quad of a row ends at the frame's edge) — fused, accumulate and in place against the colour render"""
+    w, h = 50, 37
+    t = soup(1, 36, w, h, np.float32([1, 2, 3]))
+    col = check(ctx, [frame(t, w, h)], what="50x37 fused")
+    s = stream()
+    # accumulate (as test_accumulate_mode_and_layering; the frame's own flags without SRZ_FUSED_CLEAR too, they are OR-ed in): colour
+    # render onto B == shade onto B of the visibility render onto (B.z, 0, 0, 0), and B's words stay where nobody owns the pixel
+    fs = ctx.frameset([frame(t, w, h, flags=0)])
+    rng = np.random.default_rng(4)
+    B = rng.uniform(0, 255, fs.out_shape).astype(np.float32)
+    B[:, 0] = rng.uniform(0.5, 4.0, B[:, 0].shape).astype(np.float32)
+    vb = np.zeros_like(B)
+    vb[:, 0] = B[:, 0]
+    acc, vis, out = torch.as_tensor(B).cuda(), torch.as_tensor(vb).cuda(), torch.as_tensor(B).cuda()
+    fs.render(acc.data_ptr(), fs.out_bytes, 0, s)
+    fs.render_visibility(vis.data_ptr(), fs.out_bytes, 0, s)
+    fs.shade_visibility(vis.data_ptr(), out.data_ptr(), fs.out_bytes, 0, s)
+    torch.cuda.synchronize()
+    nobody = words(vis)[:, 1] == 0
+    assert nobody.any() and (~nobody).any() and (~nobody)[:, :, 48:].any()
+    assert np.array_equal(words(out), words(acc))
+    keep = np.broadcast_to(nobody[:, None], B.shape)
+    assert np.array_equal(words(out)[keep], B.view(np.uint32)[keep])
+    assert not np.array_equal(words(out)[:, 1:], B.view(np.uint32)[:, 1:])  # (and the owned ones were shaded)
+    fs.close()
+    fs = ctx.frameset([frame(t, w, h)])  # in place (fused)
+    buf = torch.zeros(fs.out_shape, dtype=torch.float32, device="cuda")
+    fs.render_visibility(buf.data_ptr(), fs.out_bytes, abi.FUSED_CLEAR, s)
+    fs.shade_visibility(buf.data_ptr(), buf.data_ptr(), fs.out_bytes, abi.FUSED_CLEAR, s)
+    torch.cuda.synchronize()
+    assert np.array_equal(words(buf), col)
+    fs.close()
+
+
 @pytest.mark.parametrize("world", [2, 3, 8])
 def test_shards(ctx, world):
     import srz

@@ -79,6 +79,24 @@ def test_accumulate_mode_keeps_what_survives(ctx, tmp_path, orc):
     check(ctx, tmp_path, orc, frames, flags=0, prefill=pre, what="accumulate")
 
 
+def test_width_not_a_multiple_of_4_or_32(ctx, tmp_path, orc):
+    """50 x 37: two tile columns and two bands, the second of each partial, and no aligned quad in the frame (W % 4 != 0) — every quad
+    is read back and written pixel by pixel, up to the frame's edge in the last one of a row.  With SRZ_FUSED_CLEAR, and in accumulate
+    mode over a prefilled buffer, whose words stay where nobody owns the pixel"""
+    w, h = 50, 37
+    t = soup(1, 36, w, h, np.float32([1, 2, 3]))
+    _, fused = check(ctx, tmp_path, orc, [frame(t, w, h)], what="50x37 fused")
+    ids = fused[0, 1, :h]
+    assert (ids[:, 48:] != 0).any() and (ids[32:] != 0).any() and (ids[32:, 32:] != 0).any()  # the partial column, band, corner
+    rng = np.random.default_rng(9)
+    pre = rng.integers(0, 2 ** 32, (1, 4, h, w), dtype=np.uint64).astype(np.uint32).view(np.float32)
+    pre[:, 0] = rng.uniform(0.5, 4.0, (1, h, w)).astype(np.float32)
+    pre[:, 1:] = np.where(np.isnan(pre[:, 1:]), np.float32(7), pre[:, 1:])
+    _, acc = check(ctx, tmp_path, orc, [frame(t, w, h, flags=0)], flags=0, prefill=pre, what="50x37 accumulate")
+    nobody = ids == 0  # (nobody with the clear's depth behind it: nobody in front of the prefill's either)
+    assert nobody.any() and np.array_equal(acc[0, :, :h][:, nobody], pre.view(np.uint32)[0][:, nobody])
+
+
 def test_sceneset_ids_are_draw_offset_plus_face(ctx):
     """the vertex-stage path gives the buffer of a frameset of the host-built stream (spot + bunny: two draws)"""
     from srz import scenes as pscenes
