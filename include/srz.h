@@ -49,6 +49,7 @@ extern "C" {
  *      (additive, same version) shading a visibility buffer srz_frameset_shade_visibility, new shading data for a frameset
  *      srz_frameset_update_shading
  *      (additive, same version) the diagnostic srz_frameset_shade_kinds
+ *      (additive, same version) the G-buffer of a visibility buffer srz_frameset_gbuffer / srz_frameset_gbuffer_bytes, SRZ_GB_*
  */
 #define SRZ_ABI_VERSION 7
 
@@ -286,6 +287,36 @@ int srz_frameset_render_visibility(srz_ctx *ctx, srz_frameset *fs, void *d_out, 
  * runs its vertex stage first, as a render does.  The call files no sample of the side clear's grid measurement. */
 int srz_frameset_shade_visibility(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void *d_out, size_t out_bytes,
                                   uint32_t flags, void *stream);
+/* The G-BUFFER of a visibility buffer: per pixel, the attributes the built-in shaders are handed for its owner — bit for bit what
+ * they consume — so that a shader of the caller's own (a lighting model in torch, a material mask, a denoiser's guide images) need not
+ * restate the two interpolation rules, the two texel fetches and the batch → shader → texture lookup.  `what` names the groups: */
+#define SRZ_GB_NORMAL 1u  /* 3 planes nx, ny, nz */
+#define SRZ_GB_UV     2u  /* 2 planes u, v */
+#define SRZ_GB_BATCH  4u  /* 1 plane uint32 */
+#define SRZ_GB_ALBEDO 8u  /* 3 planes, in the order of the colour planes (plane 0 = texture blue) */
+/* d_vis: a visibility buffer of THIS set on this ctx's shard (srz_frameset_out_bytes); d_out: [frame][plane][local_rows][width], 4-byte
+ * words, the planes of the groups in `what` in the order above, without gaps: srz_frameset_gbuffer_bytes(what) bytes (0 for what == 0 or
+ * an unknown bit).  Band sharding, local_rows, stream semantics, 16-byte alignment of both buffers and asynchrony (no host wait) as
+ * srz_frameset_shade_visibility; a sceneset runs its vertex stage first.  d_out may not overlap d_vis (the layouts differ):
+ * SRZ_E_INVALID, like what == 0, an unknown bit of `what`, a short out_bytes and any bit of `flags` but SRZ_FUSED_CLEAR.
+ * The pass reads the id plane everywhere and alpha / beta where there is an owner; never z, and it needs no pixel coordinate.
+ * Per pixel with an owner (id != 0 and (id & 0x7fffffff) - 1 < the frame's triangle count; class = bit 31 of id; gamma =
+ * 1 - (alpha + beta) for V, (1 - alpha) - beta for S):
+ *   NORMAL  the interpolated, normalised normal as the owner's class hands it to its shader.  V: fma interpolation, then
+ *           NormalSIMD::normalized (a length that is not > 0: (0, 0, 0)); S: products and sums, then glm::normalize (zero length: NaN)
+ *   UV      the raw interpolated u, v of the class (V: fma; S: products and sums), before any scaling or clamping
+ *   BATCH   the owner's batch index within its frame (for a sceneset: its draw) + 1
+ *   ALBEDO  the kd the owner's shader multiplies its lighting by, under the set's CURRENT shading data (srz_frameset_update_shading,
+ *           srz_sceneset_update, texture uploads).  V class, TEXTURE batch: the texel at the round-half-even of the scaled coordinate
+ *           clamped to [0, size - 1], times RN(1/255); S class, TEXTURE / BUMP / DISPLACEMENT batch: the texel at the truncated
+ *           clamped-then-scaled coordinate divided by 255, black outside the texture (u or v == 1, a NaN coordinate); every other
+ *           combination: (1, 1, 1).  Only when ALBEDO is asked for must the textures be uploaded (else SRZ_E_TEXTURE).
+ * Always the exact arithmetic (correctly rounded reciprocal, root and division): SRZ_OPT_APPROX_SHADE has no effect.
+ * Pixels nobody owns (id 0 or out of range): with SRZ_FUSED_CLEAR (frame flags | flags) every requested word is 0; without it the
+ * words are left untouched. */
+size_t srz_frameset_gbuffer_bytes(const srz_ctx *ctx, const srz_frameset *fs, uint32_t what);
+int srz_frameset_gbuffer(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void *d_out, size_t out_bytes, uint32_t what, uint32_t flags,
+                         void *stream);
 /* New SHADING DATA for a set made by srz_frameset_create, its triangles untouched (batches[b].tris is ignored and may be NULL): each
  * frame's eye, ka, ks, p, kh, kn, lights and flags, each batch's shader and tex_id.  The structure must be the set's — frame count, size,
  * light counts, batch counts, n_tris per batch — else SRZ_E_INVALID and the set is unchanged; a sceneset is SRZ_E_INVALID (its shading

@@ -35,6 +35,7 @@ struct TexDesc {
 
 // the flags of srz_frame / srz_scene_frame / a render that the device sees (FrameDesc::flags, RenderArgs::flags_or)
 constexpr uint32_t FRAME_FLAGS = SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER;
+constexpr uint32_t GB_GROUPS = SRZ_GB_NORMAL | SRZ_GB_UV | SRZ_GB_BATCH | SRZ_GB_ALBEDO;
 } // namespace
 
 struct srz_ctx {
@@ -1329,6 +1330,42 @@ int srz_frameset_shade_visibility(srz_ctx *ctx, srz_frameset *fs, const void *d_
   // only itself (as after a visibility render)
   const srz_frameset::ClearTune &ct = fs->clear_tune;
   if (!ctx->env_clear_wgs && ct.d_ctl && !ct.done && fs->max_tiles >= 8192) launch_clear_rebase(ct.d_ctl, s);
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
+size_t srz_frameset_gbuffer_bytes(const srz_ctx *ctx, const srz_frameset *fs, uint32_t what) {
+  if (!fs || what == 0u || (what & ~GB_GROUPS) != 0u) return 0;
+  return (size_t)fs->n_frames * gbuf_planes(what) * fs->local_rows * (size_t)fs->width * sizeof(float);
+}
+
+int srz_frameset_gbuffer(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void *d_out, size_t out_bytes, uint32_t what, uint32_t flags,
+                         void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_gbuffer");
+  if (!fs || !d_vis || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / output");
+  if (what == 0u || (what & ~GB_GROUPS) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": `what` names no group or an unknown one");
+  if ((flags & ~(uint32_t)SRZ_FUSED_CLEAR) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": only SRZ_FUSED_CLEAR is accepted in flags");
+  const size_t need = srz_frameset_gbuffer_bytes(ctx, fs, what), vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
+  if ((((uintptr_t)d_vis | (uintptr_t)d_out) & 15u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
+  const uintptr_t v = (uintptr_t)d_vis, o = (uintptr_t)d_out;
+  if (v < o + need && o < v + vis_bytes) return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the visibility buffer");
+  if (int rc = check_renderable(ctx, fs)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const hipStream_t s = pick_stream(ctx, stream);
+  if (what & SRZ_GB_ALBEDO) // (textures uploaded, batch → shader / texture: nothing else reads them)
+    if (int rc = resolve_shading(ctx, fs, s)) return rc;
+  // a sceneset's triangles are its vertex stage's output (as srz_frameset_shade_visibility)
+  if (fs->d_draws) launch_vertex(fs->d_draws, fs->n_draws, fs->max_faces, fs->d_tris, fs->d_tri_pos, fs->d_frames, nullptr, s);
+  GbufArgs a{};
+  a.frames = fs->d_frames, a.tris = fs->d_tris, a.tri_batch = fs->d_tri_batch, a.sdesc = fs->d_sdesc;
+  a.vis = (const float *)d_vis, a.out = (float *)d_out;
+  a.vis_stride = 4ull * fs->local_rows * (uint64_t)fs->width, a.frame_stride = (uint64_t)gbuf_planes(what) * fs->local_rows * (uint64_t)fs->width;
+  a.local_rows = fs->local_rows, a.tiles_x = fs->tiles_x, a.n_local_bands = fs->n_local_bands, a.n_frames = (uint32_t)fs->n_frames;
+  a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
+  a.flags_or = flags, a.what = what;
+  launch_gbuffer(a, s);
   HIP_TRY(ctx, hipGetLastError());
   return SRZ_OK;
 }

@@ -236,6 +236,25 @@ struct ShadeVisArgs {
 };
 // one launch per build kind the set's frames need (kinds / any_generic / approx as for launch_shade); frames of other kinds are skipped
 void launch_shade_vis(const ShadeVisArgs &a, uint32_t kinds, bool any_generic, bool approx, hipStream_t s);
+// srz_frameset_gbuffer: the attribute planes of a visibility buffer (k_gbuffer).  vis in the layout of srz_frameset_render, out =
+// [frame][planes of `what`][local_rows][width]; `out` / `frame_stride` / `local_rows` / the shard are what tile_rect reads
+struct GbufArgs {
+  const FrameDesc *frames;
+  const srz_tri *tris;
+  const uint16_t *tri_batch;
+  const ShadeDescG *sdesc; // read only when `what` has SRZ_GB_ALBEDO
+  const float *vis;
+  float *out;
+  uint64_t vis_stride;     // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride;   // floats per frame in out = planes * local_rows * width
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or, what;
+};
+__host__ __device__ constexpr uint32_t gbuf_planes(uint32_t what) {
+  return ((what & SRZ_GB_NORMAL) ? 3u : 0u) + ((what & SRZ_GB_UV) ? 2u : 0u) + ((what & SRZ_GB_BATCH) ? 1u : 0u) + ((what & SRZ_GB_ALBEDO) ? 3u : 0u);
+}
+void launch_gbuffer(const GbufArgs &a, hipStream_t s);
 void launch_resolve8(const float *planes, uint8_t *out, uint32_t n_frames, uint32_t rows, uint32_t W, uint64_t frame_stride,
                      hipStream_t s);
 void launch_deinterleave(const void *gathered, void *full, uint32_t world, uint32_t n_fp, uint32_t bands_per_rank, uint32_t row_bytes,

@@ -1305,6 +1305,8 @@ __device__ __forceinline__ void s_shade(M &m, const FrameK &K, const ShadeDesc &
 // HELPER — k_shade's inline copy of it (any call in its tile loop moves its schedule; each copy names its helper; a fix goes into both):
 //    work_decode, id_none / id_sbit, ids_load_raw, ids_unpack4 — shade_tile: head, step 1 and the classification
 //    tile_rect — shade_tile, behind the FrameDesc loads (and k_shade_vis's shade_tile, head)
+//    (k_gbuffer CALLS tile_rect, the owner-id constants, v_normalized, normalize3, s_texel and cvt_rne_i32; its copy of v_shade's prologue
+//    and fetch and of shade_bary_v / _s's interpolation names them)
 //    frame_k — class_pass, head
 //    shade_bary_v / _s — the second half of shade_pixel_v / _s
 // (copies without a helper: k_shade_vis's compaction and batch-by-batch loop, of k_shade's; k_visibility's o[3][4], of quad_load / quad_at)
@@ -3126,6 +3128,173 @@ __global__ __launch_bounds__(256, FASTNL == -4 ? 3 : SRZ_SHADE_MINW) void k_shad
 }
 
 // ================================================================================================================
+// k_gbuffer — the G-BUFFER OF A VISIBILITY BUFFER (srz_frameset_gbuffer, include/srz.h): the attributes the built-in shaders are handed
+// for each pixel's owner — shade_bary_v / _s up to the call of v_shade / s_shade, v_shade's prologue and fetch, s_texel — as planes.
+// No work lists and no LDS: the grid walks every (frame, 32x32 tile) in k_shade_vis's XCD order, a thread owns 4 consecutive pixels of
+// one row (k_visibility's deal), so every plane leaves as 16-byte non-temporal stores straight from registers.  Per thread: its 4 ids in
+// one 16-byte load; α and β only for a quad with an owner; per owned pixel the owner's normals and / or texture coordinates (floats
+// 9..23 of its record, never the positions) and its batch id, gathered; the texel only where ALBEDO asks for it.  Both classes share a
+// wave: a pixel's arithmetic is tens of operations, computed per lane by class, always with IeeeMath (no flag-and-redo).  `what` is
+// wave-uniform: one branch per group.  The floor is the memory system: 4 bytes of id per pixel, 8 of α and β + 62 of gather per owned
+// pixel, 4 written per requested plane and pixel.
+// ================================================================================================================
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+struct GbufPixel {
+  float n[3], uv[2], kd[3];
+  uint32_t batch1;
+};
+__device__ __forceinline__ GbufPixel gbuf_pixel(uint32_t what, uint32_t id, float alpha, float beta, const SRZ_CAS srz_tri *tris,
+                                                const SRZ_CAS uint16_t *tri_batch, const SRZ_CAS ShadeDescG *sdesc) {
+  GbufPixel o = {{0.f, 0.f, 0.f}, {0.f, 0.f}, {1.f, 1.f, 1.f}, 0u};
+  IeeeMath m;
+  const bool isS = (id & S_CLASS_BIT) != 0u;
+  const uint32_t idx = (id & ~S_CLASS_BIT) - 1u;
+  const SRZ_CAS float *rec = reinterpret_cast<const SRZ_CAS float *>(tris + idx);
+  const float gamma = isS ? 1.0f - alpha - beta : 1.0f - (alpha + beta); // (cover_s / cover_v)
+  if (what & SRZ_GB_NORMAL) {
+    const F3 n0 = ld3(rec + 9), n1 = ld3(rec + 12), n2 = ld3(rec + 15);
+    float nx, ny, nz;
+    if (isS) {
+      nx = alpha * n0.x + beta * n1.x + gamma * n2.x;
+      ny = alpha * n0.y + beta * n1.y + gamma * n2.y;
+      nz = alpha * n0.z + beta * n1.z + gamma * n2.z;
+      normalize3(m, nx, ny, nz);
+    } else {
+      nx = fmaf_(alpha, n0.x, fmaf_(beta, n1.x, gamma * n2.x));
+      ny = fmaf_(alpha, n0.y, fmaf_(beta, n1.y, gamma * n2.y));
+      nz = fmaf_(alpha, n0.z, fmaf_(beta, n1.z, gamma * n2.z));
+      v_normalized(m, nx, ny, nz);
+    }
+    o.n[0] = nx, o.n[1] = ny, o.n[2] = nz;
+  }
+  if (what & (SRZ_GB_BATCH | SRZ_GB_ALBEDO)) o.batch1 = (uint32_t)tri_batch[idx] + 1u;
+  if (what & (SRZ_GB_UV | SRZ_GB_ALBEDO)) {
+    const f32x2 t0 = *reinterpret_cast<const SRZ_CAS f32x2 *>(rec + 18); // u0 v0
+    const f32x4 t12 = *reinterpret_cast<const SRZ_CAS f32x4 *>(rec + 20); // u1 v1 u2 v2
+    float u, v;
+    if (isS) {
+      u = alpha * t0.x + beta * t12.x + gamma * t12.z;
+      v = alpha * t0.y + beta * t12.y + gamma * t12.w;
+    } else {
+      u = fmaf_(alpha, t0.x, fmaf_(beta, t12.x, gamma * t12.z));
+      v = fmaf_(alpha, t0.y, fmaf_(beta, t12.y, gamma * t12.w));
+    }
+    o.uv[0] = u, o.uv[1] = v;
+    if (what & SRZ_GB_ALBEDO) {
+      const SRZ_CAS ShadeDescG *g = sdesc + (o.batch1 - 1u);
+      ShadeDesc sd;
+      sd.shader = g->shader, sd.tw = g->tw, sd.th = g->th, sd.tex = as_const(g->tex);
+      if (isS) { // s_shade: every textured type fetches kd through getTextureColor(vec2)
+        if (sd.shader == SRZ_SHADER_TEXTURE || sd.shader == SRZ_SHADER_BUMP || sd.shader == SRZ_SHADER_DISPLACEMENT)
+          s_texel(m, sd, u, v, o.kd[0], o.kd[1], o.kd[2]);
+      } else if (sd.shader == SRZ_SHADER_TEXTURE) { // v_shade's prologue and fetch (inline copy: it has no helper of its own)
+        const float tw = (float)sd.tw, th = (float)sd.th;
+        u = u * tw, v = v * th;
+        u = sse_max(0.0f, sse_min(u, tw - 1.0f));
+        v = sse_max(0.0f, sse_min(v, th - 1.0f));
+        const int32_t xi = cvt_rne_i32(u), yi = cvt_rne_i32(v);
+        const uint32_t texel = sd.tex[(size_t)yi * sd.tw + xi];
+        const float inv255 = 1.0f / 255.0f;
+        o.kd[0] = (float)(texel & 0xffu) * inv255, o.kd[1] = (float)((texel >> 8) & 0xffu) * inv255, o.kd[2] = (float)((texel >> 16) & 0xffu) * inv255;
+      }
+    }
+  }
+  return o;
+}
+__global__ __launch_bounds__(256) void k_gbuffer(GbufArgs a) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  const uint32_t what = a.what;
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
+  for (uint32_t j = blockIdx.x >> 3;; j += step) {
+    uint32_t f, t;
+    if (a.n_frames >= 8u) {
+      f = sub + 8u * (j / tpf), t = j % tpf;
+      if (f >= a.n_frames) break;
+    } else {
+      const uint32_t i = j * 8u + sub;
+      if (i >= n_items) break;
+      f = i / tpf, t = i % tpf;
+    }
+    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
+    const TileRect rc = tile_rect(a, fd, f, lb, tx);
+    const int W = fd->width;
+    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
+    if (!(y <= rc.ty1 && x4 <= rc.tx1)) continue; // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool whole = (W & 3) == 0 && x4 + 3 <= rc.tx1;
+    const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
+    const size_t poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)x4;
+    const float *gv = a.vis + (size_t)f * a.vis_stride + poff; // plane 0 (z: never read)
+    float *go = rc.out0 + (size_t)ly * (size_t)W + (size_t)x4;
+    // ---- 1. owner ids (index + 1 | S class; 0 or an index outside the frame's triangles: nobody)
+    uint32_t id[4] = {0u, 0u, 0u, 0u};
+    if (whole) {
+      const uint4 q = *reinterpret_cast<const uint4 *>(gv + rc.plane);
+      id[0] = q.x, id[1] = q.y, id[2] = q.z, id[3] = q.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (x4 + k <= rc.tx1) id[k] = f2u(gv[rc.plane + k]);
+    }
+    const uint32_t n_tris = fd->n_tris;
+    uint32_t own = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if ((id[k] & ~S_CLASS_BIT) - 1u >= n_tris) id[k] = 0u; // (0 and the bare class bit wrap to 0xffffffff)
+      own |= id[k] != 0u ? 1u << k : 0u;
+    }
+    if (own == 0u && !fused) continue;
+    // ---- 2. α, β of a quad with an owner; the owners' attributes
+    float4 al = make_float4(0.f, 0.f, 0.f, 0.f), be = al;
+    if (own != 0u) {
+      if (whole) {
+        al = *reinterpret_cast<const float4 *>(gv + 2 * rc.plane), be = *reinterpret_cast<const float4 *>(gv + 3 * rc.plane);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (x4 + k <= rc.tx1) quad_at(al, k) = gv[2 * rc.plane + k], quad_at(be, k) = gv[3 * rc.plane + k];
+      }
+    }
+    const SRZ_CAS srz_tri *tris = as_const(a.tris) + fd->tri_off;
+    const SRZ_CAS uint16_t *tri_batch = as_const(a.tri_batch) + fd->tri_off;
+    const SRZ_CAS ShadeDescG *sdesc = as_const(a.sdesc) + fd->batch_off;
+    float4 qn[3], quv[2], qb[1], qk[3]; // nobody: zeros
+#pragma unroll
+    for (int i = 0; i < 3; ++i) qn[i] = qk[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    quv[0] = quv[1] = qb[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (id[k] == 0u) continue;
+      const GbufPixel px = gbuf_pixel(what, id[k], quad_at(al, k), quad_at(be, k), tris, tri_batch, sdesc);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) quad_at(qn[i], k) = px.n[i], quad_at(qk[i], k) = px.kd[i];
+      quad_at(quv[0], k) = px.uv[0], quad_at(quv[1], k) = px.uv[1], quad_at(qb[0], k) = u2f_(px.batch1);
+    }
+    // ---- 3. the requested planes, group after group: whole quads (fused clear, or four owners), else the owned pixels only
+    const bool quads = fused || own == 15u;
+    auto put = [&](float *p, const auto &q) {
+      constexpr int N = (int)(sizeof(q) / sizeof(float4));
+      if (quads) {
+        quad_store(p, rc.plane, q, whole, x4, rc.tx1);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (own & (1u << k))
+#pragma unroll
+            for (int i = 0; i < N; ++i) p[i * rc.plane + k] = quad_at(q[i], k);
+      }
+    };
+    if (what & SRZ_GB_NORMAL) put(go, qn), go += 3 * rc.plane;
+    if (what & SRZ_GB_UV) put(go, quv), go += 2 * rc.plane;
+    if (what & SRZ_GB_BATCH) put(go, qb), go += rc.plane;
+    if (what & SRZ_GB_ALBEDO) put(go, qk);
+  }
+}
+
+// ================================================================================================================
 // k_resolve8 — display()'s resolve (src/Render.cpp:61-62): cv::merge(planes 0,1,2) + convertTo(CV_8UC3) =
 // saturate_cast<uchar>(cvRound(v)): round half to even, clamp to [0,255]; NaN → 0.  4 pixels per thread: three 16-byte
 // plane reads → 12 output bytes (three dword stores).
@@ -3691,6 +3860,13 @@ void launch_shade_vis(const ShadeVisArgs &a, uint32_t kinds, bool any_generic, b
   });
   // the generic build also serves the tiles the exact FAST builds hand back (redo_count: zeroed by the caller)
   if (any_generic || (kinds && !approx)) hipLaunchKernelGGL((k_shade_vis<0>), any_generic ? grid : dim3(std::min(grid.x, 128u)), blk, 0, s, a);
+}
+
+void launch_gbuffer(const GbufArgs &a, hipStream_t s) {
+  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
+  if (items == 0) return;
+  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (a multiple of 8: workgroup b serves the frames f ≡ b mod 8)
+  hipLaunchKernelGGL(k_gbuffer, grid, dim3(256), 0, s, a);
 }
 
 bool raster_four_waves(const RenderArgs &a) { return a.n_frames * a.n_local_bands * a.tiles_x <= 4096u; }

@@ -23,7 +23,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_deinterleave", "srz_frameset_allgather_inplace", "srz_frameset_gathered_row_offset",
            "srz_frameset_read_gathered_frame", "srz_frameset_sparse_capacity", "srz_frameset_sparse_pack", "srz_frameset_sparse_unpack",
            "srz_frameset_allgather_sparse", "srz_frameset_render_visibility", "srz_frameset_shade_visibility",
-           "srz_frameset_update_shading", "srz_frameset_shade_kinds"]
+           "srz_frameset_update_shading", "srz_frameset_shade_kinds", "srz_frameset_gbuffer_bytes", "srz_frameset_gbuffer"]
 
 
 class SrzError(RuntimeError):
@@ -69,6 +69,9 @@ def lib():
         L.srz_frameset_render.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]
         L.srz_frameset_render_visibility.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]
         L.srz_frameset_shade_visibility.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp]
+        L.srz_frameset_gbuffer_bytes.argtypes = [vp, vp, C.c_uint32]
+        L.srz_frameset_gbuffer_bytes.restype = C.c_size_t
+        L.srz_frameset_gbuffer.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp]
         L.srz_frameset_update_shading.argtypes = [vp, vp, C.POINTER(abi.SrzFrame), C.c_int]
         L.srz_sceneset_update.argtypes = [vp, vp, C.POINTER(abi.SrzSceneFrame), C.c_int]
         L.srz_frameset_resolve8.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
@@ -156,6 +159,22 @@ class FrameSet:
         render() of the same frames.  d_out_ptr may equal d_vis_ptr (in place); a partial overlap is an error.  Asynchronous."""
         self.ctx._check(lib().srz_frameset_shade_visibility(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_out_ptr), out_bytes,
                                                             flags, _stream(stream)))
+
+    def gbuffer_bytes(self, what=abi.GB_ALL):
+        """bytes of the G-buffer of the groups in `what` (abi.GB_*); 0 for what == 0 or an unknown bit"""
+        return int(lib().srz_frameset_gbuffer_bytes(self.ctx.h, self.h, what))
+
+    def gbuffer_shape(self, what=abi.GB_ALL):
+        """[frame][plane][local_rows][width] of 4-byte words, the planes of srz.visibility.gbuffer_planes(what)"""
+        from .visibility import gbuffer_planes
+        return (self.n_frames, len(gbuffer_planes(what)), self.local_rows, self.width)
+
+    def gbuffer(self, d_vis_ptr, d_out_ptr, out_bytes, what=abi.GB_ALL, flags=abi.FUSED_CLEAR, stream=None):
+        """the attribute planes of a visibility buffer of this set (render_visibility): what the built-in shaders are handed for every
+        pixel's owner, bit for bit — normal, uv, batch + 1, albedo (include/srz.h; srz.visibility.gbuffer_decode takes it apart).
+        d_out_ptr may not overlap d_vis_ptr; pixels nobody owns are zeros with FUSED_CLEAR, else left untouched.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_gbuffer(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_out_ptr), out_bytes, what, flags,
+                                                   _stream(stream)))
 
     def update_shading(self, frames):
         """new eye, ka, ks, p, kh, kn, lights, flags and batch shaders / textures for a set made from abi.Frame's, triangles untouched

@@ -12,6 +12,8 @@ from collections import namedtuple
 
 import torch
 
+from . import abi
+
 Visibility = namedtuple("Visibility", "z tri s_class alpha beta gamma")
 
 S_CLASS_BIT = 0x80000000
@@ -44,3 +46,35 @@ def batch_of(frame, tri):
         raise IndexError(f"batch_of: a triangle index outside the frame's {total} triangles")
     b = torch.searchsorted(ends, tri.to(torch.int64), right=True)
     return torch.where(tri < 0, torch.full_like(b, -1), b)
+
+
+_GB_GROUPS = ((abi.GB_NORMAL, ("nx", "ny", "nz")), (abi.GB_UV, ("u", "v")), (abi.GB_BATCH, ("batch",)),
+              (abi.GB_ALBEDO, ("albedo0", "albedo1", "albedo2")))
+
+
+def gbuffer_planes(what):
+    """the plane names of a G-buffer of the groups in `what` (abi.GB_*), in buffer order (include/srz.h, srz_frameset_gbuffer)"""
+    if what == 0 or what & ~abi.GB_ALL:
+        raise ValueError(f"gbuffer_planes: what = {what:#x} names no group or an unknown one")
+    return tuple(name for bit, names in _GB_GROUPS if what & bit for name in names)
+
+
+def gbuffer_decode(buf, what):
+    """buf: a FrameSet.gbuffer buffer as a torch tensor [..., planes, rows, W] of any 4-byte dtype → a dict of VIEWS (no copy) with the
+    groups of `what`: "normal" [..., 3, rows, W] and "uv" [..., 2, rows, W] float32, "batch" [..., rows, W] int32 (the owner's batch
+    index in its frame, -1 = nobody: the stored word is index + 1, so this one entry is computed) and "albedo" [..., 3, rows, W]
+    float32 in the order of the colour planes."""
+    n = len(gbuffer_planes(what))
+    if buf.element_size() != 4 or buf.dim() < 3 or buf.shape[-3] != n:
+        raise ValueError(f"gbuffer_decode: expected a [..., {n}, rows, W] tensor of 4-byte words, got {tuple(buf.shape)} {buf.dtype}")
+    f = buf.view(torch.float32) if buf.dtype != torch.float32 else buf
+    out, at = {}, 0
+    for bit, key, k in ((abi.GB_NORMAL, "normal", 3), (abi.GB_UV, "uv", 2), (abi.GB_BATCH, "batch", 1), (abi.GB_ALBEDO, "albedo", 3)):
+        if not what & bit:
+            continue
+        if key == "batch":
+            out[key] = buf.view(torch.int32)[..., at, :, :] - 1
+        else:
+            out[key] = f[..., at:at + k, :, :]
+        at += k
+    return out
