@@ -50,6 +50,7 @@ extern "C" {
  *      srz_frameset_update_shading
  *      (additive, same version) the diagnostic srz_frameset_shade_kinds
  *      (additive, same version) the G-buffer of a visibility buffer srz_frameset_gbuffer / srz_frameset_gbuffer_bytes, SRZ_GB_*
+ *      (additive, same version) the motion pass between frames of a set srz_frameset_motion / srz_frameset_motion_bytes, SRZ_MV_*
  */
 #define SRZ_ABI_VERSION 7
 
@@ -317,6 +318,43 @@ int srz_frameset_shade_visibility(srz_ctx *ctx, srz_frameset *fs, const void *d_
 size_t srz_frameset_gbuffer_bytes(const srz_ctx *ctx, const srz_frameset *fs, uint32_t what);
 int srz_frameset_gbuffer(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void *d_out, size_t out_bytes, uint32_t what, uint32_t flags,
                          void *stream);
+/* The MOTION PASS of a visibility buffer: where the surface point under each pixel of frame f lies in frame g = f + delta of the same
+ * set — optical flow, the depth there, and who owns the nearest sample there (an occlusion test) — for sets whose frames are poses of
+ * one mesh: triangle t of frame g is taken to be triangle t of frame f.  It completes the guide images a G-buffer is made for
+ * (normal, albedo, depth, motion) without the caller restating the two interpolation rules and both forms of gamma.  `what` names
+ * the groups: */
+#define SRZ_MV_FLOW   1u /* 2 planes  dx, dy   float32 */
+#define SRZ_MV_DEPTH  2u /* 1 plane   z'       float32 */
+#define SRZ_MV_TARGET 4u /* 2 planes  tid uint32, tz float32 */
+/* d_vis: a visibility buffer of THIS set on this ctx's shard; d_out: [frame][plane][local_rows][width], 4-byte words, the planes of the
+ * groups in `what` in the order above, without gaps: srz_frameset_motion_bytes(what) bytes (0 for what == 0 or an unknown bit).  Size,
+ * 16-byte alignment of both buffers, band sharding, stream semantics, asynchrony and the null-argument rules as srz_frameset_gbuffer; a
+ * sceneset runs its vertex stage first.  No texture need be uploaded.
+ * Per pixel (x, y) of frame f — y the FRAME's row, not the shard's local row — whose id names an owner t (id != 0 and
+ * (id & 0x7fffffff) - 1 < frame f's triangle count; class = bit 31 of id; gamma = 1 - (alpha + beta) for V, (1 - alpha) - beta for S),
+ * with a, b, c the three positions of triangle t in frame g's stream:
+ *   the point in g   P' = (x', y', z'), each component interpolated exactly as the class interpolates z:
+ *                    V: fma(alpha, a, fma(beta, b, gamma * c));  S: alpha * a + beta * b + gamma * c, left to right, nothing fused
+ *   FLOW    dx = x' - (float)x, dy = y' - (float)y
+ *   DEPTH   z'
+ *   TARGET  tx = rintf(x'), ty = rintf(y') (round half even; a pixel's sample point is its integer corner, so this is the nearest
+ *           sample).  Inside — tx >= 0 && tx <= W - 1 && ty >= 0 && ty <= H - 1, compared as floats before any conversion, so that a
+ *           NaN or a huge coordinate is outside and never becomes an index —: tid and tz are the raw words of planes 1 and 0 of frame
+ *           g in d_vis at (tx, ty).  Outside: tid = 0, tz = +inf.  (tid == the pixel's own id, or tz close to z', means the point is
+ *           visible in g; anything else that it is occluded there or has left the image.)
+ * The interpolation is LINEAR IN SCREEN SPACE, as everywhere in the reference, which has no perspective-correct interpolation.
+ * Always the exact arithmetic: SRZ_OPT_APPROX_SHADE has no effect.
+ * Nobody: a pixel nobody owns (id 0 or out of range), and EVERY pixel of a frame whose g lies outside [0, n_frames).  With
+ * SRZ_FUSED_CLEAR (frame flags | flags) every requested word of a nobody pixel is 0; without it those words are left untouched.
+ * Two consequences: with delta == 0, DEPTH equals plane 0 of d_vis bit for bit at every owned pixel, and TARGET returns the pixel's own
+ * id and z wherever |dx| and |dy| are below 0.5.
+ * SRZ_E_INVALID, the output untouched, for: what == 0 or an unknown bit of `what`; a short out_bytes; a misaligned pointer; d_out
+ * overlapping d_vis; any bit of `flags` but SRZ_FUSED_CLEAR; some pair (f, f + delta) inside the set whose frames differ in triangle
+ * count (nothing is launched); SRZ_MV_TARGET on a ctx whose shard world is above 1 (the target row may belong to another rank — FLOW
+ * and DEPTH work on any shard). */
+size_t srz_frameset_motion_bytes(const srz_ctx *ctx, const srz_frameset *fs, uint32_t what);
+int srz_frameset_motion(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void *d_out, size_t out_bytes, uint32_t what, int delta,
+                        uint32_t flags, void *stream);
 /* New SHADING DATA for a set made by srz_frameset_create, its triangles untouched (batches[b].tris is ignored and may be NULL): each
  * frame's eye, ka, ks, p, kh, kn, lights and flags, each batch's shader and tex_id.  The structure must be the set's — frame count, size,
  * light counts, batch counts, n_tris per batch — else SRZ_E_INVALID and the set is unchanged; a sceneset is SRZ_E_INVALID (its shading

@@ -36,6 +36,7 @@ struct TexDesc {
 // the flags of srz_frame / srz_scene_frame / a render that the device sees (FrameDesc::flags, RenderArgs::flags_or)
 constexpr uint32_t FRAME_FLAGS = SRZ_UNIFIED | SRZ_FUSED_CLEAR | SRZ_ORDERED_RASTER;
 constexpr uint32_t GB_GROUPS = SRZ_GB_NORMAL | SRZ_GB_UV | SRZ_GB_BATCH | SRZ_GB_ALBEDO;
+constexpr uint32_t MV_GROUPS = SRZ_MV_FLOW | SRZ_MV_DEPTH | SRZ_MV_TARGET;
 } // namespace
 
 struct srz_ctx {
@@ -1366,6 +1367,52 @@ int srz_frameset_gbuffer(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void
   a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
   a.flags_or = flags, a.what = what;
   launch_gbuffer(a, s);
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
+size_t srz_frameset_motion_bytes(const srz_ctx *ctx, const srz_frameset *fs, uint32_t what) {
+  if (!fs || what == 0u || (what & ~MV_GROUPS) != 0u) return 0;
+  return (size_t)fs->n_frames * motion_planes(what) * fs->local_rows * (size_t)fs->width * sizeof(float);
+}
+
+int srz_frameset_motion(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void *d_out, size_t out_bytes, uint32_t what, int delta,
+                        uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_motion");
+  if (!fs || !d_vis || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / output");
+  if (what == 0u || (what & ~MV_GROUPS) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": `what` names no group or an unknown one");
+  if ((flags & ~(uint32_t)SRZ_FUSED_CLEAR) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": only SRZ_FUSED_CLEAR is accepted in flags");
+  if ((what & SRZ_MV_TARGET) && fs->shard_world > 1)
+    return fail(ctx, SRZ_E_INVALID, fn + ": SRZ_MV_TARGET needs the whole frame on this ctx (the target row may belong to another rank)");
+  const size_t need = srz_frameset_motion_bytes(ctx, fs, what), vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
+  if ((((uintptr_t)d_vis | (uintptr_t)d_out) & 15u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
+  const uintptr_t v = (uintptr_t)d_vis, o = (uintptr_t)d_out;
+  if (v < o + need && o < v + vis_bytes) return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the visibility buffer");
+  // triangle t of frame f + delta stands for triangle t of frame f: every pair inside the set must have one triangle count
+  const int n = fs->n_frames, d = std::max(-n, std::min(n, delta)); // (beyond +-n no frame has a target: the same result)
+  for (int f = 0; f < n; ++f) {
+    const int g = f + d;
+    if (g >= 0 && g < n && fs->h_frames[f].n_tris != fs->h_frames[g].n_tris)
+      return fail(ctx, SRZ_E_INVALID, fn + ": frames " + std::to_string(f) + " and " + std::to_string(g) + " differ in triangle count");
+  }
+  if (int rc = check_renderable(ctx, fs)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const hipStream_t s = pick_stream(ctx, stream);
+  // a sceneset's triangles are its vertex stage's output (as srz_frameset_shade_visibility)
+  if (fs->d_draws) launch_vertex(fs->d_draws, fs->n_draws, fs->max_faces, fs->d_tris, fs->d_tri_pos, fs->d_frames, nullptr, s);
+  MotionArgs a{};
+  a.frames = fs->d_frames;
+  a.tri_pos = fs->d_tri_pos ? fs->d_tri_pos : reinterpret_cast<const float *>(fs->d_tris);
+  a.pos_stride = fs->d_tri_pos ? TRI_POS_F : TRI_AOS_F;
+  a.delta = d;
+  a.vis = (const float *)d_vis, a.out = (float *)d_out;
+  a.vis_stride = 4ull * fs->local_rows * (uint64_t)fs->width, a.frame_stride = (uint64_t)motion_planes(what) * fs->local_rows * (uint64_t)fs->width;
+  a.local_rows = fs->local_rows, a.tiles_x = fs->tiles_x, a.n_local_bands = fs->n_local_bands, a.n_frames = (uint32_t)fs->n_frames;
+  a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
+  a.flags_or = flags, a.what = what;
+  launch_motion(a, s);
   HIP_TRY(ctx, hipGetLastError());
   return SRZ_OK;
 }

@@ -255,6 +255,26 @@ __host__ __device__ constexpr uint32_t gbuf_planes(uint32_t what) {
   return ((what & SRZ_GB_NORMAL) ? 3u : 0u) + ((what & SRZ_GB_UV) ? 2u : 0u) + ((what & SRZ_GB_BATCH) ? 1u : 0u) + ((what & SRZ_GB_ALBEDO) ? 3u : 0u);
 }
 void launch_gbuffer(const GbufArgs &a, hipStream_t s);
+// srz_frameset_motion: where the surface point under each pixel of frame f lies in frame f + delta (k_motion).  vis as above, out =
+// [frame][planes of `what`][local_rows][width]; `out` / `frame_stride` / `local_rows` / the shard are what tile_rect reads.  The host
+// has checked that every pair (f, f + delta) inside the set has one triangle count, and that TARGET comes with shard_world == 1
+struct MotionArgs {
+  const FrameDesc *frames;
+  const float *tri_pos;    // [triangle * pos_stride], as RenderArgs has it
+  uint32_t pos_stride;
+  int32_t delta;           // (clamped to [-n_frames, n_frames] by the host: f + delta cannot overflow)
+  const float *vis;
+  float *out;
+  uint64_t vis_stride;     // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride;   // floats per frame in out = planes * local_rows * width
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or, what;
+};
+__host__ __device__ constexpr uint32_t motion_planes(uint32_t what) {
+  return ((what & SRZ_MV_FLOW) ? 2u : 0u) + ((what & SRZ_MV_DEPTH) ? 1u : 0u) + ((what & SRZ_MV_TARGET) ? 2u : 0u);
+}
+void launch_motion(const MotionArgs &a, hipStream_t s);
 void launch_resolve8(const float *planes, uint8_t *out, uint32_t n_frames, uint32_t rows, uint32_t W, uint64_t frame_stride,
                      hipStream_t s);
 void launch_deinterleave(const void *gathered, void *full, uint32_t world, uint32_t n_fp, uint32_t bands_per_rank, uint32_t row_bytes,

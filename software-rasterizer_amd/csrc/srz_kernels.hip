@@ -1306,7 +1306,8 @@ __device__ __forceinline__ void s_shade(M &m, const FrameK &K, const ShadeDesc &
 //    work_decode, id_none / id_sbit, ids_load_raw, ids_unpack4 — shade_tile: head, step 1 and the classification
 //    tile_rect — shade_tile, behind the FrameDesc loads (and k_shade_vis's shade_tile, head)
 //    (k_gbuffer CALLS tile_rect, the owner-id constants, v_normalized, normalize3, s_texel and cvt_rne_i32; its copy of v_shade's prologue
-//    and fetch and of shade_bary_v / _s's interpolation names them)
+//    and fetch and of shade_bary_v / _s's interpolation names them; k_motion CALLS tile_rect, the owner-id constants and load_pos9, its
+//    copy of cover_v / cover_s's z interpolation names them)
 //    frame_k — class_pass, head
 //    shade_bary_v / _s — the second half of shade_pixel_v / _s
 // (copies without a helper: k_shade_vis's compaction and batch-by-batch loop, of k_shade's; k_visibility's o[3][4], of quad_load / quad_at)
@@ -3295,6 +3296,147 @@ __global__ __launch_bounds__(256) void k_gbuffer(GbufArgs a) {
 }
 
 // ================================================================================================================
+// k_motion — THE MOTION PASS (srz_frameset_motion, include/srz.h): where the surface point under each pixel of frame f lies in
+// frame g = f + delta of the same set, whose triangle t is frame f's triangle t.  The point is the owner's three positions IN FRAME g
+// under the pixel's α, β, γ, each component interpolated as the owner's class interpolates z (cover_v: fma chain; cover_s: products
+// and sums); FLOW is its x, y minus the pixel's, DEPTH its z, TARGET the raw id and z words of frame g's visibility buffer at the
+// nearest sample (round half even; outside the frame, NaN included: id 0, z +inf — decided in float, before any index exists).
+// k_gbuffer's shape: no work lists, no LDS, no barrier; the grid walks every (frame, 32x32 tile) in k_shade_vis's XCD order, a thread
+// owns 4 consecutive pixels of one row, its 4 ids arrive in one 16-byte load, α and β only for a quad with an owner, per owned pixel
+// one gather of 36 bytes (load_pos9) and, with TARGET, two dependent 4-byte loads; every plane leaves through quad_store.  `what` is
+// wave-uniform: one branch per group.  Always the exact arithmetic.  A frame whose g lies outside the set has no owner anywhere.
+// The floor is the memory system: 4 bytes of id per pixel; 8 of α and β, 36 of gather and (TARGET) 8 more per owned pixel; 4 written
+// per requested plane and pixel.
+// ================================================================================================================
+struct MotionPixel {
+  float dx, dy, z, tz;
+  uint32_t tid;
+};
+__device__ __forceinline__ MotionPixel motion_pixel(uint32_t what, uint32_t id, float alpha, float beta, int x, int y, const SRZ_CAS float *tpos,
+                                                    uint32_t pos_stride, const float *vis_g, size_t plane, int W, int H) {
+  MotionPixel o = {0.f, 0.f, 0.f, __builtin_inff(), 0u};
+  const bool isS = (id & S_CLASS_BIT) != 0u;
+  const uint32_t idx = (id & ~S_CLASS_BIT) - 1u;
+  float P[9]; // ax ay z0 bx by z1 cx cy z2 of the owner in frame g
+  load_pos9(tpos + (size_t)idx * pos_stride, P);
+  float xp, yp, zp;
+  if (isS) { // (cover_s)
+    const float gamma = 1.0f - alpha - beta;
+    xp = alpha * P[0] + beta * P[3] + gamma * P[6];
+    yp = alpha * P[1] + beta * P[4] + gamma * P[7];
+    zp = alpha * P[2] + beta * P[5] + gamma * P[8];
+  } else { // (cover_v)
+    const float gamma = 1.0f - (alpha + beta);
+    xp = fmaf_(alpha, P[0], fmaf_(beta, P[3], gamma * P[6]));
+    yp = fmaf_(alpha, P[1], fmaf_(beta, P[4], gamma * P[7]));
+    zp = fmaf_(alpha, P[2], fmaf_(beta, P[5], gamma * P[8]));
+  }
+  o.dx = xp - (float)x, o.dy = yp - (float)y, o.z = zp;
+  if (what & SRZ_MV_TARGET) {
+    const float tx = __builtin_rintf(xp), ty = __builtin_rintf(yp);
+    // compared as floats: a NaN or a huge coordinate is outside and never becomes an index
+    if (tx >= 0.0f && tx <= (float)(W - 1) && ty >= 0.0f && ty <= (float)(H - 1)) {
+      const float *q = vis_g + (size_t)(int)ty * (size_t)W + (size_t)(int)tx;
+      o.tid = f2u(q[plane]), o.tz = q[0];
+    }
+  }
+  return o;
+}
+__global__ __launch_bounds__(256) void k_motion(MotionArgs a) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  const uint32_t what = a.what;
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
+  for (uint32_t j = blockIdx.x >> 3;; j += step) {
+    uint32_t f, t;
+    if (a.n_frames >= 8u) {
+      f = sub + 8u * (j / tpf), t = j % tpf;
+      if (f >= a.n_frames) break;
+    } else {
+      const uint32_t i = j * 8u + sub;
+      if (i >= n_items) break;
+      f = i / tpf, t = i % tpf;
+    }
+    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
+    const TileRect rc = tile_rect(a, fd, f, lb, tx);
+    const int W = fd->width, H = fd->height;
+    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
+    if (!(y <= rc.ty1 && x4 <= rc.tx1)) continue; // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool whole = (W & 3) == 0 && x4 + 3 <= rc.tx1;
+    const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
+    const int g = (int)f + a.delta; // the target frame; outside the set: nobody owns a pixel of frame f
+    const bool has_g = g >= 0 && g < (int)a.n_frames;
+    if (!has_g && !fused) continue;
+    const size_t poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)x4;
+    const float *gv = a.vis + (size_t)f * a.vis_stride + poff; // plane 0 (z: never read)
+    float *go = rc.out0 + (size_t)ly * (size_t)W + (size_t)x4;
+    // ---- 1. owner ids (index + 1 | S class; 0 or an index outside the frame's triangles: nobody)
+    uint32_t id[4] = {0u, 0u, 0u, 0u};
+    if (has_g) {
+      if (whole) {
+        const uint4 q = *reinterpret_cast<const uint4 *>(gv + rc.plane);
+        id[0] = q.x, id[1] = q.y, id[2] = q.z, id[3] = q.w;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (x4 + k <= rc.tx1) id[k] = f2u(gv[rc.plane + k]);
+      }
+    }
+    const uint32_t n_tris = fd->n_tris;
+    uint32_t own = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if ((id[k] & ~S_CLASS_BIT) - 1u >= n_tris) id[k] = 0u; // (0 and the bare class bit wrap to 0xffffffff)
+      own |= id[k] != 0u ? 1u << k : 0u;
+    }
+    if (own == 0u && !fused) continue;
+    // ---- 2. α, β of a quad with an owner; the owners' positions in frame g and, with TARGET, frame g's words at the nearest sample
+    float4 al = make_float4(0.f, 0.f, 0.f, 0.f), be = al;
+    float4 qf[2], qd[1], qt[2]; // nobody: zeros
+    qf[0] = qf[1] = qd[0] = qt[0] = qt[1] = al;
+    if (own != 0u) {
+      if (whole) {
+        al = *reinterpret_cast<const float4 *>(gv + 2 * rc.plane), be = *reinterpret_cast<const float4 *>(gv + 3 * rc.plane);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (x4 + k <= rc.tx1) quad_at(al, k) = gv[2 * rc.plane + k], quad_at(be, k) = gv[3 * rc.plane + k];
+      }
+      const SRZ_CAS FrameDesc *fg = as_const(a.frames) + g;
+      const SRZ_CAS float *tpos = as_const(a.tri_pos) + (size_t)fg->tri_off * a.pos_stride;
+      const float *vis_g = a.vis + (size_t)g * a.vis_stride; // (TARGET: shard_world == 1, a local row is the frame's row)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (id[k] == 0u) continue;
+        const MotionPixel px = motion_pixel(what, id[k], quad_at(al, k), quad_at(be, k), x4 + k, y, tpos, a.pos_stride, vis_g, rc.plane, W, H);
+        quad_at(qf[0], k) = px.dx, quad_at(qf[1], k) = px.dy, quad_at(qd[0], k) = px.z;
+        quad_at(qt[0], k) = u2f(px.tid), quad_at(qt[1], k) = px.tz;
+      }
+    }
+    // ---- 3. the requested planes, group after group: whole quads (fused clear, or four owners), else the owned pixels only
+    const bool quads = fused || own == 15u;
+    auto put = [&](float *p, const auto &q) {
+      constexpr int N = (int)(sizeof(q) / sizeof(float4));
+      if (quads) {
+        quad_store(p, rc.plane, q, whole, x4, rc.tx1);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (own & (1u << k))
+#pragma unroll
+            for (int i = 0; i < N; ++i) p[i * rc.plane + k] = quad_at(q[i], k);
+      }
+    };
+    if (what & SRZ_MV_FLOW) put(go, qf), go += 2 * rc.plane;
+    if (what & SRZ_MV_DEPTH) put(go, qd), go += rc.plane;
+    if (what & SRZ_MV_TARGET) put(go, qt);
+  }
+}
+
+// ================================================================================================================
 // k_resolve8 — display()'s resolve (src/Render.cpp:61-62): cv::merge(planes 0,1,2) + convertTo(CV_8UC3) =
 // saturate_cast<uchar>(cvRound(v)): round half to even, clamp to [0,255]; NaN → 0.  4 pixels per thread: three 16-byte
 // plane reads → 12 output bytes (three dword stores).
@@ -3867,6 +4009,13 @@ void launch_gbuffer(const GbufArgs &a, hipStream_t s) {
   if (items == 0) return;
   const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (a multiple of 8: workgroup b serves the frames f ≡ b mod 8)
   hipLaunchKernelGGL(k_gbuffer, grid, dim3(256), 0, s, a);
+}
+
+void launch_motion(const MotionArgs &a, hipStream_t s) {
+  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
+  if (items == 0) return;
+  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (a multiple of 8: workgroup b serves the frames f ≡ b mod 8)
+  hipLaunchKernelGGL(k_motion, grid, dim3(256), 0, s, a);
 }
 
 bool raster_four_waves(const RenderArgs &a) { return a.n_frames * a.n_local_bands * a.tiles_x <= 4096u; }

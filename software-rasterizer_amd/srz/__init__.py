@@ -23,7 +23,8 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_deinterleave", "srz_frameset_allgather_inplace", "srz_frameset_gathered_row_offset",
            "srz_frameset_read_gathered_frame", "srz_frameset_sparse_capacity", "srz_frameset_sparse_pack", "srz_frameset_sparse_unpack",
            "srz_frameset_allgather_sparse", "srz_frameset_render_visibility", "srz_frameset_shade_visibility",
-           "srz_frameset_update_shading", "srz_frameset_shade_kinds", "srz_frameset_gbuffer_bytes", "srz_frameset_gbuffer"]
+           "srz_frameset_update_shading", "srz_frameset_shade_kinds", "srz_frameset_gbuffer_bytes", "srz_frameset_gbuffer",
+           "srz_frameset_motion_bytes", "srz_frameset_motion"]
 
 
 class SrzError(RuntimeError):
@@ -72,6 +73,9 @@ def lib():
         L.srz_frameset_gbuffer_bytes.argtypes = [vp, vp, C.c_uint32]
         L.srz_frameset_gbuffer_bytes.restype = C.c_size_t
         L.srz_frameset_gbuffer.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp]
+        L.srz_frameset_motion_bytes.argtypes = [vp, vp, C.c_uint32]
+        L.srz_frameset_motion_bytes.restype = C.c_size_t
+        L.srz_frameset_motion.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, C.c_int, C.c_uint32, vp]
         L.srz_frameset_update_shading.argtypes = [vp, vp, C.POINTER(abi.SrzFrame), C.c_int]
         L.srz_sceneset_update.argtypes = [vp, vp, C.POINTER(abi.SrzSceneFrame), C.c_int]
         L.srz_frameset_resolve8.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
@@ -175,6 +179,24 @@ class FrameSet:
         d_out_ptr may not overlap d_vis_ptr; pixels nobody owns are zeros with FUSED_CLEAR, else left untouched.  Asynchronous."""
         self.ctx._check(lib().srz_frameset_gbuffer(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_out_ptr), out_bytes, what, flags,
                                                    _stream(stream)))
+
+    def motion_bytes(self, what=abi.MV_ALL):
+        """bytes of the motion buffer of the groups in `what` (abi.MV_*); 0 for what == 0 or an unknown bit"""
+        return int(lib().srz_frameset_motion_bytes(self.ctx.h, self.h, what))
+
+    def motion_shape(self, what=abi.MV_ALL):
+        """[frame][plane][local_rows][width] of 4-byte words, the planes of srz.visibility.motion_planes(what)"""
+        from .visibility import motion_planes
+        return (self.n_frames, len(motion_planes(what)), self.local_rows, self.width)
+
+    def motion(self, d_vis_ptr, d_out_ptr, out_bytes, what=abi.MV_ALL, delta=1, flags=abi.FUSED_CLEAR, stream=None):
+        """where the surface point under each pixel of frame f of a visibility buffer of this set (render_visibility) lies in frame
+        f + delta, triangle t there standing for triangle t here: flow dx, dy; the depth there; the raw id and z words of frame
+        f + delta at the nearest sample (include/srz.h; srz.visibility.motion_decode takes it apart).  d_out_ptr may not overlap
+        d_vis_ptr; pixels nobody owns, and every pixel of a frame without a target frame, are zeros with FUSED_CLEAR, else left
+        untouched.  MV_TARGET needs an unsharded context.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_motion(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_out_ptr), out_bytes, what, delta,
+                                                  flags, _stream(stream)))
 
     def update_shading(self, frames):
         """new eye, ka, ks, p, kh, kn, lights, flags and batch shaders / textures for a set made from abi.Frame's, triangles untouched

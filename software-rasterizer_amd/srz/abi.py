@@ -17,6 +17,8 @@ EXCHANGE_PLANES, EXCHANGE_BGR8 = 0, 1
 OPT_POOL_LAZY, OPT_APPROX_SHADE = 1, 2  # srz_set_option
 GB_NORMAL, GB_UV, GB_BATCH, GB_ALBEDO = 1, 2, 4, 8  # srz_frameset_gbuffer: the groups of `what` (3, 2, 1, 3 planes, in this order)
 GB_ALL = GB_NORMAL | GB_UV | GB_BATCH | GB_ALBEDO
+MV_FLOW, MV_DEPTH, MV_TARGET = 1, 2, 4  # srz_frameset_motion: the groups of `what` (2, 1, 2 planes, in this order)
+MV_ALL = MV_FLOW | MV_DEPTH | MV_TARGET
 
 # numpy view of srz_tri (96 B): pos[3][3], nrm[3][3], uv[3][2]
 TRI_DTYPE = np.dtype([("pos", "<f4", (3, 3)), ("nrm", "<f4", (3, 3)), ("uv", "<f4", (3, 2))])

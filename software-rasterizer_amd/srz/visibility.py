@@ -78,3 +78,37 @@ def gbuffer_decode(buf, what):
             out[key] = f[..., at:at + k, :, :]
         at += k
     return out
+
+
+_MV_GROUPS = ((abi.MV_FLOW, ("dx", "dy")), (abi.MV_DEPTH, ("depth",)), (abi.MV_TARGET, ("target_id", "target_z")))
+
+
+def motion_planes(what):
+    """the plane names of a motion buffer of the groups in `what` (abi.MV_*), in buffer order (include/srz.h, srz_frameset_motion)"""
+    if what == 0 or what & ~abi.MV_ALL:
+        raise ValueError(f"motion_planes: what = {what:#x} names no group or an unknown one")
+    return tuple(name for bit, names in _MV_GROUPS if what & bit for name in names)
+
+
+def motion_decode(buf, what):
+    """buf: a FrameSet.motion buffer as a torch tensor [..., planes, rows, W] of any 4-byte dtype → a dict with the groups of `what`:
+    "flow" [..., 2, rows, W] (dx, dy), "depth" [..., rows, W] and "target_z" [..., rows, W] float32 — VIEWS, no copy — and, computed
+    from the target's id word, "target_index" [..., rows, W] int64 (the index in the target frame's triangle stream of the owner of
+    the nearest sample there; -1 = nobody there, the sample outside the frame, or no owner here) and "target_s_class" bool."""
+    n = len(motion_planes(what))
+    if buf.element_size() != 4 or buf.dim() < 3 or buf.shape[-3] != n:
+        raise ValueError(f"motion_decode: expected a [..., {n}, rows, W] tensor of 4-byte words, got {tuple(buf.shape)} {buf.dtype}")
+    f = buf.view(torch.float32) if buf.dtype != torch.float32 else buf
+    out, at = {}, 0
+    if what & abi.MV_FLOW:
+        out["flow"] = f[..., at:at + 2, :, :]
+        at += 2
+    if what & abi.MV_DEPTH:
+        out["depth"] = f[..., at, :, :]
+        at += 1
+    if what & abi.MV_TARGET:
+        words = buf.view(torch.int32)[..., at, :, :].to(torch.int64) & 0xffffffff
+        out["target_index"] = (words & 0x7fffffff) - 1
+        out["target_s_class"] = (words & S_CLASS_BIT) != 0
+        out["target_z"] = f[..., at + 1, :, :]
+    return out
