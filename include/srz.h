@@ -51,6 +51,8 @@ extern "C" {
  *      (additive, same version) the diagnostic srz_frameset_shade_kinds
  *      (additive, same version) the G-buffer of a visibility buffer srz_frameset_gbuffer / srz_frameset_gbuffer_bytes, SRZ_GB_*
  *      (additive, same version) the motion pass between frames of a set srz_frameset_motion / srz_frameset_motion_bytes, SRZ_MV_*
+ *      (additive, same version) caller attributes over a visibility buffer, with gradients srz_frameset_interpolate /
+ *      srz_frameset_interpolate_bytes / srz_frameset_interpolate_grad, SRZ_ATTR_MAX_CH
  */
 #define SRZ_ABI_VERSION 7
 
@@ -355,6 +357,45 @@ int srz_frameset_gbuffer(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void
 size_t srz_frameset_motion_bytes(const srz_ctx *ctx, const srz_frameset *fs, uint32_t what);
 int srz_frameset_motion(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void *d_out, size_t out_bytes, uint32_t what, int delta,
                         uint32_t flags, void *stream);
+/* CALLER ATTRIBUTES over a visibility buffer, and their gradients: per-vertex data of the caller's own (colours, object-space
+ * positions, labels, skinning weights, tangents — whatever the 96-byte srz_tri does not carry) interpolated under each pixel's
+ * alpha, beta, gamma exactly as the owner's class interpolates uv, and the backward of that interpolation: the front half of a
+ * differentiable renderer.
+ * d_vis: a visibility buffer of THIS set on this ctx's shard.  d_attr: [attr_frames][attr_tris][3 corners][n_ch] float32, 4-byte
+ * aligned; attr_frames is 1 (every frame reads the same array: poses of one mesh) or the set's frame count; attr_tris is at least
+ * every frame's triangle count.  Triangle index and corner order are the visibility buffer's and srz_tri's: the index is the position
+ * in the frame's own stream, corners 0, 1, 2 go with alpha, beta, gamma.  d_out and d_gout: [frame][n_ch][local_rows][width] float32,
+ * srz_frameset_interpolate_bytes(n_ch) bytes (0 for n_ch == 0 or n_ch > SRZ_ATTR_MAX_CH, or a null set).  Band sharding, local_rows,
+ * stream semantics, asynchrony and the 16-byte alignment of the visibility buffer and every plane buffer (d_out, d_gout, d_gbary) as
+ * srz_frameset_gbuffer.  The passes read no position, record or texture: a sceneset does not run its vertex stage, nothing else is
+ * launched.  Owner and nobody as srz_frameset_gbuffer: (id & 0x7fffffff) - 1 < the frame's triangle count means an owner, bit 31 of
+ * id is the class, gamma = 1 - (alpha + beta) for V and (1 - alpha) - beta for S.
+ * FORWARD, bit for bit: with a, b, c the owner's three values of channel ch,
+ *   V: fma(alpha, a, fma(beta, b, gamma * c));  S: alpha * a + beta * b + gamma * c, left to right, nothing fused.
+ * Always the exact arithmetic: SRZ_OPT_APPROX_SHADE has no effect.  A nobody pixel gets 0 with SRZ_FUSED_CLEAR (frame flags | flags)
+ * and is left untouched without it.
+ * BACKWARD: at least one of d_gattr and d_gbary is non-null.
+ *   d_gattr has d_attr's shape (d_attr itself may be null when only d_gattr is asked for).  For every owned pixel with weights
+ *   w = (alpha, beta, gamma) and every channel ch the float32 product w[k] * gout[ch] is ADDED to gattr[fa][t][k][ch] (fa = 0 when
+ *   attr_frames == 1): the caller zeroes the buffer, or accumulates over several calls.  THE ORDER OF THE ADDS IS UNSPECIFIED, each
+ *   add rounds, so this buffer is NOT BIT-REPRODUCIBLE between launches — the one place in this ABI where that holds.  With n
+ *   contributing pixels an element lies within n 2^-24 / (1 - n 2^-24) * sum |w[k] * gout[ch]| of the exact sum; an element with one
+ *   contributing pixel is exact.  The adds are hardware float atomics: d_gattr must be ordinary (coarse-grained) device memory.  On
+ *   a sharded ctx each rank produces the partial sums of its own bands.
+ *   d_gbary: [frame][2][local_rows][width] float32, needs d_attr: dalpha = acc after acc = 0; for ch ascending: acc = fma(gout[ch],
+ *   a - c, acc), dbeta the same with b - c, the differences rounded to float first.  Deterministic, bit for bit.  Nobody pixels as
+ *   in the forward pass: 0 when fused, untouched otherwise.
+ *   Words of d_gout at nobody pixels never reach a result: they may hold anything.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set, d_vis, d_attr (forward; backward with d_gbary),
+ * d_out, d_gout, or both of d_gattr and d_gbary; n_ch == 0 or above SRZ_ATTR_MAX_CH; attr_frames not 1 or the frame count; attr_tris
+ * below some frame's triangle count; a misaligned pointer; a short out_bytes; any bit of `flags` but SRZ_FUSED_CLEAR; an output that
+ * overlaps an input (d_out with d_vis or d_attr; d_gattr or d_gbary with d_vis, d_gout or d_attr) or the other output. */
+#define SRZ_ATTR_MAX_CH 64u
+size_t srz_frameset_interpolate_bytes(const srz_ctx *ctx, const srz_frameset *fs, uint32_t n_ch);
+int srz_frameset_interpolate(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_attr, uint32_t n_ch, uint32_t attr_frames,
+                             uint32_t attr_tris, void *d_out, size_t out_bytes, uint32_t flags, void *stream);
+int srz_frameset_interpolate_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_gout, const float *d_attr, uint32_t n_ch,
+                                  uint32_t attr_frames, uint32_t attr_tris, float *d_gattr, void *d_gbary, uint32_t flags, void *stream);
 /* New SHADING DATA for a set made by srz_frameset_create, its triangles untouched (batches[b].tris is ignored and may be NULL): each
  * frame's eye, ka, ks, p, kh, kn, lights and flags, each batch's shader and tex_id.  The structure must be the set's — frame count, size,
  * light counts, batch counts, n_tris per batch — else SRZ_E_INVALID and the set is unchanged; a sceneset is SRZ_E_INVALID (its shading

@@ -1417,6 +1417,97 @@ int srz_frameset_motion(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void 
   return SRZ_OK;
 }
 
+size_t srz_frameset_interpolate_bytes(const srz_ctx *ctx, const srz_frameset *fs, uint32_t n_ch) {
+  if (!fs || n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH) return 0;
+  return (size_t)fs->n_frames * n_ch * fs->local_rows * (size_t)fs->width * sizeof(float);
+}
+
+} // extern "C"
+namespace {
+bool ranges_overlap(const void *p, size_t p_bytes, const void *q, size_t q_bytes) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return p && q && a < b + q_bytes && b < a + p_bytes;
+}
+// what srz_frameset_interpolate and _interpolate_grad check alike; the attribute array's bytes in *attr_bytes
+int check_interp(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, uint32_t n_ch, uint32_t attr_frames, uint32_t attr_tris,
+                 uint32_t flags, size_t *attr_bytes) {
+  if (n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_ATTR_MAX_CH");
+  if ((flags & ~(uint32_t)SRZ_FUSED_CLEAR) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": only SRZ_FUSED_CLEAR is accepted in flags");
+  if (attr_frames != 1u && attr_frames != (uint32_t)fs->n_frames)
+    return fail(ctx, SRZ_E_INVALID, fn + ": attr_frames must be 1 or the set's frame count");
+  for (const FrameDesc &d : fs->h_frames)
+    if (d.n_tris > attr_tris) return fail(ctx, SRZ_E_INVALID, fn + ": attr_tris is below a frame's triangle count");
+  *attr_bytes = (size_t)attr_frames * attr_tris * 3u * n_ch * sizeof(float);
+  return SRZ_OK;
+}
+InterpArgs interp_args(const srz_frameset *fs, const void *d_vis, const float *d_attr, uint32_t n_ch, uint32_t attr_frames, uint32_t attr_tris,
+                       uint32_t out_planes, void *d_out, uint32_t flags) {
+  InterpArgs a{};
+  const uint64_t plane = fs->local_rows * (uint64_t)fs->width;
+  a.frames = fs->d_frames, a.vis = (const float *)d_vis, a.attr = d_attr, a.out = (float *)d_out;
+  a.vis_stride = 4ull * plane, a.frame_stride = out_planes * plane, a.gout_stride = n_ch * plane;
+  a.attr_frame_stride = attr_frames == 1u ? 0ull : (uint64_t)attr_tris * 3u * n_ch;
+  a.n_ch = n_ch;
+  a.local_rows = fs->local_rows, a.tiles_x = fs->tiles_x, a.n_local_bands = fs->n_local_bands, a.n_frames = (uint32_t)fs->n_frames;
+  a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
+  a.flags_or = flags;
+  return a;
+}
+} // namespace
+extern "C" {
+
+int srz_frameset_interpolate(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_attr, uint32_t n_ch, uint32_t attr_frames,
+                             uint32_t attr_tris, void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_interpolate");
+  if (!fs || !d_vis || !d_attr || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / attributes / output");
+  size_t attr_bytes = 0;
+  if (int rc = check_interp(ctx, fs, fn, n_ch, attr_frames, attr_tris, flags, &attr_bytes)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, n_ch), vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
+  if ((((uintptr_t)d_vis | (uintptr_t)d_out) & 15u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
+  if (((uintptr_t)d_attr & 3u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": the attributes must be 4-byte aligned");
+  if (ranges_overlap(d_out, need, d_vis, vis_bytes) || ranges_overlap(d_out, need, d_attr, attr_bytes))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the visibility buffer or the attributes");
+  if (int rc = check_renderable(ctx, fs)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const hipStream_t s = pick_stream(ctx, stream);
+  launch_interp(interp_args(fs, d_vis, d_attr, n_ch, attr_frames, attr_tris, n_ch, d_out, flags), s);
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
+int srz_frameset_interpolate_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_gout, const float *d_attr, uint32_t n_ch,
+                                  uint32_t attr_frames, uint32_t attr_tris, float *d_gattr, void *d_gbary, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_interpolate_grad");
+  if (!fs || !d_vis || !d_gout) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / output gradient");
+  if (!d_gattr && !d_gbary) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gattr nor d_gbary is asked for");
+  if (d_gbary && !d_attr) return fail(ctx, SRZ_E_INVALID, fn + ": d_gbary needs the attributes");
+  size_t attr_bytes = 0;
+  if (int rc = check_interp(ctx, fs, fn, n_ch, attr_frames, attr_tris, flags, &attr_bytes)) return rc;
+  const size_t gout_bytes = srz_frameset_interpolate_bytes(ctx, fs, n_ch), gbary_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u);
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if ((((uintptr_t)d_vis | (uintptr_t)d_gout | (uintptr_t)d_gbary) & 15u) != 0)
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers must be 16-byte aligned");
+  if ((((uintptr_t)d_attr | (uintptr_t)d_gattr) & 3u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": attributes and their gradient must be 4-byte aligned");
+  const void *outs[2] = {d_gattr, d_gbary};
+  const size_t out_sizes[2] = {attr_bytes, gbary_bytes};
+  for (int i = 0; i < 2; ++i)
+    if (ranges_overlap(outs[i], out_sizes[i], d_vis, vis_bytes) || ranges_overlap(outs[i], out_sizes[i], d_gout, gout_bytes) ||
+        ranges_overlap(outs[i], out_sizes[i], d_attr, attr_bytes))
+      return fail(ctx, SRZ_E_INVALID, fn + ": an output overlaps an input");
+  if (ranges_overlap(d_gattr, attr_bytes, d_gbary, gbary_bytes)) return fail(ctx, SRZ_E_INVALID, fn + ": the two outputs overlap");
+  if (int rc = check_renderable(ctx, fs)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const hipStream_t s = pick_stream(ctx, stream);
+  InterpArgs a = interp_args(fs, d_vis, d_attr, n_ch, attr_frames, attr_tris, 2u, d_gbary, flags);
+  a.gout = (const float *)d_gout, a.gattr = d_gattr;
+  launch_interp_grad(a, s);
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
 int srz_frameset_update_shading(srz_ctx *ctx, srz_frameset *fs, const srz_frame *frames, int n_frames) {
   if (!ctx) return SRZ_E_INVALID;
   if (!fs || !frames) return fail(ctx, SRZ_E_INVALID, "srz_frameset_update_shading: null frameset / frames");

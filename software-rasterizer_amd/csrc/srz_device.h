@@ -275,6 +275,29 @@ __host__ __device__ constexpr uint32_t motion_planes(uint32_t what) {
   return ((what & SRZ_MV_FLOW) ? 2u : 0u) + ((what & SRZ_MV_DEPTH) ? 1u : 0u) + ((what & SRZ_MV_TARGET) ? 2u : 0u);
 }
 void launch_motion(const MotionArgs &a, hipStream_t s);
+// srz_frameset_interpolate / _interpolate_grad: caller attributes [attr frame][triangle][corner][channel] under each pixel's
+// barycentrics (k_interp), and the gradients of that with respect to the attributes and to alpha, beta (k_interp_grad).  vis as
+// above; `out` is the forward's [frame][n_ch][local_rows][width] or the backward's gbary [frame][2][local_rows][width] (may be null
+// there); `out` / `frame_stride` / `local_rows` / the shard are what tile_rect reads.  The host has checked attr_tris >= every
+// frame's triangle count
+struct InterpArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *attr;          // (backward: may be null when gbary is)
+  float *out;
+  const float *gout;          // backward: [frame][n_ch][local_rows][width]
+  float *gattr;               // backward: attr's shape, added into (may be null)
+  uint64_t vis_stride;        // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride;      // floats per frame in out
+  uint64_t gout_stride;       // floats per frame in gout = n_ch * local_rows * width
+  uint64_t attr_frame_stride; // floats per frame in attr / gattr = attr_tris * 3 * n_ch; 0: one array for every frame
+  uint32_t n_ch;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_interp(const InterpArgs &a, hipStream_t s);
+void launch_interp_grad(const InterpArgs &a, hipStream_t s);
 void launch_resolve8(const float *planes, uint8_t *out, uint32_t n_frames, uint32_t rows, uint32_t W, uint64_t frame_stride,
                      hipStream_t s);
 void launch_deinterleave(const void *gathered, void *full, uint32_t world, uint32_t n_fp, uint32_t bands_per_rank, uint32_t row_bytes,

@@ -1307,7 +1307,8 @@ __device__ __forceinline__ void s_shade(M &m, const FrameK &K, const ShadeDesc &
 //    tile_rect — shade_tile, behind the FrameDesc loads (and k_shade_vis's shade_tile, head)
 //    (k_gbuffer CALLS tile_rect, the owner-id constants, v_normalized, normalize3, s_texel and cvt_rne_i32; its copy of v_shade's prologue
 //    and fetch and of shade_bary_v / _s's interpolation names them; k_motion CALLS tile_rect, the owner-id constants and load_pos9, its
-//    copy of cover_v / cover_s's z interpolation names them)
+//    copy of cover_v / cover_s's z interpolation names them; k_interp and k_interp_grad CALL tile_rect, quad_store, quad_at and the
+//    owner-id constants, their copy of shade_bary_v / _s's uv interpolation names them)
 //    frame_k — class_pass, head
 //    shade_bary_v / _s — the second half of shade_pixel_v / _s
 // (copies without a helper: k_shade_vis's compaction and batch-by-batch loop, of k_shade's; k_visibility's o[3][4], of quad_load / quad_at)
@@ -3437,6 +3438,371 @@ __global__ __launch_bounds__(256) void k_motion(MotionArgs a) {
 }
 
 // ================================================================================================================
+// k_interp — CALLER ATTRIBUTES OVER A VISIBILITY BUFFER (srz_frameset_interpolate, include/srz.h): channel ch of the owner's three
+// corner values [triangle][corner][channel] under the pixel's α, β, γ, interpolated as the owner's class interpolates uv
+// (shade_bary_v: fma chain; shade_bary_s: products and sums).  k_gbuffer's shape: no work lists, no LDS, no barrier; the grid walks
+// every (frame, 32x32 tile) in k_shade_vis's XCD order, a thread owns 4 consecutive pixels of one row, its 4 ids arrive in one
+// 16-byte load, α and β only for a quad with an owner, every plane leaves through quad_store.  The ids, α, β and γ are loaded and
+// formed once; a wave-uniform loop then runs over the channels in register chunks of ATTR_CHUNK, the tail chunk masked, so that 64
+// channels cost the registers of 4.  The attribute array is only 4-byte aligned: 3 dwords per owned pixel and channel, gathered.
+// The floor is the memory system: 4 bytes of id per pixel; 8 of α and β and 12 n_ch of gather per owned pixel; 4 n_ch written per
+// pixel.
+// ================================================================================================================
+constexpr uint32_t ATTR_CHUNK = 4;
+__device__ __forceinline__ float interp_ch(bool isS, float alpha, float beta, float gamma, float a, float b, float c) {
+  return isS ? alpha * a + beta * b + gamma * c             // (shade_bary_s)
+             : fmaf_(alpha, a, fmaf_(beta, b, gamma * c));  // (shade_bary_v)
+}
+__global__ __launch_bounds__(256) void k_interp(InterpArgs a) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  const uint32_t C = a.n_ch;
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
+  for (uint32_t j = blockIdx.x >> 3;; j += step) {
+    uint32_t f, t;
+    if (a.n_frames >= 8u) {
+      f = sub + 8u * (j / tpf), t = j % tpf;
+      if (f >= a.n_frames) break;
+    } else {
+      const uint32_t i = j * 8u + sub;
+      if (i >= n_items) break;
+      f = i / tpf, t = i % tpf;
+    }
+    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
+    const TileRect rc = tile_rect(a, fd, f, lb, tx);
+    const int W = fd->width;
+    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
+    if (!(y <= rc.ty1 && x4 <= rc.tx1)) continue; // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool whole = (W & 3) == 0 && x4 + 3 <= rc.tx1;
+    const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
+    const size_t poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)x4;
+    const float *gv = a.vis + (size_t)f * a.vis_stride + poff; // plane 0 (z: never read)
+    float *go = rc.out0 + (size_t)ly * (size_t)W + (size_t)x4;
+    // ---- 1. owner ids (index + 1 | S class; 0 or an index outside the frame's triangles: nobody)
+    uint32_t id[4] = {0u, 0u, 0u, 0u};
+    if (whole) {
+      const uint4 q = *reinterpret_cast<const uint4 *>(gv + rc.plane);
+      id[0] = q.x, id[1] = q.y, id[2] = q.z, id[3] = q.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (x4 + k <= rc.tx1) id[k] = f2u(gv[rc.plane + k]);
+    }
+    const uint32_t n_tris = fd->n_tris;
+    uint32_t own = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if ((id[k] & ~S_CLASS_BIT) - 1u >= n_tris) id[k] = 0u; // (0 and the bare class bit wrap to 0xffffffff)
+      own |= id[k] != 0u ? 1u << k : 0u;
+    }
+    if (own == 0u && !fused) continue;
+    // ---- 2. α, β of a quad with an owner, each owner's γ by its class
+    float4 al = make_float4(0.f, 0.f, 0.f, 0.f), be = al, ga = al;
+    if (own != 0u) {
+      if (whole) {
+        al = *reinterpret_cast<const float4 *>(gv + 2 * rc.plane), be = *reinterpret_cast<const float4 *>(gv + 3 * rc.plane);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (x4 + k <= rc.tx1) quad_at(al, k) = gv[2 * rc.plane + k], quad_at(be, k) = gv[3 * rc.plane + k];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) // (cover_s / cover_v)
+        quad_at(ga, k) = (id[k] & S_CLASS_BIT) ? 1.0f - quad_at(al, k) - quad_at(be, k) : 1.0f - (quad_at(al, k) + quad_at(be, k));
+    }
+    const SRZ_CAS float *at = as_const(a.attr) + (size_t)f * a.attr_frame_stride;
+    const bool quads = fused || own == 15u; // whole quads (fused clear, or four owners), else the owned pixels only
+    // ---- 3. the channels, ATTR_CHUNK at a time
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 q[ATTR_CHUNK];
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) q[i] = make_float4(0.f, 0.f, 0.f, 0.f); // nobody: zeros
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (id[k] == 0u) continue;
+        const SRZ_CAS float *p = at + (size_t)((id[k] & ~S_CLASS_BIT) - 1u) * (3u * C) + c0;
+        const bool isS = (id[k] & S_CLASS_BIT) != 0u;
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+          if (i < nc) quad_at(q[i], k) = interp_ch(isS, quad_at(al, k), quad_at(be, k), quad_at(ga, k), p[i], p[C + i], p[2u * C + i]);
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+        if (i >= nc) break;
+        float *p = go + (size_t)(c0 + i) * rc.plane;
+        if (quads) {
+          quad_store(p, rc.plane, {q[i]}, whole, x4, rc.tx1);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (own & (1u << k)) p[k] = quad_at(q[i], k);
+        }
+      }
+    }
+  }
+}
+
+// ================================================================================================================
+// k_interp_grad — THE BACKWARD OF k_interp (srz_frameset_interpolate_grad): per owned pixel and channel, w[corner] * gout added into
+// the attribute gradient of the owner (gattr), and the gradient with respect to α and β (gbary: fma chain over the channels, from
+// registers, no atomics).  The same walk and the same loads as k_interp, plus gout's quads, chunk by chunk.
+// One global float atomic per (pixel, corner, channel) would be several times the forward pass's bytes at the ≈1.3 TB/s the chip adds
+// at, and collapses further when the adds of a wave scatter; neighbouring pixels share owners, so the sums are combined before they
+// leave the CU:
+//   1. a thread adds up its quad, run of equal owner by run (one run almost always);
+//   2. the quads of one owner that are neighbours in a tile row (8 lanes) are added up by a segmented scan on DPP row shifts; the
+//      last lane of each run holds its sum;
+//   3. that sum goes into the tile's table of distinct owners in LDS (open addressing on the triangle index, IG_PROBES probes, LDS
+//      float adds, 3 * ATTR_CHUNK floats per slot); an owner that finds no slot adds straight to memory — correct, only slower;
+//   4. after a barrier the table is flushed: the used slots are listed, so consecutive lanes add consecutive (corner, channel)
+//      floats of one triangle, triangle after triangle, with global_atomic_add_f32.
+// Global adds are thus per (tile, distinct owner, corner, channel).  The table's keys live for the whole tile, its values for one chunk.
+// Every thread of the workgroup reaches every barrier: a thread outside the frame owns nothing instead of moving on.
+// ================================================================================================================
+constexpr uint32_t IG_SLOT_BITS = 7, IG_SLOTS = 1u << IG_SLOT_BITS, IG_PROBES = 4, IG_VALS = 3 * ATTR_CHUNK;
+struct InterpTable {
+  uint32_t key[IG_SLOTS];  // triangle index + 1; 0: free
+  uint32_t used[IG_SLOTS]; // the slots taken, in arrival order
+  uint32_t n_used;
+  float val[IG_SLOTS * IG_VALS]; // [slot][corner][channel of the chunk]
+};
+// (no-return hardware add; the memory is the caller's ordinary device memory, include/srz.h says so)
+__device__ __forceinline__ void global_add(float *p, float v) { unsafeAtomicAdd(p, v); }
+__device__ __forceinline__ float quad_pick(const float4 &v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; } // (k: a variable)
+template <int CTRL> __device__ __forceinline__ uint32_t dpp_u32(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false); // (a lane without a source in its row: 0)
+}
+constexpr int DPP_ROW_SHL1 = 0x101, DPP_ROW_SHR1 = 0x111, DPP_ROW_SHR2 = 0x112, DPP_ROW_SHR4 = 0x114;
+template <int CTRL> __device__ __forceinline__ void ig_scan_step(float (&acc)[IG_VALS], uint32_t &stop) {
+  const uint32_t up_stop = dpp_u32<CTRL>(stop);
+#pragma unroll
+  for (uint32_t e = 0; e < IG_VALS; ++e) {
+    const float up = u2f(dpp_u32<CTRL>(f2u(acc[e])));
+    if (!stop) acc[e] += up;
+  }
+  stop |= up_stop;
+}
+__device__ __forceinline__ void ig_emit(InterpTable &tb, uint32_t key, const float (&acc)[IG_VALS], uint32_t nc, float *gattr, uint32_t C,
+                                        uint32_t c0) {
+  uint32_t h = (key * 0x9e3779b1u) >> (32u - IG_SLOT_BITS);
+  bool found = false;
+  for (uint32_t p = 0; p < IG_PROBES && !found; ++p) {
+    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
+    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= IG_SLOTS)
+    found = old == 0u || old == key;
+    if (!found) h = (h + 1u) & (IG_SLOTS - 1u);
+  }
+  if (found) {
+#pragma unroll
+    for (uint32_t e = 0; e < IG_VALS; ++e)
+      if ((e % ATTR_CHUNK) < nc) atomicAdd(&tb.val[h * IG_VALS + e], acc[e]);
+  } else {
+    float *g = gattr + (size_t)(key - 1u) * (3u * C) + c0;
+#pragma unroll
+    for (uint32_t e = 0; e < IG_VALS; ++e)
+      if ((e % ATTR_CHUNK) < nc) global_add(g + (e / ATTR_CHUNK) * C + (e % ATTR_CHUNK), acc[e]);
+  }
+}
+__global__ __launch_bounds__(256) void k_interp_grad(InterpArgs a) {
+  __shared__ InterpTable tb;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  const uint32_t C = a.n_ch;
+  const bool want_attr = a.gattr != nullptr, want_bary = a.out != nullptr;
+  if (want_attr) {
+    for (uint32_t i = tid; i < IG_SLOTS; i += 256) tb.key[i] = 0u;
+    for (uint32_t i = tid; i < IG_SLOTS * IG_VALS; i += 256) tb.val[i] = 0.0f;
+    if (tid == 0) tb.n_used = 0u;
+    __syncthreads();
+  }
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
+  for (uint32_t j = blockIdx.x >> 3;; j += step) {
+    uint32_t f, t;
+    if (a.n_frames >= 8u) {
+      f = sub + 8u * (j / tpf), t = j % tpf;
+      if (f >= a.n_frames) break;
+    } else {
+      const uint32_t i = j * 8u + sub;
+      if (i >= n_items) break;
+      f = i / tpf, t = i % tpf;
+    }
+    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
+    const TileRect rc = tile_rect(a, fd, f, lb, tx);
+    const int W = fd->width;
+    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
+    const bool inside = y <= rc.ty1 && x4 <= rc.tx1; // (a thread outside the frame owns nothing, and still meets the barriers)
+    const bool whole = (W & 3) == 0 && x4 + 3 <= rc.tx1;
+    const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
+    const size_t poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)x4;
+    const float *gv = a.vis + (size_t)f * a.vis_stride + poff; // plane 0 (z: never read)
+    const float *gg = a.gout + (size_t)f * a.gout_stride + poff;
+    // ---- 1. owner ids (index + 1 | S class; 0 or an index outside the frame's triangles: nobody)
+    uint32_t id[4] = {0u, 0u, 0u, 0u};
+    if (inside) {
+      if (whole) {
+        const uint4 q = *reinterpret_cast<const uint4 *>(gv + rc.plane);
+        id[0] = q.x, id[1] = q.y, id[2] = q.z, id[3] = q.w;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (x4 + k <= rc.tx1) id[k] = f2u(gv[rc.plane + k]);
+      }
+    }
+    const uint32_t n_tris = fd->n_tris;
+    uint32_t own = 0u, first = 0u;
+    bool one_owner = true; // every owned pixel of the quad has the same triangle (either class)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if ((id[k] & ~S_CLASS_BIT) - 1u >= n_tris) id[k] = 0u; // (0 and the bare class bit wrap to 0xffffffff)
+      if (id[k] == 0u) continue;
+      own |= 1u << k;
+      const uint32_t key = id[k] & ~S_CLASS_BIT;
+      one_owner = one_owner && (first == 0u || first == key);
+      first = first == 0u ? key : first;
+    }
+    // ---- 2. α, β of a quad with an owner, each owner's γ by its class
+    float4 al = make_float4(0.f, 0.f, 0.f, 0.f), be = al, ga = al;
+    if (own != 0u) {
+      if (whole) {
+        al = *reinterpret_cast<const float4 *>(gv + 2 * rc.plane), be = *reinterpret_cast<const float4 *>(gv + 3 * rc.plane);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (x4 + k <= rc.tx1) quad_at(al, k) = gv[2 * rc.plane + k], quad_at(be, k) = gv[3 * rc.plane + k];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) // (cover_s / cover_v)
+        quad_at(ga, k) = (id[k] & S_CLASS_BIT) ? 1.0f - quad_at(al, k) - quad_at(be, k) : 1.0f - (quad_at(al, k) + quad_at(be, k));
+    }
+    const SRZ_CAS float *at = as_const(a.attr) + (size_t)f * a.attr_frame_stride;
+    float *gat = a.gattr + (size_t)f * a.attr_frame_stride;
+    // the key a quad of one owner takes into the row's scan; 0: the quad emits its runs itself, or has none
+    const uint32_t skey = want_attr && own != 0u && one_owner ? first : 0u;
+    const bool scan = want_attr && __builtin_amdgcn_ballot_w64(skey != 0u) != 0ull; // (wave-uniform)
+    const uint32_t pos = (uint32_t)lane & 7u;
+    // (every lane executes both shifts: a lane that skipped one behind a short-circuit would be missing as its neighbour's source)
+    const uint32_t key_left = dpp_u32<DPP_ROW_SHR1>(skey), key_right = dpp_u32<DPP_ROW_SHL1>(skey);
+    const bool seg_head = (pos == 0u) | (key_left != skey) | (skey == 0u); // (a quad without a key takes no carry)
+    const bool seg_last = (pos == 7u) | (key_right != skey);
+    float4 da = make_float4(0.f, 0.f, 0.f, 0.f), db = da;
+    uint32_t n_used = 0u;
+    // ---- 3. the channels, ATTR_CHUNK at a time
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 g[ATTR_CHUNK]; // gout of the chunk's channels; words of nobody's pixels are loaded with their quad at most, never used
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (own != 0u) {
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+          if (i >= nc) break;
+          const float *p = gg + (size_t)(c0 + i) * rc.plane;
+          if (whole) {
+            g[i] = *reinterpret_cast<const float4 *>(p);
+          } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (own & (1u << k)) quad_at(g[i], k) = p[k];
+          }
+        }
+      }
+      float acc[IG_VALS];
+#pragma unroll
+      for (uint32_t e = 0; e < IG_VALS; ++e) acc[e] = 0.0f;
+      if (want_bary) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (id[k] == 0u) continue;
+          const SRZ_CAS float *p = at + (size_t)((id[k] & ~S_CLASS_BIT) - 1u) * (3u * C) + c0;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float gi = quad_at(g[i], k), c = p[2u * C + i];
+              quad_at(da, k) = fmaf_(gi, p[i] - c, quad_at(da, k)), quad_at(db, k) = fmaf_(gi, p[C + i] - c, quad_at(db, k));
+            }
+        }
+      }
+      if (want_attr) {
+        uint32_t cur = 0u; // the open run's key
+        if (skey != 0u) { // one owner: the quad is one run, summed from the registers as they stand
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (id[k] != 0u)
+#pragma unroll
+              for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+                if (i < nc) {
+                  const float gi = quad_at(g[i], k);
+                  acc[i] += quad_at(al, k) * gi, acc[ATTR_CHUNK + i] += quad_at(be, k) * gi, acc[2 * ATTR_CHUNK + i] += quad_at(ga, k) * gi;
+                }
+        } else if (own != 0u) { // several owners (an edge crosses the quad): pixel after pixel, a run that ends goes into the table
+#pragma nounroll
+          for (int k = 0; k < 4; ++k) {
+            const uint32_t idk = k == 0 ? id[0] : k == 1 ? id[1] : k == 2 ? id[2] : id[3];
+            if (idk == 0u) continue;
+            const uint32_t key = idk & ~S_CLASS_BIT;
+            if (cur != 0u && key != cur) {
+              ig_emit(tb, cur, acc, nc, gat, C, c0);
+#pragma unroll
+              for (uint32_t e = 0; e < IG_VALS; ++e) acc[e] = 0.0f;
+            }
+            cur = key;
+            const float wa = quad_pick(al, k), wb = quad_pick(be, k), wc = quad_pick(ga, k);
+#pragma unroll
+            for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+              if (i < nc) {
+                const float gi = quad_pick(g[i], k);
+                acc[i] += wa * gi, acc[ATTR_CHUNK + i] += wb * gi, acc[2 * ATTR_CHUNK + i] += wc * gi;
+              }
+          }
+        }
+        if (scan) { // inclusive segmented scan over the 8 quads of the tile row (Hillis-Steele: a lane past a head takes no carry)
+          uint32_t stop = seg_head ? 1u : 0u; // (position p < d has stop set before the step of distance d: position 0 is a head)
+          ig_scan_step<DPP_ROW_SHR1>(acc, stop);
+          ig_scan_step<DPP_ROW_SHR2>(acc, stop);
+          ig_scan_step<DPP_ROW_SHR4>(acc, stop);
+        }
+        // the last quad of a row's run holds the run's sum; a quad of several owners (a head: the scan left it alone) its last run
+        const uint32_t ekey = skey != 0u ? (seg_last ? skey : 0u) : cur;
+        if (ekey != 0u) ig_emit(tb, ekey, acc, nc, gat, C, c0);
+        // ---- 4. the table's values of this chunk into memory: lanes in (corner, channel) order within a triangle
+        __syncthreads();
+        n_used = tb.n_used;
+        for (uint32_t i = tid; i < n_used * IG_VALS; i += 256) {
+          const uint32_t s = tb.used[i / IG_VALS], e = i % IG_VALS;
+          const float v = tb.val[s * IG_VALS + e];
+          tb.val[s * IG_VALS + e] = 0.0f;
+          if ((e % ATTR_CHUNK) < nc) global_add(gat + (size_t)(tb.key[s] - 1u) * (3u * C) + (e / ATTR_CHUNK) * C + c0 + (e % ATTR_CHUNK), v);
+        }
+        __syncthreads();
+      }
+    }
+    if (want_attr) { // the tile's keys go; every thread has read n_used before the chunk's last barrier
+      for (uint32_t i = tid; i < n_used; i += 256) tb.key[tb.used[i]] = 0u;
+      if (tid == 0) tb.n_used = 0u;
+      __syncthreads();
+    }
+    // ---- 5. dα, dβ: whole quads (fused clear, or four owners), else the owned pixels only
+    if (want_bary && inside && (own != 0u || fused)) {
+      float *go = rc.out0 + (size_t)ly * (size_t)W + (size_t)x4;
+      if (fused || own == 15u) {
+        quad_store(go, rc.plane, {da, db}, whole, x4, rc.tx1);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (own & (1u << k)) go[k] = quad_at(da, k), go[rc.plane + k] = quad_at(db, k);
+      }
+    }
+  }
+}
+
+// ================================================================================================================
 // k_resolve8 — display()'s resolve (src/Render.cpp:61-62): cv::merge(planes 0,1,2) + convertTo(CV_8UC3) =
 // saturate_cast<uchar>(cvRound(v)): round half to even, clamp to [0,255]; NaN → 0.  4 pixels per thread: three 16-byte
 // plane reads → 12 output bytes (three dword stores).
@@ -4016,6 +4382,20 @@ void launch_motion(const MotionArgs &a, hipStream_t s) {
   if (items == 0) return;
   const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (a multiple of 8: workgroup b serves the frames f ≡ b mod 8)
   hipLaunchKernelGGL(k_motion, grid, dim3(256), 0, s, a);
+}
+
+void launch_interp(const InterpArgs &a, hipStream_t s) {
+  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
+  if (items == 0) return;
+  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (a multiple of 8: workgroup b serves the frames f ≡ b mod 8)
+  hipLaunchKernelGGL(k_interp, grid, dim3(256), 0, s, a);
+}
+
+void launch_interp_grad(const InterpArgs &a, hipStream_t s) {
+  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
+  if (items == 0) return;
+  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (as launch_interp)
+  hipLaunchKernelGGL(k_interp_grad, grid, dim3(256), 0, s, a);
 }
 
 bool raster_four_waves(const RenderArgs &a) { return a.n_frames * a.n_local_bands * a.tiles_x <= 4096u; }

@@ -24,7 +24,8 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_read_gathered_frame", "srz_frameset_sparse_capacity", "srz_frameset_sparse_pack", "srz_frameset_sparse_unpack",
            "srz_frameset_allgather_sparse", "srz_frameset_render_visibility", "srz_frameset_shade_visibility",
            "srz_frameset_update_shading", "srz_frameset_shade_kinds", "srz_frameset_gbuffer_bytes", "srz_frameset_gbuffer",
-           "srz_frameset_motion_bytes", "srz_frameset_motion"]
+           "srz_frameset_motion_bytes", "srz_frameset_motion", "srz_frameset_interpolate_bytes", "srz_frameset_interpolate",
+           "srz_frameset_interpolate_grad"]
 
 
 class SrzError(RuntimeError):
@@ -76,6 +77,10 @@ def lib():
         L.srz_frameset_motion_bytes.argtypes = [vp, vp, C.c_uint32]
         L.srz_frameset_motion_bytes.restype = C.c_size_t
         L.srz_frameset_motion.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, C.c_int, C.c_uint32, vp]
+        L.srz_frameset_interpolate_bytes.argtypes = [vp, vp, C.c_uint32]
+        L.srz_frameset_interpolate_bytes.restype = C.c_size_t
+        L.srz_frameset_interpolate.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.c_uint32, vp]
+        L.srz_frameset_interpolate_grad.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp]
         L.srz_frameset_update_shading.argtypes = [vp, vp, C.POINTER(abi.SrzFrame), C.c_int]
         L.srz_sceneset_update.argtypes = [vp, vp, C.POINTER(abi.SrzSceneFrame), C.c_int]
         L.srz_frameset_resolve8.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
@@ -197,6 +202,31 @@ class FrameSet:
         untouched.  MV_TARGET needs an unsharded context.  Asynchronous."""
         self.ctx._check(lib().srz_frameset_motion(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_out_ptr), out_bytes, what, delta,
                                                   flags, _stream(stream)))
+
+    def interpolate_bytes(self, n_ch):
+        """bytes of [frame][n_ch][local_rows][width] float32; 0 for n_ch == 0 or above abi.ATTR_MAX_CH"""
+        return int(lib().srz_frameset_interpolate_bytes(self.ctx.h, self.h, n_ch))
+
+    def interpolate_shape(self, n_ch):
+        """[frame][channel][local_rows][width] float32"""
+        return (self.n_frames, n_ch, self.local_rows, self.width)
+
+    def interpolate(self, d_vis_ptr, d_attr_ptr, n_ch, attr_frames, attr_tris, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """the caller's per-vertex attributes [attr_frames][attr_tris][3][n_ch] float32 (attr_frames: 1 or the frame count) under each
+        pixel's barycentrics of a visibility buffer of this set, each channel interpolated as the owner's class interpolates uv
+        (include/srz.h); pixels nobody owns are zeros with FUSED_CLEAR, else left untouched.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_interpolate(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_attr_ptr), n_ch, attr_frames,
+                                                       attr_tris, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def interpolate_grad(self, d_vis_ptr, d_gout_ptr, d_attr_ptr, n_ch, attr_frames, attr_tris, d_gattr_ptr, d_gbary_ptr, flags=abi.FUSED_CLEAR,
+                         stream=None):
+        """the backward of interpolate: d_gout [frame][n_ch][local_rows][width] → ADDED into d_gattr (the attributes' shape; the order
+        of the adds is unspecified: not bit-reproducible) and / or written to d_gbary [frame][2][local_rows][width] (the gradient with
+        respect to alpha and beta; needs d_attr_ptr).  Either output pointer may be None / 0, not both.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_interpolate_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_gout_ptr),
+                                                            C.c_void_p(d_attr_ptr or None), n_ch, attr_frames, attr_tris,
+                                                            C.c_void_p(d_gattr_ptr or None), C.c_void_p(d_gbary_ptr or None), flags,
+                                                            _stream(stream)))
 
     def update_shading(self, frames):
         """new eye, ka, ks, p, kh, kn, lights, flags and batch shaders / textures for a set made from abi.Frame's, triangles untouched

@@ -19,6 +19,7 @@ GB_NORMAL, GB_UV, GB_BATCH, GB_ALBEDO = 1, 2, 4, 8  # srz_frameset_gbuffer: the 
 GB_ALL = GB_NORMAL | GB_UV | GB_BATCH | GB_ALBEDO
 MV_FLOW, MV_DEPTH, MV_TARGET = 1, 2, 4  # srz_frameset_motion: the groups of `what` (2, 1, 2 planes, in this order)
 MV_ALL = MV_FLOW | MV_DEPTH | MV_TARGET
+ATTR_MAX_CH = 64  # srz_frameset_interpolate: the most channels of one call (SRZ_ATTR_MAX_CH)
 
 # numpy view of srz_tri (96 B): pos[3][3], nrm[3][3], uv[3][2]
 TRI_DTYPE = np.dtype([("pos", "<f4", (3, 3)), ("nrm", "<f4", (3, 3)), ("uv", "<f4", (3, 2))])

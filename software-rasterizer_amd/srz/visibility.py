@@ -112,3 +112,63 @@ def motion_decode(buf, what):
         out["target_s_class"] = (words & S_CLASS_BIT) != 0
         out["target_z"] = f[..., at + 1, :, :]
     return out
+
+
+def _attr_dims(fs, attr):
+    if attr.dtype != torch.float32 or not attr.is_cuda or attr.dim() not in (3, 4) or attr.shape[-2] != 3:
+        raise ValueError(f"interpolate: attr must be a CUDA float32 tensor [T, 3, C] or [n_frames, T, 3, C], got {tuple(attr.shape)} {attr.dtype}")
+    attr_frames = attr.shape[0] if attr.dim() == 4 else 1
+    if attr.dim() == 4 and attr_frames != fs.n_frames:
+        raise ValueError(f"interpolate: attr has {attr_frames} frames, the set {fs.n_frames}")
+    return attr_frames, attr.shape[-3], attr.shape[-1]
+
+
+def _stream_ptr(stream):
+    return torch.cuda.current_stream().cuda_stream if stream is None else stream
+
+
+class _Interpolate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, attr, fs, vis, stream):
+        attr = attr.contiguous()
+        attr_frames, tris, n_ch = _attr_dims(fs, attr)
+        out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=attr.device)
+        fs.interpolate(vis.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris, out.data_ptr(), fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR,
+                       _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.stream, ctx.attr_shape = fs, vis, stream, attr.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        fs, shape = ctx.fs, ctx.attr_shape
+        gout = gout.contiguous()
+        gattr = torch.zeros(shape, dtype=torch.float32, device=gout.device)
+        attr_frames = shape[0] if len(shape) == 4 else 1
+        fs.interpolate_grad(ctx.vis.data_ptr(), gout.data_ptr(), None, shape[-1], attr_frames, shape[-3], gattr.data_ptr(), None,
+                            abi.FUSED_CLEAR, _stream_ptr(ctx.stream))
+        return gattr, None, None, None
+
+
+def interpolate(fs, vis, attr, stream=None):
+    """per-vertex attributes of the caller's own under a visibility buffer `vis` of FrameSet `fs` (a torch tensor of fs.out_shape):
+    attr is a CUDA float32 tensor [T, 3, C] (one array for every frame: poses of one mesh) or [n_frames, T, 3, C], T at least every
+    frame's triangle count, C <= abi.ATTR_MAX_CH, triangle and corner order those of the frame's stream → [n_frames, C, rows, W]
+    float32, zeros where nobody owns the pixel; each channel interpolated exactly as the owner's class interpolates uv
+    (FrameSet.interpolate).  Differentiable with respect to attr (FrameSet.interpolate_grad into a zeroed tensor: float atomics, so
+    attr.grad is not bit-reproducible between runs); vis is not differentiated — interpolate_bary_grad gives the planes to chain
+    into alpha and beta.  stream: a raw stream handle, None = torch's current stream."""
+    return _Interpolate.apply(attr, fs, vis, stream)
+
+
+def interpolate_bary_grad(fs, vis, attr, gout, stream=None):
+    """the gradient of interpolate(fs, vis, attr) with respect to alpha and beta, given gout [n_frames, C, rows, W] →
+    [n_frames, 2, rows, W] float32 (dalpha, dbeta; zeros where nobody owns the pixel).  gamma's share is folded in: the planes are the
+    sums over the channels of gout * (a - c) and gout * (b - c).  Deterministic."""
+    attr, gout = attr.contiguous(), gout.contiguous()
+    attr_frames, tris, n_ch = _attr_dims(fs, attr)
+    if tuple(gout.shape) != tuple(fs.interpolate_shape(n_ch)) or gout.dtype != torch.float32:
+        raise ValueError(f"interpolate_bary_grad: gout must be float32 {fs.interpolate_shape(n_ch)}, got {tuple(gout.shape)} {gout.dtype}")
+    out = torch.empty(fs.interpolate_shape(2), dtype=torch.float32, device=attr.device)
+    fs.interpolate_grad(vis.data_ptr(), gout.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris, None, out.data_ptr(), abi.FUSED_CLEAR,
+                        _stream_ptr(stream))
+    return out
