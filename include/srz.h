@@ -53,6 +53,7 @@ extern "C" {
  *      (additive, same version) the motion pass between frames of a set srz_frameset_motion / srz_frameset_motion_bytes, SRZ_MV_*
  *      (additive, same version) caller attributes over a visibility buffer, with gradients srz_frameset_interpolate /
  *      srz_frameset_interpolate_bytes / srz_frameset_interpolate_grad, SRZ_ATTR_MAX_CH
+ *      (additive, same version) position gradients of a visibility buffer srz_frameset_position_grad
  */
 #define SRZ_ABI_VERSION 7
 
@@ -396,6 +397,39 @@ int srz_frameset_interpolate(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, 
                              uint32_t attr_tris, void *d_out, size_t out_bytes, uint32_t flags, void *stream);
 int srz_frameset_interpolate_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_gout, const float *d_attr, uint32_t n_ch,
                                   uint32_t attr_frames, uint32_t attr_tris, float *d_gattr, void *d_gbary, uint32_t flags, void *stream);
+/* POSITION GRADIENTS of a visibility buffer: the step behind srz_frameset_interpolate_grad's d_gbary — from the loss gradient with
+ * respect to each pixel's alpha and beta (and / or to its depth, plane 0) to the gradient with respect to the owners' SCREEN
+ * POSITIONS, the nine floats ax ay z0 bx by z1 cx cy z2 of a triangle in the dense position stream's order, and to the pixel's own
+ * sample point.  Owners are held fixed: this is the interior term of a differentiable rasteriser; silhouette (coverage) gradients
+ * are not computed.  The chain visibility -> interpolate -> loss -> interpolate_grad -> positions then runs on the device.
+ * d_vis: a visibility buffer of THIS set on this ctx's shard.  d_gbary: [frame][2][local_rows][width] float32, exactly the planes
+ * srz_frameset_interpolate_grad writes (dalpha and dbeta already carry gamma's share).  d_gz: [frame][1][local_rows][width] float32,
+ * the gradient with respect to depth plane 0.  At least one of the two is non-null.  d_gpos: [n_frames][pos_tris][9] float32, 4-byte
+ * aligned, pos_tris at least every frame's triangle count, triangle index that of the visibility buffer; ADDED into: the caller
+ * zeroes it, or accumulates over several calls.  d_gpix: [frame][2][local_rows][width] float32, the gradient with respect to the
+ * pixel's sample point (x, then y); a nobody pixel gets 0 with SRZ_FUSED_CLEAR (frame flags | flags) and is left untouched without
+ * it.  At least one of d_gpos and d_gpix is non-null.  The two-plane buffers hold srz_frameset_interpolate_bytes(2) bytes, d_gz
+ * srz_frameset_interpolate_bytes(1).  Band sharding (each rank adds the partial sums of its own bands), local_rows, stream
+ * semantics, asynchrony, the 16-byte alignment of the visibility buffer and every plane buffer, and owner and nobody
+ * ((id & 0x7fffffff) - 1 < the frame's triangle count) as srz_frameset_interpolate_grad.  The owner's positions are the set's own,
+ * obtained as srz_frameset_motion obtains them: a sceneset runs its vertex stage first.
+ * Per owned pixel, in float32, nothing fused beyond what is written, with P the owner's nine floats and w = (alpha, beta, gamma),
+ * gamma by the owner's class:
+ *   area = (bx - ax) * (cy - ay) - (by - ay) * (cx - ax);  r = 1.0f / area (the IEEE division, both classes)
+ *   da = d_gbary ? dalpha : 0, db likewise;  with d_gz: da = fma(gz, z0 - z2, da), db = fma(gz, z1 - z2, db)
+ *   gx = (da * (by - cy) + db * (cy - ay)) * r;  gy = (da * (cx - bx) + db * (ax - cx)) * r     -> d_gpix, deterministic, bit for bit
+ *   for corner k: gpos[f][t][3k] += (-w[k]) * gx;  [3k + 1] += (-w[k]) * gy;  with d_gz also [3k + 2] += w[k] * gz
+ * (d w_j / d V_k = -w_k grad w_j, grad alpha = (by - cy, cx - bx) / area, grad beta = (cy - ay, ax - cx) / area).  Without d_gz the z
+ * slots receive no add.  THE ORDER OF THE ADDS IS UNSPECIFIED, each add rounds, so d_gpos is NOT BIT-REPRODUCIBLE between launches,
+ * like d_gattr: with n contributing pixels an element lies within n 2^-24 / (1 - n 2^-24) * sum |term| of the exact sum of the
+ * float32 terms; an element with one contributing pixel is exact.  The adds are hardware float atomics: d_gpos must be ordinary
+ * (coarse-grained) device memory.  Non-finite values propagate as IEEE has them (a zero area gives inf or NaN); no input value
+ * makes the pass read or write outside its buffers.  Words of d_gbary and d_gz at nobody pixels never reach a result.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set or d_vis; both of d_gbary and d_gz null, or both of
+ * d_gpos and d_gpix; pos_tris below some frame's triangle count; a misaligned pointer; any bit of `flags` but SRZ_FUSED_CLEAR; an
+ * output that overlaps an input (d_vis, d_gbary, d_gz) or the other output. */
+int srz_frameset_position_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_gbary, const void *d_gz, uint32_t pos_tris,
+                               float *d_gpos, void *d_gpix, uint32_t flags, void *stream);
 /* New SHADING DATA for a set made by srz_frameset_create, its triangles untouched (batches[b].tris is ignored and may be NULL): each
  * frame's eye, ka, ks, p, kh, kn, lights and flags, each batch's shader and tex_id.  The structure must be the set's — frame count, size,
  * light counts, batch counts, n_tris per batch — else SRZ_E_INVALID and the set is unchanged; a sceneset is SRZ_E_INVALID (its shading

@@ -1508,6 +1508,48 @@ int srz_frameset_interpolate_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_
   return SRZ_OK;
 }
 
+int srz_frameset_position_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_gbary, const void *d_gz, uint32_t pos_tris,
+                               float *d_gpos, void *d_gpix, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_position_grad");
+  if (!fs || !d_vis) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer");
+  if (!d_gbary && !d_gz) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gbary nor d_gz is given");
+  if (!d_gpos && !d_gpix) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gpos nor d_gpix is asked for");
+  if ((flags & ~(uint32_t)SRZ_FUSED_CLEAR) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": only SRZ_FUSED_CLEAR is accepted in flags");
+  for (const FrameDesc &d : fs->h_frames)
+    if (d.n_tris > pos_tris) return fail(ctx, SRZ_E_INVALID, fn + ": pos_tris is below a frame's triangle count");
+  const size_t two_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u), one_bytes = srz_frameset_interpolate_bytes(ctx, fs, 1u);
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs), gpos_bytes = (size_t)fs->n_frames * pos_tris * TRI_POS_F * sizeof(float);
+  if ((((uintptr_t)d_vis | (uintptr_t)d_gbary | (uintptr_t)d_gz | (uintptr_t)d_gpix) & 15u) != 0)
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers must be 16-byte aligned");
+  if (((uintptr_t)d_gpos & 3u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": the position gradient must be 4-byte aligned");
+  const void *outs[2] = {d_gpos, d_gpix};
+  const size_t out_sizes[2] = {gpos_bytes, two_bytes};
+  for (int i = 0; i < 2; ++i)
+    if (ranges_overlap(outs[i], out_sizes[i], d_vis, vis_bytes) || ranges_overlap(outs[i], out_sizes[i], d_gbary, two_bytes) ||
+        ranges_overlap(outs[i], out_sizes[i], d_gz, one_bytes))
+      return fail(ctx, SRZ_E_INVALID, fn + ": an output overlaps an input");
+  if (ranges_overlap(d_gpos, gpos_bytes, d_gpix, two_bytes)) return fail(ctx, SRZ_E_INVALID, fn + ": the two outputs overlap");
+  if (int rc = check_renderable(ctx, fs)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const hipStream_t s = pick_stream(ctx, stream);
+  // a sceneset's triangles are its vertex stage's output (as srz_frameset_motion)
+  if (fs->d_draws) launch_vertex(fs->d_draws, fs->n_draws, fs->max_faces, fs->d_tris, fs->d_tri_pos, fs->d_frames, nullptr, s);
+  PosGradArgs a{};
+  const uint64_t plane = fs->local_rows * (uint64_t)fs->width;
+  a.frames = fs->d_frames;
+  a.tri_pos = fs->d_tri_pos ? fs->d_tri_pos : reinterpret_cast<const float *>(fs->d_tris);
+  a.pos_stride = fs->d_tri_pos ? TRI_POS_F : TRI_AOS_F;
+  a.vis = (const float *)d_vis, a.gbary = (const float *)d_gbary, a.gz = (const float *)d_gz, a.gpos = d_gpos, a.out = (float *)d_gpix;
+  a.vis_stride = 4ull * plane, a.frame_stride = 2ull * plane, a.gz_stride = plane, a.gpos_stride = (uint64_t)pos_tris * TRI_POS_F;
+  a.local_rows = fs->local_rows, a.tiles_x = fs->tiles_x, a.n_local_bands = fs->n_local_bands, a.n_frames = (uint32_t)fs->n_frames;
+  a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
+  a.flags_or = flags;
+  launch_pos_grad(a, s);
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
 int srz_frameset_update_shading(srz_ctx *ctx, srz_frameset *fs, const srz_frame *frames, int n_frames) {
   if (!ctx) return SRZ_E_INVALID;
   if (!fs || !frames) return fail(ctx, SRZ_E_INVALID, "srz_frameset_update_shading: null frameset / frames");

@@ -298,6 +298,29 @@ struct InterpArgs {
 };
 void launch_interp(const InterpArgs &a, hipStream_t s);
 void launch_interp_grad(const InterpArgs &a, hipStream_t s);
+// srz_frameset_position_grad: the gradients of a visibility buffer's alpha, beta and depth with respect to the owners' positions
+// (gpos, added into) and to the pixel's sample point (gpix), from the planes k_interp_grad writes (gbary) and / or the gradient of
+// plane 0 (gz) (k_pos_grad).  vis and tri_pos / pos_stride as above; `out` is gpix [frame][2][local_rows][width] (may be null);
+// `out` / `frame_stride` / `local_rows` / the shard are what tile_rect reads.  The host has checked pos_tris >= every frame's
+// triangle count
+struct PosGradArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *tri_pos;  // [triangle * pos_stride], as RenderArgs has it
+  const float *gbary;    // [frame][2][local_rows][width]: frame_stride floats per frame (may be null)
+  const float *gz;       // [frame][1][local_rows][width] (may be null)
+  float *gpos;           // [frame][pos_tris][9], added into (may be null)
+  float *out;
+  uint64_t vis_stride;   // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride; // floats per frame in out and gbary = 2 * local_rows * width
+  uint64_t gz_stride;    // floats per frame in gz = local_rows * width
+  uint64_t gpos_stride;  // floats per frame in gpos = pos_tris * 9
+  uint32_t pos_stride;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_pos_grad(const PosGradArgs &a, hipStream_t s);
 void launch_resolve8(const float *planes, uint8_t *out, uint32_t n_frames, uint32_t rows, uint32_t W, uint64_t frame_stride,
                      hipStream_t s);
 void launch_deinterleave(const void *gathered, void *full, uint32_t world, uint32_t n_fp, uint32_t bands_per_rank, uint32_t row_bytes,

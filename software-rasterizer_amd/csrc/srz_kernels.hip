@@ -1308,7 +1308,8 @@ __device__ __forceinline__ void s_shade(M &m, const FrameK &K, const ShadeDesc &
 //    (k_gbuffer CALLS tile_rect, the owner-id constants, v_normalized, normalize3, s_texel and cvt_rne_i32; its copy of v_shade's prologue
 //    and fetch and of shade_bary_v / _s's interpolation names them; k_motion CALLS tile_rect, the owner-id constants and load_pos9, its
 //    copy of cover_v / cover_s's z interpolation names them; k_interp and k_interp_grad CALL tile_rect, quad_store, quad_at and the
-//    owner-id constants, their copy of shade_bary_v / _s's uv interpolation names them)
+//    owner-id constants, their copy of shade_bary_v / _s's uv interpolation names them; k_pos_grad CALLS the same and load_pos9, its
+//    copy of k_interp_grad's scan, table and flush names them)
 //    frame_k — class_pass, head
 //    shade_bary_v / _s — the second half of shade_pixel_v / _s
 // (copies without a helper: k_shade_vis's compaction and batch-by-batch loop, of k_shade's; k_visibility's o[3][4], of quad_load / quad_at)
@@ -3803,6 +3804,264 @@ __global__ __launch_bounds__(256) void k_interp_grad(InterpArgs a) {
 }
 
 // ================================================================================================================
+// k_pos_grad — GRADIENTS TO VERTEX POSITIONS FROM A VISIBILITY BUFFER (srz_frameset_position_grad, include/srz.h): the step behind
+// k_interp_grad's gbary.  With owners held fixed a pixel's α, β, γ are affine in its sample point (cover_v / cover_s's cross
+// products over the area), ∇α = (by − cy, cx − bx) / area, ∇β = (cy − ay, ax − cx) / area, and moving corner k moves them by
+// −w_k times that gradient.  Per owned pixel, from dα, dβ (gbary) and / or the gradient of the depth plane (gz):
+//   g = (gx, gy), the gradient with respect to the sample point (gpix: from registers, deterministic, bit for bit);
+//   −w_k gx, −w_k gy and, with gz, w_k gz ADDED into the owner's nine floats of gpos (ax ay z0 bx by z1 cx cy z2).
+// k_interp_grad's walk and loads, the gradient quads in place of gout, and load_pos9 of the owner as k_motion has it — once for a
+// quad of one owner.  The nine sums take k_interp_grad's four stages with nine values per owner where it has 3 * ATTR_CHUNK (quad
+// runs; the segmented DPP row scan, every lane executing every shift; the tile's LDS table of distinct owners, an owner without a
+// slot adding straight to memory; the dense flush with global_atomic_add_f32).  pg_scan_step, pg_emit and the flush are COPIES of
+// ig_scan_step, ig_emit and k_interp_grad's step 4 (a helper templated on the value count would be inlined into k_interp_grad too
+// and may move its registers: the project's rule for helpers); a fix goes into both.  What differs, there being no channel loop:
+// the table is emptied by the flush itself — a slot's key is read and zeroed by ONE lane, which hands it to the slot's other eight
+// lanes of the same wave through ds_bpermute; the slot counter alternates between two words by the tile's parity, the idle one
+// zeroed between the barriers — so a tile costs one pair of barriers.
+// Every thread of the workgroup reaches every barrier: a thread outside the frame owns nothing instead of moving on.
+// has_gb / has_gz / want_pos / want_pix are kernel arguments: every branch on them is wave-uniform.
+// The floor is the memory system: 4 bytes of id per pixel; 8 of α and β, 36 of gather and 8 / 4 of gradient planes per owned pixel;
+// 8 written per pixel (gpix); 36 bytes of adds per distinct (tile, owner) pair, at the add rate.
+// ================================================================================================================
+constexpr uint32_t PG_VALS = 9, PG_SLOTS_PER_WAVE = 64 / PG_VALS;
+struct PosGradTable {
+  uint32_t key[IG_SLOTS];  // triangle index + 1; 0: free
+  uint32_t used[IG_SLOTS]; // the slots taken, in arrival order
+  uint32_t n_used[2];      // [tile parity]
+  float val[IG_SLOTS * PG_VALS]; // [slot][corner][x, y, z]
+};
+// what a pixel needs of its owner: the edge differences of ∇α and ∇β, 1 / area, and z0 − z2, z1 − z2
+struct PosGradTri {
+  float by_cy, cy_ay, cx_bx, ax_cx, r, z0_z2, z1_z2;
+};
+__device__ __forceinline__ PosGradTri pg_tri(const SRZ_CAS float *p) {
+  float P[9]; // ax ay z0 bx by z1 cx cy z2
+  load_pos9(p, P);
+  const float area = (P[3] - P[0]) * (P[7] - P[1]) - (P[4] - P[1]) * (P[6] - P[0]);
+  return {P[4] - P[7], P[7] - P[1], P[6] - P[3], P[0] - P[6], 1.0f / area, P[2] - P[8], P[5] - P[8]}; // (the IEEE division)
+}
+// one owned pixel: (gx, gy) from dα, dβ (0 without gbary) and gz; with ACC its nine terms onto acc
+template <bool ACC>
+__device__ __forceinline__ void pg_pixel(const PosGradTri &T, bool has_gz, float da, float db, float gz, float wa, float wb, float wc, float &gx,
+                                         float &gy, float (&acc)[PG_VALS]) {
+  if (has_gz) da = fmaf_(gz, T.z0_z2, da), db = fmaf_(gz, T.z1_z2, db);
+  gx = (da * T.by_cy + db * T.cy_ay) * T.r, gy = (da * T.cx_bx + db * T.ax_cx) * T.r;
+  if (ACC) {
+    acc[0] += (-wa) * gx, acc[1] += (-wa) * gy, acc[3] += (-wb) * gx, acc[4] += (-wb) * gy, acc[6] += (-wc) * gx, acc[7] += (-wc) * gy;
+    if (has_gz) acc[2] += wa * gz, acc[5] += wb * gz, acc[8] += wc * gz;
+  }
+}
+__device__ __forceinline__ void quad_put(float4 &v, int k, float x) { // (k: a variable)
+  v.x = k == 0 ? x : v.x, v.y = k == 1 ? x : v.y, v.z = k == 2 ? x : v.z, v.w = k == 3 ? x : v.w;
+}
+template <int CTRL> __device__ __forceinline__ void pg_scan_step(float (&acc)[PG_VALS], uint32_t &stop) { // (ig_scan_step)
+  const uint32_t up_stop = dpp_u32<CTRL>(stop);
+#pragma unroll
+  for (uint32_t e = 0; e < PG_VALS; ++e) {
+    const float up = u2f(dpp_u32<CTRL>(f2u(acc[e])));
+    if (!stop) acc[e] += up;
+  }
+  stop |= up_stop;
+}
+// (ig_emit; without gz the z slots take no add, here and in the flush)
+__device__ __forceinline__ void pg_emit(PosGradTable &tb, uint32_t par, uint32_t key, const float (&acc)[PG_VALS], bool has_gz, float *gpos) {
+  uint32_t h = (key * 0x9e3779b1u) >> (32u - IG_SLOT_BITS);
+  bool found = false;
+  for (uint32_t p = 0; p < IG_PROBES && !found; ++p) {
+    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
+    if (old == 0u) tb.used[atomicAdd(&tb.n_used[par], 1u)] = h; // (each slot is taken once: n_used <= IG_SLOTS)
+    found = old == 0u || old == key;
+    if (!found) h = (h + 1u) & (IG_SLOTS - 1u);
+  }
+  if (found) {
+#pragma unroll
+    for (uint32_t e = 0; e < PG_VALS; ++e)
+      if (has_gz || e % 3u != 2u) atomicAdd(&tb.val[h * PG_VALS + e], acc[e]);
+  } else {
+    float *g = gpos + (size_t)(key - 1u) * PG_VALS;
+#pragma unroll
+    for (uint32_t e = 0; e < PG_VALS; ++e)
+      if (has_gz || e % 3u != 2u) global_add(g + e, acc[e]);
+  }
+}
+__global__ __launch_bounds__(256) void k_pos_grad(PosGradArgs a) {
+  __shared__ PosGradTable tb;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  const bool want_pos = a.gpos != nullptr, want_pix = a.out != nullptr, has_gb = a.gbary != nullptr, has_gz = a.gz != nullptr;
+  if (want_pos) {
+    for (uint32_t i = tid; i < IG_SLOTS; i += 256) tb.key[i] = 0u;
+    for (uint32_t i = tid; i < IG_SLOTS * PG_VALS; i += 256) tb.val[i] = 0.0f;
+    if (tid < 2) tb.n_used[tid] = 0u;
+    __syncthreads();
+  }
+  uint32_t par = 0u; // the tile's parity in this workgroup's walk (the same in every thread: nobody skips a tile)
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
+  for (uint32_t j = blockIdx.x >> 3;; j += step) {
+    uint32_t f, t;
+    if (a.n_frames >= 8u) {
+      f = sub + 8u * (j / tpf), t = j % tpf;
+      if (f >= a.n_frames) break;
+    } else {
+      const uint32_t i = j * 8u + sub;
+      if (i >= n_items) break;
+      f = i / tpf, t = i % tpf;
+    }
+    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
+    const TileRect rc = tile_rect(a, fd, f, lb, tx);
+    const int W = fd->width;
+    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
+    const bool inside = y <= rc.ty1 && x4 <= rc.tx1; // (a thread outside the frame owns nothing, and still meets the barriers)
+    const bool whole = (W & 3) == 0 && x4 + 3 <= rc.tx1;
+    const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
+    const size_t poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)x4;
+    const float *gv = a.vis + (size_t)f * a.vis_stride + poff; // plane 0 (z: never read)
+    // ---- 1. owner ids (index + 1 | S class; 0 or an index outside the frame's triangles: nobody)
+    uint32_t id[4] = {0u, 0u, 0u, 0u};
+    if (inside) {
+      if (whole) {
+        const uint4 q = *reinterpret_cast<const uint4 *>(gv + rc.plane);
+        id[0] = q.x, id[1] = q.y, id[2] = q.z, id[3] = q.w;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (x4 + k <= rc.tx1) id[k] = f2u(gv[rc.plane + k]);
+      }
+    }
+    const uint32_t n_tris = fd->n_tris;
+    uint32_t own = 0u, first = 0u;
+    bool one_owner = true; // every owned pixel of the quad has the same triangle (either class)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if ((id[k] & ~S_CLASS_BIT) - 1u >= n_tris) id[k] = 0u; // (0 and the bare class bit wrap to 0xffffffff)
+      if (id[k] == 0u) continue;
+      own |= 1u << k;
+      const uint32_t key = id[k] & ~S_CLASS_BIT;
+      one_owner = one_owner && (first == 0u || first == key);
+      first = first == 0u ? key : first;
+    }
+    // ---- 2. α, β and the gradient quads of a quad with an owner, each owner's γ by its class; words of nobody's pixels are loaded
+    //         with their quad at most, never used
+    float4 al = make_float4(0.f, 0.f, 0.f, 0.f), be = al, ga = al, qa = al, qb = al, qz = al;
+    if (own != 0u) {
+      const float *gg = a.gbary + (size_t)f * a.frame_stride + poff, *gz = a.gz + (size_t)f * a.gz_stride + poff;
+      if (whole) {
+        al = *reinterpret_cast<const float4 *>(gv + 2 * rc.plane), be = *reinterpret_cast<const float4 *>(gv + 3 * rc.plane);
+        if (has_gb) qa = *reinterpret_cast<const float4 *>(gg), qb = *reinterpret_cast<const float4 *>(gg + rc.plane);
+        if (has_gz) qz = *reinterpret_cast<const float4 *>(gz);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (own & (1u << k)) {
+            quad_at(al, k) = gv[2 * rc.plane + k], quad_at(be, k) = gv[3 * rc.plane + k];
+            if (has_gb) quad_at(qa, k) = gg[k], quad_at(qb, k) = gg[rc.plane + k];
+            if (has_gz) quad_at(qz, k) = gz[k];
+          }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) // (cover_s / cover_v)
+        quad_at(ga, k) = (id[k] & S_CLASS_BIT) ? 1.0f - quad_at(al, k) - quad_at(be, k) : 1.0f - (quad_at(al, k) + quad_at(be, k));
+    }
+    const SRZ_CAS float *tpos = as_const(a.tri_pos) + (size_t)fd->tri_off * a.pos_stride;
+    float *gpo = a.gpos + (size_t)f * a.gpos_stride;
+    // the key a quad of one owner takes into the row's scan; 0: the quad emits its runs itself, or has none
+    const uint32_t skey = want_pos && own != 0u && one_owner ? first : 0u;
+    const bool scan = want_pos && __builtin_amdgcn_ballot_w64(skey != 0u) != 0ull; // (wave-uniform)
+    const uint32_t pos = (uint32_t)lane & 7u;
+    // (every lane executes both shifts: a lane that skipped one behind a short-circuit would be missing as its neighbour's source)
+    const uint32_t key_left = dpp_u32<DPP_ROW_SHR1>(skey), key_right = dpp_u32<DPP_ROW_SHL1>(skey);
+    const bool seg_head = (pos == 0u) | (key_left != skey) | (skey == 0u); // (a quad without a key takes no carry)
+    const bool seg_last = (pos == 7u) | (key_right != skey);
+    // ---- 3. the pixels: (gx, gy) into qx, qy, the nine terms onto the open run's sums
+    float4 qx = make_float4(0.f, 0.f, 0.f, 0.f), qy = qx; // nobody: zeros
+    float acc[PG_VALS];
+#pragma unroll
+    for (uint32_t e = 0; e < PG_VALS; ++e) acc[e] = 0.0f;
+    uint32_t cur = 0u; // the open run's key (a quad of several owners)
+    if (own != 0u && one_owner) { // one owner: one gather, the quad is one run
+      const PosGradTri T = pg_tri(tpos + (size_t)(first - 1u) * a.pos_stride);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (id[k] == 0u) continue;
+        float gx, gy;
+        if (want_pos)
+          pg_pixel<true>(T, has_gz, quad_at(qa, k), quad_at(qb, k), quad_at(qz, k), quad_at(al, k), quad_at(be, k), quad_at(ga, k), gx, gy, acc);
+        else
+          pg_pixel<false>(T, has_gz, quad_at(qa, k), quad_at(qb, k), quad_at(qz, k), quad_at(al, k), quad_at(be, k), quad_at(ga, k), gx, gy, acc);
+        quad_at(qx, k) = gx, quad_at(qy, k) = gy;
+      }
+    } else if (own != 0u) { // several owners (an edge crosses the quad): pixel after pixel, a run that ends goes into the table
+      PosGradTri T = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; // the open run's owner
+#pragma nounroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t idk = k == 0 ? id[0] : k == 1 ? id[1] : k == 2 ? id[2] : id[3];
+        if (idk == 0u) continue;
+        const uint32_t key = idk & ~S_CLASS_BIT;
+        if (want_pos && cur != 0u && key != cur) {
+          pg_emit(tb, par, cur, acc, has_gz, gpo);
+#pragma unroll
+          for (uint32_t e = 0; e < PG_VALS; ++e) acc[e] = 0.0f;
+        }
+        if (key != cur) T = pg_tri(tpos + (size_t)(key - 1u) * a.pos_stride);
+        cur = key;
+        float gx, gy;
+        if (want_pos)
+          pg_pixel<true>(T, has_gz, quad_pick(qa, k), quad_pick(qb, k), quad_pick(qz, k), quad_pick(al, k), quad_pick(be, k), quad_pick(ga, k), gx, gy, acc);
+        else
+          pg_pixel<false>(T, has_gz, quad_pick(qa, k), quad_pick(qb, k), quad_pick(qz, k), quad_pick(al, k), quad_pick(be, k), quad_pick(ga, k), gx, gy, acc);
+        quad_put(qx, k, gx), quad_put(qy, k, gy);
+      }
+    }
+    if (want_pos) {
+      if (scan) { // inclusive segmented scan over the 8 quads of the tile row (Hillis-Steele: a lane past a head takes no carry)
+        uint32_t stop = seg_head ? 1u : 0u; // (position p < d has stop set before the step of distance d: position 0 is a head)
+        pg_scan_step<DPP_ROW_SHR1>(acc, stop);
+        pg_scan_step<DPP_ROW_SHR2>(acc, stop);
+        pg_scan_step<DPP_ROW_SHR4>(acc, stop);
+      }
+      // the last quad of a row's run holds the run's sum; a quad of several owners (a head: the scan left it alone) its last run
+      const uint32_t ekey = skey != 0u ? (seg_last ? skey : 0u) : cur;
+      if (ekey != 0u) pg_emit(tb, par, ekey, acc, has_gz, gpo);
+      // ---- 4. the table into memory, and emptied: PG_SLOTS_PER_WAVE slots per wave and pass, a slot's nine floats on nine
+      //         consecutive lanes; the slot's first lane reads and frees the key, the others get it from that lane
+      __syncthreads();
+      const uint32_t n_used = tb.n_used[par];
+      if (tid == 0) tb.n_used[par ^ 1u] = 0u; // (last read before the previous tile's second barrier, next added to behind this tile's)
+      const uint32_t sl = (uint32_t)lane / PG_VALS, e = (uint32_t)lane - sl * PG_VALS;
+      for (uint32_t base = (uint32_t)wave * PG_SLOTS_PER_WAVE; base < n_used; base += 4u * PG_SLOTS_PER_WAVE) { // (wave-uniform)
+        const bool on = sl < PG_SLOTS_PER_WAVE && base + sl < n_used;
+        uint32_t s = 0u, key = 0u;
+        if (on) s = tb.used[base + sl];
+        if (on && e == 0u) key = tb.key[s], tb.key[s] = 0u;
+        key = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(sl * PG_VALS) << 2, (int)key); // (every lane executes it)
+        if (on) {
+          const float v = tb.val[s * PG_VALS + e];
+          tb.val[s * PG_VALS + e] = 0.0f;
+          if (has_gz || e % 3u != 2u) global_add(gpo + (size_t)(key - 1u) * PG_VALS + e, v);
+        }
+      }
+      __syncthreads();
+      par ^= 1u;
+    }
+    // ---- 5. gx, gy: whole quads (fused clear, or four owners), else the owned pixels only
+    if (want_pix && inside && (own != 0u || fused)) {
+      float *go = rc.out0 + (size_t)ly * (size_t)W + (size_t)x4;
+      if (fused || own == 15u) {
+        quad_store(go, rc.plane, {qx, qy}, whole, x4, rc.tx1);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (own & (1u << k)) go[k] = quad_at(qx, k), go[rc.plane + k] = quad_at(qy, k);
+      }
+    }
+  }
+}
+
+// ================================================================================================================
 // k_resolve8 — display()'s resolve (src/Render.cpp:61-62): cv::merge(planes 0,1,2) + convertTo(CV_8UC3) =
 // saturate_cast<uchar>(cvRound(v)): round half to even, clamp to [0,255]; NaN → 0.  4 pixels per thread: three 16-byte
 // plane reads → 12 output bytes (three dword stores).
@@ -4396,6 +4655,13 @@ void launch_interp_grad(const InterpArgs &a, hipStream_t s) {
   if (items == 0) return;
   const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (as launch_interp)
   hipLaunchKernelGGL(k_interp_grad, grid, dim3(256), 0, s, a);
+}
+
+void launch_pos_grad(const PosGradArgs &a, hipStream_t s) {
+  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
+  if (items == 0) return;
+  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (as launch_interp)
+  hipLaunchKernelGGL(k_pos_grad, grid, dim3(256), 0, s, a);
 }
 
 bool raster_four_waves(const RenderArgs &a) { return a.n_frames * a.n_local_bands * a.tiles_x <= 4096u; }

@@ -25,7 +25,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_allgather_sparse", "srz_frameset_render_visibility", "srz_frameset_shade_visibility",
            "srz_frameset_update_shading", "srz_frameset_shade_kinds", "srz_frameset_gbuffer_bytes", "srz_frameset_gbuffer",
            "srz_frameset_motion_bytes", "srz_frameset_motion", "srz_frameset_interpolate_bytes", "srz_frameset_interpolate",
-           "srz_frameset_interpolate_grad"]
+           "srz_frameset_interpolate_grad", "srz_frameset_position_grad"]
 
 
 class SrzError(RuntimeError):
@@ -81,6 +81,7 @@ def lib():
         L.srz_frameset_interpolate_bytes.restype = C.c_size_t
         L.srz_frameset_interpolate.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.c_uint32, vp]
         L.srz_frameset_interpolate_grad.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp]
+        L.srz_frameset_position_grad.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp]
         L.srz_frameset_update_shading.argtypes = [vp, vp, C.POINTER(abi.SrzFrame), C.c_int]
         L.srz_sceneset_update.argtypes = [vp, vp, C.POINTER(abi.SrzSceneFrame), C.c_int]
         L.srz_frameset_resolve8.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
@@ -227,6 +228,16 @@ class FrameSet:
                                                             C.c_void_p(d_attr_ptr or None), n_ch, attr_frames, attr_tris,
                                                             C.c_void_p(d_gattr_ptr or None), C.c_void_p(d_gbary_ptr or None), flags,
                                                             _stream(stream)))
+
+    def position_grad(self, d_vis_ptr, d_gbary_ptr, d_gz_ptr, pos_tris, d_gpos_ptr, d_gpix_ptr, flags=abi.FUSED_CLEAR, stream=None):
+        """the step behind interpolate_grad's d_gbary: d_gbary [frame][2][local_rows][width] (dalpha, dbeta) and / or d_gz
+        [frame][1][local_rows][width] (the gradient of depth plane 0) → ADDED into d_gpos [n_frames][pos_tris][9] (ax ay z0 bx by z1 cx
+        cy z2 per triangle; the order of the adds is unspecified: not bit-reproducible) and / or written to d_gpix
+        [frame][2][local_rows][width] (the gradient with respect to the pixel's sample point).  Owners are held fixed; the positions
+        are the set's own.  Either input and either output may be None / 0, not both.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_position_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_gbary_ptr or None),
+                                                         C.c_void_p(d_gz_ptr or None), pos_tris, C.c_void_p(d_gpos_ptr or None),
+                                                         C.c_void_p(d_gpix_ptr or None), flags, _stream(stream)))
 
     def update_shading(self, frames):
         """new eye, ka, ks, p, kh, kn, lights, flags and batch shaders / textures for a set made from abi.Frame's, triangles untouched

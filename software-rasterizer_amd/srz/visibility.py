@@ -172,3 +172,109 @@ def interpolate_bary_grad(fs, vis, attr, gout, stream=None):
     fs.interpolate_grad(vis.data_ptr(), gout.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris, None, out.data_ptr(), abi.FUSED_CLEAR,
                         _stream_ptr(stream))
     return out
+
+
+def _planes_arg(fs, t, n_planes, name):
+    if t is None:
+        return None
+    if t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != tuple(fs.interpolate_shape(n_planes)):
+        raise ValueError(f"position_grad: {name} must be a CUDA float32 tensor {fs.interpolate_shape(n_planes)}, got {tuple(t.shape)} {t.dtype}")
+    return t.contiguous()
+
+
+def _pos_tris(fs, pos_tris):
+    if pos_tris is not None:
+        return int(pos_tris)
+    if not all(hasattr(f, "n_tris") for f in fs.frames):
+        raise ValueError("position_grad: pos_tris must be given for a sceneset (at least every frame's triangle count)")
+    return max(f.n_tris for f in fs.frames)
+
+
+def position_grad(fs, vis, gbary=None, gz=None, pos_tris=None, want_pix=False, stream=None):
+    """the gradient of a loss with respect to the SCREEN POSITIONS of FrameSet `fs`'s triangles, through a visibility buffer `vis` of
+    it, owners held fixed (FrameSet.position_grad, include/srz.h): gbary [n_frames, 2, rows, W] is the loss gradient with respect to
+    each pixel's alpha and beta (interpolate_bary_grad's planes), gz [n_frames, 1, rows, W] the one with respect to depth plane 0; at
+    least one is given.  → gpos [n_frames, T, 3, 3] float32 (triangle, corner, (x, y, z)), T = pos_tris (default: the largest
+    triangle count of the set's frames; a sceneset must name it); with want_pix also gpix [n_frames, 2, rows, W], the gradient with
+    respect to each pixel's sample point (zeros where nobody owns the pixel).  gpos is a sum of float atomics: not bit-reproducible
+    between runs; gpix is deterministic.  stream: a raw stream handle, None = torch's current stream."""
+    if gbary is None and gz is None:
+        raise ValueError("position_grad: neither gbary nor gz is given")
+    gbary, gz = _planes_arg(fs, gbary, 2, "gbary"), _planes_arg(fs, gz, 1, "gz")
+    T = _pos_tris(fs, pos_tris)
+    gpos = torch.zeros((fs.n_frames, T, 3, 3), dtype=torch.float32, device=vis.device)
+    gpix = torch.empty(fs.interpolate_shape(2), dtype=torch.float32, device=vis.device) if want_pix else None
+    fs.position_grad(vis.data_ptr(), gbary.data_ptr() if gbary is not None else None, gz.data_ptr() if gz is not None else None, T,
+                     gpos.data_ptr(), gpix.data_ptr() if want_pix else None, abi.FUSED_CLEAR, _stream_ptr(stream))
+    return (gpos, gpix) if want_pix else gpos
+
+
+class _InterpolateGeo(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, attr, pos, fs, vis, stream):
+        attr = attr.contiguous()
+        attr_frames, tris, n_ch = _attr_dims(fs, attr)
+        if pos.dtype != torch.float32 or pos.dim() != 4 or pos.shape[0] != fs.n_frames or tuple(pos.shape[2:]) != (3, 3):
+            raise ValueError(f"interpolate_geo: pos must be float32 [n_frames, T, 3, 3], got {tuple(pos.shape)} {pos.dtype}")
+        out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=attr.device)
+        fs.interpolate(vis.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris, out.data_ptr(), fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR,
+                       _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.stream, ctx.pos_shape = fs, vis, stream, pos.shape
+        ctx.save_for_backward(attr)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        fs, vis, (attr,) = ctx.fs, ctx.vis, ctx.saved_tensors
+        need_attr, need_pos = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gout = gout.contiguous()
+        attr_frames, tris, n_ch = _attr_dims(fs, attr)
+        sp = _stream_ptr(ctx.stream)
+        # one interpolate_grad call for both of its outputs, then one position_grad call
+        gattr = torch.zeros_like(attr) if need_attr else None
+        gbary = torch.empty(fs.interpolate_shape(2), dtype=torch.float32, device=gout.device) if need_pos else None
+        if need_attr or need_pos:
+            fs.interpolate_grad(vis.data_ptr(), gout.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris,
+                                gattr.data_ptr() if need_attr else None, gbary.data_ptr() if need_pos else None, abi.FUSED_CLEAR, sp)
+        gpos = None
+        if need_pos:
+            gpos = torch.zeros(ctx.pos_shape, dtype=torch.float32, device=gout.device)
+            fs.position_grad(vis.data_ptr(), gbary.data_ptr(), None, ctx.pos_shape[1], gpos.data_ptr(), None, abi.FUSED_CLEAR, sp)
+        return gattr, gpos, None, None, None
+
+
+def interpolate_geo(fs, vis, attr, pos, stream=None):
+    """interpolate(fs, vis, attr), differentiable with respect to the triangles' screen positions too: pos is a CUDA float32 tensor
+    [n_frames, T, 3, 3] (triangle, corner, (x, y, z); T at least every frame's triangle count).  ITS VALUES ARE NEVER READ: the
+    barycentrics are those of `vis` and the positions the set's own, and the caller warrants that pos holds the same positions (it
+    is the graph's handle on them: what the caller's parameters produced and the set was made from).  Backward: attr.grad as
+    interpolate's; pos.grad from one interpolate_grad call (asking for both the attribute gradient and the alpha / beta planes) and
+    one position_grad call.  Owners are held fixed: no silhouette term.  The z column of pos.grad is zero (depth() is the function of
+    z).  Both gradients are sums of float atomics: not bit-reproducible between runs."""
+    return _InterpolateGeo.apply(attr, pos, fs, vis, stream)
+
+
+class _Depth(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, fs, vis, stream):
+        if pos.dtype != torch.float32 or pos.dim() != 4 or pos.shape[0] != fs.n_frames or tuple(pos.shape[2:]) != (3, 3):
+            raise ValueError(f"depth: pos must be float32 [n_frames, T, 3, 3], got {tuple(pos.shape)} {pos.dtype}")
+        ctx.fs, ctx.vis, ctx.stream, ctx.pos_shape = fs, vis, stream, pos.shape
+        return vis[:, 0:1].clone()
+
+    @staticmethod
+    def backward(ctx, gz):
+        fs = ctx.fs
+        gz = gz.contiguous()
+        gpos = torch.zeros(ctx.pos_shape, dtype=torch.float32, device=gz.device)
+        fs.position_grad(ctx.vis.data_ptr(), None, gz.data_ptr(), ctx.pos_shape[1], gpos.data_ptr(), None, abi.FUSED_CLEAR,
+                         _stream_ptr(ctx.stream))
+        return gpos, None, None, None
+
+
+def depth(fs, vis, pos, stream=None):
+    """plane 0 of the visibility buffer `vis` [n_frames, 1, rows, W] as a differentiable function of the triangles' screen positions
+    pos [n_frames, T, 3, 3] (see interpolate_geo: the values of pos are never read, the caller warrants they are the set's):
+    backward is one position_grad call with the incoming gradient as gz — z's own share into the z column, and x, y through the
+    barycentrics.  Words of the incoming gradient at nobody's pixels (depth +inf there in a fused-clear buffer) reach nothing."""
+    return _Depth.apply(pos, fs, vis, stream)
