@@ -205,7 +205,13 @@ int srz_set_shard(srz_ctx *ctx, int rank, int world);
  *      src/TextureLoader.cpp:3-12).  row_stride in bytes. Slots 0..63. ------------------- */
 int srz_texture_upload(srz_ctx *ctx, int tex_id, const uint8_t *bgr, int w, int h, int row_stride);
 
-/* ---- mesh = Mesh::vertices + Mesh::faces (include/object/Mesh.hpp:52-57), slots 0..255; faces = 3 indices each ---- */
+/* ---- mesh = Mesh::vertices + Mesh::faces (include/object/Mesh.hpp:52-57), slots 0..255; faces = 3 indices each ----
+ * n_faces may be 0 (a draw of such a mesh draws nothing).  Uploading to a slot that holds a mesh waits for the ctx's own stream and
+ * FREES the old buffers.  A sceneset keeps the addresses of the buffers its draws named when it was created, so once a slot it draws
+ * is uploaded anew the set must be destroyed, or at least never rendered, shaded or passed to srz_frameset_stats again (every such
+ * call runs the vertex stage over the freed buffers): srz_sceneset_update refuses it with SRZ_E_INVALID whatever the new mesh's
+ * size, which is the one thing left to do with it besides srz_frameset_destroy.  Renders of the set still running on a stream of the
+ * caller's must have finished before the upload.  srz_draw_scene handles all of this itself: it rebuilds its set. */
 int srz_mesh_upload(srz_ctx *ctx, int mesh_id, const srz_vertex *verts, uint32_t n_verts, const uint32_t *faces,
                     uint32_t n_faces);
 

@@ -51,7 +51,9 @@ struct srz_ctx {
     srz_vertex *d_verts = nullptr;
     uint32_t *d_faces = nullptr;
     uint32_t n_verts = 0, n_faces = 0;
+    uint64_t upload = 0; // which srz_mesh_upload of this ctx filled the slot (1, 2, ...): a freed buffer's address can come back, this cannot
   } mesh[MAX_MESH];
+  uint64_t mesh_uploads = 0;
   int timing = 0; // 0 off, 1 whole launch set only (2 events per render), 2 per-kernel groups as well (4 events)
   std::vector<EventPair> ev_pool, ev_used;
   double acc_ms[4] = {0, 0, 0, 0}; // bin, raster, shade, total
@@ -164,6 +166,7 @@ struct srz_frameset {
   unsigned stage_next = 0;
   std::vector<DrawDesc> h_draws;
   std::vector<int> h_draw_mesh;
+  std::vector<uint64_t> h_draw_upload; // the upload each draw's buffers came from (srz_ctx::MeshSlot::upload)
   uint32_t n_draws = 0, max_faces = 0;
   uint64_t sdesc_version = 0;
   uint32_t tiles_x = 0, max_tiles = 0;
@@ -1081,7 +1084,7 @@ int srz_mesh_upload(srz_ctx *ctx, int mesh_id, const srz_vertex *verts, uint32_t
     (void)hipFree(m.d_verts), (void)hipFree(m.d_faces);
     return fail(ctx, SRZ_E_NOMEM, std::string("srz_mesh_upload: ") + hipGetErrorString(e));
   }
-  m.n_verts = n_verts, m.n_faces = n_faces;
+  m.n_verts = n_verts, m.n_faces = n_faces, m.upload = ++ctx->mesh_uploads;
   (void)hipStreamSynchronize(ctx->stream);
   (void)hipFree(ctx->mesh[mesh_id].d_verts), (void)hipFree(ctx->mesh[mesh_id].d_faces);
   ctx->mesh[mesh_id] = m;
@@ -1128,6 +1131,7 @@ static int sceneset_create_impl(srz_ctx *ctx, const srz_scene_frame *frames, int
   if (!frames || n_frames <= 0) return fail(ctx, SRZ_E_INVALID, "srz_sceneset_create: no frames");
   std::vector<DrawDesc> draws;
   std::vector<int> draw_mesh;
+  std::vector<uint64_t> draw_upload;
   uint32_t first = 0; // (a draw's first triangle: the set's triangles are its frames' draws in order)
   for (int f = 0; f < n_frames; ++f) {
     const srz_scene_frame &sf = frames[f];
@@ -1140,7 +1144,7 @@ static int sceneset_create_impl(srz_ctx *ctx, const srz_scene_frame *frames, int
       DrawDesc dd{};
       dd.verts = m.d_verts, dd.faces = m.d_faces, dd.n_faces = m.n_faces, dd.tri_off = first, dd.frame = (uint32_t)f;
       set_draw(dd, sf, dr);
-      draws.push_back(dd), draw_mesh.push_back(dr.mesh_id);
+      draws.push_back(dd), draw_mesh.push_back(dr.mesh_id), draw_upload.push_back(m.upload);
       first += m.n_faces;
     }
   }
@@ -1150,7 +1154,7 @@ static int sceneset_create_impl(srz_ctx *ctx, const srz_scene_frame *frames, int
   srz_frameset *fs = nullptr;
   int rc = build_frameset(ctx, fr.data(), n_frames, &fs, false, false, &draws);
   if (rc) return rc;
-  fs->h_draw_mesh = draw_mesh;
+  fs->h_draw_mesh = draw_mesh, fs->h_draw_upload = draw_upload;
   *out = fs;
   return size_pool ? size_pool_at_create(ctx, out) : SRZ_OK; // (with the matrices of creation: a later srz_sceneset_update is followed by the lazy growth)
 }
@@ -1168,8 +1172,10 @@ int srz_sceneset_update(srz_ctx *ctx, srz_frameset *fs, const srz_scene_frame *f
       return fail(ctx, SRZ_E_INVALID, "srz_sceneset_update: structure changed");
     for (uint32_t k = 0; k < sf.n_draws; ++k, ++di) {
       const srz_mesh_draw &dr = sf.draws[k];
+      // (the slot must still hold the upload the set's draws point into: comparing the buffers' addresses would accept a slot
+      // uploaded twice since, whose new vertex buffer got the old one's address back while the face buffer did not)
       if (dr.mesh_id != fs->h_draw_mesh[di] || dr.mesh_id < 0 || dr.mesh_id >= MAX_MESH ||
-          ctx->mesh[dr.mesh_id].n_faces != fs->h_draws[di].n_faces || ctx->mesh[dr.mesh_id].d_verts != fs->h_draws[di].verts)
+          ctx->mesh[dr.mesh_id].n_faces != fs->h_draws[di].n_faces || ctx->mesh[dr.mesh_id].upload != fs->h_draw_upload[di])
         return fail(ctx, SRZ_E_INVALID, "srz_sceneset_update: mesh binding changed");
     }
   }

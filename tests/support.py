@@ -174,6 +174,52 @@ def random_frame(rng, w, h, n_tris, flags):
     return abi.Frame(w, h, (0.0, 0.0, float(rng.uniform(0.5, 2.0))), lights, batches, flags, p=float(rng.choice([150.0, 8.0, 2.5])))
 
 
+# ------------------------------------------------------------------------------------------------ the vertex stage
+def xform_div_w(m, v):
+    """the tests' OWN restatement in numpy binary32 of the vertex stage's transform (Tools::to_vec3 of mat4 * vec4 in glm's order, as
+    csrc/srz_kernels.hip xform_div_w and the oracle's orc_vertex_stage have it): (m0 x + m1 y) + (m2 z + m3), divided by the fourth
+    row's.  m: 16 floats, column-major; v: [n, 3].  (The product's host vertex stage is C++, libsrz_host: it takes model / view /
+    projection, not a free normal_m.)"""
+    m, v = np.asarray(m, np.float32).reshape(16), np.asarray(v, np.float32)
+    with np.errstate(all="ignore"):
+        r = [(m[0 * 4 + i] * v[:, 0] + m[1 * 4 + i] * v[:, 1]) + (m[2 * 4 + i] * v[:, 2] + m[3 * 4 + i]) for i in range(4)]
+        return np.stack([r[0] / r[3], r[1] / r[3], r[2] / r[3]], 1)
+
+
+def vertex_stage(verts8, faces, ndc_mvp, normal_m, zscale, zoffset):
+    """Scene::loadTriangleStream restated in numpy binary32 (k_vertex, the oracle's orc_vertex_stage): positions through ndc_mvp with
+    z * zscale + zoffset, normals through normal_m, uv copied, the three vertices of every face gathered -> TRI_DTYPE[n_faces]"""
+    v = np.ascontiguousarray(verts8, np.float32).reshape(-1, 8)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    pos = xform_div_w(ndc_mvp, v[:, 0:3])
+    with np.errstate(all="ignore"):
+        pos[:, 2] = pos[:, 2] * np.float32(zscale) + np.float32(zoffset)
+    nrm = xform_div_w(normal_m, v[:, 3:6])
+    assert pos.dtype == np.float32 and nrm.dtype == np.float32
+    t = np.zeros(len(f), abi.TRI_DTYPE)
+    t["pos"], t["nrm"], t["uv"] = pos[f], nrm[f], v[:, 6:8][f]
+    return t
+
+
+def scene_pair(draws, w, h, eye, lights, zscale, zoffset, flags=abi.FUSED_CLEAR, ctx=None, slots=None, **shading):
+    """One frame both ways.  draws: [(verts8, faces, shader, tex, ndc_mvp, normal_m)]; slots: the mesh slot of each draw (default 0, 1,
+    ...; a slot named twice must be given the same mesh object both times and is uploaded once).  ctx given: the meshes are uploaded
+    to their slots.  -> (abi.SceneFrame of the slots and matrices, abi.Frame whose batches hold vertex_stage()'s triangles)"""
+    slots = list(range(len(draws))) if slots is None else list(slots)
+    assert len(slots) == len(draws)
+    sdraws, batches, seen = [], [], {}
+    for slot, (v, f, shader, tex, mvp, nm) in zip(slots, draws):
+        if slot in seen:
+            assert seen[slot] is v, "one slot, two meshes"
+        elif ctx is not None:
+            ctx.mesh_upload(slot, v, np.asarray(f, np.uint32).reshape(-1, 3))
+        seen[slot] = v
+        sdraws.append((slot, shader, tex, mvp, nm))
+        batches.append((shader, tex, vertex_stage(v, f, mvp, nm, zscale, zoffset)))
+    L = np.asarray(lights, np.float32).reshape(-1, 2, 3)
+    return (abi.SceneFrame(w, h, eye, L, sdraws, zscale, zoffset, flags, **shading), abi.Frame(w, h, eye, L, batches, flags, **shading))
+
+
 # ------------------------------------------------------------------------------------------------ hostile shading inputs
 # Tame geometry, hostile values in everything the SHADERS read (uv, normals, lights, eye, ka / ks / kh / kn, the exponent, the
 # textures' shapes).  A fragment's position is (column, row, depth); the tame defaults put the eye and the lights far above the image
@@ -538,6 +584,16 @@ def render(ctx, frames, flags=abi.FUSED_CLEAR, prefill=None, vis=False):
     (fs.render_visibility if vis else fs.render)(out.data_ptr(), fs.out_bytes, flags, stream())
     torch.cuda.synchronize()
     return fs, out
+
+
+def sceneset_update(ctx, fs, sframes):
+    """srz_sceneset_update of set fs with the abi.SceneFrame's (the binding has no method for it); SrzError when it refuses.  The
+    upload is asynchronous on the context's own stream, which is not ordered against the stream the tests render on: waited for"""
+    import srz
+    sframes = list(sframes)
+    ctx._check(srz.lib().srz_sceneset_update(ctx.h, fs.h, abi.scene_frames_array(sframes), len(sframes)))
+    fs.frames = sframes  # (the set's frames own the arrays the call read: kept alive like the constructor's)
+    ctx.sync()
 
 
 def run(fs, flags=abi.FUSED_CLEAR):

@@ -24,7 +24,7 @@ import torch
 
 from srz import abi
 from support import (HOSTILE_EXPONENTS, HOSTILE_FAMILIES, MIX_ALL, MIX_PLAIN, bits, check_approx, hostile_shading_frame, lit, make_ctx,
-                     oracle_with_probes, register_hostile_textures, run, run_both, same, stream, tolerance_frames, words)
+                     oracle_with_probes, register_hostile_textures, run, run_both, same, stream, tolerance_frames, words, xform_div_w)
 
 pytestmark = pytest.mark.gpu
 
@@ -178,15 +178,6 @@ def test_every_build_kind(hctx, orc, family, parity):
 
 
 # ------------------------------------------------------------------------------------------------ c. the device vertex stage
-def xform_div_w(m, v):
-    """the test's OWN restatement in numpy binary32 of the vertex stage's transform (Tools::to_vec3 of mat4 * vec4 in glm's order, as
-    csrc/srz_kernels.hip xform_div_w and the oracle's orc_vertex_stage have it): (m0 x + m1 y) + (m2 z + m3), divided by the fourth
-    row's.  (The product's host vertex stage is C++, libsrz_host: it takes model / view / projection, not a free normal_m.)"""
-    with np.errstate(all="ignore"):
-        r = [(m[0 * 4 + i] * v[:, 0] + m[1 * 4 + i] * v[:, 1]) + (m[2 * 4 + i] * v[:, 2] + m[3 * 4 + i]) for i in range(4)]
-        return np.stack([r[0] / r[3], r[1] / r[3], r[2] / r[3]], 1)
-
-
 @pytest.mark.parametrize("family", ["normal-nonfinite", "uv-nonfinite", "uv-edge", "uv-overflow"])
 def test_sceneset_vertex_stage(hctx, orc, family):
     """meshes whose vertices carry the hostile attributes; ndc_mvp is the identity (the positions pass unchanged), normal_m is the
