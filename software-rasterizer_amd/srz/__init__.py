@@ -25,7 +25,8 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_allgather_sparse", "srz_frameset_render_visibility", "srz_frameset_shade_visibility",
            "srz_frameset_update_shading", "srz_frameset_shade_kinds", "srz_frameset_gbuffer_bytes", "srz_frameset_gbuffer",
            "srz_frameset_motion_bytes", "srz_frameset_motion", "srz_frameset_interpolate_bytes", "srz_frameset_interpolate",
-           "srz_frameset_interpolate_grad", "srz_frameset_position_grad"]
+           "srz_frameset_interpolate_grad", "srz_frameset_position_grad",
+           "srz_target_create", "srz_target_destroy", "srz_target_clear", "srz_target_draw", "srz_target_read", "srz_target_read_bgr8"]
 
 
 class SrzError(RuntimeError):
@@ -118,6 +119,13 @@ def lib():
         L.srz_frameset_sparse_pack.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_int, vp]
         L.srz_frameset_sparse_unpack.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int, vp]
         L.srz_frameset_allgather_sparse.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_int, vp]
+        L.srz_target_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
+        L.srz_target_destroy.argtypes = [vp, vp]
+        L.srz_target_destroy.restype = None
+        L.srz_target_clear.argtypes = [vp, vp, C.c_int, C.c_int]
+        L.srz_target_draw.argtypes = [vp, vp, C.c_int, vp, C.POINTER(abi.SrzStats)]
+        L.srz_target_read.argtypes = [vp, vp, fp, fp, fp, fp]
+        L.srz_target_read_bgr8.argtypes = [vp, vp, vp]
         _lib = L
     return _lib
 
@@ -339,6 +347,57 @@ class FrameSet:
             pass
 
 
+class Target:
+    """A framebuffer resident in HBM (srz_target_*): z and three colour planes that stay on the device between draws.  It starts
+    cleared (z = +inf, colour 0).  A thin handle: what the planes hold, and when a clear takes place, is the library's business."""
+
+    def __init__(self, ctx, width, height):
+        self.ctx, self.width, self.height = ctx, int(width), int(height)
+        self.h = C.c_void_p()
+        ctx._check(lib().srz_target_create(ctx.h, self.width, self.height, C.byref(self.h)))
+
+    def clear(self, color=True, depth=True):
+        """RenderingPipeline::clear(Buffers): colour planes to 0 and / or z to +inf"""
+        self.ctx._check(lib().srz_target_clear(self.ctx.h, self.h, 1 if color else 0, 1 if depth else 0))
+
+    def draw(self, frameset, primitive=abi.PRIMITIVE_TRIANGLES, want_stats=False):
+        """frame 0 of a 1-frame set of the target's size (FrameSet of abi.Frame's or abi.SceneFrame's), drawn onto what the target
+        holds; asynchronous on the context's own stream unless want_stats.  -> the counters' dict, or None"""
+        st = abi.SrzStats()
+        self.ctx._check(lib().srz_target_draw(self.ctx.h, self.h, primitive, frameset.h, C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+    def read(self, planes=(True, True, True, True)):
+        """(z, c0, c1, c2) as [height, width] float32 arrays.  An entry of `planes` that is False skips that plane (NULL is passed, None
+        comes back); an entry that is a float32 array of the target's shape is read into."""
+        out = []
+        for p in planes:
+            if isinstance(p, np.ndarray):
+                assert p.dtype == np.float32 and p.shape == (self.height, self.width) and p.flags.c_contiguous
+                out.append(p)
+            else:
+                out.append(np.empty((self.height, self.width), np.float32) if p else None)
+        self.ctx._check(lib().srz_target_read(self.ctx.h, self.h, *[None if a is None else _fp(a) for a in out]))
+        return tuple(out)
+
+    def read_bgr8(self):
+        """display()'s 8-bit resolve of the colour planes: [height, width, 3] uint8"""
+        out = np.empty((self.height, self.width, 3), np.uint8)
+        self.ctx._check(lib().srz_target_read_bgr8(self.ctx.h, self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def close(self):
+        if self.h:
+            lib().srz_target_destroy(self.ctx.h, self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Comm:
     """RCCL communicator of the band exchange (srz_comm_*): rank 0 makes the id, the host program distributes it."""
 
@@ -430,6 +489,9 @@ class Context:
 
     def frameset(self, frames):
         return FrameSet(self, frames)
+
+    def target(self, width, height):
+        return Target(self, width, height)
 
     def set_kernel_timing(self, on):
         """False/0: off; 1: whole launch set only (2 events per render); True/2: per-kernel groups as well (4 events)"""

@@ -17,7 +17,8 @@ def declared_functions():
 def test_header_declares_the_expected_entry_points():
     names = declared_functions()
     for must in ("srz_create", "srz_destroy", "srz_draw", "srz_texture_upload", "srz_frameset_create",
-                 "srz_frameset_render", "srz_set_shard", "srz_last_error"):
+                 "srz_frameset_render", "srz_set_shard", "srz_last_error", "srz_target_create", "srz_target_destroy",
+                 "srz_target_clear", "srz_target_draw", "srz_target_read", "srz_target_read_bgr8"):
         assert must in names
 
 

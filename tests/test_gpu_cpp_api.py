@@ -1,11 +1,17 @@
 """-m gpu: the C++ host surface end to end on the device — the reference README's usage (tests/cpp/api_demo.cpp) compiled
 against our headers must run to completion: device vertex stage == host vertex stage bit for bit, device 8-bit resolve ==
 host rounding of the float planes, stats consistent with the z-buffer (the checks are inside the program); the planes of
-its last frame are compared with the oracle here."""
+its last frame are compared with the oracle here.  tests/cpp/target_pipeline.cpp does the same for TraditionalRasterizer::draw over
+several scenes, meshes, shaders and textures, across structure changes, a throw and partial clears."""
 import os
 import subprocess
 
+import numpy as np
 import pytest
+
+from srz import abi
+from srz import scenes as pscenes
+from support import bits, compile_cpp_program, oracle_draws, same
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,3 +35,82 @@ def test_readme_program_runs_on_the_gpu(tmp_path, orc):
     assert rc == 0
     for p in range(4):
         assert np.array_equal(got[p].view(np.uint32), np.ascontiguousarray(ref[p]).view(np.uint32)), p
+
+
+# ------------------------------------------------------------------------------------------------ tests/cpp/target_pipeline.cpp
+TP_W, TP_H = 101, 67
+TP_ONE = [("spot", pscenes.SPOT_OBJ, abi.SHADER_TEXTURE, (-0.15, 0.0, 0.0), 0.3, pscenes.SPOT_TEX),
+          ("Crate", pscenes.CRATE_OBJ, abi.SHADER_PHONG, (0.2, -0.1, 0.1), 0.15, pscenes.CRATE_TEX)]
+TP_TWO = [("bunny", pscenes.BUNNY_OBJ, abi.SHADER_NORMAL, (-0.05, -0.12, 0.12), 2.0)]
+TP_SLOTS = [("spotA", pscenes.SPOT_OBJ, abi.SHADER_TEXTURE, (-0.2, 0.05, 0.0), 0.25, pscenes.SPOT_TEX),
+            ("Crate", pscenes.CRATE_OBJ, abi.SHADER_TEXTURE, (0.05, -0.1, 0.1), 0.15, pscenes.CRATE_TEX),
+            ("spotB", pscenes.SPOT_OBJ, abi.SHADER_TEXTURE, (0.22, 0.0, 0.05), 0.25, pscenes.SPOT_TEX)]
+TP_TEX = 20  # the oracle's texture slots these frames use: TP_TEX + the workload's own slot (the session's oracle is shared)
+
+
+def workload_frame(orc, wl, idx):
+    """frame idx of the workload as the program's host-stage pipeline builds it, flags = 0, its textures registered with the oracle"""
+    f = wl.frame(idx, flags=0)
+    batches = [(f._batches[i].shader, f._batches[i].tex_id + TP_TEX if f._batches[i].tex_id >= 0 else -1, t) for i, t in enumerate(f.tris)]
+    for slot, tex in enumerate(wl.texture_arrays):
+        orc.texture_set(TP_TEX + slot, tex)
+    c = f.c
+    return abi.Frame(c.width, c.height, tuple(c.eye), f.lights, batches, 0, tuple(c.ka), tuple(c.ks), c.p, c.kh, c.kn)
+
+
+def target_pipeline_references(orc):
+    """-> {dump name: the oracle's planes}, {stats name: the oracle's counters}.  From the oracle alone: the second scene takes pixels
+    from the first and loses others to it (the order of the scenes shows); both scenes over their own picture change nothing; the three
+    textured meshes of the slots scene each own pixels, and the picture with the two textures swapped is another one"""
+    one, two = pscenes.Workload("one", TP_W, TP_H, TP_ONE), pscenes.Workload("two", TP_W, TP_H, TP_TWO)
+    refs, stats = {}, {}
+    for name, idx in (("two_scenes", 3), ("after_throw", 5)):
+        frames = [workload_frame(orc, one, idx), workload_frame(orc, two, idx)]
+        after, st = oracle_draws(orc, frames + frames)
+        refs[name] = after[1]
+        if idx == 3:
+            same(after[3], after[1], "the oracle: both scenes over their own picture")
+            stats["two_scenes"] = {k: st[0][k] + st[1][k] for k in st[0]}
+            stats["two_scenes_again"] = {k: st[2][k] + st[3][k] for k in st[0]}
+            owned = np.isfinite(after[0][0])
+            changed = np.logical_or.reduce([bits(after[0][p]) != bits(after[1][p]) for p in range(4)])
+            (alone,), _ = oracle_draws(orc, frames[1:])
+            lost = owned & np.isfinite(alone[0]) & ~changed
+            assert (owned & changed).sum() >= 50 and lost.sum() >= 50 and (~owned & changed).sum() >= 50, \
+                (int((owned & changed).sum()), int(lost.sum()), int((~owned & changed).sum()))
+            assert st[0]["visible_textured"] >= 200 and st[0]["visible"] - st[0]["visible_textured"] >= 100, st[0]  # spot and crate
+    assert any((bits(refs["two_scenes"][p]) != bits(refs["after_throw"][p])).any() for p in range(4))
+    slots = pscenes.Workload("slots", 128, 96, TP_SLOTS)
+    f = workload_frame(orc, slots, 7)
+    assert [b.tex_id for b in f._batches[:3]] == [TP_TEX, TP_TEX + 1, TP_TEX], "two meshes share the first texture, one has its own"
+    (refs["texture_slots"],), _ = oracle_draws(orc, [f])
+    for k in range(3):  # each mesh owns pixels of the picture: without it the picture is another one
+        rest = [(f._batches[i].shader, f._batches[i].tex_id, t) for i, t in enumerate(f.tris) if i != k]
+        (without,), _ = oracle_draws(orc, [abi.Frame(128, 96, tuple(f.c.eye), f.lights, rest, 0)])
+        assert sum(int((bits(without[p]) != bits(refs["texture_slots"][p])).sum()) for p in range(4)) >= 100, k
+    swapped = [(f._batches[i].shader, TP_TEX + (1 - (f._batches[i].tex_id - TP_TEX)), t) for i, t in enumerate(f.tris)]
+    (mixed,), _ = oracle_draws(orc, [abi.Frame(128, 96, tuple(f.c.eye), f.lights, swapped, 0)])
+    assert sum(int((bits(mixed[p]) != bits(refs["texture_slots"][p])).sum()) for p in (1, 2, 3)) >= 1000  # a slot mix-up would show
+    return refs, stats
+
+
+def test_target_pipeline_program(tmp_path, orc):
+    """tests/cpp/target_pipeline.cpp once: inside it, the device vertex stage against the host one over two scenes in one pipeline,
+    with and without stats, display() at 101 x 67 and 128 x 96, shared and own TextureLoaders, a mesh added / shrunk / restored /
+    emptied between draws, the unbound-shader throw and clear(Color).  Here: the three plane sets it dumps against the oracle's draws
+    of the same frames (scene by scene onto one another), and its summed counters against the oracle's."""
+    refs, rstats = target_pipeline_references(orc)
+    exe = compile_cpp_program("target_pipeline", tmp_path)
+    prefix = str(tmp_path / "dump_")
+    r = subprocess.run([exe, REPO, prefix], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    got = {}
+    for line in r.stdout.splitlines():
+        w = line.split()
+        if w[:1] == ["STATS"]:
+            got[w[1]] = {kv.split("=")[0]: int(kv.split("=")[1]) for kv in w[2:]}
+    assert got == rstats, (got, rstats)
+    for name, ref in refs.items():
+        h, w = ref[0].shape
+        planes = np.fromfile(prefix + name + ".f32", np.float32).reshape(4, h, w)
+        same(planes, ref, f"target_pipeline {name}")

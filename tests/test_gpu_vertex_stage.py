@@ -13,7 +13,8 @@ import torch
 
 from srz import abi
 from srz import scenes as pscenes
-from support import big_tris, bits, ctx, render, same, scene_pair, sceneset_update, stream  # noqa: F401  (ctx: the fixture)
+from support import (big_tris, bits, col_major, ctx, place, render, same, scene_pair, sceneset_update, stream,  # noqa: F401  (ctx: the fixture)
+                     unshared_mesh)
 
 pytestmark = pytest.mark.gpu
 
@@ -77,17 +78,6 @@ def oracle(orc, f):
     return ref, st
 
 
-def col_major(rows):
-    """a 4 x 4 matrix written row by row -> the 16 floats of glm's layout m[col * 4 + row]"""
-    return np.asarray(rows, np.float64).T.astype(F32).reshape(16)
-
-
-def place(sx, sy, ox, oy, w=2.0, sz=1.0, oz=0.0):
-    """unit coordinates -> pixels: x' = sx x + ox, y' = sy y + oy, z' = sz z + oz, every row scaled by w and divided by it again
-    (w a power of two: the division is exact, but it is a division by something other than 1)"""
-    return col_major([[sx * w, 0, 0, ox * w], [0, sy * w, 0, oy * w], [0, 0, sz * w, oz * w], [0, 0, 0, w]])
-
-
 def set_planes(c, frames, flags=abi.FUSED_CLEAR):
     """(the set, its colour render as [n, 4, rows, W] float32 on the host)"""
     fs, out = render(c, frames, flags)
@@ -118,19 +108,6 @@ def check_draw(c, orc, sframe, hframe, what, ref=None):
     assert gst == rst, (what, gst, rst)
     same(gpu, ref, f"{what}: srz_draw_scene against the oracle")
     return rst
-
-
-def unshared_mesh(t, w, h, seed):
-    """TRI_DTYPE triangles in pixels -> (verts8 in unit coordinates, faces): three vertices of its own per triangle, stored in a
-    shuffled order, so that `faces` is no arange"""
-    n = len(t)
-    v = np.zeros((3 * n, 8), F32)
-    v[:, 0:3] = t["pos"].reshape(-1, 3) / np.array([w, h, 1.0])
-    v[:, 3:6], v[:, 6:8] = t["nrm"].reshape(-1, 3), t["uv"].reshape(-1, 2)
-    perm = np.random.default_rng(seed).permutation(3 * n)
-    where = np.empty(3 * n, np.int64)
-    where[perm] = np.arange(3 * n)
-    return v[perm], where.reshape(n, 3).astype(np.uint32)
 
 
 # ------------------------------------------------------------------------------------------------ a. projective positions

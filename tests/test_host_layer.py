@@ -10,7 +10,7 @@ import pytest
 import scenes as oscenes  # tests/scenes.py: oracle-built inputs
 from srz import abi, host
 from srz import scenes as pscenes
-from support import bits
+from support import bits, compile_cpp_program
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -258,6 +258,19 @@ def test_cpp_api_compiles_like_the_readme_and_refuses_to_run_without_a_gpu(tmp_p
         assert r.returncode == 0, r.stderr
     else:
         assert r.returncode == 3 and "no CPU fallback" in r.stderr   # constructor throws std::runtime_error
+
+
+def test_target_pipeline_program_compiles_and_refuses_to_run_without_a_gpu(tmp_path):
+    """tests/cpp/target_pipeline.cpp (the C++ pipeline over the device-resident target; run by tests/test_gpu_cpp_api.py) builds
+    against the headers as they are, and without a device its first constructor throws: exit 3, nothing dumped"""
+    exe = compile_cpp_program("target_pipeline", tmp_path)
+    import torch
+    r = subprocess.run([exe, REPO, str(tmp_path / "dump_")], capture_output=True, text=True, timeout=300)
+    if torch.cuda.is_available():
+        assert r.returncode == 0, (r.stdout, r.stderr)
+    else:
+        assert r.returncode == 3 and "no CPU fallback" in r.stderr, (r.returncode, r.stderr)
+        assert not list(tmp_path.glob("dump_*"))
 
 
 def test_bmp_loader_equals_pillow(tmp_path):
