@@ -54,6 +54,7 @@ extern "C" {
  *      (additive, same version) caller attributes over a visibility buffer, with gradients srz_frameset_interpolate /
  *      srz_frameset_interpolate_bytes / srz_frameset_interpolate_grad, SRZ_ATTR_MAX_CH
  *      (additive, same version) position gradients of a visibility buffer srz_frameset_position_grad
+ *      (additive, same version) silhouette antialiasing of a visibility buffer srz_frameset_antialias / srz_frameset_antialias_grad
  */
 #define SRZ_ABI_VERSION 7
 
@@ -406,8 +407,9 @@ int srz_frameset_interpolate_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_
 /* POSITION GRADIENTS of a visibility buffer: the step behind srz_frameset_interpolate_grad's d_gbary — from the loss gradient with
  * respect to each pixel's alpha and beta (and / or to its depth, plane 0) to the gradient with respect to the owners' SCREEN
  * POSITIONS, the nine floats ax ay z0 bx by z1 cx cy z2 of a triangle in the dense position stream's order, and to the pixel's own
- * sample point.  Owners are held fixed: this is the interior term of a differentiable rasteriser; silhouette (coverage) gradients
- * are not computed.  The chain visibility -> interpolate -> loss -> interpolate_grad -> positions then runs on the device.
+ * sample point.  Owners are held fixed: this is the interior term of a differentiable rasteriser; the silhouette (coverage) term
+ * is srz_frameset_antialias_grad's, below.  The chain visibility -> interpolate -> loss -> interpolate_grad -> positions then runs on
+ * the device.
  * d_vis: a visibility buffer of THIS set on this ctx's shard.  d_gbary: [frame][2][local_rows][width] float32, exactly the planes
  * srz_frameset_interpolate_grad writes (dalpha and dbeta already carry gamma's share).  d_gz: [frame][1][local_rows][width] float32,
  * the gradient with respect to depth plane 0.  At least one of the two is non-null.  d_gpos: [n_frames][pos_tris][9] float32, 4-byte
@@ -436,6 +438,63 @@ int srz_frameset_interpolate_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_
  * output that overlaps an input (d_vis, d_gbary, d_gz) or the other output. */
 int srz_frameset_position_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_gbary, const void *d_gz, uint32_t pos_tris,
                                float *d_gpos, void *d_gpix, uint32_t flags, void *stream);
+/* SILHOUETTE ANTIALIASING of a visibility buffer, and its gradients: planes of the caller's (a shaded image, interpolated attributes,
+ * a render's own four planes) blended across the outlines of the owners, analytically — no higher resolution is rendered — and the
+ * backward of that blend, to the planes and to the SCREEN POSITIONS of the triangles whose edges form the outlines: the silhouette
+ * (coverage) term of a differentiable rasteriser, the one srz_frameset_position_grad does not compute.
+ * d_vis: a visibility buffer of THIS set on this ctx.  d_in, d_out, d_gout, d_gin: [frame][n_ch][local_rows][width] float32,
+ * 1 <= n_ch <= SRZ_ATTR_MAX_CH, srz_frameset_interpolate_bytes(n_ch) bytes.  A render's own four-plane buffer is a valid n_ch = 4
+ * input: the z plane is then blended too.  16-byte alignment of the visibility buffer and every plane buffer, stream semantics and
+ * asynchrony as srz_frameset_interpolate.  Owner and nobody as there: (id & 0x7fffffff) - 1 < the frame's triangle count means an
+ * owner, everything else is nobody; the class bit plays no part.  The positions are the set's own, obtained as
+ * srz_frameset_position_grad obtains them: a sceneset runs its vertex stage first.  SRZ_FUSED_CLEAR is accepted and has no effect:
+ * EVERY pixel of d_out / d_gin is written, and — unlike every other pass over a visibility buffer — the words of d_in at nobody's
+ * pixels DO reach results: they are the background an outline blends with.
+ * THE RULE, all of it float32, nothing fused except where fmaf is written, divisions the IEEE division.  A pixel's sample point is
+ * its integer corner (x, y), as in the motion pass.  Every pair of 4-neighbours inside the image is evaluated, horizontal and
+ * vertical; the evaluation depends on the unordered pair only, so both pixels of a pair see the same answer:
+ *   1. a pair does nothing when both pixels are nobody, or both have an owner with the same triangle index.
+ *   2. N, the nearer pixel, and F, the farther: a nobody is farther than any owner; between two owners N is the right or lower
+ *      pixel iff its z (plane 0) is < the other's — ties and NaN give N = the left or upper pixel.
+ *   3. s = +1 if F lies at the larger coordinate, else -1.  For each vertex v of N's triangle, u_v along the pair's axis (0 at N,
+ *      1 at F) and n_v across it:  horizontal pair  u_v = s * (v.x - xN), n_v = v.y - yN;  vertical pair  u_v = s * (v.y - yN),
+ *      n_v = v.x - xN.
+ *   4. the edges (v0, v1) = (a, b), (b, c), (c, a) in this order; THE edge is the first with
+ *        (n0 <= 0 && n1 > 0) || (n1 <= 0 && n0 > 0)                                    (it straddles the pair's line, half open)
+ *        d = n0 - n1;  k = n0 / d;  t = u0 + k * (u1 - u0);  0 <= t && t <= 1          (it crosses between the two sample points)
+ *      (a NaN fails both).  No such edge: the pair does nothing.
+ *   5. F has an owner and both v0 and v1 occur among the three corners of F's triangle, compared as the three 32-bit words x, y, z:
+ *      the two owners share this edge, an interior edge of a mesh, and the pair does nothing.  (The sets are triangle soups; a
+ *      shared mesh vertex reaches both triangles with identical bits, in a frameset and from the vertex stage alike.)
+ *   6. a = t - 0.5f.  a > 0: the target is F, the source N, w = a (N's triangle covers that share of F's footprint); a < 0: the
+ *      target is N, the source F, w = -a; a == 0: nothing.
+ * FORWARD, deterministic, bit for bit (a gather: no float atomics): for every pixel p and channel,
+ *   acc = in[p];  for q in (x - 1, y), (x + 1, y), (x, y - 1), (x, y + 1), in this order, where q lies inside the image:
+ *   if pair(p, q) has target p: acc = fmaf(w, in[q] - in[p], acc);  out[p] = acc.
+ * BACKWARD: d_gout, the same d_in and the same d_vis; at least one of d_gin and d_gpos is non-null.
+ *   d_gin has the planes' shape, deterministic, bit for bit:  acc = gout[p];  for q in the same order: if the target is p:
+ *   acc = fmaf(-w, gout[p], acc), else if the target is q: acc = fmaf(w, gout[q], acc);  gin[p] = acc.
+ *   d_gpos: [n_frames][pos_tris][9] float32, 4-byte aligned, pos_tris at least every frame's triangle count, ADDED into exactly as
+ *   srz_frameset_position_grad's d_gpos (the caller zeroes it, or accumulates over several calls — the interior term and this one
+ *   into one buffer).  Per pair that has a target, once:
+ *     D = 0;  for ch ascending: D = fmaf(gout[tgt][ch], in[src][ch] - in[tgt][ch], D);   g = a > 0 ? D : -D
+ *     e = u1 - u0;  q = (g * e) / (d * d);  g_u0 = g * (1.0f - k);  g_u1 = g * k;  g_n0 = q * (-n1);  g_n1 = q * n0
+ *     horizontal pair: the x slots of v0, v1 get s * g_u0, s * g_u1, their y slots g_n0, g_n1;  vertical pair: the x slots get
+ *     g_n0, g_n1, the y slots s * g_u0, s * g_u1.
+ *   The slots are those of N's triangle; z slots and F's triangle get no add.  THE ORDER OF THE ADDS IS UNSPECIFIED, each add
+ *   rounds, so d_gpos is NOT BIT-REPRODUCIBLE between launches: with n contributing pairs an element lies within
+ *   n 2^-24 / (1 - n 2^-24) * sum |term| of the exact sum of the float32 terms; an element with one contributing pair is exact.  The
+ *   adds are hardware float atomics: d_gpos must be ordinary (coarse-grained) device memory.
+ * Non-finite values propagate as IEEE has them; no input value makes the passes read or write outside their buffers.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set, d_vis, d_in, d_out (forward), d_gout (backward),
+ * or both of d_gin and d_gpos; n_ch == 0 or above SRZ_ATTR_MAX_CH; a short out_bytes; pos_tris below some frame's triangle count
+ * when d_gpos is given; a misaligned pointer; any bit of `flags` but SRZ_FUSED_CLEAR; an output that overlaps an input (d_vis, d_in,
+ * d_gout) or the other output — in place is not allowed, the forward reads neighbours; a ctx whose shard world is above 1 (a
+ * vertical pair across a band edge needs another rank's rows: the same refusal as SRZ_MV_TARGET). */
+int srz_frameset_antialias(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_in, uint32_t n_ch, void *d_out, size_t out_bytes,
+                           uint32_t flags, void *stream);
+int srz_frameset_antialias_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_in, const void *d_gout, uint32_t n_ch,
+                                void *d_gin, uint32_t pos_tris, float *d_gpos, uint32_t flags, void *stream);
 /* New SHADING DATA for a set made by srz_frameset_create, its triangles untouched (batches[b].tris is ignored and may be NULL): each
  * frame's eye, ka, ks, p, kh, kn, lights and flags, each batch's shader and tex_id.  The structure must be the set's — frame count, size,
  * light counts, batch counts, n_tris per batch — else SRZ_E_INVALID and the set is unchanged; a sceneset is SRZ_E_INVALID (its shading

@@ -1556,6 +1556,87 @@ int srz_frameset_position_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis
   return SRZ_OK;
 }
 
+} // extern "C"
+namespace {
+// what srz_frameset_antialias and _antialias_grad check alike
+int check_antialias(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, uint32_t n_ch, uint32_t flags) {
+  if (n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_ATTR_MAX_CH");
+  if ((flags & ~(uint32_t)SRZ_FUSED_CLEAR) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": only SRZ_FUSED_CLEAR is accepted in flags");
+  if (fs->shard_world > 1)
+    return fail(ctx, SRZ_E_INVALID, fn + ": needs the whole frame on this ctx (a vertical pair across a band edge needs another rank's rows)");
+  return SRZ_OK;
+}
+AntialiasArgs antialias_args(const srz_frameset *fs, const void *d_vis, const void *d_in, uint32_t n_ch, void *d_out) {
+  AntialiasArgs a{};
+  const uint64_t plane = fs->local_rows * (uint64_t)fs->width;
+  a.frames = fs->d_frames;
+  a.tri_pos = fs->d_tri_pos ? fs->d_tri_pos : reinterpret_cast<const float *>(fs->d_tris);
+  a.pos_stride = fs->d_tri_pos ? TRI_POS_F : TRI_AOS_F;
+  a.vis = (const float *)d_vis, a.in = (const float *)d_in, a.out = (float *)d_out;
+  a.vis_stride = 4ull * plane, a.frame_stride = n_ch * plane;
+  a.n_ch = n_ch;
+  a.local_rows = fs->local_rows, a.tiles_x = fs->tiles_x, a.n_local_bands = fs->n_local_bands, a.n_frames = (uint32_t)fs->n_frames;
+  a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
+  return a;
+}
+} // namespace
+extern "C" {
+
+int srz_frameset_antialias(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_in, uint32_t n_ch, void *d_out, size_t out_bytes,
+                           uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_antialias");
+  if (!fs || !d_vis || !d_in || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / input / output");
+  if (int rc = check_antialias(ctx, fs, fn, n_ch, flags)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, n_ch), vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
+  if ((((uintptr_t)d_vis | (uintptr_t)d_in | (uintptr_t)d_out) & 15u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
+  if (ranges_overlap(d_out, need, d_vis, vis_bytes) || ranges_overlap(d_out, need, d_in, need))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the visibility buffer or the input (the pass reads neighbours: not in place)");
+  if (int rc = check_renderable(ctx, fs)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const hipStream_t s = pick_stream(ctx, stream);
+  // a sceneset's triangles are its vertex stage's output (as srz_frameset_position_grad)
+  if (fs->d_draws) launch_vertex(fs->d_draws, fs->n_draws, fs->max_faces, fs->d_tris, fs->d_tri_pos, fs->d_frames, nullptr, s);
+  launch_antialias(antialias_args(fs, d_vis, d_in, n_ch, d_out), s);
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
+int srz_frameset_antialias_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_in, const void *d_gout, uint32_t n_ch,
+                                void *d_gin, uint32_t pos_tris, float *d_gpos, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_antialias_grad");
+  if (!fs || !d_vis || !d_in || !d_gout) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / input / output gradient");
+  if (!d_gin && !d_gpos) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gin nor d_gpos is asked for");
+  if (int rc = check_antialias(ctx, fs, fn, n_ch, flags)) return rc;
+  if (d_gpos)
+    for (const FrameDesc &d : fs->h_frames)
+      if (d.n_tris > pos_tris) return fail(ctx, SRZ_E_INVALID, fn + ": pos_tris is below a frame's triangle count");
+  const size_t planes_bytes = srz_frameset_interpolate_bytes(ctx, fs, n_ch), vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  const size_t gpos_bytes = (size_t)fs->n_frames * pos_tris * TRI_POS_F * sizeof(float);
+  if ((((uintptr_t)d_vis | (uintptr_t)d_in | (uintptr_t)d_gout | (uintptr_t)d_gin) & 15u) != 0)
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers must be 16-byte aligned");
+  if (((uintptr_t)d_gpos & 3u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": the position gradient must be 4-byte aligned");
+  const void *outs[2] = {d_gin, d_gpos};
+  const size_t out_sizes[2] = {planes_bytes, gpos_bytes};
+  for (int i = 0; i < 2; ++i)
+    if (ranges_overlap(outs[i], out_sizes[i], d_vis, vis_bytes) || ranges_overlap(outs[i], out_sizes[i], d_in, planes_bytes) ||
+        ranges_overlap(outs[i], out_sizes[i], d_gout, planes_bytes))
+      return fail(ctx, SRZ_E_INVALID, fn + ": an output overlaps an input");
+  if (ranges_overlap(d_gin, planes_bytes, d_gpos, gpos_bytes)) return fail(ctx, SRZ_E_INVALID, fn + ": the two outputs overlap");
+  if (int rc = check_renderable(ctx, fs)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const hipStream_t s = pick_stream(ctx, stream);
+  // a sceneset's triangles are its vertex stage's output (as srz_frameset_position_grad)
+  if (fs->d_draws) launch_vertex(fs->d_draws, fs->n_draws, fs->max_faces, fs->d_tris, fs->d_tri_pos, fs->d_frames, nullptr, s);
+  AntialiasArgs a = antialias_args(fs, d_vis, d_in, n_ch, d_gin);
+  a.gout = (const float *)d_gout, a.gpos = d_gpos, a.gpos_stride = (uint64_t)pos_tris * TRI_POS_F;
+  launch_antialias_grad(a, s);
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
 int srz_frameset_update_shading(srz_ctx *ctx, srz_frameset *fs, const srz_frame *frames, int n_frames) {
   if (!ctx) return SRZ_E_INVALID;
   if (!fs || !frames) return fail(ctx, SRZ_E_INVALID, "srz_frameset_update_shading: null frameset / frames");

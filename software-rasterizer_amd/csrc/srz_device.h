@@ -321,6 +321,29 @@ struct PosGradArgs {
   uint32_t flags_or;
 };
 void launch_pos_grad(const PosGradArgs &a, hipStream_t s);
+// srz_frameset_antialias / _antialias_grad: the caller's planes blended across the silhouettes of a visibility buffer (k_antialias),
+// and the gradients of that with respect to the planes (gin) and to the nearer owners' positions (gpos, added into)
+// (k_antialias_grad).  vis and tri_pos / pos_stride as above; `out` is the forward's blended planes or the backward's gin (may be
+// null there), [frame][n_ch][local_rows][width] like `in` and `gout`; `out` / `frame_stride` / `local_rows` / the shard are what
+// tile_rect reads.  The host has checked shard_world == 1 (a vertical pair may cross a band) and pos_tris >= every frame's count
+struct AntialiasArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *tri_pos;  // [triangle * pos_stride], as RenderArgs has it
+  const float *in;       // the planes the forward blends
+  const float *gout;     // backward: the gradient of the blended planes (forward: null)
+  float *gpos;           // backward: [frame][pos_tris][9], added into (may be null)
+  float *out;
+  uint64_t vis_stride;   // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride; // floats per frame in in / gout / out = n_ch * local_rows * width
+  uint64_t gpos_stride;  // floats per frame in gpos = pos_tris * 9
+  uint32_t pos_stride;
+  uint32_t n_ch;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+};
+void launch_antialias(const AntialiasArgs &a, hipStream_t s);
+void launch_antialias_grad(const AntialiasArgs &a, hipStream_t s);
 void launch_resolve8(const float *planes, uint8_t *out, uint32_t n_frames, uint32_t rows, uint32_t W, uint64_t frame_stride,
                      hipStream_t s);
 void launch_deinterleave(const void *gathered, void *full, uint32_t world, uint32_t n_fp, uint32_t bands_per_rank, uint32_t row_bytes,

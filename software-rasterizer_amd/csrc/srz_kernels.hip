@@ -4062,6 +4062,295 @@ __global__ __launch_bounds__(256) void k_pos_grad(PosGradArgs a) {
 }
 
 // ================================================================================================================
+// k_antialias / k_antialias_grad — SILHOUETTE ANTIALIASING OF A VISIBILITY BUFFER (srz_frameset_antialias / _antialias_grad,
+// include/srz.h states the rule).  Where two 4-neighbours have different owners, the nearer owner's edge is intersected with the
+// segment between the two sample points; the pixel on whose side of the midpoint the crossing does not lie takes that share of
+// the other's value.  The forward is a gather (out[p] from in[p] and in[q] of its four neighbours), so is gin; gpos is the one
+// scatter: per pair four no-return global_atomic_add_f32, from the thread that holds the pair's left or upper pixel.
+// k_interp's shape: the XCD-ordered grid walk, four pixels of a row per thread, 16-byte id loads, quad_store, the channel loop
+// wave-uniform in register chunks of ATTR_CHUNK.  No LDS and no barrier.
+// THE NEIGHBOUR ROWS COME FROM THE CACHES, not from an LDS tile with a halo: a thread reads the id quads of the rows above and below
+// and the two words beside its quad straight from memory.  The rows of a tile are read by the lanes of one workgroup within a few
+// instructions of each other (a wave holds eight consecutive rows), so every id line is fetched from HBM once and its two re-reads
+// hit the vector L1 or L2; ids are 4 of the 4 + 8 n_ch bytes a pixel moves.  A tile in LDS would need the same 132 halo words from
+// memory, a barrier per tile, and would put that barrier into the path of the quads that only copy — nearly all of them.
+// FAST PATH: the 14 keys (the quad, left, right, the quads above and below; key = index + 1 of an owner, 0 for nobody: the class bit
+// and the flavour of a nobody id do not tell pixels apart) are one value → the quad's planes are copied; no z, no position is read.
+// SLOW PATH: the z words of the 14 pixels, then the quad's 13 pairs one after the other in ONE loop (its body, aa_pair, exists once
+// in the code; the keys and depths are picked with short select chains, the weights put back the same way: no indexed register array, no
+// scratch): load_pos9 of N, and of F once an edge is found and F has an owner.  Each pair's weight lands in the slots of the quad's
+// pixels it touches (16 weights: pixel x neighbour in the rule's order left, right, up, down; masks say whose target it is).  In
+// the backward the pairs whose left or upper pixel is the thread's own (8 of the 13) also form D over the channels and add.
+// The floor is the memory system: 4 bytes of id per pixel plus 8 n_ch per pixel.
+// ================================================================================================================
+constexpr int AA_PAIRS = 13;
+// the 14 values a quad's pairs are decided from: the pixel left of the quad, the quad, the pixel right of it, the quads above and below
+// (scalars, not arrays: an array picked from by a variable index is put into scratch)
+template <class T> struct AaHood {
+  T l, c0, c1, c2, c3, r, u0, u1, u2, u3, d0, d1, d2, d3;
+};
+template <class T> __device__ __forceinline__ T aa_pick4(T v0, T v1, T v2, T v3, int k) { return k == 0 ? v0 : k == 1 ? v1 : k == 2 ? v2 : v3; } // (k: a variable)
+// A and B of pair e of the quad: [0..4] left | 0 | 1 | 2 | 3 | right (k = e - 1: A's pixel), [5..8] above k | k, [9..12] k | below k
+template <class T> __device__ __forceinline__ void aa_pick(const AaHood<T> &h, bool horiz, bool above, int k, T &va, T &vb) {
+  const T ck = aa_pick4(h.c0, h.c1, h.c2, h.c3, k), ck1 = aa_pick4(h.c0, h.c1, h.c2, h.c3, k + 1);
+  const T uk = aa_pick4(h.u0, h.u1, h.u2, h.u3, k), dk = aa_pick4(h.d0, h.d1, h.d2, h.d3, k);
+  va = horiz ? (k < 0 ? h.l : ck) : above ? uk : ck;
+  vb = horiz ? (k == 3 ? h.r : ck1) : above ? ck : dk;
+}
+__device__ __forceinline__ void aa_put(float (&v)[16], int i, float x) { // (i: a variable)
+#pragma unroll
+  for (int j = 0; j < 16; ++j) v[j] = i == j ? x : v[j];
+}
+__device__ __forceinline__ uint32_t aa_key(uint32_t id, uint32_t n_tris) { // index + 1 of an owner, 0 for nobody
+  const uint32_t k = id & ~S_CLASS_BIT;
+  return k - 1u < n_tris ? k : 0u; // (0 and the bare class bit wrap to 0xffffffff)
+}
+struct AaPair {
+  uint32_t tgt;   // 0: nothing; 1: A (the left or upper pixel) is the target; 2: B
+  float w;
+  uint32_t n_key; // N's triangle index + 1
+  uint32_t c0;    // the edge's first corner
+  bool to_f;      // a > 0
+  float s, k, d, n0, n1, u0, u1;
+};
+__device__ __forceinline__ bool aa_same_vertex(float x, float y, float z, const float (&Q)[9]) {
+  const uint32_t a = f2u(x), b = f2u(y), c = f2u(z);
+  return (a == f2u(Q[0]) && b == f2u(Q[1]) && c == f2u(Q[2])) || (a == f2u(Q[3]) && b == f2u(Q[4]) && c == f2u(Q[5])) ||
+         (a == f2u(Q[6]) && b == f2u(Q[7]) && c == f2u(Q[8]));
+}
+// the pair of A at (xa, ya) with B at (xa + 1, ya) (horiz) or (xa, ya + 1); ka != kb are their keys, za, zb their depths
+__device__ __forceinline__ AaPair aa_pair(const SRZ_CAS float *tpos, uint32_t pos_stride, uint32_t ka, uint32_t kb, float za, float zb, int xa,
+                                          int ya, bool horiz) {
+  AaPair r = {0u, 0.0f, 0u, 0u, false, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  const bool n_is_b = ka == 0u || (kb != 0u && zb < za); // (a nobody is farther than any owner; ties and NaN: A)
+  const uint32_t kn = n_is_b ? kb : ka, kf = n_is_b ? ka : kb;
+  const float s = n_is_b ? -1.0f : 1.0f;
+  const float xn = (float)(xa + (horiz && n_is_b ? 1 : 0)), yn = (float)(ya + (!horiz && n_is_b ? 1 : 0));
+  float P[9];
+  load_pos9(tpos + (size_t)(kn - 1u) * pos_stride, P);
+  float u[3], n[3];
+#pragma unroll
+  for (int v = 0; v < 3; ++v) {
+    const float dx = P[3 * v] - xn, dy = P[3 * v + 1] - yn;
+    u[v] = horiz ? s * dx : s * dy, n[v] = horiz ? dy : dx;
+  }
+  bool found = false;
+  float t = 0.0f, v0x = 0.0f, v0y = 0.0f, v0z = 0.0f, v1x = 0.0f, v1y = 0.0f, v1z = 0.0f;
+#pragma unroll
+  for (int e = 0; e < 3; ++e) { // the first edge that straddles N's line and crosses it between the two sample points
+    const int e1 = (e + 1) % 3;
+    const float n0 = n[e], n1 = n[e1];
+    const bool straddle = (n0 <= 0.0f && n1 > 0.0f) || (n1 <= 0.0f && n0 > 0.0f);
+    const float d = n0 - n1, k = n0 / d; // (the IEEE division)
+    const float te = u[e] + k * (u[e1] - u[e]);
+    if (!found && straddle && 0.0f <= te && te <= 1.0f) {
+      found = true, t = te;
+      r.c0 = (uint32_t)e, r.k = k, r.d = d, r.n0 = n0, r.n1 = n1, r.u0 = u[e], r.u1 = u[e1];
+      v0x = P[3 * e], v0y = P[3 * e + 1], v0z = P[3 * e + 2], v1x = P[3 * e1], v1y = P[3 * e1 + 1], v1z = P[3 * e1 + 2];
+    }
+  }
+  if (!found) return r;
+  if (kf != 0u) { // the two owners share this edge: an interior edge of a mesh
+    float Q[9];
+    load_pos9(tpos + (size_t)(kf - 1u) * pos_stride, Q);
+    if (aa_same_vertex(v0x, v0y, v0z, Q) && aa_same_vertex(v1x, v1y, v1z, Q)) return r;
+  }
+  const float a = t - 0.5f;
+  r.n_key = kn, r.s = s, r.to_f = a > 0.0f;
+  if (a > 0.0f) r.tgt = n_is_b ? 1u : 2u, r.w = a;
+  else if (a < 0.0f) r.tgt = n_is_b ? 2u : 1u, r.w = -a;
+  return r;
+}
+// pixels x4 .. x4 + 3 of a row at p: one 16-byte load if the quad is whole, else the pixels up to tx1 (the others: 0)
+__device__ __forceinline__ float4 aa_quad(const float *p, bool whole, int x4, int tx1) {
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (whole) {
+    v = *reinterpret_cast<const float4 *>(p);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (x4 + k <= tx1) quad_at(v, k) = p[k];
+  }
+  return v;
+}
+template <bool GRAD> __device__ __forceinline__ void aa_body(const AntialiasArgs &a) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  const uint32_t C = a.n_ch;
+  const bool want_out = !GRAD || a.out != nullptr, want_pos = GRAD && a.gpos != nullptr; // (kernel arguments: wave-uniform)
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
+  for (uint32_t j = blockIdx.x >> 3;; j += step) {
+    uint32_t f, t;
+    if (a.n_frames >= 8u) {
+      f = sub + 8u * (j / tpf), t = j % tpf;
+      if (f >= a.n_frames) break;
+    } else {
+      const uint32_t i = j * 8u + sub;
+      if (i >= n_items) break;
+      f = i / tpf, t = i % tpf;
+    }
+    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
+    const TileRect rc = tile_rect(a, fd, f, lb, tx);
+    const int W = fd->width, H = fd->height;
+    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
+    if (!(y <= rc.ty1 && x4 <= rc.tx1)) continue; // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool whole = (W & 3) == 0 && x4 + 3 <= rc.tx1;
+    // (the shard is the whole frame — the host refuses anything else — so local row = frame row and y +- 1 is the row beside it)
+    const size_t poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)x4;
+    const float *gz = a.vis + (size_t)f * a.vis_stride + poff; // plane 0 (z: read by the slow path only)
+    const float *gi = gz + rc.plane;                           // plane 1 (ids)
+    const bool up = y > 0, down = y < H - 1, left = x4 > 0, right = x4 + 4 <= W - 1;
+    // ---- 1. the 14 keys
+    const uint32_t n_tris = fd->n_tris;
+    uint32_t kc[4] = {0u, 0u, 0u, 0u}, ku[4] = {0u, 0u, 0u, 0u}, kd[4] = {0u, 0u, 0u, 0u}, kl = 0u, kr = 0u; // (constant indices only)
+    if (whole) {
+      const uint4 q = *reinterpret_cast<const uint4 *>(gi);
+      kc[0] = q.x, kc[1] = q.y, kc[2] = q.z, kc[3] = q.w;
+      if (up) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(gi - W);
+        ku[0] = v.x, ku[1] = v.y, ku[2] = v.z, ku[3] = v.w;
+      }
+      if (down) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(gi + W);
+        kd[0] = v.x, kd[1] = v.y, kd[2] = v.z, kd[3] = v.w;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (x4 + k <= rc.tx1) {
+          kc[k] = f2u(gi[k]);
+          if (up) ku[k] = f2u(gi[k - W]);
+          if (down) kd[k] = f2u(gi[k + W]);
+        }
+    }
+    if (left) kl = f2u(gi[-1]);
+    if (right) kr = f2u(gi[4]);
+    kl = aa_key(kl, n_tris), kr = aa_key(kr, n_tris);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) kc[k] = aa_key(kc[k], n_tris), ku[k] = aa_key(ku[k], n_tris), kd[k] = aa_key(kd[k], n_tris);
+    // a neighbour outside the frame, and a pixel of the quad beyond the frame's edge, take the key beside them: no pair there
+#pragma unroll
+    for (int k = 1; k < 4; ++k)
+      if (x4 + k > rc.tx1) kc[k] = kc[k - 1];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (!up || x4 + k > rc.tx1) ku[k] = kc[k];
+      if (!down || x4 + k > rc.tx1) kd[k] = kc[k];
+    }
+    if (!left) kl = kc[0];
+    if (!right) kr = kc[3];
+    bool slow = kl != kc[0] || kr != kc[0];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) slow = slow || kc[k] != kc[0] || ku[k] != kc[0] || kd[k] != kc[0];
+    const AaHood<uint32_t> key = {kl, kc[0], kc[1], kc[2], kc[3], kr, ku[0], ku[1], ku[2], ku[3], kd[0], kd[1], kd[2], kd[3]};
+    // ---- 2. a quad with a differing pair: the depths, then the 13 pairs — [0..4] horizontal (left | 0 | 1 | 2 | 3 | right),
+    //         [5..8] the pixel above with pixel k, [9..12] pixel k with the pixel below
+    float wt[16]; // [pixel][left, right, up, down]: the weight of the pair with that neighbour, if it has a target
+#pragma unroll
+    for (int i = 0; i < 16; ++i) wt[i] = 0.0f;
+    uint32_t mine = 0u, theirs = 0u; // bit 4 k + j: that pair's target is pixel k / is its neighbour
+    if (slow) {
+      const float4 zc = aa_quad(gz, whole, x4, rc.tx1);
+      float4 zu = make_float4(0.f, 0.f, 0.f, 0.f), zd = zu;
+      if (up) zu = aa_quad(gz - W, whole, x4, rc.tx1);
+      if (down) zd = aa_quad(gz + W, whole, x4, rc.tx1);
+      const AaHood<float> z = {left ? gz[-1] : 0.0f, zc.x, zc.y, zc.z, zc.w, right ? gz[4] : 0.0f, zu.x, zu.y, zu.z, zu.w, zd.x, zd.y, zd.z, zd.w};
+      const SRZ_CAS float *tpos = as_const(a.tri_pos) + (size_t)fd->tri_off * a.pos_stride;
+#pragma nounroll
+      for (int e = 0; e < AA_PAIRS; ++e) {
+        const bool horiz = e < 5, above = !horiz && e < 9;
+        const int k = horiz ? e - 1 : (e - 5) & 3; // the quad's pixel of the pair: horizontal: A's (-1: A is the left neighbour)
+        uint32_t ka, kb;
+        aa_pick(key, horiz, above, k, ka, kb);
+        if (ka == kb) continue; // (two nobodies, one triangle, or no neighbour there)
+        const int xa = x4 + k, ya = above ? y - 1 : y;
+        float za, zb;
+        aa_pick(z, horiz, above, k, za, zb);
+        const AaPair pr = aa_pair(tpos, a.pos_stride, ka, kb, za, zb, xa, ya, horiz);
+        if (pr.tgt == 0u) continue;
+        // the slot of A's pair with B (A one of the quad's pixels), and of B's with A
+        const int sa = horiz ? (e >= 1 ? 4 * k + 1 : -1) : (above ? -1 : 4 * k + 3);
+        const int sb = horiz ? (e <= 3 ? 4 * (k + 1) + 0 : -1) : (above ? 4 * k + 2 : -1);
+        if (sa >= 0) aa_put(wt, sa, pr.w), (pr.tgt == 1u ? mine : theirs) |= 1u << sa;
+        if (sb >= 0) aa_put(wt, sb, pr.w), (pr.tgt == 2u ? mine : theirs) |= 1u << sb;
+        if (GRAD) {
+          if (want_pos && sa >= 0) { // each pair adds once: from its left or upper pixel
+            const ptrdiff_t oa = (ptrdiff_t)k, ob = oa + (horiz ? (ptrdiff_t)1 : (ptrdiff_t)W);
+            const ptrdiff_t ot = pr.tgt == 1u ? oa : ob, os = pr.tgt == 1u ? ob : oa;
+            const float *pin = a.in + (size_t)f * a.frame_stride + poff, *pg = a.gout + (size_t)f * a.frame_stride + poff;
+            float D = 0.0f;
+            for (uint32_t ch = 0; ch < C; ++ch) {
+              const size_t o = (size_t)ch * rc.plane;
+              D = fmaf_(pg[(ptrdiff_t)o + ot], pin[(ptrdiff_t)o + os] - pin[(ptrdiff_t)o + ot], D);
+            }
+            const float g = pr.to_f ? D : -D;
+            const float ed = pr.u1 - pr.u0;
+            const float qq = (g * ed) / (pr.d * pr.d); // (the IEEE division)
+            const float g_u0 = pr.s * (g * (1.0f - pr.k)), g_u1 = pr.s * (g * pr.k), g_n0 = qq * (-pr.n1), g_n1 = qq * pr.n0;
+            float *gp = a.gpos + (size_t)f * a.gpos_stride + (size_t)(pr.n_key - 1u) * 9u;
+            const uint32_t c0 = 3u * pr.c0, c1 = pr.c0 == 2u ? 0u : c0 + 3u;
+            global_add(gp + c0, horiz ? g_u0 : g_n0), global_add(gp + c1, horiz ? g_u1 : g_n1);
+            global_add(gp + c0 + 1u, horiz ? g_n0 : g_u0), global_add(gp + c1 + 1u, horiz ? g_n1 : g_u1);
+          }
+        }
+      }
+    }
+    if (!want_out) continue;
+    // ---- 3. the channels, ATTR_CHUNK at a time: the quad's words, blended where a pair has a target (forward: the planes; backward:
+    //         gout into gin)
+    const float *src = (GRAD ? a.gout : a.in) + (size_t)f * a.frame_stride + poff;
+    float *go = rc.out0 + (size_t)ly * (size_t)W + (size_t)x4;
+    const uint32_t any = mine | (GRAD ? theirs : 0u);
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 q[ATTR_CHUNK];
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+        q[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < nc) q[i] = aa_quad(src + (size_t)(c0 + i) * rc.plane, whole, x4, rc.tx1);
+      }
+      if (any != 0u) {
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+          if (i >= nc) break;
+          const float *p = src + (size_t)(c0 + i) * rc.plane;
+          const float4 own = q[i];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            if (((any >> (4 * k)) & 15u) == 0u) continue;
+            const float pv = quad_at(own, k);
+            float acc = pv;
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb) { // (x - 1, y), (x + 1, y), (x, y - 1), (x, y + 1)
+              const uint32_t bit = 1u << (4 * k + nb);
+              if (!(any & bit)) continue;
+              const float qv = nb == 0 ? (k > 0 ? quad_at(own, k > 0 ? k - 1 : 0) : p[-1])
+                             : nb == 1 ? (k < 3 ? quad_at(own, k < 3 ? k + 1 : 3) : p[4])
+                             : nb == 2 ? p[k - W] : p[k + W];
+              const float w = wt[4 * k + nb];
+              if (!GRAD) acc = fmaf_(w, qv - pv, acc);
+              else if (mine & bit) acc = fmaf_(-w, pv, acc);
+              else acc = fmaf_(w, qv, acc);
+            }
+            quad_at(q[i], k) = acc;
+          }
+        }
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+        if (i >= nc) break;
+        quad_store(go + (size_t)(c0 + i) * rc.plane, rc.plane, {q[i]}, whole, x4, rc.tx1);
+      }
+    }
+  }
+}
+__global__ __launch_bounds__(256) void k_antialias(AntialiasArgs a) { aa_body<false>(a); }
+__global__ __launch_bounds__(256) void k_antialias_grad(AntialiasArgs a) { aa_body<true>(a); }
+
+// ================================================================================================================
 // k_resolve8 — display()'s resolve (src/Render.cpp:61-62): cv::merge(planes 0,1,2) + convertTo(CV_8UC3) =
 // saturate_cast<uchar>(cvRound(v)): round half to even, clamp to [0,255]; NaN → 0.  4 pixels per thread: three 16-byte
 // plane reads → 12 output bytes (three dword stores).
@@ -4662,6 +4951,20 @@ void launch_pos_grad(const PosGradArgs &a, hipStream_t s) {
   if (items == 0) return;
   const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (as launch_interp)
   hipLaunchKernelGGL(k_pos_grad, grid, dim3(256), 0, s, a);
+}
+
+void launch_antialias(const AntialiasArgs &a, hipStream_t s) {
+  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
+  if (items == 0) return;
+  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (as launch_interp)
+  hipLaunchKernelGGL(k_antialias, grid, dim3(256), 0, s, a);
+}
+
+void launch_antialias_grad(const AntialiasArgs &a, hipStream_t s) {
+  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
+  if (items == 0) return;
+  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (as launch_interp)
+  hipLaunchKernelGGL(k_antialias_grad, grid, dim3(256), 0, s, a);
 }
 
 bool raster_four_waves(const RenderArgs &a) { return a.n_frames * a.n_local_bands * a.tiles_x <= 4096u; }

@@ -25,7 +25,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_allgather_sparse", "srz_frameset_render_visibility", "srz_frameset_shade_visibility",
            "srz_frameset_update_shading", "srz_frameset_shade_kinds", "srz_frameset_gbuffer_bytes", "srz_frameset_gbuffer",
            "srz_frameset_motion_bytes", "srz_frameset_motion", "srz_frameset_interpolate_bytes", "srz_frameset_interpolate",
-           "srz_frameset_interpolate_grad", "srz_frameset_position_grad",
+           "srz_frameset_interpolate_grad", "srz_frameset_position_grad", "srz_frameset_antialias", "srz_frameset_antialias_grad",
            "srz_target_create", "srz_target_destroy", "srz_target_clear", "srz_target_draw", "srz_target_read", "srz_target_read_bgr8"]
 
 
@@ -83,6 +83,8 @@ def lib():
         L.srz_frameset_interpolate.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.c_uint32, vp]
         L.srz_frameset_interpolate_grad.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp]
         L.srz_frameset_position_grad.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp]
+        L.srz_frameset_antialias.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, C.c_uint32, vp]
+        L.srz_frameset_antialias_grad.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp]
         L.srz_frameset_update_shading.argtypes = [vp, vp, C.POINTER(abi.SrzFrame), C.c_int]
         L.srz_sceneset_update.argtypes = [vp, vp, C.POINTER(abi.SrzSceneFrame), C.c_int]
         L.srz_frameset_resolve8.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
@@ -246,6 +248,24 @@ class FrameSet:
         self.ctx._check(lib().srz_frameset_position_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_gbary_ptr or None),
                                                          C.c_void_p(d_gz_ptr or None), pos_tris, C.c_void_p(d_gpos_ptr or None),
                                                          C.c_void_p(d_gpix_ptr or None), flags, _stream(stream)))
+
+    def antialias(self, d_vis_ptr, d_in_ptr, n_ch, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """the planes d_in [frame][n_ch][local_rows][width] float32 blended across the silhouettes of a visibility buffer of this set:
+        where two 4-neighbours have different owners, the nearer owner's edge is intersected with the segment between the two
+        sample points and the pixel it does not reach the middle of takes that share of the other's value (include/srz.h states the
+        rule).  Every pixel of d_out is written, deterministic; d_out may overlap neither input.  Needs an unsharded context.
+        Asynchronous."""
+        self.ctx._check(lib().srz_frameset_antialias(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_in_ptr), n_ch, C.c_void_p(d_out_ptr),
+                                                     out_bytes, flags, _stream(stream)))
+
+    def antialias_grad(self, d_vis_ptr, d_in_ptr, d_gout_ptr, n_ch, d_gin_ptr, pos_tris, d_gpos_ptr, flags=abi.FUSED_CLEAR, stream=None):
+        """the backward of antialias: d_gout and the forward's d_in, both [frame][n_ch][local_rows][width] → written to d_gin (the
+        planes' shape, deterministic) and / or ADDED into d_gpos [n_frames][pos_tris][9] (ax ay z0 bx by z1 cx cy z2 per triangle: the
+        silhouette term; the order of the adds is unspecified: not bit-reproducible; the z slots receive nothing).  Either output
+        pointer may be None / 0, not both.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_antialias_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_in_ptr), C.c_void_p(d_gout_ptr),
+                                                          n_ch, C.c_void_p(d_gin_ptr or None), pos_tris, C.c_void_p(d_gpos_ptr or None), flags,
+                                                          _stream(stream)))
 
     def update_shading(self, frames):
         """new eye, ka, ks, p, kh, kn, lights, flags and batch shaders / textures for a set made from abi.Frame's, triangles untouched

@@ -249,7 +249,8 @@ def interpolate_geo(fs, vis, attr, pos, stream=None):
     barycentrics are those of `vis` and the positions the set's own, and the caller warrants that pos holds the same positions (it
     is the graph's handle on them: what the caller's parameters produced and the set was made from).  Backward: attr.grad as
     interpolate's; pos.grad from one interpolate_grad call (asking for both the attribute gradient and the alpha / beta planes) and
-    one position_grad call.  Owners are held fixed: no silhouette term.  The z column of pos.grad is zero (depth() is the function of
+    one position_grad call.  Owners are held fixed: this is the interior term; antialias(fs, vis, interpolate_geo(...), pos) adds the
+    silhouette term.  The z column of pos.grad is zero (depth() is the function of
     z).  Both gradients are sums of float atomics: not bit-reproducible between runs."""
     return _InterpolateGeo.apply(attr, pos, fs, vis, stream)
 
@@ -278,3 +279,70 @@ def depth(fs, vis, pos, stream=None):
     backward is one position_grad call with the incoming gradient as gz — z's own share into the z column, and x, y through the
     barycentrics.  Words of the incoming gradient at nobody's pixels (depth +inf there in a fused-clear buffer) reach nothing."""
     return _Depth.apply(pos, fs, vis, stream)
+
+
+def _color_arg(fs, t, name):
+    if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 4 or tuple(t.shape) != tuple(fs.interpolate_shape(t.shape[1])):
+        raise ValueError(f"antialias: {name} must be a CUDA float32 tensor [n_frames, C, rows, W] of the set, got {tuple(t.shape)} {t.dtype}")
+    if not 1 <= t.shape[1] <= abi.ATTR_MAX_CH:
+        raise ValueError(f"antialias: {name} has {t.shape[1]} channels, 1 .. {abi.ATTR_MAX_CH} are supported")
+    return t.contiguous()
+
+
+def antialias_grad(fs, vis, color, gout, pos_tris=None, want_gin=True, want_gpos=True, stream=None):
+    """the backward of antialias(fs, vis, color) by one FrameSet.antialias_grad call: gout [n_frames, C, rows, W] → (gin, gpos), each
+    None when not wanted (not both): gin has color's shape (deterministic); gpos [n_frames, T, 3, 3] float32 (triangle, corner,
+    (x, y, z)), T = pos_tris (default: the largest triangle count of the set's frames; a sceneset must name it), is the SILHOUETTE
+    term of the gradient with respect to the triangles' screen positions — a sum of float atomics into zeros, not bit-reproducible
+    between runs; its z column is zero.  stream: a raw stream handle, None = torch's current stream."""
+    if not want_gin and not want_gpos:
+        raise ValueError("antialias_grad: neither gin nor gpos is asked for")
+    color, gout = _color_arg(fs, color, "color"), _color_arg(fs, gout, "gout")
+    if gout.shape != color.shape:
+        raise ValueError(f"antialias_grad: gout {tuple(gout.shape)} is not of color's shape {tuple(color.shape)}")
+    T = _pos_tris(fs, pos_tris) if want_gpos else 0
+    gin = torch.empty_like(color) if want_gin else None
+    gpos = torch.zeros((fs.n_frames, T, 3, 3), dtype=torch.float32, device=color.device) if want_gpos else None
+    fs.antialias_grad(vis.data_ptr(), color.data_ptr(), gout.data_ptr(), color.shape[1], gin.data_ptr() if want_gin else None, T,
+                      gpos.data_ptr() if want_gpos else None, abi.FUSED_CLEAR, _stream_ptr(stream))
+    return gin, gpos
+
+
+class _Antialias(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, color, pos, fs, vis, stream):
+        color = _color_arg(fs, color, "color")
+        if pos is not None and (pos.dtype != torch.float32 or pos.dim() != 4 or pos.shape[0] != fs.n_frames or tuple(pos.shape[2:]) != (3, 3)):
+            raise ValueError(f"antialias: pos must be float32 [n_frames, T, 3, 3], got {tuple(pos.shape)} {pos.dtype}")
+        n_ch = color.shape[1]
+        out = torch.empty_like(color)
+        fs.antialias(vis.data_ptr(), color.data_ptr(), n_ch, out.data_ptr(), fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR, _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.stream, ctx.pos_shape = fs, vis, stream, None if pos is None else pos.shape
+        ctx.save_for_backward(color)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        fs, (color,) = ctx.fs, ctx.saved_tensors
+        need_color, need_pos = ctx.needs_input_grad[0], ctx.pos_shape is not None and ctx.needs_input_grad[1]
+        gin = gpos = None
+        if need_color or need_pos:  # one call, asking only for what is needed
+            gout = gout.contiguous()
+            gin = torch.empty_like(color) if need_color else None
+            gpos = torch.zeros(ctx.pos_shape, dtype=torch.float32, device=gout.device) if need_pos else None
+            fs.antialias_grad(ctx.vis.data_ptr(), color.data_ptr(), gout.data_ptr(), color.shape[1], gin.data_ptr() if need_color else None,
+                              ctx.pos_shape[1] if need_pos else 0, gpos.data_ptr() if need_pos else None, abi.FUSED_CLEAR,
+                              _stream_ptr(ctx.stream))
+        return gin, gpos, None, None, None
+
+
+def antialias(fs, vis, color, pos=None, stream=None):
+    """color [n_frames, C, rows, W] (CUDA float32: a shaded image, interpolate's planes, ...) blended across the silhouettes of the
+    visibility buffer `vis` of FrameSet `fs` (FrameSet.antialias; include/srz.h states the rule) → the same shape.  The words of
+    color at nobody's pixels are the background the outlines blend with.  Differentiable with respect to color (deterministic) and,
+    when pos is given, to the triangles' screen positions: pos is the never-read graph handle interpolate_geo takes,
+    [n_frames, T, 3, 3], and pos.grad receives the SILHOUETTE term (its z column is zero; a sum of float atomics: not
+    bit-reproducible between runs).  antialias(fs, vis, interpolate_geo(fs, vis, attr, pos), pos) is the full chain: pos.grad is then
+    the sum of the interior and the silhouette term.  Backward is one antialias_grad call that asks only for the outputs some input
+    needs, and no call when none does.  Needs an unsharded context.  stream: a raw stream handle, None = torch's current stream."""
+    return _Antialias.apply(color, pos, fs, vis, stream)
