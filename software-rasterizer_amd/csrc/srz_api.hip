@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -336,12 +337,17 @@ bool any_frame_has(const srz_frameset *fs, uint32_t flags_or, uint32_t bit) {
   return (flags_or & bit) != 0 || std::any_of(fs->h_frames.begin(), fs->h_frames.end(), [bit](const FrameDesc &f) { return (f.flags & bit) != 0; });
 }
 
+// the set's positions, for RenderArgs and every pass's Args that reads them: the dense stream of a sceneset, else the triangles themselves
+template <class Args> void fill_positions(Args &a, const srz_frameset *fs) {
+  a.tri_pos = fs->d_tri_pos ? fs->d_tri_pos : reinterpret_cast<const float *>(fs->d_tris);
+  a.pos_stride = fs->d_tri_pos ? TRI_POS_F : TRI_AOS_F;
+}
+
 RenderArgs make_args(const srz_ctx *ctx, const srz_frameset *fs, float *d_out, uint32_t flags_or, const Pass &pass) {
   RenderArgs a{};
   a.frames = fs->d_frames;
   a.tris = fs->d_tris;
-  a.tri_pos = fs->d_tri_pos ? fs->d_tri_pos : reinterpret_cast<const float *>(fs->d_tris);
-  a.pos_stride = fs->d_tri_pos ? TRI_POS_F : TRI_AOS_F;
+  fill_positions(a, fs);
   a.bbox = fs->d_bbox;
   a.chunk_rows = fs->d_chunk_rows;
   a.band_desc = fs->d_band_desc;
@@ -733,6 +739,113 @@ int stats_pass(srz_ctx *ctx, srz_frameset *fs, const float *d_start, uint32_t fl
   else (void)hipStreamSynchronize(s);
   (void)hipFree(d_tmp);
   return rc;
+}
+
+} // namespace
+
+// The passes over a visibility buffer (srz_frameset_shade_visibility .. srz_frameset_antialias_grad): what their entry points share.
+// Each entry point is its own argument rules, these checks, its own Args fields, the launch.
+namespace {
+
+int check_pass_flags(srz_ctx *ctx, const std::string &fn, uint32_t flags) {
+  if ((flags & ~(uint32_t)SRZ_FUSED_CLEAR) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": only SRZ_FUSED_CLEAR is accepted in flags");
+  return SRZ_OK;
+}
+// `n` (the caller's `name`: attr_tris, pos_tris) is what a per-triangle array of the caller holds per frame
+int check_tri_count(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, const char *name, uint32_t n) {
+  for (const FrameDesc &d : fs->h_frames)
+    if (d.n_tris > n) return fail(ctx, SRZ_E_INVALID, fn + ": " + name + " is below a frame's triangle count");
+  return SRZ_OK;
+}
+// the plane buffers (16 bytes: the kernels move them four words at a time) and the per-triangle arrays (4 bytes); a null pointer,
+// where an entry point lets one through, counts as aligned
+template <uintptr_t BYTES> bool aligned(std::initializer_list<const void *> ptrs) {
+  uintptr_t bits = 0;
+  for (const void *p : ptrs) bits |= (uintptr_t)p;
+  return (bits & (BYTES - 1u)) == 0;
+}
+struct Range { // (a null pointer overlaps nothing)
+  const void *p;
+  size_t bytes;
+};
+bool ranges_overlap(Range x, Range y) {
+  const uintptr_t a = (uintptr_t)x.p, b = (uintptr_t)y.p;
+  return x.p && y.p && a < b + y.bytes && b < a + x.bytes;
+}
+// the gradient passes: no output overlaps an input, and the two outputs do not overlap each other
+int check_grad_overlap(srz_ctx *ctx, const std::string &fn, const Range (&outs)[2], const Range (&ins)[3]) {
+  for (const Range &o : outs)
+    for (const Range &i : ins)
+      if (ranges_overlap(o, i)) return fail(ctx, SRZ_E_INVALID, fn + ": an output overlaps an input");
+  if (ranges_overlap(outs[0], outs[1])) return fail(ctx, SRZ_E_INVALID, fn + ": the two outputs overlap");
+  return SRZ_OK;
+}
+// What a pass does once its arguments are accepted: the set is renderable, the device current, the stream picked (*s).  Then, as
+// `steps` asks: the shading state resolved (textures uploaded, batch → shader / texture), and a sceneset's vertex stage run again —
+// its triangles are that stage's output, computed as a render computes them (no setup: nothing is rasterised).
+enum : unsigned { PASS_SHADING = 1u, PASS_VERTEX = 2u };
+int begin_pass(srz_ctx *ctx, srz_frameset *fs, void *stream, unsigned steps, hipStream_t *s) {
+  if (int rc = check_renderable(ctx, fs)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  *s = pick_stream(ctx, stream);
+  if (steps & PASS_SHADING)
+    if (int rc = resolve_shading(ctx, fs, *s)) return rc;
+  if ((steps & PASS_VERTEX) && fs->d_draws)
+    launch_vertex(fs->d_draws, fs->n_draws, fs->max_faces, fs->d_tris, fs->d_tri_pos, fs->d_frames, nullptr, *s);
+  return SRZ_OK;
+}
+int end_pass(srz_ctx *ctx) {
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
+uint64_t plane_words(const srz_frameset *fs) { return fs->local_rows * (uint64_t)fs->width; }
+// the fields every pass's Args names alike: the frames, the two buffers, and what the walk over the set's tiles reads
+template <class Args> void fill_walk(Args &a, const srz_frameset *fs, const void *d_vis, void *d_out) {
+  a.frames = fs->d_frames, a.vis = (const float *)d_vis, a.out = (float *)d_out;
+  a.local_rows = fs->local_rows, a.tiles_x = fs->tiles_x, a.n_local_bands = fs->n_local_bands, a.n_frames = (uint32_t)fs->n_frames;
+  a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
+}
+// what srz_frameset_interpolate and _interpolate_grad check alike; the attribute array's bytes in *attr_bytes
+int check_interp(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, uint32_t n_ch, uint32_t attr_frames, uint32_t attr_tris,
+                 uint32_t flags, size_t *attr_bytes) {
+  if (n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_ATTR_MAX_CH");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  if (attr_frames != 1u && attr_frames != (uint32_t)fs->n_frames)
+    return fail(ctx, SRZ_E_INVALID, fn + ": attr_frames must be 1 or the set's frame count");
+  if (int rc = check_tri_count(ctx, fs, fn, "attr_tris", attr_tris)) return rc;
+  *attr_bytes = (size_t)attr_frames * attr_tris * 3u * n_ch * sizeof(float);
+  return SRZ_OK;
+}
+InterpArgs interp_args(const srz_frameset *fs, const void *d_vis, const float *d_attr, uint32_t n_ch, uint32_t attr_frames, uint32_t attr_tris,
+                       uint32_t out_planes, void *d_out, uint32_t flags) {
+  InterpArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  a.attr = d_attr;
+  a.vis_stride = 4ull * plane, a.frame_stride = out_planes * plane, a.gout_stride = n_ch * plane;
+  a.attr_frame_stride = attr_frames == 1u ? 0ull : (uint64_t)attr_tris * 3u * n_ch;
+  a.n_ch = n_ch;
+  a.flags_or = flags;
+  return a;
+}
+// what srz_frameset_antialias and _antialias_grad check alike
+int check_antialias(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, uint32_t n_ch, uint32_t flags) {
+  if (n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_ATTR_MAX_CH");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  if (fs->shard_world > 1)
+    return fail(ctx, SRZ_E_INVALID, fn + ": needs the whole frame on this ctx (a vertical pair across a band edge needs another rank's rows)");
+  return SRZ_OK;
+}
+AntialiasArgs antialias_args(const srz_frameset *fs, const void *d_vis, const void *d_in, uint32_t n_ch, void *d_out) {
+  AntialiasArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  fill_positions(a, fs);
+  a.in = (const float *)d_in;
+  a.vis_stride = 4ull * plane, a.frame_stride = n_ch * plane;
+  a.n_ch = n_ch;
+  return a;
 }
 
 } // namespace
@@ -1313,22 +1426,17 @@ int srz_frameset_shade_visibility(srz_ctx *ctx, srz_frameset *fs, const void *d_
   if (!fs || !d_vis || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / output");
   const size_t bytes = srz_frameset_out_bytes(ctx, fs);
   if (out_bytes < bytes) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
-  if ((((uintptr_t)d_vis | (uintptr_t)d_out) & 15u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
-  const uintptr_t v = (uintptr_t)d_vis, o = (uintptr_t)d_out;
-  if (v != o && v < o + bytes && o < v + bytes) return fail(ctx, SRZ_E_INVALID, fn + ": visibility buffer and output overlap partly");
-  if (int rc = check_renderable(ctx, fs)) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const hipStream_t s = pick_stream(ctx, stream);
-  if (int rc = resolve_shading(ctx, fs, s)) return rc; // (textures uploaded, batch → shader / texture)
-  // a sceneset's triangles are its vertex stage's output: computed as a render computes them (no setup: nothing is rasterised)
-  if (fs->d_draws) launch_vertex(fs->d_draws, fs->n_draws, fs->max_faces, fs->d_tris, fs->d_tri_pos, fs->d_frames, nullptr, s);
+  if (!aligned<16>({d_vis, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
+  // (this pass alone may run in place: a pixel's colour is written after its own visibility words were read, and nobody else's are)
+  if (d_vis != d_out && ranges_overlap({d_vis, bytes}, {d_out, bytes}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": visibility buffer and output overlap partly");
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, PASS_SHADING | PASS_VERTEX, &s)) return rc;
   ShadeVisArgs a{};
-  a.frames = fs->d_frames, a.tris = fs->d_tris, a.tri_batch = fs->d_tri_batch, a.lights = fs->d_lights, a.sdesc = fs->d_sdesc;
-  a.vis = (const float *)d_vis, a.out = (float *)d_out;
-  a.frame_stride = 4ull * fs->local_rows * (uint64_t)fs->width;
-  a.local_rows = fs->local_rows, a.tiles_x = fs->tiles_x, a.n_local_bands = fs->n_local_bands, a.n_frames = (uint32_t)fs->n_frames;
-  a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
-  a.flags_or = flags & FRAME_FLAGS, a.in_place = v == o ? 1u : 0u;
+  fill_walk(a, fs, d_vis, d_out);
+  a.tris = fs->d_tris, a.tri_batch = fs->d_tri_batch, a.lights = fs->d_lights, a.sdesc = fs->d_sdesc;
+  a.frame_stride = 4ull * plane_words(fs);
+  a.flags_or = flags & FRAME_FLAGS, a.in_place = d_vis == d_out ? 1u : 0u;
   a.any_generic = fs->any_generic ? 1u : 0u;
   a.redo_list = reinterpret_cast<uint32_t *>(fs->d_redo_list), a.redo_count = fs->d_slow_count + 1; // (k_shade's: a render zeroes them itself)
   HIP_TRY(ctx, hipMemsetAsync(a.redo_count, 0, sizeof(uint32_t), s));
@@ -1337,8 +1445,7 @@ int srz_frameset_shade_visibility(srz_ctx *ctx, srz_frameset *fs, const void *d_
   // only itself (as after a visibility render)
   const srz_frameset::ClearTune &ct = fs->clear_tune;
   if (!ctx->env_clear_wgs && ct.d_ctl && !ct.done && fs->max_tiles >= 8192) launch_clear_rebase(ct.d_ctl, s);
-  HIP_TRY(ctx, hipGetLastError());
-  return SRZ_OK;
+  return end_pass(ctx);
 }
 
 size_t srz_frameset_gbuffer_bytes(const srz_ctx *ctx, const srz_frameset *fs, uint32_t what) {
@@ -1352,29 +1459,20 @@ int srz_frameset_gbuffer(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void
   const std::string fn("srz_frameset_gbuffer");
   if (!fs || !d_vis || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / output");
   if (what == 0u || (what & ~GB_GROUPS) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": `what` names no group or an unknown one");
-  if ((flags & ~(uint32_t)SRZ_FUSED_CLEAR) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": only SRZ_FUSED_CLEAR is accepted in flags");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
   const size_t need = srz_frameset_gbuffer_bytes(ctx, fs, what), vis_bytes = srz_frameset_out_bytes(ctx, fs);
   if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
-  if ((((uintptr_t)d_vis | (uintptr_t)d_out) & 15u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
-  const uintptr_t v = (uintptr_t)d_vis, o = (uintptr_t)d_out;
-  if (v < o + need && o < v + vis_bytes) return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the visibility buffer");
-  if (int rc = check_renderable(ctx, fs)) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const hipStream_t s = pick_stream(ctx, stream);
-  if (what & SRZ_GB_ALBEDO) // (textures uploaded, batch → shader / texture: nothing else reads them)
-    if (int rc = resolve_shading(ctx, fs, s)) return rc;
-  // a sceneset's triangles are its vertex stage's output (as srz_frameset_shade_visibility)
-  if (fs->d_draws) launch_vertex(fs->d_draws, fs->n_draws, fs->max_faces, fs->d_tris, fs->d_tri_pos, fs->d_frames, nullptr, s);
+  if (!aligned<16>({d_vis, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
+  if (ranges_overlap({d_out, need}, {d_vis, vis_bytes})) return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the visibility buffer");
+  hipStream_t s; // (the shading state: nothing but the albedo reads it)
+  if (int rc = begin_pass(ctx, fs, stream, ((what & SRZ_GB_ALBEDO) ? PASS_SHADING : 0u) | PASS_VERTEX, &s)) return rc;
   GbufArgs a{};
-  a.frames = fs->d_frames, a.tris = fs->d_tris, a.tri_batch = fs->d_tri_batch, a.sdesc = fs->d_sdesc;
-  a.vis = (const float *)d_vis, a.out = (float *)d_out;
-  a.vis_stride = 4ull * fs->local_rows * (uint64_t)fs->width, a.frame_stride = (uint64_t)gbuf_planes(what) * fs->local_rows * (uint64_t)fs->width;
-  a.local_rows = fs->local_rows, a.tiles_x = fs->tiles_x, a.n_local_bands = fs->n_local_bands, a.n_frames = (uint32_t)fs->n_frames;
-  a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
+  fill_walk(a, fs, d_vis, d_out);
+  a.tris = fs->d_tris, a.tri_batch = fs->d_tri_batch, a.sdesc = fs->d_sdesc;
+  a.vis_stride = 4ull * plane_words(fs), a.frame_stride = gbuf_planes(what) * plane_words(fs);
   a.flags_or = flags, a.what = what;
   launch_gbuffer(a, s);
-  HIP_TRY(ctx, hipGetLastError());
-  return SRZ_OK;
+  return end_pass(ctx);
 }
 
 size_t srz_frameset_motion_bytes(const srz_ctx *ctx, const srz_frameset *fs, uint32_t what) {
@@ -1388,14 +1486,13 @@ int srz_frameset_motion(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void 
   const std::string fn("srz_frameset_motion");
   if (!fs || !d_vis || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / output");
   if (what == 0u || (what & ~MV_GROUPS) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": `what` names no group or an unknown one");
-  if ((flags & ~(uint32_t)SRZ_FUSED_CLEAR) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": only SRZ_FUSED_CLEAR is accepted in flags");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
   if ((what & SRZ_MV_TARGET) && fs->shard_world > 1)
     return fail(ctx, SRZ_E_INVALID, fn + ": SRZ_MV_TARGET needs the whole frame on this ctx (the target row may belong to another rank)");
   const size_t need = srz_frameset_motion_bytes(ctx, fs, what), vis_bytes = srz_frameset_out_bytes(ctx, fs);
   if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
-  if ((((uintptr_t)d_vis | (uintptr_t)d_out) & 15u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
-  const uintptr_t v = (uintptr_t)d_vis, o = (uintptr_t)d_out;
-  if (v < o + need && o < v + vis_bytes) return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the visibility buffer");
+  if (!aligned<16>({d_vis, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
+  if (ranges_overlap({d_out, need}, {d_vis, vis_bytes})) return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the visibility buffer");
   // triangle t of frame f + delta stands for triangle t of frame f: every pair inside the set must have one triangle count
   const int n = fs->n_frames, d = std::max(-n, std::min(n, delta)); // (beyond +-n no frame has a target: the same result)
   for (int f = 0; f < n; ++f) {
@@ -1403,64 +1500,22 @@ int srz_frameset_motion(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void 
     if (g >= 0 && g < n && fs->h_frames[f].n_tris != fs->h_frames[g].n_tris)
       return fail(ctx, SRZ_E_INVALID, fn + ": frames " + std::to_string(f) + " and " + std::to_string(g) + " differ in triangle count");
   }
-  if (int rc = check_renderable(ctx, fs)) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const hipStream_t s = pick_stream(ctx, stream);
-  // a sceneset's triangles are its vertex stage's output (as srz_frameset_shade_visibility)
-  if (fs->d_draws) launch_vertex(fs->d_draws, fs->n_draws, fs->max_faces, fs->d_tris, fs->d_tri_pos, fs->d_frames, nullptr, s);
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, PASS_VERTEX, &s)) return rc;
   MotionArgs a{};
-  a.frames = fs->d_frames;
-  a.tri_pos = fs->d_tri_pos ? fs->d_tri_pos : reinterpret_cast<const float *>(fs->d_tris);
-  a.pos_stride = fs->d_tri_pos ? TRI_POS_F : TRI_AOS_F;
+  fill_walk(a, fs, d_vis, d_out);
+  fill_positions(a, fs);
   a.delta = d;
-  a.vis = (const float *)d_vis, a.out = (float *)d_out;
-  a.vis_stride = 4ull * fs->local_rows * (uint64_t)fs->width, a.frame_stride = (uint64_t)motion_planes(what) * fs->local_rows * (uint64_t)fs->width;
-  a.local_rows = fs->local_rows, a.tiles_x = fs->tiles_x, a.n_local_bands = fs->n_local_bands, a.n_frames = (uint32_t)fs->n_frames;
-  a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
+  a.vis_stride = 4ull * plane_words(fs), a.frame_stride = motion_planes(what) * plane_words(fs);
   a.flags_or = flags, a.what = what;
   launch_motion(a, s);
-  HIP_TRY(ctx, hipGetLastError());
-  return SRZ_OK;
+  return end_pass(ctx);
 }
 
 size_t srz_frameset_interpolate_bytes(const srz_ctx *ctx, const srz_frameset *fs, uint32_t n_ch) {
   if (!fs || n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH) return 0;
   return (size_t)fs->n_frames * n_ch * fs->local_rows * (size_t)fs->width * sizeof(float);
 }
-
-} // extern "C"
-namespace {
-bool ranges_overlap(const void *p, size_t p_bytes, const void *q, size_t q_bytes) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return p && q && a < b + q_bytes && b < a + p_bytes;
-}
-// what srz_frameset_interpolate and _interpolate_grad check alike; the attribute array's bytes in *attr_bytes
-int check_interp(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, uint32_t n_ch, uint32_t attr_frames, uint32_t attr_tris,
-                 uint32_t flags, size_t *attr_bytes) {
-  if (n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_ATTR_MAX_CH");
-  if ((flags & ~(uint32_t)SRZ_FUSED_CLEAR) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": only SRZ_FUSED_CLEAR is accepted in flags");
-  if (attr_frames != 1u && attr_frames != (uint32_t)fs->n_frames)
-    return fail(ctx, SRZ_E_INVALID, fn + ": attr_frames must be 1 or the set's frame count");
-  for (const FrameDesc &d : fs->h_frames)
-    if (d.n_tris > attr_tris) return fail(ctx, SRZ_E_INVALID, fn + ": attr_tris is below a frame's triangle count");
-  *attr_bytes = (size_t)attr_frames * attr_tris * 3u * n_ch * sizeof(float);
-  return SRZ_OK;
-}
-InterpArgs interp_args(const srz_frameset *fs, const void *d_vis, const float *d_attr, uint32_t n_ch, uint32_t attr_frames, uint32_t attr_tris,
-                       uint32_t out_planes, void *d_out, uint32_t flags) {
-  InterpArgs a{};
-  const uint64_t plane = fs->local_rows * (uint64_t)fs->width;
-  a.frames = fs->d_frames, a.vis = (const float *)d_vis, a.attr = d_attr, a.out = (float *)d_out;
-  a.vis_stride = 4ull * plane, a.frame_stride = out_planes * plane, a.gout_stride = n_ch * plane;
-  a.attr_frame_stride = attr_frames == 1u ? 0ull : (uint64_t)attr_tris * 3u * n_ch;
-  a.n_ch = n_ch;
-  a.local_rows = fs->local_rows, a.tiles_x = fs->tiles_x, a.n_local_bands = fs->n_local_bands, a.n_frames = (uint32_t)fs->n_frames;
-  a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
-  a.flags_or = flags;
-  return a;
-}
-} // namespace
-extern "C" {
 
 int srz_frameset_interpolate(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_attr, uint32_t n_ch, uint32_t attr_frames,
                              uint32_t attr_tris, void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
@@ -1471,16 +1526,14 @@ int srz_frameset_interpolate(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, 
   if (int rc = check_interp(ctx, fs, fn, n_ch, attr_frames, attr_tris, flags, &attr_bytes)) return rc;
   const size_t need = srz_frameset_interpolate_bytes(ctx, fs, n_ch), vis_bytes = srz_frameset_out_bytes(ctx, fs);
   if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
-  if ((((uintptr_t)d_vis | (uintptr_t)d_out) & 15u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
-  if (((uintptr_t)d_attr & 3u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": the attributes must be 4-byte aligned");
-  if (ranges_overlap(d_out, need, d_vis, vis_bytes) || ranges_overlap(d_out, need, d_attr, attr_bytes))
+  if (!aligned<16>({d_vis, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
+  if (!aligned<4>({d_attr})) return fail(ctx, SRZ_E_INVALID, fn + ": the attributes must be 4-byte aligned");
+  if (ranges_overlap({d_out, need}, {d_vis, vis_bytes}) || ranges_overlap({d_out, need}, {d_attr, attr_bytes}))
     return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the visibility buffer or the attributes");
-  if (int rc = check_renderable(ctx, fs)) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const hipStream_t s = pick_stream(ctx, stream);
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (the caller's attributes, not the set's triangles: no vertex stage)
   launch_interp(interp_args(fs, d_vis, d_attr, n_ch, attr_frames, attr_tris, n_ch, d_out, flags), s);
-  HIP_TRY(ctx, hipGetLastError());
-  return SRZ_OK;
+  return end_pass(ctx);
 }
 
 int srz_frameset_interpolate_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_gout, const float *d_attr, uint32_t n_ch,
@@ -1494,24 +1547,17 @@ int srz_frameset_interpolate_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_
   if (int rc = check_interp(ctx, fs, fn, n_ch, attr_frames, attr_tris, flags, &attr_bytes)) return rc;
   const size_t gout_bytes = srz_frameset_interpolate_bytes(ctx, fs, n_ch), gbary_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u);
   const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs);
-  if ((((uintptr_t)d_vis | (uintptr_t)d_gout | (uintptr_t)d_gbary) & 15u) != 0)
-    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers must be 16-byte aligned");
-  if ((((uintptr_t)d_attr | (uintptr_t)d_gattr) & 3u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": attributes and their gradient must be 4-byte aligned");
-  const void *outs[2] = {d_gattr, d_gbary};
-  const size_t out_sizes[2] = {attr_bytes, gbary_bytes};
-  for (int i = 0; i < 2; ++i)
-    if (ranges_overlap(outs[i], out_sizes[i], d_vis, vis_bytes) || ranges_overlap(outs[i], out_sizes[i], d_gout, gout_bytes) ||
-        ranges_overlap(outs[i], out_sizes[i], d_attr, attr_bytes))
-      return fail(ctx, SRZ_E_INVALID, fn + ": an output overlaps an input");
-  if (ranges_overlap(d_gattr, attr_bytes, d_gbary, gbary_bytes)) return fail(ctx, SRZ_E_INVALID, fn + ": the two outputs overlap");
-  if (int rc = check_renderable(ctx, fs)) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const hipStream_t s = pick_stream(ctx, stream);
+  if (!aligned<16>({d_vis, d_gout, d_gbary})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers must be 16-byte aligned");
+  if (!aligned<4>({d_attr, d_gattr})) return fail(ctx, SRZ_E_INVALID, fn + ": attributes and their gradient must be 4-byte aligned");
+  if (int rc = check_grad_overlap(ctx, fn, {{d_gattr, attr_bytes}, {d_gbary, gbary_bytes}},
+                                  {{d_vis, vis_bytes}, {d_gout, gout_bytes}, {d_attr, attr_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_interpolate)
   InterpArgs a = interp_args(fs, d_vis, d_attr, n_ch, attr_frames, attr_tris, 2u, d_gbary, flags);
   a.gout = (const float *)d_gout, a.gattr = d_gattr;
   launch_interp_grad(a, s);
-  HIP_TRY(ctx, hipGetLastError());
-  return SRZ_OK;
+  return end_pass(ctx);
 }
 
 int srz_frameset_position_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_gbary, const void *d_gz, uint32_t pos_tris,
@@ -1521,66 +1567,27 @@ int srz_frameset_position_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis
   if (!fs || !d_vis) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer");
   if (!d_gbary && !d_gz) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gbary nor d_gz is given");
   if (!d_gpos && !d_gpix) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gpos nor d_gpix is asked for");
-  if ((flags & ~(uint32_t)SRZ_FUSED_CLEAR) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": only SRZ_FUSED_CLEAR is accepted in flags");
-  for (const FrameDesc &d : fs->h_frames)
-    if (d.n_tris > pos_tris) return fail(ctx, SRZ_E_INVALID, fn + ": pos_tris is below a frame's triangle count");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  if (int rc = check_tri_count(ctx, fs, fn, "pos_tris", pos_tris)) return rc;
   const size_t two_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u), one_bytes = srz_frameset_interpolate_bytes(ctx, fs, 1u);
   const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs), gpos_bytes = (size_t)fs->n_frames * pos_tris * TRI_POS_F * sizeof(float);
-  if ((((uintptr_t)d_vis | (uintptr_t)d_gbary | (uintptr_t)d_gz | (uintptr_t)d_gpix) & 15u) != 0)
-    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers must be 16-byte aligned");
-  if (((uintptr_t)d_gpos & 3u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": the position gradient must be 4-byte aligned");
-  const void *outs[2] = {d_gpos, d_gpix};
-  const size_t out_sizes[2] = {gpos_bytes, two_bytes};
-  for (int i = 0; i < 2; ++i)
-    if (ranges_overlap(outs[i], out_sizes[i], d_vis, vis_bytes) || ranges_overlap(outs[i], out_sizes[i], d_gbary, two_bytes) ||
-        ranges_overlap(outs[i], out_sizes[i], d_gz, one_bytes))
-      return fail(ctx, SRZ_E_INVALID, fn + ": an output overlaps an input");
-  if (ranges_overlap(d_gpos, gpos_bytes, d_gpix, two_bytes)) return fail(ctx, SRZ_E_INVALID, fn + ": the two outputs overlap");
-  if (int rc = check_renderable(ctx, fs)) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const hipStream_t s = pick_stream(ctx, stream);
-  // a sceneset's triangles are its vertex stage's output (as srz_frameset_motion)
-  if (fs->d_draws) launch_vertex(fs->d_draws, fs->n_draws, fs->max_faces, fs->d_tris, fs->d_tri_pos, fs->d_frames, nullptr, s);
+  if (!aligned<16>({d_vis, d_gbary, d_gz, d_gpix})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers must be 16-byte aligned");
+  if (!aligned<4>({d_gpos})) return fail(ctx, SRZ_E_INVALID, fn + ": the position gradient must be 4-byte aligned");
+  if (int rc = check_grad_overlap(ctx, fn, {{d_gpos, gpos_bytes}, {d_gpix, two_bytes}},
+                                  {{d_vis, vis_bytes}, {d_gbary, two_bytes}, {d_gz, one_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, PASS_VERTEX, &s)) return rc;
   PosGradArgs a{};
-  const uint64_t plane = fs->local_rows * (uint64_t)fs->width;
-  a.frames = fs->d_frames;
-  a.tri_pos = fs->d_tri_pos ? fs->d_tri_pos : reinterpret_cast<const float *>(fs->d_tris);
-  a.pos_stride = fs->d_tri_pos ? TRI_POS_F : TRI_AOS_F;
-  a.vis = (const float *)d_vis, a.gbary = (const float *)d_gbary, a.gz = (const float *)d_gz, a.gpos = d_gpos, a.out = (float *)d_gpix;
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_gpix);
+  fill_positions(a, fs);
+  a.gbary = (const float *)d_gbary, a.gz = (const float *)d_gz, a.gpos = d_gpos;
   a.vis_stride = 4ull * plane, a.frame_stride = 2ull * plane, a.gz_stride = plane, a.gpos_stride = (uint64_t)pos_tris * TRI_POS_F;
-  a.local_rows = fs->local_rows, a.tiles_x = fs->tiles_x, a.n_local_bands = fs->n_local_bands, a.n_frames = (uint32_t)fs->n_frames;
-  a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
   a.flags_or = flags;
   launch_pos_grad(a, s);
-  HIP_TRY(ctx, hipGetLastError());
-  return SRZ_OK;
+  return end_pass(ctx);
 }
-
-} // extern "C"
-namespace {
-// what srz_frameset_antialias and _antialias_grad check alike
-int check_antialias(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, uint32_t n_ch, uint32_t flags) {
-  if (n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_ATTR_MAX_CH");
-  if ((flags & ~(uint32_t)SRZ_FUSED_CLEAR) != 0u) return fail(ctx, SRZ_E_INVALID, fn + ": only SRZ_FUSED_CLEAR is accepted in flags");
-  if (fs->shard_world > 1)
-    return fail(ctx, SRZ_E_INVALID, fn + ": needs the whole frame on this ctx (a vertical pair across a band edge needs another rank's rows)");
-  return SRZ_OK;
-}
-AntialiasArgs antialias_args(const srz_frameset *fs, const void *d_vis, const void *d_in, uint32_t n_ch, void *d_out) {
-  AntialiasArgs a{};
-  const uint64_t plane = fs->local_rows * (uint64_t)fs->width;
-  a.frames = fs->d_frames;
-  a.tri_pos = fs->d_tri_pos ? fs->d_tri_pos : reinterpret_cast<const float *>(fs->d_tris);
-  a.pos_stride = fs->d_tri_pos ? TRI_POS_F : TRI_AOS_F;
-  a.vis = (const float *)d_vis, a.in = (const float *)d_in, a.out = (float *)d_out;
-  a.vis_stride = 4ull * plane, a.frame_stride = n_ch * plane;
-  a.n_ch = n_ch;
-  a.local_rows = fs->local_rows, a.tiles_x = fs->tiles_x, a.n_local_bands = fs->n_local_bands, a.n_frames = (uint32_t)fs->n_frames;
-  a.shard_rank = fs->shard_rank, a.shard_world = fs->shard_world;
-  return a;
-}
-} // namespace
-extern "C" {
 
 int srz_frameset_antialias(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_in, uint32_t n_ch, void *d_out, size_t out_bytes,
                            uint32_t flags, void *stream) {
@@ -1590,17 +1597,13 @@ int srz_frameset_antialias(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, co
   if (int rc = check_antialias(ctx, fs, fn, n_ch, flags)) return rc;
   const size_t need = srz_frameset_interpolate_bytes(ctx, fs, n_ch), vis_bytes = srz_frameset_out_bytes(ctx, fs);
   if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
-  if ((((uintptr_t)d_vis | (uintptr_t)d_in | (uintptr_t)d_out) & 15u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
-  if (ranges_overlap(d_out, need, d_vis, vis_bytes) || ranges_overlap(d_out, need, d_in, need))
+  if (!aligned<16>({d_vis, d_in, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
+  if (ranges_overlap({d_out, need}, {d_vis, vis_bytes}) || ranges_overlap({d_out, need}, {d_in, need}))
     return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the visibility buffer or the input (the pass reads neighbours: not in place)");
-  if (int rc = check_renderable(ctx, fs)) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const hipStream_t s = pick_stream(ctx, stream);
-  // a sceneset's triangles are its vertex stage's output (as srz_frameset_position_grad)
-  if (fs->d_draws) launch_vertex(fs->d_draws, fs->n_draws, fs->max_faces, fs->d_tris, fs->d_tri_pos, fs->d_frames, nullptr, s);
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, PASS_VERTEX, &s)) return rc;
   launch_antialias(antialias_args(fs, d_vis, d_in, n_ch, d_out), s);
-  HIP_TRY(ctx, hipGetLastError());
-  return SRZ_OK;
+  return end_pass(ctx);
 }
 
 int srz_frameset_antialias_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_in, const void *d_gout, uint32_t n_ch,
@@ -1611,30 +1614,20 @@ int srz_frameset_antialias_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vi
   if (!d_gin && !d_gpos) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gin nor d_gpos is asked for");
   if (int rc = check_antialias(ctx, fs, fn, n_ch, flags)) return rc;
   if (d_gpos)
-    for (const FrameDesc &d : fs->h_frames)
-      if (d.n_tris > pos_tris) return fail(ctx, SRZ_E_INVALID, fn + ": pos_tris is below a frame's triangle count");
+    if (int rc = check_tri_count(ctx, fs, fn, "pos_tris", pos_tris)) return rc;
   const size_t planes_bytes = srz_frameset_interpolate_bytes(ctx, fs, n_ch), vis_bytes = srz_frameset_out_bytes(ctx, fs);
   const size_t gpos_bytes = (size_t)fs->n_frames * pos_tris * TRI_POS_F * sizeof(float);
-  if ((((uintptr_t)d_vis | (uintptr_t)d_in | (uintptr_t)d_gout | (uintptr_t)d_gin) & 15u) != 0)
-    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers must be 16-byte aligned");
-  if (((uintptr_t)d_gpos & 3u) != 0) return fail(ctx, SRZ_E_INVALID, fn + ": the position gradient must be 4-byte aligned");
-  const void *outs[2] = {d_gin, d_gpos};
-  const size_t out_sizes[2] = {planes_bytes, gpos_bytes};
-  for (int i = 0; i < 2; ++i)
-    if (ranges_overlap(outs[i], out_sizes[i], d_vis, vis_bytes) || ranges_overlap(outs[i], out_sizes[i], d_in, planes_bytes) ||
-        ranges_overlap(outs[i], out_sizes[i], d_gout, planes_bytes))
-      return fail(ctx, SRZ_E_INVALID, fn + ": an output overlaps an input");
-  if (ranges_overlap(d_gin, planes_bytes, d_gpos, gpos_bytes)) return fail(ctx, SRZ_E_INVALID, fn + ": the two outputs overlap");
-  if (int rc = check_renderable(ctx, fs)) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const hipStream_t s = pick_stream(ctx, stream);
-  // a sceneset's triangles are its vertex stage's output (as srz_frameset_position_grad)
-  if (fs->d_draws) launch_vertex(fs->d_draws, fs->n_draws, fs->max_faces, fs->d_tris, fs->d_tri_pos, fs->d_frames, nullptr, s);
+  if (!aligned<16>({d_vis, d_in, d_gout, d_gin})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers must be 16-byte aligned");
+  if (!aligned<4>({d_gpos})) return fail(ctx, SRZ_E_INVALID, fn + ": the position gradient must be 4-byte aligned");
+  if (int rc = check_grad_overlap(ctx, fn, {{d_gin, planes_bytes}, {d_gpos, gpos_bytes}},
+                                  {{d_vis, vis_bytes}, {d_in, planes_bytes}, {d_gout, planes_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, PASS_VERTEX, &s)) return rc;
   AntialiasArgs a = antialias_args(fs, d_vis, d_in, n_ch, d_gin);
   a.gout = (const float *)d_gout, a.gpos = d_gpos, a.gpos_stride = (uint64_t)pos_tris * TRI_POS_F;
   launch_antialias_grad(a, s);
-  HIP_TRY(ctx, hipGetLastError());
-  return SRZ_OK;
+  return end_pass(ctx);
 }
 
 int srz_frameset_update_shading(srz_ctx *ctx, srz_frameset *fs, const srz_frame *frames, int n_frames) {

@@ -4861,13 +4861,14 @@ void launch_clear(const RenderArgs &a, uint32_t max_tiles, hipStream_t s, uint32
   hipLaunchKernelGGL(k_clear, dim3(n_items < cap ? n_items : cap), dim3(256), 0, s, a);
 }
 
+// The grid of a kernel that strides over `items` tiles: at most `cap` workgroups, a multiple of 8 (workgroup b serves the frames f ≡ b mod 8)
+static uint32_t tile_grid(uint32_t items, uint32_t cap = 16384u) { return (std::min(items, cap) + 7u) & ~7u; }
+
 // One stream: a LARGE grid (a tile or two per workgroup: in-order hand-out, one-tile tail).  Renders interleaved on several streams
 // (a.other_streams): a grid about as large as the machine's resident capacity, the workgroups striding through the lists — measured,
 // 2 x 128 frames of 1024^2 on two streams: 16384 workgroups 1.10 ms per batch, 4096 1.08, 2560 1.07, 1280 1.065 (and on ONE stream
 // 0.73 / 0.78 / — / 0.78 ms for k_shade alone).  A multiple of 8: workgroup b serves list b % 8.
-static dim3 shade_grid(const RenderArgs &a, uint32_t max_tiles) {
-  return dim3((std::min(max_tiles, a.other_streams ? 2048u : 16384u) + 7u) & ~7u);
-}
+static dim3 shade_grid(const RenderArgs &a, uint32_t max_tiles) { return dim3(tile_grid(max_tiles, a.other_streams ? 2048u : 16384u)); }
 
 // One launch per FAST build kind of `kinds`, in ascending kind order: launch(FASTNL, BUMPY, APPROX) gets each as std::integral_constants.
 // The tolerance mode (approx) has builds for kinds 0..3 only: classify_frames sends it no frame of another FAST kind.
@@ -4910,7 +4911,7 @@ void launch_visibility(const RenderArgs &a, uint32_t max_tiles, hipStream_t s) {
 void launch_shade_vis(const ShadeVisArgs &a, uint32_t kinds, bool any_generic, bool approx, hipStream_t s) {
   const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
   if (items == 0) return;
-  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u), blk(256); // (a multiple of 8: workgroup b serves the frames f ≡ b mod 8)
+  const dim3 grid(tile_grid(items)), blk(256);
   launch_fast_kinds(kinds, approx, [&](auto nl, auto bumpy, auto ap) {
     hipLaunchKernelGGL((k_shade_vis<decltype(nl)::value, decltype(bumpy)::value, decltype(ap)::value>), grid, blk, 0, s, a);
   });
@@ -4918,54 +4919,18 @@ void launch_shade_vis(const ShadeVisArgs &a, uint32_t kinds, bool any_generic, b
   if (any_generic || (kinds && !approx)) hipLaunchKernelGGL((k_shade_vis<0>), any_generic ? grid : dim3(std::min(grid.x, 128u)), blk, 0, s, a);
 }
 
-void launch_gbuffer(const GbufArgs &a, hipStream_t s) {
+// the passes over a visibility buffer that are one kernel each: one workgroup of 256 per tile_grid() entry, nothing for an empty set
+template <auto Kernel, class Args> static void launch_pass(const Args &a, hipStream_t s) {
   const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
-  if (items == 0) return;
-  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (a multiple of 8: workgroup b serves the frames f ≡ b mod 8)
-  hipLaunchKernelGGL(k_gbuffer, grid, dim3(256), 0, s, a);
+  if (items != 0) hipLaunchKernelGGL(Kernel, dim3(tile_grid(items)), dim3(256), 0, s, a);
 }
-
-void launch_motion(const MotionArgs &a, hipStream_t s) {
-  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
-  if (items == 0) return;
-  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (a multiple of 8: workgroup b serves the frames f ≡ b mod 8)
-  hipLaunchKernelGGL(k_motion, grid, dim3(256), 0, s, a);
-}
-
-void launch_interp(const InterpArgs &a, hipStream_t s) {
-  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
-  if (items == 0) return;
-  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (a multiple of 8: workgroup b serves the frames f ≡ b mod 8)
-  hipLaunchKernelGGL(k_interp, grid, dim3(256), 0, s, a);
-}
-
-void launch_interp_grad(const InterpArgs &a, hipStream_t s) {
-  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
-  if (items == 0) return;
-  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (as launch_interp)
-  hipLaunchKernelGGL(k_interp_grad, grid, dim3(256), 0, s, a);
-}
-
-void launch_pos_grad(const PosGradArgs &a, hipStream_t s) {
-  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
-  if (items == 0) return;
-  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (as launch_interp)
-  hipLaunchKernelGGL(k_pos_grad, grid, dim3(256), 0, s, a);
-}
-
-void launch_antialias(const AntialiasArgs &a, hipStream_t s) {
-  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
-  if (items == 0) return;
-  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (as launch_interp)
-  hipLaunchKernelGGL(k_antialias, grid, dim3(256), 0, s, a);
-}
-
-void launch_antialias_grad(const AntialiasArgs &a, hipStream_t s) {
-  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
-  if (items == 0) return;
-  const dim3 grid((std::min(items, 16384u) + 7u) & ~7u); // (as launch_interp)
-  hipLaunchKernelGGL(k_antialias_grad, grid, dim3(256), 0, s, a);
-}
+void launch_gbuffer(const GbufArgs &a, hipStream_t s) { launch_pass<k_gbuffer>(a, s); }
+void launch_motion(const MotionArgs &a, hipStream_t s) { launch_pass<k_motion>(a, s); }
+void launch_interp(const InterpArgs &a, hipStream_t s) { launch_pass<k_interp>(a, s); }
+void launch_interp_grad(const InterpArgs &a, hipStream_t s) { launch_pass<k_interp_grad>(a, s); }
+void launch_pos_grad(const PosGradArgs &a, hipStream_t s) { launch_pass<k_pos_grad>(a, s); }
+void launch_antialias(const AntialiasArgs &a, hipStream_t s) { launch_pass<k_antialias>(a, s); }
+void launch_antialias_grad(const AntialiasArgs &a, hipStream_t s) { launch_pass<k_antialias_grad>(a, s); }
 
 bool raster_four_waves(const RenderArgs &a) { return a.n_frames * a.n_local_bands * a.tiles_x <= 4096u; }
 

@@ -4,31 +4,20 @@ to the positions accumulated in double with the sum of |term| and the count of c
 a double-precision restatement of the forward for finite differences.  Built and loaded like tests/posgradref.py's library; nothing
 of the product is involved."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "antialias_ref.c")
+from support import ref_lib, word_planes
+
 COUNTERS = ("differ", "target_n", "target_f", "horizontal", "vertical", "interior", "f_nobody", "no_edge")
-_lib = None
+vp = C.c_void_p
+SIGNATURES = {"aa_forward": (None, [vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
+              "aa_backward": (None, [vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]),
+              "aa_forward64": (None, [vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp])}
 
 
 def lib(tmpdir):
-    global _lib
-    if _lib is None:
-        so = os.path.join(str(tmpdir), "libantialias_ref.so")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-o", so, SRC, "-lm"])
-        L = C.CDLL(so)
-        vp = C.c_void_p
-        L.aa_forward.argtypes = [vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]
-        L.aa_backward.argtypes = [vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
-        L.aa_forward64.argtypes = [vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]
-        for f in (L.aa_forward, L.aa_backward, L.aa_forward64):
-            f.restype = None
-        _lib = L
-    return _lib
+    return ref_lib("antialias_ref", tmpdir, SIGNATURES)
 
 
 class Grad:
@@ -52,9 +41,8 @@ class Grad:
 
 
 def _planes(vis_words):
-    w = np.ascontiguousarray(vis_words, np.uint32)
-    assert w.ndim == 3 and w.shape[0] == 4
-    return np.ascontiguousarray(w[0]).view(np.float32), np.ascontiguousarray(w[1]), w.shape[1], w.shape[2]
+    (z, ids, _, _), (rows, W) = word_planes(vis_words)
+    return z.view(np.float32), ids, rows, W
 
 
 def _p(a):
@@ -110,11 +98,6 @@ def forward64(tmpdir, pos64, n_tris, vis_words, planes64):
     out, dec = np.zeros_like(c), np.zeros((2, rows, W), np.uint8)
     lib(tmpdir).aa_forward64(_p(pos), n_tris, rows, W, _p(z), _p(ids), _p(c), c.shape[0], _p(out), _p(dec))
     return out, dec
-
-
-def frame_pos(frame):
-    """[n, 9] float32: ax ay z0 bx by z1 cx cy z2 of every triangle of an abi.Frame, in stream order"""
-    return np.ascontiguousarray(np.concatenate([t["pos"] for t in frame.tris]), np.float32).reshape(-1, 9)
 
 
 # ------------------------------------------------------------------------------------------------ the scenes of the GPU tests

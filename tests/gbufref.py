@@ -2,34 +2,25 @@
 textures, and per pixel (owner id word, alpha, beta) → the nine planes of every group, as uint32 words.  Built and loaded like
 tests/visref.py's library; nothing of the product is involved."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from srz import abi
+from support import ref_lib, word_planes
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 GROUPS = ((abi.GB_NORMAL, (0, 1, 2)), (abi.GB_UV, (3, 4)), (abi.GB_BATCH, (5,)), (abi.GB_ALBEDO, (6, 7, 8)))
-_lib = None
 
 
 class GrBatch(C.Structure):
     _fields_ = [("shader", C.c_int32), ("tw", C.c_int32), ("th", C.c_int32), ("_pad", C.c_int32), ("bgr", C.c_void_p)]
 
 
+vp = C.c_void_p
+SIGNATURES = {"gr_gbuffer": (None, [vp, C.c_uint32, vp, C.POINTER(GrBatch), C.c_size_t, vp, vp, vp, C.c_int, vp])}
+
+
 def lib(tmpdir):
-    global _lib
-    if _lib is None:
-        so = os.path.join(str(tmpdir), "libgbuf_ref.so")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-o", so,
-                               os.path.join(HERE, "gbuf_ref.c"), "-lm"])
-        L = C.CDLL(so)
-        vp = C.c_void_p
-        L.gr_gbuffer.argtypes = [vp, C.c_uint32, vp, C.POINTER(GrBatch), C.c_size_t, vp, vp, vp, C.c_int, vp]
-        L.gr_gbuffer.restype = None
-        _lib = L
-    return _lib
+    return ref_lib("gbuf_ref", tmpdir, SIGNATURES)
 
 
 def planes_of(what):
@@ -57,9 +48,7 @@ def expected(tmpdir, frame, textures, vis_words, fused=True, prefill=None, shadi
             t = np.ascontiguousarray(tex, np.uint8)
             keep.append(t)
             table[b] = GrBatch(sh, t.shape[1], t.shape[0], 0, t.ctypes.data)
-    w = np.ascontiguousarray(vis_words, np.uint32)
-    rows, W = w.shape[1:]
-    ids, al, be = (np.ascontiguousarray(w[p]) for p in (1, 2, 3))
+    (_, ids, al, be), (rows, W) = word_planes(vis_words)
     out = np.zeros((9, rows, W), np.uint32) if prefill is None else np.array(prefill, np.uint32, copy=True, order="C")
     L.gr_gbuffer(tris.ctypes.data, n, tri_batch.ctypes.data, table, rows * W, ids.ctypes.data, al.ctypes.data, be.ctypes.data, int(fused),
                  out.ctypes.data)

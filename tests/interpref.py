@@ -3,34 +3,18 @@
 with respect to alpha and beta and the attribute gradient accumulated in double.  Built and loaded like tests/gbufref.py's library;
 nothing of the product is involved."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "interp_ref.c")
-_lib = None
+from support import ref_lib, word_planes
+
+vp = C.c_void_p
+SIGNATURES = {"ir_forward": (None, [vp, C.c_uint32, C.c_uint32, C.c_size_t, vp, vp, vp, C.c_int, vp]),
+              "ir_grad": (None, [vp, C.c_uint32, C.c_uint32, C.c_size_t, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp])}
 
 
 def lib(tmpdir):
-    global _lib
-    if _lib is None:
-        so = os.path.join(str(tmpdir), "libinterp_ref.so")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-o", so, SRC, "-lm"])
-        L = C.CDLL(so)
-        vp = C.c_void_p
-        L.ir_forward.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_size_t, vp, vp, vp, C.c_int, vp]
-        L.ir_forward.restype = None
-        L.ir_grad.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_size_t, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
-        L.ir_grad.restype = None
-        _lib = L
-    return _lib
-
-
-def _planes(vis_words):
-    w = np.ascontiguousarray(vis_words, np.uint32)
-    return [np.ascontiguousarray(w[p]) for p in (1, 2, 3)], w.shape[1:]
+    return ref_lib("interp_ref", tmpdir, SIGNATURES)
 
 
 def forward(tmpdir, attr, n_tris, vis_words, fused=True, prefill=None):
@@ -38,7 +22,7 @@ def forward(tmpdir, attr, n_tris, vis_words, fused=True, prefill=None):
     buffer → [C, rows, W] float32.  prefill: [C, rows, W] uint32 words the planes start from (not fused: nobody's words stay)."""
     attr = np.ascontiguousarray(attr, np.float32)
     n_ch = attr.shape[2]
-    (ids, al, be), (rows, W) = _planes(vis_words)
+    (_, ids, al, be), (rows, W) = word_planes(vis_words)
     out = np.zeros((n_ch, rows, W), np.uint32) if prefill is None else np.array(prefill, np.uint32, copy=True, order="C")
     assert out.shape == (n_ch, rows, W) and attr.shape[0] >= n_tris and attr.shape[1] == 3
     lib(tmpdir).ir_forward(attr.ctypes.data, n_ch, n_tris, rows * W, ids.ctypes.data, al.ctypes.data, be.ctypes.data, int(fused), out.ctypes.data)
@@ -64,7 +48,7 @@ def grad(tmpdir, attr, n_tris, vis_words, gout, into=None, want_bary=True, fused
     """one frame's share: adds into `into` (a Grad, or None) and returns the gbary planes [2, rows, W] float32 (None if not wanted)"""
     attr = np.ascontiguousarray(attr, np.float32)
     n_ch = attr.shape[2]
-    (ids, al, be), (rows, W) = _planes(vis_words)
+    (_, ids, al, be), (rows, W) = word_planes(vis_words)
     gout = np.ascontiguousarray(gout, np.float32)
     assert gout.shape == (n_ch, rows, W) and attr.shape[0] >= n_tris
     gb = None

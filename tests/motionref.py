@@ -8,25 +8,16 @@ import subprocess
 import numpy as np
 
 from srz import abi
+from support import build_c, ref_lib, word_planes
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "motion_ref.c")
 GROUPS = ((abi.MV_FLOW, (0, 1)), (abi.MV_DEPTH, (2,)), (abi.MV_TARGET, (3, 4)))
 INF_WORD = 0x7f800000
-_lib = None
+vp = C.c_void_p
+SIGNATURES = {"mr_motion": (None, [vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp])}
 
 
 def lib(tmpdir):
-    global _lib
-    if _lib is None:
-        so = os.path.join(str(tmpdir), "libmotion_ref.so")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-o", so, SRC, "-lm"])
-        L = C.CDLL(so)
-        vp = C.c_void_p
-        L.mr_motion.argtypes = [vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
-        L.mr_motion.restype = None
-        _lib = L
-    return _lib
+    return ref_lib("motion_ref", tmpdir, SIGNATURES)
 
 
 def planes_of(what):
@@ -34,21 +25,14 @@ def planes_of(what):
     return [i for bit, idx in GROUPS if what & bit for i in idx]
 
 
-def positions(frame):
-    """[n, 9] float32: ax ay z0 bx by z1 cx cy z2 of every triangle of an abi.Frame, in stream order"""
-    if not sum(len(t) for t in frame.tris):
-        return np.zeros((0, 9), np.float32)
-    return np.ascontiguousarray(np.concatenate([t["pos"] for t in frame.tris]).reshape(-1, 9), np.float32)
-
-
 def _inputs(pos, vis_words, target_words, prefill):
     pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 9)
-    w, t = np.ascontiguousarray(vis_words, np.uint32), np.ascontiguousarray(target_words, np.uint32)
-    rows, W = w.shape[1:]
-    assert t.shape[1:] == (rows, W)
+    (_, ids, al, be), (rows, W) = word_planes(vis_words)
+    (tz, tid, _, _), target_shape = word_planes(target_words)
+    assert target_shape == (rows, W)
     out = np.zeros((5, rows, W), np.uint32) if prefill is None else np.array(prefill, np.uint32, copy=True, order="C")
     assert out.shape == (5, rows, W)
-    return pos, [np.ascontiguousarray(w[p]) for p in (1, 2, 3)] + [np.ascontiguousarray(t[p]) for p in (1, 0)], out
+    return pos, [ids, al, be, tid, tz], out
 
 
 def expected(tmpdir, pos, vis_words, target_words, fused=True, prefill=None):
@@ -72,9 +56,8 @@ def expected_sanitized(tmpdir, pos, vis_words, target_words, fused=True, prefill
     huge coordinate converted to an integer is a report) on heap blocks of exactly the arrays' sizes; any report fails the run"""
     exe = os.path.join(str(tmpdir), "motion_ref_asan")
     if not os.path.exists(exe):
-        subprocess.check_call(["gcc", "-O1", "-g", "-ffp-contract=off", "-fno-fast-math", "-DMOTION_REF_MAIN",
-                               "-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-                               "-o", exe, SRC, "-lm"])
+        build_c("motion_ref", exe, "-O1", "-g", "-DMOTION_REF_MAIN", "-fsanitize=address,undefined,float-cast-overflow",
+                "-fno-sanitize-recover=all", "-fno-omit-frame-pointer")
     pos, planes, out = _inputs(pos, vis_words, target_words, prefill)
     rows, W = out.shape[1:]
     src, dst = os.path.join(str(tmpdir), "motion_in.bin"), os.path.join(str(tmpdir), "motion_out.bin")

@@ -3,27 +3,17 @@
 gradient with respect to the positions accumulated in double.  Built and loaded like tests/interpref.py's library; nothing of the
 product is involved."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "posgrad_ref.c")
-_lib = None
+from support import ref_lib, word_planes
+
+vp = C.c_void_p
+SIGNATURES = {"pg_grad": (None, [vp, C.c_uint32, C.c_size_t, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp])}
 
 
 def lib(tmpdir):
-    global _lib
-    if _lib is None:
-        so = os.path.join(str(tmpdir), "libposgrad_ref.so")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-o", so, SRC, "-lm"])
-        L = C.CDLL(so)
-        vp = C.c_void_p
-        L.pg_grad.argtypes = [vp, C.c_uint32, C.c_size_t, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
-        L.pg_grad.restype = None
-        _lib = L
-    return _lib
+    return ref_lib("posgrad_ref", tmpdir, SIGNATURES)
 
 
 class Grad:
@@ -41,19 +31,12 @@ class Grad:
         return n / (1.0 - n) * (calls * self.gabs)
 
 
-def frame_pos(frame):
-    """[n, 9] float32: ax ay z0 bx by z1 cx cy z2 of every triangle of an abi.Frame, in stream order"""
-    return np.ascontiguousarray(np.concatenate([t["pos"] for t in frame.tris]), np.float32).reshape(-1, 9)
-
-
 def grad(tmpdir, pos, n_tris, vis_words, gbary=None, gz=None, into=None, want_pix=True, fused=True, prefill=None):
     """one frame: pos [T, 9] float32 (T >= n_tris, the frame's triangle count), vis_words [4, rows, W] uint32 of its visibility
     buffer, gbary [2, rows, W] and / or gz [1, rows, W] float32.  Adds into `into` (a Grad, or None) and returns the gpix planes
     [2, rows, W] float32 (None if not wanted).  prefill: [2, rows, W] uint32 words gpix starts from (not fused: nobody's words stay)."""
     pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 9)
-    w = np.ascontiguousarray(vis_words, np.uint32)
-    ids, al, be = (np.ascontiguousarray(w[p]) for p in (1, 2, 3))
-    rows, W = w.shape[1:]
+    (_, ids, al, be), (rows, W) = word_planes(vis_words)
     assert pos.shape[0] >= n_tris and (gbary is not None or gz is not None)
     gb = None if gbary is None else np.ascontiguousarray(gbary, np.float32)
     g = None if gz is None else np.ascontiguousarray(gz, np.float32)

@@ -1,5 +1,5 @@
 """What the tests share, each thing once: the frame builders (inputs, numpy only), the comparisons with their stated bounds, the
-oracle-vs-GPU steps and the context fixtures.  A plain module like tests/scenes.py: importable without a GPU and without pytest
+oracle-vs-GPU steps, the kit of the passes over a visibility buffer (and of their references) and the context fixtures.  A plain module like tests/scenes.py: importable without a GPU and without pytest
 running (tools/fuzz_probe.py imports it as a script); torch and srz are imported by the functions that need them.  Test modules
 import from here and from scenes, never from one another."""
 import functools
@@ -670,6 +670,90 @@ def oracle_with_probes(orc, f):
     assert rc1 == 0 and rc2 == 0
     s_class = cls[1] == -1.0
     return ref, rst, pre, s_class
+
+
+# ------------------------------------------------------------------------------------------------ the passes over a visibility buffer
+# What the tests of srz_frameset_gbuffer / _motion / _interpolate / _position_grad / _antialias and of their CPU references share.
+HERE = os.path.dirname(os.path.abspath(__file__))
+SENTINEL = 0xdeadbeef
+MIN_CLASS, MAX_AMBIGUOUS = 200, 0.005
+_ref_libs = {}
+
+
+def build_c(name, out, *flags):
+    """tests/<name>.c with the oracle's float rules (no contraction, no fast-math) and `flags` -> the file `out`"""
+    import subprocess
+    subprocess.check_call(["gcc", *flags, "-ffp-contract=off", "-fno-fast-math", "-o", out, os.path.join(HERE, name + ".c"), "-lm"])
+    return out
+
+
+def ref_lib(name, tmpdir, signatures):
+    """the reference tests/<name>.c as a shared library, built (into tmpdir) and loaded once per session; signatures: function ->
+    (restype, argtypes)"""
+    if name not in _ref_libs:
+        import ctypes
+        L = ctypes.CDLL(build_c(name, os.path.join(str(tmpdir), f"lib{name}.so"), "-O2", "-shared", "-fPIC"))
+        for fn, (restype, argtypes) in signatures.items():
+            getattr(L, fn).restype, getattr(L, fn).argtypes = restype, argtypes
+        _ref_libs[name] = L
+    return _ref_libs[name]
+
+
+def word_planes(vis_words):
+    """[4, rows, W] words of one frame's visibility buffer -> ([z, id, alpha, beta] as contiguous uint32 planes, (rows, W))"""
+    w = np.ascontiguousarray(vis_words, np.uint32)
+    assert w.ndim == 3 and w.shape[0] == 4
+    return [np.ascontiguousarray(w[p]) for p in range(4)], w.shape[1:]
+
+
+def frame_positions(frame):
+    """[n, 9] float32: ax ay z0 bx by z1 cx cy z2 of every triangle of an abi.Frame, in stream order"""
+    if not sum(len(t) for t in frame.tris):
+        return np.zeros((0, 9), np.float32)
+    return np.ascontiguousarray(np.concatenate([t["pos"] for t in frame.tris]).reshape(-1, 9), np.float32)
+
+
+def padded_positions(frames, T):
+    """[n, T, 9] float32: every frame's dense position stream, zeros behind its last triangle"""
+    pos = np.zeros((len(frames), T, 9), np.float32)
+    for i, f in enumerate(frames):
+        pos[i, :f.n_tris] = frame_positions(f)
+    return pos
+
+
+def visibility(fs, flags=abi.FUSED_CLEAR):
+    """the set's visibility render into a fresh buffer -> [n, 4, local_rows, W] float32 tensor"""
+    import torch
+    vis = torch.zeros(fs.out_shape, dtype=torch.float32, device="cuda")
+    fs.render_visibility(vis.data_ptr(), fs.out_bytes, flags, stream())
+    torch.cuda.synchronize()
+    return vis
+
+
+def filled(shape, fill=SENTINEL):
+    """an int32 tensor on the device, every word `fill` (a uint32 value)"""
+    import torch
+    return torch.full(shape, fill - (1 << 32) if fill >= 1 << 31 else fill, dtype=torch.int32, device="cuda")
+
+
+def visibility_of(tmp_path, orc, f, max_ambiguous=None):
+    """the oracle's visibility buffer of frame f (visref.Reference.expected) -> a namespace: words [4, H, W]; the masks own, v_class,
+    s_class; amb, the pixels left out (id 0) because their colour decodes to no single owner; n, the frame's triangle count.  Asserted,
+    so that no comparison passes vacuously: >= MIN_CLASS owned pixels of each class, the id words
+    name the owned pixels and nobody else, and (max_ambiguous given) amb <= max_ambiguous of the owned and left-out pixels"""
+    import types
+    import visref
+    words, _, amb, _, own = visref.Reference(tmp_path, f).expected(orc)
+    n = sum(len(t) for t in f.tris)
+    assert np.array_equal(own, ((words[1] & 0x7fffffff) - np.uint32(1)) < n)
+    s_class = own & ((words[1] >> 31) != 0)
+    v_class = own & ~s_class
+    n_v, n_s = int(v_class.sum()), int(s_class.sum())
+    print(f"owned V {n_v} S {n_s} ambiguous {amb}")
+    assert n_v >= MIN_CLASS and n_s >= MIN_CLASS, (n_v, n_s)
+    if max_ambiguous is not None:
+        assert amb <= max_ambiguous * (n_v + n_s + amb), amb
+    return types.SimpleNamespace(words=words, own=own, v_class=v_class, s_class=s_class, amb=amb, n=n)
 
 
 # ------------------------------------------------------------------------------------------------ the context

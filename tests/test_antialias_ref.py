@@ -6,7 +6,7 @@ import pytest
 
 import antialiasref as ref
 import visref
-from support import frame, soup
+from support import frame, frame_positions, soup
 
 TRI, BG = np.float32(8.0), np.float32(2.0)  # (dyadic: every blend below is exact)
 
@@ -175,7 +175,7 @@ def test_gradients_against_central_differences(tmp_path, orc):
     W, H, n = 48, 40, 30
     f = frame(soup(FD_SEED, n, W, H, ref.ZS), W, H)
     v = visref.Reference(tmp_path, f).expected(orc)[0]
-    pos = ref.frame_pos(f)
+    pos = frame_positions(f)
     rng = np.random.default_rng(5)
     c = rng.normal(0, 1, (3, H, W)).astype(np.float32)
     g = rng.normal(0, 1, (3, H, W)).astype(np.float32)
@@ -229,7 +229,7 @@ def test_counts_on_the_gpu_tests_scenes(tmp_path, orc, w, h, n, backdrop):
     t = ref.scene_tris(w, h, n, backdrop)
     f = frame(t, w, h)
     v = visref.Reference(tmp_path, f).expected(orc)[0]
-    k = ref.counters(tmp_path, ref.frame_pos(f), len(t), v)
+    k = ref.counters(tmp_path, frame_positions(f), len(t), v)
     print(w, h, backdrop, k)
     for name in ref.relied_on(w, h, backdrop):
         assert k[name] > 0, (name, k)

@@ -8,11 +8,9 @@ import numpy as np
 import pytest
 
 import gbufref
-import visref
 from srz import abi
-from support import bits, frame, hostile_shading_frame, hostile_textures, lit, padded_rows, soup, stack
+from support import MAX_AMBIGUOUS, bits, frame, hostile_shading_frame, hostile_textures, lit, padded_rows, soup, stack, visibility_of
 
-MIN_CLASS, MAX_AMBIGUOUS = 200, 0.005
 ZS = np.float32([1, 2, 3, 4])
 # the session's oracle is shared with modules that rely on slot 63 being empty (tests/test_oracle_kat.py): its texture goes to slot 50
 REMAP = {63: 50}
@@ -31,19 +29,6 @@ NORMAL_FRAMES = {"soup 0": lambda: frame(soup(0, 90, 64, 64, ZS), 64, 64), "soup
                  "wide and thin": lambda: hostile_shading_frame(0, "uv-edge", tame=True)}
 
 
-def visibility_of(tmp_path, orc, f):
-    """(words [4, H, W] of the frame's visibility buffer, V mask, S mask) with the conditions that keep a comparison from passing
-    vacuously asserted: >= MIN_CLASS owned pixels of each class, ambiguous pixels (left out: id 0) <= MAX_AMBIGUOUS of the owned"""
-    words, _, amb, _, own = visref.Reference(tmp_path, f).expected(orc)
-    s_class = own & ((words[1] >> 31) != 0)
-    v_class = own & ~s_class
-    n_v, n_s = int(v_class.sum()), int(s_class.sum())
-    print(f"owned V {n_v} S {n_s} ambiguous {amb}")
-    assert n_v >= MIN_CLASS and n_s >= MIN_CLASS, (n_v, n_s)
-    assert amb <= MAX_AMBIGUOUS * (n_v + n_s + amb), amb
-    return words, v_class, s_class
-
-
 def same_colour(got, ref, mask, what):
     for c in range(3):
         bad = mask & (bits(got[c]) != bits(np.ascontiguousarray(ref[c], np.float32)))
@@ -54,7 +39,8 @@ def same_colour(got, ref, mask, what):
 @pytest.mark.parametrize("name", sorted(NORMAL_FRAMES))
 def test_normals_are_what_the_normal_shader_sees(tmp_path, orc, name):
     f = NORMAL_FRAMES[name]()
-    words, v_class, s_class = visibility_of(tmp_path, orc, f)
+    v = visibility_of(tmp_path, orc, f, max_ambiguous=MAX_AMBIGUOUS)
+    words, v_class, s_class = v.words, v.v_class, v.s_class
     nf = lit(f, batches=[(abi.SHADER_NORMAL, -1, t) for t in f.tris])  # the frame's own normals, NORMAL-shaded
     rc, ref, _ = orc.draw(nf, want_stats=False)
     assert rc == 0
@@ -79,7 +65,8 @@ def test_albedo_and_uv_are_what_the_texture_shader_sees(tmp_path, orc, seed):
     uv = np.concatenate([t["uv"].ravel() for t in f.tris])
     assert uv.min() < -0.03 and uv.max() > 1.03  # (drawn from [-0.05, 1.05]: both borders are crossed)
     assert {int(f._batches[b].tex_id) for b in range(len(f.tris))} == set(tex) and len(tex) == len(hostile_textures())
-    words, v_class, s_class = visibility_of(tmp_path, orc, f)
+    v = visibility_of(tmp_path, orc, f, max_ambiguous=MAX_AMBIGUOUS)
+    words, v_class, s_class = v.words, v.v_class, v.s_class
     rc, ref, _ = orc.draw(f, want_stats=False)
     assert rc == 0
     planes = gbufref.expected(tmp_path, f, tex, words).view(np.float32)

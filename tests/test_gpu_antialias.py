@@ -11,24 +11,12 @@ import torch
 import antialiasref as ref
 import posgradref
 from srz import abi
-from support import ctx, frame, stream, words  # noqa: F401
+from support import ctx, filled, frame, padded_positions, stream, visibility, words  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F = abi.FUSED_CLEAR
-SENTINEL = 0xdeadbeef
 OUTPUTS = ((True, False), (False, True), (True, True))  # (gin, gpos)
-
-
-def visibility(fs, flags=F):
-    vis = torch.zeros(fs.out_shape, dtype=torch.float32, device="cuda")
-    fs.render_visibility(vis.data_ptr(), fs.out_bytes, flags, stream())
-    torch.cuda.synchronize()
-    return vis
-
-
-def filled(shape, fill=SENTINEL):
-    return torch.full(shape, fill - (1 << 32) if fill >= 1 << 31 else fill, dtype=torch.int32, device="cuda")
 
 
 def dev(a):
@@ -63,17 +51,9 @@ def same(got, want, what):
     assert not bad.any(), f"{what}: {int(bad.sum())} words differ, first {np.argwhere(bad)[:4].tolist()}: got {g[bad][:4]} want {w[bad][:4]}"
 
 
-def positions(frames, T):
-    """[n, T, 9] float32: every frame's dense position stream, zeros behind its last triangle"""
-    pos = np.zeros((len(frames), T, 9), np.float32)
-    for i, f in enumerate(frames):
-        pos[i, :f.n_tris] = ref.frame_pos(f)
-    return pos
-
-
 def expect(tmp_path, frames, v, c, g, T, pos=None):
     """(out [n, C, rows, W], gin likewise, an antialiasref.Grad per frame)"""
-    pos = positions(frames, T) if pos is None else pos
+    pos = padded_positions(frames, T) if pos is None else pos
     accs, out, gin = [ref.Grad(T) for _ in frames], [], []
     for i, f in enumerate(frames):
         out.append(ref.forward(tmp_path, pos[i], f.n_tris, v[i], c[i]))
@@ -382,7 +362,7 @@ def test_autograd(ctx, tmp_path, monkeypatch):
     calls = []
     real = srz.FrameSet.antialias_grad
     monkeypatch.setattr(srz.FrameSet, "antialias_grad", lambda self, *a, **k: (calls.append("antialias_grad"), real(self, *a, **k))[1])
-    pos = torch.as_tensor(positions(frames, T).reshape(2, T, 3, 3)).cuda().requires_grad_(True)
+    pos = torch.as_tensor(padded_positions(frames, T).reshape(2, T, 3, 3)).cuda().requires_grad_(True)
     attr = torch.as_tensor(np.random.default_rng(9).normal(0, 1, (T, 3, 3)).astype(np.float32)).cuda().requires_grad_(True)
     color = interpolate_geo(fs, vis, attr, pos)
     out = antialias(fs, vis, color, pos)
@@ -401,7 +381,7 @@ def test_autograd(ctx, tmp_path, monkeypatch):
     iacc = [posgradref.Grad(T) for _ in frames]
     hb = gbary.cpu().numpy()
     for i, f in enumerate(frames):
-        posgradref.grad(tmp_path, positions(frames, T)[i], f.n_tris, v[i], hb[i], None, iacc[i], False)
+        posgradref.grad(tmp_path, padded_positions(frames, T)[i], f.n_tris, v[i], hb[i], None, iacc[i], False)
     total = np.stack([a.gpos for a in accs]) + np.stack([a.gpos for a in iacc])
     bound = np.stack([a.bound() for a in accs]) + np.stack([a.bound() for a in iacc])
     assert (np.abs(gint.cpu().numpy().astype(np.float64) - np.stack([a.gpos for a in iacc])) <= np.stack([a.bound() for a in iacc])).all()

@@ -8,14 +8,13 @@ import torch
 import gbufref
 import scenes
 from srz import abi, parallel
-from support import (MIX_ALL, ccw, ctx, frame, hostile_shading_frame, hostile_textures, lit, register_hostile_textures, soup, stack, stream,  # noqa: F401
-                     words)
+from support import (MIX_ALL, SENTINEL, ccw, ctx, frame, hostile_shading_frame, hostile_textures, lit, register_hostile_textures, soup,  # noqa: F401
+                     stack, stream, visibility, words)
 
 pytestmark = pytest.mark.gpu
 
 ALL, F = abi.GB_ALL, abi.FUSED_CLEAR
 ZS = np.float32([1, 2, 3, 4])
-SENTINEL = 0xdeadbeef
 # a triangle behind everything that covers any frame here (so that the smallest ones have an owner), with attributes of its own
 BACKDROP = ccw((-8, -8), (400, -8), (-8, 400), z=80.0, nrm=((0.2, 0.1, 1.0), (-0.3, 0.2, 0.9), (0.1, -0.4, 0.8)), uv=((0.1, 0.2), (0.9, 0.3), (0.4, 0.8)))
 
@@ -27,13 +26,6 @@ def tex(ctx, orc):
     t = {slot: a for slot, (a, _) in hostile_textures().items()}
     t[scenes.TEX_SPOT] = np.ascontiguousarray(scenes.spot_texture(), np.uint8)
     return t
-
-
-def visibility(fs, flags=F):
-    vis = torch.zeros(fs.out_shape, dtype=torch.float32, device="cuda")
-    fs.render_visibility(vis.data_ptr(), fs.out_bytes, flags, stream())
-    torch.cuda.synchronize()
-    return vis
 
 
 def gbuffer(fs, vis, what=ALL, flags=F, fill=0):

@@ -10,23 +10,15 @@ import torch
 
 import interpref
 from srz import abi, parallel
-from support import ccw, ctx, frame, hostile_shading_frame, soup, stream, words  # noqa: F401
+from support import SENTINEL, ccw, ctx, frame, hostile_shading_frame, soup, stream, visibility, words  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F = abi.FUSED_CLEAR
 ZS = np.float32([1, 2, 3, 4])
-SENTINEL = 0xdeadbeef
 BACKDROP = ccw((-8, -8), (400, -8), (-8, 400), z=80.0)
 SIZES = [(64, 64, 90), (100, 70, 120), (50, 37, 40), (33, 1, 6), (1, 1, 3)]
 CHANNELS = (1, 3, 4, 5, 17, 64)
-
-
-def visibility(fs, flags=F):
-    vis = torch.zeros(fs.out_shape, dtype=torch.float32, device="cuda")
-    fs.render_visibility(vis.data_ptr(), fs.out_bytes, flags, stream())
-    torch.cuda.synchronize()
-    return vis
 
 
 def dims(fs, attr):

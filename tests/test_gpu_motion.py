@@ -7,23 +7,15 @@ import torch
 
 import motionref
 from srz import abi, parallel
-from support import ccw, ctx, frame, hostile_shading_frame, soup, stream, words  # noqa: F401
+from support import SENTINEL, ccw, ctx, frame, frame_positions, hostile_shading_frame, soup, stream, visibility, words  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ALL, F = abi.MV_ALL, abi.FUSED_CLEAR
 ZS = np.float32([1, 2, 3, 4])
-SENTINEL = 0xdeadbeef
 INF = motionref.INF_WORD
 # a triangle behind everything that covers any frame here (so that the smallest ones have an owner)
 BACKDROP = ccw((-8, -8), (400, -8), (-8, 400), z=80.0)
-
-
-def visibility(fs, flags=F):
-    vis = torch.zeros(fs.out_shape, dtype=torch.float32, device="cuda")
-    fs.render_visibility(vis.data_ptr(), fs.out_bytes, flags, stream())
-    torch.cuda.synchronize()
-    return vis
 
 
 def motion(fs, vis, what=ALL, delta=1, flags=F, fill=0):
@@ -51,7 +43,7 @@ def expect(tmp_path, frames, vis, what=ALL, delta=1, fused=True, fill=0):
         g = i + delta
         if 0 <= g < len(frames):
             pre = np.full((5,) + v.shape[2:], fill, np.uint32)
-            e = motionref.expected(tmp_path, motionref.positions(frames[g]), v[i], v[g], fused, pre)
+            e = motionref.expected(tmp_path, frame_positions(frames[g]), v[i], v[g], fused, pre)
         else:
             e = motionref.nobody(v.shape[2:], fused, fill)
         out.append(e[motionref.planes_of(what)])
@@ -174,7 +166,7 @@ def test_hostile_targets(ctx, tmp_path):
     """tests/test_motion_ref.py's hostile target positions (NaN, +-inf, +-1e30, the borders of the nearest-sample range): the planes
     are the reference's bit for bit, and nothing outside the image was read as a target"""
     f = frame(soup(4, 300, 70, 50, ZS), 70, 50)
-    frames = [f, with_positions(f, motionref.hostile_target_positions(motionref.positions(f), 70, 50))]
+    frames = [f, with_positions(f, motionref.hostile_target_positions(frame_positions(f), 70, 50))]
     fs = ctx.frameset(frames)
     vis = visibility(fs)
     got = motion(fs, vis, ALL, 1)

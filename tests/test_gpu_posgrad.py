@@ -11,28 +11,16 @@ import torch
 import interpref
 import posgradref
 from srz import abi, parallel
-from support import ccw, ctx, frame, soup, stream, words  # noqa: F401
+from support import SENTINEL, ccw, ctx, filled, frame, padded_positions, soup, stream, visibility, words  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F = abi.FUSED_CLEAR
 ZS = np.float32([1, 2, 3, 4])
-SENTINEL = 0xdeadbeef
 BACKDROP = ccw((-8, -8), (400, -8), (-8, 400), z=(80.0, 60.0, 70.0))
 SIZES = [(64, 64, 90), (100, 70, 120), (50, 37, 40), (33, 1, 6), (1, 1, 3)]
 INPUTS = ((True, False), (False, True), (True, True))  # (gbary, gz)
 OUTPUTS = ((True, False), (False, True), (True, True))  # (gpos, gpix)
-
-
-def visibility(fs, flags=F):
-    vis = torch.zeros(fs.out_shape, dtype=torch.float32, device="cuda")
-    fs.render_visibility(vis.data_ptr(), fs.out_bytes, flags, stream())
-    torch.cuda.synchronize()
-    return vis
-
-
-def filled(shape, fill):
-    return torch.full(shape, fill - (1 << 32) if fill >= 1 << 31 else fill, dtype=torch.int32, device="cuda")
 
 
 def call(fs, vis, gbary, gz, T, want_pos=True, want_pix=True, flags=F, fill=0, into=None):
@@ -57,17 +45,9 @@ def same(got, want, what):
     assert not bad.any(), f"{what}: {int(bad.sum())} words differ, first {np.argwhere(bad)[:4].tolist()}: got {g[bad][:4]} want {w[bad][:4]}"
 
 
-def positions(frames, T):
-    """[n, T, 9] float32: every frame's dense position stream, zeros behind its last triangle"""
-    pos = np.zeros((len(frames), T, 9), np.float32)
-    for i, f in enumerate(frames):
-        pos[i, :f.n_tris] = posgradref.frame_pos(f)
-    return pos
-
-
 def expect(tmp_path, frames, v, gbary, gz, T, fused=True, fill=0):
     """(a posgradref.Grad per frame, gpix [n, 2, rows, W] float32)"""
-    pos = positions(frames, T)
+    pos = padded_positions(frames, T)
     accs, gx = [posgradref.Grad(T) for _ in frames], []
     for i, f in enumerate(frames):
         pre = np.full((2,) + v.shape[2:], fill, np.uint32)
@@ -387,7 +367,7 @@ def test_cross_checks_against_the_attribute_gradient(ctx, tmp_path):
     diff = np.abs(gp.cpu().numpy()[..., 2].astype(np.float64) - ga.cpu().numpy()[..., 0])
     assert (diff <= zb + ib).all() and (ga != 0).sum() > 100
     # ---- positions as three attribute channels, gout = (0, 0, gz): interpolate_bary_grad's planes are gz's share of dalpha, dbeta
-    pos = torch.as_tensor(positions(frames, T).reshape(2, T, 3, 3)).cuda()
+    pos = torch.as_tensor(padded_positions(frames, T).reshape(2, T, 3, 3)).cuda()
     _, gz = rand_grads(3, fs)
     gout = torch.zeros(fs.interpolate_shape(3), dtype=torch.float32, device="cuda")
     gout[:, 2] = torch.as_tensor(gz[:, 0]).cuda()
@@ -415,7 +395,7 @@ def test_autograd(ctx, tmp_path, monkeypatch):
     for name in ("interpolate_grad", "position_grad"):
         real = getattr(srz.FrameSet, name)
         monkeypatch.setattr(srz.FrameSet, name, lambda self, *a, _real=real, _name=name, **k: (calls.append(_name), _real(self, *a, **k))[1])
-    pos = torch.as_tensor(positions(frames, T).reshape(2, T, 3, 3)).cuda().requires_grad_(True)
+    pos = torch.as_tensor(padded_positions(frames, T).reshape(2, T, 3, 3)).cuda().requires_grad_(True)
     attr = torch.as_tensor(np.random.default_rng(9).normal(0, 3, (T, 3, 6)).astype(np.float32)).cuda().requires_grad_(True)
     # ---- interpolate_geo: one interpolate_grad call for both gradients, one position_grad call
     out = interpolate_geo(fs, vis, attr, pos)

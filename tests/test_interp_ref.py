@@ -6,29 +6,18 @@ import pytest
 
 import gbufref
 import interpref
-import visref
-from support import bits, frame, hostile_shading_frame, soup
+from support import bits, frame, hostile_shading_frame, soup, visibility_of
 
-MIN_CLASS = 200
 ZS = np.float32([1, 2, 3, 4])
 FRAMES = {"soup 0": lambda: frame(soup(0, 90, 64, 64, ZS), 64, 64), "soup 3 (quarter-pixel vertices)": lambda: frame(soup(3, 90, 64, 64, ZS), 64, 64),
           "wide and thin": lambda: hostile_shading_frame(0, "uv-edge", tame=True)}
 
 
-def visibility_of(tmp_path, orc, f):
-    """(words [4, H, W], owned mask, S mask) of the oracle's visibility buffer of f; both classes occur"""
-    words = visref.Reference(tmp_path, f).expected(orc)[0]
-    n = sum(len(t) for t in f.tris)
-    own = ((words[1] & 0x7fffffff) - np.uint32(1)) < n
-    s_class = own & ((words[1] >> 31) != 0)
-    assert int((own & ~s_class).sum()) >= MIN_CLASS and int(s_class.sum()) >= MIN_CLASS, (int(own.sum()), int(s_class.sum()))
-    return words, own, s_class, n
-
-
 @pytest.mark.parametrize("name", sorted(FRAMES))
 def test_uv_as_attributes_is_the_gbuffers_uv(tmp_path, orc, name):
     f = FRAMES[name]()
-    words, own, _, n = visibility_of(tmp_path, orc, f)
+    v = visibility_of(tmp_path, orc, f)
+    words, own, n = v.words, v.own, v.n
     got = interpref.forward(tmp_path, interpref.frame_attr(f, "uv"), n, words)
     want = gbufref.expected(tmp_path, f, {}, words)[3:5]
     assert got.shape == (2, f.height, f.width) and np.array_equal(bits(got), want)
@@ -39,7 +28,8 @@ def test_uv_as_attributes_is_the_gbuffers_uv(tmp_path, orc, name):
 def test_positions_as_attributes_give_the_buffers_depth(tmp_path, orc, name):
     """motion's delta-0 rule: z interpolates like every attribute, so channel 2 of the positions is plane 0 at every owned pixel"""
     f = FRAMES[name]()
-    words, own, _, n = visibility_of(tmp_path, orc, f)
+    v = visibility_of(tmp_path, orc, f)
+    words, own, n = v.words, v.own, v.n
     pre = np.full((3, f.height, f.width), 0xdeadbeef, np.uint32)
     got = bits(interpref.forward(tmp_path, interpref.frame_attr(f, "pos"), n, words, fused=False, prefill=pre))
     assert np.array_equal(got[2][own], words[0][own])
@@ -49,7 +39,8 @@ def test_positions_as_attributes_give_the_buffers_depth(tmp_path, orc, name):
 @pytest.mark.parametrize("name", sorted(FRAMES))
 def test_backward_against_numpy_in_float64(tmp_path, orc, name):
     f = FRAMES[name]()
-    words, own, s_class, n = visibility_of(tmp_path, orc, f)
+    v = visibility_of(tmp_path, orc, f)
+    words, own, s_class, n = v.words, v.own, v.s_class, v.n
     rng = np.random.default_rng(7)
     H, W = f.height, f.width
     # ---- gbary at one channel: RN(g * RN(a - c)), the product exact in float64 (24 x 24 bits)

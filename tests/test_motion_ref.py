@@ -7,25 +7,13 @@ import numpy as np
 import pytest
 
 import motionref
-import visref
 from srz import abi
-from support import frame, hostile_shading_frame, soup, stack
+from support import frame, frame_positions, hostile_shading_frame, soup, stack, visibility_of
 
 ZS = np.float32([1, 2, 3, 4])
-MIN_CLASS = 200
 INF = motionref.INF_WORD
 FRAMES = {"soup 0": lambda: frame(soup(0, 90, 64, 64, ZS), 64, 64), "stack 200": lambda: stack(200),
           "wide and thin": lambda: hostile_shading_frame(0, "uv-edge", tame=True)}
-
-
-def visibility_of(tmp_path, orc, f, both_classes=True):
-    """(words [4, H, W] of the frame's visibility buffer, owned mask, S mask); enough owned pixels of each class asserted"""
-    words, _, amb, _, own = visref.Reference(tmp_path, f).expected(orc)
-    s_class = own & ((words[1] >> 31) != 0)
-    n_v, n_s = int((own & ~s_class).sum()), int(s_class.sum())
-    print(f"owned V {n_v} S {n_s} ambiguous {amb}")
-    assert n_v >= MIN_CLASS and (n_s >= MIN_CLASS or not both_classes), (n_v, n_s)
-    return words, own, s_class, amb
 
 
 def grid(shape):
@@ -41,8 +29,9 @@ def f32(words):
 def test_anchor_the_frame_is_its_own_target(tmp_path, orc, name):
     """delta == 0: DEPTH is the oracle's z plane bit for bit, TARGET the pixel's own id and z, at every owned pixel"""
     f = FRAMES[name]()
-    words, own, _, _ = visibility_of(tmp_path, orc, f)
-    out = motionref.expected(tmp_path, motionref.positions(f), words, words)
+    v = visibility_of(tmp_path, orc, f)
+    words, own = v.words, v.own
+    out = motionref.expected(tmp_path, frame_positions(f), words, words)
     assert np.array_equal(out[2][own], words[0][own]), "z' differs from the oracle's z"
     dx, dy = f32(out[0]), f32(out[1])
     worst = max(float(np.abs(dx[own]).max()), float(np.abs(dy[own]).max()))
@@ -59,9 +48,10 @@ def test_arithmetic_against_float64(tmp_path, orc, name):
     magnitude <= S.  S: the three products' roundings add up to 2^-24 * S, the first sum's is <= 2^-24 * (|alpha a| + |beta b|), the
     second's <= 2^-24 * S — the same 3 * 2^-24 * S.  dx, dy are the float32 differences x' - x, y' - y bit for bit."""
     f = FRAMES[name]()
-    words, own, s_class, _ = visibility_of(tmp_path, orc, f)
+    v = visibility_of(tmp_path, orc, f)
+    words, own, s_class = v.words, v.own, v.s_class
     rng = np.random.default_rng(7)
-    pos = motionref.positions(f).reshape(-1, 3, 3)
+    pos = frame_positions(f).reshape(-1, 3, 3)
     moved = (pos + rng.normal(0, 6, pos.shape) + rng.normal(0, 10, (1, 1, 3))).astype(np.float32).reshape(-1, 9)
     out = motionref.expected(tmp_path, moved, words, words)
     al, be = f32(words[2]), f32(words[3])
@@ -89,10 +79,10 @@ def test_translation_lands_on_the_moved_pixel(tmp_path, orc):
     pixel's own id word, class bit included, tz is the moved frame's z there, and z' = tz bit for bit"""
     k, m, _ = motionref.TRANSLATION
     f0, f1 = motionref.translation_frames()
-    w0, own0, _, amb0 = visibility_of(tmp_path, orc, f0)
-    w1, own1, _, amb1 = visibility_of(tmp_path, orc, f1)
+    v0, v1 = visibility_of(tmp_path, orc, f0), visibility_of(tmp_path, orc, f1)
+    w0, own0, amb0, w1, own1, amb1 = v0.words, v0.own, v0.amb, v1.words, v1.own, v1.amb
     assert amb0 == 0 and amb1 == 0  # (the oracle's colours decode to one owner at every pixel of both frames: no pixel is left out)
-    out = motionref.expected(tmp_path, motionref.positions(f1), w0, w1)
+    out = motionref.expected(tmp_path, frame_positions(f1), w0, w1)
     dx, dy = f32(out[0]), f32(out[1])
     assert (np.abs(dx[own0] - k) < 0.5).all() and (np.abs(dy[own0] - m) < 0.5).all()  # (4.5 and 5.5 are floats: rint(x') == x + k)
     ys, xs = np.nonzero(own0)
@@ -104,8 +94,9 @@ def test_translation_lands_on_the_moved_pixel(tmp_path, orc):
 
 def hostile_case(tmp_path, orc):
     f = frame(soup(4, 300, 70, 50, ZS), 70, 50)
-    words, own, s_class, _ = visibility_of(tmp_path, orc, f)
-    pos = motionref.hostile_target_positions(motionref.positions(f), 70, 50)
+    v = visibility_of(tmp_path, orc, f)
+    words, own, s_class = v.words, v.own, v.s_class
+    pos = motionref.hostile_target_positions(frame_positions(f), 70, 50)
     return f, words, own, s_class, pos
 
 
@@ -148,8 +139,8 @@ def test_nobody_and_out_of_range_ids(tmp_path):
     words[1, 0] = [0, 0x80000000, 6, 0x7fffffff, 0xffffffff, 1]
     words[2:, 0] = np.float32(0.25).view(np.uint32)
     pre = np.full((5, 1, 6), 0xdeadbeef, np.uint32)
-    fused = motionref.expected(tmp_path, motionref.positions(f), words, words, fused=True, prefill=pre)
-    kept = motionref.expected(tmp_path, motionref.positions(f), words, words, fused=False, prefill=pre)
+    fused = motionref.expected(tmp_path, frame_positions(f), words, words, fused=True, prefill=pre)
+    kept = motionref.expected(tmp_path, frame_positions(f), words, words, fused=False, prefill=pre)
     assert (fused[:, 0, :5] == 0).all() and (kept[:, 0, :5] == 0xdeadbeef).all()
     assert np.array_equal(fused[:, 0, 5], kept[:, 0, 5]) and not (fused[:3, 0, 5] == 0xdeadbeef).any()
     assert (motionref.nobody((1, 6)) == 0).all() and (motionref.nobody((1, 6), False, 7) == 7).all()

@@ -6,34 +6,22 @@ overlap differ by >= SEP levels of 255 in some channel); the oracle renders that
 contains it in its box and matches its colour within TOL.  Culling reads positions only, so visibility is that of the original
 frame; alpha, beta and the per-class z of that owner come from vis_ref.c."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from srz import abi
+from support import frame_positions, ref_lib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SEP, TOL, N_CAND = 4.0, 1.5, 16384
-_lib = None
+vp = C.c_void_p
+SIGNATURES = {"vr_boxes": (None, [vp, C.c_int, C.c_int, C.c_int, vp]),
+              "vr_assign": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_double, vp]),
+              "vr_decode": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp, vp, vp, vp, vp]),
+              "vr_bary": (None, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp])}
 
 
 def lib(tmpdir):
-    global _lib
-    if _lib is None:
-        so = os.path.join(str(tmpdir), "libvis_ref.so")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-o", so,
-                               os.path.join(HERE, "vis_ref.c"), "-lm"])
-        L = C.CDLL(so)
-        vp = C.c_void_p
-        L.vr_boxes.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
-        L.vr_assign.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_double, vp]
-        L.vr_decode.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp, vp, vp, vp, vp]
-        L.vr_bary.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-        L.vr_boxes.restype = None
-        L.vr_bary.restype = None
-        _lib = L
-    return _lib
+    return ref_lib("vis_ref", tmpdir, SIGNATURES)
 
 
 def _p(a):
@@ -60,8 +48,7 @@ class Reference:
         L = lib(tmpdir)
         self.W, self.H = frame.width, frame.height
         self.sizes = [len(t) for t in frame.tris]
-        self.pos = np.ascontiguousarray(np.concatenate([t["pos"] for t in frame.tris]).reshape(-1, 9), np.float32) \
-            if sum(self.sizes) else np.zeros((0, 9), np.float32)
+        self.pos = frame_positions(frame)
         n = len(self.pos)
         self.box = np.zeros((max(n, 1), 4), np.int32)
         L.vr_boxes(_p(self.pos), n, self.W, self.H, _p(self.box))

@@ -27,6 +27,7 @@ import antialiasref  # noqa: E402
 import srz  # noqa: E402
 from srz import abi  # noqa: E402
 from srz.visibility import decode  # noqa: E402
+from support import frame_positions  # noqa: E402
 from vis_probe import CONFIGS, frames_of, pct  # noqa: E402
 
 COPY_RATE = 6.29e12  # bytes / s: device-to-device copies
@@ -59,7 +60,7 @@ def main():
         tri = decode(vis).tri
         pixels = n * fs.local_rows * fs.width
         differ = int((tri[:, :, 1:] != tri[:, :, :-1]).sum()) + int((tri[:, 1:] != tri[:, :-1]).sum())
-        k0 = antialiasref.counters(tmp, antialiasref.frame_pos(frames[0]), frames[0].n_tris, vis[0].cpu().numpy().view(np.uint32))
+        k0 = antialiasref.counters(tmp, frame_positions(frames[0]), frames[0].n_tris, vis[0].cpu().numpy().view(np.uint32))
         nb = fs.interpolate_bytes(N_CH)
         cin, gout = torch.randn(fs.interpolate_shape(N_CH), device="cuda"), torch.randn(fs.interpolate_shape(N_CH), device="cuda")
         out = torch.empty_like(cin)
