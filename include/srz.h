@@ -55,6 +55,8 @@ extern "C" {
  *      srz_frameset_interpolate_bytes / srz_frameset_interpolate_grad, SRZ_ATTR_MAX_CH
  *      (additive, same version) position gradients of a visibility buffer srz_frameset_position_grad
  *      (additive, same version) silhouette antialiasing of a visibility buffer srz_frameset_antialias / srz_frameset_antialias_grad
+ *      (additive, same version) caller textures over a visibility buffer, with gradients srz_frameset_texture /
+ *      srz_frameset_texture_grad, SRZ_TEX_CLAMP, SRZ_TEX_WRAP, SRZ_TEX_MAX_SIZE
  */
 #define SRZ_ABI_VERSION 7
 
@@ -495,6 +497,59 @@ int srz_frameset_antialias(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, co
                            uint32_t flags, void *stream);
 int srz_frameset_antialias_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_in, const void *d_gout, uint32_t n_ch,
                                 void *d_gin, uint32_t pos_tris, float *d_gpos, uint32_t flags, void *stream);
+/* CALLER TEXTURES over a visibility buffer, and their gradients: a float32 texture of the caller's own sampled BILINEARLY at the uv
+ * planes srz_frameset_interpolate wrote for a two-channel attribute (or srz_frameset_gbuffer(SRZ_GB_UV)), and the backward of that
+ * lookup, to the texels and to u, v: the texture lookup of a differentiable renderer (a nearest-texel fetch, which is what the
+ * built-in shaders and SRZ_GB_ALBEDO do with an uploaded 8-bit texture, has no gradient in uv).
+ * d_vis: a visibility buffer of THIS set on this ctx's shard.  d_uv: [frame][2][local_rows][width] float32 (u, then v),
+ * srz_frameset_interpolate_bytes(2) bytes.  d_tex and d_gtex: [tex_frames][tex_h][tex_w][n_ch] float32, channels last, 4-byte aligned;
+ * tex_frames is 1 (every frame samples the same texture) or the set's frame count; 1 <= tex_w, tex_h <= SRZ_TEX_MAX_SIZE;
+ * 1 <= n_ch <= SRZ_ATTR_MAX_CH.  d_out and d_gout: [frame][n_ch][local_rows][width] float32, srz_frameset_interpolate_bytes(n_ch)
+ * bytes.  d_guv: d_uv's shape.  Band sharding (each rank adds the partial sums of its own bands), local_rows, stream semantics,
+ * asynchrony, the 16-byte alignment of the visibility buffer and every plane buffer (d_uv, d_out, d_gout, d_guv), and owner and nobody
+ * ((id & 0x7fffffff) - 1 < the frame's triangle count; the class bit plays no part) as srz_frameset_interpolate.  The passes read no
+ * position, record or uploaded texture: a sceneset does not run its vertex stage, nothing else is launched.  A nobody pixel's words
+ * of d_out and d_guv are 0 with SRZ_FUSED_CLEAR (frame flags | flags) and left untouched without it; the words of d_uv and d_gout at
+ * nobody's pixels never reach a result: they may hold anything.
+ * THE RULE, all of it float32, nothing fused except where fmaf is written, always the exact arithmetic (SRZ_OPT_APPROX_SHADE has no
+ * effect).  Per owned pixel, per axis — shown for x with u and W = tex_w; y with v and H = tex_h likewise:
+ *   unsampled: u or v not finite (!(fabsf(u) < INFINITY)) -> every channel of out is 0 (written: the pixel has an owner),
+ *              guv = (0, 0), no add
+ *   WRAP:   u = u - floorf(u)
+ *   fx = u * (float)W - 0.5f                  (texel i's centre is (i + 0.5) / W: the texel grid of the built-in shaders' fetch, no flip in v)
+ *   CLAMP:  in_x = fx > 0.0f && fx < (float)(W - 1);  fx = fminf(fmaxf(fx, 0.0f), (float)(W - 1))      WRAP: in_x = true
+ *   x0f = floorf(fx);  tx = fx - x0f;  x0 = (int)x0f;  x1 = x0 + 1
+ *   CLAMP:  x1 = min(x1, W - 1)               WRAP: if (x0 < 0) x0 += W;  if (x1 >= W) x1 -= W
+ * FORWARD, deterministic, bit for bit: per channel, with t_rc = tex[y_r][x_c],
+ *   top = fmaf(tx, t01 - t00, t00);  bot = fmaf(tx, t11 - t10, t10);  out = fmaf(ty, bot - top, top)
+ * BACKWARD: d_gout, the same d_uv and d_vis; at least one of d_gtex and d_guv is non-null.
+ *   d_gtex (d_tex itself may be null when only d_gtex is asked for): w00 = (1.0f - tx) * (1.0f - ty), w01 = tx * (1.0f - ty),
+ *   w10 = (1.0f - tx) * ty, w11 = tx * ty; for every sampled pixel, corner and channel the float32 product w_rc * gout[ch] is ADDED
+ *   to gtex[ft][y_r][x_c][ch] (ft = 0 when tex_frames == 1); two corners that coincide (a clamped border, a one-texel axis) both
+ *   add.  The caller zeroes the buffer, or accumulates over several calls.  THE ORDER OF THE ADDS IS UNSPECIFIED, each add rounds, so
+ *   d_gtex is NOT BIT-REPRODUCIBLE between launches, like d_gattr: with n contributing adds an element lies within
+ *   n 2^-24 / (1 - n 2^-24) * sum |term| of the exact sum of the float32 terms; an element with one contributing add is exact.  The
+ *   adds are hardware float atomics: d_gtex must be ordinary (coarse-grained) device memory.
+ *   d_guv, needs d_tex, deterministic, bit for bit: au = av = 0; for ch ascending:
+ *     au = fmaf(gout[ch], fmaf(ty, (t11 - t10) - (t01 - t00), t01 - t00), au);  av = fmaf(gout[ch], bot - top, av)
+ *   du = in_x ? au * (float)W : 0.0f;  dv = in_y ? av * (float)H : 0.0f.  It has the layout of srz_frameset_interpolate_grad's
+ *   d_gout at n_ch = 2: the chain texture_grad -> interpolate_grad -> position_grad runs on the device.
+ * Every conversion to an integer follows the float clamp (CLAMP) or the fraction (WRAP): no value of uv makes a pass read or write
+ * outside its buffers.  Non-finite texels and gradients propagate as IEEE has them.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set, d_vis, d_uv, d_tex (forward; backward with d_guv),
+ * d_out, d_gout, or both of d_gtex and d_guv; tex_w or tex_h 0 or above SRZ_TEX_MAX_SIZE; n_ch == 0 or above SRZ_ATTR_MAX_CH;
+ * tex_frames not 1 or the frame count; a mode other than SRZ_TEX_CLAMP and SRZ_TEX_WRAP; a short out_bytes; a misaligned pointer; any
+ * bit of `flags` but SRZ_FUSED_CLEAR; an output that overlaps an input (d_out with d_vis, d_uv or d_tex; d_gtex or d_guv with d_vis,
+ * d_uv, d_gout or d_tex) or the other output. */
+#define SRZ_TEX_CLAMP 0u
+#define SRZ_TEX_WRAP 1u
+#define SRZ_TEX_MAX_SIZE 16384u
+int srz_frameset_texture(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const float *d_tex, uint32_t tex_w,
+                         uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t mode, void *d_out, size_t out_bytes, uint32_t flags,
+                         void *stream);
+int srz_frameset_texture_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const void *d_gout, const float *d_tex,
+                              uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t mode, float *d_gtex, void *d_guv,
+                              uint32_t flags, void *stream);
 /* New SHADING DATA for a set made by srz_frameset_create, its triangles untouched (batches[b].tris is ignored and may be NULL): each
  * frame's eye, ka, ks, p, kh, kn, lights and flags, each batch's shader and tex_id.  The structure must be the set's — frame count, size,
  * light counts, batch counts, n_tris per batch — else SRZ_E_INVALID and the set is unchanged; a sceneset is SRZ_E_INVALID (its shading

@@ -743,7 +743,7 @@ int stats_pass(srz_ctx *ctx, srz_frameset *fs, const float *d_start, uint32_t fl
 
 } // namespace
 
-// The passes over a visibility buffer (srz_frameset_shade_visibility .. srz_frameset_antialias_grad): what their entry points share.
+// The passes over a visibility buffer (srz_frameset_shade_visibility .. srz_frameset_texture_grad): what their entry points share.
 // Each entry point is its own argument rules, these checks, its own Args fields, the launch.
 namespace {
 
@@ -772,8 +772,8 @@ bool ranges_overlap(Range x, Range y) {
   const uintptr_t a = (uintptr_t)x.p, b = (uintptr_t)y.p;
   return x.p && y.p && a < b + y.bytes && b < a + x.bytes;
 }
-// the gradient passes: no output overlaps an input, and the two outputs do not overlap each other
-int check_grad_overlap(srz_ctx *ctx, const std::string &fn, const Range (&outs)[2], const Range (&ins)[3]) {
+// the gradient passes: no output overlaps an input (any number of them), and the two outputs do not overlap each other
+template <size_t N_IN> int check_grad_overlap(srz_ctx *ctx, const std::string &fn, const Range (&outs)[2], const Range (&ins)[N_IN]) {
   for (const Range &o : outs)
     for (const Range &i : ins)
       if (ranges_overlap(o, i)) return fail(ctx, SRZ_E_INVALID, fn + ": an output overlaps an input");
@@ -845,6 +845,31 @@ AntialiasArgs antialias_args(const srz_frameset *fs, const void *d_vis, const vo
   a.in = (const float *)d_in;
   a.vis_stride = 4ull * plane, a.frame_stride = n_ch * plane;
   a.n_ch = n_ch;
+  return a;
+}
+// what srz_frameset_texture and _texture_grad check alike; the texture's bytes in *tex_bytes
+int check_texture(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch,
+                  uint32_t tex_frames, uint32_t mode, uint32_t flags, size_t *tex_bytes) {
+  if (n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_ATTR_MAX_CH");
+  if (tex_w == 0u || tex_w > SRZ_TEX_MAX_SIZE || tex_h == 0u || tex_h > SRZ_TEX_MAX_SIZE)
+    return fail(ctx, SRZ_E_INVALID, fn + ": tex_w and tex_h must be 1 .. SRZ_TEX_MAX_SIZE");
+  if (mode != SRZ_TEX_CLAMP && mode != SRZ_TEX_WRAP) return fail(ctx, SRZ_E_INVALID, fn + ": mode must be SRZ_TEX_CLAMP or SRZ_TEX_WRAP");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  if (tex_frames != 1u && tex_frames != (uint32_t)fs->n_frames)
+    return fail(ctx, SRZ_E_INVALID, fn + ": tex_frames must be 1 or the set's frame count");
+  *tex_bytes = (size_t)tex_frames * tex_h * tex_w * n_ch * sizeof(float);
+  return SRZ_OK;
+}
+TexArgs texture_args(const srz_frameset *fs, const void *d_vis, const void *d_uv, const float *d_tex, uint32_t tex_w, uint32_t tex_h,
+                     uint32_t n_ch, uint32_t tex_frames, uint32_t mode, uint32_t out_planes, void *d_out, uint32_t flags) {
+  TexArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  a.uv = (const float *)d_uv, a.tex = d_tex;
+  a.vis_stride = 4ull * plane, a.frame_stride = out_planes * plane, a.uv_stride = 2ull * plane, a.gout_stride = n_ch * plane;
+  a.tex_frame_stride = tex_frames == 1u ? 0ull : (uint64_t)tex_h * tex_w * n_ch;
+  a.tex_w = tex_w, a.tex_h = tex_h, a.n_ch = n_ch, a.mode = mode;
+  a.flags_or = flags;
   return a;
 }
 
@@ -1627,6 +1652,53 @@ int srz_frameset_antialias_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vi
   AntialiasArgs a = antialias_args(fs, d_vis, d_in, n_ch, d_gin);
   a.gout = (const float *)d_gout, a.gpos = d_gpos, a.gpos_stride = (uint64_t)pos_tris * TRI_POS_F;
   launch_antialias_grad(a, s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_texture(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const float *d_tex, uint32_t tex_w,
+                         uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t mode, void *d_out, size_t out_bytes, uint32_t flags,
+                         void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_texture");
+  if (!fs || !d_vis || !d_uv || !d_tex || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / uv / texture / output");
+  size_t tex_bytes = 0;
+  if (int rc = check_texture(ctx, fs, fn, tex_w, tex_h, n_ch, tex_frames, mode, flags, &tex_bytes)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, n_ch), uv_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u);
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
+  if (!aligned<16>({d_vis, d_uv, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers must be 16-byte aligned");
+  if (!aligned<4>({d_tex})) return fail(ctx, SRZ_E_INVALID, fn + ": the texture must be 4-byte aligned");
+  if (ranges_overlap({d_out, need}, {d_vis, vis_bytes}) || ranges_overlap({d_out, need}, {d_uv, uv_bytes}) ||
+      ranges_overlap({d_out, need}, {d_tex, tex_bytes}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the visibility buffer, uv or the texture");
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (the caller's uv and texture, not the set's: no shading state, no vertex stage)
+  launch_tex(texture_args(fs, d_vis, d_uv, d_tex, tex_w, tex_h, n_ch, tex_frames, mode, n_ch, d_out, flags), s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_texture_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const void *d_gout, const float *d_tex,
+                              uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t mode, float *d_gtex, void *d_guv,
+                              uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_texture_grad");
+  if (!fs || !d_vis || !d_uv || !d_gout) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / uv / output gradient");
+  if (!d_gtex && !d_guv) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gtex nor d_guv is asked for");
+  if (d_guv && !d_tex) return fail(ctx, SRZ_E_INVALID, fn + ": d_guv needs the texture");
+  size_t tex_bytes = 0;
+  if (int rc = check_texture(ctx, fs, fn, tex_w, tex_h, n_ch, tex_frames, mode, flags, &tex_bytes)) return rc;
+  const size_t gout_bytes = srz_frameset_interpolate_bytes(ctx, fs, n_ch), uv_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u);
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (!aligned<16>({d_vis, d_uv, d_gout, d_guv})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers must be 16-byte aligned");
+  if (!aligned<4>({d_tex, d_gtex})) return fail(ctx, SRZ_E_INVALID, fn + ": the texture and its gradient must be 4-byte aligned");
+  if (int rc = check_grad_overlap(ctx, fn, {{d_gtex, tex_bytes}, {d_guv, uv_bytes}},
+                                  {{d_vis, vis_bytes}, {d_uv, uv_bytes}, {d_gout, gout_bytes}, {d_tex, tex_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_texture)
+  TexArgs a = texture_args(fs, d_vis, d_uv, d_tex, tex_w, tex_h, n_ch, tex_frames, mode, 2u, d_guv, flags);
+  a.gout = (const float *)d_gout, a.gtex = d_gtex;
+  launch_tex_grad(a, s);
   return end_pass(ctx);
 }
 

@@ -344,6 +344,31 @@ struct AntialiasArgs {
 };
 void launch_antialias(const AntialiasArgs &a, hipStream_t s);
 void launch_antialias_grad(const AntialiasArgs &a, hipStream_t s);
+// srz_frameset_texture / _texture_grad: a float texture of the caller's [texture frame][row][column][channel] sampled bilinearly at
+// the uv planes [frame][2][local_rows][width] under a visibility buffer (k_tex), and the gradients of that with respect to the
+// texels (gtex, added into) and to u, v (k_tex_grad).  vis as above; `out` is the forward's [frame][n_ch][local_rows][width] or the
+// backward's guv [frame][2][local_rows][width] (may be null there); `out` / `frame_stride` / `local_rows` / the shard are what
+// tile_rect reads.  The host has checked 1 <= tex_w, tex_h <= SRZ_TEX_MAX_SIZE and the mode
+struct TexArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *uv;
+  const float *tex;          // (backward: may be null when guv is)
+  float *out;
+  const float *gout;         // backward: [frame][n_ch][local_rows][width]
+  float *gtex;               // backward: tex's shape, added into (may be null)
+  uint64_t vis_stride;       // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride;     // floats per frame in out
+  uint64_t uv_stride;        // floats per frame in uv = 2 * local_rows * width
+  uint64_t gout_stride;      // floats per frame in gout = n_ch * local_rows * width
+  uint64_t tex_frame_stride; // floats per frame in tex / gtex = tex_h * tex_w * n_ch; 0: one texture for every frame
+  uint32_t tex_w, tex_h, n_ch, mode;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_tex(const TexArgs &a, hipStream_t s);
+void launch_tex_grad(const TexArgs &a, hipStream_t s);
 void launch_resolve8(const float *planes, uint8_t *out, uint32_t n_frames, uint32_t rows, uint32_t W, uint64_t frame_stride,
                      hipStream_t s);
 void launch_deinterleave(const void *gathered, void *full, uint32_t world, uint32_t n_fp, uint32_t bands_per_rank, uint32_t row_bytes,

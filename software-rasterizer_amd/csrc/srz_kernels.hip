@@ -4351,6 +4351,333 @@ __global__ __launch_bounds__(256) void k_antialias(AntialiasArgs a) { aa_body<fa
 __global__ __launch_bounds__(256) void k_antialias_grad(AntialiasArgs a) { aa_body<true>(a); }
 
 // ================================================================================================================
+// k_tex — CALLER TEXTURES OVER A VISIBILITY BUFFER (srz_frameset_texture, include/srz.h states the rule): a float texture of the
+// caller's, [frame][row][column][channel], sampled bilinearly at the uv planes interpolate (or gbuffer(UV)) wrote.  k_interp's shape:
+// no LDS, no barrier; the XCD-ordered walk over (frame, tile), 4 pixels of a row per thread, one 16-byte id load, u and v only for a
+// quad with an owner, every plane leaves through quad_store.  The four texel indices and the two fractions of a pixel are formed
+// once; the wave-uniform channel loop then gathers 4 * nc floats per sampled pixel, ATTR_CHUNK channels at a time, the tail masked.
+// Every float -> int conversion follows the clamp (CLAMP) or the fraction (WRAP): no uv leaves the texture.
+// ================================================================================================================
+struct TexTap {
+  uint32_t i00, i01, i10, i11; // texel indices row * tex_w + column of the corners (y0, x0), (y0, x1), (y1, x0), (y1, x1)
+  float tx, ty;
+  bool in_x, in_y;             // CLAMP: the coordinate lies strictly inside the texel centres' range (else its derivative is 0)
+};
+__device__ __forceinline__ bool tex_finite(float u) { return __builtin_fabsf(u) < __builtin_inff(); }
+// one axis of the rule: coordinate u over n texels -> the two texel coordinates, the fraction, and whether u moves the sample
+__device__ __forceinline__ void tex_axis(float u, uint32_t n, bool wrap, int &i0, int &i1, float &t, bool &in) {
+  const float nf = (float)n, hi = (float)(n - 1u);
+  if (wrap) u = u - __builtin_floorf(u);
+  float fx = u * nf - 0.5f;
+  in = true;
+  if (!wrap) {
+    in = fx > 0.0f && fx < hi;
+    fx = __builtin_fminf(__builtin_fmaxf(fx, 0.0f), hi);
+  }
+  const float f0 = __builtin_floorf(fx);
+  t = fx - f0;
+  i0 = (int)f0, i1 = i0 + 1;
+  if (!wrap) {
+    i1 = min(i1, (int)n - 1);
+  } else {
+    if (i0 < 0) i0 += (int)n;
+    if (i1 >= (int)n) i1 -= (int)n;
+  }
+}
+__device__ __forceinline__ TexTap tex_tap(float u, float v, uint32_t tw, uint32_t th, bool wrap) {
+  int x0, x1, y0, y1;
+  TexTap p;
+  tex_axis(u, tw, wrap, x0, x1, p.tx, p.in_x);
+  tex_axis(v, th, wrap, y0, y1, p.ty, p.in_y);
+  p.i00 = (uint32_t)y0 * tw + (uint32_t)x0, p.i01 = (uint32_t)y0 * tw + (uint32_t)x1;
+  p.i10 = (uint32_t)y1 * tw + (uint32_t)x0, p.i11 = (uint32_t)y1 * tw + (uint32_t)x1;
+  return p;
+}
+// what k_tex and k_tex_grad do alike in front of their channel loops: the ids, the owners, u and v of a quad with an owner, the
+// taps of the sampled pixels (an owner whose u and v are both finite) -> `own` and `smp`, one bit per pixel
+template <class A>
+__device__ __forceinline__ void tex_quad(const A &a, const SRZ_CAS FrameDesc *fd, const TileRect &rc, uint32_t f, size_t poff, bool inside,
+                                         bool whole, int x4, TexTap (&tap)[4], uint32_t &own, uint32_t &smp) {
+  const float *gv = a.vis + (size_t)f * a.vis_stride + poff; // plane 0 (z: never read)
+  uint32_t id[4] = {0u, 0u, 0u, 0u};
+  if (inside) {
+    if (whole) {
+      const uint4 q = *reinterpret_cast<const uint4 *>(gv + rc.plane);
+      id[0] = q.x, id[1] = q.y, id[2] = q.z, id[3] = q.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (x4 + k <= rc.tx1) id[k] = f2u(gv[rc.plane + k]);
+    }
+  }
+  const uint32_t n_tris = fd->n_tris;
+  own = 0u, smp = 0u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if ((id[k] & ~S_CLASS_BIT) - 1u < n_tris) own |= 1u << k; // (0 and the bare class bit wrap to 0xffffffff)
+  if (own == 0u) return;
+  float4 uv[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+  quad_load(a.uv + (size_t)f * a.uv_stride + poff, rc.plane, uv, whole, x4, rc.tx1);
+  const bool wrap = a.mode == SRZ_TEX_WRAP;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float u = quad_at(uv[0], k), v = quad_at(uv[1], k);
+    if (!(own & (1u << k)) || !tex_finite(u) || !tex_finite(v)) continue;
+    smp |= 1u << k;
+    tap[k] = tex_tap(u, v, a.tex_w, a.tex_h, wrap);
+  }
+}
+__global__ __launch_bounds__(256) void k_tex(TexArgs a) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  const uint32_t C = a.n_ch;
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
+  for (uint32_t j = blockIdx.x >> 3;; j += step) {
+    uint32_t f, t;
+    if (a.n_frames >= 8u) {
+      f = sub + 8u * (j / tpf), t = j % tpf;
+      if (f >= a.n_frames) break;
+    } else {
+      const uint32_t i = j * 8u + sub;
+      if (i >= n_items) break;
+      f = i / tpf, t = i % tpf;
+    }
+    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
+    const TileRect rc = tile_rect(a, fd, f, lb, tx);
+    const int W = fd->width;
+    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
+    if (!(y <= rc.ty1 && x4 <= rc.tx1)) continue; // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool whole = (W & 3) == 0 && x4 + 3 <= rc.tx1;
+    const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
+    const size_t poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)x4;
+    float *go = rc.out0 + (size_t)ly * (size_t)W + (size_t)x4;
+    // ---- 1. owners, u and v, the taps
+    TexTap tap[4] = {};
+    uint32_t own, smp;
+    tex_quad(a, fd, rc, f, poff, true, whole, x4, tap, own, smp);
+    if (own == 0u && !fused) continue;
+    const SRZ_CAS float *tex = as_const(a.tex) + (size_t)f * a.tex_frame_stride;
+    const bool quads = fused || own == 15u; // whole quads (fused clear, or four owners), else the owned pixels only
+    // ---- 2. the channels, ATTR_CHUNK at a time
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 q[ATTR_CHUNK];
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) q[i] = make_float4(0.f, 0.f, 0.f, 0.f); // nobody, and an owner that is not sampled: zeros
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(smp & (1u << k))) continue;
+        const SRZ_CAS float *p00 = tex + (size_t)tap[k].i00 * C + c0, *p01 = tex + (size_t)tap[k].i01 * C + c0;
+        const SRZ_CAS float *p10 = tex + (size_t)tap[k].i10 * C + c0, *p11 = tex + (size_t)tap[k].i11 * C + c0;
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+          if (i < nc) {
+            const float t00 = p00[i], t01 = p01[i], t10 = p10[i], t11 = p11[i];
+            const float top = fmaf_(tap[k].tx, t01 - t00, t00), bot = fmaf_(tap[k].tx, t11 - t10, t10);
+            quad_at(q[i], k) = fmaf_(tap[k].ty, bot - top, top);
+          }
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+        if (i >= nc) break;
+        float *p = go + (size_t)(c0 + i) * rc.plane;
+        if (quads) {
+          quad_store(p, rc.plane, {q[i]}, whole, x4, rc.tx1);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (own & (1u << k)) p[k] = quad_at(q[i], k);
+        }
+      }
+    }
+  }
+}
+
+// ================================================================================================================
+// k_tex_grad — THE BACKWARD OF k_tex (srz_frameset_texture_grad): per sampled pixel and channel, four adds w[corner] * gout into the
+// texture gradient (gtex), and the gradient with respect to u and v (guv: fma chains over the channels, from registers, no atomics).
+// The same walk and the same loads as k_tex, plus gout's quads, chunk by chunk.
+// Neighbouring pixels share texels (a magnified texture: dozens of pixels per texel; one texel per pixel: every texel is a corner of
+// four pixels), so the adds are combined before they leave the CU, as k_interp_grad combines its owners':
+//   1. in front of the channel loop every (pixel, corner) finds its texel's slot in the tile's table in LDS: open addressing on the
+//      texel index, TG_PROBES probes, TG_SLOTS slots.  A HASHED table, not a dense window anchored at the tile's smallest texel: the
+//      uv of a tile are whatever the mesh's charts are — a seam, a WRAP border or a minified texture spreads a tile's texels over
+//      the whole image, where a window holds nothing, while the table's capacity counts DISTINCT texels wherever they lie;
+//   2. per chunk the adds go to the slot's ATTR_CHUNK floats with LDS float adds; a corner that found no slot adds straight to
+//      memory — correct, only slower;
+//   3. after a barrier the chunk's values are flushed: the used slots are listed, so consecutive lanes add the consecutive
+//      channels of one texel, texel after texel, with global_atomic_add_f32.
+// Global adds are thus per (tile, distinct texel, channel).  The table's keys live for the whole tile, its values for one chunk.
+// Every thread of the workgroup reaches every barrier: a thread outside the frame samples nothing instead of moving on.
+// ================================================================================================================
+constexpr uint32_t TG_SLOT_BITS = 11, TG_SLOTS = 1u << TG_SLOT_BITS, TG_PROBES = 8, TG_NONE = 0xffffffffu;
+struct TexTable {
+  uint32_t key[TG_SLOTS];  // texel index + 1; 0: free
+  uint32_t used[TG_SLOTS]; // the slots taken, in arrival order
+  uint32_t n_used;
+  float val[TG_SLOTS * ATTR_CHUNK]; // [slot][channel of the chunk]
+};
+__device__ __forceinline__ void lds_add(float *p, float v) { unsafeAtomicAdd(p, v); }
+// the slot of texel `idx` in the tile's table, taken if need be; TG_NONE: no room within TG_PROBES
+__device__ __forceinline__ uint32_t tg_slot(TexTable &tb, uint32_t idx) {
+  const uint32_t key = idx + 1u; // (idx < SRZ_TEX_MAX_SIZE^2 = 2^28)
+  uint32_t h = (key * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
+  for (uint32_t p = 0; p < TG_PROBES; ++p) {
+    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
+    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
+    if (old == 0u || old == key) return h;
+    h = (h + 1u) & (TG_SLOTS - 1u);
+  }
+  return TG_NONE;
+}
+__device__ __forceinline__ void tg_add(TexTable &tb, uint32_t slot, float *gtex, uint32_t idx, uint32_t C, uint32_t ch, uint32_t i, float v) {
+  if (slot != TG_NONE) lds_add(&tb.val[slot * ATTR_CHUNK + i], v);
+  else global_add(gtex + (size_t)idx * C + ch, v);
+}
+__global__ __launch_bounds__(256) void k_tex_grad(TexArgs a) {
+  __shared__ TexTable tb;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  const uint32_t C = a.n_ch;
+  const bool want_tex = a.gtex != nullptr, want_uv = a.out != nullptr;
+  if (want_tex) {
+    for (uint32_t i = tid; i < TG_SLOTS; i += 256) tb.key[i] = 0u;
+    for (uint32_t i = tid; i < TG_SLOTS * ATTR_CHUNK; i += 256) tb.val[i] = 0.0f;
+    if (tid == 0) tb.n_used = 0u;
+    __syncthreads();
+  }
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
+  for (uint32_t j = blockIdx.x >> 3;; j += step) {
+    uint32_t f, t;
+    if (a.n_frames >= 8u) {
+      f = sub + 8u * (j / tpf), t = j % tpf;
+      if (f >= a.n_frames) break;
+    } else {
+      const uint32_t i = j * 8u + sub;
+      if (i >= n_items) break;
+      f = i / tpf, t = i % tpf;
+    }
+    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
+    const TileRect rc = tile_rect(a, fd, f, lb, tx);
+    const int W = fd->width;
+    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
+    const bool inside = y <= rc.ty1 && x4 <= rc.tx1; // (a thread outside the frame samples nothing, and still meets the barriers)
+    const bool whole = (W & 3) == 0 && x4 + 3 <= rc.tx1;
+    const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
+    const size_t poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)x4;
+    const float *gg = a.gout + (size_t)f * a.gout_stride + poff;
+    // ---- 1. owners, u and v, the taps
+    TexTap tap[4] = {};
+    uint32_t own, smp;
+    tex_quad(a, fd, rc, f, poff, inside, whole, x4, tap, own, smp);
+    const SRZ_CAS float *tex = as_const(a.tex) + (size_t)f * a.tex_frame_stride;
+    float *gtex = a.gtex + (size_t)f * a.tex_frame_stride;
+    // ---- 2. the slots of the sampled pixels' corners (two corners on one texel: one slot, both add)
+    uint32_t slot[4][4] = {};
+    if (want_tex) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (smp & (1u << k))
+          slot[k][0] = tg_slot(tb, tap[k].i00), slot[k][1] = tg_slot(tb, tap[k].i01), slot[k][2] = tg_slot(tb, tap[k].i10),
+          slot[k][3] = tg_slot(tb, tap[k].i11);
+    }
+    float au[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f};
+    uint32_t n_used = 0u;
+    // ---- 3. the channels, ATTR_CHUNK at a time
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 g[ATTR_CHUNK]; // gout of the chunk's channels; words of pixels that are not sampled are loaded with their quad at most, never used
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (smp != 0u) {
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+          if (i >= nc) break;
+          const float *p = gg + (size_t)(c0 + i) * rc.plane;
+          if (whole) {
+            g[i] = *reinterpret_cast<const float4 *>(p);
+          } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (smp & (1u << k)) quad_at(g[i], k) = p[k];
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(smp & (1u << k))) continue;
+        if (want_uv) {
+          const SRZ_CAS float *p00 = tex + (size_t)tap[k].i00 * C + c0, *p01 = tex + (size_t)tap[k].i01 * C + c0;
+          const SRZ_CAS float *p10 = tex + (size_t)tap[k].i10 * C + c0, *p11 = tex + (size_t)tap[k].i11 * C + c0;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float gi = quad_at(g[i], k), t00 = p00[i], t01 = p01[i], t10 = p10[i], t11 = p11[i];
+              const float top = fmaf_(tap[k].tx, t01 - t00, t00), bot = fmaf_(tap[k].tx, t11 - t10, t10);
+              au[k] = fmaf_(gi, fmaf_(tap[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au[k]);
+              av[k] = fmaf_(gi, bot - top, av[k]);
+            }
+        }
+        if (want_tex) {
+          const float tx_ = tap[k].tx, ty_ = tap[k].ty;
+          const float w00 = (1.0f - tx_) * (1.0f - ty_), w01 = tx_ * (1.0f - ty_), w10 = (1.0f - tx_) * ty_, w11 = tx_ * ty_;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float gi = quad_at(g[i], k);
+              tg_add(tb, slot[k][0], gtex, tap[k].i00, C, c0 + i, i, w00 * gi);
+              tg_add(tb, slot[k][1], gtex, tap[k].i01, C, c0 + i, i, w01 * gi);
+              tg_add(tb, slot[k][2], gtex, tap[k].i10, C, c0 + i, i, w10 * gi);
+              tg_add(tb, slot[k][3], gtex, tap[k].i11, C, c0 + i, i, w11 * gi);
+            }
+        }
+      }
+      if (want_tex) {
+        // ---- 4. the table's values of this chunk into memory: lanes in channel order within a texel
+        __syncthreads();
+        n_used = tb.n_used;
+        for (uint32_t i = tid; i < n_used * ATTR_CHUNK; i += 256) {
+          const uint32_t s = tb.used[i / ATTR_CHUNK], e = i % ATTR_CHUNK;
+          const float v = tb.val[s * ATTR_CHUNK + e];
+          tb.val[s * ATTR_CHUNK + e] = 0.0f;
+          if (e < nc) global_add(gtex + (size_t)(tb.key[s] - 1u) * C + c0 + e, v);
+        }
+        __syncthreads();
+      }
+    }
+    if (want_tex) { // the tile's keys go; every thread has read n_used before the chunk's last barrier
+      for (uint32_t i = tid; i < n_used; i += 256) tb.key[tb.used[i]] = 0u;
+      if (tid == 0) tb.n_used = 0u;
+      __syncthreads();
+    }
+    // ---- 5. du, dv: whole quads (fused clear, or four owners), else the owned pixels only; an owner that is not sampled: (0, 0)
+    if (want_uv && inside && (own != 0u || fused)) {
+      float4 du = make_float4(0.f, 0.f, 0.f, 0.f), dv = du;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (smp & (1u << k)) {
+          quad_at(du, k) = tap[k].in_x ? au[k] * (float)a.tex_w : 0.0f;
+          quad_at(dv, k) = tap[k].in_y ? av[k] * (float)a.tex_h : 0.0f;
+        }
+      float *go = rc.out0 + (size_t)ly * (size_t)W + (size_t)x4;
+      if (fused || own == 15u) {
+        quad_store(go, rc.plane, {du, dv}, whole, x4, rc.tx1);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (own & (1u << k)) go[k] = quad_at(du, k), go[rc.plane + k] = quad_at(dv, k);
+      }
+    }
+  }
+}
+
+// ================================================================================================================
 // k_resolve8 — display()'s resolve (src/Render.cpp:61-62): cv::merge(planes 0,1,2) + convertTo(CV_8UC3) =
 // saturate_cast<uchar>(cvRound(v)): round half to even, clamp to [0,255]; NaN → 0.  4 pixels per thread: three 16-byte
 // plane reads → 12 output bytes (three dword stores).
@@ -4931,6 +5258,8 @@ void launch_interp_grad(const InterpArgs &a, hipStream_t s) { launch_pass<k_inte
 void launch_pos_grad(const PosGradArgs &a, hipStream_t s) { launch_pass<k_pos_grad>(a, s); }
 void launch_antialias(const AntialiasArgs &a, hipStream_t s) { launch_pass<k_antialias>(a, s); }
 void launch_antialias_grad(const AntialiasArgs &a, hipStream_t s) { launch_pass<k_antialias_grad>(a, s); }
+void launch_tex(const TexArgs &a, hipStream_t s) { launch_pass<k_tex>(a, s); }
+void launch_tex_grad(const TexArgs &a, hipStream_t s) { launch_pass<k_tex_grad>(a, s); }
 
 bool raster_four_waves(const RenderArgs &a) { return a.n_frames * a.n_local_bands * a.tiles_x <= 4096u; }
 

@@ -26,6 +26,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_update_shading", "srz_frameset_shade_kinds", "srz_frameset_gbuffer_bytes", "srz_frameset_gbuffer",
            "srz_frameset_motion_bytes", "srz_frameset_motion", "srz_frameset_interpolate_bytes", "srz_frameset_interpolate",
            "srz_frameset_interpolate_grad", "srz_frameset_position_grad", "srz_frameset_antialias", "srz_frameset_antialias_grad",
+           "srz_frameset_texture", "srz_frameset_texture_grad",
            "srz_target_create", "srz_target_destroy", "srz_target_clear", "srz_target_draw", "srz_target_read", "srz_target_read_bgr8"]
 
 
@@ -85,6 +86,8 @@ def lib():
         L.srz_frameset_position_grad.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp]
         L.srz_frameset_antialias.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, C.c_uint32, vp]
         L.srz_frameset_antialias_grad.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp]
+        L.srz_frameset_texture.argtypes = abi.TEXTURE_ARGTYPES
+        L.srz_frameset_texture_grad.argtypes = abi.TEXTURE_GRAD_ARGTYPES
         L.srz_frameset_update_shading.argtypes = [vp, vp, C.POINTER(abi.SrzFrame), C.c_int]
         L.srz_sceneset_update.argtypes = [vp, vp, C.POINTER(abi.SrzSceneFrame), C.c_int]
         L.srz_frameset_resolve8.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
@@ -266,6 +269,26 @@ class FrameSet:
         self.ctx._check(lib().srz_frameset_antialias_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_in_ptr), C.c_void_p(d_gout_ptr),
                                                           n_ch, C.c_void_p(d_gin_ptr or None), pos_tris, C.c_void_p(d_gpos_ptr or None), flags,
                                                           _stream(stream)))
+
+    def texture(self, d_vis_ptr, d_uv_ptr, d_tex_ptr, tex_w, tex_h, n_ch, tex_frames, mode, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR,
+                stream=None):
+        """the caller's float32 texture [tex_frames][tex_h][tex_w][n_ch] (tex_frames: 1 or the frame count) sampled bilinearly at the
+        planes d_uv [frame][2][local_rows][width] (interpolate's of a two-channel attribute, or gbuffer(UV)) under a visibility
+        buffer of this set → d_out [frame][n_ch][local_rows][width]; mode: abi.TEX_CLAMP or abi.TEX_WRAP (include/srz.h states the
+        rule).  Pixels nobody owns are zeros with FUSED_CLEAR, else left untouched; an owner whose u or v is not finite gets zeros.
+        Asynchronous."""
+        self.ctx._check(lib().srz_frameset_texture(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_uv_ptr), C.c_void_p(d_tex_ptr), tex_w,
+                                                   tex_h, n_ch, tex_frames, mode, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def texture_grad(self, d_vis_ptr, d_uv_ptr, d_gout_ptr, d_tex_ptr, tex_w, tex_h, n_ch, tex_frames, mode, d_gtex_ptr, d_guv_ptr,
+                     flags=abi.FUSED_CLEAR, stream=None):
+        """the backward of texture: d_gout [frame][n_ch][local_rows][width] → ADDED into d_gtex (the texture's shape; the order of the
+        adds is unspecified: not bit-reproducible) and / or written to d_guv [frame][2][local_rows][width] (the gradient with respect
+        to u and v, deterministic; needs d_tex_ptr; the layout interpolate_grad takes as d_gout at n_ch = 2).  Either output pointer
+        may be None / 0, not both.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_texture_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_uv_ptr), C.c_void_p(d_gout_ptr),
+                                                        C.c_void_p(d_tex_ptr or None), tex_w, tex_h, n_ch, tex_frames, mode,
+                                                        C.c_void_p(d_gtex_ptr or None), C.c_void_p(d_guv_ptr or None), flags, _stream(stream)))
 
     def update_shading(self, frames):
         """new eye, ka, ks, p, kh, kn, lights, flags and batch shaders / textures for a set made from abi.Frame's, triangles untouched

@@ -20,6 +20,13 @@ GB_ALL = GB_NORMAL | GB_UV | GB_BATCH | GB_ALBEDO
 MV_FLOW, MV_DEPTH, MV_TARGET = 1, 2, 4  # srz_frameset_motion: the groups of `what` (2, 1, 2 planes, in this order)
 MV_ALL = MV_FLOW | MV_DEPTH | MV_TARGET
 ATTR_MAX_CH = 64  # srz_frameset_interpolate: the most channels of one call (SRZ_ATTR_MAX_CH)
+TEX_CLAMP, TEX_WRAP = 0, 1  # srz_frameset_texture: `mode` (SRZ_TEX_CLAMP, SRZ_TEX_WRAP)
+TEX_MAX_SIZE = 16384  # srz_frameset_texture: the largest tex_w and tex_h (SRZ_TEX_MAX_SIZE)
+# the prototypes of srz_frameset_texture / _texture_grad (argtypes; both return int), set on the library by srz.lib()
+TEXTURE_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                    C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+TEXTURE_GRAD_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
 
 # numpy view of srz_tri (96 B): pos[3][3], nrm[3][3], uv[3][2]
 TRI_DTYPE = np.dtype([("pos", "<f4", (3, 3)), ("nrm", "<f4", (3, 3)), ("uv", "<f4", (3, 2))])

@@ -346,3 +346,73 @@ def antialias(fs, vis, color, pos=None, stream=None):
     the sum of the interior and the silhouette term.  Backward is one antialias_grad call that asks only for the outputs some input
     needs, and no call when none does.  Needs an unsharded context.  stream: a raw stream handle, None = torch's current stream."""
     return _Antialias.apply(color, pos, fs, vis, stream)
+
+
+def _tex_dims(fs, tex):
+    if tex.dtype != torch.float32 or not tex.is_cuda or tex.dim() not in (3, 4):
+        raise ValueError(f"texture: tex must be a CUDA float32 tensor [H, W, C] or [n_frames, H, W, C], got {tuple(tex.shape)} {tex.dtype}")
+    tex_frames = tex.shape[0] if tex.dim() == 4 else 1
+    if tex.dim() == 4 and tex_frames != fs.n_frames:
+        raise ValueError(f"texture: tex has {tex_frames} frames, the set {fs.n_frames}")
+    h, w, n_ch = tex.shape[-3:]
+    if not (1 <= w <= abi.TEX_MAX_SIZE and 1 <= h <= abi.TEX_MAX_SIZE and 1 <= n_ch <= abi.ATTR_MAX_CH):
+        raise ValueError(f"texture: tex is {w} x {h} texels of {n_ch} channels; 1 .. {abi.TEX_MAX_SIZE} and 1 .. {abi.ATTR_MAX_CH} are supported")
+    return tex_frames, h, w, n_ch
+
+
+def _uv_arg(fs, uv):
+    if uv.dtype != torch.float32 or not uv.is_cuda or tuple(uv.shape) != tuple(fs.interpolate_shape(2)):
+        raise ValueError(f"texture: uv must be a CUDA float32 tensor {fs.interpolate_shape(2)}, got {tuple(uv.shape)} {uv.dtype}")
+    return uv.contiguous()
+
+
+def texture_grad(fs, vis, tex, uv, gout, wrap=False, want_gtex=True, want_guv=True, stream=None):
+    """the backward of texture(fs, vis, tex, uv, wrap) by one FrameSet.texture_grad call: gout [n_frames, C, rows, W] → (gtex, guv),
+    each None when not wanted (not both): gtex has tex's shape — a sum of float atomics into zeros, not bit-reproducible between
+    runs; guv [n_frames, 2, rows, W] is deterministic, zeros where nobody owns the pixel or its uv is not finite, and is what
+    interpolate's backward takes for a two-channel attribute.  stream: a raw stream handle, None = torch's current stream."""
+    if not want_gtex and not want_guv:
+        raise ValueError("texture_grad: neither gtex nor guv is asked for")
+    tex, uv, gout = tex.contiguous(), _uv_arg(fs, uv), gout.contiguous()
+    tex_frames, h, w, n_ch = _tex_dims(fs, tex)
+    if tuple(gout.shape) != tuple(fs.interpolate_shape(n_ch)) or gout.dtype != torch.float32:
+        raise ValueError(f"texture_grad: gout must be float32 {fs.interpolate_shape(n_ch)}, got {tuple(gout.shape)} {gout.dtype}")
+    gtex = torch.zeros_like(tex) if want_gtex else None
+    guv = torch.empty_like(uv) if want_guv else None
+    fs.texture_grad(vis.data_ptr(), uv.data_ptr(), gout.data_ptr(), tex.data_ptr(), w, h, n_ch, tex_frames, abi.TEX_WRAP if wrap else abi.TEX_CLAMP,
+                    gtex.data_ptr() if want_gtex else None, guv.data_ptr() if want_guv else None, abi.FUSED_CLEAR, _stream_ptr(stream))
+    return gtex, guv
+
+
+class _Texture(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tex, uv, fs, vis, wrap, stream):
+        tex, uv = tex.contiguous(), _uv_arg(fs, uv)
+        tex_frames, h, w, n_ch = _tex_dims(fs, tex)
+        out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=tex.device)
+        fs.texture(vis.data_ptr(), uv.data_ptr(), tex.data_ptr(), w, h, n_ch, tex_frames, abi.TEX_WRAP if wrap else abi.TEX_CLAMP, out.data_ptr(),
+                   fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR, _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.wrap, ctx.stream = fs, vis, wrap, stream
+        ctx.save_for_backward(tex, uv)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        tex, uv = ctx.saved_tensors
+        need_tex, need_uv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gtex = guv = None
+        if need_tex or need_uv:  # one call, asking only for what is needed
+            gtex, guv = texture_grad(ctx.fs, ctx.vis, tex, uv, gout, ctx.wrap, need_tex, need_uv, ctx.stream)
+        return gtex, guv, None, None, None, None
+
+
+def texture(fs, vis, tex, uv, wrap=False, stream=None):
+    """a float texture of the caller's own sampled bilinearly under a visibility buffer `vis` of FrameSet `fs`: tex is a CUDA float32
+    tensor [H, W, C] (one texture for every frame) or [n_frames, H, W, C], channels last, C <= abi.ATTR_MAX_CH, H and W <=
+    abi.TEX_MAX_SIZE; uv is [n_frames, 2, rows, W] — interpolate(fs, vis, uv_attr) of a [T, 3, 2] attribute, or the uv group of a
+    G-buffer → [n_frames, C, rows, W] float32, zeros where nobody owns the pixel or its uv is not finite (FrameSet.texture;
+    include/srz.h states the rule).  wrap: repeat the texture instead of clamping to its border texels.  Differentiable with
+    respect to tex (float atomics into a zeroed tensor: tex.grad is not bit-reproducible between runs) and to uv (deterministic), so
+    texture(fs, vis, tex, interpolate(fs, vis, uv_attr)) backpropagates to tex and to uv_attr.  Backward is one texture_grad call that
+    asks only for the outputs some input needs.  stream: a raw stream handle, None = torch's current stream."""
+    return _Texture.apply(tex, uv, fs, vis, wrap, stream)
