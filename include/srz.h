@@ -57,6 +57,9 @@ extern "C" {
  *      (additive, same version) silhouette antialiasing of a visibility buffer srz_frameset_antialias / srz_frameset_antialias_grad
  *      (additive, same version) caller textures over a visibility buffer, with gradients srz_frameset_texture /
  *      srz_frameset_texture_grad, SRZ_TEX_CLAMP, SRZ_TEX_WRAP, SRZ_TEX_MAX_SIZE
+ *      (additive, same version) mipmapped texture sampling over a visibility buffer, with gradients srz_texture_mip_levels /
+ *      srz_texture_mip_bytes / srz_texture_mip_build / srz_texture_mip_fold / srz_frameset_interpolate_deriv /
+ *      srz_frameset_texture_mip / srz_frameset_texture_mip_grad, SRZ_TEX_MAX_LEVELS
  */
 #define SRZ_ABI_VERSION 7
 
@@ -410,7 +413,8 @@ int srz_frameset_interpolate_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_
  * respect to each pixel's alpha and beta (and / or to its depth, plane 0) to the gradient with respect to the owners' SCREEN
  * POSITIONS, the nine floats ax ay z0 bx by z1 cx cy z2 of a triangle in the dense position stream's order, and to the pixel's own
  * sample point.  Owners are held fixed: this is the interior term of a differentiable rasteriser; the silhouette (coverage) term
- * is srz_frameset_antialias_grad's, below.  The chain visibility -> interpolate -> loss -> interpolate_grad -> positions then runs on
+ * is srz_frameset_antialias_grad's, below.  (Likewise the mip level lambda of srz_frameset_texture_mip is held fixed in its backward:
+ * the derivative planes srz_frameset_interpolate_deriv writes select a level and take no gradient.)  The chain visibility -> interpolate -> loss -> interpolate_grad -> positions then runs on
  * the device.
  * d_vis: a visibility buffer of THIS set on this ctx's shard.  d_gbary: [frame][2][local_rows][width] float32, exactly the planes
  * srz_frameset_interpolate_grad writes (dalpha and dbeta already carry gamma's share).  d_gz: [frame][1][local_rows][width] float32,
@@ -550,6 +554,95 @@ int srz_frameset_texture(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, cons
 int srz_frameset_texture_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const void *d_gout, const float *d_tex,
                               uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t mode, float *d_gtex, void *d_guv,
                               uint32_t flags, void *stream);
+/* MIPMAPPED TEXTURE SAMPLING over a visibility buffer, and its gradients: the TRILINEAR lookup over a mip pyramid of the caller's
+ * texture that goes with the bilinear lookup above, its level chosen from the screen-space derivatives of uv.  Three pieces: the
+ * pyramid (build, and fold: its backward), the derivatives of an interpolated attribute, the lookup and its backward.  All of it
+ * float32, nothing fused except where fmaf is written, division and sqrtf the IEEE operations (SRZ_OPT_APPROX_SHADE has no effect).
+ * THE PYRAMID.  Level 0 is the caller's texture [tex_frames][H][W][C] as srz_frameset_texture takes it.  Level l + 1 exists iff
+ * (w_l > 1 or h_l > 1) and w_l is even or 1 and h_l is even or 1; then w_(l+1) = max(1, w_l / 2), h_(l+1) likewise — an odd extent
+ * ends the chain (100 x 70: 2 levels; 96 x 64: 6, down to 3 x 2; 32 x 8: 6, ... 4 x 1, 2 x 1, 1 x 1; 5 x 7 and 1 x 1: 1).
+ * srz_texture_mip_levels: the levels including level 0 (1024^2: 11, 16384^2: SRZ_TEX_MAX_LEVELS); 0 for an extent of 0 or above
+ * SRZ_TEX_MAX_SIZE.  srz_texture_mip_bytes: the bytes of levels 1 .. n_levels - 1, LEVEL-MAJOR — level l is [tex_frames][h_l][w_l][C]
+ * float32, the levels one after another without padding; 0 for n_levels <= 1, n_levels above srz_texture_mip_levels, n_ch == 0 or
+ * above SRZ_ATTR_MAX_CH, tex_frames == 0 or above 65536.  Both are pure host functions.
+ * srz_texture_mip_build: d_tex -> d_mip (levels 1 .. n_levels - 1), each level from the level above it, deterministic, bit for bit,
+ * whatever the wrap mode will be: where both extents halve out = ((t00 + t01) + (t10 + t11)) * 0.25f with t_rc at (2y + r, 2x + c);
+ * where one extent is already 1, out = (t0 + t1) * 0.5f along the other.  A ctx-level call (no set); stream and asynchrony as the
+ * frameset passes.  n_levels == 1 succeeds and launches nothing.
+ * srz_texture_mip_fold: the backward of the build: the gradient pyramid d_gmip (d_mip's layout, read only) folded into d_gtex
+ * (level 0, ADDED INTO by one fma per element).  A gather, no atomics, deterministic, bit for bit: per texel (y, x) of level 0 and
+ * channel, with g_l the element of level l at (y >> l, x >> l), k_l the build's factor into level l (0.25f or 0.5f) and
+ * L = n_levels:  acc = g_(L-1);  for l = L - 2 .. 1: acc = fmaf(k_(l+1), acc, g_l);  gtex = fmaf(k_1, acc, gtex).
+ * SRZ_E_INVALID from either, nothing launched: a null ctx or pointer (the pyramid's may be null at n_levels == 1); tex_w or tex_h 0
+ * or above SRZ_TEX_MAX_SIZE; n_ch 0 or above SRZ_ATTR_MAX_CH; tex_frames 0 or above 65536; n_levels 0 or above
+ * srz_texture_mip_levels(tex_w, tex_h); mip_bytes below srz_texture_mip_bytes; a pointer not 4-byte aligned; the pyramid overlapping
+ * the texture (n_levels > 1).
+ * THE DERIVATIVES.  srz_frameset_interpolate_deriv: the signature, band sharding, owner and nobody and SRZ_FUSED_CLEAR of
+ * srz_frameset_interpolate, except 1 <= n_ch <= SRZ_ATTR_MAX_CH / 2 and d_out [frame][2 * n_ch][local_rows][width],
+ * srz_frameset_interpolate_bytes(2 * n_ch) bytes: plane 2 ch is d/dx, plane 2 ch + 1 d/dy of channel ch per one-pixel step.  The
+ * positions are the set's own, read exactly as srz_frameset_position_grad reads them (a sceneset runs its vertex stage first); the
+ * class bit plays no part.  Interpolation is affine in the sample point with owners held fixed, so the derivative is a constant of
+ * the owner: with its nine floats ax ay z0 bx by z1 cx cy z2,
+ *   area = (bx - ax) * (cy - ay) - (by - ay) * (cx - ax);  r = 1.0f / area
+ *   gax = (by - cy) * r;  gay = (cx - bx) * r;  gbx = (cy - ay) * r;  gby = (ax - cx) * r
+ * and per channel, with the corner values a, b, c:  da = a - c;  db = b - c;
+ *   d/dx = fmaf(da, gax, db * gbx);  d/dy = fmaf(da, gay, db * gby)
+ * A zero area propagates inf / NaN as IEEE has it; no input value makes the pass read or write outside its buffers.  Deterministic,
+ * bit for bit.  There is no backward: the derivative planes only select a level.
+ * THE LOOKUP.  srz_frameset_texture_mip: srz_frameset_texture's arguments, plus d_uvd [frame][4][local_rows][width] — the planes
+ * ux, uy, vx, vy (du/dx, du/dy, dv/dx, dv/dy) srz_frameset_interpolate_deriv writes at n_ch = 2, 16-byte aligned —, d_mip (the
+ * pyramid srz_texture_mip_build wrote for THIS d_tex, 4-byte aligned) and n_levels.  n_levels == 1 reads neither d_uvd nor d_mip
+ * (both may be null): the output is srz_frameset_texture's, bit for bit.  Unsampled pixels (u or v not finite), nobody's pixels and
+ * SRZ_FUSED_CLEAR as the bilinear pass.  THE LEVEL of a sampled pixel, with L = n_levels and W, H the extents of level 0:
+ *   fin = all four of ux, uy, vx, vy finite (fabsf(.) < INFINITY)
+ *   ax = ux * (float)W;  ay = vx * (float)H;  bx = uy * (float)W;  by = vy * (float)H
+ *   rx = fmaf(ax, ax, ay * ay);  ry = fmaf(bx, bx, by * by);  r2 = rx > ry ? rx : ry
+ *   if (!fin || !(r2 < INFINITY))            l0 = L - 1, f = 0
+ *   else { rho = sqrtf(r2)
+ *     if (!(rho > 1.0f))                     l0 = 0, f = 0            (magnified, or no footprint)
+ *     else { m = frexpf(rho, &e)             (rho = m * 2^e, 0.5 <= m < 1)
+ *            l = e - 1;  f = fmaf(2.0f, m, -1.0f)                     (exact)
+ *            if (l >= L - 1) l0 = L - 1, f = 0  else l0 = l } }
+ * lambda = l0 + f is continuous and monotone in rho, equals log2(rho) at every power of two and lies within 0.0861 of it between
+ * them: a PIECEWISE-LINEAR log2, a deliberate deviation from the true logarithm — it needs no transcendental function, so the rule
+ * is exact on every implementation.  No level bias, no anisotropy.
+ * THE SAMPLE: c_l is the bilinear sample of level l by the per-axis rule above with n = w_l, h_l (and this level's texels);
+ *   out = c_l0 when f == 0 (level l0 + 1 is not read), else out = fmaf(f, c_(l0+1) - c_l0, c_l0).
+ * BACKWARD, srz_frameset_texture_mip_grad: d_gout and the same d_vis, d_uv, d_uvd; at least one of (d_gtex with d_gmip) and d_guv.
+ * d_gtex and d_gmip come together whenever n_levels > 1 (d_gmip is not touched, and may be null, at n_levels == 1).  LAMBDA IS HELD
+ * FIXED, as owners are: there is no gradient to d_uvd.  d_tex and d_mip may be null when only the texel gradients are asked for.
+ *   texels: for level l0 the level weight is lw = 1.0f - f, for level l0 + 1 it is lw = f, and that level gets no add when f == 0.
+ *   Per corner and channel the float32 product (w_rc * lw) * gout[ch] (w_rc as the bilinear pass, from this level's tx, ty) is ADDED
+ *   to the corner's texel of that level: level 0 in d_gtex, the others in d_gmip (d_mip's layout).  The caller zeroes the buffers,
+ *   or accumulates; srz_texture_mip_fold then folds d_gmip into d_gtex.  THE ORDER OF THE ADDS IS UNSPECIFIED, each add rounds, so
+ *   d_gtex and d_gmip are NOT BIT-REPRODUCIBLE between launches, like d_gtex of the bilinear pass: with n contributing adds an element
+ *   lies within n 2^-24 / (1 - n 2^-24) * sum |term| of the exact sum of the float32 terms; an element with one contributing add is
+ *   exact.  The adds are hardware float atomics: d_gtex and d_gmip must be ordinary (coarse-grained) device memory.
+ *   d_guv, needs d_tex (and d_mip at n_levels > 1), deterministic, bit for bit: du_l, dv_l are the bilinear pass's du, dv at level l
+ *   (its fma chains over the channels, the in_x / in_y gates and the factors (float)w_l, (float)h_l of that level);
+ *   du = du_l0 when f == 0, else fmaf(f, du_(l0+1) - du_l0, du_l0); dv likewise.  The layout is srz_frameset_interpolate_grad's d_gout
+ *   at n_ch = 2: the chain into interpolate_grad and position_grad continues unchanged.
+ * Every level index follows the clamp to L - 1 and every texel index the clamp or the fraction of its own level: no value of uv or
+ * uvd makes a pass read or write outside its buffers.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched: what the bilinear pair refuses, and n_levels 0 or above
+ * srz_texture_mip_levels(tex_w, tex_h); with n_levels > 1 a null d_uvd, a null d_mip (forward; backward with d_guv), one of d_gtex /
+ * d_gmip without the other; a misaligned pointer (16 bytes: the plane buffers, d_uvd among them; 4 bytes: d_tex, d_mip, d_gtex,
+ * d_gmip); an output that overlaps an input (d_uvd and d_mip among the inputs, d_gmip among the outputs) or another output. */
+#define SRZ_TEX_MAX_LEVELS 15u
+uint32_t srz_texture_mip_levels(uint32_t tex_w, uint32_t tex_h);
+size_t srz_texture_mip_bytes(uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels);
+int srz_texture_mip_build(srz_ctx *ctx, const float *d_tex, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames,
+                          uint32_t n_levels, float *d_mip, size_t mip_bytes, void *stream);
+int srz_texture_mip_fold(srz_ctx *ctx, const float *d_gmip, size_t mip_bytes, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch,
+                         uint32_t tex_frames, uint32_t n_levels, float *d_gtex, void *stream);
+int srz_frameset_interpolate_deriv(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_attr, uint32_t n_ch,
+                                   uint32_t attr_frames, uint32_t attr_tris, void *d_out, size_t out_bytes, uint32_t flags, void *stream);
+int srz_frameset_texture_mip(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const void *d_uvd, const float *d_tex,
+                             uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t mode, const float *d_mip,
+                             uint32_t n_levels, void *d_out, size_t out_bytes, uint32_t flags, void *stream);
+int srz_frameset_texture_mip_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const void *d_uvd, const void *d_gout,
+                                  const float *d_tex, const float *d_mip, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames,
+                                  uint32_t mode, uint32_t n_levels, float *d_gtex, float *d_gmip, void *d_guv, uint32_t flags, void *stream);
 /* New SHADING DATA for a set made by srz_frameset_create, its triangles untouched (batches[b].tris is ignored and may be NULL): each
  * frame's eye, ka, ks, p, kh, kn, lights and flags, each batch's shader and tex_id.  The structure must be the set's — frame count, size,
  * light counts, batch counts, n_tris per batch — else SRZ_E_INVALID and the set is unchanged; a sceneset is SRZ_E_INVALID (its shading

@@ -743,7 +743,7 @@ int stats_pass(srz_ctx *ctx, srz_frameset *fs, const float *d_start, uint32_t fl
 
 } // namespace
 
-// The passes over a visibility buffer (srz_frameset_shade_visibility .. srz_frameset_texture_grad): what their entry points share.
+// The passes over a visibility buffer (srz_frameset_shade_visibility .. srz_frameset_texture_mip_grad): what their entry points share.
 // Each entry point is its own argument rules, these checks, its own Args fields, the launch.
 namespace {
 
@@ -869,6 +869,56 @@ TexArgs texture_args(const srz_frameset *fs, const void *d_vis, const void *d_uv
   a.vis_stride = 4ull * plane, a.frame_stride = out_planes * plane, a.uv_stride = 2ull * plane, a.gout_stride = n_ch * plane;
   a.tex_frame_stride = tex_frames == 1u ? 0ull : (uint64_t)tex_h * tex_w * n_ch;
   a.tex_w = tex_w, a.tex_h = tex_h, a.n_ch = n_ch, a.mode = mode;
+  a.flags_or = flags;
+  return a;
+}
+// the mip passes: any number of outputs against any number of inputs, and the outputs against each other
+int check_overlaps(srz_ctx *ctx, const std::string &fn, std::initializer_list<Range> outs, std::initializer_list<Range> ins) {
+  for (const Range *o = outs.begin(); o != outs.end(); ++o) {
+    for (const Range &i : ins)
+      if (ranges_overlap(*o, i)) return fail(ctx, SRZ_E_INVALID, fn + ": an output overlaps an input");
+    for (const Range *p = o + 1; p != outs.end(); ++p)
+      if (ranges_overlap(*o, *p)) return fail(ctx, SRZ_E_INVALID, fn + ": two outputs overlap");
+  }
+  return SRZ_OK;
+}
+constexpr uint32_t MIP_MAX_FRAMES = 65536u;
+// what srz_texture_mip_build and _mip_fold check alike (no set: tex_frames is any count up to MIP_MAX_FRAMES)
+int check_mip(srz_ctx *ctx, const std::string &fn, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels,
+              size_t mip_bytes, const void *tex, const void *mip) {
+  if (!tex) return fail(ctx, SRZ_E_INVALID, fn + ": null texture");
+  if (n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_ATTR_MAX_CH");
+  if (tex_w == 0u || tex_w > SRZ_TEX_MAX_SIZE || tex_h == 0u || tex_h > SRZ_TEX_MAX_SIZE)
+    return fail(ctx, SRZ_E_INVALID, fn + ": tex_w and tex_h must be 1 .. SRZ_TEX_MAX_SIZE");
+  if (tex_frames == 0u || tex_frames > MIP_MAX_FRAMES) return fail(ctx, SRZ_E_INVALID, fn + ": tex_frames must be 1 .. 65536");
+  if (n_levels == 0u || n_levels > srz_texture_mip_levels(tex_w, tex_h))
+    return fail(ctx, SRZ_E_INVALID, fn + ": n_levels must be 1 .. srz_texture_mip_levels(tex_w, tex_h)");
+  if (!mip && n_levels > 1u) return fail(ctx, SRZ_E_INVALID, fn + ": null pyramid"); // (one level: there is none)
+  const size_t need = srz_texture_mip_bytes(tex_w, tex_h, n_ch, tex_frames, n_levels);
+  if (mip_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": mip_bytes is below srz_texture_mip_bytes");
+  if (!aligned<4>({tex, mip})) return fail(ctx, SRZ_E_INVALID, fn + ": the texture and the pyramid must be 4-byte aligned");
+  if (ranges_overlap({tex, (size_t)tex_frames * tex_h * tex_w * n_ch * sizeof(float)}, {mip, need}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the pyramid overlaps the texture");
+  return SRZ_OK;
+}
+// what srz_frameset_texture_mip and _texture_mip_grad check alike behind check_texture; the pyramid's bytes in *mip_bytes
+int check_tex_mip(srz_ctx *ctx, const std::string &fn, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels,
+                  const void *d_uvd, size_t *mip_bytes) {
+  if (n_levels == 0u || n_levels > srz_texture_mip_levels(tex_w, tex_h))
+    return fail(ctx, SRZ_E_INVALID, fn + ": n_levels must be 1 .. srz_texture_mip_levels(tex_w, tex_h)");
+  if (n_levels > 1u && !d_uvd) return fail(ctx, SRZ_E_INVALID, fn + ": n_levels > 1 needs the derivative planes");
+  *mip_bytes = srz_texture_mip_bytes(tex_w, tex_h, n_ch, tex_frames, n_levels);
+  return SRZ_OK;
+}
+TexMipArgs texture_mip_args(const srz_frameset *fs, const void *d_vis, const void *d_uv, const void *d_uvd, const float *d_tex,
+                            const float *d_mip, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t mode,
+                            uint32_t n_levels, uint32_t out_planes, void *d_out, uint32_t flags) {
+  TexMipArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  a.uv = (const float *)d_uv, a.uvd = (const float *)d_uvd, a.tex = d_tex, a.mip = d_mip;
+  a.vis_stride = 4ull * plane, a.frame_stride = out_planes * plane, a.uv_stride = 2ull * plane, a.gout_stride = n_ch * plane;
+  a.tex_w = tex_w, a.tex_h = tex_h, a.n_ch = n_ch, a.mode = mode, a.tex_frames = tex_frames, a.n_levels = n_levels;
   a.flags_or = flags;
   return a;
 }
@@ -1699,6 +1749,137 @@ int srz_frameset_texture_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis,
   TexArgs a = texture_args(fs, d_vis, d_uv, d_tex, tex_w, tex_h, n_ch, tex_frames, mode, 2u, d_guv, flags);
   a.gout = (const float *)d_gout, a.gtex = d_gtex;
   launch_tex_grad(a, s);
+  return end_pass(ctx);
+}
+
+uint32_t srz_texture_mip_levels(uint32_t tex_w, uint32_t tex_h) {
+  if (tex_w == 0u || tex_w > SRZ_TEX_MAX_SIZE || tex_h == 0u || tex_h > SRZ_TEX_MAX_SIZE) return 0u;
+  uint32_t n = 1u;
+  while ((tex_w > 1u || tex_h > 1u) && (tex_w % 2u == 0u || tex_w == 1u) && (tex_h % 2u == 0u || tex_h == 1u))
+    tex_w = std::max(1u, tex_w / 2u), tex_h = std::max(1u, tex_h / 2u), ++n;
+  return n;
+}
+
+size_t srz_texture_mip_bytes(uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels) {
+  const uint32_t most = srz_texture_mip_levels(tex_w, tex_h);
+  if (most == 0u || n_levels <= 1u || n_levels > most || n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH || tex_frames == 0u || tex_frames > MIP_MAX_FRAMES)
+    return 0;
+  return (size_t)mip_texels_before(tex_w, tex_h, n_levels) * tex_frames * n_ch * sizeof(float);
+}
+
+int srz_texture_mip_build(srz_ctx *ctx, const float *d_tex, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames,
+                          uint32_t n_levels, float *d_mip, size_t mip_bytes, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_texture_mip_build");
+  if (int rc = check_mip(ctx, fn, tex_w, tex_h, n_ch, tex_frames, n_levels, mip_bytes, d_tex, d_mip)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = pick_stream(ctx, stream);
+  const float *src = d_tex;
+  float *dst = d_mip;
+  for (uint32_t l = 1; l < n_levels; ++l) { // each level from the level above it
+    const uint32_t sw = mip_extent(tex_w, l - 1u), sh = mip_extent(tex_h, l - 1u), dw = mip_extent(tex_w, l), dh = mip_extent(tex_h, l);
+    launch_mip_build(src, dst, sw, sh, dw, dh, n_ch, tex_frames, s);
+    src = dst, dst += (size_t)tex_frames * dh * dw * n_ch;
+  }
+  return end_pass(ctx);
+}
+
+int srz_texture_mip_fold(srz_ctx *ctx, const float *d_gmip, size_t mip_bytes, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch,
+                         uint32_t tex_frames, uint32_t n_levels, float *d_gtex, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_texture_mip_fold");
+  if (int rc = check_mip(ctx, fn, tex_w, tex_h, n_ch, tex_frames, n_levels, mip_bytes, d_gtex, d_gmip)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = pick_stream(ctx, stream);
+  if (n_levels > 1u) launch_mip_fold(d_gmip, d_gtex, tex_w, tex_h, n_ch, tex_frames, n_levels, s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_interpolate_deriv(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_attr, uint32_t n_ch,
+                                   uint32_t attr_frames, uint32_t attr_tris, void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_interpolate_deriv");
+  if (!fs || !d_vis || !d_attr || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / attributes / output");
+  if (n_ch > SRZ_ATTR_MAX_CH / 2u) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_ATTR_MAX_CH / 2");
+  size_t attr_bytes = 0;
+  if (int rc = check_interp(ctx, fs, fn, n_ch, attr_frames, attr_tris, flags, &attr_bytes)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, 2u * n_ch), vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
+  if (!aligned<16>({d_vis, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
+  if (!aligned<4>({d_attr})) return fail(ctx, SRZ_E_INVALID, fn + ": the attributes must be 4-byte aligned");
+  if (ranges_overlap({d_out, need}, {d_vis, vis_bytes}) || ranges_overlap({d_out, need}, {d_attr, attr_bytes}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the visibility buffer or the attributes");
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, PASS_VERTEX, &s)) return rc; // (the set's positions, as srz_frameset_position_grad)
+  InterpDerivArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  fill_positions(a, fs);
+  a.attr = d_attr;
+  a.vis_stride = 4ull * plane, a.frame_stride = 2ull * n_ch * plane;
+  a.attr_frame_stride = attr_frames == 1u ? 0ull : (uint64_t)attr_tris * 3u * n_ch;
+  a.n_ch = n_ch;
+  a.flags_or = flags;
+  launch_interp_deriv(a, s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_texture_mip(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const void *d_uvd, const float *d_tex,
+                             uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t mode, const float *d_mip,
+                             uint32_t n_levels, void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_texture_mip");
+  if (!fs || !d_vis || !d_uv || !d_tex || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / uv / texture / output");
+  size_t tex_bytes = 0, mip_bytes = 0;
+  if (int rc = check_texture(ctx, fs, fn, tex_w, tex_h, n_ch, tex_frames, mode, flags, &tex_bytes)) return rc;
+  if (int rc = check_tex_mip(ctx, fn, tex_w, tex_h, n_ch, tex_frames, n_levels, d_uvd, &mip_bytes)) return rc;
+  if (n_levels > 1u && !d_mip) return fail(ctx, SRZ_E_INVALID, fn + ": n_levels > 1 needs the pyramid");
+  if (n_levels == 1u) d_uvd = nullptr, d_mip = nullptr; // (not read: they take no part in the checks either)
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, n_ch), uv_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u);
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs); // (the derivative planes: four per frame, the visibility buffer's size)
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
+  if (!aligned<16>({d_vis, d_uv, d_uvd, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers must be 16-byte aligned");
+  if (!aligned<4>({d_tex, d_mip})) return fail(ctx, SRZ_E_INVALID, fn + ": the texture and the pyramid must be 4-byte aligned");
+  if (int rc = check_overlaps(ctx, fn, {{d_out, need}},
+                              {{d_vis, vis_bytes}, {d_uv, uv_bytes}, {d_uvd, vis_bytes}, {d_tex, tex_bytes}, {d_mip, mip_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_texture)
+  launch_tex_mip(texture_mip_args(fs, d_vis, d_uv, d_uvd, d_tex, d_mip, tex_w, tex_h, n_ch, tex_frames, mode, n_levels, n_ch, d_out, flags), s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_texture_mip_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const void *d_uvd, const void *d_gout,
+                                  const float *d_tex, const float *d_mip, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames,
+                                  uint32_t mode, uint32_t n_levels, float *d_gtex, float *d_gmip, void *d_guv, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_texture_mip_grad");
+  if (!fs || !d_vis || !d_uv || !d_gout) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / uv / output gradient");
+  if (!d_gtex && !d_gmip && !d_guv) return fail(ctx, SRZ_E_INVALID, fn + ": neither the texel gradients nor d_guv is asked for");
+  if (d_guv && !d_tex) return fail(ctx, SRZ_E_INVALID, fn + ": d_guv needs the texture");
+  size_t tex_bytes = 0, mip_bytes = 0;
+  if (int rc = check_texture(ctx, fs, fn, tex_w, tex_h, n_ch, tex_frames, mode, flags, &tex_bytes)) return rc;
+  if (int rc = check_tex_mip(ctx, fn, tex_w, tex_h, n_ch, tex_frames, n_levels, d_uvd, &mip_bytes)) return rc;
+  if (n_levels > 1u && d_guv && !d_mip) return fail(ctx, SRZ_E_INVALID, fn + ": d_guv needs the pyramid when n_levels > 1");
+  if (n_levels > 1u && (d_gtex == nullptr) != (d_gmip == nullptr))
+    return fail(ctx, SRZ_E_INVALID, fn + ": d_gtex and d_gmip come together when n_levels > 1");
+  if (n_levels == 1u) {
+    if (!d_gtex && !d_guv) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gtex nor d_guv is asked for");
+    d_uvd = nullptr, d_mip = nullptr, d_gmip = nullptr; // (not read, not written: they take no part in the checks either)
+  }
+  const size_t gout_bytes = srz_frameset_interpolate_bytes(ctx, fs, n_ch), uv_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u);
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (!aligned<16>({d_vis, d_uv, d_uvd, d_gout, d_guv})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers must be 16-byte aligned");
+  if (!aligned<4>({d_tex, d_mip, d_gtex, d_gmip}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the texture, the pyramid and their gradients must be 4-byte aligned");
+  if (int rc = check_overlaps(ctx, fn, {{d_gtex, tex_bytes}, {d_gmip, mip_bytes}, {d_guv, uv_bytes}},
+                              {{d_vis, vis_bytes}, {d_uv, uv_bytes}, {d_uvd, vis_bytes}, {d_gout, gout_bytes}, {d_tex, tex_bytes}, {d_mip, mip_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_texture)
+  TexMipArgs a = texture_mip_args(fs, d_vis, d_uv, d_uvd, d_tex, d_mip, tex_w, tex_h, n_ch, tex_frames, mode, n_levels, 2u, d_guv, flags);
+  a.gout = (const float *)d_gout, a.gtex = d_gtex, a.gmip = d_gmip;
+  launch_tex_mip_grad(a, s);
   return end_pass(ctx);
 }
 

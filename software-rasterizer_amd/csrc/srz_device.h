@@ -369,6 +369,70 @@ struct TexArgs {
 };
 void launch_tex(const TexArgs &a, hipStream_t s);
 void launch_tex_grad(const TexArgs &a, hipStream_t s);
+// THE MIP PYRAMID of a caller texture (include/srz.h states the geometry): level l of a tex_w x tex_h texture is
+// max(1, tex_w >> l) x max(1, tex_h >> l) — every level that exists came from an even (or one-texel) extent, so the shifts are the
+// halvings — and the levels 1 .. n_levels - 1 lie one after another, each [tex_frames][h_l][w_l][n_ch].  Host and device share these.
+__host__ __device__ inline uint32_t mip_extent(uint32_t n, uint32_t l) { return (n >> l) > 1u ? n >> l : 1u; }
+// the texels of one frame in the levels 1 .. l - 1 (below tex_w * tex_h <= 2^28)
+__host__ __device__ inline uint32_t mip_texels_before(uint32_t tex_w, uint32_t tex_h, uint32_t l) {
+  uint32_t s = 0;
+  for (uint32_t k = 1; k < l; ++k) s += mip_extent(tex_w, k) * mip_extent(tex_h, k);
+  return s;
+}
+// the build's factor into level l (>= 1): 0.25f where both extents of level l - 1 halve, 0.5f where one of them is already 1
+__host__ __device__ inline float mip_factor(uint32_t tex_w, uint32_t tex_h, uint32_t l) {
+  return mip_extent(tex_w, l - 1u) > 1u && mip_extent(tex_h, l - 1u) > 1u ? 0.25f : 0.5f;
+}
+// srz_texture_mip_build: one level from the level above it (k_mip_build, one launch per level); src [frames][src_h][src_w][n_ch],
+// dst [frames][dst_h][dst_w][n_ch]
+void launch_mip_build(const float *src, float *dst, uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h, uint32_t n_ch,
+                      uint32_t tex_frames, hipStream_t s);
+// srz_texture_mip_fold: the gradient pyramid gmip (levels 1 .. n_levels - 1) folded into gtex (level 0), a gather (k_mip_fold)
+void launch_mip_fold(const float *gmip, float *gtex, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels,
+                     hipStream_t s);
+// srz_frameset_interpolate_deriv: the screen-space derivatives of caller attributes (k_interp_deriv).  vis, attr and the walk as
+// InterpArgs has them, tri_pos / pos_stride as PosGradArgs; `out` is [frame][2 * n_ch][local_rows][width]
+struct InterpDerivArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *tri_pos;       // [triangle * pos_stride], as RenderArgs has it
+  const float *attr;
+  float *out;
+  uint64_t vis_stride;        // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride;      // floats per frame in out = 2 * n_ch * local_rows * width
+  uint64_t attr_frame_stride; // floats per frame in attr = attr_tris * 3 * n_ch; 0: one array for every frame
+  uint32_t pos_stride, n_ch;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_interp_deriv(const InterpDerivArgs &a, hipStream_t s);
+// srz_frameset_texture_mip / _texture_mip_grad: TexArgs' fields, plus the derivative planes uvd [frame][4][local_rows][width], the
+// pyramid `mip` (backward: may be null when guv is), its gradient `gmip` (added into, comes with gtex) and the level count
+// (k_tex_mip, k_tex_mip_grad).  n_levels == 1: uvd, mip and gmip are not read.  The host has checked n_levels against the size
+struct TexMipArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *uv;
+  const float *uvd;
+  const float *tex;
+  const float *mip;
+  float *out;
+  const float *gout;
+  float *gtex;
+  float *gmip;
+  uint64_t vis_stride;       // floats per frame in vis and uvd = 4 * local_rows * width
+  uint64_t frame_stride;     // floats per frame in out
+  uint64_t uv_stride;        // floats per frame in uv = 2 * local_rows * width
+  uint64_t gout_stride;      // floats per frame in gout = n_ch * local_rows * width
+  uint32_t tex_w, tex_h, n_ch, mode;
+  uint32_t tex_frames, n_levels;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_tex_mip(const TexMipArgs &a, hipStream_t s);
+void launch_tex_mip_grad(const TexMipArgs &a, hipStream_t s);
 void launch_resolve8(const float *planes, uint8_t *out, uint32_t n_frames, uint32_t rows, uint32_t W, uint64_t frame_stride,
                      hipStream_t s);
 void launch_deinterleave(const void *gathered, void *full, uint32_t world, uint32_t n_fp, uint32_t bands_per_rank, uint32_t row_bytes,

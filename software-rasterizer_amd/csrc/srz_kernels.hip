@@ -4678,6 +4678,577 @@ __global__ __launch_bounds__(256) void k_tex_grad(TexArgs a) {
 }
 
 // ================================================================================================================
+// k_mip_build / k_mip_fold — THE MIP PYRAMID OF A CALLER TEXTURE (srz_texture_mip_build, srz_texture_mip_fold; include/srz.h states
+// the geometry and the arithmetic).  The build is one launch per level, each from the level above it: a workgroup walks rows of the
+// level it writes, its threads the row's (texel, channel) elements — consecutive lanes, consecutive floats.  The fold is the build's
+// transpose as a GATHER: per element of level 0 the chain of its ancestors, coarsest first, one fma per level — no atomics.
+// Both are bound by memory: the build reads 4 (2) floats per float it writes, the fold's ancestors come from cache.
+// ================================================================================================================
+__global__ __launch_bounds__(256) void k_mip_build(const float *src, float *dst, uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h,
+                                                   uint32_t C, uint32_t n_rows) {
+  const bool both = src_w > 1u && src_h > 1u, along_x = src_w > 1u;
+  const size_t row = (size_t)src_w * C;
+  const uint32_t per_row = dst_w * C; // (<= 8192 * 64)
+  for (uint32_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+    const uint32_t ft = r / dst_h, y = r % dst_h;
+    const float *s = src + ((size_t)ft * src_h + (src_h > 1u ? 2u * y : 0u)) * row;
+    float *d = dst + (size_t)r * per_row;
+    for (uint32_t i = threadIdx.x; i < per_row; i += 256u) {
+      const uint32_t x = i / C, ch = i % C;
+      const float *p = s + (size_t)(along_x ? 2u * x : 0u) * C + ch;
+      d[i] = both ? ((p[0] + p[C]) + (p[row] + p[row + C])) * 0.25f : (p[0] + p[along_x ? (size_t)C : row]) * 0.5f;
+    }
+  }
+}
+__global__ __launch_bounds__(256) void k_mip_fold(const float *gmip, float *gtex, uint32_t W, uint32_t H, uint32_t C, uint32_t TF, uint32_t L) {
+  const uint32_t n_rows = TF * H, per_row = W * C;
+  const size_t total = (size_t)mip_texels_before(W, H, L) * TF * C; // the floats of the levels 1 .. L - 1
+  for (uint32_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+    const uint32_t ft = r / H, y = r % H;
+    float *d = gtex + (size_t)r * per_row;
+    for (uint32_t i = threadIdx.x; i < per_row; i += 256u) {
+      const uint32_t x = i / C, ch = i % C;
+      size_t end = total;
+      float acc = 0.0f;
+      for (uint32_t l = L - 1u; l >= 1u; --l) { // (wave-uniform: the levels' sizes and places are scalars)
+        const uint32_t wl = mip_extent(W, l), hl = mip_extent(H, l);
+        const size_t off = end - (size_t)wl * hl * TF * C;
+        const float g = gmip[off + (((size_t)ft * hl + (y >> l)) * wl + (x >> l)) * C + ch];
+        acc = l == L - 1u ? g : fmaf_(mip_factor(W, H, l + 1u), acc, g);
+        end = off;
+      }
+      d[i] = fmaf_(mip_factor(W, H, 1u), acc, d[i]);
+    }
+  }
+}
+
+// ================================================================================================================
+// k_interp_deriv — SCREEN-SPACE DERIVATIVES OF CALLER ATTRIBUTES (srz_frameset_interpolate_deriv, include/srz.h): interpolation is
+// affine in the sample point with owners held fixed (k_pos_grad's ∇α, ∇β), so channel ch of the owner changes per one-pixel step by
+// (a − c) ∇α + (b − c) ∇β: a constant of the triangle.  k_interp's walk, loads and stores (no LDS, no barrier), plus load_pos9 of
+// the owner as k_pos_grad has it, once per run of one owner within the quad; planes 2 ch (d/dx) and 2 ch + 1 (d/dy).  The class bit
+// plays no part.  The floor is the memory system: 4 bytes of id per pixel; 36 + 12 n_ch of gather per owned pixel; 8 n_ch written.
+// ================================================================================================================
+struct DerivTri {
+  float gax, gay, gbx, gby; // ∇α, ∇β
+};
+__device__ __forceinline__ DerivTri deriv_tri(const SRZ_CAS float *p) {
+  float P[9]; // ax ay z0 bx by z1 cx cy z2
+  load_pos9(p, P);
+  const float area = (P[3] - P[0]) * (P[7] - P[1]) - (P[4] - P[1]) * (P[6] - P[0]);
+  const float r = 1.0f / area; // (the IEEE division)
+  return {(P[4] - P[7]) * r, (P[6] - P[3]) * r, (P[7] - P[1]) * r, (P[0] - P[6]) * r};
+}
+__global__ __launch_bounds__(256) void k_interp_deriv(InterpDerivArgs a) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  const uint32_t C = a.n_ch;
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
+  for (uint32_t j = blockIdx.x >> 3;; j += step) {
+    uint32_t f, t;
+    if (a.n_frames >= 8u) {
+      f = sub + 8u * (j / tpf), t = j % tpf;
+      if (f >= a.n_frames) break;
+    } else {
+      const uint32_t i = j * 8u + sub;
+      if (i >= n_items) break;
+      f = i / tpf, t = i % tpf;
+    }
+    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
+    const TileRect rc = tile_rect(a, fd, f, lb, tx);
+    const int W = fd->width;
+    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
+    if (!(y <= rc.ty1 && x4 <= rc.tx1)) continue; // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool whole = (W & 3) == 0 && x4 + 3 <= rc.tx1;
+    const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
+    const size_t poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)x4;
+    const float *gv = a.vis + (size_t)f * a.vis_stride + poff; // plane 0 (z: never read)
+    float *go = rc.out0 + (size_t)ly * (size_t)W + (size_t)x4;
+    // ---- 1. owner indices + 1 (0 or an index outside the frame's triangles: nobody)
+    uint32_t id[4] = {0u, 0u, 0u, 0u};
+    if (whole) {
+      const uint4 q = *reinterpret_cast<const uint4 *>(gv + rc.plane);
+      id[0] = q.x, id[1] = q.y, id[2] = q.z, id[3] = q.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (x4 + k <= rc.tx1) id[k] = f2u(gv[rc.plane + k]);
+    }
+    const uint32_t n_tris = fd->n_tris;
+    uint32_t own = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      id[k] &= ~S_CLASS_BIT;
+      if (id[k] - 1u >= n_tris) id[k] = 0u; // (0 wraps to 0xffffffff)
+      own |= id[k] != 0u ? 1u << k : 0u;
+    }
+    if (own == 0u && !fused) continue;
+    // ---- 2. ∇α, ∇β of each owner, gathered once per run of one owner
+    const SRZ_CAS float *tpos = as_const(a.tri_pos) + (size_t)fd->tri_off * a.pos_stride;
+    DerivTri T[4] = {};
+    {
+      uint32_t prev = 0u;
+      DerivTri cur = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (id[k] == 0u) continue;
+        if (id[k] != prev) cur = deriv_tri(tpos + (size_t)(id[k] - 1u) * a.pos_stride), prev = id[k];
+        T[k] = cur;
+      }
+    }
+    const SRZ_CAS float *at = as_const(a.attr) + (size_t)f * a.attr_frame_stride;
+    const bool quads = fused || own == 15u; // whole quads (fused clear, or four owners), else the owned pixels only
+    // ---- 3. the channels, ATTR_CHUNK at a time
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 qx[ATTR_CHUNK], qy[ATTR_CHUNK];
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) qx[i] = qy[i] = make_float4(0.f, 0.f, 0.f, 0.f); // nobody: zeros
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (id[k] == 0u) continue;
+        const SRZ_CAS float *p = at + (size_t)(id[k] - 1u) * (3u * C) + c0;
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+          if (i < nc) {
+            const float cc = p[2u * C + i], da = p[i] - cc, db = p[C + i] - cc;
+            quad_at(qx[i], k) = fmaf_(da, T[k].gax, db * T[k].gbx);
+            quad_at(qy[i], k) = fmaf_(da, T[k].gay, db * T[k].gby);
+          }
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+        if (i >= nc) break;
+        float *p = go + (size_t)(2u * (c0 + i)) * rc.plane;
+        if (quads) {
+          quad_store(p, rc.plane, {qx[i], qy[i]}, whole, x4, rc.tx1);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (own & (1u << k)) p[k] = quad_at(qx[i], k), p[rc.plane + k] = quad_at(qy[i], k);
+        }
+      }
+    }
+  }
+}
+
+// ================================================================================================================
+// k_tex_mip — THE TRILINEAR LOOKUP OVER A MIP PYRAMID (srz_frameset_texture_mip, include/srz.h states the rule): k_tex's walk and
+// shape (no LDS, no barrier, 4 pixels of a row per thread, quad_store), plus the four derivative planes of a quad with a sampled
+// pixel.  Per sampled pixel the level l0 and the fraction f come from mip_lod — compares, one sqrt, frexp: no transcendental — and
+// the taps of level l0 and, ONLY where f != 0, of level l0 + 1 from tex_tap with that level's extents; a magnified pixel (f == 0 at
+// level 0) costs what it costs in k_tex.  A level's extents are shifts of the texture's, its place in the pyramid a short sum over
+// the levels before it (mip_texels_before): nothing is indexed by a per-lane level, nothing lives in scratch.
+// l0 <= n_levels - 1 by the clamp in mip_lod; every texel index follows tex_axis's clamp within its level: no uv or derivative
+// leaves the texture or the pyramid.
+// ================================================================================================================
+struct MipLod {
+  uint32_t l0;
+  float f;
+};
+__device__ __forceinline__ MipLod mip_lod(float ux, float uy, float vx, float vy, float Wf, float Hf, uint32_t L) {
+  MipLod r = {L - 1u, 0.0f}; // not finite, or a footprint beyond the coarsest level
+  const bool fin = tex_finite(ux) && tex_finite(uy) && tex_finite(vx) && tex_finite(vy);
+  const float ax = ux * Wf, ay = vx * Hf, bx = uy * Wf, by = vy * Hf;
+  const float rx = fmaf_(ax, ax, ay * ay), ry = fmaf_(bx, bx, by * by), r2 = rx > ry ? rx : ry;
+  if (fin && r2 < __builtin_inff()) {
+    const float rho = __builtin_sqrtf(r2); // (the IEEE square root)
+    if (!(rho > 1.0f)) {
+      r.l0 = 0u; // magnified, or no footprint
+    } else {
+      int e;
+      const float m = __builtin_frexpf(rho, &e); // rho = m 2^e, 0.5 <= m < 1, 1 <= e <= 128
+      const uint32_t l = (uint32_t)(e - 1);
+      if (l < L - 1u) r.l0 = l, r.f = fmaf_(2.0f, m, -1.0f);
+    }
+  }
+  return r;
+}
+// what k_tex_mip and k_tex_mip_grad do alike in front of their loops: the ids, the owners, u and v of a quad with an owner, the
+// derivatives of a quad with a sampled pixel and the level of each -> `own` and `smp`, one bit per pixel (tex_quad, with levels)
+__device__ __forceinline__ void mip_quad(const TexMipArgs &a, const SRZ_CAS FrameDesc *fd, const TileRect &rc, uint32_t f, size_t poff,
+                                         bool inside, bool whole, int x4, float4 (&uv)[2], MipLod (&lod)[4], uint32_t &own, uint32_t &smp) {
+  const float *gv = a.vis + (size_t)f * a.vis_stride + poff; // plane 0 (z: never read)
+  uint32_t id[4] = {0u, 0u, 0u, 0u};
+  if (inside) {
+    if (whole) {
+      const uint4 q = *reinterpret_cast<const uint4 *>(gv + rc.plane);
+      id[0] = q.x, id[1] = q.y, id[2] = q.z, id[3] = q.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (x4 + k <= rc.tx1) id[k] = f2u(gv[rc.plane + k]);
+    }
+  }
+  const uint32_t n_tris = fd->n_tris;
+  own = 0u, smp = 0u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    lod[k] = {0u, 0.0f};
+    if ((id[k] & ~S_CLASS_BIT) - 1u < n_tris) own |= 1u << k; // (0 and the bare class bit wrap to 0xffffffff)
+  }
+  uv[0] = uv[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (own == 0u) return;
+  quad_load(a.uv + (size_t)f * a.uv_stride + poff, rc.plane, uv, whole, x4, rc.tx1);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if ((own & (1u << k)) && tex_finite(quad_at(uv[0], k)) && tex_finite(quad_at(uv[1], k))) smp |= 1u << k;
+  if (a.n_levels <= 1u || smp == 0u) return;
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 d[4] = {zero, zero, zero, zero}; // (words of pixels that are not sampled: loaded with their quad at most, never used)
+  quad_load(a.uvd + (size_t)f * a.vis_stride + poff, rc.plane, d, whole, x4, rc.tx1);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (smp & (1u << k))
+      lod[k] = mip_lod(quad_at(d[0], k), quad_at(d[1], k), quad_at(d[2], k), quad_at(d[3], k), (float)a.tex_w, (float)a.tex_h, a.n_levels);
+}
+// level l of frame f: level 0 is the texture itself, the others lie in the pyramid behind the levels before them
+template <class P>
+__device__ __forceinline__ P *mip_level(P *tex, P *mip, uint32_t tex_w, uint32_t tex_h, uint32_t C, uint32_t tex_frames, uint32_t f, uint32_t l) {
+  const size_t ft = tex_frames == 1u ? 0u : f, texels = (size_t)mip_extent(tex_w, l) * mip_extent(tex_h, l);
+  return l == 0u ? tex + ft * texels * C : mip + ((size_t)mip_texels_before(tex_w, tex_h, l) * tex_frames + ft * texels) * C;
+}
+__device__ __forceinline__ float tex_bilinear(const SRZ_CAS float *t, const TexTap &p, uint32_t C, uint32_t ch) {
+  const float t00 = t[(size_t)p.i00 * C + ch], t01 = t[(size_t)p.i01 * C + ch], t10 = t[(size_t)p.i10 * C + ch], t11 = t[(size_t)p.i11 * C + ch];
+  const float top = fmaf_(p.tx, t01 - t00, t00), bot = fmaf_(p.tx, t11 - t10, t10);
+  return fmaf_(p.ty, bot - top, top);
+}
+__global__ __launch_bounds__(256) void k_tex_mip(TexMipArgs a) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  const uint32_t C = a.n_ch;
+  const bool wrap = a.mode == SRZ_TEX_WRAP;
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
+  for (uint32_t j = blockIdx.x >> 3;; j += step) {
+    uint32_t f, t;
+    if (a.n_frames >= 8u) {
+      f = sub + 8u * (j / tpf), t = j % tpf;
+      if (f >= a.n_frames) break;
+    } else {
+      const uint32_t i = j * 8u + sub;
+      if (i >= n_items) break;
+      f = i / tpf, t = i % tpf;
+    }
+    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
+    const TileRect rc = tile_rect(a, fd, f, lb, tx);
+    const int W = fd->width;
+    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
+    if (!(y <= rc.ty1 && x4 <= rc.tx1)) continue; // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool whole = (W & 3) == 0 && x4 + 3 <= rc.tx1;
+    const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
+    const size_t poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)x4;
+    float *go = rc.out0 + (size_t)ly * (size_t)W + (size_t)x4;
+    // ---- 1. owners, u and v, the levels
+    float4 uv[2];
+    MipLod lod[4];
+    uint32_t own, smp;
+    mip_quad(a, fd, rc, f, poff, true, whole, x4, uv, lod, own, smp);
+    if (own == 0u && !fused) continue;
+    // ---- 2. the taps of level l0 and, where f != 0, of level l0 + 1
+    TexTap t0[4] = {}, t1[4] = {};
+    const SRZ_CAS float *p0[4], *p1[4];
+    uint32_t two = 0u; // the pixels that blend two levels
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      p0[k] = p1[k] = as_const(a.tex);
+      if (!(smp & (1u << k))) continue;
+      const uint32_t l = lod[k].l0;
+      t0[k] = tex_tap(quad_at(uv[0], k), quad_at(uv[1], k), mip_extent(a.tex_w, l), mip_extent(a.tex_h, l), wrap);
+      p0[k] = mip_level(as_const(a.tex), as_const(a.mip), a.tex_w, a.tex_h, C, a.tex_frames, f, l);
+      if (lod[k].f != 0.0f) { // (l + 1 <= n_levels - 1: mip_lod gives f == 0 at the coarsest level)
+        two |= 1u << k;
+        t1[k] = tex_tap(quad_at(uv[0], k), quad_at(uv[1], k), mip_extent(a.tex_w, l + 1u), mip_extent(a.tex_h, l + 1u), wrap);
+        p1[k] = mip_level(as_const(a.tex), as_const(a.mip), a.tex_w, a.tex_h, C, a.tex_frames, f, l + 1u);
+      }
+    }
+    const bool quads = fused || own == 15u; // whole quads (fused clear, or four owners), else the owned pixels only
+    // ---- 3. the channels, ATTR_CHUNK at a time
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 q[ATTR_CHUNK];
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) q[i] = make_float4(0.f, 0.f, 0.f, 0.f); // nobody, and an owner that is not sampled: zeros
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(smp & (1u << k))) continue;
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+          if (i < nc) {
+            float c = tex_bilinear(p0[k], t0[k], C, c0 + i);
+            if (two & (1u << k)) c = fmaf_(lod[k].f, tex_bilinear(p1[k], t1[k], C, c0 + i) - c, c);
+            quad_at(q[i], k) = c;
+          }
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+        if (i >= nc) break;
+        float *p = go + (size_t)(c0 + i) * rc.plane;
+        if (quads) {
+          quad_store(p, rc.plane, {q[i]}, whole, x4, rc.tx1);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (own & (1u << k)) p[k] = quad_at(q[i], k);
+        }
+      }
+    }
+  }
+}
+
+// ================================================================================================================
+// k_tex_mip_grad — THE BACKWARD OF k_tex_mip (srz_frameset_texture_mip_grad), λ held fixed.  k_tex_grad's walk and barriers; two
+// phases per tile, each with its own channel loop:
+//   A. guv (from registers, deterministic): the bilinear pass's fma chains at level l0 and, where f != 0, at level l0 + 1, blended
+//      by f as the forward blends the samples;
+//   B. the texel adds, ONE LEVEL AT A TIME: the tile's pixels name the levels they touch in a word of LDS; for each of them the
+//      tile's table phase runs as k_tex_grad has it — the slots of the level's taps (TexTable keyed on the texel index WITHIN the
+//      level; mg_slot / mg_add are copies of tg_slot / tg_add), per chunk the LDS adds of (w_rc * lw) * gout, the dense flush into
+//      that level's gradient, the keys released.  The table's capacity thus counts the distinct texels of ONE level, which a minified tile's
+//      footprint keeps near its pixel count; the slot numbers of one level are live at a time (k_tex_grad's 16 registers, not 32).
+//      The flush is a COPY of k_tex_grad's step 4 (the project's rule for helpers); a fix goes into both.
+// A pixel takes part in level l with lw = 1 - f when l == l0 and with lw = f when l == l0 + 1 and f != 0; its tap of the level is
+// formed again from u and v (some thirty operations) rather than kept across the phases.
+// Every thread of the workgroup reaches every barrier: the levels of a tile are read from LDS by all, a thread outside the frame
+// samples nothing.  The level word rotates over three words by the tile's count, the next one zeroed in front of the barrier: one
+// barrier per tile in front of the levels' own.
+// ================================================================================================================
+// (COPIES of tg_slot and tg_add: shared with k_tex_grad they moved ITS registers, 171 -> 221 VGPRs; a fix goes into both)
+__device__ __forceinline__ uint32_t mg_slot(TexTable &tb, uint32_t idx) {
+  const uint32_t key = idx + 1u; // (idx < SRZ_TEX_MAX_SIZE^2 = 2^28)
+  uint32_t h = (key * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
+  for (uint32_t p = 0; p < TG_PROBES; ++p) {
+    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
+    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
+    if (old == 0u || old == key) return h;
+    h = (h + 1u) & (TG_SLOTS - 1u);
+  }
+  return TG_NONE;
+}
+__device__ __forceinline__ void mg_add(TexTable &tb, uint32_t slot, float *gtex, uint32_t idx, uint32_t C, uint32_t ch, uint32_t i, float v) {
+  if (slot != TG_NONE) unsafeAtomicAdd(&tb.val[slot * ATTR_CHUNK + i], v);
+  else unsafeAtomicAdd(gtex + (size_t)idx * C + ch, v);
+}
+__global__ __launch_bounds__(256) void k_tex_mip_grad(TexMipArgs a) {
+  __shared__ TexTable tb;
+  __shared__ uint32_t levels[3];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  const uint32_t C = a.n_ch;
+  const bool want_tex = a.gtex != nullptr, want_uv = a.out != nullptr, wrap = a.mode == SRZ_TEX_WRAP;
+  if (want_tex) {
+    for (uint32_t i = tid; i < TG_SLOTS; i += 256) tb.key[i] = 0u;
+    for (uint32_t i = tid; i < TG_SLOTS * ATTR_CHUNK; i += 256) tb.val[i] = 0.0f;
+    if (tid == 0) tb.n_used = 0u;
+    if (tid < 3) levels[tid] = 0u;
+    __syncthreads();
+  }
+  uint32_t turn = 0u; // the tile's count in this workgroup's walk mod 3 (the same in every thread: nobody skips a tile)
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
+  for (uint32_t j = blockIdx.x >> 3;; j += step) {
+    uint32_t f, t;
+    if (a.n_frames >= 8u) {
+      f = sub + 8u * (j / tpf), t = j % tpf;
+      if (f >= a.n_frames) break;
+    } else {
+      const uint32_t i = j * 8u + sub;
+      if (i >= n_items) break;
+      f = i / tpf, t = i % tpf;
+    }
+    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
+    const TileRect rc = tile_rect(a, fd, f, lb, tx);
+    const int W = fd->width;
+    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
+    const bool inside = y <= rc.ty1 && x4 <= rc.tx1; // (a thread outside the frame samples nothing, and still meets the barriers)
+    const bool whole = (W & 3) == 0 && x4 + 3 <= rc.tx1;
+    const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
+    const size_t poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)x4;
+    const float *gg = a.gout + (size_t)f * a.gout_stride + poff;
+    // ---- 1. owners, u and v, the levels
+    float4 uv[2];
+    MipLod lod[4];
+    uint32_t own, smp;
+    mip_quad(a, fd, rc, f, poff, inside, whole, x4, uv, lod, own, smp);
+    // ---- A. du, dv
+    if (want_uv && inside && (own != 0u || fused)) {
+      TexTap t0[4] = {}, t1[4] = {};
+      const SRZ_CAS float *p0[4], *p1[4];
+      uint32_t two = 0u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        p0[k] = p1[k] = as_const(a.tex);
+        if (!(smp & (1u << k))) continue;
+        const uint32_t l = lod[k].l0;
+        t0[k] = tex_tap(quad_at(uv[0], k), quad_at(uv[1], k), mip_extent(a.tex_w, l), mip_extent(a.tex_h, l), wrap);
+        p0[k] = mip_level(as_const(a.tex), as_const(a.mip), a.tex_w, a.tex_h, C, a.tex_frames, f, l);
+        if (lod[k].f != 0.0f) {
+          two |= 1u << k;
+          t1[k] = tex_tap(quad_at(uv[0], k), quad_at(uv[1], k), mip_extent(a.tex_w, l + 1u), mip_extent(a.tex_h, l + 1u), wrap);
+          p1[k] = mip_level(as_const(a.tex), as_const(a.mip), a.tex_w, a.tex_h, C, a.tex_frames, f, l + 1u);
+        }
+      }
+      float au0[4] = {0.f, 0.f, 0.f, 0.f}, av0[4] = {0.f, 0.f, 0.f, 0.f}, au1[4] = {0.f, 0.f, 0.f, 0.f}, av1[4] = {0.f, 0.f, 0.f, 0.f};
+      for (uint32_t c0 = 0; c0 < C && smp != 0u; c0 += ATTR_CHUNK) {
+        const uint32_t nc = min(ATTR_CHUNK, C - c0);
+        float4 g[ATTR_CHUNK];
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+          if (i >= nc) break;
+          const float *p = gg + (size_t)(c0 + i) * rc.plane;
+          if (whole) {
+            g[i] = *reinterpret_cast<const float4 *>(p);
+          } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (smp & (1u << k)) quad_at(g[i], k) = p[k];
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (!(smp & (1u << k))) continue;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float gi = quad_at(g[i], k);
+              {
+                const SRZ_CAS float *q = p0[k] + c0 + i;
+                const float t00 = q[(size_t)t0[k].i00 * C], t01 = q[(size_t)t0[k].i01 * C], t10 = q[(size_t)t0[k].i10 * C], t11 = q[(size_t)t0[k].i11 * C];
+                const float top = fmaf_(t0[k].tx, t01 - t00, t00), bot = fmaf_(t0[k].tx, t11 - t10, t10);
+                au0[k] = fmaf_(gi, fmaf_(t0[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au0[k]);
+                av0[k] = fmaf_(gi, bot - top, av0[k]);
+              }
+              if (two & (1u << k)) {
+                const SRZ_CAS float *q = p1[k] + c0 + i;
+                const float t00 = q[(size_t)t1[k].i00 * C], t01 = q[(size_t)t1[k].i01 * C], t10 = q[(size_t)t1[k].i10 * C], t11 = q[(size_t)t1[k].i11 * C];
+                const float top = fmaf_(t1[k].tx, t01 - t00, t00), bot = fmaf_(t1[k].tx, t11 - t10, t10);
+                au1[k] = fmaf_(gi, fmaf_(t1[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au1[k]);
+                av1[k] = fmaf_(gi, bot - top, av1[k]);
+              }
+            }
+        }
+      }
+      // whole quads (fused clear, or four owners), else the owned pixels only; an owner that is not sampled: (0, 0)
+      float4 du = make_float4(0.f, 0.f, 0.f, 0.f), dv = du;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (smp & (1u << k)) {
+          const uint32_t l = lod[k].l0;
+          float u0 = t0[k].in_x ? au0[k] * (float)mip_extent(a.tex_w, l) : 0.0f, v0 = t0[k].in_y ? av0[k] * (float)mip_extent(a.tex_h, l) : 0.0f;
+          if (two & (1u << k)) {
+            const float u1 = t1[k].in_x ? au1[k] * (float)mip_extent(a.tex_w, l + 1u) : 0.0f;
+            const float v1 = t1[k].in_y ? av1[k] * (float)mip_extent(a.tex_h, l + 1u) : 0.0f;
+            u0 = fmaf_(lod[k].f, u1 - u0, u0), v0 = fmaf_(lod[k].f, v1 - v0, v0);
+          }
+          quad_at(du, k) = u0, quad_at(dv, k) = v0;
+        }
+      float *go = rc.out0 + (size_t)ly * (size_t)W + (size_t)x4;
+      if (fused || own == 15u) {
+        quad_store(go, rc.plane, {du, dv}, whole, x4, rc.tx1);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (own & (1u << k)) go[k] = quad_at(du, k), go[rc.plane + k] = quad_at(dv, k);
+      }
+    }
+    if (!want_tex) continue;
+    // ---- B. the texel adds: the levels this tile touches, then the table phase of each
+    {
+      uint32_t mine = 0u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (smp & (1u << k)) mine |= (lod[k].f != 0.0f ? 3u : 1u) << lod[k].l0; // (l0 + 1 <= n_levels - 1 <= 14 where f != 0)
+      if (mine != 0u) atomicOr(&levels[turn], mine);
+      if (tid == 0) levels[turn == 2u ? 0u : turn + 1u] = 0u; // (last read two tiles ago, in front of the previous tile's barrier)
+    }
+    __syncthreads();
+    uint32_t todo = __builtin_amdgcn_readfirstlane(levels[turn]);
+    turn = turn == 2u ? 0u : turn + 1u;
+    for (; todo != 0u; todo &= todo - 1u) {
+      const uint32_t l = (uint32_t)__builtin_ctz(todo), wl = mip_extent(a.tex_w, l), hl = mip_extent(a.tex_h, l);
+      float *gdst = mip_level(a.gtex, a.gmip, a.tex_w, a.tex_h, C, a.tex_frames, f, l);
+      // ---- B1. the pixels of this level, their taps and level weights, the slots of their corners
+      TexTap tap[4] = {};
+      float lw[4] = {0.f, 0.f, 0.f, 0.f};
+      uint32_t part = 0u;
+      uint32_t slot[4][4] = {};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(smp & (1u << k))) continue;
+        const bool lower = lod[k].l0 == l, upper = lod[k].l0 + 1u == l && lod[k].f != 0.0f;
+        if (!lower && !upper) continue;
+        part |= 1u << k;
+        lw[k] = lower ? 1.0f - lod[k].f : lod[k].f;
+        tap[k] = tex_tap(quad_at(uv[0], k), quad_at(uv[1], k), wl, hl, wrap);
+        slot[k][0] = mg_slot(tb, tap[k].i00), slot[k][1] = mg_slot(tb, tap[k].i01), slot[k][2] = mg_slot(tb, tap[k].i10),
+        slot[k][3] = mg_slot(tb, tap[k].i11);
+      }
+      uint32_t n_used = 0u;
+      // ---- B2. the channels, ATTR_CHUNK at a time
+      for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+        const uint32_t nc = min(ATTR_CHUNK, C - c0);
+        float4 g[ATTR_CHUNK];
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (part != 0u) {
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+            if (i >= nc) break;
+            const float *p = gg + (size_t)(c0 + i) * rc.plane;
+            if (whole) {
+              g[i] = *reinterpret_cast<const float4 *>(p);
+            } else {
+#pragma unroll
+              for (int k = 0; k < 4; ++k)
+                if (part & (1u << k)) quad_at(g[i], k) = p[k];
+            }
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (!(part & (1u << k))) continue;
+          const float tx_ = tap[k].tx, ty_ = tap[k].ty;
+          const float w00 = ((1.0f - tx_) * (1.0f - ty_)) * lw[k], w01 = (tx_ * (1.0f - ty_)) * lw[k];
+          const float w10 = ((1.0f - tx_) * ty_) * lw[k], w11 = (tx_ * ty_) * lw[k];
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float gi = quad_at(g[i], k);
+              mg_add(tb, slot[k][0], gdst, tap[k].i00, C, c0 + i, i, w00 * gi);
+              mg_add(tb, slot[k][1], gdst, tap[k].i01, C, c0 + i, i, w01 * gi);
+              mg_add(tb, slot[k][2], gdst, tap[k].i10, C, c0 + i, i, w10 * gi);
+              mg_add(tb, slot[k][3], gdst, tap[k].i11, C, c0 + i, i, w11 * gi);
+            }
+        }
+        // ---- B3. the table's values of this chunk into memory: lanes in channel order within a texel (k_tex_grad's step 4)
+        __syncthreads();
+        n_used = tb.n_used;
+        for (uint32_t i = tid; i < n_used * ATTR_CHUNK; i += 256) {
+          const uint32_t s = tb.used[i / ATTR_CHUNK], e = i % ATTR_CHUNK;
+          const float v = tb.val[s * ATTR_CHUNK + e];
+          tb.val[s * ATTR_CHUNK + e] = 0.0f;
+          if (e < nc) global_add(gdst + (size_t)(tb.key[s] - 1u) * C + c0 + e, v);
+        }
+        __syncthreads();
+      }
+      // the level's keys go; every thread has read n_used before the chunk's last barrier
+      for (uint32_t i = tid; i < n_used; i += 256) tb.key[tb.used[i]] = 0u;
+      if (tid == 0) tb.n_used = 0u;
+      __syncthreads();
+    }
+  }
+}
+
+// ================================================================================================================
 // k_resolve8 — display()'s resolve (src/Render.cpp:61-62): cv::merge(planes 0,1,2) + convertTo(CV_8UC3) =
 // saturate_cast<uchar>(cvRound(v)): round half to even, clamp to [0,255]; NaN → 0.  4 pixels per thread: three 16-byte
 // plane reads → 12 output bytes (three dword stores).
@@ -5260,6 +5831,20 @@ void launch_antialias(const AntialiasArgs &a, hipStream_t s) { launch_pass<k_ant
 void launch_antialias_grad(const AntialiasArgs &a, hipStream_t s) { launch_pass<k_antialias_grad>(a, s); }
 void launch_tex(const TexArgs &a, hipStream_t s) { launch_pass<k_tex>(a, s); }
 void launch_tex_grad(const TexArgs &a, hipStream_t s) { launch_pass<k_tex_grad>(a, s); }
+void launch_interp_deriv(const InterpDerivArgs &a, hipStream_t s) { launch_pass<k_interp_deriv>(a, s); }
+void launch_tex_mip(const TexMipArgs &a, hipStream_t s) { launch_pass<k_tex_mip>(a, s); }
+void launch_tex_mip_grad(const TexMipArgs &a, hipStream_t s) { launch_pass<k_tex_mip_grad>(a, s); }
+// a workgroup per row of the level written (build) or of level 0 (fold), at most MIP_GRID of them striding over the rows
+constexpr uint32_t MIP_GRID = 8192;
+void launch_mip_build(const float *src, float *dst, uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h, uint32_t n_ch,
+                      uint32_t tex_frames, hipStream_t s) {
+  const uint32_t n_rows = tex_frames * dst_h;
+  hipLaunchKernelGGL(k_mip_build, dim3(std::min(n_rows, MIP_GRID)), dim3(256), 0, s, src, dst, src_w, src_h, dst_w, dst_h, n_ch, n_rows);
+}
+void launch_mip_fold(const float *gmip, float *gtex, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels,
+                     hipStream_t s) {
+  hipLaunchKernelGGL(k_mip_fold, dim3(std::min(tex_frames * tex_h, MIP_GRID)), dim3(256), 0, s, gmip, gtex, tex_w, tex_h, n_ch, tex_frames, n_levels);
+}
 
 bool raster_four_waves(const RenderArgs &a) { return a.n_frames * a.n_local_bands * a.tiles_x <= 4096u; }
 

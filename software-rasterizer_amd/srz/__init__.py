@@ -27,6 +27,8 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_motion_bytes", "srz_frameset_motion", "srz_frameset_interpolate_bytes", "srz_frameset_interpolate",
            "srz_frameset_interpolate_grad", "srz_frameset_position_grad", "srz_frameset_antialias", "srz_frameset_antialias_grad",
            "srz_frameset_texture", "srz_frameset_texture_grad",
+           "srz_texture_mip_levels", "srz_texture_mip_bytes", "srz_texture_mip_build", "srz_texture_mip_fold",
+           "srz_frameset_interpolate_deriv", "srz_frameset_texture_mip", "srz_frameset_texture_mip_grad",
            "srz_target_create", "srz_target_destroy", "srz_target_clear", "srz_target_draw", "srz_target_read", "srz_target_read_bgr8"]
 
 
@@ -88,6 +90,15 @@ def lib():
         L.srz_frameset_antialias_grad.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp]
         L.srz_frameset_texture.argtypes = abi.TEXTURE_ARGTYPES
         L.srz_frameset_texture_grad.argtypes = abi.TEXTURE_GRAD_ARGTYPES
+        L.srz_texture_mip_levels.argtypes = abi.MIP_LEVELS_ARGTYPES
+        L.srz_texture_mip_levels.restype = C.c_uint32
+        L.srz_texture_mip_bytes.argtypes = abi.MIP_BYTES_ARGTYPES
+        L.srz_texture_mip_bytes.restype = C.c_size_t
+        L.srz_texture_mip_build.argtypes = abi.MIP_BUILD_ARGTYPES
+        L.srz_texture_mip_fold.argtypes = abi.MIP_FOLD_ARGTYPES
+        L.srz_frameset_interpolate_deriv.argtypes = abi.INTERPOLATE_DERIV_ARGTYPES
+        L.srz_frameset_texture_mip.argtypes = abi.TEXTURE_MIP_ARGTYPES
+        L.srz_frameset_texture_mip_grad.argtypes = abi.TEXTURE_MIP_GRAD_ARGTYPES
         L.srz_frameset_update_shading.argtypes = [vp, vp, C.POINTER(abi.SrzFrame), C.c_int]
         L.srz_sceneset_update.argtypes = [vp, vp, C.POINTER(abi.SrzSceneFrame), C.c_int]
         L.srz_frameset_resolve8.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
@@ -145,6 +156,18 @@ def _stream(stream):
 
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def mip_levels(tex_w, tex_h):
+    """the levels of the mip pyramid of a tex_w x tex_h texture, level 0 included: halving goes on while every extent is even or 1
+    (include/srz.h); 0 for an extent of 0 or above abi.TEX_MAX_SIZE.  No GPU involved."""
+    return int(lib().srz_texture_mip_levels(tex_w, tex_h))
+
+
+def mip_bytes(tex_w, tex_h, n_ch, tex_frames, n_levels):
+    """bytes of the levels 1 .. n_levels - 1, level-major, each [tex_frames][h_l][w_l][n_ch] float32; 0 for n_levels <= 1 or an
+    argument out of range.  No GPU involved."""
+    return int(lib().srz_texture_mip_bytes(tex_w, tex_h, n_ch, tex_frames, n_levels))
 
 
 class FrameSet:
@@ -289,6 +312,34 @@ class FrameSet:
         self.ctx._check(lib().srz_frameset_texture_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_uv_ptr), C.c_void_p(d_gout_ptr),
                                                         C.c_void_p(d_tex_ptr or None), tex_w, tex_h, n_ch, tex_frames, mode,
                                                         C.c_void_p(d_gtex_ptr or None), C.c_void_p(d_guv_ptr or None), flags, _stream(stream)))
+
+    def interpolate_deriv(self, d_vis_ptr, d_attr_ptr, n_ch, attr_frames, attr_tris, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """the screen-space derivatives of the attributes interpolate takes (n_ch <= abi.ATTR_MAX_CH // 2), from the set's own
+        positions: d_out [frame][2 * n_ch][local_rows][width], interpolate_bytes(2 * n_ch) bytes, plane 2 ch d/dx and plane 2 ch + 1
+        d/dy of channel ch per one-pixel step, constants of each pixel's owner (include/srz.h).  Nobody's pixels as interpolate.
+        Asynchronous."""
+        self.ctx._check(lib().srz_frameset_interpolate_deriv(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_attr_ptr), n_ch, attr_frames,
+                                                             attr_tris, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def texture_mip(self, d_vis_ptr, d_uv_ptr, d_uvd_ptr, d_tex_ptr, tex_w, tex_h, n_ch, tex_frames, mode, d_mip_ptr, n_levels, d_out_ptr,
+                    out_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """texture() with a mip pyramid: the trilinear lookup over the n_levels levels of d_tex (level 0) and d_mip (Context.mip_build's
+        levels 1 ..), the level of each pixel chosen from the derivative planes d_uvd [frame][4][local_rows][width] — ux, uy, vx, vy,
+        interpolate_deriv's of the two-channel uv attribute (include/srz.h states the rule).  n_levels == 1: texture()'s output, d_uvd
+        and d_mip may be None.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_texture_mip(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_uv_ptr), C.c_void_p(d_uvd_ptr or None),
+                                                       C.c_void_p(d_tex_ptr), tex_w, tex_h, n_ch, tex_frames, mode, C.c_void_p(d_mip_ptr or None),
+                                                       n_levels, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def texture_mip_grad(self, d_vis_ptr, d_uv_ptr, d_uvd_ptr, d_gout_ptr, d_tex_ptr, d_mip_ptr, tex_w, tex_h, n_ch, tex_frames, mode, n_levels,
+                         d_gtex_ptr, d_gmip_ptr, d_guv_ptr, flags=abi.FUSED_CLEAR, stream=None):
+        """the backward of texture_mip, the level held fixed: d_gout → ADDED into d_gtex (level 0) and d_gmip (the pyramid's layout; the
+        two come together when n_levels > 1; float atomics: not bit-reproducible; Context.mip_fold then folds d_gmip into d_gtex) and /
+        or written to d_guv [frame][2][local_rows][width] (deterministic; needs d_tex_ptr and d_mip_ptr).  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_texture_mip_grad(
+            self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_uv_ptr), C.c_void_p(d_uvd_ptr or None), C.c_void_p(d_gout_ptr),
+            C.c_void_p(d_tex_ptr or None), C.c_void_p(d_mip_ptr or None), tex_w, tex_h, n_ch, tex_frames, mode, n_levels,
+            C.c_void_p(d_gtex_ptr or None), C.c_void_p(d_gmip_ptr or None), C.c_void_p(d_guv_ptr or None), flags, _stream(stream)))
 
     def update_shading(self, frames):
         """new eye, ka, ks, p, kh, kn, lights, flags and batch shaders / textures for a set made from abi.Frame's, triangles untouched
@@ -491,6 +542,19 @@ class Context:
         h, w, c = a.shape
         assert c == 3
         self._check(lib().srz_texture_upload(self.h, tex_id, a.ctypes.data, w, h, w * 3))
+
+    def mip_build(self, d_tex_ptr, tex_w, tex_h, n_ch, tex_frames, n_levels, d_mip_ptr, mip_bytes, stream=None):
+        """the levels 1 .. n_levels - 1 of the float32 texture [tex_frames][tex_h][tex_w][n_ch] at d_tex_ptr → d_mip_ptr (srz.mip_bytes
+        bytes, level-major), each level the box filter of the level above it, deterministic (include/srz.h).  n_levels == 1 launches
+        nothing.  Asynchronous."""
+        self._check(lib().srz_texture_mip_build(self.h, C.c_void_p(d_tex_ptr), tex_w, tex_h, n_ch, tex_frames, n_levels, C.c_void_p(d_mip_ptr),
+                                                mip_bytes, _stream(stream)))
+
+    def mip_fold(self, d_gmip_ptr, mip_bytes, tex_w, tex_h, n_ch, tex_frames, n_levels, d_gtex_ptr, stream=None):
+        """the backward of mip_build: the gradient pyramid at d_gmip_ptr folded into the level-0 gradient at d_gtex_ptr (added into, one
+        fma per element; a gather, deterministic).  Asynchronous."""
+        self._check(lib().srz_texture_mip_fold(self.h, C.c_void_p(d_gmip_ptr), mip_bytes, tex_w, tex_h, n_ch, tex_frames, n_levels,
+                                               C.c_void_p(d_gtex_ptr), _stream(stream)))
 
     def mesh_upload(self, mesh_id, verts8, faces):
         """verts8: (nV,8) float32 [pos3 nrm3 uv2]; faces: (nF,3) uint32."""

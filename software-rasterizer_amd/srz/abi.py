@@ -27,6 +27,16 @@ TEXTURE_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, 
                     C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
 TEXTURE_GRAD_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                          C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+TEX_MAX_LEVELS = 15  # the most levels of a mip pyramid, level 0 included (SRZ_TEX_MAX_LEVELS)
+# the prototypes of the mip entry points (argtypes; the two helpers return uint32 / size_t, the others int), set by srz.lib()
+_vp, _u32 = C.c_void_p, C.c_uint32
+MIP_LEVELS_ARGTYPES = [_u32, _u32]
+MIP_BYTES_ARGTYPES = [_u32, _u32, _u32, _u32, _u32]
+MIP_BUILD_ARGTYPES = [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, C.c_size_t, _vp]
+MIP_FOLD_ARGTYPES = [_vp, _vp, C.c_size_t, _u32, _u32, _u32, _u32, _u32, _vp, _vp]
+INTERPOLATE_DERIV_ARGTYPES = [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
+TEXTURE_MIP_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, C.c_size_t, _u32, _vp]
+TEXTURE_MIP_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp]
 
 # numpy view of srz_tri (96 B): pos[3][3], nrm[3][3], uv[3][2]
 TRI_DTYPE = np.dtype([("pos", "<f4", (3, 3)), ("nrm", "<f4", (3, 3)), ("uv", "<f4", (3, 2))])

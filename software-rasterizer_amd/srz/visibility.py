@@ -416,3 +416,139 @@ def texture(fs, vis, tex, uv, wrap=False, stream=None):
     texture(fs, vis, tex, interpolate(fs, vis, uv_attr)) backpropagates to tex and to uv_attr.  Backward is one texture_grad call that
     asks only for the outputs some input needs.  stream: a raw stream handle, None = torch's current stream."""
     return _Texture.apply(tex, uv, fs, vis, wrap, stream)
+
+
+def interpolate_deriv(fs, vis, attr, stream=None):
+    """the screen-space derivatives of interpolate(fs, vis, attr): attr as interpolate takes it with C <= abi.ATTR_MAX_CH // 2 →
+    [n_frames, 2 C, rows, W] float32, plane 2 ch the change of channel ch per one-pixel step in x, plane 2 ch + 1 in y — constants of
+    each pixel's owner, from the set's own positions (FrameSet.interpolate_deriv); zeros where nobody owns the pixel.  For a [T, 3, 2]
+    uv attribute these are the planes ux, uy, vx, vy texture_mip takes.  Not differentiable: the planes only select a mip level.
+    stream: a raw stream handle, None = torch's current stream."""
+    attr = attr.detach().contiguous()
+    attr_frames, tris, n_ch = _attr_dims(fs, attr)
+    if n_ch > abi.ATTR_MAX_CH // 2:
+        raise ValueError(f"interpolate_deriv: {n_ch} channels; at most {abi.ATTR_MAX_CH // 2} are supported")
+    out = torch.empty(fs.interpolate_shape(2 * n_ch), dtype=torch.float32, device=attr.device)
+    fs.interpolate_deriv(vis.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris, out.data_ptr(), fs.interpolate_bytes(2 * n_ch), abi.FUSED_CLEAR,
+                         _stream_ptr(stream))
+    return out
+
+
+def _mip_dims(tex_shape, n_levels):
+    """(tex_frames, h, w, n_ch, n_levels) of a texture shape [H, W, C] or [frames, H, W, C]; n_levels None: every level there is"""
+    from . import mip_levels
+    tex_frames = tex_shape[0] if len(tex_shape) == 4 else 1
+    h, w, n_ch = tex_shape[-3:]
+    most = mip_levels(w, h)
+    n_levels = most if n_levels is None else n_levels
+    if most == 0 or not 1 <= n_levels <= most:
+        raise ValueError(f"mip: a {w} x {h} texture has {most} levels, {n_levels} asked for")
+    return tex_frames, h, w, n_ch, n_levels
+
+
+def mip_build(ctx_or_fs, tex, n_levels=None, stream=None):
+    """the mip pyramid of a CUDA float32 texture [H, W, C] or [frames, H, W, C]: the levels 1 .. n_levels - 1 (None: every level
+    srz.mip_levels counts) as ONE flat float32 tensor, level-major (mip_views takes it apart); each level the box filter of the level
+    above it, deterministic (Context.mip_build).  ctx_or_fs: the Context, or a FrameSet of it."""
+    from . import mip_bytes
+    ctx = getattr(ctx_or_fs, "ctx", ctx_or_fs)
+    if tex.dtype != torch.float32 or not tex.is_cuda or tex.dim() not in (3, 4):
+        raise ValueError(f"mip_build: tex must be a CUDA float32 tensor [H, W, C] or [frames, H, W, C], got {tuple(tex.shape)} {tex.dtype}")
+    tex = tex.contiguous()
+    tex_frames, h, w, n_ch, n_levels = _mip_dims(tuple(tex.shape), n_levels)
+    nbytes = mip_bytes(w, h, n_ch, tex_frames, n_levels)
+    mip = torch.empty((nbytes // 4,), dtype=torch.float32, device=tex.device)
+    if n_levels > 1:
+        ctx.mip_build(tex.data_ptr(), w, h, n_ch, tex_frames, n_levels, mip.data_ptr(), nbytes, _stream_ptr(stream))
+    return mip
+
+
+def mip_views(mip, tex_shape, n_levels=None):
+    """the levels 1 .. n_levels - 1 of a flat pyramid (mip_build's, or a gradient pyramid) as views [h_l, w_l, C] or
+    [frames, h_l, w_l, C], in level order; tex_shape: the shape of level 0"""
+    tex_frames, h, w, n_ch, n_levels = _mip_dims(tuple(tex_shape), n_levels)
+    views, off = [], 0
+    for l in range(1, n_levels):
+        hl, wl = max(1, h >> l), max(1, w >> l)
+        n = tex_frames * hl * wl * n_ch
+        views.append(mip[off:off + n].view((tex_frames, hl, wl, n_ch) if len(tex_shape) == 4 else (hl, wl, n_ch)))
+        off += n
+    return views
+
+
+def _uvd_arg(fs, uvd, n_levels):
+    if n_levels == 1 and uvd is None:
+        return None
+    if uvd is None or uvd.dtype != torch.float32 or not uvd.is_cuda or tuple(uvd.shape) != tuple(fs.interpolate_shape(4)):
+        raise ValueError(f"texture_mip: uvd must be a CUDA float32 tensor {fs.interpolate_shape(4)}")
+    return uvd.detach().contiguous()
+
+
+def texture_mip_grad(fs, vis, tex, uv, uvd, gout, wrap=False, n_levels=None, mip=None, want_gtex=True, want_guv=True, fold=True, stream=None):
+    """the backward of texture_mip(fs, vis, tex, uv, uvd, wrap, n_levels) by one FrameSet.texture_mip_grad call, the level held fixed:
+    gout [n_frames, C, rows, W] → (gtex, guv), each None when not wanted (not both).  gtex has tex's shape: the adds to level 0 and,
+    with fold (one Context.mip_fold call), the gradient pyramid folded into it — float atomics into zeros, not bit-reproducible;
+    fold=False returns (gtex, gmip, guv) with the level-0 adds and the flat gradient pyramid apart.  guv is deterministic.  mip: the
+    pyramid mip_build made of tex (built here when guv needs it and none is given)."""
+    if not want_gtex and not want_guv:
+        raise ValueError("texture_mip_grad: neither gtex nor guv is asked for")
+    from . import mip_bytes
+    tex, uv, gout = tex.detach().contiguous(), _uv_arg(fs, uv), gout.contiguous()
+    tex_frames, h, w, n_ch = _tex_dims(fs, tex)
+    n_levels = _mip_dims(tuple(tex.shape), n_levels)[4]
+    uvd = _uvd_arg(fs, uvd, n_levels)
+    if tuple(gout.shape) != tuple(fs.interpolate_shape(n_ch)) or gout.dtype != torch.float32:
+        raise ValueError(f"texture_mip_grad: gout must be float32 {fs.interpolate_shape(n_ch)}, got {tuple(gout.shape)} {gout.dtype}")
+    s = _stream_ptr(stream)
+    nbytes = mip_bytes(w, h, n_ch, tex_frames, n_levels)
+    if want_guv and n_levels > 1 and mip is None:
+        mip = mip_build(fs, tex, n_levels, stream)
+    gtex = torch.zeros_like(tex) if want_gtex else None
+    gmip = torch.zeros((nbytes // 4,), dtype=torch.float32, device=tex.device) if want_gtex and n_levels > 1 else None
+    guv = torch.empty_like(uv) if want_guv else None
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    fs.texture_mip_grad(vis.data_ptr(), uv.data_ptr(), ptr(uvd), gout.data_ptr(), tex.data_ptr(), ptr(mip) if n_levels > 1 else None, w, h, n_ch,
+                        tex_frames, abi.TEX_WRAP if wrap else abi.TEX_CLAMP, n_levels, ptr(gtex), ptr(gmip), ptr(guv), abi.FUSED_CLEAR, s)
+    if not fold:
+        return gtex, gmip, guv
+    if gmip is not None:
+        fs.ctx.mip_fold(gmip.data_ptr(), nbytes, w, h, n_ch, tex_frames, n_levels, gtex.data_ptr(), s)
+    return gtex, guv
+
+
+class _TextureMip(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tex, uv, fs, vis, uvd, wrap, n_levels, stream):
+        tex, uv = tex.contiguous(), _uv_arg(fs, uv)
+        tex_frames, h, w, n_ch = _tex_dims(fs, tex)
+        n_levels = _mip_dims(tuple(tex.shape), n_levels)[4]
+        uvd = _uvd_arg(fs, uvd, n_levels)
+        mip = mip_build(fs, tex, n_levels, stream) if n_levels > 1 else None
+        out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=tex.device)
+        fs.texture_mip(vis.data_ptr(), uv.data_ptr(), uvd.data_ptr() if uvd is not None else None, tex.data_ptr(), w, h, n_ch, tex_frames,
+                       abi.TEX_WRAP if wrap else abi.TEX_CLAMP, mip.data_ptr() if mip is not None else None, n_levels, out.data_ptr(),
+                       fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR, _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.wrap, ctx.n_levels, ctx.stream, ctx.uvd, ctx.mip = fs, vis, wrap, n_levels, stream, uvd, mip
+        ctx.save_for_backward(tex, uv)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        tex, uv = ctx.saved_tensors
+        need_tex, need_uv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gtex = guv = None
+        if need_tex or need_uv:  # one texture_mip_grad call, asking only for what is needed, then one fold into tex.grad
+            gtex, guv = texture_mip_grad(ctx.fs, ctx.vis, tex, uv, ctx.uvd, gout, ctx.wrap, ctx.n_levels, ctx.mip, need_tex, need_uv, True,
+                                         ctx.stream)
+        return gtex, guv, None, None, None, None, None, None
+
+
+def texture_mip(fs, vis, tex, uv, uvd, wrap=False, n_levels=None, stream=None):
+    """texture(fs, vis, tex, uv, wrap) with a mip pyramid: the trilinear lookup whose level each pixel takes from uvd
+    [n_frames, 4, rows, W] — interpolate_deriv(fs, vis, uv_attr) of the [T, 3, 2] attribute uv came from (ux, uy, vx, vy) — by the
+    piecewise-linear rule include/srz.h states; n_levels None: every level srz.mip_levels(W, H) counts; 1: texture() itself (uvd may
+    be None).  The forward builds the pyramid (mip_build) and samples (FrameSet.texture_mip).  Differentiable with respect to tex
+    (float atomics per level, then mip_fold: tex.grad is not bit-reproducible between runs) and to uv (deterministic); the level is
+    held fixed: uvd gets no gradient.  Backward is one texture_mip_grad call that asks only for the outputs some input needs, and one
+    fold when tex needs a gradient.  stream: a raw stream handle, None = torch's current stream."""
+    return _TextureMip.apply(tex, uv, fs, vis, uvd, wrap, n_levels, stream)
