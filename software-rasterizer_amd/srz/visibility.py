@@ -343,7 +343,9 @@ def antialias(fs, vis, color, pos=None, stream=None):
     when pos is given, to the triangles' screen positions: pos is the never-read graph handle interpolate_geo takes,
     [n_frames, T, 3, 3], and pos.grad receives the SILHOUETTE term (its z column is zero; a sum of float atomics: not
     bit-reproducible between runs).  antialias(fs, vis, interpolate_geo(fs, vis, attr, pos), pos) is the full chain: pos.grad is then
-    the sum of the interior and the silhouette term.  Backward is one antialias_grad call that asks only for the outputs some input
+    the sum of the interior and the silhouette term — together the derivative, to first order, of the loss over frames rendered
+    again while no pixel changes its owner; across an owner change the antialiased image itself jumps (DESIGN.md has both
+    measured).  Backward is one antialias_grad call that asks only for the outputs some input
     needs, and no call when none does.  Needs an unsharded context.  stream: a raw stream handle, None = torch's current stream."""
     return _Antialias.apply(color, pos, fs, vis, stream)
 
