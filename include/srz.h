@@ -217,9 +217,22 @@ int srz_texture_upload(srz_ctx *ctx, int tex_id, const uint8_t *bgr, int w, int 
  * is uploaded anew the set must be destroyed, or at least never rendered, shaded or passed to srz_frameset_stats again (every such
  * call runs the vertex stage over the freed buffers): srz_sceneset_update refuses it with SRZ_E_INVALID whatever the new mesh's
  * size, which is the one thing left to do with it besides srz_frameset_destroy.  Renders of the set still running on a stream of the
- * caller's must have finished before the upload.  srz_draw_scene handles all of this itself: it rebuilds its set. */
+ * caller's must have finished before the upload.  srz_draw_scene handles all of this itself: it rebuilds its set.
+ * The upload also builds, on the host by a counting sort, the slot's CORNER LISTS for srz_sceneset_vertex_grad's gather —
+ * corner_off[n_verts + 1] and corners[3 * n_faces]: vertex v is named by the corners corners[corner_off[v] .. corner_off[v + 1]), each
+ * 3 * face + k, in increasing order — and uploads them beside the faces; they are freed with the slot. */
 int srz_mesh_upload(srz_ctx *ctx, int mesh_id, const srz_vertex *verts, uint32_t n_verts, const uint32_t *faces,
                     uint32_t n_faces);
+/* NEW VERTICES for a slot that holds a mesh, IN PLACE, FROM DEVICE MEMORY: d_verts is a device pointer to n_verts 32-byte srz_vertex
+ * records (a [n_verts][8] float32 array: the caller updates normals and uv as they see fit), 4-byte aligned; n_verts must equal the
+ * slot's count.  ONE asynchronous device-to-device copy into the slot's existing vertex buffer on `stream` (NULL: the ctx's own
+ * stream, SRZ_STREAM_NULL: HIP's null stream).  The face list, the corner lists, the buffers' addresses and the slot's upload
+ * counter do not change: every sceneset that draws the slot stays valid — srz_sceneset_update goes on accepting it — and transforms
+ * the new vertices from its next vertex stage on (the next render, srz_frameset_positions or pass that runs the stage).  Ordering
+ * against renders and passes on other streams is the caller's, as for srz_sceneset_update; the tile-list pool follows the new demand
+ * as it does after a matrix update.  SRZ_E_INVALID, nothing copied, for: a null ctx; a mesh_id outside 0..255 or a slot that holds no
+ * mesh; a null or misaligned d_verts; n_verts other than the slot's count. */
+int srz_mesh_update(srz_ctx *ctx, int mesh_id, const srz_vertex *d_verts, uint32_t n_verts, void *stream);
 
 /* ---- draw = TraditionalRasterizer::draw(TRIANGLES) for one scene ----------------------
  * z/c0/c1/c2: W*H floats each, in/out (m_zBuffer, m_channels[0..2]); draw never clears unless
@@ -662,6 +675,53 @@ int srz_frameset_resolve8(srz_ctx *ctx, const srz_frameset *fs, const void *d_pl
  * on the context's own stream (ordered against srz_target_draw / renders submitted there, no host synchronisation);
  * renders of this set submitted on a caller-provided stream must be ordered against it by the caller. */
 int srz_sceneset_update(srz_ctx *ctx, srz_frameset *fs, const srz_scene_frame *frames, int n_frames);
+
+/* ---- the differentiable vertex stage: from the gradient of the SCREEN positions to the mesh and the matrices --------------------
+ * srz_frameset_position_grad and srz_frameset_antialias_grad end at d_gpos, nine floats per triangle and frame.  The two calls below
+ * close the chain for a sceneset: the set's own positions read out (the values the `pos` graph handle of the torch layer stands
+ * for), and the backward of the vertex stage, to what srz_mesh_upload / srz_mesh_update and srz_sceneset_create / _update are given.
+ *
+ * THE SET'S OWN POSITIONS.  d_pos: [n_frames][pos_tris][9] float32 in the dense stream's order (ax ay z0 bx by z1 cx cy z2), 4-byte
+ * aligned, pos_bytes at least n_frames * pos_tris * 36; the triangle index is the visibility buffer's (frame-local); pos_tris at
+ * least every frame's triangle count; the triangles behind a frame's last are written as +0.  For a frameset and a sceneset alike: a
+ * sceneset runs its vertex stage first, as srz_frameset_position_grad does.  The floats are bit-equal to what the rasteriser reads,
+ * whatever the ctx's shard.  Asynchronous on `stream` with the usual semantics.  SRZ_E_INVALID, nothing launched and the output
+ * untouched, for: a null ctx, set or d_pos; pos_bytes below the size; a misaligned pointer; pos_tris below a frame's count. */
+int srz_frameset_positions(srz_ctx *ctx, srz_frameset *fs, uint32_t pos_tris, float *d_pos, size_t pos_bytes, void *stream);
+/* THE BACKWARD OF THE VERTEX STAGE for one mesh slot of a sceneset.  d_gpos: [n_frames][pos_tris][9] float32, what
+ * srz_frameset_position_grad and srz_frameset_antialias_grad add into (read only here).  d_gverts: [n_frames][n_verts(mesh_id)][3]
+ * float32, the gradient with respect to srz_vertex::pos.  d_gdraw: [n_frames][draw_stride][18] float32, draw_stride at least every
+ * frame's draw count; per draw the 16 gradients of ndc_mvp in its own column-major order, then that of zscale, then that of zoffset
+ * (a frame's two constants: sum them over its draws).  At least one of the two outputs is non-null; all pointers 4-byte aligned.
+ * Only the draws that name mesh_id take part: call once per mesh that is fitted (d_gdraw may be shared between the calls).
+ * THE RULE, in float32, nothing fused but the written fmaf, IEEE divisions.  For frame f, vertex v, and each draw j of frame f that
+ * names mesh_id, in draw order, with `first` the draw's first frame-local triangle, m and zs the draw's ndc_mvp and zscale, and
+ * list(v) the corners (face, k) of the slot's corner list of v, in list order (srz_mesh_upload):
+ *   GX = GY = GZ = +0;  for (face, k) in list(v):  p = d_gpos[f][first + face] + 3 k;  GX = GX + p[0];  GY = GY + p[1];  GZ = GZ + p[2]
+ *   GX == 0 && GY == 0 && GZ == 0:  this draw contributes nothing for v                      (a NaN is not 0 and goes on)
+ *   (x, y, z) = verts[v].pos;   r_i = (m[i] * x + m[4 + i] * y) + (m[8 + i] * z + m[12 + i]),  i = 0..3   (the vertex stage's own expression)
+ *   X = r0 / r3;  Y = r1 / r3;  Q = r2 / r3;  inv = 1.0f / r3;  gq = GZ * zs
+ *   g0 = GX * inv;  g1 = GY * inv;  g2 = gq * inv;  s = gq * Q;  s = fmaf(GY, Y, s);  s = fmaf(GX, X, s);  g3 = (-s) * inv
+ *   c = 0..2:  t = m[4 c] * g0;  t = fmaf(m[4 c + 1], g1, t);  t = fmaf(m[4 c + 2], g2, t);  t = fmaf(m[4 c + 3], g3, t);
+ *              d_gverts[f][v][c] = d_gverts[f][v][c] + t
+ *   d_gdraw[f][j][4 c + i] += g_i * (x, y, z)[c]  (c = 3: g_i);   d_gdraw[f][j][16] += GZ * Q;   d_gdraw[f][j][17] += GZ
+ * d_gverts is a GATHER: the one thread that owns (f, v) adds once per contributing draw, in draw order — DETERMINISTIC, bit for bit;
+ * an element with no contributing draw is LEFT UNTOUCHED.  The skip is what keeps hidden, culled and non-finite triangles, whose
+ * d_gpos is zero, from poisoning a vertex they share (a vertex on the camera plane, r3 == 0, would otherwise yield 0 * inf).
+ * d_gdraw is ADDED into, a sum over the draw's contributing vertices IN AN UNSPECIFIED ORDER AND TREE: not bit-reproducible; with n
+ * contributing vertices an element lies within n 2^-24 / (1 - n 2^-24) * sum |term| of the exact sum of its float32 terms, and an
+ * element with one term is exact; draws of other slots and the words behind a frame's last draw are untouched.  The adds are
+ * hardware float atomics, one per workgroup of 256 vertices, draw and value: d_gdraw must be ordinary (coarse-grained) device memory.
+ * Non-finite values propagate as IEEE has them; no input value makes the pass read or write outside its buffers.  The pass reads no
+ * visibility buffer and no triangle, and is linear in d_gpos apart from the skip: on a sharded ctx each rank transforms its own
+ * partial d_gpos.  The vertices and matrices are what the device holds when the pass runs: order it against srz_mesh_update and
+ * srz_sceneset_update as a render is ordered.  Asynchronous on `stream`.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set or d_gpos; a set that is not a sceneset; a mesh_id
+ * the set does not draw, or whose slot was uploaded anew (srz_mesh_upload) since the set was created; both outputs null; pos_tris
+ * below a frame's triangle count; with d_gdraw, draw_stride below a frame's draw count; a misaligned pointer; an output that
+ * overlaps d_gpos or the other output. */
+int srz_sceneset_vertex_grad(srz_ctx *ctx, srz_frameset *fs, int mesh_id, const float *d_gpos, uint32_t pos_tris, float *d_gverts,
+                             float *d_gdraw, uint32_t draw_stride, void *stream);
 
 /* ---- multi-GPU exchange: the band shards of every rank → full row-major frames on every rank ------------------------
  * One process per GPU.  Rank 0 makes an id (srz_comm_unique_id), the host program hands the 128 bytes to every rank

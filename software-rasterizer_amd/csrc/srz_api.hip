@@ -51,6 +51,9 @@ struct srz_ctx {
   struct MeshSlot {
     srz_vertex *d_verts = nullptr;
     uint32_t *d_faces = nullptr;
+    // the corner lists of srz_sceneset_vertex_grad's gather, one block: corner_off [n_verts + 1], then corners [3 * n_faces] — vertex v is
+    // named by the corners corners[corner_off[v] .. corner_off[v + 1]), each 3 * face + k, increasing
+    uint32_t *d_corner_off = nullptr;
     uint32_t n_verts = 0, n_faces = 0;
     uint64_t upload = 0; // which srz_mesh_upload of this ctx filled the slot (1, 2, ...): a freed buffer's address can come back, this cannot
   } mesh[MAX_MESH];
@@ -977,7 +980,7 @@ void srz_destroy(srz_ctx *ctx) {
   for (auto &ep : ctx->ev_used) ctx->ev_pool.push_back(ep);
   for (auto &ep : ctx->ev_pool) (void)hipEventDestroy(ep.t0), (void)hipEventDestroy(ep.t1), (void)hipEventDestroy(ep.t2), (void)hipEventDestroy(ep.t3);
   for (int i = 0; i < MAX_TEX; ++i) (void)hipFree(ctx->d_texmem[i]);
-  for (int i = 0; i < MAX_MESH; ++i) (void)hipFree(ctx->mesh[i].d_verts), (void)hipFree(ctx->mesh[i].d_faces);
+  for (int i = 0; i < MAX_MESH; ++i) (void)hipFree(ctx->mesh[i].d_verts), (void)hipFree(ctx->mesh[i].d_faces), (void)hipFree(ctx->mesh[i].d_corner_off);
   (void)hipFree(ctx->d_stats);
   destroy_side(ctx->stream2, ctx->ev_fork, ctx->ev_join);
   destroy_side(ctx->stream3, ctx->ev_piece);
@@ -1263,19 +1266,45 @@ int srz_mesh_upload(srz_ctx *ctx, int mesh_id, const srz_vertex *verts, uint32_t
   for (uint32_t i = 0; i < 3u * n_faces; ++i)
     if (faces[i] >= n_verts) return fail(ctx, SRZ_E_INVALID, "srz_mesh_upload: face index out of range");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // the corner lists, by a counting sort on the vertex: stable, so a vertex's corners come in increasing order of 3 * face + k
+  std::vector<uint32_t> lists((size_t)n_verts + 1 + 3 * (size_t)n_faces, 0u);
+  uint32_t *off = lists.data(), *corners = off + n_verts + 1;
+  for (uint32_t i = 0; i < 3u * n_faces; ++i) ++off[faces[i] + 1];
+  for (uint32_t v = 0; v < n_verts; ++v) off[v + 1] += off[v];
+  {
+    std::vector<uint32_t> at(off, off + n_verts);
+    for (uint32_t i = 0; i < 3u * n_faces; ++i) corners[at[faces[i]]++] = i;
+  }
   srz_ctx::MeshSlot m;
   HIP_TRY(ctx, hipMalloc(&m.d_verts, sizeof(srz_vertex) * n_verts));
   hipError_t e = hipMalloc(&m.d_faces, sizeof(uint32_t) * 3 * (n_faces ? n_faces : 1));
+  if (e == hipSuccess) e = hipMalloc(&m.d_corner_off, sizeof(uint32_t) * lists.size());
   if (e == hipSuccess) e = hipMemcpy(m.d_verts, verts, sizeof(srz_vertex) * n_verts, hipMemcpyHostToDevice);
   if (e == hipSuccess && n_faces) e = hipMemcpy(m.d_faces, faces, sizeof(uint32_t) * 3 * n_faces, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(m.d_corner_off, lists.data(), sizeof(uint32_t) * lists.size(), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    (void)hipFree(m.d_verts), (void)hipFree(m.d_faces);
+    (void)hipFree(m.d_verts), (void)hipFree(m.d_faces), (void)hipFree(m.d_corner_off);
     return fail(ctx, SRZ_E_NOMEM, std::string("srz_mesh_upload: ") + hipGetErrorString(e));
   }
   m.n_verts = n_verts, m.n_faces = n_faces, m.upload = ++ctx->mesh_uploads;
   (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(ctx->mesh[mesh_id].d_verts), (void)hipFree(ctx->mesh[mesh_id].d_faces);
+  (void)hipFree(ctx->mesh[mesh_id].d_verts), (void)hipFree(ctx->mesh[mesh_id].d_faces), (void)hipFree(ctx->mesh[mesh_id].d_corner_off);
   ctx->mesh[mesh_id] = m;
+  return SRZ_OK;
+}
+
+int srz_mesh_update(srz_ctx *ctx, int mesh_id, const srz_vertex *d_verts, uint32_t n_verts, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_mesh_update");
+  if (mesh_id < 0 || mesh_id >= MAX_MESH || !ctx->mesh[mesh_id].d_verts) return fail(ctx, SRZ_E_INVALID, fn + ": no mesh in that slot");
+  if (!d_verts) return fail(ctx, SRZ_E_INVALID, fn + ": null vertices");
+  const srz_ctx::MeshSlot &m = ctx->mesh[mesh_id];
+  if (n_verts != m.n_verts) return fail(ctx, SRZ_E_INVALID, fn + ": n_verts is not the slot's vertex count");
+  if (!aligned<4>({d_verts})) return fail(ctx, SRZ_E_INVALID, fn + ": the vertices must be 4-byte aligned");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // (the slot's own buffer, its address, the faces, the corner lists and the upload counter stay: every sceneset that draws the slot
+  // remains valid and transforms the new vertices at its next vertex stage)
+  HIP_TRY(ctx, hipMemcpyAsync(m.d_verts, d_verts, sizeof(srz_vertex) * n_verts, hipMemcpyDeviceToDevice, pick_stream(ctx, stream)));
   return SRZ_OK;
 }
 
@@ -1661,6 +1690,62 @@ int srz_frameset_position_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis
   a.vis_stride = 4ull * plane, a.frame_stride = 2ull * plane, a.gz_stride = plane, a.gpos_stride = (uint64_t)pos_tris * TRI_POS_F;
   a.flags_or = flags;
   launch_pos_grad(a, s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_positions(srz_ctx *ctx, srz_frameset *fs, uint32_t pos_tris, float *d_pos, size_t pos_bytes, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_positions");
+  if (!fs || !d_pos) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / output");
+  if (int rc = check_tri_count(ctx, fs, fn, "pos_tris", pos_tris)) return rc;
+  if (pos_bytes < (size_t)fs->n_frames * pos_tris * TRI_POS_F * sizeof(float)) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
+  if (!aligned<4>({d_pos})) return fail(ctx, SRZ_E_INVALID, fn + ": the positions must be 4-byte aligned");
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, PASS_VERTEX, &s)) return rc;
+  struct {
+    const float *tri_pos;
+    uint32_t pos_stride;
+  } p;
+  fill_positions(p, fs);
+  launch_positions(fs->d_frames, (uint32_t)fs->n_frames, p.tri_pos, p.pos_stride, d_pos, pos_tris, s);
+  return end_pass(ctx);
+}
+
+int srz_sceneset_vertex_grad(srz_ctx *ctx, srz_frameset *fs, int mesh_id, const float *d_gpos, uint32_t pos_tris, float *d_gverts,
+                             float *d_gdraw, uint32_t draw_stride, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_sceneset_vertex_grad");
+  if (!fs || !fs->d_draws) return fail(ctx, SRZ_E_INVALID, fn + ": not a sceneset");
+  if (!d_gpos) return fail(ctx, SRZ_E_INVALID, fn + ": null position gradient");
+  if (!d_gverts && !d_gdraw) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gverts nor d_gdraw is asked for");
+  if (mesh_id < 0 || mesh_id >= MAX_MESH || !ctx->mesh[mesh_id].d_verts) return fail(ctx, SRZ_E_INVALID, fn + ": no mesh in that slot");
+  const srz_ctx::MeshSlot &m = ctx->mesh[mesh_id];
+  bool drawn = false;
+  for (size_t di = 0; di < fs->h_draw_mesh.size(); ++di) {
+    if (fs->h_draw_mesh[di] != mesh_id) continue;
+    drawn = true;
+    // (as srz_sceneset_update: the slot must still hold the upload the set's draws point into)
+    if (m.upload != fs->h_draw_upload[di]) return fail(ctx, SRZ_E_INVALID, fn + ": the slot was uploaded anew since the set was created");
+  }
+  if (!drawn) return fail(ctx, SRZ_E_INVALID, fn + ": the set draws no mesh of that slot");
+  if (int rc = check_tri_count(ctx, fs, fn, "pos_tris", pos_tris)) return rc;
+  if (d_gdraw)
+    for (const FrameDesc &d : fs->h_frames)
+      if (d.n_batches > draw_stride) return fail(ctx, SRZ_E_INVALID, fn + ": draw_stride is below a frame's draw count");
+  if (!aligned<4>({d_gpos, d_gverts, d_gdraw})) return fail(ctx, SRZ_E_INVALID, fn + ": the buffers must be 4-byte aligned");
+  const size_t gpos_bytes = (size_t)fs->n_frames * pos_tris * TRI_POS_F * sizeof(float);
+  const size_t gverts_bytes = (size_t)fs->n_frames * m.n_verts * 3u * sizeof(float);
+  const size_t gdraw_bytes = (size_t)fs->n_frames * draw_stride * VG_VALS * sizeof(float);
+  if (int rc = check_grad_overlap(ctx, fn, {{d_gverts, gverts_bytes}, {d_gdraw, gdraw_bytes}}, {{d_gpos, gpos_bytes}})) return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (the pass reads vertices, matrices and d_gpos: no triangle of the set)
+  VertexGradArgs a{};
+  a.frames = fs->d_frames, a.draws = fs->d_draws;
+  a.verts = m.d_verts, a.corner_off = m.d_corner_off, a.corners = m.d_corner_off + m.n_verts + 1;
+  a.gpos = d_gpos, a.gverts = d_gverts, a.gdraw = d_gdraw;
+  a.gpos_stride = (uint64_t)pos_tris * TRI_POS_F;
+  a.n_verts = m.n_verts, a.n_frames = (uint32_t)fs->n_frames, a.draw_stride = draw_stride;
+  launch_vertex_grad(a, s);
   return end_pass(ctx);
 }
 

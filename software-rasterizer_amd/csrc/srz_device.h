@@ -206,6 +206,28 @@ void launch_clear_rebase(ClearCtl *ctl, hipStream_t s); // (a render that files 
 
 void launch_vertex(const DrawDesc *draws, uint32_t n_draws, uint32_t max_faces, srz_tri *tris, float *tri_pos, const FrameDesc *frames,
                    BBox *bbox_out, hipStream_t s);
+// srz_frameset_positions: every frame's piece of the dense position stream (tri_pos / pos_stride as RenderArgs has them) into the
+// caller's [frame][pos_tris][9], +0 behind a frame's last triangle (k_positions).  The host has checked pos_tris >= every frame's count
+void launch_positions(const FrameDesc *frames, uint32_t n_frames, const float *tri_pos, uint32_t pos_stride, float *out, uint32_t pos_tris,
+                      hipStream_t s);
+// srz_sceneset_vertex_grad: the backward of k_vertex for ONE mesh slot (k_vertex_grad), from the gradient of the triangles' screen
+// positions to the slot's vertices (gverts, a gather over each vertex's corner list: one owner per element) and to the matrix and
+// depth mapping of each draw of the slot (gdraw, reduced per workgroup, then one float add per value).  A draw takes part when its
+// DrawDesc names the slot's vertex buffer.  The host has checked pos_tris and draw_stride against every frame's counts
+constexpr uint32_t VG_VALS = 18; // per draw: the 16 gradients of ndc_mvp in its own order, zscale, zoffset
+struct VertexGradArgs {
+  const FrameDesc *frames;     // n_batches / batch_off: the frame's draws in `draws`; tri_off: what a draw's tri_off is relative to
+  const DrawDesc *draws;
+  const srz_vertex *verts;     // the slot's vertices
+  const uint32_t *corner_off;  // [n_verts + 1] into corners
+  const uint32_t *corners;     // [3 * n_faces]: 3 * face + k of every corner that names the vertex, increasing
+  const float *gpos;           // [frame][pos_tris][9]
+  float *gverts;               // [frame][n_verts][3], added into (may be null)
+  float *gdraw;                // [frame][draw_stride][18], added into (may be null)
+  uint64_t gpos_stride;        // floats per frame in gpos = pos_tris * 9
+  uint32_t n_verts, n_frames, draw_stride;
+};
+void launch_vertex_grad(const VertexGradArgs &a, hipStream_t s);
 void launch_chunks(const RenderArgs &a, int n_frames, uint32_t max_tris, hipStream_t s);
 void launch_setup(const RenderArgs &a, int n_frames, uint32_t max_tris, bool stats, hipStream_t s);
 void launch_bin(const RenderArgs &a, int n_frames, uint32_t max_tris, hipStream_t s);

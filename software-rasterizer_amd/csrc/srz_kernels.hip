@@ -434,14 +434,18 @@ __device__ __forceinline__ bool cover_s(const TriXY &t, float fx, float fy, floa
 //   pos' = to_vec3(NDC_MVP * (p,1)) ; pos'.z = pos'.z*scale + offset ; nrm' = to_vec3(Normal_M * (n,1)) ; uv copied
 // glm's operator*(mat4,vec4) order: (m0*v.x + m1*v.y) + (m2*v.z + m3*v.w); Tools::to_vec3 divides by w (src/Tools.cpp:74-76).
 // ================================================================================================================
-__device__ __forceinline__ void xform_div_w(const SRZ_CAS float *m, float x, float y, float z, float &ox, float &oy, float &oz) {
-  float r[4];
+// (the four rows before the division: k_vertex_grad differentiates them, and needs their bits)
+__device__ __forceinline__ void xform_rows(const SRZ_CAS float *m, float x, float y, float z, float (&r)[4]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const float add0 = m[0 * 4 + i] * x + m[1 * 4 + i] * y;
     const float add1 = m[2 * 4 + i] * z + m[3 * 4 + i]; // * 1.0f is exact
     r[i] = add0 + add1;
   }
+}
+__device__ __forceinline__ void xform_div_w(const SRZ_CAS float *m, float x, float y, float z, float &ox, float &oy, float &oz) {
+  float r[4];
+  xform_rows(m, x, y, z, r);
   ox = r[0] / r[3], oy = r[1] / r[3], oz = r[2] / r[3];
 }
 
@@ -546,6 +550,112 @@ __device__ __forceinline__ uint32_t wave_scan_max(uint32_t v) {
   v = max(v, SRZ_DPP(v, 0x142, 0xa));
   v = max(v, SRZ_DPP(v, 0x143, 0xc));
   return v;
+}
+// (float32 adds over the same control words; a lane without a source adds +0: lane 63 ends up with the wave's sum, one fixed tree)
+#define SRZ_DPP_F(v, ctrl, rmask) __uint_as_float(SRZ_DPP(__float_as_uint(v), ctrl, rmask))
+__device__ __forceinline__ float wave_scan_addf(float v) {
+  v += SRZ_DPP_F(v, 0x111, 0xf), v += SRZ_DPP_F(v, 0x112, 0xf), v += SRZ_DPP_F(v, 0x114, 0xf), v += SRZ_DPP_F(v, 0x118, 0xf);
+  v += SRZ_DPP_F(v, 0x142, 0xa);
+  v += SRZ_DPP_F(v, 0x143, 0xc);
+  return v;
+}
+
+// ================================================================================================================
+// k_positions — srz_frameset_positions: frame blockIdx.y's triangles of the dense position stream, float by float, into the caller's
+// [frame][pos_tris][9]; the floats behind the frame's last triangle are +0.
+// ================================================================================================================
+__global__ __launch_bounds__(256) void k_positions(const FrameDesc *frames, const float *tri_pos, uint32_t pos_stride, float *out, uint32_t pos_tris) {
+  const SRZ_CAS FrameDesc *fd = as_const(frames) + blockIdx.y;
+  const uint32_t n_tris = fd->n_tris;
+  const size_t n = (size_t)pos_tris * TRI_POS_F;
+  const float *src = tri_pos + (size_t)fd->tri_off * pos_stride;
+  float *dst = out + (size_t)blockIdx.y * n;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
+    const size_t t = e / TRI_POS_F;
+    dst[e] = t < n_tris ? src[t * pos_stride + (e - t * TRI_POS_F)] : 0.0f;
+  }
+}
+
+// ================================================================================================================
+// k_vertex_grad — srz_sceneset_vertex_grad, the backward of k_vertex for one mesh slot (include/srz.h states the rule).
+// Grid (blocks of 256 vertices, frames); a thread OWNS (frame, vertex) and walks the frame's draws of the slot in draw order — the loop
+// and every barrier in it are block-uniform, so a thread past the last vertex stays and contributes nothing.
+//   gverts: a GATHER.  Per draw the thread sums the gpos floats of its vertex's corners in list order (3 * corner is the float's
+//     index behind the draw's first triangle), differentiates the transform — xform_rows is k_vertex's own expression — and adds
+//     into a register copy of its three floats, which is stored once: no atomics, bit-reproducible.
+//   gdraw: 18 values per draw, reduced on chip — across the wave on the DPP crossbar, across the four waves through LDS — then ONE
+//     float add per workgroup, draw and value (no-return global_atomic_add_f32), and none for a draw no vertex of the workgroup
+//     contributes to.
+// ================================================================================================================
+__global__ __launch_bounds__(256) void k_vertex_grad(const VertexGradArgs a) {
+  __shared__ float s_part[4][VG_VALS];
+  __shared__ uint32_t s_any[4];
+  const uint32_t f = blockIdx.y, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t v = blockIdx.x * 256 + tid;
+  const bool live = v < a.n_verts;
+  const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+  const uint32_t n_draws = fd->n_batches, draw0 = fd->batch_off, tri0 = fd->tri_off;
+  uint32_t c_begin = 0, c_end = 0;
+  float P[3] = {0.0f, 0.0f, 0.0f};
+  if (live) {
+    c_begin = a.corner_off[v], c_end = a.corner_off[v + 1];
+    P[0] = a.verts[v].pos[0], P[1] = a.verts[v].pos[1], P[2] = a.verts[v].pos[2];
+  }
+  const float *gpos_f = a.gpos + (size_t)f * a.gpos_stride;
+  float *gv = a.gverts && live ? a.gverts + ((size_t)f * a.n_verts + v) * 3 : nullptr;
+  float acc[3] = {0.0f, 0.0f, 0.0f};
+  bool touched = false;
+  for (uint32_t j = 0; j < n_draws; ++j) {
+    const SRZ_CAS DrawDesc *d = as_const(a.draws) + draw0 + j;
+    if (d->verts != a.verts) continue; // (another slot's draw)
+    const float *gp = gpos_f + (size_t)(d->tri_off - tri0) * TRI_POS_F;
+    float GX = 0.0f, GY = 0.0f, GZ = 0.0f;
+    for (uint32_t c = c_begin; c < c_end; ++c) {
+      const float *p = gp + (size_t)a.corners[c] * 3;
+      GX = GX + p[0], GY = GY + p[1], GZ = GZ + p[2];
+    }
+    const bool contrib = live && !(GX == 0.0f && GY == 0.0f && GZ == 0.0f); // (a NaN is not 0 and goes on)
+    float val[VG_VALS];
+#pragma unroll
+    for (uint32_t e = 0; e < VG_VALS; ++e) val[e] = 0.0f;
+    if (contrib) {
+      float r[4], g[4];
+      xform_rows(d->ndc_mvp, P[0], P[1], P[2], r);
+      const float X = r[0] / r[3], Y = r[1] / r[3], Q = r[2] / r[3], inv = 1.0f / r[3], gq = GZ * d->zscale;
+      g[0] = GX * inv, g[1] = GY * inv, g[2] = gq * inv;
+      float s = gq * Q;
+      s = fmaf(GY, Y, s), s = fmaf(GX, X, s);
+      g[3] = (-s) * inv;
+      if (gv) {
+        if (!touched) acc[0] = gv[0], acc[1] = gv[1], acc[2] = gv[2], touched = true;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          float t = d->ndc_mvp[4 * c] * g[0];
+          t = fmaf(d->ndc_mvp[4 * c + 1], g[1], t), t = fmaf(d->ndc_mvp[4 * c + 2], g[2], t), t = fmaf(d->ndc_mvp[4 * c + 3], g[3], t);
+          acc[c] = acc[c] + t;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) val[i] = g[i] * P[0], val[4 + i] = g[i] * P[1], val[8 + i] = g[i] * P[2], val[12 + i] = g[i];
+      val[16] = GZ * Q, val[17] = GZ;
+    }
+    if (a.gdraw) {
+      const bool wave_any = __ballot(contrib) != 0ull;
+#pragma unroll
+      for (uint32_t e = 0; e < VG_VALS; ++e) val[e] = wave_scan_addf(val[e]);
+      if (lane == 63u) {
+#pragma unroll
+        for (uint32_t e = 0; e < VG_VALS; ++e) s_part[wave][e] = val[e];
+        s_any[wave] = wave_any ? 1u : 0u;
+      }
+      __syncthreads();
+      if (tid < VG_VALS && (s_any[0] | s_any[1] | s_any[2] | s_any[3]) != 0u)
+        unsafeAtomicAdd(a.gdraw + ((size_t)f * a.draw_stride + j) * VG_VALS + tid,
+                        (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]));
+      __syncthreads();
+    }
+  }
+  if (touched) gv[0] = acc[0], gv[1] = acc[1], gv[2] = acc[2];
 }
 
 // ================================================================================================================
@@ -5647,6 +5757,19 @@ void launch_vertex(const DrawDesc *draws, uint32_t n_draws, uint32_t max_faces, 
   dim3 grid((max_faces + 255) / 256, n_draws);
   if (grid.x > 1024) grid.x = 1024;
   hipLaunchKernelGGL(k_vertex, grid, dim3(256), 0, s, draws, tris, tri_pos, frames, bbox_out);
+}
+
+void launch_positions(const FrameDesc *frames, uint32_t n_frames, const float *tri_pos, uint32_t pos_stride, float *out, uint32_t pos_tris,
+                      hipStream_t s) {
+  if (n_frames == 0 || pos_tris == 0) return;
+  const size_t blocks = ((size_t)pos_tris * TRI_POS_F + 255) / 256;
+  dim3 grid((uint32_t)(blocks > 1024 ? 1024 : blocks), n_frames);
+  hipLaunchKernelGGL(k_positions, grid, dim3(256), 0, s, frames, tri_pos, pos_stride, out, pos_tris);
+}
+
+void launch_vertex_grad(const VertexGradArgs &a, hipStream_t s) {
+  if (a.n_frames == 0 || a.n_verts == 0) return;
+  hipLaunchKernelGGL(k_vertex_grad, dim3((a.n_verts + 255) / 256, a.n_frames), dim3(256), 0, s, a);
 }
 
 void launch_chunks(const RenderArgs &a, int n_frames, uint32_t max_tris, hipStream_t s) {

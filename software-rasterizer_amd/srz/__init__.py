@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("SRZ_LIB_PATH", os.path.join(_PKG, "libsrz.so"))  # (o
 _lib = None
 
 EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "srz_set_shard", "srz_set_option", "srz_texture_upload",
-           "srz_draw", "srz_draw_scene", "srz_mesh_upload", "srz_sceneset_create", "srz_frameset_create", "srz_frameset_destroy", "srz_frameset_local_rows",
+           "srz_draw", "srz_draw_scene", "srz_mesh_upload", "srz_mesh_update", "srz_sceneset_create", "srz_frameset_create", "srz_frameset_destroy", "srz_frameset_local_rows",
            "srz_frameset_out_bytes", "srz_frameset_render", "srz_frameset_resolve8", "srz_frameset_stats", "srz_frameset_algorithmic_bytes",
            "srz_kernel_time_ms", "srz_kernel_time_samples", "srz_set_kernel_timing", "srz_sync", "srz_debug_counters", "srz_verify_fastmath", "srz_verify_fastdiv", "srz_verify_fastpow", "srz_verify_fastlen", "srz_host_register", "srz_host_unregister", "srz_frameset_debug_counters", "srz_draw_batch",
            "srz_comm_unique_id", "srz_comm_create", "srz_comm_destroy", "srz_frameset_exchange_bytes", "srz_frameset_allgather",
@@ -26,6 +26,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_update_shading", "srz_frameset_shade_kinds", "srz_frameset_gbuffer_bytes", "srz_frameset_gbuffer",
            "srz_frameset_motion_bytes", "srz_frameset_motion", "srz_frameset_interpolate_bytes", "srz_frameset_interpolate",
            "srz_frameset_interpolate_grad", "srz_frameset_position_grad", "srz_frameset_antialias", "srz_frameset_antialias_grad",
+           "srz_frameset_positions", "srz_sceneset_vertex_grad",
            "srz_frameset_texture", "srz_frameset_texture_grad",
            "srz_texture_mip_levels", "srz_texture_mip_bytes", "srz_texture_mip_build", "srz_texture_mip_fold",
            "srz_frameset_interpolate_deriv", "srz_frameset_texture_mip", "srz_frameset_texture_mip_grad",
@@ -66,6 +67,7 @@ def lib():
         L.srz_frameset_create.argtypes = [vp, C.POINTER(abi.SrzFrame), C.c_int, C.POINTER(vp)]
         L.srz_sceneset_create.argtypes = [vp, C.POINTER(abi.SrzSceneFrame), C.c_int, C.POINTER(vp)]
         L.srz_mesh_upload.argtypes = [vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32]
+        L.srz_mesh_update.argtypes = [vp, C.c_int, vp, C.c_uint32, vp]
         L.srz_draw_scene.argtypes = [vp, C.c_int, C.POINTER(abi.SrzSceneFrame), fp, fp, fp, fp, C.POINTER(abi.SrzStats)]
         L.srz_frameset_destroy.argtypes = [vp, vp]
         L.srz_frameset_destroy.restype = None
@@ -86,6 +88,8 @@ def lib():
         L.srz_frameset_interpolate.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.c_uint32, vp]
         L.srz_frameset_interpolate_grad.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp]
         L.srz_frameset_position_grad.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp]
+        L.srz_frameset_positions.argtypes = [vp, vp, C.c_uint32, vp, C.c_size_t, vp]
+        L.srz_sceneset_vertex_grad.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, vp, vp, C.c_uint32, vp]
         L.srz_frameset_antialias.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, C.c_uint32, vp]
         L.srz_frameset_antialias_grad.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp]
         L.srz_frameset_texture.argtypes = abi.TEXTURE_ARGTYPES
@@ -274,6 +278,22 @@ class FrameSet:
         self.ctx._check(lib().srz_frameset_position_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_gbary_ptr or None),
                                                          C.c_void_p(d_gz_ptr or None), pos_tris, C.c_void_p(d_gpos_ptr or None),
                                                          C.c_void_p(d_gpix_ptr or None), flags, _stream(stream)))
+
+    def positions(self, pos_tris, d_pos_ptr, pos_bytes, stream=None):
+        """the set's own screen positions, as the rasteriser reads them: d_pos [n_frames][pos_tris][9] float32 (ax ay z0 bx by z1 cx cy
+        z2 per triangle, the visibility buffer's triangle index; +0 behind a frame's last triangle), pos_tris at least every frame's
+        triangle count.  A sceneset runs its vertex stage first.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_positions(self.ctx.h, self.h, pos_tris, C.c_void_p(d_pos_ptr), pos_bytes, _stream(stream)))
+
+    def vertex_grad(self, mesh_id, d_gpos_ptr, pos_tris, d_gverts_ptr, d_gdraw_ptr, draw_stride, stream=None):
+        """the backward of a sceneset's vertex stage for mesh slot mesh_id: d_gpos [n_frames][pos_tris][9] (position_grad's and
+        antialias_grad's) → ADDED into d_gverts [n_frames][n_verts][3] (a gather: deterministic; elements no draw contributes to are
+        left untouched) and / or d_gdraw [n_frames][draw_stride][18] (per draw of the slot: ndc_mvp's 16 gradients in its own order,
+        zscale, zoffset; a sum in an unspecified order: not bit-reproducible).  Either output pointer may be None / 0, not both
+        (include/srz.h states the rule).  Asynchronous."""
+        self.ctx._check(lib().srz_sceneset_vertex_grad(self.ctx.h, self.h, mesh_id, C.c_void_p(d_gpos_ptr), pos_tris,
+                                                       C.c_void_p(d_gverts_ptr or None), C.c_void_p(d_gdraw_ptr or None), draw_stride,
+                                                       _stream(stream)))
 
     def antialias(self, d_vis_ptr, d_in_ptr, n_ch, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
         """the planes d_in [frame][n_ch][local_rows][width] float32 blended across the silhouettes of a visibility buffer of this set:
@@ -520,6 +540,7 @@ class Context:
 
     def __init__(self, device_id=0, rank=0, world=1):
         self.h = C.c_void_p()
+        self.mesh_sizes = {}  # slot -> (vertices, faces) of the mesh uploaded last
         rc = lib().srz_create(C.byref(self.h), device_id)
         if rc != 0:
             raise SrzError(rc, lib().srz_last_error(None).decode())
@@ -561,6 +582,13 @@ class Context:
         v = np.ascontiguousarray(verts8, dtype=np.float32)
         f = np.ascontiguousarray(faces, dtype=np.uint32)
         self._check(lib().srz_mesh_upload(self.h, mesh_id, v.ctypes.data, len(v), f.ctypes.data, len(f)))
+        self.mesh_sizes[mesh_id] = (len(v), len(f))
+
+    def mesh_update(self, mesh_id, d_verts_ptr, n_verts, stream=None):
+        """new vertices for a slot that holds a mesh, in place: d_verts_ptr is a DEVICE address of n_verts (the slot's count) 32-byte
+        records [pos3 nrm3 uv2] — one asynchronous device-to-device copy.  Faces, addresses and the upload counter stay: every
+        sceneset that draws the slot stays valid and transforms the new vertices from its next vertex stage on."""
+        self._check(lib().srz_mesh_update(self.h, mesh_id, C.c_void_p(d_verts_ptr), n_verts, _stream(stream)))
 
     def draw(self, frame, planes=None, primitive=abi.PRIMITIVE_TRIANGLES, want_stats=False):
         """TraditionalRasterizer::draw for one scene; planes (z,c0,c1,c2) are modified in place."""

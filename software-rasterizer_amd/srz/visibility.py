@@ -554,3 +554,116 @@ def texture_mip(fs, vis, tex, uv, uvd, wrap=False, n_levels=None, stream=None):
     held fixed: uvd gets no gradient.  Backward is one texture_mip_grad call that asks only for the outputs some input needs, and one
     fold when tex needs a gradient.  stream: a raw stream handle, None = torch's current stream."""
     return _TextureMip.apply(tex, uv, fs, vis, uvd, wrap, n_levels, stream)
+
+
+def _scene_draws(fs):
+    """per frame of a sceneset the mesh slots of its draws, in draw order"""
+    if not all(isinstance(f, abi.SceneFrame) for f in fs.frames):
+        raise ValueError("the set is not a sceneset")
+    return [[int(f._draws[i].mesh_id) for i in range(f.c.n_draws)] for f in fs.frames]
+
+
+def _set_tris(fs, pos_tris):
+    """pos_tris, or the largest triangle count of the set's frames (a sceneset: from the face counts of the slots it draws)"""
+    if pos_tris is not None:
+        return int(pos_tris)
+    if all(hasattr(f, "n_tris") for f in fs.frames):
+        return max(f.n_tris for f in fs.frames)
+    return max(sum(fs.ctx.mesh_sizes[m][1] for m in draws) for draws in _scene_draws(fs))
+
+
+def positions(fs, pos_tris=None, stream=None):
+    """the screen positions of FrameSet `fs`'s triangles as the rasteriser reads them (FrameSet.positions; a sceneset runs its vertex
+    stage) → [n_frames, T, 3, 3] float32 (triangle, corner, (x, y, z)), T = pos_tris (default: the largest triangle count of the
+    set's frames), zeros behind a frame's last triangle.  stream: a raw stream handle, None = torch's current stream."""
+    T = _set_tris(fs, pos_tris)
+    pos = torch.empty((fs.n_frames, T, 3, 3), dtype=torch.float32, device="cuda")
+    fs.positions(T, pos.data_ptr(), pos.numel() * 4, _stream_ptr(stream))
+    return pos
+
+
+def vertex_grad(fs, mesh_id, gpos, want_gverts=True, want_gdraw=True, stream=None, gdraw=None):
+    """the backward of sceneset `fs`'s vertex stage for mesh slot mesh_id by one FrameSet.vertex_grad call: gpos [n_frames, T, 3, 3]
+    (position_grad's, antialias_grad's, or their sum) → (gverts [n_frames, V, 3], gdraw [n_frames, D, 18]), each None when not wanted
+    (not both), into zeros; D the largest draw count of the set's frames.  gverts is the gradient with respect to the slot's vertex
+    positions, frame by frame — a gather, bit-reproducible; a row of gdraw is the gradient of a draw's ndc_mvp (16, its own
+    column-major order), zscale and zoffset, zeros for draws of other slots — float atomics, not bit-reproducible.  gdraw: a
+    [n_frames, D, 18] tensor to add into instead (several meshes into one buffer)."""
+    if not want_gverts and not want_gdraw:
+        raise ValueError("vertex_grad: neither gverts nor gdraw is asked for")
+    if gpos.dtype != torch.float32 or not gpos.is_cuda or gpos.dim() != 4 or gpos.shape[0] != fs.n_frames or tuple(gpos.shape[2:]) != (3, 3):
+        raise ValueError(f"vertex_grad: gpos must be a CUDA float32 tensor [n_frames, T, 3, 3], got {tuple(gpos.shape)} {gpos.dtype}")
+    gpos = gpos.contiguous()
+    D = max(1, max(len(d) for d in _scene_draws(fs)))
+    gverts = torch.zeros((fs.n_frames, fs.ctx.mesh_sizes[mesh_id][0], 3), dtype=torch.float32, device=gpos.device) if want_gverts else None
+    if want_gdraw and gdraw is None:
+        gdraw = torch.zeros((fs.n_frames, D, 18), dtype=torch.float32, device=gpos.device)
+    if want_gdraw and (gdraw.dtype != torch.float32 or not gdraw.is_contiguous() or tuple(gdraw.shape) != (fs.n_frames, D, 18)):
+        raise ValueError(f"vertex_grad: gdraw must be a contiguous float32 tensor {(fs.n_frames, D, 18)}")
+    fs.vertex_grad(mesh_id, gpos.data_ptr(), gpos.shape[1], gverts.data_ptr() if want_gverts else None,
+                   gdraw.data_ptr() if want_gdraw else None, D, _stream_ptr(stream))
+    return gverts, (gdraw if want_gdraw else None)
+
+
+def mesh_update(ctx, mesh_id, verts8, stream=None):
+    """new vertices for mesh slot mesh_id of Context `ctx`, in place, from a CUDA float32 tensor [V, 8] (pos3 nrm3 uv2; V the slot's
+    count): Context.mesh_update, one device-to-device copy.  Every sceneset that draws the slot stays valid and renders the new
+    vertices from its next vertex stage on.  stream: a raw stream handle, None = torch's current stream."""
+    if verts8.dtype != torch.float32 or not verts8.is_cuda or verts8.dim() != 2 or verts8.shape[1] != 8:
+        raise ValueError(f"mesh_update: verts8 must be a CUDA float32 tensor [V, 8], got {tuple(verts8.shape)} {verts8.dtype}")
+    verts8 = verts8.detach().contiguous()
+    ctx.mesh_update(mesh_id, verts8.data_ptr(), verts8.shape[0], _stream_ptr(stream))
+
+
+class _ScenePositions(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, fs, mesh_ids, pos_tris, stream, mvp, zmap, *verts):
+        ctx.fs, ctx.mesh_ids, ctx.stream = fs, mesh_ids, stream
+        ctx.shapes = [tuple(v.shape) for v in verts]
+        return positions(fs, pos_tris, stream)
+
+    @staticmethod
+    def backward(ctx, gpos):
+        fs = ctx.fs
+        need_draw = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
+        need_verts = {m: ctx.needs_input_grad[6 + i] for i, m in enumerate(ctx.mesh_ids)}
+        # one call per mesh that needs a gradient (for the matrices: every mesh the set draws), sharing one gdraw buffer
+        todo = sorted({m for draws in _scene_draws(fs) for m in draws} if need_draw else {m for m, need in need_verts.items() if need})
+        gpos = gpos.contiguous()
+        gdraw, gverts = None, {}
+        for m in todo:
+            gverts[m], gdraw = vertex_grad(fs, m, gpos, need_verts.get(m, False), need_draw, ctx.stream, gdraw)
+        out = []
+        for m, shape in zip(ctx.mesh_ids, ctx.shapes):
+            g = gverts.get(m)
+            out.append(None if g is None else (g.sum(0) if len(shape) == 2 else g))
+        gmvp = gdraw[:, :, :16].contiguous() if ctx.needs_input_grad[4] else None
+        gzmap = gdraw[:, :, 16:].contiguous() if ctx.needs_input_grad[5] else None
+        return (None, None, None, None, gmvp, gzmap, *out)
+
+
+def scene_positions(fs, meshes, mvp=None, zmap=None, pos_tris=None, stream=None):
+    """the screen positions of sceneset `fs`'s triangles, positions(fs), as a differentiable function of what the set was made from —
+    the `pos` that interpolate_geo, depth and antialias take, and where the chain begins.  meshes: a dict mesh slot → vertex positions,
+    a CUDA float32 tensor [V, 3] (shared by the frames) or [n_frames, V, 3]; mvp: [n_frames, D, 16], every draw's ndc_mvp in its own
+    column-major order (D the largest draw count of the frames); zmap: [n_frames, D, 2], (zscale, zoffset) of the draw's frame.  LIKE
+    THE `pos` HANDLE THESE TENSORS ARE GRAPH HANDLES WHOSE VALUES ARE NEVER READ: the positions are the set's own (its vertex stage
+    over what srz_mesh_upload / mesh_update and srz_sceneset_create / _update gave it), and the caller warrants that the tensors hold
+    the same values.  The forward returns real values: positions(fs).  Backward: one vertex_grad call per mesh that needs a gradient
+    (with mvp or zmap: per mesh the set draws), sharing one gdraw buffer; a [V, 3] tensor's gradient is the per-frame result summed
+    over the frames (deterministic); mvp.grad and zmap.grad are the first 16 and the last 2 columns of gdraw (float atomics: not
+    bit-reproducible), rows behind a frame's last draw zero.  A frame's zscale and zoffset are shared by its draws: sum zmap.grad
+    over them.  antialias(fs, vis, interpolate_geo(fs, vis, attr, pos), pos) with pos = scene_positions(...) is the whole chain from a
+    loss to the mesh and the pose."""
+    ids = tuple(sorted(meshes))
+    D = max(1, max(len(d) for d in _scene_draws(fs)))
+    for m in ids:
+        v = meshes[m]
+        V = fs.ctx.mesh_sizes[m][0]
+        if v.dtype != torch.float32 or tuple(v.shape) not in ((V, 3), (fs.n_frames, V, 3)):
+            raise ValueError(f"scene_positions: mesh {m} must be float32 [{V}, 3] or [{fs.n_frames}, {V}, 3], got {tuple(v.shape)} {v.dtype}")
+    if mvp is not None and (mvp.dtype != torch.float32 or tuple(mvp.shape) != (fs.n_frames, D, 16)):
+        raise ValueError(f"scene_positions: mvp must be float32 {(fs.n_frames, D, 16)}, got {tuple(mvp.shape)} {mvp.dtype}")
+    if zmap is not None and (zmap.dtype != torch.float32 or tuple(zmap.shape) != (fs.n_frames, D, 2)):
+        raise ValueError(f"scene_positions: zmap must be float32 {(fs.n_frames, D, 2)}, got {tuple(zmap.shape)} {zmap.dtype}")
+    return _ScenePositions.apply(fs, ids, pos_tris, stream, mvp, zmap, *[meshes[m] for m in ids])
