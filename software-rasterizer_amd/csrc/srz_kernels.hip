@@ -1414,7 +1414,7 @@ __device__ __forceinline__ void s_shade(M &m, const FrameK &K, const ShadeDesc &
 // 3. The tile's RECTANGLE in the framebuffer: tile_rect().
 // HELPER — k_shade's inline copy of it (any call in its tile loop moves its schedule; each copy names its helper; a fix goes into both):
 //    work_decode, id_none / id_sbit, ids_load_raw, ids_unpack4 — shade_tile: head, step 1 and the classification
-//    tile_rect — shade_tile, behind the FrameDesc loads (and k_shade_vis's shade_tile, head)
+//    tile_rect — shade_tile, behind the FrameDesc loads
 //    (k_gbuffer CALLS tile_rect, the owner-id constants, v_normalized, normalize3, s_texel and cvt_rne_i32; its copy of v_shade's prologue
 //    and fetch and of shade_bary_v / _s's interpolation names them; k_motion CALLS tile_rect, the owner-id constants and load_pos9, its
 //    copy of cover_v / cover_s's z interpolation names them; k_interp and k_interp_grad CALL tile_rect, quad_store, quad_at and the
@@ -2954,10 +2954,138 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
 }
 
 // ================================================================================================================
+// THE WALK OF THE PASSES OVER A VISIBILITY BUFFER (k_shade_vis and the kernels behind it, down to k_tex_mip_grad).  No work lists: the
+// buffer is all there is, so the grid (tile_grid: one workgroup per tile up to a cap) walks every (frame, 32x32 tile) of the set in
+// k_shade's XCD order: workgroup b takes the frames f ≡ b mod 8, whose triangles stay in its XCD's L2, tile after tile, gridDim / 8
+// tiles apart; a set of fewer than 8 frames has its tiles dealt round-robin instead, so that every XCD has work.  Within a tile a
+// thread owns 4 consecutive pixels of one row (k_visibility's deal: 8 threads a row, a wave 8 rows), so every plane is read and
+// written in 16-byte accesses.
+//   pass_tiles  the striding loop and the (frame, tile) decode: body(f, t) per tile of this workgroup;
+//   pass_tile   a thread's place in tile t of frame f: the tile's rectangle (tile_rect), the thread's row and first column, whether
+//               it lies inside, whether its quad is whole, and where its pixels are in a frame's plane 0 and in `out`;
+//   pass_walk   the two together.  A kernel with barriers (KEEP_OUTSIDE) gets every thread, one outside the frame owning nothing;
+//               in the others such a thread just moves on.
+// Then what the bodies do next: quad_ids (the four owner ids, strangers clamped to nobody), quad_bary (α, β and γ of the owned
+// pixels) and quad_store_owned (whole quads, or the owned pixels only).
+// CALLERS: k_shade_vis (pass_tiles with its kind filter, pass_tile, quad_ids), k_interp, k_interp_grad, k_interp_deriv (all of it).
+// COPIES, each naming this definition — a fix to the walk goes into them too: k_gbuffer, k_motion, k_pos_grad, aa_body, k_tex,
+// k_tex_grad, k_tex_mip, k_tex_mip_grad (with tex_quad and mip_quad).  Moved onto these helpers they computed the same words
+// (the whole suite passed) but ran slower than their inline text on an MI355X at 256 frames of 1024²: k_gbuffer +4 %, k_motion +6 %,
+// k_pos_grad +2..6 %, k_antialias +1.5..3 % (k_antialias_grad −15 %: one body serves both), k_tex_grad and k_tex_mip_grad +12 % on
+// their guv legs — same arithmetic, another schedule; NOTEBOOK has the series.  They stay as they were until someone finds why.
+// Left inline in the callers, because a helper would be no shorter than the statements: the per-kernel plane pointers (a.vis + f *
+// a.vis_stride + poff: the strides' names and meanings differ between the Args structs); k_shade_vis's load of z, α, β into LDS
+// (three planes by pixel, not two by owner) and its in-place write-out; the gout quads of k_interp_grad's chunk loop.
+// ================================================================================================================
+struct PassTile {
+  const SRZ_CAS FrameDesc *fd;
+  uint32_t f;    // the frame
+  TileRect rc;
+  int y, x4;     // the thread's row and first column (frame coordinates)
+  bool inside;   // its first pixel lies in the tile's rectangle
+  bool whole;    // inside, all four pixels, and the rows 16-byte aligned: one 16-byte access per plane
+  size_t poff;   // floats from a frame's plane 0 to the thread's first pixel (any buffer of the set's geometry)
+  float *out;    // the thread's first pixel in plane 0 of the frame in a.out
+  // (something the body asks for: AntialiasArgs has no flags_or)
+  __device__ __forceinline__ bool fused(uint32_t flags_or) const { return ((fd->flags | flags_or) & SRZ_FUSED_CLEAR) != 0; }
+};
+template <class A, class Body> __device__ __forceinline__ void pass_tiles(const A &a, Body body) {
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
+  for (uint32_t j = blockIdx.x >> 3;; j += step) {
+    uint32_t f, t;
+    if (a.n_frames >= 8u) {
+      f = sub + 8u * (j / tpf), t = j % tpf;
+      if (f >= a.n_frames) break;
+    } else {
+      const uint32_t i = j * 8u + sub;
+      if (i >= n_items) break;
+      f = i / tpf, t = i % tpf;
+    }
+    body(f, t);
+  }
+}
+template <class A> __device__ __forceinline__ PassTile pass_tile(const A &a, uint32_t f, uint32_t t) {
+  const int ly = (int)threadIdx.x >> 3, lx4 = ((int)threadIdx.x & 7) * 4; // (wave * 8 + lane / 8, lane % 8 * 4)
+  PassTile p;
+  p.fd = as_const(a.frames) + f, p.f = f;
+  const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
+  p.rc = tile_rect(a, p.fd, f, lb, tx);
+  const int W = p.fd->width;
+  p.y = p.rc.ty0 + ly, p.x4 = p.rc.tx0 + lx4;
+  p.inside = p.y <= p.rc.ty1 && p.x4 <= p.rc.tx1;
+  p.whole = p.inside && (W & 3) == 0 && p.x4 + 3 <= p.rc.tx1;
+  p.poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)p.x4;
+  p.out = p.rc.out0 + (size_t)ly * (size_t)W + (size_t)p.x4;
+  return p;
+}
+template <bool KEEP_OUTSIDE, class A, class Body> __device__ __forceinline__ void pass_walk(const A &a, Body body) {
+  pass_tiles(a, [&](uint32_t f, uint32_t t) {
+    const PassTile p = pass_tile(a, f, t);
+    if (KEEP_OUTSIDE || p.inside) body(p);
+  });
+}
+// The four owner ids of the thread's quad (plane 1 of the frame's visibility buffer, gv its plane 0 at the thread's first pixel):
+// index + 1 | S class.  0, the bare class bit (both wrap to 0xffffffff) and an index outside the frame's triangles are nobody: id 0.
+// -> one bit per owned pixel.  KEEP: the bits of an owner's id the kernel wants (k_interp_deriv: not the class); stray: the pixels
+// whose word is not 0 and names nobody (k_shade_vis gives them the clear values).  A thread outside the tile owns nothing.
+template <uint32_t KEEP = 0xffffffffu>
+__device__ __forceinline__ uint32_t quad_ids(const PassTile &t, const float *gv, uint32_t (&id)[4], uint32_t *stray = nullptr) {
+  id[0] = id[1] = id[2] = id[3] = 0u;
+  if (t.whole) {
+    const uint4 q = *reinterpret_cast<const uint4 *>(gv + t.rc.plane);
+    id[0] = q.x, id[1] = q.y, id[2] = q.z, id[3] = q.w;
+  } else if (t.inside) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (t.x4 + k <= t.rc.tx1) id[k] = f2u(gv[t.rc.plane + k]);
+  }
+  const uint32_t n_tris = t.fd->n_tris;
+  uint32_t own = 0u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if ((id[k] & ~S_CLASS_BIT) - 1u < n_tris) {
+      own |= 1u << k, id[k] &= KEEP;
+    } else {
+      if (stray && id[k] != 0u) *stray |= 1u << k;
+      id[k] = 0u;
+    }
+  }
+  return own;
+}
+// α and β (planes 2 and 3) of the quad's owned pixels, the others 0, and each owner's γ by its class (cover_s / cover_v)
+__device__ __forceinline__ void quad_bary(const PassTile &t, const float *gv, uint32_t own, const uint32_t (&id)[4], float4 &al, float4 &be,
+                                          float4 &ga) {
+  al = be = ga = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (own == 0u) return;
+  if (t.whole) {
+    al = *reinterpret_cast<const float4 *>(gv + 2 * t.rc.plane), be = *reinterpret_cast<const float4 *>(gv + 3 * t.rc.plane);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (own & (1u << k)) quad_at(al, k) = gv[2 * t.rc.plane + k], quad_at(be, k) = gv[3 * t.rc.plane + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    quad_at(ga, k) = (id[k] & S_CLASS_BIT) ? 1.0f - quad_at(al, k) - quad_at(be, k) : 1.0f - (quad_at(al, k) + quad_at(be, k));
+}
+// N planes of the quad at p: whole quads with the fused clear or four owners (quad_store), else the owned pixels only
+template <int N>
+__device__ __forceinline__ void quad_store_owned(float *p, const PassTile &t, const float4 (&q)[N], bool fused, uint32_t own) {
+  if (fused || own == 15u) {
+    quad_store(p, t.rc.plane, q, t.whole, t.x4, t.rc.tx1);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (own & (1u << k))
+#pragma unroll
+        for (int i = 0; i < N; ++i) p[i * t.rc.plane + k] = quad_at(q[i], k);
+  }
+}
+
+// ================================================================================================================
 // k_shade_vis — the COLOUR OF A VISIBILITY BUFFER (srz_frameset_shade_visibility, include/srz.h): what k_shade would have written,
-// from the owner id, z, α and β a visibility render left, without rasterising again.  No work lists: the buffer is all there is,
-// so the grid walks every (frame, 32x32 tile) of the set in k_shade's XCD order (workgroup b takes the frames f ≡ b mod 8, whose
-// triangles stay in its XCD's L2; fewer than 8 frames: tiles dealt round-robin).  Per tile:
+// from the owner id, z, α and β a visibility render left, without rasterising again.  The passes' walk (pass_tiles).  Per tile:
 //   1. a thread's 4 owner ids in one 16-byte load (plane 1); an id above the frame's triangle count is nobody (with SRZ_FUSED_CLEAR it
 //      gets the clear values, in place too); z, α, β only for quads with an owner, into LDS by pixel;
 //   2. the owned pixels compacted by class (V entries, then S entries), as k_shade does, so a wave runs one class per 64-entry chunk;
@@ -2988,47 +3116,24 @@ __global__ __launch_bounds__(256, FASTNL == -4 ? 3 : SRZ_SHADE_MINW) void k_shad
   __shared__ uint8_t s_bog[256]; // per thread: its pixels whose id word is out of range
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4, p0 = ly * TILE + lx4;
-  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  const int p0 = tid * 4; // (ly * TILE + lx4 of pass_tile's deal)
+  const uint32_t tpf = a.n_local_bands * a.tiles_x;
   // ---- tile t of frame f.  mode: 0 = the FAST variants (a tile where an operand left FastMath's range goes to redo_list), 1 = the
   //      generic instantiation (FastMath, then IEEE if needed), 2 = IEEE at once (the tiles handed back) --------------------------------
   auto shade_tile = [&](const uint32_t f, const uint32_t t, auto mode_c) {
     constexpr int MODE = decltype(mode_c)::value;
-    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
-    const uint32_t ff = fd->flags;
-    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x; // (inline copy of tile_rect, to `plane`)
-    const int W = fd->width, H = fd->height;
-    const int tx0 = (int)tx * TILE, ty0 = band_of((int)lb, a.shard_rank, a.shard_world) * BAND;
-    const int tx1 = min(tx0 + TILE, W) - 1, ty1 = min(ty0 + BAND, H) - 1;
-    const int y = ty0 + ly, x4 = tx0 + lx4;
-    const bool in_tile = y <= ty1 && x4 <= tx1;
-    const bool whole = in_tile && (W & 3) == 0 && x4 + 3 <= tx1;
-    const bool fused = ((ff | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
-    const size_t plane = (size_t)a.local_rows * (size_t)W;
-    const size_t off = (size_t)f * a.frame_stride + ((size_t)lb * BAND + (size_t)ly) * (size_t)W + (size_t)x4;
-    const float *gv = a.vis + off;
-    float *go = a.out + off;
-    // ---- 1. owner ids (index + 1 | S class; an index outside the frame's triangles is nobody), and z, α, β of owned quads
-    uint32_t id[4] = {0u, 0u, 0u, 0u};
-    if (whole) {
-      const uint4 q = *reinterpret_cast<const uint4 *>(gv + plane);
-      id[0] = q.x, id[1] = q.y, id[2] = q.z, id[3] = q.w;
-    } else if (in_tile) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (x4 + k <= tx1) id[k] = f2u(gv[plane + k]);
-    }
-    const uint32_t n_tris = fd->n_tris;
-    uint32_t bogus = 0u; // bit k: pixel k's id word is neither 0 nor a triangle of the frame
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if ((id[k] & ~S_CLASS_BIT) - 1u >= n_tris) { // (0 and the bare class bit wrap to 0xffffffff)
-        if (id[k] != 0u) bogus |= 1u << k;
-        id[k] = 0u;
-      }
-    s_bog[tid] = (uint8_t)bogus; // (read back by the in-place write-out only: no register holds it across the passes)
+    const PassTile pt = pass_tile(a, f, t);
+    const SRZ_CAS FrameDesc *fd = pt.fd;
+    const int tx0 = pt.rc.tx0, ty0 = pt.rc.ty0, tx1 = pt.rc.tx1, x4 = pt.x4;
+    const bool in_tile = pt.inside, whole = pt.whole, fused = pt.fused(a.flags_or);
+    const size_t plane = pt.rc.plane;
+    const float *gv = a.vis + (size_t)f * a.frame_stride + pt.poff;
+    float *go = pt.out;
+    // ---- 1. owner ids, and z, α, β of owned quads
+    uint32_t id[4], bogus = 0u; // bogus bit k: pixel k's id word is neither 0 nor a triangle of the frame
     // (what the write-out needs of the ids: one bit per pixel — the ids and the quads below are not kept alive across the passes)
-    const uint32_t own = (id[0] != 0u ? 1u : 0u) | (id[1] != 0u ? 2u : 0u) | (id[2] != 0u ? 4u : 0u) | (id[3] != 0u ? 8u : 0u);
+    const uint32_t own = quad_ids(pt, gv, id, &bogus);
+    s_bog[tid] = (uint8_t)bogus; // (read back by the in-place write-out only: no register holds it across the passes)
     const bool any_own = own != 0u;
     float4 in[3] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
     if (any_own) {
@@ -3216,21 +3321,12 @@ __global__ __launch_bounds__(256, FASTNL == -4 ? 3 : SRZ_SHADE_MINW) void k_shad
     __syncthreads(); // LDS is reused by the next tile
   };
 
-  // the frames of this build's kind, tile by tile: workgroup b walks frames f ≡ b mod 8 (fewer than 8 frames: every 8th tile)
-  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
-  for (uint32_t j = blockIdx.x >> 3; FAST || a.any_generic; j += step) {
-    uint32_t f, t;
-    if (a.n_frames >= 8u) {
-      f = sub + 8u * (j / tpf), t = j % tpf;
-      if (f >= a.n_frames) break;
-    } else {
-      const uint32_t i = j * 8u + sub;
-      if (i >= n_items) break;
-      f = i / tpf, t = i % tpf;
-    }
-    if (frame_kind(as_const(a.frames)[f].flags) != KIND) continue; // (workgroup-uniform: another launch's frame)
-    shade_tile(f, t, std::integral_constant<int, FAST ? 0 : 1>{});
-  }
+  // the frames of this build's kind, tile by tile
+  if (FAST || a.any_generic)
+    pass_tiles(a, [&](uint32_t f, uint32_t t) {
+      if (frame_kind(as_const(a.frames)[f].flags) != KIND) return; // (workgroup-uniform: another launch's frame)
+      shade_tile(f, t, std::integral_constant<int, FAST ? 0 : 1>{});
+    });
   if constexpr (!FAST) { // the tiles the FAST builds handed back (they ran before this kernel on the same stream)
     const uint32_t n_redo = *as_const(a.redo_count);
     for (uint32_t i = blockIdx.x; i < n_redo; i += gridDim.x) {
@@ -3319,7 +3415,7 @@ __global__ __launch_bounds__(256) void k_gbuffer(GbufArgs a) {
   const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
   const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
   const uint32_t what = a.what;
-  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile): an inline copy of pass_walk
   const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
   for (uint32_t j = blockIdx.x >> 3;; j += step) {
     uint32_t f, t;
@@ -3459,7 +3555,7 @@ __global__ __launch_bounds__(256) void k_motion(MotionArgs a) {
   const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
   const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
   const uint32_t what = a.what;
-  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile): an inline copy of pass_walk
   const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
   for (uint32_t j = blockIdx.x >> 3;; j += step) {
     uint32_t f, t;
@@ -3551,10 +3647,8 @@ __global__ __launch_bounds__(256) void k_motion(MotionArgs a) {
 // ================================================================================================================
 // k_interp — CALLER ATTRIBUTES OVER A VISIBILITY BUFFER (srz_frameset_interpolate, include/srz.h): channel ch of the owner's three
 // corner values [triangle][corner][channel] under the pixel's α, β, γ, interpolated as the owner's class interpolates uv
-// (shade_bary_v: fma chain; shade_bary_s: products and sums).  k_gbuffer's shape: no work lists, no LDS, no barrier; the grid walks
-// every (frame, 32x32 tile) in k_shade_vis's XCD order, a thread owns 4 consecutive pixels of one row, its 4 ids arrive in one
-// 16-byte load, α and β only for a quad with an owner, every plane leaves through quad_store.  The ids, α, β and γ are loaded and
-// formed once; a wave-uniform loop then runs over the channels in register chunks of ATTR_CHUNK, the tail chunk masked, so that 64
+// (shade_bary_v: fma chain; shade_bary_s: products and sums).  k_gbuffer's shape: pass_walk, no LDS, no barrier; quad_ids, quad_bary,
+// every plane leaves through quad_store_owned.  The ids, α, β and γ are loaded and formed once; a wave-uniform loop then runs over the channels in register chunks of ATTR_CHUNK, the tail chunk masked, so that 64
 // channels cost the registers of 4.  The attribute array is only 4-byte aligned: 3 dwords per owned pixel and channel, gathered.
 // The floor is the memory system: 4 bytes of id per pixel; 8 of α and β and 12 n_ch of gather per owned pixel; 4 n_ch written per
 // pixel.
@@ -3565,67 +3659,20 @@ __device__ __forceinline__ float interp_ch(bool isS, float alpha, float beta, fl
              : fmaf_(alpha, a, fmaf_(beta, b, gamma * c));  // (shade_bary_v)
 }
 __global__ __launch_bounds__(256) void k_interp(InterpArgs a) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
-  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
   const uint32_t C = a.n_ch;
-  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
-  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
-  for (uint32_t j = blockIdx.x >> 3;; j += step) {
-    uint32_t f, t;
-    if (a.n_frames >= 8u) {
-      f = sub + 8u * (j / tpf), t = j % tpf;
-      if (f >= a.n_frames) break;
-    } else {
-      const uint32_t i = j * 8u + sub;
-      if (i >= n_items) break;
-      f = i / tpf, t = i % tpf;
-    }
-    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
-    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
-    const TileRect rc = tile_rect(a, fd, f, lb, tx);
-    const int W = fd->width;
-    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
-    if (!(y <= rc.ty1 && x4 <= rc.tx1)) continue; // (no barrier in this kernel: a thread outside the frame just moves on)
-    const bool whole = (W & 3) == 0 && x4 + 3 <= rc.tx1;
-    const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
-    const size_t poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)x4;
-    const float *gv = a.vis + (size_t)f * a.vis_stride + poff; // plane 0 (z: never read)
-    float *go = rc.out0 + (size_t)ly * (size_t)W + (size_t)x4;
-    // ---- 1. owner ids (index + 1 | S class; 0 or an index outside the frame's triangles: nobody)
-    uint32_t id[4] = {0u, 0u, 0u, 0u};
-    if (whole) {
-      const uint4 q = *reinterpret_cast<const uint4 *>(gv + rc.plane);
-      id[0] = q.x, id[1] = q.y, id[2] = q.z, id[3] = q.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (x4 + k <= rc.tx1) id[k] = f2u(gv[rc.plane + k]);
-    }
-    const uint32_t n_tris = fd->n_tris;
-    uint32_t own = 0u;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if ((id[k] & ~S_CLASS_BIT) - 1u >= n_tris) id[k] = 0u; // (0 and the bare class bit wrap to 0xffffffff)
-      own |= id[k] != 0u ? 1u << k : 0u;
-    }
-    if (own == 0u && !fused) continue;
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const TileRect &rc = t.rc;
+    const bool fused = t.fused(a.flags_or);
+    const float *gv = a.vis + (size_t)t.f * a.vis_stride + t.poff; // plane 0 (z: never read)
+    float *go = t.out;
+    // ---- 1. owner ids
+    uint32_t id[4];
+    const uint32_t own = quad_ids(t, gv, id);
+    if (own == 0u && !fused) return;
     // ---- 2. α, β of a quad with an owner, each owner's γ by its class
-    float4 al = make_float4(0.f, 0.f, 0.f, 0.f), be = al, ga = al;
-    if (own != 0u) {
-      if (whole) {
-        al = *reinterpret_cast<const float4 *>(gv + 2 * rc.plane), be = *reinterpret_cast<const float4 *>(gv + 3 * rc.plane);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (x4 + k <= rc.tx1) quad_at(al, k) = gv[2 * rc.plane + k], quad_at(be, k) = gv[3 * rc.plane + k];
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) // (cover_s / cover_v)
-        quad_at(ga, k) = (id[k] & S_CLASS_BIT) ? 1.0f - quad_at(al, k) - quad_at(be, k) : 1.0f - (quad_at(al, k) + quad_at(be, k));
-    }
-    const SRZ_CAS float *at = as_const(a.attr) + (size_t)f * a.attr_frame_stride;
-    const bool quads = fused || own == 15u; // whole quads (fused clear, or four owners), else the owned pixels only
+    float4 al, be, ga;
+    quad_bary(t, gv, own, id, al, be, ga);
+    const SRZ_CAS float *at = as_const(a.attr) + (size_t)t.f * a.attr_frame_stride;
     // ---- 3. the channels, ATTR_CHUNK at a time
     for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
       const uint32_t nc = min(ATTR_CHUNK, C - c0);
@@ -3644,17 +3691,10 @@ __global__ __launch_bounds__(256) void k_interp(InterpArgs a) {
 #pragma unroll
       for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
         if (i >= nc) break;
-        float *p = go + (size_t)(c0 + i) * rc.plane;
-        if (quads) {
-          quad_store(p, rc.plane, {q[i]}, whole, x4, rc.tx1);
-        } else {
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (own & (1u << k)) p[k] = quad_at(q[i], k);
-        }
+        quad_store_owned(go + (size_t)(c0 + i) * rc.plane, t, {q[i]}, fused, own);
       }
     }
-  }
+  });
 }
 
 // ================================================================================================================
@@ -3720,9 +3760,7 @@ __device__ __forceinline__ void ig_emit(InterpTable &tb, uint32_t key, const flo
 }
 __global__ __launch_bounds__(256) void k_interp_grad(InterpArgs a) {
   __shared__ InterpTable tb;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
-  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
+  const int tid = threadIdx.x, lane = tid & 63;
   const uint32_t C = a.n_ch;
   const bool want_attr = a.gattr != nullptr, want_bary = a.out != nullptr;
   if (want_attr) {
@@ -3731,69 +3769,27 @@ __global__ __launch_bounds__(256) void k_interp_grad(InterpArgs a) {
     if (tid == 0) tb.n_used = 0u;
     __syncthreads();
   }
-  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
-  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
-  for (uint32_t j = blockIdx.x >> 3;; j += step) {
-    uint32_t f, t;
-    if (a.n_frames >= 8u) {
-      f = sub + 8u * (j / tpf), t = j % tpf;
-      if (f >= a.n_frames) break;
-    } else {
-      const uint32_t i = j * 8u + sub;
-      if (i >= n_items) break;
-      f = i / tpf, t = i % tpf;
-    }
-    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
-    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
-    const TileRect rc = tile_rect(a, fd, f, lb, tx);
-    const int W = fd->width;
-    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
-    const bool inside = y <= rc.ty1 && x4 <= rc.tx1; // (a thread outside the frame owns nothing, and still meets the barriers)
-    const bool whole = (W & 3) == 0 && x4 + 3 <= rc.tx1;
-    const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
-    const size_t poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)x4;
-    const float *gv = a.vis + (size_t)f * a.vis_stride + poff; // plane 0 (z: never read)
-    const float *gg = a.gout + (size_t)f * a.gout_stride + poff;
-    // ---- 1. owner ids (index + 1 | S class; 0 or an index outside the frame's triangles: nobody)
-    uint32_t id[4] = {0u, 0u, 0u, 0u};
-    if (inside) {
-      if (whole) {
-        const uint4 q = *reinterpret_cast<const uint4 *>(gv + rc.plane);
-        id[0] = q.x, id[1] = q.y, id[2] = q.z, id[3] = q.w;
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (x4 + k <= rc.tx1) id[k] = f2u(gv[rc.plane + k]);
-      }
-    }
-    const uint32_t n_tris = fd->n_tris;
-    uint32_t own = 0u, first = 0u;
+  pass_walk<true>(a, [&](const PassTile &t) { // (a thread outside the frame owns nothing, and still meets the barriers)
+    const TileRect &rc = t.rc;
+    const bool whole = t.whole;
+    const float *gv = a.vis + (size_t)t.f * a.vis_stride + t.poff; // plane 0 (z: never read)
+    const float *gg = a.gout + (size_t)t.f * a.gout_stride + t.poff;
+    // ---- 1. owner ids
+    uint32_t id[4], first = 0u;
+    const uint32_t own = quad_ids(t, gv, id);
     bool one_owner = true; // every owned pixel of the quad has the same triangle (either class)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      if ((id[k] & ~S_CLASS_BIT) - 1u >= n_tris) id[k] = 0u; // (0 and the bare class bit wrap to 0xffffffff)
       if (id[k] == 0u) continue;
-      own |= 1u << k;
       const uint32_t key = id[k] & ~S_CLASS_BIT;
       one_owner = one_owner && (first == 0u || first == key);
       first = first == 0u ? key : first;
     }
     // ---- 2. α, β of a quad with an owner, each owner's γ by its class
-    float4 al = make_float4(0.f, 0.f, 0.f, 0.f), be = al, ga = al;
-    if (own != 0u) {
-      if (whole) {
-        al = *reinterpret_cast<const float4 *>(gv + 2 * rc.plane), be = *reinterpret_cast<const float4 *>(gv + 3 * rc.plane);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (x4 + k <= rc.tx1) quad_at(al, k) = gv[2 * rc.plane + k], quad_at(be, k) = gv[3 * rc.plane + k];
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) // (cover_s / cover_v)
-        quad_at(ga, k) = (id[k] & S_CLASS_BIT) ? 1.0f - quad_at(al, k) - quad_at(be, k) : 1.0f - (quad_at(al, k) + quad_at(be, k));
-    }
-    const SRZ_CAS float *at = as_const(a.attr) + (size_t)f * a.attr_frame_stride;
-    float *gat = a.gattr + (size_t)f * a.attr_frame_stride;
+    float4 al, be, ga;
+    quad_bary(t, gv, own, id, al, be, ga);
+    const SRZ_CAS float *at = as_const(a.attr) + (size_t)t.f * a.attr_frame_stride;
+    float *gat = a.gattr + (size_t)t.f * a.attr_frame_stride;
     // the key a quad of one owner takes into the row's scan; 0: the quad emits its runs itself, or has none
     const uint32_t skey = want_attr && own != 0u && one_owner ? first : 0u;
     const bool scan = want_attr && __builtin_amdgcn_ballot_w64(skey != 0u) != 0ull; // (wave-uniform)
@@ -3899,18 +3895,10 @@ __global__ __launch_bounds__(256) void k_interp_grad(InterpArgs a) {
       if (tid == 0) tb.n_used = 0u;
       __syncthreads();
     }
-    // ---- 5. dα, dβ: whole quads (fused clear, or four owners), else the owned pixels only
-    if (want_bary && inside && (own != 0u || fused)) {
-      float *go = rc.out0 + (size_t)ly * (size_t)W + (size_t)x4;
-      if (fused || own == 15u) {
-        quad_store(go, rc.plane, {da, db}, whole, x4, rc.tx1);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (own & (1u << k)) go[k] = quad_at(da, k), go[rc.plane + k] = quad_at(db, k);
-      }
-    }
-  }
+    // ---- 5. dα, dβ
+    const bool fused = t.fused(a.flags_or);
+    if (want_bary && t.inside && (own != 0u || fused)) quad_store_owned(t.out, t, {da, db}, fused, own);
+  });
 }
 
 // ================================================================================================================
@@ -4008,7 +3996,7 @@ __global__ __launch_bounds__(256) void k_pos_grad(PosGradArgs a) {
     __syncthreads();
   }
   uint32_t par = 0u; // the tile's parity in this workgroup's walk (the same in every thread: nobody skips a tile)
-  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile): an inline copy of pass_walk
   const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
   for (uint32_t j = blockIdx.x >> 3;; j += step) {
     uint32_t f, t;
@@ -4289,7 +4277,7 @@ template <bool GRAD> __device__ __forceinline__ void aa_body(const AntialiasArgs
   const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
   const uint32_t C = a.n_ch;
   const bool want_out = !GRAD || a.out != nullptr, want_pos = GRAD && a.gpos != nullptr; // (kernel arguments: wave-uniform)
-  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile): an inline copy of pass_walk
   const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
   for (uint32_t j = blockIdx.x >> 3;; j += step) {
     uint32_t f, t;
@@ -4542,7 +4530,7 @@ __global__ __launch_bounds__(256) void k_tex(TexArgs a) {
   const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
   const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
   const uint32_t C = a.n_ch;
-  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile): an inline copy of pass_walk
   const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
   for (uint32_t j = blockIdx.x >> 3;; j += step) {
     uint32_t f, t;
@@ -4660,7 +4648,7 @@ __global__ __launch_bounds__(256) void k_tex_grad(TexArgs a) {
     if (tid == 0) tb.n_used = 0u;
     __syncthreads();
   }
-  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile): an inline copy of pass_walk
   const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
   for (uint32_t j = blockIdx.x >> 3;; j += step) {
     uint32_t f, t;
@@ -4850,54 +4838,15 @@ __device__ __forceinline__ DerivTri deriv_tri(const SRZ_CAS float *p) {
   return {(P[4] - P[7]) * r, (P[6] - P[3]) * r, (P[7] - P[1]) * r, (P[0] - P[6]) * r};
 }
 __global__ __launch_bounds__(256) void k_interp_deriv(InterpDerivArgs a) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
-  const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
   const uint32_t C = a.n_ch;
-  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
-  const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
-  for (uint32_t j = blockIdx.x >> 3;; j += step) {
-    uint32_t f, t;
-    if (a.n_frames >= 8u) {
-      f = sub + 8u * (j / tpf), t = j % tpf;
-      if (f >= a.n_frames) break;
-    } else {
-      const uint32_t i = j * 8u + sub;
-      if (i >= n_items) break;
-      f = i / tpf, t = i % tpf;
-    }
-    const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
-    const uint32_t lb = t / a.tiles_x, tx = t % a.tiles_x;
-    const TileRect rc = tile_rect(a, fd, f, lb, tx);
-    const int W = fd->width;
-    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
-    if (!(y <= rc.ty1 && x4 <= rc.tx1)) continue; // (no barrier in this kernel: a thread outside the frame just moves on)
-    const bool whole = (W & 3) == 0 && x4 + 3 <= rc.tx1;
-    const bool fused = ((fd->flags | a.flags_or) & SRZ_FUSED_CLEAR) != 0;
-    const size_t poff = (size_t)lb * BAND * (size_t)W + (size_t)ly * (size_t)W + (size_t)x4;
-    const float *gv = a.vis + (size_t)f * a.vis_stride + poff; // plane 0 (z: never read)
-    float *go = rc.out0 + (size_t)ly * (size_t)W + (size_t)x4;
-    // ---- 1. owner indices + 1 (0 or an index outside the frame's triangles: nobody)
-    uint32_t id[4] = {0u, 0u, 0u, 0u};
-    if (whole) {
-      const uint4 q = *reinterpret_cast<const uint4 *>(gv + rc.plane);
-      id[0] = q.x, id[1] = q.y, id[2] = q.z, id[3] = q.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (x4 + k <= rc.tx1) id[k] = f2u(gv[rc.plane + k]);
-    }
-    const uint32_t n_tris = fd->n_tris;
-    uint32_t own = 0u;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      id[k] &= ~S_CLASS_BIT;
-      if (id[k] - 1u >= n_tris) id[k] = 0u; // (0 wraps to 0xffffffff)
-      own |= id[k] != 0u ? 1u << k : 0u;
-    }
-    if (own == 0u && !fused) continue;
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool fused = t.fused(a.flags_or);
+    // ---- 1. owner indices + 1 (the class bit dropped)
+    uint32_t id[4];
+    const uint32_t own = quad_ids<~S_CLASS_BIT>(t, a.vis + (size_t)t.f * a.vis_stride + t.poff, id);
+    if (own == 0u && !fused) return;
     // ---- 2. ∇α, ∇β of each owner, gathered once per run of one owner
-    const SRZ_CAS float *tpos = as_const(a.tri_pos) + (size_t)fd->tri_off * a.pos_stride;
+    const SRZ_CAS float *tpos = as_const(a.tri_pos) + (size_t)t.fd->tri_off * a.pos_stride;
     DerivTri T[4] = {};
     {
       uint32_t prev = 0u;
@@ -4909,8 +4858,7 @@ __global__ __launch_bounds__(256) void k_interp_deriv(InterpDerivArgs a) {
         T[k] = cur;
       }
     }
-    const SRZ_CAS float *at = as_const(a.attr) + (size_t)f * a.attr_frame_stride;
-    const bool quads = fused || own == 15u; // whole quads (fused clear, or four owners), else the owned pixels only
+    const SRZ_CAS float *at = as_const(a.attr) + (size_t)t.f * a.attr_frame_stride;
     // ---- 3. the channels, ATTR_CHUNK at a time
     for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
       const uint32_t nc = min(ATTR_CHUNK, C - c0);
@@ -4932,17 +4880,10 @@ __global__ __launch_bounds__(256) void k_interp_deriv(InterpDerivArgs a) {
 #pragma unroll
       for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
         if (i >= nc) break;
-        float *p = go + (size_t)(2u * (c0 + i)) * rc.plane;
-        if (quads) {
-          quad_store(p, rc.plane, {qx[i], qy[i]}, whole, x4, rc.tx1);
-        } else {
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (own & (1u << k)) p[k] = quad_at(qx[i], k), p[rc.plane + k] = quad_at(qy[i], k);
-        }
+        quad_store_owned(t.out + (size_t)(2u * (c0 + i)) * t.rc.plane, t, {qx[i], qy[i]}, fused, own);
       }
     }
-  }
+  });
 }
 
 // ================================================================================================================
@@ -5032,7 +4973,7 @@ __global__ __launch_bounds__(256) void k_tex_mip(TexMipArgs a) {
   const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
   const uint32_t C = a.n_ch;
   const bool wrap = a.mode == SRZ_TEX_WRAP;
-  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile): an inline copy of pass_walk
   const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
   for (uint32_t j = blockIdx.x >> 3;; j += step) {
     uint32_t f, t;
@@ -5160,7 +5101,7 @@ __global__ __launch_bounds__(256) void k_tex_mip_grad(TexMipArgs a) {
     __syncthreads();
   }
   uint32_t turn = 0u; // the tile's count in this workgroup's walk mod 3 (the same in every thread: nobody skips a tile)
-  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile), as k_shade_vis does
+  // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile): an inline copy of pass_walk
   const uint32_t sub = blockIdx.x & 7u, step = gridDim.x >> 3;
   for (uint32_t j = blockIdx.x >> 3;; j += step) {
     uint32_t f, t;
