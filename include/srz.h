@@ -60,6 +60,7 @@ extern "C" {
  *      (additive, same version) mipmapped texture sampling over a visibility buffer, with gradients srz_texture_mip_levels /
  *      srz_texture_mip_bytes / srz_texture_mip_build / srz_texture_mip_fold / srz_frameset_interpolate_deriv /
  *      srz_frameset_texture_mip / srz_frameset_texture_mip_grad, SRZ_TEX_MAX_LEVELS
+ *      (additive, same version) depth peeling: the layer behind a visibility buffer srz_frameset_peel_visibility
  */
 #define SRZ_ABI_VERSION 7
 
@@ -298,6 +299,30 @@ int srz_frameset_render(srz_ctx *ctx, srz_frameset *fs, void *d_out, size_t out_
  * srz_frameset_allgather / _allgather_inplace / _deinterleave / _read_gathered_frame and the tile-sparse exchange unchanged, as
  * SRZ_EXCHANGE_PLANES.  No texture has to be uploaded; the render files no sample of the side clear's grid measurement. */
 int srz_frameset_render_visibility(srz_ctx *ctx, srz_frameset *fs, void *d_out, size_t out_bytes, uint32_t flags, void *stream);
+/* DEPTH PEELING: the layer BEHIND a visibility buffer.  d_prev: a visibility buffer of THIS set with its current geometry — layer k,
+ * from srz_frameset_render_visibility or from this call; d_out receives layer k + 1 in the same layout, [frame][z, id, alpha, beta]
+ * [local_rows][width], so every pass over a visibility buffer (shade, G-buffer, motion, interpolate, texture, antialias and their
+ * gradients) works on every layer unchanged.  Size, 16-byte alignment (of both), stream semantics, local_rows and band sharding as
+ * srz_frameset_render_visibility; asynchronous, no host synchronisation beyond what a render has (the tile-list pool's growth); a
+ * sceneset runs its vertex stage first; no sample of the side clear's grid measurement.  Any overlap of the two buffers is
+ * SRZ_E_INVALID.  Flags: the render's mask; SRZ_UNIFIED means what it means for a render, SRZ_ORDERED_RASTER is accepted and has no
+ * effect, and all four words of EVERY pixel are written, as by a render with SRZ_FUSED_CLEAR (implied).
+ * THE RULE, per pixel, with zp, idp the words of d_prev, wp = (idp & 0x7fffffff) - 1 and sp = idp >> 31:
+ *   the pixel has ENDED if idp == 0, or wp >= the frame's triangle count, or zp is NaN: the output is nobody (+inf, 0, 0, 0).
+ *   Otherwise take every FRAGMENT of the frame at that pixel as the renders compute it — coverage and class the reference's (V in the
+ *   8-wide columns of the owner's bounding box, S in its scalar tail; with SRZ_UNIFIED every fragment is V), depth the class's own z
+ *   expression: a fragment is (z, w = triangle index in the frame, s = class); one whose z is NaN is never taken.  The fragments of a
+ *   pixel are ORDERED by z ascending (float comparison: +0 == -0); at equal z the S fragments come first, by w descending, then the V
+ *   fragments, by w ascending — the renders' "last S at that depth, else first V" as a total order.  The output is the first
+ *   fragment in that order STRICTLY AFTER (zp, wp, sp), or nobody if there is none: z, (w + 1) | s << 31, and alpha and beta exactly
+ *   as the shaders use them (srz_frameset_render_visibility).
+ * Consequences: for frames without NaN depths layer k + 1 is what the reference renders when, at every pixel, the owners of layers
+ * 1..k are not drawn.  Peeling until a layer is all nobody visits every (triangle, pixel) pair of srz_stats.fragments exactly once.
+ * A d_prev whose every pixel is (z = -inf, id = 1) gives layer 1: for frames of finite depths bit-identical to
+ * srz_frameset_render_visibility on all four planes.  d_prev is only COMPARED, never used as an index: any words in it give defined
+ * output and no out-of-range access. */
+int srz_frameset_peel_visibility(srz_ctx *ctx, srz_frameset *fs, const void *d_prev, void *d_out, size_t out_bytes,
+                                 uint32_t flags, void *stream);
 /* The COLOUR of a visibility buffer: rasterise once (srz_frameset_render_visibility), shade many times — new lights, ka / ks / p, shader
  * types (srz_frameset_update_shading, srz_sceneset_update).  d_vis: a visibility buffer of THIS set on this ctx's shard; d_out: a buffer
  * in the layout of srz_frameset_render.  Size (srz_frameset_out_bytes, for each of the two), 16-byte alignment of both, the flag mask,
@@ -858,7 +883,7 @@ int srz_verify_fastpow(srz_ctx *ctx, float p, uint64_t *out4);
  * out5 = { pairs, results that differ although the flag was clear (must be 0), flagged random pairs, flagged Pythagorean pairs,
  * flagged few-significant-bit pairs }. */
 int srz_verify_fastlen(srz_ctx *ctx, uint64_t *out5);
-/* diagnostic only (tests): counters the LAST render of the set left — out6 = { tiles taken by the ordered rasteriser, tiles the FAST
+/* diagnostic only (tests): counters the LAST render of the set left — out6 = { tiles taken by the ordered rasteriser (after srz_frameset_peel_visibility: tiles fed from the frame's stream), tiles the FAST
  * shading builds handed to the generic build, capacity of a tile-list sub-pool, largest demand a sub-pool reported, workgroups of the
  * side-stream clear (a batch-sized set measures them on the device within its first 24 renders, and again every 4096), 1 once that measurement has been taken }; waits for the device */
 int srz_frameset_debug_counters(srz_ctx *ctx, srz_frameset *fs, uint32_t *out6);

@@ -323,16 +323,20 @@ void free_frameset_buffers(srz_frameset *fs) {
 // What a render asks for.  VISIBILITY: k_visibility writes the visibility buffer where k_shade would write colour (no texture needed; no
 // sample of the clear's grid measurement).  COUNTING: the counters of srz_stats (the reference's ordered walk).  SIZE_ONLY: the creation-
 // time pass of srz_frameset_create / srz_sceneset_create — setup + binning of every sub-batch, which size the tile-list pool, nothing else.
+// PEEL (srz_frameset_peel_visibility): a VISIBILITY render whose rasteriser is k_peel — the layer behind d_prev instead of the nearest one.
 struct Pass {
-  enum Kind { COLOUR, VISIBILITY, COUNTING, SIZE_ONLY } kind = COLOUR;
+  enum Kind { COLOUR, VISIBILITY, COUNTING, SIZE_ONLY, PEEL } kind = COLOUR;
   int f_begin = 0, f_count = -1; // only frames [f_begin, f_begin + f_count) of the set (-1: all); d_out is the whole set's buffer either way
   bool one_frame_scratch = false; // a counting run whose pixels nobody reads: every frame writes the SAME one-frame buffer
+  const float *d_prev = nullptr;  // PEEL: the previous layer, laid out like d_out
   static Pass colour() { return {}; }
   static Pass colour_frames(int f_begin, int f_count) { return {COLOUR, f_begin, f_count}; }
   static Pass visibility() { return {VISIBILITY}; }
   static Pass counting() { return {COUNTING}; }
   static Pass counting_into_one_frame() { return {COUNTING, 0, -1, true}; }
   static Pass size_only() { return {SIZE_ONLY}; }
+  static Pass peel(const float *d_prev) { return {PEEL, 0, -1, false, d_prev}; }
+  bool writes_visibility() const { return kind == VISIBILITY || kind == PEEL; } // (k_visibility behind the rasteriser, no clear-grid sample)
 };
 
 // the render's flags or some frame's have `bit`
@@ -540,7 +544,7 @@ int plan_clear(srz_ctx *ctx, srz_frameset *fs, const Pass &pass, bool detailed, 
   srz_frameset::ClearTune &ct = fs->clear_tune;
   p = ClearPlan{ctx->env_clear_wgs ? ctx->env_clear_wgs : ct.wgs};
   if (ctx->env_clear_wgs || !ct.d_ctl) return SRZ_OK;
-  p.rebase = pass.kind == Pass::VISIBILITY && !ct.done; // (the grid in effect; the next colour render's sample then times itself alone)
+  p.rebase = pass.writes_visibility() && !ct.done; // (the grid in effect; the next colour render's sample then times itself alone)
   if (pass.kind != Pass::COLOUR || pass.f_count >= 0) return SRZ_OK;
   if (ct.done && !detailed && ++ct.since >= srz_frameset::CLEAR_TUNE_AGAIN) {
     // what the clear runs beside may have changed (srz_sceneset_update): measure again (<= 18 of 4096 renders)
@@ -625,16 +629,18 @@ int enqueue_sub_batch(srz_ctx *ctx, srz_frameset *fs, const RenderPlan &r, Rende
     HIP_TRY(ctx, copy_demand(fs, part, ctx->stream2));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_join[ev], ctx->stream2));
   }
-  launch_raster(v, n, stats, s);
+  // (a peel: k_peel in k_raster's place, reading the previous layer at the same frame offset as v.out)
+  if (r.pass.kind == Pass::PEEL) launch_peel(v, r.pass.d_prev + (v.out - a.out), n, s);
+  else launch_raster(v, n, stats, s);
   if (r.turns) {
     HIP_TRY(ctx, hipEventRecord(ctx->ev_raster[ctx->raster_next++ % srz_ctx::EV_RING], s));
     ctx->raster_last_stream = s, ctx->raster_valid = true;
   }
   if (r.ep) HIP_TRY(ctx, hipEventRecord(r.ep->t2, s));
-  if (r.pass.kind == Pass::VISIBILITY) launch_visibility(v, tiles, s);
+  if (r.pass.writes_visibility()) launch_visibility(v, tiles, s);
   else launch_shade(v, tiles, stats, fs->fast_kinds, fs->any_generic, fs->approx_shade, s);
   if (r.side) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join[ev], 0));
-  else if (!raster_four_waves(v)) // (the latency build of k_raster stores the demand itself)
+  else if (r.pass.kind == Pass::PEEL || !raster_four_waves(v)) // (the latency build of k_raster stores the demand itself)
     HIP_TRY(ctx, copy_demand(fs, part, s));
   return SRZ_OK;
 }
@@ -1521,6 +1527,22 @@ int srz_frameset_render(srz_ctx *ctx, srz_frameset *fs, void *d_out, size_t out_
 
 int srz_frameset_render_visibility(srz_ctx *ctx, srz_frameset *fs, void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
   return render_entry("srz_frameset_render_visibility", ctx, fs, d_out, out_bytes, flags, stream, Pass::visibility());
+}
+
+int srz_frameset_peel_visibility(srz_ctx *ctx, srz_frameset *fs, const void *d_prev, void *d_out, size_t out_bytes, uint32_t flags,
+                                 void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_peel_visibility");
+  if (!fs || !d_prev || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / previous layer / output");
+  const size_t bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < bytes) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
+  if (!aligned<16>({d_prev, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
+  // (a tile's wave writes its pixels of d_out while other tiles' still read theirs of d_prev, and k_clear writes beside both)
+  if (ranges_overlap({d_prev, bytes}, {d_out, bytes})) return fail(ctx, SRZ_E_INVALID, fn + ": the previous layer and the output overlap");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // every pixel's four words are written: a fused-clear render with k_peel in k_raster's place
+  return render_impl(ctx, fs, (float *)d_out, (flags & FRAME_FLAGS) | SRZ_FUSED_CLEAR, pick_stream(ctx, stream),
+                     Pass::peel(static_cast<const float *>(d_prev)));
 }
 
 int srz_frameset_shade_visibility(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void *d_out, size_t out_bytes, uint32_t flags,

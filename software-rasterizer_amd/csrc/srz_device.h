@@ -232,6 +232,9 @@ void launch_chunks(const RenderArgs &a, int n_frames, uint32_t max_tris, hipStre
 void launch_setup(const RenderArgs &a, int n_frames, uint32_t max_tris, bool stats, hipStream_t s);
 void launch_bin(const RenderArgs &a, int n_frames, uint32_t max_tris, hipStream_t s);
 void launch_raster(const RenderArgs &a, int n_frames, bool stats, hipStream_t s);
+// srz_frameset_peel_visibility: in place of launch_raster (k_peel; neither k_raster nor k_raster_slow runs).  prev: the previous layer,
+// offset like a.out
+void launch_peel(const RenderArgs &a, const float *prev, int n_frames, hipStream_t s);
 bool raster_four_waves(const RenderArgs &a); // the latency build of k_raster serves this job (it also reports the pool's demand)
 void launch_clear(const RenderArgs &a, uint32_t max_tiles, hipStream_t s, uint32_t wgs);
 // kinds: bit k = some frame is shaded by FAST build kind k (frame_kind); approx: the tolerance mode's builds serve kinds 0..3

@@ -23,6 +23,9 @@
 //                                          themselves (with their list's length and offset) to their frame's work list.
 //   k_raster_slow  one wave per listed tile the reference's ORDERED algorithm for what the keys cannot express (NaN / ±0
 //                                          depths), for bands that did not fit the pool, and for counting runs.
+//   k_peel    one wave per touched tile    (srz_frameset_peel_visibility, in k_raster's place) DEPTH PEELING: per pixel the first
+//                                          fragment strictly behind the previous layer's in the visibility order, fed from the
+//                                          tile's list or, for bands that did not fit the pool, from the frame's stream.
 //   k_shade   one WORKGROUP per owned tile VISIBILITY-FIRST SHADING: each pixel's final owner is shaded exactly once (the
 //                                          reference's shaders are pure functions of (triangle,pixel) and its write is an
 //                                          overwrite), pixels compacted by semantics class into dense 64-lane chunks; the tile's
@@ -2344,6 +2347,223 @@ __global__ __launch_bounds__(64) void k_raster_slow(RenderArgs a) {
       if (n_frag) atomicAdd(&a.stats[ST_FRAGMENTS], n_frag);
       if (n_shaded) atomicAdd(&a.stats[ST_SHADED], n_shaded);
     }
+  }
+}
+
+// ================================================================================================================
+// k_peel — DEPTH PEELING (srz_frameset_peel_visibility, the rule: include/srz.h): layer k + 1 of a visibility buffer
+// from layer k (`prev`, this render's frames as `a.out` has them).  It takes k_raster's place in a render: one wave per tile with
+// k_raster<1>'s XCD-aware tile assignment and early-outs; k_visibility behind it writes id / alpha / beta as for any layer 1.
+// Per pixel the fragments are totally ordered by (z as a float, tie-break) with k_raster's tie-breaks — 0x7ffffffe - idx (S, the
+// later the smaller) < 0x80000000 | idx (V, the earlier the smaller): "last S at that depth, else first V" — and the output is the
+// smallest fragment strictly above prev's.  The tile holds prev's (z, tie-break) and the best candidate's in four LDS planes (16 KB:
+// ten waves per CU); an ENDED pixel (id 0 or out of range, NaN depth, beyond the frame's edge) holds (+inf, PEEL_NOBODY), above
+// which nothing lies.  The order does not depend on the sequence of the fragments, so a listed tile feeds the sweep from its list
+// in the pool (64 entries per load, as k_raster) and a tile of an UNLISTED band from the frame's stream (chunk_rows and the
+// bounding boxes, as k_raster_slow: counted in slow_count[0]).  A wave's LDS operations are ordered: no atomics.  prev is compared,
+// never used as an index.  The render is always a fused-clear one (the host ors the flag in).
+// (inline copies, each names its definition: the cleared tile of k_raster; the per-lane geometry, the broadcast, the V and S
+// sweeps and the write-out of k_raster_slow — as helpers they would have to leave k_raster_slow's registers as they are)
+// ================================================================================================================
+constexpr uint32_t PEEL_NOBODY = 0xffffffffu; // the tie-break of no fragment: above every fragment's
+__global__ __launch_bounds__(64) void k_peel(RenderArgs a, const float *prev) {
+  __shared__ __attribute__((aligned(16))) float s_zp[TILE * LDS_STRIDE], s_bz[TILE * LDS_STRIDE];
+  __shared__ __attribute__((aligned(16))) uint32_t s_tp[TILE * LDS_STRIDE], s_bt[TILE * LDS_STRIDE];
+  const int lane = threadIdx.x & 63;
+  // (k_raster's XCD-aware tile assignment)
+  const uint32_t wg = blockIdx.x;
+  const uint32_t xcd = wg & 7u, j0 = wg >> 3;
+  const uint32_t tiles_per_frame = a.n_local_bands * a.tiles_x;
+  const uint32_t frame = (j0 / tiles_per_frame) * 8u + xcd, tile = j0 % tiles_per_frame;
+  if (frame >= a.n_frames) return;
+  const u32x2 tinfo = as_const(reinterpret_cast<const u32x2 *>(a.tile_info))[(size_t)frame * tiles_per_frame + tile];
+  const uint32_t cnt = tinfo.x;
+  if (cnt == 0u && !a.clear_in_raster) return; // (k_clear's tile)
+  const SRZ_CAS FrameDesc *fd = as_const(a.frames) + frame;
+  const uint32_t flags = fd->flags | a.flags_or;
+  const uint32_t lb = tile / a.tiles_x, tx = tile % a.tiles_x;
+  const int W = fd->width;
+  const uint32_t n_tris = fd->n_tris;
+  const TileRect rc = tile_rect(a, fd, frame, lb, tx);
+  const bool vec_ok = (W & 3) == 0;
+  const float inf = __builtin_inff();
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (cnt == 0u) { // nothing listed: the clear itself (k_raster's cnt == 0 branch)
+    const float4 inf4 = make_float4(inf, inf, inf, inf);
+    for (int it = 0; it < 4; ++it) {
+      const int ly = it * 8 + (lane >> 3), x4 = rc.tx0 + (lane & 7) * 4;
+      if (rc.ty0 + ly > rc.ty1 || x4 > rc.tx1) continue;
+      quad_store(rc.out0 + (size_t)ly * W + x4, rc.plane, {inf4, zero4, zero4, zero4}, vec_ok && x4 + 3 <= rc.tx1, x4, rc.tx1);
+    }
+    return;
+  }
+  const uint32_t off = tinfo.y;
+  const bool listed = off != UNLISTED; // wave-uniform
+  const uint32_t idx_mask = (fd->flags & FD_PACKED) ? PACK_IDX_MASK : 0xffffffffu; // (a packed list entry = index | batch << 22)
+  if (!listed && lane == 0) atomicAdd(a.slow_count, 1u);
+  // ---- init: prev's (z, tie-break) per pixel, best = nobody ----------------------------------------------------------------
+  const float *pz = prev + (rc.out0 - a.out); // (plane 0 of prev at row ty0: the two buffers share one layout)
+  for (int i = lane; i < TILE * TILE; i += 64) {
+    const int ly = i >> 5, lx = i & 31;
+    float zp = inf;
+    uint32_t tp = PEEL_NOBODY;
+    if (rc.tx0 + lx <= rc.tx1 && rc.ty0 + ly <= rc.ty1) {
+      const size_t o = (size_t)ly * W + rc.tx0 + lx;
+      const float z = pz[o];
+      const uint32_t id = f2u(pz[rc.plane + o]);
+      const uint32_t wp = (id & 0x7fffffffu) - 1u; // (id 0, or only the class bit: 0xffffffff, out of range)
+      if (id != 0u && wp < n_tris && z == z) zp = z, tp = (id & S_CLASS_BIT) ? 0x7ffffffeu - wp : (0x80000000u | wp);
+    }
+    s_zp[ly * LDS_STRIDE + lx] = zp, s_tp[ly * LDS_STRIDE + lx] = tp;
+    s_bz[ly * LDS_STRIDE + lx] = inf, s_bt[ly * LDS_STRIDE + lx] = PEEL_NOBODY;
+  }
+  __builtin_amdgcn_wave_barrier();
+  // ---- feed: 64 triangles per round, from the tile's list or from the frame's stream -----------------------------------------
+  const SRZ_CAS u32x2 *bbox = as_const(reinterpret_cast<const u32x2 *>(a.bbox + fd->tri_off));
+  const SRZ_CAS float *tpos = as_const(a.tri_pos) + (size_t)fd->tri_off * a.pos_stride;
+  const SRZ_CAS uint32_t *chunk_rows = as_const(a.chunk_rows) + fd->chunk_off;
+  const uint32_t n_rounds = ((listed ? cnt : n_tris) + 63u) / 64u;
+  for (uint32_t c = 0; c < n_rounds; ++c) {
+    uint32_t my;
+    bool valid;
+    if (listed) {
+      const uint32_t e = c * 64u + (uint32_t)lane;
+      my = as_const(a.pool)[off + min(e, cnt - 1u)] & idx_mask;
+      valid = e < cnt;
+    } else {
+      const uint32_t cr = chunk_rows[c]; // wave-uniform
+      if ((int)(int16_t)(cr & 0xffffu) > rc.ty1 || (int)(int16_t)(cr >> 16) < rc.ty0) continue;
+      my = c * 64u + (uint32_t)lane;
+      valid = my < n_tris;
+    }
+    // (from here to the update rule: k_raster_slow's phase B)
+    const u32x2 bb = bbox[min(my, n_tris - 1u)];
+    const int bsx = (int16_t)(bb.x & 0xffff), bsy = (int16_t)(bb.x >> 16), bex = (int16_t)(bb.y & 0xffff), bey = (int16_t)(bb.y >> 16);
+    const bool hit = valid && bsx <= bex && bex >= rc.tx0 && bsx <= rc.tx1 && bey >= rc.ty0 && bsy <= rc.ty1;
+    unsigned long long m = __ballot(hit);
+    if (m == 0ull) continue;
+    TriXY t;
+    t.ax = t.ay = t.bx = t.by = t.cx = t.cy = t.z0 = t.z1 = t.z2 = t.v_inv = t.s_area = 0.0f;
+    // [4:0] x0  [9:5] x1  [14:10] y0  [19:15] y1  [25:20] v = first scalar-tail column  [27:26] / [29:28] log2(block width) - 2 of the V / S sweep
+    uint32_t geom = 0;
+    if (hit) {
+      float p[9];
+      load_pos9(tpos + (size_t)my * a.pos_stride, p);
+      t.ax = p[0], t.ay = p[1], t.z0 = p[2], t.bx = p[3], t.by = p[4], t.z1 = p[5], t.cx = p[6], t.cy = p[7], t.z2 = p[8];
+      BranchMath bm;
+      tri_consts(bm, t);
+      const int x0 = max(bsx, rc.tx0) - rc.tx0, x1 = min(bex, rc.tx1) - rc.tx0, y0 = max(bsy, rc.ty0) - rc.ty0, y1 = min(bey, rc.ty1) - rc.ty0;
+      const int vend = (flags & SRZ_UNIFIED) ? bex + 1 : bsx + ((bex - bsx + 1) & ~7);
+      const int v = min(max(vend - rc.tx0, x0), x1 + 1);
+      const int h = y1 - y0 + 1, wv = v - x0, ws = x1 + 1 - v;
+      auto pick = [h](int w) {
+        const int n88 = ((w + 7) >> 3) * ((h + 7) >> 3), n164 = ((w + 15) >> 4) * ((h + 3) >> 2), n416 = ((w + 3) >> 2) * ((h + 15) >> 4);
+        int l = 3;
+        if (n164 < n88 && n164 <= n416) l = 4;
+        if (n416 < n88 && n416 < n164) l = 2;
+        return l;
+      };
+      geom = (uint32_t)x0 | ((uint32_t)x1 << 5) | ((uint32_t)y0 << 10) | ((uint32_t)y1 << 15) | ((uint32_t)v << 20) |
+             ((uint32_t)(pick(wv) - 2) << 26) | ((uint32_t)(pick(ws) - 2) << 28);
+    }
+    while (m) {
+      const int j = __builtin_ctzll(m);
+      m &= m - 1;
+      // broadcast triangle j to the wave (uniform values → SGPRs)
+      TriXY u;
+      u.ax = rl_f(t.ax, j), u.ay = rl_f(t.ay, j), u.bx = rl_f(t.bx, j), u.by = rl_f(t.by, j), u.cx = rl_f(t.cx, j);
+      u.cy = rl_f(t.cy, j), u.z0 = rl_f(t.z0, j), u.z1 = rl_f(t.z1, j), u.z2 = rl_f(t.z2, j);
+      u.v_inv = rl_f(t.v_inv, j), u.s_area = rl_f(t.s_area, j);
+      const uint32_t idx = (uint32_t)rl_i((int)my, j);
+      const uint32_t g = (uint32_t)rl_i((int)geom, j);
+      const int x0 = g & 31, x1 = (g >> 5) & 31, y0 = (g >> 10) & 31, y1 = (g >> 15) & 31, vx = (g >> 20) & 63;
+      if (y1 < y0) continue; // (cannot happen for a hit; keeps the loops well-formed)
+      if (vx > x0) { // ---- "V" sweep over columns [x0, vx-1] (k_raster_slow's) ----------------------------------------
+        const uint32_t tb = 0x80000000u | idx; // (uniform per triangle)
+        const int lbw = (int)((g >> 26) & 3) + 2, bw = 1 << lbw, bh = 64 >> lbw;
+        const int lx = lane & (bw - 1), ly = lane >> lbw;
+        for (int yb = y0; yb <= y1; yb += bh) {
+          const int yl = yb + ly;
+          const float fy = (float)(rc.ty0 + yl);
+          const float PBy = u.by - fy, PCy = u.cy - fy, PAy = u.ay - fy;
+          const bool rowok = yl <= y1;
+          for (int xb = x0; xb < vx; xb += bw) {
+            const int xl = xb + lx;
+            const float fx = (float)(rc.tx0 + xl);
+            const float PBx = u.bx - fx, PCx = u.cx - fx, PAx = u.ax - fx;
+            const float aPBC = fmsubf(PBx, PCy, PCx * PBy), aPCA = fmsubf(PCx, PAy, PAx * PCy);
+            const float al = aPBC * u.v_inv, be = aPCA * u.v_inv, ga = 1.0f - (al + be);
+            const float z = fmaf_(al, u.z0, fmaf_(be, u.z1, ga * u.z2));
+            const int li = min(yl * LDS_STRIDE + xl, TILE * LDS_STRIDE - 1); // clamped: idle lanes read a valid word
+            const bool inside = rowok & (xl < vx) & (al > 0.0f) & (be > 0.0f) & (ga > 0.0f) & (ga < 1.0f);
+            // the update rule: strictly after prev's fragment, strictly before the best so far (a NaN z compares false throughout)
+            const float zp = s_zp[li], bz = s_bz[li];
+            const bool after = (z > zp) | ((z == zp) & (tb > s_tp[li]));
+            const bool before = (z < bz) | ((z == bz) & (tb < s_bt[li]));
+            if (inside & after & before) s_bz[li] = z, s_bt[li] = tb;
+          }
+        }
+      }
+      if (vx <= x1) { // ---- scalar-tail "S" sweep over columns [vx, x1] (k_raster_slow's) ------------------------------
+        const uint32_t tb = 0x7ffffffeu - idx;
+        const int lbw = (int)((g >> 28) & 3) + 2, bw = 1 << lbw, bh = 64 >> lbw;
+        const int lx = lane & (bw - 1), ly = lane >> lbw;
+        const float ABx = u.bx - u.ax, ABy = u.by - u.ay, BCx = u.cx - u.bx, BCy = u.cy - u.by, CAx = u.ax - u.cx,
+                    CAy = u.ay - u.cy;
+        for (int yb = y0; yb <= y1; yb += bh) {
+          const int yl = yb + ly;
+          const float fy = (float)(rc.ty0 + yl);
+          const bool rowok = yl <= y1;
+          for (int xb = vx; xb <= x1; xb += bw) {
+            const int xl = xb + lx;
+            const float fx = (float)(rc.tx0 + xl);
+            // insideTriangle (src/Rasterizer.cpp:11-41)
+            const float APx = fx - u.ax, APy = fy - u.ay, BPx = fx - u.bx, BPy = fy - u.by, CPx = fx - u.cx, CPy = fy - u.cy;
+            const float e0 = ABx * APy - ABy * APx, e1 = BCx * BPy - BCy * BPx, e2 = CAx * CPy - CAy * CPx;
+            const bool in_tri = ((e0 > 0) & (e1 > 0) & (e2 > 0)) | ((e0 < 0) & (e1 < 0) & (e2 < 0));
+            // barycentric (scalar) + z (src/Rasterizer.cpp:43-70,473)
+            const float PAx = u.ax - fx, PAy = u.ay - fy, PBx = u.bx - fx, PBy = u.by - fy, PCx = u.cx - fx, PCy = u.cy - fy;
+            const float aPBC = PBx * PCy - PBy * PCx, aPCA = PCx * PAy - PCy * PAx;
+            const float al = aPBC / u.s_area, be = aPCA / u.s_area, ga = 1.0f - al - be;
+            const float z = al * u.z0 + be * u.z1 + ga * u.z2;
+            const int li = min(yl * LDS_STRIDE + xl, TILE * LDS_STRIDE - 1);
+            const bool inside = rowok & (xl <= x1) & in_tri;
+            const float zp = s_zp[li], bz = s_bz[li];
+            const bool after = (z > zp) | ((z == zp) & (tb > s_tp[li]));
+            const bool before = (z < bz) | ((z == bz) & (tb < s_bt[li]));
+            if (inside & after & before) s_bz[li] = z, s_bt[li] = tb;
+          }
+        }
+      }
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  // ---- write-out (k_raster_slow's phase C; the tie-breaks decode as in k_raster's) ------------------------------------------
+  uint4 id4[4];
+  bool any_owner = false;
+  for (int it = 0; it < 4; ++it) {
+    const uint4 q = *reinterpret_cast<const uint4 *>(&s_bt[(it * 8 + (lane >> 3)) * LDS_STRIDE + (lane & 7) * 4]);
+    any_owner |= (q.x & q.y & q.z & q.w) != PEEL_NOBODY;
+    auto id_of = [](uint32_t tb) { return tb == PEEL_NOBODY ? NO_TRI : (tb & 0x80000000u) ? (tb & 0x7fffffffu) : ((0x7ffffffeu - tb) | S_CLASS_BIT); };
+    id4[it] = make_uint4(id_of(q.x), id_of(q.y), id_of(q.z), id_of(q.w));
+  }
+  const bool tile_has_owner = __ballot(any_owner) != 0ull; // wave-uniform
+  for (int it = 0; it < 4; ++it) {
+    const int ly = it * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
+    const int y = rc.ty0 + ly, x4 = rc.tx0 + lx4;
+    if (y > rc.ty1 || x4 > rc.tx1) continue;
+    const float4 z4 = *reinterpret_cast<const float4 *>(&s_bz[ly * LDS_STRIDE + lx4]);
+    float *gz = rc.out0 + (size_t)ly * W + x4;
+    const bool full = vec_ok && x4 + 3 <= rc.tx1;
+    if (tile_has_owner)
+      quad_store(gz, rc.plane, {z4}, full, x4, rc.tx1);
+    else // touched by a bbox but owned by nobody in this layer: the clear itself
+      quad_store(gz, rc.plane, {z4, zero4, zero4, zero4}, full, x4, rc.tx1);
+  }
+  if (tile_has_owner) { // the owners of all of the tile's pixels, by index (32 bits each), and the tile's work entry
+    uint32_t *slot = a.vis + ((size_t)frame * tiles_per_frame + tile) * PIX_SLOT;
+    for (int it = 0; it < 4; ++it) ids_store4(slot, (uint32_t)((it * 8 + (lane >> 3)) * TILE + (lane & 7) * 4), id4[it], false, false);
+    if (lane == 0) work_append(a, fd->flags, frame * tiles_per_frame + tile, work_entry(frame, lb, tx, false, false, 0u, 0u));
   }
 }
 
@@ -5929,6 +6149,12 @@ void launch_raster(const RenderArgs &a, int n_frames, bool stats, hipStream_t s)
     hipLaunchKernelGGL(k_raster_slow<true>, dim3(slow_grid), dim3(64), 0, s, a);
   else
     hipLaunchKernelGGL(k_raster_slow<false>, dim3(slow_grid), dim3(64), 0, s, a);
+}
+
+void launch_peel(const RenderArgs &a, const float *prev, int n_frames, hipStream_t s) {
+  if (n_frames <= 0 || a.n_local_bands == 0) return;
+  const uint32_t groups = ((uint32_t)n_frames + 7u) / 8u;
+  hipLaunchKernelGGL(k_peel, dim3(groups * 8u * a.n_local_bands * a.tiles_x), dim3(64), 0, s, a, prev); // (k_raster<1>'s grid)
 }
 
 void launch_tex_convert(const uint8_t *d_bgr, int w, int h, int row_stride, uint32_t *d_bgrx, hipStream_t s) {

@@ -22,7 +22,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_comm_unique_id", "srz_comm_create", "srz_comm_destroy", "srz_frameset_exchange_bytes", "srz_frameset_allgather",
            "srz_frameset_deinterleave", "srz_frameset_allgather_inplace", "srz_frameset_gathered_row_offset",
            "srz_frameset_read_gathered_frame", "srz_frameset_sparse_capacity", "srz_frameset_sparse_pack", "srz_frameset_sparse_unpack",
-           "srz_frameset_allgather_sparse", "srz_frameset_render_visibility", "srz_frameset_shade_visibility",
+           "srz_frameset_allgather_sparse", "srz_frameset_render_visibility", "srz_frameset_peel_visibility", "srz_frameset_shade_visibility",
            "srz_frameset_update_shading", "srz_frameset_shade_kinds", "srz_frameset_gbuffer_bytes", "srz_frameset_gbuffer",
            "srz_frameset_motion_bytes", "srz_frameset_motion", "srz_frameset_interpolate_bytes", "srz_frameset_interpolate",
            "srz_frameset_interpolate_grad", "srz_frameset_position_grad", "srz_frameset_antialias", "srz_frameset_antialias_grad",
@@ -76,6 +76,7 @@ def lib():
         L.srz_frameset_out_bytes.restype = C.c_size_t
         L.srz_frameset_render.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]
         L.srz_frameset_render_visibility.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]
+        L.srz_frameset_peel_visibility.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp]
         L.srz_frameset_shade_visibility.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp]
         L.srz_frameset_gbuffer_bytes.argtypes = [vp, vp, C.c_uint32]
         L.srz_frameset_gbuffer_bytes.restype = C.c_size_t
@@ -203,6 +204,13 @@ class FrameSet:
         """the visibility buffer instead of the colour: planes z, id = triangle index in the frame + 1 | S class << 31 (0 = nobody),
         alpha, beta (include/srz.h; srz.visibility.decode takes it apart).  Same buffer and arguments as render().  Asynchronous."""
         self.ctx._check(lib().srz_frameset_render_visibility(self.ctx.h, self.h, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def peel_visibility(self, d_prev_ptr, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """depth peeling: the layer behind the visibility buffer at d_prev_ptr (layer k of this set, from render_visibility or from this
+        call) into d_out_ptr, same layout — per pixel the first fragment strictly after d_prev's in the renders' visibility order, or
+        nobody (include/srz.h states the rule).  Every pixel's four words are written; the buffers may not overlap.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_peel_visibility(self.ctx.h, self.h, C.c_void_p(d_prev_ptr), C.c_void_p(d_out_ptr), out_bytes,
+                                                           flags, _stream(stream)))
 
     def shade_visibility(self, d_vis_ptr, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
         """the colour of a visibility buffer of this set (render_visibility) with the set's current shading data: equal bit for bit to

@@ -35,6 +35,60 @@ def decode(out):
     return Visibility(z, tri, s_class, alpha, beta, gamma)
 
 
+def _vis_arg(fs, t, name):
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(fs.out_shape):
+        raise ValueError(f"{name}: expected a contiguous CUDA float32 tensor {tuple(fs.out_shape)}, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def first_prev(fs):
+    """the buffer that lies in front of every fragment of frames of finite depths: (z = -inf, id = 1, 0, 0) at every pixel.  peel()
+    of it is layer 1, bit for bit FrameSet.render_visibility's buffer."""
+    t = torch.zeros(fs.out_shape, dtype=torch.float32, device="cuda")
+    t[:, 0] = float("-inf")
+    t.view(torch.int32)[:, 1] = 1
+    return t
+
+
+def peel(fs, prev, out=None, flags=abi.FUSED_CLEAR, stream=None):
+    """depth peeling (FrameSet.peel_visibility; the rule: include/srz.h): the layer behind the visibility buffer `prev` of this set
+    ([n_frames, 4, local_rows, W] float32: a render_visibility buffer, or a layer this call returned) -> that layer as a tensor in the
+    same layout (`out`, or a new one), every word of it written.  Asynchronous on `stream` (default: torch's current stream)."""
+    _vis_arg(fs, prev, "peel: prev")
+    out = torch.empty(fs.out_shape, dtype=torch.float32, device=prev.device) if out is None else _vis_arg(fs, out, "peel: out")
+    fs.peel_visibility(prev.data_ptr(), out.data_ptr(), fs.out_bytes, flags, _stream_ptr(stream))
+    return out
+
+
+def layers(fs, n, flags=abi.FUSED_CLEAR, stream=None):
+    """the first n depth layers of the set, nearest first: layer 1 by render_visibility, the others by peel() — a list of n buffers
+    [n_frames, 4, local_rows, W], each of which every pass over a visibility buffer takes.  A pixel with fewer than k fragments is
+    nobody's from layer k on.  No host synchronisation."""
+    if n < 1:
+        raise ValueError(f"layers: n = {n}, expected at least 1")
+    first = torch.empty(fs.out_shape, dtype=torch.float32, device="cuda")
+    fs.render_visibility(first.data_ptr(), fs.out_bytes, flags | abi.FUSED_CLEAR, _stream_ptr(stream))
+    out = [first]
+    while len(out) < n:
+        out.append(peel(fs, out[-1], flags=flags, stream=stream))
+    return out
+
+
+def composite(colors, alphas):
+    """front-to-back "over" of depth layers, nearest first: colors[k] is [n, C, rows, W], alphas[k] [n, 1 or C, rows, W] (0 where
+    nobody owns the pixel: decode(layer).tri >= 0 times the surface's opacity) -> sum_k colors[k] * alphas[k] * prod_{j<k} (1 -
+    alphas[j]).  Plain torch ops: autograd goes through it, into the colours and the opacities of every layer."""
+    colors, alphas = list(colors), list(alphas)
+    if not colors or len(colors) != len(alphas):
+        raise ValueError(f"composite: {len(colors)} colour layers, {len(alphas)} alpha layers")
+    acc, through = None, None
+    for c, a in zip(colors, alphas):
+        term = c * a if through is None else c * (a * through)
+        acc = term if acc is None else acc + term
+        through = (1 - a) if through is None else through * (1 - a)
+    return acc
+
+
 def batch_of(frame, tri):
     """The batch (a Frame) or draw (a SceneFrame's draws: pass their face counts as a sequence) each triangle index of `tri` belongs
     to; -1 where tri is -1.  Empty batches own no index."""
