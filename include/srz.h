@@ -61,6 +61,8 @@ extern "C" {
  *      srz_texture_mip_bytes / srz_texture_mip_build / srz_texture_mip_fold / srz_frameset_interpolate_deriv /
  *      srz_frameset_texture_mip / srz_frameset_texture_mip_grad, SRZ_TEX_MAX_LEVELS
  *      (additive, same version) depth peeling: the layer behind a visibility buffer srz_frameset_peel_visibility
+ *      (additive, same version) vertex normals and per-vertex attributes on the device, with gradients srz_mesh_normals /
+ *      srz_mesh_normals_grad / srz_sceneset_corner_attr / srz_sceneset_corner_attr_grad
  */
 #define SRZ_ABI_VERSION 7
 
@@ -234,6 +236,49 @@ int srz_mesh_upload(srz_ctx *ctx, int mesh_id, const srz_vertex *verts, uint32_t
  * as it does after a matrix update.  SRZ_E_INVALID, nothing copied, for: a null ctx; a mesh_id outside 0..255 or a slot that holds no
  * mesh; a null or misaligned d_verts; n_verts other than the slot's count. */
 int srz_mesh_update(srz_ctx *ctx, int mesh_id, const srz_vertex *d_verts, uint32_t n_verts, void *stream);
+/* VERTEX NORMALS of a slot's faces FROM POSITIONS, ON THE DEVICE: area-weighted (the sum of the cross products of the faces that name
+ * the vertex, normalised), for n_sets position sets over the slot's face list in one pass.  d_pos: n_sets sets of n_verts vertices,
+ * vertex v of set s at float (s * n_verts + v) * pos_stride, pos_stride >= 3; d_nrm laid out the same way with nrm_stride.  A null
+ * d_pos selects the slot's own vertices (stride 8; n_sets must be 1), a null d_nrm the slot's own nrm fields (stride 8; n_sets must
+ * be 1): both null REFRESHES THE SLOT IN PLACE — what srz_mesh_update leaves to the caller, one call after it on the same stream.  A
+ * caller's [V][8] record array works as d_pos = base, d_nrm = base + 3, both strides 8.
+ * THE RULE, in float32, nothing fused, in this order.  cross(u, w) = (u.y w.z - u.z w.y, u.z w.x - u.x w.z, u.x w.y - u.y w.x);
+ * dot3(a, b) = (a.x b.x + a.y b.y) + a.z b.z.  Per set and vertex v, with p the set's positions and list(v) the slot's corner list of
+ * v, in list order (srz_mesh_upload):
+ *   S = (+0, +0, +0);  for corner c in list(v):  (i0, i1, i2) = faces[c / 3];  N = cross(p[i1] - p[i0], p[i2] - p[i0]);  S = S + N
+ *   len2 = dot3(S, S)
+ *   len2 > 0 && len2 <= FLT_MAX:  r = 1.0f / sqrtf(len2);  n = S * r            (v is NORMALISED)
+ *   otherwise:                    n = (+0, +0, +0)     (no face names v, degenerate faces only, a NaN, an overflow, an underflow)
+ * N is taken in the face's OWN vertex order whichever corner asks: a face contributes the same bits to its three vertices.  The pass
+ * is a GATHER — the one thread that owns (s, v) stores its three floats once — with no atomics: DETERMINISTIC, bit for bit.  The
+ * other floats of a strided record are not touched.  THIS IS NOT THE LOADER'S RULE for files without normals (the last face that
+ * names a vertex wins there, src/ObjLoader.cpp:166-186): a mesh loaded from such a file and refreshed changes its normals.
+ * Asynchronous on `stream` (NULL: the ctx's own stream, SRZ_STREAM_NULL: HIP's null stream); order it against srz_mesh_update,
+ * renders and passes as a render is ordered.  No input value makes the pass read or write outside its buffers.
+ * SRZ_E_INVALID, nothing written and nothing launched, for: a null ctx; a mesh_id outside 0..255 or a slot that holds no mesh; n_sets
+ * of 0 or above 65535; a stride below 3 (of a non-null buffer); a null d_pos or d_nrm with n_sets != 1; a pointer that is not 4-byte
+ * aligned; normals whose span (first to last float reached) overlaps the positions' span — except the record form d_nrm == d_pos + 3
+ * with equal strides >= 6, the slot's own layout. */
+int srz_mesh_normals(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, float *d_nrm,
+                     uint32_t nrm_stride, void *stream);
+/* THE BACKWARD of srz_mesh_normals.  d_pos, pos_stride, n_sets as above (the positions of the forward call; null: the slot's own);
+ * d_gnrm: the gradient with respect to the normals, laid out like d_nrm with gnrm_stride >= 3; d_gpos: [n_sets][n_verts][3] float32,
+ * the gradient with respect to the positions, EVERY element written; d_work: a workspace of the same size whose contents afterwards
+ * are unspecified.  THE RULE, in float32, nothing fused, two phases (the second starts when the first has ended), both gathers:
+ *   PHASE 1, per set and vertex v:  S, r, n as above;  g = d_gnrm[s][v]
+ *     v normalised:  d = dot3(n, g);  gS[v] = (g - n * d) * r        (componentwise: (g.x - n.x * d) * r, ...)
+ *     otherwise:     gS[v] = (+0, +0, +0)
+ *   PHASE 2, per set and vertex v:  acc = (+0, +0, +0);  for corner c in list(v), in list order:
+ *     (i0, i1, i2) = faces[c / 3];  a, b, c' = p[i0], p[i1], p[i2];  k = c % 3;  G = (gS[i0] + gS[i1]) + gS[i2]
+ *     k == 0:  acc = acc + cross(b - c', G);   k == 1:  acc = acc + cross(c' - a, G);   k == 2:  acc = acc + cross(G, b - a)
+ *     d_gpos[s][v] = acc
+ * No atomics: DETERMINISTIC, bit for bit.  A vertex that was not normalised passes no gradient on (the forward is constant there).
+ * Non-finite values propagate as IEEE has them.  Asynchronous on `stream`.
+ * SRZ_E_INVALID, nothing written and nothing launched, for what srz_mesh_normals refuses of ctx, mesh_id, n_sets, d_pos and
+ * pos_stride, and for: a null d_gnrm, d_work or d_gpos; gnrm_stride below 3; a pointer that is not 4-byte aligned; d_work or d_gpos
+ * overlapping the positions' or d_gnrm's span, or each other. */
+int srz_mesh_normals_grad(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, const float *d_gnrm,
+                          uint32_t gnrm_stride, float *d_work, float *d_gpos, void *stream);
 
 /* ---- draw = TraditionalRasterizer::draw(TRIANGLES) for one scene ----------------------
  * z/c0/c1/c2: W*H floats each, in/out (m_zBuffer, m_channels[0..2]); draw never clears unless
@@ -747,6 +792,30 @@ int srz_frameset_positions(srz_ctx *ctx, srz_frameset *fs, uint32_t pos_tris, fl
  * overlaps d_gpos or the other output. */
 int srz_sceneset_vertex_grad(srz_ctx *ctx, srz_frameset *fs, int mesh_id, const float *d_gpos, uint32_t pos_tris, float *d_gverts,
                              float *d_gdraw, uint32_t draw_stride, void *stream);
+/* PER-VERTEX ATTRIBUTES of one mesh slot TO THE SET'S TRIANGLE STREAM, and back.  srz_frameset_interpolate takes attributes per corner,
+ * [frame][T][3][n_ch] in the frame's triangle order; these two calls lay a slot's per-vertex data out that way on the device and fold
+ * the per-corner gradient back to the vertices.
+ * FORWARD.  d_attr: [attr_frames][n_verts(mesh_id)][n_ch] float32, attr_frames 1 (one array for every frame) or the set's frame count,
+ * 1 <= n_ch <= SRZ_ATTR_MAX_CH; d_out: [n_frames][pos_tris][3][n_ch] float32 — what srz_frameset_interpolate takes with attr_frames =
+ * n_frames and attr_tris = pos_tris; pos_tris at least every frame's triangle count.  For every frame f, every draw of frame f that names
+ * mesh_id, with `first` the draw's first frame-local triangle, every face and k = 0..2:
+ *   d_out[f][first + face][k][ch] = d_attr[f or 0][faces[face][k]][ch]
+ * EVERYTHING ELSE IN d_out IS LEFT UNTOUCHED (the triangles of other slots' draws, those behind a frame's count): call once per slot
+ * into one buffer the caller has filled first.
+ * BACKWARD.  d_gout: laid out like d_out; d_gattr: [n_frames][n_verts][n_ch] float32, EVERY element written:
+ *   sum = +0;  for each draw of frame f that names mesh_id, in draw order:  for corner c in list(v), in list order:
+ *     sum = sum + d_gout[f][first + c / 3][c % 3][ch];          d_gattr[f][v][ch] = sum
+ * one running float32 sum; a frame that does not draw the slot gets +0.  A GATHER, no atomics: DETERMINISTIC, bit for bit (the
+ * gradient of a [n_verts][n_ch] array shared by the frames is the caller's sum over the frames).
+ * Both are asynchronous on `stream`; neither runs the vertex stage nor reads a triangle of the set.
+ * SRZ_E_INVALID, nothing written and nothing launched, for: a null ctx or set; a set that is not a sceneset; a mesh_id the set does
+ * not draw, or whose slot was uploaded anew (srz_mesh_upload) since the set was created; n_ch == 0 or above SRZ_ATTR_MAX_CH; pos_tris
+ * below a frame's triangle count; a null buffer; attr_frames not 1 or the frame count; a pointer that is not 4-byte aligned; an
+ * output that overlaps the input. */
+int srz_sceneset_corner_attr(srz_ctx *ctx, srz_frameset *fs, int mesh_id, const float *d_attr, uint32_t n_ch, uint32_t attr_frames,
+                             float *d_out, uint32_t pos_tris, void *stream);
+int srz_sceneset_corner_attr_grad(srz_ctx *ctx, srz_frameset *fs, int mesh_id, const float *d_gout, uint32_t n_ch, float *d_gattr,
+                                  uint32_t pos_tris, void *stream);
 
 /* ---- multi-GPU exchange: the band shards of every rank → full row-major frames on every rank ------------------------
  * One process per GPU.  Rank 0 makes an id (srz_comm_unique_id), the host program hands the 128 bytes to every rank

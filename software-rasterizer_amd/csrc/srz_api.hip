@@ -1314,6 +1314,63 @@ int srz_mesh_update(srz_ctx *ctx, int mesh_id, const srz_vertex *d_verts, uint32
   return SRZ_OK;
 }
 
+// What srz_mesh_normals and srz_mesh_normals_grad check alike; on success the slot's lists and the resolved positions are in `a`
+// (a null d_pos: the slot's own records) and *pos_span is the bytes the positions reach over.
+static int check_mesh_normals(srz_ctx *ctx, const std::string &fn, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets,
+                              MeshNormalsArgs &a, size_t *pos_span) {
+  if (mesh_id < 0 || mesh_id >= MAX_MESH || !ctx->mesh[mesh_id].d_verts) return fail(ctx, SRZ_E_INVALID, fn + ": no mesh in that slot");
+  const srz_ctx::MeshSlot &m = ctx->mesh[mesh_id];
+  if (n_sets == 0u || n_sets > 65535u) return fail(ctx, SRZ_E_INVALID, fn + ": n_sets must be 1 .. 65535");
+  if (!d_pos && n_sets != 1u) return fail(ctx, SRZ_E_INVALID, fn + ": the slot's own vertices are one set (n_sets must be 1)");
+  if (d_pos && pos_stride < 3u) return fail(ctx, SRZ_E_INVALID, fn + ": pos_stride must be at least 3");
+  a.pos = d_pos ? d_pos : reinterpret_cast<const float *>(m.d_verts), a.pos_stride = d_pos ? pos_stride : 8u;
+  a.faces = m.d_faces, a.corner_off = m.d_corner_off, a.corners = m.d_corner_off + m.n_verts + 1;
+  a.n_verts = m.n_verts, a.n_sets = n_sets;
+  *pos_span = (((size_t)n_sets * m.n_verts - 1u) * a.pos_stride + 3u) * sizeof(float);
+  return SRZ_OK;
+}
+
+int srz_mesh_normals(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, float *d_nrm, uint32_t nrm_stride,
+                     void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_mesh_normals");
+  MeshNormalsArgs a{};
+  size_t pos_span = 0;
+  if (int rc = check_mesh_normals(ctx, fn, mesh_id, d_pos, pos_stride, n_sets, a, &pos_span)) return rc;
+  if (!d_nrm && n_sets != 1u) return fail(ctx, SRZ_E_INVALID, fn + ": the slot's own normals are one set (n_sets must be 1)");
+  if (d_nrm && nrm_stride < 3u) return fail(ctx, SRZ_E_INVALID, fn + ": nrm_stride must be at least 3");
+  if (!aligned<4>({d_pos, d_nrm})) return fail(ctx, SRZ_E_INVALID, fn + ": the buffers must be 4-byte aligned");
+  a.nrm = d_nrm ? d_nrm : reinterpret_cast<float *>(ctx->mesh[mesh_id].d_verts) + 3, a.nrm_stride = d_nrm ? nrm_stride : 8u;
+  const size_t nrm_span = (((size_t)n_sets * a.n_verts - 1u) * a.nrm_stride + 3u) * sizeof(float);
+  // (the one overlap that is none: records whose floats 3..5 are the normals of their floats 0..2 — the slot's own layout)
+  const bool records = a.nrm == a.pos + 3 && a.nrm_stride == a.pos_stride && a.pos_stride >= 6u;
+  if (!records && ranges_overlap({a.nrm, nrm_span}, {a.pos, pos_span})) return fail(ctx, SRZ_E_INVALID, fn + ": the normals overlap the positions");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  launch_mesh_normals(a, pick_stream(ctx, stream));
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
+int srz_mesh_normals_grad(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, const float *d_gnrm,
+                          uint32_t gnrm_stride, float *d_work, float *d_gpos, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_mesh_normals_grad");
+  MeshNormalsArgs a{};
+  size_t pos_span = 0;
+  if (int rc = check_mesh_normals(ctx, fn, mesh_id, d_pos, pos_stride, n_sets, a, &pos_span)) return rc;
+  if (!d_gnrm || !d_work || !d_gpos) return fail(ctx, SRZ_E_INVALID, fn + ": null normal gradient / workspace / output");
+  if (gnrm_stride < 3u) return fail(ctx, SRZ_E_INVALID, fn + ": gnrm_stride must be at least 3");
+  if (!aligned<4>({d_pos, d_gnrm, d_work, d_gpos})) return fail(ctx, SRZ_E_INVALID, fn + ": the buffers must be 4-byte aligned");
+  const size_t packed = (size_t)n_sets * a.n_verts * 3u * sizeof(float);
+  const size_t gnrm_span = (((size_t)n_sets * a.n_verts - 1u) * gnrm_stride + 3u) * sizeof(float);
+  if (int rc = check_grad_overlap(ctx, fn, {{d_work, packed}, {d_gpos, packed}}, {{a.pos, pos_span}, {d_gnrm, gnrm_span}})) return rc;
+  a.gnrm = d_gnrm, a.gnrm_stride = gnrm_stride, a.work = d_work, a.gpos = d_gpos;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  launch_mesh_normals_grad(a, pick_stream(ctx, stream));
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
 // A sceneset's frames as srz_frames whose batches carry sizes only (k_vertex makes the triangles): fr[f], its batches in `batches`.
 // Every draw names an uploaded mesh (the callers have checked).
 static void scene_frames(const srz_ctx *ctx, const srz_scene_frame *frames, int n_frames, std::vector<srz_frame> &fr, std::vector<srz_batch> &batches) {
@@ -1733,6 +1790,21 @@ int srz_frameset_positions(srz_ctx *ctx, srz_frameset *fs, uint32_t pos_tris, fl
   return end_pass(ctx);
 }
 
+// what the passes over ONE mesh slot of a sceneset check alike (srz_sceneset_vertex_grad, srz_sceneset_corner_attr / _grad): the slot
+// holds a mesh, the set draws it, and the slot still holds the upload the set's draws point into
+static int check_drawn_slot(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, int mesh_id) {
+  if (mesh_id < 0 || mesh_id >= MAX_MESH || !ctx->mesh[mesh_id].d_verts) return fail(ctx, SRZ_E_INVALID, fn + ": no mesh in that slot");
+  bool drawn = false;
+  for (size_t di = 0; di < fs->h_draw_mesh.size(); ++di) {
+    if (fs->h_draw_mesh[di] != mesh_id) continue;
+    drawn = true;
+    // (as srz_sceneset_update)
+    if (ctx->mesh[mesh_id].upload != fs->h_draw_upload[di]) return fail(ctx, SRZ_E_INVALID, fn + ": the slot was uploaded anew since the set was created");
+  }
+  if (!drawn) return fail(ctx, SRZ_E_INVALID, fn + ": the set draws no mesh of that slot");
+  return SRZ_OK;
+}
+
 int srz_sceneset_vertex_grad(srz_ctx *ctx, srz_frameset *fs, int mesh_id, const float *d_gpos, uint32_t pos_tris, float *d_gverts,
                              float *d_gdraw, uint32_t draw_stride, void *stream) {
   if (!ctx) return SRZ_E_INVALID;
@@ -1740,16 +1812,8 @@ int srz_sceneset_vertex_grad(srz_ctx *ctx, srz_frameset *fs, int mesh_id, const 
   if (!fs || !fs->d_draws) return fail(ctx, SRZ_E_INVALID, fn + ": not a sceneset");
   if (!d_gpos) return fail(ctx, SRZ_E_INVALID, fn + ": null position gradient");
   if (!d_gverts && !d_gdraw) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gverts nor d_gdraw is asked for");
-  if (mesh_id < 0 || mesh_id >= MAX_MESH || !ctx->mesh[mesh_id].d_verts) return fail(ctx, SRZ_E_INVALID, fn + ": no mesh in that slot");
+  if (int rc = check_drawn_slot(ctx, fs, fn, mesh_id)) return rc;
   const srz_ctx::MeshSlot &m = ctx->mesh[mesh_id];
-  bool drawn = false;
-  for (size_t di = 0; di < fs->h_draw_mesh.size(); ++di) {
-    if (fs->h_draw_mesh[di] != mesh_id) continue;
-    drawn = true;
-    // (as srz_sceneset_update: the slot must still hold the upload the set's draws point into)
-    if (m.upload != fs->h_draw_upload[di]) return fail(ctx, SRZ_E_INVALID, fn + ": the slot was uploaded anew since the set was created");
-  }
-  if (!drawn) return fail(ctx, SRZ_E_INVALID, fn + ": the set draws no mesh of that slot");
   if (int rc = check_tri_count(ctx, fs, fn, "pos_tris", pos_tris)) return rc;
   if (d_gdraw)
     for (const FrameDesc &d : fs->h_frames)
@@ -1768,6 +1832,57 @@ int srz_sceneset_vertex_grad(srz_ctx *ctx, srz_frameset *fs, int mesh_id, const 
   a.gpos_stride = (uint64_t)pos_tris * TRI_POS_F;
   a.n_verts = m.n_verts, a.n_frames = (uint32_t)fs->n_frames, a.draw_stride = draw_stride;
   launch_vertex_grad(a, s);
+  return end_pass(ctx);
+}
+
+// what srz_sceneset_corner_attr and _corner_attr_grad check alike, and the fields of `a` they fill alike
+static int check_corner_attr(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, int mesh_id, uint32_t n_ch, uint32_t pos_tris,
+                             CornerAttrArgs &a) {
+  if (!fs || !fs->d_draws) return fail(ctx, SRZ_E_INVALID, fn + ": not a sceneset");
+  if (int rc = check_drawn_slot(ctx, fs, fn, mesh_id)) return rc;
+  if (n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_ATTR_MAX_CH");
+  if (int rc = check_tri_count(ctx, fs, fn, "pos_tris", pos_tris)) return rc;
+  const srz_ctx::MeshSlot &m = ctx->mesh[mesh_id];
+  a.frames = fs->d_frames, a.draws = fs->d_draws;
+  a.verts = m.d_verts, a.corner_off = m.d_corner_off, a.corners = m.d_corner_off + m.n_verts + 1;
+  a.n_verts = m.n_verts, a.n_ch = n_ch, a.pos_tris = pos_tris, a.n_frames = (uint32_t)fs->n_frames;
+  return SRZ_OK;
+}
+
+int srz_sceneset_corner_attr(srz_ctx *ctx, srz_frameset *fs, int mesh_id, const float *d_attr, uint32_t n_ch, uint32_t attr_frames,
+                             float *d_out, uint32_t pos_tris, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_sceneset_corner_attr");
+  CornerAttrArgs a{};
+  if (int rc = check_corner_attr(ctx, fs, fn, mesh_id, n_ch, pos_tris, a)) return rc;
+  if (!d_attr || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null attributes / output");
+  if (attr_frames != 1u && attr_frames != (uint32_t)fs->n_frames) return fail(ctx, SRZ_E_INVALID, fn + ": attr_frames must be 1 or the set's frame count");
+  if (!aligned<4>({d_attr, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": the buffers must be 4-byte aligned");
+  const size_t per_frame = (size_t)a.n_verts * n_ch;
+  if (ranges_overlap({d_out, (size_t)fs->n_frames * pos_tris * 3u * n_ch * sizeof(float)}, {d_attr, attr_frames * per_frame * sizeof(float)}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the attributes");
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (the pass reads the draws' offsets and the slot's lists: no triangle of the set)
+  a.attr = d_attr, a.out = d_out, a.attr_frame_stride = attr_frames == 1u ? 0u : per_frame;
+  launch_corner_attr(a, s);
+  return end_pass(ctx);
+}
+
+int srz_sceneset_corner_attr_grad(srz_ctx *ctx, srz_frameset *fs, int mesh_id, const float *d_gout, uint32_t n_ch, float *d_gattr,
+                                  uint32_t pos_tris, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_sceneset_corner_attr_grad");
+  CornerAttrArgs a{};
+  if (int rc = check_corner_attr(ctx, fs, fn, mesh_id, n_ch, pos_tris, a)) return rc;
+  if (!d_gout || !d_gattr) return fail(ctx, SRZ_E_INVALID, fn + ": null output gradient / attribute gradient");
+  if (!aligned<4>({d_gout, d_gattr})) return fail(ctx, SRZ_E_INVALID, fn + ": the buffers must be 4-byte aligned");
+  if (ranges_overlap({d_gattr, (size_t)fs->n_frames * a.n_verts * n_ch * sizeof(float)},
+                     {d_gout, (size_t)fs->n_frames * pos_tris * 3u * n_ch * sizeof(float)}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the attribute gradient overlaps the output gradient");
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc;
+  a.gout = d_gout, a.gattr = d_gattr;
+  launch_corner_attr_grad(a, s);
   return end_pass(ctx);
 }
 

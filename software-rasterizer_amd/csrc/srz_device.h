@@ -228,6 +228,41 @@ struct VertexGradArgs {
   uint32_t n_verts, n_frames, draw_stride;
 };
 void launch_vertex_grad(const VertexGradArgs &a, hipStream_t s);
+// srz_mesh_normals / srz_mesh_normals_grad: the area-weighted vertex normals of ONE mesh slot's faces over n_sets position sets
+// (k_mesh_normals), and their backward (k_mesh_normals_grad, two launches: gS per vertex into `work`, then the gather over each
+// vertex's corner list into gpos).  Vertex v of set s starts at float (s * n_verts + v) * stride of pos / nrm / gnrm; work and gpos are
+// packed [n_sets][n_verts][3].  The host has checked the strides, the spans and n_sets <= 65535 (the grid's y)
+struct MeshNormalsArgs {
+  const float *pos;            // the slot's own records (stride 8) or the caller's sets
+  const uint32_t *faces;       // [n_faces][3]
+  const uint32_t *corner_off;  // [n_verts + 1] into corners
+  const uint32_t *corners;     // [3 * n_faces]: 3 * face + k of every corner that names the vertex, increasing
+  float *nrm;                  // forward: the output
+  const float *gnrm;           // backward: the gradient of the normals
+  float *work, *gpos;          // backward: gS (phase 1 writes, phase 2 reads), the output
+  uint32_t pos_stride, nrm_stride, gnrm_stride;
+  uint32_t n_verts, n_sets;
+};
+void launch_mesh_normals(const MeshNormalsArgs &a, hipStream_t s);
+void launch_mesh_normals_grad(const MeshNormalsArgs &a, hipStream_t s);
+// srz_sceneset_corner_attr / _corner_attr_grad: per-vertex attributes of ONE mesh slot to the set's triangle stream
+// [frame][pos_tris][3][n_ch], and the stream's gradient back to [frame][n_verts][n_ch] (k_corner_attr, k_corner_attr_grad: a thread
+// owns (frame, vertex, channel) and walks the frame's draws of the slot and the vertex's corner list).  A draw takes part when its
+// DrawDesc names the slot's vertex buffer.  The host has checked pos_tris against every frame's count
+struct CornerAttrArgs {
+  const FrameDesc *frames;
+  const DrawDesc *draws;
+  const srz_vertex *verts;     // the slot's vertices: what a draw of the slot names
+  const uint32_t *corner_off, *corners;
+  const float *attr;           // forward: [attr_frames][n_verts][n_ch]
+  float *out;                  // forward: [frame][pos_tris][3][n_ch]
+  const float *gout;           // backward: the same layout
+  float *gattr;                // backward: [frame][n_verts][n_ch], every element written
+  uint64_t attr_frame_stride;  // floats: 0 (one array for every frame) or n_verts * n_ch
+  uint32_t n_verts, n_ch, pos_tris, n_frames;
+};
+void launch_corner_attr(const CornerAttrArgs &a, hipStream_t s);
+void launch_corner_attr_grad(const CornerAttrArgs &a, hipStream_t s);
 void launch_chunks(const RenderArgs &a, int n_frames, uint32_t max_tris, hipStream_t s);
 void launch_setup(const RenderArgs &a, int n_frames, uint32_t max_tris, bool stats, hipStream_t s);
 void launch_bin(const RenderArgs &a, int n_frames, uint32_t max_tris, hipStream_t s);

@@ -662,6 +662,117 @@ __global__ __launch_bounds__(256) void k_vertex_grad(const VertexGradArgs a) {
 }
 
 // ================================================================================================================
+// k_mesh_normals / k_mesh_normals_grad — srz_mesh_normals and its backward (include/srz.h states the rules).  Grid (blocks of 256
+// vertices, position sets); a thread OWNS (set, vertex) and walks the vertex's corner list: a gather, no atomics, no barrier, plain
+// stores, bit-reproducible.  A face's normal is computed in the face's OWN vertex order whichever corner asks, so the three vertices
+// of a face add the same bits.  The backward is two launches of one kernel: PHASE 1 recomputes S, r, n per vertex and stores
+// gS = (g - n (n . g)) r (0 where the vertex was not normalised) into `work`; PHASE 2 gathers, per corner of the vertex, the
+// face's G = (gS[i0] + gS[i1]) + gS[i2] crossed with the opposite edge.
+// ================================================================================================================
+__device__ __forceinline__ F3 ldv3(const float *p) { return F3{p[0], p[1], p[2]}; } // (ld3 for memory the pass may also write)
+__device__ __forceinline__ F3 sub3(F3 a, F3 b) { return F3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ F3 add3(F3 a, F3 b) { return F3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ F3 cross3(F3 u, F3 w) { return F3{u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x}; }
+// S of the rule: the sum over the vertex's corners, in list order, of the face normals of position set `p`
+__device__ __forceinline__ F3 normal_sum(const MeshNormalsArgs &a, const float *p, uint32_t c_begin, uint32_t c_end) {
+  F3 S{0.0f, 0.0f, 0.0f};
+  for (uint32_t c = c_begin; c < c_end; ++c) {
+    const uint32_t *f = a.faces + (size_t)(a.corners[c] / 3u) * 3;
+    const F3 p0 = ldv3(p + (size_t)f[0] * a.pos_stride);
+    S = add3(S, cross3(sub3(ldv3(p + (size_t)f[1] * a.pos_stride), p0), sub3(ldv3(p + (size_t)f[2] * a.pos_stride), p0)));
+  }
+  return S;
+}
+// r = 1 / sqrt(S . S) where the vertex is normalised (IeeeMath::rsqrt2's expression), else false: no face, degenerate faces only,
+// NaN, overflow
+__device__ __forceinline__ bool normal_scale(F3 S, float &r) {
+  const float len2 = dot3(S.x, S.y, S.z, S.x, S.y, S.z);
+  const bool ok = len2 > 0.0f && len2 <= __FLT_MAX__;
+  r = ok ? 1.0f / __builtin_sqrtf(len2) : 0.0f;
+  return ok;
+}
+__global__ __launch_bounds__(256) void k_mesh_normals(const MeshNormalsArgs a) {
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x, set = blockIdx.y;
+  if (v >= a.n_verts) return;
+  const size_t at = (size_t)set * a.n_verts + v;
+  const F3 S = normal_sum(a, a.pos + (size_t)set * a.n_verts * a.pos_stride, a.corner_off[v], a.corner_off[v + 1]);
+  float r;
+  const bool ok = normal_scale(S, r);
+  float *n = a.nrm + at * a.nrm_stride;
+  n[0] = ok ? S.x * r : 0.0f, n[1] = ok ? S.y * r : 0.0f, n[2] = ok ? S.z * r : 0.0f;
+}
+template <int PHASE> __global__ __launch_bounds__(256) void k_mesh_normals_grad(const MeshNormalsArgs a) {
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x, set = blockIdx.y;
+  if (v >= a.n_verts) return;
+  const size_t at = (size_t)set * a.n_verts + v;
+  const float *p = a.pos + (size_t)set * a.n_verts * a.pos_stride;
+  const uint32_t c_begin = a.corner_off[v], c_end = a.corner_off[v + 1];
+  if (PHASE == 1) {
+    const F3 S = normal_sum(a, p, c_begin, c_end);
+    float r;
+    F3 gS{0.0f, 0.0f, 0.0f};
+    if (normal_scale(S, r)) {
+      const F3 n{S.x * r, S.y * r, S.z * r}, g = ldv3(a.gnrm + at * a.gnrm_stride);
+      const float d = dot3(n.x, n.y, n.z, g.x, g.y, g.z);
+      gS = F3{(g.x - n.x * d) * r, (g.y - n.y * d) * r, (g.z - n.z * d) * r};
+    }
+    float *w = a.work + at * 3;
+    w[0] = gS.x, w[1] = gS.y, w[2] = gS.z;
+  } else {
+    const float *gs = a.work + (size_t)set * a.n_verts * 3;
+    F3 acc{0.0f, 0.0f, 0.0f};
+    for (uint32_t c = c_begin; c < c_end; ++c) {
+      const uint32_t corner = a.corners[c], face = corner / 3u, k = corner - 3u * face;
+      const uint32_t *f = a.faces + (size_t)face * 3;
+      const uint32_t i0 = f[0], i1 = f[1], i2 = f[2];
+      const F3 A = ldv3(p + (size_t)i0 * a.pos_stride), B = ldv3(p + (size_t)i1 * a.pos_stride), C = ldv3(p + (size_t)i2 * a.pos_stride);
+      const F3 G = add3(add3(ldv3(gs + (size_t)i0 * 3), ldv3(gs + (size_t)i1 * 3)), ldv3(gs + (size_t)i2 * 3));
+      const F3 term = k == 0u ? cross3(sub3(B, C), G) : k == 1u ? cross3(sub3(C, A), G) : cross3(G, sub3(B, A));
+      acc = add3(acc, term);
+    }
+    float *g = a.gpos + at * 3;
+    g[0] = acc.x, g[1] = acc.y, g[2] = acc.z;
+  }
+}
+
+// ================================================================================================================
+// k_corner_attr / k_corner_attr_grad — srz_sceneset_corner_attr and its backward (include/srz.h).  Grid (blocks of 256 (vertex,
+// channel) pairs, frames); a thread OWNS (frame, vertex, channel): neighbouring lanes are neighbouring channels of one vertex, so
+// the attribute row, the rows of the triangle stream and the gradient row are each read and written as runs, and the backward
+// needs ONE accumulator whatever n_ch (the corner-list words are the same address across a vertex's lanes: one fetch).  The
+// thread walks the frame's draws of the slot in draw order and its vertex's corners in list order: every corner has one owner, so
+// the forward's stores never meet; the backward is a gather.  No atomics, no barrier.
+// ================================================================================================================
+template <bool GRAD> __device__ __forceinline__ void corner_attr_walk(const CornerAttrArgs &a) {
+  const uint32_t f = blockIdx.y;
+  const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint32_t v = (e >> 32) != 0ull ? (uint32_t)(e / a.n_ch) : (uint32_t)e / a.n_ch; // (block-uniform choice)
+  if (v >= a.n_verts) return;
+  const uint32_t ch = (uint32_t)(e - (uint64_t)v * a.n_ch);
+  const SRZ_CAS FrameDesc *fd = as_const(a.frames) + f;
+  const uint32_t n_draws = fd->n_batches, draw0 = fd->batch_off, tri0 = fd->tri_off;
+  const uint32_t c_begin = a.corner_off[v], c_end = a.corner_off[v + 1];
+  const size_t frame_at = (size_t)f * a.pos_tris * 3u * a.n_ch + ch;
+  float val = 0.0f; // the forward's value, the backward's sum
+  if (!GRAD) val = a.attr[(size_t)f * a.attr_frame_stride + (size_t)v * a.n_ch + ch];
+  for (uint32_t j = 0; j < n_draws; ++j) {
+    const SRZ_CAS DrawDesc *d = as_const(a.draws) + draw0 + j;
+    if (d->verts != a.verts) continue; // (another slot's draw)
+    const size_t draw_at = frame_at + (size_t)(d->tri_off - tri0) * 3u * a.n_ch;
+    for (uint32_t c = c_begin; c < c_end; ++c) {
+      const size_t i = draw_at + (size_t)a.corners[c] * a.n_ch; // (corner = 3 * face + k: the stream's own order)
+      if (GRAD)
+        val = val + a.gout[i];
+      else
+        a.out[i] = val;
+    }
+  }
+  if (GRAD) a.gattr[((size_t)f * a.n_verts + v) * a.n_ch + ch] = val;
+}
+__global__ __launch_bounds__(256) void k_corner_attr(const CornerAttrArgs a) { corner_attr_walk<false>(a); }
+__global__ __launch_bounds__(256) void k_corner_attr_grad(const CornerAttrArgs a) { corner_attr_walk<true>(a); }
+
+// ================================================================================================================
 // Tight rectangles.  The reference tests every pixel of a triangle's bounding box; a pixel outside the triangle fails the test
 // and leaves no trace, so pixels that are CERTAINLY outside need not be tested — and a tile or band the triangle certainly
 // misses need not list it.  slab_extent gives the extent along u of (triangle ∩ slab lo <= w <= hi), (u, w) = (x, y) or (y, x),
@@ -5931,6 +6042,30 @@ void launch_positions(const FrameDesc *frames, uint32_t n_frames, const float *t
 void launch_vertex_grad(const VertexGradArgs &a, hipStream_t s) {
   if (a.n_frames == 0 || a.n_verts == 0) return;
   hipLaunchKernelGGL(k_vertex_grad, dim3((a.n_verts + 255) / 256, a.n_frames), dim3(256), 0, s, a);
+}
+
+void launch_mesh_normals(const MeshNormalsArgs &a, hipStream_t s) {
+  if (a.n_sets == 0 || a.n_verts == 0) return;
+  hipLaunchKernelGGL(k_mesh_normals, dim3((a.n_verts + 255) / 256, a.n_sets), dim3(256), 0, s, a);
+}
+
+void launch_mesh_normals_grad(const MeshNormalsArgs &a, hipStream_t s) {
+  if (a.n_sets == 0 || a.n_verts == 0) return;
+  const dim3 grid((a.n_verts + 255) / 256, a.n_sets);
+  hipLaunchKernelGGL(k_mesh_normals_grad<1>, grid, dim3(256), 0, s, a); // (stream order: every gS is stored before phase 2 reads one)
+  hipLaunchKernelGGL(k_mesh_normals_grad<2>, grid, dim3(256), 0, s, a);
+}
+
+// (n_verts * n_ch <= 2^32 * 64: at most 2^30 blocks)
+static dim3 corner_attr_grid(const CornerAttrArgs &a) { return dim3((uint32_t)(((uint64_t)a.n_verts * a.n_ch + 255) / 256), a.n_frames); }
+void launch_corner_attr(const CornerAttrArgs &a, hipStream_t s) {
+  if (a.n_frames == 0 || a.n_verts == 0) return;
+  hipLaunchKernelGGL(k_corner_attr, corner_attr_grid(a), dim3(256), 0, s, a);
+}
+
+void launch_corner_attr_grad(const CornerAttrArgs &a, hipStream_t s) {
+  if (a.n_frames == 0 || a.n_verts == 0) return;
+  hipLaunchKernelGGL(k_corner_attr_grad, corner_attr_grid(a), dim3(256), 0, s, a);
 }
 
 void launch_chunks(const RenderArgs &a, int n_frames, uint32_t max_tris, hipStream_t s) {

@@ -27,6 +27,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_motion_bytes", "srz_frameset_motion", "srz_frameset_interpolate_bytes", "srz_frameset_interpolate",
            "srz_frameset_interpolate_grad", "srz_frameset_position_grad", "srz_frameset_antialias", "srz_frameset_antialias_grad",
            "srz_frameset_positions", "srz_sceneset_vertex_grad",
+           "srz_mesh_normals", "srz_mesh_normals_grad", "srz_sceneset_corner_attr", "srz_sceneset_corner_attr_grad",
            "srz_frameset_texture", "srz_frameset_texture_grad",
            "srz_texture_mip_levels", "srz_texture_mip_bytes", "srz_texture_mip_build", "srz_texture_mip_fold",
            "srz_frameset_interpolate_deriv", "srz_frameset_texture_mip", "srz_frameset_texture_mip_grad",
@@ -91,6 +92,10 @@ def lib():
         L.srz_frameset_position_grad.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp]
         L.srz_frameset_positions.argtypes = [vp, vp, C.c_uint32, vp, C.c_size_t, vp]
         L.srz_sceneset_vertex_grad.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, vp, vp, C.c_uint32, vp]
+        L.srz_mesh_normals.argtypes = [vp, C.c_int, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]
+        L.srz_mesh_normals_grad.argtypes = [vp, C.c_int, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
+        L.srz_sceneset_corner_attr.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]
+        L.srz_sceneset_corner_attr_grad.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, vp, C.c_uint32, vp]
         L.srz_frameset_antialias.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_size_t, C.c_uint32, vp]
         L.srz_frameset_antialias_grad.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp]
         L.srz_frameset_texture.argtypes = abi.TEXTURE_ARGTYPES
@@ -302,6 +307,21 @@ class FrameSet:
         self.ctx._check(lib().srz_sceneset_vertex_grad(self.ctx.h, self.h, mesh_id, C.c_void_p(d_gpos_ptr), pos_tris,
                                                        C.c_void_p(d_gverts_ptr or None), C.c_void_p(d_gdraw_ptr or None), draw_stride,
                                                        _stream(stream)))
+
+    def corner_attr(self, mesh_id, d_attr_ptr, n_ch, attr_frames, d_out_ptr, pos_tris, stream=None):
+        """per-vertex attributes of mesh slot mesh_id, d_attr [attr_frames][n_verts][n_ch] float32 (attr_frames 1 or the frame count),
+        laid out as the set's triangle stream: corner k of every face of every draw of the slot in d_out [n_frames][pos_tris][3][n_ch]
+        — interpolate's layout with attr_frames = n_frames.  Everything else in d_out is left untouched: one call per slot into one
+        buffer.  A sceneset only.  Asynchronous."""
+        self.ctx._check(lib().srz_sceneset_corner_attr(self.ctx.h, self.h, mesh_id, C.c_void_p(d_attr_ptr), n_ch, attr_frames,
+                                                       C.c_void_p(d_out_ptr), pos_tris, _stream(stream)))
+
+    def corner_attr_grad(self, mesh_id, d_gout_ptr, n_ch, d_gattr_ptr, pos_tris, stream=None):
+        """the backward of corner_attr: d_gout [n_frames][pos_tris][3][n_ch] → d_gattr [n_frames][n_verts][n_ch], every element
+        written: one running sum over the frame's draws of the slot in draw order and the vertex's corners in list order (a gather:
+        deterministic; zeros for a frame that does not draw the slot).  Asynchronous."""
+        self.ctx._check(lib().srz_sceneset_corner_attr_grad(self.ctx.h, self.h, mesh_id, C.c_void_p(d_gout_ptr), n_ch, C.c_void_p(d_gattr_ptr),
+                                                            pos_tris, _stream(stream)))
 
     def antialias(self, d_vis_ptr, d_in_ptr, n_ch, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
         """the planes d_in [frame][n_ch][local_rows][width] float32 blended across the silhouettes of a visibility buffer of this set:
@@ -597,6 +617,20 @@ class Context:
         records [pos3 nrm3 uv2] — one asynchronous device-to-device copy.  Faces, addresses and the upload counter stay: every
         sceneset that draws the slot stays valid and transforms the new vertices from its next vertex stage on."""
         self._check(lib().srz_mesh_update(self.h, mesh_id, C.c_void_p(d_verts_ptr), n_verts, _stream(stream)))
+
+    def mesh_normals(self, mesh_id, d_pos_ptr, pos_stride, n_sets, d_nrm_ptr, nrm_stride, stream=None):
+        """area-weighted vertex normals of slot mesh_id's faces for n_sets position sets on the device: vertex v of set s at float
+        (s * n_verts + v) * stride of d_pos / d_nrm (strides >= 3).  d_pos_ptr None / 0: the slot's own vertices, d_nrm_ptr None / 0:
+        the slot's own nrm fields (n_sets 1 either way); both: the slot refreshed in place.  A gather, deterministic (include/srz.h
+        states the rule).  Asynchronous."""
+        self._check(lib().srz_mesh_normals(self.h, mesh_id, C.c_void_p(d_pos_ptr or None), pos_stride, n_sets, C.c_void_p(d_nrm_ptr or None),
+                                           nrm_stride, _stream(stream)))
+
+    def mesh_normals_grad(self, mesh_id, d_pos_ptr, pos_stride, n_sets, d_gnrm_ptr, gnrm_stride, d_work_ptr, d_gpos_ptr, stream=None):
+        """the backward of mesh_normals: d_gnrm (laid out like the normals, gnrm_stride >= 3) → d_gpos [n_sets][n_verts][3], every
+        element written; d_work: a workspace of d_gpos's size.  Two gathers, deterministic.  Asynchronous."""
+        self._check(lib().srz_mesh_normals_grad(self.h, mesh_id, C.c_void_p(d_pos_ptr or None), pos_stride, n_sets, C.c_void_p(d_gnrm_ptr or None),
+                                                gnrm_stride, C.c_void_p(d_work_ptr or None), C.c_void_p(d_gpos_ptr or None), _stream(stream)))
 
     def draw(self, frame, planes=None, primitive=abi.PRIMITIVE_TRIANGLES, want_stats=False):
         """TraditionalRasterizer::draw for one scene; planes (z,c0,c1,c2) are modified in place."""

@@ -721,3 +721,99 @@ def scene_positions(fs, meshes, mvp=None, zmap=None, pos_tris=None, stream=None)
     if zmap is not None and (zmap.dtype != torch.float32 or tuple(zmap.shape) != (fs.n_frames, D, 2)):
         raise ValueError(f"scene_positions: zmap must be float32 {(fs.n_frames, D, 2)}, got {tuple(zmap.shape)} {zmap.dtype}")
     return _ScenePositions.apply(fs, ids, pos_tris, stream, mvp, zmap, *[meshes[m] for m in ids])
+
+
+# ------------------------------------------------------------------------------------------------ normals and per-vertex attributes
+def _sets_arg(ctx, slot, t, name):
+    """a CUDA float32 [V, 3] or [B, V, 3] tensor for mesh slot `slot` -> (contiguous tensor, number of sets)"""
+    V = ctx.mesh_sizes[slot][0]
+    if t.dtype != torch.float32 or not t.is_cuda or t.dim() not in (2, 3) or tuple(t.shape[-2:]) != (V, 3) or (t.dim() == 3 and not 1 <= t.shape[0] <= 65535):
+        raise ValueError(f"mesh_normals: {name} must be a CUDA float32 tensor [{V}, 3] or [B, {V}, 3] (B <= 65535), got {tuple(t.shape)} {t.dtype}")
+    return t.contiguous(), (t.shape[0] if t.dim() == 3 else 1)
+
+
+class _MeshNormals(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, sctx, slot, stream):
+        p, n_sets = _sets_arg(sctx, slot, pos.detach(), "pos")
+        nrm = torch.empty_like(p)
+        sctx.mesh_normals(slot, p.data_ptr(), 3, n_sets, nrm.data_ptr(), 3, _stream_ptr(stream))
+        ctx.sctx, ctx.slot, ctx.stream, ctx.n_sets = sctx, slot, stream, n_sets
+        ctx.save_for_backward(p)
+        return nrm
+
+    @staticmethod
+    def backward(ctx, gnrm):
+        (p,) = ctx.saved_tensors
+        gnrm = gnrm.contiguous()
+        work, gpos = torch.empty_like(p), torch.empty_like(p)
+        ctx.sctx.mesh_normals_grad(ctx.slot, p.data_ptr(), 3, ctx.n_sets, gnrm.data_ptr(), 3, work.data_ptr(), gpos.data_ptr(),
+                                   _stream_ptr(ctx.stream))
+        return gpos, None, None, None
+
+
+def mesh_normals(ctx, slot, pos, stream=None):
+    """the area-weighted vertex normals of mesh slot `slot` of Context `ctx` at vertex positions pos, a CUDA float32 tensor [V, 3] or
+    [B, V, 3] (B sets of positions over the slot's face list, one call) → the same shape: per vertex the sum of cross(p1 - p0, p2 - p0)
+    over the faces that name it, normalised; zeros for a vertex no face names and for a sum that is zero or not finite
+    (Context.mesh_normals, include/srz.h states the rule).  Differentiable with respect to pos (Context.mesh_normals_grad).  Both
+    directions are gathers without atomics: the values and pos.grad are bit-reproducible.  The slot's own vertices are neither read
+    nor written: refresh_normals is the in-place form.  stream: a raw stream handle, None = torch's current stream."""
+    return _MeshNormals.apply(pos, ctx, slot, stream)
+
+
+def refresh_normals(ctx, slot, stream=None):
+    """the nrm fields of mesh slot `slot` recomputed IN PLACE from the positions the slot holds (Context.mesh_normals with both
+    pointers null): the call that follows mesh_update on the same stream, so that shade_visibility, gbuffer(NORMAL) and the colour
+    render of every sceneset that draws the slot see the normals of the moved mesh.  stream: a raw stream handle, None = torch's
+    current stream."""
+    ctx.mesh_normals(slot, None, 8, 1, None, 8, _stream_ptr(stream))
+
+
+class _CornerAttr(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, fs, slots, pos_tris, stream, *attrs):
+        T = _set_tris(fs, pos_tris)
+        C_ = attrs[0].shape[-1]
+        out = torch.zeros((fs.n_frames, T, 3, C_), dtype=torch.float32, device=attrs[0].device)
+        for slot, a in zip(slots, attrs):
+            a = a.detach().contiguous()
+            fs.corner_attr(slot, a.data_ptr(), C_, a.shape[0] if a.dim() == 3 else 1, out.data_ptr(), T, _stream_ptr(stream))
+        ctx.fs, ctx.slots, ctx.stream, ctx.T = fs, slots, stream, T
+        ctx.shapes = [tuple(a.shape) for a in attrs]
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        fs = ctx.fs
+        gout = gout.contiguous()
+        grads = []
+        for i, (slot, shape) in enumerate(zip(ctx.slots, ctx.shapes)):
+            if not ctx.needs_input_grad[4 + i]:
+                grads.append(None)
+                continue
+            g = torch.empty((fs.n_frames, shape[-2], shape[-1]), dtype=torch.float32, device=gout.device)
+            fs.corner_attr_grad(slot, gout.data_ptr(), shape[-1], g.data_ptr(), ctx.T, _stream_ptr(ctx.stream))
+            grads.append(g.sum(0) if len(shape) == 2 else g)
+        return (None, None, None, None, *grads)
+
+
+def corner_attr(fs, attrs, pos_tris=None, stream=None):
+    """per-vertex attributes laid out as sceneset `fs`'s triangle stream — what interpolate takes.  attrs: a dict mesh slot → a CUDA
+    float32 tensor [V, C] (shared by the frames) or [n_frames, V, C], V the slot's vertex count, one C <= abi.ATTR_MAX_CH for all →
+    [n_frames, T, 3, C] float32, T = pos_tris (default: the largest triangle count of the set's frames): zeros first, then one
+    FrameSet.corner_attr call per slot, so the triangles of slots the dict does not name stay zero.  Differentiable with respect to
+    every tensor of the dict (FrameSet.corner_attr_grad, a gather: bit-reproducible); a [V, C] tensor's gradient is the per-frame
+    result summed over the frames, as scene_positions has it.  interpolate(fs, vis, corner_attr(fs, {slot: mesh_normals(ctx, slot,
+    verts)})) carries a shading loss to the vertices through the normals.  stream: a raw stream handle, None = torch's current stream."""
+    slots = tuple(sorted(attrs))
+    if not slots:
+        raise ValueError("corner_attr: no attributes given")
+    n_ch = attrs[slots[0]].shape[-1] if attrs[slots[0]].dim() else 0
+    for m in slots:
+        a = attrs[m]
+        V = fs.ctx.mesh_sizes[m][0]
+        if a.dtype != torch.float32 or not a.is_cuda or tuple(a.shape) not in ((V, n_ch), (fs.n_frames, V, n_ch)) or not 1 <= n_ch <= abi.ATTR_MAX_CH:
+            raise ValueError(f"corner_attr: slot {m} must be a CUDA float32 tensor [{V}, C] or [{fs.n_frames}, {V}, C] with one C in "
+                             f"1..{abi.ATTR_MAX_CH} for every slot, got {tuple(a.shape)} {a.dtype}")
+    return _CornerAttr.apply(fs, slots, pos_tris, stream, *[attrs[m] for m in slots])
