@@ -63,6 +63,8 @@ extern "C" {
  *      (additive, same version) depth peeling: the layer behind a visibility buffer srz_frameset_peel_visibility
  *      (additive, same version) vertex normals and per-vertex attributes on the device, with gradients srz_mesh_normals /
  *      srz_mesh_normals_grad / srz_sceneset_corner_attr / srz_sceneset_corner_attr_grad
+ *      (additive, same version) cube-map lookup by direction over a visibility buffer, with gradients srz_frameset_texture_cube /
+ *      srz_frameset_texture_cube_grad
  */
 #define SRZ_ABI_VERSION 7
 
@@ -637,6 +639,87 @@ int srz_frameset_texture(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, cons
 int srz_frameset_texture_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const void *d_gout, const float *d_tex,
                               uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t mode, float *d_gtex, void *d_guv,
                               uint32_t flags, void *stream);
+/* A CUBE MAP LOOKED UP BY DIRECTION over a visibility buffer, and its gradients: a float32 cube map of the caller's own (an
+ * environment map, irradiance, a learned lighting probe) sampled BILINEARLY and SEAMLESSLY at the direction planes
+ * srz_frameset_interpolate wrote for a three-channel attribute (normals, reflection vectors), and the backward of that lookup, to the
+ * texels and to the direction.  No level of detail: a cube has no mip pyramid here.
+ * d_vis: a visibility buffer of THIS set on this ctx's shard.  d_dir: [frame][3][local_rows][width] float32 (x, y, z),
+ * srz_frameset_interpolate_bytes(3) bytes; the directions need not be normalised.  d_tex and d_gtex: [tex_frames][6][n][n][n_ch]
+ * float32 — face, row, column, channel; channels last — 4-byte aligned; tex_frames is 1 (every frame samples the same cube) or the
+ * set's frame count; 1 <= n <= SRZ_TEX_MAX_SIZE; 1 <= n_ch <= SRZ_ATTR_MAX_CH.  d_out and d_gout: [frame][n_ch][local_rows][width]
+ * float32, srz_frameset_interpolate_bytes(n_ch) bytes.  d_gdir: d_dir's shape.  Band sharding (each rank adds the partial sums of its
+ * own bands), local_rows, stream semantics, asynchrony, the 16-byte alignment of the visibility buffer and every plane buffer (d_dir,
+ * d_out, d_gout, d_gdir), owner and nobody, what a nobody pixel's words of d_out and d_gdir become with and without SRZ_FUSED_CLEAR,
+ * and what the passes do not read or launch: all as srz_frameset_texture.  The words of d_dir and d_gout at nobody's pixels never
+ * reach a result: they may hold anything.
+ * THE FACES, in the order +X -X +Y -Y +Z -Z.  Face f has a normal n and in-face axes su, sv, signed unit axis vectors; a point of the
+ * face is n + s su + t sv with s, t in [-1, 1], and texel (x, y) — column x, row y — has its centre at s = (2 x + 1) / N - 1,
+ * t = (2 y + 1) / N - 1:
+ *     face   n           su          sv
+ *     +X     ( 1, 0, 0)  (0, 0, -1)  (0, -1, 0)
+ *     -X     (-1, 0, 0)  (0, 0,  1)  (0, -1, 0)
+ *     +Y     (0,  1, 0)  (1, 0, 0)   (0, 0,  1)
+ *     -Y     (0, -1, 0)  (1, 0, 0)   (0, 0, -1)
+ *     +Z     (0, 0,  1)  ( 1, 0, 0)  (0, -1, 0)
+ *     -Z     (0, 0, -1)  (-1, 0, 0)  (0, -1, 0)
+ * THE RULE, all of it float32, nothing fused except where fmaf is written, the divisions the IEEE division, always the exact
+ * arithmetic (SRZ_OPT_APPROX_SHADE has no effect).  Per owned pixel with the direction (dx, dy, dz), a? = fabsf(d?):
+ *   unsampled: a component not finite (!(fabsf(c) < INFINITY)), or max(ax, ay, az) == 0 -> every channel of out is 0 (written: the
+ *              pixel has an owner), gdir = (0, 0, 0), no add
+ *   major axis: x if ax >= ay && ax >= az; else y if ay >= az; else z;   face = 2 * axis + (its component > 0 ? 0 : 1)
+ *   ma = fabsf(major component);  sc = the component su names, negated where su is negative;  tc likewise with sv
+ *   s = sc / ma;  t = tc / ma                     (both in [-1, 1]: the division is correctly rounded and |sc|, |tc| <= ma)
+ *   per axis — shown for x with s; y with t likewise:
+ *     u = fmaf(s, 0.5f, 0.5f);  fx = u * (float)N - 0.5f;  x0f = floorf(fx);  tx = fx - x0f;  x0 = (int)x0f;  x1 = x0 + 1
+ * Every conversion to an integer follows a float in [-0.5, N - 0.5]: x0, y0 lie in [-1, N - 1] and x1, y1 in [0, N].
+ * SEAMS.  A corner texel with x or y in {-1, N} is RESOLVED onto the neighbouring face: the lookup is seamless, there is no clamp
+ * mode.  Crossing in +s (x = N) or -s (x = -1), the neighbour g is the face whose normal is +su or -su, and the resolved texel is the
+ * texel of g whose centre is n_g + (1 - 1 / N) n_f + t sv_f, t the corner's own; crossing in +-t likewise with su and sv exchanged.
+ * In integers that is a fixed map per (face, side) — one index of the neighbour becomes 0 or N - 1, the other is the index i along
+ * the edge, kept or mirrored (N - 1 - i) — and the passes use that table of 24 rows, no float reprojection:
+ *     face   x = -1         x = N          y = -1             y = N
+ *     +X     +Z (N-1, i)    -Z (0, i)      +Y (N-1, N-1-i)    -Y (N-1, i)
+ *     -X     -Z (N-1, i)    +Z (0, i)      +Y (0, i)          -Y (0, N-1-i)
+ *     +Y     -X (i, 0)      +X (N-1-i, 0)  -Z (N-1-i, 0)      +Z (i, 0)
+ *     -Y     -X (N-1-i, N-1) +X (i, N-1)   +Z (i, N-1)        -Z (N-1-i, N-1)
+ *     +Z     -X (N-1, i)    +X (0, i)      +Y (i, N-1)        -Y (i, 0)
+ *     -Z     +X (N-1, i)    -X (0, i)      +Y (N-1-i, 0)      -Y (N-1-i, N-1)
+ *   (the resolved (column, row); i = the corner's row for the x sides, its column for the y sides).
+ *   A corner outside in BOTH axes — at most one per lookup, and only within half a texel of a cube vertex, where three faces meet and
+ *   no fourth texel exists — has its row clamped into [0, N - 1] first and then crosses in x.  That is a CHOICE: within that half
+ *   texel the lookup is continuous only up to the spread of the three vertex texels; everywhere else, across every edge, a direction
+ *   gives the same word through either adjacent face.
+ * FORWARD, deterministic, bit for bit: per channel, with t_rc the resolved texel of corner (y_r, x_c),
+ *   top = fmaf(tx, t01 - t00, t00);  bot = fmaf(tx, t11 - t10, t10);  out = fmaf(ty, bot - top, top)
+ * BACKWARD: d_gout, the same d_dir and d_vis; at least one of d_gtex and d_gdir is non-null.
+ *   d_gtex (d_tex itself may be null when only d_gtex is asked for): srz_frameset_texture_grad's four weights w_rc, the float32
+ *   product w_rc * gout[ch] ADDED at the RESOLVED texels (ft = 0 when tex_frames == 1): a pixel near an edge adds into both faces, and
+ *   two corners that coincide (N == 1; the clamped corner at a vertex) both add.  THE ORDER OF THE ADDS IS UNSPECIFIED, each add
+ *   rounds, so d_gtex is NOT BIT-REPRODUCIBLE between launches: srz_frameset_texture_grad's bound, n 2^-24 / (1 - n 2^-24) * sum |term|
+ *   with n contributing adds, exact at n = 1; hardware float atomics, so d_gtex must be ordinary (coarse-grained) device memory.
+ *   d_gdir, needs d_tex, deterministic, bit for bit: au, av exactly as srz_frameset_texture_grad's d_guv sums over the four
+ *   resolved texels, then
+ *     gs = au * (0.5f * (float)N);  gt = av * (0.5f * (float)N);  inv = 1.0f / ma
+ *     g_sc = gs * inv;  g_tc = gt * inv;  g_ma = -(fmaf(gs, s, gt * t) * inv)
+ *     gdir[sc's axis] = g_sc, negated where su is negative;  gdir[tc's axis] = g_tc, negated where sv is negative
+ *     gdir[major axis] = (major component > 0 ? g_ma : -g_ma)
+ *   (the face and the texels are held fixed; the lookup does not depend on the direction's length, so dot(gdir, d) is 0 up to
+ *   rounding).  It has the layout of srz_frameset_interpolate_grad's d_gout at n_ch = 3: the chain texture_cube_grad ->
+ *   interpolate_grad -> corner_attr_grad -> mesh_normals_grad runs on the device.
+ * SUBNORMALS are numbers: the library is built without flush-to-zero (binary32 denormals on, the division the correctly rounded
+ * one), so a direction of subnormal components is sampled like any other and s, t are what IEEE division gives; inv = 1.0f / ma
+ * overflows to +inf for ma below 2^-128, and gdir is then inf or NaN as IEEE has it.  Non-finite texels and gradients propagate as
+ * IEEE has them; no value of the direction makes a pass read or write outside its buffers.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set, d_vis, d_dir, d_tex (forward; backward with
+ * d_gdir), d_out, d_gout, or both of d_gtex and d_gdir; n == 0 or above SRZ_TEX_MAX_SIZE; n_ch == 0 or above SRZ_ATTR_MAX_CH;
+ * tex_frames not 1 or the frame count; a short out_bytes; a misaligned pointer; any bit of `flags` but SRZ_FUSED_CLEAR; an output
+ * that overlaps an input (d_out with d_vis, d_dir or d_tex; d_gtex or d_gdir with d_vis, d_dir, d_gout or d_tex) or the other
+ * output. */
+int srz_frameset_texture_cube(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_dir, const float *d_tex, uint32_t n,
+                              uint32_t n_ch, uint32_t tex_frames, void *d_out, size_t out_bytes, uint32_t flags, void *stream);
+int srz_frameset_texture_cube_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_dir, const void *d_gout,
+                                   const float *d_tex, uint32_t n, uint32_t n_ch, uint32_t tex_frames, float *d_gtex, void *d_gdir,
+                                   uint32_t flags, void *stream);
 /* MIPMAPPED TEXTURE SAMPLING over a visibility buffer, and its gradients: the TRILINEAR lookup over a mip pyramid of the caller's
  * texture that goes with the bilinear lookup above, its level chosen from the screen-space derivatives of uv.  Three pieces: the
  * pyramid (build, and fold: its backward), the derivatives of an interpolated attribute, the lookup and its backward.  All of it

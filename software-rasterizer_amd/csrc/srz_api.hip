@@ -752,7 +752,7 @@ int stats_pass(srz_ctx *ctx, srz_frameset *fs, const float *d_start, uint32_t fl
 
 } // namespace
 
-// The passes over a visibility buffer (srz_frameset_shade_visibility .. srz_frameset_texture_mip_grad): what their entry points share.
+// The passes over a visibility buffer (srz_frameset_shade_visibility .. srz_frameset_texture_cube_grad): what their entry points share.
 // Each entry point is its own argument rules, these checks, its own Args fields, the launch.
 namespace {
 
@@ -878,6 +878,29 @@ TexArgs texture_args(const srz_frameset *fs, const void *d_vis, const void *d_uv
   a.vis_stride = 4ull * plane, a.frame_stride = out_planes * plane, a.uv_stride = 2ull * plane, a.gout_stride = n_ch * plane;
   a.tex_frame_stride = tex_frames == 1u ? 0ull : (uint64_t)tex_h * tex_w * n_ch;
   a.tex_w = tex_w, a.tex_h = tex_h, a.n_ch = n_ch, a.mode = mode;
+  a.flags_or = flags;
+  return a;
+}
+// what srz_frameset_texture_cube and _texture_cube_grad check alike; the cube's bytes in *tex_bytes
+int check_cube(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, uint32_t n, uint32_t n_ch, uint32_t tex_frames, uint32_t flags,
+               size_t *tex_bytes) {
+  if (n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_ATTR_MAX_CH");
+  if (n == 0u || n > SRZ_TEX_MAX_SIZE) return fail(ctx, SRZ_E_INVALID, fn + ": n must be 1 .. SRZ_TEX_MAX_SIZE");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  if (tex_frames != 1u && tex_frames != (uint32_t)fs->n_frames)
+    return fail(ctx, SRZ_E_INVALID, fn + ": tex_frames must be 1 or the set's frame count");
+  *tex_bytes = (size_t)tex_frames * 6u * n * n * n_ch * sizeof(float);
+  return SRZ_OK;
+}
+CubeArgs cube_args(const srz_frameset *fs, const void *d_vis, const void *d_dir, const float *d_tex, uint32_t n, uint32_t n_ch,
+                   uint32_t tex_frames, uint32_t out_planes, void *d_out, uint32_t flags) {
+  CubeArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  a.dir = (const float *)d_dir, a.tex = d_tex;
+  a.vis_stride = 4ull * plane, a.frame_stride = out_planes * plane, a.dir_stride = 3ull * plane, a.gout_stride = n_ch * plane;
+  a.tex_frame_stride = tex_frames == 1u ? 0ull : 6ull * n * n * n_ch;
+  a.n = n, a.n_ch = n_ch;
   a.flags_or = flags;
   return a;
 }
@@ -1971,6 +1994,55 @@ int srz_frameset_texture_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis,
   TexArgs a = texture_args(fs, d_vis, d_uv, d_tex, tex_w, tex_h, n_ch, tex_frames, mode, 2u, d_guv, flags);
   a.gout = (const float *)d_gout, a.gtex = d_gtex;
   launch_tex_grad(a, s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_texture_cube(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_dir, const float *d_tex, uint32_t n,
+                              uint32_t n_ch, uint32_t tex_frames, void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_texture_cube");
+  if (!fs || !d_vis || !d_dir || !d_tex || !d_out)
+    return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_dir ? "d_dir" : !d_tex ? "d_tex" : "d_out"));
+  size_t tex_bytes = 0;
+  if (int rc = check_cube(ctx, fs, fn, n, n_ch, tex_frames, flags, &tex_bytes)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, n_ch), dir_bytes = srz_frameset_interpolate_bytes(ctx, fs, 3u);
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": out_bytes is too small for d_out");
+  if (!aligned<16>({d_vis, d_dir, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_dir, d_out) must be 16-byte aligned");
+  if (!aligned<4>({d_tex})) return fail(ctx, SRZ_E_INVALID, fn + ": d_tex must be 4-byte aligned");
+  if (ranges_overlap({d_out, need}, {d_vis, vis_bytes}) || ranges_overlap({d_out, need}, {d_dir, dir_bytes}) ||
+      ranges_overlap({d_out, need}, {d_tex, tex_bytes}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": d_out overlaps d_vis, d_dir or d_tex");
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_texture)
+  launch_cube(cube_args(fs, d_vis, d_dir, d_tex, n, n_ch, tex_frames, n_ch, d_out, flags), s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_texture_cube_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_dir, const void *d_gout,
+                                   const float *d_tex, uint32_t n, uint32_t n_ch, uint32_t tex_frames, float *d_gtex, void *d_gdir,
+                                   uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_texture_cube_grad");
+  if (!fs || !d_vis || !d_dir || !d_gout)
+    return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_dir ? "d_dir" : "d_gout"));
+  if (!d_gtex && !d_gdir) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gtex nor d_gdir is asked for");
+  if (d_gdir && !d_tex) return fail(ctx, SRZ_E_INVALID, fn + ": d_gdir needs d_tex");
+  size_t tex_bytes = 0;
+  if (int rc = check_cube(ctx, fs, fn, n, n_ch, tex_frames, flags, &tex_bytes)) return rc;
+  const size_t gout_bytes = srz_frameset_interpolate_bytes(ctx, fs, n_ch), dir_bytes = srz_frameset_interpolate_bytes(ctx, fs, 3u);
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (!aligned<16>({d_vis, d_dir, d_gout, d_gdir}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_dir, d_gout, d_gdir) must be 16-byte aligned");
+  if (!aligned<4>({d_tex, d_gtex})) return fail(ctx, SRZ_E_INVALID, fn + ": d_tex and d_gtex must be 4-byte aligned");
+  if (int rc = check_grad_overlap(ctx, fn + " (d_gtex, d_gdir against d_vis, d_dir, d_gout, d_tex)", {{d_gtex, tex_bytes}, {d_gdir, dir_bytes}},
+                                  {{d_vis, vis_bytes}, {d_dir, dir_bytes}, {d_gout, gout_bytes}, {d_tex, tex_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_texture)
+  CubeArgs a = cube_args(fs, d_vis, d_dir, d_tex, n, n_ch, tex_frames, 3u, d_gdir, flags);
+  a.gout = (const float *)d_gout, a.gtex = d_gtex;
+  launch_cube_grad(a, s);
   return end_pass(ctx);
 }
 

@@ -429,6 +429,31 @@ struct TexArgs {
 };
 void launch_tex(const TexArgs &a, hipStream_t s);
 void launch_tex_grad(const TexArgs &a, hipStream_t s);
+// srz_frameset_texture_cube / _texture_cube_grad: a float cube map of the caller's [texture frame][face][row][column][channel], faces
+// n x n, looked up seamlessly by the direction planes [frame][3][local_rows][width] under a visibility buffer (k_cube), and the
+// gradients of that with respect to the texels (gtex, added into) and to the direction (k_cube_grad).  vis as above; `out` is the
+// forward's [frame][n_ch][local_rows][width] or the backward's gdir [frame][3][local_rows][width] (may be null there).  The host
+// has checked 1 <= n <= SRZ_TEX_MAX_SIZE: a texel's index (face * n + row) * n + column stays below 6 * 2^28
+struct CubeArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *dir;
+  const float *tex;          // (backward: may be null when gdir is)
+  float *out;
+  const float *gout;         // backward: [frame][n_ch][local_rows][width]
+  float *gtex;               // backward: tex's shape, added into (may be null)
+  uint64_t vis_stride;       // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride;     // floats per frame in out
+  uint64_t dir_stride;       // floats per frame in dir = 3 * local_rows * width
+  uint64_t gout_stride;      // floats per frame in gout = n_ch * local_rows * width
+  uint64_t tex_frame_stride; // floats per frame in tex / gtex = 6 * n * n * n_ch; 0: one cube for every frame
+  uint32_t n, n_ch;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_cube(const CubeArgs &a, hipStream_t s);
+void launch_cube_grad(const CubeArgs &a, hipStream_t s);
 // THE MIP PYRAMID of a caller texture (include/srz.h states the geometry): level l of a tex_w x tex_h texture is
 // max(1, tex_w >> l) x max(1, tex_h >> l) — every level that exists came from an even (or one-texel) extent, so the shifts are the
 // halvings — and the levels 1 .. n_levels - 1 lie one after another, each [tex_frames][h_l][w_l][n_ch].  Host and device share these.

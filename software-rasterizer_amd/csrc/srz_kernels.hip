@@ -3298,7 +3298,8 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
 //               in the others such a thread just moves on.
 // Then what the bodies do next: quad_ids (the four owner ids, strangers clamped to nobody), quad_bary (α, β and γ of the owned
 // pixels) and quad_store_owned (whole quads, or the owned pixels only).
-// CALLERS: k_shade_vis (pass_tiles with its kind filter, pass_tile, quad_ids), k_interp, k_interp_grad, k_interp_deriv (all of it).
+// CALLERS: k_shade_vis (pass_tiles with its kind filter, pass_tile, quad_ids), k_interp, k_interp_grad, k_interp_deriv (all of it),
+// k_cube and k_cube_grad (the walk, quad_ids, quad_store_owned).
 // COPIES, each naming this definition — a fix to the walk goes into them too: k_gbuffer, k_motion, k_pos_grad, aa_body, k_tex,
 // k_tex_grad, k_tex_mip, k_tex_mip_grad (with tex_quad and mip_quad).  Moved onto these helpers they computed the same words
 // (the whole suite passed) but ran slower than their inline text on an MI355X at 256 frames of 1024²: k_gbuffer +4 %, k_motion +6 %,
@@ -5107,6 +5108,277 @@ __global__ __launch_bounds__(256) void k_tex_grad(TexArgs a) {
 }
 
 // ================================================================================================================
+// k_cube — A CALLER'S CUBE MAP LOOKED UP BY DIRECTION OVER A VISIBILITY BUFFER (srz_frameset_texture_cube, include/srz.h states the
+// rule): a float cube [frame][face][row][column][channel], faces n x n, sampled bilinearly and seamlessly at the direction planes
+// interpolate wrote for a three-channel attribute.  k_tex's shape on the passes' helpers: pass_walk's XCD-ordered walk, 4 pixels of a
+// row per thread, one 16-byte id load (quad_ids), the three direction words only for a quad with an owner, every plane leaves
+// through quad_store_owned; no LDS, no barrier.  The face, the two fractions and the four RESOLVED texel indices of a pixel (a
+// corner one step outside its face lands on the neighbouring face: cube_texel) are formed once, global over the cube — (face * n +
+// row) * n + column < 6 * 2^28 —; the wave-uniform channel loop then gathers 4 * nc floats per sampled pixel, ATTR_CHUNK channels at
+// a time, the tail masked: tex_quad's arithmetic from there on.
+// Every float -> int conversion follows s, t in [-1, 1] (the IEEE division of a component by the largest), so x0, y0 lie in
+// [-1, n - 1]; the integer clamp behind it never changes a value and keeps every index inside the cube whatever the division did.
+// ================================================================================================================
+struct CubeTap {
+  uint32_t i00, i01, i10, i11; // resolved texels (face * n + row) * n + column of the corners (y0, x0), (y0, x1), (y1, x0), (y1, x1)
+  float tx, ty;
+  float s, t, inv;             // the backward's: the in-face coordinates and 1 / |major component|
+  uint32_t major;              // the major axis, bit 2: its component is positive
+};
+// the seam rows of a face, one byte per side (x = -1, x = n, y = -1, y = n): the neighbour face | which of its indices is fixed
+// (8: row, else column) | fixed at n - 1 (16, else 0) | the index along the edge mirrored (32).  tests/cube_ref.c holds the same
+// 24 rows unpacked; tests/test_cube_ref.py derives them from the faces' axes
+__device__ __forceinline__ uint32_t cube_seams(uint32_t face) {
+  return face == 0u ? 0x13320514u : face == 1u ? 0x23020415u : face == 2u ? 0x0c2d2809u : face == 3u ? 0x3d1c1839u
+       : face == 4u ? 0x0b1a0011u : 0x3b2a0110u;
+}
+// texel (x, y) of `face`, x and y in [-1, n] -> its index in the cube; one outside in both axes: the row clamped first, then across in x
+__device__ __forceinline__ uint32_t cube_texel(uint32_t face, uint32_t seams, int x, int y, int n) {
+  const bool ox = (unsigned)x >= (unsigned)n, oy = (unsigned)y >= (unsigned)n;
+  if (ox && oy) y = y < 0 ? 0 : n - 1;
+  uint32_t g = face;
+  int rx = x, ry = y;
+  if (ox || oy) {
+    const uint32_t side = ox ? (x < 0 ? 0u : 1u) : (y < 0 ? 2u : 3u);
+    const int along = ox ? y : x;
+    const uint32_t r = (seams >> (8u * side)) & 0xffu;
+    const int al = (r & 32u) ? n - 1 - along : along, e = (r & 16u) ? n - 1 : 0;
+    g = r & 7u, rx = (r & 8u) ? al : e, ry = (r & 8u) ? e : al;
+  }
+  return (g * (uint32_t)n + (uint32_t)ry) * (uint32_t)n + (uint32_t)rx;
+}
+// one axis of the rule: in-face coordinate s in [-1, 1] over n texels -> the first texel coordinate, in [-1, n - 1], and the fraction
+__device__ __forceinline__ void cube_axis(float s, int n, int &i0, float &t) {
+  const float u = fmaf_(s, 0.5f, 0.5f), fx = u * (float)n - 0.5f;
+  const float f0 = __builtin_floorf(fx);
+  t = fx - f0;
+  i0 = max(-1, min((int)f0, n - 1)); // (never changes a value: fx lies in [-0.5, n - 0.5])
+}
+// the tap of one direction; false: not sampled (a component not finite, or the zero vector)
+__device__ __forceinline__ bool cube_tap(float dx, float dy, float dz, uint32_t N, CubeTap &p) {
+  const float ax = __builtin_fabsf(dx), ay = __builtin_fabsf(dy), az = __builtin_fabsf(dz);
+  if (!tex_finite(dx) || !tex_finite(dy) || !tex_finite(dz)) return false;
+  if (__builtin_fmaxf(ax, __builtin_fmaxf(ay, az)) == 0.0f) return false;
+  const uint32_t m = (ax >= ay && ax >= az) ? 0u : (ay >= az ? 1u : 2u);
+  const float mc = m == 0u ? dx : m == 1u ? dy : dz;
+  const bool pos = mc > 0.0f;
+  const float ma = __builtin_fabsf(mc);
+  // the components su and sv name, signed: +X (-z, -y)  -X (z, -y)  +Y (x, z)  -Y (x, -z)  +Z (x, -y)  -Z (-x, -y)
+  const float sc = m == 0u ? (pos ? -dz : dz) : m == 1u ? dx : (pos ? dx : -dx);
+  const float tc = m == 1u ? (pos ? dz : -dz) : -dy;
+  const uint32_t face = 2u * m + (pos ? 0u : 1u), seams = cube_seams(face);
+  p.s = sc / ma, p.t = tc / ma, p.inv = 1.0f / ma, p.major = m | (pos ? 4u : 0u);
+  int x0, y0;
+  cube_axis(p.s, (int)N, x0, p.tx);
+  cube_axis(p.t, (int)N, y0, p.ty);
+  p.i00 = cube_texel(face, seams, x0, y0, (int)N), p.i01 = cube_texel(face, seams, x0 + 1, y0, (int)N);
+  p.i10 = cube_texel(face, seams, x0, y0 + 1, (int)N), p.i11 = cube_texel(face, seams, x0 + 1, y0 + 1, (int)N);
+  return true;
+}
+// what k_cube and k_cube_grad do alike in front of their channel loops: the owners, the directions of a quad with an owner, the
+// taps of the sampled pixels -> `own` and `smp`, one bit per pixel
+__device__ __forceinline__ void cube_quad(const CubeArgs &a, const PassTile &t, CubeTap (&tap)[4], uint32_t &own, uint32_t &smp) {
+  uint32_t id[4];
+  own = quad_ids(t, a.vis + (size_t)t.f * a.vis_stride + t.poff, id), smp = 0u;
+  if (own == 0u) return;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 d[3] = {zero4, zero4, zero4};
+  quad_load(a.dir + (size_t)t.f * a.dir_stride + t.poff, t.rc.plane, d, t.whole, t.x4, t.rc.tx1);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (!(own & (1u << k))) continue;
+    if (cube_tap(quad_at(d[0], k), quad_at(d[1], k), quad_at(d[2], k), a.n, tap[k])) smp |= 1u << k;
+  }
+}
+__global__ __launch_bounds__(256) void k_cube(CubeArgs a) {
+  const uint32_t C = a.n_ch;
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const TileRect &rc = t.rc;
+    const bool fused = t.fused(a.flags_or);
+    // ---- 1. owners, directions, the taps
+    CubeTap tap[4] = {};
+    uint32_t own, smp;
+    cube_quad(a, t, tap, own, smp);
+    if (own == 0u && !fused) return;
+    const SRZ_CAS float *tex = as_const(a.tex) + (size_t)t.f * a.tex_frame_stride;
+    // ---- 2. the channels, ATTR_CHUNK at a time (k_tex's loop)
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 q[ATTR_CHUNK];
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) q[i] = make_float4(0.f, 0.f, 0.f, 0.f); // nobody, and an owner that is not sampled: zeros
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(smp & (1u << k))) continue;
+        const SRZ_CAS float *p00 = tex + (size_t)tap[k].i00 * C + c0, *p01 = tex + (size_t)tap[k].i01 * C + c0;
+        const SRZ_CAS float *p10 = tex + (size_t)tap[k].i10 * C + c0, *p11 = tex + (size_t)tap[k].i11 * C + c0;
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+          if (i < nc) {
+            const float t00 = p00[i], t01 = p01[i], t10 = p10[i], t11 = p11[i];
+            const float top = fmaf_(tap[k].tx, t01 - t00, t00), bot = fmaf_(tap[k].tx, t11 - t10, t10);
+            quad_at(q[i], k) = fmaf_(tap[k].ty, bot - top, top);
+          }
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+        if (i >= nc) break;
+        quad_store_owned(t.out + (size_t)(c0 + i) * rc.plane, t, {q[i]}, fused, own);
+      }
+    }
+  });
+}
+
+// ================================================================================================================
+// k_cube_grad — THE BACKWARD OF k_cube (srz_frameset_texture_cube_grad): per sampled pixel and channel, four adds w[corner] * gout
+// into the cube's gradient (gtex) at the RESOLVED texels — a tile that straddles a cube edge adds into both faces —, and the
+// gradient with respect to the direction (gdir: k_tex_grad's au, av chains, then the chain through s = sc / ma, t = tc / ma; from
+// registers, no atomics).  k_tex_grad's structure on the passes' helpers (pass_walk<true>: every thread of the workgroup reaches
+// every barrier, one outside the frame samples nothing): the tile's open-addressed table of distinct texels in LDS (TexTable,
+// keyed on the cube-wide texel index + 1), the slots found once in front of the channel loop, LDS float adds per chunk, the dense
+// flush with global_atomic_add_f32, a corner without a slot adding straight to memory.
+// (cg_slot and cg_add are COPIES of tg_slot and tg_add, and step 4 of k_tex_grad's flush: shared helpers have moved k_tex_grad's
+// registers before (k_tex_mip_grad's note); a fix goes into all of them)
+// ================================================================================================================
+__device__ __forceinline__ uint32_t cg_slot(TexTable &tb, uint32_t idx) {
+  const uint32_t key = idx + 1u; // (idx < 6 * SRZ_TEX_MAX_SIZE^2 = 6 * 2^28)
+  uint32_t h = (key * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
+  for (uint32_t p = 0; p < TG_PROBES; ++p) {
+    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
+    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
+    if (old == 0u || old == key) return h;
+    h = (h + 1u) & (TG_SLOTS - 1u);
+  }
+  return TG_NONE;
+}
+__device__ __forceinline__ void cg_add(TexTable &tb, uint32_t slot, float *gtex, uint32_t idx, uint32_t C, uint32_t ch, uint32_t i, float v) {
+  if (slot != TG_NONE) lds_add(&tb.val[slot * ATTR_CHUNK + i], v);
+  else global_add(gtex + (size_t)idx * C + ch, v);
+}
+__global__ __launch_bounds__(256) void k_cube_grad(CubeArgs a) {
+  __shared__ TexTable tb;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t C = a.n_ch;
+  const bool want_tex = a.gtex != nullptr, want_dir = a.out != nullptr;
+  if (want_tex) {
+    for (uint32_t i = tid; i < TG_SLOTS; i += 256) tb.key[i] = 0u;
+    for (uint32_t i = tid; i < TG_SLOTS * ATTR_CHUNK; i += 256) tb.val[i] = 0.0f;
+    if (tid == 0) tb.n_used = 0u;
+    __syncthreads();
+  }
+  pass_walk<true>(a, [&](const PassTile &t) { // (a thread outside the frame owns nothing, and still meets the barriers)
+    const TileRect &rc = t.rc;
+    const bool fused = t.fused(a.flags_or);
+    const float *gg = a.gout + (size_t)t.f * a.gout_stride + t.poff;
+    // ---- 1. owners, directions, the taps
+    CubeTap tap[4] = {};
+    uint32_t own, smp;
+    cube_quad(a, t, tap, own, smp);
+    const SRZ_CAS float *tex = as_const(a.tex) + (size_t)t.f * a.tex_frame_stride;
+    float *gtex = a.gtex + (size_t)t.f * a.tex_frame_stride;
+    // ---- 2. the slots of the sampled pixels' corners (two corners on one texel: one slot, both add)
+    uint32_t slot[4][4] = {};
+    if (want_tex) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (smp & (1u << k))
+          slot[k][0] = cg_slot(tb, tap[k].i00), slot[k][1] = cg_slot(tb, tap[k].i01), slot[k][2] = cg_slot(tb, tap[k].i10),
+          slot[k][3] = cg_slot(tb, tap[k].i11);
+    }
+    float au[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f};
+    uint32_t n_used = 0u;
+    // ---- 3. the channels, ATTR_CHUNK at a time
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 g[ATTR_CHUNK]; // gout of the chunk's channels; words of pixels that are not sampled are loaded with their quad at most, never used
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (smp != 0u) {
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+          if (i >= nc) break;
+          const float *p = gg + (size_t)(c0 + i) * rc.plane;
+          if (t.whole) {
+            g[i] = *reinterpret_cast<const float4 *>(p);
+          } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (smp & (1u << k)) quad_at(g[i], k) = p[k];
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(smp & (1u << k))) continue;
+        if (want_dir) {
+          const SRZ_CAS float *p00 = tex + (size_t)tap[k].i00 * C + c0, *p01 = tex + (size_t)tap[k].i01 * C + c0;
+          const SRZ_CAS float *p10 = tex + (size_t)tap[k].i10 * C + c0, *p11 = tex + (size_t)tap[k].i11 * C + c0;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float gi = quad_at(g[i], k), t00 = p00[i], t01 = p01[i], t10 = p10[i], t11 = p11[i];
+              const float top = fmaf_(tap[k].tx, t01 - t00, t00), bot = fmaf_(tap[k].tx, t11 - t10, t10);
+              au[k] = fmaf_(gi, fmaf_(tap[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au[k]);
+              av[k] = fmaf_(gi, bot - top, av[k]);
+            }
+        }
+        if (want_tex) {
+          const float tx_ = tap[k].tx, ty_ = tap[k].ty;
+          const float w00 = (1.0f - tx_) * (1.0f - ty_), w01 = tx_ * (1.0f - ty_), w10 = (1.0f - tx_) * ty_, w11 = tx_ * ty_;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float gi = quad_at(g[i], k);
+              cg_add(tb, slot[k][0], gtex, tap[k].i00, C, c0 + i, i, w00 * gi);
+              cg_add(tb, slot[k][1], gtex, tap[k].i01, C, c0 + i, i, w01 * gi);
+              cg_add(tb, slot[k][2], gtex, tap[k].i10, C, c0 + i, i, w10 * gi);
+              cg_add(tb, slot[k][3], gtex, tap[k].i11, C, c0 + i, i, w11 * gi);
+            }
+        }
+      }
+      if (want_tex) {
+        // ---- 4. the table's values of this chunk into memory: lanes in channel order within a texel
+        __syncthreads();
+        n_used = tb.n_used;
+        for (uint32_t i = tid; i < n_used * ATTR_CHUNK; i += 256) {
+          const uint32_t s = tb.used[i / ATTR_CHUNK], e = i % ATTR_CHUNK;
+          const float v = tb.val[s * ATTR_CHUNK + e];
+          tb.val[s * ATTR_CHUNK + e] = 0.0f;
+          if (e < nc) global_add(gtex + (size_t)(tb.key[s] - 1u) * C + c0 + e, v);
+        }
+        __syncthreads();
+      }
+    }
+    if (want_tex) { // the tile's keys go; every thread has read n_used before the chunk's last barrier
+      for (uint32_t i = tid; i < n_used; i += 256) tb.key[tb.used[i]] = 0u;
+      if (tid == 0) tb.n_used = 0u;
+      __syncthreads();
+    }
+    // ---- 5. the direction's gradient: whole quads (fused clear, or four owners), else the owned pixels only; an owner that is not
+    // sampled: (0, 0, 0)
+    if (want_dir && t.inside && (own != 0u || fused)) {
+      const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 gd[3] = {zero4, zero4, zero4};
+      const float half_n = 0.5f * (float)a.n;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (smp & (1u << k)) {
+          const float gs = au[k] * half_n, gt = av[k] * half_n, inv = tap[k].inv;
+          const float g_sc = gs * inv, g_tc = gt * inv, g_ma = -(fmaf_(gs, tap[k].s, gt * tap[k].t) * inv);
+          const uint32_t m = tap[k].major & 3u;
+          const bool pos = (tap[k].major & 4u) != 0u;
+          const float g_m = pos ? g_ma : -g_ma;
+          // su, sv of the face, undone: +X (-z, -y)  -X (z, -y)  +Y (x, z)  -Y (x, -z)  +Z (x, -y)  -Z (-x, -y)
+          quad_at(gd[0], k) = m == 0u ? g_m : m == 1u ? g_sc : (pos ? g_sc : -g_sc);
+          quad_at(gd[1], k) = m == 1u ? g_m : -g_tc;
+          quad_at(gd[2], k) = m == 0u ? (pos ? -g_sc : g_sc) : m == 1u ? (pos ? g_tc : -g_tc) : g_m;
+        }
+      quad_store_owned(t.out, t, gd, fused, own);
+    }
+  });
+}
+
+// ================================================================================================================
 // k_mip_build / k_mip_fold — THE MIP PYRAMID OF A CALLER TEXTURE (srz_texture_mip_build, srz_texture_mip_fold; include/srz.h states
 // the geometry and the arithmetic).  The build is one launch per level, each from the level above it: a workgroup walks rows of the
 // level it writes, its threads the row's (texel, channel) elements — consecutive lanes, consecutive floats.  The fold is the build's
@@ -6250,6 +6522,8 @@ void launch_antialias(const AntialiasArgs &a, hipStream_t s) { launch_pass<k_ant
 void launch_antialias_grad(const AntialiasArgs &a, hipStream_t s) { launch_pass<k_antialias_grad>(a, s); }
 void launch_tex(const TexArgs &a, hipStream_t s) { launch_pass<k_tex>(a, s); }
 void launch_tex_grad(const TexArgs &a, hipStream_t s) { launch_pass<k_tex_grad>(a, s); }
+void launch_cube(const CubeArgs &a, hipStream_t s) { launch_pass<k_cube>(a, s); }
+void launch_cube_grad(const CubeArgs &a, hipStream_t s) { launch_pass<k_cube_grad>(a, s); }
 void launch_interp_deriv(const InterpDerivArgs &a, hipStream_t s) { launch_pass<k_interp_deriv>(a, s); }
 void launch_tex_mip(const TexMipArgs &a, hipStream_t s) { launch_pass<k_tex_mip>(a, s); }
 void launch_tex_mip_grad(const TexMipArgs &a, hipStream_t s) { launch_pass<k_tex_mip_grad>(a, s); }

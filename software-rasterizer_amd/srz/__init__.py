@@ -31,6 +31,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_texture", "srz_frameset_texture_grad",
            "srz_texture_mip_levels", "srz_texture_mip_bytes", "srz_texture_mip_build", "srz_texture_mip_fold",
            "srz_frameset_interpolate_deriv", "srz_frameset_texture_mip", "srz_frameset_texture_mip_grad",
+           "srz_frameset_texture_cube", "srz_frameset_texture_cube_grad",
            "srz_target_create", "srz_target_destroy", "srz_target_clear", "srz_target_draw", "srz_target_read", "srz_target_read_bgr8"]
 
 
@@ -109,6 +110,8 @@ def lib():
         L.srz_frameset_interpolate_deriv.argtypes = abi.INTERPOLATE_DERIV_ARGTYPES
         L.srz_frameset_texture_mip.argtypes = abi.TEXTURE_MIP_ARGTYPES
         L.srz_frameset_texture_mip_grad.argtypes = abi.TEXTURE_MIP_GRAD_ARGTYPES
+        L.srz_frameset_texture_cube.argtypes = abi.TEXTURE_CUBE_ARGTYPES
+        L.srz_frameset_texture_cube_grad.argtypes = abi.TEXTURE_CUBE_GRAD_ARGTYPES
         L.srz_frameset_update_shading.argtypes = [vp, vp, C.POINTER(abi.SrzFrame), C.c_int]
         L.srz_sceneset_update.argtypes = [vp, vp, C.POINTER(abi.SrzSceneFrame), C.c_int]
         L.srz_frameset_resolve8.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
@@ -388,6 +391,26 @@ class FrameSet:
             self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_uv_ptr), C.c_void_p(d_uvd_ptr or None), C.c_void_p(d_gout_ptr),
             C.c_void_p(d_tex_ptr or None), C.c_void_p(d_mip_ptr or None), tex_w, tex_h, n_ch, tex_frames, mode, n_levels,
             C.c_void_p(d_gtex_ptr or None), C.c_void_p(d_gmip_ptr or None), C.c_void_p(d_guv_ptr or None), flags, _stream(stream)))
+
+    def texture_cube(self, d_vis_ptr, d_dir_ptr, d_tex_ptr, n, n_ch, tex_frames, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """the caller's float32 cube map [tex_frames][6][n][n][n_ch] (faces +X -X +Y -Y +Z -Z; tex_frames: 1 or the frame count) looked
+        up bilinearly and seamlessly by the direction planes d_dir [frame][3][local_rows][width] (interpolate's of a three-channel
+        attribute; any length) under a visibility buffer of this set → d_out [frame][n_ch][local_rows][width] (include/srz.h states
+        the rule).  Pixels nobody owns are zeros with FUSED_CLEAR, else left untouched; an owner whose direction is not finite or
+        zero gets zeros.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_texture_cube(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_dir_ptr), C.c_void_p(d_tex_ptr),
+                                                        n, n_ch, tex_frames, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def texture_cube_grad(self, d_vis_ptr, d_dir_ptr, d_gout_ptr, d_tex_ptr, n, n_ch, tex_frames, d_gtex_ptr, d_gdir_ptr, flags=abi.FUSED_CLEAR,
+                          stream=None):
+        """the backward of texture_cube: d_gout [frame][n_ch][local_rows][width] → ADDED into d_gtex (the cube's shape; the order of
+        the adds is unspecified: not bit-reproducible) and / or written to d_gdir [frame][3][local_rows][width] (the gradient with
+        respect to the direction, deterministic; needs d_tex_ptr; the layout interpolate_grad takes as d_gout at n_ch = 3).  Either
+        output pointer may be None / 0, not both.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_texture_cube_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_dir_ptr),
+                                                             C.c_void_p(d_gout_ptr), C.c_void_p(d_tex_ptr or None), n, n_ch, tex_frames,
+                                                             C.c_void_p(d_gtex_ptr or None), C.c_void_p(d_gdir_ptr or None), flags,
+                                                             _stream(stream)))
 
     def update_shading(self, frames):
         """new eye, ka, ks, p, kh, kn, lights, flags and batch shaders / textures for a set made from abi.Frame's, triangles untouched

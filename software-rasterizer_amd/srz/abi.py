@@ -37,6 +37,9 @@ MIP_FOLD_ARGTYPES = [_vp, _vp, C.c_size_t, _u32, _u32, _u32, _u32, _u32, _vp, _v
 INTERPOLATE_DERIV_ARGTYPES = [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
 TEXTURE_MIP_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, C.c_size_t, _u32, _vp]
 TEXTURE_MIP_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp]
+# the prototypes of srz_frameset_texture_cube / _texture_cube_grad (argtypes; both return int), set by srz.lib()
+TEXTURE_CUBE_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
+TEXTURE_CUBE_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp]
 
 # numpy view of srz_tri (96 B): pos[3][3], nrm[3][3], uv[3][2]
 TRI_DTYPE = np.dtype([("pos", "<f4", (3, 3)), ("nrm", "<f4", (3, 3)), ("uv", "<f4", (3, 2))])

@@ -474,6 +474,89 @@ def texture(fs, vis, tex, uv, wrap=False, stream=None):
     return _Texture.apply(tex, uv, fs, vis, wrap, stream)
 
 
+def cube_dirs(n, device=None):
+    """the unit direction of every texel centre of an n x n cube map → [6, n, n, 3] float32 (face, row, column; faces +X -X +Y -Y +Z
+    -Z, a face's point n + s su + t sv with s = (2 x + 1) / n - 1, t = (2 y + 1) / n - 1: include/srz.h has the table): what a caller
+    evaluates an environment on to fill a cube for texture_cube, or to read one back."""
+    c = (2.0 * torch.arange(n, dtype=torch.float64, device=device) + 1.0) / n - 1.0
+    t, s = torch.meshgrid(c, c, indexing="ij")  # rows are t, columns s
+    one = torch.ones_like(s)
+    faces = ((one, -t, -s), (-one, -t, s), (s, one, t), (s, -one, -t), (s, -t, one), (-s, -t, -one))  # n + s su + t sv, per face
+    p = torch.stack([torch.stack(f, -1) for f in faces])
+    return (p / p.norm(dim=-1, keepdim=True)).to(torch.float32)
+
+
+def _cube_dims(fs, cube):
+    if cube.dtype != torch.float32 or not cube.is_cuda or cube.dim() not in (4, 5) or cube.shape[-4] != 6 or cube.shape[-3] != cube.shape[-2]:
+        raise ValueError(f"texture_cube: cube must be a CUDA float32 tensor [6, N, N, C] or [n_frames, 6, N, N, C], got {tuple(cube.shape)} {cube.dtype}")
+    tex_frames = cube.shape[0] if cube.dim() == 5 else 1
+    if cube.dim() == 5 and tex_frames != fs.n_frames:
+        raise ValueError(f"texture_cube: cube has {tex_frames} frames, the set {fs.n_frames}")
+    n, n_ch = cube.shape[-2], cube.shape[-1]
+    if not (1 <= n <= abi.TEX_MAX_SIZE and 1 <= n_ch <= abi.ATTR_MAX_CH):
+        raise ValueError(f"texture_cube: faces of {n} x {n} texels, {n_ch} channels; 1 .. {abi.TEX_MAX_SIZE} and 1 .. {abi.ATTR_MAX_CH} are supported")
+    return tex_frames, n, n_ch
+
+
+def _dirs_arg(fs, dirs):
+    if dirs.dtype != torch.float32 or not dirs.is_cuda or tuple(dirs.shape) != tuple(fs.interpolate_shape(3)):
+        raise ValueError(f"texture_cube: dirs must be a CUDA float32 tensor {fs.interpolate_shape(3)}, got {tuple(dirs.shape)} {dirs.dtype}")
+    return dirs.contiguous()
+
+
+def texture_cube_grad(fs, vis, cube, dirs, gout, want_gtex=True, want_gdir=True, stream=None):
+    """the backward of texture_cube(fs, vis, cube, dirs) by one FrameSet.texture_cube_grad call: gout [n_frames, C, rows, W] → (gtex,
+    gdir), each None when not wanted (not both): gtex has cube's shape — a sum of float atomics into zeros, not bit-reproducible
+    between runs; gdir [n_frames, 3, rows, W] is deterministic, zeros where nobody owns the pixel or its direction is not sampled, and
+    is what interpolate's backward takes for a three-channel attribute.  stream: a raw stream handle, None = torch's current stream."""
+    if not want_gtex and not want_gdir:
+        raise ValueError("texture_cube_grad: neither gtex nor gdir is asked for")
+    cube, dirs, gout = cube.contiguous(), _dirs_arg(fs, dirs), gout.contiguous()
+    tex_frames, n, n_ch = _cube_dims(fs, cube)
+    if tuple(gout.shape) != tuple(fs.interpolate_shape(n_ch)) or gout.dtype != torch.float32:
+        raise ValueError(f"texture_cube_grad: gout must be float32 {fs.interpolate_shape(n_ch)}, got {tuple(gout.shape)} {gout.dtype}")
+    gtex = torch.zeros_like(cube) if want_gtex else None
+    gdir = torch.empty_like(dirs) if want_gdir else None
+    fs.texture_cube_grad(vis.data_ptr(), dirs.data_ptr(), gout.data_ptr(), cube.data_ptr(), n, n_ch, tex_frames,
+                         gtex.data_ptr() if want_gtex else None, gdir.data_ptr() if want_gdir else None, abi.FUSED_CLEAR, _stream_ptr(stream))
+    return gtex, gdir
+
+
+class _TextureCube(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cube, dirs, fs, vis, stream):
+        cube, dirs = cube.contiguous(), _dirs_arg(fs, dirs)
+        tex_frames, n, n_ch = _cube_dims(fs, cube)
+        out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=cube.device)
+        fs.texture_cube(vis.data_ptr(), dirs.data_ptr(), cube.data_ptr(), n, n_ch, tex_frames, out.data_ptr(), fs.interpolate_bytes(n_ch),
+                        abi.FUSED_CLEAR, _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.stream = fs, vis, stream
+        ctx.save_for_backward(cube, dirs)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        cube, dirs = ctx.saved_tensors
+        need_tex, need_dir = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gtex = gdir = None
+        if need_tex or need_dir:  # one call, asking only for what is needed
+            gtex, gdir = texture_cube_grad(ctx.fs, ctx.vis, cube, dirs, gout, need_tex, need_dir, ctx.stream)
+        return gtex, gdir, None, None, None
+
+
+def texture_cube(fs, vis, cube, dirs, stream=None):
+    """a float cube map of the caller's own looked up by direction under a visibility buffer `vis` of FrameSet `fs`: cube is a CUDA
+    float32 tensor [6, N, N, C] (one cube for every frame) or [n_frames, 6, N, N, C], faces +X -X +Y -Y +Z -Z, channels last, C <=
+    abi.ATTR_MAX_CH, N <= abi.TEX_MAX_SIZE; dirs is [n_frames, 3, rows, W] — interpolate(fs, vis, attr) of a [T, 3, 3] attribute such
+    as corner_attr's normals, of any length → [n_frames, C, rows, W] float32, bilinear and seamless across the cube's edges, zeros
+    where nobody owns the pixel or its direction is not finite or zero (FrameSet.texture_cube; include/srz.h states the rule).
+    Differentiable with respect to cube (float atomics into a zeroed tensor: cube.grad is not bit-reproducible between runs) and to
+    dirs (deterministic), so texture_cube(fs, vis, cube, interpolate(fs, vis, corner_attr(fs, {slot: mesh_normals(ctx, slot,
+    verts)}))) backpropagates to the cube and to the vertices.  Backward is one texture_cube_grad call that asks only for the
+    outputs some input needs.  stream: a raw stream handle, None = torch's current stream."""
+    return _TextureCube.apply(cube, dirs, fs, vis, stream)
+
+
 def interpolate_deriv(fs, vis, attr, stream=None):
     """the screen-space derivatives of interpolate(fs, vis, attr): attr as interpolate takes it with C <= abi.ATTR_MAX_CH // 2 →
     [n_frames, 2 C, rows, W] float32, plane 2 ch the change of channel ch per one-pixel step in x, plane 2 ch + 1 in y — constants of
