@@ -442,7 +442,9 @@ int srz_frameset_gbuffer(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, void
  *           NaN or a huge coordinate is outside and never becomes an index —: tid and tz are the raw words of planes 1 and 0 of frame
  *           g in d_vis at (tx, ty).  Outside: tid = 0, tz = +inf.  (tid == the pixel's own id, or tz close to z', means the point is
  *           visible in g; anything else that it is occluded there or has left the image.)
- * The interpolation is LINEAR IN SCREEN SPACE, as everywhere in the reference, which has no perspective-correct interpolation.
+ * The interpolation is LINEAR IN SCREEN SPACE, as everywhere in the reference, which has no perspective-correct interpolation
+ * (srz_frameset_perspective, below, adds it for the attribute-side passes; this pass interpolates screen positions and keeps the
+ * ORIGINAL buffer).
  * Always the exact arithmetic: SRZ_OPT_APPROX_SHADE has no effect.
  * Nobody: a pixel nobody owns (id 0 or out of range), and EVERY pixel of a frame whose g lies outside [0, n_frames).  With
  * SRZ_FUSED_CLEAR (frame flags | flags) every requested word of a nobody pixel is 0; without it those words are left untouched.
@@ -809,6 +811,75 @@ int srz_frameset_texture_mip(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, 
 int srz_frameset_texture_mip_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const void *d_uvd, const void *d_gout,
                                   const float *d_tex, const float *d_mip, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames,
                                   uint32_t mode, uint32_t n_levels, float *d_gtex, float *d_gmip, void *d_guv, uint32_t flags, void *stream);
+/* PERSPECTIVE-CORRECT BARYCENTRICS of a visibility buffer, their gradients, and the attribute derivatives under them.  A visibility
+ * buffer's alpha, beta are LINEAR IN SCREEN SPACE, the reference's rule and the default of every pass above.  Under a vertex stage
+ * that divides by a real w they name the wrong point of the triangle.  With q_k = 1 / w_k the reciprocal clip w of the owner's
+ * corners (the divisor the vertex stage used), the weights of the point that projects onto the pixel are
+ *   alpha' = alpha q0 / s,  beta' = beta q1 / s,  s = alpha q0 + beta q1 + gamma q2.
+ * srz_frameset_perspective writes them into a buffer of the visibility buffer's own four-plane layout, z and the ids copied (the
+ * post-divide depth is affine in screen space), so the ATTRIBUTE-SIDE passes run on that buffer unchanged and are then perspective
+ * correct: srz_frameset_interpolate, _interpolate_grad (its d_gattr, and its d_gbary, which is then d/dalpha', d/dbeta'), _gbuffer,
+ * _shade_visibility, and everything that takes their planes (_texture, _texture_mip, _texture_cube).  The GEOMETRIC passes keep
+ * taking the ORIGINAL buffer, whose alpha, beta are the screen-space ones their rules are stated in: srz_frameset_position_grad,
+ * _motion, _antialias / _antialias_grad, _peel_visibility, _interpolate_deriv.  srz_frameset_perspective_grad is the backward of the
+ * rewrite: from the gradient with respect to alpha', beta' (the planes srz_frameset_interpolate_grad writes on the perspective
+ * buffer) to the gradient with respect to the screen-linear alpha, beta — exactly the planes srz_frameset_position_grad takes, with
+ * the ORIGINAL buffer — and to q.  srz_frameset_interpolate_deriv_persp gives the per-pixel screen derivatives of an attribute under
+ * this interpolation, for srz_frameset_texture_mip, in srz_frameset_interpolate_deriv's planes.
+ * d_vis: a visibility buffer of THIS set on this ctx's shard (the original one, in all three calls).  d_q: [q_frames][q_tris][3]
+ * float32, 4-byte aligned: srz_frameset_interpolate's attribute layout at one channel (srz_sceneset_corner_attr at n_ch = 1 produces
+ * it); q_frames is 1 or the set's frame count, q_tris at least every frame's triangle count.  d_out of srz_frameset_perspective: a
+ * visibility buffer, srz_frameset_out_bytes() bytes, 16-byte aligned.  d_gbary_p, d_gbary: [frame][2][local_rows][width] float32,
+ * srz_frameset_interpolate_bytes(2) bytes, 16-byte aligned.  d_gq: d_q's shape, ADDED into.  d_attr, n_ch, attr_frames, attr_tris and
+ * d_out of srz_frameset_interpolate_deriv_persp: as srz_frameset_interpolate_deriv has them, 1 <= n_ch <= SRZ_ATTR_MAX_CH / 2.  Band
+ * sharding, local_rows, stream semantics, asynchrony, owner and nobody ((id & 0x7fffffff) - 1 < the frame's triangle count means an
+ * owner, bit 31 of id is the class, gamma = 1 - (alpha + beta) for V and (1 - alpha) - beta for S) as srz_frameset_interpolate /
+ * _interpolate_grad.  The first two calls read no position, record or texture and run no vertex stage; the third reads the set's
+ * positions exactly as srz_frameset_interpolate_deriv does (a sceneset runs its vertex stage first).
+ * THE RULE, in float32, nothing fused but the written fmaf, IEEE divisions.  Per owned pixel, q0, q1, q2 its owner's three words of q
+ * (frame 0's when q_frames == 1):
+ *   n0 = alpha * q0;  n1 = beta * q1;  n2 = gamma * q2;  s = (n0 + n1) + n2
+ *   valid = each of q0, q1, q2 and s is a positive NORMAL float: x >= 2^-126 && x < INFINITY (float compares: a NaN fails).  (Zero,
+ *           negative, subnormal, infinite and NaN values all fail, so the rule does not depend on a device's denormal mode: a
+ *           corner at or behind the camera plane, or one whose w overflowed, makes its pixels fall back.)
+ * FORWARD, srz_frameset_perspective, bit for bit:
+ *   valid: alpha' = n0 / s;  beta' = n1 / s;  else alpha' = alpha, beta' = beta (the words copied).
+ *   Planes 0 and 1 (z, id): the words of d_vis copied, for EVERY pixel of the shard; a pixel nobody owns (id 0, or a stranger id: an
+ *   index outside the frame's triangles) has all four words copied.  Every word of d_out is written whatever `flags` says, so the
+ *   result is always a complete buffer.
+ * BACKWARD, srz_frameset_perspective_grad: at least one of d_gbary and d_gq is non-null.  ga, gb = d_gbary_p's two words (gamma''s
+ * share already folded in, as srz_frameset_interpolate_grad writes them); alpha', beta', s recomputed as above.
+ *   valid:  t = fmaf(ga, alpha', gb * beta');  r = 1.0f / s;  g0 = (ga - t) * r;  g1 = (gb - t) * r;  g2 = (-t) * r
+ *           galpha = fmaf(g0, q0, -(g2 * q2));  gbeta = fmaf(g1, q1, -(g2 * q2))          -> d_gbary, deterministic, bit for bit
+ *           gq[fq][tri][0] += g0 * alpha;  [1] += g1 * beta;  [2] += g2 * gamma            -> d_gq (fq = 0 when q_frames == 1)
+ *   else:   galpha = ga, gbeta = gb, and no add.
+ *   Nobody pixels of d_gbary: 0 with SRZ_FUSED_CLEAR (frame flags | flags), untouched without, as srz_frameset_interpolate_grad.
+ *   d_gq has d_gattr's contract: THE ORDER OF THE ADDS IS UNSPECIFIED, each add rounds, so it is NOT BIT-REPRODUCIBLE between
+ *   launches; with n contributing pixels an element lies within n 2^-24 / (1 - n 2^-24) * sum |term| of the exact sum of the float32
+ *   terms, and an element with one contributing pixel is exact.  The adds are hardware float atomics: d_gq must be ordinary
+ *   (coarse-grained) device memory.  On a sharded ctx each rank produces the partial sums of its own bands.  Words of d_gbary_p at
+ *   nobody pixels never reach a result.
+ * DERIVATIVES, srz_frameset_interpolate_deriv_persp, bit for bit: area, r, gax, gay, gbx, gby as srz_frameset_interpolate_deriv; per
+ * channel with corner values a, b, c and u = the channel interpolated under alpha', beta' and gamma' (gamma' from alpha', beta' by the
+ * owner's class) by srz_frameset_interpolate's expression for that class:
+ *   e0 = (a - u) * q0;  e1 = (b - u) * q1;  e2 = (c - u) * q2
+ *   d/dx = fmaf(e0 - e2, gax, (e1 - e2) * gbx) / s;   d/dy = fmaf(e0 - e2, gay, (e1 - e2) * gby) / s
+ *   not valid: srz_frameset_interpolate_deriv's own words (the screen-linear constants).  Nobody pixels as there.  There is no
+ *   backward: the planes only select a level.
+ * Non-finite alpha, beta propagate as IEEE has them; no input value makes a pass read or write outside its buffers.  Always the exact
+ * arithmetic: SRZ_OPT_APPROX_SHADE has no effect.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set, d_vis, d_q, d_out, d_gbary_p or d_attr; both of
+ * d_gbary and d_gq null; q_frames not 1 or the frame count; q_tris below some frame's triangle count; what
+ * srz_frameset_interpolate_deriv refuses of n_ch, attr_frames and attr_tris; a misaligned pointer; a short out_bytes; any bit of
+ * `flags` but SRZ_FUSED_CLEAR; an output that overlaps an input (d_vis, d_q, d_gbary_p, d_attr: d_out == d_vis is an overlap) or the
+ * other output. */
+int srz_frameset_perspective(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_q, uint32_t q_frames, uint32_t q_tris,
+                             void *d_out, size_t out_bytes, uint32_t flags, void *stream);
+int srz_frameset_perspective_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_q, uint32_t q_frames, uint32_t q_tris,
+                                  const void *d_gbary_p, void *d_gbary, float *d_gq, uint32_t flags, void *stream);
+int srz_frameset_interpolate_deriv_persp(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_q, uint32_t q_frames,
+                                         uint32_t q_tris, const float *d_attr, uint32_t n_ch, uint32_t attr_frames, uint32_t attr_tris,
+                                         void *d_out, size_t out_bytes, uint32_t flags, void *stream);
 /* New SHADING DATA for a set made by srz_frameset_create, its triangles untouched (batches[b].tris is ignored and may be NULL): each
  * frame's eye, ka, ks, p, kh, kn, lights and flags, each batch's shader and tex_id.  The structure must be the set's — frame count, size,
  * light counts, batch counts, n_tris per batch — else SRZ_E_INVALID and the set is unchanged; a sceneset is SRZ_E_INVALID (its shading

@@ -2118,6 +2118,101 @@ int srz_frameset_interpolate_deriv(srz_ctx *ctx, srz_frameset *fs, const void *d
   return end_pass(ctx);
 }
 
+// what srz_frameset_perspective, _perspective_grad and _interpolate_deriv_persp check of q alike; its bytes in *q_bytes
+static int check_persp_q(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, uint32_t q_frames, uint32_t q_tris, size_t *q_bytes) {
+  if (q_frames != 1u && q_frames != (uint32_t)fs->n_frames) return fail(ctx, SRZ_E_INVALID, fn + ": q_frames must be 1 or the set's frame count");
+  if (int rc = check_tri_count(ctx, fs, fn, "q_tris", q_tris)) return rc;
+  *q_bytes = (size_t)q_frames * q_tris * 3u * sizeof(float);
+  return SRZ_OK;
+}
+static PerspArgs persp_args(const srz_frameset *fs, const void *d_vis, const float *d_q, uint32_t q_frames, uint32_t q_tris, uint32_t out_planes,
+                            void *d_out, uint32_t flags) {
+  PerspArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  a.q = d_q;
+  a.vis_stride = 4ull * plane, a.frame_stride = out_planes * plane;
+  a.q_frame_stride = q_frames == 1u ? 0ull : (uint64_t)q_tris * 3u;
+  a.flags_or = flags;
+  return a;
+}
+
+int srz_frameset_perspective(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_q, uint32_t q_frames, uint32_t q_tris,
+                             void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_perspective");
+  if (!fs || !d_vis || !d_q || !d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / q / output");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  size_t q_bytes = 0;
+  if (int rc = check_persp_q(ctx, fs, fn, q_frames, q_tris, &q_bytes)) return rc;
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < vis_bytes) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
+  if (!aligned<16>({d_vis, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
+  if (!aligned<4>({d_q})) return fail(ctx, SRZ_E_INVALID, fn + ": q must be 4-byte aligned");
+  if (ranges_overlap({d_out, vis_bytes}, {d_vis, vis_bytes}) || ranges_overlap({d_out, vis_bytes}, {d_q, q_bytes}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the visibility buffer or q");
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (the caller's q, not the set's triangles: no vertex stage)
+  launch_persp(persp_args(fs, d_vis, d_q, q_frames, q_tris, 4u, d_out, flags), s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_perspective_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_q, uint32_t q_frames, uint32_t q_tris,
+                                  const void *d_gbary_p, void *d_gbary, float *d_gq, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_perspective_grad");
+  if (!fs || !d_vis || !d_q || !d_gbary_p) return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / q / gradient planes");
+  if (!d_gbary && !d_gq) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gbary nor d_gq is asked for");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  size_t q_bytes = 0;
+  if (int rc = check_persp_q(ctx, fs, fn, q_frames, q_tris, &q_bytes)) return rc;
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs), two_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u);
+  if (!aligned<16>({d_vis, d_gbary_p, d_gbary})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers must be 16-byte aligned");
+  if (!aligned<4>({d_q, d_gq})) return fail(ctx, SRZ_E_INVALID, fn + ": q and its gradient must be 4-byte aligned");
+  if (int rc = check_grad_overlap(ctx, fn, {{d_gq, q_bytes}, {d_gbary, two_bytes}}, {{d_vis, vis_bytes}, {d_gbary_p, two_bytes}, {d_q, q_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_perspective)
+  PerspArgs a = persp_args(fs, d_vis, d_q, q_frames, q_tris, 2u, d_gbary, flags);
+  a.gbary_p = (const float *)d_gbary_p, a.gq = d_gq;
+  launch_persp_grad(a, s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_interpolate_deriv_persp(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_q, uint32_t q_frames,
+                                         uint32_t q_tris, const float *d_attr, uint32_t n_ch, uint32_t attr_frames, uint32_t attr_tris,
+                                         void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_interpolate_deriv_persp");
+  if (!fs || !d_vis || !d_q || !d_attr || !d_out)
+    return fail(ctx, SRZ_E_INVALID, fn + ": null frameset / visibility buffer / q / attributes / output");
+  if (n_ch > SRZ_ATTR_MAX_CH / 2u) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_ATTR_MAX_CH / 2");
+  size_t attr_bytes = 0, q_bytes = 0;
+  if (int rc = check_interp(ctx, fs, fn, n_ch, attr_frames, attr_tris, flags, &attr_bytes)) return rc;
+  if (int rc = check_persp_q(ctx, fs, fn, q_frames, q_tris, &q_bytes)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, 2u * n_ch), vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": output buffer too small");
+  if (!aligned<16>({d_vis, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": buffers must be 16-byte aligned");
+  if (!aligned<4>({d_attr, d_q})) return fail(ctx, SRZ_E_INVALID, fn + ": the attributes and q must be 4-byte aligned");
+  if (ranges_overlap({d_out, need}, {d_vis, vis_bytes}) || ranges_overlap({d_out, need}, {d_attr, attr_bytes}) ||
+      ranges_overlap({d_out, need}, {d_q, q_bytes}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the visibility buffer, the attributes or q");
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, PASS_VERTEX, &s)) return rc; // (the set's positions, as srz_frameset_interpolate_deriv)
+  PerspDerivArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  fill_positions(a, fs);
+  a.attr = d_attr, a.q = d_q;
+  a.vis_stride = 4ull * plane, a.frame_stride = 2ull * n_ch * plane;
+  a.attr_frame_stride = attr_frames == 1u ? 0ull : (uint64_t)attr_tris * 3u * n_ch;
+  a.q_frame_stride = q_frames == 1u ? 0ull : (uint64_t)q_tris * 3u;
+  a.n_ch = n_ch;
+  a.flags_or = flags;
+  launch_interp_deriv_persp(a, s);
+  return end_pass(ctx);
+}
+
 int srz_frameset_texture_mip(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const void *d_uvd, const float *d_tex,
                              uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t mode, const float *d_mip,
                              uint32_t n_levels, void *d_out, size_t out_bytes, uint32_t flags, void *stream) {

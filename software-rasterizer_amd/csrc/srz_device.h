@@ -492,6 +492,45 @@ struct InterpDerivArgs {
   uint32_t flags_or;
 };
 void launch_interp_deriv(const InterpDerivArgs &a, hipStream_t s);
+// srz_frameset_perspective / _perspective_grad: a visibility buffer's alpha, beta rewritten into the perspective-correct alpha',
+// beta' from the per-corner reciprocal clip w `q` [q frame][triangle][corner] (k_persp), and the backward of that rewrite, to the
+// screen-linear alpha, beta and to q (k_persp_grad).  vis and the walk as InterpArgs has them; `out` is the forward's four-plane
+// buffer [frame][4][local_rows][width] or the backward's gbary [frame][2][local_rows][width] (may be null there); `out` /
+// `frame_stride` / `local_rows` / the shard are what tile_rect reads.  The host has checked q_tris >= every frame's triangle count
+struct PerspArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *q;
+  float *out;
+  const float *gbary_p;    // backward: [frame][2][local_rows][width], the gradient with respect to alpha', beta'
+  float *gq;               // backward: q's shape, added into (may be null)
+  uint64_t vis_stride;     // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride;   // floats per frame in out (and in gbary_p: the backward's out has its shape)
+  uint64_t q_frame_stride; // floats per frame in q / gq = q_tris * 3; 0: one array for every frame
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_persp(const PerspArgs &a, hipStream_t s);
+void launch_persp_grad(const PerspArgs &a, hipStream_t s);
+// srz_frameset_interpolate_deriv_persp: InterpDerivArgs' fields plus q as PerspArgs has it (k_interp_deriv_persp)
+struct PerspDerivArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *tri_pos;       // [triangle * pos_stride], as RenderArgs has it
+  const float *attr;
+  const float *q;
+  float *out;
+  uint64_t vis_stride;        // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride;      // floats per frame in out = 2 * n_ch * local_rows * width
+  uint64_t attr_frame_stride; // floats per frame in attr = attr_tris * 3 * n_ch; 0: one array for every frame
+  uint64_t q_frame_stride;    // floats per frame in q = q_tris * 3; 0: one array for every frame
+  uint32_t pos_stride, n_ch;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_interp_deriv_persp(const PerspDerivArgs &a, hipStream_t s);
 // srz_frameset_texture_mip / _texture_mip_grad: TexArgs' fields, plus the derivative planes uvd [frame][4][local_rows][width], the
 // pyramid `mip` (backward: may be null when guv is), its gradient `gmip` (added into, comes with gtex) and the level count
 // (k_tex_mip, k_tex_mip_grad).  n_levels == 1: uvd, mip and gmip are not read.  The host has checked n_levels against the size

@@ -3299,7 +3299,8 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
 // Then what the bodies do next: quad_ids (the four owner ids, strangers clamped to nobody), quad_bary (α, β and γ of the owned
 // pixels) and quad_store_owned (whole quads, or the owned pixels only).
 // CALLERS: k_shade_vis (pass_tiles with its kind filter, pass_tile, quad_ids), k_interp, k_interp_grad, k_interp_deriv (all of it),
-// k_cube and k_cube_grad (the walk, quad_ids, quad_store_owned).
+// k_cube and k_cube_grad (the walk, quad_ids, quad_store_owned), k_persp (the walk, quad_ids), k_persp_grad and
+// k_interp_deriv_persp (all of it).
 // COPIES, each naming this definition — a fix to the walk goes into them too: k_gbuffer, k_motion, k_pos_grad, aa_body, k_tex,
 // k_tex_grad, k_tex_mip, k_tex_mip_grad (with tex_quad and mip_quad).  Moved onto these helpers they computed the same words
 // (the whole suite passed) but ran slower than their inline text on an MI355X at 256 frames of 1024²: k_gbuffer +4 %, k_motion +6 %,
@@ -5490,6 +5491,336 @@ __global__ __launch_bounds__(256) void k_interp_deriv(InterpDerivArgs a) {
 }
 
 // ================================================================================================================
+// k_persp / k_persp_grad / k_interp_deriv_persp — PERSPECTIVE-CORRECT BARYCENTRICS (srz_frameset_perspective, _perspective_grad,
+// _interpolate_deriv_persp; include/srz.h states the rule).  A visibility buffer's α, β are linear in screen space; with q_k the
+// reciprocal clip w of the owner's corners, α' = α q0 / s, β' = β q1 / s, s = α q0 + β q1 + γ q2 are the weights of the point of
+// the triangle that projects onto the pixel.  k_persp writes them into a buffer of the visibility buffer's own layout, so that
+// k_interp, k_interp_grad, k_gbuffer and k_shade_vis run on it unchanged; z and the ids are copied.
+//   k_persp               k_interp's shape: pass_walk<false>, no LDS, no barrier; quad_ids, the four planes' quads, three dwords of q
+//                         gathered per run of one owner within the quad; EVERY pixel of the tile is written (the words of a pixel
+//                         nobody owns are copied), so a partial quad is stored pixel by pixel whoever owns it.  Plain stores:
+//                         k_interp reads the buffer next.  Floor: 16 bytes read and 16 written per pixel, 12 gathered per owned pixel.
+//   k_persp_grad          k_pos_grad's four stages at three values per owner (g0 α, g1 β, g2 γ into gq): the quad's run sums, the
+//                         segmented DPP row scan, the tile's open-addressed owner table in LDS, the listed flush with
+//                         global_atomic_add_f32; an owner without a slot adds straight to memory.  pp_scan_step, pp_emit and the
+//                         flush are COPIES of pg_scan_step, pg_emit and k_pos_grad's step 4 (themselves copies of ig_scan_step /
+//                         ig_emit), for the reason given there; a fix goes into all three.  A pixel that is not valid takes no
+//                         part in the sums: its key is 0, like a pixel nobody owns.  galpha, gbeta from registers, no atomics.
+//                         Without gq there is no table and no barrier.
+//   k_interp_deriv_persp  k_interp_deriv's shape plus the α, β quads and the q gather; the channels in chunks of ATTR_CHUNK.
+// ================================================================================================================
+struct PerspPx {
+  float ap, bp, s; // α', β' (α, β themselves where the rule does not apply) and the denominator
+  bool valid;
+};
+// (a positive normal float: x >= 2^-126 && x < inf; a NaN fails)
+__device__ __forceinline__ bool persp_ok(float x) { return x >= 0x1p-126f && x < __builtin_inff(); }
+__device__ __forceinline__ PerspPx persp_px(float al, float be, float ga, float q0, float q1, float q2) {
+  const float n0 = al * q0, n1 = be * q1, n2 = ga * q2, s = (n0 + n1) + n2;
+  const bool valid = persp_ok(q0) && persp_ok(q1) && persp_ok(q2) && persp_ok(s);
+  return {valid ? n0 / s : al, valid ? n1 / s : be, s, valid}; // (the IEEE divisions)
+}
+__global__ __launch_bounds__(256) void k_persp(PerspArgs a) {
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const TileRect &rc = t.rc;
+    const float *gv = a.vis + (size_t)t.f * a.vis_stride + t.poff; // plane 0
+    // ---- 1. owner ids, and the words of all four planes (the id quad is the one quad_ids loaded)
+    uint32_t id[4];
+    const uint32_t own = quad_ids(t, gv, id);
+    float4 v[4];
+    v[0] = v[1] = v[2] = v[3] = make_float4(0.f, 0.f, 0.f, 0.f);
+    quad_load(gv, rc.plane, v, t.whole, t.x4, rc.tx1);
+    // ---- 2. α', β' of the owned pixels, q gathered once per run of one owner
+    if (own != 0u) {
+      const SRZ_CAS float *qf = as_const(a.q) + (size_t)t.f * a.q_frame_stride;
+      uint32_t prev = 0u;
+      float q0 = 0.f, q1 = 0.f, q2 = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (id[k] == 0u) continue;
+        const uint32_t key = id[k] & ~S_CLASS_BIT;
+        if (key != prev) {
+          const SRZ_CAS float *p = qf + (size_t)(key - 1u) * 3u;
+          q0 = p[0], q1 = p[1], q2 = p[2], prev = key;
+        }
+        const float al = quad_at(v[2], k), be = quad_at(v[3], k);
+        const float ga = (id[k] & S_CLASS_BIT) ? 1.0f - al - be : 1.0f - (al + be); // (cover_s / cover_v)
+        const PerspPx r = persp_px(al, be, ga, q0, q1, q2);
+        quad_at(v[2], k) = r.ap, quad_at(v[3], k) = r.bp;
+      }
+    }
+    // ---- 3. all four planes, every pixel of the tile
+    float *go = t.out;
+    if (t.whole) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) *reinterpret_cast<float4 *>(go + i * rc.plane) = v[i];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (t.x4 + k <= rc.tx1)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) go[i * rc.plane + k] = quad_at(v[i], k);
+    }
+  });
+}
+
+constexpr uint32_t PP_VALS = 3, PP_SLOTS_PER_WAVE = 64 / PP_VALS;
+struct PerspTable {
+  uint32_t key[IG_SLOTS];  // triangle index + 1; 0: free
+  uint32_t used[IG_SLOTS]; // the slots taken, in arrival order
+  uint32_t n_used[2];      // [tile parity]
+  float val[IG_SLOTS * PP_VALS]; // [slot][corner]
+};
+template <int CTRL> __device__ __forceinline__ void pp_scan_step(float (&acc)[PP_VALS], uint32_t &stop) { // (pg_scan_step)
+  const uint32_t up_stop = dpp_u32<CTRL>(stop);
+#pragma unroll
+  for (uint32_t e = 0; e < PP_VALS; ++e) {
+    const float up = u2f(dpp_u32<CTRL>(f2u(acc[e])));
+    if (!stop) acc[e] += up;
+  }
+  stop |= up_stop;
+}
+__device__ __forceinline__ void pp_emit(PerspTable &tb, uint32_t par, uint32_t key, const float (&acc)[PP_VALS], float *gq) { // (pg_emit)
+  uint32_t h = (key * 0x9e3779b1u) >> (32u - IG_SLOT_BITS);
+  bool found = false;
+  for (uint32_t p = 0; p < IG_PROBES && !found; ++p) {
+    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
+    if (old == 0u) tb.used[atomicAdd(&tb.n_used[par], 1u)] = h; // (each slot is taken once: n_used <= IG_SLOTS)
+    found = old == 0u || old == key;
+    if (!found) h = (h + 1u) & (IG_SLOTS - 1u);
+  }
+  if (found) {
+#pragma unroll
+    for (uint32_t e = 0; e < PP_VALS; ++e) atomicAdd(&tb.val[h * PP_VALS + e], acc[e]);
+  } else {
+    float *g = gq + (size_t)(key - 1u) * PP_VALS;
+#pragma unroll
+    for (uint32_t e = 0; e < PP_VALS; ++e) global_add(g + e, acc[e]);
+  }
+}
+// one owned pixel: galpha, gbeta (ga, gb themselves where the rule does not apply); a valid pixel with ACC: its three terms onto acc
+template <bool ACC>
+__device__ __forceinline__ bool pp_pixel(float al, float be, float ga, float q0, float q1, float q2, float gA, float gB, float &gx, float &gy,
+                                         float (&acc)[PP_VALS]) {
+  const PerspPx r = persp_px(al, be, ga, q0, q1, q2);
+  gx = gA, gy = gB;
+  if (r.valid) {
+    const float tt = fmaf_(gA, r.ap, gB * r.bp), rs = 1.0f / r.s; // (the IEEE division)
+    const float g0 = (gA - tt) * rs, g1 = (gB - tt) * rs, g2 = (-tt) * rs;
+    const float m = g2 * q2;
+    gx = fmaf_(g0, q0, -m), gy = fmaf_(g1, q1, -m);
+    if (ACC) acc[0] += g0 * al, acc[1] += g1 * be, acc[2] += g2 * ga;
+  }
+  return r.valid;
+}
+__global__ __launch_bounds__(256) void k_persp_grad(PerspArgs a) {
+  __shared__ PerspTable tb;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool want_q = a.gq != nullptr, want_bary = a.out != nullptr; // (kernel arguments: every branch on them is wave-uniform)
+  if (want_q) {
+    for (uint32_t i = tid; i < IG_SLOTS; i += 256) tb.key[i] = 0u;
+    for (uint32_t i = tid; i < IG_SLOTS * PP_VALS; i += 256) tb.val[i] = 0.0f;
+    if (tid < 2) tb.n_used[tid] = 0u;
+    __syncthreads();
+  }
+  uint32_t par = 0u; // the tile's parity in this workgroup's walk (the same in every thread: nobody skips a tile)
+  pass_walk<true>(a, [&](const PassTile &t) { // (a thread outside the frame owns nothing, and still meets the barriers)
+    const TileRect &rc = t.rc;
+    const float *gv = a.vis + (size_t)t.f * a.vis_stride + t.poff; // plane 0 (z: never read)
+    const float *gg = a.gbary_p + (size_t)t.f * a.frame_stride + t.poff;
+    // ---- 1. owner ids
+    uint32_t id[4], first = 0u;
+    const uint32_t own = quad_ids(t, gv, id);
+    bool one_owner = true; // every owned pixel of the quad has the same triangle (either class)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (id[k] == 0u) continue;
+      const uint32_t key = id[k] & ~S_CLASS_BIT;
+      one_owner = one_owner && (first == 0u || first == key);
+      first = first == 0u ? key : first;
+    }
+    // ---- 2. α, β of a quad with an owner, each owner's γ by its class, and the gradient quads; words of nobody's pixels are
+    //         loaded with their quad at most, never used
+    float4 al, be, ga;
+    quad_bary(t, gv, own, id, al, be, ga);
+    float4 qa = make_float4(0.f, 0.f, 0.f, 0.f), qb = qa;
+    if (own != 0u) {
+      if (t.whole) {
+        qa = *reinterpret_cast<const float4 *>(gg), qb = *reinterpret_cast<const float4 *>(gg + rc.plane);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (own & (1u << k)) quad_at(qa, k) = gg[k], quad_at(qb, k) = gg[rc.plane + k];
+      }
+    }
+    // ---- 3. the pixels: galpha, gbeta into ox, oy; the three terms of a valid pixel onto the open run's sums
+    float4 ox = make_float4(0.f, 0.f, 0.f, 0.f), oy = ox; // nobody: zeros
+    float acc[PP_VALS] = {0.0f, 0.0f, 0.0f};
+    uint32_t cur = 0u; // the open run's key: a pixel that is not valid opens none
+    const SRZ_CAS float *qf = as_const(a.q) + (size_t)t.f * a.q_frame_stride;
+    float *gqf = a.gq + (size_t)t.f * a.q_frame_stride;
+    if (own != 0u && one_owner) { // one owner: one gather, the quad is one run
+      const SRZ_CAS float *p = qf + (size_t)(first - 1u) * 3u;
+      const float q0 = p[0], q1 = p[1], q2 = p[2];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (id[k] == 0u) continue;
+        float gx, gy;
+        const bool valid = want_q ? pp_pixel<true>(quad_at(al, k), quad_at(be, k), quad_at(ga, k), q0, q1, q2, quad_at(qa, k), quad_at(qb, k), gx, gy, acc)
+                                  : pp_pixel<false>(quad_at(al, k), quad_at(be, k), quad_at(ga, k), q0, q1, q2, quad_at(qa, k), quad_at(qb, k), gx, gy, acc);
+        quad_at(ox, k) = gx, quad_at(oy, k) = gy;
+        if (valid) cur = first;
+      }
+    } else if (own != 0u) { // several owners (an edge crosses the quad): pixel after pixel, a run that ends goes into the table
+      uint32_t prev = 0u; // the owner whose q is held
+      float q0 = 0.f, q1 = 0.f, q2 = 0.f, run[PP_VALS] = {0.0f, 0.0f, 0.0f};
+#pragma nounroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t idk = k == 0 ? id[0] : k == 1 ? id[1] : k == 2 ? id[2] : id[3];
+        if (idk == 0u) continue;
+        const uint32_t key = idk & ~S_CLASS_BIT;
+        if (key != prev) {
+          const SRZ_CAS float *p = qf + (size_t)(key - 1u) * 3u;
+          q0 = p[0], q1 = p[1], q2 = p[2], prev = key;
+        }
+        run[0] = run[1] = run[2] = 0.0f;
+        float gx, gy;
+        const bool valid = want_q ? pp_pixel<true>(quad_pick(al, k), quad_pick(be, k), quad_pick(ga, k), q0, q1, q2, quad_pick(qa, k), quad_pick(qb, k), gx, gy, run)
+                                  : pp_pixel<false>(quad_pick(al, k), quad_pick(be, k), quad_pick(ga, k), q0, q1, q2, quad_pick(qa, k), quad_pick(qb, k), gx, gy, run);
+        quad_put(ox, k, gx), quad_put(oy, k, gy);
+        if (want_q && valid) {
+          if (cur != 0u && key != cur) {
+            pp_emit(tb, par, cur, acc, gqf);
+            acc[0] = acc[1] = acc[2] = 0.0f;
+          }
+          cur = key;
+          acc[0] += run[0], acc[1] += run[1], acc[2] += run[2];
+        }
+      }
+    }
+    if (want_q) {
+      // the key a quad of one owner takes into the row's scan; 0: the quad emits its runs itself, or has none
+      const uint32_t skey = own != 0u && one_owner ? cur : 0u;
+      const bool scan = __builtin_amdgcn_ballot_w64(skey != 0u) != 0ull; // (wave-uniform)
+      const uint32_t pos = (uint32_t)lane & 7u;
+      // (every lane executes both shifts: a lane that skipped one behind a short-circuit would be missing as its neighbour's source)
+      const uint32_t key_left = dpp_u32<DPP_ROW_SHR1>(skey), key_right = dpp_u32<DPP_ROW_SHL1>(skey);
+      const bool seg_head = (pos == 0u) | (key_left != skey) | (skey == 0u); // (a quad without a key takes no carry)
+      const bool seg_last = (pos == 7u) | (key_right != skey);
+      if (scan) { // inclusive segmented scan over the 8 quads of the tile row (Hillis-Steele: a lane past a head takes no carry)
+        uint32_t stop = seg_head ? 1u : 0u; // (position p < d has stop set before the step of distance d: position 0 is a head)
+        pp_scan_step<DPP_ROW_SHR1>(acc, stop);
+        pp_scan_step<DPP_ROW_SHR2>(acc, stop);
+        pp_scan_step<DPP_ROW_SHR4>(acc, stop);
+      }
+      // the last quad of a row's run holds the run's sum; a quad of several owners (a head: the scan left it alone) its last run
+      const uint32_t ekey = skey != 0u ? (seg_last ? skey : 0u) : cur;
+      if (ekey != 0u) pp_emit(tb, par, ekey, acc, gqf);
+      // ---- 4. the table into memory, and emptied: PP_SLOTS_PER_WAVE slots per wave and pass, a slot's three floats on three
+      //         consecutive lanes; the slot's first lane reads and frees the key, the others get it from that lane
+      __syncthreads();
+      const uint32_t n_used = tb.n_used[par];
+      if (tid == 0) tb.n_used[par ^ 1u] = 0u; // (last read before the previous tile's second barrier, next added to behind this tile's)
+      const uint32_t sl = (uint32_t)lane / PP_VALS, e = (uint32_t)lane - sl * PP_VALS;
+      for (uint32_t base = (uint32_t)wave * PP_SLOTS_PER_WAVE; base < n_used; base += 4u * PP_SLOTS_PER_WAVE) { // (wave-uniform)
+        const bool on = sl < PP_SLOTS_PER_WAVE && base + sl < n_used;
+        uint32_t s = 0u, key = 0u;
+        if (on) s = tb.used[base + sl];
+        if (on && e == 0u) key = tb.key[s], tb.key[s] = 0u;
+        key = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(sl * PP_VALS) << 2, (int)key); // (every lane executes it)
+        if (on) {
+          const float v = tb.val[s * PP_VALS + e];
+          tb.val[s * PP_VALS + e] = 0.0f;
+          global_add(gqf + (size_t)(key - 1u) * PP_VALS + e, v);
+        }
+      }
+      __syncthreads();
+      par ^= 1u;
+    }
+    // ---- 5. galpha, gbeta: whole quads (fused clear, or four owners), else the owned pixels only
+    const bool fused = t.fused(a.flags_or);
+    if (want_bary && t.inside && (own != 0u || fused)) quad_store_owned(t.out, t, {ox, oy}, fused, own);
+  });
+}
+
+__global__ __launch_bounds__(256) void k_interp_deriv_persp(PerspDerivArgs a) {
+  const uint32_t C = a.n_ch;
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool fused = t.fused(a.flags_or);
+    const float *gv = a.vis + (size_t)t.f * a.vis_stride + t.poff; // plane 0 (z: never read)
+    // ---- 1. owner ids (the class bit kept: γ and the interpolated value follow it)
+    uint32_t id[4];
+    const uint32_t own = quad_ids(t, gv, id);
+    if (own == 0u && !fused) return;
+    // ---- 2. α, β, γ of the owned pixels; ∇α, ∇β and q of each owner, gathered once per run of one owner; then α', β', γ', s
+    float4 al, be, ga;
+    quad_bary(t, gv, own, id, al, be, ga);
+    const SRZ_CAS float *tpos = as_const(a.tri_pos) + (size_t)t.fd->tri_off * a.pos_stride;
+    const SRZ_CAS float *qf = as_const(a.q) + (size_t)t.f * a.q_frame_stride;
+    DerivTri T[4] = {};
+    float4 Q0 = make_float4(0.f, 0.f, 0.f, 0.f), Q1 = Q0, Q2 = Q0, S = Q0;
+    uint32_t valid = 0u;
+    {
+      uint32_t prev = 0u;
+      DerivTri cur = {0.f, 0.f, 0.f, 0.f};
+      float q0 = 0.f, q1 = 0.f, q2 = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (id[k] == 0u) continue;
+        const uint32_t key = id[k] & ~S_CLASS_BIT;
+        if (key != prev) {
+          cur = deriv_tri(tpos + (size_t)(key - 1u) * a.pos_stride);
+          const SRZ_CAS float *p = qf + (size_t)(key - 1u) * 3u;
+          q0 = p[0], q1 = p[1], q2 = p[2], prev = key;
+        }
+        T[k] = cur;
+        const PerspPx r = persp_px(quad_at(al, k), quad_at(be, k), quad_at(ga, k), q0, q1, q2);
+        if (r.valid) {
+          valid |= 1u << k;
+          quad_at(al, k) = r.ap, quad_at(be, k) = r.bp;
+          quad_at(ga, k) = (id[k] & S_CLASS_BIT) ? 1.0f - r.ap - r.bp : 1.0f - (r.ap + r.bp); // (cover_s / cover_v)
+          quad_at(Q0, k) = q0, quad_at(Q1, k) = q1, quad_at(Q2, k) = q2, quad_at(S, k) = r.s;
+        }
+      }
+    }
+    const SRZ_CAS float *at = as_const(a.attr) + (size_t)t.f * a.attr_frame_stride;
+    // ---- 3. the channels, ATTR_CHUNK at a time
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 qx[ATTR_CHUNK], qy[ATTR_CHUNK];
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) qx[i] = qy[i] = make_float4(0.f, 0.f, 0.f, 0.f); // nobody: zeros
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (id[k] == 0u) continue;
+        const SRZ_CAS float *p = at + (size_t)((id[k] & ~S_CLASS_BIT) - 1u) * (3u * C) + c0;
+        const bool isS = (id[k] & S_CLASS_BIT) != 0u;
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+          if (i < nc) {
+            const float ca = p[i], cb = p[C + i], cc = p[2u * C + i];
+            if (valid & (1u << k)) {
+              const float u = interp_ch(isS, quad_at(al, k), quad_at(be, k), quad_at(ga, k), ca, cb, cc);
+              const float e0 = (ca - u) * quad_at(Q0, k), e1 = (cb - u) * quad_at(Q1, k), e2 = (cc - u) * quad_at(Q2, k);
+              quad_at(qx[i], k) = fmaf_(e0 - e2, T[k].gax, (e1 - e2) * T[k].gbx) / quad_at(S, k); // (the IEEE divisions)
+              quad_at(qy[i], k) = fmaf_(e0 - e2, T[k].gay, (e1 - e2) * T[k].gby) / quad_at(S, k);
+            } else { // (k_interp_deriv's words)
+              const float da = ca - cc, db = cb - cc;
+              quad_at(qx[i], k) = fmaf_(da, T[k].gax, db * T[k].gbx);
+              quad_at(qy[i], k) = fmaf_(da, T[k].gay, db * T[k].gby);
+            }
+          }
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+        if (i >= nc) break;
+        quad_store_owned(t.out + (size_t)(2u * (c0 + i)) * t.rc.plane, t, {qx[i], qy[i]}, fused, own);
+      }
+    }
+  });
+}
+
+// ================================================================================================================
 // k_tex_mip — THE TRILINEAR LOOKUP OVER A MIP PYRAMID (srz_frameset_texture_mip, include/srz.h states the rule): k_tex's walk and
 // shape (no LDS, no barrier, 4 pixels of a row per thread, quad_store), plus the four derivative planes of a quad with a sampled
 // pixel.  Per sampled pixel the level l0 and the fraction f come from mip_lod — compares, one sqrt, frexp: no transcendental — and
@@ -6525,6 +6856,9 @@ void launch_tex_grad(const TexArgs &a, hipStream_t s) { launch_pass<k_tex_grad>(
 void launch_cube(const CubeArgs &a, hipStream_t s) { launch_pass<k_cube>(a, s); }
 void launch_cube_grad(const CubeArgs &a, hipStream_t s) { launch_pass<k_cube_grad>(a, s); }
 void launch_interp_deriv(const InterpDerivArgs &a, hipStream_t s) { launch_pass<k_interp_deriv>(a, s); }
+void launch_persp(const PerspArgs &a, hipStream_t s) { launch_pass<k_persp>(a, s); }
+void launch_persp_grad(const PerspArgs &a, hipStream_t s) { launch_pass<k_persp_grad>(a, s); }
+void launch_interp_deriv_persp(const PerspDerivArgs &a, hipStream_t s) { launch_pass<k_interp_deriv_persp>(a, s); }
 void launch_tex_mip(const TexMipArgs &a, hipStream_t s) { launch_pass<k_tex_mip>(a, s); }
 void launch_tex_mip_grad(const TexMipArgs &a, hipStream_t s) { launch_pass<k_tex_mip_grad>(a, s); }
 // a workgroup per row of the level written (build) or of level 0 (fold), at most MIP_GRID of them striding over the rows

@@ -32,6 +32,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_texture_mip_levels", "srz_texture_mip_bytes", "srz_texture_mip_build", "srz_texture_mip_fold",
            "srz_frameset_interpolate_deriv", "srz_frameset_texture_mip", "srz_frameset_texture_mip_grad",
            "srz_frameset_texture_cube", "srz_frameset_texture_cube_grad",
+           "srz_frameset_perspective", "srz_frameset_perspective_grad", "srz_frameset_interpolate_deriv_persp",
            "srz_target_create", "srz_target_destroy", "srz_target_clear", "srz_target_draw", "srz_target_read", "srz_target_read_bgr8"]
 
 
@@ -112,6 +113,9 @@ def lib():
         L.srz_frameset_texture_mip_grad.argtypes = abi.TEXTURE_MIP_GRAD_ARGTYPES
         L.srz_frameset_texture_cube.argtypes = abi.TEXTURE_CUBE_ARGTYPES
         L.srz_frameset_texture_cube_grad.argtypes = abi.TEXTURE_CUBE_GRAD_ARGTYPES
+        L.srz_frameset_perspective.argtypes = abi.PERSPECTIVE_ARGTYPES
+        L.srz_frameset_perspective_grad.argtypes = abi.PERSPECTIVE_GRAD_ARGTYPES
+        L.srz_frameset_interpolate_deriv_persp.argtypes = abi.INTERPOLATE_DERIV_PERSP_ARGTYPES
         L.srz_frameset_update_shading.argtypes = [vp, vp, C.POINTER(abi.SrzFrame), C.c_int]
         L.srz_sceneset_update.argtypes = [vp, vp, C.POINTER(abi.SrzSceneFrame), C.c_int]
         L.srz_frameset_resolve8.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
@@ -411,6 +415,36 @@ class FrameSet:
                                                              C.c_void_p(d_gout_ptr), C.c_void_p(d_tex_ptr or None), n, n_ch, tex_frames,
                                                              C.c_void_p(d_gtex_ptr or None), C.c_void_p(d_gdir_ptr or None), flags,
                                                              _stream(stream)))
+
+    def perspective(self, d_vis_ptr, d_q_ptr, q_frames, q_tris, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """a visibility buffer of this set with its screen-linear alpha, beta rewritten into the PERSPECTIVE-CORRECT alpha', beta', from
+        d_q [q_frames][q_tris][3] float32, the reciprocal clip w of every triangle's corners (q_frames: 1 or the frame count;
+        corner_attr's layout at one channel) → d_out, a buffer of the same four-plane layout, every word written (z, the ids and
+        nobody's pixels copied; a pixel whose q or denominator is not a positive normal float keeps alpha, beta: include/srz.h states
+        the rule).  interpolate, interpolate_grad, gbuffer and shade_visibility take d_out and are then perspective-correct;
+        position_grad, motion, antialias, peel_visibility and interpolate_deriv keep taking the ORIGINAL buffer.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_perspective(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_q_ptr), q_frames, q_tris,
+                                                       C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def perspective_grad(self, d_vis_ptr, d_q_ptr, q_frames, q_tris, d_gbary_p_ptr, d_gbary_ptr, d_gq_ptr, flags=abi.FUSED_CLEAR, stream=None):
+        """the backward of perspective: d_gbary_p [frame][2][local_rows][width], the gradient with respect to alpha', beta'
+        (interpolate_grad's d_gbary on the perspective buffer), with the ORIGINAL buffer d_vis and the same d_q → written to d_gbary
+        (the gradient with respect to the screen-linear alpha, beta: what position_grad takes with the ORIGINAL buffer;
+        deterministic) and / or ADDED into d_gq (d_q's shape; the order of the adds is unspecified: not bit-reproducible).  Either
+        output pointer may be None / 0, not both.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_perspective_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_q_ptr), q_frames, q_tris,
+                                                            C.c_void_p(d_gbary_p_ptr), C.c_void_p(d_gbary_ptr or None),
+                                                            C.c_void_p(d_gq_ptr or None), flags, _stream(stream)))
+
+    def interpolate_deriv_persp(self, d_vis_ptr, d_q_ptr, q_frames, q_tris, d_attr_ptr, n_ch, attr_frames, attr_tris, d_out_ptr, out_bytes,
+                                flags=abi.FUSED_CLEAR, stream=None):
+        """interpolate_deriv under the perspective-correct interpolation: the per-pixel screen-space derivatives of the attributes, from
+        the ORIGINAL buffer d_vis, d_q as perspective takes it and the set's own positions → d_out
+        [frame][2 * n_ch][local_rows][width] (include/srz.h states the rule; where it does not apply, interpolate_deriv's words).
+        Asynchronous."""
+        self.ctx._check(lib().srz_frameset_interpolate_deriv_persp(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_q_ptr), q_frames,
+                                                                   q_tris, C.c_void_p(d_attr_ptr), n_ch, attr_frames, attr_tris,
+                                                                   C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
 
     def update_shading(self, frames):
         """new eye, ka, ks, p, kh, kn, lights, flags and batch shaders / textures for a set made from abi.Frame's, triangles untouched

@@ -40,6 +40,10 @@ TEXTURE_MIP_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32,
 # the prototypes of srz_frameset_texture_cube / _texture_cube_grad (argtypes; both return int), set by srz.lib()
 TEXTURE_CUBE_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
 TEXTURE_CUBE_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp]
+# the prototypes of srz_frameset_perspective / _perspective_grad / _interpolate_deriv_persp (argtypes; all return int), set by srz.lib()
+PERSPECTIVE_ARGTYPES = [_vp, _vp, _vp, _vp, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
+PERSPECTIVE_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _vp]
+INTERPOLATE_DERIV_PERSP_ARGTYPES = [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
 
 # numpy view of srz_tri (96 B): pos[3][3], nrm[3][3], uv[3][2]
 TRI_DTYPE = np.dtype([("pos", "<f4", (3, 3)), ("nrm", "<f4", (3, 3)), ("uv", "<f4", (3, 2))])

@@ -900,3 +900,154 @@ def corner_attr(fs, attrs, pos_tris=None, stream=None):
             raise ValueError(f"corner_attr: slot {m} must be a CUDA float32 tensor [{V}, C] or [{fs.n_frames}, {V}, C] with one C in "
                              f"1..{abi.ATTR_MAX_CH} for every slot, got {tuple(a.shape)} {a.dtype}")
     return _CornerAttr.apply(fs, slots, pos_tris, stream, *[attrs[m] for m in slots])
+
+
+# ------------------------------------------------------------------------------------------------ perspective-correct interpolation
+def _q_dims(fs, q, name):
+    if q.dtype != torch.float32 or not q.is_cuda or q.dim() not in (2, 3) or q.shape[-1] != 3:
+        raise ValueError(f"{name}: q must be a CUDA float32 tensor [T, 3] or [n_frames, T, 3], got {tuple(q.shape)} {q.dtype}")
+    q_frames = q.shape[0] if q.dim() == 3 else 1
+    if q.dim() == 3 and q_frames != fs.n_frames:
+        raise ValueError(f"{name}: q has {q_frames} frames, the set {fs.n_frames}")
+    return q_frames, q.shape[-2]
+
+
+def perspective(fs, vis, q, out=None, stream=None):
+    """the visibility buffer `vis` of FrameSet `fs` with its screen-linear alpha, beta rewritten into the PERSPECTIVE-CORRECT ones
+    (FrameSet.perspective; include/srz.h states the rule): q is a CUDA float32 tensor [T, 3] (one array for every frame) or
+    [n_frames, T, 3], the reciprocal clip w of every triangle's corners (clip_q gives it for a sceneset), T at least every frame's
+    triangle count → a buffer of vis's layout (`out`, or a new one), every word of it written: z, the ids and nobody's pixels
+    copied.  The ATTRIBUTE-SIDE passes take the result — interpolate, interpolate_bary_grad, FrameSet.gbuffer and
+    shade_visibility, and texture* through their planes — and are then perspective-correct; the GEOMETRIC ones keep taking the
+    ORIGINAL `vis`: position_grad, FrameSet.motion, antialias, peel, interpolate_deriv.  Not differentiable by itself:
+    interpolate_persp is the autograd form.  stream: a raw stream handle, None = torch's current stream."""
+    _vis_arg(fs, vis, "perspective: vis")
+    q = q.detach().contiguous()
+    q_frames, q_tris = _q_dims(fs, q, "perspective")
+    out = torch.empty(fs.out_shape, dtype=torch.float32, device=vis.device) if out is None else _vis_arg(fs, out, "perspective: out")
+    fs.perspective(vis.data_ptr(), q.data_ptr(), q_frames, q_tris, out.data_ptr(), fs.out_bytes, abi.FUSED_CLEAR, _stream_ptr(stream))
+    return out
+
+
+def perspective_grad(fs, vis, q, gbary_p, want_gbary=True, want_gq=True, stream=None):
+    """the backward of perspective(fs, vis, q) by one FrameSet.perspective_grad call: gbary_p [n_frames, 2, rows, W], the gradient
+    with respect to alpha', beta' (interpolate_bary_grad on the perspective buffer) → (gbary, gq), each None when not wanted (not
+    both): gbary [n_frames, 2, rows, W] is the gradient with respect to the screen-linear alpha, beta — what position_grad takes
+    together with the ORIGINAL vis; deterministic, zeros where nobody owns the pixel —, gq has q's shape: a sum of float atomics into
+    zeros, not bit-reproducible between runs.  stream: a raw stream handle, None = torch's current stream."""
+    if not want_gbary and not want_gq:
+        raise ValueError("perspective_grad: neither gbary nor gq is asked for")
+    _vis_arg(fs, vis, "perspective_grad: vis")
+    q = q.detach().contiguous()
+    q_frames, q_tris = _q_dims(fs, q, "perspective_grad")
+    if gbary_p.dtype != torch.float32 or not gbary_p.is_cuda or tuple(gbary_p.shape) != tuple(fs.interpolate_shape(2)):
+        raise ValueError(f"perspective_grad: gbary_p must be a CUDA float32 tensor {fs.interpolate_shape(2)}, got {tuple(gbary_p.shape)} {gbary_p.dtype}")
+    gbary_p = gbary_p.contiguous()
+    gbary = torch.empty_like(gbary_p) if want_gbary else None
+    gq = torch.zeros_like(q) if want_gq else None
+    fs.perspective_grad(vis.data_ptr(), q.data_ptr(), q_frames, q_tris, gbary_p.data_ptr(), gbary.data_ptr() if want_gbary else None,
+                        gq.data_ptr() if want_gq else None, abi.FUSED_CLEAR, _stream_ptr(stream))
+    return gbary, gq
+
+
+class _InterpolatePersp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, attr, pos, q, fs, vis, stream):
+        attr = attr.contiguous()
+        attr_frames, tris, n_ch = _attr_dims(fs, attr)
+        if pos.dtype != torch.float32 or pos.dim() != 4 or pos.shape[0] != fs.n_frames or tuple(pos.shape[2:]) != (3, 3):
+            raise ValueError(f"interpolate_persp: pos must be float32 [n_frames, T, 3, 3], got {tuple(pos.shape)} {pos.dtype}")
+        pvis = perspective(fs, vis, q, stream=stream)
+        out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=attr.device)
+        fs.interpolate(pvis.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris, out.data_ptr(), fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR,
+                       _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.pvis, ctx.stream, ctx.pos_shape = fs, vis, pvis, stream, pos.shape
+        ctx.save_for_backward(attr, q.detach())
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        fs, vis, pvis, (attr, q) = ctx.fs, ctx.vis, ctx.pvis, ctx.saved_tensors
+        need_attr, need_pos, need_q = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        gout = gout.contiguous()
+        attr_frames, tris, n_ch = _attr_dims(fs, attr)
+        sp = _stream_ptr(ctx.stream)
+        need_bary = need_pos or need_q
+        # one interpolate_grad call on the perspective buffer for both of its outputs, one perspective_grad call, one position_grad
+        # call on the ORIGINAL buffer
+        gattr = torch.zeros_like(attr) if need_attr else None
+        gbary_p = torch.empty(fs.interpolate_shape(2), dtype=torch.float32, device=gout.device) if need_bary else None
+        if need_attr or need_bary:
+            fs.interpolate_grad(pvis.data_ptr(), gout.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris,
+                                gattr.data_ptr() if need_attr else None, gbary_p.data_ptr() if need_bary else None, abi.FUSED_CLEAR, sp)
+        gpos = gq = None
+        if need_bary:
+            gbary, gq = perspective_grad(fs, vis, q, gbary_p, need_pos, need_q, ctx.stream)
+            if need_pos:
+                gpos = torch.zeros(ctx.pos_shape, dtype=torch.float32, device=gout.device)
+                fs.position_grad(vis.data_ptr(), gbary.data_ptr(), None, ctx.pos_shape[1], gpos.data_ptr(), None, abi.FUSED_CLEAR, sp)
+        return gattr, gpos, gq, None, None, None
+
+
+def interpolate_persp(fs, vis, attr, pos, q, stream=None):
+    """interpolate_geo under the PERSPECTIVE-CORRECT interpolation: interpolate(fs, perspective(fs, vis, q), attr), differentiable
+    with respect to attr, to the triangles' screen positions and to q.  attr and pos as interpolate_geo takes them — pos
+    [n_frames, T, 3, 3] is the graph handle whose VALUES ARE NEVER READ (scene_positions gives it) —; q, [T, 3] or [n_frames, T, 3],
+    is the reciprocal clip w of every corner and ITS VALUES ARE READ (clip_q gives it as a function of the vertices and matrices).
+    Backward: interpolate_grad on the perspective buffer gives attr.grad and the alpha', beta' planes; perspective_grad turns those
+    into q.grad and the screen-linear alpha, beta planes; position_grad on the ORIGINAL vis then gives pos.grad — each asked only for
+    what some input needs.  The perspective buffer of the forward is SAVED for the backward (16 bytes per pixel held between the
+    two), not recomputed.  Owners are held fixed; attr.grad, pos.grad and q.grad are sums of float atomics: not bit-reproducible
+    between runs.  stream: a raw stream handle, None = torch's current stream."""
+    return _InterpolatePersp.apply(attr, pos, q, fs, vis, stream)
+
+
+def clip_q(fs, meshes, mvp, pos_tris=None, stream=None):
+    """q for sceneset `fs` — the reciprocal of the clip w its vertex stage divides by, per corner of the triangle stream — as plain
+    torch ops on the tensors scene_positions takes, so that autograd reaches the vertices and the matrices: meshes, a dict mesh slot
+    → vertex positions [V, 3] or [n_frames, V, 3]; mvp [n_frames, D, 16], every draw's ndc_mvp in its own column-major order.  Per
+    frame and draw r3 = (m[3] x + m[7] y) + (m[11] z + m[15]) over the slot's vertices, q = 1 / r3, laid out by corner_attr at one
+    channel → [n_frames, T, 3] float32; the triangles of slots the dict does not name get q = 0 (their pixels keep the screen-linear
+    weights).  UNLIKE scene_positions' handles THE VALUES ARE READ: the caller warrants they are what the set was made from.
+    corner_attr gives every draw of a slot in a frame the same per-vertex array, so a set that draws one slot TWICE IN A FRAME
+    raises ValueError: such a caller lays q out themselves, per draw."""
+    draws = _scene_draws(fs)
+    D = max(1, max(len(d) for d in draws))
+    if mvp.dtype != torch.float32 or tuple(mvp.shape) != (fs.n_frames, D, 16):
+        raise ValueError(f"clip_q: mvp must be float32 {(fs.n_frames, D, 16)}, got {tuple(mvp.shape)} {mvp.dtype}")
+    per_vertex = {}
+    for m in sorted(meshes):
+        v = meshes[m]
+        V = fs.ctx.mesh_sizes[m][0]
+        if v.dtype != torch.float32 or tuple(v.shape) not in ((V, 3), (fs.n_frames, V, 3)):
+            raise ValueError(f"clip_q: mesh {m} must be float32 [{V}, 3] or [{fs.n_frames}, {V}, 3], got {tuple(v.shape)} {v.dtype}")
+        rows = []
+        for f, d in enumerate(draws):
+            if d.count(m) > 1:
+                raise ValueError(f"clip_q: frame {f} draws mesh slot {m} {d.count(m)} times; lay q out per draw instead")
+            vf = v if v.dim() == 2 else v[f]
+            if m not in d:  # (corner_attr writes nothing for this frame: any finite values)
+                rows.append(torch.ones((V, 1), dtype=torch.float32, device=v.device))
+                continue
+            w = mvp[f, d.index(m)]
+            r3 = (w[3] * vf[:, 0] + w[7] * vf[:, 1]) + (w[11] * vf[:, 2] + w[15])
+            rows.append((1.0 / r3)[:, None])
+        per_vertex[m] = torch.stack(rows)
+    return corner_attr(fs, per_vertex, pos_tris, stream)[..., 0]
+
+
+def interpolate_deriv_persp(fs, vis, attr, q, stream=None):
+    """interpolate_deriv under the PERSPECTIVE-CORRECT interpolation (FrameSet.interpolate_deriv_persp): the per-pixel screen-space
+    derivatives of interpolate(fs, perspective(fs, vis, q), attr) → [n_frames, 2 C, rows, W] float32, the planes texture_mip takes
+    for a [T, 3, 2] uv attribute.  vis is the ORIGINAL buffer, q as perspective takes it.  Not differentiable: the planes only select
+    a mip level.  stream: a raw stream handle, None = torch's current stream."""
+    _vis_arg(fs, vis, "interpolate_deriv_persp: vis")
+    attr, q = attr.detach().contiguous(), q.detach().contiguous()
+    attr_frames, tris, n_ch = _attr_dims(fs, attr)
+    q_frames, q_tris = _q_dims(fs, q, "interpolate_deriv_persp")
+    if n_ch > abi.ATTR_MAX_CH // 2:
+        raise ValueError(f"interpolate_deriv_persp: {n_ch} channels; at most {abi.ATTR_MAX_CH // 2} are supported")
+    out = torch.empty(fs.interpolate_shape(2 * n_ch), dtype=torch.float32, device=attr.device)
+    fs.interpolate_deriv_persp(vis.data_ptr(), q.data_ptr(), q_frames, q_tris, attr.data_ptr(), n_ch, attr_frames, tris, out.data_ptr(),
+                               fs.interpolate_bytes(2 * n_ch), abi.FUSED_CLEAR, _stream_ptr(stream))
+    return out
