@@ -65,6 +65,8 @@ extern "C" {
  *      srz_mesh_normals_grad / srz_sceneset_corner_attr / srz_sceneset_corner_attr_grad
  *      (additive, same version) cube-map lookup by direction over a visibility buffer, with gradients srz_frameset_texture_cube /
  *      srz_frameset_texture_cube_grad
+ *      (additive, same version) Blinn-Phong lighting pass over a visibility buffer, with gradients srz_frameset_light /
+ *      srz_frameset_light_grad / srz_frameset_light_work_bytes
  */
 #define SRZ_ABI_VERSION 7
 
@@ -722,6 +724,83 @@ int srz_frameset_texture_cube(srz_ctx *ctx, srz_frameset *fs, const void *d_vis,
 int srz_frameset_texture_cube_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_dir, const void *d_gout,
                                    const float *d_tex, uint32_t n, uint32_t n_ch, uint32_t tex_frames, float *d_gtex, void *d_gdir,
                                    uint32_t flags, void *stream);
+/* BLINN-PHONG LIGHTING UNDER POINT LIGHTS over a visibility buffer, for the caller's own planes, and its gradients: the link between
+ * the interpolated normals, positions and albedo and an image loss.  The lights, the eye and the material are device data with a
+ * gradient of their own.  This pass is for caller data and reproduces NOTHING of the reference or of the built-in shaders
+ * (srz_frameset_shade_visibility): DELIBERATELY DIFFERENT are the true 1 / r² attenuation (not the x/y distance), the NORMALISED half
+ * vector, the albedo on the ambient and diffuse terms only, and NO CLAMP and no scale by 255 (the caller's units; a clamp would cut
+ * the gradient).
+ * d_vis: a visibility buffer of THIS set on this ctx's shard.  d_nrm, d_pos, d_kd (forward and backward: may be NULL, albedo
+ * (1, 1, 1)), d_out, d_gout, d_gnrm, d_gpos, d_gkd: [frame][3][local_rows][width] float32, srz_frameset_interpolate_bytes(3) bytes each —
+ * what srz_frameset_interpolate, _texture or _gbuffer write.  d_par and d_gpar: [par_frames][SRZ_LIGHT_PAR(n_lights)] float32 in device
+ * memory, 4-byte aligned, a parameter frame being eye[3] ka[3] ks[3], then n_lights x {pos[3], intensity[3]} (srz_light's layout);
+ * par_frames is 1 (every frame shares the one parameter frame) or the set's frame count; 1 <= n_lights <= SRZ_LIGHT_MAX.  p: the
+ * specular exponent, an INTEGER in [1, 256], the same for every frame, a host argument (so a bad one is refused without reading device
+ * memory); there is no gradient to p.  Band sharding, local_rows, stream semantics, asynchrony, the 16-byte alignment of the visibility
+ * buffer and every plane buffer, owner and nobody (id 0, the bare class bit, an index outside the frame's triangles), what a nobody
+ * pixel's words of the output planes become with and without SRZ_FUSED_CLEAR (zeros; untouched), and what the passes do not read or
+ * launch: all as srz_frameset_texture_cube.  The words of the input planes at nobody's pixels never reach a result.
+ * THE RULE, all of it float32, nothing fused except where fmaf is written, / and sqrtf the correctly rounded ones, always the exact
+ * arithmetic (SRZ_OPT_APPROX_SHADE has no effect).  dot(a, b) = fmaf(ax, bx, fmaf(ay, by, az * bz)); a vector times a scalar is three
+ * products.  Per owned pixel with the normal n, the position P, the albedo kd:
+ *   nn = dot(n, n);  lit = nn > 0 && nn < INFINITY;   not lit -> out = (0, 0, 0) (written), every gradient of the pixel 0, no term
+ *   inl = 1 / sqrtf(nn);  N = n * inl
+ *   V = eye - P;  vv = dot(V, V);  view = vv > 0 && vv < INFINITY;  iv = 1 / sqrtf(vv);  Vd = view ? V * iv : (0, 0, 0)
+ *   acc = (0, 0, 0);  for each light in order, position lpos, intensity I:
+ *     Lv = lpos - P;  r2 = dot(Lv, Lv);  if !(r2 > 0 && r2 < INFINITY) the light is SKIPPED at this pixel (no term, no gradient)
+ *     ir = 1 / sqrtf(r2);  Ld = Lv * ir;  att = 1 / r2
+ *     cdr = dot(N, Ld);  cd = cdr > 0 ? cdr : 0
+ *     Hs = Ld + Vd;  h2 = dot(Hs, Hs);  spec = view && h2 > 0
+ *     spec:  ih = 1 / sqrtf(h2);  H = Hs * ih;  csr = dot(N, H);  cs = csr > 0 ? csr : 0;  sp = powi(cs, p);   else sp = 0
+ *     E_c = I_c * att
+ *     acc_c = acc_c + (kd_c * fmaf(E_c, cd, ka_c * I_c) + (ks_c * E_c) * sp)
+ *   out_c = acc_c
+ * powi(x, n): r = 1, b = x in binary64; while n: if (n & 1) r = r * b;  b = b * b;  n >>= 1;  rounded once to binary32 (powi(x, 0) = 1).
+ * BACKWARD: the exact derivative of the rule with its branches held, in THIS order of operations (g = gout of the pixel; a not-lit or
+ * nobody's pixel gives zeros and no term).  gN = gVd = gP = gkd = tka = tks = (0, 0, 0);  for each light that is not skipped, in order:
+ *     gk_c = g_c * kd_c;  gs_c = g_c * ks_c
+ *     gkd_c = gkd_c + g_c * fmaf(E_c, cd, ka_c * I_c)
+ *     tka_c = tka_c + gk_c * I_c;   tks_c = tks_c + (g_c * E_c) * sp
+ *     tI_c  = g_c * (kd_c * fmaf(att, cd, ka_c) + (ks_c * att) * sp)                        (the light's intensity term)
+ *     ge_c  = g_c * fmaf(kd_c, cd, ks_c * sp)
+ *     g_cd = cdr > 0 ? dot(gk, E) : 0;   g_sp = dot(gs, E);   g_att = dot(ge, I)
+ *     gLd = g_cd * N;   gN_c = gN_c + g_cd * Ld_c
+ *     if spec && csr > 0:  g_cs = g_sp * ((float)p * powi(cs, p - 1));  gH = g_cs * N;  gN_c = gN_c + g_cs * H_c;  d = dot(gH, H)
+ *                          gHs_c = (gH_c - H_c * d) * ih;   gLd_c = gLd_c + gHs_c;   gVd_c = gVd_c + gHs_c
+ *     d = dot(gLd, Ld);   w = 2 * -((g_att * att) * att)
+ *     tL_c = fmaf(Lv_c, w, (gLd_c - Ld_c * d) * ir)                                         (the light's position term)
+ *     gP_c = gP_c - tL_c
+ *   then:  view:  d = dot(gVd, Vd);  tE_c = (gVd_c - Vd_c * d) * iv;  gP_c = gP_c - tE_c;    else tE = (0, 0, 0)      (the eye's term)
+ *          d = dot(gN, N);  gn_c = (gN_c - N_c * d) * inl
+ *   d_gnrm = gn, d_gpos = gP, d_gkd = gkd: per pixel, deterministic, bit for bit.  Each may be NULL, not all four outputs; d_gkd must be
+ *   NULL when d_kd is.  They have the layouts srz_frameset_interpolate_grad and srz_frameset_texture_grad take as d_gout.
+ *   d_gpar (needs d_work, at least srz_frameset_light_work_bytes bytes, 4-byte aligned, scratch: what it holds afterwards is
+ *   unspecified) is WRITTEN, not added into: entry k of a frame's row is the sum over the frame's lit pixels on this shard of the
+ *   pixel's float32 term — eye: tE; ka: tka; ks: tks (each summed over the lights first, in light order); a light's pos: tL, its
+ *   intensity: tI (0 where the light is skipped) — in a FIXED tree, no atomics: a pixel (x, y) of a 32 x 32 tile belongs to lane
+ *   (y % 8) * 8 + x % 32 / 4 of wave y % 32 / 8; a lane adds its up to four pixels' terms left to right, from +0; the 64 lanes of a wave
+ *   are summed by the butterfly v = v + v[lane ^ o], o = 32, 16, 8, 4, 2, 1; the four waves as ((w0 + w1) + w2) + w3; a frame's tiles
+ *   in tile order (bands, then columns), from +0; and with par_frames == 1 the frames' rows — each exactly the row the same call with
+ *   per-frame parameters of the same values writes — in frame order, from +0.  So d_gpar is BIT-REPRODUCIBLE for a given shard
+ *   layout: two launches give the same words, and with one lit pixel in all it is that pixel's term (a term of -0 comes out +0).
+ *   Against the exact sum of the terms it lies within n 2^-24 / (1 - n 2^-24) * sum |term|, n the contributing pixels of the entry:
+ *   the bound of any summation tree.  An entry no pixel contributes to is +0.  Ranks each write the sums of their own bands.
+ * SUBNORMALS are numbers, as in srz_frameset_texture_cube; non-finite albedo, intensities and gradients propagate as IEEE has them;
+ * no value of any plane makes a pass read or write outside its buffers.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set, d_vis, d_nrm, d_pos, d_par, d_out, d_gout, or all
+ * of d_gnrm, d_gpos, d_gkd, d_gpar; n_lights == 0 or above SRZ_LIGHT_MAX; par_frames not 1 or the frame count; p outside [1, 256]; a
+ * short out_bytes, or work_bytes with d_gpar; a misaligned pointer; any bit of `flags` but SRZ_FUSED_CLEAR; an output (d_work with
+ * d_gpar counts as one) that overlaps an input or another output; d_gkd without d_kd; d_gpar without d_work. */
+#define SRZ_LIGHT_MAX 8
+/* floats of one parameter frame: eye[3] ka[3] ks[3], then n_lights x {pos[3], intensity[3]} (srz_light's layout) */
+#define SRZ_LIGHT_PAR(n_lights) (9u + 6u * (n_lights))
+int srz_frameset_light(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos, const void *d_kd,
+                       const float *d_par, uint32_t n_lights, uint32_t par_frames, uint32_t p, void *d_out, size_t out_bytes, uint32_t flags,
+                       void *stream);
+size_t srz_frameset_light_work_bytes(srz_ctx *ctx, srz_frameset *fs, uint32_t n_lights);
+int srz_frameset_light_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos, const void *d_kd,
+                            const float *d_par, uint32_t n_lights, uint32_t par_frames, uint32_t p, const void *d_gout, void *d_gnrm,
+                            void *d_gpos, void *d_gkd, float *d_gpar, void *d_work, size_t work_bytes, uint32_t flags, void *stream);
 /* MIPMAPPED TEXTURE SAMPLING over a visibility buffer, and its gradients: the TRILINEAR lookup over a mip pyramid of the caller's
  * texture that goes with the bilinear lookup above, its level chosen from the screen-space derivatives of uv.  Three pieces: the
  * pyramid (build, and fold: its backward), the derivatives of an interpolated attribute, the lookup and its backward.  All of it

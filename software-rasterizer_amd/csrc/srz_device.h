@@ -454,6 +454,30 @@ struct CubeArgs {
 };
 void launch_cube(const CubeArgs &a, hipStream_t s);
 void launch_cube_grad(const CubeArgs &a, hipStream_t s);
+// srz_frameset_light / _light_grad: Blinn-Phong under point lights for caller data.  nrm, pos, kd (may be null: ones), out, gout and
+// the backward's gnrm, gpos, gkd (each may be null) are [frame][3][local_rows][width]; par is [par frames][SRZ_LIGHT_PAR(n_lights)]:
+// eye[3] ka[3] ks[3], then per light pos[3] intensity[3].  `out` is the forward's output, null in the backward (which addresses its
+// planes by frame_stride itself).  work: the backward's [frame][tile][K] partial sums of the parameter gradient, and behind them
+// [frame][K] rows for the fold when every frame shares one parameter frame (null: the planes only)
+struct LightArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *nrm, *pos, *kd;
+  const float *par;
+  float *out;
+  const float *gout;
+  float *gnrm, *gpos, *gkd;
+  float *work;
+  uint64_t vis_stride;   // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride; // floats per frame in every three-plane buffer = 3 * local_rows * width
+  uint64_t par_stride;   // floats per frame in par = SRZ_LIGHT_PAR(n_lights); 0: one parameter frame for every frame
+  uint32_t n_lights, p;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_light(const LightArgs &a, hipStream_t s);
+void launch_light_grad(const LightArgs &a, float *gpar, hipStream_t s);
 // THE MIP PYRAMID of a caller texture (include/srz.h states the geometry): level l of a tex_w x tex_h texture is
 // max(1, tex_w >> l) x max(1, tex_h >> l) — every level that exists came from an even (or one-texel) extent, so the shifts are the
 // halvings — and the levels 1 .. n_levels - 1 lie one after another, each [tex_frames][h_l][w_l][n_ch].  Host and device share these.

@@ -296,8 +296,9 @@ __device__ __forceinline__ float pow150_cr(float x) {
 }
 // x^n for an integer exponent 0..256 that is the same for the whole wave (a per-frame constant): pow_cr's square-and-multiply
 // chain as a SCALAR loop — the very same binary64 multiplications in the same order, no per-lane selects
-__device__ __forceinline__ float pow_int_cr(float x, float p) {
-  unsigned n = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)p);
+// (the exponent as an integer already — k_light's host argument; n = 0 gives 1 —, or as the frame's float constant)
+__device__ __forceinline__ float pow_int_cr(float x, unsigned n_) {
+  unsigned n = (unsigned)__builtin_amdgcn_readfirstlane((int)n_);
   double b = (double)x, r = 1.0;
   while (n) {
     if (n & 1u) r = r * b;
@@ -306,6 +307,7 @@ __device__ __forceinline__ float pow_int_cr(float x, float p) {
   }
   return (float)r;
 }
+__device__ __forceinline__ float pow_int_cr(float x, float p) { return pow_int_cr(x, (unsigned)p); }
 // Compile-time knowledge a shading variant may have (k_shade picks the variant per 64-pixel chunk, wave-uniformly):
 //   SH   >= 0: every pixel of the chunk uses shader type SH; -1: per-pixel type (sd.shader)
 //   NL   != 0: the frame has exactly |NL| lights (1..4) (decided on the host): the light loop is unrolled, the light constants sit
@@ -3300,7 +3302,8 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
 // pixels) and quad_store_owned (whole quads, or the owned pixels only).
 // CALLERS: k_shade_vis (pass_tiles with its kind filter, pass_tile, quad_ids), k_interp, k_interp_grad, k_interp_deriv (all of it),
 // k_cube and k_cube_grad (the walk, quad_ids, quad_store_owned), k_persp (the walk, quad_ids), k_persp_grad and
-// k_interp_deriv_persp (all of it).
+// k_interp_deriv_persp (all of it), k_light (the walk, quad_ids, quad_load, quad_store_owned) and k_light_grad (the same through
+// pass_tiles and pass_tile: the tile's index names its row of partial sums).
 // COPIES, each naming this definition — a fix to the walk goes into them too: k_gbuffer, k_motion, k_pos_grad, aa_body, k_tex,
 // k_tex_grad, k_tex_mip, k_tex_mip_grad (with tex_quad and mip_quad).  Moved onto these helpers they computed the same words
 // (the whole suite passed) but ran slower than their inline text on an MI355X at 256 frames of 1024²: k_gbuffer +4 %, k_motion +6 %,
@@ -5380,6 +5383,284 @@ __global__ __launch_bounds__(256) void k_cube_grad(CubeArgs a) {
 }
 
 // ================================================================================================================
+// k_light — BLINN-PHONG UNDER POINT LIGHTS OVER A VISIBILITY BUFFER, FOR CALLER DATA (srz_frameset_light, include/srz.h states the
+// rule): the normal, position and albedo planes interpolate / texture / gbuffer wrote, a parameter frame (eye, ka, ks, then the
+// lights) and a host exponent -> three colour planes.  Nothing of the built-in shaders: true 1 / r² attenuation, a normalised half
+// vector, no clamp.  k_cube's shape on the passes' helpers: pass_walk, quad_ids, the three or four plane triples of a quad with an
+// owner in 16-byte loads, quad_store_owned; no LDS, no barrier.  The parameter frame is wave-uniform: scalar loads.
+// light_px (what a lit pixel keeps across the lights) and light_term (one light at one pixel) are the rule's text; k_light and
+// k_light_grad both go through them, so the backward differentiates the very words the forward computed.
+// ================================================================================================================
+struct LightPx {
+  float N[3], P[3], Vd[3];
+  float inl, iv;
+  bool view;
+};
+struct LightTerm {
+  float Lv[3], Ld[3], H[3], E[3];
+  float ir, att, ih, cdr, cd, csr, cs, sp;
+  bool spec;
+};
+__device__ __forceinline__ float l_dot(const float (&a)[3], const float (&b)[3]) { return fmaf_(a[0], b[0], fmaf_(a[1], b[1], a[2] * b[2])); }
+__device__ __forceinline__ bool l_pos(float x) { return x > 0.0f && x < __builtin_inff(); }
+__device__ __forceinline__ float l_rsqrt(float x) { return 1.0f / __builtin_sqrtf(x); } // (two roundings: the IEEE root, the IEEE division)
+// false: not lit (the normal's squared length is 0, not finite or NaN)
+__device__ __forceinline__ bool light_px(const float (&n)[3], const float (&P)[3], const SRZ_CAS float *par, LightPx &px) {
+  const float nn = l_dot(n, n);
+  if (!l_pos(nn)) return false;
+  px.inl = l_rsqrt(nn);
+  float V[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) px.N[i] = n[i] * px.inl, px.P[i] = P[i], V[i] = par[i] - P[i];
+  const float vv = l_dot(V, V);
+  px.view = l_pos(vv);
+  px.iv = px.view ? l_rsqrt(vv) : 0.0f;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) px.Vd[i] = px.view ? V[i] * px.iv : 0.0f;
+  return true;
+}
+// lp: the light's {pos[3], intensity[3]}.  false: the light is skipped at this pixel
+__device__ __forceinline__ bool light_term(const LightPx &px, const SRZ_CAS float *lp, uint32_t p, LightTerm &t) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t.Lv[i] = lp[i] - px.P[i];
+  const float r2 = l_dot(t.Lv, t.Lv);
+  if (!l_pos(r2)) return false;
+  t.ir = l_rsqrt(r2), t.att = 1.0f / r2;
+  float Hs[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t.Ld[i] = t.Lv[i] * t.ir, Hs[i] = t.Ld[i] + px.Vd[i], t.H[i] = 0.0f, t.E[i] = lp[3 + i] * t.att;
+  t.cdr = l_dot(px.N, t.Ld), t.cd = t.cdr > 0.0f ? t.cdr : 0.0f;
+  const float h2 = l_dot(Hs, Hs);
+  t.spec = px.view && h2 > 0.0f;
+  t.ih = t.csr = t.cs = t.sp = 0.0f;
+  if (t.spec) {
+    t.ih = l_rsqrt(h2);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t.H[i] = Hs[i] * t.ih;
+    t.csr = l_dot(px.N, t.H), t.cs = t.csr > 0.0f ? t.csr : 0.0f;
+    t.sp = pow_int_cr(t.cs, p);
+  }
+  return true;
+}
+// what k_light and k_light_grad do alike in front of the lights: the owners, the planes of a quad with an owner, the lit pixels'
+// LightPx -> `own` and `lit`, one bit per pixel; kd: ones without an albedo buffer
+__device__ __forceinline__ void light_quad(const LightArgs &a, const PassTile &t, const SRZ_CAS float *par, LightPx (&px)[4], float4 (&kd)[3],
+                                           uint32_t &own, uint32_t &lit) {
+  uint32_t id[4];
+  own = quad_ids(t, a.vis + (size_t)t.f * a.vis_stride + t.poff, id), lit = 0u;
+  kd[0] = kd[1] = kd[2] = make_float4(1.f, 1.f, 1.f, 1.f);
+  if (own == 0u) return;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 n[3] = {zero4, zero4, zero4}, P[3] = {zero4, zero4, zero4};
+  const size_t off = (size_t)t.f * a.frame_stride + t.poff;
+  quad_load(a.nrm + off, t.rc.plane, n, t.whole, t.x4, t.rc.tx1);
+  quad_load(a.pos + off, t.rc.plane, P, t.whole, t.x4, t.rc.tx1);
+  if (a.kd) quad_load(a.kd + off, t.rc.plane, kd, t.whole, t.x4, t.rc.tx1);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (!(own & (1u << k))) continue;
+    const float nk[3] = {quad_at(n[0], k), quad_at(n[1], k), quad_at(n[2], k)}, Pk[3] = {quad_at(P[0], k), quad_at(P[1], k), quad_at(P[2], k)};
+    if (light_px(nk, Pk, par, px[k])) lit |= 1u << k;
+  }
+}
+__global__ __launch_bounds__(256) void k_light(LightArgs a) {
+  const uint32_t L = a.n_lights;
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool fused = t.fused(a.flags_or);
+    const SRZ_CAS float *par = as_const(a.par) + (size_t)t.f * a.par_stride;
+    LightPx px[4];
+    float4 kd[3];
+    uint32_t own, lit;
+    light_quad(a, t, par, px, kd, own, lit);
+    if (own == 0u && !fused) return;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 o[3] = {zero4, zero4, zero4}; // nobody, and an owner that is not lit: zeros
+    if (lit != 0u) {
+      const float ka[3] = {par[3], par[4], par[5]}, ks[3] = {par[6], par[7], par[8]};
+      for (uint32_t l = 0; l < L; ++l) {
+        const SRZ_CAS float *lp = par + 9u + 6u * l;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (!(lit & (1u << k))) continue;
+          LightTerm lt;
+          if (!light_term(px[k], lp, a.p, lt)) continue;
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            quad_at(o[c], k) = quad_at(o[c], k) + (quad_at(kd[c], k) * fmaf_(lt.E[c], lt.cd, ka[c] * lp[3 + c]) + (ks[c] * lt.E[c]) * lt.sp);
+        }
+      }
+    }
+    quad_store_owned(t.out, t, o, fused, own);
+  });
+}
+
+// ================================================================================================================
+// k_light_grad — THE BACKWARD OF k_light (srz_frameset_light_grad): gout -> the gradient planes of the normal, the position and the
+// albedo (per pixel, from registers, deterministic), and, WANT_PAR, the gradient of the parameter frame: every entry is the sum of a
+// per-pixel float32 term over the frame's owned pixels, and this kernel leaves that sum per TILE in work[frame][tile][K], reduced in a
+// FIXED tree (include/srz.h states it): a thread's four pixels left to right; the wave's 64 lanes by the xor butterfly 32, 16, 8, 4, 2,
+// 1 (every lane ends with the same word: float addition commutes); the four waves through LDS, ((w0 + w1) + w2) + w3; ordinary
+// vector stores, no atomics.  k_light_fold sums the tiles.  The lights are the OUTER loop: a light's six lane sums are reduced and put
+// into LDS as its iteration ends, so a lane holds 6 of the up to 57 entries at a time, not all of them; eye, ka and ks — sums over
+// the lights — follow after the loop.  pass_walk<true>'s shape through pass_tiles / pass_tile (the tile's index is the work row):
+// every thread of the workgroup reaches every shuffle and barrier, one outside the frame owns nothing.  A tile without a lit pixel
+// (one barrier tells) writes +0 partials and skips the lights.  The planes-only build has no LDS, no shuffle and no barrier.
+// ================================================================================================================
+__device__ __forceinline__ float light_wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
+  return v;
+}
+template <bool WANT_PAR> __global__ __launch_bounds__(256) void k_light_grad(LightArgs a) {
+  __shared__ float s_part[WANT_PAR ? 4 : 1][WANT_PAR ? SRZ_LIGHT_PAR(SRZ_LIGHT_MAX) : 1];
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  const uint32_t L = a.n_lights, K = SRZ_LIGHT_PAR(L), tpf = a.n_local_bands * a.tiles_x, p = a.p;
+  const float pf = (float)p;
+  pass_tiles(a, [&](uint32_t f, uint32_t ti) {
+    const PassTile t = pass_tile(a, f, ti);
+    const bool fused = t.fused(a.flags_or);
+    const SRZ_CAS float *par = as_const(a.par) + (size_t)f * a.par_stride;
+    const size_t off = (size_t)f * a.frame_stride + t.poff;
+    // ---- 1. owners, planes, the lit pixels; gout of a quad with a lit pixel
+    LightPx px[4];
+    float4 kd[3];
+    uint32_t own, lit;
+    light_quad(a, t, par, px, kd, own, lit);
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (WANT_PAR) {
+      // a tile without a lit pixel (most tiles of a sparse frame): its partials are the empty sums, +0, what the tree below gives too,
+      // without the shuffles; its planes are zeros where they are written at all
+      if (!__syncthreads_or(lit != 0u)) {
+        if (t.inside && (own != 0u || fused)) {
+          const float4 z[3] = {zero4, zero4, zero4};
+          if (a.gnrm) quad_store_owned(a.gnrm + off, t, z, fused, own);
+          if (a.gpos) quad_store_owned(a.gpos + off, t, z, fused, own);
+          if (a.gkd) quad_store_owned(a.gkd + off, t, z, fused, own);
+        }
+        if (tid < K) a.work[((size_t)f * tpf + ti) * K + tid] = 0.0f;
+        return;
+      }
+    }
+    float4 g[3] = {zero4, zero4, zero4};
+    if (lit != 0u) quad_load(a.gout + off, t.rc.plane, g, t.whole, t.x4, t.rc.tx1);
+    float4 gN[3] = {zero4, zero4, zero4}, gVd[3] = {zero4, zero4, zero4}, gP[3] = {zero4, zero4, zero4}, gkd[3] = {zero4, zero4, zero4};
+    float4 tka[3] = {zero4, zero4, zero4}, tks[3] = {zero4, zero4, zero4};
+    const float ka[3] = {par[3], par[4], par[5]}, ks[3] = {par[6], par[7], par[8]};
+    // ---- 2. the lights
+    for (uint32_t l = 0; l < L; ++l) {
+      const SRZ_CAS float *lp = par + 9u + 6u * l;
+      const float I[3] = {lp[3], lp[4], lp[5]};
+      float tl[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; // this lane's sums of the light's terms: pos[3], intensity[3]
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(lit & (1u << k))) continue;
+        LightTerm lt;
+        if (!light_term(px[k], lp, p, lt)) continue;
+        float gk[3], gs[3], ge[3], gLd[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float gc = quad_at(g[c], k), kc = quad_at(kd[c], k);
+          gk[c] = gc * kc, gs[c] = gc * ks[c];
+          quad_at(gkd[c], k) = quad_at(gkd[c], k) + gc * fmaf_(lt.E[c], lt.cd, ka[c] * I[c]);
+          if (WANT_PAR) {
+            quad_at(tka[c], k) = quad_at(tka[c], k) + gk[c] * I[c];
+            quad_at(tks[c], k) = quad_at(tks[c], k) + (gc * lt.E[c]) * lt.sp;
+            tl[3 + c] = tl[3 + c] + gc * (kc * fmaf_(lt.att, lt.cd, ka[c]) + (ks[c] * lt.att) * lt.sp);
+          }
+          ge[c] = gc * fmaf_(kc, lt.cd, ks[c] * lt.sp);
+        }
+        const float g_cd = lt.cdr > 0.0f ? l_dot(gk, lt.E) : 0.0f, g_sp = l_dot(gs, lt.E), g_att = l_dot(ge, I);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gLd[c] = g_cd * px[k].N[c], quad_at(gN[c], k) = quad_at(gN[c], k) + g_cd * lt.Ld[c];
+        if (lt.spec && lt.csr > 0.0f) {
+          const float g_cs = g_sp * (pf * pow_int_cr(lt.cs, p - 1u));
+          float gH[3];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) gH[c] = g_cs * px[k].N[c], quad_at(gN[c], k) = quad_at(gN[c], k) + g_cs * lt.H[c];
+          const float d = l_dot(gH, lt.H);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const float gHs = (gH[c] - lt.H[c] * d) * lt.ih;
+            gLd[c] = gLd[c] + gHs, quad_at(gVd[c], k) = quad_at(gVd[c], k) + gHs;
+          }
+        }
+        const float d = l_dot(gLd, lt.Ld), two_g_r2 = 2.0f * (-((g_att * lt.att) * lt.att));
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float gLv = fmaf_(lt.Lv[c], two_g_r2, (gLd[c] - lt.Ld[c] * d) * lt.ir);
+          tl[c] = tl[c] + gLv, quad_at(gP[c], k) = quad_at(gP[c], k) - gLv;
+        }
+      }
+      if (WANT_PAR) { // (every lane of the workgroup is here: the walk and the light count are uniform)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+          const float v = light_wave_sum(tl[j]);
+          if (lane == 0u) s_part[wave][9u + 6u * l + (uint32_t)j] = v;
+        }
+      }
+    }
+    // ---- 3. behind the lights: the view direction's and the normal's normalisations; the eye's terms
+    float te[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; // this lane's sums of eye[3], ka[3], ks[3]
+    float4 gn[3] = {zero4, zero4, zero4};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (!(lit & (1u << k))) continue;
+      if (px[k].view) {
+        const float v[3] = {quad_at(gVd[0], k), quad_at(gVd[1], k), quad_at(gVd[2], k)};
+        const float d = l_dot(v, px[k].Vd);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float gV = (v[c] - px[k].Vd[c] * d) * px[k].iv;
+          te[c] = te[c] + gV, quad_at(gP[c], k) = quad_at(gP[c], k) - gV;
+        }
+      }
+      const float v[3] = {quad_at(gN[0], k), quad_at(gN[1], k), quad_at(gN[2], k)};
+      const float d = l_dot(v, px[k].N);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        quad_at(gn[c], k) = (v[c] - px[k].N[c] * d) * px[k].inl;
+        te[3 + c] = te[3 + c] + quad_at(tka[c], k), te[6 + c] = te[6 + c] + quad_at(tks[c], k);
+      }
+    }
+    // ---- 4. the planes: whole quads (fused clear, or four owners), else the owned pixels only; an owner that is not lit: zeros
+    if (t.inside && (own != 0u || fused)) {
+      if (a.gnrm) quad_store_owned(a.gnrm + off, t, gn, fused, own);
+      if (a.gpos) quad_store_owned(a.gpos + off, t, gP, fused, own);
+      if (a.gkd) quad_store_owned(a.gkd + off, t, gkd, fused, own);
+    }
+    // ---- 5. the tile's K partial sums
+    if (WANT_PAR) {
+#pragma unroll
+      for (int j = 0; j < 9; ++j) {
+        const float v = light_wave_sum(te[j]);
+        if (lane == 0u) s_part[wave][j] = v;
+      }
+      __syncthreads();
+      if (tid < K) a.work[((size_t)f * tpf + ti) * K + tid] = ((s_part[0][tid] + s_part[1][tid]) + s_part[2][tid]) + s_part[3][tid];
+      __syncthreads(); // s_part is the next tile's too
+    }
+  });
+}
+// k_light_fold — dst[o][k] = src[o][0][k] + src[o][1][k] + ... in that order from +0, k < K: a frame's tiles in tile order (o: the
+// frame), then, for a parameter frame every frame shares, the frames in frame order (o: 0).  A workgroup of 64 per row of dst.
+__global__ __launch_bounds__(64) void k_light_fold(const float *src, float *dst, uint32_t n_inner, uint32_t K) {
+  const uint32_t k = threadIdx.x;
+  if (k >= K) return;
+  const float *p = src + (size_t)blockIdx.x * n_inner * K + k;
+  float s = 0.0f;
+  uint32_t i = 0;
+  for (; i + 16u <= n_inner; i += 16u) { // sixteen loads in flight, then the adds in order: the sum is the serial one
+    float v[16];
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; ++j) v[j] = p[(size_t)(i + j) * K];
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; ++j) s = s + v[j];
+  }
+  for (; i < n_inner; ++i) s = s + p[(size_t)i * K];
+  dst[(size_t)blockIdx.x * K + k] = s;
+}
+
+// ================================================================================================================
 // k_mip_build / k_mip_fold — THE MIP PYRAMID OF A CALLER TEXTURE (srz_texture_mip_build, srz_texture_mip_fold; include/srz.h states
 // the geometry and the arithmetic).  The build is one launch per level, each from the level above it: a workgroup walks rows of the
 // level it writes, its threads the row's (texel, channel) elements — consecutive lanes, consecutive floats.  The fold is the build's
@@ -6855,6 +7136,20 @@ void launch_tex(const TexArgs &a, hipStream_t s) { launch_pass<k_tex>(a, s); }
 void launch_tex_grad(const TexArgs &a, hipStream_t s) { launch_pass<k_tex_grad>(a, s); }
 void launch_cube(const CubeArgs &a, hipStream_t s) { launch_pass<k_cube>(a, s); }
 void launch_cube_grad(const CubeArgs &a, hipStream_t s) { launch_pass<k_cube_grad>(a, s); }
+void launch_light(const LightArgs &a, hipStream_t s) { launch_pass<k_light>(a, s); }
+// with a.work: the tiles' partial sums, then k_light_fold over each frame's tiles — into gpar's rows, or (one parameter frame for
+// every frame) into the rows behind the partials and from there, frame after frame, into gpar.  Not launch_pass for the fold: its
+// grid is the rows it writes, not the set's tiles.  A shard without bands has no tiles and launches no k_light_grad; the folds run all
+// the same — a sum of no partials is +0 — so every row of gpar is WRITTEN there too
+void launch_light_grad(const LightArgs &a, float *gpar, hipStream_t s) {
+  if (!gpar) return launch_pass<k_light_grad<false>>(a, s);
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, K = SRZ_LIGHT_PAR(a.n_lights);
+  const bool shared = a.par_stride == 0u;
+  launch_pass<k_light_grad<true>>(a, s);
+  float *rows = shared ? a.work + (size_t)a.n_frames * tpf * K : gpar;
+  if (a.n_frames != 0u) hipLaunchKernelGGL(k_light_fold, dim3(a.n_frames), dim3(64), 0, s, (const float *)a.work, rows, tpf, K);
+  if (shared) hipLaunchKernelGGL(k_light_fold, dim3(1), dim3(64), 0, s, (const float *)rows, gpar, a.n_frames, K);
+}
 void launch_interp_deriv(const InterpDerivArgs &a, hipStream_t s) { launch_pass<k_interp_deriv>(a, s); }
 void launch_persp(const PerspArgs &a, hipStream_t s) { launch_pass<k_persp>(a, s); }
 void launch_persp_grad(const PerspArgs &a, hipStream_t s) { launch_pass<k_persp_grad>(a, s); }

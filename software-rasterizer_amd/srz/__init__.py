@@ -32,6 +32,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_texture_mip_levels", "srz_texture_mip_bytes", "srz_texture_mip_build", "srz_texture_mip_fold",
            "srz_frameset_interpolate_deriv", "srz_frameset_texture_mip", "srz_frameset_texture_mip_grad",
            "srz_frameset_texture_cube", "srz_frameset_texture_cube_grad",
+           "srz_frameset_light", "srz_frameset_light_work_bytes", "srz_frameset_light_grad",
            "srz_frameset_perspective", "srz_frameset_perspective_grad", "srz_frameset_interpolate_deriv_persp",
            "srz_target_create", "srz_target_destroy", "srz_target_clear", "srz_target_draw", "srz_target_read", "srz_target_read_bgr8"]
 
@@ -113,6 +114,10 @@ def lib():
         L.srz_frameset_texture_mip_grad.argtypes = abi.TEXTURE_MIP_GRAD_ARGTYPES
         L.srz_frameset_texture_cube.argtypes = abi.TEXTURE_CUBE_ARGTYPES
         L.srz_frameset_texture_cube_grad.argtypes = abi.TEXTURE_CUBE_GRAD_ARGTYPES
+        L.srz_frameset_light.argtypes = abi.LIGHT_ARGTYPES
+        L.srz_frameset_light_work_bytes.argtypes = abi.LIGHT_WORK_BYTES_ARGTYPES
+        L.srz_frameset_light_work_bytes.restype = C.c_size_t
+        L.srz_frameset_light_grad.argtypes = abi.LIGHT_GRAD_ARGTYPES
         L.srz_frameset_perspective.argtypes = abi.PERSPECTIVE_ARGTYPES
         L.srz_frameset_perspective_grad.argtypes = abi.PERSPECTIVE_GRAD_ARGTYPES
         L.srz_frameset_interpolate_deriv_persp.argtypes = abi.INTERPOLATE_DERIV_PERSP_ARGTYPES
@@ -445,6 +450,32 @@ class FrameSet:
         self.ctx._check(lib().srz_frameset_interpolate_deriv_persp(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_q_ptr), q_frames,
                                                                    q_tris, C.c_void_p(d_attr_ptr), n_ch, attr_frames, attr_tris,
                                                                    C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def light(self, d_vis_ptr, d_nrm_ptr, d_pos_ptr, d_kd_ptr, d_par_ptr, n_lights, par_frames, p, d_out_ptr, out_bytes,
+              flags=abi.FUSED_CLEAR, stream=None):
+        """Blinn-Phong under n_lights point lights for the caller's planes d_nrm, d_pos, d_kd (None / 0: albedo ones), each
+        [frame][3][local_rows][width], and the parameter block d_par [par_frames][abi.light_par(n_lights)] (eye ka ks, then per light
+        pos intensity; par_frames: 1 or the frame count) with the integer exponent p in 1 .. 256 → d_out [frame][3][local_rows][width],
+        unclamped (include/srz.h states the rule).  Pixels nobody owns are zeros with FUSED_CLEAR, else left untouched; an owner whose
+        normal has no finite positive length gets zeros.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_light(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_nrm_ptr), C.c_void_p(d_pos_ptr),
+                                                 C.c_void_p(d_kd_ptr or None), C.c_void_p(d_par_ptr), n_lights, par_frames, p,
+                                                 C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def light_work_bytes(self, n_lights):
+        """bytes of the scratch buffer light_grad needs for d_gpar; 0 for n_lights == 0 or above abi.LIGHT_MAX"""
+        return int(lib().srz_frameset_light_work_bytes(self.ctx.h, self.h, n_lights))
+
+    def light_grad(self, d_vis_ptr, d_nrm_ptr, d_pos_ptr, d_kd_ptr, d_par_ptr, n_lights, par_frames, p, d_gout_ptr, d_gnrm_ptr, d_gpos_ptr,
+                   d_gkd_ptr, d_gpar_ptr, d_work_ptr, work_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """the backward of light: d_gout [frame][3][local_rows][width] → written to d_gnrm, d_gpos, d_gkd (the planes' shape,
+        deterministic) and / or d_gpar (d_par's shape: WRITTEN, reduced in a fixed tree, bit-reproducible for a shard layout; needs
+        d_work of light_work_bytes(n_lights) bytes).  Every output pointer may be None / 0, not all; d_gkd needs d_kd.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_light_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_nrm_ptr), C.c_void_p(d_pos_ptr),
+                                                      C.c_void_p(d_kd_ptr or None), C.c_void_p(d_par_ptr), n_lights, par_frames, p,
+                                                      C.c_void_p(d_gout_ptr), C.c_void_p(d_gnrm_ptr or None), C.c_void_p(d_gpos_ptr or None),
+                                                      C.c_void_p(d_gkd_ptr or None), C.c_void_p(d_gpar_ptr or None),
+                                                      C.c_void_p(d_work_ptr or None), work_bytes, flags, _stream(stream)))
 
     def update_shading(self, frames):
         """new eye, ka, ks, p, kh, kn, lights, flags and batch shaders / textures for a set made from abi.Frame's, triangles untouched

@@ -22,6 +22,12 @@ MV_ALL = MV_FLOW | MV_DEPTH | MV_TARGET
 ATTR_MAX_CH = 64  # srz_frameset_interpolate: the most channels of one call (SRZ_ATTR_MAX_CH)
 TEX_CLAMP, TEX_WRAP = 0, 1  # srz_frameset_texture: `mode` (SRZ_TEX_CLAMP, SRZ_TEX_WRAP)
 TEX_MAX_SIZE = 16384  # srz_frameset_texture: the largest tex_w and tex_h (SRZ_TEX_MAX_SIZE)
+LIGHT_MAX = 8  # srz_frameset_light: the most lights of one call (SRZ_LIGHT_MAX)
+
+
+def light_par(n_lights):
+    """floats of one parameter frame of srz_frameset_light: eye[3] ka[3] ks[3], then n_lights x {pos[3], intensity[3]} (SRZ_LIGHT_PAR)"""
+    return 9 + 6 * n_lights
 # the prototypes of srz_frameset_texture / _texture_grad (argtypes; both return int), set on the library by srz.lib()
 TEXTURE_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                     C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
@@ -40,6 +46,10 @@ TEXTURE_MIP_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32,
 # the prototypes of srz_frameset_texture_cube / _texture_cube_grad (argtypes; both return int), set by srz.lib()
 TEXTURE_CUBE_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
 TEXTURE_CUBE_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp]
+# the prototypes of srz_frameset_light / _light_work_bytes (returns size_t) / _light_grad (argtypes), set by srz.lib()
+LIGHT_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
+LIGHT_WORK_BYTES_ARGTYPES = [_vp, _vp, _u32]
+LIGHT_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _u32, _vp]
 # the prototypes of srz_frameset_perspective / _perspective_grad / _interpolate_deriv_persp (argtypes; all return int), set by srz.lib()
 PERSPECTIVE_ARGTYPES = [_vp, _vp, _vp, _vp, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
 PERSPECTIVE_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _vp]

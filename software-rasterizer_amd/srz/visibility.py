@@ -557,6 +557,101 @@ def texture_cube(fs, vis, cube, dirs, stream=None):
     return _TextureCube.apply(cube, dirs, fs, vis, stream)
 
 
+def light_params(fs, lights, eye, ka, ks):
+    """the parameter block of light / light_grad from its pieces, with torch ops (so gradients of the block flow back to the pieces):
+    lights [L, 6] or [n_frames, L, 6] (a light: pos[3], intensity[3]), eye, ka, ks [3] or [n_frames, 3] → [1, 9 + 6 L] when every piece
+    is shared by the frames, else [n_frames, 9 + 6 L] (per frame as soon as one of them is)"""
+    if lights.dim() not in (2, 3) or lights.shape[-1] != 6 or not 1 <= lights.shape[-2] <= abi.LIGHT_MAX:
+        raise ValueError(f"light: lights must be [L, 6] or [n_frames, L, 6] with 1 <= L <= {abi.LIGHT_MAX}, got {tuple(lights.shape)}")
+    pieces = [("eye", eye), ("ka", ka), ("ks", ks)]
+    for name, t in pieces:
+        if t.dim() not in (1, 2) or t.shape[-1] != 3:
+            raise ValueError(f"light: {name} must be [3] or [n_frames, 3], got {tuple(t.shape)}")
+    per_frame = lights.dim() == 3 or any(t.dim() == 2 for _, t in pieces)
+    n = fs.n_frames if per_frame else 1
+    n_l = lights.shape[-2]
+    rows = [t.reshape(-1, 3) for _, t in pieces] + [lights.reshape(-1, 6 * n_l)]
+    for (name, _), r in zip(pieces + [("lights", lights)], rows):
+        if r.shape[0] not in (1, n):
+            raise ValueError(f"light: {name} has {r.shape[0]} frames, the set {fs.n_frames}")
+    return torch.cat([r.expand(n, r.shape[1]) for r in rows], dim=1).to(torch.float32).contiguous()
+
+
+def _light_args(fs, nrm, pos, kd, par, p):
+    """→ (nrm, pos, kd or None, par, n_lights, par_frames), checked and contiguous"""
+    shape = tuple(fs.interpolate_shape(3))
+    for name, t in (("nrm", nrm), ("pos", pos), ("kd", kd)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != shape):
+            raise ValueError(f"light: {name} must be a CUDA float32 tensor {shape}, got {tuple(t.shape)} {t.dtype}")
+    if par.dtype != torch.float32 or not par.is_cuda or par.dim() != 2 or par.shape[1] < 15 or (par.shape[1] - 9) % 6:
+        raise ValueError(f"light: par must be a CUDA float32 tensor [1 or n_frames, 9 + 6 L], got {tuple(par.shape)} {par.dtype}")
+    n_l = (par.shape[1] - 9) // 6
+    if n_l > abi.LIGHT_MAX or par.shape[0] not in (1, fs.n_frames):
+        raise ValueError(f"light: par of {par.shape[0]} frames and {n_l} lights; 1 or {fs.n_frames} frames and 1 .. {abi.LIGHT_MAX} lights are supported")
+    if int(p) != p or not 1 <= p <= 256:
+        raise ValueError(f"light: p must be an integer in 1 .. 256, got {p}")
+    return nrm.contiguous(), pos.contiguous(), None if kd is None else kd.contiguous(), par.contiguous(), n_l, par.shape[0]
+
+
+def light_grad(fs, vis, nrm, pos, kd, par, p, gout, want_gnrm=True, want_gpos=True, want_gkd=True, want_gpar=True, stream=None):
+    """the backward of light by one FrameSet.light_grad call: par is light_params' block, gout [n_frames, 3, rows, W] → (gnrm, gpos,
+    gkd, gpar), each None when not wanted (not all; gkd is None without kd): the planes are deterministic, zeros where nobody owns
+    the pixel or its normal is not lit; gpar has par's shape, reduced in a fixed tree (bit-reproducible for a shard layout).
+    stream: a raw stream handle, None = torch's current stream."""
+    want_gkd = want_gkd and kd is not None
+    if not (want_gnrm or want_gpos or want_gkd or want_gpar):
+        raise ValueError("light_grad: no gradient is asked for")
+    nrm, pos, kd, par, n_l, par_frames = _light_args(fs, nrm, pos, kd, par, p)
+    gout = gout.contiguous()
+    if tuple(gout.shape) != tuple(nrm.shape) or gout.dtype != torch.float32:
+        raise ValueError(f"light_grad: gout must be float32 {tuple(nrm.shape)}, got {tuple(gout.shape)} {gout.dtype}")
+    gnrm, gpos, gkd = (torch.empty_like(nrm) if w else None for w in (want_gnrm, want_gpos, want_gkd))
+    gpar = work = None
+    work_bytes = 0
+    if want_gpar:
+        work_bytes = fs.light_work_bytes(n_l)
+        gpar, work = torch.empty_like(par), torch.empty(max(work_bytes // 4, 1), dtype=torch.float32, device=par.device)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    fs.light_grad(vis.data_ptr(), nrm.data_ptr(), pos.data_ptr(), ptr(kd), par.data_ptr(), n_l, par_frames, int(p), gout.data_ptr(), ptr(gnrm),
+                  ptr(gpos), ptr(gkd), ptr(gpar), ptr(work), work_bytes, abi.FUSED_CLEAR, _stream_ptr(stream))
+    return gnrm, gpos, gkd, gpar
+
+
+class _Light(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, nrm, pos, kd, par, fs, vis, p, stream):
+        nrm, pos, kd, par, n_l, par_frames = _light_args(fs, nrm, pos, kd, par, p)
+        out = torch.empty(fs.interpolate_shape(3), dtype=torch.float32, device=nrm.device)
+        fs.light(vis.data_ptr(), nrm.data_ptr(), pos.data_ptr(), None if kd is None else kd.data_ptr(), par.data_ptr(), n_l, par_frames, int(p),
+                 out.data_ptr(), fs.interpolate_bytes(3), abi.FUSED_CLEAR, _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.p, ctx.stream, ctx.has_kd = fs, vis, int(p), stream, kd is not None
+        ctx.save_for_backward(nrm, pos, par, *([kd] if kd is not None else []))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        nrm, pos, par = ctx.saved_tensors[:3]
+        kd = ctx.saved_tensors[3] if ctx.has_kd else None
+        need = list(ctx.needs_input_grad[:4])
+        need[2] = need[2] and ctx.has_kd
+        grads = (None, None, None, None)
+        if any(need):  # one call, asking only for what is needed
+            grads = light_grad(ctx.fs, ctx.vis, nrm, pos, kd, par, ctx.p, gout, need[0], need[1], need[2], need[3], ctx.stream)
+        return (*grads, None, None, None, None)
+
+
+def light(fs, vis, nrm, pos, kd, lights, eye, ka, ks, p, stream=None):
+    """Blinn-Phong under point lights for the caller's own planes under a visibility buffer `vis` of FrameSet `fs`: nrm, pos and kd (or
+    None: albedo ones) are [n_frames, 3, rows, W] CUDA float32 — interpolate's normals and positions, texture's albedo —, lights is
+    [L, 6] or [n_frames, L, 6] (pos[3], intensity[3]; L <= abi.LIGHT_MAX), eye, ka, ks [3] or [n_frames, 3], p an integer exponent in
+    1 .. 256 → [n_frames, 3, rows, W] float32: true 1 / r² attenuation, a normalised half vector, no clamp, zeros where nobody owns the
+    pixel or its normal has no finite positive length (FrameSet.light; include/srz.h states the rule — nothing of the built-in
+    shaders).  Differentiable with respect to nrm, pos, kd (deterministic planes) and to lights, eye, ka, ks (sums over the pixels in
+    a fixed tree: bit-reproducible), not to p.  Backward is one light_grad call that asks only for the outputs some input needs.
+    stream: a raw stream handle, None = torch's current stream."""
+    return _Light.apply(nrm, pos, kd, light_params(fs, lights, eye, ka, ks), fs, vis, p, stream)
+
+
 def interpolate_deriv(fs, vis, attr, stream=None):
     """the screen-space derivatives of interpolate(fs, vis, attr): attr as interpolate takes it with C <= abi.ATTR_MAX_CH // 2 →
     [n_frames, 2 C, rows, W] float32, plane 2 ch the change of channel ch per one-pixel step in x, plane 2 ch + 1 in y — constants of
