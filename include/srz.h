@@ -67,6 +67,8 @@ extern "C" {
  *      srz_frameset_texture_cube_grad
  *      (additive, same version) Blinn-Phong lighting pass over a visibility buffer, with gradients srz_frameset_light /
  *      srz_frameset_light_grad / srz_frameset_light_work_bytes
+ *      (additive, same version) shadow-map lookup over a visibility buffer, with gradients srz_frameset_shadow /
+ *      srz_frameset_shadow_grad
  */
 #define SRZ_ABI_VERSION 7
 
@@ -801,6 +803,64 @@ size_t srz_frameset_light_work_bytes(srz_ctx *ctx, srz_frameset *fs, uint32_t n_
 int srz_frameset_light_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos, const void *d_kd,
                             const float *d_par, uint32_t n_lights, uint32_t par_frames, uint32_t p, const void *d_gout, void *d_gnrm,
                             void *d_gpos, void *d_gkd, float *d_gpar, void *d_work, size_t work_bytes, uint32_t flags, void *stream);
+/* SHADOW-MAP LOOKUP over a visibility buffer, and its gradients: PERCENTAGE-CLOSER FILTERING of a float32 depth map of the caller's
+ * own at caller coordinates — the four texels around (sx, sy) are each COMPARED with the pixel's depth sd, and the four results are
+ * blended bilinearly — and the backward of that, to the map and to the coordinates.  `width` turns the hard depth test into a linear
+ * ramp, so that a gradient exists in depth.  The pieces a shadow needs besides are passes that exist: a light's view is another
+ * frameset, plane 0 of ITS visibility buffer is the depth map (+inf where nobody is: lit), srz_frameset_position_grad with d_gz
+ * makes that map differentiable in the occluders' positions, and the light set's screen positions, read as a [T][3][3] per-corner attribute and run through
+ * srz_frameset_interpolate over the CAMERA set, are every camera pixel's coordinates in the map.
+ * d_vis: a visibility buffer of THIS (the camera's) set on this ctx's shard.  d_sc: [frame][3][local_rows][width] float32 — sx, sy,
+ * sd: srz_frameset_interpolate's output at three channels.  sx and sy are in map texel units with the texel CENTRES ON THE INTEGERS:
+ * a render samples a pixel at its integer corner, so texel (x, y) of a depth plane is the depth at screen (x, y) and fx = sx, with no
+ * -0.5 (srz_frameset_texture's grid has the centres at i + 0.5).  sd is in the map's depth units.  d_map and d_gmap:
+ * [map_frames][map_h][map_w] float32, dense, 4-byte aligned; map_frames is 1 (every frame looks up the same map) or the set's frame
+ * count; 1 <= map_w, map_h <= SRZ_TEX_MAX_SIZE.  The map is WHOLE, never band-sharded: on a sharded ctx the caller gathers it, as a
+ * texture.  bias, width: host floats, finite, width >= 0 (0: the hard test); neither gets a gradient.  d_out and d_gout:
+ * [frame][1][local_rows][width] float32, srz_frameset_interpolate_bytes(1) bytes; d_gsc: d_sc's shape.  Owner and nobody, the fused
+ * clear (a nobody pixel's words of d_out and d_gsc are 0 with SRZ_FUSED_CLEAR (frame flags | flags), else left untouched), band
+ * sharding (each rank adds the partial sums of its own bands to d_gmap), local_rows, stream semantics, asynchrony and the 16-byte
+ * alignment of the visibility buffer and every plane buffer (d_sc, d_out, d_gout, d_gsc): all as srz_frameset_texture.  The words of
+ * d_sc and d_gout at nobody's pixels never reach a result.
+ * THE RULE, all of it float32, nothing fused except where fmaf is written, `/` the IEEE division, always the exact arithmetic
+ * (SRZ_OPT_APPROX_SHADE has no effect).  Per owned pixel:
+ *   unsampled: sx, sy or sd not finite (!(fabsf(s) < INFINITY)) -> out = 1.0f (written: the pixel has an owner; no occluder is
+ *              known: lit), gsc = (0, 0, 0), no add
+ *   per axis — shown for x with sx and W = map_w; y with sy and H = map_h likewise:
+ *     in_x = sx > -1.0f && sx < (float)W;   fx = fminf(fmaxf(sx, -1.0f), (float)W)
+ *     x0f = floorf(fx);  tx = fx - x0f;  x0 = (int)x0f;  x1 = x0 + 1                  (x0 in [-1, W], x1 in [0, W + 1])
+ *   corner (r, c) OUTSIDE the map (x_c < 0 || x_c >= W || y_r < 0 || y_r >= H): v = 1.0f, not moving; never read, never added to
+ *     (beyond the map nothing is known to occlude: the result fades to lit across the map's last texel)
+ *   corner inside:  m = map[fm][y_r][x_c] (fm = 0 when map_frames == 1);  e = (m + bias) - sd
+ *     width == 0:  v = e >= 0.0f ? 1.0f : 0.0f;  not moving                            (a NaN gives 0; m = +inf gives 1)
+ *     width  > 0:  q = e / width + 0.5f;  v = fminf(fmaxf(q, 0.0f), 1.0f) (a NaN gives 0);  moving = q > 0.0f && q < 1.0f
+ * FORWARD, deterministic, bit for bit:
+ *   top = fmaf(tx, v01 - v00, v00);  bot = fmaf(tx, v11 - v10, v10);  out = fmaf(ty, bot - top, top)
+ * BACKWARD: d_gout, the same d_sc, d_map and d_vis; at least one of d_gmap and d_gsc is non-null.  With g = gout:
+ *   gsx = in_x ? g * fmaf(ty, (v11 - v10) - (v01 - v00), v01 - v00) : 0.0f;   gsy = in_y ? g * (bot - top) : 0.0f
+ *   w00 = (1.0f - tx) * (1.0f - ty), w01 = tx * (1.0f - ty), w10 = (1.0f - tx) * ty, w11 = tx * ty
+ *   d_rc = moving_rc ? (w_rc * g) / width : 0.0f;   gsd = -(((d00 + d01) + d10) + d11)
+ *   d_gsc = (gsx, gsy, gsd): per pixel, deterministic, bit for bit; the layout srz_frameset_interpolate_grad takes as d_gout at
+ *   n_ch = 3 (the hard test leaves gsd = -0.0f: the sum of four +0 terms, negated).
+ *   d_gmap: for every MOVING corner of every sampled pixel d_rc is ADDED to gmap[fm][y_r][x_c] (two corners of one pixel never
+ *   coincide: x1 = x0 + 1 always).  width == 0 is allowed and adds nothing.  The caller zeroes the buffer, or accumulates over
+ *   several calls.  THE ORDER OF THE ADDS IS UNSPECIFIED, each add rounds, so d_gmap is NOT BIT-REPRODUCIBLE between launches, like
+ *   d_gtex: with n contributing adds an element lies within n 2^-24 / (1 - n 2^-24) * sum |term| of the exact sum of the float32
+ *   terms; an element with one contributing add is exact.  The adds are hardware float atomics: d_gmap must be ordinary
+ *   (coarse-grained) device memory.
+ * Every conversion to an integer follows the float clamp, and a corner is touched only where its own coordinates lie inside the map:
+ * no value of d_sc makes a pass read or write outside its buffers.  Non-finite texels and gradients propagate as IEEE has them
+ * through the comparisons above.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set, d_vis, d_sc, d_map, d_out (forward), d_gout
+ * (backward), or both of d_gmap and d_gsc; map_w or map_h 0 or above SRZ_TEX_MAX_SIZE; map_frames not 1 or the frame count; a bias or
+ * width that is not finite; width < 0; a short out_bytes; a misaligned pointer; any bit of `flags` but SRZ_FUSED_CLEAR; an output that
+ * overlaps an input (d_out with d_vis, d_sc or d_map; d_gmap or d_gsc with d_vis, d_sc, d_gout or d_map) or the other output. */
+int srz_frameset_shadow(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_sc, const float *d_map, uint32_t map_w,
+                        uint32_t map_h, uint32_t map_frames, float bias, float width, void *d_out, size_t out_bytes, uint32_t flags,
+                        void *stream);
+int srz_frameset_shadow_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_sc, const void *d_gout, const float *d_map,
+                             uint32_t map_w, uint32_t map_h, uint32_t map_frames, float bias, float width, float *d_gmap, void *d_gsc,
+                             uint32_t flags, void *stream);
 /* MIPMAPPED TEXTURE SAMPLING over a visibility buffer, and its gradients: the TRILINEAR lookup over a mip pyramid of the caller's
  * texture that goes with the bilinear lookup above, its level chosen from the screen-space derivatives of uv.  Three pieces: the
  * pyramid (build, and fold: its backward), the derivatives of an interpolated attribute, the lookup and its backward.  All of it

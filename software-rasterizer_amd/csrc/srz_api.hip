@@ -937,6 +937,31 @@ LightArgs light_args(const srz_frameset *fs, const void *d_vis, const void *d_nr
   a.flags_or = flags;
   return a;
 }
+// what srz_frameset_shadow and _shadow_grad check alike (check_cube's shape); the map's bytes in *map_bytes
+int check_shadow(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, uint32_t map_w, uint32_t map_h, uint32_t map_frames, float bias,
+                 float width, uint32_t flags, size_t *map_bytes) {
+  if (map_w == 0u || map_w > SRZ_TEX_MAX_SIZE || map_h == 0u || map_h > SRZ_TEX_MAX_SIZE)
+    return fail(ctx, SRZ_E_INVALID, fn + ": map_w and map_h must be 1 .. SRZ_TEX_MAX_SIZE");
+  if (!std::isfinite(bias) || !std::isfinite(width)) return fail(ctx, SRZ_E_INVALID, fn + ": bias and width must be finite");
+  if (width < 0.0f) return fail(ctx, SRZ_E_INVALID, fn + ": width must be >= 0 (0: the hard test)");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  if (map_frames != 1u && map_frames != (uint32_t)fs->n_frames)
+    return fail(ctx, SRZ_E_INVALID, fn + ": map_frames must be 1 or the set's frame count");
+  *map_bytes = (size_t)map_frames * map_h * map_w * sizeof(float);
+  return SRZ_OK;
+}
+ShadowArgs shadow_args(const srz_frameset *fs, const void *d_vis, const void *d_sc, const float *d_map, uint32_t map_w, uint32_t map_h,
+                       uint32_t map_frames, float bias, float width, uint32_t out_planes, void *d_out, uint32_t flags) {
+  ShadowArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  a.sc = (const float *)d_sc, a.map = d_map;
+  a.vis_stride = 4ull * plane, a.frame_stride = out_planes * plane, a.sc_stride = 3ull * plane, a.gout_stride = plane;
+  a.map_frame_stride = map_frames == 1u ? 0ull : (uint64_t)map_h * map_w;
+  a.map_w = map_w, a.map_h = map_h, a.bias = bias, a.width = width;
+  a.flags_or = flags;
+  return a;
+}
 constexpr uint32_t MIP_MAX_FRAMES = 65536u;
 // what srz_texture_mip_build and _mip_fold check alike (no set: tex_frames is any count up to MIP_MAX_FRAMES)
 int check_mip(srz_ctx *ctx, const std::string &fn, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels,
@@ -2066,6 +2091,55 @@ int srz_frameset_texture_cube_grad(srz_ctx *ctx, srz_frameset *fs, const void *d
   CubeArgs a = cube_args(fs, d_vis, d_dir, d_tex, n, n_ch, tex_frames, 3u, d_gdir, flags);
   a.gout = (const float *)d_gout, a.gtex = d_gtex;
   launch_cube_grad(a, s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_shadow(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_sc, const float *d_map, uint32_t map_w,
+                        uint32_t map_h, uint32_t map_frames, float bias, float width, void *d_out, size_t out_bytes, uint32_t flags,
+                        void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_shadow");
+  if (!fs || !d_vis || !d_sc || !d_map || !d_out)
+    return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_sc ? "d_sc" : !d_map ? "d_map" : "d_out"));
+  size_t map_bytes = 0;
+  if (int rc = check_shadow(ctx, fs, fn, map_w, map_h, map_frames, bias, width, flags, &map_bytes)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, 1u), sc_bytes = srz_frameset_interpolate_bytes(ctx, fs, 3u);
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": out_bytes is too small for d_out");
+  if (!aligned<16>({d_vis, d_sc, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_sc, d_out) must be 16-byte aligned");
+  if (!aligned<4>({d_map})) return fail(ctx, SRZ_E_INVALID, fn + ": d_map must be 4-byte aligned");
+  if (ranges_overlap({d_out, need}, {d_vis, vis_bytes}) || ranges_overlap({d_out, need}, {d_sc, sc_bytes}) ||
+      ranges_overlap({d_out, need}, {d_map, map_bytes}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": d_out overlaps d_vis, d_sc or d_map");
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_texture)
+  launch_shadow(shadow_args(fs, d_vis, d_sc, d_map, map_w, map_h, map_frames, bias, width, 1u, d_out, flags), s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_shadow_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_sc, const void *d_gout, const float *d_map,
+                             uint32_t map_w, uint32_t map_h, uint32_t map_frames, float bias, float width, float *d_gmap, void *d_gsc,
+                             uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_shadow_grad");
+  if (!fs || !d_vis || !d_sc || !d_gout || !d_map)
+    return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_sc ? "d_sc" : !d_gout ? "d_gout" : "d_map"));
+  if (!d_gmap && !d_gsc) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gmap nor d_gsc is asked for");
+  size_t map_bytes = 0;
+  if (int rc = check_shadow(ctx, fs, fn, map_w, map_h, map_frames, bias, width, flags, &map_bytes)) return rc;
+  const size_t gout_bytes = srz_frameset_interpolate_bytes(ctx, fs, 1u), sc_bytes = srz_frameset_interpolate_bytes(ctx, fs, 3u);
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (!aligned<16>({d_vis, d_sc, d_gout, d_gsc}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_sc, d_gout, d_gsc) must be 16-byte aligned");
+  if (!aligned<4>({d_map, d_gmap})) return fail(ctx, SRZ_E_INVALID, fn + ": d_map and d_gmap must be 4-byte aligned");
+  if (int rc = check_grad_overlap(ctx, fn + " (d_gmap, d_gsc against d_vis, d_sc, d_gout, d_map)", {{d_gmap, map_bytes}, {d_gsc, sc_bytes}},
+                                  {{d_vis, vis_bytes}, {d_sc, sc_bytes}, {d_gout, gout_bytes}, {d_map, map_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_texture)
+  ShadowArgs a = shadow_args(fs, d_vis, d_sc, d_map, map_w, map_h, map_frames, bias, width, 3u, d_gsc, flags);
+  a.gout = (const float *)d_gout, a.gmap = d_gmap;
+  launch_shadow_grad(a, s);
   return end_pass(ctx);
 }
 

@@ -478,6 +478,33 @@ struct LightArgs {
 };
 void launch_light(const LightArgs &a, hipStream_t s);
 void launch_light_grad(const LightArgs &a, float *gpar, hipStream_t s);
+// srz_frameset_shadow / _shadow_grad: a float depth map of the caller's [map frame][row][column] compared and filtered at the
+// coordinate planes sc [frame][3][local_rows][width] (sx, sy in texels, sd in the map's depth units) under a visibility buffer
+// (k_shadow), and the gradients of that with respect to the map (gmap, added into) and to the coordinates (k_shadow_grad).  vis as
+// above; `out` is the forward's [frame][1][local_rows][width] or the backward's gsc [frame][3][local_rows][width] (may be null
+// there).  The host has checked 1 <= map_w, map_h <= SRZ_TEX_MAX_SIZE (a texel's index stays below 2^28), bias and width finite,
+// width >= 0 (0: the hard test)
+struct ShadowArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *sc;
+  const float *map;
+  float *out;
+  const float *gout;         // backward: [frame][1][local_rows][width]
+  float *gmap;               // backward: map's shape, added into (may be null)
+  uint64_t vis_stride;       // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride;     // floats per frame in out
+  uint64_t sc_stride;        // floats per frame in sc = 3 * local_rows * width
+  uint64_t gout_stride;      // floats per frame in gout = local_rows * width
+  uint64_t map_frame_stride; // floats per frame in map / gmap = map_h * map_w; 0: one map for every frame
+  uint32_t map_w, map_h;
+  float bias, width;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_shadow(const ShadowArgs &a, hipStream_t s);
+void launch_shadow_grad(const ShadowArgs &a, hipStream_t s);
 // THE MIP PYRAMID of a caller texture (include/srz.h states the geometry): level l of a tex_w x tex_h texture is
 // max(1, tex_w >> l) x max(1, tex_h >> l) — every level that exists came from an even (or one-texel) extent, so the shifts are the
 // halvings — and the levels 1 .. n_levels - 1 lie one after another, each [tex_frames][h_l][w_l][n_ch].  Host and device share these.

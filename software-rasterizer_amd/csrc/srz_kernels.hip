@@ -6515,6 +6515,218 @@ __global__ __launch_bounds__(256) void k_tex_mip_grad(TexMipArgs a) {
 }
 
 // ================================================================================================================
+// k_shadow — A CALLER'S DEPTH MAP COMPARED AND FILTERED OVER A VISIBILITY BUFFER (srz_frameset_shadow, include/srz.h states the rule):
+// percentage-closer filtering of a float map [map frame][row][column] at the coordinate planes sx, sy, sd interpolate wrote for a
+// three-channel attribute: the four texels around (sx, sy) are each compared with sd — the hard test, or with width > 0 a linear ramp
+// — and the four results are blended bilinearly.  k_cube's shape on the passes' helpers: pass_walk, quad_ids, the three coordinate
+// words only for a quad with an owner (quad_load), quad_store_owned; 4 pixels of a row per thread; no LDS, no barrier.  bias, width
+// and the map's extents are kernel arguments (wave-uniform), hard or soft ONE wave-uniform branch per corner.  The four taps of a
+// pixel are two row-adjacent pairs, each pair TWO 4-BYTE LOADS: one unaligned 8-byte load would need both texels of the pair inside
+// the map, and at x0 = -1 and x1 = map_w only one of them is — the pair would need the very per-texel branch it was to save.
+// Every float -> int conversion follows the float clamp to [-1, map_w] (and [-1, map_h]); a corner is read (and, in the backward,
+// added to) only behind the unsigned compare of its own coordinates with the map's extents: no value of the planes leaves the map.
+// shadow_px (a sampled pixel's fractions, corner values and moving corners) is the rule's text; k_shadow and k_shadow_grad both go
+// through it, so the backward differentiates the very words the forward computed.
+// ================================================================================================================
+struct ShadowPx {
+  float v[4];      // the corners' values v00, v01, v10, v11 (corner r * 2 + c is texel (y0 + r, x0 + c)); outside the map: 1
+  float tx, ty;
+  int base;        // y0 * map_w + x0 with x0 in [-1, map_w], y0 in [-1, map_h]: corner (r, c) is texel base + r * map_w + c, IF inside
+  uint32_t moving; // bit r * 2 + c: the corner lies inside the map and on the ramp (0 < r < 1): its texel and sd move the sample
+  bool in_x, in_y; // the coordinate lies strictly inside (-1, map_w) / (-1, map_h) (else its derivative is 0)
+};
+// one axis of the rule: coordinate s in texel units over n texels (centres on the integers) -> the first texel coordinate, in
+// [-1, n], the fraction, and whether s moves the sample
+__device__ __forceinline__ void shadow_axis(float s, uint32_t n, int &i0, float &t, bool &in) {
+  const float nf = (float)n;
+  in = s > -1.0f && s < nf;
+  const float fx = __builtin_fminf(__builtin_fmaxf(s, -1.0f), nf);
+  const float f0 = __builtin_floorf(fx);
+  t = fx - f0;
+  i0 = (int)f0;
+}
+// the pixel at (sx, sy, sd) of map `map`; false: not sampled (a coordinate not finite)
+__device__ __forceinline__ bool shadow_px(const ShadowArgs &a, const SRZ_CAS float *map, float sx, float sy, float sd, ShadowPx &p) {
+  if (!tex_finite(sx) || !tex_finite(sy) || !tex_finite(sd)) return false;
+  const int W = (int)a.map_w, H = (int)a.map_h;
+  int x0, y0;
+  shadow_axis(sx, a.map_w, x0, p.tx, p.in_x);
+  shadow_axis(sy, a.map_h, y0, p.ty, p.in_y);
+  p.base = y0 * W + x0;
+  p.moving = 0u;
+  const bool soft = a.width > 0.0f;
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      float v = 1.0f;
+      if ((unsigned)(x0 + c) < (unsigned)W && (unsigned)(y0 + r) < (unsigned)H) {
+        const float e = (map[p.base + r * W + c] + a.bias) - sd;
+        if (soft) {
+          const float q = e / a.width + 0.5f;
+          v = __builtin_fminf(__builtin_fmaxf(q, 0.0f), 1.0f); // (NaN -> 0)
+          if (q > 0.0f && q < 1.0f) p.moving |= 1u << (r * 2 + c);
+        } else {
+          v = e >= 0.0f ? 1.0f : 0.0f;
+        }
+      }
+      p.v[r * 2 + c] = v;
+    }
+  return true;
+}
+// what k_shadow and k_shadow_grad do alike: the owners, the coordinates of a quad with an owner, the sampled pixels -> `own` and
+// `smp`, one bit per pixel
+__device__ __forceinline__ void shadow_quad(const ShadowArgs &a, const PassTile &t, ShadowPx (&px)[4], uint32_t &own, uint32_t &smp) {
+  uint32_t id[4];
+  own = quad_ids(t, a.vis + (size_t)t.f * a.vis_stride + t.poff, id), smp = 0u;
+  if (own == 0u) return;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 s[3] = {zero4, zero4, zero4};
+  quad_load(a.sc + (size_t)t.f * a.sc_stride + t.poff, t.rc.plane, s, t.whole, t.x4, t.rc.tx1);
+  const SRZ_CAS float *map = as_const(a.map) + (size_t)t.f * a.map_frame_stride;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (!(own & (1u << k))) continue;
+    if (shadow_px(a, map, quad_at(s[0], k), quad_at(s[1], k), quad_at(s[2], k), px[k])) smp |= 1u << k;
+  }
+}
+__global__ __launch_bounds__(256) void k_shadow(ShadowArgs a) {
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool fused = t.fused(a.flags_or);
+    ShadowPx px[4];
+    uint32_t own, smp;
+    shadow_quad(a, t, px, own, smp);
+    if (own == 0u && !fused) return;
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f); // nobody: zeros (stored with the fused clear only)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (!(own & (1u << k))) continue;
+      float r = 1.0f; // an owner that is not sampled: no occluder known, lit
+      if (smp & (1u << k)) {
+        const ShadowPx &p = px[k];
+        const float top = fmaf_(p.tx, p.v[1] - p.v[0], p.v[0]), bot = fmaf_(p.tx, p.v[3] - p.v[2], p.v[2]);
+        r = fmaf_(p.ty, bot - top, top);
+      }
+      quad_at(o, k) = r;
+    }
+    quad_store_owned(t.out, t, {o}, fused, own);
+  });
+}
+
+// ================================================================================================================
+// k_shadow_grad — THE BACKWARD OF k_shadow (srz_frameset_shadow_grad): gout -> the gradient planes of sx, sy, sd (gsc: per pixel,
+// from registers, deterministic) and, WANT_MAP, the map's gradient: per MOVING corner one add (w[corner] * gout) / width into gmap.
+// The planes-only build has no LDS, no shuffle and no barrier (k_light_grad<false>'s precedent): a call that does not ask for gmap
+// pays for no table.  The WANT_MAP build is k_tex_grad's structure at one channel on the passes' helpers (pass_walk<true>: every
+// thread of the workgroup reaches every barrier, one outside the frame samples nothing): the tile's open-addressed table of distinct
+// texels in LDS (ShadowTable: TexTable's fields with ONE value per slot, 24 KB, not ATTR_CHUNK — 48 KB would halve the workgroups a
+// CU holds — keyed on y * map_w + x + 1), the slots of the moving corners found first, LDS float adds, the dense flush with
+// global_atomic_add_f32, a corner without a slot adding straight to memory.  A tile without a moving corner (every tile of a hard
+// call; the lit and the fully shadowed tiles of a soft one) skips the table behind one __syncthreads_or, as k_light_grad does.
+// (sg_slot and sg_add are COPIES of tg_slot and tg_add, the flush of k_tex_grad's step 4: shared helpers have moved k_tex_grad's
+// registers before (k_tex_mip_grad's note); a fix goes into all of them)
+// ================================================================================================================
+struct ShadowTable {
+  uint32_t key[TG_SLOTS];  // texel index + 1; 0: free
+  uint32_t used[TG_SLOTS]; // the slots taken, in arrival order
+  uint32_t n_used;
+  float val[TG_SLOTS];
+};
+__device__ __forceinline__ uint32_t sg_slot(ShadowTable &tb, uint32_t idx) {
+  const uint32_t key = idx + 1u; // (idx < SRZ_TEX_MAX_SIZE^2 = 2^28)
+  uint32_t h = (key * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
+  for (uint32_t p = 0; p < TG_PROBES; ++p) {
+    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
+    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
+    if (old == 0u || old == key) return h;
+    h = (h + 1u) & (TG_SLOTS - 1u);
+  }
+  return TG_NONE;
+}
+__device__ __forceinline__ void sg_add(ShadowTable &tb, uint32_t slot, float *gmap, uint32_t idx, float v) {
+  if (slot != TG_NONE) lds_add(&tb.val[slot], v);
+  else global_add(gmap + idx, v);
+}
+template <bool WANT_MAP> __device__ __forceinline__ void shadow_grad_body(const ShadowArgs &a, ShadowTable *tb) {
+  const uint32_t tid = threadIdx.x;
+  const bool want_sc = a.out != nullptr;
+  if (WANT_MAP) {
+    for (uint32_t i = tid; i < TG_SLOTS; i += 256) tb->key[i] = 0u, tb->val[i] = 0.0f;
+    if (tid == 0) tb->n_used = 0u;
+    __syncthreads();
+  }
+  pass_walk<WANT_MAP>(a, [&](const PassTile &t) { // (WANT_MAP: a thread outside the frame owns nothing, and still meets the barriers)
+    const bool fused = t.fused(a.flags_or);
+    // ---- 1. owners, coordinates, the sampled pixels; gout of a quad with a sampled pixel
+    ShadowPx px[4];
+    uint32_t own, smp;
+    shadow_quad(a, t, px, own, smp);
+    if (!WANT_MAP && own == 0u && !fused) return;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 g[1] = {zero4};
+    if (smp != 0u) quad_load(a.gout + (size_t)t.f * a.gout_stride + t.poff, t.rc.plane, g, t.whole, t.x4, t.rc.tx1);
+    // ---- 2. per sampled pixel: gsx, gsy from the corner values, the moving corners' terms d_rc and gsd = -(their sum)
+    float4 gs[3] = {zero4, zero4, zero4};
+    float d[4][4];
+    uint32_t mov = 0u; // the thread's moving corners, bit k * 4 + corner
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      d[k][0] = d[k][1] = d[k][2] = d[k][3] = 0.0f;
+      if (!(smp & (1u << k))) continue;
+      const ShadowPx &p = px[k];
+      const float gk = quad_at(g[0], k);
+      const float top = fmaf_(p.tx, p.v[1] - p.v[0], p.v[0]), bot = fmaf_(p.tx, p.v[3] - p.v[2], p.v[2]);
+      quad_at(gs[0], k) = p.in_x ? gk * fmaf_(p.ty, (p.v[3] - p.v[2]) - (p.v[1] - p.v[0]), p.v[1] - p.v[0]) : 0.0f;
+      quad_at(gs[1], k) = p.in_y ? gk * (bot - top) : 0.0f;
+      const float w[4] = {(1.0f - p.tx) * (1.0f - p.ty), p.tx * (1.0f - p.ty), (1.0f - p.tx) * p.ty, p.tx * p.ty};
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (p.moving & (1u << c)) d[k][c] = (w[c] * gk) / a.width; // (moving: width > 0)
+      quad_at(gs[2], k) = -(((d[k][0] + d[k][1]) + d[k][2]) + d[k][3]);
+      mov |= p.moving << (4 * k);
+    }
+    if (want_sc && t.inside && (own != 0u || fused)) quad_store_owned(t.out, t, gs, fused, own);
+    if (WANT_MAP) {
+      // ---- 3. the tile's moving corners through the table into gmap; a tile without one is done
+      if (!__syncthreads_or(mov != 0u)) return;
+      float *gmap = a.gmap + (size_t)t.f * a.map_frame_stride;
+      const int W = (int)a.map_w;
+      uint32_t slot[4][4] = {};
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (mov & (1u << (4 * k + c))) slot[k][c] = sg_slot(*tb, (uint32_t)(px[k].base + (c >> 1) * W + (c & 1)));
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (mov & (1u << (4 * k + c))) sg_add(*tb, slot[k][c], gmap, (uint32_t)(px[k].base + (c >> 1) * W + (c & 1)), d[k][c]);
+      // ---- 4. the table's values into memory, texel after texel, and the tile's keys go (k_tex_grad's step 4 and its release)
+      __syncthreads();
+      const uint32_t n_used = tb->n_used;
+      for (uint32_t i = tid; i < n_used; i += 256) {
+        const uint32_t s = tb->used[i];
+        const float v = tb->val[s];
+        global_add(gmap + (tb->key[s] - 1u), v);
+        tb->val[s] = 0.0f, tb->key[s] = 0u;
+      }
+      __syncthreads();
+      if (tid == 0) tb->n_used = 0u;
+      __syncthreads();
+    }
+  });
+}
+template <bool WANT_MAP> __global__ __launch_bounds__(256) void k_shadow_grad(ShadowArgs a) {
+  if constexpr (WANT_MAP) {
+    __shared__ ShadowTable tb;
+    shadow_grad_body<true>(a, &tb);
+  } else {
+    shadow_grad_body<false>(a, nullptr);
+  }
+}
+
+// ================================================================================================================
 // k_resolve8 — display()'s resolve (src/Render.cpp:61-62): cv::merge(planes 0,1,2) + convertTo(CV_8UC3) =
 // saturate_cast<uchar>(cvRound(v)): round half to even, clamp to [0,255]; NaN → 0.  4 pixels per thread: three 16-byte
 // plane reads → 12 output bytes (three dword stores).
@@ -7149,6 +7361,12 @@ void launch_light_grad(const LightArgs &a, float *gpar, hipStream_t s) {
   float *rows = shared ? a.work + (size_t)a.n_frames * tpf * K : gpar;
   if (a.n_frames != 0u) hipLaunchKernelGGL(k_light_fold, dim3(a.n_frames), dim3(64), 0, s, (const float *)a.work, rows, tpf, K);
   if (shared) hipLaunchKernelGGL(k_light_fold, dim3(1), dim3(64), 0, s, (const float *)rows, gpar, a.n_frames, K);
+}
+void launch_shadow(const ShadowArgs &a, hipStream_t s) { launch_pass<k_shadow>(a, s); }
+// (without gmap: the build that has no table)
+void launch_shadow_grad(const ShadowArgs &a, hipStream_t s) {
+  if (a.gmap) launch_pass<k_shadow_grad<true>>(a, s);
+  else launch_pass<k_shadow_grad<false>>(a, s);
 }
 void launch_interp_deriv(const InterpDerivArgs &a, hipStream_t s) { launch_pass<k_interp_deriv>(a, s); }
 void launch_persp(const PerspArgs &a, hipStream_t s) { launch_pass<k_persp>(a, s); }

@@ -33,6 +33,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_interpolate_deriv", "srz_frameset_texture_mip", "srz_frameset_texture_mip_grad",
            "srz_frameset_texture_cube", "srz_frameset_texture_cube_grad",
            "srz_frameset_light", "srz_frameset_light_work_bytes", "srz_frameset_light_grad",
+           "srz_frameset_shadow", "srz_frameset_shadow_grad",
            "srz_frameset_perspective", "srz_frameset_perspective_grad", "srz_frameset_interpolate_deriv_persp",
            "srz_target_create", "srz_target_destroy", "srz_target_clear", "srz_target_draw", "srz_target_read", "srz_target_read_bgr8"]
 
@@ -118,6 +119,8 @@ def lib():
         L.srz_frameset_light_work_bytes.argtypes = abi.LIGHT_WORK_BYTES_ARGTYPES
         L.srz_frameset_light_work_bytes.restype = C.c_size_t
         L.srz_frameset_light_grad.argtypes = abi.LIGHT_GRAD_ARGTYPES
+        L.srz_frameset_shadow.argtypes = abi.SHADOW_ARGTYPES
+        L.srz_frameset_shadow_grad.argtypes = abi.SHADOW_GRAD_ARGTYPES
         L.srz_frameset_perspective.argtypes = abi.PERSPECTIVE_ARGTYPES
         L.srz_frameset_perspective_grad.argtypes = abi.PERSPECTIVE_GRAD_ARGTYPES
         L.srz_frameset_interpolate_deriv_persp.argtypes = abi.INTERPOLATE_DERIV_PERSP_ARGTYPES
@@ -420,6 +423,27 @@ class FrameSet:
                                                              C.c_void_p(d_gout_ptr), C.c_void_p(d_tex_ptr or None), n, n_ch, tex_frames,
                                                              C.c_void_p(d_gtex_ptr or None), C.c_void_p(d_gdir_ptr or None), flags,
                                                              _stream(stream)))
+
+    def shadow(self, d_vis_ptr, d_sc_ptr, d_map_ptr, map_w, map_h, map_frames, bias, width, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR,
+               stream=None):
+        """percentage-closer filtering of the caller's float32 depth map [map_frames][map_h][map_w] (map_frames: 1 or the frame count;
+        whole, never band-sharded) at the coordinate planes d_sc [frame][3][local_rows][width] — sx, sy in map texels with the texel
+        centres on the integers, sd in the map's depth units: interpolate's of a three-channel attribute — under a visibility buffer
+        of this (the camera's) set → d_out [frame][1][local_rows][width], 1 lit .. 0 shadowed (include/srz.h states the rule).
+        bias, width: finite floats, width >= 0; 0 is the hard test, above it a linear ramp of that width in depth.  Pixels nobody owns
+        are zeros with FUSED_CLEAR, else left untouched; an owner whose coordinates are not finite gets 1.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_shadow(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_sc_ptr), C.c_void_p(d_map_ptr), map_w,
+                                                  map_h, map_frames, bias, width, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def shadow_grad(self, d_vis_ptr, d_sc_ptr, d_gout_ptr, d_map_ptr, map_w, map_h, map_frames, bias, width, d_gmap_ptr, d_gsc_ptr,
+                    flags=abi.FUSED_CLEAR, stream=None):
+        """the backward of shadow: d_gout [frame][1][local_rows][width] → ADDED into d_gmap (the map's shape; only corners on the ramp
+        add, none with width == 0; the order of the adds is unspecified: not bit-reproducible) and / or written to d_gsc
+        [frame][3][local_rows][width] (the gradient with respect to sx, sy, sd, deterministic; the layout interpolate_grad takes as
+        d_gout at n_ch = 3).  Either output pointer may be None / 0, not both.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_shadow_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_sc_ptr), C.c_void_p(d_gout_ptr),
+                                                       C.c_void_p(d_map_ptr), map_w, map_h, map_frames, bias, width,
+                                                       C.c_void_p(d_gmap_ptr or None), C.c_void_p(d_gsc_ptr or None), flags, _stream(stream)))
 
     def perspective(self, d_vis_ptr, d_q_ptr, q_frames, q_tris, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
         """a visibility buffer of this set with its screen-linear alpha, beta rewritten into the PERSPECTIVE-CORRECT alpha', beta', from

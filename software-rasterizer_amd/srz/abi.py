@@ -50,6 +50,9 @@ TEXTURE_CUBE_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _v
 LIGHT_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
 LIGHT_WORK_BYTES_ARGTYPES = [_vp, _vp, _u32]
 LIGHT_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _u32, _vp]
+# the prototypes of srz_frameset_shadow / _shadow_grad (argtypes; both return int), set by srz.lib()
+SHADOW_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, C.c_float, C.c_float, _vp, C.c_size_t, _u32, _vp]
+SHADOW_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, C.c_float, C.c_float, _vp, _vp, _u32, _vp]
 # the prototypes of srz_frameset_perspective / _perspective_grad / _interpolate_deriv_persp (argtypes; all return int), set by srz.lib()
 PERSPECTIVE_ARGTYPES = [_vp, _vp, _vp, _vp, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
 PERSPECTIVE_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _vp]

@@ -8,6 +8,7 @@
 
 Any per-vertex attribute a of the owner interpolates as alpha * a0 + beta * a1 + gamma * a2.
 """
+import math
 from collections import namedtuple
 
 import torch
@@ -555,6 +556,102 @@ def texture_cube(fs, vis, cube, dirs, stream=None):
     verts)}))) backpropagates to the cube and to the vertices.  Backward is one texture_cube_grad call that asks only for the
     outputs some input needs.  stream: a raw stream handle, None = torch's current stream."""
     return _TextureCube.apply(cube, dirs, fs, vis, stream)
+
+
+def _map_dims(fs, map):
+    """map [H, W], [n_frames, H, W] or depth()'s [n_frames, 1, H, W] → (map_frames, H, W)"""
+    if map.dtype != torch.float32 or map.dim() not in (2, 3, 4) or (map.dim() == 4 and map.shape[1] != 1):
+        raise ValueError(f"shadow: map must be a float32 tensor [H, W], [n_frames, H, W] or [n_frames, 1, H, W], got {tuple(map.shape)} {map.dtype}")
+    map_frames = map.shape[0] if map.dim() > 2 else 1
+    if map.dim() > 2 and map_frames != fs.n_frames:
+        raise ValueError(f"shadow: map has {map_frames} frames, the set {fs.n_frames}")
+    h, w = map.shape[-2:]
+    if not (1 <= w <= abi.TEX_MAX_SIZE and 1 <= h <= abi.TEX_MAX_SIZE):
+        raise ValueError(f"shadow: map is {w} x {h} texels; 1 .. {abi.TEX_MAX_SIZE} are supported")
+    if not map.is_cuda:
+        raise ValueError(f"shadow: map must be on the device, got {map.device}")
+    return map_frames, h, w
+
+
+def _sc_arg(fs, sc):
+    if sc.dtype != torch.float32 or tuple(sc.shape) != tuple(fs.interpolate_shape(3)):
+        raise ValueError(f"shadow: sc must be a float32 tensor {fs.interpolate_shape(3)}, got {tuple(sc.shape)} {sc.dtype}")
+    if not sc.is_cuda:
+        raise ValueError(f"shadow: sc must be on the device, got {sc.device}")
+    return sc.contiguous()
+
+
+def _ramp_args(bias, width):
+    bias, width = float(bias), float(width)
+    if not (math.isfinite(bias) and math.isfinite(width) and width >= 0.0):
+        raise ValueError(f"shadow: bias and width must be finite and width >= 0, got bias {bias}, width {width}")
+    return bias, width
+
+
+def shadow_grad(fs, vis, map, sc, gout, bias, width, want_gmap=True, want_gsc=True, stream=None):
+    """the backward of shadow(fs, vis, map, sc, bias, width) by one FrameSet.shadow_grad call: gout [n_frames, 1, rows, W] → (gmap,
+    gsc), each None when not wanted (not both): gmap has map's shape — a sum of float atomics into zeros, not bit-reproducible
+    between runs, all zeros with width == 0; gsc [n_frames, 3, rows, W] is deterministic, zeros where nobody owns the pixel or its
+    coordinates are not finite, and is what interpolate's backward takes for a three-channel attribute.  bias and width get no
+    gradient.  stream: a raw stream handle, None = torch's current stream."""
+    if not want_gmap and not want_gsc:
+        raise ValueError("shadow_grad: neither gmap nor gsc is asked for")
+    bias, width = _ramp_args(bias, width)
+    map_frames, h, w = _map_dims(fs, map)
+    map, sc, gout = map.contiguous(), _sc_arg(fs, sc), gout.contiguous()
+    if tuple(gout.shape) != tuple(fs.interpolate_shape(1)) or gout.dtype != torch.float32:
+        raise ValueError(f"shadow_grad: gout must be float32 {fs.interpolate_shape(1)}, got {tuple(gout.shape)} {gout.dtype}")
+    gmap = torch.zeros_like(map) if want_gmap else None
+    gsc = torch.empty_like(sc) if want_gsc else None
+    fs.shadow_grad(vis.data_ptr(), sc.data_ptr(), gout.data_ptr(), map.data_ptr(), w, h, map_frames, bias, width,
+                   gmap.data_ptr() if want_gmap else None, gsc.data_ptr() if want_gsc else None, abi.FUSED_CLEAR, _stream_ptr(stream))
+    return gmap, gsc
+
+
+class _Shadow(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, map, sc, fs, vis, bias, width, stream):
+        bias, width = _ramp_args(bias, width)
+        map_frames, h, w = _map_dims(fs, map)
+        map, sc = map.contiguous(), _sc_arg(fs, sc)
+        out = torch.empty(fs.interpolate_shape(1), dtype=torch.float32, device=sc.device)
+        fs.shadow(vis.data_ptr(), sc.data_ptr(), map.data_ptr(), w, h, map_frames, bias, width, out.data_ptr(), fs.interpolate_bytes(1),
+                  abi.FUSED_CLEAR, _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.bias, ctx.width, ctx.stream = fs, vis, bias, width, stream
+        ctx.save_for_backward(map, sc)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        map, sc = ctx.saved_tensors
+        need_map, need_sc = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gmap = gsc = None
+        if need_map or need_sc:  # one call, asking only for what is needed
+            gmap, gsc = shadow_grad(ctx.fs, ctx.vis, map, sc, gout, ctx.bias, ctx.width, need_map, need_sc, ctx.stream)
+        return gmap, gsc, None, None, None, None, None
+
+
+def shadow(fs, vis, map, sc, bias=0.0, width=0.0, stream=None):
+    """a shadow-map lookup under a visibility buffer `vis` of FrameSet `fs` (the CAMERA's set): percentage-closer filtering of the
+    depth map `map` — a CUDA float32 tensor [H, W] (one map for every frame), [n_frames, H, W] or depth()'s [n_frames, 1, H, W]; a
+    non-contiguous view such as vis_l[:, 0] is made contiguous; on a sharded context the WHOLE map, gathered — at the coordinates sc
+    [n_frames, 3, rows, W]: sx, sy in map texels with the texel centres on the integers (a depth plane's texel (x, y) is the depth at
+    screen (x, y)), sd in the map's depth units → [n_frames, 1, rows, W] float32, 1 lit .. 0 shadowed, 1 where the coordinates are not
+    finite or beyond the map, zeros where nobody owns the pixel (FrameSet.shadow; include/srz.h states the rule).  The four texels
+    around (sx, sy) each pass (map + bias) - sd >= 0 or fail it — width == 0, the hard test — or, width > 0, are ramped linearly over
+    that width in depth, and the four results are blended bilinearly.  Differentiable with respect to map (float atomics into a
+    zeroed tensor: map.grad is not bit-reproducible between runs; zero with width == 0) and to sc (deterministic); bias and width get
+    no gradient.  THE CHAIN, a light's view being just another set fs_l of the same triangles with its own matrices:
+        pos_l = scene_positions(fs_l, ...)                     # [n, T, 3, 3]: the light set's screen positions
+        lit = shadow(fs_cam, vis_cam, depth(fs_l, vis_l, pos_l), interpolate(fs_cam, vis_cam, pos_l.view(n, T, 3, 3)), bias, width)
+    depth() is plane 0 of the light's visibility buffer (+inf where nobody is: lit) as a function of the occluders' positions, and
+    the light set's positions interpolated over the CAMERA set are every camera pixel's (sx, sy, sd): pos_l.grad gets the receiver's
+    share through interpolate and the occluder's through depth.  With SEVERAL LIGHTS each shadowed light takes its own light() call,
+    and its factor is multiplied in torch: light() sums its lights before it returns.  Screen-linear interpolation of light-space
+    positions is exact ONLY WHEN NEITHER VIEW DIVIDES BY w (orthographic camera and light); otherwise interpolate the world positions
+    and transform them in torch, or use interpolate_persp.  Backward is one shadow_grad call that asks only for the outputs some
+    input needs.  stream: a raw stream handle, None = torch's current stream."""
+    return _Shadow.apply(map, sc, fs, vis, bias, width, stream)
 
 
 def light_params(fs, lights, eye, ka, ks):
