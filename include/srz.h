@@ -69,6 +69,9 @@ extern "C" {
  *      srz_frameset_light_grad / srz_frameset_light_work_bytes
  *      (additive, same version) shadow-map lookup over a visibility buffer, with gradients srz_frameset_shadow /
  *      srz_frameset_shadow_grad
+ *      (additive, same version) mipmapped cube-map lookup by direction and level, with gradients srz_cube_mip_levels /
+ *      srz_cube_mip_bytes / srz_cube_mip_build / srz_cube_mip_fold / srz_frameset_texture_cube_mip /
+ *      srz_frameset_texture_cube_mip_grad / srz_frameset_cube_level
  */
 #define SRZ_ABI_VERSION 7
 
@@ -648,7 +651,8 @@ int srz_frameset_texture_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis,
 /* A CUBE MAP LOOKED UP BY DIRECTION over a visibility buffer, and its gradients: a float32 cube map of the caller's own (an
  * environment map, irradiance, a learned lighting probe) sampled BILINEARLY and SEAMLESSLY at the direction planes
  * srz_frameset_interpolate wrote for a three-channel attribute (normals, reflection vectors), and the backward of that lookup, to the
- * texels and to the direction.  No level of detail: a cube has no mip pyramid here.
+ * texels and to the direction.  No level of detail in this pair: the lookup over a cube's mip pyramid is
+ * srz_frameset_texture_cube_mip, in the section MIPMAPPED CUBE-MAP LOOKUP below.
  * d_vis: a visibility buffer of THIS set on this ctx's shard.  d_dir: [frame][3][local_rows][width] float32 (x, y, z),
  * srz_frameset_interpolate_bytes(3) bytes; the directions need not be normalised.  d_tex and d_gtex: [tex_frames][6][n][n][n_ch]
  * float32 — face, row, column, channel; channels last — 4-byte aligned; tex_frames is 1 (every frame samples the same cube) or the
@@ -950,6 +954,93 @@ int srz_frameset_texture_mip(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, 
 int srz_frameset_texture_mip_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const void *d_uvd, const void *d_gout,
                                   const float *d_tex, const float *d_mip, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames,
                                   uint32_t mode, uint32_t n_levels, float *d_gtex, float *d_gmip, void *d_guv, uint32_t flags, void *stream);
+/* MIPMAPPED CUBE-MAP LOOKUP by direction AND LEVEL over a visibility buffer, and its gradients: srz_frameset_texture_cube's lookup
+ * over a mip pyramid of the cube, blended between two levels by a per-pixel level of detail lam that the CALLER supplies — a
+ * roughness for a prefiltered specular probe, or the footprint level srz_frameset_cube_level derives for minified reflections — with
+ * gradients to every level's texels, to the direction and to lam itself.  Four pieces: the pyramid (build, and fold: its backward),
+ * the lookup, its backward, the level from the footprint.  All of it float32, nothing fused except where fmaf is written, division
+ * and sqrtf the IEEE operations (SRZ_OPT_APPROX_SHADE has no effect).  Unless said otherwise, band sharding, local_rows, stream
+ * semantics and asynchrony, the alignment (16 bytes: the plane buffers and the visibility buffer; 4 bytes: texels), owner, nobody and
+ * SRZ_FUSED_CLEAR, overlap and refusal rules are srz_frameset_texture_cube's and srz_frameset_texture_mip's.
+ * THE PYRAMID OF A CUBE.  Level 0 is the caller's cube [tex_frames][6][n][n][C].  Level l + 1 exists iff n_l > 1 and n_l is even; then
+ * n_(l+1) = n_l / 2 (96: 6 levels, down to 3; 64: 7; 6: 2; 1 and 5: 1).  Each face is box-filtered ON ITS OWN — a 2 x 2 block never
+ * crosses a face —, so every level is a cube that the 24-row seam table above resolves with N = n_l.  The layout is LEVEL-MAJOR:
+ * level l is [tex_frames][6][n_l][n_l][C] float32, the levels 1 .. L - 1 one after another without padding.  That is exactly
+ * srz_texture_mip_build / _fold on the cube viewed as 6 * tex_frames textures of n x n, and the four functions are that:
+ *   srz_cube_mip_levels(n) = srz_texture_mip_levels(n, n)
+ *   srz_cube_mip_bytes(n, n_ch, tex_frames, n_levels) = srz_texture_mip_bytes(n, n, n_ch, 6 * tex_frames, n_levels); 0 for
+ *     tex_frames == 0 or 6 * tex_frames > 65536
+ *   srz_cube_mip_build / srz_cube_mip_fold = srz_texture_mip_build / _fold with tex_w = tex_h = n and 6 * tex_frames frames, bit for
+ *     bit, with their refusals; SRZ_E_INVALID also for tex_frames == 0 or 6 * tex_frames > 65536.
+ * A caller may equally hand in a pyramid of their own in this layout (a GGX-prefiltered one): the lookup does not care who wrote it.
+ * THE LOOKUP.  srz_frameset_texture_cube_mip: srz_frameset_texture_cube's arguments, plus d_mip (the levels 1 .. L - 1, 4-byte
+ * aligned), n_levels = L, 1 <= L <= srz_cube_mip_levels(n), and d_lam [frame][1][local_rows][width] float32,
+ * srz_frameset_interpolate_bytes(1) bytes, 16-byte aligned: the level of detail per pixel.  n_levels == 1 reads neither d_lam nor d_mip
+ * (both may be null): the output is srz_frameset_texture_cube's, bit for bit.  A pixel is unsampled exactly as in the flat pass (a
+ * direction component not finite, or the zero direction); the words of d_lam at unsampled and at nobody's pixels never reach a result.
+ * THE LEVEL of a sampled pixel, with lam its word of d_lam:
+ *   if (!(lam > 0.0f))                  l0 = 0, f = 0                 (NaN, negative, +-0)
+ *   else if (lam >= (float)(L - 1))     l0 = L - 1, f = 0             (+inf too)
+ *   else { lf = floorf(lam);  l0 = (int)lf;  f = lam - lf }           (exact)
+ * Every level index follows these clamps: no value of lam makes a pass read or write outside its buffers.
+ * THE SAMPLE: c_l is the flat pass's seamless bilinear sample of level l — the per-axis rule, the seam resolution and the three
+ * fma's, with N = n_l and that level's texels.  The face and s, t do not depend on the level, only the per-axis step does.
+ *   out = c_l0 when f == 0 (level l0 + 1 is not read), else out = fmaf(f, c_(l0+1) - c_l0, c_l0).
+ * BACKWARD, srz_frameset_texture_cube_mip_grad: d_gout and the same d_vis, d_dir, d_lam; at least one of (d_gtex with d_gmip),
+ * d_gdir and d_glam.  d_gtex and d_gmip come together whenever L > 1 (d_gmip is not touched, and may be null, at L == 1).  d_tex
+ * and d_mip may be null when only the texel gradients are asked for.
+ *   texels: for level l0 the level weight is lw = 1.0f - f, for level l0 + 1 it is lw = f, and that level gets no add when f == 0.
+ *   Per corner and channel the float32 product (w_rc * lw) * gout[ch] (w_rc as the flat pass, from this level's tx, ty) is ADDED at
+ *   the RESOLVED texel of that level: level 0 in d_gtex, the others in d_gmip (d_mip's layout).  The caller zeroes the buffers, or
+ *   accumulates.  srz_cube_mip_fold then folds d_gmip into d_gtex for a box-built pyramid; a caller-made pyramid keeps d_gmip as its
+ *   own gradient.  THE ORDER OF THE ADDS IS UNSPECIFIED, each add rounds, so d_gtex and d_gmip are NOT BIT-REPRODUCIBLE between
+ *   launches: srz_frameset_texture_mip_grad's bound — with n contributing adds an element lies within n 2^-24 / (1 - n 2^-24) *
+ *   sum |term| of the exact sum of the float32 terms; an element with one contributing add is exact.  Hardware float atomics: d_gtex
+ *   and d_gmip must be ordinary (coarse-grained) device memory.
+ *   d_gdir, needs d_tex (and d_mip at L > 1), deterministic, bit for bit: gdir_l is srz_frameset_texture_cube_grad's gdir computed at
+ *   level l — au, av over that level's resolved texels, the factor 0.5f * (float)n_l, the chain through s, t and ma;
+ *   gdir = gdir_l0 when f == 0, else per component fmaf(f, gdir_(l0+1) - gdir_l0, gdir_l0).  srz_frameset_texture_cube_grad's layout.
+ *   d_glam [frame][1][local_rows][width], needs d_tex (and d_mip at L > 1), deterministic, bit for bit:
+ *     where lam >= 0.0f && lam < (float)(L - 1):  acc = 0;  for ch in order: acc = fmaf(gout[ch], c_(l0+1)[ch] - c_l0[ch], acc);
+ *       glam = acc — the RIGHT-HAND derivative: it reads level l0 + 1 even when f == 0, so a level initialised at an integer is not
+ *       stuck at a zero gradient;
+ *     elsewhere glam = 0: NaN, a negative lam (-0.0f counts as 0), lam at or beyond L - 1, L == 1, an unsampled pixel; nobody's
+ *     pixels as the fused-clear rule has them.
+ * THE LEVEL FROM THE FOOTPRINT.  srz_frameset_cube_level: d_dir, and d_dird [frame][6][local_rows][width] — the planes
+ * srz_frameset_interpolate_deriv or _interpolate_deriv_persp writes for the direction's attribute at n_ch = 3 (plane 2 c is d/dx,
+ * plane 2 c + 1 d/dy of component c), srz_frameset_interpolate_bytes(6) bytes — with n and n_levels = L -> a d_lam plane in d_out,
+ * srz_frameset_interpolate_bytes(1) bytes.  Per sampled pixel take the flat pass's face, s, t and inv = 1.0f / ma.  For the x step,
+ * dsc, dtc, dma are the components of (d dx/dx, d dy/dx, d dz/dx) that the face's su, sv and major axis name, with the sign flips of
+ * sc, tc and ma (dma is negated where the major component is not positive); then
+ *   sx = (dsc - s * dma) * inv;  tx = (dtc - t * dma) * inv;  ax = sx * (0.5f * (float)n);  ay = tx * (0.5f * (float)n)
+ * and sy, ty, bx, by likewise from the y step (ax, bx from s; ay, by from t).  From there srz_frameset_texture_mip's rule word for
+ * word, with fin = all four of sx, tx, sy, ty finite:  rx = fmaf(ax, ax, ay * ay);  ry = fmaf(bx, bx, by * by);  r2 = rx > ry ? rx : ry;
+ * !fin or !(r2 < INFINITY) -> l0 = L - 1, f = 0;  rho = sqrtf(r2);  !(rho > 1.0f) -> l0 = 0, f = 0;  else m = frexpf(rho, &e),
+ * l = e - 1, f = fmaf(2.0f, m, -1.0f), and l >= L - 1 -> l0 = L - 1, f = 0.  The output is lam = (float)l0 + f, a float32 sum that
+ * may round: the lookup derives l0 and f from lam again.  An unsampled pixel writes 0; nobody's pixels follow the fused-clear rule.
+ * There is no backward: the footprint level is held fixed, as in srz_frameset_texture_mip.  Deterministic, bit for bit.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched: what srz_frameset_texture_cube and _texture_cube_grad refuse, and
+ * n_levels 0 or above srz_cube_mip_levels(n); with n_levels > 1 a null d_lam, a null d_mip (forward; backward with d_gdir or
+ * d_glam), one of d_gtex / d_gmip without the other, 6 * tex_frames above 65536; d_gdir or d_glam without d_tex; none of the four
+ * outputs; a misaligned pointer (16 bytes: the plane buffers, d_lam, d_glam and d_dird among them; 4 bytes: d_tex, d_mip, d_gtex,
+ * d_gmip); a short out_bytes; any bit of `flags` but SRZ_FUSED_CLEAR; an output that overlaps an input (d_lam, d_mip and d_dird
+ * among the inputs, d_gmip and d_glam among the outputs) or another output.  srz_frameset_cube_level: a null pointer, n 0 or above
+ * SRZ_TEX_MAX_SIZE, n_levels 0 or above srz_cube_mip_levels(n), and the same alignment, size, flag and overlap rules. */
+uint32_t srz_cube_mip_levels(uint32_t n);
+size_t srz_cube_mip_bytes(uint32_t n, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels);
+int srz_cube_mip_build(srz_ctx *ctx, const float *d_tex, uint32_t n, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels, float *d_mip,
+                       size_t mip_bytes, void *stream);
+int srz_cube_mip_fold(srz_ctx *ctx, const float *d_gmip, size_t mip_bytes, uint32_t n, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels,
+                      float *d_gtex, void *stream);
+int srz_frameset_texture_cube_mip(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_dir, const void *d_lam, const float *d_tex,
+                                  uint32_t n, uint32_t n_ch, uint32_t tex_frames, const float *d_mip, uint32_t n_levels, void *d_out,
+                                  size_t out_bytes, uint32_t flags, void *stream);
+int srz_frameset_texture_cube_mip_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_dir, const void *d_lam,
+                                       const void *d_gout, const float *d_tex, const float *d_mip, uint32_t n, uint32_t n_ch,
+                                       uint32_t tex_frames, uint32_t n_levels, float *d_gtex, float *d_gmip, void *d_gdir, void *d_glam,
+                                       uint32_t flags, void *stream);
+int srz_frameset_cube_level(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_dir, const void *d_dird, uint32_t n,
+                            uint32_t n_levels, void *d_out, size_t out_bytes, uint32_t flags, void *stream);
 /* PERSPECTIVE-CORRECT BARYCENTRICS of a visibility buffer, their gradients, and the attribute derivatives under them.  A visibility
  * buffer's alpha, beta are LINEAR IN SCREEN SPACE, the reference's rule and the default of every pass above.  Under a vertex stage
  * that divides by a real w they name the wrong point of the triangle.  With q_k = 1 / w_k the reciprocal clip w of the owner's

@@ -1002,6 +1002,26 @@ TexMipArgs texture_mip_args(const srz_frameset *fs, const void *d_vis, const voi
   a.flags_or = flags;
   return a;
 }
+// what srz_frameset_texture_cube_mip and _texture_cube_mip_grad check alike behind check_cube; the pyramid's bytes in *mip_bytes
+int check_cube_mip(srz_ctx *ctx, const std::string &fn, uint32_t n, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels, const void *d_lam,
+                   size_t *mip_bytes) {
+  if (n_levels == 0u || n_levels > srz_cube_mip_levels(n)) return fail(ctx, SRZ_E_INVALID, fn + ": n_levels must be 1 .. srz_cube_mip_levels(n)");
+  if (n_levels > 1u && tex_frames > MIP_MAX_FRAMES / 6u) return fail(ctx, SRZ_E_INVALID, fn + ": 6 * tex_frames must not exceed 65536 with a pyramid");
+  if (n_levels > 1u && !d_lam) return fail(ctx, SRZ_E_INVALID, fn + ": n_levels > 1 needs the level plane");
+  *mip_bytes = srz_cube_mip_bytes(n, n_ch, tex_frames, n_levels);
+  return SRZ_OK;
+}
+CubeMipArgs cube_mip_args(const srz_frameset *fs, const void *d_vis, const void *d_dir, const void *d_lam, const float *d_tex, const float *d_mip,
+                          uint32_t n, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels, uint32_t out_planes, void *d_out, uint32_t flags) {
+  CubeMipArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  a.dir = (const float *)d_dir, a.lam = (const float *)d_lam, a.tex = d_tex, a.mip = d_mip;
+  a.vis_stride = 4ull * plane, a.frame_stride = out_planes * plane, a.dir_stride = 3ull * plane, a.gout_stride = n_ch * plane, a.lam_stride = plane;
+  a.n = n, a.n_ch = n_ch, a.tex_frames = tex_frames, a.n_levels = n_levels;
+  a.flags_or = flags;
+  return a;
+}
 
 } // namespace
 
@@ -2430,6 +2450,115 @@ int srz_frameset_texture_mip_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_
   TexMipArgs a = texture_mip_args(fs, d_vis, d_uv, d_uvd, d_tex, d_mip, tex_w, tex_h, n_ch, tex_frames, mode, n_levels, 2u, d_guv, flags);
   a.gout = (const float *)d_gout, a.gtex = d_gtex, a.gmip = d_gmip;
   launch_tex_mip_grad(a, s);
+  return end_pass(ctx);
+}
+
+// ---- the mip pyramid of a cube: the cube viewed as 6 * tex_frames textures of n x n, through the 2D functions above
+uint32_t srz_cube_mip_levels(uint32_t n) { return srz_texture_mip_levels(n, n); }
+
+size_t srz_cube_mip_bytes(uint32_t n, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels) {
+  if (tex_frames == 0u || tex_frames > MIP_MAX_FRAMES / 6u) return 0; // (6 * tex_frames <= 65536)
+  return srz_texture_mip_bytes(n, n, n_ch, 6u * tex_frames, n_levels);
+}
+
+int srz_cube_mip_build(srz_ctx *ctx, const float *d_tex, uint32_t n, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels, float *d_mip,
+                       size_t mip_bytes, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  if (tex_frames == 0u || tex_frames > MIP_MAX_FRAMES / 6u) return fail(ctx, SRZ_E_INVALID, "srz_cube_mip_build: 6 * tex_frames must be 6 .. 65536");
+  return srz_texture_mip_build(ctx, d_tex, n, n, n_ch, 6u * tex_frames, n_levels, d_mip, mip_bytes, stream);
+}
+
+int srz_cube_mip_fold(srz_ctx *ctx, const float *d_gmip, size_t mip_bytes, uint32_t n, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels,
+                      float *d_gtex, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  if (tex_frames == 0u || tex_frames > MIP_MAX_FRAMES / 6u) return fail(ctx, SRZ_E_INVALID, "srz_cube_mip_fold: 6 * tex_frames must be 6 .. 65536");
+  return srz_texture_mip_fold(ctx, d_gmip, mip_bytes, n, n, n_ch, 6u * tex_frames, n_levels, d_gtex, stream);
+}
+
+int srz_frameset_texture_cube_mip(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_dir, const void *d_lam, const float *d_tex,
+                                  uint32_t n, uint32_t n_ch, uint32_t tex_frames, const float *d_mip, uint32_t n_levels, void *d_out,
+                                  size_t out_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_texture_cube_mip");
+  if (!fs || !d_vis || !d_dir || !d_tex || !d_out)
+    return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_dir ? "d_dir" : !d_tex ? "d_tex" : "d_out"));
+  size_t tex_bytes = 0, mip_bytes = 0;
+  if (int rc = check_cube(ctx, fs, fn, n, n_ch, tex_frames, flags, &tex_bytes)) return rc;
+  if (int rc = check_cube_mip(ctx, fn, n, n_ch, tex_frames, n_levels, d_lam, &mip_bytes)) return rc;
+  if (n_levels > 1u && !d_mip) return fail(ctx, SRZ_E_INVALID, fn + ": n_levels > 1 needs the pyramid");
+  if (n_levels == 1u) d_lam = nullptr, d_mip = nullptr; // (not read: they take no part in the checks either)
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, n_ch), dir_bytes = srz_frameset_interpolate_bytes(ctx, fs, 3u);
+  const size_t lam_bytes = srz_frameset_interpolate_bytes(ctx, fs, 1u), vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": out_bytes is too small for d_out");
+  if (!aligned<16>({d_vis, d_dir, d_lam, d_out}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_dir, d_lam, d_out) must be 16-byte aligned");
+  if (!aligned<4>({d_tex, d_mip})) return fail(ctx, SRZ_E_INVALID, fn + ": d_tex and d_mip must be 4-byte aligned");
+  if (int rc = check_overlaps(ctx, fn, {{d_out, need}},
+                              {{d_vis, vis_bytes}, {d_dir, dir_bytes}, {d_lam, lam_bytes}, {d_tex, tex_bytes}, {d_mip, mip_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_texture_cube)
+  launch_cube_mip(cube_mip_args(fs, d_vis, d_dir, d_lam, d_tex, d_mip, n, n_ch, tex_frames, n_levels, n_ch, d_out, flags), s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_texture_cube_mip_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_dir, const void *d_lam,
+                                       const void *d_gout, const float *d_tex, const float *d_mip, uint32_t n, uint32_t n_ch,
+                                       uint32_t tex_frames, uint32_t n_levels, float *d_gtex, float *d_gmip, void *d_gdir, void *d_glam,
+                                       uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_texture_cube_mip_grad");
+  if (!fs || !d_vis || !d_dir || !d_gout)
+    return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_dir ? "d_dir" : "d_gout"));
+  if (!d_gtex && !d_gmip && !d_gdir && !d_glam) return fail(ctx, SRZ_E_INVALID, fn + ": no output is asked for");
+  if ((d_gdir || d_glam) && !d_tex) return fail(ctx, SRZ_E_INVALID, fn + ": d_gdir and d_glam need d_tex");
+  size_t tex_bytes = 0, mip_bytes = 0;
+  if (int rc = check_cube(ctx, fs, fn, n, n_ch, tex_frames, flags, &tex_bytes)) return rc;
+  if (int rc = check_cube_mip(ctx, fn, n, n_ch, tex_frames, n_levels, d_lam, &mip_bytes)) return rc;
+  if (n_levels > 1u && (d_gdir || d_glam) && !d_mip) return fail(ctx, SRZ_E_INVALID, fn + ": d_gdir and d_glam need the pyramid when n_levels > 1");
+  if (n_levels > 1u && (d_gtex == nullptr) != (d_gmip == nullptr))
+    return fail(ctx, SRZ_E_INVALID, fn + ": d_gtex and d_gmip come together when n_levels > 1");
+  if (n_levels == 1u) {
+    if (!d_gtex && !d_gdir && !d_glam) return fail(ctx, SRZ_E_INVALID, fn + ": no output is asked for");
+    d_lam = nullptr, d_mip = nullptr, d_gmip = nullptr; // (not read, not written: they take no part in the checks either)
+  }
+  const size_t gout_bytes = srz_frameset_interpolate_bytes(ctx, fs, n_ch), dir_bytes = srz_frameset_interpolate_bytes(ctx, fs, 3u);
+  const size_t lam_bytes = srz_frameset_interpolate_bytes(ctx, fs, 1u), vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (!aligned<16>({d_vis, d_dir, d_lam, d_gout, d_gdir, d_glam}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_dir, d_lam, d_gout, d_gdir, d_glam) must be 16-byte aligned");
+  if (!aligned<4>({d_tex, d_mip, d_gtex, d_gmip}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the cube, the pyramid and their gradients must be 4-byte aligned");
+  if (int rc = check_overlaps(ctx, fn, {{d_gtex, tex_bytes}, {d_gmip, mip_bytes}, {d_gdir, dir_bytes}, {d_glam, lam_bytes}},
+                              {{d_vis, vis_bytes}, {d_dir, dir_bytes}, {d_lam, lam_bytes}, {d_gout, gout_bytes}, {d_tex, tex_bytes}, {d_mip, mip_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_texture_cube)
+  CubeMipArgs a = cube_mip_args(fs, d_vis, d_dir, d_lam, d_tex, d_mip, n, n_ch, tex_frames, n_levels, 3u, d_gdir, flags);
+  a.gout = (const float *)d_gout, a.gtex = d_gtex, a.gmip = d_gmip, a.glam = (float *)d_glam;
+  launch_cube_mip_grad(a, s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_cube_level(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_dir, const void *d_dird, uint32_t n,
+                            uint32_t n_levels, void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_cube_level");
+  if (!fs || !d_vis || !d_dir || !d_dird || !d_out)
+    return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_dir ? "d_dir" : !d_dird ? "d_dird" : "d_out"));
+  if (n == 0u || n > SRZ_TEX_MAX_SIZE) return fail(ctx, SRZ_E_INVALID, fn + ": n must be 1 .. SRZ_TEX_MAX_SIZE");
+  if (n_levels == 0u || n_levels > srz_cube_mip_levels(n)) return fail(ctx, SRZ_E_INVALID, fn + ": n_levels must be 1 .. srz_cube_mip_levels(n)");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, 1u), dir_bytes = srz_frameset_interpolate_bytes(ctx, fs, 3u);
+  const size_t dird_bytes = srz_frameset_interpolate_bytes(ctx, fs, 6u), vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": out_bytes is too small for d_out");
+  if (!aligned<16>({d_vis, d_dir, d_dird, d_out}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_dir, d_dird, d_out) must be 16-byte aligned");
+  if (int rc = check_overlaps(ctx, fn, {{d_out, need}}, {{d_vis, vis_bytes}, {d_dir, dir_bytes}, {d_dird, dird_bytes}})) return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (planes only: no vertex stage)
+  CubeMipArgs a = cube_mip_args(fs, d_vis, d_dir, nullptr, nullptr, nullptr, n, 1u, 1u, n_levels, 1u, d_out, flags);
+  a.dird = (const float *)d_dird;
+  launch_cube_level(a, s);
   return end_pass(ctx);
 }
 

@@ -608,6 +608,40 @@ struct TexMipArgs {
 };
 void launch_tex_mip(const TexMipArgs &a, hipStream_t s);
 void launch_tex_mip_grad(const TexMipArgs &a, hipStream_t s);
+// srz_frameset_texture_cube_mip / _texture_cube_mip_grad / srz_frameset_cube_level: CubeArgs' fields, plus the cube's pyramid `mip`
+// (levels 1 .. n_levels - 1, level l [tex_frames][6][n >> l][n >> l][n_ch]), its gradient `gmip` (added into, comes with gtex), the
+// level plane `lam` [frame][1][local_rows][width] with its gradient `glam`, and for the level pass the derivative planes `dird`
+// [frame][6][local_rows][width] (k_cube_mip, k_cube_mip_grad, k_cube_level).  `out` is the forward's [frame][n_ch][local_rows][width],
+// the backward's gdir [frame][3][local_rows][width] (may be null there) or the level pass's lam plane.  n_levels == 1: lam, mip and
+// gmip are not read.  The host has checked n_levels against n: every level l < n_levels has n >> l >= 1 texels a side, and a
+// texel's offset in one frame's concatenated pyramid, 6 * (n^2 + (n >> 1)^2 + ...) + its index in the level, stays below 2^31
+struct CubeMipArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *dir;
+  const float *dird;         // level pass only
+  const float *lam;          // (null at n_levels == 1)
+  const float *tex;          // (backward: may be null when only the texel gradients are asked for)
+  const float *mip;
+  float *out;
+  const float *gout;         // backward: [frame][n_ch][local_rows][width]
+  float *gtex;               // backward: tex's shape, added into (may be null)
+  float *gmip;               // backward: mip's shape, added into (null with gtex, and at n_levels == 1)
+  float *glam;               // backward: lam's shape (may be null)
+  uint64_t vis_stride;       // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride;     // floats per frame in out
+  uint64_t dir_stride;       // floats per frame in dir = 3 * local_rows * width (dird: twice that)
+  uint64_t gout_stride;      // floats per frame in gout = n_ch * local_rows * width
+  uint64_t lam_stride;       // floats per frame in lam / glam = local_rows * width
+  uint32_t n, n_ch;
+  uint32_t tex_frames, n_levels;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_cube_mip(const CubeMipArgs &a, hipStream_t s);
+void launch_cube_mip_grad(const CubeMipArgs &a, hipStream_t s);
+void launch_cube_level(const CubeMipArgs &a, hipStream_t s);
 void launch_resolve8(const float *planes, uint8_t *out, uint32_t n_frames, uint32_t rows, uint32_t W, uint64_t frame_stride,
                      hipStream_t s);
 void launch_deinterleave(const void *gathered, void *full, uint32_t world, uint32_t n_fp, uint32_t bands_per_rank, uint32_t row_bytes,

@@ -3301,7 +3301,8 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
 // Then what the bodies do next: quad_ids (the four owner ids, strangers clamped to nobody), quad_bary (α, β and γ of the owned
 // pixels) and quad_store_owned (whole quads, or the owned pixels only).
 // CALLERS: k_shade_vis (pass_tiles with its kind filter, pass_tile, quad_ids), k_interp, k_interp_grad, k_interp_deriv (all of it),
-// k_cube and k_cube_grad (the walk, quad_ids, quad_store_owned), k_persp (the walk, quad_ids), k_persp_grad and
+// k_cube and k_cube_grad (the walk, quad_ids, quad_store_owned), k_cube_mip, k_cube_mip_grad and k_cube_level (the same, and
+// quad_load), k_persp (the walk, quad_ids), k_persp_grad and
 // k_interp_deriv_persp (all of it), k_light (the walk, quad_ids, quad_load, quad_store_owned) and k_light_grad (the same through
 // pass_tiles and pass_tile: the tile's index names its row of partial sums).
 // COPIES, each naming this definition — a fix to the walk goes into them too: k_gbuffer, k_motion, k_pos_grad, aa_body, k_tex,
@@ -5158,8 +5159,11 @@ __device__ __forceinline__ void cube_axis(float s, int n, int &i0, float &t) {
   t = fx - f0;
   i0 = max(-1, min((int)f0, n - 1)); // (never changes a value: fx lies in [-0.5, n - 0.5])
 }
-// the tap of one direction; false: not sampled (a component not finite, or the zero vector)
-__device__ __forceinline__ bool cube_tap(float dx, float dy, float dz, uint32_t N, CubeTap &p) {
+// The tap of one direction in its two halves, so that the passes over a cube's mip pyramid share them: cube_face — what does not
+// depend on the face size: the major axis (bit 2: its component is positive), the in-face coordinates s, t and 1 / |major
+// component|; false: not sampled (a component not finite, or the zero vector) — and cube_corners — the fractions and the four
+// resolved texels of that point on faces of N x N texels.
+__device__ __forceinline__ bool cube_face(float dx, float dy, float dz, float &s, float &t, float &inv, uint32_t &major) {
   const float ax = __builtin_fabsf(dx), ay = __builtin_fabsf(dy), az = __builtin_fabsf(dz);
   if (!tex_finite(dx) || !tex_finite(dy) || !tex_finite(dz)) return false;
   if (__builtin_fmaxf(ax, __builtin_fmaxf(ay, az)) == 0.0f) return false;
@@ -5170,13 +5174,22 @@ __device__ __forceinline__ bool cube_tap(float dx, float dy, float dz, uint32_t 
   // the components su and sv name, signed: +X (-z, -y)  -X (z, -y)  +Y (x, z)  -Y (x, -z)  +Z (x, -y)  -Z (-x, -y)
   const float sc = m == 0u ? (pos ? -dz : dz) : m == 1u ? dx : (pos ? dx : -dx);
   const float tc = m == 1u ? (pos ? dz : -dz) : -dy;
-  const uint32_t face = 2u * m + (pos ? 0u : 1u), seams = cube_seams(face);
-  p.s = sc / ma, p.t = tc / ma, p.inv = 1.0f / ma, p.major = m | (pos ? 4u : 0u);
+  s = sc / ma, t = tc / ma, inv = 1.0f / ma, major = m | (pos ? 4u : 0u);
+  return true;
+}
+__device__ __forceinline__ void cube_corners(uint32_t major, float s, float t, uint32_t N, uint32_t &i00, uint32_t &i01, uint32_t &i10,
+                                             uint32_t &i11, float &tx, float &ty) {
+  const uint32_t face = 2u * (major & 3u) + ((major & 4u) ? 0u : 1u), seams = cube_seams(face);
   int x0, y0;
-  cube_axis(p.s, (int)N, x0, p.tx);
-  cube_axis(p.t, (int)N, y0, p.ty);
-  p.i00 = cube_texel(face, seams, x0, y0, (int)N), p.i01 = cube_texel(face, seams, x0 + 1, y0, (int)N);
-  p.i10 = cube_texel(face, seams, x0, y0 + 1, (int)N), p.i11 = cube_texel(face, seams, x0 + 1, y0 + 1, (int)N);
+  cube_axis(s, (int)N, x0, tx);
+  cube_axis(t, (int)N, y0, ty);
+  i00 = cube_texel(face, seams, x0, y0, (int)N), i01 = cube_texel(face, seams, x0 + 1, y0, (int)N);
+  i10 = cube_texel(face, seams, x0, y0 + 1, (int)N), i11 = cube_texel(face, seams, x0 + 1, y0 + 1, (int)N);
+}
+// the tap of one direction; false: not sampled
+__device__ __forceinline__ bool cube_tap(float dx, float dy, float dz, uint32_t N, CubeTap &p) {
+  if (!cube_face(dx, dy, dz, p.s, p.t, p.inv, p.major)) return false;
+  cube_corners(p.major, p.s, p.t, N, p.i00, p.i01, p.i10, p.i11, p.tx, p.ty);
   return true;
 }
 // what k_cube and k_cube_grad do alike in front of their channel loops: the owners, the directions of a quad with an owner, the
@@ -6515,6 +6528,464 @@ __global__ __launch_bounds__(256) void k_tex_mip_grad(TexMipArgs a) {
 }
 
 // ================================================================================================================
+// k_cube_mip — A CUBE MAP'S MIP PYRAMID LOOKED UP BY DIRECTION AND LEVEL (srz_frameset_texture_cube_mip, include/srz.h states the
+// rule): k_cube's walk and shape (pass_walk, no LDS, no barrier, quad_ids, quad_store_owned) with k_tex_mip's blend of two levels.
+// The level is the caller's plane lam, clamped into [0, n_levels - 1] (cube_lod).  cube_face runs once per pixel — the face, its
+// seams, s and t do not depend on the level —, cube_corners once per level read, with that level's face size: every level is a cube
+// of its own, so a corner that leaves its face resolves within its level.  Level l of a frame lies at cube_level_ptr: the cube is
+// 6 * tex_frames textures of n x n to the pyramid's layout.  A pixel with f == 0 reads one level and costs what it costs in k_cube;
+// the wave skips the second level's gathers when none of its lanes blends.
+// l0 <= n_levels - 1 and l0 + 1 <= n_levels - 1 where f != 0 by cube_lod's clamps; every texel index follows cube_axis's clamp within
+// its level: no direction and no lam leaves the cube or the pyramid.
+// ================================================================================================================
+struct CubeFace {
+  float s, t, inv;
+  uint32_t major;
+};
+struct CubeCorners {
+  uint32_t i00, i01, i10, i11;
+  float tx, ty;
+};
+// the level and the fraction of a caller's lam (MipLod: k_tex_mip's pair)
+__device__ __forceinline__ MipLod cube_lod(float lam, uint32_t L) {
+  MipLod r = {0u, 0.0f};
+  if (!(lam > 0.0f)) return r; // NaN, negative, +-0
+  if (lam >= (float)(L - 1u)) {
+    r.l0 = L - 1u; // (+inf too)
+    return r;
+  }
+  const float lf = __builtin_floorf(lam);
+  r.l0 = min((uint32_t)(int)lf, L - 1u), r.f = lam - lf; // (the clamp never changes a value: 0 < lam < L - 1)
+  return r;
+}
+__device__ __forceinline__ CubeCorners cube_corners_of(const CubeFace &c, uint32_t N) {
+  CubeCorners p;
+  cube_corners(c.major, c.s, c.t, N, p.i00, p.i01, p.i10, p.i11, p.tx, p.ty);
+  return p;
+}
+// level l of frame f's cube: level 0 is the cube itself, the others lie in the pyramid behind the levels before them
+template <class P> __device__ __forceinline__ P *cube_level_ptr(P *tex, P *mip, uint32_t n, uint32_t C, uint32_t tex_frames, uint32_t f, uint32_t l) {
+  const size_t ft = tex_frames == 1u ? 0u : f, texels = 6u * (size_t)mip_extent(n, l) * mip_extent(n, l);
+  return l == 0u ? tex + ft * texels * C : mip + ((size_t)mip_texels_before(n, n, l) * 6u * tex_frames + ft * texels) * C;
+}
+// what k_cube_mip and k_cube_mip_grad do alike in front of their loops: the owners, the directions of a quad with an owner, the
+// faces of the sampled pixels and their levels -> `own`, `smp` and `rhd`, one bit per pixel; rhd: a sampled pixel with
+// 0 <= lam < n_levels - 1, where the level has a right-hand derivative (level l0 + 1 exists)
+__device__ __forceinline__ void cube_mip_quad(const CubeMipArgs &a, const PassTile &t, CubeFace (&cf)[4], MipLod (&lod)[4], uint32_t &own,
+                                              uint32_t &smp, uint32_t &rhd) {
+  uint32_t id[4];
+  own = quad_ids(t, a.vis + (size_t)t.f * a.vis_stride + t.poff, id), smp = 0u, rhd = 0u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) lod[k] = {0u, 0.0f};
+  if (own == 0u) return;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 d[3] = {zero4, zero4, zero4};
+  quad_load(a.dir + (size_t)t.f * a.dir_stride + t.poff, t.rc.plane, d, t.whole, t.x4, t.rc.tx1);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (!(own & (1u << k))) continue;
+    if (cube_face(quad_at(d[0], k), quad_at(d[1], k), quad_at(d[2], k), cf[k].s, cf[k].t, cf[k].inv, cf[k].major)) smp |= 1u << k;
+  }
+  if (a.n_levels <= 1u || smp == 0u) return;
+  float4 lq[1] = {zero4}; // (words of pixels that are not sampled: loaded with their quad at most, never used)
+  quad_load(a.lam + (size_t)t.f * a.lam_stride + t.poff, t.rc.plane, lq, t.whole, t.x4, t.rc.tx1);
+  const float top = (float)(a.n_levels - 1u);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (smp & (1u << k)) {
+      const float lam = quad_at(lq[0], k);
+      lod[k] = cube_lod(lam, a.n_levels);
+      if (lam >= 0.0f && lam < top) rhd |= 1u << k;
+    }
+}
+__device__ __forceinline__ float cube_bilinear(const SRZ_CAS float *t, const CubeCorners &p, uint32_t C, uint32_t ch) {
+  const float t00 = t[(size_t)p.i00 * C + ch], t01 = t[(size_t)p.i01 * C + ch], t10 = t[(size_t)p.i10 * C + ch], t11 = t[(size_t)p.i11 * C + ch];
+  const float top = fmaf_(p.tx, t01 - t00, t00), bot = fmaf_(p.tx, t11 - t10, t10);
+  return fmaf_(p.ty, bot - top, top);
+}
+__global__ __launch_bounds__(256) void k_cube_mip(CubeMipArgs a) {
+  const uint32_t C = a.n_ch;
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const TileRect &rc = t.rc;
+    const bool fused = t.fused(a.flags_or);
+    // ---- 1. owners, directions, the faces, the levels
+    CubeFace cf[4] = {};
+    MipLod lod[4];
+    uint32_t own, smp, rhd;
+    cube_mip_quad(a, t, cf, lod, own, smp, rhd);
+    if (own == 0u && !fused) return;
+    // ---- 2. the corners of level l0 and, where f != 0, of level l0 + 1
+    CubeCorners lo[4] = {}, hi[4] = {};
+    const SRZ_CAS float *p0[4], *p1[4];
+    uint32_t two = 0u; // the pixels that blend two levels
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      p0[k] = p1[k] = as_const(a.tex);
+      if (!(smp & (1u << k))) continue;
+      const uint32_t l = lod[k].l0;
+      lo[k] = cube_corners_of(cf[k], mip_extent(a.n, l));
+      p0[k] = cube_level_ptr(as_const(a.tex), as_const(a.mip), a.n, C, a.tex_frames, t.f, l);
+      if (lod[k].f != 0.0f) { // (l + 1 <= n_levels - 1: cube_lod gives f == 0 at the coarsest level)
+        two |= 1u << k;
+        hi[k] = cube_corners_of(cf[k], mip_extent(a.n, l + 1u));
+        p1[k] = cube_level_ptr(as_const(a.tex), as_const(a.mip), a.n, C, a.tex_frames, t.f, l + 1u);
+      }
+    }
+    const bool wave_two = __builtin_amdgcn_ballot_w64(two != 0u) != 0ull; // (wave-uniform: no lane blends -> no second gather)
+    // ---- 3. the channels, ATTR_CHUNK at a time (k_cube's loop)
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 q[ATTR_CHUNK];
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) q[i] = make_float4(0.f, 0.f, 0.f, 0.f); // nobody, and an owner that is not sampled: zeros
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(smp & (1u << k))) continue;
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+          if (i < nc) quad_at(q[i], k) = cube_bilinear(p0[k], lo[k], C, c0 + i);
+      }
+      if (wave_two) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (!(two & (1u << k))) continue;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float c = quad_at(q[i], k);
+              quad_at(q[i], k) = fmaf_(lod[k].f, cube_bilinear(p1[k], hi[k], C, c0 + i) - c, c);
+            }
+        }
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+        if (i >= nc) break;
+        quad_store_owned(t.out + (size_t)(c0 + i) * rc.plane, t, {q[i]}, fused, own);
+      }
+    }
+  });
+}
+
+// ================================================================================================================
+// k_cube_mip_grad — THE BACKWARD OF k_cube_mip (srz_frameset_texture_cube_mip_grad).  k_cube_grad's walk and barriers
+// (pass_walk<true>: every thread of the workgroup reaches every barrier, one outside the frame samples nothing); two phases per
+// tile, each with its own channel loop:
+//   A. gdir and glam, from registers, deterministic: k_cube_grad's au, av chains at level l0 and at level l0 + 1, each taken through
+//      cube_gdir with its own level's face size and blended by f as the forward blends the samples; glam is the fma chain of gout
+//      over c_(l0+1) - c_l0, which reads level l0 + 1 wherever 0 <= lam < n_levels - 1 — at f == 0 too (the right-hand derivative);
+//   B. the texel adds, BOTH LEVELS IN ONE TABLE: TexTable keyed on the texel's offset in the frame's concatenated pyramid + 1
+//      (cube_pyr_before(l) + its index in level l, below 2^31), the slots found once in front of the channel loop, per chunk the
+//      LDS adds of (w_rc * lw) * gout, the dense flush — cube_pyr_texel finds a key's level and its place in gtex or gmip again —,
+//      the keys released.  A tile where no pixel is sampled skips the phase after one barrier: the tile's threads say so in a word
+//      of LDS that rotates over three words by the tile's count (k_tex_mip_grad's level word), the next one zeroed in front of the
+//      barrier.  A corner without a slot adds straight to memory.
+// The corners of both levels stay in registers across the phases; the slot numbers are live in B only.
+// (qg_slot and qg_add are COPIES of tg_slot and tg_add, and B's flush of k_tex_grad's step 4: shared helpers have moved k_tex_grad's
+// registers before (k_tex_mip_grad's note); a fix goes into all of them)
+// ================================================================================================================
+// the texels of one frame's levels 0 .. l - 1
+__device__ __forceinline__ uint32_t cube_pyr_before(uint32_t n, uint32_t l) {
+  uint32_t s = 0u;
+  for (uint32_t k = 0; k < l; ++k) s += 6u * mip_extent(n, k) * mip_extent(n, k);
+  return s;
+}
+// texel `off` of frame f's concatenated pyramid in the gradient buffers: level 0 in gtex, the others in gmip
+__device__ __forceinline__ float *cube_pyr_texel(const CubeMipArgs &a, uint32_t f, uint32_t off) {
+  uint32_t l = 0u, sz = 6u * a.n * a.n;
+  while (l + 1u < a.n_levels && off >= sz) off -= sz, ++l, sz = 6u * mip_extent(a.n, l) * mip_extent(a.n, l);
+  return cube_level_ptr(a.gtex, a.gmip, a.n, a.n_ch, a.tex_frames, f, l) + (size_t)off * a.n_ch;
+}
+__device__ __forceinline__ uint32_t qg_slot(TexTable &tb, uint32_t off) {
+  const uint32_t key = off + 1u; // (off < 2^31)
+  uint32_t h = (key * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
+  for (uint32_t p = 0; p < TG_PROBES; ++p) {
+    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
+    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
+    if (old == 0u || old == key) return h;
+    h = (h + 1u) & (TG_SLOTS - 1u);
+  }
+  return TG_NONE;
+}
+__device__ __forceinline__ void qg_add(TexTable &tb, uint32_t slot, float *glevel, uint32_t idx, uint32_t C, uint32_t ch, uint32_t i, float v) {
+  if (slot != TG_NONE) lds_add(&tb.val[slot * ATTR_CHUNK + i], v);
+  else global_add(glevel + (size_t)idx * C + ch, v);
+}
+// srz_frameset_texture_cube_grad's chain from au, av at one level (half_n = 0.5f * (float)N of that level) to the direction
+__device__ __forceinline__ void cube_gdir(const CubeFace &c, float au, float av, float half_n, float (&g)[3]) {
+  const float gs = au * half_n, gt = av * half_n, inv = c.inv;
+  const float g_sc = gs * inv, g_tc = gt * inv, g_ma = -(fmaf_(gs, c.s, gt * c.t) * inv);
+  const uint32_t m = c.major & 3u;
+  const bool pos = (c.major & 4u) != 0u;
+  const float g_m = pos ? g_ma : -g_ma;
+  // su, sv of the face, undone: +X (-z, -y)  -X (z, -y)  +Y (x, z)  -Y (x, -z)  +Z (x, -y)  -Z (-x, -y)
+  g[0] = m == 0u ? g_m : m == 1u ? g_sc : (pos ? g_sc : -g_sc);
+  g[1] = m == 1u ? g_m : -g_tc;
+  g[2] = m == 0u ? (pos ? -g_sc : g_sc) : m == 1u ? (pos ? g_tc : -g_tc) : g_m;
+}
+__global__ __launch_bounds__(256) void k_cube_mip_grad(CubeMipArgs a) {
+  __shared__ TexTable tb;
+  __shared__ uint32_t busy[3];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t C = a.n_ch;
+  const bool want_tex = a.gtex != nullptr, want_dir = a.out != nullptr, want_lam = a.glam != nullptr;
+  if (want_tex) {
+    for (uint32_t i = tid; i < TG_SLOTS; i += 256) tb.key[i] = 0u;
+    for (uint32_t i = tid; i < TG_SLOTS * ATTR_CHUNK; i += 256) tb.val[i] = 0.0f;
+    if (tid == 0) tb.n_used = 0u;
+    if (tid < 3) busy[tid] = 0u;
+    __syncthreads();
+  }
+  uint32_t turn = 0u; // the tile's count in this workgroup's walk mod 3 (the same in every thread: nobody skips a tile)
+  pass_walk<true>(a, [&](const PassTile &t) { // (a thread outside the frame owns nothing, and still meets the barriers)
+    const TileRect &rc = t.rc;
+    const bool fused = t.fused(a.flags_or);
+    const float *gg = a.gout + (size_t)t.f * a.gout_stride + t.poff;
+    // ---- 1. owners, directions, the faces, the levels; the corners of level l0 and, where it is read, of level l0 + 1
+    CubeFace cf[4] = {};
+    MipLod lod[4];
+    uint32_t own, smp, rhd;
+    cube_mip_quad(a, t, cf, lod, own, smp, rhd);
+    if (!want_lam) rhd = 0u;
+    CubeCorners lo[4] = {}, hi[4] = {};
+    uint32_t two = 0u, up = 0u; // the pixels that blend two levels; those whose level l0 + 1 is read (the blend, or glam)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (!(smp & (1u << k))) continue;
+      const uint32_t l = lod[k].l0;
+      lo[k] = cube_corners_of(cf[k], mip_extent(a.n, l));
+      if (lod[k].f != 0.0f) two |= 1u << k;
+      if (((two | rhd) >> k) & 1u) { // (l + 1 <= n_levels - 1: f != 0, or 0 <= lam < n_levels - 1)
+        up |= 1u << k;
+        hi[k] = cube_corners_of(cf[k], mip_extent(a.n, l + 1u));
+      }
+    }
+    // ---- A. gdir and glam
+    if ((want_dir || want_lam) && t.inside && (own != 0u || fused)) {
+      const SRZ_CAS float *p0[4], *p1[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        p0[k] = p1[k] = as_const(a.tex);
+        if (!(smp & (1u << k))) continue;
+        p0[k] = cube_level_ptr(as_const(a.tex), as_const(a.mip), a.n, C, a.tex_frames, t.f, lod[k].l0);
+        if (up & (1u << k)) p1[k] = cube_level_ptr(as_const(a.tex), as_const(a.mip), a.n, C, a.tex_frames, t.f, lod[k].l0 + 1u);
+      }
+      float au0[4] = {0.f, 0.f, 0.f, 0.f}, av0[4] = {0.f, 0.f, 0.f, 0.f}, au1[4] = {0.f, 0.f, 0.f, 0.f}, av1[4] = {0.f, 0.f, 0.f, 0.f};
+      float gl[4] = {0.f, 0.f, 0.f, 0.f};
+      for (uint32_t c0 = 0; c0 < C && smp != 0u; c0 += ATTR_CHUNK) {
+        const uint32_t nc = min(ATTR_CHUNK, C - c0);
+        float4 g[ATTR_CHUNK]; // gout of the chunk's channels; words of pixels that are not sampled are loaded with their quad at most, never used
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+          if (i >= nc) break;
+          const float *p = gg + (size_t)(c0 + i) * rc.plane;
+          if (t.whole) {
+            g[i] = *reinterpret_cast<const float4 *>(p);
+          } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (smp & (1u << k)) quad_at(g[i], k) = p[k];
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (!(smp & (1u << k))) continue;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float gi = quad_at(g[i], k);
+              float c_lo;
+              {
+                const SRZ_CAS float *q = p0[k] + c0 + i;
+                const float t00 = q[(size_t)lo[k].i00 * C], t01 = q[(size_t)lo[k].i01 * C], t10 = q[(size_t)lo[k].i10 * C], t11 = q[(size_t)lo[k].i11 * C];
+                const float top = fmaf_(lo[k].tx, t01 - t00, t00), bot = fmaf_(lo[k].tx, t11 - t10, t10);
+                au0[k] = fmaf_(gi, fmaf_(lo[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au0[k]);
+                av0[k] = fmaf_(gi, bot - top, av0[k]);
+                c_lo = fmaf_(lo[k].ty, bot - top, top);
+              }
+              if (up & (1u << k)) {
+                const SRZ_CAS float *q = p1[k] + c0 + i;
+                const float t00 = q[(size_t)hi[k].i00 * C], t01 = q[(size_t)hi[k].i01 * C], t10 = q[(size_t)hi[k].i10 * C], t11 = q[(size_t)hi[k].i11 * C];
+                const float top = fmaf_(hi[k].tx, t01 - t00, t00), bot = fmaf_(hi[k].tx, t11 - t10, t10);
+                au1[k] = fmaf_(gi, fmaf_(hi[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au1[k]);
+                av1[k] = fmaf_(gi, bot - top, av1[k]);
+                if (rhd & (1u << k)) gl[k] = fmaf_(gi, fmaf_(hi[k].ty, bot - top, top) - c_lo, gl[k]);
+              }
+            }
+        }
+      }
+      // whole quads (fused clear, or four owners), else the owned pixels only; an owner that is not sampled: zeros
+      const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (want_dir) {
+        float4 gd[3] = {zero4, zero4, zero4};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (smp & (1u << k)) {
+            const uint32_t l = lod[k].l0;
+            float g0[3];
+            cube_gdir(cf[k], au0[k], av0[k], 0.5f * (float)mip_extent(a.n, l), g0);
+            if (two & (1u << k)) {
+              float g1[3];
+              cube_gdir(cf[k], au1[k], av1[k], 0.5f * (float)mip_extent(a.n, l + 1u), g1);
+#pragma unroll
+              for (int c = 0; c < 3; ++c) g0[c] = fmaf_(lod[k].f, g1[c] - g0[c], g0[c]);
+            }
+            quad_at(gd[0], k) = g0[0], quad_at(gd[1], k) = g0[1], quad_at(gd[2], k) = g0[2];
+          }
+        quad_store_owned(t.out, t, gd, fused, own);
+      }
+      if (want_lam) {
+        float4 gq[1] = {zero4};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (rhd & (1u << k)) quad_at(gq[0], k) = gl[k];
+        quad_store_owned(a.glam + (size_t)t.f * a.lam_stride + t.poff, t, gq, fused, own);
+      }
+    }
+    if (!want_tex) return;
+    // ---- B. the texel adds; a tile with nothing to add leaves after the barrier
+    if (smp != 0u) atomicOr(&busy[turn], 1u);
+    if (tid == 0) busy[turn == 2u ? 0u : turn + 1u] = 0u; // (last read two tiles ago, in front of the previous tile's barrier)
+    __syncthreads();
+    const bool any = __builtin_amdgcn_readfirstlane(busy[turn]) != 0u;
+    turn = turn == 2u ? 0u : turn + 1u;
+    if (!any) return;
+    // ---- B1. the slots of the sampled pixels' corners at both levels (two corners on one texel: one slot, both add)
+    uint32_t slot[4][8] = {};
+    float *q0[4], *q1[4]; // the pixel's two levels in the gradient buffers: where a corner without a slot adds
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      q0[k] = q1[k] = a.gtex;
+      if (!(smp & (1u << k))) continue;
+      const uint32_t l = lod[k].l0, off0 = cube_pyr_before(a.n, l);
+      q0[k] = cube_level_ptr(a.gtex, a.gmip, a.n, C, a.tex_frames, t.f, l);
+      slot[k][0] = qg_slot(tb, off0 + lo[k].i00), slot[k][1] = qg_slot(tb, off0 + lo[k].i01);
+      slot[k][2] = qg_slot(tb, off0 + lo[k].i10), slot[k][3] = qg_slot(tb, off0 + lo[k].i11);
+      if (two & (1u << k)) {
+        const uint32_t off1 = off0 + 6u * mip_extent(a.n, l) * mip_extent(a.n, l);
+        q1[k] = cube_level_ptr(a.gtex, a.gmip, a.n, C, a.tex_frames, t.f, l + 1u);
+        slot[k][4] = qg_slot(tb, off1 + hi[k].i00), slot[k][5] = qg_slot(tb, off1 + hi[k].i01);
+        slot[k][6] = qg_slot(tb, off1 + hi[k].i10), slot[k][7] = qg_slot(tb, off1 + hi[k].i11);
+      }
+    }
+    uint32_t n_used = 0u;
+    // ---- B2. the channels, ATTR_CHUNK at a time
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 g[ATTR_CHUNK];
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (smp != 0u) {
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+          if (i >= nc) break;
+          const float *p = gg + (size_t)(c0 + i) * rc.plane;
+          if (t.whole) {
+            g[i] = *reinterpret_cast<const float4 *>(p);
+          } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (smp & (1u << k)) quad_at(g[i], k) = p[k];
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(smp & (1u << k))) continue;
+        {
+          const float tx_ = lo[k].tx, ty_ = lo[k].ty, lw = 1.0f - lod[k].f;
+          const float w00 = ((1.0f - tx_) * (1.0f - ty_)) * lw, w01 = (tx_ * (1.0f - ty_)) * lw;
+          const float w10 = ((1.0f - tx_) * ty_) * lw, w11 = (tx_ * ty_) * lw;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float gi = quad_at(g[i], k);
+              qg_add(tb, slot[k][0], q0[k], lo[k].i00, C, c0 + i, i, w00 * gi);
+              qg_add(tb, slot[k][1], q0[k], lo[k].i01, C, c0 + i, i, w01 * gi);
+              qg_add(tb, slot[k][2], q0[k], lo[k].i10, C, c0 + i, i, w10 * gi);
+              qg_add(tb, slot[k][3], q0[k], lo[k].i11, C, c0 + i, i, w11 * gi);
+            }
+        }
+        if (two & (1u << k)) {
+          const float tx_ = hi[k].tx, ty_ = hi[k].ty, lw = lod[k].f;
+          const float w00 = ((1.0f - tx_) * (1.0f - ty_)) * lw, w01 = (tx_ * (1.0f - ty_)) * lw;
+          const float w10 = ((1.0f - tx_) * ty_) * lw, w11 = (tx_ * ty_) * lw;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float gi = quad_at(g[i], k);
+              qg_add(tb, slot[k][4], q1[k], hi[k].i00, C, c0 + i, i, w00 * gi);
+              qg_add(tb, slot[k][5], q1[k], hi[k].i01, C, c0 + i, i, w01 * gi);
+              qg_add(tb, slot[k][6], q1[k], hi[k].i10, C, c0 + i, i, w10 * gi);
+              qg_add(tb, slot[k][7], q1[k], hi[k].i11, C, c0 + i, i, w11 * gi);
+            }
+        }
+      }
+      // ---- B3. the table's values of this chunk into memory: lanes in channel order within a texel (k_tex_grad's step 4)
+      __syncthreads();
+      n_used = tb.n_used;
+      for (uint32_t i = tid; i < n_used * ATTR_CHUNK; i += 256) {
+        const uint32_t s = tb.used[i / ATTR_CHUNK], e = i % ATTR_CHUNK;
+        const float v = tb.val[s * ATTR_CHUNK + e];
+        tb.val[s * ATTR_CHUNK + e] = 0.0f;
+        if (e < nc) global_add(cube_pyr_texel(a, t.f, tb.key[s] - 1u) + c0 + e, v);
+      }
+      __syncthreads();
+    }
+    // the tile's keys go; every thread has read n_used before the chunk's last barrier
+    for (uint32_t i = tid; i < n_used; i += 256) tb.key[tb.used[i]] = 0u;
+    if (tid == 0) tb.n_used = 0u;
+    __syncthreads();
+  });
+}
+
+// ================================================================================================================
+// k_cube_level — THE LEVEL OF A CUBE LOOKUP FROM ITS SCREEN-SPACE FOOTPRINT (srz_frameset_cube_level, include/srz.h states the rule):
+// pointwise, no LDS, no barrier, k_cube's walk.  Per sampled pixel the direction's face, s, t and 1 / ma (cube_face), the derivative
+// of s and t per one-pixel step in x and in y from the six derivative planes interpolate_deriv wrote for the direction — the
+// quotient rule on sc / ma, tc / ma with the face held fixed —, scaled to texels of level 0 (n / 2 texels per unit of s), then
+// k_tex_mip's level rule word for word (mip_lod) and lam = (float)l0 + f.
+// ================================================================================================================
+__global__ __launch_bounds__(256) void k_cube_level(CubeMipArgs a) {
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool fused = t.fused(a.flags_or);
+    uint32_t id[4];
+    const uint32_t own = quad_ids(t, a.vis + (size_t)t.f * a.vis_stride + t.poff, id);
+    if (own == 0u && !fused) return;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 lq[1] = {zero4}; // nobody, and an owner that is not sampled: 0
+    if (own != 0u) {
+      float4 d[3] = {zero4, zero4, zero4}, dd[6] = {zero4, zero4, zero4, zero4, zero4, zero4};
+      quad_load(a.dir + (size_t)t.f * a.dir_stride + t.poff, t.rc.plane, d, t.whole, t.x4, t.rc.tx1);
+      quad_load(a.dird + (size_t)t.f * (2u * a.dir_stride) + t.poff, t.rc.plane, dd, t.whole, t.x4, t.rc.tx1);
+      const float half_n = 0.5f * (float)a.n;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(own & (1u << k))) continue;
+        CubeFace c;
+        if (!cube_face(quad_at(d[0], k), quad_at(d[1], k), quad_at(d[2], k), c.s, c.t, c.inv, c.major)) continue;
+        const uint32_t m = c.major & 3u;
+        const bool pos = (c.major & 4u) != 0u;
+        float ds[2], dt[2]; // d s, d t per step in x, in y
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const float vx = quad_at(dd[0 + e], k), vy = quad_at(dd[2 + e], k), vz = quad_at(dd[4 + e], k);
+          // the components su, sv and the major axis name, with sc's, tc's and ma's sign flips (cube_face)
+          const float dsc = m == 0u ? (pos ? -vz : vz) : m == 1u ? vx : (pos ? vx : -vx);
+          const float dtc = m == 1u ? (pos ? vz : -vz) : -vy;
+          const float dmc = m == 0u ? vx : m == 1u ? vy : vz, dma = pos ? dmc : -dmc;
+          ds[e] = (dsc - c.s * dma) * c.inv, dt[e] = (dtc - c.t * dma) * c.inv;
+        }
+        const MipLod r = mip_lod(ds[0], ds[1], dt[0], dt[1], half_n, half_n, a.n_levels);
+        quad_at(lq[0], k) = (float)r.l0 + r.f;
+      }
+    }
+    quad_store_owned(t.out, t, lq, fused, own);
+  });
+}
+
+// ================================================================================================================
 // k_shadow — A CALLER'S DEPTH MAP COMPARED AND FILTERED OVER A VISIBILITY BUFFER (srz_frameset_shadow, include/srz.h states the rule):
 // percentage-closer filtering of a float map [map frame][row][column] at the coordinate planes sx, sy, sd interpolate wrote for a
 // three-channel attribute: the four texels around (sx, sy) are each compared with sd — the hard test, or with width > 0 a linear ramp
@@ -7374,6 +7845,9 @@ void launch_persp_grad(const PerspArgs &a, hipStream_t s) { launch_pass<k_persp_
 void launch_interp_deriv_persp(const PerspDerivArgs &a, hipStream_t s) { launch_pass<k_interp_deriv_persp>(a, s); }
 void launch_tex_mip(const TexMipArgs &a, hipStream_t s) { launch_pass<k_tex_mip>(a, s); }
 void launch_tex_mip_grad(const TexMipArgs &a, hipStream_t s) { launch_pass<k_tex_mip_grad>(a, s); }
+void launch_cube_mip(const CubeMipArgs &a, hipStream_t s) { launch_pass<k_cube_mip>(a, s); }
+void launch_cube_mip_grad(const CubeMipArgs &a, hipStream_t s) { launch_pass<k_cube_mip_grad>(a, s); }
+void launch_cube_level(const CubeMipArgs &a, hipStream_t s) { launch_pass<k_cube_level>(a, s); }
 // a workgroup per row of the level written (build) or of level 0 (fold), at most MIP_GRID of them striding over the rows
 constexpr uint32_t MIP_GRID = 8192;
 void launch_mip_build(const float *src, float *dst, uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h, uint32_t n_ch,

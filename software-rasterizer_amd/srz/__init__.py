@@ -32,6 +32,8 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_texture_mip_levels", "srz_texture_mip_bytes", "srz_texture_mip_build", "srz_texture_mip_fold",
            "srz_frameset_interpolate_deriv", "srz_frameset_texture_mip", "srz_frameset_texture_mip_grad",
            "srz_frameset_texture_cube", "srz_frameset_texture_cube_grad",
+           "srz_cube_mip_levels", "srz_cube_mip_bytes", "srz_cube_mip_build", "srz_cube_mip_fold",
+           "srz_frameset_texture_cube_mip", "srz_frameset_texture_cube_mip_grad", "srz_frameset_cube_level",
            "srz_frameset_light", "srz_frameset_light_work_bytes", "srz_frameset_light_grad",
            "srz_frameset_shadow", "srz_frameset_shadow_grad",
            "srz_frameset_perspective", "srz_frameset_perspective_grad", "srz_frameset_interpolate_deriv_persp",
@@ -115,6 +117,15 @@ def lib():
         L.srz_frameset_texture_mip_grad.argtypes = abi.TEXTURE_MIP_GRAD_ARGTYPES
         L.srz_frameset_texture_cube.argtypes = abi.TEXTURE_CUBE_ARGTYPES
         L.srz_frameset_texture_cube_grad.argtypes = abi.TEXTURE_CUBE_GRAD_ARGTYPES
+        L.srz_cube_mip_levels.argtypes = abi.CUBE_MIP_LEVELS_ARGTYPES
+        L.srz_cube_mip_levels.restype = C.c_uint32
+        L.srz_cube_mip_bytes.argtypes = abi.CUBE_MIP_BYTES_ARGTYPES
+        L.srz_cube_mip_bytes.restype = C.c_size_t
+        L.srz_cube_mip_build.argtypes = abi.CUBE_MIP_BUILD_ARGTYPES
+        L.srz_cube_mip_fold.argtypes = abi.CUBE_MIP_FOLD_ARGTYPES
+        L.srz_frameset_texture_cube_mip.argtypes = abi.TEXTURE_CUBE_MIP_ARGTYPES
+        L.srz_frameset_texture_cube_mip_grad.argtypes = abi.TEXTURE_CUBE_MIP_GRAD_ARGTYPES
+        L.srz_frameset_cube_level.argtypes = abi.CUBE_LEVEL_ARGTYPES
         L.srz_frameset_light.argtypes = abi.LIGHT_ARGTYPES
         L.srz_frameset_light_work_bytes.argtypes = abi.LIGHT_WORK_BYTES_ARGTYPES
         L.srz_frameset_light_work_bytes.restype = C.c_size_t
@@ -193,6 +204,17 @@ def mip_bytes(tex_w, tex_h, n_ch, tex_frames, n_levels):
     """bytes of the levels 1 .. n_levels - 1, level-major, each [tex_frames][h_l][w_l][n_ch] float32; 0 for n_levels <= 1 or an
     argument out of range.  No GPU involved."""
     return int(lib().srz_texture_mip_bytes(tex_w, tex_h, n_ch, tex_frames, n_levels))
+
+
+def cube_mip_levels(n):
+    """the levels of the mip pyramid of a cube with n x n faces, level 0 included: mip_levels(n, n).  No GPU involved."""
+    return int(lib().srz_cube_mip_levels(n))
+
+
+def cube_mip_bytes(n, n_ch, tex_frames, n_levels):
+    """bytes of the levels 1 .. n_levels - 1 of a cube's pyramid, level-major, each [tex_frames][6][n_l][n_l][n_ch] float32; 0 for
+    n_levels <= 1 or an argument out of range (6 * tex_frames above 65536 among them).  No GPU involved."""
+    return int(lib().srz_cube_mip_bytes(n, n_ch, tex_frames, n_levels))
 
 
 class FrameSet:
@@ -423,6 +445,36 @@ class FrameSet:
                                                              C.c_void_p(d_gout_ptr), C.c_void_p(d_tex_ptr or None), n, n_ch, tex_frames,
                                                              C.c_void_p(d_gtex_ptr or None), C.c_void_p(d_gdir_ptr or None), flags,
                                                              _stream(stream)))
+
+    def texture_cube_mip(self, d_vis_ptr, d_dir_ptr, d_lam_ptr, d_tex_ptr, n, n_ch, tex_frames, d_mip_ptr, n_levels, d_out_ptr, out_bytes,
+                         flags=abi.FUSED_CLEAR, stream=None):
+        """texture_cube() over a mip pyramid of the cube: the lookup blended between the two levels around the per-pixel level of
+        detail d_lam [frame][1][local_rows][width] (the caller's: a roughness, or cube_level's footprint level), over the n_levels
+        levels of d_tex (level 0) and d_mip (Context.cube_mip_build's pyramid, or the caller's own in that layout) → d_out
+        [frame][n_ch][local_rows][width] (include/srz.h states the rule).  n_levels == 1 is texture_cube itself (d_lam_ptr and
+        d_mip_ptr may be None).  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_texture_cube_mip(
+            self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_dir_ptr), C.c_void_p(d_lam_ptr or None), C.c_void_p(d_tex_ptr), n, n_ch,
+            tex_frames, C.c_void_p(d_mip_ptr or None), n_levels, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def texture_cube_mip_grad(self, d_vis_ptr, d_dir_ptr, d_lam_ptr, d_gout_ptr, d_tex_ptr, d_mip_ptr, n, n_ch, tex_frames, n_levels,
+                              d_gtex_ptr, d_gmip_ptr, d_gdir_ptr, d_glam_ptr, flags=abi.FUSED_CLEAR, stream=None):
+        """the backward of texture_cube_mip: d_gout → ADDED into d_gtex (level 0) and d_gmip (the pyramid's layout; the two come
+        together when n_levels > 1; float atomics: not bit-reproducible; Context.cube_mip_fold then folds d_gmip into d_gtex for a
+        box-built pyramid) and / or written to d_gdir [frame][3][local_rows][width] and d_glam [frame][1][local_rows][width] (the
+        gradients with respect to the direction and to the level, deterministic; they need d_tex_ptr and, at n_levels > 1,
+        d_mip_ptr).  Output pointers may be None / 0, not all.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_texture_cube_mip_grad(
+            self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_dir_ptr), C.c_void_p(d_lam_ptr or None), C.c_void_p(d_gout_ptr),
+            C.c_void_p(d_tex_ptr or None), C.c_void_p(d_mip_ptr or None), n, n_ch, tex_frames, n_levels, C.c_void_p(d_gtex_ptr or None),
+            C.c_void_p(d_gmip_ptr or None), C.c_void_p(d_gdir_ptr or None), C.c_void_p(d_glam_ptr or None), flags, _stream(stream)))
+
+    def cube_level(self, d_vis_ptr, d_dir_ptr, d_dird_ptr, n, n_levels, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """the level of detail of a cube lookup from its screen-space footprint: the direction planes d_dir and their derivative planes
+        d_dird [frame][6][local_rows][width] (interpolate_deriv's at n_ch = 3) for a cube of n x n faces with n_levels levels → the
+        plane d_out [frame][1][local_rows][width] texture_cube_mip takes as d_lam (include/srz.h states the rule).  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_cube_level(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_dir_ptr), C.c_void_p(d_dird_ptr),
+                                                      n, n_levels, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
 
     def shadow(self, d_vis_ptr, d_sc_ptr, d_map_ptr, map_w, map_h, map_frames, bias, width, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR,
                stream=None):
@@ -716,6 +768,18 @@ class Context:
         fma per element; a gather, deterministic).  Asynchronous."""
         self._check(lib().srz_texture_mip_fold(self.h, C.c_void_p(d_gmip_ptr), mip_bytes, tex_w, tex_h, n_ch, tex_frames, n_levels,
                                                C.c_void_p(d_gtex_ptr), _stream(stream)))
+
+    def cube_mip_build(self, d_tex_ptr, n, n_ch, tex_frames, n_levels, d_mip_ptr, mip_bytes, stream=None):
+        """the levels 1 .. n_levels - 1 of the float32 cube [tex_frames][6][n][n][n_ch] at d_tex_ptr → d_mip_ptr (srz.cube_mip_bytes
+        bytes, level-major), every face box-filtered on its own: mip_build on the cube as 6 * tex_frames textures.  Asynchronous."""
+        self._check(lib().srz_cube_mip_build(self.h, C.c_void_p(d_tex_ptr), n, n_ch, tex_frames, n_levels, C.c_void_p(d_mip_ptr), mip_bytes,
+                                             _stream(stream)))
+
+    def cube_mip_fold(self, d_gmip_ptr, mip_bytes, n, n_ch, tex_frames, n_levels, d_gtex_ptr, stream=None):
+        """the backward of cube_mip_build: the gradient pyramid at d_gmip_ptr folded into the level-0 gradient at d_gtex_ptr (mip_fold
+        on the cube as 6 * tex_frames textures; deterministic).  Asynchronous."""
+        self._check(lib().srz_cube_mip_fold(self.h, C.c_void_p(d_gmip_ptr), mip_bytes, n, n_ch, tex_frames, n_levels, C.c_void_p(d_gtex_ptr),
+                                            _stream(stream)))
 
     def mesh_upload(self, mesh_id, verts8, faces):
         """verts8: (nV,8) float32 [pos3 nrm3 uv2]; faces: (nF,3) uint32."""

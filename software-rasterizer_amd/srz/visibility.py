@@ -885,6 +885,173 @@ def texture_mip(fs, vis, tex, uv, uvd, wrap=False, n_levels=None, stream=None):
     return _TextureMip.apply(tex, uv, fs, vis, uvd, wrap, n_levels, stream)
 
 
+def _cube_mip_dims(cube_shape, n_levels):
+    """(tex_frames, n, n_ch, n_levels) of a cube shape [6, N, N, C] or [frames, 6, N, N, C]; n_levels None: every level there is"""
+    from . import cube_mip_levels
+    if len(cube_shape) not in (4, 5) or cube_shape[-4] != 6 or cube_shape[-3] != cube_shape[-2]:
+        raise ValueError(f"cube_mip: a cube is [6, N, N, C] or [frames, 6, N, N, C], got {tuple(cube_shape)}")
+    tex_frames = cube_shape[0] if len(cube_shape) == 5 else 1
+    n, n_ch = cube_shape[-2], cube_shape[-1]
+    most = cube_mip_levels(n)
+    n_levels = most if n_levels is None else n_levels
+    if most == 0 or not 1 <= n_levels <= most:
+        raise ValueError(f"cube_mip: a cube of {n} x {n} faces has {most} levels, {n_levels} asked for")
+    return tex_frames, n, n_ch, n_levels
+
+
+def cube_mip_build(ctx_or_fs, cube, n_levels=None, stream=None):
+    """the mip pyramid of a CUDA float32 cube [6, N, N, C] or [frames, 6, N, N, C]: the levels 1 .. n_levels - 1 (None: every level
+    srz.cube_mip_levels counts) as ONE flat float32 tensor, level-major (cube_mip_views takes it apart); every face box-filtered on
+    its own, deterministic (Context.cube_mip_build).  ctx_or_fs: the Context, or a FrameSet of it."""
+    from . import cube_mip_bytes
+    ctx = getattr(ctx_or_fs, "ctx", ctx_or_fs)
+    if cube.dtype != torch.float32 or not cube.is_cuda:
+        raise ValueError(f"cube_mip_build: cube must be a CUDA float32 tensor, got {tuple(cube.shape)} {cube.dtype}")
+    cube = cube.contiguous()
+    tex_frames, n, n_ch, n_levels = _cube_mip_dims(tuple(cube.shape), n_levels)
+    nbytes = cube_mip_bytes(n, n_ch, tex_frames, n_levels)
+    mip = torch.empty((nbytes // 4,), dtype=torch.float32, device=cube.device)
+    if n_levels > 1:
+        ctx.cube_mip_build(cube.data_ptr(), n, n_ch, tex_frames, n_levels, mip.data_ptr(), nbytes, _stream_ptr(stream))
+    return mip
+
+
+def cube_mip_views(mip, cube_shape, n_levels=None):
+    """the levels 1 .. n_levels - 1 of a cube's flat pyramid (cube_mip_build's, a caller's own, or a gradient pyramid) as views
+    [6, n_l, n_l, C] or [frames, 6, n_l, n_l, C], in level order; cube_shape: the shape of level 0"""
+    tex_frames, n, n_ch, n_levels = _cube_mip_dims(tuple(cube_shape), n_levels)
+    views, off = [], 0
+    for l in range(1, n_levels):
+        nl = n >> l
+        k = tex_frames * 6 * nl * nl * n_ch
+        views.append(mip[off:off + k].view((tex_frames, 6, nl, nl, n_ch) if len(cube_shape) == 5 else (6, nl, nl, n_ch)))
+        off += k
+    return views
+
+
+def _lam_arg(fs, lam, n_levels):
+    if n_levels == 1 and lam is None:
+        return None
+    if lam is None or lam.dtype != torch.float32 or not lam.is_cuda or tuple(lam.shape) != tuple(fs.interpolate_shape(1)):
+        raise ValueError(f"texture_cube_mip: lam must be a CUDA float32 tensor {fs.interpolate_shape(1)}")
+    return lam.contiguous()
+
+
+def _cube_mip_arg(mip, n, n_ch, tex_frames, n_levels):
+    from . import cube_mip_bytes
+    nbytes = cube_mip_bytes(n, n_ch, tex_frames, n_levels)
+    if n_levels > 1 and (mip.dtype != torch.float32 or not mip.is_cuda or mip.dim() != 1 or mip.numel() * 4 != nbytes):
+        raise ValueError(f"texture_cube_mip: mip must be a flat CUDA float32 tensor of {nbytes // 4} elements (cube_mip_build's layout)")
+    return mip.contiguous()
+
+
+def cube_level(fs, vis, dirs, dird, n, n_levels, stream=None):
+    """the level of detail of texture_cube_mip from the lookup's screen-space footprint: dirs [n_frames, 3, rows, W] and dird
+    [n_frames, 6, rows, W] = interpolate_deriv(fs, vis, attr) (or interpolate_deriv_persp) of the [T, 3, 3] attribute dirs came from,
+    for a cube of n x n faces with n_levels levels → lam [n_frames, 1, rows, W] float32 (FrameSet.cube_level; include/srz.h states
+    the rule), zeros where nobody owns the pixel or its direction is not sampled.  Not differentiable: the footprint level is held
+    fixed.  stream: a raw stream handle, None = torch's current stream."""
+    dirs = _dirs_arg(fs, dirs.detach())
+    if dird.dtype != torch.float32 or not dird.is_cuda or tuple(dird.shape) != tuple(fs.interpolate_shape(6)):
+        raise ValueError(f"cube_level: dird must be a CUDA float32 tensor {fs.interpolate_shape(6)}, got {tuple(dird.shape)} {dird.dtype}")
+    dird = dird.detach().contiguous()
+    out = torch.empty(fs.interpolate_shape(1), dtype=torch.float32, device=dirs.device)
+    fs.cube_level(vis.data_ptr(), dirs.data_ptr(), dird.data_ptr(), n, n_levels, out.data_ptr(), fs.interpolate_bytes(1), abi.FUSED_CLEAR,
+                  _stream_ptr(stream))
+    return out
+
+
+def texture_cube_mip_grad(fs, vis, cube, dirs, lam, gout, n_levels=None, mip=None, want_gtex=True, want_gdir=True, want_glam=True, fold=True,
+                          stream=None):
+    """the backward of texture_cube_mip(fs, vis, cube, dirs, lam, n_levels, mip) by one FrameSet.texture_cube_mip_grad call: gout
+    [n_frames, C, rows, W] → (gtex, gdir, glam), each None when not wanted (not all).  gtex has cube's shape: the adds to level 0
+    and, with fold (one Context.cube_mip_fold call — right for a box-built pyramid), the gradient pyramid folded into it — float
+    atomics into zeros, not bit-reproducible; fold=False returns (gtex, gmip, gdir, glam) with the level-0 adds and the flat
+    gradient pyramid apart: a caller-made pyramid's own gradient.  gdir [n_frames, 3, rows, W] and glam [n_frames, 1, rows, W] are
+    deterministic.  mip: the pyramid the forward read (built here with cube_mip_build when gdir or glam needs it and none is
+    given)."""
+    if not want_gtex and not want_gdir and not want_glam:
+        raise ValueError("texture_cube_mip_grad: no gradient is asked for")
+    from . import cube_mip_bytes
+    cube, dirs, gout = cube.detach().contiguous(), _dirs_arg(fs, dirs.detach()), gout.contiguous()
+    tex_frames, n, n_ch = _cube_dims(fs, cube)
+    n_levels = _cube_mip_dims(tuple(cube.shape), n_levels)[3]
+    lam = _lam_arg(fs, None if lam is None else lam.detach(), n_levels)
+    if tuple(gout.shape) != tuple(fs.interpolate_shape(n_ch)) or gout.dtype != torch.float32:
+        raise ValueError(f"texture_cube_mip_grad: gout must be float32 {fs.interpolate_shape(n_ch)}, got {tuple(gout.shape)} {gout.dtype}")
+    s = _stream_ptr(stream)
+    nbytes = cube_mip_bytes(n, n_ch, tex_frames, n_levels)
+    if n_levels > 1:
+        if mip is not None:
+            mip = _cube_mip_arg(mip.detach(), n, n_ch, tex_frames, n_levels)
+        elif want_gdir or want_glam:
+            mip = cube_mip_build(fs, cube, n_levels, stream)
+    gtex = torch.zeros_like(cube) if want_gtex else None
+    gmip = torch.zeros((nbytes // 4,), dtype=torch.float32, device=cube.device) if want_gtex and n_levels > 1 else None
+    gdir = torch.empty_like(dirs) if want_gdir else None
+    glam = torch.empty(fs.interpolate_shape(1), dtype=torch.float32, device=cube.device) if want_glam else None
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    fs.texture_cube_mip_grad(vis.data_ptr(), dirs.data_ptr(), ptr(lam), gout.data_ptr(), cube.data_ptr(), ptr(mip) if n_levels > 1 else None, n, n_ch,
+                             tex_frames, n_levels, ptr(gtex), ptr(gmip), ptr(gdir), ptr(glam), abi.FUSED_CLEAR, s)
+    if not fold:
+        return gtex, gmip, gdir, glam
+    if gmip is not None:
+        fs.ctx.cube_mip_fold(gmip.data_ptr(), nbytes, n, n_ch, tex_frames, n_levels, gtex.data_ptr(), s)
+    return gtex, gdir, glam
+
+
+class _TextureCubeMip(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cube, dirs, lam, mip, fs, vis, n_levels, stream):
+        cube, dirs = cube.contiguous(), _dirs_arg(fs, dirs)
+        tex_frames, n, n_ch = _cube_dims(fs, cube)
+        n_levels = _cube_mip_dims(tuple(cube.shape), n_levels)[3]
+        lam = _lam_arg(fs, lam, n_levels)
+        own_mip = mip is not None  # the caller's pyramid: an input with a gradient of its own, no fold
+        if n_levels == 1:
+            mip_ = None
+        elif own_mip:
+            mip_ = _cube_mip_arg(mip, n, n_ch, tex_frames, n_levels)
+        else:
+            mip_ = cube_mip_build(fs, cube, n_levels, stream)
+        out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=cube.device)
+        fs.texture_cube_mip(vis.data_ptr(), dirs.data_ptr(), lam.data_ptr() if lam is not None else None, cube.data_ptr(), n, n_ch, tex_frames,
+                            mip_.data_ptr() if mip_ is not None else None, n_levels, out.data_ptr(), fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR,
+                            _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.n_levels, ctx.stream, ctx.own_mip, ctx.mip, ctx.lam = fs, vis, n_levels, stream, own_mip, mip_, lam
+        ctx.save_for_backward(cube, dirs)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        cube, dirs = ctx.saved_tensors
+        need_cube, need_dir, need_lam, need_mip = ctx.needs_input_grad[:4]
+        need_lam = need_lam and ctx.lam is not None
+        need_mip = need_mip and ctx.own_mip and ctx.n_levels > 1
+        gtex = gmip = gdir = glam = None
+        if need_cube or need_mip or need_dir or need_lam:  # one call, asking only for what is needed; the fold for a pyramid built inside
+            if ctx.own_mip:
+                gtex, gmip, gdir, glam = texture_cube_mip_grad(ctx.fs, ctx.vis, cube, dirs, ctx.lam, gout, ctx.n_levels, ctx.mip,
+                                                               need_cube or need_mip, need_dir, need_lam, False, ctx.stream)
+            else:
+                gtex, gdir, glam = texture_cube_mip_grad(ctx.fs, ctx.vis, cube, dirs, ctx.lam, gout, ctx.n_levels, ctx.mip, need_cube, need_dir,
+                                                         need_lam, True, ctx.stream)
+        return (gtex if need_cube else None, gdir, glam, gmip if need_mip else None, None, None, None, None)
+
+
+def texture_cube_mip(fs, vis, cube, dirs, lam, n_levels=None, mip=None, stream=None):
+    """texture_cube(fs, vis, cube, dirs) over a mip pyramid of the cube, blended between the two levels around lam
+    [n_frames, 1, rows, W] — the caller's per-pixel level of detail: a roughness scaled to levels for a prefiltered probe, or
+    cube_level's footprint level — by the rule include/srz.h states; n_levels None: every level srz.cube_mip_levels(N) counts; 1:
+    texture_cube itself (lam may be None).  mip None: the forward builds the box-filtered pyramid (cube_mip_build) and the backward
+    folds its gradient into cube.grad; a caller's mip (cube_mip_build's layout, e.g. GGX-prefiltered levels): cube and mip are
+    separate differentiable inputs, no fold.  Differentiable with respect to cube and mip (float atomics: not bit-reproducible
+    between runs), to dirs and to lam (deterministic; lam's is the right-hand derivative c_(l0+1) - c_l0, zero outside
+    [0, n_levels - 1)).  Backward is one texture_cube_mip_grad call that asks only for the outputs some input needs.  stream: a raw
+    stream handle, None = torch's current stream."""
+    return _TextureCubeMip.apply(cube, dirs, lam, mip, fs, vis, n_levels, stream)
+
+
 def _scene_draws(fs):
     """per frame of a sceneset the mesh slots of its draws, in draw order"""
     if not all(isinstance(f, abi.SceneFrame) for f in fs.frames):
