@@ -72,6 +72,8 @@ extern "C" {
  *      (additive, same version) mipmapped cube-map lookup by direction and level, with gradients srz_cube_mip_levels /
  *      srz_cube_mip_bytes / srz_cube_mip_build / srz_cube_mip_fold / srz_frameset_texture_cube_mip /
  *      srz_frameset_texture_cube_mip_grad / srz_frameset_cube_level
+ *      (additive, same version) tangent-space normal mapping over a visibility buffer, with gradients srz_mesh_tangents /
+ *      srz_mesh_tangents_grad / srz_frameset_normal_map / srz_frameset_normal_map_grad
  */
 #define SRZ_ABI_VERSION 7
 
@@ -288,6 +290,49 @@ int srz_mesh_normals(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos
  * overlapping the positions' or d_gnrm's span, or each other. */
 int srz_mesh_normals_grad(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, const float *d_gnrm,
                           uint32_t gnrm_stride, float *d_work, float *d_gpos, void *stream);
+/* VERTEX TANGENTS AND HANDEDNESS of a slot's faces FROM POSITIONS AND UV, ON THE DEVICE: srz_mesh_normals' sibling, for tangent-space
+ * normal mapping (srz_frameset_normal_map).  d_pos, pos_stride, n_sets: as srz_mesh_normals (null: the slot's own positions, n_sets
+ * must be 1).  d_uv: ONE uv set of n_verts entries shared by every position set, vertex v at float v * uv_stride, uv_stride >= 2; null
+ * selects the slot's own uv (floats 6..7 of its records, stride 8).  d_tan: per set and vertex, at float (s * n_verts + v) * tan_stride,
+ * tan_stride >= 4, FOUR floats: the unit tangent (x, y, z) and the handedness w = +-1 — a 4-channel attribute for
+ * srz_sceneset_corner_attr.  There is no in-place record form: a vertex record has no tangent field, d_tan must not be null.
+ * THE RULE, in float32, nothing fused, in this order, dot3 and the list order as srz_mesh_normals has them.  Per set and vertex v, with
+ * p the set's positions:
+ *   S = (+0, +0, +0);  D = +0;  for corner c in list(v):  (i0, i1, i2) = faces[c / 3]
+ *     e1 = p[i1] - p[i0];  e2 = p[i2] - p[i0]
+ *     du1 = uv[i1].u - uv[i0].u;  dv1 = uv[i1].v - uv[i0].v;  du2 = uv[i2].u - uv[i0].u;  dv2 = uv[i2].v - uv[i0].v
+ *     det = du1 * dv2 - du2 * dv1
+ *     Tf  = e1 * dv2 - e2 * dv1        (componentwise; = det * dP/du: a face weighs in by its uv area)
+ *     s   = det < 0 ? -1 : +1
+ *     S = S + s * Tf;   D = D + det
+ *   len2 = dot3(S, S)
+ *   len2 > 0 && len2 <= FLT_MAX:  r = 1.0f / sqrtf(len2);  t = S * r          (v is NORMALISED)
+ *   otherwise:                    t = (+0, +0, +0)        (no face names v, all uv equal, a NaN, an overflow, an underflow)
+ *   w = D < 0 ? -1 : +1
+ * The face's terms are taken in the face's OWN vertex order whichever corner asks.  So t points along +u whether or not the uv are
+ * mirrored, and with a normal N that follows the winding (srz_mesh_normals') w * cross(N, t) points along +v.  A gather, no atomics:
+ * DETERMINISTIC, bit for bit.  The other floats of a strided record are not touched.  Asynchronous on `stream`.  No input value makes
+ * the pass read or write outside its buffers.
+ * SRZ_E_INVALID, nothing written and nothing launched, for what srz_mesh_normals refuses of ctx, mesh_id, n_sets, d_pos and pos_stride,
+ * and for: uv_stride below 2 (of a non-null d_uv); a null d_tan; tan_stride below 4; a pointer that is not 4-byte aligned; tangents
+ * whose span overlaps the positions' or the uv's span. */
+int srz_mesh_tangents(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, const float *d_uv,
+                      uint32_t uv_stride, float *d_tan, uint32_t tan_stride, void *stream);
+/* THE BACKWARD of srz_mesh_tangents, TO THE POSITIONS ONLY: uv, s and w are held fixed.  d_gtan: the gradient with respect to the
+ * tangents, laid out like d_tan with gtan_stride >= 4; its w float is NEVER READ.  d_gpos: [n_sets][n_verts][3], EVERY element
+ * written; d_work: a workspace of the same size whose contents afterwards are unspecified.  Two phases, both gathers:
+ *   PHASE 1, per set and vertex v:  S, r, t as above;  g = d_gtan[s][v].xyz
+ *     v normalised:  d = dot3(t, g);  gS[v] = (g - t * d) * r;     otherwise:  gS[v] = (+0, +0, +0)
+ *   PHASE 2, per set and vertex v:  acc = (+0, +0, +0);  for corner c in list(v), in list order:
+ *     (i0, i1, i2) = faces[c / 3];  dv1, dv2, s as above;  k = c % 3;  G = (gS[i0] + gS[i1]) + gS[i2]
+ *     k == 0:  co = s * (dv1 - dv2);   k == 1:  co = s * dv2;   k == 2:  co = -(s * dv1);     acc = acc + G * co
+ *     d_gpos[s][v] = acc
+ * No atomics: DETERMINISTIC, bit for bit.  Non-finite values propagate as IEEE has them.  Asynchronous on `stream`.
+ * SRZ_E_INVALID, nothing written and nothing launched, for what srz_mesh_tangents refuses of ctx, mesh_id, n_sets, d_pos, pos_stride,
+ * d_uv and uv_stride, and for: a null d_gtan, d_work or d_gpos; gtan_stride below 4; a pointer that is not 4-byte aligned; d_work or
+ * d_gpos overlapping the positions', the uv's or d_gtan's span, or each other. */
+int srz_mesh_tangents_grad(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, const float *d_uv,
+                           uint32_t uv_stride, const float *d_gtan, uint32_t gtan_stride, float *d_work, float *d_gpos, void *stream);
 
 /* ---- draw = TraditionalRasterizer::draw(TRIANGLES) for one scene ----------------------
  * z/c0/c1/c2: W*H floats each, in/out (m_zBuffer, m_channels[0..2]); draw never clears unless
@@ -807,6 +852,48 @@ size_t srz_frameset_light_work_bytes(srz_ctx *ctx, srz_frameset *fs, uint32_t n_
 int srz_frameset_light_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos, const void *d_kd,
                             const float *d_par, uint32_t n_lights, uint32_t par_frames, uint32_t p, const void *d_gout, void *d_gnrm,
                             void *d_gpos, void *d_gkd, float *d_gpar, void *d_work, size_t work_bytes, uint32_t flags, void *stream);
+/* TANGENT-SPACE NORMAL MAPPING over a visibility buffer, for the caller's own planes, and its gradients: the interpolated normal, the
+ * interpolated tangent with its handedness (srz_mesh_tangents through srz_sceneset_corner_attr and srz_frameset_interpolate at 4
+ * channels) and a tangent-space normal m, AS THE CALLER DECODED IT (srz_frameset_texture's output, or a learned map that stores signed
+ * values), give the unit shading normal srz_frameset_light and srz_frameset_texture_cube take.  Nothing of the built-in BUMP shader.
+ * d_vis: a visibility buffer of THIS set on this ctx's shard.  d_nrm, d_m, d_out, d_gout, d_gnrm, d_gm: [frame][3][local_rows][width]
+ * float32, srz_frameset_interpolate_bytes(3) bytes each; d_tan, d_gtan: [frame][4][local_rows][width], _interpolate_bytes(4).  Band
+ * sharding, local_rows, stream semantics, asynchrony, the 16-byte alignment, owner and nobody, what a nobody pixel's words of the
+ * output planes become with and without SRZ_FUSED_CLEAR (zeros; untouched): all as srz_frameset_light.  The words of the input planes
+ * at nobody's pixels never reach a result.
+ * THE RULE, all of it float32, nothing fused except where fmaf is written, / and sqrtf the correctly rounded ones, always the exact
+ * arithmetic (SRZ_OPT_APPROX_SHADE has no effect).  dot(a, b) = fmaf(ax, bx, fmaf(ay, by, az * bz));  cross(u, w) = (u.y w.z - u.z w.y,
+ * u.z w.x - u.x w.z, u.x w.y - u.y w.x);  a vector times a scalar is three products.  Per owned pixel with the normal n, the tangent t
+ * (t.xyz, t.w) and m:
+ *   nn = dot(n, n);  !(nn > 0 && nn < INFINITY) -> out = (0, 0, 0) (written), every gradient of the pixel 0     (light: not lit)
+ *   inl = 1 / sqrtf(nn);  N = n * inl
+ *   d = dot(N, t.xyz);  Tp = t.xyz - N * d;  tt = dot(Tp, Tp)
+ *   !(tt > 0 && tt < INFINITY) -> out = N                                          (no frame: the unperturbed normal)
+ *   it = 1 / sqrtf(tt);  T = Tp * it;  hw = t.w < 0 ? -1 : +1;  B = cross(N, T) * hw
+ *   R_c = fmaf(m.x, T_c, fmaf(m.y, B_c, m.z * N_c));  rr = dot(R, R)
+ *   !(rr > 0 && rr < INFINITY) -> out = N
+ *   ir = 1 / sqrtf(rr);  out = R * ir
+ * BACKWARD: the exact derivative of the rule with its branches held, in THIS order of operations (g = gout of the pixel):
+ *   out = R * ir:   dq = dot(g, out);  gR_c = (g_c - out_c * dq) * ir
+ *                   gm = (dot(gR, T), dot(gR, B), dot(gR, N))
+ *                   gT_c = m.x * gR_c;  gC_c = (m.y * gR_c) * hw;  gN_c = m.z * gR_c
+ *                   gN = gN + cross(T, gC);  gT = gT + cross(gC, N)
+ *                   dT = dot(gT, T);  gTp_c = (gT_c - T_c * dT) * it;  gd = -dot(gTp, N)
+ *                   gN_c = (gN_c - gTp_c * d) + gd * t_c;   gt_c = gTp_c + gd * N_c;   gt.w = +0
+ *   out = N:        gN = g;  gt = (0, 0, 0, 0);  gm = (0, 0, 0)
+ *   then both:      dn = dot(gN, N);  gn_c = (gN_c - N_c * dn) * inl
+ *   d_gnrm = gn, d_gtan = gt (four planes, the w plane +0: there is no gradient to the handedness), d_gm = gm: per pixel,
+ *   deterministic, bit for bit.  Each may be NULL, not all three.  d_gtan has the layout srz_frameset_interpolate_grad takes as d_gout
+ *   at 4 channels, d_gm the one srz_frameset_texture_grad takes.
+ * SUBNORMALS are numbers; non-finite m and gradients propagate as IEEE has them (a NaN in m makes rr a NaN: out = N); no value of any
+ * plane makes a pass read or write outside its buffers.  No LDS, no atomics.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set, d_vis, d_nrm, d_tan, d_m, d_out, d_gout, or all of
+ * d_gnrm, d_gtan, d_gm; a short out_bytes; a misaligned pointer; any bit of `flags` but SRZ_FUSED_CLEAR; an output that overlaps an
+ * input or another output. */
+int srz_frameset_normal_map(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_tan, const void *d_m,
+                            void *d_out, size_t out_bytes, uint32_t flags, void *stream);
+int srz_frameset_normal_map_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_tan, const void *d_m,
+                                 const void *d_gout, void *d_gnrm, void *d_gtan, void *d_gm, uint32_t flags, void *stream);
 /* SHADOW-MAP LOOKUP over a visibility buffer, and its gradients: PERCENTAGE-CLOSER FILTERING of a float32 depth map of the caller's
  * own at caller coordinates — the four texels around (sx, sy) are each COMPARED with the pixel's depth sd, and the four results are
  * blended bilinearly — and the backward of that, to the map and to the coordinates.  `width` turns the hard depth test into a linear

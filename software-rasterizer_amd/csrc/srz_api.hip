@@ -752,7 +752,7 @@ int stats_pass(srz_ctx *ctx, srz_frameset *fs, const float *d_start, uint32_t fl
 
 } // namespace
 
-// The passes over a visibility buffer (srz_frameset_shade_visibility .. srz_frameset_light_grad): what their entry points share.
+// The passes over a visibility buffer (srz_frameset_shade_visibility .. srz_frameset_normal_map_grad): what their entry points share.
 // Each entry point is its own argument rules, these checks, its own Args fields, the launch.
 namespace {
 
@@ -1458,6 +1458,61 @@ int srz_mesh_normals_grad(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_
   a.gnrm = d_gnrm, a.gnrm_stride = gnrm_stride, a.work = d_work, a.gpos = d_gpos;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   launch_mesh_normals_grad(a, pick_stream(ctx, stream));
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
+// What srz_mesh_tangents and srz_mesh_tangents_grad check alike (check_mesh_normals, and the uv set); on success the slot's lists and
+// the resolved positions and uv are in `a`, *pos_span and *uv_span the bytes they reach over.
+static int check_mesh_tangents(srz_ctx *ctx, const std::string &fn, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets,
+                               const float *d_uv, uint32_t uv_stride, MeshTangentsArgs &a, size_t *pos_span, size_t *uv_span) {
+  MeshNormalsArgs n{};
+  if (int rc = check_mesh_normals(ctx, fn, mesh_id, d_pos, pos_stride, n_sets, n, pos_span)) return rc;
+  if (d_uv && uv_stride < 2u) return fail(ctx, SRZ_E_INVALID, fn + ": uv_stride must be at least 2");
+  a.pos = n.pos, a.pos_stride = n.pos_stride, a.faces = n.faces, a.corner_off = n.corner_off, a.corners = n.corners;
+  a.n_verts = n.n_verts, a.n_sets = n.n_sets;
+  a.uv = d_uv ? d_uv : reinterpret_cast<const float *>(ctx->mesh[mesh_id].d_verts) + 6, a.uv_stride = d_uv ? uv_stride : 8u;
+  *uv_span = (((size_t)a.n_verts - 1u) * a.uv_stride + 2u) * sizeof(float);
+  return SRZ_OK;
+}
+
+int srz_mesh_tangents(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, const float *d_uv,
+                      uint32_t uv_stride, float *d_tan, uint32_t tan_stride, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_mesh_tangents");
+  MeshTangentsArgs a{};
+  size_t pos_span = 0, uv_span = 0;
+  if (int rc = check_mesh_tangents(ctx, fn, mesh_id, d_pos, pos_stride, n_sets, d_uv, uv_stride, a, &pos_span, &uv_span)) return rc;
+  if (!d_tan) return fail(ctx, SRZ_E_INVALID, fn + ": null d_tan (a vertex record has no tangent field)");
+  if (tan_stride < 4u) return fail(ctx, SRZ_E_INVALID, fn + ": tan_stride must be at least 4");
+  if (!aligned<4>({d_pos, d_uv, d_tan})) return fail(ctx, SRZ_E_INVALID, fn + ": the buffers must be 4-byte aligned");
+  const size_t tan_span = (((size_t)n_sets * a.n_verts - 1u) * tan_stride + 4u) * sizeof(float);
+  if (ranges_overlap({d_tan, tan_span}, {a.pos, pos_span}) || ranges_overlap({d_tan, tan_span}, {a.uv, uv_span}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the tangents overlap the positions or the uv");
+  a.tan = d_tan, a.tan_stride = tan_stride;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  launch_mesh_tangents(a, pick_stream(ctx, stream));
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
+int srz_mesh_tangents_grad(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, const float *d_uv,
+                           uint32_t uv_stride, const float *d_gtan, uint32_t gtan_stride, float *d_work, float *d_gpos, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_mesh_tangents_grad");
+  MeshTangentsArgs a{};
+  size_t pos_span = 0, uv_span = 0;
+  if (int rc = check_mesh_tangents(ctx, fn, mesh_id, d_pos, pos_stride, n_sets, d_uv, uv_stride, a, &pos_span, &uv_span)) return rc;
+  if (!d_gtan || !d_work || !d_gpos) return fail(ctx, SRZ_E_INVALID, fn + ": null tangent gradient / workspace / output");
+  if (gtan_stride < 4u) return fail(ctx, SRZ_E_INVALID, fn + ": gtan_stride must be at least 4");
+  if (!aligned<4>({d_pos, d_uv, d_gtan, d_work, d_gpos})) return fail(ctx, SRZ_E_INVALID, fn + ": the buffers must be 4-byte aligned");
+  const size_t packed = (size_t)n_sets * a.n_verts * 3u * sizeof(float);
+  const size_t gtan_span = (((size_t)n_sets * a.n_verts - 1u) * gtan_stride + 4u) * sizeof(float);
+  if (int rc = check_overlaps(ctx, fn, {{d_work, packed}, {d_gpos, packed}}, {{a.pos, pos_span}, {a.uv, uv_span}, {d_gtan, gtan_span}}))
+    return rc;
+  a.gtan = d_gtan, a.gtan_stride = gtan_stride, a.work = d_work, a.gpos = d_gpos;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  launch_mesh_tangents_grad(a, pick_stream(ctx, stream));
   HIP_TRY(ctx, hipGetLastError());
   return SRZ_OK;
 }
@@ -2224,6 +2279,65 @@ int srz_frameset_light_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, c
   a.gout = (const float *)d_gout, a.gnrm = (float *)d_gnrm, a.gpos = (float *)d_gpos, a.gkd = (float *)d_gkd;
   a.work = d_gpar ? (float *)d_work : nullptr;
   launch_light_grad(a, d_gpar, s);
+  return end_pass(ctx);
+}
+
+namespace {
+NormalMapArgs normal_map_args(const srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_tan, const void *d_m, void *d_out,
+                              uint32_t flags) {
+  NormalMapArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  a.nrm = (const float *)d_nrm, a.tan = (const float *)d_tan, a.m = (const float *)d_m;
+  a.vis_stride = 4ull * plane, a.frame_stride = 3ull * plane, a.tan_stride = 4ull * plane;
+  a.flags_or = flags;
+  return a;
+}
+} // namespace
+
+int srz_frameset_normal_map(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_tan, const void *d_m,
+                            void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_normal_map");
+  if (!fs || !d_vis || !d_nrm || !d_tan || !d_m || !d_out)
+    return fail(ctx, SRZ_E_INVALID,
+                fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_nrm ? "d_nrm" : !d_tan ? "d_tan" : !d_m ? "d_m" : "d_out"));
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, 3u), tan_bytes = srz_frameset_interpolate_bytes(ctx, fs, 4u),
+               vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": out_bytes is too small for d_out");
+  if (!aligned<16>({d_vis, d_nrm, d_tan, d_m, d_out}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_nrm, d_tan, d_m, d_out) must be 16-byte aligned");
+  if (int rc = check_overlaps(ctx, fn + " (d_out against d_vis, d_nrm, d_tan, d_m)", {{d_out, need}},
+                              {{d_vis, vis_bytes}, {d_nrm, need}, {d_tan, tan_bytes}, {d_m, need}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_light: caller data only)
+  launch_normal_map(normal_map_args(fs, d_vis, d_nrm, d_tan, d_m, d_out, flags), s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_normal_map_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_tan, const void *d_m,
+                                 const void *d_gout, void *d_gnrm, void *d_gtan, void *d_gm, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_normal_map_grad");
+  if (!fs || !d_vis || !d_nrm || !d_tan || !d_m || !d_gout)
+    return fail(ctx, SRZ_E_INVALID,
+                fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_nrm ? "d_nrm" : !d_tan ? "d_tan" : !d_m ? "d_m" : "d_gout"));
+  if (!d_gnrm && !d_gtan && !d_gm) return fail(ctx, SRZ_E_INVALID, fn + ": none of d_gnrm, d_gtan, d_gm is asked for");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  const size_t b3 = srz_frameset_interpolate_bytes(ctx, fs, 3u), b4 = srz_frameset_interpolate_bytes(ctx, fs, 4u),
+               vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (!aligned<16>({d_vis, d_nrm, d_tan, d_m, d_gout, d_gnrm, d_gtan, d_gm}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_nrm, d_tan, d_m, d_gout, d_gnrm, d_gtan, d_gm) must be 16-byte aligned");
+  if (int rc = check_overlaps(ctx, fn + " (d_gnrm, d_gtan, d_gm against d_vis, d_nrm, d_tan, d_m, d_gout)",
+                              {{d_gnrm, b3}, {d_gtan, b4}, {d_gm, b3}}, {{d_vis, vis_bytes}, {d_nrm, b3}, {d_tan, b4}, {d_m, b3}, {d_gout, b3}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc;
+  NormalMapArgs a = normal_map_args(fs, d_vis, d_nrm, d_tan, d_m, nullptr, flags);
+  a.gout = (const float *)d_gout, a.gnrm = (float *)d_gnrm, a.gtan = (float *)d_gtan, a.gm = (float *)d_gm;
+  launch_normal_map_grad(a, s);
   return end_pass(ctx);
 }
 

@@ -245,6 +245,24 @@ struct MeshNormalsArgs {
 };
 void launch_mesh_normals(const MeshNormalsArgs &a, hipStream_t s);
 void launch_mesh_normals_grad(const MeshNormalsArgs &a, hipStream_t s);
+// srz_mesh_tangents / srz_mesh_tangents_grad: the uv-area-weighted vertex tangents (x, y, z) and handedness w of ONE mesh slot's
+// faces over n_sets position sets and ONE uv set (k_mesh_tangents), and their backward to the positions (k_mesh_tangents_grad, two
+// launches as k_mesh_normals_grad).  Vertex v of set s starts at float (s * n_verts + v) * stride of pos / tan / gtan, uv of vertex v
+// at float v * uv_stride; work and gpos are packed [n_sets][n_verts][3].  The host has checked the strides, the spans and n_sets
+struct MeshTangentsArgs {
+  const float *pos;            // the slot's own records (stride 8) or the caller's sets
+  const float *uv;             // the slot's own records + 6 (stride 8) or the caller's one set
+  const uint32_t *faces;       // [n_faces][3]
+  const uint32_t *corner_off;  // [n_verts + 1] into corners
+  const uint32_t *corners;     // [3 * n_faces]
+  float *tan;                  // forward: the output, 4 floats a vertex
+  const float *gtan;           // backward: the gradient of the tangents (its w is never read)
+  float *work, *gpos;          // backward: gS (phase 1 writes, phase 2 reads), the output
+  uint32_t pos_stride, uv_stride, tan_stride, gtan_stride;
+  uint32_t n_verts, n_sets;
+};
+void launch_mesh_tangents(const MeshTangentsArgs &a, hipStream_t s);
+void launch_mesh_tangents_grad(const MeshTangentsArgs &a, hipStream_t s);
 // srz_sceneset_corner_attr / _corner_attr_grad: per-vertex attributes of ONE mesh slot to the set's triangle stream
 // [frame][pos_tris][3][n_ch], and the stream's gradient back to [frame][n_verts][n_ch] (k_corner_attr, k_corner_attr_grad: a thread
 // owns (frame, vertex, channel) and walks the frame's draws of the slot and the vertex's corner list).  A draw takes part when its
@@ -478,6 +496,26 @@ struct LightArgs {
 };
 void launch_light(const LightArgs &a, hipStream_t s);
 void launch_light_grad(const LightArgs &a, float *gpar, hipStream_t s);
+// srz_frameset_normal_map / _normal_map_grad: the shading normal of an interpolated normal nrm [frame][3][..], an interpolated tangent
+// with handedness tan [frame][4][..] and a tangent-space normal m [frame][3][..] (k_normal_map), and the backward of that to all
+// three (k_normal_map_grad: gnrm and gm three planes, gtan four with w written +0; each may be null).  `out` is the forward's output,
+// null in the backward, which addresses its planes by frame_stride (three planes) and tan_stride (four) itself
+struct NormalMapArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *nrm, *tan, *m;
+  float *out;
+  const float *gout;
+  float *gnrm, *gtan, *gm;
+  uint64_t vis_stride;   // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride; // floats per frame in every three-plane buffer = 3 * local_rows * width
+  uint64_t tan_stride;   // floats per frame in tan / gtan = 4 * local_rows * width
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_normal_map(const NormalMapArgs &a, hipStream_t s);
+void launch_normal_map_grad(const NormalMapArgs &a, hipStream_t s);
 // srz_frameset_shadow / _shadow_grad: a float depth map of the caller's [map frame][row][column] compared and filtered at the
 // coordinate planes sc [frame][3][local_rows][width] (sx, sy in texels, sd in the map's depth units) under a visibility buffer
 // (k_shadow), and the gradients of that with respect to the map (gmap, added into) and to the coordinates (k_shadow_grad).  vis as

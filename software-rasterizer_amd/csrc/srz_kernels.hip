@@ -738,6 +738,81 @@ template <int PHASE> __global__ __launch_bounds__(256) void k_mesh_normals_grad(
 }
 
 // ================================================================================================================
+// k_mesh_tangents / k_mesh_tangents_grad — srz_mesh_tangents and its backward (include/srz.h states the rules): k_mesh_normals'
+// shape — grid (blocks of 256 vertices, position sets), a thread OWNS (set, vertex) and walks the vertex's corner list, a gather, no
+// atomics, no barrier, plain stores, bit-reproducible.  A face's uv-area-weighted tangent s * Tf and its det are computed in the
+// face's OWN vertex order whichever corner asks.  The uv are ONE set shared by the position sets.  The backward goes to the
+// positions only (uv, s and w are held): PHASE 1 stores gS = (g - t (t . g)) r per vertex into `work`, PHASE 2 gathers, per corner
+// of the vertex, the face's G = (gS[i0] + gS[i1]) + gS[i2] times the corner's uv coefficient — no position is read there.
+// ================================================================================================================
+struct FaceUv {
+  float dv1, dv2, det, s;
+};
+__device__ __forceinline__ FaceUv face_uv(const MeshTangentsArgs &a, const uint32_t *f) {
+  const float *q0 = a.uv + (size_t)f[0] * a.uv_stride, *q1 = a.uv + (size_t)f[1] * a.uv_stride, *q2 = a.uv + (size_t)f[2] * a.uv_stride;
+  const float u0 = q0[0], v0 = q0[1];
+  const float du1 = q1[0] - u0, dv1 = q1[1] - v0, du2 = q2[0] - u0, dv2 = q2[1] - v0;
+  const float det = du1 * dv2 - du2 * dv1;
+  return FaceUv{dv1, dv2, det, det < 0.0f ? -1.0f : 1.0f};
+}
+// S and D of the rule: the sums over the vertex's corners, in list order, of s * Tf and of det, for position set `p`
+__device__ __forceinline__ F3 tangent_sum(const MeshTangentsArgs &a, const float *p, uint32_t c_begin, uint32_t c_end, float &D) {
+  F3 S{0.0f, 0.0f, 0.0f};
+  D = 0.0f;
+  for (uint32_t c = c_begin; c < c_end; ++c) {
+    const uint32_t *f = a.faces + (size_t)(a.corners[c] / 3u) * 3;
+    const F3 p0 = ldv3(p + (size_t)f[0] * a.pos_stride);
+    const F3 e1 = sub3(ldv3(p + (size_t)f[1] * a.pos_stride), p0), e2 = sub3(ldv3(p + (size_t)f[2] * a.pos_stride), p0);
+    const FaceUv q = face_uv(a, f);
+    const F3 Tf{e1.x * q.dv2 - e2.x * q.dv1, e1.y * q.dv2 - e2.y * q.dv1, e1.z * q.dv2 - e2.z * q.dv1};
+    S = add3(S, F3{q.s * Tf.x, q.s * Tf.y, q.s * Tf.z});
+    D = D + q.det;
+  }
+  return S;
+}
+__global__ __launch_bounds__(256) void k_mesh_tangents(const MeshTangentsArgs a) {
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x, set = blockIdx.y;
+  if (v >= a.n_verts) return;
+  const size_t at = (size_t)set * a.n_verts + v;
+  float D, r;
+  const F3 S = tangent_sum(a, a.pos + (size_t)set * a.n_verts * a.pos_stride, a.corner_off[v], a.corner_off[v + 1], D);
+  const bool ok = normal_scale(S, r);
+  float *t = a.tan + at * a.tan_stride;
+  t[0] = ok ? S.x * r : 0.0f, t[1] = ok ? S.y * r : 0.0f, t[2] = ok ? S.z * r : 0.0f, t[3] = D < 0.0f ? -1.0f : 1.0f;
+}
+template <int PHASE> __global__ __launch_bounds__(256) void k_mesh_tangents_grad(const MeshTangentsArgs a) {
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x, set = blockIdx.y;
+  if (v >= a.n_verts) return;
+  const size_t at = (size_t)set * a.n_verts + v;
+  const uint32_t c_begin = a.corner_off[v], c_end = a.corner_off[v + 1];
+  if (PHASE == 1) {
+    float D, r;
+    const F3 S = tangent_sum(a, a.pos + (size_t)set * a.n_verts * a.pos_stride, c_begin, c_end, D);
+    F3 gS{0.0f, 0.0f, 0.0f};
+    if (normal_scale(S, r)) {
+      const F3 t{S.x * r, S.y * r, S.z * r}, g = ldv3(a.gtan + at * a.gtan_stride);
+      const float d = dot3(t.x, t.y, t.z, g.x, g.y, g.z);
+      gS = F3{(g.x - t.x * d) * r, (g.y - t.y * d) * r, (g.z - t.z * d) * r};
+    }
+    float *w = a.work + at * 3;
+    w[0] = gS.x, w[1] = gS.y, w[2] = gS.z;
+  } else {
+    const float *gs = a.work + (size_t)set * a.n_verts * 3;
+    F3 acc{0.0f, 0.0f, 0.0f};
+    for (uint32_t c = c_begin; c < c_end; ++c) {
+      const uint32_t corner = a.corners[c], face = corner / 3u, k = corner - 3u * face;
+      const uint32_t *f = a.faces + (size_t)face * 3;
+      const F3 G = add3(add3(ldv3(gs + (size_t)f[0] * 3), ldv3(gs + (size_t)f[1] * 3)), ldv3(gs + (size_t)f[2] * 3));
+      const FaceUv q = face_uv(a, f);
+      const float co = k == 0u ? q.s * (q.dv1 - q.dv2) : k == 1u ? q.s * q.dv2 : -(q.s * q.dv1);
+      acc = add3(acc, F3{G.x * co, G.y * co, G.z * co});
+    }
+    float *g = a.gpos + at * 3;
+    g[0] = acc.x, g[1] = acc.y, g[2] = acc.z;
+  }
+}
+
+// ================================================================================================================
 // k_corner_attr / k_corner_attr_grad — srz_sceneset_corner_attr and its backward (include/srz.h).  Grid (blocks of 256 (vertex,
 // channel) pairs, frames); a thread OWNS (frame, vertex, channel): neighbouring lanes are neighbouring channels of one vertex, so
 // the attribute row, the rows of the triangle stream and the gradient row are each read and written as runs, and the backward
@@ -3304,7 +3379,7 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
 // k_cube and k_cube_grad (the walk, quad_ids, quad_store_owned), k_cube_mip, k_cube_mip_grad and k_cube_level (the same, and
 // quad_load), k_persp (the walk, quad_ids), k_persp_grad and
 // k_interp_deriv_persp (all of it), k_light (the walk, quad_ids, quad_load, quad_store_owned) and k_light_grad (the same through
-// pass_tiles and pass_tile: the tile's index names its row of partial sums).
+// pass_tiles and pass_tile: the tile's index names its row of partial sums), k_normal_map and k_normal_map_grad (as k_light).
 // COPIES, each naming this definition — a fix to the walk goes into them too: k_gbuffer, k_motion, k_pos_grad, aa_body, k_tex,
 // k_tex_grad, k_tex_mip, k_tex_mip_grad (with tex_quad and mip_quad).  Moved onto these helpers they computed the same words
 // (the whole suite passed) but ran slower than their inline text on an MI355X at 256 frames of 1024²: k_gbuffer +4 %, k_motion +6 %,
@@ -5674,6 +5749,136 @@ __global__ __launch_bounds__(64) void k_light_fold(const float *src, float *dst,
 }
 
 // ================================================================================================================
+// k_normal_map / k_normal_map_grad — TANGENT-SPACE NORMAL MAPPING OVER A VISIBILITY BUFFER, FOR CALLER DATA (srz_frameset_normal_map
+// and its backward, include/srz.h states the rule and the backward's order of operations): the interpolated normal (3 planes), the
+// interpolated tangent with its handedness (4 planes) and the tangent-space normal m (3 planes) -> the unit shading normal k_light
+// and k_cube take.  k_light's shape on the passes' helpers: pass_walk, quad_ids, the planes of a quad with an owner in 16-byte
+// loads, quad_store_owned; no LDS, no barrier, no atomics; every output is per pixel, from registers.  nm_px is the rule's text;
+// both kernels go through it, so the backward differentiates the very words the forward computed.
+// ================================================================================================================
+enum : int { NM_UNLIT = 0, NM_PLAIN = 1, NM_MAPPED = 2 }; // out = 0; out = N (no frame, or R = 0); out = R / |R|
+struct NmPx {
+  float N[3], T[3], B[3], o[3]; // o: the output
+  float inl, d, it, hw, ir;
+};
+__device__ __forceinline__ void nm_cross(const float (&u)[3], const float (&w)[3], float (&c)[3]) {
+  c[0] = u[1] * w[2] - u[2] * w[1], c[1] = u[2] * w[0] - u[0] * w[2], c[2] = u[0] * w[1] - u[1] * w[0];
+}
+__device__ __forceinline__ int nm_px(const float (&n)[3], const float (&t)[4], const float (&m)[3], NmPx &px) {
+  px.o[0] = px.o[1] = px.o[2] = 0.0f;
+  const float nn = l_dot(n, n);
+  if (!l_pos(nn)) return NM_UNLIT;
+  px.inl = l_rsqrt(nn);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) px.N[i] = n[i] * px.inl, px.o[i] = px.N[i];
+  const float t3[3] = {t[0], t[1], t[2]};
+  px.d = l_dot(px.N, t3);
+  float Tp[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) Tp[i] = t3[i] - px.N[i] * px.d;
+  const float tt = l_dot(Tp, Tp);
+  if (!l_pos(tt)) return NM_PLAIN;
+  px.it = l_rsqrt(tt), px.hw = t[3] < 0.0f ? -1.0f : 1.0f;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) px.T[i] = Tp[i] * px.it;
+  float Cr[3], R[3];
+  nm_cross(px.N, px.T, Cr);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) px.B[i] = Cr[i] * px.hw, R[i] = fmaf_(m[0], px.T[i], fmaf_(m[1], px.B[i], m[2] * px.N[i]));
+  const float rr = l_dot(R, R);
+  if (!l_pos(rr)) return NM_PLAIN;
+  px.ir = l_rsqrt(rr);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) px.o[i] = R[i] * px.ir;
+  return NM_MAPPED;
+}
+// the owners of the thread's quad and, for a quad with one, its ten input planes -> `own`
+__device__ __forceinline__ uint32_t normal_map_quad(const NormalMapArgs &a, const PassTile &t, float4 (&n)[3], float4 (&tn)[4], float4 (&m)[3]) {
+  uint32_t id[4];
+  const uint32_t own = quad_ids(t, a.vis + (size_t)t.f * a.vis_stride + t.poff, id);
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  n[0] = n[1] = n[2] = m[0] = m[1] = m[2] = tn[0] = tn[1] = tn[2] = tn[3] = zero4;
+  if (own == 0u) return own;
+  const size_t off = (size_t)t.f * a.frame_stride + t.poff;
+  quad_load(a.nrm + off, t.rc.plane, n, t.whole, t.x4, t.rc.tx1);
+  quad_load(a.tan + (size_t)t.f * a.tan_stride + t.poff, t.rc.plane, tn, t.whole, t.x4, t.rc.tx1);
+  quad_load(a.m + off, t.rc.plane, m, t.whole, t.x4, t.rc.tx1);
+  return own;
+}
+__global__ __launch_bounds__(256) void k_normal_map(NormalMapArgs a) {
+  pass_walk<false>(a, [&](const PassTile &t) {
+    const bool fused = t.fused(a.flags_or);
+    float4 n[3], tn[4], m[3];
+    const uint32_t own = normal_map_quad(a, t, n, tn, m);
+    if (own == 0u && !fused) return;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 o[3] = {zero4, zero4, zero4}; // nobody, and an owner without a normal: zeros
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (!(own & (1u << k))) continue;
+      const float nk[3] = {quad_at(n[0], k), quad_at(n[1], k), quad_at(n[2], k)}, mk[3] = {quad_at(m[0], k), quad_at(m[1], k), quad_at(m[2], k)};
+      const float tk[4] = {quad_at(tn[0], k), quad_at(tn[1], k), quad_at(tn[2], k), quad_at(tn[3], k)};
+      NmPx px;
+      nm_px(nk, tk, mk, px);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) quad_at(o[c], k) = px.o[c];
+    }
+    quad_store_owned(t.out, t, o, fused, own);
+  });
+}
+__global__ __launch_bounds__(256) void k_normal_map_grad(NormalMapArgs a) {
+  pass_walk<false>(a, [&](const PassTile &t) {
+    const bool fused = t.fused(a.flags_or);
+    float4 n[3], tn[4], m[3];
+    const uint32_t own = normal_map_quad(a, t, n, tn, m);
+    if (own == 0u && !fused) return;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const size_t off = (size_t)t.f * a.frame_stride + t.poff, off4 = (size_t)t.f * a.tan_stride + t.poff;
+    float4 g[3] = {zero4, zero4, zero4};
+    if (own != 0u) quad_load(a.gout + off, t.rc.plane, g, t.whole, t.x4, t.rc.tx1);
+    float4 gn[3] = {zero4, zero4, zero4}, gt[4] = {zero4, zero4, zero4, zero4}, gm[3] = {zero4, zero4, zero4};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (!(own & (1u << k))) continue;
+      const float nk[3] = {quad_at(n[0], k), quad_at(n[1], k), quad_at(n[2], k)}, mk[3] = {quad_at(m[0], k), quad_at(m[1], k), quad_at(m[2], k)};
+      const float tk[4] = {quad_at(tn[0], k), quad_at(tn[1], k), quad_at(tn[2], k), quad_at(tn[3], k)};
+      NmPx px;
+      const int mode = nm_px(nk, tk, mk, px);
+      if (mode == NM_UNLIT) continue;
+      float gN[3] = {quad_at(g[0], k), quad_at(g[1], k), quad_at(g[2], k)};
+      if (mode == NM_MAPPED) {
+        const float gk[3] = {gN[0], gN[1], gN[2]};
+        const float dq = l_dot(gk, px.o);
+        float gR[3], gT[3], gC[3], X[3], Y[3], gTp[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gR[c] = (gk[c] - px.o[c] * dq) * px.ir;
+        quad_at(gm[0], k) = l_dot(gR, px.T), quad_at(gm[1], k) = l_dot(gR, px.B), quad_at(gm[2], k) = l_dot(gR, px.N);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gT[c] = mk[0] * gR[c], gC[c] = (mk[1] * gR[c]) * px.hw, gN[c] = mk[2] * gR[c];
+        nm_cross(px.T, gC, X), nm_cross(gC, px.N, Y);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gN[c] = gN[c] + X[c], gT[c] = gT[c] + Y[c];
+        const float dT = l_dot(gT, px.T);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gTp[c] = (gT[c] - px.T[c] * dT) * px.it;
+        const float gd = -l_dot(gTp, px.N);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          gN[c] = (gN[c] - gTp[c] * px.d) + gd * tk[c];
+          quad_at(gt[c], k) = gTp[c] + gd * px.N[c];
+        }
+      }
+      const float dn = l_dot(gN, px.N);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) quad_at(gn[c], k) = (gN[c] - px.N[c] * dn) * px.inl;
+    }
+    if (a.gnrm) quad_store_owned(a.gnrm + off, t, gn, fused, own);
+    if (a.gtan) quad_store_owned(a.gtan + off4, t, gt, fused, own);
+    if (a.gm) quad_store_owned(a.gm + off, t, gm, fused, own);
+  });
+}
+
+// ================================================================================================================
 // k_mip_build / k_mip_fold — THE MIP PYRAMID OF A CALLER TEXTURE (srz_texture_mip_build, srz_texture_mip_fold; include/srz.h states
 // the geometry and the arithmetic).  The build is one launch per level, each from the level above it: a workgroup walks rows of the
 // level it writes, its threads the row's (texel, channel) elements — consecutive lanes, consecutive floats.  The fold is the build's
@@ -7623,6 +7828,18 @@ void launch_mesh_normals_grad(const MeshNormalsArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_mesh_normals_grad<2>, grid, dim3(256), 0, s, a);
 }
 
+void launch_mesh_tangents(const MeshTangentsArgs &a, hipStream_t s) {
+  if (a.n_sets == 0 || a.n_verts == 0) return;
+  hipLaunchKernelGGL(k_mesh_tangents, dim3((a.n_verts + 255) / 256, a.n_sets), dim3(256), 0, s, a);
+}
+
+void launch_mesh_tangents_grad(const MeshTangentsArgs &a, hipStream_t s) {
+  if (a.n_sets == 0 || a.n_verts == 0) return;
+  const dim3 grid((a.n_verts + 255) / 256, a.n_sets);
+  hipLaunchKernelGGL(k_mesh_tangents_grad<1>, grid, dim3(256), 0, s, a); // (stream order, as launch_mesh_normals_grad)
+  hipLaunchKernelGGL(k_mesh_tangents_grad<2>, grid, dim3(256), 0, s, a);
+}
+
 // (n_verts * n_ch <= 2^32 * 64: at most 2^30 blocks)
 static dim3 corner_attr_grid(const CornerAttrArgs &a) { return dim3((uint32_t)(((uint64_t)a.n_verts * a.n_ch + 255) / 256), a.n_frames); }
 void launch_corner_attr(const CornerAttrArgs &a, hipStream_t s) {
@@ -7833,6 +8050,8 @@ void launch_light_grad(const LightArgs &a, float *gpar, hipStream_t s) {
   if (a.n_frames != 0u) hipLaunchKernelGGL(k_light_fold, dim3(a.n_frames), dim3(64), 0, s, (const float *)a.work, rows, tpf, K);
   if (shared) hipLaunchKernelGGL(k_light_fold, dim3(1), dim3(64), 0, s, (const float *)rows, gpar, a.n_frames, K);
 }
+void launch_normal_map(const NormalMapArgs &a, hipStream_t s) { launch_pass<k_normal_map>(a, s); }
+void launch_normal_map_grad(const NormalMapArgs &a, hipStream_t s) { launch_pass<k_normal_map_grad>(a, s); }
 void launch_shadow(const ShadowArgs &a, hipStream_t s) { launch_pass<k_shadow>(a, s); }
 // (without gmap: the build that has no table)
 void launch_shadow_grad(const ShadowArgs &a, hipStream_t s) {

@@ -36,6 +36,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_texture_cube_mip", "srz_frameset_texture_cube_mip_grad", "srz_frameset_cube_level",
            "srz_frameset_light", "srz_frameset_light_work_bytes", "srz_frameset_light_grad",
            "srz_frameset_shadow", "srz_frameset_shadow_grad",
+           "srz_mesh_tangents", "srz_mesh_tangents_grad", "srz_frameset_normal_map", "srz_frameset_normal_map_grad",
            "srz_frameset_perspective", "srz_frameset_perspective_grad", "srz_frameset_interpolate_deriv_persp",
            "srz_target_create", "srz_target_destroy", "srz_target_clear", "srz_target_draw", "srz_target_read", "srz_target_read_bgr8"]
 
@@ -130,6 +131,10 @@ def lib():
         L.srz_frameset_light_work_bytes.argtypes = abi.LIGHT_WORK_BYTES_ARGTYPES
         L.srz_frameset_light_work_bytes.restype = C.c_size_t
         L.srz_frameset_light_grad.argtypes = abi.LIGHT_GRAD_ARGTYPES
+        L.srz_mesh_tangents.argtypes = abi.MESH_TANGENTS_ARGTYPES
+        L.srz_mesh_tangents_grad.argtypes = abi.MESH_TANGENTS_GRAD_ARGTYPES
+        L.srz_frameset_normal_map.argtypes = abi.NORMAL_MAP_ARGTYPES
+        L.srz_frameset_normal_map_grad.argtypes = abi.NORMAL_MAP_GRAD_ARGTYPES
         L.srz_frameset_shadow.argtypes = abi.SHADOW_ARGTYPES
         L.srz_frameset_shadow_grad.argtypes = abi.SHADOW_GRAD_ARGTYPES
         L.srz_frameset_perspective.argtypes = abi.PERSPECTIVE_ARGTYPES
@@ -553,6 +558,24 @@ class FrameSet:
                                                       C.c_void_p(d_gkd_ptr or None), C.c_void_p(d_gpar_ptr or None),
                                                       C.c_void_p(d_work_ptr or None), work_bytes, flags, _stream(stream)))
 
+    def normal_map(self, d_vis_ptr, d_nrm_ptr, d_tan_ptr, d_m_ptr, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """tangent-space normal mapping of the caller's planes: d_nrm [frame][3][local_rows][width] (the interpolated normal), d_tan
+        [frame][4][...] (the interpolated tangent and handedness of Context.mesh_tangents) and d_m [frame][3][...] (the tangent-space
+        normal as the caller decoded it) → d_out [frame][3][...], the unit shading normal light and texture_cube take (include/srz.h
+        states the rule).  Pixels nobody owns are zeros with FUSED_CLEAR, else left untouched; an owner whose normal has no finite
+        positive length gets zeros, one without a tangent frame the unperturbed unit normal.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_normal_map(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_nrm_ptr), C.c_void_p(d_tan_ptr),
+                                                      C.c_void_p(d_m_ptr), C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def normal_map_grad(self, d_vis_ptr, d_nrm_ptr, d_tan_ptr, d_m_ptr, d_gout_ptr, d_gnrm_ptr, d_gtan_ptr, d_gm_ptr, flags=abi.FUSED_CLEAR,
+                        stream=None):
+        """the backward of normal_map: d_gout [frame][3][local_rows][width] → written to d_gnrm, d_gm (three planes) and d_gtan (four
+        planes, the w plane +0), per pixel, deterministic.  Every output pointer may be None / 0, not all.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_normal_map_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_nrm_ptr),
+                                                           C.c_void_p(d_tan_ptr), C.c_void_p(d_m_ptr), C.c_void_p(d_gout_ptr),
+                                                           C.c_void_p(d_gnrm_ptr or None), C.c_void_p(d_gtan_ptr or None),
+                                                           C.c_void_p(d_gm_ptr or None), flags, _stream(stream)))
+
     def update_shading(self, frames):
         """new eye, ka, ks, p, kh, kn, lights, flags and batch shaders / textures for a set made from abi.Frame's, triangles untouched
         (same frame count, size, light counts, batch counts and triangles per batch).  Ordered on the context's own stream."""
@@ -807,6 +830,22 @@ class Context:
         element written; d_work: a workspace of d_gpos's size.  Two gathers, deterministic.  Asynchronous."""
         self._check(lib().srz_mesh_normals_grad(self.h, mesh_id, C.c_void_p(d_pos_ptr or None), pos_stride, n_sets, C.c_void_p(d_gnrm_ptr or None),
                                                 gnrm_stride, C.c_void_p(d_work_ptr or None), C.c_void_p(d_gpos_ptr or None), _stream(stream)))
+
+    def mesh_tangents(self, mesh_id, d_pos_ptr, pos_stride, n_sets, d_uv_ptr, uv_stride, d_tan_ptr, tan_stride, stream=None):
+        """uv-area-weighted vertex tangents (x, y, z) and handedness w = +-1 of slot mesh_id's faces for n_sets position sets and ONE
+        uv set on the device: vertex v of set s at float (s * n_verts + v) * stride of d_pos (>= 3) / d_tan (>= 4), uv of v at float
+        v * uv_stride (>= 2).  d_pos_ptr None / 0: the slot's own positions (n_sets 1), d_uv_ptr None / 0: the slot's own uv.  A
+        gather, deterministic (include/srz.h states the rule).  Asynchronous."""
+        self._check(lib().srz_mesh_tangents(self.h, mesh_id, C.c_void_p(d_pos_ptr or None), pos_stride, n_sets, C.c_void_p(d_uv_ptr or None),
+                                            uv_stride, C.c_void_p(d_tan_ptr or None), tan_stride, _stream(stream)))
+
+    def mesh_tangents_grad(self, mesh_id, d_pos_ptr, pos_stride, n_sets, d_uv_ptr, uv_stride, d_gtan_ptr, gtan_stride, d_work_ptr, d_gpos_ptr,
+                           stream=None):
+        """the backward of mesh_tangents to the positions: d_gtan (laid out like the tangents, gtan_stride >= 4, its w never read) →
+        d_gpos [n_sets][n_verts][3], every element written; d_work: a workspace of d_gpos's size.  Two gathers, deterministic."""
+        self._check(lib().srz_mesh_tangents_grad(self.h, mesh_id, C.c_void_p(d_pos_ptr or None), pos_stride, n_sets, C.c_void_p(d_uv_ptr or None),
+                                                 uv_stride, C.c_void_p(d_gtan_ptr or None), gtan_stride, C.c_void_p(d_work_ptr or None),
+                                                 C.c_void_p(d_gpos_ptr or None), _stream(stream)))
 
     def draw(self, frame, planes=None, primitive=abi.PRIMITIVE_TRIANGLES, want_stats=False):
         """TraditionalRasterizer::draw for one scene; planes (z,c0,c1,c2) are modified in place."""

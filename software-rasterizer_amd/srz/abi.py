@@ -59,6 +59,11 @@ CUBE_LEVEL_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, C.c_size_t, _u3
 LIGHT_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
 LIGHT_WORK_BYTES_ARGTYPES = [_vp, _vp, _u32]
 LIGHT_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _u32, _vp]
+# the prototypes of srz_mesh_tangents / _tangents_grad and srz_frameset_normal_map / _normal_map_grad (argtypes; all return int)
+MESH_TANGENTS_ARGTYPES = [_vp, C.c_int, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp]
+MESH_TANGENTS_GRAD_ARGTYPES = [_vp, C.c_int, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp]
+NORMAL_MAP_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _u32, _vp]
+NORMAL_MAP_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]
 # the prototypes of srz_frameset_shadow / _shadow_grad (argtypes; both return int), set by srz.lib()
 SHADOW_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, C.c_float, C.c_float, _vp, C.c_size_t, _u32, _vp]
 SHADOW_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, C.c_float, C.c_float, _vp, _vp, _u32, _vp]

@@ -749,6 +749,65 @@ def light(fs, vis, nrm, pos, kd, lights, eye, ka, ks, p, stream=None):
     return _Light.apply(nrm, pos, kd, light_params(fs, lights, eye, ka, ks), fs, vis, p, stream)
 
 
+def _normal_map_args(fs, nrm, tan, m):
+    """→ (nrm, tan, m), checked and contiguous"""
+    for name, t, n in (("nrm", nrm, 3), ("tan", tan, 4), ("m", m, 3)):
+        shape = tuple(fs.interpolate_shape(n))
+        if t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != shape:
+            raise ValueError(f"normal_map: {name} must be a CUDA float32 tensor {shape}, got {tuple(t.shape)} {t.dtype}")
+    return nrm.contiguous(), tan.contiguous(), m.contiguous()
+
+
+def normal_map_grad(fs, vis, nrm, tan, m, gout, want_gnrm=True, want_gtan=True, want_gm=True, stream=None):
+    """the backward of normal_map by one FrameSet.normal_map_grad call: gout [n_frames, 3, rows, W] → (gnrm, gtan, gm), each None when
+    not wanted (not all): gnrm and gm [n_frames, 3, rows, W], gtan [n_frames, 4, rows, W] with a zero w plane; per pixel,
+    deterministic, zeros where nobody owns the pixel.  stream: a raw stream handle, None = torch's current stream."""
+    if not (want_gnrm or want_gtan or want_gm):
+        raise ValueError("normal_map_grad: no gradient is asked for")
+    nrm, tan, m = _normal_map_args(fs, nrm, tan, m)
+    gout = gout.contiguous()
+    if tuple(gout.shape) != tuple(nrm.shape) or gout.dtype != torch.float32:
+        raise ValueError(f"normal_map_grad: gout must be float32 {tuple(nrm.shape)}, got {tuple(gout.shape)} {gout.dtype}")
+    gnrm, gtan, gm = (torch.empty_like(t) if w else None for t, w in ((nrm, want_gnrm), (tan, want_gtan), (m, want_gm)))
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    fs.normal_map_grad(vis.data_ptr(), nrm.data_ptr(), tan.data_ptr(), m.data_ptr(), gout.data_ptr(), ptr(gnrm), ptr(gtan), ptr(gm),
+                       abi.FUSED_CLEAR, _stream_ptr(stream))
+    return gnrm, gtan, gm
+
+
+class _NormalMap(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, nrm, tan, m, fs, vis, stream):
+        nrm, tan, m = _normal_map_args(fs, nrm, tan, m)
+        out = torch.empty(fs.interpolate_shape(3), dtype=torch.float32, device=nrm.device)
+        fs.normal_map(vis.data_ptr(), nrm.data_ptr(), tan.data_ptr(), m.data_ptr(), out.data_ptr(), fs.interpolate_bytes(3), abi.FUSED_CLEAR,
+                      _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.stream = fs, vis, stream
+        ctx.save_for_backward(nrm, tan, m)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        nrm, tan, m = ctx.saved_tensors
+        need = ctx.needs_input_grad[:3]
+        grads = (None, None, None)
+        if any(need):  # one call, asking only for what is needed
+            grads = normal_map_grad(ctx.fs, ctx.vis, nrm, tan, m, gout, need[0], need[1], need[2], ctx.stream)
+        return (*grads, None, None, None)
+
+
+def normal_map(fs, vis, nrm, tan, m, stream=None):
+    """tangent-space normal mapping under a visibility buffer `vis` of FrameSet `fs`: nrm [n_frames, 3, rows, W] (interpolate's normals
+    of any length), tan [n_frames, 4, rows, W] (interpolate's of mesh_tangents' 4-channel corner_attr: tangent and handedness) and m
+    [n_frames, 3, rows, W] (the tangent-space normal as the caller decoded it: texture's output, or a learned signed map) →
+    [n_frames, 3, rows, W] float32, the unit shading normal light and texture_cube take: m.x T + m.y B + m.z N normalised, T the
+    tangent made orthogonal to N, B = cross(N, T) * sign(w); zeros where nobody owns the pixel or the normal has no finite positive
+    length, the unperturbed unit normal where there is no tangent frame (FrameSet.normal_map; include/srz.h states the rule).
+    Differentiable with respect to nrm, tan and m (per pixel, deterministic; no gradient to the handedness).  Backward is one
+    normal_map_grad call that asks only for the outputs some input needs.  stream: a raw stream handle, None = torch's current stream."""
+    return _NormalMap.apply(nrm, tan, m, fs, vis, stream)
+
+
 def interpolate_deriv(fs, vis, attr, stream=None):
     """the screen-space derivatives of interpolate(fs, vis, attr): attr as interpolate takes it with C <= abi.ATTR_MAX_CH // 2 →
     [n_frames, 2 C, rows, W] float32, plane 2 ch the change of channel ch per one-pixel step in x, plane 2 ch + 1 in y — constants of
@@ -1202,6 +1261,43 @@ def mesh_normals(ctx, slot, pos, stream=None):
     directions are gathers without atomics: the values and pos.grad are bit-reproducible.  The slot's own vertices are neither read
     nor written: refresh_normals is the in-place form.  stream: a raw stream handle, None = torch's current stream."""
     return _MeshNormals.apply(pos, ctx, slot, stream)
+
+
+class _MeshTangents(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, sctx, slot, uv, stream):
+        p, n_sets = _sets_arg(sctx, slot, pos.detach(), "pos")
+        V = p.shape[-2]
+        if uv is not None:
+            if uv.dtype != torch.float32 or not uv.is_cuda or tuple(uv.shape) != (V, 2):
+                raise ValueError(f"mesh_tangents: uv must be a CUDA float32 tensor [{V}, 2], got {tuple(uv.shape)} {uv.dtype}")
+            uv = uv.detach().contiguous()
+        tan = torch.empty(p.shape[:-1] + (4,), dtype=torch.float32, device=p.device)
+        sctx.mesh_tangents(slot, p.data_ptr(), 3, n_sets, None if uv is None else uv.data_ptr(), 2, tan.data_ptr(), 4, _stream_ptr(stream))
+        ctx.sctx, ctx.slot, ctx.stream, ctx.n_sets, ctx.uv = sctx, slot, stream, n_sets, uv
+        ctx.save_for_backward(p)
+        return tan
+
+    @staticmethod
+    def backward(ctx, gtan):
+        (p,) = ctx.saved_tensors
+        gtan = gtan.contiguous()
+        work, gpos = torch.empty_like(p), torch.empty_like(p)
+        ctx.sctx.mesh_tangents_grad(ctx.slot, p.data_ptr(), 3, ctx.n_sets, None if ctx.uv is None else ctx.uv.data_ptr(), 2, gtan.data_ptr(), 4,
+                                    work.data_ptr(), gpos.data_ptr(), _stream_ptr(ctx.stream))
+        return gpos, None, None, None, None
+
+
+def mesh_tangents(ctx, slot, pos, uv=None, stream=None):
+    """the uv-area-weighted vertex tangents and handedness of mesh slot `slot` of Context `ctx` at vertex positions pos, a CUDA float32
+    tensor [V, 3] or [B, V, 3] → [V, 4] or [B, V, 4]: per vertex the unit tangent (along +u, mirrored uv or not) and w = +-1, so that
+    w * cross(normal, tangent) points along +v; a zero tangent for a vertex no face names and for a sum that is zero or not finite
+    (Context.mesh_tangents, include/srz.h states the rule).  uv: a CUDA float32 tensor [V, 2] shared by the B sets, None = the slot's
+    own uv.  Differentiable with respect to pos only (Context.mesh_tangents_grad; uv and w are held).  Both directions are gathers
+    without atomics: the values and pos.grad are bit-reproducible.  The 4-channel result is a corner_attr attribute:
+    interpolate(fs, vis, corner_attr(fs, {slot: mesh_tangents(ctx, slot, verts)})) is normal_map's tan.  stream: a raw stream handle,
+    None = torch's current stream."""
+    return _MeshTangents.apply(pos, ctx, slot, uv, stream)
 
 
 def refresh_normals(ctx, slot, stream=None):
