@@ -74,6 +74,8 @@ extern "C" {
  *      srz_frameset_texture_cube_mip_grad / srz_frameset_cube_level
  *      (additive, same version) tangent-space normal mapping over a visibility buffer, with gradients srz_mesh_tangents /
  *      srz_mesh_tangents_grad / srz_frameset_normal_map / srz_frameset_normal_map_grad
+ *      (additive, same version) Cook-Torrance GGX shading pass over a visibility buffer, with gradients srz_frameset_microfacet /
+ *      srz_frameset_microfacet_grad / srz_frameset_microfacet_work_bytes, SRZ_MICROFACET_PAR
  */
 #define SRZ_ABI_VERSION 7
 
@@ -852,6 +854,95 @@ size_t srz_frameset_light_work_bytes(srz_ctx *ctx, srz_frameset *fs, uint32_t n_
 int srz_frameset_light_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos, const void *d_kd,
                             const float *d_par, uint32_t n_lights, uint32_t par_frames, uint32_t p, const void *d_gout, void *d_gnrm,
                             void *d_gpos, void *d_gkd, float *d_gpar, void *d_work, size_t work_bytes, uint32_t flags, void *stream);
+/* COOK-TORRANCE SHADING UNDER POINT LIGHTS over a visibility buffer, for the caller's own planes, and its gradients: the
+ * metallic-roughness material the chain's other passes feed — a GGX normal distribution, the separable Schlick-Smith visibility and
+ * Schlick's Fresnel term — with PER-PIXEL roughness and metallic, both with a gradient.  A sibling of srz_frameset_light, not a change
+ * to it; like it, for caller data, nothing of the reference or of the built-in shaders, no clamp of the result, the caller's units.
+ * d_vis: a visibility buffer of THIS set on this ctx's shard.  d_nrm, d_pos, d_base (forward and backward: may be NULL, base colour
+ * (1, 1, 1)), d_out, d_gout, d_gnrm, d_gpos, d_gbase: [frame][3][local_rows][width] float32, srz_frameset_interpolate_bytes(3) bytes
+ * each.  d_mat (required) and d_gmat: [frame][2][local_rows][width], srz_frameset_interpolate_bytes(2) bytes: plane 0 the roughness,
+ * plane 1 the metallic.  d_par and d_gpar: [par_frames][SRZ_MICROFACET_PAR(n_lights)] float32 in device memory, 4-byte aligned, a
+ * parameter frame being eye[3] amb[3], then n_lights x {pos[3], intensity[3]} (srz_light's layout); par_frames is 1 or the set's frame
+ * count; 1 <= n_lights <= SRZ_LIGHT_MAX.  Band sharding, local_rows, stream semantics, asynchrony, the 16-byte alignment of the
+ * visibility buffer and every plane buffer, owner and nobody, what a nobody pixel's words of the output planes become with and without
+ * SRZ_FUSED_CLEAR (zeros; untouched), and what the passes do not read or launch: all as srz_frameset_light.  The words of the input
+ * planes at nobody's pixels never reach a result.
+ * THE RULE, all of it float32, nothing fused except where fmaf is written, / and sqrtf the correctly rounded ones, always the exact
+ * arithmetic (SRZ_OPT_APPROX_SHADE has no effect); no transcendental function.  dot, the test l_pos(x) = x > 0 && x < INFINITY and
+ * 1 / sqrtf(x) (two roundings) as in srz_frameset_light.  INV_PI = 0x1.45f306p-2f, RMIN = 0.0625f.  Per owned pixel with the normal n,
+ * the position P, the base colour base, the material (mat0, mat1):
+ *   nn, lit, inl, N, V, vv, view, iv, Vd: exactly as srz_frameset_light          (not lit -> out = (0, 0, 0) (written), no gradient, no term)
+ *   r = mat0;  rc = r > RMIN ? (r < 1 ? r : 1) : RMIN;  r_in = r > RMIN && r < 1                         (a NaN: RMIN, no gradient)
+ *   m = mat1;  mc = m > 0 ? (m < 1 ? m : 1) : 0;        m_in = m > 0 && m < 1                            (a NaN: 0, no gradient)
+ *   al = rc * rc;  a2 = al * al;  k = 0.5f * al;  omk = 1 - k;  om = 1 - mc
+ *   F0_c = fmaf(mc, base_c - 0.04f, 0.04f);  cdif_c = base_c * om
+ *   nv = view ? dot(N, Vd) : 0
+ *   acc = (0, 0, 0);  for each light in order, position lpos, intensity I:
+ *     Lv = lpos - P;  r2 = dot(Lv, Lv);  if !l_pos(r2) the light is SKIPPED at this pixel (no term, no gradient)
+ *     ir = 1 / sqrtf(r2);  Ld = Lv * ir;  att = 1 / r2;  E_c = I_c * att
+ *     nl = dot(N, Ld);  if !(nl > 0) the light adds nothing at this pixel (no term, no gradient)
+ *     Hs = Ld + Vd;  h2 = dot(Hs, Hs);  spec = view && h2 > 0 && nv > 0
+ *     spec:  ih = 1 / sqrtf(h2);  H = Hs * ih
+ *            nhr = dot(N, H);   nh = nhr > 0 ? (nhr < 1 ? nhr : 1) : 0;   vhr = dot(Vd, H);  vh = vhr > 0 ? (vhr < 1 ? vhr : 1) : 0
+ *            t = fmaf(nh * nh, a2 - 1, 1);  tt = t * t;  D = (a2 * INV_PI) / tt
+ *            gl = fmaf(nl, omk, k);  gv = fmaf(nv, omk, k);  Vs = 0.25f / (gl * gv);  DV = D * Vs
+ *            x = 1 - vh;  x2 = x * x;  x4 = x2 * x2;  x5 = x4 * x;  F_c = fmaf(1 - F0_c, x5, F0_c)
+ *            f_c = fmaf(cdif_c * INV_PI, 1 - F_c, F_c * DV)
+ *     else:  f_c = cdif_c * INV_PI
+ *     acc_c = acc_c + (f_c * E_c) * nl
+ *   out_c = fmaf(amb_c, base_c, acc_c)
+ * RMIN keeps D at or below INV_PI * 2^16; the separable visibility divides by no cosine (gl, gv >= k >= 2^-9); every clamp is a pair
+ * of comparisons, so a NaN takes the stated branch.
+ * BACKWARD: the exact derivative of the rule with its branches and clamps held, in THIS order of operations (g = gout of the pixel; a
+ * not-lit or nobody's pixel gives zeros and no term).  gN = gVd = gP = (0, 0, 0);  g_a2 = g_k = g_nv = g_om = g_mc = 0;
+ * gb_c = g_c * amb_c;  tamb_c = g_c * base_c (the amb term);  for each light that adds something, in order:
+ *     gq = g_c * nl;  gf_c = gq * E_c;  ge_c = gq * f_c;  q_c = f_c * E_c;  tI_c = ge_c * att      (the light's intensity term)
+ *     g_nl = dot(g, q);  g_att = dot(ge, I);  gLd = (0, 0, 0)
+ *     spec:  gcd_c = (gf_c * (1 - F_c)) * INV_PI;  gF_c = gf_c * (DV - cdif_c * INV_PI);  gF0_c = gF_c * (1 - x5)
+ *            gb_c = gb_c + gF0_c * mc;   g_mc = g_mc + dot(gF0, base - 0.04f)
+ *            gDV = dot(gf, F);  gD = gDV * Vs;  gVs = gDV * D
+ *            gx = dot(gF, 1 - F0) * (5 * x4);   g_vhr = vhr > 0 && vhr < 1 ? -gx : 0
+ *            gw = -(gVs * Vs);  ggl = gw / gl;  ggv = gw / gv
+ *            g_nl = fmaf(ggl, omk, g_nl);  g_nv = fmaf(ggv, omk, g_nv);  g_k = g_k + fmaf(ggl, 1 - nl, ggv * (1 - nv))
+ *            g_t = -((2 * (gD * D)) / t);  g_a2 = g_a2 + fmaf(g_t, nh * nh, gD * (INV_PI / tt))
+ *            g_nhr = nhr > 0 && nhr < 1 ? g_t * ((2 * nh) * (a2 - 1)) : 0
+ *            gH_c = fmaf(g_nhr, N_c, g_vhr * Vd_c);  gN_c = gN_c + g_nhr * H_c;  gVd_c = gVd_c + g_vhr * H_c
+ *            d = dot(gH, H);  gHs_c = (gH_c - H_c * d) * ih;  gLd_c = gHs_c;  gVd_c = gVd_c + gHs_c
+ *     else:  gcd_c = gf_c * INV_PI
+ *     g_om = g_om + dot(gcd, base);  gb_c = gb_c + gcd_c * om
+ *     gLd_c = fmaf(g_nl, N_c, gLd_c);  gN_c = gN_c + g_nl * Ld_c
+ *     d = dot(gLd, Ld);  w = 2 * -((g_att * att) * att)
+ *     tL_c = fmaf(Lv_c, w, (gLd_c - Ld_c * d) * ir)                                                 (the light's position term)
+ *     gP_c = gP_c - tL_c
+ *   then:  view:  gN_c = fmaf(g_nv, Vd_c, gN_c);  gVd_c = fmaf(g_nv, N_c, gVd_c);  d = dot(gVd, Vd)
+ *                 tE_c = (gVd_c - Vd_c * d) * iv;  gP_c = gP_c - tE_c;                 else tE = (0, 0, 0)        (the eye's term)
+ *          d = dot(gN, N);  gn_c = (gN_c - N_c * d) * inl
+ *          g_al = fmaf(g_a2, 2 * al, 0.5f * g_k);  gmat0 = r_in ? g_al * (2 * rc) : 0;  gmat1 = m_in ? g_mc - g_om : 0
+ *   d_gnrm = gn, d_gpos = gP, d_gbase = gb, d_gmat = (gmat0, gmat1): per pixel, deterministic, bit for bit.  Each may be NULL, not all
+ *   five outputs; d_gbase must be NULL when d_base is.
+ *   d_gpar (needs d_work, at least srz_frameset_microfacet_work_bytes bytes, 4-byte aligned, scratch) is WRITTEN, not added into:
+ *   entry k of a frame's row is the sum over the frame's lit pixels on this shard of the pixel's float32 term — eye: tE; amb: tamb; a
+ *   light's pos: tL, its intensity: tI (0 where the light adds nothing) — in srz_frameset_light_grad's FIXED tree, word for word (the
+ *   lane's four pixels, the xor butterfly, the four waves, the tiles in order, and with par_frames == 1 the frames in order): so d_gpar
+ *   is BIT-REPRODUCIBLE for a given shard layout, with one lit pixel in all it is that pixel's term (a term of -0 comes out +0), and
+ *   against the exact sum of the terms it lies within n 2^-24 / (1 - n 2^-24) * sum |term|, n the contributing pixels of the entry.
+ *   An entry no pixel contributes to is +0.  Ranks each write the sums of their own bands; a rank without bands writes +0.
+ * SUBNORMALS are numbers; non-finite base colours, intensities and gradients propagate as IEEE has them; no value of any plane makes
+ * a pass read or write outside its buffers.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set, d_vis, d_nrm, d_pos, d_mat, d_par, d_out, d_gout,
+ * or all of d_gnrm, d_gpos, d_gbase, d_gmat, d_gpar; n_lights == 0 or above SRZ_LIGHT_MAX; par_frames not 1 or the frame count; a
+ * short out_bytes, or work_bytes with d_gpar; a misaligned pointer; any bit of `flags` but SRZ_FUSED_CLEAR; an output (d_work with
+ * d_gpar counts as one) that overlaps an input or another output; d_gbase without d_base; d_gpar without d_work. */
+/* floats of one parameter frame: eye[3] amb[3], then n_lights x {pos[3], intensity[3]} (srz_light's layout) */
+#define SRZ_MICROFACET_PAR(n_lights) (6u + 6u * (n_lights))
+int srz_frameset_microfacet(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos, const void *d_base,
+                            const void *d_mat, const float *d_par, uint32_t n_lights, uint32_t par_frames, void *d_out, size_t out_bytes,
+                            uint32_t flags, void *stream);
+size_t srz_frameset_microfacet_work_bytes(srz_ctx *ctx, srz_frameset *fs, uint32_t n_lights);
+int srz_frameset_microfacet_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos,
+                                 const void *d_base, const void *d_mat, const float *d_par, uint32_t n_lights, uint32_t par_frames,
+                                 const void *d_gout, void *d_gnrm, void *d_gpos, void *d_gbase, void *d_gmat, float *d_gpar, void *d_work,
+                                 size_t work_bytes, uint32_t flags, void *stream);
 /* TANGENT-SPACE NORMAL MAPPING over a visibility buffer, for the caller's own planes, and its gradients: the interpolated normal, the
  * interpolated tangent with its handedness (srz_mesh_tangents through srz_sceneset_corner_attr and srz_frameset_interpolate at 4
  * channels) and a tangent-space normal m, AS THE CALLER DECODED IT (srz_frameset_texture's output, or a learned map that stores signed

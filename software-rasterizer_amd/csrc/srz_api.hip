@@ -2283,6 +2283,104 @@ int srz_frameset_light_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, c
 }
 
 namespace {
+// what srz_frameset_microfacet and _microfacet_grad check alike (check_light without the exponent, in its words); the parameter
+// block's bytes in *par_bytes
+int check_microfacet(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, uint32_t n_lights, uint32_t par_frames, uint32_t flags,
+                     size_t *par_bytes) {
+  if (n_lights == 0u || n_lights > SRZ_LIGHT_MAX) return fail(ctx, SRZ_E_INVALID, fn + ": n_lights must be 1 .. SRZ_LIGHT_MAX");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  if (par_frames != 1u && par_frames != (uint32_t)fs->n_frames)
+    return fail(ctx, SRZ_E_INVALID, fn + ": par_frames must be 1 or the set's frame count");
+  *par_bytes = (size_t)par_frames * SRZ_MICROFACET_PAR(n_lights) * sizeof(float);
+  return SRZ_OK;
+}
+MicrofacetArgs microfacet_args(const srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos, const void *d_base,
+                               const void *d_mat, const float *d_par, uint32_t n_lights, uint32_t par_frames, void *d_out, uint32_t flags) {
+  MicrofacetArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  a.nrm = (const float *)d_nrm, a.pos = (const float *)d_pos, a.base = (const float *)d_base, a.mat = (const float *)d_mat, a.par = d_par;
+  a.vis_stride = 4ull * plane, a.frame_stride = 3ull * plane, a.mat_stride = 2ull * plane;
+  a.par_stride = par_frames == 1u ? 0ull : (uint64_t)SRZ_MICROFACET_PAR(n_lights);
+  a.n_lights = n_lights;
+  a.flags_or = flags;
+  return a;
+}
+} // namespace
+
+int srz_frameset_microfacet(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos, const void *d_base,
+                            const void *d_mat, const float *d_par, uint32_t n_lights, uint32_t par_frames, void *d_out, size_t out_bytes,
+                            uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_microfacet");
+  if (!fs || !d_vis || !d_nrm || !d_pos || !d_mat || !d_par || !d_out)
+    return fail(ctx, SRZ_E_INVALID,
+                fn + ": null " +
+                    (!fs ? "frameset" : !d_vis ? "d_vis" : !d_nrm ? "d_nrm" : !d_pos ? "d_pos" : !d_mat ? "d_mat" : !d_par ? "d_par" : "d_out"));
+  size_t par_bytes = 0;
+  if (int rc = check_microfacet(ctx, fs, fn, n_lights, par_frames, flags, &par_bytes)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, 3u), mat_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u),
+               vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": out_bytes is too small for d_out");
+  if (!aligned<16>({d_vis, d_nrm, d_pos, d_base, d_mat, d_out}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_nrm, d_pos, d_base, d_mat, d_out) must be 16-byte aligned");
+  if (!aligned<4>({d_par})) return fail(ctx, SRZ_E_INVALID, fn + ": d_par must be 4-byte aligned");
+  if (int rc = check_overlaps(ctx, fn + " (d_out against d_vis, d_nrm, d_pos, d_base, d_mat, d_par)", {{d_out, need}},
+                              {{d_vis, vis_bytes}, {d_nrm, need}, {d_pos, need}, {d_base, need}, {d_mat, mat_bytes}, {d_par, par_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_light: caller data only)
+  launch_microfacet(microfacet_args(fs, d_vis, d_nrm, d_pos, d_base, d_mat, d_par, n_lights, par_frames, d_out, flags), s);
+  return end_pass(ctx);
+}
+
+size_t srz_frameset_microfacet_work_bytes(srz_ctx *ctx, srz_frameset *fs, uint32_t n_lights) {
+  if (!ctx || !fs || n_lights == 0u || n_lights > SRZ_LIGHT_MAX) return 0;
+  // [frame][tile][K] partial sums, and [frame][K] rows for the fold of a shared parameter frame
+  return (size_t)fs->n_frames * ((size_t)fs->n_local_bands * fs->tiles_x + 1u) * SRZ_MICROFACET_PAR(n_lights) * sizeof(float);
+}
+
+int srz_frameset_microfacet_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos,
+                                 const void *d_base, const void *d_mat, const float *d_par, uint32_t n_lights, uint32_t par_frames,
+                                 const void *d_gout, void *d_gnrm, void *d_gpos, void *d_gbase, void *d_gmat, float *d_gpar, void *d_work,
+                                 size_t work_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_microfacet_grad");
+  if (!fs || !d_vis || !d_nrm || !d_pos || !d_mat || !d_par || !d_gout)
+    return fail(ctx, SRZ_E_INVALID,
+                fn + ": null " +
+                    (!fs ? "frameset" : !d_vis ? "d_vis" : !d_nrm ? "d_nrm" : !d_pos ? "d_pos" : !d_mat ? "d_mat" : !d_par ? "d_par" : "d_gout"));
+  if (!d_gnrm && !d_gpos && !d_gbase && !d_gmat && !d_gpar)
+    return fail(ctx, SRZ_E_INVALID, fn + ": none of d_gnrm, d_gpos, d_gbase, d_gmat, d_gpar is asked for");
+  if (d_gbase && !d_base) return fail(ctx, SRZ_E_INVALID, fn + ": d_gbase needs d_base");
+  if (d_gpar && !d_work) return fail(ctx, SRZ_E_INVALID, fn + ": d_gpar needs d_work");
+  size_t par_bytes = 0;
+  if (int rc = check_microfacet(ctx, fs, fn, n_lights, par_frames, flags, &par_bytes)) return rc;
+  const size_t plane_bytes = srz_frameset_interpolate_bytes(ctx, fs, 3u), mat_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u),
+               vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  const size_t need_work = d_gpar ? srz_frameset_microfacet_work_bytes(ctx, fs, n_lights) : 0;
+  if (work_bytes < need_work) return fail(ctx, SRZ_E_INVALID, fn + ": work_bytes is below srz_frameset_microfacet_work_bytes");
+  if (!aligned<16>({d_vis, d_nrm, d_pos, d_base, d_mat, d_gout, d_gnrm, d_gpos, d_gbase, d_gmat}))
+    return fail(ctx, SRZ_E_INVALID,
+                fn + ": the plane buffers (d_vis, d_nrm, d_pos, d_base, d_mat, d_gout, d_gnrm, d_gpos, d_gbase, d_gmat) must be 16-byte aligned");
+  if (!aligned<4>({d_par, d_gpar, d_gpar ? d_work : nullptr})) return fail(ctx, SRZ_E_INVALID, fn + ": d_par, d_gpar and d_work must be 4-byte aligned");
+  if (int rc = check_overlaps(
+          ctx, fn + " (d_gnrm, d_gpos, d_gbase, d_gmat, d_gpar, d_work against d_vis, d_nrm, d_pos, d_base, d_mat, d_par, d_gout)",
+          {{d_gnrm, plane_bytes}, {d_gpos, plane_bytes}, {d_gbase, plane_bytes}, {d_gmat, mat_bytes}, {d_gpar, par_bytes},
+           {d_gpar ? d_work : nullptr, need_work}},
+          {{d_vis, vis_bytes}, {d_nrm, plane_bytes}, {d_pos, plane_bytes}, {d_base, plane_bytes}, {d_mat, mat_bytes}, {d_par, par_bytes},
+           {d_gout, plane_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc;
+  MicrofacetArgs a = microfacet_args(fs, d_vis, d_nrm, d_pos, d_base, d_mat, d_par, n_lights, par_frames, nullptr, flags);
+  a.gout = (const float *)d_gout, a.gnrm = (float *)d_gnrm, a.gpos = (float *)d_gpos, a.gbase = (float *)d_gbase, a.gmat = (float *)d_gmat;
+  a.work = d_gpar ? (float *)d_work : nullptr;
+  launch_microfacet_grad(a, d_gpar, s);
+  return end_pass(ctx);
+}
+
+namespace {
 NormalMapArgs normal_map_args(const srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_tan, const void *d_m, void *d_out,
                               uint32_t flags) {
   NormalMapArgs a{};

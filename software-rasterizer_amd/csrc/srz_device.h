@@ -496,6 +496,32 @@ struct LightArgs {
 };
 void launch_light(const LightArgs &a, hipStream_t s);
 void launch_light_grad(const LightArgs &a, float *gpar, hipStream_t s);
+// srz_frameset_microfacet / _microfacet_grad: Cook-Torrance (GGX, Schlick-Smith, Schlick Fresnel; metallic-roughness) under point
+// lights for caller data.  nrm, pos, base (may be null: ones), out, gout and the backward's gnrm, gpos, gbase (each may be null) are
+// [frame][3][local_rows][width]; mat and gmat (may be null) [frame][2][local_rows][width]: roughness, metallic; par is
+// [par frames][SRZ_MICROFACET_PAR(n_lights)]: eye[3] amb[3], then per light pos[3] intensity[3].  `out` is the forward's output,
+// null in the backward (which addresses its planes by frame_stride and mat_stride itself).  work: as LightArgs', K =
+// SRZ_MICROFACET_PAR(n_lights)
+struct MicrofacetArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *nrm, *pos, *base, *mat;
+  const float *par;
+  float *out;
+  const float *gout;
+  float *gnrm, *gpos, *gbase, *gmat;
+  float *work;
+  uint64_t vis_stride;   // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride; // floats per frame in every three-plane buffer = 3 * local_rows * width
+  uint64_t mat_stride;   // floats per frame in mat / gmat = 2 * local_rows * width
+  uint64_t par_stride;   // floats per frame in par = SRZ_MICROFACET_PAR(n_lights); 0: one parameter frame for every frame
+  uint32_t n_lights;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_microfacet(const MicrofacetArgs &a, hipStream_t s);
+void launch_microfacet_grad(const MicrofacetArgs &a, float *gpar, hipStream_t s);
 // srz_frameset_normal_map / _normal_map_grad: the shading normal of an interpolated normal nrm [frame][3][..], an interpolated tangent
 // with handedness tan [frame][4][..] and a tangent-space normal m [frame][3][..] (k_normal_map), and the backward of that to all
 // three (k_normal_map_grad: gnrm and gm three planes, gtan four with w written +0; each may be null).  `out` is the forward's output,

@@ -3379,7 +3379,7 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
 // k_cube and k_cube_grad (the walk, quad_ids, quad_store_owned), k_cube_mip, k_cube_mip_grad and k_cube_level (the same, and
 // quad_load), k_persp (the walk, quad_ids), k_persp_grad and
 // k_interp_deriv_persp (all of it), k_light (the walk, quad_ids, quad_load, quad_store_owned) and k_light_grad (the same through
-// pass_tiles and pass_tile: the tile's index names its row of partial sums), k_normal_map and k_normal_map_grad (as k_light).
+// pass_tiles and pass_tile: the tile's index names its row of partial sums), k_normal_map and k_normal_map_grad (as k_light), k_microfacet and k_microfacet_grad (as k_light and k_light_grad).
 // COPIES, each naming this definition — a fix to the walk goes into them too: k_gbuffer, k_motion, k_pos_grad, aa_body, k_tex,
 // k_tex_grad, k_tex_mip, k_tex_mip_grad (with tex_quad and mip_quad).  Moved onto these helpers they computed the same words
 // (the whole suite passed) but ran slower than their inline text on an MI355X at 256 frames of 1024²: k_gbuffer +4 %, k_motion +6 %,
@@ -5749,6 +5749,336 @@ __global__ __launch_bounds__(64) void k_light_fold(const float *src, float *dst,
 }
 
 // ================================================================================================================
+// k_microfacet — COOK-TORRANCE UNDER POINT LIGHTS OVER A VISIBILITY BUFFER, FOR CALLER DATA (srz_frameset_microfacet, include/srz.h
+// states the rule): the normal, position and base colour planes, a two-plane material (roughness, metallic) and a parameter frame
+// (eye, amb, then the lights) -> three colour planes.  GGX distribution, separable Schlick-Smith visibility, Schlick Fresnel; no
+// transcendental function: /, sqrtf, fmaf and a fifth power by multiplication.  k_light's shape on the passes' helpers: pass_walk,
+// quad_ids, quad_load, quad_store_owned; no LDS, no barrier.  The parameter frame is wave-uniform: scalar loads.
+// mf_px (what a lit pixel keeps across the lights: light_px's part, then the material) and mf_term (one light at one pixel) are the
+// rule's text; k_microfacet and k_microfacet_grad both go through them.
+// ================================================================================================================
+#define MF_INV_PI 0x1.45f306p-2f
+#define MF_RMIN 0.0625f
+struct MfPx {
+  LightPx g; // N, P, Vd, inl, iv, view: light_px's, exactly
+  float base[3], F0[3], cdif[3];
+  float rc, mc, al, a2, k, omk, om, nv;
+  bool r_in, m_in;
+};
+struct MfTerm {
+  float Lv[3], Ld[3], H[3], E[3], F[3], f[3];
+  float ir, att, ih, nl, nhr, nh, vhr, vh, t, tt, D, gl, gv, Vs, DV, x4, x5;
+  bool spec;
+};
+// false: not lit
+__device__ __forceinline__ bool mf_px(const float (&n)[3], const float (&P)[3], const float (&base)[3], float r, float m,
+                                      const SRZ_CAS float *par, MfPx &px) {
+  if (!light_px(n, P, par, px.g)) return false;
+  px.rc = r > MF_RMIN ? (r < 1.0f ? r : 1.0f) : MF_RMIN, px.r_in = r > MF_RMIN && r < 1.0f;
+  px.mc = m > 0.0f ? (m < 1.0f ? m : 1.0f) : 0.0f, px.m_in = m > 0.0f && m < 1.0f;
+  px.al = px.rc * px.rc, px.a2 = px.al * px.al, px.k = 0.5f * px.al, px.omk = 1.0f - px.k, px.om = 1.0f - px.mc;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    px.base[c] = base[c];
+    px.F0[c] = fmaf_(px.mc, base[c] - 0.04f, 0.04f);
+    px.cdif[c] = base[c] * px.om;
+  }
+  px.nv = px.g.view ? l_dot(px.g.N, px.g.Vd) : 0.0f;
+  return true;
+}
+// lp: the light's {pos[3], intensity[3]}.  false: the light adds nothing at this pixel (skipped, or nl not above 0)
+__device__ __forceinline__ bool mf_term(const MfPx &px, const SRZ_CAS float *lp, MfTerm &t) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t.Lv[i] = lp[i] - px.g.P[i];
+  const float r2 = l_dot(t.Lv, t.Lv);
+  if (!l_pos(r2)) return false;
+  t.ir = l_rsqrt(r2), t.att = 1.0f / r2;
+  float Hs[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t.Ld[i] = t.Lv[i] * t.ir, Hs[i] = t.Ld[i] + px.g.Vd[i], t.E[i] = lp[3 + i] * t.att;
+  t.nl = l_dot(px.g.N, t.Ld);
+  if (!(t.nl > 0.0f)) return false;
+  const float h2 = l_dot(Hs, Hs);
+  t.spec = px.g.view && h2 > 0.0f && px.nv > 0.0f;
+  if (t.spec) {
+    t.ih = l_rsqrt(h2);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t.H[i] = Hs[i] * t.ih;
+    t.nhr = l_dot(px.g.N, t.H), t.nh = t.nhr > 0.0f ? (t.nhr < 1.0f ? t.nhr : 1.0f) : 0.0f;
+    t.vhr = l_dot(px.g.Vd, t.H), t.vh = t.vhr > 0.0f ? (t.vhr < 1.0f ? t.vhr : 1.0f) : 0.0f;
+    t.t = fmaf_(t.nh * t.nh, px.a2 - 1.0f, 1.0f), t.tt = t.t * t.t, t.D = (px.a2 * MF_INV_PI) / t.tt;
+    t.gl = fmaf_(t.nl, px.omk, px.k), t.gv = fmaf_(px.nv, px.omk, px.k), t.Vs = 0.25f / (t.gl * t.gv);
+    t.DV = t.D * t.Vs;
+    const float x = 1.0f - t.vh, x2 = x * x;
+    t.x4 = x2 * x2, t.x5 = t.x4 * x;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      t.F[c] = fmaf_(1.0f - px.F0[c], t.x5, px.F0[c]);
+      t.f[c] = fmaf_(px.cdif[c] * MF_INV_PI, 1.0f - t.F[c], t.F[c] * t.DV);
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) t.f[c] = px.cdif[c] * MF_INV_PI;
+  }
+  return true;
+}
+// what k_microfacet and k_microfacet_grad do alike in front of the lights: the owners (`own`, one bit per pixel) and the planes of a quad
+// with an owner (base: ones without a base colour buffer) — mf_quad_load —, then pixel k's MfPx — mf_quad_px; false: not owned or not lit
+struct MfQuad {
+  float4 n[3], P[3], b[3], m[2];
+  uint32_t own;
+};
+__device__ __forceinline__ void mf_quad_load(const MicrofacetArgs &a, const PassTile &t, MfQuad &q) {
+  uint32_t id[4];
+  q.own = quad_ids(t, a.vis + (size_t)t.f * a.vis_stride + t.poff, id);
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f), one4 = make_float4(1.f, 1.f, 1.f, 1.f);
+  q.n[0] = q.n[1] = q.n[2] = q.P[0] = q.P[1] = q.P[2] = q.m[0] = q.m[1] = zero4, q.b[0] = q.b[1] = q.b[2] = one4;
+  if (q.own == 0u) return;
+  const size_t off = (size_t)t.f * a.frame_stride + t.poff;
+  quad_load(a.nrm + off, t.rc.plane, q.n, t.whole, t.x4, t.rc.tx1);
+  quad_load(a.pos + off, t.rc.plane, q.P, t.whole, t.x4, t.rc.tx1);
+  if (a.base) quad_load(a.base + off, t.rc.plane, q.b, t.whole, t.x4, t.rc.tx1);
+  quad_load(a.mat + (size_t)t.f * a.mat_stride + t.poff, t.rc.plane, q.m, t.whole, t.x4, t.rc.tx1);
+}
+__device__ __forceinline__ bool mf_quad_px(const MfQuad &q, int k, const SRZ_CAS float *par, MfPx &px) { // (k: a constant)
+  if (!(q.own & (1u << k))) return false;
+  const float nk[3] = {quad_at(q.n[0], k), quad_at(q.n[1], k), quad_at(q.n[2], k)}, Pk[3] = {quad_at(q.P[0], k), quad_at(q.P[1], k), quad_at(q.P[2], k)};
+  const float bk[3] = {quad_at(q.b[0], k), quad_at(q.b[1], k), quad_at(q.b[2], k)};
+  return mf_px(nk, Pk, bk, quad_at(q.m[0], k), quad_at(q.m[1], k), par, px);
+}
+__global__ __launch_bounds__(256) void k_microfacet(MicrofacetArgs a) {
+  const uint32_t L = a.n_lights;
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool fused = t.fused(a.flags_or);
+    const SRZ_CAS float *par = as_const(a.par) + (size_t)t.f * a.par_stride;
+    MfQuad q;
+    mf_quad_load(a, t, q);
+    const uint32_t own = q.own;
+    if (own == 0u && !fused) return;
+    MfPx px[4];
+    uint32_t lit = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (mf_quad_px(q, k, par, px[k])) lit |= 1u << k;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 o[3] = {zero4, zero4, zero4}; // nobody, and an owner that is not lit: zeros
+    if (lit != 0u) {
+      for (uint32_t l = 0; l < L; ++l) {
+        const SRZ_CAS float *lp = par + 6u + 6u * l;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (!(lit & (1u << k))) continue;
+          MfTerm lt;
+          if (!mf_term(px[k], lp, lt)) continue;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) quad_at(o[c], k) = quad_at(o[c], k) + (lt.f[c] * lt.E[c]) * lt.nl;
+        }
+      }
+      const float amb[3] = {par[3], par[4], par[5]};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(lit & (1u << k))) continue;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) quad_at(o[c], k) = fmaf_(amb[c], px[k].base[c], quad_at(o[c], k));
+      }
+    }
+    quad_store_owned(t.out, t, o, fused, own);
+  });
+}
+
+// ================================================================================================================
+// k_microfacet_grad — THE BACKWARD OF k_microfacet (srz_frameset_microfacet_grad; include/srz.h fixes the order of operations): gout ->
+// the gradient planes of the normal, the position, the base colour and the material (per pixel, from registers, deterministic), and,
+// WANT_PAR, the gradient of the parameter frame in k_light_grad's fixed tree, word for word: a thread's four pixels left to right, the
+// xor butterfly, the four waves through LDS, a row of work per tile; k_light_fold sums the tiles.  The lights are the OUTER loop: a
+// light's six lane sums are reduced and put into LDS as its iteration ends; eye and amb follow after the loop.  pass_tiles / pass_tile:
+// every thread of the workgroup reaches every shuffle and barrier, one outside the frame owns nothing.  A tile without a lit pixel
+// (one barrier tells) writes +0 partials and skips the lights.  The planes-only build has no LDS, no shuffle and no barrier, and walks
+// the quad TWO PIXELS AT A TIME (the lights' loop twice): a pixel's arithmetic is the same words either way, and half the live state
+// fits two waves per SIMD where four pixels at once overflow the 256 VGPRs into the accumulator file at one wave.
+// ================================================================================================================
+template <bool WANT_PAR> __global__ __launch_bounds__(256) void k_microfacet_grad(MicrofacetArgs a) {
+  __shared__ float s_part[WANT_PAR ? 4 : 1][WANT_PAR ? SRZ_MICROFACET_PAR(SRZ_LIGHT_MAX) : 1];
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  const uint32_t L = a.n_lights, K = SRZ_MICROFACET_PAR(L), tpf = a.n_local_bands * a.tiles_x;
+  pass_tiles(a, [&](uint32_t f, uint32_t ti) {
+    const PassTile t = pass_tile(a, f, ti);
+    const bool fused = t.fused(a.flags_or);
+    const SRZ_CAS float *par = as_const(a.par) + (size_t)f * a.par_stride;
+    const size_t off = (size_t)f * a.frame_stride + t.poff, moff = (size_t)f * a.mat_stride + t.poff;
+    // ---- 1. owners and planes; then, PIX pixels of the quad at a time (planes only: two — half the registers, two waves per SIMD —;
+    //         with the parameter sums: all four, a lane's sums of a light being over its four pixels): the lit pixels, gout
+    MfQuad quad;
+    mf_quad_load(a, t, quad);
+    const uint32_t own = quad.own;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 g[3] = {zero4, zero4, zero4};
+    float4 gN[3] = {zero4, zero4, zero4}, gVd[3] = {zero4, zero4, zero4}, gP[3] = {zero4, zero4, zero4}, gb[3] = {zero4, zero4, zero4};
+    float4 g_a2 = zero4, g_k = zero4, g_nv = zero4, g_om = zero4, g_mc = zero4;
+    float4 gn[3] = {zero4, zero4, zero4}, gm[2] = {zero4, zero4};
+    const float amb[3] = {par[3], par[4], par[5]};
+    float te[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; // this lane's sums of eye[3], amb[3]
+    constexpr int PIX = WANT_PAR ? 4 : 2;
+    if (!WANT_PAR && own != 0u) quad_load(a.gout + off, t.rc.plane, g, t.whole, t.x4, t.rc.tx1);
+#pragma unroll
+    for (int h0 = 0; h0 < 4; h0 += PIX) {
+      MfPx px[4];
+      uint32_t lit = 0u;
+#pragma unroll
+      for (int k = h0; k < h0 + PIX; ++k)
+        if (mf_quad_px(quad, k, par, px[k])) lit |= 1u << k;
+      if (WANT_PAR) {
+        // a tile without a lit pixel: its partials are the empty sums, +0; its planes are zeros where they are written at all
+        if (!__syncthreads_or(lit != 0u)) {
+          if (t.inside && (own != 0u || fused)) {
+            const float4 z[3] = {zero4, zero4, zero4}, z2[2] = {zero4, zero4};
+            if (a.gnrm) quad_store_owned(a.gnrm + off, t, z, fused, own);
+            if (a.gpos) quad_store_owned(a.gpos + off, t, z, fused, own);
+            if (a.gbase) quad_store_owned(a.gbase + off, t, z, fused, own);
+            if (a.gmat) quad_store_owned(a.gmat + moff, t, z2, fused, own);
+          }
+          if (tid < K) a.work[((size_t)f * tpf + ti) * K + tid] = 0.0f;
+          return;
+        }
+        if (lit != 0u) quad_load(a.gout + off, t.rc.plane, g, t.whole, t.x4, t.rc.tx1);
+      }
+#pragma unroll
+      for (int k = h0; k < h0 + PIX; ++k) {
+        if (!(lit & (1u << k))) continue;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          quad_at(gb[c], k) = quad_at(g[c], k) * amb[c];
+          te[3 + c] = te[3 + c] + quad_at(g[c], k) * px[k].base[c];
+        }
+      }
+      // ---- 2. the lights
+      for (uint32_t l = 0; l < L; ++l) {
+        const SRZ_CAS float *lp = par + 6u + 6u * l;
+        const float I[3] = {lp[3], lp[4], lp[5]};
+        float tl[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; // this lane's sums of the light's terms: pos[3], intensity[3]
+#pragma unroll
+        for (int k = h0; k < h0 + PIX; ++k) {
+          if (!(lit & (1u << k))) continue;
+          const MfPx &p = px[k];
+          MfTerm lt;
+          if (!mf_term(p, lp, lt)) continue;
+          const float gk[3] = {quad_at(g[0], k), quad_at(g[1], k), quad_at(g[2], k)};
+          float gf[3], ge[3], q[3], gcd[3], gLd[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const float gq = gk[c] * lt.nl;
+            gf[c] = gq * lt.E[c], ge[c] = gq * lt.f[c], q[c] = lt.f[c] * lt.E[c];
+            if (WANT_PAR) tl[3 + c] = tl[3 + c] + ge[c] * lt.att;
+          }
+          float g_nl = l_dot(gk, q);
+          const float g_att = l_dot(ge, I);
+          if (lt.spec) {
+            float gF[3], gF0[3], omF0[3], bm[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+              gcd[c] = (gf[c] * (1.0f - lt.F[c])) * MF_INV_PI;
+              gF[c] = gf[c] * (lt.DV - p.cdif[c] * MF_INV_PI);
+              gF0[c] = gF[c] * (1.0f - lt.x5);
+              omF0[c] = 1.0f - p.F0[c], bm[c] = p.base[c] - 0.04f;
+              quad_at(gb[c], k) = quad_at(gb[c], k) + gF0[c] * p.mc;
+            }
+            quad_at(g_mc, k) = quad_at(g_mc, k) + l_dot(gF0, bm);
+            const float gDV = l_dot(gf, lt.F), gD = gDV * lt.Vs, gVs = gDV * lt.D;
+            const float gx = l_dot(gF, omF0) * (5.0f * lt.x4);
+            const float g_vhr = lt.vhr > 0.0f && lt.vhr < 1.0f ? -gx : 0.0f;
+            const float gw = -(gVs * lt.Vs), ggl = gw / lt.gl, ggv = gw / lt.gv;
+            g_nl = fmaf_(ggl, p.omk, g_nl);
+            quad_at(g_nv, k) = fmaf_(ggv, p.omk, quad_at(g_nv, k));
+            quad_at(g_k, k) = quad_at(g_k, k) + fmaf_(ggl, 1.0f - lt.nl, ggv * (1.0f - p.nv));
+            const float g_t = -((2.0f * (gD * lt.D)) / lt.t);
+            quad_at(g_a2, k) = quad_at(g_a2, k) + fmaf_(g_t, lt.nh * lt.nh, gD * (MF_INV_PI / lt.tt));
+            const float g_nhr = lt.nhr > 0.0f && lt.nhr < 1.0f ? g_t * ((2.0f * lt.nh) * (p.a2 - 1.0f)) : 0.0f;
+            float gH[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+              gH[c] = fmaf_(g_nhr, p.g.N[c], g_vhr * p.g.Vd[c]);
+              quad_at(gN[c], k) = quad_at(gN[c], k) + g_nhr * lt.H[c];
+              quad_at(gVd[c], k) = quad_at(gVd[c], k) + g_vhr * lt.H[c];
+            }
+            const float d = l_dot(gH, lt.H);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+              const float gHs = (gH[c] - lt.H[c] * d) * lt.ih;
+              gLd[c] = gHs, quad_at(gVd[c], k) = quad_at(gVd[c], k) + gHs;
+            }
+          } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) gcd[c] = gf[c] * MF_INV_PI;
+          }
+          quad_at(g_om, k) = quad_at(g_om, k) + l_dot(gcd, p.base);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            quad_at(gb[c], k) = quad_at(gb[c], k) + gcd[c] * p.om;
+            gLd[c] = fmaf_(g_nl, p.g.N[c], gLd[c]);
+            quad_at(gN[c], k) = quad_at(gN[c], k) + g_nl * lt.Ld[c];
+          }
+          const float d = l_dot(gLd, lt.Ld), two_g_r2 = 2.0f * (-((g_att * lt.att) * lt.att));
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const float gLv = fmaf_(lt.Lv[c], two_g_r2, (gLd[c] - lt.Ld[c] * d) * lt.ir);
+            tl[c] = tl[c] + gLv, quad_at(gP[c], k) = quad_at(gP[c], k) - gLv;
+          }
+        }
+        if (WANT_PAR) { // (every lane of the workgroup is here: the walk and the light count are uniform)
+#pragma unroll
+          for (int j = 0; j < 6; ++j) {
+            const float v = light_wave_sum(tl[j]);
+            if (lane == 0u) s_part[wave][6u + 6u * l + (uint32_t)j] = v;
+          }
+        }
+      }
+      // ---- 3. behind the lights: nv's share, the view direction's and the normal's normalisations, the eye's terms, the material
+#pragma unroll
+      for (int k = h0; k < h0 + PIX; ++k) {
+        if (!(lit & (1u << k))) continue;
+        const MfPx &p = px[k];
+        float vN[3] = {quad_at(gN[0], k), quad_at(gN[1], k), quad_at(gN[2], k)};
+        if (p.g.view) {
+          float v[3] = {quad_at(gVd[0], k), quad_at(gVd[1], k), quad_at(gVd[2], k)};
+#pragma unroll
+          for (int c = 0; c < 3; ++c) vN[c] = fmaf_(quad_at(g_nv, k), p.g.Vd[c], vN[c]), v[c] = fmaf_(quad_at(g_nv, k), p.g.N[c], v[c]);
+          const float d = l_dot(v, p.g.Vd);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const float gV = (v[c] - p.g.Vd[c] * d) * p.g.iv;
+            te[c] = te[c] + gV, quad_at(gP[c], k) = quad_at(gP[c], k) - gV;
+          }
+        }
+        const float d = l_dot(vN, p.g.N);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) quad_at(gn[c], k) = (vN[c] - p.g.N[c] * d) * p.g.inl;
+        const float g_al = fmaf_(quad_at(g_a2, k), 2.0f * p.al, 0.5f * quad_at(g_k, k));
+        quad_at(gm[0], k) = p.r_in ? g_al * (2.0f * p.rc) : 0.0f;
+        quad_at(gm[1], k) = p.m_in ? quad_at(g_mc, k) - quad_at(g_om, k) : 0.0f;
+      }
+    } // (the next PIX pixels)
+    // ---- 4. the planes: whole quads (fused clear, or four owners), else the owned pixels only; an owner that is not lit: zeros
+    if (t.inside && (own != 0u || fused)) {
+      if (a.gnrm) quad_store_owned(a.gnrm + off, t, gn, fused, own);
+      if (a.gpos) quad_store_owned(a.gpos + off, t, gP, fused, own);
+      if (a.gbase) quad_store_owned(a.gbase + off, t, gb, fused, own);
+      if (a.gmat) quad_store_owned(a.gmat + moff, t, gm, fused, own);
+    }
+    // ---- 5. the tile's K partial sums
+    if (WANT_PAR) {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        const float v = light_wave_sum(te[j]);
+        if (lane == 0u) s_part[wave][j] = v;
+      }
+      __syncthreads();
+      if (tid < K) a.work[((size_t)f * tpf + ti) * K + tid] = ((s_part[0][tid] + s_part[1][tid]) + s_part[2][tid]) + s_part[3][tid];
+      __syncthreads(); // s_part is the next tile's too
+    }
+  });
+}
+
+// ================================================================================================================
 // k_normal_map / k_normal_map_grad — TANGENT-SPACE NORMAL MAPPING OVER A VISIBILITY BUFFER, FOR CALLER DATA (srz_frameset_normal_map
 // and its backward, include/srz.h states the rule and the backward's order of operations): the interpolated normal (3 planes), the
 // interpolated tangent with its handedness (4 planes) and the tangent-space normal m (3 planes) -> the unit shading normal k_light
@@ -8046,6 +8376,17 @@ void launch_light_grad(const LightArgs &a, float *gpar, hipStream_t s) {
   const uint32_t tpf = a.n_local_bands * a.tiles_x, K = SRZ_LIGHT_PAR(a.n_lights);
   const bool shared = a.par_stride == 0u;
   launch_pass<k_light_grad<true>>(a, s);
+  float *rows = shared ? a.work + (size_t)a.n_frames * tpf * K : gpar;
+  if (a.n_frames != 0u) hipLaunchKernelGGL(k_light_fold, dim3(a.n_frames), dim3(64), 0, s, (const float *)a.work, rows, tpf, K);
+  if (shared) hipLaunchKernelGGL(k_light_fold, dim3(1), dim3(64), 0, s, (const float *)rows, gpar, a.n_frames, K);
+}
+void launch_microfacet(const MicrofacetArgs &a, hipStream_t s) { launch_pass<k_microfacet>(a, s); }
+// (launch_light_grad's two steps, k_light_fold unchanged: K = SRZ_MICROFACET_PAR(n_lights) <= 54 of its 64 threads)
+void launch_microfacet_grad(const MicrofacetArgs &a, float *gpar, hipStream_t s) {
+  if (!gpar) return launch_pass<k_microfacet_grad<false>>(a, s);
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, K = SRZ_MICROFACET_PAR(a.n_lights);
+  const bool shared = a.par_stride == 0u;
+  launch_pass<k_microfacet_grad<true>>(a, s);
   float *rows = shared ? a.work + (size_t)a.n_frames * tpf * K : gpar;
   if (a.n_frames != 0u) hipLaunchKernelGGL(k_light_fold, dim3(a.n_frames), dim3(64), 0, s, (const float *)a.work, rows, tpf, K);
   if (shared) hipLaunchKernelGGL(k_light_fold, dim3(1), dim3(64), 0, s, (const float *)rows, gpar, a.n_frames, K);

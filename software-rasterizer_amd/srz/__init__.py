@@ -35,6 +35,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_cube_mip_levels", "srz_cube_mip_bytes", "srz_cube_mip_build", "srz_cube_mip_fold",
            "srz_frameset_texture_cube_mip", "srz_frameset_texture_cube_mip_grad", "srz_frameset_cube_level",
            "srz_frameset_light", "srz_frameset_light_work_bytes", "srz_frameset_light_grad",
+           "srz_frameset_microfacet", "srz_frameset_microfacet_work_bytes", "srz_frameset_microfacet_grad",
            "srz_frameset_shadow", "srz_frameset_shadow_grad",
            "srz_mesh_tangents", "srz_mesh_tangents_grad", "srz_frameset_normal_map", "srz_frameset_normal_map_grad",
            "srz_frameset_perspective", "srz_frameset_perspective_grad", "srz_frameset_interpolate_deriv_persp",
@@ -131,6 +132,10 @@ def lib():
         L.srz_frameset_light_work_bytes.argtypes = abi.LIGHT_WORK_BYTES_ARGTYPES
         L.srz_frameset_light_work_bytes.restype = C.c_size_t
         L.srz_frameset_light_grad.argtypes = abi.LIGHT_GRAD_ARGTYPES
+        L.srz_frameset_microfacet.argtypes = abi.MICROFACET_ARGTYPES
+        L.srz_frameset_microfacet_work_bytes.argtypes = abi.MICROFACET_WORK_BYTES_ARGTYPES
+        L.srz_frameset_microfacet_work_bytes.restype = C.c_size_t
+        L.srz_frameset_microfacet_grad.argtypes = abi.MICROFACET_GRAD_ARGTYPES
         L.srz_mesh_tangents.argtypes = abi.MESH_TANGENTS_ARGTYPES
         L.srz_mesh_tangents_grad.argtypes = abi.MESH_TANGENTS_GRAD_ARGTYPES
         L.srz_frameset_normal_map.argtypes = abi.NORMAL_MAP_ARGTYPES
@@ -557,6 +562,36 @@ class FrameSet:
                                                       C.c_void_p(d_gout_ptr), C.c_void_p(d_gnrm_ptr or None), C.c_void_p(d_gpos_ptr or None),
                                                       C.c_void_p(d_gkd_ptr or None), C.c_void_p(d_gpar_ptr or None),
                                                       C.c_void_p(d_work_ptr or None), work_bytes, flags, _stream(stream)))
+
+    def microfacet(self, d_vis_ptr, d_nrm_ptr, d_pos_ptr, d_base_ptr, d_mat_ptr, d_par_ptr, n_lights, par_frames, d_out_ptr, out_bytes,
+                   flags=abi.FUSED_CLEAR, stream=None):
+        """Cook-Torrance (GGX, Schlick-Smith, Schlick Fresnel; metallic-roughness) under n_lights point lights for the caller's planes
+        d_nrm, d_pos, d_base (None / 0: base colour ones), each [frame][3][local_rows][width], the material d_mat
+        [frame][2][local_rows][width] (roughness, metallic) and the parameter block d_par [par_frames][abi.microfacet_par(n_lights)]
+        (eye amb, then per light pos intensity; par_frames: 1 or the frame count) → d_out [frame][3][local_rows][width], unclamped
+        (include/srz.h states the rule).  Pixels nobody owns are zeros with FUSED_CLEAR, else left untouched; an owner whose normal has
+        no finite positive length gets zeros.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_microfacet(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_nrm_ptr), C.c_void_p(d_pos_ptr),
+                                                      C.c_void_p(d_base_ptr or None), C.c_void_p(d_mat_ptr), C.c_void_p(d_par_ptr), n_lights,
+                                                      par_frames, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def microfacet_work_bytes(self, n_lights):
+        """bytes of the scratch buffer microfacet_grad needs for d_gpar; 0 for n_lights == 0 or above abi.LIGHT_MAX"""
+        return int(lib().srz_frameset_microfacet_work_bytes(self.ctx.h, self.h, n_lights))
+
+    def microfacet_grad(self, d_vis_ptr, d_nrm_ptr, d_pos_ptr, d_base_ptr, d_mat_ptr, d_par_ptr, n_lights, par_frames, d_gout_ptr, d_gnrm_ptr,
+                        d_gpos_ptr, d_gbase_ptr, d_gmat_ptr, d_gpar_ptr, d_work_ptr, work_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """the backward of microfacet: d_gout [frame][3][local_rows][width] → written to d_gnrm, d_gpos, d_gbase (three planes), d_gmat
+        (two planes: roughness, metallic; 0 where a clamp holds), all deterministic, and / or d_gpar (d_par's shape: WRITTEN, reduced
+        in a fixed tree, bit-reproducible for a shard layout; needs d_work of microfacet_work_bytes(n_lights) bytes).  Every output
+        pointer may be None / 0, not all; d_gbase needs d_base.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_microfacet_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_nrm_ptr),
+                                                           C.c_void_p(d_pos_ptr), C.c_void_p(d_base_ptr or None), C.c_void_p(d_mat_ptr),
+                                                           C.c_void_p(d_par_ptr), n_lights, par_frames, C.c_void_p(d_gout_ptr),
+                                                           C.c_void_p(d_gnrm_ptr or None), C.c_void_p(d_gpos_ptr or None),
+                                                           C.c_void_p(d_gbase_ptr or None), C.c_void_p(d_gmat_ptr or None),
+                                                           C.c_void_p(d_gpar_ptr or None), C.c_void_p(d_work_ptr or None), work_bytes, flags,
+                                                           _stream(stream)))
 
     def normal_map(self, d_vis_ptr, d_nrm_ptr, d_tan_ptr, d_m_ptr, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
         """tangent-space normal mapping of the caller's planes: d_nrm [frame][3][local_rows][width] (the interpolated normal), d_tan

@@ -28,6 +28,12 @@ LIGHT_MAX = 8  # srz_frameset_light: the most lights of one call (SRZ_LIGHT_MAX)
 def light_par(n_lights):
     """floats of one parameter frame of srz_frameset_light: eye[3] ka[3] ks[3], then n_lights x {pos[3], intensity[3]} (SRZ_LIGHT_PAR)"""
     return 9 + 6 * n_lights
+
+
+def microfacet_par(n_lights):
+    """floats of one parameter frame of srz_frameset_microfacet: eye[3] amb[3], then n_lights x {pos[3], intensity[3]}
+    (SRZ_MICROFACET_PAR)"""
+    return 6 + 6 * n_lights
 # the prototypes of srz_frameset_texture / _texture_grad (argtypes; both return int), set on the library by srz.lib()
 TEXTURE_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                     C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
@@ -59,6 +65,10 @@ CUBE_LEVEL_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, C.c_size_t, _u3
 LIGHT_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
 LIGHT_WORK_BYTES_ARGTYPES = [_vp, _vp, _u32]
 LIGHT_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _u32, _vp]
+# the prototypes of srz_frameset_microfacet / _microfacet_work_bytes (returns size_t) / _microfacet_grad (argtypes), set by srz.lib()
+MICROFACET_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
+MICROFACET_WORK_BYTES_ARGTYPES = [_vp, _vp, _u32]
+MICROFACET_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _u32, _vp]
 # the prototypes of srz_mesh_tangents / _tangents_grad and srz_frameset_normal_map / _normal_map_grad (argtypes; all return int)
 MESH_TANGENTS_ARGTYPES = [_vp, C.c_int, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp]
 MESH_TANGENTS_GRAD_ARGTYPES = [_vp, C.c_int, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp]

@@ -749,6 +749,108 @@ def light(fs, vis, nrm, pos, kd, lights, eye, ka, ks, p, stream=None):
     return _Light.apply(nrm, pos, kd, light_params(fs, lights, eye, ka, ks), fs, vis, p, stream)
 
 
+def microfacet_params(fs, lights, eye, amb):
+    """the parameter block of microfacet / microfacet_grad from its pieces, with torch ops (so gradients of the block flow back to the
+    pieces): lights [L, 6] or [n_frames, L, 6] (a light: pos[3], intensity[3]), eye, amb [3] or [n_frames, 3] → [1, 6 + 6 L] when every
+    piece is shared by the frames, else [n_frames, 6 + 6 L] (per frame as soon as one of them is)"""
+    if lights.dim() not in (2, 3) or lights.shape[-1] != 6 or not 1 <= lights.shape[-2] <= abi.LIGHT_MAX:
+        raise ValueError(f"microfacet: lights must be [L, 6] or [n_frames, L, 6] with 1 <= L <= {abi.LIGHT_MAX}, got {tuple(lights.shape)}")
+    pieces = [("eye", eye), ("amb", amb)]
+    for name, t in pieces:
+        if t.dim() not in (1, 2) or t.shape[-1] != 3:
+            raise ValueError(f"microfacet: {name} must be [3] or [n_frames, 3], got {tuple(t.shape)}")
+    per_frame = lights.dim() == 3 or any(t.dim() == 2 for _, t in pieces)
+    n = fs.n_frames if per_frame else 1
+    n_l = lights.shape[-2]
+    rows = [t.reshape(-1, 3) for _, t in pieces] + [lights.reshape(-1, 6 * n_l)]
+    for (name, _), r in zip(pieces + [("lights", lights)], rows):
+        if r.shape[0] not in (1, n):
+            raise ValueError(f"microfacet: {name} has {r.shape[0]} frames, the set {fs.n_frames}")
+    return torch.cat([r.expand(n, r.shape[1]) for r in rows], dim=1).to(torch.float32).contiguous()
+
+
+def _microfacet_args(fs, nrm, pos, base, mat, par):
+    """→ (nrm, pos, base or None, mat, par, n_lights, par_frames), checked and contiguous"""
+    shape, shape2 = tuple(fs.interpolate_shape(3)), tuple(fs.interpolate_shape(2))
+    for name, t, s in (("nrm", nrm, shape), ("pos", pos, shape), ("base", base, shape), ("mat", mat, shape2)):
+        if name == "base" and t is None:
+            continue
+        if t is None or t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != s:
+            raise ValueError(f"microfacet: {name} must be a CUDA float32 tensor {s}, got "
+                             f"{None if t is None else (tuple(t.shape), t.dtype)}")
+    if par.dtype != torch.float32 or not par.is_cuda or par.dim() != 2 or par.shape[1] < 12 or (par.shape[1] - 6) % 6:
+        raise ValueError(f"microfacet: par must be a CUDA float32 tensor [1 or n_frames, 6 + 6 L], got {tuple(par.shape)} {par.dtype}")
+    n_l = (par.shape[1] - 6) // 6
+    if n_l > abi.LIGHT_MAX or par.shape[0] not in (1, fs.n_frames):
+        raise ValueError(f"microfacet: par of {par.shape[0]} frames and {n_l} lights; 1 or {fs.n_frames} frames and 1 .. {abi.LIGHT_MAX} "
+                         "lights are supported")
+    return nrm.contiguous(), pos.contiguous(), None if base is None else base.contiguous(), mat.contiguous(), par.contiguous(), n_l, par.shape[0]
+
+
+def microfacet_grad(fs, vis, nrm, pos, base, mat, par, gout, want_gnrm=True, want_gpos=True, want_gbase=True, want_gmat=True, want_gpar=True,
+                    stream=None):
+    """the backward of microfacet by one FrameSet.microfacet_grad call: par is microfacet_params' block, gout [n_frames, 3, rows, W] →
+    (gnrm, gpos, gbase, gmat, gpar), each None when not wanted (not all; gbase is None without base): the planes are deterministic,
+    zeros where nobody owns the pixel or its normal is not lit, gmat [n_frames, 2, rows, W] zero where a clamp holds; gpar has par's
+    shape, reduced in a fixed tree (bit-reproducible for a shard layout).  stream: a raw stream handle, None = torch's current stream."""
+    want_gbase = want_gbase and base is not None
+    if not (want_gnrm or want_gpos or want_gbase or want_gmat or want_gpar):
+        raise ValueError("microfacet_grad: no gradient is asked for")
+    nrm, pos, base, mat, par, n_l, par_frames = _microfacet_args(fs, nrm, pos, base, mat, par)
+    gout = gout.contiguous()
+    if tuple(gout.shape) != tuple(nrm.shape) or gout.dtype != torch.float32:
+        raise ValueError(f"microfacet_grad: gout must be float32 {tuple(nrm.shape)}, got {tuple(gout.shape)} {gout.dtype}")
+    gnrm, gpos, gbase = (torch.empty_like(nrm) if w else None for w in (want_gnrm, want_gpos, want_gbase))
+    gmat = torch.empty_like(mat) if want_gmat else None
+    gpar = work = None
+    work_bytes = 0
+    if want_gpar:
+        work_bytes = fs.microfacet_work_bytes(n_l)
+        gpar, work = torch.empty_like(par), torch.empty(max(work_bytes // 4, 1), dtype=torch.float32, device=par.device)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    fs.microfacet_grad(vis.data_ptr(), nrm.data_ptr(), pos.data_ptr(), ptr(base), mat.data_ptr(), par.data_ptr(), n_l, par_frames,
+                       gout.data_ptr(), ptr(gnrm), ptr(gpos), ptr(gbase), ptr(gmat), ptr(gpar), ptr(work), work_bytes, abi.FUSED_CLEAR,
+                       _stream_ptr(stream))
+    return gnrm, gpos, gbase, gmat, gpar
+
+
+class _Microfacet(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, nrm, pos, base, mat, par, fs, vis, stream):
+        nrm, pos, base, mat, par, n_l, par_frames = _microfacet_args(fs, nrm, pos, base, mat, par)
+        out = torch.empty(fs.interpolate_shape(3), dtype=torch.float32, device=nrm.device)
+        fs.microfacet(vis.data_ptr(), nrm.data_ptr(), pos.data_ptr(), None if base is None else base.data_ptr(), mat.data_ptr(),
+                      par.data_ptr(), n_l, par_frames, out.data_ptr(), fs.interpolate_bytes(3), abi.FUSED_CLEAR, _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.stream, ctx.has_base = fs, vis, stream, base is not None
+        ctx.save_for_backward(nrm, pos, mat, par, *([base] if base is not None else []))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        nrm, pos, mat, par = ctx.saved_tensors[:4]
+        base = ctx.saved_tensors[4] if ctx.has_base else None
+        need = list(ctx.needs_input_grad[:5])
+        need[2] = need[2] and ctx.has_base
+        grads = (None, None, None, None, None)
+        if any(need):  # one call, asking only for what is needed
+            grads = microfacet_grad(ctx.fs, ctx.vis, nrm, pos, base, mat, par, gout, *need, ctx.stream)
+        return (*grads, None, None, None)
+
+
+def microfacet(fs, vis, nrm, pos, base, mat, lights, eye, amb, stream=None):
+    """Cook-Torrance shading under point lights for the caller's own planes under a visibility buffer `vis` of FrameSet `fs`: nrm, pos
+    and base (or None: base colour ones) are [n_frames, 3, rows, W] CUDA float32 — interpolate's or normal_map's normals, interpolate's
+    positions, texture's base colour —, mat [n_frames, 2, rows, W] the roughness (clamped to [1 / 16, 1]) and the metallic (clamped to
+    [0, 1]) — a two-channel texture's output —, lights [L, 6] or [n_frames, L, 6] (pos[3], intensity[3]; L <= abi.LIGHT_MAX), eye, amb [3]
+    or [n_frames, 3] → [n_frames, 3, rows, W] float32: a GGX distribution, Schlick-Smith visibility and Schlick Fresnel over the
+    metallic-roughness parametrisation, true 1 / r² attenuation, amb * base added, no clamp, zeros where nobody owns the pixel or its
+    normal has no finite positive length (FrameSet.microfacet; include/srz.h states the rule).  Differentiable with respect to nrm, pos,
+    base, mat (deterministic planes; mat's gradient is zero where a clamp holds) and to lights, eye, amb (sums over the pixels in a
+    fixed tree: bit-reproducible).  Backward is one microfacet_grad call that asks only for the outputs some input needs.  stream: a raw
+    stream handle, None = torch's current stream."""
+    return _Microfacet.apply(nrm, pos, base, mat, microfacet_params(fs, lights, eye, amb), fs, vis, stream)
+
+
 def _normal_map_args(fs, nrm, tan, m):
     """→ (nrm, tan, m), checked and contiguous"""
     for name, t, n in (("nrm", nrm, 3), ("tan", tan, 4), ("m", m, 3)):
