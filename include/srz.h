@@ -76,6 +76,8 @@ extern "C" {
  *      srz_mesh_tangents_grad / srz_frameset_normal_map / srz_frameset_normal_map_grad
  *      (additive, same version) Cook-Torrance GGX shading pass over a visibility buffer, with gradients srz_frameset_microfacet /
  *      srz_frameset_microfacet_grad / srz_frameset_microfacet_work_bytes, SRZ_MICROFACET_PAR
+ *      (additive, same version) a cube prefiltered on the device with a cosine or a GGX lobe, with gradients srz_cube_prefilter /
+ *      srz_cube_prefilter_grad / srz_cube_prefilter_work_bytes, SRZ_PREFILTER_COSINE, SRZ_PREFILTER_GGX
  */
 #define SRZ_ABI_VERSION 7
 
@@ -1150,7 +1152,8 @@ int srz_frameset_texture_mip_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_
  *     tex_frames == 0 or 6 * tex_frames > 65536
  *   srz_cube_mip_build / srz_cube_mip_fold = srz_texture_mip_build / _fold with tex_w = tex_h = n and 6 * tex_frames frames, bit for
  *     bit, with their refusals; SRZ_E_INVALID also for tex_frames == 0 or 6 * tex_frames > 65536.
- * A caller may equally hand in a pyramid of their own in this layout (a GGX-prefiltered one): the lookup does not care who wrote it.
+ * A caller may equally hand in a pyramid of their own in this layout (a GGX-prefiltered one, which srz_cube_prefilter writes level
+ * by level): the lookup does not care who wrote it.
  * THE LOOKUP.  srz_frameset_texture_cube_mip: srz_frameset_texture_cube's arguments, plus d_mip (the levels 1 .. L - 1, 4-byte
  * aligned), n_levels = L, 1 <= L <= srz_cube_mip_levels(n), and d_lam [frame][1][local_rows][width] float32,
  * srz_frameset_interpolate_bytes(1) bytes, 16-byte aligned: the level of detail per pixel.  n_levels == 1 reads neither d_lam nor d_mip
@@ -1219,6 +1222,62 @@ int srz_frameset_texture_cube_mip_grad(srz_ctx *ctx, srz_frameset *fs, const voi
                                        uint32_t flags, void *stream);
 int srz_frameset_cube_level(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_dir, const void *d_dird, uint32_t n,
                             uint32_t n_levels, void *d_out, size_t out_bytes, uint32_t flags, void *stream);
+/* A CUBE PREFILTERED WITH A LOBE, and the exact transpose of that as its backward: what turns an environment cube into the levels
+ * srz_frameset_texture_cube_mip blends by roughness (GGX) and into the irradiance cube srz_frameset_texture_cube looks up by the
+ * normal (COSINE), with the gradient carried back to the environment's texels.  It is an all-pairs convolution, O(n_dst^2 n_src^2)
+ * per channel.  No set and no visibility buffer are involved; stream semantics and asynchrony as srz_cube_mip_build.
+ * d_src and d_gsrc: [tex_frames][6][n_src][n_src][n_ch] float32, srz_frameset_texture_cube's cube layout, faces and axes from its
+ * table.  d_dst and d_gdst: the same layout with n_dst.  d_den: [6][n_dst][n_dst] float32, the normaliser: it depends on the
+ * geometry, kind, roughness and cmin only, not on texel values or frames; the forward writes it when non-null, the backward needs it
+ * as the forward wrote it (for the same n_src, n_dst, kind, roughness, cmin).  n_src and n_dst are independent, each 1 ..
+ * SRZ_TEX_MAX_SIZE, any parity; 1 <= n_ch <= SRZ_ATTR_MAX_CH; 1 <= tex_frames <= 65536, every frame convolved alike.  d_work: scratch
+ * of srz_cube_prefilter_work_bytes(n_src, n_dst, n_ch, tex_frames) bytes, 16-byte aligned, the same size for both calls (0 for
+ * sizes out of range); its contents mean nothing between calls.  Every other pointer is 4-byte aligned.
+ * THE RULE, all of it float32, nothing fused except where fmaf is written, / and sqrtf the correctly rounded operations, always the
+ * exact arithmetic (SRZ_OPT_APPROX_SHADE has no effect).
+ *   TEXEL GEOMETRY of texel (f, y, x) — face, row, column — of a cube of N x N faces:
+ *     s = (float)(2 x + 1) / (float)N - 1.0f;  t = (float)(2 y + 1) / (float)N - 1.0f       (the texel centre of the cube section)
+ *     p = n_f + s su_f + t sv_f, exact: in the order (x, y, z) the component along the face's normal is +-1, the component su names
+ *       is s, negated where su is negative, the component sv names is t, negated where sv is negative — +X: (1, -t, -s);
+ *       -X: (-1, -t, s);  +Y: (s, 1, t);  -Y: (s, -1, -t);  +Z: (s, -t, 1);  -Z: (-s, -t, -1)
+ *     r2 = fmaf(s, s, fmaf(t, t, 1.0f));  inv = 1.0f / sqrtf(r2);  d = p * inv per component;  jac = (inv * inv) * inv
+ *     (jac is the texel's solid angle up to the constant 4 / N^2, which cancels in the normalisation)
+ *   PAIR WEIGHT of output texel o (geometry at N = n_dst) and source texel i (at N = n_src):
+ *     c = fmaf(d_o.x, d_i.x, fmaf(d_o.y, d_i.y, d_o.z * d_i.z));  c = c > 1.0f ? 1.0f : c
+ *     the pair is SKIPPED iff !(c > cmin): not added — never multiplied by zero — so an infinite or NaN texel behind the cutoff
+ *     reaches no result.  cmin is finite and in [0, 1): the backward hemisphere is always skipped.
+ *     SRZ_PREFILTER_COSINE:  w = c * jac_i
+ *     SRZ_PREFILTER_GGX, with N = V = R, so that nh^2 = (1 + c) / 2 needs no square root:
+ *       r = roughness < 0.0625f ? 0.0625f : roughness;  a = r * r;  a2 = a * a
+ *       nh2 = fmaf(0.5f, c, 0.5f);  t = fmaf(nh2, a2 - 1.0f, 1.0f);  w = (c * jac_i) / (t * t)
+ *     The weight is D (n.l) dw; pi and a2 cancel in the normalisation.  That is a CHOICE among the published prefilters (no
+ *     importance sampling, no mip-biased source level, the lobe not renormalised by 1 / (4 v.h)).  At roughness 1 it is COSINE bit
+ *     for bit (t = 1), and every roughness below 0.0625 is 0.0625.
+ *   SUMS per output texel and channel, three levels in a fixed order, each from +0.0f:
+ *     within a source row, columns ascending:  num = fmaf(w, src, num);  den = den + w
+ *     the rows of a face, ascending, by plain adds;  the six faces in order, by plain adds
+ *     dst = den > 0.0f ? num / den : 0.0f  (always written);  d_den gets den
+ *   (a sequential sum is bounded at n_src terms, and the work may be split by row or by face without changing a bit.)
+ *   BACKWARD, srz_cube_prefilter_grad:  q[o][ch] = den_o > 0.0f ? gdst[o][ch] / den_o : 0.0f, and gsrc[i][ch] is the same three-level
+ *     sum over the OUTPUT texels — a row of the output cube, its faces, the cube — of acc = fmaf(w(o, i), q[o][ch], acc), with w by
+ *     the identical text and the identical skip.  It is a gather: bit-reproducible, and d_gsrc is WRITTEN, not added into.  There
+ *     is no gradient with respect to roughness or cmin.
+ * An output texel that no pair reaches (a narrow cutoff over a coarse source) has den = 0, the value 0 and no share in the backward.
+ * SUBNORMALS are numbers; non-finite texels and gradients propagate as IEEE has them through the pairs that are not skipped.  Both
+ * passes use no atomics: two calls with the same arguments give the same words.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, d_src, d_dst, d_gdst, d_gsrc, d_work, or d_den in the
+ * backward; n_src or n_dst 0 or above SRZ_TEX_MAX_SIZE; n_ch 0 or above SRZ_ATTR_MAX_CH; tex_frames 0 or above 65536; an unknown
+ * kind; a roughness that is not finite or outside [0, 1]; a cmin that is not finite or outside [0, 1); work_bytes below
+ * srz_cube_prefilter_work_bytes; d_work not 16-byte aligned, another pointer not 4-byte aligned; an output (d_dst, d_den, d_gsrc,
+ * d_work) that overlaps an input or another output. */
+#define SRZ_PREFILTER_COSINE 0u
+#define SRZ_PREFILTER_GGX 1u
+size_t srz_cube_prefilter_work_bytes(uint32_t n_src, uint32_t n_dst, uint32_t n_ch, uint32_t tex_frames);
+int srz_cube_prefilter(srz_ctx *ctx, const float *d_src, uint32_t n_src, float *d_dst, uint32_t n_dst, uint32_t n_ch, uint32_t tex_frames,
+                       uint32_t kind, float roughness, float cmin, float *d_den, void *d_work, size_t work_bytes, void *stream);
+int srz_cube_prefilter_grad(srz_ctx *ctx, const float *d_gdst, const float *d_den, uint32_t n_src, uint32_t n_dst, uint32_t n_ch,
+                            uint32_t tex_frames, uint32_t kind, float roughness, float cmin, float *d_gsrc, void *d_work, size_t work_bytes,
+                            void *stream);
 /* PERSPECTIVE-CORRECT BARYCENTRICS of a visibility buffer, their gradients, and the attribute derivatives under them.  A visibility
  * buffer's alpha, beta are LINEAR IN SCREEN SPACE, the reference's rule and the default of every pass above.  Under a vertex stage
  * that divides by a real w they name the wrong point of the triangle.  With q_k = 1 / w_k the reciprocal clip w of the owner's

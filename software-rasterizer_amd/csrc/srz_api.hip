@@ -2687,6 +2687,78 @@ int srz_cube_mip_fold(srz_ctx *ctx, const float *d_gmip, size_t mip_bytes, uint3
   return srz_texture_mip_fold(ctx, d_gmip, mip_bytes, n, n, n_ch, 6u * tex_frames, n_levels, d_gtex, stream);
 }
 
+// ---- the prefilter of a cube (no set: tex_frames is any count up to MIP_MAX_FRAMES)
+namespace {
+bool prefilter_sizes_ok(uint32_t n_src, uint32_t n_dst, uint32_t n_ch, uint32_t tex_frames) {
+  return n_src != 0u && n_src <= SRZ_TEX_MAX_SIZE && n_dst != 0u && n_dst <= SRZ_TEX_MAX_SIZE && n_ch != 0u && n_ch <= SRZ_ATTR_MAX_CH &&
+         tex_frames != 0u && tex_frames <= MIP_MAX_FRAMES;
+}
+// what srz_cube_prefilter and _prefilter_grad check alike, the pointers apart
+int check_prefilter(srz_ctx *ctx, const std::string &fn, uint32_t n_src, uint32_t n_dst, uint32_t n_ch, uint32_t tex_frames, uint32_t kind,
+                    float roughness, float cmin, const void *d_work, size_t work_bytes) {
+  if (n_src == 0u || n_src > SRZ_TEX_MAX_SIZE || n_dst == 0u || n_dst > SRZ_TEX_MAX_SIZE)
+    return fail(ctx, SRZ_E_INVALID, fn + ": n_src and n_dst must be 1 .. SRZ_TEX_MAX_SIZE");
+  if (n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_ATTR_MAX_CH");
+  if (tex_frames == 0u || tex_frames > MIP_MAX_FRAMES) return fail(ctx, SRZ_E_INVALID, fn + ": tex_frames must be 1 .. 65536");
+  if (kind != SRZ_PREFILTER_COSINE && kind != SRZ_PREFILTER_GGX) return fail(ctx, SRZ_E_INVALID, fn + ": kind must be SRZ_PREFILTER_COSINE or SRZ_PREFILTER_GGX");
+  if (!std::isfinite(roughness) || roughness < 0.0f || roughness > 1.0f) return fail(ctx, SRZ_E_INVALID, fn + ": roughness must be in [0, 1]");
+  if (!std::isfinite(cmin) || cmin < 0.0f || !(cmin < 1.0f)) return fail(ctx, SRZ_E_INVALID, fn + ": cmin must be in [0, 1)");
+  if (!d_work) return fail(ctx, SRZ_E_INVALID, fn + ": null d_work");
+  if (work_bytes < srz_cube_prefilter_work_bytes(n_src, n_dst, n_ch, tex_frames))
+    return fail(ctx, SRZ_E_INVALID, fn + ": work_bytes is below srz_cube_prefilter_work_bytes");
+  if (!aligned<16>({d_work})) return fail(ctx, SRZ_E_INVALID, fn + ": d_work must be 16-byte aligned");
+  return SRZ_OK;
+}
+} // namespace
+
+size_t srz_cube_prefilter_work_bytes(uint32_t n_src, uint32_t n_dst, uint32_t n_ch, uint32_t tex_frames) {
+  if (!prefilter_sizes_ok(n_src, n_dst, n_ch, tex_frames)) return 0;
+  const size_t fwd = prefilter_table_bytes(n_src) + prefilter_part_bytes(n_dst, n_src, n_ch, tex_frames, false);
+  const size_t bwd = prefilter_table_bytes(n_dst) + prefilter_q_bytes(n_dst, n_ch, tex_frames) + prefilter_part_bytes(n_src, n_dst, n_ch, tex_frames, true);
+  return std::max(fwd, bwd);
+}
+
+int srz_cube_prefilter(srz_ctx *ctx, const float *d_src, uint32_t n_src, float *d_dst, uint32_t n_dst, uint32_t n_ch, uint32_t tex_frames,
+                       uint32_t kind, float roughness, float cmin, float *d_den, void *d_work, size_t work_bytes, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_cube_prefilter");
+  if (!d_src || !d_dst) return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!d_src ? "d_src" : "d_dst"));
+  if (int rc = check_prefilter(ctx, fn, n_src, n_dst, n_ch, tex_frames, kind, roughness, cmin, d_work, work_bytes)) return rc;
+  if (!aligned<4>({d_src, d_dst, d_den})) return fail(ctx, SRZ_E_INVALID, fn + ": d_src, d_dst and d_den must be 4-byte aligned");
+  const size_t need = srz_cube_prefilter_work_bytes(n_src, n_dst, n_ch, tex_frames), den_bytes = (size_t)prefilter_texels(n_dst) * sizeof(float);
+  const size_t src_bytes = (size_t)prefilter_texels(n_src) * tex_frames * n_ch * sizeof(float), dst_bytes = den_bytes * tex_frames * n_ch;
+  if (int rc = check_overlaps(ctx, fn + " (d_dst, d_den, d_work against d_src)", {{d_dst, dst_bytes}, {d_den, den_bytes}, {d_work, need}},
+                              {{d_src, src_bytes}}))
+    return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PrefilterArgs a{};
+  a.src = d_src, a.dst = d_dst, a.den_out = d_den, a.work = d_work;
+  a.n_src = n_src, a.n_dst = n_dst, a.n_ch = n_ch, a.frames = tex_frames, a.kind = kind, a.roughness = roughness, a.cmin = cmin;
+  launch_prefilter(a, pick_stream(ctx, stream));
+  return end_pass(ctx);
+}
+
+int srz_cube_prefilter_grad(srz_ctx *ctx, const float *d_gdst, const float *d_den, uint32_t n_src, uint32_t n_dst, uint32_t n_ch,
+                            uint32_t tex_frames, uint32_t kind, float roughness, float cmin, float *d_gsrc, void *d_work, size_t work_bytes,
+                            void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_cube_prefilter_grad");
+  if (!d_gdst || !d_den || !d_gsrc) return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!d_gdst ? "d_gdst" : !d_den ? "d_den" : "d_gsrc"));
+  if (int rc = check_prefilter(ctx, fn, n_src, n_dst, n_ch, tex_frames, kind, roughness, cmin, d_work, work_bytes)) return rc;
+  if (!aligned<4>({d_gdst, d_den, d_gsrc})) return fail(ctx, SRZ_E_INVALID, fn + ": d_gdst, d_den and d_gsrc must be 4-byte aligned");
+  const size_t need = srz_cube_prefilter_work_bytes(n_src, n_dst, n_ch, tex_frames), den_bytes = (size_t)prefilter_texels(n_dst) * sizeof(float);
+  const size_t gsrc_bytes = (size_t)prefilter_texels(n_src) * tex_frames * n_ch * sizeof(float), gdst_bytes = den_bytes * tex_frames * n_ch;
+  if (int rc = check_overlaps(ctx, fn + " (d_gsrc, d_work against d_gdst, d_den)", {{d_gsrc, gsrc_bytes}, {d_work, need}},
+                              {{d_gdst, gdst_bytes}, {d_den, den_bytes}}))
+    return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PrefilterArgs a{};
+  a.src = d_gdst, a.den = d_den, a.dst = d_gsrc, a.work = d_work;
+  a.n_src = n_src, a.n_dst = n_dst, a.n_ch = n_ch, a.frames = tex_frames, a.kind = kind, a.roughness = roughness, a.cmin = cmin;
+  launch_prefilter_grad(a, pick_stream(ctx, stream));
+  return end_pass(ctx);
+}
+
 int srz_frameset_texture_cube_mip(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_dir, const void *d_lam, const float *d_tex,
                                   uint32_t n, uint32_t n_ch, uint32_t tex_frames, const float *d_mip, uint32_t n_levels, void *d_out,
                                   size_t out_bytes, uint32_t flags, void *stream) {

@@ -590,6 +590,44 @@ void launch_mip_build(const float *src, float *dst, uint32_t src_w, uint32_t src
 // srz_texture_mip_fold: the gradient pyramid gmip (levels 1 .. n_levels - 1) folded into gtex (level 0), a gather (k_mip_fold)
 void launch_mip_fold(const float *gmip, float *gtex, uint32_t tex_w, uint32_t tex_h, uint32_t n_ch, uint32_t tex_frames, uint32_t n_levels,
                      hipStream_t s);
+// srz_cube_prefilter / _prefilter_grad (include/srz.h states the rule): an ALL-PAIRS pass between an OWN cube — a lane owns one of
+// its texels: the forward's output, the backward's source — and a WALKED cube, whose texels every lane visits in the same order.
+// The three-level sum (row, face, cube) lets the walk be cut into `chunks` pieces without changing a bit: 1 (a lane walks the whole
+// cube), 6 (a face) or 6 * n_walk (a row); every piece leaves its partial sums in the work buffer, k_prefilter_rows adds a face's rows
+// in order and k_prefilter_fold the faces.  Host and device share the choice and the layout of the work buffer:
+//   [table: 6 n_walk^2 x {d.x, d.y, d.z, jac}] [backward only: q = gdst / den, [frames][6 n_walk^2][n_ch]]
+//   [partials: [chunk][frame][6 n_own^2][n_ch (+ 1 in the forward: den)]] [a walk cut into rows only: the six faces' partials]
+constexpr uint32_t PREFILTER_CG = 4u;                 // channels a lane accumulates at a time
+constexpr uint64_t PREFILTER_LANES = 1ull << 19;      // the lanes worth having in flight (8 waves per SIMD of 256 CUs)
+constexpr uint64_t PREFILTER_ROW_FLOATS = 1ull << 23; // the partials a walk cut into rows may take (32 MiB)
+inline uint64_t prefilter_texels(uint32_t n) { return 6ull * n * n; }
+inline uint32_t prefilter_groups(uint32_t n_ch) { return (n_ch + PREFILTER_CG - 1u) / PREFILTER_CG; }
+inline uint32_t prefilter_chunks(uint32_t n_own, uint32_t n_walk, uint32_t n_ch, uint32_t frames) {
+  const uint64_t lanes = prefilter_texels(n_own) * frames * prefilter_groups(n_ch);
+  if (lanes >= PREFILTER_LANES) return 1u;
+  const uint64_t row_floats = 6ull * n_walk * prefilter_texels(n_own) * frames * (n_ch + 1u);
+  return lanes * 6u >= PREFILTER_LANES || row_floats > PREFILTER_ROW_FLOATS ? 6u : 6u * n_walk;
+}
+inline size_t prefilter_align(size_t bytes) { return (bytes + 15u) & ~(size_t)15u; }
+inline size_t prefilter_table_bytes(uint32_t n_walk) { return (size_t)prefilter_texels(n_walk) * 4u * sizeof(float); }
+inline size_t prefilter_q_bytes(uint32_t n_dst, uint32_t n_ch, uint32_t frames) {
+  return prefilter_align((size_t)prefilter_texels(n_dst) * frames * n_ch * sizeof(float));
+}
+inline size_t prefilter_part_bytes(uint32_t n_own, uint32_t n_walk, uint32_t n_ch, uint32_t frames, bool backward) {
+  const uint32_t chunks = prefilter_chunks(n_own, n_walk, n_ch, frames);
+  return (size_t)(chunks > 6u ? chunks + 6u : chunks) * frames * prefilter_texels(n_own) * (n_ch + (backward ? 0u : 1u)) * sizeof(float);
+}
+struct PrefilterArgs {
+  const float *src;   // forward: the source cube; backward: gdst
+  const float *den;   // backward: the forward's normaliser [6 n_dst^2]
+  float *dst;         // forward: the output cube; backward: gsrc
+  float *den_out;     // forward: the normaliser (may be null)
+  void *work;         // the layout above
+  uint32_t n_src, n_dst, n_ch, frames, kind;
+  float roughness, cmin;
+};
+void launch_prefilter(const PrefilterArgs &a, hipStream_t s);
+void launch_prefilter_grad(const PrefilterArgs &a, hipStream_t s);
 // srz_frameset_interpolate_deriv: the screen-space derivatives of caller attributes (k_interp_deriv).  vis, attr and the walk as
 // InterpArgs has them, tri_pos / pos_stride as PosGradArgs; `out` is [frame][2 * n_ch][local_rows][width]
 struct InterpDerivArgs {

@@ -6254,6 +6254,153 @@ __global__ __launch_bounds__(256) void k_mip_fold(const float *gmip, float *gtex
 }
 
 // ================================================================================================================
+// k_prefilter — A CUBE CONVOLVED WITH A COSINE OR GGX LOBE, AND THE TRANSPOSE (srz_cube_prefilter, srz_cube_prefilter_grad;
+// include/srz.h states the rule).  The one all-pairs kernel here, bound by the vector ALU: a lane OWNS one texel of one cube (the
+// forward's output texel, the backward's source texel) with its direction in registers, and every lane WALKS the other cube's texels
+// in the same order, so the walked direction, jac and channel values are wave-uniform and arrive through the scalar cache
+// (k_light's parameter frame).  k_prefilter_table writes the walked cube's {d, jac} once per call; a lane computes its own texel
+// with the same function, so both sides are the same words.  A pair costs the dot product, the clamp, the test and the weight
+// (COSINE: one multiply; GGX: two fma's, two multiplies and the IEEE division) against n_ch + 1 fma's: the weight is generated per
+// group of PREFILTER_CG channels, a wider cube walks again.  A skipped pair is a select that keeps the sums, never a product with 0.
+// The walk is cut by blockIdx.y into pieces of whole rows (srz_device.h: prefilter_chunks) whose partial sums k_prefilter_rows and
+// k_prefilter_fold add in the rule's order; the fold divides in the forward.  No LDS, no barrier, no atomics.
+// ================================================================================================================
+struct alignas(16) PfTexel {
+  float x, y, z, jac;
+};
+__device__ __forceinline__ PfTexel pf_texel(uint32_t N, uint32_t texel) {
+  const uint32_t f = texel / (N * N), r = texel % (N * N), y = r / N, x = r % N;
+  const float s = (float)(2u * x + 1u) / (float)N - 1.0f, t = (float)(2u * y + 1u) / (float)N - 1.0f;
+  const float r2 = fmaf_(s, s, fmaf_(t, t, 1.0f));
+  const float inv = 1.0f / __builtin_sqrtf(r2);
+  float px, py, pz; // n_f + s su_f + t sv_f by include/srz.h's table of the faces
+  switch (f) {
+  case 0u: px = 1.0f, py = -t, pz = -s; break;
+  case 1u: px = -1.0f, py = -t, pz = s; break;
+  case 2u: px = s, py = 1.0f, pz = t; break;
+  case 3u: px = s, py = -1.0f, pz = -t; break;
+  case 4u: px = s, py = -t, pz = 1.0f; break;
+  default: px = -s, py = -t, pz = -1.0f; break;
+  }
+  return {px * inv, py * inv, pz * inv, (inv * inv) * inv};
+}
+__global__ __launch_bounds__(256) void k_prefilter_table(PfTexel *tab, uint32_t N) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < 6u * N * N) tab[i] = pf_texel(N, i);
+}
+// the backward's q = den > 0 ? gdst / den : 0, [frames][n_out][C]
+__global__ __launch_bounds__(256) void k_prefilter_q(const float *gdst, const float *den, float *q, uint32_t n_out, uint32_t C, uint32_t frames) {
+  const size_t per = (size_t)n_out * C, i = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= per * frames) return;
+  const float d = den[(i % per) / C];
+  q[i] = d > 0.0f ? gdst[i] / d : 0.0f;
+}
+struct PfWalk {
+  const PfTexel *tab; // the walked cube's table
+  const float *val;   // the walked values [frame][6 n_walk^2][C]
+  float *part;        // [chunk][frame][6 n_own^2][CS]
+  uint32_t n_own, n_walk, C, CS, frames, chunks, kind;
+  float a2m1, cmin;
+};
+// one lane's walk over the rows [g0, g1) of the 6 n_walk rows for NC channels from ch0
+template <bool BWD, int NC>
+__device__ __forceinline__ void pf_walk(const PfWalk &a, const PfTexel &me, uint32_t frame, uint32_t ch0, uint32_t g0, uint32_t g1, float (&cube)[NC],
+                                        float &cube_den) {
+  const SRZ_CAS PfTexel *tab = as_const(a.tab);
+  const SRZ_CAS float *val = as_const(a.val) + (size_t)frame * 6u * a.n_walk * a.n_walk * a.C + ch0;
+  const bool ggx = a.kind == SRZ_PREFILTER_GGX;
+  for (int k = 0; k < NC; ++k) cube[k] = 0.0f;
+  cube_den = 0.0f;
+  for (uint32_t g = g0; g < g1;) {
+    const uint32_t face_end = (g / a.n_walk + 1u) * a.n_walk, stop = face_end < g1 ? face_end : g1;
+    float face[NC], face_den = 0.0f;
+    for (int k = 0; k < NC; ++k) face[k] = 0.0f;
+    for (; g < stop; ++g) {
+      float row[NC], row_den = 0.0f;
+      for (int k = 0; k < NC; ++k) row[k] = 0.0f;
+      const size_t first = (size_t)g * a.n_walk;
+#pragma unroll 4
+      for (uint32_t x = 0; x < a.n_walk; ++x) {
+        const SRZ_CAS PfTexel *t = tab + first + x;
+        float c = fmaf_(me.x, t->x, fmaf_(me.y, t->y, me.z * t->z));
+        c = c > 1.0f ? 1.0f : c;
+        const bool take = c > a.cmin;
+        float w = c * (BWD ? me.jac : t->jac);
+        if (ggx) {
+          const float nh2 = fmaf_(0.5f, c, 0.5f);
+          const float u = fmaf_(nh2, a.a2m1, 1.0f);
+          w = w / (u * u);
+        }
+        if (!BWD) row_den = take ? row_den + w : row_den;
+        for (int k = 0; k < NC; ++k) row[k] = take ? fmaf_(w, val[(first + x) * a.C + k], row[k]) : row[k];
+      }
+      if (!BWD) face_den = face_den + row_den;
+      for (int k = 0; k < NC; ++k) face[k] = face[k] + row[k];
+    }
+    if (!BWD) cube_den = cube_den + face_den;
+    for (int k = 0; k < NC; ++k) cube[k] = cube[k] + face[k];
+  }
+}
+template <bool BWD, int NC> __device__ __forceinline__ void pf_group(const PfWalk &a, const PfTexel &me, uint32_t own, bool live, uint32_t frame, uint32_t ch0) {
+  const uint32_t per = 6u * a.n_walk / a.chunks; // rows per piece: the cube's, a face's, or one
+  float cube[NC], den;
+  pf_walk<BWD, NC>(a, me, frame, ch0, blockIdx.y * per, (blockIdx.y + 1u) * per, cube, den);
+  if (!live) return;
+  float *p = a.part + (((size_t)blockIdx.y * a.frames + frame) * (6u * a.n_own * a.n_own) + own) * a.CS;
+  for (int k = 0; k < NC; ++k) p[ch0 + k] = cube[k];
+  if (!BWD && ch0 == 0u) p[a.C] = den;
+}
+template <bool BWD> __global__ __launch_bounds__(256) void k_prefilter(PfWalk a) {
+  const uint32_t n_own = 6u * a.n_own * a.n_own, own = blockIdx.x * 256u + threadIdx.x;
+  const bool live = own < n_own; // (a lane past the cube walks with texel 0's direction and writes nothing)
+  const PfTexel me = pf_texel(a.n_own, live ? own : 0u);
+  const uint32_t groups = (a.C + PREFILTER_CG - 1u) / PREFILTER_CG;
+  for (uint32_t fg = blockIdx.z; fg < a.frames * groups; fg += gridDim.z) { // (wave-uniform)
+    const uint32_t frame = fg / groups, ch0 = (fg % groups) * PREFILTER_CG, nc = a.C - ch0;
+    if (nc >= 4u) pf_group<BWD, 4>(a, me, own, live, frame, ch0);
+    else if (nc == 3u) pf_group<BWD, 3>(a, me, own, live, frame, ch0);
+    else if (nc == 2u) pf_group<BWD, 2>(a, me, own, live, frame, ch0);
+    else pf_group<BWD, 1>(a, me, own, live, frame, ch0);
+  }
+}
+// a walk cut into rows: every face's rows added in order, a thread per (face, frame, texel, slot) — consecutive threads, consecutive
+// floats of a piece — into `faces`, the partial sums a walk cut into faces would have left
+__global__ __launch_bounds__(256) void k_prefilter_rows(PfWalk a, float *faces) {
+  const size_t piece = (size_t)a.frames * (6u * a.n_own * a.n_own) * a.CS, i = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= 6u * piece) return;
+  const uint32_t per_face = a.chunks / 6u;
+  const float *p = a.part + (i / piece) * per_face * piece + i % piece;
+  float face = 0.0f;
+  for (uint32_t y = 0; y < per_face; ++y) face = face + p[(size_t)y * piece];
+  faces[i] = face;
+}
+// slot `e` of texel `own` of `frame`: the cube's sum itself, or the six faces' partial sums added in order
+__device__ __forceinline__ float pf_fold(const PfWalk &a, uint32_t frame, uint32_t own, uint32_t e) {
+  const size_t piece = (size_t)a.frames * (6u * a.n_own * a.n_own) * a.CS;
+  const float *p = a.part + ((size_t)frame * (6u * a.n_own * a.n_own) + own) * a.CS + e;
+  if (a.chunks == 1u) return p[0];
+  float cube = 0.0f;
+  for (uint32_t f = 0; f < 6u; ++f) cube = cube + p[f * piece];
+  return cube;
+}
+// out: the forward's dst (num / den, and den itself into den_out when non-null) or the backward's gsrc (the sum)
+template <bool BWD> __global__ __launch_bounds__(256) void k_prefilter_fold(PfWalk a, float *out, float *den_out) {
+  const uint32_t n_own = 6u * a.n_own * a.n_own;
+  const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= (size_t)n_own * a.frames) return;
+  const uint32_t frame = (uint32_t)(i / n_own), own = (uint32_t)(i % n_own);
+  float den = 1.0f;
+  if (!BWD) {
+    den = pf_fold(a, frame, own, a.C);
+    if (den_out && frame == 0u) den_out[own] = den;
+  }
+  for (uint32_t ch = 0; ch < a.C; ++ch) {
+    const float num = pf_fold(a, frame, own, ch);
+    out[i * a.C + ch] = BWD ? num : (den > 0.0f ? num / den : 0.0f);
+  }
+}
+
+// ================================================================================================================
 // k_interp_deriv — SCREEN-SPACE DERIVATIVES OF CALLER ATTRIBUTES (srz_frameset_interpolate_deriv, include/srz.h): interpolation is
 // affine in the sample point with owners held fixed (k_pos_grad's ∇α, ∇β), so channel ch of the owner changes per one-pixel step by
 // (a − c) ∇α + (b − c) ∇β: a constant of the triangle.  k_interp's walk, loads and stores (no LDS, no barrier), plus load_pos9 of
@@ -8419,6 +8566,38 @@ void launch_mip_fold(const float *gmip, float *gtex, uint32_t tex_w, uint32_t te
                      hipStream_t s) {
   hipLaunchKernelGGL(k_mip_fold, dim3(std::min(tex_frames * tex_h, MIP_GRID)), dim3(256), 0, s, gmip, gtex, tex_w, tex_h, n_ch, tex_frames, n_levels);
 }
+// the table, (backward) q, the pieces' walks, (a walk cut into rows) the rows' fold, the fold: five launches at the most, in stream order
+template <bool BWD> static void launch_prefilter_impl(const PrefilterArgs &p, hipStream_t s) {
+  const uint32_t n_own = BWD ? p.n_src : p.n_dst, n_walk = BWD ? p.n_dst : p.n_src;
+  const uint32_t own_texels = (uint32_t)prefilter_texels(n_own), walk_texels = (uint32_t)prefilter_texels(n_walk);
+  const float r = p.roughness < 0.0625f ? 0.0625f : p.roughness, al = r * r;
+  PfWalk a{};
+  a.tab = (const PfTexel *)p.work;
+  char *after = (char *)p.work + prefilter_table_bytes(n_walk);
+  a.val = p.src;
+  hipLaunchKernelGGL(k_prefilter_table, dim3((walk_texels + 255u) / 256u), dim3(256), 0, s, (PfTexel *)p.work, n_walk);
+  if (BWD) {
+    const size_t n_q = (size_t)walk_texels * p.n_ch * p.frames;
+    hipLaunchKernelGGL(k_prefilter_q, dim3((uint32_t)((n_q + 255u) / 256u)), dim3(256), 0, s, p.src, p.den, (float *)after, walk_texels, p.n_ch, p.frames);
+    a.val = (const float *)after;
+    after += prefilter_q_bytes(p.n_dst, p.n_ch, p.frames);
+  }
+  a.part = (float *)after;
+  a.n_own = n_own, a.n_walk = n_walk, a.C = p.n_ch, a.CS = p.n_ch + (BWD ? 0u : 1u), a.frames = p.frames;
+  a.chunks = prefilter_chunks(n_own, n_walk, p.n_ch, p.frames), a.kind = p.kind;
+  a.a2m1 = al * al - 1.0f, a.cmin = p.cmin;
+  const uint32_t fg = p.frames * prefilter_groups(p.n_ch);
+  hipLaunchKernelGGL(k_prefilter<BWD>, dim3((own_texels + 255u) / 256u, a.chunks, std::min(fg, 65535u)), dim3(256), 0, s, a);
+  const size_t n_fold = (size_t)own_texels * p.frames;
+  if (a.chunks > 6u) { // rows into faces first, behind the rows' partial sums
+    float *faces = a.part + (size_t)a.chunks * n_fold * a.CS;
+    hipLaunchKernelGGL(k_prefilter_rows, dim3((uint32_t)((6u * n_fold * a.CS + 255u) / 256u)), dim3(256), 0, s, a, faces);
+    a.part = faces, a.chunks = 6u;
+  }
+  hipLaunchKernelGGL(k_prefilter_fold<BWD>, dim3((uint32_t)((n_fold + 255u) / 256u)), dim3(256), 0, s, a, p.dst, p.den_out);
+}
+void launch_prefilter(const PrefilterArgs &a, hipStream_t s) { launch_prefilter_impl<false>(a, s); }
+void launch_prefilter_grad(const PrefilterArgs &a, hipStream_t s) { launch_prefilter_impl<true>(a, s); }
 
 bool raster_four_waves(const RenderArgs &a) { return a.n_frames * a.n_local_bands * a.tiles_x <= 4096u; }
 

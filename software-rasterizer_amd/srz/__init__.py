@@ -34,6 +34,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_texture_cube", "srz_frameset_texture_cube_grad",
            "srz_cube_mip_levels", "srz_cube_mip_bytes", "srz_cube_mip_build", "srz_cube_mip_fold",
            "srz_frameset_texture_cube_mip", "srz_frameset_texture_cube_mip_grad", "srz_frameset_cube_level",
+           "srz_cube_prefilter_work_bytes", "srz_cube_prefilter", "srz_cube_prefilter_grad",
            "srz_frameset_light", "srz_frameset_light_work_bytes", "srz_frameset_light_grad",
            "srz_frameset_microfacet", "srz_frameset_microfacet_work_bytes", "srz_frameset_microfacet_grad",
            "srz_frameset_shadow", "srz_frameset_shadow_grad",
@@ -128,6 +129,10 @@ def lib():
         L.srz_frameset_texture_cube_mip.argtypes = abi.TEXTURE_CUBE_MIP_ARGTYPES
         L.srz_frameset_texture_cube_mip_grad.argtypes = abi.TEXTURE_CUBE_MIP_GRAD_ARGTYPES
         L.srz_frameset_cube_level.argtypes = abi.CUBE_LEVEL_ARGTYPES
+        L.srz_cube_prefilter_work_bytes.argtypes = abi.CUBE_PREFILTER_WORK_BYTES_ARGTYPES
+        L.srz_cube_prefilter_work_bytes.restype = C.c_size_t
+        L.srz_cube_prefilter.argtypes = abi.CUBE_PREFILTER_ARGTYPES
+        L.srz_cube_prefilter_grad.argtypes = abi.CUBE_PREFILTER_GRAD_ARGTYPES
         L.srz_frameset_light.argtypes = abi.LIGHT_ARGTYPES
         L.srz_frameset_light_work_bytes.argtypes = abi.LIGHT_WORK_BYTES_ARGTYPES
         L.srz_frameset_light_work_bytes.restype = C.c_size_t
@@ -838,6 +843,26 @@ class Context:
         on the cube as 6 * tex_frames textures; deterministic).  Asynchronous."""
         self._check(lib().srz_cube_mip_fold(self.h, C.c_void_p(d_gmip_ptr), mip_bytes, n, n_ch, tex_frames, n_levels, C.c_void_p(d_gtex_ptr),
                                             _stream(stream)))
+
+    def cube_prefilter_work_bytes(self, n_src, n_dst, n_ch, tex_frames):
+        """bytes of the scratch cube_prefilter and cube_prefilter_grad take for these sizes (0: a size out of range)"""
+        return int(lib().srz_cube_prefilter_work_bytes(n_src, n_dst, n_ch, tex_frames))
+
+    def cube_prefilter(self, d_src_ptr, n_src, d_dst_ptr, n_dst, n_ch, tex_frames, kind, roughness, cmin, d_den_ptr, d_work_ptr, work_bytes,
+                       stream=None):
+        """the float32 cube [tex_frames][6][n_src][n_src][n_ch] at d_src_ptr convolved with the cosine lobe (abi.PREFILTER_COSINE) or
+        the GGX lobe at `roughness` (abi.PREFILTER_GGX) over the pairs with a cosine above cmin → the cube of n_dst x n_dst faces at
+        d_dst_ptr and (d_den_ptr not None / 0) the normaliser [6][n_dst][n_dst]; d_work_ptr: cube_prefilter_work_bytes bytes of
+        scratch.  Deterministic, no atomics (include/srz.h states the rule).  Asynchronous."""
+        self._check(lib().srz_cube_prefilter(self.h, C.c_void_p(d_src_ptr), n_src, C.c_void_p(d_dst_ptr), n_dst, n_ch, tex_frames, kind, roughness,
+                                             cmin, C.c_void_p(d_den_ptr), C.c_void_p(d_work_ptr), work_bytes, _stream(stream)))
+
+    def cube_prefilter_grad(self, d_gdst_ptr, d_den_ptr, n_src, n_dst, n_ch, tex_frames, kind, roughness, cmin, d_gsrc_ptr, d_work_ptr, work_bytes,
+                            stream=None):
+        """the backward of cube_prefilter, its exact transpose as a gather: d_gdst_ptr and the normaliser the forward wrote →
+        d_gsrc_ptr (written, not added into), deterministic.  Asynchronous."""
+        self._check(lib().srz_cube_prefilter_grad(self.h, C.c_void_p(d_gdst_ptr), C.c_void_p(d_den_ptr), n_src, n_dst, n_ch, tex_frames, kind,
+                                                  roughness, cmin, C.c_void_p(d_gsrc_ptr), C.c_void_p(d_work_ptr), work_bytes, _stream(stream)))
 
     def mesh_upload(self, mesh_id, verts8, faces):
         """verts8: (nV,8) float32 [pos3 nrm3 uv2]; faces: (nF,3) uint32."""

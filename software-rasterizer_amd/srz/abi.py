@@ -81,6 +81,11 @@ SHADOW_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, C.c_floa
 PERSPECTIVE_ARGTYPES = [_vp, _vp, _vp, _vp, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
 PERSPECTIVE_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _vp]
 INTERPOLATE_DERIV_PERSP_ARGTYPES = [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
+# the prototypes of srz_cube_prefilter_work_bytes (returns size_t) / srz_cube_prefilter / _prefilter_grad (argtypes), set by srz.lib()
+PREFILTER_COSINE, PREFILTER_GGX = 0, 1  # SRZ_PREFILTER_*
+CUBE_PREFILTER_WORK_BYTES_ARGTYPES = [_u32, _u32, _u32, _u32]
+CUBE_PREFILTER_ARGTYPES = [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, C.c_float, C.c_float, _vp, _vp, C.c_size_t, _vp]
+CUBE_PREFILTER_GRAD_ARGTYPES = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, C.c_float, C.c_float, _vp, _vp, C.c_size_t, _vp]
 
 # numpy view of srz_tri (96 B): pos[3][3], nrm[3][3], uv[3][2]
 TRI_DTYPE = np.dtype([("pos", "<f4", (3, 3)), ("nrm", "<f4", (3, 3)), ("uv", "<f4", (3, 2))])

@@ -1213,6 +1213,117 @@ def texture_cube_mip(fs, vis, cube, dirs, lam, n_levels=None, mip=None, stream=N
     return _TextureCubeMip.apply(cube, dirs, lam, mip, fs, vis, n_levels, stream)
 
 
+def _prefilter_dims(cube, what):
+    if cube.dtype != torch.float32 or not cube.is_cuda or cube.dim() not in (4, 5) or cube.shape[-4] != 6 or cube.shape[-3] != cube.shape[-2]:
+        raise ValueError(f"{what}: a cube is a CUDA float32 tensor [6, N, N, C] or [frames, 6, N, N, C], got {tuple(cube.shape)} {cube.dtype}")
+    return (cube.shape[0] if cube.dim() == 5 else 1), cube.shape[-2], cube.shape[-1]
+
+
+def _prefilter_call(ctx, src, n_dst, kind, roughness, cmin, dst, den, stream):
+    """one Context.cube_prefilter call on contiguous tensors (dst, den: written) with scratch of its own"""
+    frames, n_src, n_ch = _prefilter_dims(src, "cube_prefilter")
+    nbytes = ctx.cube_prefilter_work_bytes(n_src, n_dst, n_ch, frames)
+    work = torch.empty((max(nbytes, 16) // 4,), dtype=torch.float32, device=src.device)
+    ctx.cube_prefilter(src.data_ptr(), n_src, dst.data_ptr(), n_dst, n_ch, frames, kind, roughness, cmin, den.data_ptr() if den is not None else None,
+                       work.data_ptr(), nbytes, _stream_ptr(stream))
+
+
+def cube_prefilter_grad(ctx_or_fs, gdst, den, n_src, kind, roughness=1.0, cmin=0.0, stream=None, out=None):
+    """the backward of cube_prefilter by one Context.cube_prefilter_grad call: gdst, the forward's output shape, and den
+    [6, n_out, n_out] as the forward kept it → the gradient of the source cube, [..., 6, n_src, n_src, C] — the exact transpose as a
+    gather, bit-reproducible.  out: a contiguous tensor of that shape to write instead of a fresh one."""
+    ctx = getattr(ctx_or_fs, "ctx", ctx_or_fs)
+    gdst = gdst.contiguous()
+    frames, n_dst, n_ch = _prefilter_dims(gdst, "cube_prefilter_grad")
+    if den.dtype != torch.float32 or not den.is_cuda or tuple(den.shape) != (6, n_dst, n_dst):
+        raise ValueError(f"cube_prefilter_grad: den must be a CUDA float32 tensor {(6, n_dst, n_dst)}, got {tuple(den.shape)} {den.dtype}")
+    den = den.contiguous()
+    shape = tuple(gdst.shape[:-3]) + (n_src, n_src, n_ch)
+    gsrc = torch.empty(shape, dtype=torch.float32, device=gdst.device) if out is None else out
+    if tuple(gsrc.shape) != shape or gsrc.dtype != torch.float32 or not gsrc.is_contiguous():
+        raise ValueError(f"cube_prefilter_grad: out must be a contiguous float32 tensor {shape}")
+    nbytes = ctx.cube_prefilter_work_bytes(n_src, n_dst, n_ch, frames)
+    work = torch.empty((max(nbytes, 16) // 4,), dtype=torch.float32, device=gdst.device)
+    ctx.cube_prefilter_grad(gdst.data_ptr(), den.data_ptr(), n_src, n_dst, n_ch, frames, kind, roughness, cmin, gsrc.data_ptr(), work.data_ptr(),
+                            nbytes, _stream_ptr(stream))
+    return gsrc
+
+
+class _CubePrefilter(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cube, c, n_out, kind, roughness, cmin, stream):
+        cube = cube.contiguous()
+        _, n_src, n_ch = _prefilter_dims(cube, "cube_prefilter")
+        out = torch.empty(tuple(cube.shape[:-3]) + (n_out, n_out, n_ch), dtype=torch.float32, device=cube.device)
+        den = torch.empty((6, n_out, n_out), dtype=torch.float32, device=cube.device)
+        _prefilter_call(c, cube, n_out, kind, roughness, cmin, out, den, stream)
+        ctx.c, ctx.n_src, ctx.kind, ctx.roughness, ctx.cmin, ctx.stream, ctx.den = c, n_src, kind, roughness, cmin, stream, den
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        g = None
+        if ctx.needs_input_grad[0]:
+            g = cube_prefilter_grad(ctx.c, gout, ctx.den, ctx.n_src, ctx.kind, ctx.roughness, ctx.cmin, ctx.stream)
+        return g, None, None, None, None, None, None
+
+
+def cube_prefilter(ctx_or_fs, cube, n_out, kind, roughness=1.0, cmin=0.0, stream=None):
+    """a CUDA float32 cube [6, N, N, C] or [frames, 6, N, N, C] convolved with the cosine lobe (kind abi.PREFILTER_COSINE) or the GGX
+    lobe at `roughness` in [0, 1] (abi.PREFILTER_GGX) → the cube of n_out x n_out faces, every output texel the normalised sum over
+    the source texels whose cosine with it exceeds cmin in [0, 1) (Context.cube_prefilter; include/srz.h states the rule).  All
+    pairs, O(n_out² N²): deterministic, no atomics.  Differentiable with respect to cube — the backward is the exact transpose, one
+    cube_prefilter_grad call with the normaliser the forward kept, bit-reproducible —, not to roughness or cmin.  ctx_or_fs: the
+    Context, or a FrameSet of it.  stream: a raw stream handle, None = torch's current stream."""
+    return _CubePrefilter.apply(cube, getattr(ctx_or_fs, "ctx", ctx_or_fs), int(n_out), int(kind), float(roughness), float(cmin), stream)
+
+
+def cube_irradiance(ctx_or_fs, cube, n_out, stream=None):
+    """the irradiance cube of an environment cube, n_out x n_out faces, for texture_cube by the normal: cube_prefilter with the cosine
+    lobe over the whole hemisphere.  Differentiable with respect to cube."""
+    return cube_prefilter(ctx_or_fs, cube, n_out, abi.PREFILTER_COSINE, 1.0, 0.0, stream)
+
+
+class _CubePrefilterPyramid(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cube, c, roughness, cmin, stream):
+        cube = cube.contiguous()
+        _prefilter_dims(cube, "cube_prefilter_pyramid")
+        L = len(roughness) + 1
+        box = cube_mip_build(c, cube, L, stream)
+        mip, dens = torch.empty_like(box), []
+        for r, src, dst in zip(roughness, cube_mip_views(box, cube.shape, L), cube_mip_views(mip, cube.shape, L)):
+            dens.append(torch.empty((6, src.shape[-2], src.shape[-2]), dtype=torch.float32, device=cube.device))
+            _prefilter_call(c, src, src.shape[-2], abi.PREFILTER_GGX, r, cmin, dst, dens[-1], stream)
+        ctx.c, ctx.roughness, ctx.cmin, ctx.stream, ctx.dens, ctx.shape = c, roughness, cmin, stream, dens, tuple(cube.shape)
+        return mip
+
+    @staticmethod
+    def backward(ctx, gmip):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        from . import cube_mip_bytes
+        gmip = gmip.contiguous()
+        L = len(ctx.roughness) + 1
+        gbox = torch.empty_like(gmip)  # the gradient of the box pyramid: every level written by its own prefilter_grad call
+        for r, den, g, out in zip(ctx.roughness, ctx.dens, cube_mip_views(gmip, ctx.shape, L), cube_mip_views(gbox, ctx.shape, L)):
+            cube_prefilter_grad(ctx.c, g, den, g.shape[-2], abi.PREFILTER_GGX, r, ctx.cmin, ctx.stream, out=out)
+        gcube = torch.zeros(ctx.shape, dtype=torch.float32, device=gmip.device)
+        tex_frames, n, n_ch, _ = _cube_mip_dims(ctx.shape, L)
+        if L > 1:
+            ctx.c.cube_mip_fold(gbox.data_ptr(), cube_mip_bytes(n, n_ch, tex_frames, L), n, n_ch, tex_frames, L, gcube.data_ptr(), _stream_ptr(ctx.stream))
+        return gcube, None, None, None, None
+
+
+def cube_prefilter_pyramid(ctx_or_fs, cube, roughness, cmin=0.0, stream=None):
+    """the GGX-prefiltered levels 1 .. L - 1 of an environment cube [6, N, N, C] or [frames, 6, N, N, C] as ONE flat float32 tensor in
+    cube_mip_build's layout, to pass as texture_cube_mip(..., mip=): roughness is a sequence, one value per level (L = len + 1 levels,
+    at most srz.cube_mip_levels(N)); level l is cube_prefilter's GGX lobe at roughness[l - 1] of the BOX level l (cube_mip_build's),
+    same size in and out.  Level 0 stays the cube itself.  One differentiable step with respect to cube: the backward runs
+    cube_prefilter_grad per level into a gradient pyramid and folds it into cube.grad (cube_mip_fold); deterministic."""
+    return _CubePrefilterPyramid.apply(cube, getattr(ctx_or_fs, "ctx", ctx_or_fs), tuple(float(r) for r in roughness), float(cmin), stream)
+
+
 def _scene_draws(fs):
     """per frame of a sceneset the mesh slots of its draws, in draw order"""
     if not all(isinstance(f, abi.SceneFrame) for f in fs.frames):
