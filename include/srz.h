@@ -78,6 +78,8 @@ extern "C" {
  *      srz_frameset_microfacet_grad / srz_frameset_microfacet_work_bytes, SRZ_MICROFACET_PAR
  *      (additive, same version) a cube prefiltered on the device with a cosine or a GGX lobe, with gradients srz_cube_prefilter /
  *      srz_cube_prefilter_grad / srz_cube_prefilter_work_bytes, SRZ_PREFILTER_COSINE, SRZ_PREFILTER_GGX
+ *      (additive, same version) image-based lighting over a visibility buffer, with gradients srz_frameset_reflect /
+ *      srz_frameset_reflect_grad / srz_brdf_table / srz_frameset_ibl / srz_frameset_ibl_grad, SRZ_BRDF_TABLE_MAX
  */
 #define SRZ_ABI_VERSION 7
 
@@ -1278,6 +1280,99 @@ int srz_cube_prefilter(srz_ctx *ctx, const float *d_src, uint32_t n_src, float *
 int srz_cube_prefilter_grad(srz_ctx *ctx, const float *d_gdst, const float *d_den, uint32_t n_src, uint32_t n_dst, uint32_t n_ch,
                             uint32_t tex_frames, uint32_t kind, float roughness, float cmin, float *d_gsrc, void *d_work, size_t work_bytes,
                             void *stream);
+/* IMAGE-BASED LIGHTING over a visibility buffer, for the caller's own planes, with gradients: the three pieces between
+ * srz_cube_prefilter's cubes, the cube lookups and srz_frameset_microfacet's material — the reflection vector, the split-sum table of
+ * srz_frameset_microfacet's OWN specular lobe, and the combine.  The chain: srz_brdf_table once; srz_frameset_reflect -> R and n.v;
+ * srz_frameset_texture_cube_mip at R and roughness * (levels - 1) over the GGX levels -> spec; srz_frameset_texture_cube of the
+ * cosine cube at the normal -> irr; srz_frameset_ibl -> the colour, to which srz_frameset_microfacet's point lights add.  Band
+ * sharding, local_rows, stream semantics, asynchrony, the 16-byte alignment of the visibility buffer and every plane buffer, owner and
+ * nobody, what a nobody pixel's words of the output planes become with and without SRZ_FUSED_CLEAR (zeros; untouched), and what the
+ * passes do not read or launch: all as srz_frameset_microfacet.  The words of the input planes at nobody's pixels never reach a
+ * result.  All of it float32, nothing fused except where fmaf is written, / and sqrtf the correctly rounded ones, always the exact
+ * arithmetic; NO TRANSCENDENTAL FUNCTION: /, sqrtf, fmaf, floorf, products and a fifth power by multiplication.  dot, l_pos,
+ * 1 / sqrtf(x), INV_PI and RMIN as in srz_frameset_microfacet.
+ *
+ * srz_frameset_reflect: d_nrm, d_pos, d_gnrm, d_gpos [frame][3][local_rows][width]; d_eye [par_frames][3] float32 in device memory,
+ * 4-byte aligned, par_frames 1 or the set's frame count; d_out and d_gout [frame][4][local_rows][width],
+ * srz_frameset_interpolate_bytes(4) bytes.  Per owned pixel:
+ *   nn, lit, inl, N, V, vv, view, iv, Vd: exactly as srz_frameset_light (the eye is d_eye's)
+ *   not lit, or no view -> out = (0, 0, 0, 0) (written), no gradient: a zero direction is srz_frameset_texture_cube's "unsampled"
+ *   nv = dot(N, Vd);  t2 = 2 * nv;  R_c = fmaf(t2, N_c, -Vd_c);  out = (R_0, R_1, R_2, nv)
+ * Plane 3 is the RAW nv, not clamped: the consumer clamps it.
+ * BACKWARD (g = gout of the pixel, gR its first three words), through both normalisations:
+ *   g_nv = fmaf(2, dot(gR, N), g_3);  gN_c = fmaf(g_nv, Vd_c, gR_c * t2);  gVd_c = fmaf(g_nv, N_c, -gR_c)
+ *   dv = dot(gVd, Vd);  gpos_c = -((gVd_c - Vd_c * dv) * iv);  dn = dot(gN, N);  gnrm_c = (gN_c - N_c * dn) * inl
+ * per pixel, no atomics, bit for bit.  d_gnrm or d_gpos may be NULL, not both.  THERE IS NO EYE GRADIENT in this ABI: R and nv depend
+ * on eye - P only, so the gradient of a frame's eye is minus the sum of that frame's d_gpos over its owned pixels (over every frame
+ * when the eye is shared); the caller takes that sum.
+ *
+ * srz_brdf_table: no set and no visibility buffer; d_tab [n][n][2] float32 (A, B), 4-byte aligned, WRITTEN; 2 <= n <=
+ * SRZ_BRDF_TABLE_MAX; 1 <= m <= 256.  Entry (i, j): nv = (float)i / (float)(n - 1);  rc = fmaf(0.9375f, (float)j / (float)(n - 1),
+ * RMIN): the nodes lie on the clamp edges, so the lookup never extrapolates.  F0 * A + B is the directional albedo of exactly the
+ * lobe srz_frameset_microfacet shades with (its D, its Vs with k = al / 2, Schlick's F), by a deterministic, rational quadrature
+ * over the projected half vector with the GGX density taken out analytically:
+ *   al = rc * rc;  a2 = al * al;  k = 0.5f * al;  omk = 1 - k;  vx = sqrtf(fmaf(-nv, nv, 1));  gv = fmaf(nv, omk, k);  fm = (float)m
+ *   A = B = +0;  for ring a = 0 .. m - 1 in order:
+ *     u = ((float)a + 0.5f) / fm;  q = 1 - u;  xi = fmaf(-q, q, 1);  wr = (2 * q) / fm
+ *     s = (a2 * xi) / fmaf(-xi, 1 - a2, 1);  r = sqrtf(s);  hz = sqrtf(1 - s)                   (the inverse of the GGX CDF in r^2)
+ *     ra = rb = +0;  for b = 0 .. m - 1 in order:
+ *       t = ((float)b + 0.5f) / fm;  tt = t * t;  den = 1 + tt;  c = (1 - tt) / den;  wa = (2 / den) / fm        (the rational circle)
+ *       for hx = r * c, then hx = -(r * c)  (the half y < 0 is the mirror image: INV_PI carries its factor):
+ *         vh = fmaf(vx, hx, nv * hz);  nl = fmaf(2 * vh, hz, -nv);  take = vh > 0 && nl > 0  (a select: a sample not taken adds +0)
+ *         gl = fmaf(nl, omk, k);  f = (nl * vh) / (hz * (gl * gv))
+ *         x = 1 - (vh < 1 ? vh : 1);  x2 = x * x;  x4 = x2 * x2;  x5 = x4 * x
+ *         ra = ra + (take ? (f * (1 - x5)) * wa : 0);  rb = rb + (take ? (f * x5) * wa : 0)
+ *     A = fmaf(ra, wr, A);  B = fmaf(rb, wr, B)
+ *   tab = (A * INV_PI, B * INV_PI)
+ * The sums run in THIS order whatever the launch shape: two calls, and any implementation of this text, give the same words.  The
+ * error is the quadrature's; the substitution xi = 1 - q^2 is part of the rule (it tames the 1 / hz tail).  No gradient: the table
+ * has no differentiable input.
+ *
+ * srz_frameset_ibl: d_base (may be NULL: ones; d_gbase must then be NULL), d_irr, d_spec, d_out, d_gout, d_gbase, d_girr, d_gspec
+ * [frame][3][local_rows][width]; d_mat, d_gmat [frame][2][..] (roughness, metallic); d_nv, d_gnv [frame][1][..] (srz_frameset_reflect's
+ * plane 3, or any cosine); d_tab and d_gtab [n][n][2] float32, 4-byte aligned, one table for every frame, 2 <= n <=
+ * SRZ_BRDF_TABLE_MAX.  Per owned pixel:
+ *   rc, r_in, mc, m_in: exactly as srz_frameset_microfacet clamps them
+ *   nvc = nv > 0 ? (nv < 1 ? nv : 1) : 0;  nv_in = nv > 0 && nv < 1                                       (a NaN: 0, no gradient)
+ *   sx = (float)(n - 1);  sy = (float)(n - 1) / 0.9375f;  x = nvc * sx;  y = (rc - RMIN) * sy
+ *   x0 = min((int)floorf(x), n - 2);  tx = x - (float)x0;  y0 = min((int)floorf(y), n - 2);  ty = y - (float)y0
+ *   for e = A, B, with t00 = tab[x0][y0][e], t01 = tab[x0][y0 + 1][e], t10 = tab[x0 + 1][y0][e], t11 = tab[x0 + 1][y0 + 1][e]:
+ *     d0 = t01 - t00;  d1 = t11 - t10;  top = fmaf(ty, d0, t00);  bot = fmaf(ty, d1, t10);  dx_e = bot - top;  e = fmaf(tx, dx_e, top)
+ *     dy_e = fmaf(tx, d1 - d0, d0)                                                      (the cell's bilinear slopes, for the backward)
+ *   om = 1 - mc;  F0_c = fmaf(mc, base_c - 0.04f, 0.04f);  cdif_c = base_c * om;  sc_c = fmaf(F0_c, A, B)
+ *   out_c = fmaf(cdif_c, irr_c, spec_c * sc_c)
+ * There is no pi (srz_cube_prefilter's cosine cube is already the normalised average) and no clamp of the result.  The clamps leave x
+ * and y finite and inside [0, n - 1] up to a rounding, and the min holds the cell: NO PLANE VALUE MAKES A PASS READ OUTSIDE THE TABLE.
+ * A coordinate exactly on a node below the last returns the node's word (tx = 0); on the last node tx = 1 and the word is
+ * fmaf(1, t01 - t00, t00), the node's word wherever that difference is exact.
+ * BACKWARD (g = gout of the pixel), in THIS order of operations:
+ *   gcd_c = g_c * irr_c;  girr_c = g_c * cdif_c;  gs_c = g_c * spec_c;  gspec_c = g_c * sc_c;  gF0_c = gs_c * A
+ *   gbase_c = fmaf(gF0_c, mc, gcd_c * om);  gA = dot(gs, F0);  gB = dot(g, spec)
+ *   g_mc = dot(gF0, base - 0.04f);  g_om = dot(gcd, base);  g_x = fmaf(gA, dx_A, gB * dx_B);  g_y = fmaf(gA, dy_A, gB * dy_B)
+ *   gmat0 = r_in ? g_y * sy : 0;  gmat1 = m_in ? g_mc - g_om : 0;  gnv = nv_in ? g_x * sx : 0
+ * per pixel, no atomics, bit for bit.  d_gtab is ADDED INTO, like srz_frameset_texture_grad's d_gtex: with ux = 1 - tx, uy = 1 - ty
+ * and the weights w = (ux * uy, ux * ty, tx * uy, tx * ty) of (x0, y0), (x0, y0 + 1), (x0 + 1, y0), (x0 + 1, y0 + 1), each owned
+ * pixel adds the float32 terms w_q * gA to A and w_q * gB to B of its four entries.  Float adds in no fixed order: NOT
+ * bit-reproducible; against the exact sum of the terms a word lies within n 2^-24 / (1 - n 2^-24) * sum |term|, n its contributing
+ * pixels (+ 1 for the add into the caller's word); with one contributing pixel and a zeroed table it is that pixel's term.  Any of
+ * d_gbase, d_gmat, d_gnv, d_girr, d_gspec, d_gtab may be NULL, not all six.
+ * SUBNORMALS are numbers; non-finite values propagate as IEEE has them.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set (the table: not needed), d_vis, a null required
+ * input (d_nrm, d_pos, d_eye; d_mat, d_nv, d_irr, d_spec, d_tab), d_out, d_gout, or every output of a backward; par_frames not 1 or
+ * the frame count; n outside [2, SRZ_BRDF_TABLE_MAX]; m outside [1, 256]; a short out_bytes or tab_bytes; a misaligned pointer; any
+ * bit of `flags` but SRZ_FUSED_CLEAR; an output that overlaps an input or another output; d_gbase without d_base. */
+#define SRZ_BRDF_TABLE_MAX 64u
+int srz_frameset_reflect(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos, const float *d_eye,
+                         uint32_t par_frames, void *d_out, size_t out_bytes, uint32_t flags, void *stream);
+int srz_frameset_reflect_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos, const float *d_eye,
+                              uint32_t par_frames, const void *d_gout, void *d_gnrm, void *d_gpos, uint32_t flags, void *stream);
+int srz_brdf_table(srz_ctx *ctx, float *d_tab, size_t tab_bytes, uint32_t n, uint32_t m, void *stream);
+int srz_frameset_ibl(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_base, const void *d_mat, const void *d_nv,
+                     const void *d_irr, const void *d_spec, const float *d_tab, uint32_t n, void *d_out, size_t out_bytes, uint32_t flags,
+                     void *stream);
+int srz_frameset_ibl_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_base, const void *d_mat, const void *d_nv,
+                          const void *d_irr, const void *d_spec, const float *d_tab, uint32_t n, const void *d_gout, void *d_gbase,
+                          void *d_gmat, void *d_gnv, void *d_girr, void *d_gspec, float *d_gtab, uint32_t flags, void *stream);
 /* PERSPECTIVE-CORRECT BARYCENTRICS of a visibility buffer, their gradients, and the attribute derivatives under them.  A visibility
  * buffer's alpha, beta are LINEAR IN SCREEN SPACE, the reference's rule and the default of every pass above.  Under a vertex stage
  * that divides by a real w they name the wrong point of the triangle.  With q_k = 1 / w_k the reciprocal clip w of the owner's

@@ -2380,6 +2380,170 @@ int srz_frameset_microfacet_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_v
   return end_pass(ctx);
 }
 
+// ---- image-based lighting: the reflection vector, the split-sum table, the combine
+namespace {
+ReflectArgs reflect_args(const srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos, const float *d_eye,
+                         uint32_t par_frames, void *d_out, uint32_t flags) {
+  ReflectArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  a.nrm = (const float *)d_nrm, a.pos = (const float *)d_pos, a.eye = d_eye;
+  a.vis_stride = 4ull * plane, a.frame_stride = 4ull * plane, a.nrm_stride = 3ull * plane;
+  a.eye_stride = par_frames == 1u ? 0ull : 3ull;
+  a.flags_or = flags;
+  return a;
+}
+// what srz_frameset_reflect and _reflect_grad check alike
+int check_reflect(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, uint32_t par_frames, uint32_t flags) {
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  if (par_frames != 1u && par_frames != (uint32_t)fs->n_frames)
+    return fail(ctx, SRZ_E_INVALID, fn + ": par_frames must be 1 or the set's frame count");
+  return SRZ_OK;
+}
+IblArgs ibl_args(const srz_frameset *fs, const void *d_vis, const void *d_base, const void *d_mat, const void *d_nv, const void *d_irr,
+                 const void *d_spec, const float *d_tab, uint32_t n, void *d_out, uint32_t flags) {
+  IblArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  a.base = (const float *)d_base, a.mat = (const float *)d_mat, a.nv = (const float *)d_nv, a.irr = (const float *)d_irr;
+  a.spec = (const float *)d_spec, a.tab = d_tab;
+  a.vis_stride = 4ull * plane, a.frame_stride = 3ull * plane, a.mat_stride = 2ull * plane, a.nv_stride = plane;
+  a.n = n;
+  a.flags_or = flags;
+  return a;
+}
+// what srz_frameset_ibl and _ibl_grad check alike
+int check_ibl(srz_ctx *ctx, const std::string &fn, uint32_t n, uint32_t flags) {
+  if (n < 2u || n > SRZ_BRDF_TABLE_MAX) return fail(ctx, SRZ_E_INVALID, fn + ": n must be 2 .. SRZ_BRDF_TABLE_MAX");
+  return check_pass_flags(ctx, fn, flags);
+}
+} // namespace
+
+int srz_frameset_reflect(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos, const float *d_eye,
+                         uint32_t par_frames, void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_reflect");
+  if (!fs || !d_vis || !d_nrm || !d_pos || !d_eye || !d_out)
+    return fail(ctx, SRZ_E_INVALID,
+                fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_nrm ? "d_nrm" : !d_pos ? "d_pos" : !d_eye ? "d_eye" : "d_out"));
+  if (int rc = check_reflect(ctx, fs, fn, par_frames, flags)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, 4u), plane_bytes = srz_frameset_interpolate_bytes(ctx, fs, 3u),
+               vis_bytes = srz_frameset_out_bytes(ctx, fs), eye_bytes = (size_t)par_frames * 3u * sizeof(float);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": out_bytes is too small for d_out");
+  if (!aligned<16>({d_vis, d_nrm, d_pos, d_out}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_nrm, d_pos, d_out) must be 16-byte aligned");
+  if (!aligned<4>({d_eye})) return fail(ctx, SRZ_E_INVALID, fn + ": d_eye must be 4-byte aligned");
+  if (int rc = check_overlaps(ctx, fn + " (d_out against d_vis, d_nrm, d_pos, d_eye)", {{d_out, need}},
+                              {{d_vis, vis_bytes}, {d_nrm, plane_bytes}, {d_pos, plane_bytes}, {d_eye, eye_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_light: caller data only)
+  launch_reflect(reflect_args(fs, d_vis, d_nrm, d_pos, d_eye, par_frames, d_out, flags), s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_reflect_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_pos, const float *d_eye,
+                              uint32_t par_frames, const void *d_gout, void *d_gnrm, void *d_gpos, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_reflect_grad");
+  if (!fs || !d_vis || !d_nrm || !d_pos || !d_eye || !d_gout)
+    return fail(ctx, SRZ_E_INVALID,
+                fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_nrm ? "d_nrm" : !d_pos ? "d_pos" : !d_eye ? "d_eye" : "d_gout"));
+  if (!d_gnrm && !d_gpos) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gnrm nor d_gpos is asked for");
+  if (int rc = check_reflect(ctx, fs, fn, par_frames, flags)) return rc;
+  const size_t gout_bytes = srz_frameset_interpolate_bytes(ctx, fs, 4u), plane_bytes = srz_frameset_interpolate_bytes(ctx, fs, 3u),
+               vis_bytes = srz_frameset_out_bytes(ctx, fs), eye_bytes = (size_t)par_frames * 3u * sizeof(float);
+  if (!aligned<16>({d_vis, d_nrm, d_pos, d_gout, d_gnrm, d_gpos}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_nrm, d_pos, d_gout, d_gnrm, d_gpos) must be 16-byte aligned");
+  if (!aligned<4>({d_eye})) return fail(ctx, SRZ_E_INVALID, fn + ": d_eye must be 4-byte aligned");
+  if (int rc = check_overlaps(ctx, fn + " (d_gnrm, d_gpos against d_vis, d_nrm, d_pos, d_eye, d_gout)",
+                              {{d_gnrm, plane_bytes}, {d_gpos, plane_bytes}},
+                              {{d_vis, vis_bytes}, {d_nrm, plane_bytes}, {d_pos, plane_bytes}, {d_eye, eye_bytes}, {d_gout, gout_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc;
+  ReflectArgs a = reflect_args(fs, d_vis, d_nrm, d_pos, d_eye, par_frames, nullptr, flags);
+  a.gout = (const float *)d_gout, a.gnrm = (float *)d_gnrm, a.gpos = (float *)d_gpos;
+  launch_reflect_grad(a, s);
+  return end_pass(ctx);
+}
+
+int srz_brdf_table(srz_ctx *ctx, float *d_tab, size_t tab_bytes, uint32_t n, uint32_t m, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_brdf_table");
+  if (!d_tab) return fail(ctx, SRZ_E_INVALID, fn + ": null d_tab");
+  if (n < 2u || n > SRZ_BRDF_TABLE_MAX) return fail(ctx, SRZ_E_INVALID, fn + ": n must be 2 .. SRZ_BRDF_TABLE_MAX");
+  if (m == 0u || m > 256u) return fail(ctx, SRZ_E_INVALID, fn + ": m must be 1 .. 256");
+  if (tab_bytes < (size_t)n * n * 2u * sizeof(float)) return fail(ctx, SRZ_E_INVALID, fn + ": tab_bytes is too small for d_tab");
+  if (!aligned<4>({d_tab})) return fail(ctx, SRZ_E_INVALID, fn + ": d_tab must be 4-byte aligned");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  launch_brdf_table(d_tab, n, m, pick_stream(ctx, stream));
+  return end_pass(ctx);
+}
+
+int srz_frameset_ibl(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_base, const void *d_mat, const void *d_nv,
+                     const void *d_irr, const void *d_spec, const float *d_tab, uint32_t n, void *d_out, size_t out_bytes, uint32_t flags,
+                     void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_ibl");
+  if (!fs || !d_vis || !d_mat || !d_nv || !d_irr || !d_spec || !d_tab || !d_out)
+    return fail(ctx, SRZ_E_INVALID,
+                fn + ": null " +
+                    (!fs ? "frameset" : !d_vis ? "d_vis" : !d_mat ? "d_mat" : !d_nv ? "d_nv" : !d_irr ? "d_irr" : !d_spec ? "d_spec" : !d_tab ? "d_tab" : "d_out"));
+  if (int rc = check_ibl(ctx, fn, n, flags)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, 3u), mat_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u),
+               nv_bytes = srz_frameset_interpolate_bytes(ctx, fs, 1u), vis_bytes = srz_frameset_out_bytes(ctx, fs),
+               tab_bytes = (size_t)n * n * 2u * sizeof(float);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": out_bytes is too small for d_out");
+  if (!aligned<16>({d_vis, d_base, d_mat, d_nv, d_irr, d_spec, d_out}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_base, d_mat, d_nv, d_irr, d_spec, d_out) must be 16-byte aligned");
+  if (!aligned<4>({d_tab})) return fail(ctx, SRZ_E_INVALID, fn + ": d_tab must be 4-byte aligned");
+  if (int rc = check_overlaps(ctx, fn + " (d_out against d_vis, d_base, d_mat, d_nv, d_irr, d_spec, d_tab)", {{d_out, need}},
+                              {{d_vis, vis_bytes}, {d_base, need}, {d_mat, mat_bytes}, {d_nv, nv_bytes}, {d_irr, need}, {d_spec, need},
+                               {d_tab, tab_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_light: caller data only)
+  launch_ibl(ibl_args(fs, d_vis, d_base, d_mat, d_nv, d_irr, d_spec, d_tab, n, d_out, flags), s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_ibl_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_base, const void *d_mat, const void *d_nv,
+                          const void *d_irr, const void *d_spec, const float *d_tab, uint32_t n, const void *d_gout, void *d_gbase,
+                          void *d_gmat, void *d_gnv, void *d_girr, void *d_gspec, float *d_gtab, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_ibl_grad");
+  if (!fs || !d_vis || !d_mat || !d_nv || !d_irr || !d_spec || !d_tab || !d_gout)
+    return fail(ctx, SRZ_E_INVALID,
+                fn + ": null " +
+                    (!fs ? "frameset" : !d_vis ? "d_vis" : !d_mat ? "d_mat" : !d_nv ? "d_nv" : !d_irr ? "d_irr" : !d_spec ? "d_spec" : !d_tab ? "d_tab" : "d_gout"));
+  if (!d_gbase && !d_gmat && !d_gnv && !d_girr && !d_gspec && !d_gtab)
+    return fail(ctx, SRZ_E_INVALID, fn + ": none of d_gbase, d_gmat, d_gnv, d_girr, d_gspec, d_gtab is asked for");
+  if (d_gbase && !d_base) return fail(ctx, SRZ_E_INVALID, fn + ": d_gbase needs d_base");
+  if (int rc = check_ibl(ctx, fn, n, flags)) return rc;
+  const size_t plane_bytes = srz_frameset_interpolate_bytes(ctx, fs, 3u), mat_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u),
+               nv_bytes = srz_frameset_interpolate_bytes(ctx, fs, 1u), vis_bytes = srz_frameset_out_bytes(ctx, fs),
+               tab_bytes = (size_t)n * n * 2u * sizeof(float);
+  if (!aligned<16>({d_vis, d_base, d_mat, d_nv, d_irr, d_spec, d_gout, d_gbase, d_gmat, d_gnv, d_girr, d_gspec}))
+    return fail(ctx, SRZ_E_INVALID,
+                fn + ": the plane buffers (d_vis, d_base, d_mat, d_nv, d_irr, d_spec, d_gout, d_gbase, d_gmat, d_gnv, d_girr, d_gspec) must be "
+                     "16-byte aligned");
+  if (!aligned<4>({d_tab, d_gtab})) return fail(ctx, SRZ_E_INVALID, fn + ": d_tab and d_gtab must be 4-byte aligned");
+  if (int rc = check_overlaps(
+          ctx, fn + " (d_gbase, d_gmat, d_gnv, d_girr, d_gspec, d_gtab against d_vis, d_base, d_mat, d_nv, d_irr, d_spec, d_tab, d_gout)",
+          {{d_gbase, plane_bytes}, {d_gmat, mat_bytes}, {d_gnv, nv_bytes}, {d_girr, plane_bytes}, {d_gspec, plane_bytes}, {d_gtab, tab_bytes}},
+          {{d_vis, vis_bytes}, {d_base, plane_bytes}, {d_mat, mat_bytes}, {d_nv, nv_bytes}, {d_irr, plane_bytes}, {d_spec, plane_bytes},
+           {d_tab, tab_bytes}, {d_gout, plane_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc;
+  IblArgs a = ibl_args(fs, d_vis, d_base, d_mat, d_nv, d_irr, d_spec, d_tab, n, nullptr, flags);
+  a.gout = (const float *)d_gout, a.gbase = (float *)d_gbase, a.gmat = (float *)d_gmat, a.gnv = (float *)d_gnv;
+  a.girr = (float *)d_girr, a.gspec = (float *)d_gspec, a.gtab = d_gtab;
+  launch_ibl_grad(a, s);
+  return end_pass(ctx);
+}
+
 namespace {
 NormalMapArgs normal_map_args(const srz_frameset *fs, const void *d_vis, const void *d_nrm, const void *d_tan, const void *d_m, void *d_out,
                               uint32_t flags) {

@@ -522,6 +522,54 @@ struct MicrofacetArgs {
 };
 void launch_microfacet(const MicrofacetArgs &a, hipStream_t s);
 void launch_microfacet_grad(const MicrofacetArgs &a, float *gpar, hipStream_t s);
+// srz_frameset_reflect / _reflect_grad: the reflection of the view direction about the normal and the raw N.Vd.  nrm, pos and the
+// backward's gnrm, gpos (each may be null) are [frame][3][local_rows][width]; eye is [eye frames][3]; `out` is the forward's
+// [frame][4][local_rows][width] (R, then nv), null in the backward, whose gout has that shape
+struct ReflectArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *nrm, *pos;
+  const float *eye;
+  float *out;
+  const float *gout;
+  float *gnrm, *gpos;
+  uint64_t vis_stride;   // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride; // floats per frame in out / gout = 4 * local_rows * width
+  uint64_t nrm_stride;   // floats per frame in every three-plane buffer = 3 * local_rows * width
+  uint64_t eye_stride;   // 3; 0: one eye for every frame
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_reflect(const ReflectArgs &a, hipStream_t s);
+void launch_reflect_grad(const ReflectArgs &a, hipStream_t s);
+// srz_brdf_table: the split-sum table [n][n][2] of the microfacet pass's specular lobe, m rings of 2 m samples (k_brdf_table).  The
+// host has checked 2 <= n <= SRZ_BRDF_TABLE_MAX and 1 <= m <= 256
+void launch_brdf_table(float *tab, uint32_t n, uint32_t m, hipStream_t s);
+// srz_frameset_ibl / _ibl_grad: the split-sum combine.  base (may be null: ones), irr, spec, out, gout and the backward's gbase, girr,
+// gspec are [frame][3][local_rows][width]; mat and gmat [frame][2][..]: roughness, metallic; nv and gnv [frame][1][..]; tab and gtab
+// (added into) [n][n][2], one for every frame.  Every backward output may be null.  `out` is the forward's output, null in the
+// backward (which addresses its planes by the strides itself).  The host has checked 2 <= n <= SRZ_BRDF_TABLE_MAX
+struct IblArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *base, *mat, *nv, *irr, *spec;
+  const float *tab;
+  float *out;
+  const float *gout;
+  float *gbase, *gmat, *gnv, *girr, *gspec;
+  float *gtab;
+  uint64_t vis_stride;   // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride; // floats per frame in every three-plane buffer = 3 * local_rows * width
+  uint64_t mat_stride;   // floats per frame in mat / gmat = 2 * local_rows * width
+  uint64_t nv_stride;    // floats per frame in nv / gnv = local_rows * width
+  uint32_t n;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_ibl(const IblArgs &a, hipStream_t s);
+void launch_ibl_grad(const IblArgs &a, hipStream_t s);
 // srz_frameset_normal_map / _normal_map_grad: the shading normal of an interpolated normal nrm [frame][3][..], an interpolated tangent
 // with handedness tan [frame][4][..] and a tangent-space normal m [frame][3][..] (k_normal_map), and the backward of that to all
 // three (k_normal_map_grad: gnrm and gm three planes, gtan four with w written +0; each may be null).  `out` is the forward's output,

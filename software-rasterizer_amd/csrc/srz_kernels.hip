@@ -3379,7 +3379,8 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
 // k_cube and k_cube_grad (the walk, quad_ids, quad_store_owned), k_cube_mip, k_cube_mip_grad and k_cube_level (the same, and
 // quad_load), k_persp (the walk, quad_ids), k_persp_grad and
 // k_interp_deriv_persp (all of it), k_light (the walk, quad_ids, quad_load, quad_store_owned) and k_light_grad (the same through
-// pass_tiles and pass_tile: the tile's index names its row of partial sums), k_normal_map and k_normal_map_grad (as k_light), k_microfacet and k_microfacet_grad (as k_light and k_light_grad).
+// pass_tiles and pass_tile: the tile's index names its row of partial sums), k_normal_map and k_normal_map_grad (as k_light), k_microfacet and k_microfacet_grad (as k_light and k_light_grad),
+// k_reflect, k_reflect_grad, k_ibl and k_ibl_grad (as k_light).
 // COPIES, each naming this definition — a fix to the walk goes into them too: k_gbuffer, k_motion, k_pos_grad, aa_body, k_tex,
 // k_tex_grad, k_tex_mip, k_tex_mip_grad (with tex_quad and mip_quad).  Moved onto these helpers they computed the same words
 // (the whole suite passed) but ran slower than their inline text on an MI355X at 256 frames of 1024²: k_gbuffer +4 %, k_motion +6 %,
@@ -6079,6 +6080,282 @@ template <bool WANT_PAR> __global__ __launch_bounds__(256) void k_microfacet_gra
 }
 
 // ================================================================================================================
+// k_reflect / k_reflect_grad — THE REFLECTION VECTOR AND n.v OVER A VISIBILITY BUFFER, FOR CALLER DATA (srz_frameset_reflect and its
+// backward, include/srz.h states the rule and the backward's order of operations): the normal and position planes and the eye ->
+// R = 2 (N.Vd) N - Vd in three planes and the raw N.Vd in a fourth.  light_px is the rule's front part, word for word (the eye is
+// where k_light's parameter frame has it: wave-uniform, scalar loads).  k_microfacet's shape on the passes' helpers: pass_walk,
+// quad_ids, quad_load, quad_store_owned; no LDS, no barrier, no atomics; every output is per pixel, from registers.
+// ================================================================================================================
+struct RfQuad {
+  float4 n[3], P[3];
+  uint32_t own;
+};
+__device__ __forceinline__ void rf_quad_load(const ReflectArgs &a, const PassTile &t, RfQuad &q) {
+  uint32_t id[4];
+  q.own = quad_ids(t, a.vis + (size_t)t.f * a.vis_stride + t.poff, id);
+  q.n[0] = q.n[1] = q.n[2] = q.P[0] = q.P[1] = q.P[2] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (q.own == 0u) return;
+  const size_t off = (size_t)t.f * a.nrm_stride + t.poff;
+  quad_load(a.nrm + off, t.rc.plane, q.n, t.whole, t.x4, t.rc.tx1);
+  quad_load(a.pos + off, t.rc.plane, q.P, t.whole, t.x4, t.rc.tx1);
+}
+// false: not owned, not lit or no view — four zeros, no gradient; nv: the raw cosine
+__device__ __forceinline__ bool rf_quad_px(const RfQuad &q, int k, const SRZ_CAS float *eye, LightPx &px, float &nv) { // (k: a constant)
+  if (!(q.own & (1u << k))) return false;
+  const float nk[3] = {quad_at(q.n[0], k), quad_at(q.n[1], k), quad_at(q.n[2], k)}, Pk[3] = {quad_at(q.P[0], k), quad_at(q.P[1], k), quad_at(q.P[2], k)};
+  if (!light_px(nk, Pk, eye, px) || !px.view) return false;
+  nv = l_dot(px.N, px.Vd);
+  return true;
+}
+__global__ __launch_bounds__(256) void k_reflect(ReflectArgs a) {
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool fused = t.fused(a.flags_or);
+    const SRZ_CAS float *eye = as_const(a.eye) + (size_t)t.f * a.eye_stride;
+    RfQuad q;
+    rf_quad_load(a, t, q);
+    if (q.own == 0u && !fused) return;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 o[4] = {zero4, zero4, zero4, zero4}; // nobody, an owner that is not lit, one without a view: zeros
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      LightPx px;
+      float nv;
+      if (!rf_quad_px(q, k, eye, px, nv)) continue;
+      const float t2 = 2.0f * nv;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) quad_at(o[c], k) = fmaf_(t2, px.N[c], -px.Vd[c]);
+      quad_at(o[3], k) = nv;
+    }
+    quad_store_owned(t.out, t, o, fused, q.own);
+  });
+}
+__global__ __launch_bounds__(256) void k_reflect_grad(ReflectArgs a) {
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool fused = t.fused(a.flags_or);
+    const SRZ_CAS float *eye = as_const(a.eye) + (size_t)t.f * a.eye_stride;
+    RfQuad q;
+    rf_quad_load(a, t, q);
+    if (q.own == 0u && !fused) return;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 g[4] = {zero4, zero4, zero4, zero4}, gn[3] = {zero4, zero4, zero4}, gP[3] = {zero4, zero4, zero4};
+    if (q.own != 0u) quad_load(a.gout + (size_t)t.f * a.frame_stride + t.poff, t.rc.plane, g, t.whole, t.x4, t.rc.tx1);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      LightPx px;
+      float nv;
+      if (!rf_quad_px(q, k, eye, px, nv)) continue;
+      const float gR[3] = {quad_at(g[0], k), quad_at(g[1], k), quad_at(g[2], k)}, t2 = 2.0f * nv;
+      const float g_nv = fmaf_(2.0f, l_dot(gR, px.N), quad_at(g[3], k));
+      float gN[3], gVd[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) gN[c] = fmaf_(g_nv, px.Vd[c], gR[c] * t2), gVd[c] = fmaf_(g_nv, px.N[c], -gR[c]);
+      const float dv = l_dot(gVd, px.Vd), dn = l_dot(gN, px.N);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        quad_at(gP[c], k) = -((gVd[c] - px.Vd[c] * dv) * px.iv);
+        quad_at(gn[c], k) = (gN[c] - px.N[c] * dn) * px.inl;
+      }
+    }
+    const size_t off = (size_t)t.f * a.nrm_stride + t.poff;
+    if (a.gnrm) quad_store_owned(a.gnrm + off, t, gn, fused, q.own);
+    if (a.gpos) quad_store_owned(a.gpos + off, t, gP, fused, q.own);
+  });
+}
+
+// ================================================================================================================
+// k_brdf_table — THE SPLIT-SUM ENVIRONMENT BRDF OF k_microfacet's OWN SPECULAR LOBE (srz_brdf_table, include/srz.h states the
+// quadrature and the order of its sums): entry (i, j) of [n][n][2] is (A, B) at nv = i / (n - 1), roughness RMIN + 0.9375 j / (n - 1),
+// so that F0 A + B is the directional albedo of the lobe mf_term shades with.  m rings of 2 m samples over the projected half vector,
+// rational throughout: /, sqrtf, fmaf.  One wave per entry, the lanes over the rings (ring a on lane a mod 64): a lane sums its ring's
+// 2 m samples in sequence from +0, the ring sums meet in LDS, and lane 0 folds them in ring order with the ring weights — the order
+// is the rule's, whatever the launch shape, so the words are the CPU reference's.
+// ================================================================================================================
+constexpr uint32_t BRDF_M_MAX = 256u;
+__global__ __launch_bounds__(64) void k_brdf_table(float *tab, uint32_t n, uint32_t m) {
+  __shared__ float s_ring[3][BRDF_M_MAX]; // the ring's A sum, its B sum, its weight
+  const uint32_t i = blockIdx.x / n, j = blockIdx.x % n, lane = threadIdx.x;
+  const float nv = (float)i / (float)(n - 1u), rc = fmaf_(0.9375f, (float)j / (float)(n - 1u), MF_RMIN);
+  const float al = rc * rc, a2 = al * al, k = 0.5f * al, omk = 1.0f - k;
+  const float vx = __builtin_sqrtf(fmaf_(-nv, nv, 1.0f)), gv = fmaf_(nv, omk, k), fm = (float)m;
+  for (uint32_t ra = lane; ra < m; ra += 64u) {
+    const float u = ((float)ra + 0.5f) / fm, q = 1.0f - u, xi = fmaf_(-q, q, 1.0f);
+    const float s = (a2 * xi) / fmaf_(-xi, 1.0f - a2, 1.0f), r = __builtin_sqrtf(s), hz = __builtin_sqrtf(1.0f - s);
+    float sa = 0.0f, sb = 0.0f;
+    for (uint32_t b = 0; b < m; ++b) {
+      const float t = ((float)b + 0.5f) / fm, tt = t * t, den = 1.0f + tt, c = (1.0f - tt) / den, wa = (2.0f / den) / fm;
+#pragma unroll
+      for (int sgn = 0; sgn < 2; ++sgn) {
+        const float hx = sgn ? -(r * c) : r * c;
+        const float vh = fmaf_(vx, hx, nv * hz), nl = fmaf_(2.0f * vh, hz, -nv);
+        const bool take = vh > 0.0f && nl > 0.0f;
+        const float gl = fmaf_(nl, omk, k), f = (nl * vh) / (hz * (gl * gv));
+        const float x = 1.0f - (vh < 1.0f ? vh : 1.0f), x2 = x * x, x4 = x2 * x2, x5 = x4 * x;
+        sa = sa + (take ? (f * (1.0f - x5)) * wa : 0.0f), sb = sb + (take ? (f * x5) * wa : 0.0f);
+      }
+    }
+    s_ring[0][ra] = sa, s_ring[1][ra] = sb, s_ring[2][ra] = (2.0f * q) / fm;
+  }
+  __syncthreads();
+  if (lane == 0u) {
+    float A = 0.0f, B = 0.0f;
+    for (uint32_t ra = 0; ra < m; ++ra) A = fmaf_(s_ring[0][ra], s_ring[2][ra], A), B = fmaf_(s_ring[1][ra], s_ring[2][ra], B);
+    tab[2u * blockIdx.x] = A * MF_INV_PI, tab[2u * blockIdx.x + 1u] = B * MF_INV_PI;
+  }
+}
+
+// ================================================================================================================
+// k_ibl / k_ibl_grad — THE SPLIT-SUM COMBINE OVER A VISIBILITY BUFFER, FOR CALLER DATA (srz_frameset_ibl and its backward,
+// include/srz.h states the rule and the backward's order of operations): base colour, material (roughness, metallic: mf_px's clamps,
+// word for word), nv, the irradiance and the prefiltered specular planes and the table [n][n][2] ->
+// out = cdif irr + spec (F0 A + B), (A, B) bilinear at (nv, roughness) in tex_bilinear's three-fmaf form.  The clamps hold the cell
+// inside the table whatever the planes hold.  k_microfacet's shape on the passes' helpers.  ibl_px is the rule's text; both kernels go
+// through it.  The backward's planes are per pixel, from registers; WANT_TAB, the table's gradient is summed per WORKGROUP in LDS
+// (the whole table fits: 32 KiB at n = 64; ds float adds) over every tile the workgroup walks, then one global float add per word
+// the workgroup touched: not bit-reproducible, within texture_grad's bound.  That build's grid is capped lower, so that a workgroup
+// walks several tiles per clear and flush of its table.
+// ================================================================================================================
+struct IblPx {
+  float base[3], F0[3], cdif[3], irr[3], spec[3], sc[3];
+  float mc, om, tx, ty, A, B, dAx, dBx, dAy, dBy;
+  bool r_in, m_in, nv_in;
+  uint32_t at; // the cell's first word pair: x0 * n + y0
+};
+__device__ __forceinline__ void ibl_px(const float (&base)[3], float r, float m, float nv, const float (&irr)[3], const float (&spec)[3],
+                                       const float *tab, uint32_t n, float sx, float sy, IblPx &p) {
+  const float rc = r > MF_RMIN ? (r < 1.0f ? r : 1.0f) : MF_RMIN;
+  p.r_in = r > MF_RMIN && r < 1.0f;
+  p.mc = m > 0.0f ? (m < 1.0f ? m : 1.0f) : 0.0f, p.m_in = m > 0.0f && m < 1.0f;
+  const float nvc = nv > 0.0f ? (nv < 1.0f ? nv : 1.0f) : 0.0f;
+  p.nv_in = nv > 0.0f && nv < 1.0f;
+  const float x = nvc * sx, y = (rc - MF_RMIN) * sy; // (both in [0, n - 1 + an ulp]: the clamps leave no NaN)
+  const int fx = (int)__builtin_floorf(x), fy = (int)__builtin_floorf(y), last = (int)n - 2;
+  const int x0 = fx < last ? fx : last, y0 = fy < last ? fy : last;
+  p.tx = x - (float)x0, p.ty = y - (float)y0;
+  p.at = (uint32_t)x0 * n + (uint32_t)y0;
+  const float *t00 = tab + 2u * p.at, *t10 = t00 + 2u * n;
+  float v[2], dx[2], dy[2];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const float d0 = t00[2 + e] - t00[e], d1 = t10[2 + e] - t10[e];
+    const float top = fmaf_(p.ty, d0, t00[e]), bot = fmaf_(p.ty, d1, t10[e]);
+    dx[e] = bot - top, v[e] = fmaf_(p.tx, dx[e], top), dy[e] = fmaf_(p.tx, d1 - d0, d0);
+  }
+  p.A = v[0], p.B = v[1], p.dAx = dx[0], p.dBx = dx[1], p.dAy = dy[0], p.dBy = dy[1];
+  p.om = 1.0f - p.mc;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    p.base[c] = base[c], p.irr[c] = irr[c], p.spec[c] = spec[c];
+    p.F0[c] = fmaf_(p.mc, base[c] - 0.04f, 0.04f);
+    p.cdif[c] = base[c] * p.om;
+    p.sc[c] = fmaf_(p.F0[c], p.A, p.B);
+  }
+}
+struct IblQuad {
+  float4 b[3], m[2], nv[1], irr[3], spec[3];
+  uint32_t own;
+};
+__device__ __forceinline__ void ibl_quad_load(const IblArgs &a, const PassTile &t, IblQuad &q) {
+  uint32_t id[4];
+  q.own = quad_ids(t, a.vis + (size_t)t.f * a.vis_stride + t.poff, id);
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f), one4 = make_float4(1.f, 1.f, 1.f, 1.f);
+  q.m[0] = q.m[1] = q.nv[0] = q.irr[0] = q.irr[1] = q.irr[2] = q.spec[0] = q.spec[1] = q.spec[2] = zero4, q.b[0] = q.b[1] = q.b[2] = one4;
+  if (q.own == 0u) return;
+  const size_t off = (size_t)t.f * a.frame_stride + t.poff;
+  if (a.base) quad_load(a.base + off, t.rc.plane, q.b, t.whole, t.x4, t.rc.tx1);
+  quad_load(a.mat + (size_t)t.f * a.mat_stride + t.poff, t.rc.plane, q.m, t.whole, t.x4, t.rc.tx1);
+  quad_load(a.nv + (size_t)t.f * a.nv_stride + t.poff, t.rc.plane, q.nv, t.whole, t.x4, t.rc.tx1);
+  quad_load(a.irr + off, t.rc.plane, q.irr, t.whole, t.x4, t.rc.tx1);
+  quad_load(a.spec + off, t.rc.plane, q.spec, t.whole, t.x4, t.rc.tx1);
+}
+__device__ __forceinline__ void ibl_quad_px(const IblArgs &a, const IblQuad &q, int k, float sx, float sy, IblPx &p) { // (k: a constant)
+  const float bk[3] = {quad_at(q.b[0], k), quad_at(q.b[1], k), quad_at(q.b[2], k)};
+  const float ik[3] = {quad_at(q.irr[0], k), quad_at(q.irr[1], k), quad_at(q.irr[2], k)};
+  const float sk[3] = {quad_at(q.spec[0], k), quad_at(q.spec[1], k), quad_at(q.spec[2], k)};
+  ibl_px(bk, quad_at(q.m[0], k), quad_at(q.m[1], k), quad_at(q.nv[0], k), ik, sk, a.tab, a.n, sx, sy, p);
+}
+__global__ __launch_bounds__(256) void k_ibl(IblArgs a) {
+  const float sx = (float)(a.n - 1u), sy = (float)(a.n - 1u) / 0.9375f;
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool fused = t.fused(a.flags_or);
+    IblQuad q;
+    ibl_quad_load(a, t, q);
+    if (q.own == 0u && !fused) return;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 o[3] = {zero4, zero4, zero4}; // nobody: zeros
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (!(q.own & (1u << k))) continue;
+      IblPx p;
+      ibl_quad_px(a, q, k, sx, sy, p);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) quad_at(o[c], k) = fmaf_(p.cdif[c], p.irr[c], p.spec[c] * p.sc[c]);
+    }
+    quad_store_owned(t.out, t, o, fused, q.own);
+  });
+}
+constexpr uint32_t IBL_TAB_MAX = 64u; // SRZ_BRDF_TABLE_MAX: the table's words fit LDS
+template <bool WANT_TAB> __global__ __launch_bounds__(256) void k_ibl_grad(IblArgs a) {
+  __shared__ float s_tab[WANT_TAB ? 2u * IBL_TAB_MAX * IBL_TAB_MAX : 1u];
+  const uint32_t tid = threadIdx.x, n_words = 2u * a.n * a.n; // (the host has checked n <= 64)
+  const float sx = (float)(a.n - 1u), sy = (float)(a.n - 1u) / 0.9375f;
+  if (WANT_TAB) {
+    for (uint32_t i = tid; i < n_words; i += 256u) s_tab[i] = 0.0f;
+    __syncthreads();
+  }
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier inside the walk: a thread outside the frame just moves on)
+    const bool fused = t.fused(a.flags_or);
+    IblQuad q;
+    ibl_quad_load(a, t, q);
+    if (q.own == 0u && !fused) return;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 g[3] = {zero4, zero4, zero4}, gb[3] = {zero4, zero4, zero4}, gi[3] = {zero4, zero4, zero4}, gsp[3] = {zero4, zero4, zero4};
+    float4 gm[2] = {zero4, zero4}, gn[1] = {zero4};
+    const size_t off = (size_t)t.f * a.frame_stride + t.poff;
+    if (q.own != 0u) quad_load(a.gout + off, t.rc.plane, g, t.whole, t.x4, t.rc.tx1);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (!(q.own & (1u << k))) continue;
+      IblPx p;
+      ibl_quad_px(a, q, k, sx, sy, p);
+      const float gk[3] = {quad_at(g[0], k), quad_at(g[1], k), quad_at(g[2], k)};
+      float gcd[3], gs[3], gF0[3], bm[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        gcd[c] = gk[c] * p.irr[c], quad_at(gi[c], k) = gk[c] * p.cdif[c];
+        gs[c] = gk[c] * p.spec[c], quad_at(gsp[c], k) = gk[c] * p.sc[c];
+        gF0[c] = gs[c] * p.A, bm[c] = p.base[c] - 0.04f;
+        quad_at(gb[c], k) = fmaf_(gF0[c], p.mc, gcd[c] * p.om);
+      }
+      const float gA = l_dot(gs, p.F0), gB = l_dot(gk, p.spec);
+      const float g_mc = l_dot(gF0, bm), g_om = l_dot(gcd, p.base);
+      const float g_x = fmaf_(gA, p.dAx, gB * p.dBx), g_y = fmaf_(gA, p.dAy, gB * p.dBy);
+      quad_at(gm[0], k) = p.r_in ? g_y * sy : 0.0f;
+      quad_at(gm[1], k) = p.m_in ? g_mc - g_om : 0.0f;
+      quad_at(gn[0], k) = p.nv_in ? g_x * sx : 0.0f;
+      if (WANT_TAB) {
+        const float ux = 1.0f - p.tx, uy = 1.0f - p.ty;
+        const float w[4] = {ux * uy, ux * p.ty, p.tx * uy, p.tx * p.ty};
+        const uint32_t at[4] = {p.at, p.at + 1u, p.at + a.n, p.at + a.n + 1u}; // (x0, y0 <= n - 2: all four inside the table)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) atomicAdd(&s_tab[2u * at[c]], w[c] * gA), atomicAdd(&s_tab[2u * at[c] + 1u], w[c] * gB);
+      }
+    }
+    if (a.gbase) quad_store_owned(a.gbase + off, t, gb, fused, q.own);
+    if (a.gmat) quad_store_owned(a.gmat + (size_t)t.f * a.mat_stride + t.poff, t, gm, fused, q.own);
+    if (a.gnv) quad_store_owned(a.gnv + (size_t)t.f * a.nv_stride + t.poff, t, gn, fused, q.own);
+    if (a.girr) quad_store_owned(a.girr + off, t, gi, fused, q.own);
+    if (a.gspec) quad_store_owned(a.gspec + off, t, gsp, fused, q.own);
+  });
+  if (WANT_TAB) { // (the walk's exit is uniform over the workgroup: every thread is here)
+    __syncthreads();
+    for (uint32_t i = tid; i < n_words; i += 256u) {
+      const float v = s_tab[i];
+      if (v != 0.0f) global_add(a.gtab + i, v); // (a NaN is not 0: it goes too)
+    }
+  }
+}
+
+// ================================================================================================================
 // k_normal_map / k_normal_map_grad — TANGENT-SPACE NORMAL MAPPING OVER A VISIBILITY BUFFER, FOR CALLER DATA (srz_frameset_normal_map
 // and its backward, include/srz.h states the rule and the backward's order of operations): the interpolated normal (3 planes), the
 // interpolated tangent with its handedness (4 planes) and the tangent-space normal m (3 planes) -> the unit shading normal k_light
@@ -8537,6 +8814,16 @@ void launch_microfacet_grad(const MicrofacetArgs &a, float *gpar, hipStream_t s)
   float *rows = shared ? a.work + (size_t)a.n_frames * tpf * K : gpar;
   if (a.n_frames != 0u) hipLaunchKernelGGL(k_light_fold, dim3(a.n_frames), dim3(64), 0, s, (const float *)a.work, rows, tpf, K);
   if (shared) hipLaunchKernelGGL(k_light_fold, dim3(1), dim3(64), 0, s, (const float *)rows, gpar, a.n_frames, K);
+}
+void launch_reflect(const ReflectArgs &a, hipStream_t s) { launch_pass<k_reflect>(a, s); }
+void launch_reflect_grad(const ReflectArgs &a, hipStream_t s) { launch_pass<k_reflect_grad>(a, s); }
+void launch_brdf_table(float *tab, uint32_t n, uint32_t m, hipStream_t s) { hipLaunchKernelGGL(k_brdf_table, dim3(n * n), dim3(64), 0, s, tab, n, m); }
+void launch_ibl(const IblArgs &a, hipStream_t s) { launch_pass<k_ibl>(a, s); }
+// (with gtab: a grid of at most 1024 workgroups, so that each clears and flushes its LDS table once for several tiles)
+void launch_ibl_grad(const IblArgs &a, hipStream_t s) {
+  if (!a.gtab) return launch_pass<k_ibl_grad<false>>(a, s);
+  const uint32_t items = a.n_frames * a.n_local_bands * a.tiles_x;
+  if (items != 0) hipLaunchKernelGGL(k_ibl_grad<true>, dim3(tile_grid(items, 1024u)), dim3(256), 0, s, a);
 }
 void launch_normal_map(const NormalMapArgs &a, hipStream_t s) { launch_pass<k_normal_map>(a, s); }
 void launch_normal_map_grad(const NormalMapArgs &a, hipStream_t s) { launch_pass<k_normal_map_grad>(a, s); }

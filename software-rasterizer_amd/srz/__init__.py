@@ -37,6 +37,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_cube_prefilter_work_bytes", "srz_cube_prefilter", "srz_cube_prefilter_grad",
            "srz_frameset_light", "srz_frameset_light_work_bytes", "srz_frameset_light_grad",
            "srz_frameset_microfacet", "srz_frameset_microfacet_work_bytes", "srz_frameset_microfacet_grad",
+           "srz_frameset_reflect", "srz_frameset_reflect_grad", "srz_brdf_table", "srz_frameset_ibl", "srz_frameset_ibl_grad",
            "srz_frameset_shadow", "srz_frameset_shadow_grad",
            "srz_mesh_tangents", "srz_mesh_tangents_grad", "srz_frameset_normal_map", "srz_frameset_normal_map_grad",
            "srz_frameset_perspective", "srz_frameset_perspective_grad", "srz_frameset_interpolate_deriv_persp",
@@ -141,6 +142,11 @@ def lib():
         L.srz_frameset_microfacet_work_bytes.argtypes = abi.MICROFACET_WORK_BYTES_ARGTYPES
         L.srz_frameset_microfacet_work_bytes.restype = C.c_size_t
         L.srz_frameset_microfacet_grad.argtypes = abi.MICROFACET_GRAD_ARGTYPES
+        L.srz_frameset_reflect.argtypes = abi.REFLECT_ARGTYPES
+        L.srz_frameset_reflect_grad.argtypes = abi.REFLECT_GRAD_ARGTYPES
+        L.srz_brdf_table.argtypes = abi.BRDF_TABLE_ARGTYPES
+        L.srz_frameset_ibl.argtypes = abi.IBL_ARGTYPES
+        L.srz_frameset_ibl_grad.argtypes = abi.IBL_GRAD_ARGTYPES
         L.srz_mesh_tangents.argtypes = abi.MESH_TANGENTS_ARGTYPES
         L.srz_mesh_tangents_grad.argtypes = abi.MESH_TANGENTS_GRAD_ARGTYPES
         L.srz_frameset_normal_map.argtypes = abi.NORMAL_MAP_ARGTYPES
@@ -598,6 +604,43 @@ class FrameSet:
                                                            C.c_void_p(d_gpar_ptr or None), C.c_void_p(d_work_ptr or None), work_bytes, flags,
                                                            _stream(stream)))
 
+    def reflect(self, d_vis_ptr, d_nrm_ptr, d_pos_ptr, d_eye_ptr, par_frames, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """the reflection of the view direction about the normal, and n.v: the caller's planes d_nrm, d_pos
+        [frame][3][local_rows][width] and the eye d_eye [par_frames][3] on the device (par_frames: 1 or the frame count) → d_out
+        [frame][4][local_rows][width]: R = 2 (N.Vd) N - Vd, then the RAW N.Vd (include/srz.h states the rule).  An owner without a
+        lit normal or a view gets four zeros: texture_cube's "unsampled".  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_reflect(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_nrm_ptr), C.c_void_p(d_pos_ptr),
+                                                   C.c_void_p(d_eye_ptr), par_frames, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def reflect_grad(self, d_vis_ptr, d_nrm_ptr, d_pos_ptr, d_eye_ptr, par_frames, d_gout_ptr, d_gnrm_ptr, d_gpos_ptr, flags=abi.FUSED_CLEAR,
+                     stream=None):
+        """the backward of reflect: d_gout [frame][4][local_rows][width] → written to d_gnrm and / or d_gpos (three planes; one may be
+        None / 0), per pixel, deterministic.  The eye's gradient is minus the sum of a frame's d_gpos.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_reflect_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_nrm_ptr), C.c_void_p(d_pos_ptr),
+                                                        C.c_void_p(d_eye_ptr), par_frames, C.c_void_p(d_gout_ptr), C.c_void_p(d_gnrm_ptr or None),
+                                                        C.c_void_p(d_gpos_ptr or None), flags, _stream(stream)))
+
+    def ibl(self, d_vis_ptr, d_base_ptr, d_mat_ptr, d_nv_ptr, d_irr_ptr, d_spec_ptr, d_tab_ptr, n, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR,
+            stream=None):
+        """the split-sum combine: d_base (None / 0: ones), d_irr, d_spec [frame][3][local_rows][width], d_mat [frame][2][..] (roughness,
+        metallic), d_nv [frame][1][..] and Context.brdf_table's d_tab [n][n][2] → d_out [frame][3][..] = cdif irr + spec (F0 A + B),
+        unclamped (include/srz.h states the rule).  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_ibl(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_base_ptr or None), C.c_void_p(d_mat_ptr),
+                                               C.c_void_p(d_nv_ptr), C.c_void_p(d_irr_ptr), C.c_void_p(d_spec_ptr), C.c_void_p(d_tab_ptr), n,
+                                               C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def ibl_grad(self, d_vis_ptr, d_base_ptr, d_mat_ptr, d_nv_ptr, d_irr_ptr, d_spec_ptr, d_tab_ptr, n, d_gout_ptr, d_gbase_ptr, d_gmat_ptr,
+                 d_gnv_ptr, d_girr_ptr, d_gspec_ptr, d_gtab_ptr, flags=abi.FUSED_CLEAR, stream=None):
+        """the backward of ibl: d_gout [frame][3][local_rows][width] → written to d_gbase, d_girr, d_gspec (three planes), d_gmat (two),
+        d_gnv (one), all per pixel and deterministic, and / or ADDED INTO d_gtab [n][n][2] (float adds: within texture_grad's bound).
+        Every output pointer may be None / 0, not all; d_gbase needs d_base.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_ibl_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_base_ptr or None),
+                                                    C.c_void_p(d_mat_ptr), C.c_void_p(d_nv_ptr), C.c_void_p(d_irr_ptr), C.c_void_p(d_spec_ptr),
+                                                    C.c_void_p(d_tab_ptr), n, C.c_void_p(d_gout_ptr), C.c_void_p(d_gbase_ptr or None),
+                                                    C.c_void_p(d_gmat_ptr or None), C.c_void_p(d_gnv_ptr or None),
+                                                    C.c_void_p(d_girr_ptr or None), C.c_void_p(d_gspec_ptr or None),
+                                                    C.c_void_p(d_gtab_ptr or None), flags, _stream(stream)))
+
     def normal_map(self, d_vis_ptr, d_nrm_ptr, d_tan_ptr, d_m_ptr, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
         """tangent-space normal mapping of the caller's planes: d_nrm [frame][3][local_rows][width] (the interpolated normal), d_tan
         [frame][4][...] (the interpolated tangent and handedness of Context.mesh_tangents) and d_m [frame][3][...] (the tangent-space
@@ -863,6 +906,12 @@ class Context:
         d_gsrc_ptr (written, not added into), deterministic.  Asynchronous."""
         self._check(lib().srz_cube_prefilter_grad(self.h, C.c_void_p(d_gdst_ptr), C.c_void_p(d_den_ptr), n_src, n_dst, n_ch, tex_frames, kind,
                                                   roughness, cmin, C.c_void_p(d_gsrc_ptr), C.c_void_p(d_work_ptr), work_bytes, _stream(stream)))
+
+    def brdf_table(self, d_tab_ptr, tab_bytes, n, m, stream=None):
+        """the split-sum table of FrameSet.microfacet's own specular lobe → d_tab [n][n][2] float32 (A, B; F0 A + B is the lobe's
+        directional albedo), rows nv = i / (n - 1), columns roughness 1/16 + 15/16 j / (n - 1); m rings of 2 m samples, in a fixed
+        order (include/srz.h states the quadrature): deterministic.  2 <= n <= abi.BRDF_TABLE_MAX, 1 <= m <= 256.  Asynchronous."""
+        self._check(lib().srz_brdf_table(self.h, C.c_void_p(d_tab_ptr), tab_bytes, n, m, _stream(stream)))
 
     def mesh_upload(self, mesh_id, verts8, faces):
         """verts8: (nV,8) float32 [pos3 nrm3 uv2]; faces: (nF,3) uint32."""

@@ -86,6 +86,13 @@ PREFILTER_COSINE, PREFILTER_GGX = 0, 1  # SRZ_PREFILTER_*
 CUBE_PREFILTER_WORK_BYTES_ARGTYPES = [_u32, _u32, _u32, _u32]
 CUBE_PREFILTER_ARGTYPES = [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, C.c_float, C.c_float, _vp, _vp, C.c_size_t, _vp]
 CUBE_PREFILTER_GRAD_ARGTYPES = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, C.c_float, C.c_float, _vp, _vp, C.c_size_t, _vp]
+# the prototypes of srz_frameset_reflect / _reflect_grad / srz_brdf_table / srz_frameset_ibl / _ibl_grad (argtypes; all return int)
+BRDF_TABLE_MAX = 64  # srz_brdf_table, srz_frameset_ibl: the largest table side (SRZ_BRDF_TABLE_MAX)
+REFLECT_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, C.c_size_t, _u32, _vp]
+REFLECT_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp]
+BRDF_TABLE_ARGTYPES = [_vp, _vp, C.c_size_t, _u32, _u32, _vp]
+IBL_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, C.c_size_t, _u32, _vp]
+IBL_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]
 
 # numpy view of srz_tri (96 B): pos[3][3], nrm[3][3], uv[3][2]
 TRI_DTYPE = np.dtype([("pos", "<f4", (3, 3)), ("nrm", "<f4", (3, 3)), ("uv", "<f4", (3, 2))])

@@ -851,6 +851,151 @@ def microfacet(fs, vis, nrm, pos, base, mat, lights, eye, amb, stream=None):
     return _Microfacet.apply(nrm, pos, base, mat, microfacet_params(fs, lights, eye, amb), fs, vis, stream)
 
 
+def _plane_check(what, name, t, shape):
+    if t is None or t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} must be a CUDA float32 tensor {tuple(shape)}, got {None if t is None else (tuple(t.shape), t.dtype)}")
+    return t.contiguous()
+
+
+def _reflect_args(fs, nrm, pos, eye):
+    """→ (nrm, pos, eye [1 or n_frames, 3]), checked and contiguous"""
+    shape = fs.interpolate_shape(3)
+    nrm, pos = _plane_check("reflect", "nrm", nrm, shape), _plane_check("reflect", "pos", pos, shape)
+    if eye.dtype != torch.float32 or not eye.is_cuda or eye.dim() not in (1, 2) or eye.shape[-1] != 3 or \
+            (eye.dim() == 2 and eye.shape[0] not in (1, fs.n_frames)):
+        raise ValueError(f"reflect: eye must be a CUDA float32 tensor [3] or [1 or {fs.n_frames}, 3], got {tuple(eye.shape)} {eye.dtype}")
+    return nrm, pos, eye.reshape(-1, 3).contiguous()
+
+
+def reflect_grad(fs, vis, nrm, pos, eye, gout, want_gnrm=True, want_gpos=True, stream=None):
+    """the backward of reflect by one FrameSet.reflect_grad call: gout [n_frames, 4, rows, W] → (gnrm, gpos), each [n_frames, 3, rows,
+    W] or None when not wanted (not both): per pixel, deterministic, zeros where nobody owns the pixel, its normal is not lit or it has
+    no view.  The eye's gradient is minus gpos summed over a frame.  stream: a raw stream handle, None = torch's current stream."""
+    if not (want_gnrm or want_gpos):
+        raise ValueError("reflect_grad: no gradient is asked for")
+    nrm, pos, eye = _reflect_args(fs, nrm, pos, eye)
+    gout = _plane_check("reflect_grad", "gout", gout, fs.interpolate_shape(4))
+    gnrm, gpos = (torch.empty_like(nrm) if w else None for w in (want_gnrm, want_gpos))
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    fs.reflect_grad(vis.data_ptr(), nrm.data_ptr(), pos.data_ptr(), eye.data_ptr(), eye.shape[0], gout.data_ptr(), ptr(gnrm), ptr(gpos),
+                    abi.FUSED_CLEAR, _stream_ptr(stream))
+    return gnrm, gpos
+
+
+class _Reflect(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, nrm, pos, eye, fs, vis, stream):
+        ctx.eye_shape = tuple(eye.shape)
+        nrm, pos, eye = _reflect_args(fs, nrm, pos, eye)
+        out = torch.empty(fs.interpolate_shape(4), dtype=torch.float32, device=nrm.device)
+        fs.reflect(vis.data_ptr(), nrm.data_ptr(), pos.data_ptr(), eye.data_ptr(), eye.shape[0], out.data_ptr(), fs.interpolate_bytes(4),
+                   abi.FUSED_CLEAR, _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.stream = fs, vis, stream
+        ctx.save_for_backward(nrm, pos, eye)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        nrm, pos, eye = ctx.saved_tensors
+        need_n, need_p, need_e = ctx.needs_input_grad[:3]
+        gnrm = gpos = geye = None
+        if need_n or need_p or need_e:
+            gnrm, gpos = reflect_grad(ctx.fs, ctx.vis, nrm, pos, eye, gout, need_n, need_p or need_e, ctx.stream)
+        if need_e:  # R and nv depend on eye - P only: the eye's gradient is minus the owned pixels' gpos, summed (nobody's are zeros)
+            per_frame = -gpos.sum(dim=(2, 3))
+            geye = (per_frame if eye.shape[0] != 1 else per_frame.sum(0, keepdim=True)).reshape(ctx.eye_shape)
+        return gnrm, gpos if need_p else None, geye, None, None, None
+
+
+def reflect(fs, vis, nrm, pos, eye, stream=None):
+    """the reflection vector and n.v for image-based lighting under a visibility buffer `vis` of FrameSet `fs`: nrm, pos
+    [n_frames, 3, rows, W] CUDA float32, eye [3] or [n_frames, 3] on the device → [n_frames, 4, rows, W]: planes 0..2 R = 2 (N.Vd) N -
+    Vd — the direction texture_cube_mip takes —, plane 3 the RAW N.Vd — what ibl takes, and clamps — (FrameSet.reflect; include/srz.h
+    states the rule).  Four zeros where nobody owns the pixel, its normal has no finite positive length or the eye lies on it: a zero
+    direction is texture_cube's "unsampled".  Differentiable with respect to nrm, pos (one reflect_grad call, deterministic planes) and
+    eye (minus the sum of pos's gradient, a torch reduction).  stream: a raw stream handle, None = torch's current stream."""
+    return _Reflect.apply(nrm, pos, eye, fs, vis, stream)
+
+
+def brdf_table(ctx_or_fs, n, m=64, stream=None, device=None):
+    """the split-sum table [n, n, 2] CUDA float32 (A, B) of microfacet's own specular lobe, for ibl: rows over n.v in [0, 1], columns
+    over the roughness in [1 / 16, 1], nodes on the clamp edges; m rings of 2 m samples (Context.brdf_table; include/srz.h states the
+    quadrature).  Deterministic.  Build it once.  ctx_or_fs: the Context, or a FrameSet of it."""
+    ctx = getattr(ctx_or_fs, "ctx", ctx_or_fs)
+    if not 2 <= int(n) <= abi.BRDF_TABLE_MAX or not 1 <= int(m) <= 256:
+        raise ValueError(f"brdf_table: 2 <= n <= {abi.BRDF_TABLE_MAX} and 1 <= m <= 256, got n {n}, m {m}")
+    tab = torch.empty((int(n), int(n), 2), dtype=torch.float32, device=device or "cuda")
+    ctx.brdf_table(tab.data_ptr(), tab.numel() * 4, int(n), int(m), _stream_ptr(stream))
+    return tab
+
+
+def _ibl_args(fs, base, mat, nv, irr, spec, tab):
+    """→ (base or None, mat, nv, irr, spec, tab, n), checked and contiguous"""
+    s3, s2, s1 = fs.interpolate_shape(3), fs.interpolate_shape(2), fs.interpolate_shape(1)
+    base = None if base is None else _plane_check("ibl", "base", base, s3)
+    mat, nv = _plane_check("ibl", "mat", mat, s2), _plane_check("ibl", "nv", nv, s1)
+    irr, spec = _plane_check("ibl", "irr", irr, s3), _plane_check("ibl", "spec", spec, s3)
+    if tab is None or tab.dtype != torch.float32 or not tab.is_cuda or tab.dim() != 3 or tab.shape[0] != tab.shape[1] or tab.shape[2] != 2 or \
+            not 2 <= tab.shape[0] <= abi.BRDF_TABLE_MAX:
+        raise ValueError(f"ibl: tab must be a CUDA float32 tensor [n, n, 2] with 2 <= n <= {abi.BRDF_TABLE_MAX}, got "
+                         f"{None if tab is None else (tuple(tab.shape), tab.dtype)}")
+    return base, mat, nv, irr, spec, tab.contiguous(), tab.shape[0]
+
+
+def ibl_grad(fs, vis, base, mat, nv, irr, spec, tab, gout, want_gbase=True, want_gmat=True, want_gnv=True, want_girr=True, want_gspec=True,
+             want_gtab=True, stream=None):
+    """the backward of ibl by one FrameSet.ibl_grad call: gout [n_frames, 3, rows, W] → (gbase, gmat, gnv, girr, gspec, gtab), each None
+    when not wanted (not all; gbase is None without base): the planes per pixel and deterministic, gmat and gnv zero where a clamp
+    holds; gtab [n, n, 2] summed with float adds (not bit-reproducible).  stream: a raw stream handle, None = torch's current stream."""
+    want_gbase = want_gbase and base is not None
+    if not (want_gbase or want_gmat or want_gnv or want_girr or want_gspec or want_gtab):
+        raise ValueError("ibl_grad: no gradient is asked for")
+    base, mat, nv, irr, spec, tab, n = _ibl_args(fs, base, mat, nv, irr, spec, tab)
+    gout = _plane_check("ibl_grad", "gout", gout, fs.interpolate_shape(3))
+    gbase, gmat, gnv, girr, gspec = (torch.empty_like(t) if w else None for t, w in
+                                     ((irr, want_gbase), (mat, want_gmat), (nv, want_gnv), (irr, want_girr), (spec, want_gspec)))
+    gtab = torch.zeros_like(tab) if want_gtab else None
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    fs.ibl_grad(vis.data_ptr(), ptr(base), mat.data_ptr(), nv.data_ptr(), irr.data_ptr(), spec.data_ptr(), tab.data_ptr(), n, gout.data_ptr(),
+                ptr(gbase), ptr(gmat), ptr(gnv), ptr(girr), ptr(gspec), ptr(gtab), abi.FUSED_CLEAR, _stream_ptr(stream))
+    return gbase, gmat, gnv, girr, gspec, gtab
+
+
+class _Ibl(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, base, mat, nv, irr, spec, tab, fs, vis, stream):
+        base, mat, nv, irr, spec, tab, n = _ibl_args(fs, base, mat, nv, irr, spec, tab)
+        out = torch.empty(fs.interpolate_shape(3), dtype=torch.float32, device=mat.device)
+        fs.ibl(vis.data_ptr(), None if base is None else base.data_ptr(), mat.data_ptr(), nv.data_ptr(), irr.data_ptr(), spec.data_ptr(),
+               tab.data_ptr(), n, out.data_ptr(), fs.interpolate_bytes(3), abi.FUSED_CLEAR, _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.stream, ctx.has_base = fs, vis, stream, base is not None
+        ctx.save_for_backward(mat, nv, irr, spec, tab, *([base] if base is not None else []))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        mat, nv, irr, spec, tab = ctx.saved_tensors[:5]
+        base = ctx.saved_tensors[5] if ctx.has_base else None
+        need = list(ctx.needs_input_grad[:6])
+        need[0] = need[0] and ctx.has_base
+        grads = (None,) * 6
+        if any(need):  # one call, asking only for what is needed
+            grads = ibl_grad(ctx.fs, ctx.vis, base, mat, nv, irr, spec, tab, gout, *need, ctx.stream)
+        return (*grads, None, None, None)
+
+
+def ibl(fs, vis, base, mat, nv, irr, spec, tab, stream=None):
+    """image-based lighting's split-sum combine for the caller's own planes under a visibility buffer `vis` of FrameSet `fs`: base (or
+    None: ones), irr — texture_cube of cube_irradiance at the normal —, spec — texture_cube_mip of cube_prefilter_pyramid at reflect's R
+    and roughness * (levels - 1) — [n_frames, 3, rows, W] CUDA float32, mat [n_frames, 2, rows, W] (roughness, metallic: microfacet's
+    clamps), nv [n_frames, 1, rows, W] (reflect's plane 3; clamped to [0, 1] here), tab brdf_table's [n, n, 2] →
+    [n_frames, 3, rows, W]: base (1 - metallic) irr + spec (F0 A + B), (A, B) bilinear in the table, no pi, no clamp of the result,
+    zeros where nobody owns the pixel (FrameSet.ibl; include/srz.h states the rule).  Differentiable with respect to base, mat, nv,
+    irr, spec (deterministic planes) and tab (float adds).  Backward is one ibl_grad call that asks only for the outputs some input
+    needs.  Add microfacet(...) for the point lights.  stream: a raw stream handle, None = torch's current stream."""
+    return _Ibl.apply(base, mat, nv, irr, spec, tab, fs, vis, stream)
+
+
 def _normal_map_args(fs, nrm, tan, m):
     """→ (nrm, tan, m), checked and contiguous"""
     for name, t, n in (("nrm", nrm, 3), ("tan", tan, 4), ("m", m, 3)):
