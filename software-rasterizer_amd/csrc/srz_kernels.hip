@@ -3381,6 +3381,9 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
 // k_interp_deriv_persp (all of it), k_light (the walk, quad_ids, quad_load, quad_store_owned) and k_light_grad (the same through
 // pass_tiles and pass_tile: the tile's index names its row of partial sums), k_normal_map and k_normal_map_grad (as k_light), k_microfacet and k_microfacet_grad (as k_light and k_light_grad),
 // k_reflect, k_reflect_grad, k_ibl and k_ibl_grad (as k_light).
+// Beyond tile_grid's cap (a workgroup's second trip round pass_tiles' loop, with what it carries) the callers are tested in
+// tests/test_gpu_pass_walk.py (k_shade_vis, k_interp, k_interp_grad, k_interp_deriv, and the COPIES) and in
+// tests/test_gpu_pass_walk_lit.py (every other caller, and k_shadow and k_shadow_grad).
 // COPIES, each naming this definition — a fix to the walk goes into them too: k_gbuffer, k_motion, k_pos_grad, aa_body, k_tex,
 // k_tex_grad, k_tex_mip, k_tex_mip_grad (with tex_quad and mip_quad).  Moved onto these helpers they computed the same words
 // (the whole suite passed) but ran slower than their inline text on an MI355X at 256 frames of 1024²: k_gbuffer +4 %, k_motion +6 %,
