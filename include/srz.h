@@ -80,6 +80,8 @@ extern "C" {
  *      srz_cube_prefilter_grad / srz_cube_prefilter_work_bytes, SRZ_PREFILTER_COSINE, SRZ_PREFILTER_GGX
  *      (additive, same version) image-based lighting over a visibility buffer, with gradients srz_frameset_reflect /
  *      srz_frameset_reflect_grad / srz_brdf_table / srz_frameset_ibl / srz_frameset_ibl_grad, SRZ_BRDF_TABLE_MAX
+ *      (additive, same version) the environment behind a visibility buffer, by view ray, with gradients srz_frameset_background /
+ *      srz_frameset_background_work_bytes / srz_frameset_background_grad, SRZ_BG_NOBODY, SRZ_BG_ALL
  */
 #define SRZ_ABI_VERSION 7
 
@@ -1373,6 +1375,55 @@ int srz_frameset_ibl(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const vo
 int srz_frameset_ibl_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_base, const void *d_mat, const void *d_nv,
                           const void *d_irr, const void *d_spec, const float *d_tab, uint32_t n, const void *d_gout, void *d_gbase,
                           void *d_gmat, void *d_gnv, void *d_girr, void *d_gspec, float *d_gtab, uint32_t flags, void *stream);
+/* THE ENVIRONMENT BEHIND A VISIBILITY BUFFER, BY VIEW RAY, and its gradients: the COMPLEMENT of every pass above.  They write the
+ * pixels somebody owns; this one writes the pixels nobody owns (or, on request, all of them): it forms the pixel's view ray from a small
+ * device block, looks that ray up in a caller cube by srz_frameset_texture_cube's rule, seams included, and its backward goes to the
+ * cube's texels and to the ray block — so an environment can be fitted to the pixels around an object, srz_frameset_antialias has a
+ * background to blend an outline with, and the camera's rotation and intrinsics are learnable from the backdrop.
+ * d_tex, d_gtex, n, n_ch, tex_frames, d_out, d_gout: exactly srz_frameset_texture_cube's — shapes, limits, alignment, band sharding,
+ * stream semantics, asynchrony.  d_ray and d_gray: [ray_frames][9] float32 in device memory, 4-byte aligned; ray_frames is 1 (every
+ * frame shares the one block) or the set's frame count; a row is r0[3] rx[3] ry[3].  d_vis: a visibility buffer of THIS set on this
+ * ctx's shard.
+ * `where`: SRZ_BG_NOBODY — the pass's pixels are those nobody owns: id 0, the bare class bit, or an index outside the frame's
+ * triangles —, or SRZ_BG_ALL — every pixel of the frame is the pass's; d_vis may be NULL and is not read: an environment preview, and
+ * the layer behind the last peel of a composite.
+ * OWNED PIXELS (SRZ_BG_NOBODY) are what nobody's pixels are to the other passes: their words of d_out are 0 with SRZ_FUSED_CLEAR
+ * (frame flags | `flags`), otherwise LEFT UNTOUCHED — a caller can pass its shaded buffer and have the holes filled in place.  The
+ * words of d_gout there are never read.
+ * THE RULE, all of it float32, nothing fused except where fmaf is written, the divisions the IEEE division, always the exact
+ * arithmetic (SRZ_OPT_APPROX_SHADE has no effect).  A pixel's sample point is its INTEGER CORNER (x, y), as in srz_frameset_antialias
+ * and srz_frameset_motion; y is the frame's row, not the shard-local one:
+ *   d_c = fmaf((float)y, ry_c, fmaf((float)x, rx_c, r0_c))                for c = x, y, z
+ * and from d on the forward is srz_frameset_texture_cube's rule, word for word: unsampled (a component not finite, or the zero
+ * vector), the major axis, s and t, the seams, the three fmafs.  An unsampled pixel of the pass writes zeros and contributes nothing.
+ * BACKWARD: at least one of d_gtex and d_gray is non-null.
+ *   d_gtex (d_tex may be null when only d_gtex is asked for): srz_frameset_texture_cube_grad's adds at the resolved texels, the same
+ *   contract — float atomics, combined per tile and distinct texel first, the order unspecified, NOT BIT-REPRODUCIBLE, within
+ *   n 2^-24 / (1 - n 2^-24) * sum |term| with n contributing adds, exact at n = 1; ordinary (coarse-grained) device memory.
+ *   d_gray (needs d_tex, and d_work of at least srz_frameset_background_work_bytes bytes, 4-byte aligned, scratch: what it holds
+ *   afterwards is unspecified) is WRITTEN, not added into.  Per sampled pixel gdir is formed exactly as srz_frameset_texture_cube_grad
+ *   forms it; the nine terms of the pixel are gdir_c (r0), (float)x * gdir_c (rx), (float)y * gdir_c (ry); entry k of a frame's row
+ *   is the sum of the pixels' terms in srz_frameset_light_grad's FIXED tree, word for word: a lane's up to four pixels left to right,
+ *   from +0; the xor butterfly over the 64 lanes, o = 32, 16, 8, 4, 2, 1; the four waves as ((w0 + w1) + w2) + w3; a frame's tiles in
+ *   tile order, from +0; and with ray_frames == 1 the frames' rows in frame order, from +0.  So d_gray is BIT-REPRODUCIBLE for a given
+ *   shard layout, with one sampled pixel in all it is that pixel's term (a term of -0 comes out +0), and against the exact sum it
+ *   carries that section's bound.  Ranks each write the sums of their own bands.
+ * SUBNORMALS, non-finite texels and gradients: as srz_frameset_texture_cube.  No value of the block or of a texel makes a pass read
+ * or write outside its buffers.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set, d_ray, d_tex (forward; backward with d_gray),
+ * d_out, d_gout, d_vis with SRZ_BG_NOBODY, or both of d_gtex and d_gray; n == 0 or above SRZ_TEX_MAX_SIZE; n_ch == 0 or above
+ * SRZ_ATTR_MAX_CH; ray_frames or tex_frames not 1 or the frame count; `where` above 1; a short out_bytes, or work_bytes with d_gray;
+ * a misaligned pointer; any bit of `flags` but SRZ_FUSED_CLEAR; an output (d_work with d_gray counts as one) that overlaps an input
+ * or another output; d_gray without d_work or d_tex. */
+#define SRZ_BG_NOBODY 0u
+#define SRZ_BG_ALL 1u
+int srz_frameset_background(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_ray, uint32_t ray_frames, const float *d_tex,
+                            uint32_t n, uint32_t n_ch, uint32_t tex_frames, uint32_t where, void *d_out, size_t out_bytes, uint32_t flags,
+                            void *stream);
+size_t srz_frameset_background_work_bytes(srz_ctx *ctx, srz_frameset *fs);
+int srz_frameset_background_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_ray, uint32_t ray_frames,
+                                 const void *d_gout, const float *d_tex, uint32_t n, uint32_t n_ch, uint32_t tex_frames, uint32_t where,
+                                 float *d_gtex, float *d_gray, void *d_work, size_t work_bytes, uint32_t flags, void *stream);
 /* PERSPECTIVE-CORRECT BARYCENTRICS of a visibility buffer, their gradients, and the attribute derivatives under them.  A visibility
  * buffer's alpha, beta are LINEAR IN SCREEN SPACE, the reference's rule and the default of every pass above.  Under a vertex stage
  * that divides by a real w they name the wrong point of the triangle.  With q_k = 1 / w_k the reciprocal clip w of the owner's

@@ -2169,6 +2169,94 @@ int srz_frameset_texture_cube_grad(srz_ctx *ctx, srz_frameset *fs, const void *d
   return end_pass(ctx);
 }
 
+namespace {
+// what srz_frameset_background and _background_grad check alike behind their null pointers (check_cube, then the block and `where`);
+// the cube's bytes in *tex_bytes, the block's in *ray_bytes
+int check_background(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, uint32_t ray_frames, uint32_t n, uint32_t n_ch,
+                     uint32_t tex_frames, uint32_t where, uint32_t flags, size_t *tex_bytes, size_t *ray_bytes) {
+  if (int rc = check_cube(ctx, fs, fn, n, n_ch, tex_frames, flags, tex_bytes)) return rc;
+  if (ray_frames != 1u && ray_frames != (uint32_t)fs->n_frames)
+    return fail(ctx, SRZ_E_INVALID, fn + ": ray_frames must be 1 or the set's frame count");
+  if (where > SRZ_BG_ALL) return fail(ctx, SRZ_E_INVALID, fn + ": where must be SRZ_BG_NOBODY or SRZ_BG_ALL");
+  *ray_bytes = (size_t)ray_frames * 9u * sizeof(float);
+  return SRZ_OK;
+}
+BgArgs background_args(const srz_frameset *fs, const void *d_vis, const float *d_ray, uint32_t ray_frames, const float *d_tex, uint32_t n,
+                       uint32_t n_ch, uint32_t tex_frames, uint32_t where, void *d_out, uint32_t flags) {
+  BgArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  a.ray = d_ray, a.tex = d_tex;
+  a.vis_stride = 4ull * plane, a.frame_stride = n_ch * plane, a.gout_stride = n_ch * plane;
+  a.tex_frame_stride = tex_frames == 1u ? 0ull : 6ull * n * n * n_ch;
+  a.ray_stride = ray_frames == 1u ? 0ull : 9ull;
+  a.n = n, a.n_ch = n_ch, a.where = where;
+  a.flags_or = flags;
+  return a;
+}
+} // namespace
+
+int srz_frameset_background(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_ray, uint32_t ray_frames, const float *d_tex,
+                            uint32_t n, uint32_t n_ch, uint32_t tex_frames, uint32_t where, void *d_out, size_t out_bytes, uint32_t flags,
+                            void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_background");
+  if (where == SRZ_BG_ALL) d_vis = nullptr; // (not read: it may be anything)
+  if (!fs || (!d_vis && where == SRZ_BG_NOBODY) || !d_ray || !d_tex || !d_out)
+    return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!fs ? "frameset" : !d_ray ? "d_ray" : !d_tex ? "d_tex" : !d_out ? "d_out" : "d_vis"));
+  size_t tex_bytes = 0, ray_bytes = 0;
+  if (int rc = check_background(ctx, fs, fn, ray_frames, n, n_ch, tex_frames, where, flags, &tex_bytes, &ray_bytes)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, n_ch), vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": out_bytes is too small for d_out");
+  if (!aligned<16>({d_vis, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_out) must be 16-byte aligned");
+  if (!aligned<4>({d_ray, d_tex})) return fail(ctx, SRZ_E_INVALID, fn + ": d_ray and d_tex must be 4-byte aligned");
+  if (int rc = check_overlaps(ctx, fn + " (d_out against d_vis, d_ray, d_tex)", {{d_out, need}},
+                              {{d_vis, vis_bytes}, {d_ray, ray_bytes}, {d_tex, tex_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_texture_cube: caller data only)
+  launch_background(background_args(fs, d_vis, d_ray, ray_frames, d_tex, n, n_ch, tex_frames, where, d_out, flags), s);
+  return end_pass(ctx);
+}
+
+size_t srz_frameset_background_work_bytes(srz_ctx *ctx, srz_frameset *fs) {
+  if (!ctx || !fs) return 0;
+  // [frame][tile][9] partial sums, and [frame][9] rows for the fold of a shared ray block
+  return (size_t)fs->n_frames * ((size_t)fs->n_local_bands * fs->tiles_x + 1u) * 9u * sizeof(float);
+}
+
+int srz_frameset_background_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_ray, uint32_t ray_frames,
+                                 const void *d_gout, const float *d_tex, uint32_t n, uint32_t n_ch, uint32_t tex_frames, uint32_t where,
+                                 float *d_gtex, float *d_gray, void *d_work, size_t work_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_background_grad");
+  if (where == SRZ_BG_ALL) d_vis = nullptr; // (not read: it may be anything)
+  if (!fs || (!d_vis && where == SRZ_BG_NOBODY) || !d_ray || !d_gout)
+    return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!fs ? "frameset" : !d_ray ? "d_ray" : !d_gout ? "d_gout" : "d_vis"));
+  if (!d_gtex && !d_gray) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gtex nor d_gray is asked for");
+  if (d_gray && !d_tex) return fail(ctx, SRZ_E_INVALID, fn + ": d_gray needs d_tex");
+  if (d_gray && !d_work) return fail(ctx, SRZ_E_INVALID, fn + ": d_gray needs d_work");
+  size_t tex_bytes = 0, ray_bytes = 0;
+  if (int rc = check_background(ctx, fs, fn, ray_frames, n, n_ch, tex_frames, where, flags, &tex_bytes, &ray_bytes)) return rc;
+  const size_t gout_bytes = srz_frameset_interpolate_bytes(ctx, fs, n_ch), vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  const size_t need_work = d_gray ? srz_frameset_background_work_bytes(ctx, fs) : 0;
+  if (work_bytes < need_work) return fail(ctx, SRZ_E_INVALID, fn + ": work_bytes is below srz_frameset_background_work_bytes");
+  if (!aligned<16>({d_vis, d_gout})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_gout) must be 16-byte aligned");
+  if (!aligned<4>({d_ray, d_tex, d_gtex, d_gray, d_gray ? d_work : nullptr}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": d_ray, d_tex, d_gtex, d_gray and d_work must be 4-byte aligned");
+  if (int rc = check_overlaps(ctx, fn + " (d_gtex, d_gray, d_work against d_vis, d_ray, d_gout, d_tex)",
+                              {{d_gtex, tex_bytes}, {d_gray, ray_bytes}, {d_gray ? d_work : nullptr, need_work}},
+                              {{d_vis, vis_bytes}, {d_ray, ray_bytes}, {d_gout, gout_bytes}, {d_tex, tex_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_texture_cube: caller data only)
+  BgArgs a = background_args(fs, d_vis, d_ray, ray_frames, d_tex, n, n_ch, tex_frames, where, nullptr, flags);
+  a.gout = (const float *)d_gout, a.gtex = d_gtex;
+  a.work = d_gray ? (float *)d_work : nullptr;
+  launch_background_grad(a, d_gray, s);
+  return end_pass(ctx);
+}
+
 int srz_frameset_shadow(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_sc, const float *d_map, uint32_t map_w,
                         uint32_t map_h, uint32_t map_frames, float bias, float width, void *d_out, size_t out_bytes, uint32_t flags,
                         void *stream) {

@@ -496,6 +496,32 @@ struct LightArgs {
 };
 void launch_light(const LightArgs &a, hipStream_t s);
 void launch_light_grad(const LightArgs &a, float *gpar, hipStream_t s);
+// srz_frameset_background / _background_grad: the environment behind a visibility buffer, looked up in a cube (CubeArgs' tex, gtex,
+// n, n_ch, out, gout) by the pixel's view ray r0 + x rx + y ry from the ray block ray [ray frames][9]: r0[3] rx[3] ry[3].  where:
+// SRZ_BG_NOBODY (the pixels nobody owns) or SRZ_BG_ALL (every pixel; vis may be null and is not read).  `out` is the forward's
+// [frame][n_ch][local_rows][width], null in the backward.  work: the backward's [frame][tile][9] partial sums of the block's
+// gradient, and behind them [frame][9] rows for the fold when every frame shares one block (null: gtex only)
+struct BgArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *ray;
+  const float *tex;          // (backward: may be null when gray is)
+  float *out;
+  const float *gout;         // backward: [frame][n_ch][local_rows][width]
+  float *gtex;               // backward: tex's shape, added into (may be null)
+  float *work;
+  uint64_t vis_stride;       // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride;     // floats per frame in out
+  uint64_t gout_stride;      // floats per frame in gout = n_ch * local_rows * width
+  uint64_t tex_frame_stride; // floats per frame in tex / gtex = 6 * n * n * n_ch; 0: one cube for every frame
+  uint64_t ray_stride;       // floats per frame in ray = 9; 0: one block for every frame
+  uint32_t n, n_ch, where;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_background(const BgArgs &a, hipStream_t s);
+void launch_background_grad(const BgArgs &a, float *gray, hipStream_t s);
 // srz_frameset_microfacet / _microfacet_grad: Cook-Torrance (GGX, Schlick-Smith, Schlick Fresnel; metallic-roughness) under point
 // lights for caller data.  nrm, pos, base (may be null: ones), out, gout and the backward's gnrm, gpos, gbase (each may be null) are
 // [frame][3][local_rows][width]; mat and gmat (may be null) [frame][2][local_rows][width]: roughness, metallic; par is

@@ -5753,6 +5753,253 @@ __global__ __launch_bounds__(64) void k_light_fold(const float *src, float *dst,
 }
 
 // ================================================================================================================
+// k_background — THE ENVIRONMENT BEHIND A VISIBILITY BUFFER, BY VIEW RAY (srz_frameset_background, include/srz.h states the rule):
+// k_cube's body with three differences.  The direction is COMPUTED, not loaded: d = r0 + x rx + y ry at the pixel's integer corner
+// (x, y), two fmafs per component, from the frame's nine ray words — wave-uniform, read through the constant address space: scalar
+// loads, as k_light reads its parameter frame.  The pixel mask is INVERTED: the pass's pixels are those quad_ids calls nobody
+// (SRZ_BG_NOBODY), or every pixel of the frame (SRZ_BG_ALL: the ids are not loaded, vis may be null).  And the owned pixels are the
+// ones that keep their words: zeros with the fused clear, untouched without it — quad_store_owned with the pass's pixels as its
+// mask.  A thread none of whose pixels is the pass's, without the fused clear, does nothing after its id load.  From the direction
+// on everything is k_cube's: cube_tap, the channel loop, ATTR_CHUNK channels at a time.  No LDS, no barrier.
+// ================================================================================================================
+// what k_background and k_background_grad do alike in front of their channel loops: the pass's pixels of the quad, their directions
+// and the taps of the sampled ones -> `px` and `smp`, one bit per pixel
+__device__ __forceinline__ void bg_quad(const BgArgs &a, const PassTile &t, const SRZ_CAS float *ray, CubeTap (&tap)[4], float (&gx)[4],
+                                        uint32_t &px, uint32_t &smp) {
+  px = smp = 0u;
+  uint32_t in = 0u;
+  if (t.inside) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (t.x4 + k <= t.rc.tx1) in |= 1u << k;
+  }
+  if (a.where == SRZ_BG_ALL) {
+    px = in;
+  } else {
+    uint32_t id[4];
+    px = in & ~quad_ids(t, a.vis + (size_t)t.f * a.vis_stride + t.poff, id);
+  }
+  if (px == 0u) return;
+  const float r0[3] = {ray[0], ray[1], ray[2]}, rx[3] = {ray[3], ray[4], ray[5]}, ry[3] = {ray[6], ray[7], ray[8]};
+  const float fy = (float)t.y;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    gx[k] = (float)(t.x4 + k);
+    if (!(px & (1u << k))) continue;
+    const float dx = fmaf_(fy, ry[0], fmaf_(gx[k], rx[0], r0[0])), dy = fmaf_(fy, ry[1], fmaf_(gx[k], rx[1], r0[1]));
+    const float dz = fmaf_(fy, ry[2], fmaf_(gx[k], rx[2], r0[2]));
+    if (cube_tap(dx, dy, dz, a.n, tap[k])) smp |= 1u << k;
+  }
+}
+__global__ __launch_bounds__(256) void k_background(BgArgs a) {
+  const uint32_t C = a.n_ch;
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const TileRect &rc = t.rc;
+    const bool fused = t.fused(a.flags_or);
+    // ---- 1. the pass's pixels, their directions, the taps
+    CubeTap tap[4] = {};
+    float gx[4] = {0.f, 0.f, 0.f, 0.f};
+    uint32_t px, smp;
+    bg_quad(a, t, as_const(a.ray) + (size_t)t.f * a.ray_stride, tap, gx, px, smp);
+    if (px == 0u && !fused) return;
+    const SRZ_CAS float *tex = as_const(a.tex) + (size_t)t.f * a.tex_frame_stride;
+    // ---- 2. the channels, ATTR_CHUNK at a time (k_cube's loop)
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 q[ATTR_CHUNK];
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) q[i] = make_float4(0.f, 0.f, 0.f, 0.f); // an owner under the fused clear, and a pixel that is not sampled: zeros
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(smp & (1u << k))) continue;
+        const SRZ_CAS float *p00 = tex + (size_t)tap[k].i00 * C + c0, *p01 = tex + (size_t)tap[k].i01 * C + c0;
+        const SRZ_CAS float *p10 = tex + (size_t)tap[k].i10 * C + c0, *p11 = tex + (size_t)tap[k].i11 * C + c0;
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+          if (i < nc) {
+            const float t00 = p00[i], t01 = p01[i], t10 = p10[i], t11 = p11[i];
+            const float top = fmaf_(tap[k].tx, t01 - t00, t00), bot = fmaf_(tap[k].tx, t11 - t10, t10);
+            quad_at(q[i], k) = fmaf_(tap[k].ty, bot - top, top);
+          }
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+        if (i >= nc) break;
+        quad_store_owned(t.out + (size_t)(c0 + i) * rc.plane, t, {q[i]}, fused, px); // (the mask: the pass's pixels)
+      }
+    }
+  });
+}
+
+// ================================================================================================================
+// k_background_grad — THE BACKWARD OF k_background (srz_frameset_background_grad): k_cube_grad's table and flush for the cube's
+// gradient (the tile's open-addressed table of distinct texels in LDS, copies of cg_slot / cg_add, the dense flush with float
+// atomics, a corner without a slot adding straight to memory) together with k_light_grad's per-tile partials for the ray block's:
+// per sampled pixel gdir exactly as k_cube_grad forms it, its nine terms gdir_c, x gdir_c, y gdir_c summed in the FIXED tree — a
+// thread's four pixels left to right from +0, the xor butterfly, the four waves through LDS, a row of 9 per tile in work;
+// k_light_fold sums the tiles and, for a shared block, the frames.  pass_tiles / pass_tile as in k_light_grad (the tile's index is
+// the work row): every thread of the workgroup reaches every shuffle and barrier, one outside the frame samples nothing.  WANT_RAY:
+// a tile without a sampled pixel (one barrier tells) writes +0 partials and skips the rest.  The build without WANT_RAY has no
+// partials, no shuffle and no barrier beyond the table's.
+// ================================================================================================================
+// (bg_slot and bg_add are COPIES of cg_slot and cg_add, as those are of tg_slot and tg_add: called from here as they are, the
+// shared helpers moved k_cube_grad's registers, 193 -> 243 VGPRs, as sharing has moved k_tex_grad's before; a fix goes into all of them)
+__device__ __forceinline__ uint32_t bg_slot(TexTable &tb, uint32_t idx) {
+  const uint32_t key = idx + 1u; // (idx < 6 * SRZ_TEX_MAX_SIZE^2 = 6 * 2^28)
+  uint32_t h = (key * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
+  for (uint32_t p = 0; p < TG_PROBES; ++p) {
+    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
+    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
+    if (old == 0u || old == key) return h;
+    h = (h + 1u) & (TG_SLOTS - 1u);
+  }
+  return TG_NONE;
+}
+__device__ __forceinline__ void bg_add(TexTable &tb, uint32_t slot, float *gtex, uint32_t idx, uint32_t C, uint32_t ch, uint32_t i, float v) {
+  if (slot != TG_NONE) lds_add(&tb.val[slot * ATTR_CHUNK + i], v);
+  else global_add(gtex + (size_t)idx * C + ch, v);
+}
+template <bool WANT_RAY> __global__ __launch_bounds__(256) void k_background_grad(BgArgs a) {
+  __shared__ TexTable tb;
+  __shared__ float s_part[WANT_RAY ? 4 : 1][WANT_RAY ? 9 : 1];
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  const uint32_t C = a.n_ch, tpf = a.n_local_bands * a.tiles_x;
+  const bool want_tex = a.gtex != nullptr;
+  if (want_tex) {
+    for (uint32_t i = tid; i < TG_SLOTS; i += 256) tb.key[i] = 0u;
+    for (uint32_t i = tid; i < TG_SLOTS * ATTR_CHUNK; i += 256) tb.val[i] = 0.0f;
+    if (tid == 0) tb.n_used = 0u;
+    __syncthreads();
+  }
+  pass_tiles(a, [&](uint32_t f, uint32_t ti) {
+    const PassTile t = pass_tile(a, f, ti);
+    const TileRect &rc = t.rc;
+    const float *gg = a.gout + (size_t)f * a.gout_stride + t.poff;
+    // ---- 1. the pass's pixels, their directions, the taps
+    CubeTap tap[4] = {};
+    float gx[4] = {0.f, 0.f, 0.f, 0.f};
+    uint32_t px, smp;
+    bg_quad(a, t, as_const(a.ray) + (size_t)f * a.ray_stride, tap, gx, px, smp);
+    if (WANT_RAY) {
+      // a tile without a sampled pixel (every tile inside the object): its partials are the empty sums, +0, what the tree below gives
+      // too, without the shuffles; it adds nothing to the cube
+      if (!__syncthreads_or(smp != 0u)) {
+        if (tid < 9u) a.work[((size_t)f * tpf + ti) * 9u + tid] = 0.0f;
+        return;
+      }
+    }
+    const SRZ_CAS float *tex = as_const(a.tex) + (size_t)f * a.tex_frame_stride;
+    float *gtex = a.gtex + (size_t)f * a.tex_frame_stride;
+    // ---- 2. the slots of the sampled pixels' corners (two corners on one texel: one slot, both add)
+    uint32_t slot[4][4] = {};
+    if (want_tex) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (smp & (1u << k))
+          slot[k][0] = bg_slot(tb, tap[k].i00), slot[k][1] = bg_slot(tb, tap[k].i01), slot[k][2] = bg_slot(tb, tap[k].i10),
+          slot[k][3] = bg_slot(tb, tap[k].i11);
+    }
+    float au[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f};
+    uint32_t n_used = 0u;
+    // ---- 3. the channels, ATTR_CHUNK at a time (k_cube_grad's loop)
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 g[ATTR_CHUNK]; // gout of the chunk's channels; words of pixels that are not sampled are loaded with their quad at most, never used
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (smp != 0u) {
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+          if (i >= nc) break;
+          const float *p = gg + (size_t)(c0 + i) * rc.plane;
+          if (t.whole) {
+            g[i] = *reinterpret_cast<const float4 *>(p);
+          } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (smp & (1u << k)) quad_at(g[i], k) = p[k];
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(smp & (1u << k))) continue;
+        if (WANT_RAY) {
+          const SRZ_CAS float *p00 = tex + (size_t)tap[k].i00 * C + c0, *p01 = tex + (size_t)tap[k].i01 * C + c0;
+          const SRZ_CAS float *p10 = tex + (size_t)tap[k].i10 * C + c0, *p11 = tex + (size_t)tap[k].i11 * C + c0;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float gi = quad_at(g[i], k), t00 = p00[i], t01 = p01[i], t10 = p10[i], t11 = p11[i];
+              const float top = fmaf_(tap[k].tx, t01 - t00, t00), bot = fmaf_(tap[k].tx, t11 - t10, t10);
+              au[k] = fmaf_(gi, fmaf_(tap[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au[k]);
+              av[k] = fmaf_(gi, bot - top, av[k]);
+            }
+        }
+        if (want_tex) {
+          const float tx_ = tap[k].tx, ty_ = tap[k].ty;
+          const float w00 = (1.0f - tx_) * (1.0f - ty_), w01 = tx_ * (1.0f - ty_), w10 = (1.0f - tx_) * ty_, w11 = tx_ * ty_;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float gi = quad_at(g[i], k);
+              bg_add(tb, slot[k][0], gtex, tap[k].i00, C, c0 + i, i, w00 * gi);
+              bg_add(tb, slot[k][1], gtex, tap[k].i01, C, c0 + i, i, w01 * gi);
+              bg_add(tb, slot[k][2], gtex, tap[k].i10, C, c0 + i, i, w10 * gi);
+              bg_add(tb, slot[k][3], gtex, tap[k].i11, C, c0 + i, i, w11 * gi);
+            }
+        }
+      }
+      if (want_tex) {
+        // ---- 4. the table's values of this chunk into memory: lanes in channel order within a texel
+        __syncthreads();
+        n_used = tb.n_used;
+        for (uint32_t i = tid; i < n_used * ATTR_CHUNK; i += 256) {
+          const uint32_t s = tb.used[i / ATTR_CHUNK], e = i % ATTR_CHUNK;
+          const float v = tb.val[s * ATTR_CHUNK + e];
+          tb.val[s * ATTR_CHUNK + e] = 0.0f;
+          if (e < nc) global_add(gtex + (size_t)(tb.key[s] - 1u) * C + c0 + e, v);
+        }
+        __syncthreads();
+      }
+    }
+    if (want_tex) { // the tile's keys go; every thread has read n_used before the chunk's last barrier
+      for (uint32_t i = tid; i < n_used; i += 256) tb.key[tb.used[i]] = 0u;
+      if (tid == 0) tb.n_used = 0u;
+      __syncthreads();
+    }
+    // ---- 5. the ray block's nine partial sums of the tile
+    if (WANT_RAY) {
+      float tr[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; // this lane's sums of r0[3], rx[3], ry[3]
+      const float half_n = 0.5f * (float)a.n, fy = (float)t.y;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (smp & (1u << k)) {
+          const float gs = au[k] * half_n, gt = av[k] * half_n, inv = tap[k].inv;
+          const float g_sc = gs * inv, g_tc = gt * inv, g_ma = -(fmaf_(gs, tap[k].s, gt * tap[k].t) * inv);
+          const uint32_t m = tap[k].major & 3u;
+          const bool pos = (tap[k].major & 4u) != 0u;
+          const float g_m = pos ? g_ma : -g_ma;
+          // su, sv of the face, undone (k_cube_grad): +X (-z, -y)  -X (z, -y)  +Y (x, z)  -Y (x, -z)  +Z (x, -y)  -Z (-x, -y)
+          const float gd[3] = {m == 0u ? g_m : m == 1u ? g_sc : (pos ? g_sc : -g_sc), m == 1u ? g_m : -g_tc,
+                               m == 0u ? (pos ? -g_sc : g_sc) : m == 1u ? (pos ? g_tc : -g_tc) : g_m};
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            tr[c] = tr[c] + gd[c], tr[3 + c] = tr[3 + c] + gx[k] * gd[c], tr[6 + c] = tr[6 + c] + fy * gd[c];
+        }
+#pragma unroll
+      for (int j = 0; j < 9; ++j) {
+        const float v = light_wave_sum(tr[j]);
+        if (lane == 0u) s_part[wave][j] = v;
+      }
+      __syncthreads();
+      if (tid < 9u) a.work[((size_t)f * tpf + ti) * 9u + tid] = ((s_part[0][tid] + s_part[1][tid]) + s_part[2][tid]) + s_part[3][tid];
+      __syncthreads(); // s_part is the next tile's too
+    }
+  });
+}
+
+// ================================================================================================================
 // k_microfacet — COOK-TORRANCE UNDER POINT LIGHTS OVER A VISIBILITY BUFFER, FOR CALLER DATA (srz_frameset_microfacet, include/srz.h
 // states the rule): the normal, position and base colour planes, a two-plane material (roughness, metallic) and a parameter frame
 // (eye, amb, then the lights) -> three colour planes.  GGX distribution, separable Schlick-Smith visibility, Schlick Fresnel; no
@@ -8806,6 +9053,17 @@ void launch_light_grad(const LightArgs &a, float *gpar, hipStream_t s) {
   float *rows = shared ? a.work + (size_t)a.n_frames * tpf * K : gpar;
   if (a.n_frames != 0u) hipLaunchKernelGGL(k_light_fold, dim3(a.n_frames), dim3(64), 0, s, (const float *)a.work, rows, tpf, K);
   if (shared) hipLaunchKernelGGL(k_light_fold, dim3(1), dim3(64), 0, s, (const float *)rows, gpar, a.n_frames, K);
+}
+// (launch_light_grad's two steps over rows of 9, k_light_fold unchanged; ray_stride == 0: one ray block for every frame)
+void launch_background(const BgArgs &a, hipStream_t s) { launch_pass<k_background>(a, s); }
+void launch_background_grad(const BgArgs &a, float *gray, hipStream_t s) {
+  if (!gray) return launch_pass<k_background_grad<false>>(a, s);
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, K = 9u;
+  const bool shared = a.ray_stride == 0u;
+  launch_pass<k_background_grad<true>>(a, s);
+  float *rows = shared ? a.work + (size_t)a.n_frames * tpf * K : gray;
+  if (a.n_frames != 0u) hipLaunchKernelGGL(k_light_fold, dim3(a.n_frames), dim3(64), 0, s, (const float *)a.work, rows, tpf, K);
+  if (shared) hipLaunchKernelGGL(k_light_fold, dim3(1), dim3(64), 0, s, (const float *)rows, gray, a.n_frames, K);
 }
 void launch_microfacet(const MicrofacetArgs &a, hipStream_t s) { launch_pass<k_microfacet>(a, s); }
 // (launch_light_grad's two steps, k_light_fold unchanged: K = SRZ_MICROFACET_PAR(n_lights) <= 54 of its 64 threads)

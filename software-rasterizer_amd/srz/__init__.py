@@ -32,6 +32,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_texture_mip_levels", "srz_texture_mip_bytes", "srz_texture_mip_build", "srz_texture_mip_fold",
            "srz_frameset_interpolate_deriv", "srz_frameset_texture_mip", "srz_frameset_texture_mip_grad",
            "srz_frameset_texture_cube", "srz_frameset_texture_cube_grad",
+           "srz_frameset_background", "srz_frameset_background_work_bytes", "srz_frameset_background_grad",
            "srz_cube_mip_levels", "srz_cube_mip_bytes", "srz_cube_mip_build", "srz_cube_mip_fold",
            "srz_frameset_texture_cube_mip", "srz_frameset_texture_cube_mip_grad", "srz_frameset_cube_level",
            "srz_cube_prefilter_work_bytes", "srz_cube_prefilter", "srz_cube_prefilter_grad",
@@ -121,6 +122,10 @@ def lib():
         L.srz_frameset_texture_mip_grad.argtypes = abi.TEXTURE_MIP_GRAD_ARGTYPES
         L.srz_frameset_texture_cube.argtypes = abi.TEXTURE_CUBE_ARGTYPES
         L.srz_frameset_texture_cube_grad.argtypes = abi.TEXTURE_CUBE_GRAD_ARGTYPES
+        L.srz_frameset_background.argtypes = abi.BACKGROUND_ARGTYPES
+        L.srz_frameset_background_work_bytes.argtypes = abi.BACKGROUND_WORK_BYTES_ARGTYPES
+        L.srz_frameset_background_work_bytes.restype = C.c_size_t
+        L.srz_frameset_background_grad.argtypes = abi.BACKGROUND_GRAD_ARGTYPES
         L.srz_cube_mip_levels.argtypes = abi.CUBE_MIP_LEVELS_ARGTYPES
         L.srz_cube_mip_levels.restype = C.c_uint32
         L.srz_cube_mip_bytes.argtypes = abi.CUBE_MIP_BYTES_ARGTYPES
@@ -466,6 +471,32 @@ class FrameSet:
                                                              C.c_void_p(d_gout_ptr), C.c_void_p(d_tex_ptr or None), n, n_ch, tex_frames,
                                                              C.c_void_p(d_gtex_ptr or None), C.c_void_p(d_gdir_ptr or None), flags,
                                                              _stream(stream)))
+
+    def background(self, d_vis_ptr, d_ray_ptr, ray_frames, d_tex_ptr, n, n_ch, tex_frames, where, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR,
+                   stream=None):
+        """the environment behind a visibility buffer of this set: at the pixels nobody owns (where = abi.BG_NOBODY) or at every pixel
+        (abi.BG_ALL: d_vis_ptr may be None / 0 and is not read) the pixel's view ray r0 + x rx + y ry — the block d_ray
+        [ray_frames][9]: r0[3] rx[3] ry[3]; ray_frames: 1 or the frame count — looked up in texture_cube's cube by texture_cube's
+        rule → d_out [frame][n_ch][local_rows][width] (include/srz.h states the rule).  Owned pixels (BG_NOBODY) are zeros with
+        FUSED_CLEAR, else left untouched; a pixel of the pass whose ray is not finite or zero gets zeros.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_background(self.ctx.h, self.h, C.c_void_p(d_vis_ptr or None), C.c_void_p(d_ray_ptr), ray_frames,
+                                                      C.c_void_p(d_tex_ptr), n, n_ch, tex_frames, where, C.c_void_p(d_out_ptr), out_bytes, flags,
+                                                      _stream(stream)))
+
+    def background_work_bytes(self):
+        """bytes of the scratch buffer background_grad needs for d_gray"""
+        return int(lib().srz_frameset_background_work_bytes(self.ctx.h, self.h))
+
+    def background_grad(self, d_vis_ptr, d_ray_ptr, ray_frames, d_gout_ptr, d_tex_ptr, n, n_ch, tex_frames, where, d_gtex_ptr, d_gray_ptr,
+                        d_work_ptr, work_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """the backward of background: d_gout [frame][n_ch][local_rows][width] → ADDED into d_gtex (the cube's shape; the order of the
+        adds is unspecified: not bit-reproducible) and / or WRITTEN to d_gray [ray_frames][9] (the gradient of the ray block, summed
+        in a fixed tree: bit-reproducible; needs d_tex_ptr and d_work of background_work_bytes() bytes).  Either output pointer may be
+        None / 0, not both.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_background_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr or None), C.c_void_p(d_ray_ptr), ray_frames,
+                                                           C.c_void_p(d_gout_ptr), C.c_void_p(d_tex_ptr or None), n, n_ch, tex_frames, where,
+                                                           C.c_void_p(d_gtex_ptr or None), C.c_void_p(d_gray_ptr or None),
+                                                           C.c_void_p(d_work_ptr or None), work_bytes, flags, _stream(stream)))
 
     def texture_cube_mip(self, d_vis_ptr, d_dir_ptr, d_lam_ptr, d_tex_ptr, n, n_ch, tex_frames, d_mip_ptr, n_levels, d_out_ptr, out_bytes,
                          flags=abi.FUSED_CLEAR, stream=None):

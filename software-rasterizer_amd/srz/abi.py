@@ -52,6 +52,11 @@ TEXTURE_MIP_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32,
 # the prototypes of srz_frameset_texture_cube / _texture_cube_grad (argtypes; both return int), set by srz.lib()
 TEXTURE_CUBE_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
 TEXTURE_CUBE_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp]
+# the prototypes of srz_frameset_background / _background_work_bytes (returns size_t) / _background_grad (argtypes), set by srz.lib()
+BG_NOBODY, BG_ALL = 0, 1  # srz_frameset_background: `where` (SRZ_BG_NOBODY, SRZ_BG_ALL)
+BACKGROUND_ARGTYPES = [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
+BACKGROUND_WORK_BYTES_ARGTYPES = [_vp, _vp]
+BACKGROUND_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, C.c_size_t, _u32, _vp]
 # the prototypes of the cube pyramid's entry points srz_cube_mip_levels (returns uint32) / _bytes (size_t) / _build / _fold and of
 # srz_frameset_texture_cube_mip / _texture_cube_mip_grad / srz_frameset_cube_level (argtypes), set by srz.lib()
 CUBE_MIP_LEVELS_ARGTYPES = [_u32]

@@ -558,6 +558,101 @@ def texture_cube(fs, vis, cube, dirs, stream=None):
     return _TextureCube.apply(cube, dirs, fs, vis, stream)
 
 
+def view_rays(screen_from_world, front=1.0, dtype=torch.float32):
+    """the ray block of background from a camera, with differentiable torch ops: screen_from_world is the 4 x 4 matrix S a draw's
+    ndc_mvp has in front of its model matrix (screen <- NDC <- projection <- view), [4, 4] or [n_frames, 4, 4], mathematical layout
+    (S @ (P, 1) = (x w, y w, z w, w): a draw's column-major 16 floats reshaped [4, 4] and transposed) → [1, 9] or [n_frames, 9]
+    float32 on S's device, a row r0[3] rx[3] ry[3] with r0 + x rx + y ry a direction of the world points that project onto the
+    screen point (x, y).  With B the rows X, Y, W of S's first three columns, B (P - eye) = w (x, y, 1), so (rx, ry, r0) are the
+    columns of B^-1, times `front`: the sign of w in FRONT of the camera — +1 for the reference's camera (lookAtLH with
+    perspectiveLH_NO, srz.host.Scene and srz.scenes: w is the view-space depth), and for an OpenGL-style one (w = -z_view) too; -1
+    for a projection whose w is negative in front.  Inverted in float64 and rounded once to float32 (dtype: torch.float64 keeps the
+    binary64 block, for checks; background takes float32)."""
+    S = screen_from_world
+    if S.dim() not in (2, 3) or tuple(S.shape[-2:]) != (4, 4):
+        raise ValueError(f"view_rays: screen_from_world must be [4, 4] or [n_frames, 4, 4], got {tuple(S.shape)}")
+    if front not in (1, -1):
+        raise ValueError(f"view_rays: front must be +1 or -1, got {front}")
+    B = S.reshape(-1, 4, 4).to(torch.float64)[:, [0, 1, 3], :3]
+    # the inverse by cofactors (its columns are the cross products of B's rows over the determinant): plain differentiable ops
+    bx, by, bw = B[:, 0], B[:, 1], B[:, 2]
+    cx, cy, cw = torch.linalg.cross(by, bw), torch.linalg.cross(bw, bx), torch.linalg.cross(bx, by)
+    det = (bx * cx).sum(-1, keepdim=True)
+    rows = torch.cat([cw, cx, cy], dim=1) / (det * float(front))  # r0, rx, ry
+    return rows.to(dtype).contiguous()
+
+
+_BG_WHERE = {"nobody": abi.BG_NOBODY, "all": abi.BG_ALL}
+
+
+def _background_args(fs, vis, cube, rays, where):
+    """→ (cube, rays, tex_frames, n, n_ch, ray_frames, where word, vis pointer or None), checked and contiguous"""
+    if where not in _BG_WHERE:
+        raise ValueError(f"background: where must be 'nobody' or 'all', got {where!r}")
+    tex_frames, n, n_ch = _cube_dims(fs, cube)
+    if rays.dtype != torch.float32 or not rays.is_cuda or rays.dim() != 2 or rays.shape[1] != 9 or rays.shape[0] not in (1, fs.n_frames):
+        raise ValueError(f"background: rays must be a CUDA float32 tensor [1 or {fs.n_frames}, 9], got {tuple(rays.shape)} {rays.dtype}")
+    if vis is None and where != "all":
+        raise ValueError("background: vis may be None only with where='all'")
+    return cube.contiguous(), rays.contiguous(), tex_frames, n, n_ch, rays.shape[0], _BG_WHERE[where], None if vis is None else vis.data_ptr()
+
+
+def background_grad(fs, vis, cube, rays, gout, where="nobody", want_gtex=True, want_gray=True, stream=None):
+    """the backward of background(fs, vis, cube, rays, where) by one FrameSet.background_grad call: gout [n_frames, C, rows, W] →
+    (gtex, gray), each None when not wanted (not both): gtex has cube's shape — a sum of float atomics into zeros, not
+    bit-reproducible between runs; gray has rays' shape, summed in a fixed tree (bit-reproducible for a shard layout).  stream: a raw
+    stream handle, None = torch's current stream."""
+    if not want_gtex and not want_gray:
+        raise ValueError("background_grad: neither gtex nor gray is asked for")
+    cube, rays, tex_frames, n, n_ch, ray_frames, w, vis_ptr = _background_args(fs, vis, cube, rays, where)
+    gout = gout.contiguous()
+    if tuple(gout.shape) != tuple(fs.interpolate_shape(n_ch)) or gout.dtype != torch.float32:
+        raise ValueError(f"background_grad: gout must be float32 {fs.interpolate_shape(n_ch)}, got {tuple(gout.shape)} {gout.dtype}")
+    gtex = torch.zeros_like(cube) if want_gtex else None
+    gray = work = None
+    work_bytes = 0
+    if want_gray:
+        work_bytes = fs.background_work_bytes()
+        gray, work = torch.empty_like(rays), torch.empty(max(work_bytes // 4, 1), dtype=torch.float32, device=rays.device)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    fs.background_grad(vis_ptr, rays.data_ptr(), ray_frames, gout.data_ptr(), cube.data_ptr(), n, n_ch, tex_frames, w, ptr(gtex), ptr(gray),
+                       ptr(work), work_bytes, abi.FUSED_CLEAR, _stream_ptr(stream))
+    return gtex, gray
+
+
+class _Background(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cube, rays, fs, vis, where, stream):
+        cube, rays, tex_frames, n, n_ch, ray_frames, w, vis_ptr = _background_args(fs, vis, cube, rays, where)
+        out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=cube.device)
+        fs.background(vis_ptr, rays.data_ptr(), ray_frames, cube.data_ptr(), n, n_ch, tex_frames, w, out.data_ptr(), fs.interpolate_bytes(n_ch),
+                      abi.FUSED_CLEAR, _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.where, ctx.stream = fs, vis, where, stream
+        ctx.save_for_backward(cube, rays)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        cube, rays = ctx.saved_tensors
+        need_tex, need_ray = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gtex = gray = None
+        if need_tex or need_ray:  # one call, asking only for what is needed
+            gtex, gray = background_grad(ctx.fs, ctx.vis, cube, rays, gout, ctx.where, need_tex, need_ray, ctx.stream)
+        return gtex, gray, None, None, None, None
+
+
+def background(fs, vis, cube, rays, where="nobody", stream=None):
+    """the environment behind a visibility buffer `vis` of FrameSet `fs`, by view ray: cube is texture_cube's cube ([6, N, N, C] or
+    [n_frames, 6, N, N, C]), rays is view_rays' block [1, 9] or [n_frames, 9] → [n_frames, C, rows, W] float32: at the pixels nobody
+    owns (where="nobody") or at every pixel (where="all"; vis may be None) the cube looked up along the pixel's ray r0 + x rx + y ry
+    by texture_cube's rule, zeros at the owned pixels and where the ray is not finite or zero (FrameSet.background; include/srz.h
+    states the rule).  So antialias(fs, vis, shaded + background(fs, vis, env, view_rays(S)), pos) blends an outline with what is
+    behind it.  Differentiable with respect to cube (float atomics into a zeroed tensor: cube.grad is not bit-reproducible between
+    runs) and to rays (a fixed tree: bit-reproducible), and through view_rays to the camera.  Backward is one background_grad call
+    that asks only for the outputs some input needs.  stream: a raw stream handle, None = torch's current stream."""
+    return _Background.apply(cube, rays, fs, vis, where, stream)
+
+
 def _map_dims(fs, map):
     """map [H, W], [n_frames, H, W] or depth()'s [n_frames, 1, H, W] → (map_frames, H, W)"""
     if map.dtype != torch.float32 or map.dim() not in (2, 3, 4) or (map.dim() == 4 and map.shape[1] != 1):
