@@ -82,6 +82,8 @@ extern "C" {
  *      srz_frameset_reflect_grad / srz_brdf_table / srz_frameset_ibl / srz_frameset_ibl_grad, SRZ_BRDF_TABLE_MAX
  *      (additive, same version) the environment behind a visibility buffer, by view ray, with gradients srz_frameset_background /
  *      srz_frameset_background_work_bytes / srz_frameset_background_grad, SRZ_BG_NOBODY, SRZ_BG_ALL
+ *      (additive, same version) compositing depth layers front to back, with gradients srz_frameset_composite /
+ *      srz_frameset_composite_grad, srz_composite_layer, SRZ_COMPOSITE_MAX
  */
 #define SRZ_ABI_VERSION 7
 
@@ -1424,6 +1426,56 @@ size_t srz_frameset_background_work_bytes(srz_ctx *ctx, srz_frameset *fs);
 int srz_frameset_background_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const float *d_ray, uint32_t ray_frames,
                                  const void *d_gout, const float *d_tex, uint32_t n, uint32_t n_ch, uint32_t tex_frames, uint32_t where,
                                  float *d_gtex, float *d_gray, void *d_work, size_t work_bytes, uint32_t flags, void *stream);
+/* COMPOSITING DEPTH LAYERS FRONT TO BACK, and its gradients: the step that turns the shaded layers of a depth peel
+ * (srz_frameset_peel_visibility) into one image, in one pass over the tiles.  A call takes n_layers layers, 1 .. SRZ_COMPOSITE_MAX,
+ * NEAREST FIRST, in a HOST array of srz_composite_layer (read before the call returns).  A layer is: `vis`, a visibility buffer of
+ * THIS set on this ctx's shard, of which only the id plane is read; `color`, n_ch planes (1 .. SRZ_ATTR_MAX_CH) in
+ * srz_frameset_interpolate's output layout [frame][n_ch][local_rows][width]; and `alpha`, one plane [frame][1][local_rows][width],
+ * or, if `alpha` is NULL, the scalar `opacity` for every pixel of the layer.  d_bg (may be NULL): n_ch planes behind everything,
+ * srz_frameset_background's output for one.  want_through (0 or 1): the transmittance T is appended to the output as plane n_ch, so
+ * d_out and d_gout are [frame][n_ch + want_through][local_rows][width] and out_bytes covers srz_frameset_interpolate_bytes of that
+ * many planes.  Stream semantics, asynchrony, local_rows and band sharding: exactly srz_frameset_normal_map's.
+ * COVERAGE.  Layer k covers a pixel when its id word names an owner: id 0, the bare class bit and an index outside the frame's
+ * triangles are nobody, as in every pass above.  A layer that does not cover the pixel is SKIPPED: its colour and alpha words at that
+ * pixel never reach a result (they may be NaN).  THE LAYERS NEED NOT COME FROM ONE PEEL CHAIN: a nobody layer does not end the
+ * pixel, and the same buffer may be passed as two layers.
+ * THE RULE, all of it float32, nothing fused except where fmaf is written.  FORWARD, per pixel: T = 1, acc_c = +0; for each covering
+ * layer in order, with a its alpha (the plane's word, or opacity) and col_c its colour:
+ *   w = a * T;   acc_c = acc_c + col_c * w   for every channel c;   T = T * (1 - a)
+ * then, with d_bg, acc_c = acc_c + bg_c * T.  The output is acc_c, and T in plane n_ch if asked for.  THERE IS NO CLAMP OF a AND NO
+ * EARLY EXIT at T == 0: a covered layer behind an opaque one is still read, because the opaque layer's alpha gradient needs it.
+ * EVERY WORD OF d_out IN THE SHARD'S OWNED ROWS IS WRITTEN, whatever `flags` (as srz_frameset_peel_visibility): a pixel no layer
+ * covers is bg_c (or +0) with T = 1.  Padding rows of a shard keep what they held.
+ * BACKWARD.  g_c are d_gout's first n_ch planes, gT its plane n_ch, or 0 when want_through is 0.  T_k (the T layer k met) and
+ * w_k = a_k * T_k are recomputed as in the forward pass, T_n is the final T.  No division appears, so a = 1 is an ordinary value.
+ *   gbg_c = g_c * T_n
+ *   S = gT;   with d_bg: S = fmaf(g_c, bg_c, S) for c = 0, 1, .. in channel order
+ *   for the covering layers FROM LAST TO FIRST:
+ *     d = +0;   d = fmaf(g_c, col_c, d) for c = 0, 1, .. in channel order
+ *     gcol_c = g_c * w_k
+ *     galpha = T_k * (d - S)
+ *     S = fmaf(a, d, (1 - a) * S)
+ * d_gcolor and d_galpha are HOST arrays of n_layers device pointers (color's and alpha's shapes), or NULL: none of them; each entry
+ * may be NULL; d_gbg has d_bg's shape.  At least one output is asked for.  d_galpha[k] may be asked for even when layer k's alpha is
+ * the scalar: the scalar's gradient is the sum of that plane.  Every word of an asked-for plane in the owned rows is WRITTEN, +0 where
+ * the layer does not cover the pixel; per pixel, no atomics: BIT-REPRODUCIBLE.  Without any d_galpha the colour planes are not read.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set, layers, a layer's vis or color, d_out, d_gout;
+ * n_layers 0 or above SRZ_COMPOSITE_MAX; n_ch 0 or above SRZ_ATTR_MAX_CH; want_through above 1; a short out_bytes; a pointer that is
+ * not 16-byte aligned; any bit of `flags` but SRZ_FUSED_CLEAR (which changes nothing here); an output that overlaps an input or
+ * another output (inputs may alias each other); a gradient call with nothing asked for; d_gbg without d_bg. */
+#define SRZ_COMPOSITE_MAX 8
+typedef struct srz_composite_layer {
+  const void *vis;   /* device: the layer's visibility buffer */
+  const void *color; /* device: [frame][n_ch][local_rows][width] */
+  const void *alpha; /* device: [frame][1][local_rows][width], or NULL: `opacity` */
+  float opacity;
+  uint32_t _pad;
+} srz_composite_layer;
+int srz_frameset_composite(srz_ctx *ctx, srz_frameset *fs, const srz_composite_layer *layers, uint32_t n_layers, uint32_t n_ch,
+                           const void *d_bg, uint32_t want_through, void *d_out, size_t out_bytes, uint32_t flags, void *stream);
+int srz_frameset_composite_grad(srz_ctx *ctx, srz_frameset *fs, const srz_composite_layer *layers, uint32_t n_layers, uint32_t n_ch,
+                                const void *d_bg, uint32_t want_through, const void *d_gout, void *const *d_gcolor,
+                                void *const *d_galpha, void *d_gbg, uint32_t flags, void *stream);
 /* PERSPECTIVE-CORRECT BARYCENTRICS of a visibility buffer, their gradients, and the attribute derivatives under them.  A visibility
  * buffer's alpha, beta are LINEAR IN SCREEN SPACE, the reference's rule and the default of every pass above.  Under a vertex stage
  * that divides by a real w they name the wrong point of the triangle.  With q_k = 1 / w_k the reciprocal clip w of the owner's

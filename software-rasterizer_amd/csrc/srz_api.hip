@@ -2691,6 +2691,114 @@ int srz_frameset_normal_map_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_v
   return end_pass(ctx);
 }
 
+namespace {
+// check_overlaps for a number of buffers known at run time (the composite's layers): the same rule, the same messages
+int check_overlaps_n(srz_ctx *ctx, const std::string &fn, const std::vector<Range> &outs, const std::vector<Range> &ins) {
+  for (size_t o = 0; o < outs.size(); ++o) {
+    for (const Range &i : ins)
+      if (ranges_overlap(outs[o], i)) return fail(ctx, SRZ_E_INVALID, fn + ": an output overlaps an input");
+    for (size_t p = o + 1; p < outs.size(); ++p)
+      if (ranges_overlap(outs[o], outs[p])) return fail(ctx, SRZ_E_INVALID, fn + ": two outputs overlap");
+  }
+  return SRZ_OK;
+}
+// what srz_frameset_composite and _composite_grad check alike behind their null ctx, and the Args they share.  *ins: every input's
+// range, for the caller's overlap check
+int check_composite(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, const srz_composite_layer *layers, uint32_t n_layers,
+                    uint32_t n_ch, const void *d_bg, uint32_t want_through, uint32_t flags, std::vector<Range> *ins) {
+  if (!fs || !layers) return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!fs ? "frameset" : "layers"));
+  if (n_layers == 0u || n_layers > (uint32_t)SRZ_COMPOSITE_MAX) return fail(ctx, SRZ_E_INVALID, fn + ": n_layers must be 1 .. SRZ_COMPOSITE_MAX");
+  if (n_ch == 0u || n_ch > SRZ_ATTR_MAX_CH) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_ATTR_MAX_CH");
+  if (want_through > 1u) return fail(ctx, SRZ_E_INVALID, fn + ": want_through must be 0 or 1");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, const_cast<srz_frameset *>(fs));
+  const size_t col_bytes = srz_frameset_interpolate_bytes(ctx, const_cast<srz_frameset *>(fs), n_ch);
+  const size_t one_bytes = srz_frameset_interpolate_bytes(ctx, const_cast<srz_frameset *>(fs), 1u);
+  for (uint32_t k = 0; k < n_layers; ++k) {
+    const srz_composite_layer &l = layers[k];
+    if (!l.vis || !l.color) return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!l.vis ? "vis" : "color") + " in layer " + std::to_string(k));
+    if (!aligned<16>({l.vis, l.color, l.alpha}))
+      return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (every layer's vis, color, alpha) must be 16-byte aligned");
+    ins->push_back({l.vis, vis_bytes}), ins->push_back({l.color, col_bytes}), ins->push_back({l.alpha, one_bytes});
+  }
+  ins->push_back({d_bg, col_bytes});
+  return SRZ_OK;
+}
+CompositeArgs composite_args(const srz_frameset *fs, const srz_composite_layer *layers, uint32_t n_layers, uint32_t n_ch, const void *d_bg,
+                             uint32_t want_through, void *d_out, uint32_t flags) {
+  CompositeArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, layers[0].vis, d_out);
+  for (uint32_t k = 0; k < n_layers; ++k) {
+    a.lvis[k] = (const float *)layers[k].vis, a.col[k] = (const float *)layers[k].color, a.alpha[k] = (const float *)layers[k].alpha;
+    a.opacity[k] = layers[k].opacity;
+  }
+  a.bg = (const float *)d_bg;
+  a.vis_stride = 4ull * plane, a.frame_stride = (uint64_t)(n_ch + want_through) * plane, a.col_stride = (uint64_t)n_ch * plane;
+  a.n_layers = n_layers, a.n_ch = n_ch, a.through = want_through;
+  a.flags_or = flags;
+  return a;
+}
+} // namespace
+
+int srz_frameset_composite(srz_ctx *ctx, srz_frameset *fs, const srz_composite_layer *layers, uint32_t n_layers, uint32_t n_ch,
+                           const void *d_bg, uint32_t want_through, void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_composite");
+  std::vector<Range> ins;
+  if (int rc = check_composite(ctx, fs, fn, layers, n_layers, n_ch, d_bg, want_through, flags, &ins)) return rc;
+  if (!d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null d_out");
+  // (n_ch + 1 may be one above SRZ_ATTR_MAX_CH, where srz_frameset_interpolate_bytes answers 0: the bytes by planes of one)
+  const size_t need = (size_t)(n_ch + want_through) * srz_frameset_interpolate_bytes(ctx, fs, 1u);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": out_bytes is too small for d_out");
+  if (!aligned<16>({d_bg, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_bg, d_out) must be 16-byte aligned");
+  if (int rc = check_overlaps_n(ctx, fn + " (d_out against every layer's vis, color, alpha and d_bg)", std::vector<Range>{{d_out, need}}, ins))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_normal_map: caller data only)
+  launch_composite(composite_args(fs, layers, n_layers, n_ch, d_bg, want_through, d_out, flags), s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_composite_grad(srz_ctx *ctx, srz_frameset *fs, const srz_composite_layer *layers, uint32_t n_layers, uint32_t n_ch,
+                                const void *d_bg, uint32_t want_through, const void *d_gout, void *const *d_gcolor,
+                                void *const *d_galpha, void *d_gbg, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_composite_grad");
+  std::vector<Range> ins;
+  if (int rc = check_composite(ctx, fs, fn, layers, n_layers, n_ch, d_bg, want_through, flags, &ins)) return rc;
+  if (!d_gout) return fail(ctx, SRZ_E_INVALID, fn + ": null d_gout");
+  const size_t one_bytes = srz_frameset_interpolate_bytes(ctx, fs, 1u), col_bytes = (size_t)n_ch * one_bytes;
+  std::vector<Range> outs;
+  const void *any = d_gbg;
+  bool misaligned = !aligned<16>({d_bg, d_gout, d_gbg});
+  for (uint32_t k = 0; k < n_layers; ++k) {
+    void *gc = d_gcolor ? d_gcolor[k] : nullptr, *ga = d_galpha ? d_galpha[k] : nullptr;
+    if (gc) any = gc;
+    if (ga) any = ga;
+    misaligned = misaligned || !aligned<16>({gc, ga});
+    outs.push_back({gc, col_bytes}), outs.push_back({ga, one_bytes});
+  }
+  outs.push_back({d_gbg, col_bytes});
+  if (!any) return fail(ctx, SRZ_E_INVALID, fn + ": none of d_gcolor, d_galpha, d_gbg is asked for");
+  if (d_gbg && !d_bg) return fail(ctx, SRZ_E_INVALID, fn + ": d_gbg needs d_bg");
+  if (misaligned)
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_bg, d_gout, d_gcolor[k], d_galpha[k], d_gbg) must be 16-byte aligned");
+  ins.push_back({d_gout, (size_t)(n_ch + want_through) * one_bytes});
+  if (int rc = check_overlaps_n(ctx, fn + " (d_gcolor, d_galpha, d_gbg against every layer's vis, color, alpha, d_bg and d_gout)", outs, ins))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc;
+  CompositeArgs a = composite_args(fs, layers, n_layers, n_ch, d_bg, want_through, nullptr, flags);
+  a.gout = (const float *)d_gout, a.gbg = (float *)d_gbg;
+  for (uint32_t k = 0; k < n_layers; ++k) {
+    a.gcol[k] = d_gcolor ? (float *)d_gcolor[k] : nullptr, a.galpha[k] = d_galpha ? (float *)d_galpha[k] : nullptr;
+    if (a.galpha[k]) a.want_d = 1u;
+  }
+  launch_composite_grad(a, s);
+  return end_pass(ctx);
+}
+
 uint32_t srz_texture_mip_levels(uint32_t tex_w, uint32_t tex_h) {
   if (tex_w == 0u || tex_w > SRZ_TEX_MAX_SIZE || tex_h == 0u || tex_h > SRZ_TEX_MAX_SIZE) return 0u;
   uint32_t n = 1u;

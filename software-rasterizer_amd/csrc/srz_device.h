@@ -616,6 +616,33 @@ struct NormalMapArgs {
 };
 void launch_normal_map(const NormalMapArgs &a, hipStream_t s);
 void launch_normal_map_grad(const NormalMapArgs &a, hipStream_t s);
+// srz_frameset_composite / _composite_grad: n_layers depth layers, nearest first, composited front to back per pixel.  Layer k is a
+// visibility buffer lvis[k] [frame][4][..] (only its id plane is read), a colour buffer col[k] [frame][n_ch][..] and an alpha plane
+// alpha[k] [frame][1][..] or, null, the scalar opacity[k]; bg [frame][n_ch][..] may be null.  `out` is the forward's
+// [frame][n_ch + through][..] (plane n_ch: the transmittance), null in the backward, whose gout has the same planes and whose outputs
+// gcol[k] (col's shape), galpha[k] (one plane) and gbg (bg's shape) may each be null.  `vis` is fill_walk's field (layer 0's buffer);
+// the kernels read lvis.
+struct CompositeArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  float *out;
+  const float *lvis[SRZ_COMPOSITE_MAX], *col[SRZ_COMPOSITE_MAX], *alpha[SRZ_COMPOSITE_MAX];
+  float opacity[SRZ_COMPOSITE_MAX];
+  const float *bg;
+  const float *gout;
+  float *gcol[SRZ_COMPOSITE_MAX], *galpha[SRZ_COMPOSITE_MAX];
+  float *gbg;
+  uint64_t vis_stride;   // floats per frame in a visibility buffer = 4 * local_rows * width
+  uint64_t frame_stride; // floats per frame in out / gout = (n_ch + through) * local_rows * width
+  uint64_t col_stride;   // floats per frame in col / gcol / bg / gbg = n_ch * local_rows * width
+  uint32_t n_layers, n_ch, through;
+  uint32_t want_d;       // backward: some galpha is asked for (the colour planes are read)
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_composite(const CompositeArgs &a, hipStream_t s);
+void launch_composite_grad(const CompositeArgs &a, hipStream_t s);
 // srz_frameset_shadow / _shadow_grad: a float depth map of the caller's [map frame][row][column] compared and filtered at the
 // coordinate planes sc [frame][3][local_rows][width] (sx, sy in texels, sd in the map's depth units) under a visibility buffer
 // (k_shadow), and the gradients of that with respect to the map (gmap, added into) and to the coordinates (k_shadow_grad).  vis as

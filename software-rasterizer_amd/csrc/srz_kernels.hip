@@ -9179,4 +9179,227 @@ void launch_tex_convert(const uint8_t *d_bgr, int w, int h, int row_stride, uint
   hipLaunchKernelGGL(k_tex_convert, dim3((n + 255) / 256), dim3(256), 0, s, d_bgr, w, h, row_stride, d_bgrx);
 }
 
+// ================================================================================================================
+// k_composite, k_composite_grad — DEPTH LAYERS COMPOSITED FRONT TO BACK (srz_frameset_composite / _composite_grad, include/srz.h
+// states the rule).  k_interp's shape on the passes' helpers: pass_walk, four pixels of a row per thread, quad_load, quad_store; no
+// LDS, no barrier, no atomics.  A thread reads the id quads of ALL layers first (comp_cover: independent 16-byte loads, then the
+// passes' owner test, four bits per layer), and loads a layer's alpha and colour quads only where the layer covers one of its pixels.
+// The loops over the layers are unrolled by the build's maximum ML with the run-time count as a guard, so that the per-layer values (w_k in
+// the forward; a_k, T_k and d_k in the backward) are registers and the layers' pointers scalar loads of the kernel arguments.  The
+// channels go in register chunks of ATTR_CHUNK, as in k_interp.  EVERY pixel of the walk is written (quad_store, never
+// quad_store_owned): a pixel no layer covers is bg (or +0) with T = 1, and +0 in the gradients of a layer that does not cover it.
+// (At the end of the file, behind the launchers: no existing kernel moves.)
+// ================================================================================================================
+// the coverage of the thread's quad: bit 4 k + j = layer k covers pixel j
+template <int ML> __device__ __forceinline__ uint32_t comp_cover(const CompositeArgs &a, const PassTile &t) {
+  uint32_t idw[ML][4];
+  const size_t off = (size_t)t.f * a.vis_stride + t.poff + t.rc.plane; // (plane 1: the ids)
+#pragma unroll
+  for (int k = 0; k < ML; ++k) {
+    idw[k][0] = idw[k][1] = idw[k][2] = idw[k][3] = 0u;
+    if ((uint32_t)k < a.n_layers) {
+      if (t.whole) {
+        const uint4 q = *reinterpret_cast<const uint4 *>(a.lvis[k] + off);
+        idw[k][0] = q.x, idw[k][1] = q.y, idw[k][2] = q.z, idw[k][3] = q.w;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (t.x4 + j <= t.rc.tx1) idw[k][j] = f2u(a.lvis[k][off + j]);
+      }
+    }
+  }
+  const uint32_t n_tris = t.fd->n_tris;
+  uint32_t cov = 0u;
+#pragma unroll
+  for (int k = 0; k < ML; ++k)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if ((idw[k][j] & ~S_CLASS_BIT) - 1u < n_tris) cov |= 1u << (4 * k + j); // (quad_ids' test: 0 and the bare class bit wrap)
+  return cov;
+}
+// layer k's alpha quad: the plane's words, or the scalar in every pixel
+__device__ __forceinline__ float4 comp_alpha(const CompositeArgs &a, const PassTile &t, int k) {
+  float4 al[1] = {make_float4(a.opacity[k], a.opacity[k], a.opacity[k], a.opacity[k])};
+  if (a.alpha[k]) quad_load(a.alpha[k] + (size_t)t.f * t.rc.plane + t.poff, t.rc.plane, al, t.whole, t.x4, t.rc.tx1);
+  return al[0];
+}
+// planes c0 .. c0 + nc - 1 of the thread's quad in an n_ch-plane buffer
+__device__ __forceinline__ void comp_chunk_load(const float *buf, const CompositeArgs &a, const PassTile &t, uint32_t c0, uint32_t nc,
+                                                float4 (&v)[ATTR_CHUNK]) {
+  const float *p = buf + (size_t)t.f * a.col_stride + t.poff + (size_t)c0 * t.rc.plane;
+#pragma unroll
+  for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+    float4 q[1] = {make_float4(0.f, 0.f, 0.f, 0.f)};
+    if (i < nc) quad_load(p + (size_t)i * t.rc.plane, t.rc.plane, q, t.whole, t.x4, t.rc.tx1);
+    v[i] = q[0];
+  }
+}
+__device__ __forceinline__ void comp_chunk_store(float *buf, const CompositeArgs &a, const PassTile &t, uint32_t c0, uint32_t nc,
+                                                 const float4 (&v)[ATTR_CHUNK]) {
+  float *p = buf + (size_t)t.f * a.col_stride + t.poff + (size_t)c0 * t.rc.plane;
+#pragma unroll
+  for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+    if (i < nc) quad_store(p + (size_t)i * t.rc.plane, t.rc.plane, {v[i]}, t.whole, t.x4, t.rc.tx1);
+}
+
+template <int ML> __global__ __launch_bounds__(256) void k_composite(CompositeArgs a) {
+  const uint32_t C = a.n_ch;
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const TileRect &rc = t.rc;
+    // ---- 1. every layer's ids, then w_k = a_k T_k of the covering layers and the final T
+    const uint32_t cov = comp_cover<ML>(a, t);
+    float4 T = make_float4(1.f, 1.f, 1.f, 1.f);
+    float4 w[ML];
+#pragma unroll
+    for (int k = 0; k < ML; ++k) {
+      w[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+      const uint32_t m = (cov >> (4 * k)) & 15u;
+      if (m == 0u) continue;
+      const float4 al = comp_alpha(a, t, k);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (m & (1u << j)) {
+          quad_at(w[k], j) = quad_at(al, j) * quad_at(T, j);
+          quad_at(T, j) = quad_at(T, j) * (1.0f - quad_at(al, j));
+        }
+    }
+    // ---- 2. the channels, ATTR_CHUNK at a time: acc = acc + col * w over the covering layers, then + bg * T
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 q[ATTR_CHUNK];
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) q[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int k = 0; k < ML; ++k) {
+        const uint32_t m = (cov >> (4 * k)) & 15u;
+        if (m == 0u) continue;
+        float4 col[ATTR_CHUNK];
+        comp_chunk_load(a.col[k], a, t, c0, nc, col);
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (m & (1u << j)) quad_at(q[i], j) = quad_at(q[i], j) + quad_at(col[i], j) * quad_at(w[k], j);
+      }
+      if (a.bg) {
+        float4 bg[ATTR_CHUNK];
+        comp_chunk_load(a.bg, a, t, c0, nc, bg);
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) quad_at(q[i], j) = quad_at(q[i], j) + quad_at(bg[i], j) * quad_at(T, j);
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+        if (i < nc) quad_store(t.out + (size_t)(c0 + i) * rc.plane, rc.plane, {q[i]}, t.whole, t.x4, rc.tx1);
+    }
+    if (a.through) quad_store(t.out + (size_t)C * rc.plane, rc.plane, {T}, t.whole, t.x4, rc.tx1);
+  });
+}
+
+template <int ML> __global__ __launch_bounds__(256) void k_composite_grad(CompositeArgs a) {
+  const uint32_t C = a.n_ch;
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const TileRect &rc = t.rc;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    // ---- 1. every layer's ids; a_k and T_k of the covering layers, recomputed as the forward computes them; the final T
+    const uint32_t cov = comp_cover<ML>(a, t);
+    float4 T = make_float4(1.f, 1.f, 1.f, 1.f);
+    float4 al[ML], Tk[ML], d[ML];
+#pragma unroll
+    for (int k = 0; k < ML; ++k) {
+      al[k] = Tk[k] = d[k] = zero4;
+      const uint32_t m = (cov >> (4 * k)) & 15u;
+      if (m == 0u) continue;
+      al[k] = comp_alpha(a, t, k);
+      Tk[k] = T;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (m & (1u << j)) quad_at(T, j) = quad_at(T, j) * (1.0f - quad_at(al[k], j));
+    }
+    const float *gout = a.gout + (size_t)t.f * a.frame_stride + t.poff;
+    float4 S[1] = {zero4}; // gT, then + sum g_c bg_c
+    if (a.through) quad_load(gout + (size_t)C * rc.plane, rc.plane, S, t.whole, t.x4, rc.tx1);
+    // ---- 2. the channels, ATTR_CHUNK at a time: gbg and gcol leave, S's bg term and every d_k grow in channel order
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 g[ATTR_CHUNK];
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+        float4 q[1] = {zero4};
+        if (i < nc) quad_load(gout + (size_t)(c0 + i) * rc.plane, rc.plane, q, t.whole, t.x4, rc.tx1);
+        g[i] = q[0];
+      }
+      if (a.bg) {
+        float4 bg[ATTR_CHUNK];
+        comp_chunk_load(a.bg, a, t, c0, nc, bg);
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+          if (i < nc)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) quad_at(S[0], j) = fmaf_(quad_at(g[i], j), quad_at(bg[i], j), quad_at(S[0], j));
+      }
+      if (a.gbg) {
+        float4 o[ATTR_CHUNK];
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) quad_at(o[i], j) = quad_at(g[i], j) * quad_at(T, j);
+        comp_chunk_store(a.gbg, a, t, c0, nc, o);
+      }
+#pragma unroll
+      for (int k = 0; k < ML; ++k) {
+        if ((uint32_t)k >= a.n_layers) continue;
+        const uint32_t m = (cov >> (4 * k)) & 15u;
+        if (m != 0u && a.want_d) {
+          float4 col[ATTR_CHUNK];
+          comp_chunk_load(a.col[k], a, t, c0, nc, col);
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc)
+#pragma unroll
+              for (int j = 0; j < 4; ++j)
+                if (m & (1u << j)) quad_at(d[k], j) = fmaf_(quad_at(g[i], j), quad_at(col[i], j), quad_at(d[k], j));
+        }
+        if (a.gcol[k]) {
+          float4 o[ATTR_CHUNK];
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              quad_at(o[i], j) = (m & (1u << j)) ? quad_at(g[i], j) * (quad_at(al[k], j) * quad_at(Tk[k], j)) : 0.f;
+          comp_chunk_store(a.gcol[k], a, t, c0, nc, o);
+        }
+      }
+    }
+    // ---- 3. the alphas, from the last layer to the first: galpha = T_k (d - S), then S = a d + (1 - a) S
+    if (!a.want_d) return;
+#pragma unroll
+    for (int k = ML - 1; k >= 0; --k) {
+      if ((uint32_t)k >= a.n_layers) continue;
+      const uint32_t m = (cov >> (4 * k)) & 15u;
+      float4 ga[1] = {zero4};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (m & (1u << j)) {
+          const float aj = quad_at(al[k], j), dj = quad_at(d[k], j), Sj = quad_at(S[0], j);
+          quad_at(ga[0], j) = quad_at(Tk[k], j) * (dj - Sj);
+          quad_at(S[0], j) = fmaf_(aj, dj, (1.0f - aj) * Sj);
+        }
+      if (a.galpha[k]) quad_store(a.galpha[k] + (size_t)t.f * rc.plane + t.poff, rc.plane, ga, t.whole, t.x4, rc.tx1);
+    }
+  });
+}
+// (two builds of each, for up to COMP_FEW layers and for up to SRZ_COMPOSITE_MAX: the per-layer registers of the unrolled loops are
+// what the kernels cost, and the generic backward spilled to scratch when held to three waves a SIMD)
+constexpr uint32_t COMP_FEW = 4;
+void launch_composite(const CompositeArgs &a, hipStream_t s) {
+  if (a.n_layers <= COMP_FEW) launch_pass<k_composite<(int)COMP_FEW>>(a, s);
+  else launch_pass<k_composite<SRZ_COMPOSITE_MAX>>(a, s);
+}
+void launch_composite_grad(const CompositeArgs &a, hipStream_t s) {
+  if (a.n_layers <= COMP_FEW) launch_pass<k_composite_grad<(int)COMP_FEW>>(a, s);
+  else launch_pass<k_composite_grad<SRZ_COMPOSITE_MAX>>(a, s);
+}
+
 } // namespace srz

@@ -41,6 +41,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_reflect", "srz_frameset_reflect_grad", "srz_brdf_table", "srz_frameset_ibl", "srz_frameset_ibl_grad",
            "srz_frameset_shadow", "srz_frameset_shadow_grad",
            "srz_mesh_tangents", "srz_mesh_tangents_grad", "srz_frameset_normal_map", "srz_frameset_normal_map_grad",
+           "srz_frameset_composite", "srz_frameset_composite_grad",
            "srz_frameset_perspective", "srz_frameset_perspective_grad", "srz_frameset_interpolate_deriv_persp",
            "srz_target_create", "srz_target_destroy", "srz_target_clear", "srz_target_draw", "srz_target_read", "srz_target_read_bgr8"]
 
@@ -156,6 +157,8 @@ def lib():
         L.srz_mesh_tangents_grad.argtypes = abi.MESH_TANGENTS_GRAD_ARGTYPES
         L.srz_frameset_normal_map.argtypes = abi.NORMAL_MAP_ARGTYPES
         L.srz_frameset_normal_map_grad.argtypes = abi.NORMAL_MAP_GRAD_ARGTYPES
+        L.srz_frameset_composite.argtypes = abi.COMPOSITE_ARGTYPES
+        L.srz_frameset_composite_grad.argtypes = abi.COMPOSITE_GRAD_ARGTYPES
         L.srz_frameset_shadow.argtypes = abi.SHADOW_ARGTYPES
         L.srz_frameset_shadow_grad.argtypes = abi.SHADOW_GRAD_ARGTYPES
         L.srz_frameset_perspective.argtypes = abi.PERSPECTIVE_ARGTYPES
@@ -689,6 +692,36 @@ class FrameSet:
                                                            C.c_void_p(d_tan_ptr), C.c_void_p(d_m_ptr), C.c_void_p(d_gout_ptr),
                                                            C.c_void_p(d_gnrm_ptr or None), C.c_void_p(d_gtan_ptr or None),
                                                            C.c_void_p(d_gm_ptr or None), flags, _stream(stream)))
+
+    def composite(self, layers, n_ch, d_bg_ptr, want_through, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """depth layers composited front to back in one pass: layers is a sequence, nearest first, of (d_vis_ptr, d_color_ptr,
+        d_alpha_ptr or None, opacity) — a visibility buffer of this set, its colours [frame][n_ch][local_rows][width] and its alpha
+        plane [frame][1][...] or, with None, the scalar opacity; d_bg_ptr (None / 0: nothing) is [frame][n_ch][...] behind everything
+        → d_out [frame][n_ch + want_through][...], the last plane the transmittance if asked for (include/srz.h states the rule).  A
+        layer that does not cover a pixel is skipped; every pixel is written.  Asynchronous."""
+        arr = abi.composite_layers_array(list(layers))
+        self.ctx._check(lib().srz_frameset_composite(self.ctx.h, self.h, arr, len(layers), n_ch, C.c_void_p(d_bg_ptr or None), int(want_through),
+                                                     C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def composite_grad(self, layers, n_ch, d_bg_ptr, want_through, d_gout_ptr, d_gcolor_ptrs, d_galpha_ptrs, d_gbg_ptr, flags=abi.FUSED_CLEAR,
+                       stream=None):
+        """the backward of composite: d_gout [frame][n_ch + want_through][local_rows][width] → written to d_gcolor_ptrs[k] (layer k's
+        colour shape), d_galpha_ptrs[k] (one plane, also for a scalar opacity) and d_gbg_ptr (d_bg's shape); the two sequences are None
+        or one entry per layer, every entry and d_gbg_ptr may be None / 0, not all.  +0 where the layer does not cover the pixel; per
+        pixel, deterministic.  Asynchronous."""
+        layers = list(layers)
+        arr = abi.composite_layers_array(layers)
+
+        def ptrs(seq):
+            if seq is None:
+                return None
+            seq = list(seq)
+            if len(seq) != len(layers):
+                raise ValueError(f"composite_grad: {len(seq)} gradient pointers for {len(layers)} layers")
+            return (C.c_void_p * max(1, len(seq)))(*[p or None for p in seq])
+        self.ctx._check(lib().srz_frameset_composite_grad(self.ctx.h, self.h, arr, len(layers), n_ch, C.c_void_p(d_bg_ptr or None),
+                                                          int(want_through), C.c_void_p(d_gout_ptr), ptrs(d_gcolor_ptrs), ptrs(d_galpha_ptrs),
+                                                          C.c_void_p(d_gbg_ptr or None), flags, _stream(stream)))
 
     def update_shading(self, frames):
         """new eye, ka, ks, p, kh, kn, lights, flags and batch shaders / textures for a set made from abi.Frame's, triangles untouched

@@ -98,6 +98,10 @@ REFLECT_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32
 BRDF_TABLE_ARGTYPES = [_vp, _vp, C.c_size_t, _u32, _u32, _vp]
 IBL_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, C.c_size_t, _u32, _vp]
 IBL_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]
+# the prototypes of srz_frameset_composite / _composite_grad (argtypes; both return int), set by srz.lib()
+COMPOSITE_MAX = 8  # srz_frameset_composite: the most layers of one call (SRZ_COMPOSITE_MAX)
+COMPOSITE_ARGTYPES = [_vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, C.c_size_t, _u32, _vp]
+COMPOSITE_GRAD_ARGTYPES = [_vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp]
 
 # numpy view of srz_tri (96 B): pos[3][3], nrm[3][3], uv[3][2]
 TRI_DTYPE = np.dtype([("pos", "<f4", (3, 3)), ("nrm", "<f4", (3, 3)), ("uv", "<f4", (3, 2))])
@@ -128,6 +132,19 @@ class SrzSceneFrame(C.Structure):
                 ("ks", C.c_float * 3), ("p", C.c_float), ("kh", C.c_float), ("kn", C.c_float),
                 ("zscale", C.c_float), ("zoffset", C.c_float), ("n_lights", C.c_uint32), ("n_draws", C.c_uint32),
                 ("lights", C.c_void_p), ("draws", C.c_void_p), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class SrzCompositeLayer(C.Structure):
+    """srz_composite_layer: one layer of srz_frameset_composite (three device pointers; alpha None: the scalar opacity)"""
+    _fields_ = [("vis", C.c_void_p), ("color", C.c_void_p), ("alpha", C.c_void_p), ("opacity", C.c_float), ("_pad", C.c_uint32)]
+
+
+def composite_layers_array(layers):
+    """layers: (vis_ptr, color_ptr, alpha_ptr or None, opacity) per layer → a ctypes array of srz_composite_layer"""
+    arr = (SrzCompositeLayer * max(1, len(layers)))()
+    for i, (vis, color, alpha, opacity) in enumerate(layers):
+        arr[i] = SrzCompositeLayer(vis or None, color or None, alpha or None, float(opacity), 0)
+    return arr
 
 
 class SrzStats(C.Structure):

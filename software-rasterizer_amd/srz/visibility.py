@@ -78,7 +78,8 @@ def layers(fs, n, flags=abi.FUSED_CLEAR, stream=None):
 def composite(colors, alphas):
     """front-to-back "over" of depth layers, nearest first: colors[k] is [n, C, rows, W], alphas[k] [n, 1 or C, rows, W] (0 where
     nobody owns the pixel: decode(layer).tri >= 0 times the surface's opacity) -> sum_k colors[k] * alphas[k] * prod_{j<k} (1 -
-    alphas[j]).  Plain torch ops: autograd goes through it, into the colours and the opacities of every layer."""
+    alphas[j]).  Plain torch ops: autograd goes through it, into the colours and the opacities of every layer.
+    composite_layers does the same in one pass on the device (one alpha per layer, coverage from the layers' own ids)."""
     colors, alphas = list(colors), list(alphas)
     if not colors or len(colors) != len(alphas):
         raise ValueError(f"composite: {len(colors)} colour layers, {len(alphas)} alpha layers")
@@ -88,6 +89,120 @@ def composite(colors, alphas):
         acc = term if acc is None else acc + term
         through = (1 - a) if through is None else through * (1 - a)
     return acc
+
+
+def _composite_args(fs, layers, colors, alphas, background):
+    """→ (layer tuples for FrameSet.composite, n_ch, colours, alpha planes or None, opacities, background or None), checked, contiguous"""
+    layers, colors, alphas = list(layers), list(colors), list(alphas)
+    n = len(layers)
+    if not 1 <= n <= abi.COMPOSITE_MAX or len(colors) != n or len(alphas) != n:
+        raise ValueError(f"composite_layers: {n} layers (1 .. {abi.COMPOSITE_MAX}), {len(colors)} colour buffers, {len(alphas)} alphas")
+    n_ch = colors[0].shape[1] if colors[0].dim() == 4 else 0
+    shape, one = tuple(fs.interpolate_shape(n_ch)), tuple(fs.interpolate_shape(1))
+    cols, planes, opac, tup = [], [], [], []
+    for k in range(n):
+        _vis_arg(fs, layers[k], f"composite_layers: layers[{k}]")
+        c, a = colors[k], alphas[k]
+        if not 1 <= n_ch <= abi.ATTR_MAX_CH or c.dtype != torch.float32 or not c.is_cuda or tuple(c.shape) != shape:
+            raise ValueError(f"composite_layers: colors[{k}] must be a CUDA float32 tensor {shape}, got {tuple(c.shape)} {c.dtype}")
+        c = c.contiguous()
+        if isinstance(a, torch.Tensor) and a.dim() != 0:
+            if a.dtype != torch.float32 or not a.is_cuda or tuple(a.shape) != one:
+                raise ValueError(f"composite_layers: alphas[{k}] must be a CUDA float32 tensor {one} or a scalar, got {tuple(a.shape)} {a.dtype}")
+            a = a.contiguous()
+            planes.append(a), opac.append(0.0)
+        else:
+            planes.append(None), opac.append(float(a))
+        cols.append(c)
+        tup.append((layers[k].data_ptr(), c.data_ptr(), None if planes[k] is None else planes[k].data_ptr(), opac[k]))
+    if background is not None:
+        if background.dtype != torch.float32 or not background.is_cuda or tuple(background.shape) != shape:
+            raise ValueError(f"composite_layers: background must be a CUDA float32 tensor {shape}, got {tuple(background.shape)}")
+        background = background.contiguous()
+    return tup, n_ch, cols, planes, opac, background
+
+
+def composite_grad(fs, layers, colors, alphas, gout, background=None, through=False, want_gcolor=True, want_galpha=True, want_gbg=None,
+                   stream=None):
+    """the backward of composite_layers(fs, layers, colors, alphas, background, through) by one FrameSet.composite_grad call: gout
+    [n_frames, C (+ 1), rows, W] → (gcolors, galphas, gbg): two lists with one entry per layer and the background's gradient, an
+    entry None where not wanted.  want_gcolor and want_galpha are a bool or one bool per layer; want_gbg defaults to "there is a
+    background".  galphas[k] is a plane [n_frames, 1, rows, W] also where alphas[k] is a scalar (its gradient is the plane's sum).  +0
+    where the layer does not cover the pixel; per pixel, deterministic.  stream: a raw stream handle, None = torch's current stream."""
+    tup, n_ch, cols, planes, opac, bg = _composite_args(fs, layers, colors, alphas, background)
+    n = len(tup)
+    want_gcolor = [bool(want_gcolor)] * n if isinstance(want_gcolor, bool) else [bool(w) for w in want_gcolor]
+    want_galpha = [bool(want_galpha)] * n if isinstance(want_galpha, bool) else [bool(w) for w in want_galpha]
+    want_gbg = bg is not None if want_gbg is None else bool(want_gbg)
+    if len(want_gcolor) != n or len(want_galpha) != n:
+        raise ValueError(f"composite_grad: want_gcolor / want_galpha must be a bool or {n} bools")
+    if want_gbg and bg is None:
+        raise ValueError("composite_grad: gbg without a background")
+    if not (any(want_gcolor) or any(want_galpha) or want_gbg):
+        raise ValueError("composite_grad: no gradient is asked for")
+    gout = gout.contiguous()
+    planes_out = n_ch + (1 if through else 0)
+    if tuple(gout.shape) != tuple(fs.interpolate_shape(planes_out)) or gout.dtype != torch.float32 or not gout.is_cuda:
+        raise ValueError(f"composite_grad: gout must be a CUDA float32 tensor {fs.interpolate_shape(planes_out)}, got {tuple(gout.shape)} {gout.dtype}")
+    dev = gout.device
+    gcol = [torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=dev) if w else None for w in want_gcolor]
+    galpha = [torch.empty(fs.interpolate_shape(1), dtype=torch.float32, device=dev) if w else None for w in want_galpha]
+    gbg = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=dev) if want_gbg else None
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    fs.composite_grad(tup, n_ch, ptr(bg), bool(through), gout.data_ptr(), [ptr(t) for t in gcol], [ptr(t) for t in galpha], ptr(gbg),
+                      abi.FUSED_CLEAR, _stream_ptr(stream))
+    return gcol, galpha, gbg
+
+
+class _CompositeLayers(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, fs, layers, through, stream, n, has_bg, *tensors):
+        colors, alphas, bg = tensors[:n], tensors[n:2 * n], tensors[2 * n] if has_bg else None
+        tup, n_ch, cols, planes, opac, bg = _composite_args(fs, layers, colors, alphas, bg)
+        planes_out = n_ch + (1 if through else 0)
+        out = torch.empty(fs.interpolate_shape(planes_out), dtype=torch.float32, device=cols[0].device)
+        fs.composite(tup, n_ch, None if bg is None else bg.data_ptr(), bool(through), out.data_ptr(), out.numel() * 4, abi.FUSED_CLEAR,
+                     _stream_ptr(stream))
+        ctx.fs, ctx.layers, ctx.through, ctx.stream, ctx.n, ctx.has_bg = fs, list(layers), through, stream, n, has_bg
+        ctx.scalar = [p is None for p in planes]
+        ctx.alpha_meta = [(a.dtype, a.device) if isinstance(a, torch.Tensor) else None for a in alphas]
+        ctx.save_for_backward(*cols, *[torch.as_tensor(o) if p is None else p for p, o in zip(planes, opac)], *([bg] if has_bg else []))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        n, saved = ctx.n, ctx.saved_tensors
+        cols, alphas, bg = saved[:n], saved[n:2 * n], saved[2 * n] if ctx.has_bg else None
+        alphas = [float(a) if s else a for a, s in zip(alphas, ctx.scalar)]
+        need = ctx.needs_input_grad[6:]
+        need_c, need_a, need_bg = list(need[:n]), list(need[n:2 * n]), bool(ctx.has_bg and need[2 * n])
+        grads = [None] * (2 * n + (1 if ctx.has_bg else 0))
+        if any(need_c) or any(need_a) or need_bg:  # one call, asking only for what is needed
+            gcol, galpha, gbg = composite_grad(ctx.fs, ctx.layers, cols, alphas, gout, bg, ctx.through, need_c, need_a, need_bg, ctx.stream)
+            for k in range(n):
+                grads[k] = gcol[k]
+                if galpha[k] is not None:  # (a scalar opacity: the plane's sum, in the scalar's dtype and on its device)
+                    grads[n + k] = galpha[k].sum().to(dtype=ctx.alpha_meta[k][0], device=ctx.alpha_meta[k][1]) if ctx.scalar[k] else galpha[k]
+            if ctx.has_bg:
+                grads[2 * n] = gbg
+        return (None, None, None, None, None, None, *grads)
+
+
+def composite_layers(fs, layers, colors, alphas, background=None, through=False, stream=None):
+    """front-to-back "over" of depth layers in ONE pass on the device (FrameSet.composite; include/srz.h states the rule): layers is
+    layers(fs, n)'s list (or any 1 .. 8 visibility buffers of `fs`, nearest first), colors[k] [n_frames, C, rows, W] float32,
+    alphas[k] a plane [n_frames, 1, rows, W] or a scalar (a Python float or a 0-dim tensor: the layer's opacity), background
+    [n_frames, C, rows, W] or None → [n_frames, C, rows, W]: sum_k colors[k] alphas[k] T_k (+ background T_n), T the product of (1 -
+    alpha) over the covering layers in front; with through=True the final T is appended as plane C.  A layer counts at a pixel only
+    where its own id word names an owner — no alpha * coverage tensor is needed, and colours and alphas may hold anything (NaN) where
+    it does not.  Differentiable with respect to every colour, alpha (a scalar that requires grad gets the sum of its plane) and the
+    background; backward is one composite_grad call that asks only for what some input needs, and nothing but the inputs is kept for
+    it.  stream: a raw stream handle, None = torch's current stream."""
+    layers, colors, alphas = list(layers), list(colors), list(alphas)
+    if not (len(layers) == len(colors) == len(alphas)):
+        raise ValueError(f"composite_layers: {len(layers)} layers, {len(colors)} colour buffers, {len(alphas)} alphas")
+    extra = [] if background is None else [background]
+    return _CompositeLayers.apply(fs, layers, through, stream, len(layers), background is not None, *colors, *alphas, *extra)
 
 
 def batch_of(frame, tri):
