@@ -36,10 +36,85 @@ def decode(out):
     return Visibility(z, tri, s_class, alpha, beta, gamma)
 
 
-def _vis_arg(fs, t, name):
-    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(fs.out_shape):
-        raise ValueError(f"{name}: expected a contiguous CUDA float32 tensor {tuple(fs.out_shape)}, got {tuple(t.shape)} {t.dtype}")
+# ------------------------------------------------------------------------------------------------ the argument checks, each once
+# Every tensor whose address goes to the library is checked by one of these, on the host, before the call.  Their texts are pinned
+# word for word by tests/visrefusals.py, so a caller passes its own name and the few words its refusal has always had.
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _got(t, form):
+    """the tail of a refusal: "" says nothing, "plain" the shape and the dtype, "pair" the two as a tuple, "shape" the shape alone"""
+    if not form:
+        return ""
+    if t is None:
+        return ", got None"
+    return ", got " + {"plain": f"{tuple(t.shape)} {t.dtype}", "pair": f"{(tuple(t.shape), t.dtype)}", "shape": f"{tuple(t.shape)}"}[form]
+
+
+def _on_device(t, who):
+    if not t.is_cuda:
+        raise ValueError(f"{who} must be on the device, got {t.device}")
     return t
+
+
+def _vis_arg(fs, t, name):
+    """a visibility buffer of the set: a contiguous CUDA float32 tensor of fs.out_shape, as it is (no copy)"""
+    if t is None or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(fs.out_shape):
+        raise ValueError(f"{name}: expected a contiguous CUDA float32 tensor {tuple(fs.out_shape)}" + _got(t, "plain"))
+    return t
+
+
+def _vis_ptr(fs, vis, fn):
+    """the address of `vis` for the library: there is no way to it past the check"""
+    return _vis_arg(fs, vis, f"{fn}: vis").data_ptr()
+
+
+def _plane(fs, t, n_planes, who, must="a CUDA float32 tensor {shape}", got="plain", ok=True):
+    """a plane tensor of the set: a float32 tensor of fs.interpolate_shape(n_planes) → it, contiguous.  who: "<function>: <argument>";
+    must: the refusal's words — one that names CUDA refuses a host tensor in them, the others leave that to _on_device —; ok: a
+    further condition of the caller's, refused in the same words"""
+    shape = tuple(fs.interpolate_shape(n_planes))
+    if t is None or t.dtype != torch.float32 or ("CUDA" in must and not t.is_cuda) or tuple(t.shape) != shape or not ok:
+        raise ValueError(f"{who} must be {must.format(shape=shape)}" + _got(t, got))
+    return t.contiguous()
+
+
+def _gout(fs, gout, n_planes, fn):
+    """the incoming gradient of a *_grad function: float32 of the set's shape, then on the device"""
+    return _on_device(_plane(fs, gout, n_planes, f"{fn}: gout", "float32 {shape}"), f"{fn}: gout")
+
+
+def _pos_handle(fs, pos, fn):
+    """the graph handle on the triangles' screen positions, float32 [n_frames, T, 3, 3] of any device: its values are never read"""
+    if pos is None or pos.dtype != torch.float32 or pos.dim() != 4 or pos.shape[0] != fs.n_frames or tuple(pos.shape[2:]) != (3, 3):
+        raise ValueError(f"{fn}: pos must be float32 [n_frames, T, 3, 3]" + _got(pos, "plain"))
+    return pos.shape
+
+
+def _lead_frames(fs, t, dims, who, must, ok=lambda t: True, cuda=True):
+    """the "[tail] or [n_frames, tail]" rule: `t` has dims[0] dimensions (one array for every frame) or more (one per frame of the
+    set) → its frame count.  must: the refusal's words; ok: the caller's own conditions on the shape, refused in the same words"""
+    if t is None or t.dtype != torch.float32 or (cuda and not t.is_cuda) or t.dim() not in dims or not ok(t):
+        raise ValueError(f"{who} must be {must}" + _got(t, "plain"))
+    if t.dim() > dims[0] and t.shape[0] != fs.n_frames:
+        raise ValueError(f"{who} has {t.shape[0]} frames, the set {fs.n_frames}")
+    return t.shape[0] if t.dim() > dims[0] else 1
+
+
+def _backward(ctx, k, grad, optional=None):
+    """the backward of a pass whose first k inputs are the differentiable ones: one grad(*need) call asking only for what is needed
+    (none when nothing is), None for every other input.  optional: (index, given) of an input that may have been None"""
+    need = list(ctx.needs_input_grad[:k])
+    if optional is not None:
+        need[optional[0]] = need[optional[0]] and optional[1]
+    grads = grad(*need) if any(need) else (None,) * k
+    return (*grads, *[None] * (len(ctx.needs_input_grad) - k))
+
+
+def _reduced(par, work_bytes):
+    """(the gradient of a parameter block, the scratch its fixed-tree reduction takes)"""
+    return torch.empty_like(par), torch.empty(max(work_bytes // 4, 1), dtype=torch.float32, device=par.device)
 
 
 def first_prev(fs):
@@ -97,28 +172,19 @@ def _composite_args(fs, layers, colors, alphas, background):
     n = len(layers)
     if not 1 <= n <= abi.COMPOSITE_MAX or len(colors) != n or len(alphas) != n:
         raise ValueError(f"composite_layers: {n} layers (1 .. {abi.COMPOSITE_MAX}), {len(colors)} colour buffers, {len(alphas)} alphas")
-    n_ch = colors[0].shape[1] if colors[0].dim() == 4 else 0
-    shape, one = tuple(fs.interpolate_shape(n_ch)), tuple(fs.interpolate_shape(1))
+    n_ch = colors[0].shape[1] if isinstance(colors[0], torch.Tensor) and colors[0].dim() == 4 else 0
     cols, planes, opac, tup = [], [], [], []
     for k in range(n):
         _vis_arg(fs, layers[k], f"composite_layers: layers[{k}]")
-        c, a = colors[k], alphas[k]
-        if not 1 <= n_ch <= abi.ATTR_MAX_CH or c.dtype != torch.float32 or not c.is_cuda or tuple(c.shape) != shape:
-            raise ValueError(f"composite_layers: colors[{k}] must be a CUDA float32 tensor {shape}, got {tuple(c.shape)} {c.dtype}")
-        c = c.contiguous()
+        c, a = _plane(fs, colors[k], n_ch, f"composite_layers: colors[{k}]", ok=1 <= n_ch <= abi.ATTR_MAX_CH), alphas[k]
         if isinstance(a, torch.Tensor) and a.dim() != 0:
-            if a.dtype != torch.float32 or not a.is_cuda or tuple(a.shape) != one:
-                raise ValueError(f"composite_layers: alphas[{k}] must be a CUDA float32 tensor {one} or a scalar, got {tuple(a.shape)} {a.dtype}")
-            a = a.contiguous()
-            planes.append(a), opac.append(0.0)
+            planes.append(_plane(fs, a, 1, f"composite_layers: alphas[{k}]", "a CUDA float32 tensor {shape} or a scalar")), opac.append(0.0)
         else:
             planes.append(None), opac.append(float(a))
         cols.append(c)
-        tup.append((layers[k].data_ptr(), c.data_ptr(), None if planes[k] is None else planes[k].data_ptr(), opac[k]))
+        tup.append((layers[k].data_ptr(), c.data_ptr(), _ptr(planes[k]), opac[k]))
     if background is not None:
-        if background.dtype != torch.float32 or not background.is_cuda or tuple(background.shape) != shape:
-            raise ValueError(f"composite_layers: background must be a CUDA float32 tensor {shape}, got {tuple(background.shape)}")
-        background = background.contiguous()
+        background = _plane(fs, background, n_ch, "composite_layers: background", got="shape")
     return tup, n_ch, cols, planes, opac, background
 
 
@@ -140,16 +206,12 @@ def composite_grad(fs, layers, colors, alphas, gout, background=None, through=Fa
         raise ValueError("composite_grad: gbg without a background")
     if not (any(want_gcolor) or any(want_galpha) or want_gbg):
         raise ValueError("composite_grad: no gradient is asked for")
-    gout = gout.contiguous()
-    planes_out = n_ch + (1 if through else 0)
-    if tuple(gout.shape) != tuple(fs.interpolate_shape(planes_out)) or gout.dtype != torch.float32 or not gout.is_cuda:
-        raise ValueError(f"composite_grad: gout must be a CUDA float32 tensor {fs.interpolate_shape(planes_out)}, got {tuple(gout.shape)} {gout.dtype}")
+    gout = _plane(fs, gout, n_ch + (1 if through else 0), "composite_grad: gout")
     dev = gout.device
     gcol = [torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=dev) if w else None for w in want_gcolor]
     galpha = [torch.empty(fs.interpolate_shape(1), dtype=torch.float32, device=dev) if w else None for w in want_galpha]
     gbg = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=dev) if want_gbg else None
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    fs.composite_grad(tup, n_ch, ptr(bg), bool(through), gout.data_ptr(), [ptr(t) for t in gcol], [ptr(t) for t in galpha], ptr(gbg),
+    fs.composite_grad(tup, n_ch, _ptr(bg), bool(through), gout.data_ptr(), [_ptr(t) for t in gcol], [_ptr(t) for t in galpha], _ptr(gbg),
                       abi.FUSED_CLEAR, _stream_ptr(stream))
     return gcol, galpha, gbg
 
@@ -161,8 +223,7 @@ class _CompositeLayers(torch.autograd.Function):
         tup, n_ch, cols, planes, opac, bg = _composite_args(fs, layers, colors, alphas, bg)
         planes_out = n_ch + (1 if through else 0)
         out = torch.empty(fs.interpolate_shape(planes_out), dtype=torch.float32, device=cols[0].device)
-        fs.composite(tup, n_ch, None if bg is None else bg.data_ptr(), bool(through), out.data_ptr(), out.numel() * 4, abi.FUSED_CLEAR,
-                     _stream_ptr(stream))
+        fs.composite(tup, n_ch, _ptr(bg), bool(through), out.data_ptr(), out.numel() * 4, abi.FUSED_CLEAR, _stream_ptr(stream))
         ctx.fs, ctx.layers, ctx.through, ctx.stream, ctx.n, ctx.has_bg = fs, list(layers), through, stream, n, has_bg
         ctx.scalar = [p is None for p in planes]
         ctx.alpha_meta = [(a.dtype, a.device) if isinstance(a, torch.Tensor) else None for a in alphas]
@@ -285,11 +346,8 @@ def motion_decode(buf, what):
 
 
 def _attr_dims(fs, attr):
-    if attr.dtype != torch.float32 or not attr.is_cuda or attr.dim() not in (3, 4) or attr.shape[-2] != 3:
-        raise ValueError(f"interpolate: attr must be a CUDA float32 tensor [T, 3, C] or [n_frames, T, 3, C], got {tuple(attr.shape)} {attr.dtype}")
-    attr_frames = attr.shape[0] if attr.dim() == 4 else 1
-    if attr.dim() == 4 and attr_frames != fs.n_frames:
-        raise ValueError(f"interpolate: attr has {attr_frames} frames, the set {fs.n_frames}")
+    attr_frames = _lead_frames(fs, attr, (3, 4), "interpolate: attr", "a CUDA float32 tensor [T, 3, C] or [n_frames, T, 3, C]",
+                               lambda t: t.shape[-2] == 3)
     return attr_frames, attr.shape[-3], attr.shape[-1]
 
 
@@ -300,11 +358,11 @@ def _stream_ptr(stream):
 class _Interpolate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, attr, fs, vis, stream):
-        attr = attr.contiguous()
         attr_frames, tris, n_ch = _attr_dims(fs, attr)
+        attr = attr.contiguous()
         out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=attr.device)
-        fs.interpolate(vis.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris, out.data_ptr(), fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR,
-                       _stream_ptr(stream))
+        fs.interpolate(_vis_ptr(fs, vis, "interpolate"), attr.data_ptr(), n_ch, attr_frames, tris, out.data_ptr(), fs.interpolate_bytes(n_ch),
+                       abi.FUSED_CLEAR, _stream_ptr(stream))
         ctx.fs, ctx.vis, ctx.stream, ctx.attr_shape = fs, vis, stream, attr.shape
         return out
 
@@ -334,22 +392,12 @@ def interpolate_bary_grad(fs, vis, attr, gout, stream=None):
     """the gradient of interpolate(fs, vis, attr) with respect to alpha and beta, given gout [n_frames, C, rows, W] →
     [n_frames, 2, rows, W] float32 (dalpha, dbeta; zeros where nobody owns the pixel).  gamma's share is folded in: the planes are the
     sums over the channels of gout * (a - c) and gout * (b - c).  Deterministic."""
-    attr, gout = attr.contiguous(), gout.contiguous()
     attr_frames, tris, n_ch = _attr_dims(fs, attr)
-    if tuple(gout.shape) != tuple(fs.interpolate_shape(n_ch)) or gout.dtype != torch.float32:
-        raise ValueError(f"interpolate_bary_grad: gout must be float32 {fs.interpolate_shape(n_ch)}, got {tuple(gout.shape)} {gout.dtype}")
+    attr, gout = attr.contiguous(), _gout(fs, gout, n_ch, "interpolate_bary_grad")
     out = torch.empty(fs.interpolate_shape(2), dtype=torch.float32, device=attr.device)
-    fs.interpolate_grad(vis.data_ptr(), gout.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris, None, out.data_ptr(), abi.FUSED_CLEAR,
-                        _stream_ptr(stream))
+    fs.interpolate_grad(_vis_ptr(fs, vis, "interpolate_bary_grad"), gout.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris, None, out.data_ptr(),
+                        abi.FUSED_CLEAR, _stream_ptr(stream))
     return out
-
-
-def _planes_arg(fs, t, n_planes, name):
-    if t is None:
-        return None
-    if t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != tuple(fs.interpolate_shape(n_planes)):
-        raise ValueError(f"position_grad: {name} must be a CUDA float32 tensor {fs.interpolate_shape(n_planes)}, got {tuple(t.shape)} {t.dtype}")
-    return t.contiguous()
 
 
 def _pos_tris(fs, pos_tris):
@@ -370,26 +418,25 @@ def position_grad(fs, vis, gbary=None, gz=None, pos_tris=None, want_pix=False, s
     between runs; gpix is deterministic.  stream: a raw stream handle, None = torch's current stream."""
     if gbary is None and gz is None:
         raise ValueError("position_grad: neither gbary nor gz is given")
-    gbary, gz = _planes_arg(fs, gbary, 2, "gbary"), _planes_arg(fs, gz, 1, "gz")
+    gbary = None if gbary is None else _plane(fs, gbary, 2, "position_grad: gbary")
+    gz = None if gz is None else _plane(fs, gz, 1, "position_grad: gz")
     T = _pos_tris(fs, pos_tris)
-    gpos = torch.zeros((fs.n_frames, T, 3, 3), dtype=torch.float32, device=vis.device)
-    gpix = torch.empty(fs.interpolate_shape(2), dtype=torch.float32, device=vis.device) if want_pix else None
-    fs.position_grad(vis.data_ptr(), gbary.data_ptr() if gbary is not None else None, gz.data_ptr() if gz is not None else None, T,
-                     gpos.data_ptr(), gpix.data_ptr() if want_pix else None, abi.FUSED_CLEAR, _stream_ptr(stream))
+    dev = _vis_arg(fs, vis, "position_grad: vis").device
+    gpos = torch.zeros((fs.n_frames, T, 3, 3), dtype=torch.float32, device=dev)
+    gpix = torch.empty(fs.interpolate_shape(2), dtype=torch.float32, device=dev) if want_pix else None
+    fs.position_grad(vis.data_ptr(), _ptr(gbary), _ptr(gz), T, gpos.data_ptr(), _ptr(gpix), abi.FUSED_CLEAR, _stream_ptr(stream))
     return (gpos, gpix) if want_pix else gpos
 
 
 class _InterpolateGeo(torch.autograd.Function):
     @staticmethod
     def forward(ctx, attr, pos, fs, vis, stream):
-        attr = attr.contiguous()
         attr_frames, tris, n_ch = _attr_dims(fs, attr)
-        if pos.dtype != torch.float32 or pos.dim() != 4 or pos.shape[0] != fs.n_frames or tuple(pos.shape[2:]) != (3, 3):
-            raise ValueError(f"interpolate_geo: pos must be float32 [n_frames, T, 3, 3], got {tuple(pos.shape)} {pos.dtype}")
+        attr, ctx.pos_shape = attr.contiguous(), _pos_handle(fs, pos, "interpolate_geo")
         out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=attr.device)
-        fs.interpolate(vis.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris, out.data_ptr(), fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR,
-                       _stream_ptr(stream))
-        ctx.fs, ctx.vis, ctx.stream, ctx.pos_shape = fs, vis, stream, pos.shape
+        fs.interpolate(_vis_ptr(fs, vis, "interpolate_geo"), attr.data_ptr(), n_ch, attr_frames, tris, out.data_ptr(), fs.interpolate_bytes(n_ch),
+                       abi.FUSED_CLEAR, _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.stream = fs, vis, stream
         ctx.save_for_backward(attr)
         return out
 
@@ -404,8 +451,7 @@ class _InterpolateGeo(torch.autograd.Function):
         gattr = torch.zeros_like(attr) if need_attr else None
         gbary = torch.empty(fs.interpolate_shape(2), dtype=torch.float32, device=gout.device) if need_pos else None
         if need_attr or need_pos:
-            fs.interpolate_grad(vis.data_ptr(), gout.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris,
-                                gattr.data_ptr() if need_attr else None, gbary.data_ptr() if need_pos else None, abi.FUSED_CLEAR, sp)
+            fs.interpolate_grad(vis.data_ptr(), gout.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris, _ptr(gattr), _ptr(gbary), abi.FUSED_CLEAR, sp)
         gpos = None
         if need_pos:
             gpos = torch.zeros(ctx.pos_shape, dtype=torch.float32, device=gout.device)
@@ -428,9 +474,8 @@ def interpolate_geo(fs, vis, attr, pos, stream=None):
 class _Depth(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, fs, vis, stream):
-        if pos.dtype != torch.float32 or pos.dim() != 4 or pos.shape[0] != fs.n_frames or tuple(pos.shape[2:]) != (3, 3):
-            raise ValueError(f"depth: pos must be float32 [n_frames, T, 3, 3], got {tuple(pos.shape)} {pos.dtype}")
-        ctx.fs, ctx.vis, ctx.stream, ctx.pos_shape = fs, vis, stream, pos.shape
+        ctx.pos_shape = _pos_handle(fs, pos, "depth")
+        ctx.fs, ctx.vis, ctx.stream = fs, _vis_arg(fs, vis, "depth: vis"), stream
         return vis[:, 0:1].clone()
 
     @staticmethod
@@ -452,11 +497,11 @@ def depth(fs, vis, pos, stream=None):
 
 
 def _color_arg(fs, t, name):
-    if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 4 or tuple(t.shape) != tuple(fs.interpolate_shape(t.shape[1])):
-        raise ValueError(f"antialias: {name} must be a CUDA float32 tensor [n_frames, C, rows, W] of the set, got {tuple(t.shape)} {t.dtype}")
-    if not 1 <= t.shape[1] <= abi.ATTR_MAX_CH:
-        raise ValueError(f"antialias: {name} has {t.shape[1]} channels, 1 .. {abi.ATTR_MAX_CH} are supported")
-    return t.contiguous()
+    n_ch = t.shape[1] if isinstance(t, torch.Tensor) and t.dim() == 4 else 0
+    t = _plane(fs, t, n_ch, f"antialias: {name}", "a CUDA float32 tensor [n_frames, C, rows, W] of the set")
+    if not 1 <= n_ch <= abi.ATTR_MAX_CH:
+        raise ValueError(f"antialias: {name} has {n_ch} channels, 1 .. {abi.ATTR_MAX_CH} are supported")
+    return t
 
 
 def antialias_grad(fs, vis, color, gout, pos_tris=None, want_gin=True, want_gpos=True, stream=None):
@@ -473,8 +518,8 @@ def antialias_grad(fs, vis, color, gout, pos_tris=None, want_gin=True, want_gpos
     T = _pos_tris(fs, pos_tris) if want_gpos else 0
     gin = torch.empty_like(color) if want_gin else None
     gpos = torch.zeros((fs.n_frames, T, 3, 3), dtype=torch.float32, device=color.device) if want_gpos else None
-    fs.antialias_grad(vis.data_ptr(), color.data_ptr(), gout.data_ptr(), color.shape[1], gin.data_ptr() if want_gin else None, T,
-                      gpos.data_ptr() if want_gpos else None, abi.FUSED_CLEAR, _stream_ptr(stream))
+    fs.antialias_grad(_vis_ptr(fs, vis, "antialias_grad"), color.data_ptr(), gout.data_ptr(), color.shape[1], _ptr(gin), T, _ptr(gpos),
+                      abi.FUSED_CLEAR, _stream_ptr(stream))
     return gin, gpos
 
 
@@ -482,12 +527,12 @@ class _Antialias(torch.autograd.Function):
     @staticmethod
     def forward(ctx, color, pos, fs, vis, stream):
         color = _color_arg(fs, color, "color")
-        if pos is not None and (pos.dtype != torch.float32 or pos.dim() != 4 or pos.shape[0] != fs.n_frames or tuple(pos.shape[2:]) != (3, 3)):
-            raise ValueError(f"antialias: pos must be float32 [n_frames, T, 3, 3], got {tuple(pos.shape)} {pos.dtype}")
+        ctx.pos_shape = None if pos is None else _pos_handle(fs, pos, "antialias")
         n_ch = color.shape[1]
         out = torch.empty_like(color)
-        fs.antialias(vis.data_ptr(), color.data_ptr(), n_ch, out.data_ptr(), fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR, _stream_ptr(stream))
-        ctx.fs, ctx.vis, ctx.stream, ctx.pos_shape = fs, vis, stream, None if pos is None else pos.shape
+        fs.antialias(_vis_ptr(fs, vis, "antialias"), color.data_ptr(), n_ch, out.data_ptr(), fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR,
+                     _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.stream = fs, vis, stream
         ctx.save_for_backward(color)
         return out
 
@@ -500,9 +545,8 @@ class _Antialias(torch.autograd.Function):
             gout = gout.contiguous()
             gin = torch.empty_like(color) if need_color else None
             gpos = torch.zeros(ctx.pos_shape, dtype=torch.float32, device=gout.device) if need_pos else None
-            fs.antialias_grad(ctx.vis.data_ptr(), color.data_ptr(), gout.data_ptr(), color.shape[1], gin.data_ptr() if need_color else None,
-                              ctx.pos_shape[1] if need_pos else 0, gpos.data_ptr() if need_pos else None, abi.FUSED_CLEAR,
-                              _stream_ptr(ctx.stream))
+            fs.antialias_grad(ctx.vis.data_ptr(), color.data_ptr(), gout.data_ptr(), color.shape[1], _ptr(gin), ctx.pos_shape[1] if need_pos else 0,
+                              _ptr(gpos), abi.FUSED_CLEAR, _stream_ptr(ctx.stream))
         return gin, gpos, None, None, None
 
 
@@ -521,21 +565,11 @@ def antialias(fs, vis, color, pos=None, stream=None):
 
 
 def _tex_dims(fs, tex):
-    if tex.dtype != torch.float32 or not tex.is_cuda or tex.dim() not in (3, 4):
-        raise ValueError(f"texture: tex must be a CUDA float32 tensor [H, W, C] or [n_frames, H, W, C], got {tuple(tex.shape)} {tex.dtype}")
-    tex_frames = tex.shape[0] if tex.dim() == 4 else 1
-    if tex.dim() == 4 and tex_frames != fs.n_frames:
-        raise ValueError(f"texture: tex has {tex_frames} frames, the set {fs.n_frames}")
+    tex_frames = _lead_frames(fs, tex, (3, 4), "texture: tex", "a CUDA float32 tensor [H, W, C] or [n_frames, H, W, C]")
     h, w, n_ch = tex.shape[-3:]
     if not (1 <= w <= abi.TEX_MAX_SIZE and 1 <= h <= abi.TEX_MAX_SIZE and 1 <= n_ch <= abi.ATTR_MAX_CH):
         raise ValueError(f"texture: tex is {w} x {h} texels of {n_ch} channels; 1 .. {abi.TEX_MAX_SIZE} and 1 .. {abi.ATTR_MAX_CH} are supported")
     return tex_frames, h, w, n_ch
-
-
-def _uv_arg(fs, uv):
-    if uv.dtype != torch.float32 or not uv.is_cuda or tuple(uv.shape) != tuple(fs.interpolate_shape(2)):
-        raise ValueError(f"texture: uv must be a CUDA float32 tensor {fs.interpolate_shape(2)}, got {tuple(uv.shape)} {uv.dtype}")
-    return uv.contiguous()
 
 
 def texture_grad(fs, vis, tex, uv, gout, wrap=False, want_gtex=True, want_guv=True, stream=None):
@@ -545,25 +579,25 @@ def texture_grad(fs, vis, tex, uv, gout, wrap=False, want_gtex=True, want_guv=Tr
     interpolate's backward takes for a two-channel attribute.  stream: a raw stream handle, None = torch's current stream."""
     if not want_gtex and not want_guv:
         raise ValueError("texture_grad: neither gtex nor guv is asked for")
-    tex, uv, gout = tex.contiguous(), _uv_arg(fs, uv), gout.contiguous()
+    uv = _plane(fs, uv, 2, "texture: uv")
     tex_frames, h, w, n_ch = _tex_dims(fs, tex)
-    if tuple(gout.shape) != tuple(fs.interpolate_shape(n_ch)) or gout.dtype != torch.float32:
-        raise ValueError(f"texture_grad: gout must be float32 {fs.interpolate_shape(n_ch)}, got {tuple(gout.shape)} {gout.dtype}")
+    tex, gout = tex.contiguous(), _gout(fs, gout, n_ch, "texture_grad")
     gtex = torch.zeros_like(tex) if want_gtex else None
     guv = torch.empty_like(uv) if want_guv else None
-    fs.texture_grad(vis.data_ptr(), uv.data_ptr(), gout.data_ptr(), tex.data_ptr(), w, h, n_ch, tex_frames, abi.TEX_WRAP if wrap else abi.TEX_CLAMP,
-                    gtex.data_ptr() if want_gtex else None, guv.data_ptr() if want_guv else None, abi.FUSED_CLEAR, _stream_ptr(stream))
+    fs.texture_grad(_vis_ptr(fs, vis, "texture_grad"), uv.data_ptr(), gout.data_ptr(), tex.data_ptr(), w, h, n_ch, tex_frames,
+                    abi.TEX_WRAP if wrap else abi.TEX_CLAMP, _ptr(gtex), _ptr(guv), abi.FUSED_CLEAR, _stream_ptr(stream))
     return gtex, guv
 
 
 class _Texture(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tex, uv, fs, vis, wrap, stream):
-        tex, uv = tex.contiguous(), _uv_arg(fs, uv)
+        uv = _plane(fs, uv, 2, "texture: uv")
         tex_frames, h, w, n_ch = _tex_dims(fs, tex)
+        tex = tex.contiguous()
         out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=tex.device)
-        fs.texture(vis.data_ptr(), uv.data_ptr(), tex.data_ptr(), w, h, n_ch, tex_frames, abi.TEX_WRAP if wrap else abi.TEX_CLAMP, out.data_ptr(),
-                   fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR, _stream_ptr(stream))
+        fs.texture(_vis_ptr(fs, vis, "texture"), uv.data_ptr(), tex.data_ptr(), w, h, n_ch, tex_frames, abi.TEX_WRAP if wrap else abi.TEX_CLAMP,
+                   out.data_ptr(), fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR, _stream_ptr(stream))
         ctx.fs, ctx.vis, ctx.wrap, ctx.stream = fs, vis, wrap, stream
         ctx.save_for_backward(tex, uv)
         return out
@@ -571,11 +605,7 @@ class _Texture(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         tex, uv = ctx.saved_tensors
-        need_tex, need_uv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gtex = guv = None
-        if need_tex or need_uv:  # one call, asking only for what is needed
-            gtex, guv = texture_grad(ctx.fs, ctx.vis, tex, uv, gout, ctx.wrap, need_tex, need_uv, ctx.stream)
-        return gtex, guv, None, None, None, None
+        return _backward(ctx, 2, lambda *need: texture_grad(ctx.fs, ctx.vis, tex, uv, gout, ctx.wrap, *need, ctx.stream))
 
 
 def texture(fs, vis, tex, uv, wrap=False, stream=None):
@@ -603,21 +633,12 @@ def cube_dirs(n, device=None):
 
 
 def _cube_dims(fs, cube):
-    if cube.dtype != torch.float32 or not cube.is_cuda or cube.dim() not in (4, 5) or cube.shape[-4] != 6 or cube.shape[-3] != cube.shape[-2]:
-        raise ValueError(f"texture_cube: cube must be a CUDA float32 tensor [6, N, N, C] or [n_frames, 6, N, N, C], got {tuple(cube.shape)} {cube.dtype}")
-    tex_frames = cube.shape[0] if cube.dim() == 5 else 1
-    if cube.dim() == 5 and tex_frames != fs.n_frames:
-        raise ValueError(f"texture_cube: cube has {tex_frames} frames, the set {fs.n_frames}")
+    tex_frames = _lead_frames(fs, cube, (4, 5), "texture_cube: cube", "a CUDA float32 tensor [6, N, N, C] or [n_frames, 6, N, N, C]",
+                              lambda t: t.shape[-4] == 6 and t.shape[-3] == t.shape[-2])
     n, n_ch = cube.shape[-2], cube.shape[-1]
     if not (1 <= n <= abi.TEX_MAX_SIZE and 1 <= n_ch <= abi.ATTR_MAX_CH):
         raise ValueError(f"texture_cube: faces of {n} x {n} texels, {n_ch} channels; 1 .. {abi.TEX_MAX_SIZE} and 1 .. {abi.ATTR_MAX_CH} are supported")
     return tex_frames, n, n_ch
-
-
-def _dirs_arg(fs, dirs):
-    if dirs.dtype != torch.float32 or not dirs.is_cuda or tuple(dirs.shape) != tuple(fs.interpolate_shape(3)):
-        raise ValueError(f"texture_cube: dirs must be a CUDA float32 tensor {fs.interpolate_shape(3)}, got {tuple(dirs.shape)} {dirs.dtype}")
-    return dirs.contiguous()
 
 
 def texture_cube_grad(fs, vis, cube, dirs, gout, want_gtex=True, want_gdir=True, stream=None):
@@ -627,25 +648,25 @@ def texture_cube_grad(fs, vis, cube, dirs, gout, want_gtex=True, want_gdir=True,
     is what interpolate's backward takes for a three-channel attribute.  stream: a raw stream handle, None = torch's current stream."""
     if not want_gtex and not want_gdir:
         raise ValueError("texture_cube_grad: neither gtex nor gdir is asked for")
-    cube, dirs, gout = cube.contiguous(), _dirs_arg(fs, dirs), gout.contiguous()
+    dirs = _plane(fs, dirs, 3, "texture_cube: dirs")
     tex_frames, n, n_ch = _cube_dims(fs, cube)
-    if tuple(gout.shape) != tuple(fs.interpolate_shape(n_ch)) or gout.dtype != torch.float32:
-        raise ValueError(f"texture_cube_grad: gout must be float32 {fs.interpolate_shape(n_ch)}, got {tuple(gout.shape)} {gout.dtype}")
+    cube, gout = cube.contiguous(), _gout(fs, gout, n_ch, "texture_cube_grad")
     gtex = torch.zeros_like(cube) if want_gtex else None
     gdir = torch.empty_like(dirs) if want_gdir else None
-    fs.texture_cube_grad(vis.data_ptr(), dirs.data_ptr(), gout.data_ptr(), cube.data_ptr(), n, n_ch, tex_frames,
-                         gtex.data_ptr() if want_gtex else None, gdir.data_ptr() if want_gdir else None, abi.FUSED_CLEAR, _stream_ptr(stream))
+    fs.texture_cube_grad(_vis_ptr(fs, vis, "texture_cube_grad"), dirs.data_ptr(), gout.data_ptr(), cube.data_ptr(), n, n_ch, tex_frames, _ptr(gtex),
+                         _ptr(gdir), abi.FUSED_CLEAR, _stream_ptr(stream))
     return gtex, gdir
 
 
 class _TextureCube(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cube, dirs, fs, vis, stream):
-        cube, dirs = cube.contiguous(), _dirs_arg(fs, dirs)
+        dirs = _plane(fs, dirs, 3, "texture_cube: dirs")
         tex_frames, n, n_ch = _cube_dims(fs, cube)
+        cube = cube.contiguous()
         out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=cube.device)
-        fs.texture_cube(vis.data_ptr(), dirs.data_ptr(), cube.data_ptr(), n, n_ch, tex_frames, out.data_ptr(), fs.interpolate_bytes(n_ch),
-                        abi.FUSED_CLEAR, _stream_ptr(stream))
+        fs.texture_cube(_vis_ptr(fs, vis, "texture_cube"), dirs.data_ptr(), cube.data_ptr(), n, n_ch, tex_frames, out.data_ptr(),
+                        fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR, _stream_ptr(stream))
         ctx.fs, ctx.vis, ctx.stream = fs, vis, stream
         ctx.save_for_backward(cube, dirs)
         return out
@@ -653,11 +674,7 @@ class _TextureCube(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         cube, dirs = ctx.saved_tensors
-        need_tex, need_dir = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gtex = gdir = None
-        if need_tex or need_dir:  # one call, asking only for what is needed
-            gtex, gdir = texture_cube_grad(ctx.fs, ctx.vis, cube, dirs, gout, need_tex, need_dir, ctx.stream)
-        return gtex, gdir, None, None, None
+        return _backward(ctx, 2, lambda *need: texture_cube_grad(ctx.fs, ctx.vis, cube, dirs, gout, *need, ctx.stream))
 
 
 def texture_cube(fs, vis, cube, dirs, stream=None):
@@ -701,15 +718,15 @@ _BG_WHERE = {"nobody": abi.BG_NOBODY, "all": abi.BG_ALL}
 
 
 def _background_args(fs, vis, cube, rays, where):
-    """→ (cube, rays, tex_frames, n, n_ch, ray_frames, where word, vis pointer or None), checked and contiguous"""
+    """→ (cube, rays, tex_frames, n, n_ch, ray_frames, where word), checked and contiguous"""
     if where not in _BG_WHERE:
         raise ValueError(f"background: where must be 'nobody' or 'all', got {where!r}")
     tex_frames, n, n_ch = _cube_dims(fs, cube)
-    if rays.dtype != torch.float32 or not rays.is_cuda or rays.dim() != 2 or rays.shape[1] != 9 or rays.shape[0] not in (1, fs.n_frames):
-        raise ValueError(f"background: rays must be a CUDA float32 tensor [1 or {fs.n_frames}, 9], got {tuple(rays.shape)} {rays.dtype}")
+    if rays is None or rays.dtype != torch.float32 or not rays.is_cuda or rays.dim() != 2 or rays.shape[1] != 9 or rays.shape[0] not in (1, fs.n_frames):
+        raise ValueError(f"background: rays must be a CUDA float32 tensor [1 or {fs.n_frames}, 9]" + _got(rays, "plain"))
     if vis is None and where != "all":
         raise ValueError("background: vis may be None only with where='all'")
-    return cube.contiguous(), rays.contiguous(), tex_frames, n, n_ch, rays.shape[0], _BG_WHERE[where], None if vis is None else vis.data_ptr()
+    return cube.contiguous(), rays.contiguous(), tex_frames, n, n_ch, rays.shape[0], _BG_WHERE[where]
 
 
 def background_grad(fs, vis, cube, rays, gout, where="nobody", want_gtex=True, want_gray=True, stream=None):
@@ -719,29 +736,23 @@ def background_grad(fs, vis, cube, rays, gout, where="nobody", want_gtex=True, w
     stream handle, None = torch's current stream."""
     if not want_gtex and not want_gray:
         raise ValueError("background_grad: neither gtex nor gray is asked for")
-    cube, rays, tex_frames, n, n_ch, ray_frames, w, vis_ptr = _background_args(fs, vis, cube, rays, where)
-    gout = gout.contiguous()
-    if tuple(gout.shape) != tuple(fs.interpolate_shape(n_ch)) or gout.dtype != torch.float32:
-        raise ValueError(f"background_grad: gout must be float32 {fs.interpolate_shape(n_ch)}, got {tuple(gout.shape)} {gout.dtype}")
+    cube, rays, tex_frames, n, n_ch, ray_frames, w = _background_args(fs, vis, cube, rays, where)
+    gout = _gout(fs, gout, n_ch, "background_grad")
     gtex = torch.zeros_like(cube) if want_gtex else None
-    gray = work = None
-    work_bytes = 0
-    if want_gray:
-        work_bytes = fs.background_work_bytes()
-        gray, work = torch.empty_like(rays), torch.empty(max(work_bytes // 4, 1), dtype=torch.float32, device=rays.device)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    fs.background_grad(vis_ptr, rays.data_ptr(), ray_frames, gout.data_ptr(), cube.data_ptr(), n, n_ch, tex_frames, w, ptr(gtex), ptr(gray),
-                       ptr(work), work_bytes, abi.FUSED_CLEAR, _stream_ptr(stream))
+    work_bytes = fs.background_work_bytes() if want_gray else 0
+    gray, work = _reduced(rays, work_bytes) if want_gray else (None, None)
+    fs.background_grad(None if vis is None else _vis_ptr(fs, vis, "background_grad"), rays.data_ptr(), ray_frames, gout.data_ptr(), cube.data_ptr(),
+                       n, n_ch, tex_frames, w, _ptr(gtex), _ptr(gray), _ptr(work), work_bytes, abi.FUSED_CLEAR, _stream_ptr(stream))
     return gtex, gray
 
 
 class _Background(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cube, rays, fs, vis, where, stream):
-        cube, rays, tex_frames, n, n_ch, ray_frames, w, vis_ptr = _background_args(fs, vis, cube, rays, where)
+        cube, rays, tex_frames, n, n_ch, ray_frames, w = _background_args(fs, vis, cube, rays, where)
         out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=cube.device)
-        fs.background(vis_ptr, rays.data_ptr(), ray_frames, cube.data_ptr(), n, n_ch, tex_frames, w, out.data_ptr(), fs.interpolate_bytes(n_ch),
-                      abi.FUSED_CLEAR, _stream_ptr(stream))
+        fs.background(None if vis is None else _vis_ptr(fs, vis, "background"), rays.data_ptr(), ray_frames, cube.data_ptr(), n, n_ch, tex_frames, w,
+                      out.data_ptr(), fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR, _stream_ptr(stream))
         ctx.fs, ctx.vis, ctx.where, ctx.stream = fs, vis, where, stream
         ctx.save_for_backward(cube, rays)
         return out
@@ -749,11 +760,7 @@ class _Background(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         cube, rays = ctx.saved_tensors
-        need_tex, need_ray = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gtex = gray = None
-        if need_tex or need_ray:  # one call, asking only for what is needed
-            gtex, gray = background_grad(ctx.fs, ctx.vis, cube, rays, gout, ctx.where, need_tex, need_ray, ctx.stream)
-        return gtex, gray, None, None, None, None
+        return _backward(ctx, 2, lambda *need: background_grad(ctx.fs, ctx.vis, cube, rays, gout, ctx.where, *need, ctx.stream))
 
 
 def background(fs, vis, cube, rays, where="nobody", stream=None):
@@ -770,25 +777,17 @@ def background(fs, vis, cube, rays, where="nobody", stream=None):
 
 def _map_dims(fs, map):
     """map [H, W], [n_frames, H, W] or depth()'s [n_frames, 1, H, W] → (map_frames, H, W)"""
-    if map.dtype != torch.float32 or map.dim() not in (2, 3, 4) or (map.dim() == 4 and map.shape[1] != 1):
-        raise ValueError(f"shadow: map must be a float32 tensor [H, W], [n_frames, H, W] or [n_frames, 1, H, W], got {tuple(map.shape)} {map.dtype}")
-    map_frames = map.shape[0] if map.dim() > 2 else 1
-    if map.dim() > 2 and map_frames != fs.n_frames:
-        raise ValueError(f"shadow: map has {map_frames} frames, the set {fs.n_frames}")
+    map_frames = _lead_frames(fs, map, (2, 3, 4), "shadow: map", "a float32 tensor [H, W], [n_frames, H, W] or [n_frames, 1, H, W]",
+                              lambda t: t.dim() < 4 or t.shape[1] == 1, cuda=False)
     h, w = map.shape[-2:]
     if not (1 <= w <= abi.TEX_MAX_SIZE and 1 <= h <= abi.TEX_MAX_SIZE):
         raise ValueError(f"shadow: map is {w} x {h} texels; 1 .. {abi.TEX_MAX_SIZE} are supported")
-    if not map.is_cuda:
-        raise ValueError(f"shadow: map must be on the device, got {map.device}")
+    _on_device(map, "shadow: map")
     return map_frames, h, w
 
 
 def _sc_arg(fs, sc):
-    if sc.dtype != torch.float32 or tuple(sc.shape) != tuple(fs.interpolate_shape(3)):
-        raise ValueError(f"shadow: sc must be a float32 tensor {fs.interpolate_shape(3)}, got {tuple(sc.shape)} {sc.dtype}")
-    if not sc.is_cuda:
-        raise ValueError(f"shadow: sc must be on the device, got {sc.device}")
-    return sc.contiguous()
+    return _on_device(_plane(fs, sc, 3, "shadow: sc", "a float32 tensor {shape}"), "shadow: sc")
 
 
 def _ramp_args(bias, width):
@@ -808,13 +807,11 @@ def shadow_grad(fs, vis, map, sc, gout, bias, width, want_gmap=True, want_gsc=Tr
         raise ValueError("shadow_grad: neither gmap nor gsc is asked for")
     bias, width = _ramp_args(bias, width)
     map_frames, h, w = _map_dims(fs, map)
-    map, sc, gout = map.contiguous(), _sc_arg(fs, sc), gout.contiguous()
-    if tuple(gout.shape) != tuple(fs.interpolate_shape(1)) or gout.dtype != torch.float32:
-        raise ValueError(f"shadow_grad: gout must be float32 {fs.interpolate_shape(1)}, got {tuple(gout.shape)} {gout.dtype}")
+    map, sc, gout = map.contiguous(), _sc_arg(fs, sc), _gout(fs, gout, 1, "shadow_grad")
     gmap = torch.zeros_like(map) if want_gmap else None
     gsc = torch.empty_like(sc) if want_gsc else None
-    fs.shadow_grad(vis.data_ptr(), sc.data_ptr(), gout.data_ptr(), map.data_ptr(), w, h, map_frames, bias, width,
-                   gmap.data_ptr() if want_gmap else None, gsc.data_ptr() if want_gsc else None, abi.FUSED_CLEAR, _stream_ptr(stream))
+    fs.shadow_grad(_vis_ptr(fs, vis, "shadow_grad"), sc.data_ptr(), gout.data_ptr(), map.data_ptr(), w, h, map_frames, bias, width, _ptr(gmap),
+                   _ptr(gsc), abi.FUSED_CLEAR, _stream_ptr(stream))
     return gmap, gsc
 
 
@@ -825,8 +822,8 @@ class _Shadow(torch.autograd.Function):
         map_frames, h, w = _map_dims(fs, map)
         map, sc = map.contiguous(), _sc_arg(fs, sc)
         out = torch.empty(fs.interpolate_shape(1), dtype=torch.float32, device=sc.device)
-        fs.shadow(vis.data_ptr(), sc.data_ptr(), map.data_ptr(), w, h, map_frames, bias, width, out.data_ptr(), fs.interpolate_bytes(1),
-                  abi.FUSED_CLEAR, _stream_ptr(stream))
+        fs.shadow(_vis_ptr(fs, vis, "shadow"), sc.data_ptr(), map.data_ptr(), w, h, map_frames, bias, width, out.data_ptr(),
+                  fs.interpolate_bytes(1), abi.FUSED_CLEAR, _stream_ptr(stream))
         ctx.fs, ctx.vis, ctx.bias, ctx.width, ctx.stream = fs, vis, bias, width, stream
         ctx.save_for_backward(map, sc)
         return out
@@ -834,11 +831,7 @@ class _Shadow(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         map, sc = ctx.saved_tensors
-        need_map, need_sc = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gmap = gsc = None
-        if need_map or need_sc:  # one call, asking only for what is needed
-            gmap, gsc = shadow_grad(ctx.fs, ctx.vis, map, sc, gout, ctx.bias, ctx.width, need_map, need_sc, ctx.stream)
-        return gmap, gsc, None, None, None, None, None
+        return _backward(ctx, 2, lambda *need: shadow_grad(ctx.fs, ctx.vis, map, sc, gout, ctx.bias, ctx.width, *need, ctx.stream))
 
 
 def shadow(fs, vis, map, sc, bias=0.0, width=0.0, stream=None):
@@ -864,40 +857,42 @@ def shadow(fs, vis, map, sc, bias=0.0, width=0.0, stream=None):
     return _Shadow.apply(map, sc, fs, vis, bias, width, stream)
 
 
-def light_params(fs, lights, eye, ka, ks):
-    """the parameter block of light / light_grad from its pieces, with torch ops (so gradients of the block flow back to the pieces):
-    lights [L, 6] or [n_frames, L, 6] (a light: pos[3], intensity[3]), eye, ka, ks [3] or [n_frames, 3] → [1, 9 + 6 L] when every piece
-    is shared by the frames, else [n_frames, 9 + 6 L] (per frame as soon as one of them is)"""
-    if lights.dim() not in (2, 3) or lights.shape[-1] != 6 or not 1 <= lights.shape[-2] <= abi.LIGHT_MAX:
-        raise ValueError(f"light: lights must be [L, 6] or [n_frames, L, 6] with 1 <= L <= {abi.LIGHT_MAX}, got {tuple(lights.shape)}")
-    pieces = [("eye", eye), ("ka", ka), ("ks", ks)]
+def _params(fs, what, lights, pieces):
+    """the parameter block of `what`: the three-vector pieces [(name, [3] or [n_frames, 3])] in order, then the lights' rows"""
+    if lights is None or lights.dim() not in (2, 3) or lights.shape[-1] != 6 or not 1 <= lights.shape[-2] <= abi.LIGHT_MAX:
+        raise ValueError(f"{what}: lights must be [L, 6] or [n_frames, L, 6] with 1 <= L <= {abi.LIGHT_MAX}" + _got(lights, "shape"))
     for name, t in pieces:
-        if t.dim() not in (1, 2) or t.shape[-1] != 3:
-            raise ValueError(f"light: {name} must be [3] or [n_frames, 3], got {tuple(t.shape)}")
+        if t is None or t.dim() not in (1, 2) or t.shape[-1] != 3:
+            raise ValueError(f"{what}: {name} must be [3] or [n_frames, 3]" + _got(t, "shape"))
     per_frame = lights.dim() == 3 or any(t.dim() == 2 for _, t in pieces)
     n = fs.n_frames if per_frame else 1
     n_l = lights.shape[-2]
     rows = [t.reshape(-1, 3) for _, t in pieces] + [lights.reshape(-1, 6 * n_l)]
     for (name, _), r in zip(pieces + [("lights", lights)], rows):
         if r.shape[0] not in (1, n):
-            raise ValueError(f"light: {name} has {r.shape[0]} frames, the set {fs.n_frames}")
+            raise ValueError(f"{what}: {name} has {r.shape[0]} frames, the set {fs.n_frames}")
     return torch.cat([r.expand(n, r.shape[1]) for r in rows], dim=1).to(torch.float32).contiguous()
+
+
+def light_params(fs, lights, eye, ka, ks):
+    """the parameter block of light / light_grad from its pieces, with torch ops (so gradients of the block flow back to the pieces):
+    lights [L, 6] or [n_frames, L, 6] (a light: pos[3], intensity[3]), eye, ka, ks [3] or [n_frames, 3] → [1, 9 + 6 L] when every piece
+    is shared by the frames, else [n_frames, 9 + 6 L] (per frame as soon as one of them is)"""
+    return _params(fs, "light", lights, [("eye", eye), ("ka", ka), ("ks", ks)])
 
 
 def _light_args(fs, nrm, pos, kd, par, p):
     """→ (nrm, pos, kd or None, par, n_lights, par_frames), checked and contiguous"""
-    shape = tuple(fs.interpolate_shape(3))
-    for name, t in (("nrm", nrm), ("pos", pos), ("kd", kd)):
-        if t is not None and (t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != shape):
-            raise ValueError(f"light: {name} must be a CUDA float32 tensor {shape}, got {tuple(t.shape)} {t.dtype}")
-    if par.dtype != torch.float32 or not par.is_cuda or par.dim() != 2 or par.shape[1] < 15 or (par.shape[1] - 9) % 6:
-        raise ValueError(f"light: par must be a CUDA float32 tensor [1 or n_frames, 9 + 6 L], got {tuple(par.shape)} {par.dtype}")
+    nrm, pos = _plane(fs, nrm, 3, "light: nrm"), _plane(fs, pos, 3, "light: pos")
+    kd = None if kd is None else _plane(fs, kd, 3, "light: kd")
+    if par is None or par.dtype != torch.float32 or not par.is_cuda or par.dim() != 2 or par.shape[1] < 15 or (par.shape[1] - 9) % 6:
+        raise ValueError("light: par must be a CUDA float32 tensor [1 or n_frames, 9 + 6 L]" + _got(par, "plain"))
     n_l = (par.shape[1] - 9) // 6
     if n_l > abi.LIGHT_MAX or par.shape[0] not in (1, fs.n_frames):
         raise ValueError(f"light: par of {par.shape[0]} frames and {n_l} lights; 1 or {fs.n_frames} frames and 1 .. {abi.LIGHT_MAX} lights are supported")
     if int(p) != p or not 1 <= p <= 256:
         raise ValueError(f"light: p must be an integer in 1 .. 256, got {p}")
-    return nrm.contiguous(), pos.contiguous(), None if kd is None else kd.contiguous(), par.contiguous(), n_l, par.shape[0]
+    return nrm, pos, kd, par.contiguous(), n_l, par.shape[0]
 
 
 def light_grad(fs, vis, nrm, pos, kd, par, p, gout, want_gnrm=True, want_gpos=True, want_gkd=True, want_gpar=True, stream=None):
@@ -909,18 +904,12 @@ def light_grad(fs, vis, nrm, pos, kd, par, p, gout, want_gnrm=True, want_gpos=Tr
     if not (want_gnrm or want_gpos or want_gkd or want_gpar):
         raise ValueError("light_grad: no gradient is asked for")
     nrm, pos, kd, par, n_l, par_frames = _light_args(fs, nrm, pos, kd, par, p)
-    gout = gout.contiguous()
-    if tuple(gout.shape) != tuple(nrm.shape) or gout.dtype != torch.float32:
-        raise ValueError(f"light_grad: gout must be float32 {tuple(nrm.shape)}, got {tuple(gout.shape)} {gout.dtype}")
+    gout = _gout(fs, gout, 3, "light_grad")
     gnrm, gpos, gkd = (torch.empty_like(nrm) if w else None for w in (want_gnrm, want_gpos, want_gkd))
-    gpar = work = None
-    work_bytes = 0
-    if want_gpar:
-        work_bytes = fs.light_work_bytes(n_l)
-        gpar, work = torch.empty_like(par), torch.empty(max(work_bytes // 4, 1), dtype=torch.float32, device=par.device)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    fs.light_grad(vis.data_ptr(), nrm.data_ptr(), pos.data_ptr(), ptr(kd), par.data_ptr(), n_l, par_frames, int(p), gout.data_ptr(), ptr(gnrm),
-                  ptr(gpos), ptr(gkd), ptr(gpar), ptr(work), work_bytes, abi.FUSED_CLEAR, _stream_ptr(stream))
+    work_bytes = fs.light_work_bytes(n_l) if want_gpar else 0
+    gpar, work = _reduced(par, work_bytes) if want_gpar else (None, None)
+    fs.light_grad(_vis_ptr(fs, vis, "light_grad"), nrm.data_ptr(), pos.data_ptr(), _ptr(kd), par.data_ptr(), n_l, par_frames, int(p), gout.data_ptr(),
+                  _ptr(gnrm), _ptr(gpos), _ptr(gkd), _ptr(gpar), _ptr(work), work_bytes, abi.FUSED_CLEAR, _stream_ptr(stream))
     return gnrm, gpos, gkd, gpar
 
 
@@ -929,8 +918,8 @@ class _Light(torch.autograd.Function):
     def forward(ctx, nrm, pos, kd, par, fs, vis, p, stream):
         nrm, pos, kd, par, n_l, par_frames = _light_args(fs, nrm, pos, kd, par, p)
         out = torch.empty(fs.interpolate_shape(3), dtype=torch.float32, device=nrm.device)
-        fs.light(vis.data_ptr(), nrm.data_ptr(), pos.data_ptr(), None if kd is None else kd.data_ptr(), par.data_ptr(), n_l, par_frames, int(p),
-                 out.data_ptr(), fs.interpolate_bytes(3), abi.FUSED_CLEAR, _stream_ptr(stream))
+        fs.light(_vis_ptr(fs, vis, "light"), nrm.data_ptr(), pos.data_ptr(), _ptr(kd), par.data_ptr(), n_l, par_frames, int(p), out.data_ptr(),
+                 fs.interpolate_bytes(3), abi.FUSED_CLEAR, _stream_ptr(stream))
         ctx.fs, ctx.vis, ctx.p, ctx.stream, ctx.has_kd = fs, vis, int(p), stream, kd is not None
         ctx.save_for_backward(nrm, pos, par, *([kd] if kd is not None else []))
         return out
@@ -939,12 +928,7 @@ class _Light(torch.autograd.Function):
     def backward(ctx, gout):
         nrm, pos, par = ctx.saved_tensors[:3]
         kd = ctx.saved_tensors[3] if ctx.has_kd else None
-        need = list(ctx.needs_input_grad[:4])
-        need[2] = need[2] and ctx.has_kd
-        grads = (None, None, None, None)
-        if any(need):  # one call, asking only for what is needed
-            grads = light_grad(ctx.fs, ctx.vis, nrm, pos, kd, par, ctx.p, gout, need[0], need[1], need[2], need[3], ctx.stream)
-        return (*grads, None, None, None, None)
+        return _backward(ctx, 4, lambda *need: light_grad(ctx.fs, ctx.vis, nrm, pos, kd, par, ctx.p, gout, *need, ctx.stream), (2, ctx.has_kd))
 
 
 def light(fs, vis, nrm, pos, kd, lights, eye, ka, ks, p, stream=None):
@@ -963,38 +947,21 @@ def microfacet_params(fs, lights, eye, amb):
     """the parameter block of microfacet / microfacet_grad from its pieces, with torch ops (so gradients of the block flow back to the
     pieces): lights [L, 6] or [n_frames, L, 6] (a light: pos[3], intensity[3]), eye, amb [3] or [n_frames, 3] → [1, 6 + 6 L] when every
     piece is shared by the frames, else [n_frames, 6 + 6 L] (per frame as soon as one of them is)"""
-    if lights.dim() not in (2, 3) or lights.shape[-1] != 6 or not 1 <= lights.shape[-2] <= abi.LIGHT_MAX:
-        raise ValueError(f"microfacet: lights must be [L, 6] or [n_frames, L, 6] with 1 <= L <= {abi.LIGHT_MAX}, got {tuple(lights.shape)}")
-    pieces = [("eye", eye), ("amb", amb)]
-    for name, t in pieces:
-        if t.dim() not in (1, 2) or t.shape[-1] != 3:
-            raise ValueError(f"microfacet: {name} must be [3] or [n_frames, 3], got {tuple(t.shape)}")
-    per_frame = lights.dim() == 3 or any(t.dim() == 2 for _, t in pieces)
-    n = fs.n_frames if per_frame else 1
-    n_l = lights.shape[-2]
-    rows = [t.reshape(-1, 3) for _, t in pieces] + [lights.reshape(-1, 6 * n_l)]
-    for (name, _), r in zip(pieces + [("lights", lights)], rows):
-        if r.shape[0] not in (1, n):
-            raise ValueError(f"microfacet: {name} has {r.shape[0]} frames, the set {fs.n_frames}")
-    return torch.cat([r.expand(n, r.shape[1]) for r in rows], dim=1).to(torch.float32).contiguous()
+    return _params(fs, "microfacet", lights, [("eye", eye), ("amb", amb)])
 
 
 def _microfacet_args(fs, nrm, pos, base, mat, par):
     """→ (nrm, pos, base or None, mat, par, n_lights, par_frames), checked and contiguous"""
-    shape, shape2 = tuple(fs.interpolate_shape(3)), tuple(fs.interpolate_shape(2))
-    for name, t, s in (("nrm", nrm, shape), ("pos", pos, shape), ("base", base, shape), ("mat", mat, shape2)):
-        if name == "base" and t is None:
-            continue
-        if t is None or t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != s:
-            raise ValueError(f"microfacet: {name} must be a CUDA float32 tensor {s}, got "
-                             f"{None if t is None else (tuple(t.shape), t.dtype)}")
-    if par.dtype != torch.float32 or not par.is_cuda or par.dim() != 2 or par.shape[1] < 12 or (par.shape[1] - 6) % 6:
-        raise ValueError(f"microfacet: par must be a CUDA float32 tensor [1 or n_frames, 6 + 6 L], got {tuple(par.shape)} {par.dtype}")
+    nrm, pos = _plane(fs, nrm, 3, "microfacet: nrm", got="pair"), _plane(fs, pos, 3, "microfacet: pos", got="pair")
+    base = None if base is None else _plane(fs, base, 3, "microfacet: base", got="pair")
+    mat = _plane(fs, mat, 2, "microfacet: mat", got="pair")
+    if par is None or par.dtype != torch.float32 or not par.is_cuda or par.dim() != 2 or par.shape[1] < 12 or (par.shape[1] - 6) % 6:
+        raise ValueError("microfacet: par must be a CUDA float32 tensor [1 or n_frames, 6 + 6 L]" + _got(par, "plain"))
     n_l = (par.shape[1] - 6) // 6
     if n_l > abi.LIGHT_MAX or par.shape[0] not in (1, fs.n_frames):
         raise ValueError(f"microfacet: par of {par.shape[0]} frames and {n_l} lights; 1 or {fs.n_frames} frames and 1 .. {abi.LIGHT_MAX} "
                          "lights are supported")
-    return nrm.contiguous(), pos.contiguous(), None if base is None else base.contiguous(), mat.contiguous(), par.contiguous(), n_l, par.shape[0]
+    return nrm, pos, base, mat, par.contiguous(), n_l, par.shape[0]
 
 
 def microfacet_grad(fs, vis, nrm, pos, base, mat, par, gout, want_gnrm=True, want_gpos=True, want_gbase=True, want_gmat=True, want_gpar=True,
@@ -1007,20 +974,14 @@ def microfacet_grad(fs, vis, nrm, pos, base, mat, par, gout, want_gnrm=True, wan
     if not (want_gnrm or want_gpos or want_gbase or want_gmat or want_gpar):
         raise ValueError("microfacet_grad: no gradient is asked for")
     nrm, pos, base, mat, par, n_l, par_frames = _microfacet_args(fs, nrm, pos, base, mat, par)
-    gout = gout.contiguous()
-    if tuple(gout.shape) != tuple(nrm.shape) or gout.dtype != torch.float32:
-        raise ValueError(f"microfacet_grad: gout must be float32 {tuple(nrm.shape)}, got {tuple(gout.shape)} {gout.dtype}")
+    gout = _gout(fs, gout, 3, "microfacet_grad")
     gnrm, gpos, gbase = (torch.empty_like(nrm) if w else None for w in (want_gnrm, want_gpos, want_gbase))
     gmat = torch.empty_like(mat) if want_gmat else None
-    gpar = work = None
-    work_bytes = 0
-    if want_gpar:
-        work_bytes = fs.microfacet_work_bytes(n_l)
-        gpar, work = torch.empty_like(par), torch.empty(max(work_bytes // 4, 1), dtype=torch.float32, device=par.device)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    fs.microfacet_grad(vis.data_ptr(), nrm.data_ptr(), pos.data_ptr(), ptr(base), mat.data_ptr(), par.data_ptr(), n_l, par_frames,
-                       gout.data_ptr(), ptr(gnrm), ptr(gpos), ptr(gbase), ptr(gmat), ptr(gpar), ptr(work), work_bytes, abi.FUSED_CLEAR,
-                       _stream_ptr(stream))
+    work_bytes = fs.microfacet_work_bytes(n_l) if want_gpar else 0
+    gpar, work = _reduced(par, work_bytes) if want_gpar else (None, None)
+    fs.microfacet_grad(_vis_ptr(fs, vis, "microfacet_grad"), nrm.data_ptr(), pos.data_ptr(), _ptr(base), mat.data_ptr(), par.data_ptr(), n_l,
+                       par_frames, gout.data_ptr(), _ptr(gnrm), _ptr(gpos), _ptr(gbase), _ptr(gmat), _ptr(gpar), _ptr(work), work_bytes,
+                       abi.FUSED_CLEAR, _stream_ptr(stream))
     return gnrm, gpos, gbase, gmat, gpar
 
 
@@ -1029,8 +990,8 @@ class _Microfacet(torch.autograd.Function):
     def forward(ctx, nrm, pos, base, mat, par, fs, vis, stream):
         nrm, pos, base, mat, par, n_l, par_frames = _microfacet_args(fs, nrm, pos, base, mat, par)
         out = torch.empty(fs.interpolate_shape(3), dtype=torch.float32, device=nrm.device)
-        fs.microfacet(vis.data_ptr(), nrm.data_ptr(), pos.data_ptr(), None if base is None else base.data_ptr(), mat.data_ptr(),
-                      par.data_ptr(), n_l, par_frames, out.data_ptr(), fs.interpolate_bytes(3), abi.FUSED_CLEAR, _stream_ptr(stream))
+        fs.microfacet(_vis_ptr(fs, vis, "microfacet"), nrm.data_ptr(), pos.data_ptr(), _ptr(base), mat.data_ptr(), par.data_ptr(), n_l,
+                      par_frames, out.data_ptr(), fs.interpolate_bytes(3), abi.FUSED_CLEAR, _stream_ptr(stream))
         ctx.fs, ctx.vis, ctx.stream, ctx.has_base = fs, vis, stream, base is not None
         ctx.save_for_backward(nrm, pos, mat, par, *([base] if base is not None else []))
         return out
@@ -1039,12 +1000,7 @@ class _Microfacet(torch.autograd.Function):
     def backward(ctx, gout):
         nrm, pos, mat, par = ctx.saved_tensors[:4]
         base = ctx.saved_tensors[4] if ctx.has_base else None
-        need = list(ctx.needs_input_grad[:5])
-        need[2] = need[2] and ctx.has_base
-        grads = (None, None, None, None, None)
-        if any(need):  # one call, asking only for what is needed
-            grads = microfacet_grad(ctx.fs, ctx.vis, nrm, pos, base, mat, par, gout, *need, ctx.stream)
-        return (*grads, None, None, None)
+        return _backward(ctx, 5, lambda *need: microfacet_grad(ctx.fs, ctx.vis, nrm, pos, base, mat, par, gout, *need, ctx.stream), (2, ctx.has_base))
 
 
 def microfacet(fs, vis, nrm, pos, base, mat, lights, eye, amb, stream=None):
@@ -1061,19 +1017,12 @@ def microfacet(fs, vis, nrm, pos, base, mat, lights, eye, amb, stream=None):
     return _Microfacet.apply(nrm, pos, base, mat, microfacet_params(fs, lights, eye, amb), fs, vis, stream)
 
 
-def _plane_check(what, name, t, shape):
-    if t is None or t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{what}: {name} must be a CUDA float32 tensor {tuple(shape)}, got {None if t is None else (tuple(t.shape), t.dtype)}")
-    return t.contiguous()
-
-
 def _reflect_args(fs, nrm, pos, eye):
     """→ (nrm, pos, eye [1 or n_frames, 3]), checked and contiguous"""
-    shape = fs.interpolate_shape(3)
-    nrm, pos = _plane_check("reflect", "nrm", nrm, shape), _plane_check("reflect", "pos", pos, shape)
-    if eye.dtype != torch.float32 or not eye.is_cuda or eye.dim() not in (1, 2) or eye.shape[-1] != 3 or \
+    nrm, pos = _plane(fs, nrm, 3, "reflect: nrm", got="pair"), _plane(fs, pos, 3, "reflect: pos", got="pair")
+    if eye is None or eye.dtype != torch.float32 or not eye.is_cuda or eye.dim() not in (1, 2) or eye.shape[-1] != 3 or \
             (eye.dim() == 2 and eye.shape[0] not in (1, fs.n_frames)):
-        raise ValueError(f"reflect: eye must be a CUDA float32 tensor [3] or [1 or {fs.n_frames}, 3], got {tuple(eye.shape)} {eye.dtype}")
+        raise ValueError(f"reflect: eye must be a CUDA float32 tensor [3] or [1 or {fs.n_frames}, 3]" + _got(eye, "plain"))
     return nrm, pos, eye.reshape(-1, 3).contiguous()
 
 
@@ -1084,22 +1033,22 @@ def reflect_grad(fs, vis, nrm, pos, eye, gout, want_gnrm=True, want_gpos=True, s
     if not (want_gnrm or want_gpos):
         raise ValueError("reflect_grad: no gradient is asked for")
     nrm, pos, eye = _reflect_args(fs, nrm, pos, eye)
-    gout = _plane_check("reflect_grad", "gout", gout, fs.interpolate_shape(4))
+    gout = _plane(fs, gout, 4, "reflect_grad: gout", got="pair")
     gnrm, gpos = (torch.empty_like(nrm) if w else None for w in (want_gnrm, want_gpos))
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    fs.reflect_grad(vis.data_ptr(), nrm.data_ptr(), pos.data_ptr(), eye.data_ptr(), eye.shape[0], gout.data_ptr(), ptr(gnrm), ptr(gpos),
-                    abi.FUSED_CLEAR, _stream_ptr(stream))
+    fs.reflect_grad(_vis_ptr(fs, vis, "reflect_grad"), nrm.data_ptr(), pos.data_ptr(), eye.data_ptr(), eye.shape[0], gout.data_ptr(), _ptr(gnrm),
+                    _ptr(gpos), abi.FUSED_CLEAR, _stream_ptr(stream))
     return gnrm, gpos
 
 
 class _Reflect(torch.autograd.Function):
     @staticmethod
     def forward(ctx, nrm, pos, eye, fs, vis, stream):
-        ctx.eye_shape = tuple(eye.shape)
+        eye_shape = None if eye is None else tuple(eye.shape)
         nrm, pos, eye = _reflect_args(fs, nrm, pos, eye)
+        ctx.eye_shape = eye_shape
         out = torch.empty(fs.interpolate_shape(4), dtype=torch.float32, device=nrm.device)
-        fs.reflect(vis.data_ptr(), nrm.data_ptr(), pos.data_ptr(), eye.data_ptr(), eye.shape[0], out.data_ptr(), fs.interpolate_bytes(4),
-                   abi.FUSED_CLEAR, _stream_ptr(stream))
+        fs.reflect(_vis_ptr(fs, vis, "reflect"), nrm.data_ptr(), pos.data_ptr(), eye.data_ptr(), eye.shape[0], out.data_ptr(),
+                   fs.interpolate_bytes(4), abi.FUSED_CLEAR, _stream_ptr(stream))
         ctx.fs, ctx.vis, ctx.stream = fs, vis, stream
         ctx.save_for_backward(nrm, pos, eye)
         return out
@@ -1134,21 +1083,19 @@ def brdf_table(ctx_or_fs, n, m=64, stream=None, device=None):
     ctx = getattr(ctx_or_fs, "ctx", ctx_or_fs)
     if not 2 <= int(n) <= abi.BRDF_TABLE_MAX or not 1 <= int(m) <= 256:
         raise ValueError(f"brdf_table: 2 <= n <= {abi.BRDF_TABLE_MAX} and 1 <= m <= 256, got n {n}, m {m}")
-    tab = torch.empty((int(n), int(n), 2), dtype=torch.float32, device=device or "cuda")
+    tab = _on_device(torch.empty((int(n), int(n), 2), dtype=torch.float32, device=device or "cuda"), "brdf_table: tab")
     ctx.brdf_table(tab.data_ptr(), tab.numel() * 4, int(n), int(m), _stream_ptr(stream))
     return tab
 
 
 def _ibl_args(fs, base, mat, nv, irr, spec, tab):
     """→ (base or None, mat, nv, irr, spec, tab, n), checked and contiguous"""
-    s3, s2, s1 = fs.interpolate_shape(3), fs.interpolate_shape(2), fs.interpolate_shape(1)
-    base = None if base is None else _plane_check("ibl", "base", base, s3)
-    mat, nv = _plane_check("ibl", "mat", mat, s2), _plane_check("ibl", "nv", nv, s1)
-    irr, spec = _plane_check("ibl", "irr", irr, s3), _plane_check("ibl", "spec", spec, s3)
+    base = None if base is None else _plane(fs, base, 3, "ibl: base", got="pair")
+    mat, nv = _plane(fs, mat, 2, "ibl: mat", got="pair"), _plane(fs, nv, 1, "ibl: nv", got="pair")
+    irr, spec = _plane(fs, irr, 3, "ibl: irr", got="pair"), _plane(fs, spec, 3, "ibl: spec", got="pair")
     if tab is None or tab.dtype != torch.float32 or not tab.is_cuda or tab.dim() != 3 or tab.shape[0] != tab.shape[1] or tab.shape[2] != 2 or \
             not 2 <= tab.shape[0] <= abi.BRDF_TABLE_MAX:
-        raise ValueError(f"ibl: tab must be a CUDA float32 tensor [n, n, 2] with 2 <= n <= {abi.BRDF_TABLE_MAX}, got "
-                         f"{None if tab is None else (tuple(tab.shape), tab.dtype)}")
+        raise ValueError(f"ibl: tab must be a CUDA float32 tensor [n, n, 2] with 2 <= n <= {abi.BRDF_TABLE_MAX}" + _got(tab, "pair"))
     return base, mat, nv, irr, spec, tab.contiguous(), tab.shape[0]
 
 
@@ -1161,13 +1108,12 @@ def ibl_grad(fs, vis, base, mat, nv, irr, spec, tab, gout, want_gbase=True, want
     if not (want_gbase or want_gmat or want_gnv or want_girr or want_gspec or want_gtab):
         raise ValueError("ibl_grad: no gradient is asked for")
     base, mat, nv, irr, spec, tab, n = _ibl_args(fs, base, mat, nv, irr, spec, tab)
-    gout = _plane_check("ibl_grad", "gout", gout, fs.interpolate_shape(3))
+    gout = _plane(fs, gout, 3, "ibl_grad: gout", got="pair")
     gbase, gmat, gnv, girr, gspec = (torch.empty_like(t) if w else None for t, w in
                                      ((irr, want_gbase), (mat, want_gmat), (nv, want_gnv), (irr, want_girr), (spec, want_gspec)))
     gtab = torch.zeros_like(tab) if want_gtab else None
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    fs.ibl_grad(vis.data_ptr(), ptr(base), mat.data_ptr(), nv.data_ptr(), irr.data_ptr(), spec.data_ptr(), tab.data_ptr(), n, gout.data_ptr(),
-                ptr(gbase), ptr(gmat), ptr(gnv), ptr(girr), ptr(gspec), ptr(gtab), abi.FUSED_CLEAR, _stream_ptr(stream))
+    fs.ibl_grad(_vis_ptr(fs, vis, "ibl_grad"), _ptr(base), mat.data_ptr(), nv.data_ptr(), irr.data_ptr(), spec.data_ptr(), tab.data_ptr(), n,
+                gout.data_ptr(), _ptr(gbase), _ptr(gmat), _ptr(gnv), _ptr(girr), _ptr(gspec), _ptr(gtab), abi.FUSED_CLEAR, _stream_ptr(stream))
     return gbase, gmat, gnv, girr, gspec, gtab
 
 
@@ -1176,8 +1122,8 @@ class _Ibl(torch.autograd.Function):
     def forward(ctx, base, mat, nv, irr, spec, tab, fs, vis, stream):
         base, mat, nv, irr, spec, tab, n = _ibl_args(fs, base, mat, nv, irr, spec, tab)
         out = torch.empty(fs.interpolate_shape(3), dtype=torch.float32, device=mat.device)
-        fs.ibl(vis.data_ptr(), None if base is None else base.data_ptr(), mat.data_ptr(), nv.data_ptr(), irr.data_ptr(), spec.data_ptr(),
-               tab.data_ptr(), n, out.data_ptr(), fs.interpolate_bytes(3), abi.FUSED_CLEAR, _stream_ptr(stream))
+        fs.ibl(_vis_ptr(fs, vis, "ibl"), _ptr(base), mat.data_ptr(), nv.data_ptr(), irr.data_ptr(), spec.data_ptr(), tab.data_ptr(), n,
+               out.data_ptr(), fs.interpolate_bytes(3), abi.FUSED_CLEAR, _stream_ptr(stream))
         ctx.fs, ctx.vis, ctx.stream, ctx.has_base = fs, vis, stream, base is not None
         ctx.save_for_backward(mat, nv, irr, spec, tab, *([base] if base is not None else []))
         return out
@@ -1186,12 +1132,7 @@ class _Ibl(torch.autograd.Function):
     def backward(ctx, gout):
         mat, nv, irr, spec, tab = ctx.saved_tensors[:5]
         base = ctx.saved_tensors[5] if ctx.has_base else None
-        need = list(ctx.needs_input_grad[:6])
-        need[0] = need[0] and ctx.has_base
-        grads = (None,) * 6
-        if any(need):  # one call, asking only for what is needed
-            grads = ibl_grad(ctx.fs, ctx.vis, base, mat, nv, irr, spec, tab, gout, *need, ctx.stream)
-        return (*grads, None, None, None)
+        return _backward(ctx, 6, lambda *need: ibl_grad(ctx.fs, ctx.vis, base, mat, nv, irr, spec, tab, gout, *need, ctx.stream), (0, ctx.has_base))
 
 
 def ibl(fs, vis, base, mat, nv, irr, spec, tab, stream=None):
@@ -1208,11 +1149,7 @@ def ibl(fs, vis, base, mat, nv, irr, spec, tab, stream=None):
 
 def _normal_map_args(fs, nrm, tan, m):
     """→ (nrm, tan, m), checked and contiguous"""
-    for name, t, n in (("nrm", nrm, 3), ("tan", tan, 4), ("m", m, 3)):
-        shape = tuple(fs.interpolate_shape(n))
-        if t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != shape:
-            raise ValueError(f"normal_map: {name} must be a CUDA float32 tensor {shape}, got {tuple(t.shape)} {t.dtype}")
-    return nrm.contiguous(), tan.contiguous(), m.contiguous()
+    return _plane(fs, nrm, 3, "normal_map: nrm"), _plane(fs, tan, 4, "normal_map: tan"), _plane(fs, m, 3, "normal_map: m")
 
 
 def normal_map_grad(fs, vis, nrm, tan, m, gout, want_gnrm=True, want_gtan=True, want_gm=True, stream=None):
@@ -1222,13 +1159,10 @@ def normal_map_grad(fs, vis, nrm, tan, m, gout, want_gnrm=True, want_gtan=True, 
     if not (want_gnrm or want_gtan or want_gm):
         raise ValueError("normal_map_grad: no gradient is asked for")
     nrm, tan, m = _normal_map_args(fs, nrm, tan, m)
-    gout = gout.contiguous()
-    if tuple(gout.shape) != tuple(nrm.shape) or gout.dtype != torch.float32:
-        raise ValueError(f"normal_map_grad: gout must be float32 {tuple(nrm.shape)}, got {tuple(gout.shape)} {gout.dtype}")
+    gout = _gout(fs, gout, 3, "normal_map_grad")
     gnrm, gtan, gm = (torch.empty_like(t) if w else None for t, w in ((nrm, want_gnrm), (tan, want_gtan), (m, want_gm)))
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    fs.normal_map_grad(vis.data_ptr(), nrm.data_ptr(), tan.data_ptr(), m.data_ptr(), gout.data_ptr(), ptr(gnrm), ptr(gtan), ptr(gm),
-                       abi.FUSED_CLEAR, _stream_ptr(stream))
+    fs.normal_map_grad(_vis_ptr(fs, vis, "normal_map_grad"), nrm.data_ptr(), tan.data_ptr(), m.data_ptr(), gout.data_ptr(), _ptr(gnrm), _ptr(gtan),
+                       _ptr(gm), abi.FUSED_CLEAR, _stream_ptr(stream))
     return gnrm, gtan, gm
 
 
@@ -1237,8 +1171,8 @@ class _NormalMap(torch.autograd.Function):
     def forward(ctx, nrm, tan, m, fs, vis, stream):
         nrm, tan, m = _normal_map_args(fs, nrm, tan, m)
         out = torch.empty(fs.interpolate_shape(3), dtype=torch.float32, device=nrm.device)
-        fs.normal_map(vis.data_ptr(), nrm.data_ptr(), tan.data_ptr(), m.data_ptr(), out.data_ptr(), fs.interpolate_bytes(3), abi.FUSED_CLEAR,
-                      _stream_ptr(stream))
+        fs.normal_map(_vis_ptr(fs, vis, "normal_map"), nrm.data_ptr(), tan.data_ptr(), m.data_ptr(), out.data_ptr(), fs.interpolate_bytes(3),
+                      abi.FUSED_CLEAR, _stream_ptr(stream))
         ctx.fs, ctx.vis, ctx.stream = fs, vis, stream
         ctx.save_for_backward(nrm, tan, m)
         return out
@@ -1246,11 +1180,7 @@ class _NormalMap(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         nrm, tan, m = ctx.saved_tensors
-        need = ctx.needs_input_grad[:3]
-        grads = (None, None, None)
-        if any(need):  # one call, asking only for what is needed
-            grads = normal_map_grad(ctx.fs, ctx.vis, nrm, tan, m, gout, need[0], need[1], need[2], ctx.stream)
-        return (*grads, None, None, None)
+        return _backward(ctx, 3, lambda *need: normal_map_grad(ctx.fs, ctx.vis, nrm, tan, m, gout, *need, ctx.stream))
 
 
 def normal_map(fs, vis, nrm, tan, m, stream=None):
@@ -1271,13 +1201,13 @@ def interpolate_deriv(fs, vis, attr, stream=None):
     each pixel's owner, from the set's own positions (FrameSet.interpolate_deriv); zeros where nobody owns the pixel.  For a [T, 3, 2]
     uv attribute these are the planes ux, uy, vx, vy texture_mip takes.  Not differentiable: the planes only select a mip level.
     stream: a raw stream handle, None = torch's current stream."""
-    attr = attr.detach().contiguous()
     attr_frames, tris, n_ch = _attr_dims(fs, attr)
+    attr = attr.detach().contiguous()
     if n_ch > abi.ATTR_MAX_CH // 2:
         raise ValueError(f"interpolate_deriv: {n_ch} channels; at most {abi.ATTR_MAX_CH // 2} are supported")
     out = torch.empty(fs.interpolate_shape(2 * n_ch), dtype=torch.float32, device=attr.device)
-    fs.interpolate_deriv(vis.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris, out.data_ptr(), fs.interpolate_bytes(2 * n_ch), abi.FUSED_CLEAR,
-                         _stream_ptr(stream))
+    fs.interpolate_deriv(_vis_ptr(fs, vis, "interpolate_deriv"), attr.data_ptr(), n_ch, attr_frames, tris, out.data_ptr(),
+                         fs.interpolate_bytes(2 * n_ch), abi.FUSED_CLEAR, _stream_ptr(stream))
     return out
 
 
@@ -1299,8 +1229,8 @@ def mip_build(ctx_or_fs, tex, n_levels=None, stream=None):
     above it, deterministic (Context.mip_build).  ctx_or_fs: the Context, or a FrameSet of it."""
     from . import mip_bytes
     ctx = getattr(ctx_or_fs, "ctx", ctx_or_fs)
-    if tex.dtype != torch.float32 or not tex.is_cuda or tex.dim() not in (3, 4):
-        raise ValueError(f"mip_build: tex must be a CUDA float32 tensor [H, W, C] or [frames, H, W, C], got {tuple(tex.shape)} {tex.dtype}")
+    if tex is None or tex.dtype != torch.float32 or not tex.is_cuda or tex.dim() not in (3, 4):
+        raise ValueError("mip_build: tex must be a CUDA float32 tensor [H, W, C] or [frames, H, W, C]" + _got(tex, "plain"))
     tex = tex.contiguous()
     tex_frames, h, w, n_ch, n_levels = _mip_dims(tuple(tex.shape), n_levels)
     nbytes = mip_bytes(w, h, n_ch, tex_frames, n_levels)
@@ -1326,9 +1256,7 @@ def mip_views(mip, tex_shape, n_levels=None):
 def _uvd_arg(fs, uvd, n_levels):
     if n_levels == 1 and uvd is None:
         return None
-    if uvd is None or uvd.dtype != torch.float32 or not uvd.is_cuda or tuple(uvd.shape) != tuple(fs.interpolate_shape(4)):
-        raise ValueError(f"texture_mip: uvd must be a CUDA float32 tensor {fs.interpolate_shape(4)}")
-    return uvd.detach().contiguous()
+    return _plane(fs, uvd, 4, "texture_mip: uvd", got="").detach()
 
 
 def texture_mip_grad(fs, vis, tex, uv, uvd, gout, wrap=False, n_levels=None, mip=None, want_gtex=True, want_guv=True, fold=True, stream=None):
@@ -1340,22 +1268,24 @@ def texture_mip_grad(fs, vis, tex, uv, uvd, gout, wrap=False, n_levels=None, mip
     if not want_gtex and not want_guv:
         raise ValueError("texture_mip_grad: neither gtex nor guv is asked for")
     from . import mip_bytes
-    tex, uv, gout = tex.detach().contiguous(), _uv_arg(fs, uv), gout.contiguous()
+    uv = _plane(fs, uv, 2, "texture: uv")
     tex_frames, h, w, n_ch = _tex_dims(fs, tex)
+    tex = tex.detach().contiguous()
     n_levels = _mip_dims(tuple(tex.shape), n_levels)[4]
     uvd = _uvd_arg(fs, uvd, n_levels)
-    if tuple(gout.shape) != tuple(fs.interpolate_shape(n_ch)) or gout.dtype != torch.float32:
-        raise ValueError(f"texture_mip_grad: gout must be float32 {fs.interpolate_shape(n_ch)}, got {tuple(gout.shape)} {gout.dtype}")
+    gout = _gout(fs, gout, n_ch, "texture_mip_grad")
     s = _stream_ptr(stream)
     nbytes = mip_bytes(w, h, n_ch, tex_frames, n_levels)
+    if n_levels > 1 and mip is not None and (mip.dtype != torch.float32 or not mip.is_cuda or mip.dim() != 1 or mip.numel() * 4 != nbytes):
+        raise ValueError(f"texture_mip_grad: mip must be a flat CUDA float32 tensor of {nbytes // 4} elements (mip_build's layout)")
+    vis_ptr = _vis_ptr(fs, vis, "texture_mip_grad")  # (before the pyramid is built: a refused call launches nothing)
     if want_guv and n_levels > 1 and mip is None:
         mip = mip_build(fs, tex, n_levels, stream)
     gtex = torch.zeros_like(tex) if want_gtex else None
     gmip = torch.zeros((nbytes // 4,), dtype=torch.float32, device=tex.device) if want_gtex and n_levels > 1 else None
     guv = torch.empty_like(uv) if want_guv else None
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    fs.texture_mip_grad(vis.data_ptr(), uv.data_ptr(), ptr(uvd), gout.data_ptr(), tex.data_ptr(), ptr(mip) if n_levels > 1 else None, w, h, n_ch,
-                        tex_frames, abi.TEX_WRAP if wrap else abi.TEX_CLAMP, n_levels, ptr(gtex), ptr(gmip), ptr(guv), abi.FUSED_CLEAR, s)
+    fs.texture_mip_grad(vis_ptr, uv.data_ptr(), _ptr(uvd), gout.data_ptr(), tex.data_ptr(), _ptr(mip) if n_levels > 1 else None, w, h, n_ch,
+                        tex_frames, abi.TEX_WRAP if wrap else abi.TEX_CLAMP, n_levels, _ptr(gtex), _ptr(gmip), _ptr(guv), abi.FUSED_CLEAR, s)
     if not fold:
         return gtex, gmip, guv
     if gmip is not None:
@@ -1366,28 +1296,24 @@ def texture_mip_grad(fs, vis, tex, uv, uvd, gout, wrap=False, n_levels=None, mip
 class _TextureMip(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tex, uv, fs, vis, uvd, wrap, n_levels, stream):
-        tex, uv = tex.contiguous(), _uv_arg(fs, uv)
+        uv = _plane(fs, uv, 2, "texture: uv")
         tex_frames, h, w, n_ch = _tex_dims(fs, tex)
+        tex = tex.contiguous()
         n_levels = _mip_dims(tuple(tex.shape), n_levels)[4]
-        uvd = _uvd_arg(fs, uvd, n_levels)
+        uvd, vis_ptr = _uvd_arg(fs, uvd, n_levels), _vis_ptr(fs, vis, "texture_mip")  # (before the pyramid is built)
         mip = mip_build(fs, tex, n_levels, stream) if n_levels > 1 else None
         out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=tex.device)
-        fs.texture_mip(vis.data_ptr(), uv.data_ptr(), uvd.data_ptr() if uvd is not None else None, tex.data_ptr(), w, h, n_ch, tex_frames,
-                       abi.TEX_WRAP if wrap else abi.TEX_CLAMP, mip.data_ptr() if mip is not None else None, n_levels, out.data_ptr(),
-                       fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR, _stream_ptr(stream))
+        fs.texture_mip(vis_ptr, uv.data_ptr(), _ptr(uvd), tex.data_ptr(), w, h, n_ch, tex_frames, abi.TEX_WRAP if wrap else abi.TEX_CLAMP, _ptr(mip),
+                       n_levels, out.data_ptr(), fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR, _stream_ptr(stream))
         ctx.fs, ctx.vis, ctx.wrap, ctx.n_levels, ctx.stream, ctx.uvd, ctx.mip = fs, vis, wrap, n_levels, stream, uvd, mip
         ctx.save_for_backward(tex, uv)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        tex, uv = ctx.saved_tensors
-        need_tex, need_uv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gtex = guv = None
-        if need_tex or need_uv:  # one texture_mip_grad call, asking only for what is needed, then one fold into tex.grad
-            gtex, guv = texture_mip_grad(ctx.fs, ctx.vis, tex, uv, ctx.uvd, gout, ctx.wrap, ctx.n_levels, ctx.mip, need_tex, need_uv, True,
-                                         ctx.stream)
-        return gtex, guv, None, None, None, None, None, None
+        tex, uv = ctx.saved_tensors  # (one texture_mip_grad call, then its one fold into tex.grad)
+        return _backward(ctx, 2, lambda *need: texture_mip_grad(ctx.fs, ctx.vis, tex, uv, ctx.uvd, gout, ctx.wrap, ctx.n_levels, ctx.mip, *need, True,
+                                                                ctx.stream))
 
 
 def texture_mip(fs, vis, tex, uv, uvd, wrap=False, n_levels=None, stream=None):
@@ -1421,8 +1347,8 @@ def cube_mip_build(ctx_or_fs, cube, n_levels=None, stream=None):
     its own, deterministic (Context.cube_mip_build).  ctx_or_fs: the Context, or a FrameSet of it."""
     from . import cube_mip_bytes
     ctx = getattr(ctx_or_fs, "ctx", ctx_or_fs)
-    if cube.dtype != torch.float32 or not cube.is_cuda:
-        raise ValueError(f"cube_mip_build: cube must be a CUDA float32 tensor, got {tuple(cube.shape)} {cube.dtype}")
+    if cube is None or cube.dtype != torch.float32 or not cube.is_cuda:
+        raise ValueError("cube_mip_build: cube must be a CUDA float32 tensor" + _got(cube, "plain"))
     cube = cube.contiguous()
     tex_frames, n, n_ch, n_levels = _cube_mip_dims(tuple(cube.shape), n_levels)
     nbytes = cube_mip_bytes(n, n_ch, tex_frames, n_levels)
@@ -1448,9 +1374,7 @@ def cube_mip_views(mip, cube_shape, n_levels=None):
 def _lam_arg(fs, lam, n_levels):
     if n_levels == 1 and lam is None:
         return None
-    if lam is None or lam.dtype != torch.float32 or not lam.is_cuda or tuple(lam.shape) != tuple(fs.interpolate_shape(1)):
-        raise ValueError(f"texture_cube_mip: lam must be a CUDA float32 tensor {fs.interpolate_shape(1)}")
-    return lam.contiguous()
+    return _plane(fs, lam, 1, "texture_cube_mip: lam", got="")
 
 
 def _cube_mip_arg(mip, n, n_ch, tex_frames, n_levels):
@@ -1467,13 +1391,10 @@ def cube_level(fs, vis, dirs, dird, n, n_levels, stream=None):
     for a cube of n x n faces with n_levels levels → lam [n_frames, 1, rows, W] float32 (FrameSet.cube_level; include/srz.h states
     the rule), zeros where nobody owns the pixel or its direction is not sampled.  Not differentiable: the footprint level is held
     fixed.  stream: a raw stream handle, None = torch's current stream."""
-    dirs = _dirs_arg(fs, dirs.detach())
-    if dird.dtype != torch.float32 or not dird.is_cuda or tuple(dird.shape) != tuple(fs.interpolate_shape(6)):
-        raise ValueError(f"cube_level: dird must be a CUDA float32 tensor {fs.interpolate_shape(6)}, got {tuple(dird.shape)} {dird.dtype}")
-    dird = dird.detach().contiguous()
+    dirs, dird = _plane(fs, dirs, 3, "texture_cube: dirs").detach(), _plane(fs, dird, 6, "cube_level: dird").detach()
     out = torch.empty(fs.interpolate_shape(1), dtype=torch.float32, device=dirs.device)
-    fs.cube_level(vis.data_ptr(), dirs.data_ptr(), dird.data_ptr(), n, n_levels, out.data_ptr(), fs.interpolate_bytes(1), abi.FUSED_CLEAR,
-                  _stream_ptr(stream))
+    fs.cube_level(_vis_ptr(fs, vis, "cube_level"), dirs.data_ptr(), dird.data_ptr(), n, n_levels, out.data_ptr(), fs.interpolate_bytes(1),
+                  abi.FUSED_CLEAR, _stream_ptr(stream))
     return out
 
 
@@ -1489,26 +1410,27 @@ def texture_cube_mip_grad(fs, vis, cube, dirs, lam, gout, n_levels=None, mip=Non
     if not want_gtex and not want_gdir and not want_glam:
         raise ValueError("texture_cube_mip_grad: no gradient is asked for")
     from . import cube_mip_bytes
-    cube, dirs, gout = cube.detach().contiguous(), _dirs_arg(fs, dirs.detach()), gout.contiguous()
+    dirs = _plane(fs, dirs, 3, "texture_cube: dirs").detach()
     tex_frames, n, n_ch = _cube_dims(fs, cube)
+    cube = cube.detach().contiguous()
     n_levels = _cube_mip_dims(tuple(cube.shape), n_levels)[3]
     lam = _lam_arg(fs, None if lam is None else lam.detach(), n_levels)
-    if tuple(gout.shape) != tuple(fs.interpolate_shape(n_ch)) or gout.dtype != torch.float32:
-        raise ValueError(f"texture_cube_mip_grad: gout must be float32 {fs.interpolate_shape(n_ch)}, got {tuple(gout.shape)} {gout.dtype}")
+    gout = _plane(fs, gout, n_ch, "texture_cube_mip_grad: gout", "float32 {shape}")
     s = _stream_ptr(stream)
     nbytes = cube_mip_bytes(n, n_ch, tex_frames, n_levels)
-    if n_levels > 1:
-        if mip is not None:
-            mip = _cube_mip_arg(mip.detach(), n, n_ch, tex_frames, n_levels)
-        elif want_gdir or want_glam:
-            mip = cube_mip_build(fs, cube, n_levels, stream)
+    if n_levels > 1 and mip is not None:
+        mip = _cube_mip_arg(mip.detach(), n, n_ch, tex_frames, n_levels)
+    # (gout's home and vis after the caller's pyramid, whose check came first, and before one is built: a refused call launches nothing)
+    _on_device(gout, "texture_cube_mip_grad: gout")
+    vis_ptr = _vis_ptr(fs, vis, "texture_cube_mip_grad")
+    if n_levels > 1 and mip is None and (want_gdir or want_glam):
+        mip = cube_mip_build(fs, cube, n_levels, stream)
     gtex = torch.zeros_like(cube) if want_gtex else None
     gmip = torch.zeros((nbytes // 4,), dtype=torch.float32, device=cube.device) if want_gtex and n_levels > 1 else None
     gdir = torch.empty_like(dirs) if want_gdir else None
     glam = torch.empty(fs.interpolate_shape(1), dtype=torch.float32, device=cube.device) if want_glam else None
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    fs.texture_cube_mip_grad(vis.data_ptr(), dirs.data_ptr(), ptr(lam), gout.data_ptr(), cube.data_ptr(), ptr(mip) if n_levels > 1 else None, n, n_ch,
-                             tex_frames, n_levels, ptr(gtex), ptr(gmip), ptr(gdir), ptr(glam), abi.FUSED_CLEAR, s)
+    fs.texture_cube_mip_grad(vis_ptr, dirs.data_ptr(), _ptr(lam), gout.data_ptr(), cube.data_ptr(), _ptr(mip) if n_levels > 1 else None, n, n_ch,
+                             tex_frames, n_levels, _ptr(gtex), _ptr(gmip), _ptr(gdir), _ptr(glam), abi.FUSED_CLEAR, s)
     if not fold:
         return gtex, gmip, gdir, glam
     if gmip is not None:
@@ -1519,21 +1441,19 @@ def texture_cube_mip_grad(fs, vis, cube, dirs, lam, gout, n_levels=None, mip=Non
 class _TextureCubeMip(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cube, dirs, lam, mip, fs, vis, n_levels, stream):
-        cube, dirs = cube.contiguous(), _dirs_arg(fs, dirs)
+        dirs = _plane(fs, dirs, 3, "texture_cube: dirs")
         tex_frames, n, n_ch = _cube_dims(fs, cube)
+        cube = cube.contiguous()
         n_levels = _cube_mip_dims(tuple(cube.shape), n_levels)[3]
         lam = _lam_arg(fs, lam, n_levels)
         own_mip = mip is not None  # the caller's pyramid: an input with a gradient of its own, no fold
-        if n_levels == 1:
-            mip_ = None
-        elif own_mip:
-            mip_ = _cube_mip_arg(mip, n, n_ch, tex_frames, n_levels)
-        else:
+        mip_ = _cube_mip_arg(mip, n, n_ch, tex_frames, n_levels) if own_mip and n_levels > 1 else None
+        vis_ptr = _vis_ptr(fs, vis, "texture_cube_mip")  # (before the pyramid is built: a refused call launches nothing)
+        if n_levels > 1 and not own_mip:
             mip_ = cube_mip_build(fs, cube, n_levels, stream)
         out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=cube.device)
-        fs.texture_cube_mip(vis.data_ptr(), dirs.data_ptr(), lam.data_ptr() if lam is not None else None, cube.data_ptr(), n, n_ch, tex_frames,
-                            mip_.data_ptr() if mip_ is not None else None, n_levels, out.data_ptr(), fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR,
-                            _stream_ptr(stream))
+        fs.texture_cube_mip(vis_ptr, dirs.data_ptr(), _ptr(lam), cube.data_ptr(), n, n_ch, tex_frames, _ptr(mip_), n_levels, out.data_ptr(),
+                            fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR, _stream_ptr(stream))
         ctx.fs, ctx.vis, ctx.n_levels, ctx.stream, ctx.own_mip, ctx.mip, ctx.lam = fs, vis, n_levels, stream, own_mip, mip_, lam
         ctx.save_for_backward(cube, dirs)
         return out
@@ -1569,8 +1489,9 @@ def texture_cube_mip(fs, vis, cube, dirs, lam, n_levels=None, mip=None, stream=N
 
 
 def _prefilter_dims(cube, what):
-    if cube.dtype != torch.float32 or not cube.is_cuda or cube.dim() not in (4, 5) or cube.shape[-4] != 6 or cube.shape[-3] != cube.shape[-2]:
-        raise ValueError(f"{what}: a cube is a CUDA float32 tensor [6, N, N, C] or [frames, 6, N, N, C], got {tuple(cube.shape)} {cube.dtype}")
+    if cube is None or cube.dtype != torch.float32 or not cube.is_cuda or cube.dim() not in (4, 5) or cube.shape[-4] != 6 or \
+            cube.shape[-3] != cube.shape[-2]:
+        raise ValueError(f"{what}: a cube is a CUDA float32 tensor [6, N, N, C] or [frames, 6, N, N, C]" + _got(cube, "plain"))
     return (cube.shape[0] if cube.dim() == 5 else 1), cube.shape[-2], cube.shape[-1]
 
 
@@ -1579,8 +1500,8 @@ def _prefilter_call(ctx, src, n_dst, kind, roughness, cmin, dst, den, stream):
     frames, n_src, n_ch = _prefilter_dims(src, "cube_prefilter")
     nbytes = ctx.cube_prefilter_work_bytes(n_src, n_dst, n_ch, frames)
     work = torch.empty((max(nbytes, 16) // 4,), dtype=torch.float32, device=src.device)
-    ctx.cube_prefilter(src.data_ptr(), n_src, dst.data_ptr(), n_dst, n_ch, frames, kind, roughness, cmin, den.data_ptr() if den is not None else None,
-                       work.data_ptr(), nbytes, _stream_ptr(stream))
+    ctx.cube_prefilter(src.data_ptr(), n_src, dst.data_ptr(), n_dst, n_ch, frames, kind, roughness, cmin, _ptr(den), work.data_ptr(), nbytes,
+                       _stream_ptr(stream))
 
 
 def cube_prefilter_grad(ctx_or_fs, gdst, den, n_src, kind, roughness=1.0, cmin=0.0, stream=None, out=None):
@@ -1588,15 +1509,15 @@ def cube_prefilter_grad(ctx_or_fs, gdst, den, n_src, kind, roughness=1.0, cmin=0
     [6, n_out, n_out] as the forward kept it → the gradient of the source cube, [..., 6, n_src, n_src, C] — the exact transpose as a
     gather, bit-reproducible.  out: a contiguous tensor of that shape to write instead of a fresh one."""
     ctx = getattr(ctx_or_fs, "ctx", ctx_or_fs)
-    gdst = gdst.contiguous()
     frames, n_dst, n_ch = _prefilter_dims(gdst, "cube_prefilter_grad")
-    if den.dtype != torch.float32 or not den.is_cuda or tuple(den.shape) != (6, n_dst, n_dst):
-        raise ValueError(f"cube_prefilter_grad: den must be a CUDA float32 tensor {(6, n_dst, n_dst)}, got {tuple(den.shape)} {den.dtype}")
-    den = den.contiguous()
+    if den is None or den.dtype != torch.float32 or not den.is_cuda or tuple(den.shape) != (6, n_dst, n_dst):
+        raise ValueError(f"cube_prefilter_grad: den must be a CUDA float32 tensor {(6, n_dst, n_dst)}" + _got(den, "plain"))
+    gdst, den = gdst.contiguous(), den.contiguous()
     shape = tuple(gdst.shape[:-3]) + (n_src, n_src, n_ch)
     gsrc = torch.empty(shape, dtype=torch.float32, device=gdst.device) if out is None else out
     if tuple(gsrc.shape) != shape or gsrc.dtype != torch.float32 or not gsrc.is_contiguous():
         raise ValueError(f"cube_prefilter_grad: out must be a contiguous float32 tensor {shape}")
+    _on_device(gsrc, "cube_prefilter_grad: out")
     nbytes = ctx.cube_prefilter_work_bytes(n_src, n_dst, n_ch, frames)
     work = torch.empty((max(nbytes, 16) // 4,), dtype=torch.float32, device=gdst.device)
     ctx.cube_prefilter_grad(gdst.data_ptr(), den.data_ptr(), n_src, n_dst, n_ch, frames, kind, roughness, cmin, gsrc.data_ptr(), work.data_ptr(),
@@ -1607,8 +1528,8 @@ def cube_prefilter_grad(ctx_or_fs, gdst, den, n_src, kind, roughness=1.0, cmin=0
 class _CubePrefilter(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cube, c, n_out, kind, roughness, cmin, stream):
-        cube = cube.contiguous()
         _, n_src, n_ch = _prefilter_dims(cube, "cube_prefilter")
+        cube = cube.contiguous()
         out = torch.empty(tuple(cube.shape[:-3]) + (n_out, n_out, n_ch), dtype=torch.float32, device=cube.device)
         den = torch.empty((6, n_out, n_out), dtype=torch.float32, device=cube.device)
         _prefilter_call(c, cube, n_out, kind, roughness, cmin, out, den, stream)
@@ -1642,8 +1563,8 @@ def cube_irradiance(ctx_or_fs, cube, n_out, stream=None):
 class _CubePrefilterPyramid(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cube, c, roughness, cmin, stream):
-        cube = cube.contiguous()
         _prefilter_dims(cube, "cube_prefilter_pyramid")
+        cube = cube.contiguous()
         L = len(roughness) + 1
         box = cube_mip_build(c, cube, L, stream)
         mip, dens = torch.empty_like(box), []
@@ -1714,8 +1635,9 @@ def vertex_grad(fs, mesh_id, gpos, want_gverts=True, want_gdraw=True, stream=Non
     [n_frames, D, 18] tensor to add into instead (several meshes into one buffer)."""
     if not want_gverts and not want_gdraw:
         raise ValueError("vertex_grad: neither gverts nor gdraw is asked for")
-    if gpos.dtype != torch.float32 or not gpos.is_cuda or gpos.dim() != 4 or gpos.shape[0] != fs.n_frames or tuple(gpos.shape[2:]) != (3, 3):
-        raise ValueError(f"vertex_grad: gpos must be a CUDA float32 tensor [n_frames, T, 3, 3], got {tuple(gpos.shape)} {gpos.dtype}")
+    if gpos is None or gpos.dtype != torch.float32 or not gpos.is_cuda or gpos.dim() != 4 or gpos.shape[0] != fs.n_frames or \
+            tuple(gpos.shape[2:]) != (3, 3):
+        raise ValueError("vertex_grad: gpos must be a CUDA float32 tensor [n_frames, T, 3, 3]" + _got(gpos, "plain"))
     gpos = gpos.contiguous()
     D = max(1, max(len(d) for d in _scene_draws(fs)))
     gverts = torch.zeros((fs.n_frames, fs.ctx.mesh_sizes[mesh_id][0], 3), dtype=torch.float32, device=gpos.device) if want_gverts else None
@@ -1723,8 +1645,9 @@ def vertex_grad(fs, mesh_id, gpos, want_gverts=True, want_gdraw=True, stream=Non
         gdraw = torch.zeros((fs.n_frames, D, 18), dtype=torch.float32, device=gpos.device)
     if want_gdraw and (gdraw.dtype != torch.float32 or not gdraw.is_contiguous() or tuple(gdraw.shape) != (fs.n_frames, D, 18)):
         raise ValueError(f"vertex_grad: gdraw must be a contiguous float32 tensor {(fs.n_frames, D, 18)}")
-    fs.vertex_grad(mesh_id, gpos.data_ptr(), gpos.shape[1], gverts.data_ptr() if want_gverts else None,
-                   gdraw.data_ptr() if want_gdraw else None, D, _stream_ptr(stream))
+    if want_gdraw:
+        _on_device(gdraw, "vertex_grad: gdraw")
+    fs.vertex_grad(mesh_id, gpos.data_ptr(), gpos.shape[1], _ptr(gverts), gdraw.data_ptr() if want_gdraw else None, D, _stream_ptr(stream))
     return gverts, (gdraw if want_gdraw else None)
 
 
@@ -1732,8 +1655,8 @@ def mesh_update(ctx, mesh_id, verts8, stream=None):
     """new vertices for mesh slot mesh_id of Context `ctx`, in place, from a CUDA float32 tensor [V, 8] (pos3 nrm3 uv2; V the slot's
     count): Context.mesh_update, one device-to-device copy.  Every sceneset that draws the slot stays valid and renders the new
     vertices from its next vertex stage on.  stream: a raw stream handle, None = torch's current stream."""
-    if verts8.dtype != torch.float32 or not verts8.is_cuda or verts8.dim() != 2 or verts8.shape[1] != 8:
-        raise ValueError(f"mesh_update: verts8 must be a CUDA float32 tensor [V, 8], got {tuple(verts8.shape)} {verts8.dtype}")
+    if verts8 is None or verts8.dtype != torch.float32 or not verts8.is_cuda or verts8.dim() != 2 or verts8.shape[1] != 8:
+        raise ValueError("mesh_update: verts8 must be a CUDA float32 tensor [V, 8]" + _got(verts8, "plain"))
     verts8 = verts8.detach().contiguous()
     ctx.mesh_update(mesh_id, verts8.data_ptr(), verts8.shape[0], _stream_ptr(stream))
 
@@ -1794,17 +1717,18 @@ def scene_positions(fs, meshes, mvp=None, zmap=None, pos_tris=None, stream=None)
 
 # ------------------------------------------------------------------------------------------------ normals and per-vertex attributes
 def _sets_arg(ctx, slot, t, name):
-    """a CUDA float32 [V, 3] or [B, V, 3] tensor for mesh slot `slot` -> (contiguous tensor, number of sets)"""
+    """a CUDA float32 [V, 3] or [B, V, 3] tensor for mesh slot `slot` -> (the tensor detached and contiguous, number of sets)"""
     V = ctx.mesh_sizes[slot][0]
-    if t.dtype != torch.float32 or not t.is_cuda or t.dim() not in (2, 3) or tuple(t.shape[-2:]) != (V, 3) or (t.dim() == 3 and not 1 <= t.shape[0] <= 65535):
-        raise ValueError(f"mesh_normals: {name} must be a CUDA float32 tensor [{V}, 3] or [B, {V}, 3] (B <= 65535), got {tuple(t.shape)} {t.dtype}")
-    return t.contiguous(), (t.shape[0] if t.dim() == 3 else 1)
+    if t is None or t.dtype != torch.float32 or not t.is_cuda or t.dim() not in (2, 3) or tuple(t.shape[-2:]) != (V, 3) or \
+            (t.dim() == 3 and not 1 <= t.shape[0] <= 65535):
+        raise ValueError(f"mesh_normals: {name} must be a CUDA float32 tensor [{V}, 3] or [B, {V}, 3] (B <= 65535)" + _got(t, "plain"))
+    return t.detach().contiguous(), (t.shape[0] if t.dim() == 3 else 1)
 
 
 class _MeshNormals(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, sctx, slot, stream):
-        p, n_sets = _sets_arg(sctx, slot, pos.detach(), "pos")
+        p, n_sets = _sets_arg(sctx, slot, pos, "pos")
         nrm = torch.empty_like(p)
         sctx.mesh_normals(slot, p.data_ptr(), 3, n_sets, nrm.data_ptr(), 3, _stream_ptr(stream))
         ctx.sctx, ctx.slot, ctx.stream, ctx.n_sets = sctx, slot, stream, n_sets
@@ -1834,14 +1758,14 @@ def mesh_normals(ctx, slot, pos, stream=None):
 class _MeshTangents(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, sctx, slot, uv, stream):
-        p, n_sets = _sets_arg(sctx, slot, pos.detach(), "pos")
+        p, n_sets = _sets_arg(sctx, slot, pos, "pos")
         V = p.shape[-2]
         if uv is not None:
             if uv.dtype != torch.float32 or not uv.is_cuda or tuple(uv.shape) != (V, 2):
                 raise ValueError(f"mesh_tangents: uv must be a CUDA float32 tensor [{V}, 2], got {tuple(uv.shape)} {uv.dtype}")
             uv = uv.detach().contiguous()
         tan = torch.empty(p.shape[:-1] + (4,), dtype=torch.float32, device=p.device)
-        sctx.mesh_tangents(slot, p.data_ptr(), 3, n_sets, None if uv is None else uv.data_ptr(), 2, tan.data_ptr(), 4, _stream_ptr(stream))
+        sctx.mesh_tangents(slot, p.data_ptr(), 3, n_sets, _ptr(uv), 2, tan.data_ptr(), 4, _stream_ptr(stream))
         ctx.sctx, ctx.slot, ctx.stream, ctx.n_sets, ctx.uv = sctx, slot, stream, n_sets, uv
         ctx.save_for_backward(p)
         return tan
@@ -1851,8 +1775,8 @@ class _MeshTangents(torch.autograd.Function):
         (p,) = ctx.saved_tensors
         gtan = gtan.contiguous()
         work, gpos = torch.empty_like(p), torch.empty_like(p)
-        ctx.sctx.mesh_tangents_grad(ctx.slot, p.data_ptr(), 3, ctx.n_sets, None if ctx.uv is None else ctx.uv.data_ptr(), 2, gtan.data_ptr(), 4,
-                                    work.data_ptr(), gpos.data_ptr(), _stream_ptr(ctx.stream))
+        ctx.sctx.mesh_tangents_grad(ctx.slot, p.data_ptr(), 3, ctx.n_sets, _ptr(ctx.uv), 2, gtan.data_ptr(), 4, work.data_ptr(), gpos.data_ptr(),
+                                    _stream_ptr(ctx.stream))
         return gpos, None, None, None, None
 
 
@@ -1927,12 +1851,9 @@ def corner_attr(fs, attrs, pos_tris=None, stream=None):
 
 # ------------------------------------------------------------------------------------------------ perspective-correct interpolation
 def _q_dims(fs, q, name):
-    if q.dtype != torch.float32 or not q.is_cuda or q.dim() not in (2, 3) or q.shape[-1] != 3:
-        raise ValueError(f"{name}: q must be a CUDA float32 tensor [T, 3] or [n_frames, T, 3], got {tuple(q.shape)} {q.dtype}")
-    q_frames = q.shape[0] if q.dim() == 3 else 1
-    if q.dim() == 3 and q_frames != fs.n_frames:
-        raise ValueError(f"{name}: q has {q_frames} frames, the set {fs.n_frames}")
-    return q_frames, q.shape[-2]
+    """→ (q detached and contiguous, its frame count, its triangle count)"""
+    q_frames = _lead_frames(fs, q, (2, 3), f"{name}: q", "a CUDA float32 tensor [T, 3] or [n_frames, T, 3]", lambda t: t.shape[-1] == 3)
+    return q.detach().contiguous(), q_frames, q.shape[-2]
 
 
 def perspective(fs, vis, q, out=None, stream=None):
@@ -1945,8 +1866,7 @@ def perspective(fs, vis, q, out=None, stream=None):
     ORIGINAL `vis`: position_grad, FrameSet.motion, antialias, peel, interpolate_deriv.  Not differentiable by itself:
     interpolate_persp is the autograd form.  stream: a raw stream handle, None = torch's current stream."""
     _vis_arg(fs, vis, "perspective: vis")
-    q = q.detach().contiguous()
-    q_frames, q_tris = _q_dims(fs, q, "perspective")
+    q, q_frames, q_tris = _q_dims(fs, q, "perspective")
     out = torch.empty(fs.out_shape, dtype=torch.float32, device=vis.device) if out is None else _vis_arg(fs, out, "perspective: out")
     fs.perspective(vis.data_ptr(), q.data_ptr(), q_frames, q_tris, out.data_ptr(), fs.out_bytes, abi.FUSED_CLEAR, _stream_ptr(stream))
     return out
@@ -1961,30 +1881,25 @@ def perspective_grad(fs, vis, q, gbary_p, want_gbary=True, want_gq=True, stream=
     if not want_gbary and not want_gq:
         raise ValueError("perspective_grad: neither gbary nor gq is asked for")
     _vis_arg(fs, vis, "perspective_grad: vis")
-    q = q.detach().contiguous()
-    q_frames, q_tris = _q_dims(fs, q, "perspective_grad")
-    if gbary_p.dtype != torch.float32 or not gbary_p.is_cuda or tuple(gbary_p.shape) != tuple(fs.interpolate_shape(2)):
-        raise ValueError(f"perspective_grad: gbary_p must be a CUDA float32 tensor {fs.interpolate_shape(2)}, got {tuple(gbary_p.shape)} {gbary_p.dtype}")
-    gbary_p = gbary_p.contiguous()
+    q, q_frames, q_tris = _q_dims(fs, q, "perspective_grad")
+    gbary_p = _plane(fs, gbary_p, 2, "perspective_grad: gbary_p")
     gbary = torch.empty_like(gbary_p) if want_gbary else None
     gq = torch.zeros_like(q) if want_gq else None
-    fs.perspective_grad(vis.data_ptr(), q.data_ptr(), q_frames, q_tris, gbary_p.data_ptr(), gbary.data_ptr() if want_gbary else None,
-                        gq.data_ptr() if want_gq else None, abi.FUSED_CLEAR, _stream_ptr(stream))
+    fs.perspective_grad(vis.data_ptr(), q.data_ptr(), q_frames, q_tris, gbary_p.data_ptr(), _ptr(gbary), _ptr(gq), abi.FUSED_CLEAR,
+                        _stream_ptr(stream))
     return gbary, gq
 
 
 class _InterpolatePersp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, attr, pos, q, fs, vis, stream):
-        attr = attr.contiguous()
         attr_frames, tris, n_ch = _attr_dims(fs, attr)
-        if pos.dtype != torch.float32 or pos.dim() != 4 or pos.shape[0] != fs.n_frames or tuple(pos.shape[2:]) != (3, 3):
-            raise ValueError(f"interpolate_persp: pos must be float32 [n_frames, T, 3, 3], got {tuple(pos.shape)} {pos.dtype}")
+        attr, ctx.pos_shape = attr.contiguous(), _pos_handle(fs, pos, "interpolate_persp")
         pvis = perspective(fs, vis, q, stream=stream)
         out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=attr.device)
         fs.interpolate(pvis.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris, out.data_ptr(), fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR,
                        _stream_ptr(stream))
-        ctx.fs, ctx.vis, ctx.pvis, ctx.stream, ctx.pos_shape = fs, vis, pvis, stream, pos.shape
+        ctx.fs, ctx.vis, ctx.pvis, ctx.stream = fs, vis, pvis, stream
         ctx.save_for_backward(attr, q.detach())
         return out
 
@@ -2001,8 +1916,7 @@ class _InterpolatePersp(torch.autograd.Function):
         gattr = torch.zeros_like(attr) if need_attr else None
         gbary_p = torch.empty(fs.interpolate_shape(2), dtype=torch.float32, device=gout.device) if need_bary else None
         if need_attr or need_bary:
-            fs.interpolate_grad(pvis.data_ptr(), gout.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris,
-                                gattr.data_ptr() if need_attr else None, gbary_p.data_ptr() if need_bary else None, abi.FUSED_CLEAR, sp)
+            fs.interpolate_grad(pvis.data_ptr(), gout.data_ptr(), attr.data_ptr(), n_ch, attr_frames, tris, _ptr(gattr), _ptr(gbary_p), abi.FUSED_CLEAR, sp)
         gpos = gq = None
         if need_bary:
             gbary, gq = perspective_grad(fs, vis, q, gbary_p, need_pos, need_q, ctx.stream)
@@ -2065,9 +1979,8 @@ def interpolate_deriv_persp(fs, vis, attr, q, stream=None):
     for a [T, 3, 2] uv attribute.  vis is the ORIGINAL buffer, q as perspective takes it.  Not differentiable: the planes only select
     a mip level.  stream: a raw stream handle, None = torch's current stream."""
     _vis_arg(fs, vis, "interpolate_deriv_persp: vis")
-    attr, q = attr.detach().contiguous(), q.detach().contiguous()
     attr_frames, tris, n_ch = _attr_dims(fs, attr)
-    q_frames, q_tris = _q_dims(fs, q, "interpolate_deriv_persp")
+    attr, (q, q_frames, q_tris) = attr.detach().contiguous(), _q_dims(fs, q, "interpolate_deriv_persp")
     if n_ch > abi.ATTR_MAX_CH // 2:
         raise ValueError(f"interpolate_deriv_persp: {n_ch} channels; at most {abi.ATTR_MAX_CH // 2} are supported")
     out = torch.empty(fs.interpolate_shape(2 * n_ch), dtype=torch.float32, device=attr.device)
