@@ -84,6 +84,8 @@ extern "C" {
  *      srz_frameset_background_work_bytes / srz_frameset_background_grad, SRZ_BG_NOBODY, SRZ_BG_ALL
  *      (additive, same version) compositing depth layers front to back, with gradients srz_frameset_composite /
  *      srz_frameset_composite_grad, srz_composite_layer, SRZ_COMPOSITE_MAX
+ *      (additive, same version) texture sets: each pixel's caller texture picked by its owner's batch, with gradients
+ *      srz_frameset_texture_set / srz_frameset_texture_set_grad, srz_texset_slot, SRZ_TEXSET_MAX, SRZ_TEXSET_NONE
  */
 #define SRZ_ABI_VERSION 7
 
@@ -1476,6 +1478,44 @@ int srz_frameset_composite(srz_ctx *ctx, srz_frameset *fs, const srz_composite_l
 int srz_frameset_composite_grad(srz_ctx *ctx, srz_frameset *fs, const srz_composite_layer *layers, uint32_t n_layers, uint32_t n_ch,
                                 const void *d_bg, uint32_t want_through, const void *d_gout, void *const *d_gcolor,
                                 void *const *d_galpha, void *d_gbg, uint32_t flags, void *stream);
+/* TEXTURE SETS: srz_frameset_texture with the texture of each pixel chosen by its owner's batch, and the gradients of that — the
+ * first texture lookup of a scene with more than one material in one pass over the tiles.  A call takes n_slots textures,
+ * 1 .. SRZ_TEXSET_MAX, in a HOST array of srz_texset_slot (read before the call returns, like srz_composite_layer's array), and
+ * d_batch_slot, DEVICE memory of n_batch_slot bytes (1 .. 65536): ONE map for every frame of the set, indexed by the owner's batch
+ * within its frame — for a sceneset its draw, the value SRZ_GB_BATCH writes minus 1.  A slot is d_tex [tex_frames][tex_h][tex_w][n_ch]
+ * as srz_frameset_texture takes it, its own tex_w, tex_h, tex_frames (1 or the set's frame count) and mode (SRZ_TEX_CLAMP /
+ * SRZ_TEX_WRAP), and, in the backward only, d_gtex of d_tex's shape (ADDED INTO) or NULL: this slot's texel gradient is not wanted.
+ * n_ch is one value for the call: every slot's texture has n_ch channels.  d_vis, d_uv, d_out, d_gout, d_guv: srz_frameset_texture's.
+ * THE RULE.  Owner and nobody: exactly as srz_frameset_texture.  THE SLOT of an owned pixel: with b the owner's batch,
+ *   s = b < n_batch_slot ? d_batch_slot[b] : SRZ_TEXSET_NONE
+ * If s >= n_slots (so in particular SRZ_TEXSET_NONE) the pixel is UNSAMPLED in srz_frameset_texture's sense: every channel of out
+ * is 0 (written: the pixel has an owner), guv = (0, 0), no add.  No byte of the map makes a pass read or write outside its
+ * buffers; the host cannot validate device bytes and does not try.  Otherwise the pixel follows srz_frameset_texture's rule, word
+ * for word, with slot s's d_tex, tex_w, tex_h, tex_frames and mode: the forward, d_guv, and the adds into slot s's d_gtex (none when
+ * that is NULL).  Two slots MAY share one d_tex (one image clamped for one mesh and wrapped for another).
+ * As srz_frameset_texture / _texture_grad: the fused clear at nobody's pixels, band sharding (each rank adds the partial sums of its
+ * own bands), asynchrony and stream semantics, the 16-byte alignment of the plane buffers and the 4-byte alignment of the textures,
+ * SRZ_OPT_APPROX_SHADE having no effect.  BACKWARD: at least one of d_guv and some slot's d_gtex is asked for; d_guv needs every
+ * slot's d_tex.  The d_gtex buffers are NOT BIT-REPRODUCIBLE, within srz_frameset_texture_grad's bound; d_guv and the forward are
+ * deterministic, bit for bit.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set, d_vis, d_uv, slots, d_batch_slot, d_out, d_gout,
+ * a slot's d_tex (forward; backward with d_guv), or no d_guv and no d_gtex; n_slots 0 or above SRZ_TEXSET_MAX; n_batch_slot 0 or
+ * above 65536; per slot everything srz_frameset_texture refuses of a texture; a short out_bytes; a misaligned pointer; any bit of
+ * `flags` but SRZ_FUSED_CLEAR; an output that overlaps an input (the map's bytes count as one) or another output — two slots'
+ * d_gtex ranges that overlap each other included. */
+#define SRZ_TEXSET_MAX 8u     /* slots of one call */
+#define SRZ_TEXSET_NONE 0xffu /* conventional "no slot" value of the map */
+typedef struct srz_texset_slot {
+  const float *d_tex; /* [tex_frames][tex_h][tex_w][n_ch], as srz_frameset_texture takes it */
+  float *d_gtex;      /* backward only: ADDED INTO, or NULL — this slot's texel gradient is not wanted */
+  uint32_t tex_w, tex_h, tex_frames, mode; /* per slot: sizes, 1 or the set's frame count, SRZ_TEX_CLAMP / SRZ_TEX_WRAP */
+} srz_texset_slot;
+int srz_frameset_texture_set(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const srz_texset_slot *slots,
+                             uint32_t n_slots, const uint8_t *d_batch_slot, uint32_t n_batch_slot, uint32_t n_ch, void *d_out,
+                             size_t out_bytes, uint32_t flags, void *stream);
+int srz_frameset_texture_set_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const void *d_gout,
+                                  const srz_texset_slot *slots, uint32_t n_slots, const uint8_t *d_batch_slot, uint32_t n_batch_slot,
+                                  uint32_t n_ch, void *d_guv, uint32_t flags, void *stream);
 /* PERSPECTIVE-CORRECT BARYCENTRICS of a visibility buffer, their gradients, and the attribute derivatives under them.  A visibility
  * buffer's alpha, beta are LINEAR IN SCREEN SPACE, the reference's rule and the default of every pass above.  Under a vertex stage
  * that divides by a real w they name the wrong point of the triangle.  With q_k = 1 / w_k the reciprocal clip w of the owner's

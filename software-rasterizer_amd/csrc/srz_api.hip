@@ -2799,6 +2799,99 @@ int srz_frameset_composite_grad(srz_ctx *ctx, srz_frameset *fs, const srz_compos
   return end_pass(ctx);
 }
 
+namespace {
+// what srz_frameset_texture_set and _texture_set_grad check alike behind their nulls: the counts, then every slot as
+// srz_frameset_texture checks its texture (check_texture, not restated).  need_tex: a slot's d_tex may not be null.  *ins gets the
+// map's and every texture's range, *tex_bytes every slot's bytes
+int check_texset(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, const srz_texset_slot *slots, uint32_t n_slots,
+                 const uint8_t *d_batch_slot, uint32_t n_batch_slot, uint32_t n_ch, uint32_t flags, bool need_tex, std::vector<Range> *ins,
+                 std::vector<size_t> *tex_bytes) {
+  if (n_slots == 0u || n_slots > SRZ_TEXSET_MAX) return fail(ctx, SRZ_E_INVALID, fn + ": n_slots must be 1 .. SRZ_TEXSET_MAX");
+  if (n_batch_slot == 0u || n_batch_slot > 65536u) return fail(ctx, SRZ_E_INVALID, fn + ": n_batch_slot must be 1 .. 65536");
+  ins->push_back({d_batch_slot, (size_t)n_batch_slot});
+  for (uint32_t k = 0; k < n_slots; ++k) {
+    const srz_texset_slot &sl = slots[k];
+    size_t bytes = 0;
+    if (int rc = check_texture(ctx, fs, fn + " (slot " + std::to_string(k) + ")", sl.tex_w, sl.tex_h, n_ch, sl.tex_frames, sl.mode, flags, &bytes))
+      return rc;
+    if (need_tex && !sl.d_tex) return fail(ctx, SRZ_E_INVALID, fn + ": null d_tex in slot " + std::to_string(k));
+    if (!aligned<4>({sl.d_tex, sl.d_gtex}))
+      return fail(ctx, SRZ_E_INVALID, fn + ": every slot's texture and its gradient must be 4-byte aligned");
+    ins->push_back({sl.d_tex, bytes}), tex_bytes->push_back(bytes);
+  }
+  return SRZ_OK;
+}
+TexSetArgs texset_args(const srz_frameset *fs, const void *d_vis, const void *d_uv, const srz_texset_slot *slots, uint32_t n_slots,
+                       const uint8_t *d_batch_slot, uint32_t n_batch_slot, uint32_t n_ch, uint32_t out_planes, void *d_out, uint32_t flags) {
+  TexSetArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  a.uv = (const float *)d_uv, a.tri_batch = fs->d_tri_batch, a.batch_slot = d_batch_slot;
+  for (uint32_t k = 0; k < n_slots; ++k) {
+    const srz_texset_slot &sl = slots[k];
+    a.tex[k] = sl.d_tex, a.tex_w[k] = sl.tex_w, a.tex_h[k] = sl.tex_h;
+    a.tex_frame_stride[k] = sl.tex_frames == 1u ? 0ull : (uint64_t)sl.tex_h * sl.tex_w * n_ch;
+    if (sl.mode == SRZ_TEX_WRAP) a.wrap_mask |= 1u << k;
+  }
+  a.vis_stride = 4ull * plane, a.frame_stride = out_planes * plane, a.uv_stride = 2ull * plane, a.gout_stride = n_ch * plane;
+  a.n_slots = n_slots, a.n_batch_slot = n_batch_slot, a.n_ch = n_ch;
+  a.flags_or = flags;
+  return a;
+}
+} // namespace
+
+int srz_frameset_texture_set(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const srz_texset_slot *slots,
+                             uint32_t n_slots, const uint8_t *d_batch_slot, uint32_t n_batch_slot, uint32_t n_ch, void *d_out,
+                             size_t out_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_texture_set");
+  if (!fs || !d_vis || !d_uv || !slots || !d_batch_slot || !d_out)
+    return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_uv ? "d_uv" : !slots ? "slots" : !d_batch_slot ? "d_batch_slot" : "d_out"));
+  std::vector<Range> ins;
+  std::vector<size_t> tex_bytes;
+  if (int rc = check_texset(ctx, fs, fn, slots, n_slots, d_batch_slot, n_batch_slot, n_ch, flags, true, &ins, &tex_bytes)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, n_ch), uv_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": out_bytes is too small for d_out");
+  if (!aligned<16>({d_vis, d_uv, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_uv, d_out) must be 16-byte aligned");
+  ins.push_back({d_vis, srz_frameset_out_bytes(ctx, fs)}), ins.push_back({d_uv, uv_bytes});
+  if (int rc = check_overlaps_n(ctx, fn + " (d_out against d_vis, d_uv, the map and every slot's d_tex)", std::vector<Range>{{d_out, need}}, ins))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_texture)
+  launch_tex_set(texset_args(fs, d_vis, d_uv, slots, n_slots, d_batch_slot, n_batch_slot, n_ch, n_ch, d_out, flags), s);
+  return end_pass(ctx);
+}
+
+int srz_frameset_texture_set_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_uv, const void *d_gout,
+                                  const srz_texset_slot *slots, uint32_t n_slots, const uint8_t *d_batch_slot, uint32_t n_batch_slot,
+                                  uint32_t n_ch, void *d_guv, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_texture_set_grad");
+  if (!fs || !d_vis || !d_uv || !d_gout || !slots || !d_batch_slot)
+    return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_uv ? "d_uv" : !d_gout ? "d_gout" : !slots ? "slots" : "d_batch_slot"));
+  std::vector<Range> ins;
+  std::vector<size_t> tex_bytes;
+  if (int rc = check_texset(ctx, fs, fn, slots, n_slots, d_batch_slot, n_batch_slot, n_ch, flags, d_guv != nullptr, &ins, &tex_bytes)) return rc;
+  const size_t gout_bytes = srz_frameset_interpolate_bytes(ctx, fs, n_ch), uv_bytes = srz_frameset_interpolate_bytes(ctx, fs, 2u);
+  std::vector<Range> outs;
+  bool any_gtex = false;
+  for (uint32_t k = 0; k < n_slots; ++k) any_gtex = any_gtex || slots[k].d_gtex, outs.push_back({slots[k].d_gtex, tex_bytes[k]});
+  outs.push_back({d_guv, uv_bytes});
+  if (!any_gtex && !d_guv) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_guv nor any slot's d_gtex is asked for");
+  if (!aligned<16>({d_vis, d_uv, d_gout, d_guv}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_uv, d_gout, d_guv) must be 16-byte aligned");
+  ins.push_back({d_vis, srz_frameset_out_bytes(ctx, fs)}), ins.push_back({d_uv, uv_bytes}), ins.push_back({d_gout, gout_bytes});
+  if (int rc = check_overlaps_n(ctx, fn + " (d_guv and every slot's d_gtex against d_vis, d_uv, d_gout, the map and every slot's d_tex)", outs, ins))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_texture)
+  TexSetArgs a = texset_args(fs, d_vis, d_uv, slots, n_slots, d_batch_slot, n_batch_slot, n_ch, 2u, d_guv, flags);
+  a.gout = (const float *)d_gout, a.want_tex = any_gtex ? 1u : 0u;
+  for (uint32_t k = 0; k < n_slots; ++k) a.gtex[k] = slots[k].d_gtex;
+  launch_tex_set_grad(a, s);
+  return end_pass(ctx);
+}
+
 uint32_t srz_texture_mip_levels(uint32_t tex_w, uint32_t tex_h) {
   if (tex_w == 0u || tex_w > SRZ_TEX_MAX_SIZE || tex_h == 0u || tex_h > SRZ_TEX_MAX_SIZE) return 0u;
   uint32_t n = 1u;

@@ -643,6 +643,33 @@ struct CompositeArgs {
 };
 void launch_composite(const CompositeArgs &a, hipStream_t s);
 void launch_composite_grad(const CompositeArgs &a, hipStream_t s);
+// srz_frameset_texture_set / _texture_set_grad: TexArgs with n_slots textures, the one of a pixel picked by its owner's batch
+// (k_tex_set, k_tex_set_grad).  tri_batch: the set's batch of every triangle, as RenderArgs has it; batch_slot: the caller's
+// n_batch_slot bytes, batch -> slot (a byte >= n_slots: the pixel is not sampled).  Per slot: tex (backward: may be null when guv
+// is), gtex (backward: tex's shape, added into, may be null), tex_frame_stride (0: one texture for every frame), tex_w, tex_h; bit
+// s of wrap_mask: slot s's mode is SRZ_TEX_WRAP.  vis, uv, out, gout and the strides as in TexArgs.  The host has checked every slot
+// as srz_frameset_texture checks its texture, 1 <= n_slots <= SRZ_TEXSET_MAX and 1 <= n_batch_slot <= 65536
+struct TexSetArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *uv;
+  const uint16_t *tri_batch;
+  const uint8_t *batch_slot;
+  float *out;
+  const float *gout;
+  const float *tex[SRZ_TEXSET_MAX];
+  float *gtex[SRZ_TEXSET_MAX];
+  uint64_t tex_frame_stride[SRZ_TEXSET_MAX];
+  uint32_t tex_w[SRZ_TEXSET_MAX], tex_h[SRZ_TEXSET_MAX];
+  uint64_t vis_stride, frame_stride, uv_stride, gout_stride;
+  uint32_t n_slots, n_batch_slot, n_ch, wrap_mask;
+  uint32_t want_tex; // backward: some slot's gtex is asked for (the tile's table is kept)
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_tex_set(const TexSetArgs &a, hipStream_t s);
+void launch_tex_set_grad(const TexSetArgs &a, hipStream_t s);
 // srz_frameset_shadow / _shadow_grad: a float depth map of the caller's [map frame][row][column] compared and filtered at the
 // coordinate planes sc [frame][3][local_rows][width] (sx, sy in texels, sd in the map's depth units) under a visibility buffer
 // (k_shadow), and the gradients of that with respect to the map (gmap, added into) and to the coordinates (k_shadow_grad).  vis as

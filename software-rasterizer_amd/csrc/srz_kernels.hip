@@ -9402,4 +9402,278 @@ void launch_composite_grad(const CompositeArgs &a, hipStream_t s) {
   else launch_pass<k_composite_grad<SRZ_COMPOSITE_MAX>>(a, s);
 }
 
+
+// ================================================================================================================
+// k_tex_set, k_tex_set_grad — TEXTURE SETS (srz_frameset_texture_set / _texture_set_grad, include/srz.h states the rule): k_tex and
+// k_tex_grad with the texture of each pixel picked by its owner's batch.  k_cube's and k_cube_grad's shape on the passes' helpers:
+// pass_walk, quad_ids, quad_load, quad_store_owned; tex_tap and TexTable are k_tex's and k_tex_grad's own, used as they are.
+// The slot is a per-LANE value (a quad can straddle two meshes): one 2-byte gather of the owner's batch per owned pixel — not
+// repeated for a pixel whose owner was looked up last — and one byte of the caller's map; a byte that names no slot leaves
+// the pixel unsampled, so no byte of the map reaches an address.  The per-slot pointers and sizes are never indexed by the lane's
+// slot (that would put the table into scratch): as in k_composite the loop over the slots is unrolled by SRZ_TEXSET_MAX with the
+// run-time count as guard, a wave skips a slot none of its lanes has (ballot), and the slot's pointer and sizes are then scalar
+// loads of the kernel arguments; what a sampled pixel keeps of its slot is its taps and the slot number, in registers.  The
+// forward's channel loop is k_tex's slot after slot (the same unrolled loop and ballot: the texture stays a scalar base under the
+// lanes' texel offsets — with a per-pixel pointer the build took 130 VGPRs and three waves a SIMD, this way 118 and k_tex's four);
+// the backward's is k_tex_grad's with the texture's pointer at the frame per pixel (213 VGPRs, k_tex_grad's two waves).
+// The gradient's table counts distinct (slot, texel) pairs of the tile: its key is (slot << 28 | texel index) + 1 — a texel index
+// is below SRZ_TEX_MAX_SIZE^2 = 2^28, eight slots end at 2^31 —, so two slots that touch the same texel index are two entries.  A
+// corner of a slot without gtex takes no entry and adds nothing.  The flush takes the slot out of the key and adds into THAT
+// slot's gtex at its own frame stride (0: every frame folds into the one texture), and so does the straight-to-memory add of a
+// corner that found no entry (ts_gtex: a chain of selects over the kernel arguments, no indexing).  Every thread of the workgroup
+// reaches every barrier.
+// (ts_slot is a COPY of tg_slot, ts_add of tg_add with the slot's gtex looked up where it is needed, the flush of k_tex_grad's step
+// 4: called from here as they are, tg_slot and tg_add moved k_tex_grad's registers, 171 -> 221 VGPRs, as sharing has moved them
+// before (k_tex_mip_grad's note); a fix goes into all of them)
+// (At the end of the file, behind the launchers: no existing kernel moves.)
+// ================================================================================================================
+constexpr uint32_t TS_IDX_BITS = 28;
+static_assert((uint64_t)SRZ_TEX_MAX_SIZE * SRZ_TEX_MAX_SIZE <= (1ull << TS_IDX_BITS) && ((uint64_t)SRZ_TEXSET_MAX << TS_IDX_BITS) < 0xffffffffull,
+              "a (slot, texel) pair + 1 fits the table's 32-bit key");
+// what k_tex_set and k_tex_set_grad do alike in front of their channel loops: the owners, their batches' slots, u and v of a quad
+// with an owner, and per sampled pixel (an owner with a slot whose u and v are both finite) its taps and the slot as the key's
+// high bits -> `own` and `smp`.  keep(k, s): what else the caller keeps of slot s for pixel k, called where s is wave-uniform
+template <class Keep>
+__device__ __forceinline__ void texset_quad(const TexSetArgs &a, const PassTile &t, TexTap (&tap)[4], uint32_t (&hi)[4], uint32_t &own,
+                                            uint32_t &smp, Keep keep) {
+  uint32_t id[4];
+  own = quad_ids<~S_CLASS_BIT>(t, a.vis + (size_t)t.f * a.vis_stride + t.poff, id), smp = 0u;
+  if (own == 0u) return;
+  float4 uv[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+  quad_load(a.uv + (size_t)t.f * a.uv_stride + t.poff, t.rc.plane, uv, t.whole, t.x4, t.rc.tx1);
+  const SRZ_CAS uint16_t *tri_batch = as_const(a.tri_batch) + t.fd->tri_off;
+  const SRZ_CAS uint8_t *map = as_const(a.batch_slot);
+  uint32_t bs[4], last_id = 0u, last_bs = SRZ_TEXSET_NONE; // (the owner looked up last, and its slot: no owner's id is 0)
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    bs[k] = SRZ_TEXSET_NONE;
+    if (!(own & (1u << k))) continue;
+    if (id[k] != last_id) {
+      const uint32_t b = tri_batch[id[k] - 1u]; // (id - 1 < the frame's triangle count: quad_ids)
+      last_id = id[k], last_bs = b < a.n_batch_slot ? (uint32_t)map[b] : (uint32_t)SRZ_TEXSET_NONE;
+    }
+    bs[k] = last_bs;
+    if (bs[k] < a.n_slots && tex_finite(quad_at(uv[0], k)) && tex_finite(quad_at(uv[1], k))) smp |= 1u << k;
+  }
+#pragma unroll
+  for (uint32_t s = 0; s < SRZ_TEXSET_MAX; ++s) {
+    if (s >= a.n_slots) continue;
+    uint32_t m = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if ((smp & (1u << k)) && bs[k] == s) m |= 1u << k;
+    if (__ballot(m != 0u) == 0ull) continue;
+    const uint32_t tw = a.tex_w[s], th = a.tex_h[s];
+    const bool wrap = ((a.wrap_mask >> s) & 1u) != 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (m & (1u << k)) {
+        tap[k] = tex_tap(quad_at(uv[0], k), quad_at(uv[1], k), tw, th, wrap);
+        hi[k] = s << TS_IDX_BITS;
+        keep(k, s);
+      }
+  }
+}
+__global__ __launch_bounds__(256) void k_tex_set(TexSetArgs a) {
+  const uint32_t C = a.n_ch;
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const TileRect &rc = t.rc;
+    const bool fused = t.fused(a.flags_or);
+    // ---- 1. owners, slots, u and v, the taps
+    TexTap tap[4] = {};
+    uint32_t hi[4] = {0u, 0u, 0u, 0u}, own, smp;
+    texset_quad(a, t, tap, hi, own, smp, [](int, uint32_t) {});
+    if (own == 0u && !fused) return;
+    // ---- 2. the channels, ATTR_CHUNK at a time (k_tex's loop)
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 q[ATTR_CHUNK];
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) q[i] = make_float4(0.f, 0.f, 0.f, 0.f); // nobody, and an owner that is not sampled: zeros
+      // (slot after slot, so that the texture is a scalar base under the lanes' texel offsets: a wave skips a slot it does not hold)
+#pragma unroll
+      for (uint32_t s = 0; s < SRZ_TEXSET_MAX; ++s) {
+        if (s >= a.n_slots) continue;
+        uint32_t m = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if ((smp & (1u << k)) && hi[k] == s << TS_IDX_BITS) m |= 1u << k;
+        if (__ballot(m != 0u) == 0ull) continue;
+        const SRZ_CAS float *slot_tex = as_const(a.tex[s]) + (size_t)t.f * a.tex_frame_stride[s];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (!(m & (1u << k))) continue;
+          const SRZ_CAS float *p00 = slot_tex + (size_t)tap[k].i00 * C + c0, *p01 = slot_tex + (size_t)tap[k].i01 * C + c0;
+          const SRZ_CAS float *p10 = slot_tex + (size_t)tap[k].i10 * C + c0, *p11 = slot_tex + (size_t)tap[k].i11 * C + c0;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float t00 = p00[i], t01 = p01[i], t10 = p10[i], t11 = p11[i];
+              const float top = fmaf_(tap[k].tx, t01 - t00, t00), bot = fmaf_(tap[k].tx, t11 - t10, t10);
+              quad_at(q[i], k) = fmaf_(tap[k].ty, bot - top, top);
+            }
+        }
+      }
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+        if (i >= nc) break;
+        quad_store_owned(t.out + (size_t)(c0 + i) * rc.plane, t, {q[i]}, fused, own);
+      }
+    }
+  });
+}
+
+// slot s's texel gradient at frame f (null: not asked for)
+__device__ __forceinline__ float *ts_gtex(const TexSetArgs &a, uint32_t s, uint32_t f) {
+  float *g = nullptr;
+  uint64_t stride = 0u;
+#pragma unroll
+  for (uint32_t q = 0; q < SRZ_TEXSET_MAX; ++q)
+    if (s == q) g = a.gtex[q], stride = a.tex_frame_stride[q];
+  return g ? g + (size_t)f * stride : nullptr;
+}
+// the entry of (slot, texel) pair `pair` in the tile's table, taken if need be; TG_NONE: no room within TG_PROBES
+__device__ __forceinline__ uint32_t ts_slot(TexTable &tb, uint32_t pair) {
+  const uint32_t key = pair + 1u; // (pair < SRZ_TEXSET_MAX << TS_IDX_BITS = 2^31)
+  uint32_t h = (key * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
+  for (uint32_t p = 0; p < TG_PROBES; ++p) {
+    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
+    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
+    if (old == 0u || old == key) return h;
+    h = (h + 1u) & (TG_SLOTS - 1u);
+  }
+  return TG_NONE;
+}
+__device__ __forceinline__ void ts_add(TexTable &tb, uint32_t slot, const TexSetArgs &a, uint32_t hi, uint32_t f, uint32_t idx, uint32_t C,
+                                       uint32_t ch, uint32_t i, float v) {
+  if (slot != TG_NONE) lds_add(&tb.val[slot * ATTR_CHUNK + i], v);
+  else global_add(ts_gtex(a, hi >> TS_IDX_BITS, f) + (size_t)idx * C + ch, v); // (the pixel's slot has a gtex: step 2)
+}
+__global__ __launch_bounds__(256) void k_tex_set_grad(TexSetArgs a) {
+  __shared__ TexTable tb;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t C = a.n_ch;
+  const bool want_tex = a.want_tex != 0u, want_uv = a.out != nullptr;
+  uint32_t asked = 0u; // bit s: slot s's gtex is asked for
+#pragma unroll
+  for (uint32_t q = 0; q < SRZ_TEXSET_MAX; ++q)
+    if (a.gtex[q]) asked |= 1u << q;
+  if (want_tex) {
+    for (uint32_t i = tid; i < TG_SLOTS; i += 256) tb.key[i] = 0u;
+    for (uint32_t i = tid; i < TG_SLOTS * ATTR_CHUNK; i += 256) tb.val[i] = 0.0f;
+    if (tid == 0) tb.n_used = 0u;
+    __syncthreads();
+  }
+  pass_walk<true>(a, [&](const PassTile &t) { // (a thread outside the frame owns nothing, and still meets the barriers)
+    const TileRect &rc = t.rc;
+    const bool fused = t.fused(a.flags_or);
+    const float *gg = a.gout + (size_t)t.f * a.gout_stride + t.poff;
+    // ---- 1. owners, slots, u and v, the taps
+    TexTap tap[4] = {};
+    const SRZ_CAS float *tex[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t hi[4] = {0u, 0u, 0u, 0u}, own, smp;
+    texset_quad(a, t, tap, hi, own, smp, [&](int k, uint32_t s) { tex[k] = as_const(a.tex[s]) + (size_t)t.f * a.tex_frame_stride[s]; });
+    // ---- 2. the table entries of the sampled pixels' corners, keyed by (slot, texel); none for a slot without gtex
+    uint32_t slot[4][4] = {};
+    uint32_t add = 0u; // the sampled pixels whose slot's gtex is asked for
+    if (want_tex) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if ((smp & (1u << k)) && ((asked >> (hi[k] >> TS_IDX_BITS)) & 1u)) {
+          add |= 1u << k;
+          slot[k][0] = ts_slot(tb, hi[k] | tap[k].i00), slot[k][1] = ts_slot(tb, hi[k] | tap[k].i01);
+          slot[k][2] = ts_slot(tb, hi[k] | tap[k].i10), slot[k][3] = ts_slot(tb, hi[k] | tap[k].i11);
+        }
+    }
+    float au[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f};
+    uint32_t n_used = 0u;
+    // ---- 3. the channels, ATTR_CHUNK at a time
+    for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
+      const uint32_t nc = min(ATTR_CHUNK, C - c0);
+      float4 g[ATTR_CHUNK]; // gout of the chunk's channels; words of pixels that are not sampled are loaded with their quad at most, never used
+#pragma unroll
+      for (uint32_t i = 0; i < ATTR_CHUNK; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (smp != 0u) {
+#pragma unroll
+        for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
+          if (i >= nc) break;
+          const float *p = gg + (size_t)(c0 + i) * rc.plane;
+          if (t.whole) {
+            g[i] = *reinterpret_cast<const float4 *>(p);
+          } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (smp & (1u << k)) quad_at(g[i], k) = p[k];
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(smp & (1u << k))) continue;
+        if (want_uv) {
+          const SRZ_CAS float *p00 = tex[k] + (size_t)tap[k].i00 * C + c0, *p01 = tex[k] + (size_t)tap[k].i01 * C + c0;
+          const SRZ_CAS float *p10 = tex[k] + (size_t)tap[k].i10 * C + c0, *p11 = tex[k] + (size_t)tap[k].i11 * C + c0;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float gi = quad_at(g[i], k), t00 = p00[i], t01 = p01[i], t10 = p10[i], t11 = p11[i];
+              const float top = fmaf_(tap[k].tx, t01 - t00, t00), bot = fmaf_(tap[k].tx, t11 - t10, t10);
+              au[k] = fmaf_(gi, fmaf_(tap[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au[k]);
+              av[k] = fmaf_(gi, bot - top, av[k]);
+            }
+        }
+        if (add & (1u << k)) {
+          const float tx_ = tap[k].tx, ty_ = tap[k].ty;
+          const float w00 = (1.0f - tx_) * (1.0f - ty_), w01 = tx_ * (1.0f - ty_), w10 = (1.0f - tx_) * ty_, w11 = tx_ * ty_;
+#pragma unroll
+          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+            if (i < nc) {
+              const float gi = quad_at(g[i], k);
+              ts_add(tb, slot[k][0], a, hi[k], t.f, tap[k].i00, C, c0 + i, i, w00 * gi);
+              ts_add(tb, slot[k][1], a, hi[k], t.f, tap[k].i01, C, c0 + i, i, w01 * gi);
+              ts_add(tb, slot[k][2], a, hi[k], t.f, tap[k].i10, C, c0 + i, i, w10 * gi);
+              ts_add(tb, slot[k][3], a, hi[k], t.f, tap[k].i11, C, c0 + i, i, w11 * gi);
+            }
+        }
+      }
+      if (want_tex) {
+        // ---- 4. the table's values of this chunk into memory, each into its own slot's gtex: lanes in channel order within a texel
+        __syncthreads();
+        n_used = tb.n_used;
+        for (uint32_t i = tid; i < n_used * ATTR_CHUNK; i += 256) {
+          const uint32_t s = tb.used[i / ATTR_CHUNK], e = i % ATTR_CHUNK;
+          const float v = tb.val[s * ATTR_CHUNK + e];
+          tb.val[s * ATTR_CHUNK + e] = 0.0f;
+          const uint32_t key = tb.key[s] - 1u, ks = key >> TS_IDX_BITS, idx = key & ((1u << TS_IDX_BITS) - 1u);
+          float *gs = ts_gtex(a, ks, t.f); // (an entry's slot has a gtex: step 2)
+          if (e < nc && gs) global_add(gs + (size_t)idx * C + c0 + e, v);
+        }
+        __syncthreads();
+      }
+    }
+    if (want_tex) { // the tile's keys go; every thread has read n_used before the chunk's last barrier
+      for (uint32_t i = tid; i < n_used; i += 256) tb.key[tb.used[i]] = 0u;
+      if (tid == 0) tb.n_used = 0u;
+      __syncthreads();
+    }
+    // ---- 5. du, dv: whole quads (fused clear, or four owners), else the owned pixels only; an owner that is not sampled: (0, 0)
+    if (want_uv && t.inside && (own != 0u || fused)) {
+      float4 d[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (smp & (1u << k)) {
+          uint32_t tw = 0u, th = 0u; // the extents of the pixel's slot
+#pragma unroll
+          for (uint32_t q = 0; q < SRZ_TEXSET_MAX; ++q)
+            if ((hi[k] >> TS_IDX_BITS) == q) tw = a.tex_w[q], th = a.tex_h[q];
+          quad_at(d[0], k) = tap[k].in_x ? au[k] * (float)tw : 0.0f;
+          quad_at(d[1], k) = tap[k].in_y ? av[k] * (float)th : 0.0f;
+        }
+      quad_store_owned(t.out, t, d, fused, own);
+    }
+  });
+}
+void launch_tex_set(const TexSetArgs &a, hipStream_t s) { launch_pass<k_tex_set>(a, s); }
+void launch_tex_set_grad(const TexSetArgs &a, hipStream_t s) { launch_pass<k_tex_set_grad>(a, s); }
+
 } // namespace srz

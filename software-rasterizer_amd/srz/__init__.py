@@ -42,6 +42,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_shadow", "srz_frameset_shadow_grad",
            "srz_mesh_tangents", "srz_mesh_tangents_grad", "srz_frameset_normal_map", "srz_frameset_normal_map_grad",
            "srz_frameset_composite", "srz_frameset_composite_grad",
+           "srz_frameset_texture_set", "srz_frameset_texture_set_grad",
            "srz_frameset_perspective", "srz_frameset_perspective_grad", "srz_frameset_interpolate_deriv_persp",
            "srz_target_create", "srz_target_destroy", "srz_target_clear", "srz_target_draw", "srz_target_read", "srz_target_read_bgr8"]
 
@@ -159,6 +160,8 @@ def lib():
         L.srz_frameset_normal_map_grad.argtypes = abi.NORMAL_MAP_GRAD_ARGTYPES
         L.srz_frameset_composite.argtypes = abi.COMPOSITE_ARGTYPES
         L.srz_frameset_composite_grad.argtypes = abi.COMPOSITE_GRAD_ARGTYPES
+        L.srz_frameset_texture_set.argtypes = abi.TEXTURE_SET_ARGTYPES
+        L.srz_frameset_texture_set_grad.argtypes = abi.TEXTURE_SET_GRAD_ARGTYPES
         L.srz_frameset_shadow.argtypes = abi.SHADOW_ARGTYPES
         L.srz_frameset_shadow_grad.argtypes = abi.SHADOW_GRAD_ARGTYPES
         L.srz_frameset_perspective.argtypes = abi.PERSPECTIVE_ARGTYPES
@@ -722,6 +725,30 @@ class FrameSet:
         self.ctx._check(lib().srz_frameset_composite_grad(self.ctx.h, self.h, arr, len(layers), n_ch, C.c_void_p(d_bg_ptr or None),
                                                           int(want_through), C.c_void_p(d_gout_ptr), ptrs(d_gcolor_ptrs), ptrs(d_galpha_ptrs),
                                                           C.c_void_p(d_gbg_ptr or None), flags, _stream(stream)))
+
+    def texture_set(self, d_vis_ptr, d_uv_ptr, slots, d_batch_slot_ptr, n_batch_slot, n_ch, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR,
+                    stream=None):
+        """texture() with the texture of each pixel picked by its owner's batch: slots is a sequence of 1 .. abi.TEXSET_MAX tuples
+        (d_tex_ptr, d_gtex_ptr (unused here: None), tex_w, tex_h, tex_frames, mode), each a texture [tex_frames][tex_h][tex_w][n_ch] as
+        texture() takes it; d_batch_slot_ptr is DEVICE memory of n_batch_slot bytes, batch (a sceneset: draw) → slot, one map for
+        every frame.  A pixel whose batch lies beyond the map or whose byte names no slot (abi.TEXSET_NONE) gets zeros, like one
+        whose uv is not finite → d_out [frame][n_ch][local_rows][width] (include/srz.h states the rule).  Asynchronous."""
+        slots = list(slots)
+        arr = abi.texset_slots_array(slots)
+        self.ctx._check(lib().srz_frameset_texture_set(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_uv_ptr), arr, len(slots),
+                                                       C.c_void_p(d_batch_slot_ptr), n_batch_slot, n_ch, C.c_void_p(d_out_ptr), out_bytes,
+                                                       flags, _stream(stream)))
+
+    def texture_set_grad(self, d_vis_ptr, d_uv_ptr, d_gout_ptr, slots, d_batch_slot_ptr, n_batch_slot, n_ch, d_guv_ptr, flags=abi.FUSED_CLEAR,
+                         stream=None):
+        """the backward of texture_set: d_gout [frame][n_ch][local_rows][width] → ADDED into every slot's d_gtex_ptr that is not None
+        (that slot's texture shape; float atomics: not bit-reproducible) and / or written to d_guv [frame][2][local_rows][width]
+        (deterministic; needs every slot's d_tex_ptr).  d_guv_ptr may be None / 0 if some slot asks for its gradient.  Asynchronous."""
+        slots = list(slots)
+        arr = abi.texset_slots_array(slots)
+        self.ctx._check(lib().srz_frameset_texture_set_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_uv_ptr),
+                                                            C.c_void_p(d_gout_ptr), arr, len(slots), C.c_void_p(d_batch_slot_ptr),
+                                                            n_batch_slot, n_ch, C.c_void_p(d_guv_ptr or None), flags, _stream(stream)))
 
     def update_shading(self, frames):
         """new eye, ka, ks, p, kh, kn, lights, flags and batch shaders / textures for a set made from abi.Frame's, triangles untouched

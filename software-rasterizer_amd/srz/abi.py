@@ -102,6 +102,11 @@ IBL_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp
 COMPOSITE_MAX = 8  # srz_frameset_composite: the most layers of one call (SRZ_COMPOSITE_MAX)
 COMPOSITE_ARGTYPES = [_vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, C.c_size_t, _u32, _vp]
 COMPOSITE_GRAD_ARGTYPES = [_vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp]
+# the prototypes of srz_frameset_texture_set / _texture_set_grad (argtypes; both return int), set on the library by srz.lib()
+TEXSET_MAX = 8  # srz_frameset_texture_set: the most slots of one call (SRZ_TEXSET_MAX)
+TEXSET_NONE = 0xff  # the conventional "no slot" byte of the batch -> slot map (SRZ_TEXSET_NONE)
+TEXTURE_SET_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
+TEXTURE_SET_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _u32, _vp]
 
 # numpy view of srz_tri (96 B): pos[3][3], nrm[3][3], uv[3][2]
 TRI_DTYPE = np.dtype([("pos", "<f4", (3, 3)), ("nrm", "<f4", (3, 3)), ("uv", "<f4", (3, 2))])
@@ -144,6 +149,20 @@ def composite_layers_array(layers):
     arr = (SrzCompositeLayer * max(1, len(layers)))()
     for i, (vis, color, alpha, opacity) in enumerate(layers):
         arr[i] = SrzCompositeLayer(vis or None, color or None, alpha or None, float(opacity), 0)
+    return arr
+
+
+class SrzTexsetSlot(C.Structure):
+    """srz_texset_slot: one texture of srz_frameset_texture_set (d_gtex: the backward's, None = this slot's gradient is not wanted)"""
+    _fields_ = [("d_tex", C.c_void_p), ("d_gtex", C.c_void_p), ("tex_w", C.c_uint32), ("tex_h", C.c_uint32),
+                ("tex_frames", C.c_uint32), ("mode", C.c_uint32)]
+
+
+def texset_slots_array(slots):
+    """slots: (tex_ptr or None, gtex_ptr or None, tex_w, tex_h, tex_frames, mode) per slot → a ctypes array of srz_texset_slot"""
+    arr = (SrzTexsetSlot * max(1, len(slots)))()
+    for i, (tex, gtex, w, h, frames, mode) in enumerate(slots):
+        arr[i] = SrzTexsetSlot(tex or None, gtex or None, int(w), int(h), int(frames), int(mode))
     return arr
 
 

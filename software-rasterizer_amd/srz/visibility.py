@@ -620,6 +620,90 @@ def texture(fs, vis, tex, uv, wrap=False, stream=None):
     return _Texture.apply(tex, uv, fs, vis, wrap, stream)
 
 
+def _each(flag, n):
+    """a bool for every one of n textures, or one bool per texture (zip below refuses another count)"""
+    return [bool(flag)] * n if isinstance(flag, bool) else [bool(f) for f in flag]
+
+
+def _slot_map(batch_slot, device):
+    """the batch → slot map of texture_set as a uint8 tensor: a uint8 tensor as it is (it must be on the device), else a sequence of
+    ints on `device` — None, and an entry that is no index at all (negative, beyond a byte), is "no slot" """
+    if isinstance(batch_slot, torch.Tensor) and batch_slot.dtype == torch.uint8:
+        return _on_device(batch_slot, "texture_set: batch_slot").reshape(-1).contiguous()
+    seq = batch_slot.tolist() if isinstance(batch_slot, torch.Tensor) else list(batch_slot)
+    return torch.tensor([int(s) if s is not None and 0 <= int(s) < abi.TEXSET_NONE else abi.TEXSET_NONE for s in seq], dtype=torch.uint8).to(device)
+
+
+def _texset_args(fs, texs, wrap):
+    """→ (the textures, contiguous; per texture (tex_frames, h, w); n_ch; per texture its mode).  texs[0] (None: no texture at all)
+    and, for its channel count, every other texture go through _lead_frames in texture_set's name, each through _tex_dims; the
+    counts (1 .. abi.TEXSET_MAX textures, 1 .. 65536 map entries) are the library's to refuse"""
+    texs = list(texs)
+    _lead_frames(fs, texs[0] if texs else None, (3, 4), "texture_set: texs[0]", "a CUDA float32 tensor [H, W, C] or [n_frames, H, W, C]")
+    dims = [_tex_dims(fs, t) for t in texs]
+    n_ch = dims[0][3]
+    for k, t in enumerate(texs[1:], 1):
+        _lead_frames(fs, t, (3, 4), f"texture_set: texs[{k}]", f"a CUDA float32 tensor [H, W, {n_ch}] or [n_frames, H, W, {n_ch}]: texs[0]'s channels",
+                     lambda t: t.shape[-1] == n_ch)
+    modes = [abi.TEX_WRAP if w else abi.TEX_CLAMP for _, w in zip(texs, _each(wrap, len(texs)), strict=True)]
+    return [t.contiguous() for t in texs], [d[:3] for d in dims], n_ch, modes
+
+
+def texture_set_grad(fs, vis, texs, uv, gout, batch_slot, wrap=False, want_gtex=True, want_guv=True, stream=None):
+    """the backward of texture_set(fs, vis, texs, uv, batch_slot, wrap) by one FrameSet.texture_set_grad call: gout [n_frames, C,
+    rows, W] → (gtexs, guv): a list with one entry per texture, of its shape — a sum of float atomics into zeros, not
+    bit-reproducible between runs — and guv [n_frames, 2, rows, W], deterministic; an entry None where not wanted (the library
+    refuses a call that wants nothing).  want_gtex is a bool or one bool per texture.  stream: a raw stream handle, None = torch's
+    current stream."""
+    uv = _plane(fs, uv, 2, "texture_set: uv")
+    texs, dims, n_ch, modes = _texset_args(fs, texs, wrap)
+    slot_map = _slot_map(batch_slot, uv.device)
+    gout = _gout(fs, gout, n_ch, "texture_set_grad")
+    gtexs = [torch.zeros_like(t) if w else None for t, w in zip(texs, _each(want_gtex, len(texs)), strict=True)]
+    guv = torch.empty_like(uv) if want_guv else None
+    slots = [(t.data_ptr(), _ptr(g), w, h, frames, m) for t, g, (frames, h, w), m in zip(texs, gtexs, dims, modes)]
+    fs.texture_set_grad(_vis_ptr(fs, vis, "texture_set_grad"), uv.data_ptr(), gout.data_ptr(), slots, slot_map.data_ptr(), slot_map.numel(),
+                        n_ch, _ptr(guv), abi.FUSED_CLEAR, _stream_ptr(stream))
+    return gtexs, guv
+
+
+class _TextureSet(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, fs, vis, slot_map, wrap, stream, uv, *texs):
+        uv = _plane(fs, uv, 2, "texture_set: uv")
+        texs, dims, n_ch, modes = _texset_args(fs, texs, wrap)
+        out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=texs[0].device)
+        slots = [(t.data_ptr(), None, w, h, frames, m) for t, (frames, h, w), m in zip(texs, dims, modes)]
+        fs.texture_set(_vis_ptr(fs, vis, "texture_set"), uv.data_ptr(), slots, slot_map.data_ptr(), slot_map.numel(), n_ch, out.data_ptr(),
+                       fs.interpolate_bytes(n_ch), abi.FUSED_CLEAR, _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.slot_map, ctx.wrap, ctx.stream = fs, vis, slot_map, wrap, stream
+        ctx.save_for_backward(uv, *texs)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        uv, *texs = ctx.saved_tensors
+        need_uv, need_tex = ctx.needs_input_grad[5], list(ctx.needs_input_grad[6:])
+        gtexs, guv = [None] * len(texs), None
+        if need_uv or any(need_tex):  # one call, asking only for what is needed
+            gtexs, guv = texture_set_grad(ctx.fs, ctx.vis, texs, uv, gout, ctx.slot_map, ctx.wrap, need_tex, need_uv, ctx.stream)
+        return (None, None, None, None, None, guv, *gtexs)
+
+
+def texture_set(fs, vis, texs, uv, batch_slot, wrap=False, stream=None):
+    """texture() for a scene of several materials in ONE pass: the texture of each pixel is picked by its owner's batch
+    (FrameSet.texture_set; include/srz.h states the rule).  texs is a sequence of 1 .. 8 CUDA float32 tensors [H, W, C] or
+    [n_frames, H, W, C], each of its own size, C common; batch_slot maps a batch of a frame (a sceneset: a draw) to an index into
+    texs — a sequence of ints (None, or an int that is no index: no slot) or a uint8 CUDA tensor (abi.TEXSET_NONE: no slot), one
+    map of 1 .. 65536 entries for every frame; wrap is a bool or one per texture; uv as texture() takes it → [n_frames, C, rows, W] float32: per pixel texture(fs, vis,
+    texs[batch_slot[batch]], uv, wrap), zeros where nobody owns the pixel, its uv is not finite, or its batch has no slot (beyond
+    the map, None, an index outside texs).  Differentiable with respect to every texture that requires grad (float atomics into a
+    zeroed tensor: not bit-reproducible between runs) and to uv (deterministic); backward is one texture_set_grad call that asks only
+    for the gradients some input needs.  stream: a raw stream handle, None = torch's current stream."""
+    slot_map = _slot_map(batch_slot, uv.device if isinstance(uv, torch.Tensor) else "cuda")  # (everything else is checked in forward, once)
+    return _TextureSet.apply(fs, vis, slot_map, wrap, stream, uv, *texs)
+
+
 def cube_dirs(n, device=None):
     """the unit direction of every texel centre of an n x n cube map → [6, n, n, 3] float32 (face, row, column; faces +X -X +Y -Y +Z
     -Z, a face's point n + s su + t sv with s = (2 x + 1) / n - 1, t = (2 y + 1) / n - 1: include/srz.h has the table): what a caller
