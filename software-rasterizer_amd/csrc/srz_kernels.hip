@@ -5028,40 +5028,115 @@ __global__ __launch_bounds__(256) void k_tex(TexArgs a) {
 // Every thread of the workgroup reaches every barrier: a thread outside the frame samples nothing instead of moving on.
 // ================================================================================================================
 constexpr uint32_t TG_SLOT_BITS = 11, TG_SLOTS = 1u << TG_SLOT_BITS, TG_PROBES = 8, TG_NONE = 0xffffffffu;
-struct TexTable {
-  uint32_t key[TG_SLOTS];  // texel index + 1; 0: free
+__device__ __forceinline__ void lds_add(float *p, float v) { unsafeAtomicAdd(p, v); }
+// The table, for every kernel that scatters into a caller's texture.  WHO is the kernel's argument struct and only a tag: it gives
+// each kernel its own instantiation of the members, and with that the registers it had with a copy of its own, where the same
+// helpers shared by name moved them (DESIGN.md §4 has the figures, and what the pieces below cost in instructions).  VALS: the
+// values per slot, ATTR_CHUNK (49 156 bytes of LDS), or 1 for k_shadow_grad's one channel (24 KB).  A key is the 32-bit number,
+// below 2^32 - 1, that names a texel to the kernel: a texel index (below SRZ_TEX_MAX_SIZE^2 = 2^28; a cube's below 6 * 2^28), an
+// offset in a cube's pyramid or a (slot, texel) pair (both below 2^31).
+// Every thread of the workgroup calls init (a barrier follows it), flush and release (they hold their barriers).
+// The helpers take plain values and are straight-line per channel; the chunk's loops stay in the kernels.  That is measured, not
+// taste: an adder that took its destination as a closure, or a helper that held the loop over the chunk, changed the registers of
+// half the kernels (k_background_grad 169 -> 101 VGPRs with 3 more spilled SGPRs; one form did not compile), these do not.
+template <class WHO, uint32_t VALS> struct TexelTable {
+  uint32_t key[TG_SLOTS];  // the texel's key + 1; 0: free
   uint32_t used[TG_SLOTS]; // the slots taken, in arrival order
   uint32_t n_used;
-  float val[TG_SLOTS * ATTR_CHUNK]; // [slot][channel of the chunk]
-};
-__device__ __forceinline__ void lds_add(float *p, float v) { unsafeAtomicAdd(p, v); }
-// the slot of texel `idx` in the tile's table, taken if need be; TG_NONE: no room within TG_PROBES
-__device__ __forceinline__ uint32_t tg_slot(TexTable &tb, uint32_t idx) {
-  const uint32_t key = idx + 1u; // (idx < SRZ_TEX_MAX_SIZE^2 = 2^28)
-  uint32_t h = (key * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
-  for (uint32_t p = 0; p < TG_PROBES; ++p) {
-    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
-    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
-    if (old == 0u || old == key) return h;
-    h = (h + 1u) & (TG_SLOTS - 1u);
+  float val[TG_SLOTS * VALS]; // [slot][channel of the chunk]
+  __device__ __forceinline__ void init(uint32_t tid) {
+    for (uint32_t i = tid; i < TG_SLOTS; i += 256) key[i] = 0u;
+    for (uint32_t i = tid; i < TG_SLOTS * VALS; i += 256) val[i] = 0.0f;
+    if (tid == 0) n_used = 0u;
   }
-  return TG_NONE;
+  // the slot of texel `idx`, taken if need be; TG_NONE: no room within TG_PROBES
+  __device__ __forceinline__ uint32_t slot(uint32_t idx) {
+    const uint32_t k = idx + 1u;
+    uint32_t h = (k * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
+    for (uint32_t p = 0; p < TG_PROBES; ++p) {
+      const uint32_t old = atomicCAS(&key[h], 0u, k);
+      if (old == 0u) used[atomicAdd(&n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
+      if (old == 0u || old == k) return h;
+      h = (h + 1u) & (TG_SLOTS - 1u);
+    }
+    return TG_NONE;
+  }
+  // v to value i of slot `s`; without a slot straight to memory, to channel ch of texel idx in `mem` (C channels a texel)
+  __device__ __forceinline__ void add(uint32_t s, uint32_t i, float v, float *mem, uint32_t idx, uint32_t C, uint32_t ch) {
+    if (s != TG_NONE) lds_add(&val[s * VALS + i], v);
+    else global_add(mem + (size_t)idx * C + ch, v);
+  }
+  // step 4: the values of the chunk at channel c0 (nc of them) into memory, lanes in channel order within a texel, texel after
+  // texel; at(idx): where texel idx lies in memory.  -> n_used, for release
+  template <class At> __device__ __forceinline__ uint32_t flush(uint32_t tid, uint32_t c0, uint32_t nc, At at) {
+    __syncthreads();
+    const uint32_t n = n_used;
+    for (uint32_t i = tid; i < n * VALS; i += 256) {
+      const uint32_t s = used[i / VALS], e = i % VALS;
+      const float v = val[s * VALS + e];
+      val[s * VALS + e] = 0.0f;
+      if (e < nc) global_add(at(key[s] - 1u) + c0 + e, v);
+    }
+    __syncthreads();
+    return n;
+  }
+  // the tile's keys go; every thread has read n_used before the last flush's last barrier
+  __device__ __forceinline__ void release(uint32_t tid, uint32_t n) {
+    for (uint32_t i = tid; i < n; i += 256) key[used[i]] = 0u;
+    if (tid == 0) n_used = 0u;
+    __syncthreads();
+  }
+};
+// THE CHANNEL LOOP'S PIECES
+// gout of one channel for a thread's quad; words of pixels outside `mask` are loaded with their quad at most, never used
+__device__ __forceinline__ void gout_quad(const float *p, bool whole, uint32_t mask, float4 &g) {
+  if (whole) {
+    g = *reinterpret_cast<const float4 *>(p);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (mask & (1u << k)) quad_at(g, k) = p[k];
+  }
 }
-__device__ __forceinline__ void tg_add(TexTable &tb, uint32_t slot, float *gtex, uint32_t idx, uint32_t C, uint32_t ch, uint32_t i, float v) {
-  if (slot != TG_NONE) lds_add(&tb.val[slot * ATTR_CHUNK + i], v);
-  else global_add(gtex + (size_t)idx * C + ch, v);
+// one channel of the bilinear sample's derivatives: gi times d/dtx into au, times d/dty into av; -> the sample.  The products
+// associate as the oracles have them
+__device__ __forceinline__ float bilerp_chain(const SRZ_CAS float *p00, const SRZ_CAS float *p01, const SRZ_CAS float *p10, const SRZ_CAS float *p11,
+                                              float tx, float ty, float gi, float &au, float &av) {
+  const float t00 = *p00, t01 = *p01, t10 = *p10, t11 = *p11;
+  const float top = fmaf_(tx, t01 - t00, t00), bot = fmaf_(tx, t11 - t10, t10);
+  au = fmaf_(gi, fmaf_(ty, (t11 - t10) - (t01 - t00), t01 - t00), au);
+  av = fmaf_(gi, bot - top, av);
+  return fmaf_(ty, bot - top, top);
+}
+// the four corner-weight adds of one pixel and channel: w[corner] * gi into the corners' slots `s`, a corner without one straight
+// to memory (TexelTable::add).  lw: the pixel's weight of this mip level
+struct CornerW {
+  float w00, w01, w10, w11;
+};
+__device__ __forceinline__ CornerW corner_weights(float tx, float ty) {
+  return {(1.0f - tx) * (1.0f - ty), tx * (1.0f - ty), (1.0f - tx) * ty, tx * ty};
+}
+__device__ __forceinline__ CornerW corner_weights(float tx, float ty, float lw) {
+  const CornerW w = corner_weights(tx, ty);
+  return {w.w00 * lw, w.w01 * lw, w.w10 * lw, w.w11 * lw};
+}
+template <class Table, class Tap>
+__device__ __forceinline__ void corner_adds(Table &tb, const uint32_t *s, const Tap &p, const CornerW &w, float gi, uint32_t i, float *mem, uint32_t C,
+                                            uint32_t ch) {
+  tb.add(s[0], i, w.w00 * gi, mem, p.i00, C, ch);
+  tb.add(s[1], i, w.w01 * gi, mem, p.i01, C, ch);
+  tb.add(s[2], i, w.w10 * gi, mem, p.i10, C, ch);
+  tb.add(s[3], i, w.w11 * gi, mem, p.i11, C, ch);
 }
 __global__ __launch_bounds__(256) void k_tex_grad(TexArgs a) {
-  __shared__ TexTable tb;
+  __shared__ TexelTable<TexArgs, ATTR_CHUNK> tb;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
   const uint32_t tpf = a.n_local_bands * a.tiles_x, n_items = a.n_frames * tpf;
   const uint32_t C = a.n_ch;
   const bool want_tex = a.gtex != nullptr, want_uv = a.out != nullptr;
   if (want_tex) {
-    for (uint32_t i = tid; i < TG_SLOTS; i += 256) tb.key[i] = 0u;
-    for (uint32_t i = tid; i < TG_SLOTS * ATTR_CHUNK; i += 256) tb.val[i] = 0.0f;
-    if (tid == 0) tb.n_used = 0u;
+    tb.init(tid);
     __syncthreads();
   }
   // workgroup b walks the frames f ≡ b mod 8 tile by tile (fewer than 8 frames: every 8th tile): an inline copy of pass_walk
@@ -5098,29 +5173,22 @@ __global__ __launch_bounds__(256) void k_tex_grad(TexArgs a) {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
         if (smp & (1u << k))
-          slot[k][0] = tg_slot(tb, tap[k].i00), slot[k][1] = tg_slot(tb, tap[k].i01), slot[k][2] = tg_slot(tb, tap[k].i10),
-          slot[k][3] = tg_slot(tb, tap[k].i11);
+          slot[k][0] = tb.slot(tap[k].i00), slot[k][1] = tb.slot(tap[k].i01), slot[k][2] = tb.slot(tap[k].i10), slot[k][3] = tb.slot(tap[k].i11);
     }
+    const auto at = [=](uint32_t idx) { return gtex + (size_t)idx * C; };
     float au[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f};
     uint32_t n_used = 0u;
     // ---- 3. the channels, ATTR_CHUNK at a time
     for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
       const uint32_t nc = min(ATTR_CHUNK, C - c0);
-      float4 g[ATTR_CHUNK]; // gout of the chunk's channels; words of pixels that are not sampled are loaded with their quad at most, never used
+      float4 g[ATTR_CHUNK];
 #pragma unroll
       for (uint32_t i = 0; i < ATTR_CHUNK; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (smp != 0u) {
 #pragma unroll
         for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
           if (i >= nc) break;
-          const float *p = gg + (size_t)(c0 + i) * rc.plane;
-          if (whole) {
-            g[i] = *reinterpret_cast<const float4 *>(p);
-          } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-              if (smp & (1u << k)) quad_at(g[i], k) = p[k];
-          }
+          gout_quad(gg + (size_t)(c0 + i) * rc.plane, whole, smp, g[i]);
         }
       }
 #pragma unroll
@@ -5131,45 +5199,18 @@ __global__ __launch_bounds__(256) void k_tex_grad(TexArgs a) {
           const SRZ_CAS float *p10 = tex + (size_t)tap[k].i10 * C + c0, *p11 = tex + (size_t)tap[k].i11 * C + c0;
 #pragma unroll
           for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
-            if (i < nc) {
-              const float gi = quad_at(g[i], k), t00 = p00[i], t01 = p01[i], t10 = p10[i], t11 = p11[i];
-              const float top = fmaf_(tap[k].tx, t01 - t00, t00), bot = fmaf_(tap[k].tx, t11 - t10, t10);
-              au[k] = fmaf_(gi, fmaf_(tap[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au[k]);
-              av[k] = fmaf_(gi, bot - top, av[k]);
-            }
+            if (i < nc) bilerp_chain(p00 + i, p01 + i, p10 + i, p11 + i, tap[k].tx, tap[k].ty, quad_at(g[i], k), au[k], av[k]);
         }
         if (want_tex) {
-          const float tx_ = tap[k].tx, ty_ = tap[k].ty;
-          const float w00 = (1.0f - tx_) * (1.0f - ty_), w01 = tx_ * (1.0f - ty_), w10 = (1.0f - tx_) * ty_, w11 = tx_ * ty_;
+          const CornerW w = corner_weights(tap[k].tx, tap[k].ty);
 #pragma unroll
           for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
-            if (i < nc) {
-              const float gi = quad_at(g[i], k);
-              tg_add(tb, slot[k][0], gtex, tap[k].i00, C, c0 + i, i, w00 * gi);
-              tg_add(tb, slot[k][1], gtex, tap[k].i01, C, c0 + i, i, w01 * gi);
-              tg_add(tb, slot[k][2], gtex, tap[k].i10, C, c0 + i, i, w10 * gi);
-              tg_add(tb, slot[k][3], gtex, tap[k].i11, C, c0 + i, i, w11 * gi);
-            }
+            if (i < nc) corner_adds(tb, slot[k], tap[k], w, quad_at(g[i], k), i, gtex, C, c0 + i);
         }
       }
-      if (want_tex) {
-        // ---- 4. the table's values of this chunk into memory: lanes in channel order within a texel
-        __syncthreads();
-        n_used = tb.n_used;
-        for (uint32_t i = tid; i < n_used * ATTR_CHUNK; i += 256) {
-          const uint32_t s = tb.used[i / ATTR_CHUNK], e = i % ATTR_CHUNK;
-          const float v = tb.val[s * ATTR_CHUNK + e];
-          tb.val[s * ATTR_CHUNK + e] = 0.0f;
-          if (e < nc) global_add(gtex + (size_t)(tb.key[s] - 1u) * C + c0 + e, v);
-        }
-        __syncthreads();
-      }
+      if (want_tex) n_used = tb.flush(tid, c0, nc, at); // ---- 4. the table's values of this chunk into memory
     }
-    if (want_tex) { // the tile's keys go; every thread has read n_used before the chunk's last barrier
-      for (uint32_t i = tid; i < n_used; i += 256) tb.key[tb.used[i]] = 0u;
-      if (tid == 0) tb.n_used = 0u;
-      __syncthreads();
-    }
+    if (want_tex) tb.release(tid, n_used);
     // ---- 5. du, dv: whole quads (fused clear, or four owners), else the owned pixels only; an owner that is not sampled: (0, 0)
     if (want_uv && inside && (own != 0u || fused)) {
       float4 du = make_float4(0.f, 0.f, 0.f, 0.f), dv = du;
@@ -5203,12 +5244,27 @@ __global__ __launch_bounds__(256) void k_tex_grad(TexArgs a) {
 // Every float -> int conversion follows s, t in [-1, 1] (the IEEE division of a component by the largest), so x0, y0 lie in
 // [-1, n - 1]; the integer clamp behind it never changes a value and keeps every index inside the cube whatever the division did.
 // ================================================================================================================
+struct CubeFace {
+  float s, t, inv; // the in-face coordinates and 1 / |major component|
+  uint32_t major;  // the major axis, bit 2: its component is positive
+};
 struct CubeTap {
   uint32_t i00, i01, i10, i11; // resolved texels (face * n + row) * n + column of the corners (y0, x0), (y0, x1), (y1, x0), (y1, x1)
   float tx, ty;
-  float s, t, inv;             // the backward's: the in-face coordinates and 1 / |major component|
-  uint32_t major;              // the major axis, bit 2: its component is positive
+  CubeFace f;                  // the backward's
 };
+// srz_frameset_texture_cube_grad's chain from au, av at one level (half_n = 0.5f * (float)N of that level) to the direction
+__device__ __forceinline__ void cube_gdir(const CubeFace &c, float au, float av, float half_n, float (&g)[3]) {
+  const float gs = au * half_n, gt = av * half_n, inv = c.inv;
+  const float g_sc = gs * inv, g_tc = gt * inv, g_ma = -(fmaf_(gs, c.s, gt * c.t) * inv);
+  const uint32_t m = c.major & 3u;
+  const bool pos = (c.major & 4u) != 0u;
+  const float g_m = pos ? g_ma : -g_ma;
+  // su, sv of the face, undone: +X (-z, -y)  -X (z, -y)  +Y (x, z)  -Y (x, -z)  +Z (x, -y)  -Z (-x, -y)
+  g[0] = m == 0u ? g_m : m == 1u ? g_sc : (pos ? g_sc : -g_sc);
+  g[1] = m == 1u ? g_m : -g_tc;
+  g[2] = m == 0u ? (pos ? -g_sc : g_sc) : m == 1u ? (pos ? g_tc : -g_tc) : g_m;
+}
 // the seam rows of a face, one byte per side (x = -1, x = n, y = -1, y = n): the neighbour face | which of its indices is fixed
 // (8: row, else column) | fixed at n - 1 (16, else 0) | the index along the edge mirrored (32).  tests/cube_ref.c holds the same
 // 24 rows unpacked; tests/test_cube_ref.py derives them from the faces' axes
@@ -5267,8 +5323,8 @@ __device__ __forceinline__ void cube_corners(uint32_t major, float s, float t, u
 }
 // the tap of one direction; false: not sampled
 __device__ __forceinline__ bool cube_tap(float dx, float dy, float dz, uint32_t N, CubeTap &p) {
-  if (!cube_face(dx, dy, dz, p.s, p.t, p.inv, p.major)) return false;
-  cube_corners(p.major, p.s, p.t, N, p.i00, p.i01, p.i10, p.i11, p.tx, p.ty);
+  if (!cube_face(dx, dy, dz, p.f.s, p.f.t, p.f.inv, p.f.major)) return false;
+  cube_corners(p.f.major, p.f.s, p.f.t, N, p.i00, p.i01, p.i10, p.i11, p.tx, p.ty);
   return true;
 }
 // what k_cube and k_cube_grad do alike in front of their channel loops: the owners, the directions of a quad with an owner, the
@@ -5330,36 +5386,17 @@ __global__ __launch_bounds__(256) void k_cube(CubeArgs a) {
 // into the cube's gradient (gtex) at the RESOLVED texels — a tile that straddles a cube edge adds into both faces —, and the
 // gradient with respect to the direction (gdir: k_tex_grad's au, av chains, then the chain through s = sc / ma, t = tc / ma; from
 // registers, no atomics).  k_tex_grad's structure on the passes' helpers (pass_walk<true>: every thread of the workgroup reaches
-// every barrier, one outside the frame samples nothing): the tile's open-addressed table of distinct texels in LDS (TexTable,
-// keyed on the cube-wide texel index + 1), the slots found once in front of the channel loop, LDS float adds per chunk, the dense
+// every barrier, one outside the frame samples nothing): the tile's open-addressed table of distinct texels in LDS (TexelTable,
+// keyed on the cube-wide texel index), the slots found once in front of the channel loop, LDS float adds per chunk, the dense
 // flush with global_atomic_add_f32, a corner without a slot adding straight to memory.
-// (cg_slot and cg_add are COPIES of tg_slot and tg_add, and step 4 of k_tex_grad's flush: shared helpers have moved k_tex_grad's
-// registers before (k_tex_mip_grad's note); a fix goes into all of them)
 // ================================================================================================================
-__device__ __forceinline__ uint32_t cg_slot(TexTable &tb, uint32_t idx) {
-  const uint32_t key = idx + 1u; // (idx < 6 * SRZ_TEX_MAX_SIZE^2 = 6 * 2^28)
-  uint32_t h = (key * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
-  for (uint32_t p = 0; p < TG_PROBES; ++p) {
-    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
-    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
-    if (old == 0u || old == key) return h;
-    h = (h + 1u) & (TG_SLOTS - 1u);
-  }
-  return TG_NONE;
-}
-__device__ __forceinline__ void cg_add(TexTable &tb, uint32_t slot, float *gtex, uint32_t idx, uint32_t C, uint32_t ch, uint32_t i, float v) {
-  if (slot != TG_NONE) lds_add(&tb.val[slot * ATTR_CHUNK + i], v);
-  else global_add(gtex + (size_t)idx * C + ch, v);
-}
 __global__ __launch_bounds__(256) void k_cube_grad(CubeArgs a) {
-  __shared__ TexTable tb;
+  __shared__ TexelTable<CubeArgs, ATTR_CHUNK> tb;
   const uint32_t tid = threadIdx.x;
   const uint32_t C = a.n_ch;
   const bool want_tex = a.gtex != nullptr, want_dir = a.out != nullptr;
   if (want_tex) {
-    for (uint32_t i = tid; i < TG_SLOTS; i += 256) tb.key[i] = 0u;
-    for (uint32_t i = tid; i < TG_SLOTS * ATTR_CHUNK; i += 256) tb.val[i] = 0.0f;
-    if (tid == 0) tb.n_used = 0u;
+    tb.init(tid);
     __syncthreads();
   }
   pass_walk<true>(a, [&](const PassTile &t) { // (a thread outside the frame owns nothing, and still meets the barriers)
@@ -5378,29 +5415,22 @@ __global__ __launch_bounds__(256) void k_cube_grad(CubeArgs a) {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
         if (smp & (1u << k))
-          slot[k][0] = cg_slot(tb, tap[k].i00), slot[k][1] = cg_slot(tb, tap[k].i01), slot[k][2] = cg_slot(tb, tap[k].i10),
-          slot[k][3] = cg_slot(tb, tap[k].i11);
+          slot[k][0] = tb.slot(tap[k].i00), slot[k][1] = tb.slot(tap[k].i01), slot[k][2] = tb.slot(tap[k].i10), slot[k][3] = tb.slot(tap[k].i11);
     }
+    const auto at = [=](uint32_t idx) { return gtex + (size_t)idx * C; };
     float au[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f};
     uint32_t n_used = 0u;
     // ---- 3. the channels, ATTR_CHUNK at a time
     for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
       const uint32_t nc = min(ATTR_CHUNK, C - c0);
-      float4 g[ATTR_CHUNK]; // gout of the chunk's channels; words of pixels that are not sampled are loaded with their quad at most, never used
+      float4 g[ATTR_CHUNK];
 #pragma unroll
       for (uint32_t i = 0; i < ATTR_CHUNK; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (smp != 0u) {
 #pragma unroll
         for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
           if (i >= nc) break;
-          const float *p = gg + (size_t)(c0 + i) * rc.plane;
-          if (t.whole) {
-            g[i] = *reinterpret_cast<const float4 *>(p);
-          } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-              if (smp & (1u << k)) quad_at(g[i], k) = p[k];
-          }
+          gout_quad(gg + (size_t)(c0 + i) * rc.plane, t.whole, smp, g[i]);
         }
       }
 #pragma unroll
@@ -5411,45 +5441,18 @@ __global__ __launch_bounds__(256) void k_cube_grad(CubeArgs a) {
           const SRZ_CAS float *p10 = tex + (size_t)tap[k].i10 * C + c0, *p11 = tex + (size_t)tap[k].i11 * C + c0;
 #pragma unroll
           for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
-            if (i < nc) {
-              const float gi = quad_at(g[i], k), t00 = p00[i], t01 = p01[i], t10 = p10[i], t11 = p11[i];
-              const float top = fmaf_(tap[k].tx, t01 - t00, t00), bot = fmaf_(tap[k].tx, t11 - t10, t10);
-              au[k] = fmaf_(gi, fmaf_(tap[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au[k]);
-              av[k] = fmaf_(gi, bot - top, av[k]);
-            }
+            if (i < nc) bilerp_chain(p00 + i, p01 + i, p10 + i, p11 + i, tap[k].tx, tap[k].ty, quad_at(g[i], k), au[k], av[k]);
         }
         if (want_tex) {
-          const float tx_ = tap[k].tx, ty_ = tap[k].ty;
-          const float w00 = (1.0f - tx_) * (1.0f - ty_), w01 = tx_ * (1.0f - ty_), w10 = (1.0f - tx_) * ty_, w11 = tx_ * ty_;
+          const CornerW w = corner_weights(tap[k].tx, tap[k].ty);
 #pragma unroll
           for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
-            if (i < nc) {
-              const float gi = quad_at(g[i], k);
-              cg_add(tb, slot[k][0], gtex, tap[k].i00, C, c0 + i, i, w00 * gi);
-              cg_add(tb, slot[k][1], gtex, tap[k].i01, C, c0 + i, i, w01 * gi);
-              cg_add(tb, slot[k][2], gtex, tap[k].i10, C, c0 + i, i, w10 * gi);
-              cg_add(tb, slot[k][3], gtex, tap[k].i11, C, c0 + i, i, w11 * gi);
-            }
+            if (i < nc) corner_adds(tb, slot[k], tap[k], w, quad_at(g[i], k), i, gtex, C, c0 + i);
         }
       }
-      if (want_tex) {
-        // ---- 4. the table's values of this chunk into memory: lanes in channel order within a texel
-        __syncthreads();
-        n_used = tb.n_used;
-        for (uint32_t i = tid; i < n_used * ATTR_CHUNK; i += 256) {
-          const uint32_t s = tb.used[i / ATTR_CHUNK], e = i % ATTR_CHUNK;
-          const float v = tb.val[s * ATTR_CHUNK + e];
-          tb.val[s * ATTR_CHUNK + e] = 0.0f;
-          if (e < nc) global_add(gtex + (size_t)(tb.key[s] - 1u) * C + c0 + e, v);
-        }
-        __syncthreads();
-      }
+      if (want_tex) n_used = tb.flush(tid, c0, nc, at); // ---- 4. the table's values of this chunk into memory
     }
-    if (want_tex) { // the tile's keys go; every thread has read n_used before the chunk's last barrier
-      for (uint32_t i = tid; i < n_used; i += 256) tb.key[tb.used[i]] = 0u;
-      if (tid == 0) tb.n_used = 0u;
-      __syncthreads();
-    }
+    if (want_tex) tb.release(tid, n_used);
     // ---- 5. the direction's gradient: whole quads (fused clear, or four owners), else the owned pixels only; an owner that is not
     // sampled: (0, 0, 0)
     if (want_dir && t.inside && (own != 0u || fused)) {
@@ -5459,15 +5462,9 @@ __global__ __launch_bounds__(256) void k_cube_grad(CubeArgs a) {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
         if (smp & (1u << k)) {
-          const float gs = au[k] * half_n, gt = av[k] * half_n, inv = tap[k].inv;
-          const float g_sc = gs * inv, g_tc = gt * inv, g_ma = -(fmaf_(gs, tap[k].s, gt * tap[k].t) * inv);
-          const uint32_t m = tap[k].major & 3u;
-          const bool pos = (tap[k].major & 4u) != 0u;
-          const float g_m = pos ? g_ma : -g_ma;
-          // su, sv of the face, undone: +X (-z, -y)  -X (z, -y)  +Y (x, z)  -Y (x, -z)  +Z (x, -y)  -Z (-x, -y)
-          quad_at(gd[0], k) = m == 0u ? g_m : m == 1u ? g_sc : (pos ? g_sc : -g_sc);
-          quad_at(gd[1], k) = m == 1u ? g_m : -g_tc;
-          quad_at(gd[2], k) = m == 0u ? (pos ? -g_sc : g_sc) : m == 1u ? (pos ? g_tc : -g_tc) : g_m;
+          float gk[3];
+          cube_gdir(tap[k].f, au[k], av[k], half_n, gk);
+          quad_at(gd[0], k) = gk[0], quad_at(gd[1], k) = gk[1], quad_at(gd[2], k) = gk[2];
         }
       quad_store_owned(t.out, t, gd, fused, own);
     }
@@ -5833,8 +5830,8 @@ __global__ __launch_bounds__(256) void k_background(BgArgs a) {
 
 // ================================================================================================================
 // k_background_grad — THE BACKWARD OF k_background (srz_frameset_background_grad): k_cube_grad's table and flush for the cube's
-// gradient (the tile's open-addressed table of distinct texels in LDS, copies of cg_slot / cg_add, the dense flush with float
-// atomics, a corner without a slot adding straight to memory) together with k_light_grad's per-tile partials for the ray block's:
+// gradient (the tile's open-addressed table of distinct texels in LDS, the dense flush with float atomics, a corner without a slot
+// adding straight to memory) together with k_light_grad's per-tile partials for the ray block's:
 // per sampled pixel gdir exactly as k_cube_grad forms it, its nine terms gdir_c, x gdir_c, y gdir_c summed in the FIXED tree — a
 // thread's four pixels left to right from +0, the xor butterfly, the four waves through LDS, a row of 9 per tile in work;
 // k_light_fold sums the tiles and, for a shared block, the frames.  pass_tiles / pass_tile as in k_light_grad (the tile's index is
@@ -5842,33 +5839,14 @@ __global__ __launch_bounds__(256) void k_background(BgArgs a) {
 // a tile without a sampled pixel (one barrier tells) writes +0 partials and skips the rest.  The build without WANT_RAY has no
 // partials, no shuffle and no barrier beyond the table's.
 // ================================================================================================================
-// (bg_slot and bg_add are COPIES of cg_slot and cg_add, as those are of tg_slot and tg_add: called from here as they are, the
-// shared helpers moved k_cube_grad's registers, 193 -> 243 VGPRs, as sharing has moved k_tex_grad's before; a fix goes into all of them)
-__device__ __forceinline__ uint32_t bg_slot(TexTable &tb, uint32_t idx) {
-  const uint32_t key = idx + 1u; // (idx < 6 * SRZ_TEX_MAX_SIZE^2 = 6 * 2^28)
-  uint32_t h = (key * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
-  for (uint32_t p = 0; p < TG_PROBES; ++p) {
-    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
-    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
-    if (old == 0u || old == key) return h;
-    h = (h + 1u) & (TG_SLOTS - 1u);
-  }
-  return TG_NONE;
-}
-__device__ __forceinline__ void bg_add(TexTable &tb, uint32_t slot, float *gtex, uint32_t idx, uint32_t C, uint32_t ch, uint32_t i, float v) {
-  if (slot != TG_NONE) lds_add(&tb.val[slot * ATTR_CHUNK + i], v);
-  else global_add(gtex + (size_t)idx * C + ch, v);
-}
 template <bool WANT_RAY> __global__ __launch_bounds__(256) void k_background_grad(BgArgs a) {
-  __shared__ TexTable tb;
+  __shared__ TexelTable<BgArgs, ATTR_CHUNK> tb;
   __shared__ float s_part[WANT_RAY ? 4 : 1][WANT_RAY ? 9 : 1];
   const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
   const uint32_t C = a.n_ch, tpf = a.n_local_bands * a.tiles_x;
   const bool want_tex = a.gtex != nullptr;
   if (want_tex) {
-    for (uint32_t i = tid; i < TG_SLOTS; i += 256) tb.key[i] = 0u;
-    for (uint32_t i = tid; i < TG_SLOTS * ATTR_CHUNK; i += 256) tb.val[i] = 0.0f;
-    if (tid == 0) tb.n_used = 0u;
+    tb.init(tid);
     __syncthreads();
   }
   pass_tiles(a, [&](uint32_t f, uint32_t ti) {
@@ -5896,29 +5874,22 @@ template <bool WANT_RAY> __global__ __launch_bounds__(256) void k_background_gra
 #pragma unroll
       for (int k = 0; k < 4; ++k)
         if (smp & (1u << k))
-          slot[k][0] = bg_slot(tb, tap[k].i00), slot[k][1] = bg_slot(tb, tap[k].i01), slot[k][2] = bg_slot(tb, tap[k].i10),
-          slot[k][3] = bg_slot(tb, tap[k].i11);
+          slot[k][0] = tb.slot(tap[k].i00), slot[k][1] = tb.slot(tap[k].i01), slot[k][2] = tb.slot(tap[k].i10), slot[k][3] = tb.slot(tap[k].i11);
     }
+    const auto at = [=](uint32_t idx) { return gtex + (size_t)idx * C; };
     float au[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f};
     uint32_t n_used = 0u;
     // ---- 3. the channels, ATTR_CHUNK at a time (k_cube_grad's loop)
     for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
       const uint32_t nc = min(ATTR_CHUNK, C - c0);
-      float4 g[ATTR_CHUNK]; // gout of the chunk's channels; words of pixels that are not sampled are loaded with their quad at most, never used
+      float4 g[ATTR_CHUNK];
 #pragma unroll
       for (uint32_t i = 0; i < ATTR_CHUNK; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (smp != 0u) {
 #pragma unroll
         for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
           if (i >= nc) break;
-          const float *p = gg + (size_t)(c0 + i) * rc.plane;
-          if (t.whole) {
-            g[i] = *reinterpret_cast<const float4 *>(p);
-          } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-              if (smp & (1u << k)) quad_at(g[i], k) = p[k];
-          }
+          gout_quad(gg + (size_t)(c0 + i) * rc.plane, t.whole, smp, g[i]);
         }
       }
 #pragma unroll
@@ -5929,45 +5900,18 @@ template <bool WANT_RAY> __global__ __launch_bounds__(256) void k_background_gra
           const SRZ_CAS float *p10 = tex + (size_t)tap[k].i10 * C + c0, *p11 = tex + (size_t)tap[k].i11 * C + c0;
 #pragma unroll
           for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
-            if (i < nc) {
-              const float gi = quad_at(g[i], k), t00 = p00[i], t01 = p01[i], t10 = p10[i], t11 = p11[i];
-              const float top = fmaf_(tap[k].tx, t01 - t00, t00), bot = fmaf_(tap[k].tx, t11 - t10, t10);
-              au[k] = fmaf_(gi, fmaf_(tap[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au[k]);
-              av[k] = fmaf_(gi, bot - top, av[k]);
-            }
+            if (i < nc) bilerp_chain(p00 + i, p01 + i, p10 + i, p11 + i, tap[k].tx, tap[k].ty, quad_at(g[i], k), au[k], av[k]);
         }
         if (want_tex) {
-          const float tx_ = tap[k].tx, ty_ = tap[k].ty;
-          const float w00 = (1.0f - tx_) * (1.0f - ty_), w01 = tx_ * (1.0f - ty_), w10 = (1.0f - tx_) * ty_, w11 = tx_ * ty_;
+          const CornerW w = corner_weights(tap[k].tx, tap[k].ty);
 #pragma unroll
           for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
-            if (i < nc) {
-              const float gi = quad_at(g[i], k);
-              bg_add(tb, slot[k][0], gtex, tap[k].i00, C, c0 + i, i, w00 * gi);
-              bg_add(tb, slot[k][1], gtex, tap[k].i01, C, c0 + i, i, w01 * gi);
-              bg_add(tb, slot[k][2], gtex, tap[k].i10, C, c0 + i, i, w10 * gi);
-              bg_add(tb, slot[k][3], gtex, tap[k].i11, C, c0 + i, i, w11 * gi);
-            }
+            if (i < nc) corner_adds(tb, slot[k], tap[k], w, quad_at(g[i], k), i, gtex, C, c0 + i);
         }
       }
-      if (want_tex) {
-        // ---- 4. the table's values of this chunk into memory: lanes in channel order within a texel
-        __syncthreads();
-        n_used = tb.n_used;
-        for (uint32_t i = tid; i < n_used * ATTR_CHUNK; i += 256) {
-          const uint32_t s = tb.used[i / ATTR_CHUNK], e = i % ATTR_CHUNK;
-          const float v = tb.val[s * ATTR_CHUNK + e];
-          tb.val[s * ATTR_CHUNK + e] = 0.0f;
-          if (e < nc) global_add(gtex + (size_t)(tb.key[s] - 1u) * C + c0 + e, v);
-        }
-        __syncthreads();
-      }
+      if (want_tex) n_used = tb.flush(tid, c0, nc, at); // ---- 4. the table's values of this chunk into memory
     }
-    if (want_tex) { // the tile's keys go; every thread has read n_used before the chunk's last barrier
-      for (uint32_t i = tid; i < n_used; i += 256) tb.key[tb.used[i]] = 0u;
-      if (tid == 0) tb.n_used = 0u;
-      __syncthreads();
-    }
+    if (want_tex) tb.release(tid, n_used);
     // ---- 5. the ray block's nine partial sums of the tile
     if (WANT_RAY) {
       float tr[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; // this lane's sums of r0[3], rx[3], ry[3]
@@ -5975,14 +5919,8 @@ template <bool WANT_RAY> __global__ __launch_bounds__(256) void k_background_gra
 #pragma unroll
       for (int k = 0; k < 4; ++k)
         if (smp & (1u << k)) {
-          const float gs = au[k] * half_n, gt = av[k] * half_n, inv = tap[k].inv;
-          const float g_sc = gs * inv, g_tc = gt * inv, g_ma = -(fmaf_(gs, tap[k].s, gt * tap[k].t) * inv);
-          const uint32_t m = tap[k].major & 3u;
-          const bool pos = (tap[k].major & 4u) != 0u;
-          const float g_m = pos ? g_ma : -g_ma;
-          // su, sv of the face, undone (k_cube_grad): +X (-z, -y)  -X (z, -y)  +Y (x, z)  -Y (x, -z)  +Z (x, -y)  -Z (-x, -y)
-          const float gd[3] = {m == 0u ? g_m : m == 1u ? g_sc : (pos ? g_sc : -g_sc), m == 1u ? g_m : -g_tc,
-                               m == 0u ? (pos ? -g_sc : g_sc) : m == 1u ? (pos ? g_tc : -g_tc) : g_m};
+          float gd[3]; // (k_cube_grad's gdir)
+          cube_gdir(tap[k].f, au[k], av[k], half_n, gd);
 #pragma unroll
           for (int c = 0; c < 3; ++c)
             tr[c] = tr[c] + gd[c], tr[3 + c] = tr[3 + c] + gx[k] * gd[c], tr[6 + c] = tr[6 + c] + fy * gd[c];
@@ -7495,35 +7433,18 @@ __global__ __launch_bounds__(256) void k_tex_mip(TexMipArgs a) {
 //   A. guv (from registers, deterministic): the bilinear pass's fma chains at level l0 and, where f != 0, at level l0 + 1, blended
 //      by f as the forward blends the samples;
 //   B. the texel adds, ONE LEVEL AT A TIME: the tile's pixels name the levels they touch in a word of LDS; for each of them the
-//      tile's table phase runs as k_tex_grad has it — the slots of the level's taps (TexTable keyed on the texel index WITHIN the
-//      level; mg_slot / mg_add are copies of tg_slot / tg_add), per chunk the LDS adds of (w_rc * lw) * gout, the dense flush into
-//      that level's gradient, the keys released.  The table's capacity thus counts the distinct texels of ONE level, which a minified tile's
-//      footprint keeps near its pixel count; the slot numbers of one level are live at a time (k_tex_grad's 16 registers, not 32).
-//      The flush is a COPY of k_tex_grad's step 4 (the project's rule for helpers); a fix goes into both.
+//      tile's table phase runs as k_tex_grad has it — the slots of the level's taps (TexelTable keyed on the texel index WITHIN the
+//      level), per chunk the LDS adds of (w_rc * lw) * gout, the dense flush into that level's gradient, the keys released.  The
+//      table's capacity thus counts the distinct texels of ONE level, which a minified tile's footprint keeps near its pixel
+//      count; the slot numbers of one level are live at a time (k_tex_grad's 16 registers, not 32).
 // A pixel takes part in level l with lw = 1 - f when l == l0 and with lw = f when l == l0 + 1 and f != 0; its tap of the level is
 // formed again from u and v (some thirty operations) rather than kept across the phases.
 // Every thread of the workgroup reaches every barrier: the levels of a tile are read from LDS by all, a thread outside the frame
 // samples nothing.  The level word rotates over three words by the tile's count, the next one zeroed in front of the barrier: one
 // barrier per tile in front of the levels' own.
 // ================================================================================================================
-// (COPIES of tg_slot and tg_add: shared with k_tex_grad they moved ITS registers, 171 -> 221 VGPRs; a fix goes into both)
-__device__ __forceinline__ uint32_t mg_slot(TexTable &tb, uint32_t idx) {
-  const uint32_t key = idx + 1u; // (idx < SRZ_TEX_MAX_SIZE^2 = 2^28)
-  uint32_t h = (key * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
-  for (uint32_t p = 0; p < TG_PROBES; ++p) {
-    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
-    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
-    if (old == 0u || old == key) return h;
-    h = (h + 1u) & (TG_SLOTS - 1u);
-  }
-  return TG_NONE;
-}
-__device__ __forceinline__ void mg_add(TexTable &tb, uint32_t slot, float *gtex, uint32_t idx, uint32_t C, uint32_t ch, uint32_t i, float v) {
-  if (slot != TG_NONE) unsafeAtomicAdd(&tb.val[slot * ATTR_CHUNK + i], v);
-  else unsafeAtomicAdd(gtex + (size_t)idx * C + ch, v);
-}
 __global__ __launch_bounds__(256) void k_tex_mip_grad(TexMipArgs a) {
-  __shared__ TexTable tb;
+  __shared__ TexelTable<TexMipArgs, ATTR_CHUNK> tb;
   __shared__ uint32_t levels[3];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ly = wave * 8 + (lane >> 3), lx4 = (lane & 7) * 4;
@@ -7531,9 +7452,7 @@ __global__ __launch_bounds__(256) void k_tex_mip_grad(TexMipArgs a) {
   const uint32_t C = a.n_ch;
   const bool want_tex = a.gtex != nullptr, want_uv = a.out != nullptr, wrap = a.mode == SRZ_TEX_WRAP;
   if (want_tex) {
-    for (uint32_t i = tid; i < TG_SLOTS; i += 256) tb.key[i] = 0u;
-    for (uint32_t i = tid; i < TG_SLOTS * ATTR_CHUNK; i += 256) tb.val[i] = 0.0f;
-    if (tid == 0) tb.n_used = 0u;
+    tb.init(tid);
     if (tid < 3) levels[tid] = 0u;
     __syncthreads();
   }
@@ -7592,14 +7511,7 @@ __global__ __launch_bounds__(256) void k_tex_mip_grad(TexMipArgs a) {
 #pragma unroll
         for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
           if (i >= nc) break;
-          const float *p = gg + (size_t)(c0 + i) * rc.plane;
-          if (whole) {
-            g[i] = *reinterpret_cast<const float4 *>(p);
-          } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-              if (smp & (1u << k)) quad_at(g[i], k) = p[k];
-          }
+          gout_quad(gg + (size_t)(c0 + i) * rc.plane, whole, smp, g[i]);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -7610,17 +7522,13 @@ __global__ __launch_bounds__(256) void k_tex_mip_grad(TexMipArgs a) {
               const float gi = quad_at(g[i], k);
               {
                 const SRZ_CAS float *q = p0[k] + c0 + i;
-                const float t00 = q[(size_t)t0[k].i00 * C], t01 = q[(size_t)t0[k].i01 * C], t10 = q[(size_t)t0[k].i10 * C], t11 = q[(size_t)t0[k].i11 * C];
-                const float top = fmaf_(t0[k].tx, t01 - t00, t00), bot = fmaf_(t0[k].tx, t11 - t10, t10);
-                au0[k] = fmaf_(gi, fmaf_(t0[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au0[k]);
-                av0[k] = fmaf_(gi, bot - top, av0[k]);
+                bilerp_chain(q + (size_t)t0[k].i00 * C, q + (size_t)t0[k].i01 * C, q + (size_t)t0[k].i10 * C, q + (size_t)t0[k].i11 * C, t0[k].tx,
+                             t0[k].ty, gi, au0[k], av0[k]);
               }
               if (two & (1u << k)) {
                 const SRZ_CAS float *q = p1[k] + c0 + i;
-                const float t00 = q[(size_t)t1[k].i00 * C], t01 = q[(size_t)t1[k].i01 * C], t10 = q[(size_t)t1[k].i10 * C], t11 = q[(size_t)t1[k].i11 * C];
-                const float top = fmaf_(t1[k].tx, t01 - t00, t00), bot = fmaf_(t1[k].tx, t11 - t10, t10);
-                au1[k] = fmaf_(gi, fmaf_(t1[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au1[k]);
-                av1[k] = fmaf_(gi, bot - top, av1[k]);
+                bilerp_chain(q + (size_t)t1[k].i00 * C, q + (size_t)t1[k].i01 * C, q + (size_t)t1[k].i10 * C, q + (size_t)t1[k].i11 * C, t1[k].tx,
+                             t1[k].ty, gi, au1[k], av1[k]);
               }
             }
         }
@@ -7677,9 +7585,9 @@ __global__ __launch_bounds__(256) void k_tex_mip_grad(TexMipArgs a) {
         part |= 1u << k;
         lw[k] = lower ? 1.0f - lod[k].f : lod[k].f;
         tap[k] = tex_tap(quad_at(uv[0], k), quad_at(uv[1], k), wl, hl, wrap);
-        slot[k][0] = mg_slot(tb, tap[k].i00), slot[k][1] = mg_slot(tb, tap[k].i01), slot[k][2] = mg_slot(tb, tap[k].i10),
-        slot[k][3] = mg_slot(tb, tap[k].i11);
+        slot[k][0] = tb.slot(tap[k].i00), slot[k][1] = tb.slot(tap[k].i01), slot[k][2] = tb.slot(tap[k].i10), slot[k][3] = tb.slot(tap[k].i11);
       }
+      const auto at = [=](uint32_t idx) { return gdst + (size_t)idx * C; };
       uint32_t n_used = 0u;
       // ---- B2. the channels, ATTR_CHUNK at a time
       for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
@@ -7691,47 +7599,20 @@ __global__ __launch_bounds__(256) void k_tex_mip_grad(TexMipArgs a) {
 #pragma unroll
           for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
             if (i >= nc) break;
-            const float *p = gg + (size_t)(c0 + i) * rc.plane;
-            if (whole) {
-              g[i] = *reinterpret_cast<const float4 *>(p);
-            } else {
-#pragma unroll
-              for (int k = 0; k < 4; ++k)
-                if (part & (1u << k)) quad_at(g[i], k) = p[k];
-            }
+            gout_quad(gg + (size_t)(c0 + i) * rc.plane, whole, part, g[i]);
           }
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if (!(part & (1u << k))) continue;
-          const float tx_ = tap[k].tx, ty_ = tap[k].ty;
-          const float w00 = ((1.0f - tx_) * (1.0f - ty_)) * lw[k], w01 = (tx_ * (1.0f - ty_)) * lw[k];
-          const float w10 = ((1.0f - tx_) * ty_) * lw[k], w11 = (tx_ * ty_) * lw[k];
+        for (int k = 0; k < 4; ++k)
+          if (part & (1u << k)) {
+            const CornerW w = corner_weights(tap[k].tx, tap[k].ty, lw[k]);
 #pragma unroll
-          for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
-            if (i < nc) {
-              const float gi = quad_at(g[i], k);
-              mg_add(tb, slot[k][0], gdst, tap[k].i00, C, c0 + i, i, w00 * gi);
-              mg_add(tb, slot[k][1], gdst, tap[k].i01, C, c0 + i, i, w01 * gi);
-              mg_add(tb, slot[k][2], gdst, tap[k].i10, C, c0 + i, i, w10 * gi);
-              mg_add(tb, slot[k][3], gdst, tap[k].i11, C, c0 + i, i, w11 * gi);
-            }
-        }
-        // ---- B3. the table's values of this chunk into memory: lanes in channel order within a texel (k_tex_grad's step 4)
-        __syncthreads();
-        n_used = tb.n_used;
-        for (uint32_t i = tid; i < n_used * ATTR_CHUNK; i += 256) {
-          const uint32_t s = tb.used[i / ATTR_CHUNK], e = i % ATTR_CHUNK;
-          const float v = tb.val[s * ATTR_CHUNK + e];
-          tb.val[s * ATTR_CHUNK + e] = 0.0f;
-          if (e < nc) global_add(gdst + (size_t)(tb.key[s] - 1u) * C + c0 + e, v);
-        }
-        __syncthreads();
+            for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
+              if (i < nc) corner_adds(tb, slot[k], tap[k], w, quad_at(g[i], k), i, gdst, C, c0 + i);
+          }
+        n_used = tb.flush(tid, c0, nc, at); // ---- B3. the table's values of this chunk into memory (k_tex_grad's step 4)
       }
-      // the level's keys go; every thread has read n_used before the chunk's last barrier
-      for (uint32_t i = tid; i < n_used; i += 256) tb.key[tb.used[i]] = 0u;
-      if (tid == 0) tb.n_used = 0u;
-      __syncthreads();
+      tb.release(tid, n_used); // the level's keys go
     }
   }
 }
@@ -7747,10 +7628,6 @@ __global__ __launch_bounds__(256) void k_tex_mip_grad(TexMipArgs a) {
 // l0 <= n_levels - 1 and l0 + 1 <= n_levels - 1 where f != 0 by cube_lod's clamps; every texel index follows cube_axis's clamp within
 // its level: no direction and no lam leaves the cube or the pyramid.
 // ================================================================================================================
-struct CubeFace {
-  float s, t, inv;
-  uint32_t major;
-};
 struct CubeCorners {
   uint32_t i00, i01, i10, i11;
   float tx, ty;
@@ -7882,15 +7759,13 @@ __global__ __launch_bounds__(256) void k_cube_mip(CubeMipArgs a) {
 //   A. gdir and glam, from registers, deterministic: k_cube_grad's au, av chains at level l0 and at level l0 + 1, each taken through
 //      cube_gdir with its own level's face size and blended by f as the forward blends the samples; glam is the fma chain of gout
 //      over c_(l0+1) - c_l0, which reads level l0 + 1 wherever 0 <= lam < n_levels - 1 — at f == 0 too (the right-hand derivative);
-//   B. the texel adds, BOTH LEVELS IN ONE TABLE: TexTable keyed on the texel's offset in the frame's concatenated pyramid + 1
+//   B. the texel adds, BOTH LEVELS IN ONE TABLE: TexelTable keyed on the texel's offset in the frame's concatenated pyramid
 //      (cube_pyr_before(l) + its index in level l, below 2^31), the slots found once in front of the channel loop, per chunk the
 //      LDS adds of (w_rc * lw) * gout, the dense flush — cube_pyr_texel finds a key's level and its place in gtex or gmip again —,
 //      the keys released.  A tile where no pixel is sampled skips the phase after one barrier: the tile's threads say so in a word
 //      of LDS that rotates over three words by the tile's count (k_tex_mip_grad's level word), the next one zeroed in front of the
 //      barrier.  A corner without a slot adds straight to memory.
 // The corners of both levels stay in registers across the phases; the slot numbers are live in B only.
-// (qg_slot and qg_add are COPIES of tg_slot and tg_add, and B's flush of k_tex_grad's step 4: shared helpers have moved k_tex_grad's
-// registers before (k_tex_mip_grad's note); a fix goes into all of them)
 // ================================================================================================================
 // the texels of one frame's levels 0 .. l - 1
 __device__ __forceinline__ uint32_t cube_pyr_before(uint32_t n, uint32_t l) {
@@ -7904,43 +7779,14 @@ __device__ __forceinline__ float *cube_pyr_texel(const CubeMipArgs &a, uint32_t 
   while (l + 1u < a.n_levels && off >= sz) off -= sz, ++l, sz = 6u * mip_extent(a.n, l) * mip_extent(a.n, l);
   return cube_level_ptr(a.gtex, a.gmip, a.n, a.n_ch, a.tex_frames, f, l) + (size_t)off * a.n_ch;
 }
-__device__ __forceinline__ uint32_t qg_slot(TexTable &tb, uint32_t off) {
-  const uint32_t key = off + 1u; // (off < 2^31)
-  uint32_t h = (key * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
-  for (uint32_t p = 0; p < TG_PROBES; ++p) {
-    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
-    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
-    if (old == 0u || old == key) return h;
-    h = (h + 1u) & (TG_SLOTS - 1u);
-  }
-  return TG_NONE;
-}
-__device__ __forceinline__ void qg_add(TexTable &tb, uint32_t slot, float *glevel, uint32_t idx, uint32_t C, uint32_t ch, uint32_t i, float v) {
-  if (slot != TG_NONE) lds_add(&tb.val[slot * ATTR_CHUNK + i], v);
-  else global_add(glevel + (size_t)idx * C + ch, v);
-}
-// srz_frameset_texture_cube_grad's chain from au, av at one level (half_n = 0.5f * (float)N of that level) to the direction
-__device__ __forceinline__ void cube_gdir(const CubeFace &c, float au, float av, float half_n, float (&g)[3]) {
-  const float gs = au * half_n, gt = av * half_n, inv = c.inv;
-  const float g_sc = gs * inv, g_tc = gt * inv, g_ma = -(fmaf_(gs, c.s, gt * c.t) * inv);
-  const uint32_t m = c.major & 3u;
-  const bool pos = (c.major & 4u) != 0u;
-  const float g_m = pos ? g_ma : -g_ma;
-  // su, sv of the face, undone: +X (-z, -y)  -X (z, -y)  +Y (x, z)  -Y (x, -z)  +Z (x, -y)  -Z (-x, -y)
-  g[0] = m == 0u ? g_m : m == 1u ? g_sc : (pos ? g_sc : -g_sc);
-  g[1] = m == 1u ? g_m : -g_tc;
-  g[2] = m == 0u ? (pos ? -g_sc : g_sc) : m == 1u ? (pos ? g_tc : -g_tc) : g_m;
-}
 __global__ __launch_bounds__(256) void k_cube_mip_grad(CubeMipArgs a) {
-  __shared__ TexTable tb;
+  __shared__ TexelTable<CubeMipArgs, ATTR_CHUNK> tb;
   __shared__ uint32_t busy[3];
   const uint32_t tid = threadIdx.x;
   const uint32_t C = a.n_ch;
   const bool want_tex = a.gtex != nullptr, want_dir = a.out != nullptr, want_lam = a.glam != nullptr;
   if (want_tex) {
-    for (uint32_t i = tid; i < TG_SLOTS; i += 256) tb.key[i] = 0u;
-    for (uint32_t i = tid; i < TG_SLOTS * ATTR_CHUNK; i += 256) tb.val[i] = 0.0f;
-    if (tid == 0) tb.n_used = 0u;
+    tb.init(tid);
     if (tid < 3) busy[tid] = 0u;
     __syncthreads();
   }
@@ -7982,20 +7828,13 @@ __global__ __launch_bounds__(256) void k_cube_mip_grad(CubeMipArgs a) {
       float gl[4] = {0.f, 0.f, 0.f, 0.f};
       for (uint32_t c0 = 0; c0 < C && smp != 0u; c0 += ATTR_CHUNK) {
         const uint32_t nc = min(ATTR_CHUNK, C - c0);
-        float4 g[ATTR_CHUNK]; // gout of the chunk's channels; words of pixels that are not sampled are loaded with their quad at most, never used
+        float4 g[ATTR_CHUNK];
 #pragma unroll
         for (uint32_t i = 0; i < ATTR_CHUNK; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
           if (i >= nc) break;
-          const float *p = gg + (size_t)(c0 + i) * rc.plane;
-          if (t.whole) {
-            g[i] = *reinterpret_cast<const float4 *>(p);
-          } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-              if (smp & (1u << k)) quad_at(g[i], k) = p[k];
-          }
+          gout_quad(gg + (size_t)(c0 + i) * rc.plane, t.whole, smp, g[i]);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -8004,22 +7843,14 @@ __global__ __launch_bounds__(256) void k_cube_mip_grad(CubeMipArgs a) {
           for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
             if (i < nc) {
               const float gi = quad_at(g[i], k);
-              float c_lo;
-              {
-                const SRZ_CAS float *q = p0[k] + c0 + i;
-                const float t00 = q[(size_t)lo[k].i00 * C], t01 = q[(size_t)lo[k].i01 * C], t10 = q[(size_t)lo[k].i10 * C], t11 = q[(size_t)lo[k].i11 * C];
-                const float top = fmaf_(lo[k].tx, t01 - t00, t00), bot = fmaf_(lo[k].tx, t11 - t10, t10);
-                au0[k] = fmaf_(gi, fmaf_(lo[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au0[k]);
-                av0[k] = fmaf_(gi, bot - top, av0[k]);
-                c_lo = fmaf_(lo[k].ty, bot - top, top);
-              }
+              const SRZ_CAS float *q = p0[k] + c0 + i;
+              const float c_lo = bilerp_chain(q + (size_t)lo[k].i00 * C, q + (size_t)lo[k].i01 * C, q + (size_t)lo[k].i10 * C, q + (size_t)lo[k].i11 * C,
+                                              lo[k].tx, lo[k].ty, gi, au0[k], av0[k]);
               if (up & (1u << k)) {
-                const SRZ_CAS float *q = p1[k] + c0 + i;
-                const float t00 = q[(size_t)hi[k].i00 * C], t01 = q[(size_t)hi[k].i01 * C], t10 = q[(size_t)hi[k].i10 * C], t11 = q[(size_t)hi[k].i11 * C];
-                const float top = fmaf_(hi[k].tx, t01 - t00, t00), bot = fmaf_(hi[k].tx, t11 - t10, t10);
-                au1[k] = fmaf_(gi, fmaf_(hi[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au1[k]);
-                av1[k] = fmaf_(gi, bot - top, av1[k]);
-                if (rhd & (1u << k)) gl[k] = fmaf_(gi, fmaf_(hi[k].ty, bot - top, top) - c_lo, gl[k]);
+                const SRZ_CAS float *r = p1[k] + c0 + i;
+                const float c_hi = bilerp_chain(r + (size_t)hi[k].i00 * C, r + (size_t)hi[k].i01 * C, r + (size_t)hi[k].i10 * C, r + (size_t)hi[k].i11 * C,
+                                                hi[k].tx, hi[k].ty, gi, au1[k], av1[k]);
+                if (rhd & (1u << k)) gl[k] = fmaf_(gi, c_hi - c_lo, gl[k]);
               }
             }
         }
@@ -8069,13 +7900,13 @@ __global__ __launch_bounds__(256) void k_cube_mip_grad(CubeMipArgs a) {
       if (!(smp & (1u << k))) continue;
       const uint32_t l = lod[k].l0, off0 = cube_pyr_before(a.n, l);
       q0[k] = cube_level_ptr(a.gtex, a.gmip, a.n, C, a.tex_frames, t.f, l);
-      slot[k][0] = qg_slot(tb, off0 + lo[k].i00), slot[k][1] = qg_slot(tb, off0 + lo[k].i01);
-      slot[k][2] = qg_slot(tb, off0 + lo[k].i10), slot[k][3] = qg_slot(tb, off0 + lo[k].i11);
+      slot[k][0] = tb.slot(off0 + lo[k].i00), slot[k][1] = tb.slot(off0 + lo[k].i01);
+      slot[k][2] = tb.slot(off0 + lo[k].i10), slot[k][3] = tb.slot(off0 + lo[k].i11);
       if (two & (1u << k)) {
         const uint32_t off1 = off0 + 6u * mip_extent(a.n, l) * mip_extent(a.n, l);
         q1[k] = cube_level_ptr(a.gtex, a.gmip, a.n, C, a.tex_frames, t.f, l + 1u);
-        slot[k][4] = qg_slot(tb, off1 + hi[k].i00), slot[k][5] = qg_slot(tb, off1 + hi[k].i01);
-        slot[k][6] = qg_slot(tb, off1 + hi[k].i10), slot[k][7] = qg_slot(tb, off1 + hi[k].i11);
+        slot[k][4] = tb.slot(off1 + hi[k].i00), slot[k][5] = tb.slot(off1 + hi[k].i01);
+        slot[k][6] = tb.slot(off1 + hi[k].i10), slot[k][7] = tb.slot(off1 + hi[k].i11);
       }
     }
     uint32_t n_used = 0u;
@@ -8089,63 +7920,29 @@ __global__ __launch_bounds__(256) void k_cube_mip_grad(CubeMipArgs a) {
 #pragma unroll
         for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
           if (i >= nc) break;
-          const float *p = gg + (size_t)(c0 + i) * rc.plane;
-          if (t.whole) {
-            g[i] = *reinterpret_cast<const float4 *>(p);
-          } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-              if (smp & (1u << k)) quad_at(g[i], k) = p[k];
-          }
+          gout_quad(gg + (size_t)(c0 + i) * rc.plane, t.whole, smp, g[i]);
         }
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         if (!(smp & (1u << k))) continue;
         {
-          const float tx_ = lo[k].tx, ty_ = lo[k].ty, lw = 1.0f - lod[k].f;
-          const float w00 = ((1.0f - tx_) * (1.0f - ty_)) * lw, w01 = (tx_ * (1.0f - ty_)) * lw;
-          const float w10 = ((1.0f - tx_) * ty_) * lw, w11 = (tx_ * ty_) * lw;
+          const CornerW w = corner_weights(lo[k].tx, lo[k].ty, 1.0f - lod[k].f);
 #pragma unroll
           for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
-            if (i < nc) {
-              const float gi = quad_at(g[i], k);
-              qg_add(tb, slot[k][0], q0[k], lo[k].i00, C, c0 + i, i, w00 * gi);
-              qg_add(tb, slot[k][1], q0[k], lo[k].i01, C, c0 + i, i, w01 * gi);
-              qg_add(tb, slot[k][2], q0[k], lo[k].i10, C, c0 + i, i, w10 * gi);
-              qg_add(tb, slot[k][3], q0[k], lo[k].i11, C, c0 + i, i, w11 * gi);
-            }
+            if (i < nc) corner_adds(tb, slot[k], lo[k], w, quad_at(g[i], k), i, q0[k], C, c0 + i);
         }
         if (two & (1u << k)) {
-          const float tx_ = hi[k].tx, ty_ = hi[k].ty, lw = lod[k].f;
-          const float w00 = ((1.0f - tx_) * (1.0f - ty_)) * lw, w01 = (tx_ * (1.0f - ty_)) * lw;
-          const float w10 = ((1.0f - tx_) * ty_) * lw, w11 = (tx_ * ty_) * lw;
+          const CornerW w = corner_weights(hi[k].tx, hi[k].ty, lod[k].f);
 #pragma unroll
           for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
-            if (i < nc) {
-              const float gi = quad_at(g[i], k);
-              qg_add(tb, slot[k][4], q1[k], hi[k].i00, C, c0 + i, i, w00 * gi);
-              qg_add(tb, slot[k][5], q1[k], hi[k].i01, C, c0 + i, i, w01 * gi);
-              qg_add(tb, slot[k][6], q1[k], hi[k].i10, C, c0 + i, i, w10 * gi);
-              qg_add(tb, slot[k][7], q1[k], hi[k].i11, C, c0 + i, i, w11 * gi);
-            }
+            if (i < nc) corner_adds(tb, slot[k] + 4, hi[k], w, quad_at(g[i], k), i, q1[k], C, c0 + i);
         }
       }
-      // ---- B3. the table's values of this chunk into memory: lanes in channel order within a texel (k_tex_grad's step 4)
-      __syncthreads();
-      n_used = tb.n_used;
-      for (uint32_t i = tid; i < n_used * ATTR_CHUNK; i += 256) {
-        const uint32_t s = tb.used[i / ATTR_CHUNK], e = i % ATTR_CHUNK;
-        const float v = tb.val[s * ATTR_CHUNK + e];
-        tb.val[s * ATTR_CHUNK + e] = 0.0f;
-        if (e < nc) global_add(cube_pyr_texel(a, t.f, tb.key[s] - 1u) + c0 + e, v);
-      }
-      __syncthreads();
+      // ---- B3. the table's values of this chunk into memory (k_tex_grad's step 4), each key to its level again
+      n_used = tb.flush(tid, c0, nc, [&a, f = t.f](uint32_t off) { return cube_pyr_texel(a, f, off); });
     }
-    // the tile's keys go; every thread has read n_used before the chunk's last barrier
-    for (uint32_t i = tid; i < n_used; i += 256) tb.key[tb.used[i]] = 0u;
-    if (tid == 0) tb.n_used = 0u;
-    __syncthreads();
+    tb.release(tid, n_used);
   });
 }
 
@@ -8299,38 +8096,15 @@ __global__ __launch_bounds__(256) void k_shadow(ShadowArgs a) {
 // The planes-only build has no LDS, no shuffle and no barrier (k_light_grad<false>'s precedent): a call that does not ask for gmap
 // pays for no table.  The WANT_MAP build is k_tex_grad's structure at one channel on the passes' helpers (pass_walk<true>: every
 // thread of the workgroup reaches every barrier, one outside the frame samples nothing): the tile's open-addressed table of distinct
-// texels in LDS (ShadowTable: TexTable's fields with ONE value per slot, 24 KB, not ATTR_CHUNK — 48 KB would halve the workgroups a
-// CU holds — keyed on y * map_w + x + 1), the slots of the moving corners found first, LDS float adds, the dense flush with
-// global_atomic_add_f32, a corner without a slot adding straight to memory.  A tile without a moving corner (every tile of a hard
-// call; the lit and the fully shadowed tiles of a soft one) skips the table behind one __syncthreads_or, as k_light_grad does.
-// (sg_slot and sg_add are COPIES of tg_slot and tg_add, the flush of k_tex_grad's step 4: shared helpers have moved k_tex_grad's
-// registers before (k_tex_mip_grad's note); a fix goes into all of them)
+// texels in LDS (TexelTable with ONE value per slot, 24 KB, not ATTR_CHUNK — 48 KB would halve the workgroups a CU holds — keyed
+// on y * map_w + x), the slots of the moving corners found first, LDS float adds, the dense flush with global_atomic_add_f32, a
+// corner without a slot adding straight to memory.  A tile without a moving corner (every tile of a hard call; the lit and the
+// fully shadowed tiles of a soft one) skips the table behind one __syncthreads_or, as k_light_grad does.
 // ================================================================================================================
-struct ShadowTable {
-  uint32_t key[TG_SLOTS];  // texel index + 1; 0: free
-  uint32_t used[TG_SLOTS]; // the slots taken, in arrival order
-  uint32_t n_used;
-  float val[TG_SLOTS];
-};
-__device__ __forceinline__ uint32_t sg_slot(ShadowTable &tb, uint32_t idx) {
-  const uint32_t key = idx + 1u; // (idx < SRZ_TEX_MAX_SIZE^2 = 2^28)
-  uint32_t h = (key * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
-  for (uint32_t p = 0; p < TG_PROBES; ++p) {
-    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
-    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
-    if (old == 0u || old == key) return h;
-    h = (h + 1u) & (TG_SLOTS - 1u);
-  }
-  return TG_NONE;
-}
-__device__ __forceinline__ void sg_add(ShadowTable &tb, uint32_t slot, float *gmap, uint32_t idx, float v) {
-  if (slot != TG_NONE) lds_add(&tb.val[slot], v);
-  else global_add(gmap + idx, v);
-}
-template <bool WANT_MAP> __device__ __forceinline__ void shadow_grad_body(const ShadowArgs &a, ShadowTable *tb) {
+template <bool WANT_MAP> __device__ __forceinline__ void shadow_grad_body(const ShadowArgs &a, TexelTable<ShadowArgs, 1u> *tb) {
   const uint32_t tid = threadIdx.x;
   const bool want_sc = a.out != nullptr;
-  if (WANT_MAP) {
+  if (WANT_MAP) { // (its own text, one loop: with TexelTable::init the kernel has 7 601 instructions, so 7 575)
     for (uint32_t i = tid; i < TG_SLOTS; i += 256) tb->key[i] = 0u, tb->val[i] = 0.0f;
     if (tid == 0) tb->n_used = 0u;
     __syncthreads();
@@ -8376,13 +8150,15 @@ template <bool WANT_MAP> __device__ __forceinline__ void shadow_grad_body(const 
       for (int k = 0; k < 4; ++k)
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-          if (mov & (1u << (4 * k + c))) slot[k][c] = sg_slot(*tb, (uint32_t)(px[k].base + (c >> 1) * W + (c & 1)));
+          if (mov & (1u << (4 * k + c))) slot[k][c] = tb->slot((uint32_t)(px[k].base + (c >> 1) * W + (c & 1)));
 #pragma unroll
       for (int k = 0; k < 4; ++k)
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-          if (mov & (1u << (4 * k + c))) sg_add(*tb, slot[k][c], gmap, (uint32_t)(px[k].base + (c >> 1) * W + (c & 1)), d[k][c]);
-      // ---- 4. the table's values into memory, texel after texel, and the tile's keys go (k_tex_grad's step 4 and its release)
+          if (mov & (1u << (4 * k + c)))
+            tb->add(slot[k][c], 0u, d[k][c], gmap, (uint32_t)(px[k].base + (c >> 1) * W + (c & 1)), 1u, 0u);
+      // ---- 4. the table's values into memory, texel after texel, and the tile's keys go in the same loop (its own text: with
+      // TexelTable::flush and release the kernel has 7 591 instructions, so 7 575, and measured 1.5 % slower, NOTEBOOK.md)
       __syncthreads();
       const uint32_t n_used = tb->n_used;
       for (uint32_t i = tid; i < n_used; i += 256) {
@@ -8399,7 +8175,7 @@ template <bool WANT_MAP> __device__ __forceinline__ void shadow_grad_body(const 
 }
 template <bool WANT_MAP> __global__ __launch_bounds__(256) void k_shadow_grad(ShadowArgs a) {
   if constexpr (WANT_MAP) {
-    __shared__ ShadowTable tb;
+    __shared__ TexelTable<ShadowArgs, 1u> tb;
     shadow_grad_body<true>(a, &tb);
   } else {
     shadow_grad_body<false>(a, nullptr);
@@ -9406,7 +9182,7 @@ void launch_composite_grad(const CompositeArgs &a, hipStream_t s) {
 // ================================================================================================================
 // k_tex_set, k_tex_set_grad — TEXTURE SETS (srz_frameset_texture_set / _texture_set_grad, include/srz.h states the rule): k_tex and
 // k_tex_grad with the texture of each pixel picked by its owner's batch.  k_cube's and k_cube_grad's shape on the passes' helpers:
-// pass_walk, quad_ids, quad_load, quad_store_owned; tex_tap and TexTable are k_tex's and k_tex_grad's own, used as they are.
+// pass_walk, quad_ids, quad_load, quad_store_owned; tex_tap and TexelTable are k_tex's and k_tex_grad's own, used as they are.
 // The slot is a per-LANE value (a quad can straddle two meshes): one 2-byte gather of the owner's batch per owned pixel — not
 // repeated for a pixel whose owner was looked up last — and one byte of the caller's map; a byte that names no slot leaves
 // the pixel unsampled, so no byte of the map reaches an address.  The per-slot pointers and sizes are never indexed by the lane's
@@ -9416,15 +9192,12 @@ void launch_composite_grad(const CompositeArgs &a, hipStream_t s) {
 // forward's channel loop is k_tex's slot after slot (the same unrolled loop and ballot: the texture stays a scalar base under the
 // lanes' texel offsets — with a per-pixel pointer the build took 130 VGPRs and three waves a SIMD, this way 118 and k_tex's four);
 // the backward's is k_tex_grad's with the texture's pointer at the frame per pixel (213 VGPRs, k_tex_grad's two waves).
-// The gradient's table counts distinct (slot, texel) pairs of the tile: its key is (slot << 28 | texel index) + 1 — a texel index
+// The gradient's table counts distinct (slot, texel) pairs of the tile: its key is slot << 28 | texel index — a texel index
 // is below SRZ_TEX_MAX_SIZE^2 = 2^28, eight slots end at 2^31 —, so two slots that touch the same texel index are two entries.  A
 // corner of a slot without gtex takes no entry and adds nothing.  The flush takes the slot out of the key and adds into THAT
 // slot's gtex at its own frame stride (0: every frame folds into the one texture), and so does the straight-to-memory add of a
 // corner that found no entry (ts_gtex: a chain of selects over the kernel arguments, no indexing).  Every thread of the workgroup
 // reaches every barrier.
-// (ts_slot is a COPY of tg_slot, ts_add of tg_add with the slot's gtex looked up where it is needed, the flush of k_tex_grad's step
-// 4: called from here as they are, tg_slot and tg_add moved k_tex_grad's registers, 171 -> 221 VGPRs, as sharing has moved them
-// before (k_tex_mip_grad's note); a fix goes into all of them)
 // (At the end of the file, behind the launchers: no existing kernel moves.)
 // ================================================================================================================
 constexpr uint32_t TS_IDX_BITS = 28;
@@ -9532,25 +9305,8 @@ __device__ __forceinline__ float *ts_gtex(const TexSetArgs &a, uint32_t s, uint3
     if (s == q) g = a.gtex[q], stride = a.tex_frame_stride[q];
   return g ? g + (size_t)f * stride : nullptr;
 }
-// the entry of (slot, texel) pair `pair` in the tile's table, taken if need be; TG_NONE: no room within TG_PROBES
-__device__ __forceinline__ uint32_t ts_slot(TexTable &tb, uint32_t pair) {
-  const uint32_t key = pair + 1u; // (pair < SRZ_TEXSET_MAX << TS_IDX_BITS = 2^31)
-  uint32_t h = (key * 0x9e3779b1u) >> (32u - TG_SLOT_BITS);
-  for (uint32_t p = 0; p < TG_PROBES; ++p) {
-    const uint32_t old = atomicCAS(&tb.key[h], 0u, key);
-    if (old == 0u) tb.used[atomicAdd(&tb.n_used, 1u)] = h; // (each slot is taken once: n_used <= TG_SLOTS)
-    if (old == 0u || old == key) return h;
-    h = (h + 1u) & (TG_SLOTS - 1u);
-  }
-  return TG_NONE;
-}
-__device__ __forceinline__ void ts_add(TexTable &tb, uint32_t slot, const TexSetArgs &a, uint32_t hi, uint32_t f, uint32_t idx, uint32_t C,
-                                       uint32_t ch, uint32_t i, float v) {
-  if (slot != TG_NONE) lds_add(&tb.val[slot * ATTR_CHUNK + i], v);
-  else global_add(ts_gtex(a, hi >> TS_IDX_BITS, f) + (size_t)idx * C + ch, v); // (the pixel's slot has a gtex: step 2)
-}
 __global__ __launch_bounds__(256) void k_tex_set_grad(TexSetArgs a) {
-  __shared__ TexTable tb;
+  __shared__ TexelTable<TexSetArgs, ATTR_CHUNK> tb;
   const uint32_t tid = threadIdx.x;
   const uint32_t C = a.n_ch;
   const bool want_tex = a.want_tex != 0u, want_uv = a.out != nullptr;
@@ -9559,9 +9315,7 @@ __global__ __launch_bounds__(256) void k_tex_set_grad(TexSetArgs a) {
   for (uint32_t q = 0; q < SRZ_TEXSET_MAX; ++q)
     if (a.gtex[q]) asked |= 1u << q;
   if (want_tex) {
-    for (uint32_t i = tid; i < TG_SLOTS; i += 256) tb.key[i] = 0u;
-    for (uint32_t i = tid; i < TG_SLOTS * ATTR_CHUNK; i += 256) tb.val[i] = 0.0f;
-    if (tid == 0) tb.n_used = 0u;
+    tb.init(tid);
     __syncthreads();
   }
   pass_walk<true>(a, [&](const PassTile &t) { // (a thread outside the frame owns nothing, and still meets the barriers)
@@ -9581,8 +9335,8 @@ __global__ __launch_bounds__(256) void k_tex_set_grad(TexSetArgs a) {
       for (int k = 0; k < 4; ++k)
         if ((smp & (1u << k)) && ((asked >> (hi[k] >> TS_IDX_BITS)) & 1u)) {
           add |= 1u << k;
-          slot[k][0] = ts_slot(tb, hi[k] | tap[k].i00), slot[k][1] = ts_slot(tb, hi[k] | tap[k].i01);
-          slot[k][2] = ts_slot(tb, hi[k] | tap[k].i10), slot[k][3] = ts_slot(tb, hi[k] | tap[k].i11);
+          slot[k][0] = tb.slot(hi[k] | tap[k].i00), slot[k][1] = tb.slot(hi[k] | tap[k].i01);
+          slot[k][2] = tb.slot(hi[k] | tap[k].i10), slot[k][3] = tb.slot(hi[k] | tap[k].i11);
         }
     }
     float au[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f};
@@ -9590,21 +9344,14 @@ __global__ __launch_bounds__(256) void k_tex_set_grad(TexSetArgs a) {
     // ---- 3. the channels, ATTR_CHUNK at a time
     for (uint32_t c0 = 0; c0 < C; c0 += ATTR_CHUNK) {
       const uint32_t nc = min(ATTR_CHUNK, C - c0);
-      float4 g[ATTR_CHUNK]; // gout of the chunk's channels; words of pixels that are not sampled are loaded with their quad at most, never used
+      float4 g[ATTR_CHUNK];
 #pragma unroll
       for (uint32_t i = 0; i < ATTR_CHUNK; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (smp != 0u) {
 #pragma unroll
         for (uint32_t i = 0; i < ATTR_CHUNK; ++i) {
           if (i >= nc) break;
-          const float *p = gg + (size_t)(c0 + i) * rc.plane;
-          if (t.whole) {
-            g[i] = *reinterpret_cast<const float4 *>(p);
-          } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-              if (smp & (1u << k)) quad_at(g[i], k) = p[k];
-          }
+          gout_quad(gg + (size_t)(c0 + i) * rc.plane, t.whole, smp, g[i]);
         }
       }
 #pragma unroll
@@ -9615,47 +9362,22 @@ __global__ __launch_bounds__(256) void k_tex_set_grad(TexSetArgs a) {
           const SRZ_CAS float *p10 = tex[k] + (size_t)tap[k].i10 * C + c0, *p11 = tex[k] + (size_t)tap[k].i11 * C + c0;
 #pragma unroll
           for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
-            if (i < nc) {
-              const float gi = quad_at(g[i], k), t00 = p00[i], t01 = p01[i], t10 = p10[i], t11 = p11[i];
-              const float top = fmaf_(tap[k].tx, t01 - t00, t00), bot = fmaf_(tap[k].tx, t11 - t10, t10);
-              au[k] = fmaf_(gi, fmaf_(tap[k].ty, (t11 - t10) - (t01 - t00), t01 - t00), au[k]);
-              av[k] = fmaf_(gi, bot - top, av[k]);
-            }
+            if (i < nc) bilerp_chain(p00 + i, p01 + i, p10 + i, p11 + i, tap[k].tx, tap[k].ty, quad_at(g[i], k), au[k], av[k]);
         }
         if (add & (1u << k)) {
-          const float tx_ = tap[k].tx, ty_ = tap[k].ty;
-          const float w00 = (1.0f - tx_) * (1.0f - ty_), w01 = tx_ * (1.0f - ty_), w10 = (1.0f - tx_) * ty_, w11 = tx_ * ty_;
+          const CornerW w = corner_weights(tap[k].tx, tap[k].ty);
 #pragma unroll
           for (uint32_t i = 0; i < ATTR_CHUNK; ++i)
-            if (i < nc) {
-              const float gi = quad_at(g[i], k);
-              ts_add(tb, slot[k][0], a, hi[k], t.f, tap[k].i00, C, c0 + i, i, w00 * gi);
-              ts_add(tb, slot[k][1], a, hi[k], t.f, tap[k].i01, C, c0 + i, i, w01 * gi);
-              ts_add(tb, slot[k][2], a, hi[k], t.f, tap[k].i10, C, c0 + i, i, w10 * gi);
-              ts_add(tb, slot[k][3], a, hi[k], t.f, tap[k].i11, C, c0 + i, i, w11 * gi);
-            }
+            if (i < nc) corner_adds(tb, slot[k], tap[k], w, quad_at(g[i], k), i, ts_gtex(a, hi[k] >> TS_IDX_BITS, t.f), C, c0 + i);
         }
       }
-      if (want_tex) {
-        // ---- 4. the table's values of this chunk into memory, each into its own slot's gtex: lanes in channel order within a texel
-        __syncthreads();
-        n_used = tb.n_used;
-        for (uint32_t i = tid; i < n_used * ATTR_CHUNK; i += 256) {
-          const uint32_t s = tb.used[i / ATTR_CHUNK], e = i % ATTR_CHUNK;
-          const float v = tb.val[s * ATTR_CHUNK + e];
-          tb.val[s * ATTR_CHUNK + e] = 0.0f;
-          const uint32_t key = tb.key[s] - 1u, ks = key >> TS_IDX_BITS, idx = key & ((1u << TS_IDX_BITS) - 1u);
-          float *gs = ts_gtex(a, ks, t.f); // (an entry's slot has a gtex: step 2)
-          if (e < nc && gs) global_add(gs + (size_t)idx * C + c0 + e, v);
-        }
-        __syncthreads();
-      }
+      // ---- 4. the table's values of this chunk into memory, each into its own slot's gtex (an entry's slot has one: step 2)
+      if (want_tex)
+        n_used = tb.flush(tid, c0, nc, [&a, f = t.f, C](uint32_t pair) {
+          return ts_gtex(a, pair >> TS_IDX_BITS, f) + (size_t)(pair & ((1u << TS_IDX_BITS) - 1u)) * C;
+        });
     }
-    if (want_tex) { // the tile's keys go; every thread has read n_used before the chunk's last barrier
-      for (uint32_t i = tid; i < n_used; i += 256) tb.key[tb.used[i]] = 0u;
-      if (tid == 0) tb.n_used = 0u;
-      __syncthreads();
-    }
+    if (want_tex) tb.release(tid, n_used);
     // ---- 5. du, dv: whole quads (fused clear, or four owners), else the owned pixels only; an owner that is not sampled: (0, 0)
     if (want_uv && t.inside && (own != 0u || fused)) {
       float4 d[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};

@@ -198,3 +198,35 @@ def soup_frames(w=64, h=64, n=90, k=2, uv_scale=1.0, flags=None):
 def make_tex(seed, w, h, n_ch, frames=None):
     shape = (h, w, n_ch) if frames is None else (frames, h, w, n_ch)
     return np.random.default_rng([seed, w, h, n_ch]).normal(0, 3, shape).astype(np.float32)
+
+
+TG_SLOTS = 2048  # the capacity of k_tex_mip_grad's table of distinct texels per tile and level
+TILE = 32
+
+
+def overflow_planes(w=64, h=64, tw=256, th=256):
+    """the planes of k_tex_mip_grad's no-slot case, two frames of w x h: uv steps 2.5 texels of a tw x th texture per pixel, so no two
+    pixels of a tile share a corner at level 0; frame 0's uvd gives a footprint of half a texel (l0 = 0, f = 0), frame 1's rho = 1.5
+    exactly along both axes (levels 0 and 1) → (uv [2, 2, h, w], uvd [2, 4, h, w]) float32"""
+    xs, ys = np.meshgrid(np.arange(w), np.arange(h))
+    uv = np.stack([np.stack([(2.5 * xs + 0.85) / tw, (2.5 * ys + 1.1) / th]).astype(np.float32)] * 2)
+    uvd = np.zeros((2, 4, h, w), np.float32)
+    uvd[0, 0], uvd[0, 3] = 0.5 / tw, 0.5 / th
+    uvd[1, 0], uvd[1, 3] = 1.5 / tw, 1.5 / th
+    return uv, uvd
+
+
+def tile_texels(tmpdir, ids, uv, uvd, tex_hw, mode, n_levels, n_tris):
+    """the distinct texels each TILE x TILE tile of one frame adds into, per level, counted from the reference's own accumulators (each
+    add names its texel) → int [tiles_y, tiles_x, n_levels]"""
+    rows, W = ids.shape
+    out = np.zeros(((rows + TILE - 1) // TILE, (W + TILE - 1) // TILE, n_levels), np.int64)
+    zero = np.zeros(tuple(tex_hw) + (1,), np.float32)
+    for ty in range(out.shape[0]):
+        for tx in range(out.shape[1]):
+            sl = (slice(ty * TILE, (ty + 1) * TILE), slice(tx * TILE, (tx + 1) * TILE))
+            probe = Grad(tmpdir, zero.shape, n_levels)
+            grad(tmpdir, zero, None, mode, n_levels, n_tris, ids[sl], uv[(slice(None),) + sl], uvd[(slice(None),) + sl],
+                 np.ones((1,) + ids[sl].shape, np.float32), probe, False)
+            out[ty, tx] = [int((probe.level(l)[2] > 0).sum()) for l in range(n_levels)]
+    return out

@@ -560,6 +560,34 @@ def test_texel_gradients_of_a_minified_tile_land_on_level_3(ctx, tmp_path):
     fs.close()
 
 
+@pytest.mark.parametrize("mode", [CLAMP, WRAP])
+def test_texel_gradients_past_the_table_add_straight_to_memory(ctx, tmp_path, mode):
+    """the opposite regime (tests/test_gpu_cube.py's test_table_overflow): mipref.overflow_planes over four tiles a frame — every tile
+    touches 4 096 distinct texels of level 0 against the table's 2 048 slots, in frame 1 next to a level 1 that fits —, so corners
+    without a slot add straight to memory at level 0, with and without a second level; C = 5: two chunks, the second with a masked
+    tail.  The bound is test_texel_gradients_on_rendered_buffers_and_accumulation's."""
+    w = h = 64
+    n, C, tw, th, L = 2, 5, 256, 256, 9
+    uvw, uvdw = mipref.overflow_planes(w, h, tw, th)
+    frames = hand_frames(w, h, n, 20)
+    ids = rand_ids(np.random.default_rng(31), n, h, w, 20, holes=False)
+    for i in range(n):  # every tile really exceeds the table at level 0; frame 1 adds into level 1 too
+        per_tile = mipref.tile_texels(tmp_path, ids[i], uvw[i], uvdw[i], (th, tw), mode, L, 20)
+        assert per_tile.shape == (2, 2, L) and (per_tile[..., 0] > mipref.TG_SLOTS).all() and (per_tile[..., 2:] == 0).all()
+        assert ((per_tile[..., 1] > 0) == (i == 1)).all() and (per_tile[..., 1] <= mipref.TG_SLOTS).all()
+    fs = ctx.frameset(frames)
+    v = hand_vis(ids)
+    vis, uv, uvd = torch.as_tensor(v).cuda(), dev(uvw), dev(uvdw)
+    for tex in (mipref.make_tex(8, tw, th, C), mipref.make_tex(8, tw, th, C, frames=n)):
+        gout = rand_gout(11, (n, C, h, w))
+        gt, gm, gu = bwd(fs, vis, uv, uvd, gout, tex, mode, L, fill=SENTINEL)
+        accs, want_gu = expect_bwd(tmp_path, frames, v.view(np.uint32), uvw, uvdw, gout, tex, mode, L, fill=SENTINEL)
+        same(gu, want_gu, "overflow guv")
+        check_levels(tmp_path, gt, gm, accs, tex.shape, L, f"overflow {tex.ndim} mode {mode}")
+        assert (gt != 0).any() and (gm != 0).any()
+    fs.close()
+
+
 # ------------------------------------------------------------------------------------------------------ the chain, autograd
 def test_guv_chains_into_interpolate_grad(ctx, tmp_path):
     frames, fs, vis, v, uv, uvd, attr = rendered(ctx, 100, 70, 120)

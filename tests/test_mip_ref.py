@@ -363,3 +363,18 @@ def test_the_gpu_tests_frames_are_not_vacuous(tmp_path, orc):
     print(f"sampled {int(smp.sum())} magnified {magnified} blended {blended} per level {per_level}")
     assert magnified >= 100 and blended >= 100
     assert sum(1 for n in per_level.values() if n >= 10) >= 3
+
+
+@pytest.mark.parametrize("mode", [CLAMP, WRAP])
+def test_the_overflow_case_exceeds_the_table_in_every_tile(tmp_path, mode):
+    """what tests/test_gpu_texture_mip.py's no-slot test rests on: each of the four tiles of both frames touches more than TG_SLOTS
+    distinct texels of level 0 (every pixel's four corners its own: 4 * 32 * 32), frame 0 nothing else, frame 1 a level 1 that fits"""
+    uv, uvd = mipref.overflow_planes()
+    ids = np.ones((64, 64), np.uint32)
+    for i in range(2):
+        l0, f = mipref.lod(tmp_path, (256, 256), 9, uvd[i])
+        assert (l0 == 0).all() and (f == (0.0, 0.5)[i]).all()
+        per_tile = mipref.tile_texels(tmp_path, ids, uv[i], uvd[i], (256, 256), mode, 9, 1)
+        assert per_tile.shape == (2, 2, 9) and (per_tile[..., 0] == 4096).all() and 4096 > mipref.TG_SLOTS
+        level1 = per_tile[..., 1]
+        assert (per_tile[..., 2:] == 0).all() and ((level1 == 0).all() if i == 0 else ((level1 > 0) & (level1 <= mipref.TG_SLOTS)).all())
