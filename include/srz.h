@@ -86,6 +86,9 @@ extern "C" {
  *      srz_frameset_composite_grad, srz_composite_layer, SRZ_COMPOSITE_MAX
  *      (additive, same version) texture sets: each pixel's caller texture picked by its owner's batch, with gradients
  *      srz_frameset_texture_set / srz_frameset_texture_set_grad, srz_texset_slot, SRZ_TEXSET_MAX, SRZ_TEXSET_NONE
+ *      (additive, same version) SH9 lighting: a cube projected to nine spherical-harmonic coefficients per channel, and those
+ *      evaluated at each pixel's normal, with gradients srz_cube_sh / srz_cube_sh_grad / srz_cube_sh_work_bytes / srz_frameset_sh /
+ *      srz_frameset_sh_grad / srz_frameset_sh_work_bytes, SRZ_SH_MAX_CH, SRZ_SH_IRRADIANCE, SRZ_SH_RADIANCE
  */
 #define SRZ_ABI_VERSION 7
 
@@ -1286,6 +1289,88 @@ int srz_cube_prefilter(srz_ctx *ctx, const float *d_src, uint32_t n_src, float *
 int srz_cube_prefilter_grad(srz_ctx *ctx, const float *d_gdst, const float *d_den, uint32_t n_src, uint32_t n_dst, uint32_t n_ch,
                             uint32_t tex_frames, uint32_t kind, float roughness, float cmin, float *d_gsrc, void *d_work, size_t work_bytes,
                             void *stream);
+/* SH9 LIGHTING: the diffuse environment as NINE SPHERICAL-HARMONIC COEFFICIENTS PER CHANNEL (order 2), with gradients — the usual
+ * unknown of inverse rendering in place of a cube of texels: 27 numbers for RGB, which carry the irradiance of any environment to
+ * about 1 % (Ramamoorthi and Hanrahan).  Two pieces: srz_cube_sh projects a cube to its coefficients in one O(n^2) pass (no all-pairs
+ * prefilter), srz_frameset_sh evaluates coefficients at each pixel's normal.  On srz_frameset_ibl's scale (E / pi), so the output is a
+ * drop-in for srz_frameset_texture_cube of srz_cube_prefilter's COSINE cube at the normal.
+ * THE CONSTANTS, binary32, each the binary32 nearest to the binary64 value (the products of the H's taken in binary64, rounded once):
+ *   Yc0 = sqrt(1 / 4 pi) = 0x1.20dd76p-2f (0x3e906ebb);  Yc1 = sqrt(3 / 4 pi) = 0x1.f45438p-2f (0x3efa2a1c);
+ *   Yc2 = sqrt(15 / 4 pi) = 0x1.17b142p+0f (0x3f8bd8a1);  Yc3 = sqrt(5 / 16 pi) = 0x1.42f602p-2f (0x3ea17b01);
+ *   Yc4 = sqrt(15 / 16 pi) = 0x1.17b142p-1f (0x3f0bd8a1);  FOURPI = 12.566371f = 0x1.921fb6p+3f
+ *   the band factors A_l / pi = 1, 2 / 3, 1 / 4 folded in:  H0 = Yc0 = 0x1.20dd76p-2f;  H1 = Yc1 * 2 / 3 = 0x1.4d8d7ap-2f;
+ *   H2 = Yc2 / 4 = 0x1.17b142p-2f;  H3 = Yc3 / 4 = 0x1.42f602p-4f;  H4 = Yc4 / 4 = 0x1.17b142p-3f
+ * THE POLYNOMIALS of a unit vector (x, y, z), in the standard real-SH order k = 0 .. 8:
+ *   p = 1, y, z, x, x * y, y * z, fmaf(3.0f * z, z, -1.0f), x * z, fmaf(x, x, -(y * y));  constant index per k: 0, 1, 1, 1, 2, 2, 3, 2, 4
+ *   (Yc[k], H[k] below: the constant of k's index.)
+ * All of it float32, nothing fused except where fmaf is written, / and sqrtf the correctly rounded operations, always the exact
+ * arithmetic (SRZ_OPT_APPROX_SHADE has no effect).  SUBNORMALS are numbers; non-finite values propagate as IEEE has them.
+ *
+ * srz_cube_sh / srz_cube_sh_grad / srz_cube_sh_work_bytes: A CUBE TO ITS SH9 COEFFICIENTS.  No set and no visibility buffer are
+ * involved; stream semantics and asynchrony as srz_cube_mip_build.  d_src and d_gsrc: [tex_frames][6][n][n][n_ch] float32,
+ * srz_frameset_texture_cube's layout; d_sh and d_gsh: [tex_frames][9][n_ch] float32; d_den: one float32, the normaliser: it depends
+ * on n only; the forward writes it when non-null, the backward needs it as the forward wrote it (for the same n).  n is 1 ..
+ * SRZ_TEX_MAX_SIZE, any parity; 1 <= n_ch <= SRZ_SH_MAX_CH; 1 <= tex_frames <= 65536.  d_work: scratch of
+ * srz_cube_sh_work_bytes(n, n_ch, tex_frames) bytes (0 for sizes out of range), the same size for both calls; its contents mean
+ * nothing between calls.  Every pointer is 4-byte aligned.
+ * THE RULE: the texel geometry d, jac of texel (f, y, x) is srz_cube_prefilter's TEXEL GEOMETRY at N = n, word for word.
+ *   b_k = Yc[k] * p_k(d);  w_k = jac * b_k                                                    (k = 0 .. 8; b_0 = Yc0 * 1.0f)
+ *   per frame, k and channel, the numerator is summed in a FIXED TREE: within a face row, lane j of 64 takes the columns j, j + 64,
+ *   ... ascending, with a = fmaf(w_k, src, a) from +0; the 64 lane sums go through the butterfly v = v + v[lane ^ o], o = 32, 16, 8,
+ *   4, 2, 1 (a lane without a column holds +0); the rows of a face are added ascending by plain adds from +0; the six faces in order
+ *   by plain adds from +0.  den is the same tree over a = a + jac.
+ *   sh[k][c] = (FOURPI * num) / den        (always written)
+ * BACKWARD, srz_cube_sh_grad, a gather per source texel, no atomics, d_gsrc WRITTEN, not added into:
+ *   q[k][c] = (FOURPI * gsh[k][c]) / den;   gsrc[c] = w_0 * q[0][c], then gsrc[c] = fmaf(w_k, q[k][c], gsrc[c]) for k = 1 .. 8,
+ *   w_k by the identical text.  Both directions are bit-reproducible: two calls with the same arguments give the same words.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, d_src, d_sh, d_gsh, d_gsrc, d_work, or d_den in the
+ * backward; n 0 or above SRZ_TEX_MAX_SIZE; n_ch 0 or above SRZ_SH_MAX_CH; tex_frames 0 or above 65536; work_bytes below
+ * srz_cube_sh_work_bytes; a pointer not 4-byte aligned; an output (d_sh, d_den, d_gsrc, d_work) that overlaps an input or another
+ * output.
+ *
+ * srz_frameset_sh / srz_frameset_sh_grad / srz_frameset_sh_work_bytes: SH9 EVALUATED AT EACH PIXEL'S NORMAL over a visibility
+ * buffer.  d_vis, d_nrm (3 planes), d_out / d_gout (n_ch planes, srz_frameset_interpolate_bytes(n_ch) bytes) and d_gnrm: exactly as in
+ * srz_frameset_light — band sharding, local_rows, stream semantics, asynchrony, the 16-byte alignment, owner and nobody, what a nobody
+ * pixel's words of the output planes become with and without SRZ_FUSED_CLEAR (zeros; untouched).  d_sh and d_gsh:
+ * [sh_frames][9][n_ch] float32 in device memory, 4-byte aligned; sh_frames is 1 (every frame shares the coefficients) or the set's
+ * frame count; 1 <= n_ch <= SRZ_SH_MAX_CH.  kind, a host argument: SRZ_SH_IRRADIANCE (K = H: the cosine-convolved function, E / pi)
+ * or SRZ_SH_RADIANCE (K = Yc: the function itself, for a low-frequency background or a test); no gradient to it.
+ * THE RULE, dot as srz_frameset_light's.  Per owned pixel with the normal n:
+ *   nn = dot(n, n);  lit = nn > 0 && nn < INFINITY;   not lit -> out = 0 in every channel (written), every gradient of the pixel 0, no term
+ *   inl = 1 / sqrtf(nn);  N = n * inl;  e_0 = K[0];  e_k = K[k] * p_k(N)  (k = 1 .. 8)
+ *   out_c = sh[0][c] * e_0, then out_c = fmaf(sh[k][c], e_k, out_c) for k = 1 .. 8.        There is NO CLAMP (SH ringing can go
+ *   slightly negative; a clamp would cut the gradient).
+ * BACKWARD: the exact derivative with the lit branch held, in THIS order of operations (g = gout of the pixel, N = (x, y, z)):
+ *   ge_k = g_0 * sh[k][0], then ge_k = fmaf(g_c, sh[k][c], ge_k) for c = 1 .. n_ch - 1;   gp_k = ge_k * K[k]       (k = 1 .. 8)
+ *   gN_x = fmaf(2.0f * x, gp_8, fmaf(gp_7, z, fmaf(gp_4, y, gp_3)))
+ *   gN_y = fmaf(-2.0f * y, gp_8, fmaf(gp_5, z, fmaf(gp_4, x, gp_1)))
+ *   gN_z = fmaf(6.0f * z, gp_6, fmaf(gp_7, x, fmaf(gp_5, y, gp_2)))
+ *   d = dot(gN, N);  gn_i = (gN_i - N_i * d) * inl
+ *   d_gnrm = gn: per pixel, deterministic, bit for bit.  d_gsh (needs d_work, at least srz_frameset_sh_work_bytes bytes, 4-byte
+ *   aligned, scratch) is WRITTEN, not added into: entry (k, c) is the sum over the frame's lit pixels on this shard of the float32
+ *   term g_c * e_k in srz_frameset_light_grad's FIXED tree, word for word (lane quads left to right, the butterfly, the four waves
+ *   through LDS, the tiles in tile order, then with sh_frames == 1 the frames in frame order): no atomics, BIT-REPRODUCIBLE for a
+ *   given shard layout, with one lit pixel in all that pixel's term (-0 comes out +0), +0 where nobody contributes, and within
+ *   n 2^-24 / (1 - n 2^-24) * sum |term| of the exact sum.  Ranks each write the sums of their own bands.  Each of d_gnrm and d_gsh
+ *   may be NULL, not both.
+ * SRZ_E_INVALID, the outputs untouched and nothing launched, for: a null ctx, set, d_vis, d_nrm, d_sh, d_out, d_gout, or both of
+ * d_gnrm, d_gsh; n_ch == 0 or above SRZ_SH_MAX_CH; sh_frames not 1 or the frame count; an unknown kind; a short out_bytes, or
+ * work_bytes with d_gsh; a misaligned pointer; any bit of `flags` but SRZ_FUSED_CLEAR; an output (d_work with d_gsh counts as one)
+ * that overlaps an input or another output; d_gsh without d_work. */
+#define SRZ_SH_MAX_CH 7 /* 9 * n_ch <= 63: a row of the fixed tree's 64 */
+#define SRZ_SH_IRRADIANCE 0u
+#define SRZ_SH_RADIANCE 1u
+size_t srz_cube_sh_work_bytes(uint32_t n, uint32_t n_ch, uint32_t tex_frames);
+int srz_cube_sh(srz_ctx *ctx, const float *d_src, uint32_t n, uint32_t n_ch, uint32_t tex_frames, float *d_sh, float *d_den, void *d_work,
+                size_t work_bytes, void *stream);
+int srz_cube_sh_grad(srz_ctx *ctx, const float *d_gsh, const float *d_den, uint32_t n, uint32_t n_ch, uint32_t tex_frames, float *d_gsrc,
+                     void *d_work, size_t work_bytes, void *stream);
+int srz_frameset_sh(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const float *d_sh, uint32_t n_ch, uint32_t sh_frames,
+                    uint32_t kind, void *d_out, size_t out_bytes, uint32_t flags, void *stream);
+size_t srz_frameset_sh_work_bytes(srz_ctx *ctx, srz_frameset *fs, uint32_t n_ch);
+int srz_frameset_sh_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const float *d_sh, uint32_t n_ch,
+                         uint32_t sh_frames, uint32_t kind, const void *d_gout, void *d_gnrm, float *d_gsh, void *d_work, size_t work_bytes,
+                         uint32_t flags, void *stream);
 /* IMAGE-BASED LIGHTING over a visibility buffer, for the caller's own planes, with gradients: the three pieces between
  * srz_cube_prefilter's cubes, the cube lookups and srz_frameset_microfacet's material — the reflection vector, the split-sum table of
  * srz_frameset_microfacet's OWN specular lobe, and the combine.  The chain: srz_brdf_table once; srz_frameset_reflect -> R and n.v;

@@ -3212,6 +3212,149 @@ int srz_cube_prefilter_grad(srz_ctx *ctx, const float *d_gdst, const float *d_de
   return end_pass(ctx);
 }
 
+// ---- SH9 lighting: a cube to its coefficients (no set), and the coefficients at each pixel's normal
+namespace {
+bool cube_sh_sizes_ok(uint32_t n, uint32_t n_ch, uint32_t tex_frames) {
+  return n != 0u && n <= SRZ_TEX_MAX_SIZE && n_ch != 0u && n_ch <= SRZ_SH_MAX_CH && tex_frames != 0u && tex_frames <= MIP_MAX_FRAMES;
+}
+// what srz_cube_sh and _cube_sh_grad check alike, the pointers apart
+int check_cube_sh(srz_ctx *ctx, const std::string &fn, uint32_t n, uint32_t n_ch, uint32_t tex_frames, const void *d_work, size_t work_bytes) {
+  if (n == 0u || n > SRZ_TEX_MAX_SIZE) return fail(ctx, SRZ_E_INVALID, fn + ": n must be 1 .. SRZ_TEX_MAX_SIZE");
+  if (n_ch == 0u || n_ch > SRZ_SH_MAX_CH) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_SH_MAX_CH");
+  if (tex_frames == 0u || tex_frames > MIP_MAX_FRAMES) return fail(ctx, SRZ_E_INVALID, fn + ": tex_frames must be 1 .. 65536");
+  if (!d_work) return fail(ctx, SRZ_E_INVALID, fn + ": null d_work");
+  if (work_bytes < srz_cube_sh_work_bytes(n, n_ch, tex_frames)) return fail(ctx, SRZ_E_INVALID, fn + ": work_bytes is below srz_cube_sh_work_bytes");
+  return SRZ_OK;
+}
+// what srz_frameset_sh and _sh_grad check alike (check_light's shape); the coefficients' bytes in *sh_bytes
+int check_sh(srz_ctx *ctx, const srz_frameset *fs, const std::string &fn, uint32_t n_ch, uint32_t sh_frames, uint32_t kind, uint32_t flags,
+             size_t *sh_bytes) {
+  if (n_ch == 0u || n_ch > SRZ_SH_MAX_CH) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. SRZ_SH_MAX_CH");
+  if (kind != SRZ_SH_IRRADIANCE && kind != SRZ_SH_RADIANCE) return fail(ctx, SRZ_E_INVALID, fn + ": kind must be SRZ_SH_IRRADIANCE or SRZ_SH_RADIANCE");
+  if (int rc = check_pass_flags(ctx, fn, flags)) return rc;
+  if (sh_frames != 1u && sh_frames != (uint32_t)fs->n_frames)
+    return fail(ctx, SRZ_E_INVALID, fn + ": sh_frames must be 1 or the set's frame count");
+  *sh_bytes = (size_t)sh_frames * 9u * n_ch * sizeof(float);
+  return SRZ_OK;
+}
+ShArgs sh_args(const srz_frameset *fs, const void *d_vis, const void *d_nrm, const float *d_sh, uint32_t n_ch, uint32_t sh_frames, uint32_t kind,
+               void *d_out, uint32_t flags) {
+  ShArgs a{};
+  const uint64_t plane = plane_words(fs);
+  fill_walk(a, fs, d_vis, d_out);
+  a.nrm = (const float *)d_nrm, a.sh = d_sh;
+  a.vis_stride = 4ull * plane, a.frame_stride = n_ch * plane, a.nrm_stride = 3ull * plane;
+  a.sh_stride = sh_frames == 1u ? 0ull : 9ull * n_ch;
+  a.n_ch = n_ch, a.kind = kind;
+  a.flags_or = flags;
+  return a;
+}
+} // namespace
+
+size_t srz_cube_sh_work_bytes(uint32_t n, uint32_t n_ch, uint32_t tex_frames) {
+  if (!cube_sh_sizes_ok(n, n_ch, tex_frames)) return 0;
+  return cube_sh_work_floats(n, n_ch, tex_frames) * sizeof(float); // (the backward's q fits in front of it)
+}
+
+int srz_cube_sh(srz_ctx *ctx, const float *d_src, uint32_t n, uint32_t n_ch, uint32_t tex_frames, float *d_sh, float *d_den, void *d_work,
+                size_t work_bytes, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_cube_sh");
+  if (!d_src || !d_sh) return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!d_src ? "d_src" : "d_sh"));
+  if (int rc = check_cube_sh(ctx, fn, n, n_ch, tex_frames, d_work, work_bytes)) return rc;
+  if (!aligned<4>({d_src, d_sh, d_den, d_work})) return fail(ctx, SRZ_E_INVALID, fn + ": d_src, d_sh, d_den and d_work must be 4-byte aligned");
+  const size_t need = srz_cube_sh_work_bytes(n, n_ch, tex_frames), sh_bytes = (size_t)tex_frames * 9u * n_ch * sizeof(float);
+  const size_t src_bytes = (size_t)prefilter_texels(n) * tex_frames * n_ch * sizeof(float);
+  if (int rc = check_overlaps(ctx, fn + " (d_sh, d_den, d_work against d_src)", {{d_sh, sh_bytes}, {d_den, sizeof(float)}, {d_work, need}},
+                              {{d_src, src_bytes}}))
+    return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  CubeShArgs a{};
+  a.src = d_src, a.dst = d_sh, a.den_out = d_den, a.work = (float *)d_work;
+  a.n = n, a.n_ch = n_ch, a.frames = tex_frames;
+  launch_cube_sh(a, pick_stream(ctx, stream));
+  return end_pass(ctx);
+}
+
+int srz_cube_sh_grad(srz_ctx *ctx, const float *d_gsh, const float *d_den, uint32_t n, uint32_t n_ch, uint32_t tex_frames, float *d_gsrc,
+                     void *d_work, size_t work_bytes, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_cube_sh_grad");
+  if (!d_gsh || !d_den || !d_gsrc) return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!d_gsh ? "d_gsh" : !d_den ? "d_den" : "d_gsrc"));
+  if (int rc = check_cube_sh(ctx, fn, n, n_ch, tex_frames, d_work, work_bytes)) return rc;
+  if (!aligned<4>({d_gsh, d_den, d_gsrc, d_work})) return fail(ctx, SRZ_E_INVALID, fn + ": d_gsh, d_den, d_gsrc and d_work must be 4-byte aligned");
+  const size_t need = srz_cube_sh_work_bytes(n, n_ch, tex_frames), sh_bytes = (size_t)tex_frames * 9u * n_ch * sizeof(float);
+  const size_t gsrc_bytes = (size_t)prefilter_texels(n) * tex_frames * n_ch * sizeof(float);
+  if (int rc = check_overlaps(ctx, fn + " (d_gsrc, d_work against d_gsh, d_den)", {{d_gsrc, gsrc_bytes}, {d_work, need}},
+                              {{d_gsh, sh_bytes}, {d_den, sizeof(float)}}))
+    return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  CubeShArgs a{};
+  a.src = d_gsh, a.den = d_den, a.dst = d_gsrc, a.work = (float *)d_work;
+  a.n = n, a.n_ch = n_ch, a.frames = tex_frames;
+  launch_cube_sh_grad(a, pick_stream(ctx, stream));
+  return end_pass(ctx);
+}
+
+int srz_frameset_sh(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const float *d_sh, uint32_t n_ch, uint32_t sh_frames,
+                    uint32_t kind, void *d_out, size_t out_bytes, uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_sh");
+  if (!fs || !d_vis || !d_nrm || !d_sh || !d_out)
+    return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_nrm ? "d_nrm" : !d_sh ? "d_sh" : "d_out"));
+  size_t sh_bytes = 0;
+  if (int rc = check_sh(ctx, fs, fn, n_ch, sh_frames, kind, flags, &sh_bytes)) return rc;
+  const size_t need = srz_frameset_interpolate_bytes(ctx, fs, n_ch), nrm_bytes = srz_frameset_interpolate_bytes(ctx, fs, 3u);
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  if (out_bytes < need) return fail(ctx, SRZ_E_INVALID, fn + ": out_bytes is too small for d_out");
+  if (!aligned<16>({d_vis, d_nrm, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_nrm, d_out) must be 16-byte aligned");
+  if (!aligned<4>({d_sh})) return fail(ctx, SRZ_E_INVALID, fn + ": d_sh must be 4-byte aligned");
+  if (int rc = check_overlaps(ctx, fn + " (d_out against d_vis, d_nrm, d_sh)", {{d_out, need}},
+                              {{d_vis, vis_bytes}, {d_nrm, nrm_bytes}, {d_sh, sh_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc; // (as srz_frameset_light: caller data only)
+  launch_sh(sh_args(fs, d_vis, d_nrm, d_sh, n_ch, sh_frames, kind, d_out, flags), s);
+  return end_pass(ctx);
+}
+
+size_t srz_frameset_sh_work_bytes(srz_ctx *ctx, srz_frameset *fs, uint32_t n_ch) {
+  if (!ctx || !fs || n_ch == 0u || n_ch > SRZ_SH_MAX_CH) return 0;
+  // [frame][tile][K] partial sums, and [frame][K] rows for the fold of shared coefficients
+  return (size_t)fs->n_frames * ((size_t)fs->n_local_bands * fs->tiles_x + 1u) * 9u * n_ch * sizeof(float);
+}
+
+int srz_frameset_sh_grad(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_nrm, const float *d_sh, uint32_t n_ch,
+                         uint32_t sh_frames, uint32_t kind, const void *d_gout, void *d_gnrm, float *d_gsh, void *d_work, size_t work_bytes,
+                         uint32_t flags, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  const std::string fn("srz_frameset_sh_grad");
+  if (!fs || !d_vis || !d_nrm || !d_sh || !d_gout)
+    return fail(ctx, SRZ_E_INVALID, fn + ": null " + (!fs ? "frameset" : !d_vis ? "d_vis" : !d_nrm ? "d_nrm" : !d_sh ? "d_sh" : "d_gout"));
+  if (!d_gnrm && !d_gsh) return fail(ctx, SRZ_E_INVALID, fn + ": neither d_gnrm nor d_gsh is asked for");
+  if (d_gsh && !d_work) return fail(ctx, SRZ_E_INVALID, fn + ": d_gsh needs d_work");
+  size_t sh_bytes = 0;
+  if (int rc = check_sh(ctx, fs, fn, n_ch, sh_frames, kind, flags, &sh_bytes)) return rc;
+  const size_t gout_bytes = srz_frameset_interpolate_bytes(ctx, fs, n_ch), nrm_bytes = srz_frameset_interpolate_bytes(ctx, fs, 3u);
+  const size_t vis_bytes = srz_frameset_out_bytes(ctx, fs);
+  const size_t need_work = d_gsh ? srz_frameset_sh_work_bytes(ctx, fs, n_ch) : 0;
+  if (work_bytes < need_work) return fail(ctx, SRZ_E_INVALID, fn + ": work_bytes is below srz_frameset_sh_work_bytes");
+  if (!aligned<16>({d_vis, d_nrm, d_gout, d_gnrm}))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the plane buffers (d_vis, d_nrm, d_gout, d_gnrm) must be 16-byte aligned");
+  if (!aligned<4>({d_sh, d_gsh, d_gsh ? d_work : nullptr})) return fail(ctx, SRZ_E_INVALID, fn + ": d_sh, d_gsh and d_work must be 4-byte aligned");
+  if (int rc = check_overlaps(ctx, fn + " (d_gnrm, d_gsh, d_work against d_vis, d_nrm, d_sh, d_gout)",
+                              {{d_gnrm, nrm_bytes}, {d_gsh, sh_bytes}, {d_gsh ? d_work : nullptr, need_work}},
+                              {{d_vis, vis_bytes}, {d_nrm, nrm_bytes}, {d_sh, sh_bytes}, {d_gout, gout_bytes}}))
+    return rc;
+  hipStream_t s;
+  if (int rc = begin_pass(ctx, fs, stream, 0u, &s)) return rc;
+  ShArgs a = sh_args(fs, d_vis, d_nrm, d_sh, n_ch, sh_frames, kind, nullptr, flags);
+  a.gout = (const float *)d_gout, a.gnrm = (float *)d_gnrm;
+  a.work = d_gsh ? (float *)d_work : nullptr;
+  launch_sh_grad(a, d_gsh, s);
+  return end_pass(ctx);
+}
+
 int srz_frameset_texture_cube_mip(srz_ctx *ctx, srz_frameset *fs, const void *d_vis, const void *d_dir, const void *d_lam, const float *d_tex,
                                   uint32_t n, uint32_t n_ch, uint32_t tex_frames, const float *d_mip, uint32_t n_levels, void *d_out,
                                   size_t out_bytes, uint32_t flags, void *stream) {

@@ -756,6 +756,48 @@ struct PrefilterArgs {
 };
 void launch_prefilter(const PrefilterArgs &a, hipStream_t s);
 void launch_prefilter_grad(const PrefilterArgs &a, hipStream_t s);
+// srz_cube_sh / _cube_sh_grad (include/srz.h states the rule): a cube projected to nine SH coefficients per channel, one wave per
+// face row (k_cube_sh), the rows and then the faces added by k_light_fold, the division by k_cube_sh_finish; the backward a gather
+// per source texel (k_cube_sh_grad) behind k_cube_sh_q.  K = 9 n_ch + 1 (the last slot: den) <= 64.  The work buffer, in floats:
+//   forward:  [frame][face][row][K] row partials | [frame][face][K] face sums | [frame][K] cube sums
+//   backward: [frame][9 n_ch] q = (FOURPI * gsh) / den
+inline uint32_t cube_sh_slots(uint32_t n_ch) { return 9u * n_ch + 1u; }
+inline size_t cube_sh_work_floats(uint32_t n, uint32_t n_ch, uint32_t frames) {
+  return (size_t)frames * (6u * (size_t)n + 6u + 1u) * cube_sh_slots(n_ch);
+}
+struct CubeShArgs {
+  const float *src;  // forward: the cube; backward: gsh [frame][9][n_ch]
+  const float *den;  // backward: the forward's normaliser, one float
+  float *dst;        // forward: sh [frame][9][n_ch]; backward: gsrc, the cube's shape
+  float *den_out;    // forward: the normaliser (may be null)
+  float *work;       // the layout above
+  uint32_t n, n_ch, frames;
+};
+void launch_cube_sh(const CubeShArgs &a, hipStream_t s);
+void launch_cube_sh_grad(const CubeShArgs &a, hipStream_t s);
+// srz_frameset_sh / _sh_grad: SH9 coefficients sh [sh frames][9][n_ch] evaluated at the normal planes nrm [frame][3][..] (k_sh), and
+// the backward of that to the normal (gnrm, three planes, may be null) and to the coefficients (k_sh_grad).  `out` is the forward's
+// [frame][n_ch][..], null in the backward (which addresses its planes by the strides itself).  work: as LightArgs', K = 9 n_ch
+struct ShArgs {
+  const FrameDesc *frames;
+  const float *vis;
+  const float *nrm;
+  const float *sh;
+  float *out;
+  const float *gout;
+  float *gnrm;
+  float *work;
+  uint64_t vis_stride;   // floats per frame in vis = 4 * local_rows * width
+  uint64_t frame_stride; // floats per frame in out / gout = n_ch * local_rows * width
+  uint64_t nrm_stride;   // floats per frame in nrm / gnrm = 3 * local_rows * width
+  uint64_t sh_stride;    // floats per frame in sh = 9 * n_ch; 0: one set of coefficients for every frame
+  uint32_t n_ch, kind;
+  uint32_t local_rows, tiles_x, n_local_bands, n_frames;
+  int32_t shard_rank, shard_world;
+  uint32_t flags_or;
+};
+void launch_sh(const ShArgs &a, hipStream_t s);
+void launch_sh_grad(const ShArgs &a, float *gsh, hipStream_t s);
 // srz_frameset_interpolate_deriv: the screen-space derivatives of caller attributes (k_interp_deriv).  vis, attr and the walk as
 // InterpArgs has them, tri_pos / pos_stride as PosGradArgs; `out` is [frame][2 * n_ch][local_rows][width]
 struct InterpDerivArgs {

@@ -3380,10 +3380,11 @@ __global__ __launch_bounds__(256) void k_visibility(RenderArgs a) {
 // quad_load), k_persp (the walk, quad_ids), k_persp_grad and
 // k_interp_deriv_persp (all of it), k_light (the walk, quad_ids, quad_load, quad_store_owned) and k_light_grad (the same through
 // pass_tiles and pass_tile: the tile's index names its row of partial sums), k_normal_map and k_normal_map_grad (as k_light), k_microfacet and k_microfacet_grad (as k_light and k_light_grad),
-// k_reflect, k_reflect_grad, k_ibl and k_ibl_grad (as k_light).
+// k_reflect, k_reflect_grad, k_ibl and k_ibl_grad (as k_light), k_sh and k_sh_grad (as k_light and k_light_grad).
 // Beyond tile_grid's cap (a workgroup's second trip round pass_tiles' loop, with what it carries) the callers are tested in
-// tests/test_gpu_pass_walk.py (k_shade_vis, k_interp, k_interp_grad, k_interp_deriv, and the COPIES) and in
-// tests/test_gpu_pass_walk_lit.py (every other caller, and k_shadow and k_shadow_grad).
+// tests/test_gpu_pass_walk.py (k_shade_vis, k_interp, k_interp_grad, k_interp_deriv, and the COPIES), in
+// tests/test_gpu_pass_walk_lit.py (every other caller but the two below, and k_shadow and k_shadow_grad) and in
+// tests/test_gpu_pass_walk_sh.py (k_sh, k_sh_grad).
 // COPIES, each naming this definition — a fix to the walk goes into them too: k_gbuffer, k_motion, k_pos_grad, aa_body, k_tex,
 // k_tex_grad, k_tex_mip, k_tex_mip_grad (with tex_quad and mip_quad).  Moved onto these helpers they computed the same words
 // (the whole suite passed) but ran slower than their inline text on an MI355X at 256 frames of 1024²: k_gbuffer +4 %, k_motion +6 %,
@@ -6866,6 +6867,258 @@ template <bool BWD> __global__ __launch_bounds__(256) void k_prefilter_fold(PfWa
 }
 
 // ================================================================================================================
+// SH9 LIGHTING (srz_cube_sh, srz_frameset_sh and their backwards; include/srz.h states the rules and the constants).
+// sh_poly is the polynomials' text for both pieces; sh_yc / sh_h the constants by k.
+//   k_cube_sh         a cube -> the row partials of its nine coefficients per channel and of the normaliser: ONE WAVE PER FACE ROW,
+//                     lane j the columns j, j + 64, ..., pf_texel for the geometry (k_prefilter's, so the same words), the channels
+//                     PREFILTER_CG at a time in registers, the butterfly, lane 0's ordinary stores into work[row][K].  k_light_fold adds
+//                     a face's rows, then a frame's faces; k_cube_sh_finish divides.  No LDS, no barrier, no atomics.
+//   k_cube_sh_grad    the backward, a gather: a lane per source texel, q (k_cube_sh_q wrote it) wave-uniform through the scalar cache.
+//   k_sh              coefficients evaluated at each pixel's normal: k_light's shape on the passes' helpers, the coefficients read as
+//                     k_light reads its parameter frame; no LDS, no barrier; 16 bytes read and 4 n_ch written per owned pixel.
+//   k_sh_grad         gout -> gnrm (per pixel, from registers) and, WANT_SH, the tiles' partial sums of gsh in k_light_grad's fixed
+//                     tree, word for word; the CHANNELS are the outer loop, so a lane holds nine sums at a time.  k_light_fold as there.
+// ================================================================================================================
+constexpr float SH_FOURPI = 12.566371f;
+__device__ __forceinline__ float sh_yc(int k) {
+  constexpr float c[5] = {0x1.20dd76p-2f, 0x1.f45438p-2f, 0x1.17b142p+0f, 0x1.42f602p-2f, 0x1.17b142p-1f};
+  constexpr int idx[9] = {0, 1, 1, 1, 2, 2, 3, 2, 4};
+  return c[idx[k]];
+}
+__device__ __forceinline__ float sh_h(int k) {
+  constexpr float c[5] = {0x1.20dd76p-2f, 0x1.4d8d7ap-2f, 0x1.17b142p-2f, 0x1.42f602p-4f, 0x1.17b142p-3f};
+  constexpr int idx[9] = {0, 1, 1, 1, 2, 2, 3, 2, 4};
+  return c[idx[k]];
+}
+__device__ __forceinline__ void sh_poly(float x, float y, float z, float (&p)[9]) {
+  p[0] = 1.0f, p[1] = y, p[2] = z, p[3] = x, p[4] = x * y, p[5] = y * z;
+  p[6] = fmaf_(3.0f * z, z, -1.0f), p[7] = x * z, p[8] = fmaf_(x, x, -(y * y));
+}
+// w_k = jac * (Yc[k] * p_k(d)) of a texel
+__device__ __forceinline__ void sh_texel_weights(const PfTexel &t, float (&w)[9]) {
+  float p[9];
+  sh_poly(t.x, t.y, t.z, p);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) w[k] = t.jac * (sh_yc(k) * p[k]);
+}
+// one wave, one face row (row: frame * 6 n + face * n + y), NC channels from ch0; den with the first group
+template <int NC> __device__ __forceinline__ void cube_sh_row(const CubeShArgs &a, uint64_t row, uint32_t ch0, uint32_t lane) {
+  const uint32_t n = a.n, C = a.n_ch, K = 9u * C + 1u;
+  const uint32_t r = (uint32_t)(row % (6u * n)); // face * n + y: the row within its cube
+  const float *src = a.src + ((size_t)(row / (6u * n)) * 6u * n * n + (size_t)r * n) * C + ch0;
+  float acc[9][NC], den = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 9; ++k)
+#pragma unroll
+    for (int i = 0; i < NC; ++i) acc[k][i] = 0.0f;
+  for (uint32_t x = lane; x < n; x += 64u) {
+    const PfTexel t = pf_texel(n, r * n + x);
+    float w[9], v[NC];
+    sh_texel_weights(t, w);
+#pragma unroll
+    for (int i = 0; i < NC; ++i) v[i] = src[(size_t)x * C + i];
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+#pragma unroll
+      for (int i = 0; i < NC; ++i) acc[k][i] = fmaf_(w[k], v[i], acc[k][i]);
+    den = den + t.jac;
+  }
+  float *part = a.work + (size_t)row * K;
+#pragma unroll
+  for (int k = 0; k < 9; ++k)
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+      const float s = light_wave_sum(acc[k][i]);
+      if (lane == 0u) part[(uint32_t)k * C + ch0 + (uint32_t)i] = s;
+    }
+  if (ch0 == 0u) {
+    const float s = light_wave_sum(den);
+    if (lane == 0u) part[9u * C] = s;
+  }
+}
+__global__ __launch_bounds__(256) void k_cube_sh(CubeShArgs a) {
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint64_t rows = (uint64_t)a.frames * 6u * a.n;
+  for (uint64_t row = (uint64_t)blockIdx.x * 4u + wave; row < rows; row += (uint64_t)gridDim.x * 4u) // (wave-uniform)
+    for (uint32_t ch0 = 0; ch0 < a.n_ch; ch0 += PREFILTER_CG) {
+      const uint32_t nc = a.n_ch - ch0;
+      if (nc >= 4u) cube_sh_row<4>(a, row, ch0, lane);
+      else if (nc == 3u) cube_sh_row<3>(a, row, ch0, lane);
+      else if (nc == 2u) cube_sh_row<2>(a, row, ch0, lane);
+      else cube_sh_row<1>(a, row, ch0, lane);
+    }
+}
+// cube: [frame][K] sums, the last slot den -> sh [frame][9][n_ch], and frame 0's den into den_out when non-null
+__global__ __launch_bounds__(256) void k_cube_sh_finish(const float *cube, float *sh, float *den_out, uint32_t C, uint32_t frames) {
+  const uint32_t per = 9u * C, i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= per * frames) return;
+  const float *row = cube + (size_t)(i / per) * (per + 1u);
+  const float den = row[per];
+  sh[i] = (SH_FOURPI * row[i % per]) / den;
+  if (den_out && i == 0u) den_out[0] = den;
+}
+// the backward's q = (FOURPI * gsh) / den, [frames][9][n_ch]
+__global__ __launch_bounds__(256) void k_cube_sh_q(const float *gsh, const float *den, float *q, uint32_t count) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < count) q[i] = (SH_FOURPI * gsh[i]) / den[0];
+}
+__global__ __launch_bounds__(256) void k_cube_sh_grad(CubeShArgs a) {
+  const uint32_t C = a.n_ch, texels = 6u * a.n * a.n, bpf = (texels + 255u) / 256u;
+  const uint64_t total = (uint64_t)a.frames * bpf;
+  for (uint64_t b = blockIdx.x; b < total; b += gridDim.x) {
+    const uint32_t frame = (uint32_t)(b / bpf), texel = (uint32_t)(b % bpf) * 256u + threadIdx.x;
+    if (texel >= texels) continue;
+    const SRZ_CAS float *q = as_const(a.work) + (size_t)frame * 9u * C; // (wave-uniform: scalar loads)
+    float w[9];
+    sh_texel_weights(pf_texel(a.n, texel), w);
+    float *g = a.dst + ((size_t)frame * texels + texel) * C;
+    for (uint32_t c = 0; c < C; ++c) {
+      float v = w[0] * q[c];
+#pragma unroll
+      for (uint32_t k = 1; k < 9u; ++k) v = fmaf_(w[k], q[k * C + c], v);
+      g[c] = v;
+    }
+  }
+}
+
+struct ShPx {
+  float N[3], inl;
+  float e[9]; // e_k = K[k] * p_k(N), e_0 = K[0]
+};
+// what k_sh and k_sh_grad do alike in front of the channels: the owners, the normals of a quad with an owner, the lit pixels' ShPx
+// -> `own` and `lit`, one bit per pixel
+__device__ __forceinline__ void sh_quad(const ShArgs &a, const PassTile &t, ShPx (&px)[4], uint32_t &own, uint32_t &lit) {
+  uint32_t id[4];
+  own = quad_ids(t, a.vis + (size_t)t.f * a.vis_stride + t.poff, id), lit = 0u;
+  if (own == 0u) return;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 n[3] = {zero4, zero4, zero4};
+  quad_load(a.nrm + (size_t)t.f * a.nrm_stride + t.poff, t.rc.plane, n, t.whole, t.x4, t.rc.tx1);
+  const bool rad = a.kind == SRZ_SH_RADIANCE;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (!(own & (1u << k))) continue;
+    const float nk[3] = {quad_at(n[0], k), quad_at(n[1], k), quad_at(n[2], k)};
+    const float nn = l_dot(nk, nk);
+    if (!l_pos(nn)) continue;
+    lit |= 1u << k;
+    ShPx &p = px[k];
+    p.inl = l_rsqrt(nn);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) p.N[i] = nk[i] * p.inl;
+    float poly[9];
+    sh_poly(p.N[0], p.N[1], p.N[2], poly);
+    p.e[0] = rad ? sh_yc(0) : sh_h(0);
+#pragma unroll
+    for (int j = 1; j < 9; ++j) p.e[j] = (rad ? sh_yc(j) : sh_h(j)) * poly[j];
+  }
+}
+__global__ __launch_bounds__(256) void k_sh(ShArgs a) {
+  const uint32_t C = a.n_ch;
+  pass_walk<false>(a, [&](const PassTile &t) { // (no barrier in this kernel: a thread outside the frame just moves on)
+    const bool fused = t.fused(a.flags_or);
+    const SRZ_CAS float *sh = as_const(a.sh) + (size_t)t.f * a.sh_stride;
+    ShPx px[4];
+    uint32_t own, lit;
+    sh_quad(a, t, px, own, lit);
+    if (own == 0u && !fused) return;
+    for (uint32_t c = 0; c < C; ++c) {
+      float4 o = make_float4(0.f, 0.f, 0.f, 0.f); // nobody, and an owner that is not lit: zeros
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(lit & (1u << k))) continue;
+        float v = sh[c] * px[k].e[0];
+#pragma unroll
+        for (uint32_t j = 1; j < 9u; ++j) v = fmaf_(sh[j * C + c], px[k].e[j], v);
+        quad_at(o, k) = v;
+      }
+      quad_store_owned(t.out + (size_t)c * t.rc.plane, t, {o}, fused, own);
+    }
+  });
+}
+template <bool WANT_SH> __global__ __launch_bounds__(256) void k_sh_grad(ShArgs a) {
+  __shared__ float s_part[WANT_SH ? 4 : 1][WANT_SH ? 64 : 1];
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  const uint32_t C = a.n_ch, K = 9u * C, tpf = a.n_local_bands * a.tiles_x;
+  const bool rad = a.kind == SRZ_SH_RADIANCE;
+  pass_tiles(a, [&](uint32_t f, uint32_t ti) {
+    const PassTile t = pass_tile(a, f, ti);
+    const bool fused = t.fused(a.flags_or);
+    const SRZ_CAS float *sh = as_const(a.sh) + (size_t)f * a.sh_stride;
+    float *gn_out = a.gnrm ? a.gnrm + (size_t)f * a.nrm_stride + t.poff : nullptr;
+    // ---- 1. owners, normals, the lit pixels
+    ShPx px[4];
+    uint32_t own, lit;
+    sh_quad(a, t, px, own, lit);
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (WANT_SH) {
+      // a tile without a lit pixel: its partials are the empty sums, +0, what the tree below gives too, without the shuffles
+      if (!__syncthreads_or(lit != 0u)) {
+        if (gn_out && t.inside && (own != 0u || fused)) {
+          const float4 z[3] = {zero4, zero4, zero4};
+          quad_store_owned(gn_out, t, z, fused, own);
+        }
+        if (tid < K) a.work[((size_t)f * tpf + ti) * K + tid] = 0.0f;
+        return;
+      }
+    }
+    // ---- 2. the channels: ge_k summed over them ascending; a channel's nine lane sums reduced and put into LDS as it ends
+    float ge[4][9];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int j = 0; j < 9; ++j) ge[k][j] = 0.0f;
+    for (uint32_t c = 0; c < C; ++c) {
+      float4 g[1] = {zero4};
+      if (lit != 0u) quad_load(a.gout + (size_t)f * a.frame_stride + (size_t)c * t.rc.plane + t.poff, t.rc.plane, g, t.whole, t.x4, t.rc.tx1);
+      float tl[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; // this lane's sums of the channel's terms
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(lit & (1u << k))) continue;
+        const float gc = quad_at(g[0], k);
+#pragma unroll
+        for (uint32_t j = 0; j < 9u; ++j) {
+          if (WANT_SH) tl[j] = tl[j] + gc * px[k].e[j];
+          if (j != 0u) ge[k][j] = c == 0u ? gc * sh[j * C] : fmaf_(gc, sh[j * C + c], ge[k][j]);
+        }
+      }
+      if (WANT_SH) { // (every lane of the workgroup is here: the walk and the channel count are uniform)
+#pragma unroll
+        for (uint32_t j = 0; j < 9u; ++j) {
+          const float v = light_wave_sum(tl[j]);
+          if (lane == 0u) s_part[wave][j * C + c] = v;
+        }
+      }
+    }
+    // ---- 3. the normal's gradient through the polynomials and the normalisation
+    if (gn_out && t.inside && (own != 0u || fused)) {
+      float4 gn[3] = {zero4, zero4, zero4};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!(lit & (1u << k))) continue;
+        const float x = px[k].N[0], y = px[k].N[1], z = px[k].N[2];
+        float gp[9];
+#pragma unroll
+        for (int j = 1; j < 9; ++j) gp[j] = ge[k][j] * (rad ? sh_yc(j) : sh_h(j));
+        const float gN[3] = {fmaf_(2.0f * x, gp[8], fmaf_(gp[7], z, fmaf_(gp[4], y, gp[3]))),
+                             fmaf_(-2.0f * y, gp[8], fmaf_(gp[5], z, fmaf_(gp[4], x, gp[1]))),
+                             fmaf_(6.0f * z, gp[6], fmaf_(gp[7], x, fmaf_(gp[5], y, gp[2])))};
+        const float d = l_dot(gN, px[k].N);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) quad_at(gn[i], k) = (gN[i] - px[k].N[i] * d) * px[k].inl;
+      }
+      quad_store_owned(gn_out, t, gn, fused, own);
+    }
+    // ---- 4. the tile's K partial sums
+    if (WANT_SH) {
+      __syncthreads();
+      if (tid < K) a.work[((size_t)f * tpf + ti) * K + tid] = ((s_part[0][tid] + s_part[1][tid]) + s_part[2][tid]) + s_part[3][tid];
+      __syncthreads(); // s_part is the next tile's too
+    }
+  });
+}
+
+// ================================================================================================================
 // k_interp_deriv — SCREEN-SPACE DERIVATIVES OF CALLER ATTRIBUTES (srz_frameset_interpolate_deriv, include/srz.h): interpolation is
 // affine in the sample point with owners held fixed (k_pos_grad's ∇α, ∇β), so channel ch of the owner changes per one-pixel step by
 // (a − c) ∇α + (b − c) ∇β: a constant of the triangle.  k_interp's walk, loads and stores (no LDS, no barrier), plus load_pos9 of
@@ -8922,6 +9175,35 @@ template <bool BWD> static void launch_prefilter_impl(const PrefilterArgs &p, hi
 }
 void launch_prefilter(const PrefilterArgs &a, hipStream_t s) { launch_prefilter_impl<false>(a, s); }
 void launch_prefilter_grad(const PrefilterArgs &a, hipStream_t s) { launch_prefilter_impl<true>(a, s); }
+// the rows' partials, k_light_fold twice (a face's rows, a frame's faces: K = 9 n_ch + 1 of its 64 threads), the division
+constexpr uint32_t CUBE_SH_GRID = 65536;
+void launch_cube_sh(const CubeShArgs &a, hipStream_t s) {
+  const uint32_t K = cube_sh_slots(a.n_ch);
+  const uint64_t rows = (uint64_t)a.frames * 6u * a.n;
+  float *faces = a.work + (size_t)rows * K, *cube = faces + (size_t)a.frames * 6u * K;
+  hipLaunchKernelGGL(k_cube_sh, dim3((uint32_t)std::min<uint64_t>((rows + 3u) / 4u, CUBE_SH_GRID)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_light_fold, dim3(a.frames * 6u), dim3(64), 0, s, (const float *)a.work, faces, a.n, K);
+  hipLaunchKernelGGL(k_light_fold, dim3(a.frames), dim3(64), 0, s, (const float *)faces, cube, 6u, K);
+  const uint32_t count = a.frames * 9u * a.n_ch;
+  hipLaunchKernelGGL(k_cube_sh_finish, dim3((count + 255u) / 256u), dim3(256), 0, s, (const float *)cube, a.dst, a.den_out, a.n_ch, a.frames);
+}
+void launch_cube_sh_grad(const CubeShArgs &a, hipStream_t s) {
+  const uint32_t count = a.frames * 9u * a.n_ch;
+  const uint64_t blocks = (uint64_t)a.frames * ((6u * a.n * a.n + 255u) / 256u);
+  hipLaunchKernelGGL(k_cube_sh_q, dim3((count + 255u) / 256u), dim3(256), 0, s, a.src, a.den, a.work, count);
+  hipLaunchKernelGGL(k_cube_sh_grad, dim3((uint32_t)std::min<uint64_t>(blocks, 1u << 20)), dim3(256), 0, s, a);
+}
+void launch_sh(const ShArgs &a, hipStream_t s) { launch_pass<k_sh>(a, s); }
+// (launch_light_grad's two steps over rows of 9 n_ch, k_light_fold unchanged; sh_stride == 0: one set of coefficients for every frame)
+void launch_sh_grad(const ShArgs &a, float *gsh, hipStream_t s) {
+  if (!gsh) return launch_pass<k_sh_grad<false>>(a, s);
+  const uint32_t tpf = a.n_local_bands * a.tiles_x, K = 9u * a.n_ch;
+  const bool shared = a.sh_stride == 0u;
+  launch_pass<k_sh_grad<true>>(a, s);
+  float *rows = shared ? a.work + (size_t)a.n_frames * tpf * K : gsh;
+  if (a.n_frames != 0u) hipLaunchKernelGGL(k_light_fold, dim3(a.n_frames), dim3(64), 0, s, (const float *)a.work, rows, tpf, K);
+  if (shared) hipLaunchKernelGGL(k_light_fold, dim3(1), dim3(64), 0, s, (const float *)rows, gsh, a.n_frames, K);
+}
 
 bool raster_four_waves(const RenderArgs &a) { return a.n_frames * a.n_local_bands * a.tiles_x <= 4096u; }
 

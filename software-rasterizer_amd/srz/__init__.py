@@ -36,6 +36,8 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_cube_mip_levels", "srz_cube_mip_bytes", "srz_cube_mip_build", "srz_cube_mip_fold",
            "srz_frameset_texture_cube_mip", "srz_frameset_texture_cube_mip_grad", "srz_frameset_cube_level",
            "srz_cube_prefilter_work_bytes", "srz_cube_prefilter", "srz_cube_prefilter_grad",
+           "srz_cube_sh_work_bytes", "srz_cube_sh", "srz_cube_sh_grad",
+           "srz_frameset_sh", "srz_frameset_sh_work_bytes", "srz_frameset_sh_grad",
            "srz_frameset_light", "srz_frameset_light_work_bytes", "srz_frameset_light_grad",
            "srz_frameset_microfacet", "srz_frameset_microfacet_work_bytes", "srz_frameset_microfacet_grad",
            "srz_frameset_reflect", "srz_frameset_reflect_grad", "srz_brdf_table", "srz_frameset_ibl", "srz_frameset_ibl_grad",
@@ -141,6 +143,14 @@ def lib():
         L.srz_cube_prefilter_work_bytes.restype = C.c_size_t
         L.srz_cube_prefilter.argtypes = abi.CUBE_PREFILTER_ARGTYPES
         L.srz_cube_prefilter_grad.argtypes = abi.CUBE_PREFILTER_GRAD_ARGTYPES
+        L.srz_cube_sh_work_bytes.argtypes = abi.CUBE_SH_WORK_BYTES_ARGTYPES
+        L.srz_cube_sh_work_bytes.restype = C.c_size_t
+        L.srz_cube_sh.argtypes = abi.CUBE_SH_ARGTYPES
+        L.srz_cube_sh_grad.argtypes = abi.CUBE_SH_GRAD_ARGTYPES
+        L.srz_frameset_sh.argtypes = abi.SH_ARGTYPES
+        L.srz_frameset_sh_work_bytes.argtypes = abi.SH_WORK_BYTES_ARGTYPES
+        L.srz_frameset_sh_work_bytes.restype = C.c_size_t
+        L.srz_frameset_sh_grad.argtypes = abi.SH_GRAD_ARGTYPES
         L.srz_frameset_light.argtypes = abi.LIGHT_ARGTYPES
         L.srz_frameset_light_work_bytes.argtypes = abi.LIGHT_WORK_BYTES_ARGTYPES
         L.srz_frameset_light_work_bytes.restype = C.c_size_t
@@ -611,6 +621,29 @@ class FrameSet:
                                                       C.c_void_p(d_gkd_ptr or None), C.c_void_p(d_gpar_ptr or None),
                                                       C.c_void_p(d_work_ptr or None), work_bytes, flags, _stream(stream)))
 
+    def sh(self, d_vis_ptr, d_nrm_ptr, d_sh_ptr, n_ch, sh_frames, kind, d_out_ptr, out_bytes, flags=abi.FUSED_CLEAR, stream=None):
+        """nine order-2 spherical-harmonic coefficients per channel d_sh [sh_frames][9][n_ch] (sh_frames: 1 or the frame count; 1 <=
+        n_ch <= abi.SH_MAX_CH) evaluated at the caller's normal planes d_nrm [frame][3][local_rows][width] → d_out
+        [frame][n_ch][local_rows][width], unclamped: the irradiance over pi (kind abi.SH_IRRADIANCE, ibl's `irr`) or the function
+        itself (abi.SH_RADIANCE) (include/srz.h states the rule).  Pixels nobody owns are zeros with FUSED_CLEAR, else left untouched;
+        an owner whose normal has no finite positive length gets zeros.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_sh(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_nrm_ptr), C.c_void_p(d_sh_ptr), n_ch,
+                                              sh_frames, kind, C.c_void_p(d_out_ptr), out_bytes, flags, _stream(stream)))
+
+    def sh_work_bytes(self, n_ch):
+        """bytes of the scratch buffer sh_grad needs for d_gsh; 0 for n_ch == 0 or above abi.SH_MAX_CH"""
+        return int(lib().srz_frameset_sh_work_bytes(self.ctx.h, self.h, n_ch))
+
+    def sh_grad(self, d_vis_ptr, d_nrm_ptr, d_sh_ptr, n_ch, sh_frames, kind, d_gout_ptr, d_gnrm_ptr, d_gsh_ptr, d_work_ptr, work_bytes,
+                flags=abi.FUSED_CLEAR, stream=None):
+        """the backward of sh: d_gout [frame][n_ch][local_rows][width] → written to d_gnrm (three planes, deterministic) and / or d_gsh
+        (d_sh's shape: WRITTEN, reduced in a fixed tree, bit-reproducible for a shard layout; needs d_work of sh_work_bytes(n_ch)
+        bytes).  Each output pointer may be None / 0, not both.  Asynchronous."""
+        self.ctx._check(lib().srz_frameset_sh_grad(self.ctx.h, self.h, C.c_void_p(d_vis_ptr), C.c_void_p(d_nrm_ptr), C.c_void_p(d_sh_ptr), n_ch,
+                                                   sh_frames, kind, C.c_void_p(d_gout_ptr), C.c_void_p(d_gnrm_ptr or None),
+                                                   C.c_void_p(d_gsh_ptr or None), C.c_void_p(d_work_ptr or None), work_bytes, flags,
+                                                   _stream(stream)))
+
     def microfacet(self, d_vis_ptr, d_nrm_ptr, d_pos_ptr, d_base_ptr, d_mat_ptr, d_par_ptr, n_lights, par_frames, d_out_ptr, out_bytes,
                    flags=abi.FUSED_CLEAR, stream=None):
         """Cook-Torrance (GGX, Schlick-Smith, Schlick Fresnel; metallic-roughness) under n_lights point lights for the caller's planes
@@ -997,6 +1030,24 @@ class Context:
         d_gsrc_ptr (written, not added into), deterministic.  Asynchronous."""
         self._check(lib().srz_cube_prefilter_grad(self.h, C.c_void_p(d_gdst_ptr), C.c_void_p(d_den_ptr), n_src, n_dst, n_ch, tex_frames, kind,
                                                   roughness, cmin, C.c_void_p(d_gsrc_ptr), C.c_void_p(d_work_ptr), work_bytes, _stream(stream)))
+
+    def cube_sh_work_bytes(self, n, n_ch, tex_frames):
+        """bytes of the scratch cube_sh and cube_sh_grad take for these sizes (0: a size out of range)"""
+        return int(lib().srz_cube_sh_work_bytes(n, n_ch, tex_frames))
+
+    def cube_sh(self, d_src_ptr, n, n_ch, tex_frames, d_sh_ptr, d_den_ptr, d_work_ptr, work_bytes, stream=None):
+        """the float32 cube [tex_frames][6][n][n][n_ch] at d_src_ptr projected to its nine order-2 spherical-harmonic coefficients per
+        channel → d_sh_ptr [tex_frames][9][n_ch] and (d_den_ptr not None / 0) the normaliser, one float; d_work_ptr: cube_sh_work_bytes
+        bytes of scratch; 1 <= n_ch <= abi.SH_MAX_CH.  One O(n²) pass summed in a fixed tree: deterministic, no atomics (include/srz.h
+        states the rule).  Asynchronous."""
+        self._check(lib().srz_cube_sh(self.h, C.c_void_p(d_src_ptr), n, n_ch, tex_frames, C.c_void_p(d_sh_ptr), C.c_void_p(d_den_ptr or None),
+                                      C.c_void_p(d_work_ptr), work_bytes, _stream(stream)))
+
+    def cube_sh_grad(self, d_gsh_ptr, d_den_ptr, n, n_ch, tex_frames, d_gsrc_ptr, d_work_ptr, work_bytes, stream=None):
+        """the backward of cube_sh, a gather per source texel: d_gsh_ptr [tex_frames][9][n_ch] and the normaliser the forward wrote →
+        d_gsrc_ptr, the cube's shape (written, not added into), deterministic.  Asynchronous."""
+        self._check(lib().srz_cube_sh_grad(self.h, C.c_void_p(d_gsh_ptr), C.c_void_p(d_den_ptr), n, n_ch, tex_frames, C.c_void_p(d_gsrc_ptr),
+                                           C.c_void_p(d_work_ptr), work_bytes, _stream(stream)))
 
     def brdf_table(self, d_tab_ptr, tab_bytes, n, m, stream=None):
         """the split-sum table of FrameSet.microfacet's own specular lobe → d_tab [n][n][2] float32 (A, B; F0 A + B is the lobe's

@@ -91,6 +91,16 @@ PREFILTER_COSINE, PREFILTER_GGX = 0, 1  # SRZ_PREFILTER_*
 CUBE_PREFILTER_WORK_BYTES_ARGTYPES = [_u32, _u32, _u32, _u32]
 CUBE_PREFILTER_ARGTYPES = [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, C.c_float, C.c_float, _vp, _vp, C.c_size_t, _vp]
 CUBE_PREFILTER_GRAD_ARGTYPES = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, C.c_float, C.c_float, _vp, _vp, C.c_size_t, _vp]
+# the prototypes of srz_cube_sh_work_bytes (returns size_t) / srz_cube_sh / _cube_sh_grad and of srz_frameset_sh / _sh_work_bytes
+# (returns size_t) / _sh_grad (argtypes), set by srz.lib()
+SH_MAX_CH = 7  # srz_cube_sh, srz_frameset_sh: the most channels of one call (SRZ_SH_MAX_CH)
+SH_IRRADIANCE, SH_RADIANCE = 0, 1  # srz_frameset_sh: `kind` (SRZ_SH_*)
+CUBE_SH_WORK_BYTES_ARGTYPES = [_u32, _u32, _u32]
+CUBE_SH_ARGTYPES = [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, C.c_size_t, _vp]
+CUBE_SH_GRAD_ARGTYPES = [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, C.c_size_t, _vp]
+SH_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, C.c_size_t, _u32, _vp]
+SH_WORK_BYTES_ARGTYPES = [_vp, _vp, _u32]
+SH_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, C.c_size_t, _u32, _vp]
 # the prototypes of srz_frameset_reflect / _reflect_grad / srz_brdf_table / srz_frameset_ibl / _ibl_grad (argtypes; all return int)
 BRDF_TABLE_MAX = 64  # srz_brdf_table, srz_frameset_ibl: the largest table side (SRZ_BRDF_TABLE_MAX)
 REFLECT_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, C.c_size_t, _u32, _vp]

@@ -1644,6 +1644,112 @@ def cube_irradiance(ctx_or_fs, cube, n_out, stream=None):
     return cube_prefilter(ctx_or_fs, cube, n_out, abi.PREFILTER_COSINE, 1.0, 0.0, stream)
 
 
+class _OwnFrames:
+    """what _lead_frames asks of a set, for an array whose frame count is its own — a cube's, not a set's: any count agrees"""
+
+    def __init__(self, t):
+        self.n_frames = t.shape[0] if t is not None and t.dim() else 0
+
+
+def _cube_sh_work(ctx, n, n_ch, frames, device):
+    nbytes = ctx.cube_sh_work_bytes(n, n_ch, frames)
+    return torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=device), nbytes
+
+
+def cube_sh_grad(ctx_or_fs, gsh, den, n, stream=None):
+    """the backward of cube_sh by one Context.cube_sh_grad call: gsh [9, C] or [frames, 9, C] and den [1] as the forward kept it →
+    the gradient of the source cube, [..., 6, n, n, C] — a gather per texel, bit-reproducible."""
+    ctx = getattr(ctx_or_fs, "ctx", ctx_or_fs)
+    frames = _lead_frames(_OwnFrames(gsh), gsh, (2, 3), "cube_sh_grad: gsh", "a CUDA float32 tensor [9, C] or [frames, 9, C]",
+                          lambda t: t.shape[-2] == 9)
+    _lead_frames(_OwnFrames(den), den, (1,), "cube_sh_grad: den", "a CUDA float32 tensor [1]", lambda t: t.shape[0] == 1)
+    gsh, den, n_ch = gsh.contiguous(), den.contiguous(), gsh.shape[-1]
+    gsrc = torch.empty(tuple(gsh.shape[:-2]) + (6, n, n, n_ch), dtype=torch.float32, device=gsh.device)
+    work, nbytes = _cube_sh_work(ctx, n, n_ch, frames, gsh.device)
+    ctx.cube_sh_grad(gsh.data_ptr(), den.data_ptr(), n, n_ch, frames, gsrc.data_ptr(), work.data_ptr(), nbytes, _stream_ptr(stream))
+    return gsrc
+
+
+class _CubeSh(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cube, c, stream):
+        frames, n, n_ch = _prefilter_dims(cube, "cube_sh")
+        cube = cube.contiguous()
+        sh = torch.empty(tuple(cube.shape[:-4]) + (9, n_ch), dtype=torch.float32, device=cube.device)
+        den = torch.empty((1,), dtype=torch.float32, device=cube.device)
+        work, nbytes = _cube_sh_work(c, n, n_ch, frames, cube.device)
+        c.cube_sh(cube.data_ptr(), n, n_ch, frames, sh.data_ptr(), den.data_ptr(), work.data_ptr(), nbytes, _stream_ptr(stream))
+        ctx.c, ctx.n, ctx.stream, ctx.den = c, n, stream, den
+        return sh
+
+    @staticmethod
+    def backward(ctx, gsh):
+        g = cube_sh_grad(ctx.c, gsh, ctx.den, ctx.n, ctx.stream) if ctx.needs_input_grad[0] else None
+        return g, None, None
+
+
+def cube_sh(ctx_or_fs, cube, stream=None):
+    """a CUDA float32 cube [6, N, N, C] or [frames, 6, N, N, C], C <= abi.SH_MAX_CH, projected to its nine order-2 spherical-harmonic
+    coefficients per channel → [9, C] or [frames, 9, C] (Context.cube_sh; include/srz.h states the rule): one O(N²) pass summed in a
+    fixed tree, deterministic, no atomics — the environment's diffuse term without the all-pairs prefilter.  Differentiable with
+    respect to cube: the backward is one cube_sh_grad call, bit-reproducible.  ctx_or_fs: the Context, or a FrameSet of it.
+    stream: a raw stream handle, None = torch's current stream."""
+    return _CubeSh.apply(cube, getattr(ctx_or_fs, "ctx", ctx_or_fs), stream)
+
+
+_SH_KINDS = {"irradiance": abi.SH_IRRADIANCE, "radiance": abi.SH_RADIANCE}
+
+
+def _sh_args(fs, sh, nrm, kind):
+    """→ (sh, nrm, n_ch, sh_frames, kind), checked and contiguous"""
+    nrm = _plane(fs, nrm, 3, "sh_light: nrm")
+    sh_frames = _lead_frames(fs, sh, (2, 3), "sh_light: sh", "a CUDA float32 tensor [9, C] or [n_frames, 9, C]", lambda t: t.shape[-2] == 9)
+    return sh.contiguous(), nrm, sh.shape[-1], sh_frames, _SH_KINDS.get(kind, len(_SH_KINDS))  # (an unknown kind is the library's to refuse)
+
+
+def sh_light_grad(fs, vis, sh, nrm, gout, kind="irradiance", want_gsh=True, want_gnrm=True, stream=None):
+    """the backward of sh_light by one FrameSet.sh_grad call: gout [n_frames, C, rows, W] → (gsh, gnrm), each None when not wanted
+    (not both: the library refuses that): gnrm is deterministic, zeros where nobody owns the pixel or its normal is not lit; gsh has sh's shape, reduced in a
+    fixed tree (bit-reproducible for a shard layout).  stream: a raw stream handle, None = torch's current stream."""
+    sh, nrm, n_ch, sh_frames, k = _sh_args(fs, sh, nrm, kind)
+    gout = _gout(fs, gout, n_ch, "sh_light_grad")
+    gnrm = torch.empty_like(nrm) if want_gnrm else None
+    work_bytes = fs.sh_work_bytes(n_ch) if want_gsh else 0
+    gsh, work = _reduced(sh, work_bytes) if want_gsh else (None, None)
+    fs.sh_grad(_vis_ptr(fs, vis, "sh_light_grad"), nrm.data_ptr(), sh.data_ptr(), n_ch, sh_frames, k, gout.data_ptr(), _ptr(gnrm), _ptr(gsh),
+               _ptr(work), work_bytes, abi.FUSED_CLEAR, _stream_ptr(stream))
+    return gsh, gnrm
+
+
+class _ShLight(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sh, nrm, fs, vis, kind, stream):
+        sh, nrm, n_ch, sh_frames, k = _sh_args(fs, sh, nrm, kind)
+        out = torch.empty(fs.interpolate_shape(n_ch), dtype=torch.float32, device=nrm.device)
+        fs.sh(_vis_ptr(fs, vis, "sh_light"), nrm.data_ptr(), sh.data_ptr(), n_ch, sh_frames, k, out.data_ptr(), fs.interpolate_bytes(n_ch),
+              abi.FUSED_CLEAR, _stream_ptr(stream))
+        ctx.fs, ctx.vis, ctx.kind, ctx.stream = fs, vis, kind, stream
+        ctx.save_for_backward(sh, nrm)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        sh, nrm = ctx.saved_tensors
+        return _backward(ctx, 2, lambda *need: sh_light_grad(ctx.fs, ctx.vis, sh, nrm, gout, ctx.kind, *need, ctx.stream))
+
+
+def sh_light(fs, vis, sh, nrm, kind="irradiance", stream=None):
+    """nine order-2 spherical-harmonic coefficients per channel evaluated at each pixel's normal under a visibility buffer `vis` of
+    FrameSet `fs`: sh is [9, C] (every frame shares it) or [n_frames, 9, C] CUDA float32, C <= abi.SH_MAX_CH — cube_sh's output, a
+    captured probe, or a learned parameter —, nrm [n_frames, 3, rows, W] of any length → [n_frames, C, rows, W] float32, unclamped:
+    kind "irradiance", the cosine-convolved environment over pi, a drop-in for texture_cube(cube_irradiance(env, m), nrm) as ibl's
+    `irr`; kind "radiance", the function itself.  Zeros where nobody owns the pixel or its normal has no finite positive length
+    (FrameSet.sh; include/srz.h states the rule).  Differentiable with respect to sh (sums over the pixels in a fixed tree:
+    bit-reproducible) and nrm (deterministic planes), not to kind.  Backward is one sh_light_grad call that asks only for the
+    outputs some input needs.  stream: a raw stream handle, None = torch's current stream."""
+    return _ShLight.apply(sh, nrm, fs, vis, kind, stream)
+
+
 class _CubePrefilterPyramid(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cube, c, roughness, cmin, stream):
