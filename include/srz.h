@@ -89,6 +89,8 @@ extern "C" {
  *      (additive, same version) SH9 lighting: a cube projected to nine spherical-harmonic coefficients per channel, and those
  *      evaluated at each pixel's normal, with gradients srz_cube_sh / srz_cube_sh_grad / srz_cube_sh_work_bytes / srz_frameset_sh /
  *      srz_frameset_sh_grad / srz_frameset_sh_work_bytes, SRZ_SH_MAX_CH, SRZ_SH_IRRADIANCE, SRZ_SH_RADIANCE
+ *      (additive, same version) the mesh Laplacian over a slot's connectivity: umbrella, graph and cotangent, with gradients
+ *      srz_mesh_laplacian / srz_mesh_laplacian_grad, SRZ_LAP_UMBRELLA, SRZ_LAP_GRAPH, SRZ_LAP_COTAN
  */
 #define SRZ_ABI_VERSION 7
 
@@ -348,6 +350,55 @@ int srz_mesh_tangents(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t po
  * d_gpos overlapping the positions', the uv's or d_gtan's span, or each other. */
 int srz_mesh_tangents_grad(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, const float *d_uv,
                            uint32_t uv_stride, const float *d_gtan, uint32_t gtan_stride, float *d_work, float *d_gpos, void *stream);
+/* THE MESH LAPLACIAN over a slot's connectivity, ON THE DEVICE: one linear operator in three kinds over per-vertex fields of 1 to 64
+ * channels — the regulariser of the mesh side (a penalty on positions or on a learned attribute, or the operator of a solve
+ * (I + lambda L) u = b).  d_x: n_sets fields of n_verts vertices, vertex v of set s at float (s * n_verts + v) * x_stride, n_ch floats
+ * read there, x_stride >= n_ch; d_out laid out the same way with out_stride >= n_ch, n_ch floats written per vertex, the other floats
+ * of a strided record are not touched.  n_ch is 1 .. 64, n_sets 1 .. 65535.  A null d_x selects the slot's own positions (stride 8;
+ * n_ch must be 3 and n_sets 1).  d_wpos: ONE position set shared by the sets, vertex v at float v * wpos_stride, wpos_stride >= 3;
+ * only COTAN reads it, and there null selects the slot's own positions.  d_out is never null. */
+#define SRZ_LAP_UMBRELLA 0   /* x[v] - mean of the neighbours: not symmetric */
+#define SRZ_LAP_GRAPH    1   /* n x[v] - sum of the neighbours: symmetric, positive semidefinite */
+#define SRZ_LAP_COTAN    2   /* cotangent weights from a position set held fixed: symmetric */
+/* THE RULE, in float32, nothing fused, in this order; dot3 and cross are srz_mesh_normals'.  The channels j are independent and
+ * follow the same order of operations.  Per set and vertex v: list(v) is the slot's corner list of v, in list order
+ * (srz_mesh_upload); per corner c:  f = c / 3;  k = c % 3;  (i0, i1, i2) = faces[f];  a = i[(k + 1) % 3];  b = i[(k + 2) % 3];
+ * n_v = (float)(2 * |list(v)|).
+ *   UMBRELLA:  S = +0;  for c in list(v):  S = S + (x[a] + x[b]);   n_v > 0:  out[v] = x[v] - S / n_v;   otherwise out[v] = +0
+ *     (a neighbour counts once per face it shares with v: twice across an interior edge, once on a boundary edge; on a closed
+ *     manifold mesh this is the uniform Laplacian)
+ *   GRAPH:     S as above;   out[v] = n_v * x[v] - S
+ *   COTAN:     with p = wpos, in the face's OWN vertex order whichever corner asks:
+ *                N = cross(p[i1] - p[i0], p[i2] - p[i0]);  d2 = dot3(N, N);  ok = d2 > 0 && d2 <= FLT_MAX;  ia = 1.0f / sqrtf(d2)
+ *                cot_m = dot3(p[i_(m+1)] - p[i_m], p[i_(m+2)] - p[i_m]) * ia        (m = 0, 1, 2, indices mod 3)
+ *              acc = +0;  for c in list(v) whose face is ok:  acc = acc + (cot_b * (x[v] - x[a]) + cot_a * (x[v] - x[b]))
+ *                (cot_a, cot_b: the face's cotangents at a and at b);   out[v] = 0.5f * acc
+ *              A face that is not ok is SKIPPED, never multiplied by zero: a non-finite x behind it reaches nothing.  The weight of
+ *              edge (v, a) in face f is the same word from v's side and from a's side: the matrix is symmetric in the bits.
+ * A GATHER — the one thread that owns (s, v) and a chunk of channels stores its floats once — with plain stores and no atomics:
+ * DETERMINISTIC, bit for bit.  Non-finite values propagate as IEEE has them, to the vertex itself and to its neighbours only.  No
+ * input value makes the pass read or write outside its buffers.  Asynchronous on `stream` (NULL: the ctx's own stream,
+ * SRZ_STREAM_NULL: HIP's null stream), as the other mesh passes are.
+ * SRZ_E_INVALID, nothing written and nothing launched, for: everything srz_mesh_normals refuses of ctx, mesh_id and n_sets; n_ch of 0
+ * or above 64; a stride of a non-null buffer below n_ch, or a wpos_stride below 3 (of a non-null d_wpos, whichever kind); an unknown
+ * kind; a null d_x with n_ch != 3 or n_sets != 1; a null d_out; a pointer that is not 4-byte aligned; an output whose span (first to
+ * last float reached) overlaps the input's span, or overlaps wpos' span when COTAN reads it.  There is NO in-place record form: the
+ * pass reads its neighbours' inputs, so running it in place is a race. */
+int srz_mesh_laplacian(srz_ctx *ctx, int mesh_id, const float *d_x, uint32_t x_stride, uint32_t n_ch, uint32_t n_sets, int kind,
+                       const float *d_wpos, uint32_t wpos_stride, float *d_out, uint32_t out_stride, void *stream);
+/* THE BACKWARD of srz_mesh_laplacian: THE EXACT TRANSPOSE, also a gather; it needs neither x nor a workspace.  d_gout: the gradient
+ * with respect to the output, laid out like d_out with gout_stride >= n_ch; d_gx: the gradient with respect to x, laid out the same
+ * way with gx_stride >= n_ch, EVERY element (n_ch floats per vertex) written.  kind, d_wpos, wpos_stride: the forward call's.
+ *   GRAPH, COTAN:  the matrix is symmetric: srz_mesh_laplacian_grad IS the forward rule applied to gout — the same kernel, the same
+ *     bits as srz_mesh_laplacian over the same data.
+ *   UMBRELLA:  T = +0;  for c in list(v):  T = T + (gout[a] / n_a + gout[b] / n_b);   gx[v] = (n_v > 0 ? gout[v] : +0) - T
+ *     (n_u = (float)(2 * |list(u)|), read from the corner lists; a vertex that a face names has n_u >= 2)
+ * Plain stores, no atomics: DETERMINISTIC, bit for bit.  Non-finite values propagate as IEEE has them, to the vertex itself and to
+ * its neighbours only.  No input value makes the pass read or write outside its buffers.  Asynchronous on `stream`.
+ * SRZ_E_INVALID, nothing written and nothing launched, for what srz_mesh_laplacian refuses (d_gout in d_x's place, d_gx in d_out's)
+ * and for a null d_gout: the backward has no null form. */
+int srz_mesh_laplacian_grad(srz_ctx *ctx, int mesh_id, const float *d_gout, uint32_t gout_stride, uint32_t n_ch, uint32_t n_sets, int kind,
+                            const float *d_wpos, uint32_t wpos_stride, float *d_gx, uint32_t gx_stride, void *stream);
 
 /* ---- draw = TraditionalRasterizer::draw(TRIANGLES) for one scene ----------------------
  * z/c0/c1/c2: W*H floats each, in/out (m_zBuffer, m_channels[0..2]); draw never clears unless

@@ -1517,6 +1517,52 @@ int srz_mesh_tangents_grad(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32
   return SRZ_OK;
 }
 
+// srz_mesh_laplacian and srz_mesh_laplacian_grad: one set of checks and one launch — the backward is the operator's transpose over
+// d_gout, laid out like the forward's d_x (only the forward has the null form: the slot's own positions).
+static int mesh_laplacian(srz_ctx *ctx, const std::string &fn, bool grad, int mesh_id, const float *d_x, uint32_t x_stride, uint32_t n_ch,
+                          uint32_t n_sets, int kind, const float *d_wpos, uint32_t wpos_stride, float *d_out, uint32_t out_stride, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  if (mesh_id < 0 || mesh_id >= MAX_MESH || !ctx->mesh[mesh_id].d_verts) return fail(ctx, SRZ_E_INVALID, fn + ": no mesh in that slot");
+  const srz_ctx::MeshSlot &m = ctx->mesh[mesh_id];
+  if (n_sets == 0u || n_sets > 65535u) return fail(ctx, SRZ_E_INVALID, fn + ": n_sets must be 1 .. 65535");
+  if (n_ch == 0u || n_ch > 64u) return fail(ctx, SRZ_E_INVALID, fn + ": n_ch must be 1 .. 64");
+  if (kind != SRZ_LAP_UMBRELLA && kind != SRZ_LAP_GRAPH && kind != SRZ_LAP_COTAN) return fail(ctx, SRZ_E_INVALID, fn + ": unknown kind");
+  if (!d_x && grad) return fail(ctx, SRZ_E_INVALID, fn + ": null d_gout");
+  if (!d_x && (n_ch != 3u || n_sets != 1u))
+    return fail(ctx, SRZ_E_INVALID, fn + ": the slot's own positions are one set of three channels (n_ch must be 3, n_sets 1)");
+  if (!d_out) return fail(ctx, SRZ_E_INVALID, fn + ": null output");
+  if ((d_x && x_stride < n_ch) || out_stride < n_ch) return fail(ctx, SRZ_E_INVALID, fn + ": a stride is below n_ch");
+  if (d_wpos && wpos_stride < 3u) return fail(ctx, SRZ_E_INVALID, fn + ": wpos_stride must be at least 3");
+  if (!aligned<4>({d_x, d_wpos, d_out})) return fail(ctx, SRZ_E_INVALID, fn + ": the buffers must be 4-byte aligned");
+  MeshLaplacianArgs a{};
+  const float *own = reinterpret_cast<const float *>(m.d_verts);
+  a.x = d_x ? d_x : own, a.x_stride = d_x ? x_stride : 8u;
+  a.wpos = d_wpos ? d_wpos : own, a.wpos_stride = d_wpos ? wpos_stride : 8u;
+  a.faces = m.d_faces, a.corner_off = m.d_corner_off, a.corners = m.d_corner_off + m.n_verts + 1;
+  a.out = d_out, a.out_stride = out_stride, a.n_ch = n_ch, a.n_verts = m.n_verts, a.n_sets = n_sets;
+  const size_t last = (size_t)n_sets * m.n_verts - 1u;
+  const Range x_span{a.x, (last * a.x_stride + n_ch) * sizeof(float)}, out_span{d_out, (last * out_stride + n_ch) * sizeof(float)};
+  const Range wpos_span{a.wpos, (((size_t)m.n_verts - 1u) * a.wpos_stride + 3u) * sizeof(float)};
+  // (no in-place record form: the pass reads its neighbours' inputs, so an output inside the input's span is a race)
+  if (ranges_overlap(out_span, x_span)) return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the input");
+  if (kind == SRZ_LAP_COTAN && ranges_overlap(out_span, wpos_span)) return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the weight positions");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  launch_mesh_laplacian(a, kind, grad, pick_stream(ctx, stream));
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
+int srz_mesh_laplacian(srz_ctx *ctx, int mesh_id, const float *d_x, uint32_t x_stride, uint32_t n_ch, uint32_t n_sets, int kind,
+                       const float *d_wpos, uint32_t wpos_stride, float *d_out, uint32_t out_stride, void *stream) {
+  return mesh_laplacian(ctx, "srz_mesh_laplacian", false, mesh_id, d_x, x_stride, n_ch, n_sets, kind, d_wpos, wpos_stride, d_out, out_stride, stream);
+}
+
+int srz_mesh_laplacian_grad(srz_ctx *ctx, int mesh_id, const float *d_gout, uint32_t gout_stride, uint32_t n_ch, uint32_t n_sets, int kind,
+                            const float *d_wpos, uint32_t wpos_stride, float *d_gx, uint32_t gx_stride, void *stream) {
+  return mesh_laplacian(ctx, "srz_mesh_laplacian_grad", true, mesh_id, d_gout, gout_stride, n_ch, n_sets, kind, d_wpos, wpos_stride, d_gx, gx_stride,
+                        stream);
+}
+
 // A sceneset's frames as srz_frames whose batches carry sizes only (k_vertex makes the triangles): fr[f], its batches in `batches`.
 // Every draw names an uploaded mesh (the callers have checked).
 static void scene_frames(const srz_ctx *ctx, const srz_scene_frame *frames, int n_frames, std::vector<srz_frame> &fr, std::vector<srz_batch> &batches) {

@@ -263,6 +263,22 @@ struct MeshTangentsArgs {
 };
 void launch_mesh_tangents(const MeshTangentsArgs &a, hipStream_t s);
 void launch_mesh_tangents_grad(const MeshTangentsArgs &a, hipStream_t s);
+// srz_mesh_laplacian / srz_mesh_laplacian_grad: the mesh Laplacian of ONE mesh slot's connectivity over n_sets per-vertex fields of
+// n_ch channels (k_mesh_laplacian: a thread owns (set, vertex, chunk of channels) and walks the vertex's corner list).  Vertex v of
+// set s starts at float (s * n_verts + v) * stride of x / out; wpos (COTAN only) is ONE position set, vertex v at float
+// v * wpos_stride.  The backward is the same launch over gout: `transpose` picks UMBRELLA's transposed rule, the other two kinds are
+// symmetric.  The host has checked the strides, the spans, n_ch 1 .. 64 and n_sets <= 65535 (the grid's y)
+struct MeshLaplacianArgs {
+  const float *x;              // the field (the backward: gout)
+  const float *wpos;           // COTAN: the positions the weights are made from (the slot's own records or the caller's)
+  const uint32_t *faces;       // [n_faces][3]
+  const uint32_t *corner_off;  // [n_verts + 1] into corners
+  const uint32_t *corners;     // [3 * n_faces]
+  float *out;                  // the output (the backward: gx)
+  uint32_t x_stride, wpos_stride, out_stride, n_ch;
+  uint32_t n_verts, n_sets;
+};
+void launch_mesh_laplacian(const MeshLaplacianArgs &a, int kind, bool transpose, hipStream_t s);
 // srz_sceneset_corner_attr / _corner_attr_grad: per-vertex attributes of ONE mesh slot to the set's triangle stream
 // [frame][pos_tris][3][n_ch], and the stream's gradient back to [frame][n_verts][n_ch] (k_corner_attr, k_corner_attr_grad: a thread
 // owns (frame, vertex, channel) and walks the frame's draws of the slot and the vertex's corner list).  A draw takes part when its

@@ -813,6 +813,83 @@ template <int PHASE> __global__ __launch_bounds__(256) void k_mesh_tangents_grad
 }
 
 // ================================================================================================================
+// k_mesh_laplacian — srz_mesh_laplacian and srz_mesh_laplacian_grad (include/srz.h states the rules): k_mesh_normals' shape — a
+// thread OWNS (set, vertex) and walks the vertex's corner list, a gather, no atomics, no barrier, no LDS, plain stores,
+// bit-reproducible.  Grid (blocks of 256 vertices, sets, chunks of LAP_CHUNK channels): the thread keeps its chunk's sums in
+// registers; a COTAN thread recomputes the face's weights for its chunk (nine position loads the sixteen chunks of a 64-channel
+// field share through the cache; no workspace, no second launch).  MODE 0 .. 2 are the kinds; MODE 3 is UMBRELLA's transpose —
+// GRAPH and COTAN are symmetric, their backward is the forward kernel over gout.  corner_off, corners and faces are indexed per
+// lane (nothing is wave-uniform: vector loads, as k_mesh_normals has them; neighbouring vertices share faces, so they hit L2).
+// ================================================================================================================
+constexpr uint32_t LAP_CHUNK = 4;
+constexpr int LAP_UMBRELLA_T = 3;
+struct LapV {
+  float c[LAP_CHUNK];
+};
+// the chunk's channels of one record (the channels behind n are not read: +0)
+__device__ __forceinline__ LapV lap_ld(const float *p, uint32_t n) {
+  LapV r;
+#pragma unroll
+  for (uint32_t j = 0; j < LAP_CHUNK; ++j) r.c[j] = j < n ? p[j] : 0.0f;
+  return r;
+}
+template <int MODE> __global__ __launch_bounds__(256) void k_mesh_laplacian(const MeshLaplacianArgs a) {
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x, set = blockIdx.y, ch0 = blockIdx.z * LAP_CHUNK;
+  if (v >= a.n_verts) return;
+  const uint32_t n = a.n_ch - ch0 < LAP_CHUNK ? a.n_ch - ch0 : LAP_CHUNK; // (the host: gridDim.z = ceil(n_ch / LAP_CHUNK), so >= 1)
+  const float *x = a.x + (size_t)set * a.n_verts * a.x_stride + ch0;
+  const uint32_t c_begin = a.corner_off[v], c_end = a.corner_off[v + 1];
+  const float n_v = (float)(2u * (c_end - c_begin));
+  const LapV xv = lap_ld(x + (size_t)v * a.x_stride, n);
+  LapV S;
+#pragma unroll
+  for (uint32_t j = 0; j < LAP_CHUNK; ++j) S.c[j] = 0.0f;
+  for (uint32_t c = c_begin; c < c_end; ++c) {
+    const uint32_t corner = a.corners[c], face = corner / 3u, k = corner - 3u * face;
+    const uint32_t *f = a.faces + (size_t)face * 3;
+    const uint32_t i0 = f[0], i1 = f[1], i2 = f[2];
+    const uint32_t ia = k == 0u ? i1 : k == 1u ? i2 : i0, ib = k == 0u ? i2 : k == 1u ? i0 : i1;
+    if (MODE == SRZ_LAP_COTAN) {
+      const F3 p0 = ldv3(a.wpos + (size_t)i0 * a.wpos_stride), p1 = ldv3(a.wpos + (size_t)i1 * a.wpos_stride),
+               p2 = ldv3(a.wpos + (size_t)i2 * a.wpos_stride);
+      const F3 e01 = sub3(p1, p0), e02 = sub3(p2, p0);
+      const F3 N = cross3(e01, e02);
+      const float d2 = dot3(N.x, N.y, N.z, N.x, N.y, N.z);
+      if (!(d2 > 0.0f && d2 <= __FLT_MAX__)) continue; // (SKIPPED, never multiplied by zero: no x behind the face is read)
+      const float inv = 1.0f / __builtin_sqrtf(d2);
+      // cot_m = dot3(p[i_(m+1)] - p[i_m], p[i_(m+2)] - p[i_m]) * inv, in the face's own order
+      const F3 e12 = sub3(p2, p1), e10 = sub3(p0, p1), e20 = sub3(p0, p2), e21 = sub3(p1, p2);
+      const float cot0 = dot3(e01.x, e01.y, e01.z, e02.x, e02.y, e02.z) * inv, cot1 = dot3(e12.x, e12.y, e12.z, e10.x, e10.y, e10.z) * inv,
+                  cot2 = dot3(e20.x, e20.y, e20.z, e21.x, e21.y, e21.z) * inv;
+      const float cot_a = k == 0u ? cot1 : k == 1u ? cot2 : cot0, cot_b = k == 0u ? cot2 : k == 1u ? cot0 : cot1;
+      const LapV xa = lap_ld(x + (size_t)ia * a.x_stride, n), xb = lap_ld(x + (size_t)ib * a.x_stride, n);
+#pragma unroll
+      for (uint32_t j = 0; j < LAP_CHUNK; ++j) S.c[j] = S.c[j] + (cot_b * (xv.c[j] - xa.c[j]) + cot_a * (xv.c[j] - xb.c[j]));
+    } else {
+      const LapV xa = lap_ld(x + (size_t)ia * a.x_stride, n), xb = lap_ld(x + (size_t)ib * a.x_stride, n);
+      if (MODE == LAP_UMBRELLA_T) {
+        const float n_a = (float)(2u * (a.corner_off[ia + 1] - a.corner_off[ia])), n_b = (float)(2u * (a.corner_off[ib + 1] - a.corner_off[ib]));
+#pragma unroll
+        for (uint32_t j = 0; j < LAP_CHUNK; ++j) S.c[j] = S.c[j] + (xa.c[j] / n_a + xb.c[j] / n_b);
+      } else {
+#pragma unroll
+        for (uint32_t j = 0; j < LAP_CHUNK; ++j) S.c[j] = S.c[j] + (xa.c[j] + xb.c[j]);
+      }
+    }
+  }
+  float *o = a.out + ((size_t)set * a.n_verts + v) * a.out_stride + ch0;
+#pragma unroll
+  for (uint32_t j = 0; j < LAP_CHUNK; ++j) {
+    float r;
+    if (MODE == SRZ_LAP_UMBRELLA) r = n_v > 0.0f ? xv.c[j] - S.c[j] / n_v : 0.0f;
+    else if (MODE == SRZ_LAP_GRAPH) r = n_v * xv.c[j] - S.c[j];
+    else if (MODE == SRZ_LAP_COTAN) r = 0.5f * S.c[j];
+    else r = (n_v > 0.0f ? xv.c[j] : 0.0f) - S.c[j];
+    if (j < n) o[j] = r;
+  }
+}
+
+// ================================================================================================================
 // k_corner_attr / k_corner_attr_grad — srz_sceneset_corner_attr and its backward (include/srz.h).  Grid (blocks of 256 (vertex,
 // channel) pairs, frames); a thread OWNS (frame, vertex, channel): neighbouring lanes are neighbouring channels of one vertex, so
 // the attribute row, the rows of the triangle stream and the gradient row are each read and written as runs, and the backward
@@ -8864,6 +8941,15 @@ void launch_mesh_normals_grad(const MeshNormalsArgs &a, hipStream_t s) {
 void launch_mesh_tangents(const MeshTangentsArgs &a, hipStream_t s) {
   if (a.n_sets == 0 || a.n_verts == 0) return;
   hipLaunchKernelGGL(k_mesh_tangents, dim3((a.n_verts + 255) / 256, a.n_sets), dim3(256), 0, s, a);
+}
+
+void launch_mesh_laplacian(const MeshLaplacianArgs &a, int kind, bool transpose, hipStream_t s) {
+  if (a.n_verts == 0u) return;
+  const dim3 grid((a.n_verts + 255) / 256, a.n_sets, (a.n_ch + LAP_CHUNK - 1) / LAP_CHUNK);
+  if (kind == SRZ_LAP_COTAN) hipLaunchKernelGGL(k_mesh_laplacian<SRZ_LAP_COTAN>, grid, dim3(256), 0, s, a);
+  else if (kind == SRZ_LAP_GRAPH) hipLaunchKernelGGL(k_mesh_laplacian<SRZ_LAP_GRAPH>, grid, dim3(256), 0, s, a);
+  else if (transpose) hipLaunchKernelGGL(k_mesh_laplacian<LAP_UMBRELLA_T>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_mesh_laplacian<SRZ_LAP_UMBRELLA>, grid, dim3(256), 0, s, a);
 }
 
 void launch_mesh_tangents_grad(const MeshTangentsArgs &a, hipStream_t s) {

@@ -43,6 +43,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_reflect", "srz_frameset_reflect_grad", "srz_brdf_table", "srz_frameset_ibl", "srz_frameset_ibl_grad",
            "srz_frameset_shadow", "srz_frameset_shadow_grad",
            "srz_mesh_tangents", "srz_mesh_tangents_grad", "srz_frameset_normal_map", "srz_frameset_normal_map_grad",
+           "srz_mesh_laplacian", "srz_mesh_laplacian_grad",
            "srz_frameset_composite", "srz_frameset_composite_grad",
            "srz_frameset_texture_set", "srz_frameset_texture_set_grad",
            "srz_frameset_perspective", "srz_frameset_perspective_grad", "srz_frameset_interpolate_deriv_persp",
@@ -166,6 +167,7 @@ def lib():
         L.srz_frameset_ibl_grad.argtypes = abi.IBL_GRAD_ARGTYPES
         L.srz_mesh_tangents.argtypes = abi.MESH_TANGENTS_ARGTYPES
         L.srz_mesh_tangents_grad.argtypes = abi.MESH_TANGENTS_GRAD_ARGTYPES
+        L.srz_mesh_laplacian.argtypes = L.srz_mesh_laplacian_grad.argtypes = abi.MESH_LAPLACIAN_ARGTYPES
         L.srz_frameset_normal_map.argtypes = abi.NORMAL_MAP_ARGTYPES
         L.srz_frameset_normal_map_grad.argtypes = abi.NORMAL_MAP_GRAD_ARGTYPES
         L.srz_frameset_composite.argtypes = abi.COMPOSITE_ARGTYPES
@@ -1097,6 +1099,24 @@ class Context:
         self._check(lib().srz_mesh_tangents_grad(self.h, mesh_id, C.c_void_p(d_pos_ptr or None), pos_stride, n_sets, C.c_void_p(d_uv_ptr or None),
                                                  uv_stride, C.c_void_p(d_gtan_ptr or None), gtan_stride, C.c_void_p(d_work_ptr or None),
                                                  C.c_void_p(d_gpos_ptr or None), _stream(stream)))
+
+    def mesh_laplacian(self, mesh_id, d_x_ptr, x_stride, n_ch, n_sets, kind, d_wpos_ptr, wpos_stride, d_out_ptr, out_stride, stream=None):
+        """the mesh Laplacian (kind: abi.LAP_UMBRELLA / LAP_GRAPH / LAP_COTAN) of slot mesh_id's connectivity over n_sets per-vertex
+        fields of n_ch (1 .. 64) channels on the device: vertex v of set s at float (s * n_verts + v) * stride of d_x / d_out (strides
+        >= n_ch).  d_x_ptr None / 0: the slot's own positions (n_ch 3, n_sets 1).  d_wpos_ptr: ONE position set (wpos_stride >= 3)
+        COTAN makes its weights from, None / 0: the slot's own.  A gather, deterministic (include/srz.h states the rule).
+        Asynchronous."""
+        self._check(lib().srz_mesh_laplacian(self.h, mesh_id, C.c_void_p(d_x_ptr or None), x_stride, n_ch, n_sets, kind,
+                                             C.c_void_p(d_wpos_ptr or None), wpos_stride, C.c_void_p(d_out_ptr or None), out_stride, _stream(stream)))
+
+    def mesh_laplacian_grad(self, mesh_id, d_gout_ptr, gout_stride, n_ch, n_sets, kind, d_wpos_ptr, wpos_stride, d_gx_ptr, gx_stride,
+                            stream=None):
+        """the backward of mesh_laplacian, its exact transpose: d_gout (laid out like the output) → d_gx (laid out like x), every
+        element written.  GRAPH and COTAN are symmetric: the forward's kernel and bits over d_gout.  A gather, deterministic, no
+        workspace.  Asynchronous."""
+        self._check(lib().srz_mesh_laplacian_grad(self.h, mesh_id, C.c_void_p(d_gout_ptr or None), gout_stride, n_ch, n_sets, kind,
+                                                  C.c_void_p(d_wpos_ptr or None), wpos_stride, C.c_void_p(d_gx_ptr or None), gx_stride,
+                                                  _stream(stream)))
 
     def draw(self, frame, planes=None, primitive=abi.PRIMITIVE_TRIANGLES, want_stats=False):
         """TraditionalRasterizer::draw for one scene; planes (z,c0,c1,c2) are modified in place."""

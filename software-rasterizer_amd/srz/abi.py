@@ -79,6 +79,10 @@ MESH_TANGENTS_ARGTYPES = [_vp, C.c_int, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _
 MESH_TANGENTS_GRAD_ARGTYPES = [_vp, C.c_int, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp]
 NORMAL_MAP_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _u32, _vp]
 NORMAL_MAP_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]
+# srz_mesh_laplacian / _laplacian_grad: `kind` (SRZ_LAP_*), the most channels of one call, and the prototype the two share
+LAP_UMBRELLA, LAP_GRAPH, LAP_COTAN = 0, 1, 2
+LAP_MAX_CH = 64
+MESH_LAPLACIAN_ARGTYPES = [_vp, C.c_int, _vp, _u32, _u32, _u32, C.c_int, _vp, _u32, _vp, _u32, _vp]
 # the prototypes of srz_frameset_shadow / _shadow_grad (argtypes; both return int), set by srz.lib()
 SHADOW_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, C.c_float, C.c_float, _vp, C.c_size_t, _u32, _vp]
 SHADOW_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, C.c_float, C.c_float, _vp, _vp, _u32, _vp]

@@ -8,6 +8,7 @@
 
 Any per-vertex attribute a of the owner interpolates as alpha * a0 + beta * a1 + gamma * a2.
 """
+import contextlib
 import math
 from collections import namedtuple
 
@@ -1906,12 +1907,19 @@ def scene_positions(fs, meshes, mvp=None, zmap=None, pos_tris=None, stream=None)
 
 
 # ------------------------------------------------------------------------------------------------ normals and per-vertex attributes
-def _sets_arg(ctx, slot, t, name):
-    """a CUDA float32 [V, 3] or [B, V, 3] tensor for mesh slot `slot` -> (the tensor detached and contiguous, number of sets)"""
+def _sets_arg(ctx, slot, t, name, who="mesh_normals", channels=3, batched=True):
+    """a CUDA float32 per-vertex tensor for mesh slot `slot`, [V, C] or (batched) [B, V, C] with B <= 65535 -> (the tensor detached
+    and contiguous, number of sets).  channels: the C asked for (3: positions, the default), None = a field of 1 .. abi.LAP_MAX_CH
+    channels; batched False: [V, C] only (one set shared by the sets, as wpos is); who: the function the refusal names.  The ONE
+    refusal of the mesh passes' tensors: its text says the form that was asked for"""
     V = ctx.mesh_sizes[slot][0]
-    if t is None or t.dtype != torch.float32 or not t.is_cuda or t.dim() not in (2, 3) or tuple(t.shape[-2:]) != (V, 3) or \
-            (t.dim() == 3 and not 1 <= t.shape[0] <= 65535):
-        raise ValueError(f"mesh_normals: {name} must be a CUDA float32 tensor [{V}, 3] or [B, {V}, 3] (B <= 65535)" + _got(t, "plain"))
+    ok = t is not None and t.dtype == torch.float32 and t.is_cuda and t.dim() in ((2, 3) if batched else (2,))
+    ok = ok and t.shape[-2] == V and (t.shape[-1] == channels if channels else 1 <= t.shape[-1] <= abi.LAP_MAX_CH)
+    ok = ok and (t.dim() == 2 or 1 <= t.shape[0] <= 65535)
+    if not ok:
+        C_, cap = (channels, "") if channels else ("C", f"C 1 .. {abi.LAP_MAX_CH}, ")
+        form = f"[{V}, {C_}] or [B, {V}, {C_}] ({cap}B <= 65535)" if batched else f"[{V}, {C_}]"
+        raise ValueError(f"{who}: {name} must be a CUDA float32 tensor {form}" + _got(t, "plain"))
     return t.detach().contiguous(), (t.shape[0] if t.dim() == 3 else 1)
 
 
@@ -1980,6 +1988,115 @@ def mesh_tangents(ctx, slot, pos, uv=None, stream=None):
     interpolate(fs, vis, corner_attr(fs, {slot: mesh_tangents(ctx, slot, verts)})) is normal_map's tan.  stream: a raw stream handle,
     None = torch's current stream."""
     return _MeshTangents.apply(pos, ctx, slot, uv, stream)
+
+
+_LAP_KINDS = {"umbrella": abi.LAP_UMBRELLA, "graph": abi.LAP_GRAPH, "cotan": abi.LAP_COTAN}
+
+
+def _lap_args(ctx, slot, x, name, kind, wpos, who):
+    """the arguments of mesh_laplacian and mesh_solve, all through _sets_arg -> (the field detached and contiguous, number of sets,
+    channels, SRZ_LAP_* of the kind's name — -1 for a name that is none: the library's to refuse —, wpos detached and contiguous or
+    None)"""
+    t, n_sets = _sets_arg(ctx, slot, x, name, who, None)
+    if wpos is not None:
+        wpos, _ = _sets_arg(ctx, slot, wpos, "wpos", who, 3, False)
+    return t, n_sets, t.shape[-1], _LAP_KINDS.get(kind, -1) if isinstance(kind, str) else -1, wpos
+
+
+def _lap_call(call, slot, t, n_sets, n_ch, kind, wpos, stream):
+    """one plain call (Context.mesh_laplacian or its _grad) over the packed field t -> a new tensor of t's shape"""
+    out = torch.empty_like(t)
+    call(slot, t.data_ptr(), n_ch, n_ch, n_sets, kind, _ptr(wpos), 3, out.data_ptr(), n_ch, _stream_ptr(stream))
+    return out
+
+
+class _MeshLaplacian(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, sctx, slot, kind, wpos, stream):
+        t, n_sets, n_ch, k, wpos = _lap_args(sctx, slot, x, "x", kind, wpos, "mesh_laplacian")
+        ctx.sctx, ctx.slot, ctx.kind, ctx.wpos, ctx.stream, ctx.dims = sctx, slot, k, wpos, stream, (n_sets, n_ch)
+        return _lap_call(sctx.mesh_laplacian, slot, t, n_sets, n_ch, k, wpos, stream)
+
+    @staticmethod
+    def backward(ctx, gout):
+        gx = _lap_call(ctx.sctx.mesh_laplacian_grad, ctx.slot, gout.contiguous(), *ctx.dims, ctx.kind, ctx.wpos, ctx.stream)
+        return gx, None, None, None, None, None
+
+
+def mesh_laplacian(ctx, slot, x, kind="umbrella", wpos=None, stream=None):
+    """the mesh Laplacian of mesh slot `slot` of Context `ctx` over the per-vertex field x, a CUDA float32 tensor [V, C] or [B, V, C]
+    (C 1 .. 64 channels, B fields over the slot's connectivity in one call) → the same shape.  kind: "umbrella" (x[v] minus the mean
+    of its neighbours, a neighbour counted once per face it shares with v), "graph" (n x[v] minus their sum: symmetric, positive
+    semidefinite) or "cotan" (cotangent weights made from wpos, a CUDA float32 tensor [V, 3] shared by the B fields and HELD — None
+    = the slot's own positions; a zero-area face is skipped).  Context.mesh_laplacian, include/srz.h states the rule.
+    Differentiable with respect to x only (Context.mesh_laplacian_grad, the exact transpose; wpos is held as mesh_tangents holds
+    uv).  Both directions are gathers without atomics: the values and x.grad are bit-reproducible.  The regulariser of the mesh
+    side:
+      reg   = (mesh_laplacian(ctx, slot, verts) ** 2).sum()                  # penalty
+      verts = mesh_solve(ctx, slot, u, 10.0); ... loss(verts).backward()     # u.grad is the diffused gradient
+    stream: a raw stream handle, None = torch's current stream."""
+    return _MeshLaplacian.apply(x, ctx, slot, kind, wpos, stream)
+
+
+def _cg(apply, b, iters, tol):
+    """conjugate gradients in torch ops from a zero start: `apply` is a symmetric positive definite operator on tensors of b's
+    shape (the whole tensor is ONE vector: the sums run over every element) -> u with apply(u) ~ b.  `apply` is called once per
+    iteration and nowhere else.  tol None: exactly `iters` iterations and nothing read back — a zero p . Ap (or a zero r . r)
+    gives a zero step through torch.where, never a division by zero.  tol: stops before an iteration once the recursive residual
+    |r| is at most tol |b| (one scalar read back per iteration), after `iters` at the latest."""
+    u, r = torch.zeros_like(b), b.clone()
+    p, rr = r.clone(), (r * r).sum()
+    zero, one = torch.zeros_like(rr), torch.ones_like(rr)
+    stop = None if tol is None else rr * (float(tol) * float(tol))
+
+    def ratio(num, den):
+        ok = den != 0
+        return torch.where(ok, num / torch.where(ok, den, one), zero)
+    for _ in range(iters):
+        if stop is not None and bool(rr <= stop):
+            break
+        Ap = apply(p)
+        alpha = ratio(rr, (p * Ap).sum())
+        u, r = u + alpha * p, r - alpha * Ap
+        rr_new = (r * r).sum()
+        p, rr = r + ratio(rr_new, rr) * p, rr_new
+    return u
+
+
+class _MeshSolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, b, sctx, slot, lam, kind, wpos, iters, tol, stream):
+        if kind not in ("graph", "cotan"):
+            raise NotImplementedError(f"mesh_solve: conjugate gradients need a symmetric operator: kind must be 'graph' or 'cotan', got {kind!r}")
+        t, n_sets, n_ch, k, wpos = _lap_args(sctx, slot, b, "b", kind, wpos, "mesh_solve")
+        lam, iters = float(lam), int(iters)
+        ctx.args = (sctx, slot, lam, kind, wpos, iters, tol, stream)
+        # (sctx.mesh_laplacian is looked up per application: the plain call, once per iteration.  A raw handle is made torch's
+        # current stream for the loop, so that its torch ops and the operator's launches are in ONE stream's order)
+        with contextlib.nullcontext() if stream is None else torch.cuda.stream(torch.cuda.ExternalStream(stream)):
+            return _cg(lambda p: p + lam * _lap_call(sctx.mesh_laplacian, slot, p.contiguous(), n_sets, n_ch, k, wpos, stream), t, iters, tol)
+
+    @staticmethod
+    def backward(ctx, gu):
+        return (_MeshSolve.apply(gu.contiguous(), *ctx.args),) + (None,) * 8
+
+
+def mesh_solve(ctx, slot, b, lam, kind="graph", wpos=None, iters=64, tol=None, stream=None):
+    """u with (I + lam L) u = b, L = mesh_laplacian of mesh slot `slot` in one of its two SYMMETRIC kinds ("graph", "cotan";
+    "umbrella" raises), lam >= 0; b: a CUDA float32 tensor [V, C] or [B, V, C] → the same shape.  The "large steps"
+    reparameterisation of a mesh fit: optimise u, render verts = mesh_solve(ctx, slot, u, lam), and u.grad is the image gradient
+    DIFFUSED over the surface instead of a penalty on the result:
+      reg   = (mesh_laplacian(ctx, slot, verts) ** 2).sum()                  # penalty
+      verts = mesh_solve(ctx, slot, u, 10.0); ... loss(verts).backward()     # u.grad is the diffused gradient
+    Conjugate gradients in torch ops on the device over the plain Context.mesh_laplacian call, from a zero start, the whole of b one
+    vector.  tol None: exactly `iters` iterations (as many applications of the operator) and no device-to-host read; a zero p . Ap
+    gives a zero step, never a division by zero.  tol: stops once the recursive residual is at most tol |b| (one scalar read back
+    per iteration), after `iters` at the latest.  The matrix is symmetric, so the backward is mesh_solve of the incoming gradient
+    with the same arguments; wpos (cotan: a CUDA float32 [V, 3], None = the slot's own positions) is held.  stream: a raw stream
+    handle, None = torch's current stream; the whole solve — the loop's torch ops and the operator's launches — runs on it (a handle
+    is made torch's current stream for the duration), and ordering b before it and the result after it is the caller's, as for every
+    pass."""
+    return _MeshSolve.apply(b, ctx, slot, lam, kind, wpos, iters, tol, stream)
 
 
 def refresh_normals(ctx, slot, stream=None):
