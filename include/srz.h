@@ -91,6 +91,8 @@ extern "C" {
  *      srz_frameset_sh_grad / srz_frameset_sh_work_bytes, SRZ_SH_MAX_CH, SRZ_SH_IRRADIANCE, SRZ_SH_RADIANCE
  *      (additive, same version) the mesh Laplacian over a slot's connectivity: umbrella, graph and cotangent, with gradients
  *      srz_mesh_laplacian / srz_mesh_laplacian_grad, SRZ_LAP_UMBRELLA, SRZ_LAP_GRAPH, SRZ_LAP_COTAN
+ *      (additive, same version) the mesh edge terms over a slot's connectivity: edge count, edge length and normal consistency, with
+ *      gradients srz_mesh_edges / srz_mesh_edges_grad, SRZ_EDGE_COUNT, SRZ_EDGE_LENGTH, SRZ_EDGE_DIHEDRAL
  */
 #define SRZ_ABI_VERSION 7
 
@@ -399,6 +401,69 @@ int srz_mesh_laplacian(srz_ctx *ctx, int mesh_id, const float *d_x, uint32_t x_s
  * and for a null d_gout: the backward has no null form. */
 int srz_mesh_laplacian_grad(srz_ctx *ctx, int mesh_id, const float *d_gout, uint32_t gout_stride, uint32_t n_ch, uint32_t n_sets, int kind,
                             const float *d_wpos, uint32_t wpos_stride, float *d_gx, uint32_t gx_stride, void *stream);
+/* THE MESH EDGE TERMS over a slot's connectivity, ON THE DEVICE: per (face, edge) the number of faces on the edge, the edge's length,
+ * and the normal consistency (1 - cos of the dihedral angle) with the faces across it — the two regularisers a fitting loop uses
+ * beside a Laplacian.  The slot holds no edge table: the adjacency is found from the corner lists (srz_mesh_upload).
+ * d_pos, pos_stride, n_sets: as srz_mesh_normals (a null d_pos selects the slot's own positions, stride 8, n_sets must be 1).
+ * d_out: a per-(face, edge) field, for set s and face f THREE floats at float (s * n_faces + f) * out_stride, out_stride >= 3; the
+ * other floats of a strided record are not touched.  EDGE j of a face (i0, i1, i2) lies opposite corner j: it joins
+ * a_j = i[(j + 1) % 3] and b_j = i[(j + 2) % 3]. */
+#define SRZ_EDGE_COUNT    0   /* the number of faces on the edge: 1 boundary, 2 manifold, more non-manifold */
+#define SRZ_EDGE_LENGTH   1   /* |p[b_j] - p[a_j]| */
+#define SRZ_EDGE_DIHEDRAL 2   /* the sum over the faces across the edge of 1 - dot3(unit normal of f, unit normal of g) */
+/* THE NEIGHBOURS OF (f, j), which every kind uses: a list of ENTRIES (g, j'), g a face and j' one of its edges.
+ *   w = whichever of a_j, b_j has the SHORTER corner list, a_j on a tie;  o = the other of the two
+ *   for corner c in list(w), in list order:  g = c / 3;  k = c % 3;  (g0, g1, g2) = faces[g]
+ *     g == f:                  no entry
+ *     g[(k + 1) % 3] == o:     the entry (g, (k + 2) % 3)      (o is at g's next corner; the edge opposite the remaining corner)
+ *     else g[(k + 2) % 3] == o:  the entry (g, (k + 1) % 3)    (o is at g's previous corner)
+ *     otherwise:               no entry
+ * ONE entry per corner, never two.  A face that names a vertex twice follows this rule as written.  Between two faces of three
+ * distinct vertices each the relation is mutual: (g, j') is an entry of (f, j) exactly when (f, j) is an entry of (g, j').
+ * THE RULES, in float32, nothing fused, in this order; dot3 and cross are srz_mesh_normals'.  p: the set's positions.
+ *   COUNT:     out[f][j] = (float)(1 + the number of entries).  Positions are not read; n_sets must be 1.
+ *   LENGTH:    d = p[b_j] - p[a_j];  out[f][j] = sqrtf(dot3(d, d))
+ *   DIHEDRAL:  THE UNIT NORMAL of a face (i0, i1, i2), in the face's OWN vertex order whichever side asks:
+ *                N = cross(p[i1] - p[i0], p[i2] - p[i0]);  d2 = dot3(N, N);  ok = d2 > 0 && d2 <= FLT_MAX;  r = 1.0f / sqrtf(d2);
+ *                n = N * r      (componentwise)
+ *              f not ok:  out[f][j] = +0.  Otherwise  acc = +0;  for the entries (g, j') in entry order whose g is ok:
+ *                acc = acc + (1.0f - dot3(n_f, n_g));   out[f][j] = acc
+ *              A face that is not ok is SKIPPED, never multiplied by zero.  The term of the pair (f, g) is the same word from both
+ *              sides: dot3's products commute and its adds keep their order.
+ * A GATHER — the one thread that owns (s, f) stores its three floats once — with plain stores and no atomics: DETERMINISTIC, bit for
+ * bit.  Non-finite positions propagate as IEEE has them, to the faces that name the vertex and to their edge neighbours only.  No
+ * input value makes the pass read or write outside its buffers.  Asynchronous on `stream` (NULL: the ctx's own stream,
+ * SRZ_STREAM_NULL: HIP's null stream), as the other mesh passes are.  A slot with no faces is not an error: nothing is launched.
+ * SRZ_E_INVALID, nothing written and nothing launched, for: everything srz_mesh_normals refuses of ctx, mesh_id, n_sets, d_pos and
+ * pos_stride; an unknown kind; COUNT with n_sets != 1; a null d_out; out_stride below 3; a pointer that is not 4-byte aligned; an
+ * output span (first to last float reached) that overlaps the positions' span (under COUNT too). */
+int srz_mesh_edges(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, int kind, float *d_out,
+                   uint32_t out_stride, void *stream);
+/* THE BACKWARD of srz_mesh_edges to the positions.  d_gout: the gradient with respect to the output, laid out like d_out with
+ * gout_stride >= 3; d_gpos: [n_sets][n_verts][3] packed, EVERY element written (zeros for a slot with no faces); d_work: DIHEDRAL's
+ * workspace [n_sets][n_faces][3] packed, whose contents afterwards are unspecified — LENGTH does not use it, it may be null there.
+ * COUNT has no backward: it is refused.  In float32, nothing fused, all gathers:
+ *   LENGTH, one phase, per set and vertex v:  acc = (+0, +0, +0);  for corner c in list(v), in list order:  f = c / 3;  k = c % 3
+ *     v is the b end of edge j1 = (k + 1) % 3 and the a end of edge j2 = (k + 2) % 3 of f.  For an edge j:  d_j = p[b_j] - p[a_j];
+ *     len_j = sqrtf(dot3(d_j, d_j));  the edge is LIVE when len_j > 0 && len_j <= FLT_MAX;  u_j = d_j * (1.0f / len_j)
+ *     j1 live:  acc = acc + gout[f][j1] * u_j1;    then j2 live:  acc = acc - gout[f][j2] * u_j2        (componentwise)
+ *     An edge that is not live is SKIPPED.   d_gpos[s][v] = acc
+ *   DIHEDRAL, two phases (the second starts when the first has ended), w = gout:
+ *     PHASE 1, per set and face f:  f not ok:  gN[f] = (+0, +0, +0).  Otherwise  H = (+0, +0, +0);  for j = 0, 1, 2, for the entries
+ *       (g, j') of (f, j) in entry order whose g is ok:  s = w[f][j] + w[g][j'];  H = H - n_g * s        (componentwise)
+ *       t = dot3(n_f, H);  gN[f] = (H - n_f * t) * r_f        (componentwise: (H.x - n_f.x * t) * r_f, ...);  d_work[s][f] = gN[f]
+ *     PHASE 2, per set and vertex v:  srz_mesh_normals_grad's phase 2 with G = gN of the corner's own face:  acc = (+0, +0, +0);
+ *       for corner c in list(v), in list order:  (i0, i1, i2) = faces[c / 3];  a, b, c' = p[i0], p[i1], p[i2];  k = c % 3;  G = gN[c / 3]
+ *       k == 0:  acc = acc + cross(b - c', G);   k == 1:  acc = acc + cross(c' - a, G);   k == 2:  acc = acc + cross(G, b - a)
+ *       d_gpos[s][v] = acc
+ * Plain stores, no atomics: DETERMINISTIC, bit for bit.  The gradient is that of the rule as stated wherever the neighbour relation
+ * is mutual (it is between ok faces).  Non-finite values propagate as IEEE has them.  No input value makes the pass read or write
+ * outside its buffers.  Asynchronous on `stream`.
+ * SRZ_E_INVALID, nothing written and nothing launched, for what srz_mesh_edges refuses of ctx, mesh_id, n_sets, d_pos and pos_stride,
+ * and for: a kind that is not LENGTH or DIHEDRAL; a null d_gout or d_gpos; a null d_work under DIHEDRAL; gout_stride below 3; a
+ * pointer that is not 4-byte aligned; d_gpos or (DIHEDRAL) d_work overlapping the positions' or d_gout's span, or each other. */
+int srz_mesh_edges_grad(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, int kind,
+                        const float *d_gout, uint32_t gout_stride, float *d_work, float *d_gpos, void *stream);
 
 /* ---- draw = TraditionalRasterizer::draw(TRIANGLES) for one scene ----------------------
  * z/c0/c1/c2: W*H floats each, in/out (m_zBuffer, m_channels[0..2]); draw never clears unless

@@ -1563,6 +1563,52 @@ int srz_mesh_laplacian_grad(srz_ctx *ctx, int mesh_id, const float *d_gout, uint
                         stream);
 }
 
+// srz_mesh_edges and srz_mesh_edges_grad: check_mesh_normals for the slot and the positions, then the pass's own buffers.  A face
+// field of a slot with no faces reaches over nothing (a null Range overlaps nothing).
+static int mesh_edges(srz_ctx *ctx, const std::string &fn, bool grad, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, int kind,
+                      const float *d_gout, float *d_out, uint32_t stride, float *d_work, float *d_gpos, void *stream) {
+  if (!ctx) return SRZ_E_INVALID;
+  MeshNormalsArgs n{};
+  size_t pos_span = 0;
+  if (int rc = check_mesh_normals(ctx, fn, mesh_id, d_pos, pos_stride, n_sets, n, &pos_span)) return rc;
+  const uint32_t n_faces = ctx->mesh[mesh_id].n_faces;
+  if (kind != SRZ_EDGE_COUNT && kind != SRZ_EDGE_LENGTH && kind != SRZ_EDGE_DIHEDRAL) return fail(ctx, SRZ_E_INVALID, fn + ": unknown kind");
+  if (grad && kind == SRZ_EDGE_COUNT) return fail(ctx, SRZ_E_INVALID, fn + ": SRZ_EDGE_COUNT has no backward");
+  if (kind == SRZ_EDGE_COUNT && n_sets != 1u) return fail(ctx, SRZ_E_INVALID, fn + ": SRZ_EDGE_COUNT reads no positions (n_sets must be 1)");
+  if (grad ? !d_gout || !d_gpos : !d_out) return fail(ctx, SRZ_E_INVALID, fn + (grad ? ": null output gradient / output" : ": null output"));
+  if (grad && kind == SRZ_EDGE_DIHEDRAL && !d_work) return fail(ctx, SRZ_E_INVALID, fn + ": SRZ_EDGE_DIHEDRAL needs a workspace");
+  if (stride < 3u) return fail(ctx, SRZ_E_INVALID, fn + (grad ? ": gout_stride must be at least 3" : ": out_stride must be at least 3"));
+  if (!aligned<4>({d_pos, d_gout, d_out, d_work, d_gpos})) return fail(ctx, SRZ_E_INVALID, fn + ": the buffers must be 4-byte aligned");
+  const size_t field_span = n_faces ? (((size_t)n_sets * n_faces - 1u) * stride + 3u) * sizeof(float) : 0u;
+  const Range pos{n.pos, pos_span}, field{n_faces ? (grad ? (const void *)d_gout : (const void *)d_out) : nullptr, field_span};
+  if (!grad) {
+    if (ranges_overlap(field, pos)) return fail(ctx, SRZ_E_INVALID, fn + ": the output overlaps the positions");
+  } else {
+    const bool dihedral = kind == SRZ_EDGE_DIHEDRAL; // (LENGTH neither reads nor writes d_work)
+    const Range work{dihedral && n_faces ? d_work : nullptr, (size_t)n_sets * n_faces * 3u * sizeof(float)};
+    if (int rc = check_grad_overlap(ctx, fn, {work, {d_gpos, (size_t)n_sets * n.n_verts * 3u * sizeof(float)}}, {pos, field})) return rc;
+  }
+  MeshEdgesArgs a{};
+  a.pos = n.pos, a.pos_stride = n.pos_stride, a.faces = n.faces, a.corner_off = n.corner_off, a.corners = n.corners;
+  a.out = d_out, a.out_stride = stride, a.gout = d_gout, a.gout_stride = stride, a.work = d_work, a.gpos = d_gpos;
+  a.n_verts = n.n_verts, a.n_faces = n_faces, a.n_sets = n_sets;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (grad) launch_mesh_edges_grad(a, kind, pick_stream(ctx, stream));
+  else launch_mesh_edges(a, kind, pick_stream(ctx, stream));
+  HIP_TRY(ctx, hipGetLastError());
+  return SRZ_OK;
+}
+
+int srz_mesh_edges(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, int kind, float *d_out,
+                   uint32_t out_stride, void *stream) {
+  return mesh_edges(ctx, "srz_mesh_edges", false, mesh_id, d_pos, pos_stride, n_sets, kind, nullptr, d_out, out_stride, nullptr, nullptr, stream);
+}
+
+int srz_mesh_edges_grad(srz_ctx *ctx, int mesh_id, const float *d_pos, uint32_t pos_stride, uint32_t n_sets, int kind,
+                        const float *d_gout, uint32_t gout_stride, float *d_work, float *d_gpos, void *stream) {
+  return mesh_edges(ctx, "srz_mesh_edges_grad", true, mesh_id, d_pos, pos_stride, n_sets, kind, d_gout, nullptr, gout_stride, d_work, d_gpos, stream);
+}
+
 // A sceneset's frames as srz_frames whose batches carry sizes only (k_vertex makes the triangles): fr[f], its batches in `batches`.
 // Every draw names an uploaded mesh (the callers have checked).
 static void scene_frames(const srz_ctx *ctx, const srz_scene_frame *frames, int n_frames, std::vector<srz_frame> &fr, std::vector<srz_batch> &batches) {

@@ -279,6 +279,25 @@ struct MeshLaplacianArgs {
   uint32_t n_verts, n_sets;
 };
 void launch_mesh_laplacian(const MeshLaplacianArgs &a, int kind, bool transpose, hipStream_t s);
+// srz_mesh_edges / srz_mesh_edges_grad: the per-(face, edge) terms of ONE mesh slot over n_sets position sets (k_mesh_edges: a
+// thread owns (set, face) and finds the faces across each edge in the shorter corner list of the edge's two ends) and their backward
+// to the positions (k_mesh_edges_grad: LENGTH one launch over the vertices; DIHEDRAL two, gN per face into `work`, then the gather
+// over each vertex's corner list).  Vertex v of set s starts at float (s * n_verts + v) * pos_stride; face f of set s at float
+// (s * n_faces + f) * stride of out / gout; work is packed [n_sets][n_faces][3], gpos [n_sets][n_verts][3].  The host has checked
+// the kind, the strides, the spans and n_sets <= 65535 (the grid's y)
+struct MeshEdgesArgs {
+  const float *pos;            // the slot's own records (stride 8) or the caller's sets
+  const uint32_t *faces;       // [n_faces][3]
+  const uint32_t *corner_off;  // [n_verts + 1] into corners
+  const uint32_t *corners;     // [3 * n_faces]: 3 * face + k of every corner that names the vertex, increasing
+  float *out;                  // forward: the output
+  const float *gout;           // backward: the gradient of the output
+  float *work, *gpos;          // backward: gN (DIHEDRAL's phase 1 writes, phase 2 reads), the output
+  uint32_t pos_stride, out_stride, gout_stride;
+  uint32_t n_verts, n_faces, n_sets;
+};
+void launch_mesh_edges(const MeshEdgesArgs &a, int kind, hipStream_t s);
+void launch_mesh_edges_grad(const MeshEdgesArgs &a, int kind, hipStream_t s);
 // srz_sceneset_corner_attr / _corner_attr_grad: per-vertex attributes of ONE mesh slot to the set's triangle stream
 // [frame][pos_tris][3][n_ch], and the stream's gradient back to [frame][n_verts][n_ch] (k_corner_attr, k_corner_attr_grad: a thread
 // owns (frame, vertex, channel) and walks the frame's draws of the slot and the vertex's corner list).  A draw takes part when its

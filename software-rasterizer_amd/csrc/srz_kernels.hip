@@ -890,6 +890,148 @@ template <int MODE> __global__ __launch_bounds__(256) void k_mesh_laplacian(cons
 }
 
 // ================================================================================================================
+// k_mesh_edges / k_mesh_edges_grad — srz_mesh_edges and its backward (include/srz.h states the rules): k_mesh_normals' shape, over
+// FACES — grid (blocks of 256 faces, position sets), a thread OWNS (set, face) and stores its three floats once — and, for the
+// backward's gathers, over vertices.  No atomics, no barrier, no LDS, plain stores, bit-reproducible.  The slot holds no edge table:
+// the faces across edge (a, b) of f are found in the corner list of whichever end has the SHORTER list (a hub vertex of thousands of
+// faces costs its spokes' other ends a walk of their own few corners, not of the hub's list).  corner_off, corners and faces are
+// indexed per lane (nothing is wave-uniform: vector loads, as k_mesh_laplacian has them).  MODE of the backward: 0 LENGTH (per
+// vertex), 1 DIHEDRAL's phase 1 (per face: gN into `work`), 2 DIHEDRAL's phase 2 (per vertex: srz_mesh_normals_grad's gather with
+// G = gN of the corner's own face).
+// ================================================================================================================
+// the unit normal of face (i0, i1, i2) of position set p, in the face's own order; r = 1 / |N|.  false: the face is not ok
+__device__ __forceinline__ bool edge_unit_normal(const float *p, uint32_t stride, uint32_t i0, uint32_t i1, uint32_t i2, F3 &n, float &r) {
+  const F3 p0 = ldv3(p + (size_t)i0 * stride);
+  const F3 N = cross3(sub3(ldv3(p + (size_t)i1 * stride), p0), sub3(ldv3(p + (size_t)i2 * stride), p0));
+  const float d2 = dot3(N.x, N.y, N.z, N.x, N.y, N.z);
+  const bool ok = d2 > 0.0f && d2 <= __FLT_MAX__;
+  r = ok ? 1.0f / __builtin_sqrtf(d2) : 0.0f;
+  n = F3{N.x * r, N.y * r, N.z * r};
+  return ok;
+}
+// THE NEIGHBOURS of edge (va, vb) of face f: visit(g, j', g0, g1, g2) per entry, in entry order (g's three vertices come along)
+template <class Visit> __device__ __forceinline__ void edge_neighbours(const MeshEdgesArgs &a, uint32_t f, uint32_t va, uint32_t vb, Visit visit) {
+  const uint32_t a0 = a.corner_off[va], a1 = a.corner_off[va + 1], b0 = a.corner_off[vb], b1 = a.corner_off[vb + 1];
+  const bool walk_b = b1 - b0 < a1 - a0;
+  const uint32_t o = walk_b ? va : vb, end = walk_b ? b1 : a1;
+  for (uint32_t c = walk_b ? b0 : a0; c < end; ++c) {
+    const uint32_t corner = a.corners[c], g = corner / 3u, k = corner - 3u * g;
+    if (g == f) continue;
+    const uint32_t *gf = a.faces + (size_t)g * 3;
+    const uint32_t g0 = gf[0], g1 = gf[1], g2 = gf[2];
+    const uint32_t next = k == 0u ? g1 : k == 1u ? g2 : g0, prev = k == 0u ? g2 : k == 1u ? g0 : g1;
+    if (next == o) visit(g, k == 0u ? 2u : k - 1u, g0, g1, g2);      // the edge opposite the remaining corner (k + 2) % 3
+    else if (prev == o) visit(g, k == 2u ? 0u : k + 1u, g0, g1, g2); // ... (k + 1) % 3
+  }
+}
+template <int KIND> __global__ __launch_bounds__(256) void k_mesh_edges(const MeshEdgesArgs a) {
+  const uint32_t f = blockIdx.x * 256 + threadIdx.x, set = blockIdx.y;
+  if (f >= a.n_faces) return;
+  const float *p = a.pos + (size_t)set * a.n_verts * a.pos_stride;
+  const uint32_t *fi = a.faces + (size_t)f * 3;
+  const uint32_t i0 = fi[0], i1 = fi[1], i2 = fi[2];
+  float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
+  if (KIND == SRZ_EDGE_LENGTH) {
+    const F3 P0 = ldv3(p + (size_t)i0 * a.pos_stride), P1 = ldv3(p + (size_t)i1 * a.pos_stride), P2 = ldv3(p + (size_t)i2 * a.pos_stride);
+    const F3 d0 = sub3(P2, P1), d1 = sub3(P0, P2), d2 = sub3(P1, P0); // d_j = p[b_j] - p[a_j]
+    r0 = __builtin_sqrtf(dot3(d0.x, d0.y, d0.z, d0.x, d0.y, d0.z));
+    r1 = __builtin_sqrtf(dot3(d1.x, d1.y, d1.z, d1.x, d1.y, d1.z));
+    r2 = __builtin_sqrtf(dot3(d2.x, d2.y, d2.z, d2.x, d2.y, d2.z));
+  } else {
+    F3 nf{0.0f, 0.0f, 0.0f};
+    float rf;
+    if (KIND == SRZ_EDGE_COUNT || edge_unit_normal(p, a.pos_stride, i0, i1, i2, nf, rf)) {
+#pragma unroll
+      for (uint32_t j = 0; j < 3u; ++j) {
+        const uint32_t va = j == 0u ? i1 : j == 1u ? i2 : i0, vb = j == 0u ? i2 : j == 1u ? i0 : i1;
+        uint32_t count = 1u;
+        float acc = 0.0f;
+        edge_neighbours(a, f, va, vb, [&](uint32_t, uint32_t, uint32_t g0, uint32_t g1, uint32_t g2) {
+          if (KIND == SRZ_EDGE_COUNT) {
+            ++count;
+          } else {
+            F3 ng;
+            float rg;
+            if (edge_unit_normal(p, a.pos_stride, g0, g1, g2, ng, rg)) acc = acc + (1.0f - dot3(nf.x, nf.y, nf.z, ng.x, ng.y, ng.z));
+          }
+        });
+        const float r = KIND == SRZ_EDGE_COUNT ? (float)count : acc;
+        if (j == 0u) r0 = r;
+        else if (j == 1u) r1 = r;
+        else r2 = r;
+      }
+    }
+  }
+  float *o = a.out + ((size_t)set * a.n_faces + f) * a.out_stride;
+  o[0] = r0, o[1] = r1, o[2] = r2;
+}
+template <int MODE> __global__ __launch_bounds__(256) void k_mesh_edges_grad(const MeshEdgesArgs a) {
+  const uint32_t id = blockIdx.x * 256 + threadIdx.x, set = blockIdx.y;
+  if (id >= (MODE == 1 ? a.n_faces : a.n_verts)) return;
+  const float *p = a.pos + (size_t)set * a.n_verts * a.pos_stride;
+  const float *gout = a.gout + (size_t)set * a.n_faces * a.gout_stride;
+  if (MODE == 1) {
+    const uint32_t f = id;
+    const uint32_t *fi = a.faces + (size_t)f * 3;
+    const uint32_t i0 = fi[0], i1 = fi[1], i2 = fi[2];
+    F3 nf, gN{0.0f, 0.0f, 0.0f};
+    float rf;
+    if (edge_unit_normal(p, a.pos_stride, i0, i1, i2, nf, rf)) {
+      F3 H{0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (uint32_t j = 0; j < 3u; ++j) {
+        const uint32_t va = j == 0u ? i1 : j == 1u ? i2 : i0, vb = j == 0u ? i2 : j == 1u ? i0 : i1;
+        const float w_fj = gout[(size_t)f * a.gout_stride + j];
+        edge_neighbours(a, f, va, vb, [&](uint32_t g, uint32_t jp, uint32_t g0, uint32_t g1, uint32_t g2) {
+          F3 ng;
+          float rg;
+          if (!edge_unit_normal(p, a.pos_stride, g0, g1, g2, ng, rg)) return;
+          const float s = w_fj + gout[(size_t)g * a.gout_stride + jp];
+          H = F3{H.x - ng.x * s, H.y - ng.y * s, H.z - ng.z * s};
+        });
+      }
+      const float t = dot3(nf.x, nf.y, nf.z, H.x, H.y, H.z);
+      gN = F3{(H.x - nf.x * t) * rf, (H.y - nf.y * t) * rf, (H.z - nf.z * t) * rf};
+    }
+    float *w = a.work + ((size_t)set * a.n_faces + f) * 3;
+    w[0] = gN.x, w[1] = gN.y, w[2] = gN.z;
+  } else {
+    const uint32_t v = id;
+    const float *gn = MODE == 2 ? a.work + (size_t)set * a.n_faces * 3 : nullptr; // (LENGTH has no workspace)
+    F3 acc{0.0f, 0.0f, 0.0f};
+    for (uint32_t c = a.corner_off[v], c_end = a.corner_off[v + 1]; c < c_end; ++c) {
+      const uint32_t corner = a.corners[c], face = corner / 3u, k = corner - 3u * face;
+      const uint32_t *fi = a.faces + (size_t)face * 3;
+      const uint32_t i0 = fi[0], i1 = fi[1], i2 = fi[2];
+      const F3 A = ldv3(p + (size_t)i0 * a.pos_stride), B = ldv3(p + (size_t)i1 * a.pos_stride), C = ldv3(p + (size_t)i2 * a.pos_stride);
+      if (MODE == 0) {
+        // v is corner k: the b end of edge j1 = (k + 1) % 3 (from the previous corner) and the a end of j2 = (k + 2) % 3 (to the next)
+        const F3 Pk = k == 0u ? A : k == 1u ? B : C, Pn = k == 0u ? B : k == 1u ? C : A, Pp = k == 0u ? C : k == 1u ? A : B;
+        const uint32_t j1 = k == 2u ? 0u : k + 1u, j2 = k == 0u ? 2u : k - 1u;
+        const float *g = gout + (size_t)face * a.gout_stride;
+        const F3 d1 = sub3(Pk, Pp), d2 = sub3(Pn, Pk);
+        const float len1 = __builtin_sqrtf(dot3(d1.x, d1.y, d1.z, d1.x, d1.y, d1.z));
+        if (len1 > 0.0f && len1 <= __FLT_MAX__) {
+          const float inv = 1.0f / len1, g1 = g[j1];
+          acc = F3{acc.x + g1 * (d1.x * inv), acc.y + g1 * (d1.y * inv), acc.z + g1 * (d1.z * inv)};
+        }
+        const float len2 = __builtin_sqrtf(dot3(d2.x, d2.y, d2.z, d2.x, d2.y, d2.z));
+        if (len2 > 0.0f && len2 <= __FLT_MAX__) {
+          const float inv = 1.0f / len2, g2 = g[j2];
+          acc = F3{acc.x - g2 * (d2.x * inv), acc.y - g2 * (d2.y * inv), acc.z - g2 * (d2.z * inv)};
+        }
+      } else {
+        const F3 G = ldv3(gn + (size_t)face * 3);
+        const F3 term = k == 0u ? cross3(sub3(B, C), G) : k == 1u ? cross3(sub3(C, A), G) : cross3(G, sub3(B, A));
+        acc = add3(acc, term);
+      }
+    }
+    float *g = a.gpos + ((size_t)set * a.n_verts + v) * 3;
+    g[0] = acc.x, g[1] = acc.y, g[2] = acc.z;
+  }
+}
+
+// ================================================================================================================
 // k_corner_attr / k_corner_attr_grad — srz_sceneset_corner_attr and its backward (include/srz.h).  Grid (blocks of 256 (vertex,
 // channel) pairs, frames); a thread OWNS (frame, vertex, channel): neighbouring lanes are neighbouring channels of one vertex, so
 // the attribute row, the rows of the triangle stream and the gradient row are each read and written as runs, and the backward
@@ -8950,6 +9092,26 @@ void launch_mesh_laplacian(const MeshLaplacianArgs &a, int kind, bool transpose,
   else if (kind == SRZ_LAP_GRAPH) hipLaunchKernelGGL(k_mesh_laplacian<SRZ_LAP_GRAPH>, grid, dim3(256), 0, s, a);
   else if (transpose) hipLaunchKernelGGL(k_mesh_laplacian<LAP_UMBRELLA_T>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(k_mesh_laplacian<SRZ_LAP_UMBRELLA>, grid, dim3(256), 0, s, a);
+}
+
+void launch_mesh_edges(const MeshEdgesArgs &a, int kind, hipStream_t s) {
+  if (a.n_faces == 0u) return;
+  const dim3 grid((a.n_faces + 255) / 256, a.n_sets);
+  if (kind == SRZ_EDGE_COUNT) hipLaunchKernelGGL(k_mesh_edges<SRZ_EDGE_COUNT>, grid, dim3(256), 0, s, a);
+  else if (kind == SRZ_EDGE_LENGTH) hipLaunchKernelGGL(k_mesh_edges<SRZ_EDGE_LENGTH>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_mesh_edges<SRZ_EDGE_DIHEDRAL>, grid, dim3(256), 0, s, a);
+}
+
+void launch_mesh_edges_grad(const MeshEdgesArgs &a, int kind, hipStream_t s) {
+  if (a.n_verts == 0u) return;
+  const dim3 verts((a.n_verts + 255) / 256, a.n_sets), faces((a.n_faces + 255) / 256, a.n_sets);
+  if (kind == SRZ_EDGE_LENGTH) {
+    hipLaunchKernelGGL(k_mesh_edges_grad<0>, verts, dim3(256), 0, s, a);
+    return;
+  }
+  // (a slot with no faces: every corner list is empty, phase 2 alone writes the zeros)
+  if (a.n_faces != 0u) hipLaunchKernelGGL(k_mesh_edges_grad<1>, faces, dim3(256), 0, s, a); // (stream order, as launch_mesh_normals_grad)
+  hipLaunchKernelGGL(k_mesh_edges_grad<2>, verts, dim3(256), 0, s, a);
 }
 
 void launch_mesh_tangents_grad(const MeshTangentsArgs &a, hipStream_t s) {

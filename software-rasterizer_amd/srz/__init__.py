@@ -44,6 +44,7 @@ EXPORTS = ["srz_abi_version", "srz_create", "srz_destroy", "srz_last_error", "sr
            "srz_frameset_shadow", "srz_frameset_shadow_grad",
            "srz_mesh_tangents", "srz_mesh_tangents_grad", "srz_frameset_normal_map", "srz_frameset_normal_map_grad",
            "srz_mesh_laplacian", "srz_mesh_laplacian_grad",
+           "srz_mesh_edges", "srz_mesh_edges_grad",
            "srz_frameset_composite", "srz_frameset_composite_grad",
            "srz_frameset_texture_set", "srz_frameset_texture_set_grad",
            "srz_frameset_perspective", "srz_frameset_perspective_grad", "srz_frameset_interpolate_deriv_persp",
@@ -168,6 +169,8 @@ def lib():
         L.srz_mesh_tangents.argtypes = abi.MESH_TANGENTS_ARGTYPES
         L.srz_mesh_tangents_grad.argtypes = abi.MESH_TANGENTS_GRAD_ARGTYPES
         L.srz_mesh_laplacian.argtypes = L.srz_mesh_laplacian_grad.argtypes = abi.MESH_LAPLACIAN_ARGTYPES
+        L.srz_mesh_edges.argtypes = abi.MESH_EDGES_ARGTYPES
+        L.srz_mesh_edges_grad.argtypes = abi.MESH_EDGES_GRAD_ARGTYPES
         L.srz_frameset_normal_map.argtypes = abi.NORMAL_MAP_ARGTYPES
         L.srz_frameset_normal_map_grad.argtypes = abi.NORMAL_MAP_GRAD_ARGTYPES
         L.srz_frameset_composite.argtypes = abi.COMPOSITE_ARGTYPES
@@ -1117,6 +1120,23 @@ class Context:
         self._check(lib().srz_mesh_laplacian_grad(self.h, mesh_id, C.c_void_p(d_gout_ptr or None), gout_stride, n_ch, n_sets, kind,
                                                   C.c_void_p(d_wpos_ptr or None), wpos_stride, C.c_void_p(d_gx_ptr or None), gx_stride,
                                                   _stream(stream)))
+
+    def mesh_edges(self, mesh_id, d_pos_ptr, pos_stride, n_sets, kind, d_out_ptr, out_stride, stream=None):
+        """the per-(face, edge) terms (kind: abi.EDGE_COUNT / EDGE_LENGTH / EDGE_DIHEDRAL) of slot mesh_id over n_sets position sets
+        on the device: for set s and face f three floats at float (s * n_faces + f) * out_stride of d_out (out_stride >= 3), edge j
+        opposite corner j.  d_pos_ptr None / 0: the slot's own positions (n_sets 1).  COUNT: the number of faces on the edge
+        (n_sets 1); LENGTH: the edge's length; DIHEDRAL: the sum over the faces across the edge of 1 - cos of the unit normals.  The
+        adjacency is found from the slot's corner lists; a gather, deterministic (include/srz.h states the rules).  Asynchronous."""
+        self._check(lib().srz_mesh_edges(self.h, mesh_id, C.c_void_p(d_pos_ptr or None), pos_stride, n_sets, kind, C.c_void_p(d_out_ptr or None),
+                                         out_stride, _stream(stream)))
+
+    def mesh_edges_grad(self, mesh_id, d_pos_ptr, pos_stride, n_sets, kind, d_gout_ptr, gout_stride, d_work_ptr, d_gpos_ptr, stream=None):
+        """the backward of mesh_edges (LENGTH or DIHEDRAL; COUNT has none) to the positions: d_gout (laid out like the output) →
+        d_gpos [n_sets][n_verts][3], every element written.  d_work: DIHEDRAL's workspace [n_sets][n_faces][3]; LENGTH takes None /
+        0.  Gathers without atomics, deterministic.  Asynchronous."""
+        self._check(lib().srz_mesh_edges_grad(self.h, mesh_id, C.c_void_p(d_pos_ptr or None), pos_stride, n_sets, kind,
+                                              C.c_void_p(d_gout_ptr or None), gout_stride, C.c_void_p(d_work_ptr or None),
+                                              C.c_void_p(d_gpos_ptr or None), _stream(stream)))
 
     def draw(self, frame, planes=None, primitive=abi.PRIMITIVE_TRIANGLES, want_stats=False):
         """TraditionalRasterizer::draw for one scene; planes (z,c0,c1,c2) are modified in place."""

@@ -83,6 +83,10 @@ NORMAL_MAP_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u
 LAP_UMBRELLA, LAP_GRAPH, LAP_COTAN = 0, 1, 2
 LAP_MAX_CH = 64
 MESH_LAPLACIAN_ARGTYPES = [_vp, C.c_int, _vp, _u32, _u32, _u32, C.c_int, _vp, _u32, _vp, _u32, _vp]
+# srz_mesh_edges / _edges_grad: `kind` (SRZ_EDGE_*) and the two prototypes
+EDGE_COUNT, EDGE_LENGTH, EDGE_DIHEDRAL = 0, 1, 2
+MESH_EDGES_ARGTYPES = [_vp, C.c_int, _vp, _u32, _u32, C.c_int, _vp, _u32, _vp]
+MESH_EDGES_GRAD_ARGTYPES = [_vp, C.c_int, _vp, _u32, _u32, C.c_int, _vp, _u32, _vp, _vp, _vp]
 # the prototypes of srz_frameset_shadow / _shadow_grad (argtypes; both return int), set by srz.lib()
 SHADOW_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, C.c_float, C.c_float, _vp, C.c_size_t, _u32, _vp]
 SHADOW_GRAD_ARGTYPES = [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, C.c_float, C.c_float, _vp, _vp, _u32, _vp]

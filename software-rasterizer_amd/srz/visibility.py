@@ -2099,6 +2099,83 @@ def mesh_solve(ctx, slot, b, lam, kind="graph", wpos=None, iters=64, tol=None, s
     return _MeshSolve.apply(b, ctx, slot, lam, kind, wpos, iters, tol, stream)
 
 
+def _face_field(ctx, slot, sets):
+    """an uninitialised CUDA float32 tensor sets + [F, 3] for mesh slot `slot` (never without an address: a slot with no faces is not
+    an error, a null output is)"""
+    F = ctx.mesh_sizes[slot][1]
+    return torch.empty(tuple(sets) + (max(F, 1), 3), dtype=torch.float32, device="cuda")[..., :F, :]
+
+
+def mesh_edge_counts(ctx, slot, stream=None):
+    """the number of faces on every edge of mesh slot `slot` of Context `ctx` → a CUDA float32 tensor [F, 3], edge j of a face opposite
+    its corner j: 1 a boundary edge, 2 a manifold edge, more a non-manifold one (Context.mesh_edges with abi.EDGE_COUNT; the
+    adjacency is found from the slot's corner lists, include/srz.h states the rule).  It reads no positions and carries no gradient:
+    the weight 1 / count that makes every undirected edge count once, and the boundary's mark.  stream: a raw stream handle, None =
+    torch's current stream."""
+    out = _face_field(ctx, slot, ())
+    ctx.mesh_edges(slot, None, 8, 1, abi.EDGE_COUNT, out.data_ptr(), 3, _stream_ptr(stream))
+    return out
+
+
+class _MeshEdges(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, sctx, slot, kind, who, stream):
+        p, n_sets = _sets_arg(sctx, slot, pos, "pos", who)
+        out = _face_field(sctx, slot, p.shape[:-2])
+        sctx.mesh_edges(slot, p.data_ptr(), 3, n_sets, kind, out.data_ptr(), 3, _stream_ptr(stream))
+        ctx.sctx, ctx.slot, ctx.kind, ctx.stream, ctx.n_sets = sctx, slot, kind, stream, n_sets
+        ctx.save_for_backward(p)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        (p,) = ctx.saved_tensors
+        gout = gout.contiguous()
+        work = torch.empty_like(gout) if ctx.kind == abi.EDGE_DIHEDRAL else None
+        gpos = torch.empty_like(p)
+        ctx.sctx.mesh_edges_grad(ctx.slot, p.data_ptr(), 3, ctx.n_sets, ctx.kind, gout.data_ptr(), 3, _ptr(work), gpos.data_ptr(),
+                                 _stream_ptr(ctx.stream))
+        return gpos, None, None, None, None, None
+
+
+def mesh_edge_lengths(ctx, slot, pos, stream=None):
+    """the edge lengths of mesh slot `slot` of Context `ctx` at vertex positions pos, a CUDA float32 tensor [V, 3] or [B, V, 3] → [F, 3]
+    or [B, F, 3]: edge j of a face (i0, i1, i2) lies opposite corner j and joins i[(j + 1) % 3] and i[(j + 2) % 3]
+    (Context.mesh_edges with abi.EDGE_LENGTH, include/srz.h states the rule).  An interior edge appears once per face on it:
+    weight by 1 / mesh_edge_counts to count every undirected edge once (mesh_edge_loss does).  Differentiable with respect to pos
+    (Context.mesh_edges_grad; an edge of zero length passes no gradient on).  Both directions are gathers without atomics: the
+    values and pos.grad are bit-reproducible.  stream: a raw stream handle, None = torch's current stream."""
+    return _MeshEdges.apply(pos, ctx, slot, abi.EDGE_LENGTH, "mesh_edge_lengths", stream)
+
+
+def mesh_normal_consistency(ctx, slot, pos, stream=None):
+    """the normal consistency of mesh slot `slot` of Context `ctx` at vertex positions pos, a CUDA float32 tensor [V, 3] or [B, V, 3] →
+    [F, 3] or [B, F, 3]: per face and edge the sum, over the faces across the edge, of 1 - cos of the two unit face normals — 0 flat, 2
+    folded back or wound against each other, +0 on a boundary edge and on a face of zero area, which is skipped, never multiplied by
+    zero (Context.mesh_edges with abi.EDGE_DIHEDRAL; the faces across an edge are found from the slot's corner lists, include/srz.h
+    states the rule).  A pair of faces appears at both: the sum over the result counts it twice (mesh_normal_loss takes the mean).
+    Differentiable with respect to pos (Context.mesh_edges_grad).  Both directions are gathers without atomics: the values and
+    pos.grad are bit-reproducible.  stream: a raw stream handle, None = torch's current stream."""
+    return _MeshEdges.apply(pos, ctx, slot, abi.EDGE_DIHEDRAL, "mesh_normal_consistency", stream)
+
+
+def mesh_edge_loss(ctx, slot, pos, target=0.0, stream=None):
+    """the mean over the UNDIRECTED edges of mesh slot `slot` of (length - target)^2, a scalar (per set of a [B, V, 3] pos: [B]): plain
+    torch ops over mesh_edge_lengths weighted by 1 / mesh_edge_counts, so that an edge counts once however many faces share it.
+    Keeps triangles from collapsing or stretching; differentiable with respect to pos."""
+    w = 1.0 / mesh_edge_counts(ctx, slot, stream)
+    d = mesh_edge_lengths(ctx, slot, pos, stream) - target
+    return (w * d * d).sum((-2, -1)) / w.sum().clamp(min=1.0)
+
+
+def mesh_normal_loss(ctx, slot, pos, stream=None):
+    """the mean over the adjacent face pairs of mesh slot `slot` of 1 - cos of their normals, a scalar (per set of a [B, V, 3] pos:
+    [B]): plain torch ops over mesh_normal_consistency — its sum counts every pair at both faces, and so does the divisor, the sum
+    of mesh_edge_counts - 1.  Keeps a surface from creasing; differentiable with respect to pos."""
+    pairs = (mesh_edge_counts(ctx, slot, stream) - 1.0).sum()
+    return mesh_normal_consistency(ctx, slot, pos, stream).sum((-2, -1)) / pairs.clamp(min=1.0)
+
+
 def refresh_normals(ctx, slot, stream=None):
     """the nrm fields of mesh slot `slot` recomputed IN PLACE from the positions the slot holds (Context.mesh_normals with both
     pointers null): the call that follows mesh_update on the same stream, so that shade_visibility, gbuffer(NORMAL) and the colour
